@@ -102,7 +102,16 @@ def parse_args():
                          "quote the stored profiles/rNN_pmc_kernels.json figure instead")
     ap.add_argument("--traffic-bytes", type=float, default=None,
                     help="HBM bytes per launch from a separate rocprofv3 --pmc pass (profiles/), if known")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (device 0's Q=1 scan: one float32 distance "
+                         "per item) to DIR/distances.npy, at most 64 MB (a fixed, seeded sample of a larger scan, its item ids in "
+                         "DIR/distances_ids.npy); the inputs are fixed by the seed, so two builds can be compared output for output")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1 (the timed region is --steps launches of the scan)")
+    if args.dump_outputs and args.dry_run:
+        ap.error("--dump-outputs with --dry-run: a dry run computes no outputs")
+    return args
 
 
 def scan_source_hash():
@@ -817,6 +826,23 @@ class ThreadSync:
         pass
 
 
+DUMP_MAX_BYTES = 60_000_000  # --dump-outputs writes an output up to this size whole: every file it writes stays under 64 MB
+DUMP_SAMPLE = 4_000_000  # entries kept of a larger output: 16 MB of float32 values + 32 MB of float64 ids
+
+
+def dump_output(out_dir, name, a):
+    """--dump-outputs: `a` (float32, as computed) as out_dir/<name>.npy.  An output larger than DUMP_MAX_BYTES is replaced by
+    a fixed sample of DUMP_SAMPLE entries (seeded, ascending, the same in every run) whose indices go to <name>_ids.npy as
+    float64 (exact below 2**53)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    if a.nbytes > DUMP_MAX_BYTES:
+        ids = np.sort(np.random.default_rng(SEED).choice(a.size, size=DUMP_SAMPLE, replace=False))
+        np.save(os.path.join(out_dir, f"{name}_ids.npy"), ids.astype(np.float64))
+        a = a[ids]
+    np.save(os.path.join(out_dir, f"{name}.npy"), a)
+
+
 def device_work(args, rank, world, device, sync, ds_1m, result):
     """Everything one device measures.  `ds_1m`: this device's replica of the configs[1] dataset (threads mode) or None
     (the rank fills its own)."""
@@ -840,6 +866,11 @@ def device_work(args, rank, world, device, sync, ds_1m, result):
     sync.barrier(rank)
     result["elapsed"] = sync.max(time.perf_counter() - t0, rank)
     result["kernel_ms"] = sync.max(kernel_ms_total / args.steps, rank)
+    if rank == 0 and args.dump_outputs:
+        # the last timed step once more, outside the timed region: the same kernel on the same resident rows and query writes
+        # the same distances bit for bit (reading them back inside the timed call would put a copy of n floats in ms_per_step)
+        _ms, out = ds.bench_scan(query_item, n, 1, want_out=True)
+        dump_output(args.dump_outputs, "distances", out)
     if rank == 0:
         result["device"] = arroy_amd.device_name(device)
         # measured streaming ceilings of this device, next to the spec peak

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Regenerate tests/golden/*.json from the reference's own test assets and test sources.
+"""Regenerate tests/golden/*.json from the reference's own test assets and test sources (and, for
+integration_patch_lines.json, line hashes of the reference files arroy-hip.patch touches).
 
 Run in the build container only (needs /root/reference):  python tests/golden/make_golden.py
 
@@ -144,6 +145,46 @@ def inline_snapshots(src):
     return out
 
 
+def patch_lines():
+    """integration_patch_lines.json: for each reference file integration/arroy-hip/arroy-hip.patch touches, its line count
+    and the sha256 of every line the patch (context and removed lines) or an anchor of make_patch.py records — lines
+    already in the repository verbatim.  tests/test_integration_patch.py checks the recorded lines against it."""
+    import hashlib
+    import importlib.util
+    import re
+    patch_dir = os.path.join(HERE, "..", "..", "integration", "arroy-hip")
+    spec = importlib.util.spec_from_file_location("make_patch", os.path.join(patch_dir, "make_patch.py"))
+    make_patch = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(make_patch)
+    recorded, rel, n = {}, None, 0
+    for line in open(os.path.join(patch_dir, "arroy-hip.patch")).read().splitlines():
+        if line.startswith("--- a/"):
+            continue
+        if line.startswith("+++ b/"):
+            rel = line[6:]
+            continue
+        m = re.match(r"@@ -(\d+)", line)
+        if m:
+            n = int(m.group(1))
+        elif line[:1] in (" ", "-"):
+            recorded.setdefault(rel, set()).add(n)
+            n += 1
+    out = {"_source": "generated by tests/golden/make_golden.py from the reference files arroy-hip.patch touches",
+           "files": {}}
+    for rel, edits in make_patch.EDITS.items():
+        text = open(os.path.join(REF, rel)).read()
+        lines = text.splitlines()
+        for before, _after in edits:
+            assert text.count(before) == 1, rel
+            first = text.count("\n", 0, text.index(before)) + 1
+            recorded[rel].update(range(first, first + len(before.splitlines())))
+        out["files"][rel] = {"lines": len(lines), "sha256": {
+            str(k): hashlib.sha256(lines[k - 1].encode()).hexdigest() for k in sorted(recorded[rel])}}
+    with open(os.path.join(HERE, "integration_patch_lines.json"), "w") as f:
+        json.dump(out, f, indent=1)
+    print("wrote", os.path.join(HERE, "integration_patch_lines.json"), sum(len(v["sha256"]) for v in out["files"].values()))
+
+
 def main():
     if not os.path.isdir(REF):
         sys.exit("reference not mounted; fixtures are committed, nothing to do")
@@ -250,6 +291,7 @@ def main():
     with open(os.path.join(HERE, "reference_golden.json"), "w") as f:
         json.dump(golden, f, indent=1)
     print("wrote", os.path.join(HERE, "reference_golden.json"), len(v1), len(a1))
+    patch_lines()
 
 
 if __name__ == "__main__":

@@ -1,9 +1,13 @@
 """integration/arroy-hip: the Rust side of the drop-in as FILES (review item 9).  It cannot be compiled in this image (no
 cargo / rustc), but it can be kept applicable and in sync with the C header: the patch must `git apply --check` against
-the reference, be exactly what its generator produces, and `src/hip.rs` must bind only symbols the header declares, with
-struct fields in the header's order."""
+the reference (arroy v0.7.0, pinned line by line by tests/golden/integration_patch_lines.json), be what its generator
+produces, and `src/hip.rs` must bind only symbols the header declares, with struct fields in the header's order."""
+import hashlib
+import importlib.util
+import json
 import os
 import re
+import shutil
 import subprocess
 import sys
 
@@ -11,8 +15,8 @@ import pytest
 
 from conftest import ROOT
 
-REF = "/root/reference"
 HERE = os.path.join(ROOT, "integration", "arroy-hip")
+TOUCHED = {"Cargo.toml", "src/lib.rs", "src/parallel.rs", "src/writer.rs", "src/reader.rs", "src/distance/dot_product.rs"}
 
 
 def header():
@@ -23,15 +27,91 @@ def rust():
     return open(os.path.join(HERE, "src", "hip.rs")).read()
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "src")), reason="the reference checkout is not on this machine")
-def test_patch_applies_to_the_reference_and_matches_its_generator():
+def patch_hunks(text):
+    """{file: [(first line of the old side, [hunk lines]), ...]} of a unified diff."""
+    files, cur = {}, None
+    for line in text.splitlines(keepends=True):
+        if line.startswith("--- a/"):
+            continue
+        if line.startswith("+++ b/"):
+            cur = files.setdefault(line[6:].rstrip("\n"), [])
+            continue
+        m = re.match(r"@@ -(\d+)(?:,\d+)? \+\d+(?:,\d+)? @@", line)
+        if m:
+            cur.append((int(m.group(1)), []))
+        else:
+            cur[-1][1].append(line)
+    return files
+
+
+def recorded_lines(rel, hunks, edits):
+    """{line number: line} of the reference file `rel` as far as the patch (context and removed lines, at their line
+    numbers) and the generator's anchors record it.  An anchor goes where it agrees with the most recorded lines, and must
+    agree with them everywhere."""
+    known = {}
+    for start, lines in hunks:
+        n = start
+        for l in lines:
+            if l[0] in " -":
+                known[n] = l[1:]
+                n += 1
+    for before, _after in edits:
+        bl = before.splitlines(keepends=True)
+        fits = {}
+        for o in range(min(known) - len(bl), max(known) + 1):
+            got = [known.get(o + i) for i in range(len(bl))]
+            if all(g is None or g == t for g, t in zip(got, bl)):
+                fits[o] = sum(g is not None for g in got)
+        best = max(fits.values(), default=0)
+        at = [o for o, v in fits.items() if v == best]
+        assert best > 0 and len(at) == 1, f"{rel}: an anchor of make_patch.py does not sit on the patch's lines:\n{before}"
+        for i, t in enumerate(bl):
+            known[at[0] + i] = t
+    return known
+
+
+def test_patch_applies_to_the_reference_and_matches_its_generator(tmp_path):
+    """The six reference files are rebuilt without a checkout of the reference: every line the patch and make_patch.py
+    record must be the reference's own line at that number (tests/golden/integration_patch_lines.json: line counts and a
+    sha256 per recorded line, made by tests/golden/make_golden.py), every other line is a unique placeholder.  The
+    committed patch must apply to them, the generator must run on them (every anchor found once), and the generator's diff
+    must produce exactly the files the committed patch produces."""
     patch = os.path.join(HERE, "arroy-hip.patch")
-    out = subprocess.run([sys.executable, os.path.join(HERE, "make_patch.py"), REF], capture_output=True, text=True, check=True)
-    assert out.stdout == open(patch).read(), "arroy-hip.patch is stale: python integration/arroy-hip/make_patch.py > arroy-hip.patch"
-    chk = subprocess.run(["git", "apply", "--check", "--verbose", patch], cwd=REF, capture_output=True, text=True)
-    assert chk.returncode == 0, chk.stderr
-    touched = set(re.findall(r"^\+\+\+ b/(\S+)", open(patch).read(), re.M))
-    assert touched == {"Cargo.toml", "src/lib.rs", "src/parallel.rs", "src/writer.rs", "src/reader.rs", "src/distance/dot_product.rs"}
+    text = open(patch).read()
+    spec = importlib.util.spec_from_file_location("make_patch", os.path.join(HERE, "make_patch.py"))
+    make_patch = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(make_patch)
+    hunks = patch_hunks(text)
+    assert set(hunks) == set(make_patch.EDITS) == TOUCHED
+    pinned = json.load(open(os.path.join(ROOT, "tests", "golden", "integration_patch_lines.json")))["files"]
+    ref = tmp_path / "reference"
+    for rel, hs in hunks.items():
+        known = recorded_lines(rel, hs, make_patch.EDITS[rel])
+        want = pinned[rel]["sha256"]
+        wrong = [n for n in sorted(known) if want.get(str(n)) != hashlib.sha256(known[n].rstrip("\n").encode()).hexdigest()]
+        assert not wrong, (f"{rel}: lines {wrong} of arroy-hip.patch / make_patch.py are not the reference's lines at those "
+                           "numbers (after a new edit that records new lines: python tests/golden/make_golden.py)")
+        assert max(known) <= pinned[rel]["lines"]
+        (ref / rel).parent.mkdir(parents=True, exist_ok=True)
+        (ref / rel).write_text("".join(known.get(n, f"@@ line {n} @@\n") for n in range(1, pinned[rel]["lines"] + 1)))
+    out = subprocess.run([sys.executable, os.path.join(HERE, "make_patch.py"), str(ref)], capture_output=True, text=True)
+    assert out.returncode == 0, out.stderr
+    (tmp_path / "generated.patch").write_text(out.stdout)
+    trees = {}
+    for name, p in (("committed", patch), ("generated", str(tmp_path / "generated.patch"))):
+        tree = tmp_path / name
+        shutil.copytree(ref, tree)
+        subprocess.run(["git", "init", "-q", str(tree)], check=True)
+        chk = subprocess.run(["git", "apply", "--check", "--verbose", p], cwd=tree, capture_output=True, text=True)
+        assert chk.returncode == 0, chk.stderr
+        subprocess.run(["git", "apply", p], cwd=tree, check=True)
+        trees[name] = {rel: (tree / rel).read_text() for rel in TOUCHED}
+    # the files both patches produce, not the patch texts: around the placeholders difflib may align a hunk differently
+    # (e.g. where an inserted `}` could pair with either of two) than it does on the whole reference file
+    assert trees["committed"] == trees["generated"], \
+        "arroy-hip.patch is stale: python integration/arroy-hip/make_patch.py > arroy-hip.patch"
+    touched = set(re.findall(r"^\+\+\+ b/(\S+)", text, re.M))
+    assert touched == TOUCHED
 
 
 def test_every_public_function_of_hip_rs_has_a_call_site():
