@@ -194,6 +194,20 @@ SIGNATURES = {
     "ah_bench_memcpy": (C.c_int, [C.c_int, C.c_uint64, C.c_uint32, C.POINTER(C.c_double)]),
     "ah_bench_read": (C.c_int, [C.c_int, C.c_uint64, C.c_uint32, C.POINTER(C.c_double)]),
     "ah_device_name": (C.c_int, [C.c_int, C.c_char_p, C.c_size_t]),
+    # device groups: one replica per listed device, one forest over all of them
+    "ah_group_create": (C.c_int, [C.c_int, C.c_uint32, C.c_uint64, C.POINTER(C.c_int), C.c_uint32, C.POINTER(C.c_void_p)]),
+    "ah_group_upload_records": (C.c_int, [_VP, _U32P, _VP, C.c_size_t, C.c_size_t]),
+    "ah_group_upload_vectors": (C.c_int, [_VP, _U32P, _F32P, C.c_size_t]),
+    "ah_group_upload_flush": (C.c_int, [_VP]),
+    "ah_group_set_preprocessed": (C.c_int, [_VP, C.c_int]),
+    "ah_group_finalize": (C.c_int, [_VP]),
+    "ah_group_preprocess_dot": (C.c_int, [_VP, C.POINTER(C.c_float)]),
+    "ah_group_reserve_build": (C.c_int, [_VP, C.c_uint32, C.c_uint32]),
+    "ah_group_size": (C.c_int, [_VP, C.POINTER(C.c_uint32)]),
+    "ah_group_member": (C.c_int, [_VP, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "ah_group_destroy": (C.c_int, [_VP]),
+    "ah_build_forest_group_stream": (C.c_int, [_VP, C.POINTER(AhBuildOptions), NODE_BATCH_FN, _VP, _U32P, C.POINTER(AhBuildStats),
+                                               C.POINTER(AhBuildStats)]),
 }
 
 _lib = None

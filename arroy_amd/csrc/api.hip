@@ -928,10 +928,13 @@ int ah_dataset_create(int metric, uint32_t dimensions, uint64_t capacity, int de
 }
 
 static int upload_flush(ah_dataset *ds);
+static int finalize_impl(ah_dataset *ds);
+static int preprocess_dot_impl(ah_dataset *ds, float *out_max_norm);
 
 int ah_dataset_destroy(ah_dataset *ds) {
     AH_GUARDED("ah_dataset_destroy")
     if (!ds) return AH_OK;
+    AH_REQUIRE(!ds->group_member, AH_ERR_INVALID_ARGUMENT, "the dataset is a member of a device group (ah_group_destroy frees it)");
     NoFailScope no_fail;
     ds->join_reserve();
     (void)upload_flush(ds);
@@ -975,8 +978,7 @@ int ah_dataset_destroy(ah_dataset *ds) {
     AH_GUARDED_END
 }
 
-static int check_append(ah_dataset *ds, const uint32_t *item_ids, size_t n) {
-    AH_REQUIRE(ds, AH_ERR_INVALID_ARGUMENT, "dataset is NULL");
+static int check_ids(ah_dataset *ds, const uint32_t *item_ids, size_t n) {
     AH_REQUIRE(!ds->finalized, AH_ERR_INVALID_ARGUMENT, "dataset already finalized");
     AH_REQUIRE(item_ids || n == 0, AH_ERR_INVALID_ARGUMENT, "item_ids is NULL");
     AH_REQUIRE(ds->n + n <= ds->capacity, AH_ERR_INVALID_ARGUMENT, "upload of %zu items exceeds capacity %llu", n,
@@ -988,6 +990,18 @@ static int check_append(ah_dataset *ds, const uint32_t *item_ids, size_t n) {
                    "item ids must be strictly ascending (id %u after %u)", item_ids[i], prev);
     }
     return AH_OK;
+}
+static int check_append(ah_dataset *ds, const uint32_t *item_ids, size_t n) {
+    AH_REQUIRE(ds, AH_ERR_INVALID_ARGUMENT, "dataset is NULL");
+    AH_REQUIRE(!ds->group_member, AH_ERR_INVALID_ARGUMENT, "the dataset is a member of a device group: stage through ah_group_upload_*");
+    return check_ids(ds, item_ids, n);
+}
+
+// room for n more ids in the host mirror, grown geometrically; called before a group's uploads touch any member, so that
+// note_ids (which then allocates nothing) cannot leave one member's ids recorded and another's not
+static void reserve_ids(ah_dataset *ds, size_t n) {
+    const size_t need = ds->h_ids.size() + n;
+    if (ds->h_ids.capacity() < need) ds->h_ids.reserve(std::max(need, 2 * ds->h_ids.capacity()));
 }
 
 static void note_ids(ah_dataset *ds, const uint32_t *item_ids, size_t n) {
@@ -1009,6 +1023,7 @@ static constexpr int kRing = 3;
 static constexpr size_t kStageBytes = 32u << 20;
 
 static int upload_flush(ah_dataset *ds) {
+    std::lock_guard<std::mutex> lk(ds->up_mu);  // (several threads replicating one unfinalized source flush it together)
     if (!ds->up_ctx) return AH_OK;
     Context *c = ds->up_ctx;
     const hipError_t e = hipStreamSynchronize(c->stream);
@@ -1043,6 +1058,74 @@ static int upload_context(ah_dataset *ds, size_t buf_bytes, Context **out) {
     return AH_OK;
 }
 
+// One chunk of an upload in a pinned slot, and the two steps every chunk takes: the gather out of the caller's pages
+// (once, whatever the number of datasets it goes to — ah_group_upload_*) and the send to one dataset on one of its streams.
+struct RecordSlot {  // stored records: rows re-pitched to whole lines, headers and ids apart
+    uint8_t *rows, *hdr, *ids;
+    RecordSlot(uint8_t *base, size_t chunk, size_t rb, size_t hs)
+        : rows(base), hdr(base + pad256(chunk * rb)), ids(base + pad256(chunk * rb) + pad256(chunk * hs)) {}
+    static size_t bytes(size_t chunk, size_t rb, size_t hs) { return pad256(chunk * rb) + pad256(chunk * hs) + pad256(chunk * 4); }
+};
+static int gather_records(const RecordSlot &slot, const uint8_t *const *record_ptrs, const uint32_t *item_ids, size_t c,
+                          size_t rb, size_t hs, size_t vs, size_t first_index) {
+    for (size_t i = 0; i < c; i++) {
+        const uint8_t *rec = record_ptrs[i];
+        AH_REQUIRE(rec && rec[0] == 0, AH_ERR_INVALID_ARGUMENT, "record %zu is not a leaf (tag %d)", first_index + i,
+                   rec ? rec[0] : -1);
+    }
+    parallel_rows(c, rb + hs, [&](size_t lo, size_t hi) {
+        for (size_t i = lo; i < hi; i++) {
+            const uint8_t *rec = record_ptrs[i];
+            memcpy(slot.hdr + i * hs, rec + 1, hs);
+            copy_row(slot.rows + i * rb, rec + 1 + hs, vs);
+            if (rb > vs) memset(slot.rows + i * rb + vs, 0, rb - vs);
+        }
+        copy_fence();
+    });
+    memcpy(slot.ids, item_ids, c * 4);
+    return AH_OK;
+}
+static int send_records(ah_dataset *ds, const RecordSlot &slot, uint64_t row0, size_t c, hipStream_t s) {
+    const size_t rb = ds->row_bytes(), hs = ah_header_size(ds->metric);
+    uint8_t *d_rows = ds->d_rows_f32 ? reinterpret_cast<uint8_t *>(ds->d_rows_f32) : reinterpret_cast<uint8_t *>(ds->d_rows_bq);
+    AH_HIP(hipMemcpyAsync(d_rows + row0 * rb, slot.rows, c * rb, hipMemcpyHostToDevice, s));
+    AH_HIP(hipMemcpyAsync(reinterpret_cast<uint8_t *>(ds->d_headers) + row0 * hs, slot.hdr, c * hs, hipMemcpyHostToDevice, s));
+    AH_HIP(hipMemcpyAsync(ds->d_ids + row0, slot.ids, c * 4, hipMemcpyHostToDevice, s));
+    return AH_OK;
+}
+struct VectorSlot {  // f32 vectors at the staging pitch, then the ids
+    float *rows;
+    uint8_t *ids;
+    VectorSlot(uint8_t *base, size_t chunk, size_t frb) : rows(reinterpret_cast<float *>(base)), ids(base + pad256(chunk * frb)) {}
+    static size_t bytes(size_t chunk, size_t frb) { return pad256(chunk * frb) + pad256(chunk * 4); }
+};
+static void gather_vectors(const VectorSlot &slot, const float *vectors, const uint32_t *item_ids, size_t c, uint32_t dims,
+                           uint32_t fpitch) {
+    parallel_rows(c, (size_t)fpitch * 4, [&](size_t lo, size_t hi) {
+        for (size_t i = lo; i < hi; i++) {
+            copy_row(reinterpret_cast<uint8_t *>(slot.rows + i * fpitch), reinterpret_cast<const uint8_t *>(vectors + i * (size_t)dims),
+                     (size_t)dims * 4);
+            for (uint32_t e = dims; e < fpitch; e++) slot.rows[i * fpitch + e] = 0.0f;
+        }
+        copy_fence();
+    });
+    memcpy(slot.ids, item_ids, c * 4);
+}
+// BQ metrics: the f32 rows land in d_tmp (one ring slot of the context's device scratch) and are quantised from there
+static int send_vectors(ah_dataset *ds, const VectorSlot &slot, uint64_t row0, size_t c, uint32_t fpitch, float *d_tmp,
+                        hipStream_t s) {
+    const size_t frb = (size_t)fpitch * 4;
+    if (!metric_is_bq(ds->metric)) {
+        AH_HIP(hipMemcpyAsync(ds->d_rows_f32 + row0 * ds->pitch, slot.rows, c * frb, hipMemcpyHostToDevice, s));
+    } else {
+        AH_HIP(hipMemcpyAsync(d_tmp, slot.rows, c * frb, hipMemcpyHostToDevice, s));
+        AH_TRY(launch_quantize_rows(d_tmp, fpitch, ds->dims, ds->d_rows_bq + row0 * ds->pitch, ds->pitch, ds->words, c, s));
+    }
+    AH_HIP(hipMemcpyAsync(ds->d_ids + row0, slot.ids, c * 4, hipMemcpyHostToDevice, s));
+    AH_TRY(launch_headers_from_vectors(ds->view(), row0, c, s));
+    return AH_OK;
+}
+
 // LMDB pages -> pinned staging (header and vector split apart, rows re-pitched to 128-byte lines) -> hipMemcpyAsync.
 int ah_dataset_upload_records(ah_dataset *ds, const uint32_t *item_ids, const uint8_t *const *record_ptrs,
                               size_t record_len, size_t n) {
@@ -1061,7 +1144,7 @@ int ah_dataset_upload_records(ah_dataset *ds, const uint32_t *item_ids, const ui
     }
     const size_t rb = ds->row_bytes();
     const size_t chunk = std::max<size_t>(1, std::min<size_t>(n, kStageBytes / (rb + hs + 4)));
-    const size_t buf_bytes = pad256(chunk * rb) + pad256(chunk * hs) + pad256(chunk * 4);
+    const size_t buf_bytes = RecordSlot::bytes(chunk, rb, hs);
     Context *ctx = nullptr;
     AH_TRY(upload_context(ds, buf_bytes, &ctx));
     const size_t ring_stride = ctx->h_cap / kRing & ~(size_t)255;
@@ -1071,29 +1154,9 @@ int ah_dataset_upload_records(ah_dataset *ds, const uint32_t *item_ids, const ui
         const int b = ds->up_buf;
         uint8_t *base = reinterpret_cast<uint8_t *>(ctx->h_pinned) + (size_t)b * ring_stride;
         if (ds->up_used[b]) AH_HIP(hipEventSynchronize(ctx->ev_ring[b]));
-        uint8_t *h_rows = base, *h_hdr = base + pad256(chunk * rb), *h_ids = h_hdr + pad256(chunk * hs);
-        for (size_t i = 0; i < c; i++) {
-            const uint8_t *rec = record_ptrs[done + i];
-            AH_REQUIRE(rec && rec[0] == 0, AH_ERR_INVALID_ARGUMENT, "record %zu is not a leaf (tag %d)", done + i,
-                       rec ? rec[0] : -1);
-        }
-        parallel_rows(c, rb + hs, [&](size_t lo, size_t hi) {
-            for (size_t i = lo; i < hi; i++) {
-                const uint8_t *rec = record_ptrs[done + i];
-                memcpy(h_hdr + i * hs, rec + 1, hs);
-                copy_row(h_rows + i * rb, rec + 1 + hs, vs);
-                if (rb > vs) memset(h_rows + i * rb + vs, 0, rb - vs);
-            }
-            copy_fence();
-        });
-        memcpy(h_ids, item_ids + done, c * 4);
-        const uint64_t row0 = ds->n + done;
-        uint8_t *d_rows = ds->d_rows_f32 ? reinterpret_cast<uint8_t *>(ds->d_rows_f32)
-                                         : reinterpret_cast<uint8_t *>(ds->d_rows_bq);
-        AH_HIP(hipMemcpyAsync(d_rows + row0 * rb, h_rows, c * rb, hipMemcpyHostToDevice, ctx->stream));
-        AH_HIP(hipMemcpyAsync(reinterpret_cast<uint8_t *>(ds->d_headers) + row0 * hs, h_hdr, c * hs,
-                              hipMemcpyHostToDevice, ctx->stream));
-        AH_HIP(hipMemcpyAsync(ds->d_ids + row0, h_ids, c * 4, hipMemcpyHostToDevice, ctx->stream));
+        const RecordSlot slot(base, chunk, rb, hs);
+        AH_TRY(gather_records(slot, record_ptrs + done, item_ids + done, c, rb, hs, vs, done));
+        AH_TRY(send_records(ds, slot, ds->n + done, c, ctx->stream));
         AH_HIP(hipEventRecord(ctx->ev_ring[b], ctx->stream));
         ds->up_used[b] = true;
         ds->up_buf = (b + 1) % kRing;
@@ -1137,7 +1200,7 @@ int ah_dataset_upload_vectors(ah_dataset *ds, const uint32_t *item_ids, const fl
         (void)hipGetLastError();  // not registrable: fall through to the bounce path
     }
     const size_t chunk = std::max<size_t>(1, std::min<size_t>(n, kStageBytes / (frb + 4)));
-    const size_t buf_bytes = pad256(chunk * frb) + pad256(chunk * 4);
+    const size_t buf_bytes = VectorSlot::bytes(chunk, frb);
     const bool timing = tun(TUN_TIMING) != 0;
     auto now = [] { return std::chrono::steady_clock::now(); };
     auto secs = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
@@ -1161,32 +1224,13 @@ int ah_dataset_upload_vectors(ah_dataset *ds, const uint32_t *item_ids, const fl
         const auto t0 = now();
         if (ds->up_used[b]) AH_HIP(hipEventSynchronize(ctx->ev_ring[b]));
         const auto t1 = now();
-        float *h_rows = reinterpret_cast<float *>(base);
-        uint8_t *h_ids = base + pad256(chunk * frb);
-        parallel_rows(c, frb, [&](size_t lo, size_t hi) {
-            for (size_t i = lo; i < hi; i++) {
-                copy_row(reinterpret_cast<uint8_t *>(h_rows + i * fpitch),
-                         reinterpret_cast<const uint8_t *>(vectors + (done + i) * (size_t)ds->dims), (size_t)ds->dims * 4);
-                for (uint32_t e = ds->dims; e < fpitch; e++) h_rows[i * fpitch + e] = 0.0f;
-            }
-            copy_fence();
-        });
+        const VectorSlot slot(base, chunk, frb);
+        gather_vectors(slot, vectors + done * (size_t)ds->dims, item_ids + done, c, ds->dims, fpitch);
         t_wait += secs(t0, t1);
         t_gather += secs(t1, now());
-        memcpy(h_ids, item_ids + done, c * 4);
-        const uint64_t row0 = ds->n + done;
-        if (!bq) {
-            AH_HIP(hipMemcpyAsync(ds->d_rows_f32 + row0 * ds->pitch, h_rows, c * frb, hipMemcpyHostToDevice,
-                                  ctx->stream));
-        } else {
-            float *d_tmp = reinterpret_cast<float *>(reinterpret_cast<uint8_t *>(ctx->d_scratch) +
-                                                     (size_t)b * pad256(chunk * frb));
-            AH_HIP(hipMemcpyAsync(d_tmp, h_rows, c * frb, hipMemcpyHostToDevice, ctx->stream));
-            AH_TRY(launch_quantize_rows(d_tmp, fpitch, ds->dims, ds->d_rows_bq + row0 * ds->pitch, ds->pitch, ds->words,
-                                        c, ctx->stream));
-        }
-        AH_HIP(hipMemcpyAsync(ds->d_ids + row0, h_ids, c * 4, hipMemcpyHostToDevice, ctx->stream));
-        AH_TRY(launch_headers_from_vectors(dv, row0, c, ctx->stream));
+        float *d_tmp = bq ? reinterpret_cast<float *>(reinterpret_cast<uint8_t *>(ctx->d_scratch) + (size_t)b * pad256(chunk * frb))
+                          : nullptr;
+        AH_TRY(send_vectors(ds, slot, ds->n + done, c, fpitch, d_tmp, ctx->stream));
         AH_HIP(hipEventRecord(ctx->ev_ring[b], ctx->stream));
         ds->up_used[b] = true;
         ds->up_buf = (b + 1) % kRing;
@@ -1212,6 +1256,7 @@ int ah_dataset_upload_flush(ah_dataset *ds) {
 int ah_dataset_set_preprocessed(ah_dataset *ds, int preprocessed) {
     AH_GUARDED("ah_dataset_set_preprocessed")
     AH_REQUIRE(ds, AH_ERR_INVALID_ARGUMENT, "dataset is NULL");
+    AH_REQUIRE(!ds->group_member, AH_ERR_INVALID_ARGUMENT, "the dataset is a member of a device group: use the ah_group_* call");
     AH_REQUIRE(ds->metric == AH_DOT_PRODUCT, AH_ERR_INVALID_ARGUMENT, "only DotProduct datasets have a preprocess step");
     ds->dot_preprocessed = preprocessed != 0;
     return AH_OK;
@@ -1221,6 +1266,7 @@ int ah_dataset_set_preprocessed(ah_dataset *ds, int preprocessed) {
 int ah_dataset_fill_synthetic(ah_dataset *ds, uint64_t seed, int distribution, uint64_t n_items) {
     AH_GUARDED("ah_dataset_fill_synthetic")
     AH_REQUIRE(ds, AH_ERR_INVALID_ARGUMENT, "dataset is NULL");
+    AH_REQUIRE(!ds->group_member, AH_ERR_INVALID_ARGUMENT, "the dataset is a member of a device group: use the ah_group_* call");
     AH_REQUIRE(!ds->finalized && ds->n == 0, AH_ERR_INVALID_ARGUMENT, "synthetic fill needs an empty dataset");
     AH_REQUIRE(n_items <= ds->capacity, AH_ERR_INVALID_ARGUMENT, "n_items exceeds capacity");
     AH_REQUIRE(distribution >= AH_SYNTH_UNIFORM_01 && distribution <= AH_SYNTH_LAST, AH_ERR_INVALID_ARGUMENT,
@@ -1254,6 +1300,13 @@ int ah_dataset_fill_synthetic(ah_dataset *ds, uint64_t seed, int distribution, u
 int ah_dataset_finalize(ah_dataset *ds) {
     AH_GUARDED("ah_dataset_finalize")
     AH_REQUIRE(ds, AH_ERR_INVALID_ARGUMENT, "dataset is NULL");
+    AH_REQUIRE(!ds->group_member, AH_ERR_INVALID_ARGUMENT, "the dataset is a member of a device group: use the ah_group_* call");
+    return finalize_impl(ds);
+    AH_GUARDED_END
+}
+
+// ah_dataset_finalize, and ah_group_finalize for every member
+static int finalize_impl(ah_dataset *ds) {
     if (ds->finalized) return AH_OK;
     AH_TRY(upload_flush(ds));  // every staged record has landed
     AH_LEASE(ds, ctx);
@@ -1275,7 +1328,6 @@ int ah_dataset_finalize(ah_dataset *ds) {
     }
     ds->finalized = true;
     return AH_OK;
-    AH_GUARDED_END
 }
 
 int ah_dataset_len(const ah_dataset *ds, uint64_t *out_n_items) {
@@ -1382,17 +1434,8 @@ int ah_dataset_replicate(ah_dataset *src, int device, ah_dataset **out) {
     AH_REQUIRE(out, AH_ERR_INVALID_ARGUMENT, "out is NULL");
     *out = nullptr;
     AH_REQUIRE(src, AH_ERR_INVALID_ARGUMENT, "dataset is NULL");
-    AH_TRY(upload_flush(src));
-    // the calling thread may hold another device current (a host thread per GPU): put it back on every path out
-    struct DeviceRestore {
-        int prev = -1;
-        DeviceRestore() {
-            if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        }
-        ~DeviceRestore() {
-            if (prev >= 0) (void)hipSetDevice(prev);
-        }
-    } restore_device;
+    AH_TRY(upload_flush(src));  // (under the source's staging lock: several threads may replicate one unfinalized source)
+    DeviceRestore restore_device;  // (the calling thread may hold another device current: a host thread per GPU)
     ah_dataset *dst = nullptr;
     AH_TRY(ah_dataset_create(src->metric, src->dims, std::max<uint64_t>(src->capacity, 1), device, &dst));
     int st = AH_OK;
@@ -1444,6 +1487,301 @@ int ah_dataset_replicate(ah_dataset *src, int device, ah_dataset **out) {
         return st;
     }
     *out = dst;
+    return AH_OK;
+    AH_GUARDED_END
+}
+
+// ---------------------------------------------------------------------------------------------
+// device groups (include/arroy_hip.h, "Device groups"): staging.  The build is in group.hip.
+// ---------------------------------------------------------------------------------------------
+namespace {
+// wait until no member's transfer out of ring slot b is in flight
+int group_wait_slot(ah_group *g, int b) {
+    if (!g->slot_used[b]) return AH_OK;
+    for (ah_dataset *m : g->members)
+        if (m->up_ctx && m->up_ctx->ev_ring[b]) AH_HIP(hipEventSynchronize(m->up_ctx->ev_ring[b]));
+    g->slot_used[b] = false;
+    return AH_OK;
+}
+
+// the pinned ring (kRing slots of at least slot_bytes; grown only when idle) and every member's upload context: its stream,
+// its ring events and, for the 1-bit metrics, device scratch for one f32 chunk per slot
+int group_stage_begin(ah_group *g, size_t slot_bytes, size_t member_scratch) {
+    if (g->slot_bytes < slot_bytes) {
+        for (int b = 0; b < ah_group::kRing; b++) AH_TRY(group_wait_slot(g, b));
+        if (g->h_ring) AH_HIP(hipHostFree(g->h_ring));
+        g->h_ring = nullptr;
+        g->slot_bytes = 0;
+        const size_t slot = (slot_bytes + 4095) & ~(size_t)4095;
+        AH_REQUIRE(!fail_alloc_tick(), AH_ERR_OUT_OF_MEMORY, "pinned host allocation of %zu bytes failed (AH_FAIL_ALLOC_AFTER)",
+                   slot * ah_group::kRing);
+        // portable: every member's device may use the slot as its DMA source
+        AH_HIP(hipHostMalloc(&g->h_ring, slot * ah_group::kRing, hipHostMallocPortable));
+        g->slot_bytes = slot;
+    }
+    for (ah_dataset *m : g->members) {
+        AH_HIP(hipSetDevice(m->device));
+        std::lock_guard<std::mutex> lk(m->up_mu);
+        if (!m->up_ctx) {
+            m->up_ctx = m->acquire();
+            AH_REQUIRE(m->up_ctx, AH_ERR_DEVICE, "cannot create a HIP stream");
+        }
+        Context *c = m->up_ctx;
+        for (hipEvent_t &e : c->ev_ring)
+            if (!e) AH_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        if (member_scratch && c->d_cap < member_scratch) {
+            AH_HIP(hipStreamSynchronize(c->stream));  // the old scratch may still be a quantize source
+            AH_TRY(c->ensure_device(member_scratch));
+        }
+    }
+    return AH_OK;
+}
+}  // namespace
+
+int ah_group_create(int metric, uint32_t dimensions, uint64_t capacity, const int *devices, uint32_t n_devices,
+                    ah_group **out) {
+    AH_GUARDED("ah_group_create")
+    AH_REQUIRE(out, AH_ERR_INVALID_ARGUMENT, "out is NULL");
+    *out = nullptr;
+    AH_REQUIRE(devices && n_devices > 0, AH_ERR_INVALID_ARGUMENT, "a group needs at least one device");
+    AH_REQUIRE(metric_valid(metric), AH_ERR_INVALID_ARGUMENT, "unknown metric %d", metric);
+    int n_dev = 0;
+    AH_TRY(ah_device_count(&n_dev));
+    for (uint32_t i = 0; i < n_devices; i++)
+        AH_REQUIRE(devices[i] >= 0 && devices[i] < n_dev, AH_ERR_INVALID_ARGUMENT, "device %d of the group is not present (%d visible)",
+                   devices[i], n_dev);
+    DeviceRestore restore_device;
+    ah_group *g = new ah_group();
+    g->metric = metric;
+    g->dims = dimensions;
+    int st = AH_OK;
+    try {
+        g->members.reserve(n_devices);
+        for (uint32_t i = 0; i < n_devices && st == AH_OK; i++) {
+            ah_dataset *ds = nullptr;
+            st = ah_dataset_create(metric, dimensions, capacity, devices[i], &ds);
+            if (st == AH_OK) {
+                ds->group_member = true;
+                g->members.push_back(ds);
+            }
+        }
+    } catch (...) {
+        (void)ah_group_destroy(g);
+        throw;
+    }
+    if (st != AH_OK) {
+        const std::string why = last_error();
+        (void)ah_group_destroy(g);
+        set_error("%s", why.c_str());
+        set_error_status(st);
+        return st;
+    }
+    *out = g;
+    return AH_OK;
+    AH_GUARDED_END
+}
+
+int ah_group_destroy(ah_group *g) {
+    AH_GUARDED("ah_group_destroy")
+    if (!g) return AH_OK;
+    NoFailScope no_fail;
+    DeviceRestore restore_device;
+    for (ah_dataset *m : g->members) {
+        (void)upload_flush(m);  // (every transfer out of the ring has landed before the ring goes)
+        m->group_member = false;
+        (void)ah_dataset_destroy(m);
+    }
+    if (g->h_ring) (void)hipHostFree(g->h_ring);
+    delete g;
+    return AH_OK;
+    AH_GUARDED_END
+}
+
+// Writer::add_item for a batch, on every member: the chunk is gathered once into the group's pinned ring and sent from that
+// same slot to every member, each on its own stream, where the codec / header kernels run on the member's device.
+int ah_group_upload_vectors(ah_group *g, const uint32_t *item_ids, const float *vectors, size_t n) {
+    AH_GUARDED("ah_group_upload_vectors")
+    AH_REQUIRE(g, AH_ERR_INVALID_ARGUMENT, "group is NULL");
+    ah_dataset *m0 = g->members[0];
+    AH_TRY(check_ids(m0, item_ids, n));  // (the members are in the same state)
+    if (n == 0) return AH_OK;
+    AH_REQUIRE(item_ids && vectors, AH_ERR_INVALID_ARGUMENT, "NULL input");
+    DeviceRestore restore_device;
+    for (ah_dataset *m : g->members) reserve_ids(m, n);
+    const bool bq = metric_is_bq(g->metric);
+    const uint32_t fpitch = bq ? ((g->dims + 3u) & ~3u) : m0->pitch;
+    const size_t frb = (size_t)fpitch * 4;
+    const size_t chunk = std::max<size_t>(1, std::min<size_t>(n, kStageBytes / (frb + 4)));
+    // AH_TIMING=1: where the call's time went, in the form of ah_dataset_upload_vectors' line (scripts/exp_group.py reads
+    // the gather: it is paid once whatever the number of members)
+    const bool timing = tun(TUN_TIMING) != 0;
+    auto now = [] { return std::chrono::steady_clock::now(); };
+    auto secs = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
+        return std::chrono::duration<double>(b - a).count();
+    };
+    const auto t_begin = now();
+    double t_gather = 0, t_wait = 0;
+    AH_TRY(group_stage_begin(g, VectorSlot::bytes(chunk, frb), bq ? (size_t)ah_group::kRing * pad256(chunk * frb) : 0));
+    const auto t_ctx = now();
+    size_t done = 0;
+    while (done < n) {
+        const size_t c = std::min(chunk, n - done);
+        const int b = g->next_slot;
+        const auto t0 = now();
+        AH_TRY(group_wait_slot(g, b));
+        const auto t1 = now();
+        const VectorSlot slot(reinterpret_cast<uint8_t *>(g->h_ring) + (size_t)b * g->slot_bytes, chunk, frb);
+        gather_vectors(slot, vectors + done * (size_t)g->dims, item_ids + done, c, g->dims, fpitch);
+        t_wait += secs(t0, t1);
+        t_gather += secs(t1, now());
+        for (ah_dataset *m : g->members) {
+            Context *ctx = m->up_ctx;
+            AH_HIP(hipSetDevice(m->device));
+            float *d_tmp = bq ? reinterpret_cast<float *>(reinterpret_cast<uint8_t *>(ctx->d_scratch) + (size_t)b * pad256(chunk * frb))
+                              : nullptr;
+            g->slot_used[b] = true;
+            AH_TRY(send_vectors(m, slot, m->n + done, c, fpitch, d_tmp, ctx->stream));
+            AH_HIP(hipEventRecord(ctx->ev_ring[b], ctx->stream));
+        }
+        g->next_slot = (b + 1) % ah_group::kRing;
+        done += c;
+    }
+    const auto t_loop = now();
+    for (ah_dataset *m : g->members) note_ids(m, item_ids, n);
+    if (timing)
+        fprintf(stderr, "[ah] group upload_vectors %zu x %u to %zu members: context + pinned ring %.4f s, gather %.4f s, waiting for "
+                        "the ring %.4f s, launch/other %.4f s, note_ids %.4f s\n",
+                n, g->dims, g->members.size(), secs(t_begin, t_ctx), t_gather, t_wait, secs(t_ctx, t_loop) - t_gather - t_wait,
+                secs(t_loop, now()));
+    return AH_OK;
+    AH_GUARDED_END
+}
+
+// LMDB pages -> the group's pinned ring (once) -> every member.
+int ah_group_upload_records(ah_group *g, const uint32_t *item_ids, const uint8_t *const *record_ptrs, size_t record_len,
+                            size_t n) {
+    AH_GUARDED("ah_group_upload_records")
+    AH_REQUIRE(g, AH_ERR_INVALID_ARGUMENT, "group is NULL");
+    ah_dataset *m0 = g->members[0];
+    AH_TRY(check_ids(m0, item_ids, n));
+    if (n == 0) return AH_OK;
+    AH_REQUIRE(item_ids && record_ptrs, AH_ERR_INVALID_ARGUMENT, "NULL input");
+    const size_t hs = ah_header_size(g->metric), vs = ah_vector_size(g->metric, g->dims);
+    if (record_len != 1 + hs + vs) {
+        set_error("record length %zu does not match 1 + %zu + %zu for %u dimensions", record_len, hs, vs, g->dims);
+        set_error_status(AH_ERR_INVALID_DIMENSION);
+        set_error_detail(0, 1 + hs + vs, record_len);
+        return AH_ERR_INVALID_DIMENSION;
+    }
+    DeviceRestore restore_device;
+    for (ah_dataset *m : g->members) reserve_ids(m, n);
+    const size_t rb = m0->row_bytes();
+    const size_t chunk = std::max<size_t>(1, std::min<size_t>(n, kStageBytes / (rb + hs + 4)));
+    AH_TRY(group_stage_begin(g, RecordSlot::bytes(chunk, rb, hs), 0));
+    size_t done = 0;
+    while (done < n) {
+        const size_t c = std::min(chunk, n - done);
+        const int b = g->next_slot;
+        AH_TRY(group_wait_slot(g, b));
+        const RecordSlot slot(reinterpret_cast<uint8_t *>(g->h_ring) + (size_t)b * g->slot_bytes, chunk, rb, hs);
+        AH_TRY(gather_records(slot, record_ptrs + done, item_ids + done, c, rb, hs, vs, done));
+        for (ah_dataset *m : g->members) {
+            Context *ctx = m->up_ctx;
+            AH_HIP(hipSetDevice(m->device));
+            g->slot_used[b] = true;
+            AH_TRY(send_records(m, slot, m->n + done, c, ctx->stream));
+            AH_HIP(hipEventRecord(ctx->ev_ring[b], ctx->stream));
+        }
+        g->next_slot = (b + 1) % ah_group::kRing;
+        done += c;
+    }
+    for (ah_dataset *m : g->members) note_ids(m, item_ids, n);
+    return AH_OK;
+    AH_GUARDED_END
+}
+
+int ah_group_upload_flush(ah_group *g) {
+    AH_GUARDED("ah_group_upload_flush")
+    AH_REQUIRE(g, AH_ERR_INVALID_ARGUMENT, "group is NULL");
+    DeviceRestore restore_device;
+    int st = AH_OK;
+    for (ah_dataset *m : g->members) {
+        const int s = upload_flush(m);
+        if (st == AH_OK) st = s;
+    }
+    for (bool &u : g->slot_used) u = false;
+    return st;
+    AH_GUARDED_END
+}
+
+int ah_group_set_preprocessed(ah_group *g, int preprocessed) {
+    AH_GUARDED("ah_group_set_preprocessed")
+    AH_REQUIRE(g, AH_ERR_INVALID_ARGUMENT, "group is NULL");
+    AH_REQUIRE(g->metric == AH_DOT_PRODUCT, AH_ERR_INVALID_ARGUMENT, "only DotProduct datasets have a preprocess step");
+    for (ah_dataset *m : g->members) m->dot_preprocessed = preprocessed != 0;
+    return AH_OK;
+    AH_GUARDED_END
+}
+
+int ah_group_finalize(ah_group *g) {
+    AH_GUARDED("ah_group_finalize")
+    AH_REQUIRE(g, AH_ERR_INVALID_ARGUMENT, "group is NULL");
+    DeviceRestore restore_device;
+    AH_TRY(ah_group_upload_flush(g));
+    for (ah_dataset *m : g->members) AH_TRY(finalize_impl(m));
+    return AH_OK;
+    AH_GUARDED_END
+}
+
+int ah_group_preprocess_dot(ah_group *g, float *out_max_norm) {
+    AH_GUARDED("ah_group_preprocess_dot")
+    AH_REQUIRE(g, AH_ERR_INVALID_ARGUMENT, "group is NULL");
+    DeviceRestore restore_device;
+    AH_TRY(ah_group_upload_flush(g));
+    float first = 0.0f;
+    for (size_t i = 0; i < g->members.size(); i++) {
+        float m = 0.0f;
+        AH_TRY(preprocess_dot_impl(g->members[i], &m));
+        if (i == 0) first = m;
+        uint32_t a, b;
+        memcpy(&a, &first, 4);
+        memcpy(&b, &m, 4);
+        AH_REQUIRE(a == b, AH_ERR_DEVICE, "DotProduct preprocess: member %zu found max norm %a, member 0 %a (the replicas differ)", i,
+                   (double)m, (double)first);
+    }
+    if (out_max_norm) *out_max_norm = first;
+    return AH_OK;
+    AH_GUARDED_END
+}
+
+int ah_group_reserve_build(ah_group *g, uint32_t n_trees, uint32_t split_after) {
+    AH_GUARDED("ah_group_reserve_build")
+    AH_REQUIRE(g, AH_ERR_INVALID_ARGUMENT, "group is NULL");
+    DeviceRestore restore_device;
+    const uint32_t G = (uint32_t)g->members.size();
+    for (uint32_t i = 0; i < G; i++) {
+        const uint32_t share = n_trees > i ? (n_trees - i + G - 1) / G : 0;  // trees t = i (mod G)
+        if (share) AH_TRY(ah_dataset_reserve_build(g->members[i], share, split_after));
+    }
+    return AH_OK;
+    AH_GUARDED_END
+}
+
+int ah_group_size(const ah_group *g, uint32_t *out_n_members) {
+    AH_GUARDED("ah_group_size")
+    AH_REQUIRE(g && out_n_members, AH_ERR_INVALID_ARGUMENT, "NULL argument");
+    *out_n_members = (uint32_t)g->members.size();
+    return AH_OK;
+    AH_GUARDED_END
+}
+
+int ah_group_member(ah_group *g, uint32_t i, ah_dataset **out) {
+    AH_GUARDED("ah_group_member")
+    AH_REQUIRE(out, AH_ERR_INVALID_ARGUMENT, "out is NULL");
+    *out = nullptr;
+    AH_REQUIRE(g, AH_ERR_INVALID_ARGUMENT, "group is NULL");
+    AH_REQUIRE(i < g->members.size(), AH_ERR_INVALID_ARGUMENT, "member %u of a group of %zu", i, g->members.size());
+    *out = g->members[i];
     return AH_OK;
     AH_GUARDED_END
 }
@@ -1508,6 +1846,13 @@ int ah_dataset_read_headers(ah_dataset *ds, uint64_t first_row, uint64_t n, void
 int ah_preprocess_dot(ah_dataset *ds, float *out_max_norm) {
     AH_GUARDED("ah_preprocess_dot")
     AH_REQUIRE(ds, AH_ERR_INVALID_ARGUMENT, "dataset is NULL");
+    AH_REQUIRE(!ds->group_member, AH_ERR_INVALID_ARGUMENT, "the dataset is a member of a device group: use the ah_group_* call");
+    return preprocess_dot_impl(ds, out_max_norm);
+    AH_GUARDED_END
+}
+
+// ah_preprocess_dot, and ah_group_preprocess_dot for every member
+static int preprocess_dot_impl(ah_dataset *ds, float *out_max_norm) {
     AH_REQUIRE(ds->metric == AH_DOT_PRODUCT, AH_ERR_INVALID_ARGUMENT, "preprocess is only defined for DotProduct");
     AH_TRY(upload_flush(ds));
     AH_LEASE(ds, ctx);
@@ -1519,7 +1864,6 @@ int ah_preprocess_dot(ah_dataset *ds, float *out_max_norm) {
     ds->dot_preprocessed = true;
     if (out_max_norm) *out_max_norm = m;
     return AH_OK;
-    AH_GUARDED_END
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -373,6 +373,8 @@ struct ah_dataset {
     ah::Context *up_ctx = nullptr;
     int up_buf = 0;
     bool up_used[4] = {false, false, false, false};
+    std::mutex up_mu;                            // upload_flush: concurrent flushes (replication of an unstaged source) take turns
+    bool group_member = false;                   // a member of an ah_group: borrowed handle, no staging / destroy of its own
     std::mutex mu;
     std::vector<ah::Context *> pool;
     bool counted = false;                        // dataset_born() ran for this handle (its destroy then runs dataset_gone())
@@ -403,7 +405,32 @@ struct ah_dataset {
     void release(ah::Context *c);
 };
 
+// ah_group (include/arroy_hip.h, "Device groups"): the member datasets and the pinned ring every upload chunk is gathered into
+// once.  The staging calls live in api.hip, the build in group.hip.
+struct ah_group {
+    static constexpr int kRing = 3;
+    int metric = 0;
+    uint32_t dims = 0;
+    std::vector<ah_dataset *> members;
+    void *h_ring = nullptr;                      // kRing slots of `slot_bytes`, hipHostMallocPortable (every member's DMA source)
+    size_t slot_bytes = 0;
+    int next_slot = 0;
+    bool slot_used[kRing] = {false, false, false};  // a member's transfer out of the slot may still be in flight
+};
+
 namespace ah {
+
+// The calling thread may hold another device current (a host thread per GPU): entry points that switch devices put it back
+// on every path out.
+struct DeviceRestore {
+    int prev = -1;
+    DeviceRestore() {
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+    }
+    ~DeviceRestore() {
+        if (prev >= 0) (void)hipSetDevice(prev);
+    }
+};
 
 // owning device pointer for short-lived buffers on paths with early error returns
 struct DevMem {

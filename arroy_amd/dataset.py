@@ -28,7 +28,8 @@ def _ptr(a: Optional[np.ndarray]):
 
 class Dataset:
     def __init__(self, distance: type[Distance], dimensions: int, capacity: int, device: int = 0, _handle=None,
-                 _finalized: bool = False):
+                 _finalized: bool = False, _owner=None):
+        self._owner = _owner  # a DatasetGroup whose member this is (borrowed handle: the group frees it)
         self.distance = distance
         self.metric = distance.metric
         self.dimensions = int(dimensions)
@@ -315,7 +316,145 @@ class Dataset:
 
     def close(self) -> None:
         if self._h:
-            _lib.lib().ah_dataset_destroy(self._h)
+            if self._owner is None:
+                _lib.lib().ah_dataset_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DatasetGroup:
+    """One replica of a dataset per listed device (ah_group): staged from one host pass, one forest built on all of them —
+    tree t on member t mod G, the forest a single Dataset builds with the same seeds.  `devices` may repeat a device."""
+
+    def __init__(self, distance: type[Distance], dimensions: int, capacity: int, devices: Sequence[int]):
+        self.distance = distance
+        self.metric = distance.metric
+        self.dimensions = int(dimensions)
+        self.devices = [int(d) for d in devices]
+        self._h = C.c_void_p()
+        arr = (C.c_int * max(1, len(self.devices)))(*self.devices)
+        _lib.check(_lib.lib().ah_group_create(self.metric, self.dimensions, int(capacity), arr, len(self.devices),
+                                              C.byref(self._h)))
+        self.finalized = False
+        self._members = {}
+
+    def __len__(self) -> int:
+        return len(self.devices)
+
+    def upload_vectors(self, item_ids: Sequence[int], vectors) -> None:
+        """Dataset.upload_vectors for every member: each chunk is gathered once and sent to every device."""
+        ids = _u32(item_ids)
+        v = _f32(vectors)
+        if v.ndim != 2 or v.shape[1] != self.dimensions:
+            got = v.shape[1] if v.ndim == 2 else v.size
+            raise _lib.InvalidVecDimension(1, f"invalid vector dimensions, provided {got} but expected {self.dimensions}")
+        if v.shape[0] != ids.size:
+            raise ValueError("ids and vectors disagree on the number of items")
+        _lib.check(_lib.lib().ah_group_upload_vectors(self._h, _ptr(ids), _ptr(v), ids.size))
+
+    def upload_records(self, item_ids: Sequence[int], records: Sequence[bytes], preprocessed: Optional[bool] = None) -> None:
+        """Dataset.upload_records for every member."""
+        ids = _u32(item_ids)
+        n = ids.size
+        if self.metric == 3 and preprocessed is not None:
+            _lib.check(_lib.lib().ah_group_set_preprocessed(self._h, 1 if preprocessed else 0))
+        if n == 0:
+            return
+        rec_len = len(records[0])
+        keep = [C.create_string_buffer(b"\0" + bytes(r), rec_len + 1) for r in records]
+        ptrs = (C.c_void_p * n)(*[C.addressof(b) + 1 for b in keep])
+        _lib.check(_lib.lib().ah_group_upload_records(self._h, _ptr(ids), ptrs, rec_len, n))
+
+    def flush(self) -> None:
+        _lib.check(_lib.lib().ah_group_upload_flush(self._h))
+
+    def reserve_build(self, n_trees: int, split_after: int = 0) -> None:
+        _lib.check(_lib.lib().ah_group_reserve_build(self._h, int(n_trees), int(split_after)))
+
+    def preprocess_dot(self) -> np.float32:
+        m = C.c_float(0)
+        _lib.check(_lib.lib().ah_group_preprocess_dot(self._h, C.byref(m)))
+        return np.float32(m.value)
+
+    def finalize(self) -> "DatasetGroup":
+        _lib.check(_lib.lib().ah_group_finalize(self._h))
+        self.finalized = True
+        for m in self._members.values():
+            m.finalized = True
+        return self
+
+    def member(self, i: int) -> Dataset:
+        """Member i as a Dataset (borrowed: it lives as long as the group; reading calls only)."""
+        if i not in self._members:
+            h = C.c_void_p()
+            _lib.check(_lib.lib().ah_group_member(self._h, int(i), C.byref(h)))
+            self._members[i] = Dataset(self.distance, self.dimensions, 0, device=self.devices[i], _handle=h,
+                                       _finalized=self.finalized, _owner=self)
+        return self._members[i]
+
+    def build_stream(self, tree_seeds: Sequence[int], sink=None, split_after: int = 0, margin_mode: int = 0,
+                     max_trees_in_flight: int = 0, max_host_threads: int = 0, cancel=None, progress=None):
+        """ah_build_forest_group_stream: the whole forest over the members, streamed to `sink(batch)` with the contract of
+        Dataset.build_forest_stream (sink=None collects a StreamedForest).  `cancel`: a ctypes c_int the caller may raise;
+        `progress(level, nodes_done, items_routed)`.  Returns (roots, summed stats, per-member stats, collected or None)."""
+        seeds = np.ascontiguousarray(tree_seeds, dtype=np.uint64)
+        opt = _lib.AhBuildOptions()
+        opt.n_trees = seeds.size
+        opt.split_after = int(split_after)
+        opt.tree_seeds = seeds.ctypes.data_as(C.POINTER(C.c_uint64))
+        opt.margin_mode = int(margin_mode)
+        opt.max_trees_in_flight = int(max_trees_in_flight)
+        opt.max_host_threads = int(max_host_threads)
+        if cancel is not None:
+            opt.cancel = C.pointer(cancel)
+        keep = None
+        if progress is not None:
+            def _pcb(_user, level, nodes_done, items_routed):
+                try:
+                    progress(level, nodes_done, items_routed)
+                except BaseException:  # noqa: BLE001 — nothing may unwind through the C frames
+                    pass
+            keep = _lib.PROGRESS_FN(_pcb)
+            opt.progress = keep
+        collected = StreamedForest(self.distance, self.dimensions) if sink is None else None
+        fn = collected.take if sink is None else sink
+        failure = []
+
+        def _cb(_user, batch_p):
+            try:
+                return int(fn(batch_p.contents) or 0)
+            except BaseException as e:  # noqa: BLE001
+                failure.append(e)
+                return -1
+        cb = _lib.NODE_BATCH_FN(_cb)
+        roots = np.zeros(seeds.size, dtype=np.uint32)
+        st = _lib.AhBuildStats()
+        per = (_lib.AhBuildStats * len(self.devices))()
+        code = _lib.lib().ah_build_forest_group_stream(self._h, C.byref(opt), cb, None, _ptr(roots), C.byref(st), per)
+        del keep
+        if failure:
+            raise failure[0]
+        _lib.check(code)
+
+        def _d(s):
+            d = {f: getattr(s, f) for f, _ in _lib.AhBuildStats._fields_}
+            d["margin_mode_launches"] = list(s.margin_mode_launches)
+            return d
+        if collected is not None:
+            collected.roots = roots
+        return roots, _d(st), [_d(s) for s in per], collected
+
+    def close(self) -> None:
+        if self._h:
+            for m in self._members.values():
+                m._h = C.c_void_p()
+            self._members = {}
+            _lib.lib().ah_group_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):

@@ -161,6 +161,28 @@ class TreeStore:
                                       None if vec is None else vec.tobytes())
         return ids[int(forest.roots[tree])]
 
+    def import_streamed_tree(self, streamed, tree: int, root_id: Optional[int] = None) -> int:
+        """import_tree for a tree of a StreamedForest (what a streaming / device-group build delivered): the same node
+        order, hence the same ids as importing the ah_forest of a single-device build."""
+        root = int(streamed.roots[tree])
+        order, stack = [], [root]
+        while stack:
+            i = stack.pop()
+            order.append(i)
+            if i in streamed.splits:
+                stack += [streamed.splits[i][1], streamed.splits[i][2]]
+        hs = streamed.distance.header_size()
+        ids: Dict[int, int] = {}
+        for i in reversed(order):
+            ids[i] = root_id if (i == root and root_id is not None) else self.next_id()
+            if i in streamed.leaves:
+                self.nodes[ids[i]] = ("D", np.array(streamed.leaves[i][0], dtype=np.uint32))
+            else:
+                nb, left, right = streamed.splits[i][:3]
+                hdr = np.frombuffer(nb[:hs], dtype=np.float32).copy() if nb is not None else np.zeros(hs // 4, np.float32)
+                self.nodes[ids[i]] = ("S", ids[left], ids[right], hdr, None if nb is None else bytes(nb[hs:]))
+        return ids[root]
+
     def subtree_ids(self, root: int) -> List[int]:
         out, stack = [], [root]
         while stack:
@@ -286,15 +308,21 @@ class Writer:
     def need_build(self) -> bool:  # src/writer.rs:355-363
         return bool(self._st.updated) or self._st.metadata is None
 
-    def builder(self, rng: Optional[random.Random] = None) -> "ArroyBuilder":
-        return ArroyBuilder(self, rng if rng is not None else random.Random())
+    def builder(self, rng: Optional[random.Random] = None, devices: Optional[Sequence[int]] = None) -> "ArroyBuilder":
+        return ArroyBuilder(self, rng if rng is not None else random.Random(), devices=devices)
 
 
 class ArroyBuilder:
     """`ArroyBuilder` (src/writer.rs:37-265): n_trees / split_after / cancel / progress / build."""
 
-    def __init__(self, writer: Writer, rng: random.Random):
+    def __init__(self, writer: Writer, rng: random.Random, devices: Optional[Sequence[int]] = None):
+        """`devices`: stage the items on every listed device (a DatasetGroup: one host pass) and build the new trees on all
+        of them, tree t on device t mod len(devices) — the same forest as one device.  None: one device (device 0)."""
         self._w, self._rng = writer, rng
+        self._devices = None if devices is None else [int(d) for d in devices]
+        if self._devices is not None and not self._devices:
+            raise ValueError("devices must list at least one device")
+        self._group = None
         self._n_trees: Optional[int] = None
         self._split_after: Optional[int] = None
         self._cancel: Optional[Callable[[], bool]] = None
@@ -333,7 +361,17 @@ class ArroyBuilder:
         split_after = self._split_after or w.dimensions
         st.index = None
         ds = None
-        if n:
+        self._group = None
+        if n and self._devices is not None:
+            from .dataset import DatasetGroup
+            vecs = np.stack([st.items[int(i)] for i in ids])
+            self._group = DatasetGroup(dist, w.dimensions, n, self._devices)
+            self._group.upload_vectors(ids, vecs)
+            if dist.metric == 3:
+                self._group.preprocess_dot()
+            self._group.finalize()
+            ds = self._group.member(0)  # search and the incremental paths use member 0 (it keeps the group alive)
+        elif n:
             vecs = np.stack([st.items[int(i)] for i in ids])
             ds = Dataset(dist, w.dimensions, n)
             ds.upload_vectors(ids, vecs)
@@ -372,6 +410,9 @@ class ArroyBuilder:
         # ((768 / dims)^4 in the exponent); the reference then builds that many trees, and so does this mirror
         # (ah_node.tree is 32 bits since ABI v2) — in slices, so that the host-side forest stays bounded.
         seeds = self._seeds(count)
+        if self._group is not None:
+            self._add_trees_group(trees, seeds, split_after)
+            return
         for lo in range(0, count, 4096):
             forest = ds.build_forest(seeds[lo:lo + 4096], split_after=split_after, cancel=self._cancel,
                                      progress=self._progress)
@@ -380,6 +421,33 @@ class ArroyBuilder:
                 trees.import_tree(forest, t, root_id=root)
                 trees.roots.append(root)
             forest.close()
+
+    def _add_trees_group(self, trees: TreeStore, seeds: List[int], split_after: int) -> None:
+        """_add_trees on the device group: one streamed build over all members, imported tree by tree in tree order."""
+        import threading
+        cflag, watcher_stop = None, None
+        if self._cancel is not None:
+            import ctypes
+            cflag, watcher_stop = ctypes.c_int(0), threading.Event()
+            cancel = self._cancel
+
+            def _watch():
+                while not watcher_stop.wait(0.0005):
+                    if cancel():
+                        cflag.value = 1
+                        return
+            threading.Thread(target=_watch, daemon=True).start()
+        try:
+            for lo in range(0, len(seeds), 4096):
+                _roots, _stats, _per, streamed = self._group.build_stream(
+                    seeds[lo:lo + 4096], split_after=split_after, cancel=cflag, progress=self._progress)
+                for t in range(len(streamed.roots)):
+                    root = trees.next_id()
+                    trees.import_streamed_tree(streamed, t, root_id=root)
+                    trees.roots.append(root)
+        finally:
+            if watcher_stop is not None:
+                watcher_stop.set()
 
     def _incremental(self, ds: Dataset, st: "_IndexState", ids: np.ndarray, split_after: int) -> None:
         from .dataset import Index

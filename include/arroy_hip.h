@@ -46,7 +46,9 @@ extern "C" {
                               v7: ah_build_stats.seconds_reserve / seconds_reserve_wait (appended), ah_rerank_stats /
                                   ah_dataset_rerank_stats, ah_search_stats.rerank_screened8 / screen8_retried_chunks / descent_multi, AH_SYNTH_CLUSTERED / AH_SYNTH_LOW_RANK (arroy_hip_policy.h),
                                   ah_dataset_replicate falls back to a copy through pinned host memory when the two devices
-                                  have no peer access */
+                                  have no peer access;
+                                  device groups (ah_group_*, ah_build_forest_group_stream): additions only, the number stays 7 —
+                                  a caller that needs them looks the symbols up */
 
 /* every entry point is exported from the shared object (it is built with -fvisibility=hidden) */
 #if defined(__GNUC__)
@@ -445,6 +447,59 @@ typedef int (*ah_node_batch_fn)(void *user, const ah_node_batch *batch);
  * ah_forest_view numbers children before parents). */
 AH_API int ah_build_forest_stream(ah_dataset *ds, const ah_build_options *options, ah_node_batch_fn sink, void *user,
                                   uint32_t *out_roots, ah_build_stats *out_stats);
+
+/* ------------------------------------------------------------------------------------------
+ * Device groups: one replica of the dataset per listed device, staged from ONE host pass, and one forest built on all of
+ * them.  Trees are independent given the read-only dataset (`Writer::build` runs one task per root over ONE shared
+ * ImmutableLeafs, src/writer.rs:530,556-591), so a group shards TREES: tree t of a build is built on member t mod G, and
+ * the forest is the one a single dataset builds with the same seeds, node for node.
+ *
+ * Staging: every chunk of an upload is gathered from the caller's pages into the group's pinned ring ONCE and sent to
+ * every member by one hipMemcpyAsync per member from that same slot, on the member's own stream (no peer copy, no second
+ * host pass); each member then runs the codec / header kernels on its own device.  A slot is reused once every member's
+ * transfer out of it has completed; the gather of chunk k+1 overlaps the transfers of chunk k.  Group calls are
+ * single-caller, like the staging calls of a dataset.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct ah_group ah_group;   /* opaque: one replica dataset per listed device */
+
+/* `devices[0 .. n_devices)`: a device may be listed more than once (several replicas on one GPU).  n_devices == 0, a NULL
+ * pointer or a device index >= ah_device_count is AH_ERR_INVALID_ARGUMENT, reported before any device is touched. */
+AH_API int ah_group_create(int metric, uint32_t dimensions, uint64_t capacity, const int *devices, uint32_t n_devices,
+                           ah_group **out);
+/* The contracts of ah_dataset_upload_records / ah_dataset_upload_vectors, for every member at once. */
+AH_API int ah_group_upload_records(ah_group *group, const uint32_t *item_ids, const uint8_t *const *record_ptrs,
+                                   size_t record_len, size_t n);
+AH_API int ah_group_upload_vectors(ah_group *group, const uint32_t *item_ids, const float *vectors, size_t n);
+AH_API int ah_group_upload_flush(ah_group *group);
+AH_API int ah_group_set_preprocessed(ah_group *group, int preprocessed);
+AH_API int ah_group_finalize(ah_group *group);
+/* ah_preprocess_dot on every member; the members' max norms must agree bit for bit (AH_ERR_DEVICE otherwise). */
+AH_API int ah_group_preprocess_dot(ah_group *group, float *out_max_norm);
+/* ah_dataset_reserve_build for every member, with its share of `n_trees` (trees t = member mod G). */
+AH_API int ah_group_reserve_build(ah_group *group, uint32_t n_trees, uint32_t split_after);
+AH_API int ah_group_size(const ah_group *group, uint32_t *out_n_members);
+/* Member i as a BORROWED dataset handle: every call that reads a dataset takes it (distances, re-rank, ah_index_create*,
+ * search, the builds ...).  Every call that would change one replica without the others refuses it with
+ * AH_ERR_INVALID_ARGUMENT — ah_dataset_upload_records / _vectors, ah_dataset_fill_synthetic, ah_dataset_set_preprocessed,
+ * ah_dataset_finalize, ah_preprocess_dot — and so does ah_dataset_destroy: use the ah_group_* call.  It lives as long as
+ * the group. */
+AH_API int ah_group_member(ah_group *group, uint32_t i, ah_dataset **out);
+AH_API int ah_group_destroy(ah_group *group);   /* the members, the pinned ring, everything */
+
+/* One forest on every member: `options->n_trees` / `tree_seeds` describe the WHOLE forest; tree t is built on member
+ * t mod G by one host thread per member (each holds its own device; options->max_host_threads is split between them; the
+ * caller's current device is restored).  `sink` sees the contract of ah_build_forest_stream: called from one library
+ * thread at a time, a split node before its children, ids unique and dense from 0 over the whole call, children
+ * id-consecutive, `tree` = the global tree index; out_roots in global tree order.  One difference: the members' batches
+ * interleave in the order they reach the sink, so the Descendants nodes arrive in ascending (tree, position) order per
+ * member, not over the whole call (a sink keyed by id, as TmpNodes is, does not notice).  `options->cancel` stops every member;
+ * `progress` is called from the calling thread only, with nodes_done / items_routed summed over the members (they never
+ * decrease).  A non-zero sink return, a cancel or a member's error stops all members; no sink call follows the decision,
+ * every thread is joined and the FIRST error's status and text are returned; the group stays usable.  out_stats (may be
+ * NULL): the members' counters summed, levels = the deepest member's, seconds_total = wall time of this call;
+ * out_member_stats (may be NULL): one entry per member. */
+AH_API int ah_build_forest_group_stream(ah_group *group, const ah_build_options *options, ah_node_batch_fn sink, void *user,
+                                        uint32_t *out_roots, ah_build_stats *out_stats, ah_build_stats *out_member_stats);
 
 /* ------------------------------------------------------------------------------------------
  * Whole search on device (src/reader.rs:317-401): the forest mirrored in HBM next to its dataset, best-first

@@ -21,6 +21,12 @@
 //! * [`preprocess_dot_records`] — both passes of `DotProduct::preprocess` (the max norm, every item's `extra_dim` / `norm`) on
 //!   the device, from the pages the reference's first pass walks; the second pass only writes the headers back.
 //!
+//! With `ARROY_HIP_DEVICES` naming more than one device (e.g. `0,1,2,3`), [`stage_leafs`] stages the records into a device
+//! group — one replica per listed device, each record copied out of its page once (`ah_group_upload_records`) — and
+//! [`build_new_trees`] builds the new trees on all of them (`ah_build_forest_group_stream`: tree t on device t mod G, the
+//! same forest as one device, the same sink contract but for the order of Descendants nodes across devices, which
+//! `TmpNodes` — keyed by id — does not depend on).  Search and the incremental paths use the group's first member.
+//!
 //! LMDB, roaring, `NodeCodec`, `TmpNodes`, node-id allocation, the RNG and the public API stay as they are.
 //! Link with `RUSTFLAGS="-L <dir of libarroy_hip.so>"`; the library needs `libamdhip64` at run time.
 
@@ -49,6 +55,11 @@ const AH_NODE_SPLIT: u8 = 2;
 
 #[repr(C)]
 pub struct AhDataset {
+    _p: [u8; 0],
+}
+
+#[repr(C)]
+pub struct AhGroup {
     _p: [u8; 0],
 }
 
@@ -163,6 +174,34 @@ extern "C" {
         user: *mut c_void,
         out_roots: *mut u32,
         out_stats: *mut c_void,
+    ) -> c_int;
+    fn ah_group_create(
+        metric: c_int,
+        dims: u32,
+        capacity: u64,
+        devices: *const c_int,
+        n_devices: u32,
+        out: *mut *mut AhGroup,
+    ) -> c_int;
+    fn ah_group_upload_records(
+        group: *mut AhGroup,
+        ids: *const u32,
+        records: *const *const u8,
+        record_len: usize,
+        n: usize,
+    ) -> c_int;
+    fn ah_group_set_preprocessed(group: *mut AhGroup, preprocessed: c_int) -> c_int;
+    fn ah_group_finalize(group: *mut AhGroup) -> c_int;
+    fn ah_group_member(group: *mut AhGroup, i: u32, out: *mut *mut AhDataset) -> c_int;
+    fn ah_group_destroy(group: *mut AhGroup) -> c_int;
+    fn ah_build_forest_group_stream(
+        group: *mut AhGroup,
+        options: *const AhBuildOptions,
+        sink: extern "C" fn(*mut c_void, *const AhNodeBatch) -> c_int,
+        user: *mut c_void,
+        out_roots: *mut u32,
+        out_stats: *mut c_void,
+        out_member_stats: *mut c_void,
     ) -> c_int;
     fn ah_rerank_by_vector(
         ds: *mut AhDataset,
@@ -318,7 +357,10 @@ pub fn vector_len<D: Distance>(dimensions: usize) -> usize {
 /// The HBM-resident image of `ImmutableLeafs` (an `ah_dataset`).  Immutable once staged; `Sync` like the reference's
 /// structure (the library gives every calling thread its own stream and scratch).
 pub struct HipLeafs<D> {
+    /// the dataset, or the first member of `group`
     ds: *mut AhDataset,
+    /// non-null: the items are staged on every device of `ARROY_HIP_DEVICES` and new trees are built on all of them
+    group: *mut AhGroup,
     index: u16,
     /// bytes of one stored vector (record length - tag - header): 4 x dims, or 8 x ceil(dims / 64) for the 1-bit codecs
     vector_len: usize,
@@ -329,8 +371,26 @@ unsafe impl<D> Sync for HipLeafs<D> {}
 
 impl<D> Drop for HipLeafs<D> {
     fn drop(&mut self) {
-        unsafe { ah_dataset_destroy(self.ds) };
+        if self.group.is_null() {
+            unsafe { ah_dataset_destroy(self.ds) };
+        } else {
+            unsafe { ah_group_destroy(self.group) }; // (the member is borrowed from the group)
+        }
     }
+}
+
+/// `ARROY_HIP_DEVICES=0,1,2,3`: the devices a build stages its items on and shares its trees between.  `None` when the
+/// variable is unset or names fewer than two devices (one device: the `device` argument of [`stage_leafs`]).
+fn group_devices() -> Result<Option<Vec<c_int>>> {
+    let Some(list) = std::env::var_os("ARROY_HIP_DEVICES") else { return Ok(None) };
+    let list = list.to_string_lossy().into_owned();
+    let devices = list
+        .split(',')
+        .filter(|s| !s.trim().is_empty())
+        .map(|s| s.trim().parse::<c_int>())
+        .collect::<std::result::Result<Vec<_>, _>>()
+        .map_err(|e| Error::Panic(format!("ARROY_HIP_DEVICES={list}: {e}")))?;
+    Ok(if devices.len() > 1 { Some(devices) } else { None })
 }
 
 /// `ImmutableLeafs::new` for the device: the records `[0u8][header][vector]` are copied out of their LMDB pages (odd
@@ -355,11 +415,40 @@ pub fn stage_leafs<D: Distance>(
             let _ = unsafe { ah_tuning_set(b"AH_CACHE_KEEP_IDLE\0".as_ptr() as *const c_char, 1) };
         }
     });
+    if let Some(devices) = group_devices()? {
+        // one replica per device: every record is copied out of its page once and sent to all of them
+        let mut group = std::ptr::null_mut();
+        check(
+            unsafe {
+                ah_group_create(
+                    metric_of::<D>()?,
+                    dimensions as u32,
+                    items.len(),
+                    devices.as_ptr(),
+                    devices.len() as u32,
+                    &mut group,
+                )
+            },
+            index,
+        )?;
+        let (ids, ptrs, record_len) = leafs.raw_records(items);
+        let vector_len = record_len.saturating_sub(1 + size_of::<D::Header>());
+        let mut staged = HipLeafs { ds: std::ptr::null_mut(), group, index, vector_len, _marker: PhantomData };
+        for (ids, ptrs) in ids.chunks(1 << 16).zip(ptrs.chunks(1 << 16)) {
+            check(unsafe { ah_group_upload_records(group, ids.as_ptr(), ptrs.as_ptr(), record_len, ids.len()) }, index)?;
+        }
+        if preprocessed {
+            check(unsafe { ah_group_set_preprocessed(group, 1) }, index)?;
+        }
+        check(unsafe { ah_group_finalize(group) }, index)?;
+        check(unsafe { ah_group_member(group, 0, &mut staged.ds) }, index)?;
+        return Ok(staged);
+    }
     let mut ds = std::ptr::null_mut();
     check(unsafe { ah_dataset_create(metric_of::<D>()?, dimensions as u32, items.len(), device, &mut ds) }, index)?;
     let (ids, ptrs, record_len) = leafs.raw_records(items);
     let vector_len = record_len.saturating_sub(1 + size_of::<D::Header>());
-    let staged = HipLeafs { ds, index, vector_len, _marker: PhantomData };
+    let staged = HipLeafs { ds, group: std::ptr::null_mut(), index, vector_len, _marker: PhantomData };
     for (ids, ptrs) in ids.chunks(1 << 16).zip(ptrs.chunks(1 << 16)) {
         // ascending ids: RoaringBitmap order; asynchronous: returns once the records are copied out of the pages
         check(unsafe { ah_dataset_upload_records(ds, ids.as_ptr(), ptrs.as_ptr(), record_len, ids.len()) }, index)?;
@@ -490,15 +579,23 @@ pub fn build_new_trees<D: Distance, R: Rng>(
                 std::thread::sleep(std::time::Duration::from_micros(500));
             }
         });
-        let code = unsafe {
-            ah_build_forest_stream(
-                leafs.ds,
-                &opt,
-                sink_trampoline::<D>,
-                &mut state as *mut SinkState<D> as *mut c_void,
-                roots.as_mut_ptr(),
-                std::ptr::null_mut(),
-            )
+        let user = &mut state as *mut SinkState<D> as *mut c_void;
+        let code = if leafs.group.is_null() {
+            unsafe { ah_build_forest_stream(leafs.ds, &opt, sink_trampoline::<D>, user, roots.as_mut_ptr(), std::ptr::null_mut()) }
+        } else {
+            // the stream contract over every device of the group: one sink call at a time, ids dense from 0, a parent
+            // before its children, roots in tree order
+            unsafe {
+                ah_build_forest_group_stream(
+                    leafs.group,
+                    &opt,
+                    sink_trampoline::<D>,
+                    user,
+                    roots.as_mut_ptr(),
+                    std::ptr::null_mut(),
+                    std::ptr::null_mut(),
+                )
+            }
         };
         done.store(1, Ordering::Relaxed);
         let _ = watcher.join();
@@ -1006,7 +1103,7 @@ pub fn preprocess_dot_records<'a, D: Distance>(
     assert_eq!(unsafe { ah_abi_version() }, AH_ABI_VERSION, "libarroy_hip.so of another ABI version");
     let mut ds = std::ptr::null_mut();
     check(unsafe { ah_dataset_create(metric_of::<D>()?, (vector_len / 4) as u32, ids.len() as u64, 0, &mut ds) }, index)?;
-    let staged = HipLeafs::<D> { ds, index, vector_len, _marker: PhantomData };
+    let staged = HipLeafs::<D> { ds, group: std::ptr::null_mut(), index, vector_len, _marker: PhantomData };
     let record_len = 1 + size_of::<D::Header>() + vector_len;
     for (ids, ptrs) in ids.chunks(1 << 16).zip(ptrs.chunks(1 << 16)) {
         check(unsafe { ah_dataset_upload_records(ds, ids.as_ptr(), ptrs.as_ptr(), record_len, ids.len()) }, index)?;
