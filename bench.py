@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """bench.py — the headline measurement of arroy's distance-kernel hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W          # the headline alone
+    python bench.py --gpus N --steps K --warmup W --full   # ... and every other leg listed below
+
+A plain run does what the headline needs and nothing else: it fills the dataset, warms up, times the K steps, writes
+--dump-outputs if asked and prints the line (`roofline` from the timed launches and the stored, hash-stamped traffic
+figure).  Every other measurement and check — the device's copy / read ceilings, the forest builds, the CPU baseline,
+configs[3] / configs[4] / search, the live PMC passes, the cold child, `--extra` — runs under --full only.
 
 N > 1 runs either way: launched by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N` (one
 rank per GPU, RCCL only for the barrier and the max of the elapsed time; WORLD_SIZE must equal --gpus), or started
@@ -63,6 +69,9 @@ def parse_args():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--items", type=int, default=N_ITEMS)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run every other leg too (ceilings, builds, CPU baseline, configs[3] / configs[4] / "
+                         "search, live PMC, cold child); the --no-* options, --extra and --check-union choose among them")
     ap.add_argument("--trees", type=int, default=N_TREES)
     ap.add_argument("--no-build", action="store_true", help="skip the forest-build measurements")
     ap.add_argument("--no-build-10m", action="store_true",
@@ -111,6 +120,11 @@ def parse_args():
         ap.error("--steps must be at least 1 (the timed region is --steps launches of the scan)")
     if args.dump_outputs and args.dry_run:
         ap.error("--dump-outputs with --dry-run: a dry run computes no outputs")
+    if not args.full:
+        if args.extra or args.check_union:
+            ap.error("--extra and --check-union choose legs of --full: add --full")
+        # a plain run: the headline alone (the cold child goes with the builds; the ceilings check args.full where they run)
+        args.no_build = args.no_cpu = args.no_extra = args.no_live_pmc = True
     return args
 
 
@@ -873,6 +887,7 @@ def device_work(args, rank, world, device, sync, ds_1m, result):
         dump_output(args.dump_outputs, "distances", out)
     if rank == 0:
         result["device"] = arroy_amd.device_name(device)
+    if rank == 0 and args.full:
         # measured streaming ceilings of this device, next to the spec peak
         cp_bytes, cp_iters = 2 << 30, 10
         cp_ms = ahlib.bench_memcpy(device, cp_bytes, cp_iters)
@@ -1618,6 +1633,7 @@ def main():
             "cpu_baseline": dict(result["cpu"], build_10m=result.get("cpu_10m")) if result.get("cpu") else None,
             "build": result.get("build"),
             "build_10m": result.get("build_10m"),
+            "full": args.full,  # false: a plain run, the headline alone (cpu_baseline, build, build_10m and the rest: --full)
             # runtime switches this process ran under (GPU_MAX_HW_QUEUES: set at the top of this file unless the caller set it)
             "env": {k: os.environ[k] for k in ("GPU_MAX_HW_QUEUES", "HSA_ENABLE_IPC_MODE_LEGACY") if k in os.environ},
         }

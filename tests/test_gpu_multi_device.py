@@ -226,7 +226,7 @@ def test_bench_four_virtual_devices_on_one_gpu_threads():
     """`python bench.py --gpus 4 --virtual`: one process, four device threads, the 1M x 768 dataset staged once and replicated
     (ah_dataset_replicate onto the same device), every thread builds its trees t = rank (mod 4); the union of the shares'
     per-tree digests must equal a one-device build of all 100 trees (bench.py exits 6 otherwise)."""
-    out = _bench(["--gpus", "4", "--virtual", "--steps", "3", "--warmup", "1", "--no-cpu", "--no-extra", "--no-live-pmc"])
+    out = _bench(["--gpus", "4", "--virtual", "--full", "--steps", "3", "--warmup", "1", "--no-cpu", "--no-extra", "--no-live-pmc"])
     j = _check_virtual_line(out, 4)
     assert j["replicate_10m"]["replicas"] == 3 and j["replicate_10m"]["gb_per_s_total"] > 0
     assert "4 host threads" in j["config"]["launch"]
@@ -236,7 +236,8 @@ def test_bench_two_virtual_devices_one_process_per_rank():
     """The launch the driver uses for N > 1 (`python -m torch.distributed.run --nproc-per-node N bench.py --gpus N`), two ranks
     on the one GPU: each rank fills its own dataset, builds its share, rank 0 gathers the per-device figures and checks the
     union (gloo for the control path: RCCL wants one rank per device)."""
-    out = _bench(["--gpus", "2", "--virtual-devices", "--steps", "3", "--warmup", "1", "--no-cpu", "--no-extra", "--no-live-pmc"],
+    out = _bench(["--gpus", "2", "--virtual-devices", "--full", "--steps", "3", "--warmup", "1", "--no-cpu", "--no-extra",
+                  "--no-live-pmc"],
                  launcher=["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                            "--master-port", "29577"])
     j = _check_virtual_line(out, 2)
