@@ -959,6 +959,8 @@ int ah_dataset_destroy(ah_dataset *ds) {
         }
     }
     ds->pool.clear();
+    if (ds->d_packed) (void)dev_free(ds->d_packed);
+    if (ds->d_packed_exp) (void)dev_free(ds->d_packed_exp);
     if (ds->d_rows_h16) (void)dev_free(ds->d_rows_h16);
     if (ds->d_rows_i8) (void)dev_free(ds->d_rows_i8);
     if (ds->d_rows_i8_lo) (void)dev_free(ds->d_rows_i8_lo);
@@ -1934,7 +1936,8 @@ static int distances_impl(ah_dataset *ds, const float *query, const uint32_t *qu
     float *d_out = dev.take<float>(n);
     float *h_out = pin.take<float>(n);
     uint32_t *h_err = pin.take<uint32_t>(1);
-    AH_TRY(launch_distances(ds->view(), qb.d_qvec, qb.d_qhdr, d_ids, n, d_out, qb.d_err, ctx->stream));
+    const PackedView pk = d_ids ? PackedView{} : ensure_packed(ds, ctx->stream);
+    AH_TRY(launch_distances(ds->view(), qb.d_qvec, qb.d_qhdr, d_ids, n, d_out, qb.d_err, ctx->stream, pk));
     AH_HIP(hipMemcpyAsync(h_out, d_out, n * 4, hipMemcpyDeviceToHost, ctx->stream));
     AH_HIP(hipMemcpyAsync(h_err, qb.d_err, 4, hipMemcpyDeviceToHost, ctx->stream));
     AH_HIP(hipStreamSynchronize(ctx->stream));
@@ -2360,6 +2363,16 @@ int ah_dataset_rerank_stats(ah_dataset *ds, ah_rerank_stats *out, int reset) {
     AH_GUARDED_END
 }
 
+int ah_dataset_packed_info(ah_dataset *ds, int *out_present, uint64_t *out_raw_rows) {
+    AH_GUARDED("ah_dataset_packed_info")
+    AH_REQUIRE(ds, AH_ERR_INVALID_ARGUMENT, "dataset is NULL");
+    std::lock_guard<std::mutex> lk(ds->mu);
+    if (out_present) *out_present = ds->d_packed ? 1 : 0;
+    if (out_raw_rows) *out_raw_rows = ds->d_packed ? ds->packed_raw_rows : 0;
+    return AH_OK;
+    AH_GUARDED_END
+}
+
 // ---------------------------------------------------------------------------------------------
 // build side: single-node entry points (the incremental paths of arroy call these per node)
 // ---------------------------------------------------------------------------------------------
@@ -2511,9 +2524,10 @@ int ah_bench_scan(ah_dataset *ds, uint32_t query_item, uint64_t n, uint32_t iter
     AH_TRY(stage_query(ds, ctx, nullptr, &query_item, pad256(n * 4), 256, &qb, &dev, &pin));
     float *d_out = dev.take<float>(n);
     DataView dv = ds->view();
+    const PackedView pk = ensure_packed(ds, ctx->stream);  // (made by the first call, before the timed region)
     AH_HIP(hipEventRecord(ctx->ev0, ctx->stream));
     for (uint32_t it = 0; it < iterations; it++)
-        AH_TRY(launch_distances(dv, qb.d_qvec, qb.d_qhdr, nullptr, n, d_out, qb.d_err, ctx->stream));
+        AH_TRY(launch_distances(dv, qb.d_qvec, qb.d_qhdr, nullptr, n, d_out, qb.d_err, ctx->stream, pk));
     AH_HIP(hipEventRecord(ctx->ev1, ctx->stream));
     AH_HIP(hipEventSynchronize(ctx->ev1));
     float ms = 0.0f;

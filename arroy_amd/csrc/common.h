@@ -141,6 +141,7 @@ inline int guarded(const char *what, F &&f) noexcept {
     X(TAIL_NODE_ITEMS, "AH_BUILD_TAIL_NODE_ITEMS", 2) /* ... from the first node-major level on whose nodes hold at most this many x split_after items on average (2: most children are Descendants nodes) */ \
     X(TAIL_RATIO, "AH_BUILD_TAIL_RATIO", 76)    /* ... each group this many percent of the trees of the group before it (100: equal groups): a group's ids and normals take ~0.76 of the time its kernels do, and what is left after the last launch is the LAST group's */ \
     X(SCAN_BLOCKS, "AH_SCAN_BLOCKS", 0)         /* grid cap of the distance scan (0 = built-in) */                        \
+    X(SCAN_PACKED, "AH_SCAN_PACKED", -1)        /* f32 scan from the 28-bit packed copy: 0 never, 1 always, -1 where it saves bytes */ \
     X(MANHATTAN_ROWS, "AH_MANHATTAN_ROWS", 1)                                                                            \
     X(RERANK_INVERT, "AH_RERANK_INVERT", -1)    /* 0 / 1: never / always the row-major re-rank of big submissions */      \
     X(RERANK_SMALL, "AH_RERANK_SMALL", 1)       /* 0: ah_rerank_by_vector / _by_item never take the one-launch selection of short lists (k_topk_small) */ \
@@ -302,6 +303,35 @@ struct ScreenView {
     float4 max8b;
 };
 
+// Lossless 28-bit copy of the f32 rows for the ungathered scan (distance.hip: k_pack_rows / octet_reduce_packed).  Row r
+// is `pitch` bytes at rows + r * pitch: three planes of 128-byte pieces, each plane only as long as its own pieces need
+// (B = dims / 32 blocks), every piece in lane order (lane j of an octet reads bytes 16j .. 16j + 15, which hold the
+// elements 32k + 4j .. 32k + 4j + 3 of the octet_reduce_stream mapping):
+//   lo   at 0         ceil(B / 2) pieces   piece q: blocks 2q, 2q + 1    the low 16 mantissa bits of each element
+//   hi   at hi_off    ceil(B / 4) pieces   piece q: blocks 4q .. 4q + 3  sign << 7 | the top 7 mantissa bits
+//   code at code_off  ceil(B / 8) pieces   piece q: blocks 8q .. 8q + 7  4-bit exponent code, low nibble first: c < 15 is
+//                                                                        e_max - c, 15 is 0
+// Elements of a piece past block B - 1 are zeros.  row_exp[r] = e_max (the row's largest biased exponent) | kPackedZeros
+// when some element has exponent field 0, or kPackedRaw: the row holds an inf / NaN or a normal element 15 or more
+// binades below e_max and is read from rows_f32.
+static constexpr uint16_t kPackedRaw = 0xFFu;
+static constexpr uint16_t kPackedZeros = 0x100u;
+struct PackedView {
+    const uint8_t *rows = nullptr;  // nullptr: no copy, the scan reads rows_f32
+    const uint16_t *row_exp = nullptr;
+    uint32_t pitch = 0;             // bytes per row = 128 x (ceil(B / 2) + ceil(B / 4) + ceil(B / 8))
+    uint32_t hi_off = 0, code_off = 0;
+};
+// the row pitch and plane offsets of the packed copy for `dims` (a multiple of 32)
+inline PackedView packed_layout(uint32_t dims) {
+    const uint32_t b = dims / 32;
+    PackedView pk;
+    pk.hi_off = 128u * ((b + 1) / 2);
+    pk.code_off = pk.hi_off + 128u * ((b + 3) / 4);
+    pk.pitch = pk.code_off + 128u * ((b + 7) / 8);
+    return pk;
+}
+
 // One per concurrently calling host thread: a stream plus growable device / pinned scratch.
 struct Context {
     hipStream_t stream = nullptr;
@@ -380,6 +410,14 @@ struct ah_dataset {
     bool counted = false;                        // dataset_born() ran for this handle (its destroy then runs dataset_gone())
     std::thread reserve_thread;                  // ah_dataset_reserve_build: fills the device cache while records are staged
     bool replicated_through_host = false;        // ah_dataset_replicate made this replica without peer access (diagnostic)
+    // the packed copy of the rows (PackedView), built by the first ungathered f32 scan (ensure_packed); d_packed /
+    // d_packed_exp / packed_raw_rows are published like screen_ready.  packed_decided: built, found useless or unavailable
+    // — the automatic mode does not try again
+    uint8_t *d_packed = nullptr;
+    uint16_t *d_packed_exp = nullptr;
+    uint64_t packed_raw_rows = 0;
+    std::atomic<bool> packed_decided{false};
+    std::atomic<bool> packed_ready{false};
     ah_rerank_stats rr_stats{};                  // AH_RERANK_TIMING=1: where ah_rerank_batch's wall time went (under `mu`)
     double reserve_seconds = 0.0;                // ... how long that helper ran (written by it, read after the join)
     double reserve_wait_seconds = 0.0;           // ... and how long the first build then waited for it (ah_build_stats, ABI v7)
@@ -461,8 +499,13 @@ struct ContextLease {
 int launch_prepare_query(const DataView &dv, const float *d_query_f32, void *d_qvec, float *d_qhdr, hipStream_t s);
 int launch_load_item_as_query(const DataView &dv, uint32_t row, void *d_qvec, float *d_qhdr, hipStream_t s);
 // distances of `n` rows: rows given by d_ids (item ids, may be nullptr = rows 0..n-1). d_err: u32 flags.
+// pk: the packed copy for an ungathered scan (ensure_packed), ignored with d_ids
 int launch_distances(const DataView &dv, const void *d_qvec, const float *d_qhdr, const uint32_t *d_ids, uint64_t n,
-                     float *d_out, uint32_t *d_err, hipStream_t s);
+                     float *d_out, uint32_t *d_err, hipStream_t s, const PackedView &pk = PackedView{});
+// the packed copy of an f32 dataset (AH_SCAN_PACKED), made on `s` the first time it is asked for; an empty view when there is
+// none (tunable off, metric / dims without one, too few rows or no bytes saved, no memory, too many raw rows): the scan
+// then reads rows_f32 (k_distances_f32_rows)
+PackedView ensure_packed(ah_dataset *ds, hipStream_t s);
 size_t topk_scratch_bytes(uint64_t n, size_t k);
 int launch_topk(const DataView &dv, const float *d_dist, const uint32_t *d_ids, uint64_t n, size_t k, void *d_scratch,
                 uint32_t *d_out_ids, float *d_out_dist, hipStream_t s);

@@ -40,6 +40,12 @@ __device__ __forceinline__ float4 ld_stream(const float4 *p) {
     return make_float4(v.x, v.y, v.z, v.w);
 }
 
+typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ uint4 ld_stream_u4(const uint4 *p) {
+    u32x4_t v = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t *>(p));
+    return make_uint4(v.x, v.y, v.z, v.w);
+}
+
 __host__ __device__ __forceinline__ bool metric_is_bq_dev(int m) { return m >= AH_BQ_EUCLIDEAN; }
 
 template <int OP>
@@ -194,6 +200,97 @@ __device__ __forceinline__ float octet_reduce_stream(const float4 *s_b4, const f
     for (; k < blocks; k++) fma_step<OP>(acc, b4[k * 8], r4[k * 8]);
     float r = octet_finish(acc);
     return scalar_tail<OP>(r, reinterpret_cast<const float *>(s_b4), row, blocks << 5, dims);
+}
+
+// One element of a packed row (common.h: PackedView) back to its f32 bits.  lo: the dword with its low 16 mantissa bits,
+// hi: the dword with its sign / top-7 byte, nc: ~(the dword with its code); SEL puts [lo16, hi byte, hi byte] in bytes 0..3,
+// SH is the code's nibble.  base = (e_max - 15) << 23, so (15 - c) << 23 + base is the exponent e_max - c in bits 30..23.
+// ZEROS: the row has elements of exponent field 0 (code 15), whose exponent is 0 instead.
+template <bool ZEROS, uint32_t SEL, uint32_t SH>
+__device__ __forceinline__ float packed_value(uint32_t lo, uint32_t hi, uint32_t nc, uint32_t base) {
+    // Four VALU operations (two more with ZEROS).  The field extract and the insert are spelled out: written in C (or with
+    // __builtin_amdgcn_ubfe, which the optimizer turns back into shifts) they become shift / and / add / and / and / or.
+    const uint32_t a = __builtin_amdgcn_perm(hi, lo, SEL);  // v_perm_b32: bytes 0-3 of the pool are `lo`, 4-7 `hi`
+    uint32_t g, r;
+    asm("v_bfe_u32 %0, %1, %2, 4" : "=v"(g) : "v"(nc), "n"(SH));
+    uint32_t e = (g << 23) + base;  // v_lshl_add_u32
+    if (ZEROS) e = g == 0u ? 0u : e;
+    asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(r) : "s"(0x807FFFFFu), "v"(a), "v"(e));  // sign, mantissa from a; exponent from e
+    return __uint_as_float(r);
+}
+// Block 8o + T of a packed row: lane j's four elements, the same float4 octet_reduce_stream loads from the f32 row.
+template <bool ZEROS, int T>
+__device__ __forceinline__ float4 packed_block(const uint4 (&lo)[4], const uint4 (&hi)[2], const uint4 nc, uint32_t base) {
+    constexpr int P = T & 1;  // block of the lo piece
+    const uint4 l = lo[T >> 1];
+    const uint32_t l0 = P ? l.z : l.x, l1 = P ? l.w : l.y;
+    const uint4 h = hi[T >> 2];
+    const uint32_t hw = (T & 3) == 0 ? h.x : (T & 3) == 1 ? h.y : (T & 3) == 2 ? h.z : h.w;
+    const uint32_t cw = (T >> 1) == 0 ? nc.x : (T >> 1) == 1 ? nc.y : (T >> 1) == 2 ? nc.z : nc.w;
+    constexpr uint32_t S = 16u * P;  // first nibble of the block in its code dword
+    // SEL for element i: bytes 2(i & 1), 2(i & 1) + 1 of the lo dword, byte 4 + i (hi dword byte i) twice
+    return make_float4(packed_value<ZEROS, 0x04040100u, S + 0>(l0, hw, cw, base),
+                       packed_value<ZEROS, 0x05050302u, S + 4>(l0, hw, cw, base),
+                       packed_value<ZEROS, 0x06060100u, S + 8>(l1, hw, cw, base),
+                       packed_value<ZEROS, 0x07070302u, S + 12>(l1, hw, cw, base));
+}
+// octet_reduce_stream on a packed row (dims a multiple of 32, blocks = dims / 32): per 8 blocks lane j loads 7 pieces of
+// 16 B (4 lo, 2 hi, 1 code) instead of 8 float4, decodes each float4 in registers and feeds the same fma_step chain in the
+// same order — the same bits.  A last group of m < 8 blocks loads only the pieces that hold them (ceil(m / 2) lo,
+// ceil(m / 4) hi, 1 code).  hi_off / code_off: the planes' byte offsets (packed_layout), emax = the row's e_max.
+template <int OP, bool ZEROS>
+__device__ __forceinline__ float octet_reduce_packed(const float4 *s_b4, const uint8_t *prow, uint32_t hi_off, uint32_t code_off,
+                                                     uint32_t blocks, uint32_t emax, uint32_t j) {
+    const uint4 *lo4 = reinterpret_cast<const uint4 *>(prow) + j;
+    const uint4 *hi4 = reinterpret_cast<const uint4 *>(prow + hi_off) + j;
+    const uint4 *c4 = reinterpret_cast<const uint4 *>(prow + code_off) + j;
+    const float4 *b4 = s_b4 + j;
+    uint32_t base = (emax - 15u) << 23;
+    asm("" : "+v"(base));  // (opaque: otherwise (g << 23) + base is rebuilt as ((g + emax) << 23) - (15 << 23), one more add)
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    const uint32_t full = blocks / 8;
+#pragma unroll 1
+    for (uint32_t o = 0; o < full; o++) {
+        uint4 lo[4], hi[2];
+#pragma unroll
+        for (int u = 0; u < 4; u++) lo[u] = ld_stream_u4(lo4 + (4 * o + u) * 8);
+#pragma unroll
+        for (int u = 0; u < 2; u++) hi[u] = ld_stream_u4(hi4 + (2 * o + u) * 8);
+        uint4 nc = ld_stream_u4(c4 + o * 8);
+        nc = make_uint4(~nc.x, ~nc.y, ~nc.z, ~nc.w);
+        const float4 *bq = b4 + o * 64;
+        fma_step<OP>(acc, bq[0], packed_block<ZEROS, 0>(lo, hi, nc, base));
+        fma_step<OP>(acc, bq[8], packed_block<ZEROS, 1>(lo, hi, nc, base));
+        fma_step<OP>(acc, bq[16], packed_block<ZEROS, 2>(lo, hi, nc, base));
+        fma_step<OP>(acc, bq[24], packed_block<ZEROS, 3>(lo, hi, nc, base));
+        fma_step<OP>(acc, bq[32], packed_block<ZEROS, 4>(lo, hi, nc, base));
+        fma_step<OP>(acc, bq[40], packed_block<ZEROS, 5>(lo, hi, nc, base));
+        fma_step<OP>(acc, bq[48], packed_block<ZEROS, 6>(lo, hi, nc, base));
+        fma_step<OP>(acc, bq[56], packed_block<ZEROS, 7>(lo, hi, nc, base));
+    }
+    const uint32_t m = blocks - 8 * full;
+    if (m) {  // the last group of a row whose blocks are not a multiple of 8
+        const uint32_t o = full;
+        const uint4 z = make_uint4(0u, 0u, 0u, 0u);
+        uint4 lo[4] = {z, z, z, z}, hi[2] = {z, z};
+#pragma unroll
+        for (uint32_t u = 0; u < 4; u++)
+            if (2 * u < m) lo[u] = ld_stream_u4(lo4 + (4 * o + u) * 8);
+#pragma unroll
+        for (uint32_t u = 0; u < 2; u++)
+            if (4 * u < m) hi[u] = ld_stream_u4(hi4 + (2 * o + u) * 8);
+        uint4 nc = ld_stream_u4(c4 + o * 8);
+        nc = make_uint4(~nc.x, ~nc.y, ~nc.z, ~nc.w);
+        const float4 *bq = b4 + o * 64;
+        fma_step<OP>(acc, bq[0], packed_block<ZEROS, 0>(lo, hi, nc, base));
+        if (m > 1) fma_step<OP>(acc, bq[8], packed_block<ZEROS, 1>(lo, hi, nc, base));
+        if (m > 2) fma_step<OP>(acc, bq[16], packed_block<ZEROS, 2>(lo, hi, nc, base));
+        if (m > 3) fma_step<OP>(acc, bq[24], packed_block<ZEROS, 3>(lo, hi, nc, base));
+        if (m > 4) fma_step<OP>(acc, bq[32], packed_block<ZEROS, 4>(lo, hi, nc, base));
+        if (m > 5) fma_step<OP>(acc, bq[40], packed_block<ZEROS, 5>(lo, hi, nc, base));
+        if (m > 6) fma_step<OP>(acc, bq[48], packed_block<ZEROS, 6>(lo, hi, nc, base));
+    }
+    return octet_finish(acc);
 }
 
 // SSE tier (16 <= dims < 32, simple_sse.rs) and scalar tier (dims < 16, simple.rs:49-51,81-83),

@@ -96,16 +96,16 @@ __device__ __forceinline__ float f32_epilogue(float r, const float *qhdr, const 
     return r;                                 // euclidean.rs:45-47 / manhattan.rs:44-46
 }
 
-template <int METRIC, bool GATHER>
-__global__ __launch_bounds__(kBlock) void k_distances_f32(DataView dv, const float *__restrict__ qvec,
-                                                          const float *__restrict__ qhdr,
-                                                          const uint32_t *__restrict__ ids, uint64_t n,
-                                                          float *__restrict__ out, uint32_t *err) {
+// PACKED (ungathered only): rows with a packed copy (PackedView) are read from it, raw rows from rows_f32, octet by octet.
+// Without it the kernel is the plain f32 scan — a separate instantiation, so that scans with no copy keep its registers
+// (62 VGPRs, 8 waves per SIMD; the packed one needs 98).
+template <int METRIC, bool GATHER, bool PACKED>
+__device__ __forceinline__ void f32_scan(const DataView &dv, const PackedView &pk, float4 *s_q4, float *s_hdr,
+                                         const float *__restrict__ qvec, const float *__restrict__ qhdr,
+                                         const uint32_t *__restrict__ ids, uint64_t n, float *__restrict__ out, uint32_t *err) {
     constexpr int OP = METRIC == AH_EUCLIDEAN ? OP_EUCLID : OP_DOT;
-    extern __shared__ float4 s_q4[];
     const uint32_t nq4 = dv.pitch >> 2;
     for (uint32_t i = threadIdx.x; i < nq4; i += blockDim.x) s_q4[i] = reinterpret_cast<const float4 *>(qvec)[i];
-    __shared__ float s_hdr[2];
     if (threadIdx.x < 2) s_hdr[threadIdx.x] = qhdr[threadIdx.x];
     __syncthreads();
     const float *s_q = reinterpret_cast<const float *>(s_q4);
@@ -129,11 +129,40 @@ __global__ __launch_bounds__(kBlock) void k_distances_f32(DataView dv, const flo
         float r;
         if (METRIC == AH_MANHATTAN) {
             r = octet_manhattan(s_q, rp, dv.dims, j);
+        } else if constexpr (PACKED) {
+            const uint32_t ex = pk.row_exp[row];
+            const uint8_t *pr = pk.rows + row * pk.pitch;
+            if (ex == kPackedRaw)
+                r = octet_reduce_stream<OP>(s_q4, rp, dv.dims, j);
+            else if (ex & kPackedZeros)
+                r = octet_reduce_packed<OP, true>(s_q4, pr, pk.hi_off, pk.code_off, dv.dims >> 5, ex & 0xFFu, j);
+            else
+                r = octet_reduce_packed<OP, false>(s_q4, pr, pk.hi_off, pk.code_off, dv.dims >> 5, ex, j);
         } else {
             r = octet_reduce_stream<OP>(s_q4, rp, dv.dims, j);
         }
         if (j == 0) out[i] = f32_epilogue<METRIC>(r, s_hdr, dv, row);
     }
+}
+
+// <M, true>: gather from the f32 rows.  <M, false>: the ungathered scan with a packed copy (the headline kernel; launched
+// only when pk holds one).  k_distances_f32_rows<M>: the ungathered scan of the f32 rows.
+template <int METRIC, bool GATHER>
+__global__ __launch_bounds__(kBlock) void k_distances_f32(DataView dv, PackedView pk, const float *__restrict__ qvec,
+                                                          const float *__restrict__ qhdr,
+                                                          const uint32_t *__restrict__ ids, uint64_t n,
+                                                          float *__restrict__ out, uint32_t *err) {
+    extern __shared__ float4 s_q4[];
+    __shared__ float s_hdr[2];
+    f32_scan<METRIC, GATHER, !GATHER>(dv, pk, s_q4, s_hdr, qvec, qhdr, ids, n, out, err);
+}
+template <int METRIC>
+__global__ __launch_bounds__(kBlock) void k_distances_f32_rows(DataView dv, const float *__restrict__ qvec,
+                                                               const float *__restrict__ qhdr, uint64_t n,
+                                                               float *__restrict__ out, uint32_t *err) {
+    extern __shared__ float4 s_q4[];
+    __shared__ float s_hdr[2];
+    f32_scan<METRIC, false, false>(dv, PackedView{}, s_q4, s_hdr, qvec, qhdr, nullptr, n, out, err);
 }
 
 // Manhattan scan / gather, dims >= 32.  `built_distance` is a strictly sequential sum (src/distance/manhattan.rs:44-46):
@@ -394,7 +423,7 @@ __global__ __launch_bounds__(kBlock) void k_distances_bq_wide(DataView dv, const
 
 template <bool GATHER>
 static int launch_distances_t(const DataView &dv, const void *qvec, const float *qhdr, const uint32_t *ids, uint64_t n,
-                              float *out, uint32_t *err, hipStream_t s) {
+                              float *out, uint32_t *err, hipStream_t s, const PackedView &pk) {
     if (n == 0) return AH_OK;
     if (metric_is_bq(dv.metric)) {
         const uint32_t C = dv.pitch >> 1;
@@ -409,9 +438,15 @@ static int launch_distances_t(const DataView &dv, const void *qvec, const float 
     } else if (dv.dims >= 32) {
         const unsigned g = grid_for(n, kBlock / 8);
         const size_t sh = (size_t)dv.pitch * 4;
-#define AH_LAUNCH_F32(M)                                                                                          \
-    hipLaunchKernelGGL((k_distances_f32<M, GATHER>), dim3(g), dim3(kBlock), sh, s, dv, (const float *)qvec, qhdr, \
-                       ids, n, out, err)
+#define AH_LAUNCH_F32(M)                                                                                               \
+    do {                                                                                                               \
+        if (GATHER || (pk.rows && M != AH_MANHATTAN))                                                                  \
+            hipLaunchKernelGGL((k_distances_f32<M, GATHER>), dim3(g), dim3(kBlock), sh, s, dv, pk, (const float *)qvec, \
+                               qhdr, ids, n, out, err);                                                                \
+        else                                                                                                           \
+            hipLaunchKernelGGL((k_distances_f32_rows<M>), dim3(g), dim3(kBlock), sh, s, dv, (const float *)qvec, qhdr, \
+                               n, out, err);                                                                           \
+    } while (0)
         switch (dv.metric) {
         case AH_EUCLIDEAN: AH_LAUNCH_F32(AH_EUCLIDEAN); break;
         case AH_MANHATTAN:
@@ -443,9 +478,148 @@ static int launch_distances_t(const DataView &dv, const void *qvec, const float 
 }
 
 int launch_distances(const DataView &dv, const void *d_qvec, const float *d_qhdr, const uint32_t *d_ids, uint64_t n,
-                     float *d_out, uint32_t *d_err, hipStream_t s) {
-    return d_ids ? launch_distances_t<true>(dv, d_qvec, d_qhdr, d_ids, n, d_out, d_err, s)
-                 : launch_distances_t<false>(dv, d_qvec, d_qhdr, nullptr, n, d_out, d_err, s);
+                     float *d_out, uint32_t *d_err, hipStream_t s, const PackedView &pk) {
+    return d_ids ? launch_distances_t<true>(dv, d_qvec, d_qhdr, d_ids, n, d_out, d_err, s, PackedView{})
+                 : launch_distances_t<false>(dv, d_qvec, d_qhdr, nullptr, n, d_out, d_err, s, pk);
+}
+
+// ------------------------------------------------------------------------------------------------
+// The packed copy of the rows (common.h: PackedView).  One octet per row, lane j on the elements octet_reduce_packed gives
+// it: a first pass finds e_max, the smallest exponent of a normal element, inf / NaN and exponent-0 elements; a second
+// writes lane j's 16-byte share of every piece (elements past the last block as zeros).  Raw rows get only their row_exp.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kBlock) void k_pack_rows(DataView dv, uint8_t *__restrict__ rows, uint16_t *__restrict__ row_exp,
+                                                      PackedView lay, unsigned long long *raw_rows) {
+    const uint32_t j = threadIdx.x & 7u;
+    const uint32_t blocks = dv.dims >> 5;
+    const uint64_t n_octets = ((uint64_t)gridDim.x * blockDim.x) >> 3;
+    uint32_t raw_here = 0;
+    for (uint64_t r = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 3; r < dv.n; r += n_octets) {
+        const float4 *src = reinterpret_cast<const float4 *>(dv.rows_f32 + r * dv.pitch) + j;
+        uint32_t emax = 0, emin = 255, special = 0, zeros = 0;
+        for (uint32_t k = 0; k < blocks; k++) {
+            const float4 x = src[k * 8];
+            const float v[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                const uint32_t e = (__float_as_uint(v[i]) >> 23) & 255u;
+                emax = max(emax, e);
+                if (e != 0u) emin = min(emin, e);
+                special |= e == 255u;
+                zeros |= e == 0u;
+            }
+        }
+#pragma unroll
+        for (int m = 1; m < 8; m <<= 1) {  // (the lanes of one octet: xor 1, 2, 4 stays inside it)
+            emax = max(emax, (uint32_t)__shfl_xor((int)emax, m));
+            emin = min(emin, (uint32_t)__shfl_xor((int)emin, m));
+            special |= (uint32_t)__shfl_xor((int)special, m);
+            zeros |= (uint32_t)__shfl_xor((int)zeros, m);
+        }
+        const bool raw = special || (int)emax - (int)emin >= 15;
+        if (j == 0) row_exp[r] = raw ? kPackedRaw : (uint16_t)(emax | (zeros ? kPackedZeros : 0u));
+        if (raw) {
+            raw_here += j == 0;
+            continue;
+        }
+        uint8_t *dst = rows + r * lay.pitch;
+        for (uint32_t o = 0; o < (blocks + 7) / 8; o++) {
+            uint32_t lo[16], hi[8], cd[4];
+#pragma unroll
+            for (int w = 0; w < 16; w++) lo[w] = 0u;
+#pragma unroll
+            for (int w = 0; w < 8; w++) hi[w] = 0u;
+#pragma unroll
+            for (int w = 0; w < 4; w++) cd[w] = 0u;
+#pragma unroll
+            for (int t = 0; t < 8; t++) {
+                const uint32_t k = 8 * o + t;
+                const float4 x = k < blocks ? src[k * 8] : make_float4(0.f, 0.f, 0.f, 0.f);
+                const float v[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+                for (int i = 0; i < 4; i++) {
+                    const uint32_t b = __float_as_uint(v[i]);
+                    const uint32_t e = (b >> 23) & 255u;
+                    const uint32_t c = e == 0u ? 15u : emax - e;
+                    const int u = (t & 1) * 4 + i;  // element of the lo piece / nibble of the code dword
+                    lo[(t >> 1) * 4 + u / 2] |= (b & 0xFFFFu) << (16 * (u & 1));
+                    hi[t] |= (((b >> 24) & 0x80u) | ((b >> 16) & 0x7Fu)) << (8 * i);
+                    cd[t >> 1] |= c << (4 * u);
+                }
+            }
+            uint4 *lo4 = reinterpret_cast<uint4 *>(dst) + j;
+            uint4 *hi4 = reinterpret_cast<uint4 *>(dst + lay.hi_off) + j;
+            uint4 *c4 = reinterpret_cast<uint4 *>(dst + lay.code_off) + j;
+            // (only the pieces that hold a block: the planes end there)
+#pragma unroll
+            for (uint32_t u = 0; u < 4; u++)
+                if (8 * o + 2 * u < blocks) lo4[(4 * o + u) * 8] = make_uint4(lo[4 * u], lo[4 * u + 1], lo[4 * u + 2], lo[4 * u + 3]);
+#pragma unroll
+            for (uint32_t u = 0; u < 2; u++)
+                if (8 * o + 4 * u < blocks) hi4[(2 * o + u) * 8] = make_uint4(hi[4 * u], hi[4 * u + 1], hi[4 * u + 2], hi[4 * u + 3]);
+            c4[o * 8] = make_uint4(cd[0], cd[1], cd[2], cd[3]);
+        }
+    }
+    if (raw_here) atomicAdd(raw_rows, (unsigned long long)raw_here);
+}
+
+static int launch_pack_rows(const DataView &dv, uint8_t *rows, uint16_t *row_exp, const PackedView &lay,
+                            unsigned long long *d_raw, hipStream_t s) {
+    const unsigned grid = (unsigned)std::min<uint64_t>((dv.n + 31) / 32, 1u << 16);
+    hipLaunchKernelGGL(k_pack_rows, dim3(grid), dim3(kBlock), 0, s, dv, rows, row_exp, lay, d_raw);
+    AH_HIP(hipGetLastError());
+    return AH_OK;
+}
+
+// The packed copy of the rows for the ungathered scan (common.h: PackedView), made by the first scan that asks and kept until the
+// dataset goes.  AH_SCAN_PACKED=-1 makes it only where it pays: from 64 Ki rows, and only when a packed row (pitch + 2 B of
+// row_exp) is at most 15/16 of the f32 row — 768 dims: 2690 B of 3072, 384: 1410 of 1536; never at 32 .. 160 dims, where
+// the pieces' rounding eats the saving — and keeps it while at most a quarter of the rows are raw.  1 makes and keeps it
+// for any Cosine / Euclidean / DotProduct dataset with dims % 32 == 0, whatever the size and the data.  The cheap checks
+// come before the dataset lock; a decision against the copy (or a failed allocation) is remembered by the automatic mode.
+static constexpr uint64_t kPackedMinRows = 65536;
+static bool packed_pays(uint32_t dims) { return 16ull * (packed_layout(dims).pitch + 2) <= 15ull * 4 * dims; }
+PackedView ensure_packed(ah_dataset *ds, hipStream_t s) {
+    const long long mode = tun(TUN_SCAN_PACKED);
+    if (mode == 0) return PackedView{};
+    PackedView pk = packed_layout(ds->dims);
+    if (!ds->packed_ready.load(std::memory_order_acquire)) {
+        if (ds->metric != AH_COSINE && ds->metric != AH_EUCLIDEAN && ds->metric != AH_DOT_PRODUCT) return PackedView{};
+        if (ds->dims < 32 || ds->dims % 32 != 0 || ds->n == 0) return PackedView{};
+        if (mode != 1 && (ds->packed_decided.load(std::memory_order_acquire) || ds->n < kPackedMinRows || !packed_pays(ds->dims)))
+            return PackedView{};
+        std::lock_guard<std::mutex> lk(ds->mu);
+        if (!ds->d_packed) {
+            if (mode != 1 && ds->packed_decided.load(std::memory_order_relaxed)) return PackedView{};  // (decided meanwhile)
+            ds->packed_decided.store(true, std::memory_order_release);
+            uint8_t *rows = nullptr;
+            uint16_t *row_exp = nullptr;
+            unsigned long long *d_raw = nullptr, h_raw = 0;
+            // (optional allocations: a full device does not make them empty the cache)
+            bool ok = dev_malloc((void **)&rows, ds->n * (size_t)pk.pitch, true) == hipSuccess &&
+                      dev_malloc((void **)&row_exp, ds->n * 2, true) == hipSuccess &&
+                      dev_malloc((void **)&d_raw, 8, true) == hipSuccess && hipMemsetAsync(d_raw, 0, 8, s) == hipSuccess;
+            ok = ok && launch_pack_rows(ds->view(), rows, row_exp, pk, d_raw, s) == AH_OK;
+            ok = ok && hipMemcpyAsync(&h_raw, d_raw, 8, hipMemcpyDeviceToHost, s) == hipSuccess;
+            // (other contexts' streams read the copy once it is published: it is complete before that)
+            ok = hipStreamSynchronize(s) == hipSuccess && ok;
+            ok = ok && (mode == 1 || h_raw <= ds->n / 4);
+            if (d_raw) (void)dev_free(d_raw);
+            if (!ok) {
+                (void)hipGetLastError();
+                if (rows) (void)dev_free(rows);
+                if (row_exp) (void)dev_free(row_exp);
+                return PackedView{};
+            }
+            ds->d_packed = rows;
+            ds->d_packed_exp = row_exp;
+            ds->packed_raw_rows = h_raw;
+            ds->packed_ready.store(true, std::memory_order_release);
+        }
+    }
+    pk.rows = ds->d_packed;
+    pk.row_exp = ds->d_packed_exp;
+    return pk;
 }
 
 int launch_prepare_query(const DataView &dv, const float *d_query_f32, void *d_qvec, float *d_qhdr, hipStream_t s) {

@@ -63,12 +63,6 @@ __device__ __forceinline__ int dot16_i8(const uint4 a, const uint4 b, int acc) {
     return acc;
 }
 
-typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ uint4 ld_stream_u4(const uint4 *p) {
-    u32x4_t v = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t *>(p));
-    return make_uint4(v.x, v.y, v.z, v.w);
-}
-
 // sum over the 8 lanes of an octet (any order: the screen's accumulation error is covered by gamma_s)
 __device__ __forceinline__ float octet_sum(float v) {
     v += dpp_f32<0xB1>(v);   // lane ^ 1

@@ -169,6 +169,12 @@ class Dataset:
         _lib.check(_lib.lib().ah_dataset_rerank_stats(self._h, C.byref(st), 1 if reset else 0))
         return {f: getattr(st, f) for f, _ in _lib.AhRerankStats._fields_}
 
+    def packed_info(self) -> dict:
+        """ah_dataset_packed_info: whether the scan's packed copy of the rows exists, and how many of its rows stay f32."""
+        present, raw = C.c_int(0), C.c_uint64(0)
+        _lib.check(_lib.lib().ah_dataset_packed_info(self._h, C.byref(present), C.byref(raw)))
+        return {"present": bool(present.value), "raw_rows": raw.value}
+
     # -- build side --------------------------------------------------------------------------------
     def split_sides(self, normal_vector: np.ndarray, normal_header, sorted_ids=None, want_margins: bool = True):
         """The margin loop (src/writer.rs:1201-1207). Returns (sides u8 per item, n_left, margins)."""

@@ -212,6 +212,10 @@ typedef struct ah_rerank_stats {
     uint64_t chunks_int8_retried; /* ... that left more survivors than the selection holds and ran again on binary16 rows */
 } ah_rerank_stats;
 AH_API int ah_dataset_rerank_stats(ah_dataset *ds, ah_rerank_stats *out, int reset);
+/* The packed copy of the rows that the ungathered f32 scan reads (tunable AH_SCAN_PACKED): *out_present = 1 when it exists,
+ * *out_raw_rows = its rows kept in f32 (an inf / NaN, or an exponent spread of 15 binades or more).  Either pointer may be
+ * NULL.  Made by the first ah_distances_by_* / ah_bench_scan call over all rows, never by a build or a search. */
+AH_API int ah_dataset_packed_info(ah_dataset *ds, int *out_present, uint64_t *out_raw_rows);
 
 /* ------------------------------------------------------------------------------------------
  * Build side (src/writer.rs:1193-1233, 1398-1531; src/distance/mod.rs:126-223)
