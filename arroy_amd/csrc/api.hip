@@ -967,6 +967,7 @@ int ah_dataset_destroy(ah_dataset *ds) {
     if (ds->d_scale8_rows) (void)dev_free(ds->d_scale8_rows);
     if (ds->d_dim_scale) (void)dev_free(ds->d_dim_scale);
     if (ds->d_screen_stats) (void)dev_free(ds->d_screen_stats);
+    if (ds->d_query_verify) (void)dev_free(ds->d_query_verify);
     if (ds->d_rows_f32) (void)dev_free(ds->d_rows_f32);
     if (ds->d_rows_bq) (void)dev_free(ds->d_rows_bq);
     if (ds->d_headers) (void)dev_free(ds->d_headers);
@@ -2171,20 +2172,24 @@ static int rerank_batch_chunk(ah_dataset *ds, Context *ctx, const float *queries
     uint32_t *h_err = pin.take<uint32_t>(16);  // [error bits][the selection's counters: words 9, 10 of search.hip's SearchStatSlot]
     // More survivors than the selection holds (bit 3) on the int8 stage is not a reason to leave the screen: the same lists once
     // more on the binary16 rows.  A dataset where that keeps happening (candidates closer together than the int8 error) stops
-    // trying: `rerank8_off` after 8 such submissions out of the last <= 64.
+    // trying: `rerank8_off` after 8 such sub-batches within one window of 64 the stage served (screen8_window_note).
     bool retried8 = false;
     auto note_screened = [&](const uint32_t *words) {  // ah_rerank_stats: how the screen went (always kept: three additions)
         std::lock_guard<std::mutex> lk(ds->mu);
         ds->rr_stats.queries_screened += words[9];
         ds->rr_stats.survivors += words[10];
         ds->rr_stats.chunks_int8 += screened8 && !retried8 ? 1 : 0;
-        ds->rr_stats.chunks_int8_retried += retried8 ? 1 : 0;
     };
     auto retry_on_binary16 = [&](uint32_t err_bits) -> int {
-        if (!screened8 || (err_bits & ~1u) != 8u) return AH_OK;
+        if (!screened8) return AH_OK;
+        const bool overflow = (err_bits & ~1u) == 8u;
+        if (screen8_window_note(ds->rerank8_seen, ds->rerank8_fails, overflow)) ds->rerank8_off.store(true, std::memory_order_relaxed);
+        if (!overflow) return AH_OK;
         retried8 = true;
-        const uint32_t fails = ds->rerank8_fails.fetch_add(1, std::memory_order_relaxed) + 1;
-        if (fails >= 8) ds->rerank8_off.store(true, std::memory_order_relaxed);
+        {  // (counted whatever the retry leads to: a retry that ends on the exact path ran all the same)
+            std::lock_guard<std::mutex> lk(ds->mu);
+            ds->rr_stats.chunks_int8_retried += 1;
+        }
         AH_HIP(hipMemsetAsync(d_err, 0, 64, ctx->stream));
         AH_TRY(launch_rerank_screened(ds, (uint32_t)nq, d_qvecs, qstride, d_qhdrs, d_segs, d_tiles, 0u, (uint32_t)tiles.size(), tc, d_ids,
                                       d_dist, d_aux, d_q16, d_qstats, (uint32_t)k, d_oi, d_od, d_err, ctx->stream, true, true));
@@ -2246,6 +2251,7 @@ static int rerank_batch_chunk(ah_dataset *ds, Context *ctx, const float *queries
         AH_HIP(hipMemcpyAsync(h_od, d_od, nq * k * 4, hipMemcpyDeviceToHost, s));
         AH_HIP(hipMemcpyAsync(h_err, d_err, 64, hipMemcpyDeviceToHost, s));
         AH_RR_SYNC(s);
+        AH_TRY(check_err_flags(*h_err, true));  // a missing id or a list that is not ascending and unique: no other pass changes that
         AH_TRY(retry_on_binary16(*h_err));
         if ((*h_err & ~1u) == 0) {
             note_screened(h_err);
@@ -2283,6 +2289,7 @@ static int rerank_batch_chunk(ah_dataset *ds, Context *ctx, const float *queries
         AH_HIP(hipMemcpyAsync(h_od, d_od, nq * k * 4, hipMemcpyDeviceToHost, s));
         AH_HIP(hipMemcpyAsync(h_err, d_err, 64, hipMemcpyDeviceToHost, s));
         AH_RR_SYNC(s);
+        AH_TRY(check_err_flags(*h_err, true));  // a missing id or a list that is not ascending and unique: no other pass changes that
         AH_TRY(retry_on_binary16(*h_err));
         if ((*h_err & ~1u) == 0) {
             note_screened(h_err);
@@ -2369,6 +2376,25 @@ int ah_dataset_packed_info(ah_dataset *ds, int *out_present, uint64_t *out_raw_r
     std::lock_guard<std::mutex> lk(ds->mu);
     if (out_present) *out_present = ds->d_packed ? 1 : 0;
     if (out_raw_rows) *out_raw_rows = ds->d_packed ? ds->packed_raw_rows : 0;
+    return AH_OK;
+    AH_GUARDED_END
+}
+
+int ah_debug_query_screen_verify(ah_dataset *ds, uint64_t *out_checked, uint64_t *out_violations, int reset) {
+    AH_GUARDED("ah_debug_query_screen_verify")
+    AH_REQUIRE(ds, AH_ERR_INVALID_ARGUMENT, "dataset is NULL");
+    DeviceRestore restore;
+    std::lock_guard<std::mutex> lk(ds->mu);
+    unsigned long long c[2] = {0ull, 0ull};
+    if (ds->d_query_verify) {
+        // (the kernels that add to the counters run on the dataset's streams; the caller's submissions have returned)
+        AH_HIP(hipSetDevice(ds->device));
+        AH_HIP(hipDeviceSynchronize());
+        AH_HIP(hipMemcpy(c, ds->d_query_verify, 16, hipMemcpyDeviceToHost));
+        if (reset) AH_HIP(hipMemset(ds->d_query_verify, 0, 16));
+    }
+    if (out_checked) *out_checked = c[0];
+    if (out_violations) *out_violations = c[1];
     return AH_OK;
     AH_GUARDED_END
 }

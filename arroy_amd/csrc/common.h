@@ -357,6 +357,19 @@ struct Context {
     void destroy();
 };
 
+// The int8 first stage of the certified top-k screen switches itself off for a dataset (ah_rerank_batch) or an index
+// (ah_search_batch) after 8 sub-batches whose selection it overflowed within one window of 64 sub-batches it served.
+// `seen` counts the sub-batches of the current window, `fails` its overflows; both restart at every 64th.  Returns true
+// when the stage should be switched off.
+inline bool screen8_window_note(std::atomic<uint32_t> &seen, std::atomic<uint32_t> &fails, bool failed) {
+    const bool off = failed && fails.fetch_add(1, std::memory_order_relaxed) + 1 >= 8;
+    if (seen.fetch_add(1, std::memory_order_relaxed) + 1 >= 64) {
+        seen.store(0, std::memory_order_relaxed);
+        fails.store(0, std::memory_order_relaxed);
+    }
+    return off;
+}
+
 }  // namespace ah
 
 struct ah_dataset {
@@ -395,7 +408,8 @@ struct ah_dataset {
     // the copies above are published: d_rows_h16 / d_screen_stats / hpitch / screen_max are final and may be read without
     // `mu` (store-release in ensure_screen after the last of them is written, load-acquire by the search paths)
     std::atomic<bool> screen_ready{false};
-    std::atomic<uint32_t> rerank8_fails{0};      // ah_rerank_batch submissions whose int8 stage left too many survivors
+    std::atomic<uint32_t> rerank8_fails{0};      // ah_rerank_batch sub-batches whose int8 stage left too many survivors ...
+    std::atomic<uint32_t> rerank8_seen{0};       // ... among this many it served (screen8_window_note: windows of 64)
     std::atomic<bool> rerank8_off{false};        // ... often enough that the dataset's re-rank starts on the binary16 rows from now on
     std::atomic<bool> screen8_ready{false};      // ... and d_rows_i8 / d_scale8_rows / d_dim_scale / pitch8 / screen8_max likewise
     // staging in flight (ah_dataset_upload_*): the context whose stream / pinned ring the uploads use until
@@ -418,6 +432,9 @@ struct ah_dataset {
     uint64_t packed_raw_rows = 0;
     std::atomic<bool> packed_decided{false};
     std::atomic<bool> packed_ready{false};
+    // AH_SCREEN_VERIFY=1: {candidates checked, candidates whose reference distance fell outside [L, U]} of the search and
+    // re-rank screens (k_screen_verify, search.hip), allocated by the first verified submission (ah_debug_query_screen_verify)
+    unsigned long long *d_query_verify = nullptr;
     ah_rerank_stats rr_stats{};                  // AH_RERANK_TIMING=1: where ah_rerank_batch's wall time went (under `mu`)
     double reserve_seconds = 0.0;                // ... how long that helper ran (written by it, read after the join)
     double reserve_wait_seconds = 0.0;           // ... and how long the first build then waited for it (ah_build_stats, ABI v7)

@@ -2715,7 +2715,8 @@ __global__ __launch_bounds__(256) void k_pairs_screen16(DataView dv, ScreenSearc
     const uint32_t j = threadIdx.x & 7u, steps = ss.hpitch >> 6;
     const uint32_t end = min(seg.n, tl.first + tile_candidates);
     for (uint32_t c = tl.first + (threadIdx.x >> 3); c < end; c += blockDim.x >> 3) {
-        const uint64_t row = row_of_id(dv, ids[seg.off + c]);
+        const uint32_t id = ids[seg.off + c];
+        const uint64_t row = row_of_id(dv, id);
         const bool missing = row == ~0ull;
         const uint4 *r4 = reinterpret_cast<const uint4 *>(ss.rows16 + (missing ? 0ull : row) * ss.hpitch) + j;
         float a0 = 0.f, a1 = 0.f;
@@ -2734,6 +2735,7 @@ __global__ __launch_bounds__(256) void k_pairs_screen16(DataView dv, ScreenSearc
         const float sdot = octet_sum(a0 + a1);
         if (j == 0) {
             if (missing) atomicOr(err, 1u);
+            if (c > 0 && id <= ids[seg.off + c - 1]) atomicOr(err, 2u);  // ascending and unique, as k_batch_distances_f32 checks
             dist[seg.off + c] = missing ? __uint_as_float(0x7FC00000u) : sdot;
             if (ss.aux) ss.aux[seg.off + c] = missing ? 0.0f : dv.headers[row];
         }
@@ -2756,7 +2758,8 @@ __global__ __launch_bounds__(256) void k_pairs_screen8(DataView dv, ScreenSearch
     const float s_q = ss.q8stats[tl.query].x;
     const uint32_t end = min(seg.n, tl.first + tile_candidates);
     for (uint32_t c = tl.first + (threadIdx.x >> 3); c < end; c += blockDim.x >> 3) {
-        const uint64_t row = row_of_id(dv, ids[seg.off + c]);
+        const uint32_t id = ids[seg.off + c];
+        const uint64_t row = row_of_id(dv, id);
         const bool missing = row == ~0ull;
         const uint4 *r4 = reinterpret_cast<const uint4 *>(ss.rows8 + (missing ? 0ull : row) * ss.pitch8) + j;
         int h0 = 0, h1 = 0, l0 = 0, l1 = 0;
@@ -2781,6 +2784,7 @@ __global__ __launch_bounds__(256) void k_pairs_screen8(DataView dv, ScreenSearch
         const float v = octet_sum((float)(h0 + h1) + (float)(l0 + l1) * 0.00390625f);
         if (j == 0) {
             if (missing) atomicOr(err, 1u);
+            if (c > 0 && id <= ids[seg.off + c - 1]) atomicOr(err, 2u);
             const float s_r = missing ? 0.0f : ss.row_scale8[row];
             dist[seg.off + c] = missing ? __uint_as_float(0x7FC00000u) : (v * s_q) * s_r;  // (inf scale x 0 digits = NaN: not screened)
             ss.aux8[seg.off + c] = s_r;
@@ -2806,6 +2810,16 @@ __device__ __forceinline__ void screened_bounds(float sdot, float e_query, float
         lo = cosine_from_dot(r_hi, qn, xn);
         hi = cosine_from_dot(r_lo, qn, xn);
     }
+}
+
+// The int8 stage's bound of one candidate: the query's A_q times the row's scale s_r, plus the rounding of s itself.
+__device__ __forceinline__ float screen8_error(float a8, float sr, float sdot) { return a8 * sr + 1.3e-7f * fabsf(sdot); }
+// L and U of one candidate from its screen value: its own int8 bound when the value came from the int8 rows (s8 and sr >= 0),
+// the query's binary16 bound e_query otherwise.  The selection and k_screen_verify both take their bounds from here.
+template <int METRIC>
+__device__ __forceinline__ void candidate_bounds(bool s8, float sdot, float sr, float a8, float e_query, float qn, float xn,
+                                                 float &lo, float &hi) {
+    screened_bounds<METRIC>(sdot, (s8 && !(sr < 0.0f)) ? screen8_error(a8, sr, sdot) : e_query, qn, xn, lo, hi);
 }
 
 // Selection of k_search_select with the screen in front: `dist_all` holds the SCREEN dot products of the candidates.
@@ -2890,7 +2904,7 @@ __device__ __forceinline__ void search_select_screened_body(DataView dv, ScreenS
             return false;
         }
         float lo, hi;
-        screened_bounds<METRIC>(sdot, (s8 && !(sr < 0.0f)) ? a8 * sr + 1.3e-7f * fabsf(sdot) : e_query, qn, xn, lo, hi);
+        candidate_bounds<METRIC>(s8, sdot, sr, a8, e_query, qn, xn, lo, hi);
         ukey = orderable_key(hi);
         lkey = orderable_key(lo);
         return true;
@@ -3129,6 +3143,88 @@ __global__ __launch_bounds__(1024) void k_search_select_screened(DataView dv, Sc
             }
         }
     }
+}
+
+// AH_SCREEN_VERIFY=1 (a test aid; the host launches it only under that tunable, in front of the selection, which it leaves as
+// it is): every candidate with a finite screen value is also evaluated in the reference's f32 arithmetic — the chain the
+// selection runs for its survivors — and checked against the [L, U] the selection derives from its screen value (the same
+// device functions).  out[0] += candidates checked, out[1] += candidates outside their interval.  The candidates are laid out
+// as for the selection (`segs`: the lists of ah_rerank_batch; otherwise slots of `stride`, `counts[q]` each, flagged
+// duplicates 0xFFFFFFFF).  Grid (blocks per query, queries), one octet per candidate, the query's f32 leaf in LDS.
+template <int METRIC>
+__global__ __launch_bounds__(256) void k_screen_verify(DataView dv, ScreenSearch ss, const uint32_t *__restrict__ nns,
+                                                       const float *__restrict__ dist_all, uint32_t stride,
+                                                       const uint32_t *__restrict__ counts, const PairSeg *__restrict__ segs,
+                                                       const uint8_t *__restrict__ qvecs, uint64_t qstride,
+                                                       const float *__restrict__ qhdrs, unsigned long long *__restrict__ out) {
+    extern __shared__ float4 s_qf4[];  // the query leaf in f32 (row pitch)
+    __shared__ uint32_t s_checked, s_bad;
+    const uint32_t q = blockIdx.y, tid = threadIdx.x, j = tid & 7u;
+    const uint64_t first = segs ? segs[q].off : (uint64_t)q * stride;
+    const uint32_t n = segs ? segs[q].n : counts[q];
+    const float4 *g_q4 = reinterpret_cast<const float4 *>(qvecs + (uint64_t)q * qstride);
+    for (uint32_t i = tid; i < (dv.pitch >> 2); i += blockDim.x) s_qf4[i] = g_q4[i];
+    if (tid == 0) s_checked = s_bad = 0u;
+    __syncthreads();
+    const float qn = qhdrs[2 * (uint64_t)q];
+    const bool s8 = ss.aux8 != nullptr;
+    const float e_query = ss.qstats ? screened_error(ss.max_stats, ss.qstats[q], ss.gamma_s, ss.gamma_r) : 0.0f;
+    const float a8 = s8 ? ss.q8stats[q].y : 0.0f;
+    uint32_t checked = 0, bad = 0;
+    const uint32_t octets = blockDim.x >> 3;
+    for (uint32_t c = blockIdx.x * octets + (tid >> 3); c < n; c += gridDim.x * octets) {  // (every test below is octet-uniform)
+        const uint32_t id = nns[first + c];
+        const float sdot = dist_all[first + c];
+        if (!segs && id == 0xFFFFFFFFu) continue;  // a flagged duplicate
+        if (!(fabsf(sdot) <= 3.0e38f)) continue;   // not screened: the selection sends the submission to the exact path
+        const uint64_t row = row_of_id(dv, id);
+        if (row == ~0ull) continue;
+        float lo, hi;
+        candidate_bounds<METRIC>(s8, sdot, s8 ? ss.aux8[first + c] : 0.0f, a8, e_query, qn,
+                                 METRIC == AH_COSINE ? ss.aux[first + c] : 0.0f, lo, hi);
+        if (lo != lo || hi != hi) continue;  // a NaN bound (a NaN norm or maximum): the selection sends the submission to the exact path
+        const float r = octet_reduce_stream<OP_DOT, 16, true>(s_qf4, dv.rows_f32 + row * dv.pitch, dv.dims, j);
+        const float d = METRIC == AH_COSINE ? cosine_from_dot(r, qn, dv.headers[row]) : -r;
+        if (j == 0) {
+            checked++;
+            if (!(lo <= d && d <= hi)) bad++;
+        }
+    }
+    if (checked) atomicAdd(&s_checked, checked);
+    if (bad) atomicAdd(&s_bad, bad);
+    __syncthreads();
+    if (tid == 0 && s_checked) atomicAdd(&out[0], (unsigned long long)s_checked);
+    if (tid == 0 && s_bad) atomicAdd(&out[1], (unsigned long long)s_bad);
+}
+
+// Launches k_screen_verify over a screened submission when AH_SCREEN_VERIFY is 1 (otherwise nothing).  The counters live in
+// the dataset (ah_debug_query_screen_verify) and are made by the first verified submission.
+static int launch_screen_verify(ah_dataset *ds, const ScreenSearch &ss, const uint32_t *nns, const float *dist, uint32_t stride,
+                                const uint32_t *counts, const PairSeg *segs, uint32_t nq, const uint8_t *qvecs, uint64_t qstride,
+                                const float *qhdrs, hipStream_t s) {
+    if (tun(TUN_SCREEN_VERIFY) == 0 || nq == 0) return AH_OK;
+    unsigned long long *ctr = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(ds->mu);
+        if (!ds->d_query_verify) {
+            AH_HIP(dev_malloc(&ds->d_query_verify, 16));
+            AH_HIP(hipMemsetAsync(ds->d_query_verify, 0, 16, s));
+        }
+        ctr = ds->d_query_verify;
+    }
+    const DataView dv = ds->view();
+    const size_t lds = (size_t)ds->pitch * 4;
+    if (lds > 48 * 1024) {
+        AH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_screen_verify<AH_COSINE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        AH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_screen_verify<AH_DOT_PRODUCT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    }
+    const dim3 grid(64, nq);
+    if (ds->metric == AH_COSINE)
+        hipLaunchKernelGGL(k_screen_verify<AH_COSINE>, grid, dim3(256), lds, s, dv, ss, nns, dist, stride, counts, segs, qvecs, qstride, qhdrs, ctr);
+    else
+        hipLaunchKernelGGL(k_screen_verify<AH_DOT_PRODUCT>, grid, dim3(256), lds, s, dv, ss, nns, dist, stride, counts, segs, qvecs, qstride, qhdrs, ctr);
+    AH_HIP(hipGetLastError());
+    return AH_OK;
 }
 
 // The k smallest (OrderedFloat(distance), id) of one query's unflagged candidates, ascending, as (id, normalized
@@ -3444,6 +3540,8 @@ int launch_rerank_screened(ah_dataset *ds, uint32_t nq, const uint8_t *d_qvecs, 
         AH_HIP(hipGetLastError());
         return AH_OK;
     }
+    AH_TRY(launch_screen_verify(ds, ss, d_ids, d_dist, 0u, nullptr, reinterpret_cast<const PairSeg *>(d_segs), nq, d_qvecs, qstride,
+                                d_qhdrs, s));
     const size_t sel_lds = (size_t)ds->pitch * 4;
     if (sel_lds > 32 * 1024) {
         AH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_search_select_screened<AH_COSINE>),
@@ -3480,7 +3578,8 @@ struct ah_index {
     std::mutex stats_mu;       // ah_search_batch may run on any number of threads
     ah_search_stats stats{};
     std::atomic<uint32_t> search8_fails{0};  // sub-batches whose int8 stage left too many survivors ...
-    std::atomic<bool> search8_off{false};    // ... eight of them: the index's tile re-rank starts on the binary16 rows from now on
+    std::atomic<uint32_t> search8_seen{0};   // ... among this many it served (screen8_window_note: windows of 64) ...
+    std::atomic<bool> search8_off{false};    // ... eight in one window: the index's tile re-rank starts on the binary16 rows from now on
 };
 
 extern "C" {
@@ -4140,6 +4239,7 @@ static int search_chunk(ah_index *ix, Context *ctx, const float *queries, const 
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)sel_lds));
         }
         uint32_t *sel_trace = multi_launched && tun(TUN_SEARCH_MULTI_TRACE) != 0 ? &reinterpret_cast<MultiCtl *>(ctx->d_multi)->sel_trace[0] : nullptr;
+        if (screened) AH_TRY(launch_screen_verify(ds, ss, d_nns, d_dist, nns_stride, d_counts, nullptr, (uint32_t)nq, d_qvecs, qstride, d_qhdrs, s));
         if (fused_flag && ds->metric == AH_COSINE)
             hipLaunchKernelGGL((k_search_select_screened<AH_COSINE, true>), dim3((unsigned)nq), dim3(1024), fused_lds, s, dv, ss, d_nns, d_dist,
                                nns_stride, d_counts, d_unique, (uint32_t)k, d_qvecs, qstride, d_qhdrs, h_oi, h_od, d_err, (const PairSeg *)nullptr,
@@ -4212,6 +4312,7 @@ static int search_chunk(ah_index *ix, Context *ctx, const float *queries, const 
             cs.device_words(h_err);
             cs.s.rerank_tiles = nq;
             cs.s.rerank_screened8 = screened8 ? h_err[SS_SCREENED] : 0;
+            if (screened8) (void)screen8_window_note(ix->search8_seen, ix->search8_fails, false);
             (bitmap_fits ? cs.s.dedup_flag_bitmap : cs.s.dedup_flag_hash) = nq;
             cs.commit(ix);
             return AH_OK;
@@ -4219,7 +4320,7 @@ static int search_chunk(ah_index *ix, Context *ctx, const float *queries, const 
         if (screened8 && launch_err == hipSuccess && (*h_err & ~1u) == 8u) {
             // more survivors than the selection holds on the int8 stage (candidates closer together than its error bound): the
             // same sub-batch once more with the binary16 rows first — not the long way
-            if (ix->search8_fails.fetch_add(1, std::memory_order_relaxed) + 1 >= 8) ix->search8_off.store(true, std::memory_order_relaxed);
+            if (screen8_window_note(ix->search8_seen, ix->search8_fails, true)) ix->search8_off.store(true, std::memory_order_relaxed);
             {
                 std::lock_guard<std::mutex> lk(ix->stats_mu);
                 ix->stats.screen8_retried_chunks += 1;

@@ -175,6 +175,13 @@ class Dataset:
         _lib.check(_lib.lib().ah_dataset_packed_info(self._h, C.byref(present), C.byref(raw)))
         return {"present": bool(present.value), "raw_rows": raw.value}
 
+    def query_screen_verify(self, reset: bool = False) -> dict:
+        """ah_debug_query_screen_verify: under the tunable AH_SCREEN_VERIFY=1, the candidates of the search and re-rank screens
+        checked in f32, and those whose reference distance fell outside the screen's interval (must be 0)."""
+        checked, bad = C.c_uint64(0), C.c_uint64(0)
+        _lib.check(_lib.lib().ah_debug_query_screen_verify(self._h, C.byref(checked), C.byref(bad), 1 if reset else 0))
+        return {"checked": checked.value, "violations": bad.value}
+
     # -- build side --------------------------------------------------------------------------------
     def split_sides(self, normal_vector: np.ndarray, normal_header, sorted_ids=None, want_margins: bool = True):
         """The margin loop (src/writer.rs:1201-1207). Returns (sides u8 per item, n_left, margins)."""

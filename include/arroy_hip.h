@@ -48,7 +48,8 @@ extern "C" {
                                   ah_dataset_replicate falls back to a copy through pinned host memory when the two devices
                                   have no peer access;
                                   device groups (ah_group_*, ah_build_forest_group_stream): additions only, the number stays 7 —
-                                  a caller that needs them looks the symbols up */
+                                  a caller that needs them looks the symbols up; so are ah_dataset_packed_info and the
+                                  test aid ah_debug_query_screen_verify */
 
 /* every entry point is exported from the shared object (it is built with -fvisibility=hidden) */
 #if defined(__GNUC__)
@@ -209,13 +210,21 @@ typedef struct ah_rerank_stats {
     uint64_t queries_screened;    /* queries answered through the screen (int8 or binary16 rows first, f32 for the survivors) */
     uint64_t survivors;           /* ... candidates of theirs evaluated in f32                                            */
     uint64_t chunks_int8;         /* sub-batches whose screen started on the int8 copy of the rows and stayed there       */
-    uint64_t chunks_int8_retried; /* ... that left more survivors than the selection holds and ran again on binary16 rows */
+    uint64_t chunks_int8_retried; /* ... that left more survivors than the selection holds and ran again on binary16 rows
+                                     (eight of them within one window of 64 sub-batches the int8 stage served switch that
+                                     stage off for the dataset) */
 } ah_rerank_stats;
 AH_API int ah_dataset_rerank_stats(ah_dataset *ds, ah_rerank_stats *out, int reset);
 /* The packed copy of the rows that the ungathered f32 scan reads (tunable AH_SCAN_PACKED): *out_present = 1 when it exists,
  * *out_raw_rows = its rows kept in f32 (an inf / NaN, or an exponent spread of 15 binades or more).  Either pointer may be
  * NULL.  Made by the first ah_distances_by_* / ah_bench_scan call over all rows, never by a build or a search. */
 AH_API int ah_dataset_packed_info(ah_dataset *ds, int *out_present, uint64_t *out_raw_rows);
+/* Test aid: the counters of the tunable AH_SCREEN_VERIFY=1 for the query-side screens (the certified top-k screen of
+ * ah_search_batch and ah_rerank_batch on this dataset).  Under it every candidate with a finite screen value is also evaluated
+ * in the reference's f32 arithmetic: *out_checked counts those candidates, *out_violations the ones whose reference distance
+ * fell outside the interval [L, U] the screen derived for them (must be 0).  Both stay 0 while the tunable is 0.  Either
+ * pointer may be NULL; reset != 0 zeroes the counters after reading them. */
+AH_API int ah_debug_query_screen_verify(ah_dataset *ds, uint64_t *out_checked, uint64_t *out_violations, int reset);
 
 /* ------------------------------------------------------------------------------------------
  * Build side (src/writer.rs:1193-1233, 1398-1531; src/distance/mod.rs:126-223)
@@ -576,7 +585,8 @@ typedef struct ah_search_stats {
     /* ABI v7: the int8 copy of the rows as the first stage of that screen (big submissions; 1 byte per dimension) */
     uint64_t rerank_screened8;      /* queries (of rerank_screened) whose candidates were evaluated on the int8 rows first */
     uint64_t screen8_retried_chunks; /* sub-batches whose int8 stage left more survivors than the selection holds: done again
-                                       with the binary16 rows first (eight of them switch the int8 stage of the index off)  */
+                                       with the binary16 rows first (eight of them within one window of 64 sub-batches the
+                                       int8 stage served switch that stage of the index off) */
     uint64_t descent_multi;         /* queries (of descent_block) whose trees were dealt over several blocks, one wave of
                                        eight octets each: one query on more than one compute unit (submissions of <= 32 queries) */
 } ah_search_stats;
