@@ -210,6 +210,12 @@ SIGNATURES = {
     "ah_group_destroy": (C.c_int, [_VP]),
     "ah_build_forest_group_stream": (C.c_int, [_VP, C.POINTER(AhBuildOptions), NODE_BATCH_FN, _VP, _U32P, C.POINTER(AhBuildStats),
                                                C.POINTER(AhBuildStats)]),
+    # updates of a finalized dataset (only the changed rows are staged)
+    "ah_dataset_update_vectors": (C.c_int, [_VP, _U32P, C.c_size_t, _U32P, _F32P, C.c_size_t]),
+    "ah_dataset_update_records": (C.c_int, [_VP, _U32P, C.c_size_t, _U32P, _VP, C.c_size_t, C.c_size_t]),
+    "ah_group_update_vectors": (C.c_int, [_VP, _U32P, C.c_size_t, _U32P, _F32P, C.c_size_t]),
+    "ah_group_update_records": (C.c_int, [_VP, _U32P, C.c_size_t, _U32P, _VP, C.c_size_t, C.c_size_t]),
+    "ah_debug_update_paths": (C.c_int, [_VP, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
 }
 
 _lib = None

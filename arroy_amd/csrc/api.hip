@@ -1088,12 +1088,11 @@ static int gather_records(const RecordSlot &slot, const uint8_t *const *record_p
     memcpy(slot.ids, item_ids, c * 4);
     return AH_OK;
 }
-static int send_records(ah_dataset *ds, const RecordSlot &slot, uint64_t row0, size_t c, hipStream_t s) {
+static int send_records(ah_dataset *ds, const StageDst &dst, const RecordSlot &slot, uint64_t row0, size_t c, hipStream_t s) {
     const size_t rb = ds->row_bytes(), hs = ah_header_size(ds->metric);
-    uint8_t *d_rows = ds->d_rows_f32 ? reinterpret_cast<uint8_t *>(ds->d_rows_f32) : reinterpret_cast<uint8_t *>(ds->d_rows_bq);
-    AH_HIP(hipMemcpyAsync(d_rows + row0 * rb, slot.rows, c * rb, hipMemcpyHostToDevice, s));
-    AH_HIP(hipMemcpyAsync(reinterpret_cast<uint8_t *>(ds->d_headers) + row0 * hs, slot.hdr, c * hs, hipMemcpyHostToDevice, s));
-    AH_HIP(hipMemcpyAsync(ds->d_ids + row0, slot.ids, c * 4, hipMemcpyHostToDevice, s));
+    AH_HIP(hipMemcpyAsync(dst.rows + row0 * rb, slot.rows, c * rb, hipMemcpyHostToDevice, s));
+    AH_HIP(hipMemcpyAsync(reinterpret_cast<uint8_t *>(dst.headers) + row0 * hs, slot.hdr, c * hs, hipMemcpyHostToDevice, s));
+    AH_HIP(hipMemcpyAsync(dst.ids + row0, slot.ids, c * 4, hipMemcpyHostToDevice, s));
     return AH_OK;
 }
 struct VectorSlot {  // f32 vectors at the staging pitch, then the ids
@@ -1115,17 +1114,95 @@ static void gather_vectors(const VectorSlot &slot, const float *vectors, const u
     memcpy(slot.ids, item_ids, c * 4);
 }
 // BQ metrics: the f32 rows land in d_tmp (one ring slot of the context's device scratch) and are quantised from there
-static int send_vectors(ah_dataset *ds, const VectorSlot &slot, uint64_t row0, size_t c, uint32_t fpitch, float *d_tmp,
-                        hipStream_t s) {
+static int send_vectors(ah_dataset *ds, const StageDst &dst, const VectorSlot &slot, uint64_t row0, size_t c, uint32_t fpitch,
+                        float *d_tmp, hipStream_t s) {
     const size_t frb = (size_t)fpitch * 4;
+    DataView dv = ds->view();  // (the codec and header kernels write into `dst`)
+    dv.rows_f32 = metric_is_bq(ds->metric) ? nullptr : reinterpret_cast<const float *>(dst.rows);
+    dv.rows_bq = metric_is_bq(ds->metric) ? reinterpret_cast<const uint64_t *>(dst.rows) : nullptr;
+    dv.headers = dst.headers;
     if (!metric_is_bq(ds->metric)) {
-        AH_HIP(hipMemcpyAsync(ds->d_rows_f32 + row0 * ds->pitch, slot.rows, c * frb, hipMemcpyHostToDevice, s));
+        AH_HIP(hipMemcpyAsync(dst.rows + row0 * frb, slot.rows, c * frb, hipMemcpyHostToDevice, s));
     } else {
         AH_HIP(hipMemcpyAsync(d_tmp, slot.rows, c * frb, hipMemcpyHostToDevice, s));
-        AH_TRY(launch_quantize_rows(d_tmp, fpitch, ds->dims, ds->d_rows_bq + row0 * ds->pitch, ds->pitch, ds->words, c, s));
+        AH_TRY(launch_quantize_rows(d_tmp, fpitch, ds->dims, reinterpret_cast<uint64_t *>(dst.rows) + row0 * ds->pitch, ds->pitch,
+                                    ds->words, c, s));
     }
-    AH_HIP(hipMemcpyAsync(ds->d_ids + row0, slot.ids, c * 4, hipMemcpyHostToDevice, s));
-    AH_TRY(launch_headers_from_vectors(ds->view(), row0, c, s));
+    AH_HIP(hipMemcpyAsync(dst.ids + row0, slot.ids, c * 4, hipMemcpyHostToDevice, s));
+    AH_TRY(launch_headers_from_vectors(dv, row0, c, s));
+    return AH_OK;
+}
+
+// The ring loops of ah_dataset_upload_records / _vectors: n items into rows row0 .. row0 + n of `dst` (the dataset's own
+// arrays, or the side buffers of an update, update.hip); the caller has checked the ids and keeps the books.
+static int stage_records_loop(ah_dataset *ds, const StageDst &dst, uint64_t row0, const uint32_t *item_ids,
+                              const uint8_t *const *record_ptrs, size_t n) {
+    const size_t hs = ah_header_size(ds->metric), vs = ah_vector_size(ds->metric, ds->dims);
+    const size_t rb = ds->row_bytes();
+    const size_t chunk = std::max<size_t>(1, std::min<size_t>(n, kStageBytes / (rb + hs + 4)));
+    const size_t buf_bytes = RecordSlot::bytes(chunk, rb, hs);
+    Context *ctx = nullptr;
+    AH_TRY(upload_context(ds, buf_bytes, &ctx));
+    const size_t ring_stride = ctx->h_cap / kRing & ~(size_t)255;
+    size_t done = 0;
+    while (done < n) {
+        const size_t c = std::min(chunk, n - done);
+        const int b = ds->up_buf;
+        uint8_t *base = reinterpret_cast<uint8_t *>(ctx->h_pinned) + (size_t)b * ring_stride;
+        if (ds->up_used[b]) AH_HIP(hipEventSynchronize(ctx->ev_ring[b]));
+        const RecordSlot slot(base, chunk, rb, hs);
+        AH_TRY(gather_records(slot, record_ptrs + done, item_ids + done, c, rb, hs, vs, done));
+        AH_TRY(send_records(ds, dst, slot, row0 + done, c, ctx->stream));
+        AH_HIP(hipEventRecord(ctx->ev_ring[b], ctx->stream));
+        ds->up_used[b] = true;
+        ds->up_buf = (b + 1) % kRing;
+        done += c;
+    }
+    return AH_OK;
+}
+struct StageTimes {
+    double ctx = 0, gather = 0, wait = 0;  // seconds: context + pinned ring, the gathers, waiting for ring slots
+};
+static double secs_between(std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
+    return std::chrono::duration<double>(b - a).count();
+}
+static int stage_vectors_loop(ah_dataset *ds, const StageDst &dst, uint64_t row0, const uint32_t *item_ids, const float *vectors,
+                              size_t n, StageTimes *tm) {
+    const bool bq = metric_is_bq(ds->metric);
+    const uint32_t fpitch = bq ? ((ds->dims + 3u) & ~3u) : ds->pitch;  // staging pitch in floats
+    const size_t frb = (size_t)fpitch * 4;
+    const size_t chunk = std::max<size_t>(1, std::min<size_t>(n, kStageBytes / (frb + 4)));
+    const size_t buf_bytes = VectorSlot::bytes(chunk, frb);
+    auto now = [] { return std::chrono::steady_clock::now(); };
+    const auto t_begin = now();
+    Context *ctx = nullptr;
+    AH_TRY(upload_context(ds, buf_bytes, &ctx));
+    tm->ctx = secs_between(t_begin, now());
+    const size_t ring_stride = ctx->h_cap / kRing & ~(size_t)255;
+    if (bq) {
+        if (ctx->d_cap < (size_t)kRing * pad256(chunk * frb)) AH_HIP(hipStreamSynchronize(ctx->stream));
+        AH_TRY(ctx->ensure_device((size_t)kRing * pad256(chunk * frb)));
+    }
+    size_t done = 0;
+    while (done < n) {
+        const size_t c = std::min(chunk, n - done);
+        const int b = ds->up_buf;
+        uint8_t *base = reinterpret_cast<uint8_t *>(ctx->h_pinned) + (size_t)b * ring_stride;
+        const auto t0 = now();
+        if (ds->up_used[b]) AH_HIP(hipEventSynchronize(ctx->ev_ring[b]));
+        const auto t1 = now();
+        const VectorSlot slot(base, chunk, frb);
+        gather_vectors(slot, vectors + done * (size_t)ds->dims, item_ids + done, c, ds->dims, fpitch);
+        tm->wait += secs_between(t0, t1);
+        tm->gather += secs_between(t1, now());
+        float *d_tmp = bq ? reinterpret_cast<float *>(reinterpret_cast<uint8_t *>(ctx->d_scratch) + (size_t)b * pad256(chunk * frb))
+                          : nullptr;
+        AH_TRY(send_vectors(ds, dst, slot, row0 + done, c, fpitch, d_tmp, ctx->stream));
+        AH_HIP(hipEventRecord(ctx->ev_ring[b], ctx->stream));
+        ds->up_used[b] = true;
+        ds->up_buf = (b + 1) % kRing;
+        done += c;
+    }
     return AH_OK;
 }
 
@@ -1145,26 +1222,7 @@ int ah_dataset_upload_records(ah_dataset *ds, const uint32_t *item_ids, const ui
         set_error_detail(0, 1 + hs + vs, record_len);
         return AH_ERR_INVALID_DIMENSION;
     }
-    const size_t rb = ds->row_bytes();
-    const size_t chunk = std::max<size_t>(1, std::min<size_t>(n, kStageBytes / (rb + hs + 4)));
-    const size_t buf_bytes = RecordSlot::bytes(chunk, rb, hs);
-    Context *ctx = nullptr;
-    AH_TRY(upload_context(ds, buf_bytes, &ctx));
-    const size_t ring_stride = ctx->h_cap / kRing & ~(size_t)255;
-    size_t done = 0;
-    while (done < n) {
-        const size_t c = std::min(chunk, n - done);
-        const int b = ds->up_buf;
-        uint8_t *base = reinterpret_cast<uint8_t *>(ctx->h_pinned) + (size_t)b * ring_stride;
-        if (ds->up_used[b]) AH_HIP(hipEventSynchronize(ctx->ev_ring[b]));
-        const RecordSlot slot(base, chunk, rb, hs);
-        AH_TRY(gather_records(slot, record_ptrs + done, item_ids + done, c, rb, hs, vs, done));
-        AH_TRY(send_records(ds, slot, ds->n + done, c, ctx->stream));
-        AH_HIP(hipEventRecord(ctx->ev_ring[b], ctx->stream));
-        ds->up_used[b] = true;
-        ds->up_buf = (b + 1) % kRing;
-        done += c;
-    }
+    AH_TRY(stage_records_loop(ds, own_dst(ds), ds->n, item_ids, record_ptrs, n));
     note_ids(ds, item_ids, n);
     // The stored DotProduct headers are taken as they are: items written by `Writer::add_item` carry {0, 0} until
     // `DotProduct::preprocess` ran over the database (src/distance/dot_product.rs:119-165), so the dataset still needs
@@ -1202,49 +1260,18 @@ int ah_dataset_upload_vectors(ah_dataset *ds, const uint32_t *item_ids, const fl
         }
         (void)hipGetLastError();  // not registrable: fall through to the bounce path
     }
-    const size_t chunk = std::max<size_t>(1, std::min<size_t>(n, kStageBytes / (frb + 4)));
-    const size_t buf_bytes = VectorSlot::bytes(chunk, frb);
     const bool timing = tun(TUN_TIMING) != 0;
     auto now = [] { return std::chrono::steady_clock::now(); };
-    auto secs = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
-        return std::chrono::duration<double>(b - a).count();
-    };
     const auto t_begin = now();
-    double t_gather = 0, t_wait = 0;
-    Context *ctx = nullptr;
-    AH_TRY(upload_context(ds, buf_bytes, &ctx));
-    const auto t_ctx = now();
-    const size_t ring_stride = ctx->h_cap / kRing & ~(size_t)255;
-    if (bq) {
-        if (ctx->d_cap < (size_t)kRing * pad256(chunk * frb)) AH_HIP(hipStreamSynchronize(ctx->stream));
-        AH_TRY(ctx->ensure_device((size_t)kRing * pad256(chunk * frb)));
-    }
-    size_t done = 0;
-    while (done < n) {
-        const size_t c = std::min(chunk, n - done);
-        const int b = ds->up_buf;
-        uint8_t *base = reinterpret_cast<uint8_t *>(ctx->h_pinned) + (size_t)b * ring_stride;
-        const auto t0 = now();
-        if (ds->up_used[b]) AH_HIP(hipEventSynchronize(ctx->ev_ring[b]));
-        const auto t1 = now();
-        const VectorSlot slot(base, chunk, frb);
-        gather_vectors(slot, vectors + done * (size_t)ds->dims, item_ids + done, c, ds->dims, fpitch);
-        t_wait += secs(t0, t1);
-        t_gather += secs(t1, now());
-        float *d_tmp = bq ? reinterpret_cast<float *>(reinterpret_cast<uint8_t *>(ctx->d_scratch) + (size_t)b * pad256(chunk * frb))
-                          : nullptr;
-        AH_TRY(send_vectors(ds, slot, ds->n + done, c, fpitch, d_tmp, ctx->stream));
-        AH_HIP(hipEventRecord(ctx->ev_ring[b], ctx->stream));
-        ds->up_used[b] = true;
-        ds->up_buf = (b + 1) % kRing;
-        done += c;
-    }
+    StageTimes tm;
+    AH_TRY(stage_vectors_loop(ds, own_dst(ds), ds->n, item_ids, vectors, n, &tm));
     const auto t_loop = now();
     note_ids(ds, item_ids, n);
     if (timing)
         fprintf(stderr, "[ah] upload_vectors %zu x %u: context + pinned ring %.4f s, gather %.4f s, waiting for the ring %.4f s, "
                         "launch/other %.4f s, note_ids %.4f s\n",
-                n, ds->dims, secs(t_begin, t_ctx), t_gather, t_wait, secs(t_ctx, t_loop) - t_gather - t_wait, secs(t_loop, now()));
+                n, ds->dims, tm.ctx, tm.gather, tm.wait, secs_between(t_begin, t_loop) - tm.ctx - tm.gather - tm.wait,
+                secs_between(t_loop, now()));
     return AH_OK;
     AH_GUARDED_END
 }
@@ -1600,6 +1627,71 @@ int ah_group_destroy(ah_group *g) {
     AH_GUARDED_END
 }
 
+// The ring loops of ah_group_upload_vectors / _records: n items into rows row0 .. row0 + n of dst[i] on member i (the members'
+// own arrays, or the side buffers of an update).
+static int group_stage_vectors_loop(ah_group *g, const StageDst *dst, uint64_t row0, const uint32_t *item_ids, const float *vectors,
+                                    size_t n, StageTimes *tm) {
+    const bool bq = metric_is_bq(g->metric);
+    const uint32_t fpitch = bq ? ((g->dims + 3u) & ~3u) : g->members[0]->pitch;
+    const size_t frb = (size_t)fpitch * 4;
+    const size_t chunk = std::max<size_t>(1, std::min<size_t>(n, kStageBytes / (frb + 4)));
+    auto now = [] { return std::chrono::steady_clock::now(); };
+    const auto t_begin = now();
+    AH_TRY(group_stage_begin(g, VectorSlot::bytes(chunk, frb), bq ? (size_t)ah_group::kRing * pad256(chunk * frb) : 0));
+    tm->ctx = secs_between(t_begin, now());
+    size_t done = 0;
+    while (done < n) {
+        const size_t c = std::min(chunk, n - done);
+        const int b = g->next_slot;
+        const auto t0 = now();
+        AH_TRY(group_wait_slot(g, b));
+        const auto t1 = now();
+        const VectorSlot slot(reinterpret_cast<uint8_t *>(g->h_ring) + (size_t)b * g->slot_bytes, chunk, frb);
+        gather_vectors(slot, vectors + done * (size_t)g->dims, item_ids + done, c, g->dims, fpitch);
+        tm->wait += secs_between(t0, t1);
+        tm->gather += secs_between(t1, now());
+        for (size_t i = 0; i < g->members.size(); i++) {
+            ah_dataset *m = g->members[i];
+            Context *ctx = m->up_ctx;
+            AH_HIP(hipSetDevice(m->device));
+            float *d_tmp = bq ? reinterpret_cast<float *>(reinterpret_cast<uint8_t *>(ctx->d_scratch) + (size_t)b * pad256(chunk * frb))
+                              : nullptr;
+            g->slot_used[b] = true;
+            AH_TRY(send_vectors(m, dst[i], slot, row0 + done, c, fpitch, d_tmp, ctx->stream));
+            AH_HIP(hipEventRecord(ctx->ev_ring[b], ctx->stream));
+        }
+        g->next_slot = (b + 1) % ah_group::kRing;
+        done += c;
+    }
+    return AH_OK;
+}
+static int group_stage_records_loop(ah_group *g, const StageDst *dst, uint64_t row0, const uint32_t *item_ids,
+                                    const uint8_t *const *record_ptrs, size_t n) {
+    const size_t hs = ah_header_size(g->metric), vs = ah_vector_size(g->metric, g->dims);
+    const size_t rb = g->members[0]->row_bytes();
+    const size_t chunk = std::max<size_t>(1, std::min<size_t>(n, kStageBytes / (rb + hs + 4)));
+    AH_TRY(group_stage_begin(g, RecordSlot::bytes(chunk, rb, hs), 0));
+    size_t done = 0;
+    while (done < n) {
+        const size_t c = std::min(chunk, n - done);
+        const int b = g->next_slot;
+        AH_TRY(group_wait_slot(g, b));
+        const RecordSlot slot(reinterpret_cast<uint8_t *>(g->h_ring) + (size_t)b * g->slot_bytes, chunk, rb, hs);
+        AH_TRY(gather_records(slot, record_ptrs + done, item_ids + done, c, rb, hs, vs, done));
+        for (size_t i = 0; i < g->members.size(); i++) {
+            ah_dataset *m = g->members[i];
+            Context *ctx = m->up_ctx;
+            AH_HIP(hipSetDevice(m->device));
+            g->slot_used[b] = true;
+            AH_TRY(send_records(m, dst[i], slot, row0 + done, c, ctx->stream));
+            AH_HIP(hipEventRecord(ctx->ev_ring[b], ctx->stream));
+        }
+        g->next_slot = (b + 1) % ah_group::kRing;
+        done += c;
+    }
+    return AH_OK;
+}
+
 // Writer::add_item for a batch, on every member: the chunk is gathered once into the group's pinned ring and sent from that
 // same slot to every member, each on its own stream, where the codec / header kernels run on the member's device.
 int ah_group_upload_vectors(ah_group *g, const uint32_t *item_ids, const float *vectors, size_t n) {
@@ -1611,51 +1703,22 @@ int ah_group_upload_vectors(ah_group *g, const uint32_t *item_ids, const float *
     AH_REQUIRE(item_ids && vectors, AH_ERR_INVALID_ARGUMENT, "NULL input");
     DeviceRestore restore_device;
     for (ah_dataset *m : g->members) reserve_ids(m, n);
-    const bool bq = metric_is_bq(g->metric);
-    const uint32_t fpitch = bq ? ((g->dims + 3u) & ~3u) : m0->pitch;
-    const size_t frb = (size_t)fpitch * 4;
-    const size_t chunk = std::max<size_t>(1, std::min<size_t>(n, kStageBytes / (frb + 4)));
     // AH_TIMING=1: where the call's time went, in the form of ah_dataset_upload_vectors' line (scripts/exp_group.py reads
     // the gather: it is paid once whatever the number of members)
     const bool timing = tun(TUN_TIMING) != 0;
     auto now = [] { return std::chrono::steady_clock::now(); };
-    auto secs = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
-        return std::chrono::duration<double>(b - a).count();
-    };
     const auto t_begin = now();
-    double t_gather = 0, t_wait = 0;
-    AH_TRY(group_stage_begin(g, VectorSlot::bytes(chunk, frb), bq ? (size_t)ah_group::kRing * pad256(chunk * frb) : 0));
-    const auto t_ctx = now();
-    size_t done = 0;
-    while (done < n) {
-        const size_t c = std::min(chunk, n - done);
-        const int b = g->next_slot;
-        const auto t0 = now();
-        AH_TRY(group_wait_slot(g, b));
-        const auto t1 = now();
-        const VectorSlot slot(reinterpret_cast<uint8_t *>(g->h_ring) + (size_t)b * g->slot_bytes, chunk, frb);
-        gather_vectors(slot, vectors + done * (size_t)g->dims, item_ids + done, c, g->dims, fpitch);
-        t_wait += secs(t0, t1);
-        t_gather += secs(t1, now());
-        for (ah_dataset *m : g->members) {
-            Context *ctx = m->up_ctx;
-            AH_HIP(hipSetDevice(m->device));
-            float *d_tmp = bq ? reinterpret_cast<float *>(reinterpret_cast<uint8_t *>(ctx->d_scratch) + (size_t)b * pad256(chunk * frb))
-                              : nullptr;
-            g->slot_used[b] = true;
-            AH_TRY(send_vectors(m, slot, m->n + done, c, fpitch, d_tmp, ctx->stream));
-            AH_HIP(hipEventRecord(ctx->ev_ring[b], ctx->stream));
-        }
-        g->next_slot = (b + 1) % ah_group::kRing;
-        done += c;
-    }
+    StageTimes tm;
+    std::vector<StageDst> dst;
+    for (ah_dataset *m : g->members) dst.push_back(own_dst(m));
+    AH_TRY(group_stage_vectors_loop(g, dst.data(), m0->n, item_ids, vectors, n, &tm));
     const auto t_loop = now();
     for (ah_dataset *m : g->members) note_ids(m, item_ids, n);
     if (timing)
         fprintf(stderr, "[ah] group upload_vectors %zu x %u to %zu members: context + pinned ring %.4f s, gather %.4f s, waiting for "
                         "the ring %.4f s, launch/other %.4f s, note_ids %.4f s\n",
-                n, g->dims, g->members.size(), secs(t_begin, t_ctx), t_gather, t_wait, secs(t_ctx, t_loop) - t_gather - t_wait,
-                secs(t_loop, now()));
+                n, g->dims, g->members.size(), tm.ctx, tm.gather, tm.wait, secs_between(t_begin, t_loop) - tm.ctx - tm.gather - tm.wait,
+                secs_between(t_loop, now()));
     return AH_OK;
     AH_GUARDED_END
 }
@@ -1678,26 +1741,9 @@ int ah_group_upload_records(ah_group *g, const uint32_t *item_ids, const uint8_t
     }
     DeviceRestore restore_device;
     for (ah_dataset *m : g->members) reserve_ids(m, n);
-    const size_t rb = m0->row_bytes();
-    const size_t chunk = std::max<size_t>(1, std::min<size_t>(n, kStageBytes / (rb + hs + 4)));
-    AH_TRY(group_stage_begin(g, RecordSlot::bytes(chunk, rb, hs), 0));
-    size_t done = 0;
-    while (done < n) {
-        const size_t c = std::min(chunk, n - done);
-        const int b = g->next_slot;
-        AH_TRY(group_wait_slot(g, b));
-        const RecordSlot slot(reinterpret_cast<uint8_t *>(g->h_ring) + (size_t)b * g->slot_bytes, chunk, rb, hs);
-        AH_TRY(gather_records(slot, record_ptrs + done, item_ids + done, c, rb, hs, vs, done));
-        for (ah_dataset *m : g->members) {
-            Context *ctx = m->up_ctx;
-            AH_HIP(hipSetDevice(m->device));
-            g->slot_used[b] = true;
-            AH_TRY(send_records(m, slot, m->n + done, c, ctx->stream));
-            AH_HIP(hipEventRecord(ctx->ev_ring[b], ctx->stream));
-        }
-        g->next_slot = (b + 1) % ah_group::kRing;
-        done += c;
-    }
+    std::vector<StageDst> dst;
+    for (ah_dataset *m : g->members) dst.push_back(own_dst(m));
+    AH_TRY(group_stage_records_loop(g, dst.data(), m0->n, item_ids, record_ptrs, n));
     for (ah_dataset *m : g->members) note_ids(m, item_ids, n);
     return AH_OK;
     AH_GUARDED_END
@@ -2622,3 +2668,27 @@ int ah_bench_read(int device, uint64_t bytes, uint32_t iterations, double *out_m
 }
 
 }  // extern "C"
+
+// The staging loops for the updates of a finalized dataset (update.hip): the upserted items go through the same rings, codec
+// and header kernels as ah_dataset_upload_* / ah_group_upload_*, into the update's side buffers.
+namespace ah {
+int stage_vectors(ah_dataset *ds, const StageDst &dst, const uint32_t *item_ids, const float *vectors, size_t n) {
+    StageTimes tm;
+    AH_TRY(stage_vectors_loop(ds, dst, 0, item_ids, vectors, n, &tm));
+    return upload_flush(ds);
+}
+int stage_records(ah_dataset *ds, const StageDst &dst, const uint32_t *item_ids, const uint8_t *const *record_ptrs, size_t n) {
+    AH_TRY(stage_records_loop(ds, dst, 0, item_ids, record_ptrs, n));
+    return upload_flush(ds);
+}
+int group_stage_vectors(ah_group *g, const StageDst *dst, const uint32_t *item_ids, const float *vectors, size_t n) {
+    StageTimes tm;
+    AH_TRY(group_stage_vectors_loop(g, dst, 0, item_ids, vectors, n, &tm));
+    return ah_group_upload_flush(g);
+}
+int group_stage_records(ah_group *g, const StageDst *dst, const uint32_t *item_ids, const uint8_t *const *record_ptrs, size_t n) {
+    AH_TRY(group_stage_records_loop(g, dst, 0, item_ids, record_ptrs, n));
+    return ah_group_upload_flush(g);
+}
+int flush_staging(ah_dataset *ds) { return upload_flush(ds); }
+}  // namespace ah

@@ -438,6 +438,10 @@ struct ah_dataset {
     ah_rerank_stats rr_stats{};                  // AH_RERANK_TIMING=1: where ah_rerank_batch's wall time went (under `mu`)
     double reserve_seconds = 0.0;                // ... how long that helper ran (written by it, read after the join)
     double reserve_wait_seconds = 0.0;           // ... and how long the first build then waited for it (ah_build_stats, ABI v7)
+    // ah_index handles alive on this dataset (ah_index_create* / ah_index_destroy): they hold row positions, so an update
+    // (update.hip) refuses while any is alive
+    std::atomic<int> live_indexes{0};
+    uint64_t update_fast_paths[3] = {0, 0, 0};   // updates done in place / appended / merged into new buffers (ah_debug_update_paths)
 
     // Wait for ah_dataset_reserve_build's helper, whoever gets there first (concurrent builds on one dataset are allowed: the
     // handle is moved out under `mu`, so exactly one caller joins it; a failing join must not cross the C ABI)
@@ -486,6 +490,24 @@ struct DeviceRestore {
         if (prev >= 0) (void)hipSetDevice(prev);
     }
 };
+
+// Where a staging pass writes: the dataset's own arrays (ah_dataset_upload_*, from row n on) or the side buffers of an update.
+struct StageDst {
+    uint8_t *rows;     // f32 rows or BQ words, ds->row_bytes() apart
+    float *headers;
+    uint32_t *ids;
+};
+inline StageDst own_dst(ah_dataset *ds) {
+    uint8_t *rows = ds->d_rows_f32 ? reinterpret_cast<uint8_t *>(ds->d_rows_f32) : reinterpret_cast<uint8_t *>(ds->d_rows_bq);
+    return StageDst{rows, ds->d_headers, ds->d_ids};
+}
+// api.hip: n items staged into rows 0 .. n of `dst` through the dataset's (the group's) pinned ring, codec and header
+// kernels included; returns once every transfer has landed
+int stage_vectors(ah_dataset *ds, const StageDst &dst, const uint32_t *item_ids, const float *vectors, size_t n);
+int stage_records(ah_dataset *ds, const StageDst &dst, const uint32_t *item_ids, const uint8_t *const *record_ptrs, size_t n);
+int group_stage_vectors(ah_group *g, const StageDst *dst, const uint32_t *item_ids, const float *vectors, size_t n);
+int group_stage_records(ah_group *g, const StageDst *dst, const uint32_t *item_ids, const uint8_t *const *record_ptrs, size_t n);
+int flush_staging(ah_dataset *ds);  // wait for a dataset's staging transfers (upload_flush)
 
 // owning device pointer for short-lived buffers on paths with early error returns
 struct DevMem {

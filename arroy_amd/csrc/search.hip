@@ -3580,6 +3580,7 @@ struct ah_index {
     std::atomic<uint32_t> search8_fails{0};  // sub-batches whose int8 stage left too many survivors ...
     std::atomic<uint32_t> search8_seen{0};   // ... among this many it served (screen8_window_note: windows of 64) ...
     std::atomic<bool> search8_off{false};    // ... eight in one window: the index's tile re-rank starts on the binary16 rows from now on
+    bool counted = false;                    // counted in ds->live_indexes (an update of the dataset refuses meanwhile)
 };
 
 extern "C" {
@@ -3597,6 +3598,7 @@ int ah_index_destroy(ah_index *ix) {
     if (ix->d_desc) (void)dev_free(ix->d_desc);
     if (ix->d_nrows) (void)dev_free(ix->d_nrows);
     if (ix->d_nhdrs) (void)dev_free(ix->d_nhdrs);
+    if (ix->counted) ix->ds->live_indexes.fetch_sub(1, std::memory_order_acq_rel);
     delete ix;
     return AH_OK;
     AH_GUARDED_END
@@ -3774,6 +3776,8 @@ int ah_index_create_from_view(ah_dataset *ds, const ah_forest_view *view, ah_ind
     ix->nv.lut = nullptr;
     ix->nv.lut_len = 0;
     ix->nv.identity_ids = 1;
+    ds->live_indexes.fetch_add(1, std::memory_order_acq_rel);
+    ix->counted = true;
     guard.p = nullptr;
     *out = ix;
     return AH_OK;

@@ -26,6 +26,27 @@ def _ptr(a: Optional[np.ndarray]):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def _update_rows(dimensions: int, up: np.ndarray, vectors) -> Optional[np.ndarray]:
+    if up.size == 0:
+        return None
+    v = _f32(vectors)
+    if v.ndim != 2 or v.shape[1] != dimensions:
+        got = v.shape[1] if v.ndim == 2 else v.size
+        raise _lib.InvalidVecDimension(1, f"invalid vector dimensions, provided {got} but expected {dimensions}")
+    if v.shape[0] != up.size:
+        raise ValueError("ids and vectors disagree on the number of items")
+    return v
+
+
+def _record_pointers(records: Sequence[bytes]):
+    """(pointer array, record length, keep-alive) for the record calls; deliberately misaligned copies, as upload_records."""
+    if not len(records):
+        return None, 0, None
+    rec_len = len(records[0])
+    keep = [C.create_string_buffer(b"\0" + bytes(r), rec_len + 1) for r in records]
+    return (C.c_void_p * len(records))(*[C.addressof(b) + 1 for b in keep]), rec_len, keep
+
+
 class Dataset:
     def __init__(self, distance: type[Distance], dimensions: int, capacity: int, device: int = 0, _handle=None,
                  _finalized: bool = False, _owner=None):
@@ -78,6 +99,27 @@ class Dataset:
         keep = [C.create_string_buffer(b"\0" + bytes(r), rec_len + 1) for r in records]
         ptrs = (C.c_void_p * n)(*[C.addressof(b) + 1 for b in keep])
         _lib.check(_lib.lib().ah_dataset_upload_records(self._h, _ptr(ids), ptrs, rec_len, n))
+
+    # -- updates of a finalized dataset -------------------------------------------------------------
+    def update_vectors(self, remove_ids: Sequence[int], upsert_ids: Sequence[int], vectors) -> None:
+        """ah_dataset_update_vectors: `remove_ids` leave (absent ids are ignored), then `upsert_ids` are written with `vectors`
+        (replacing their rows or adding new ones); both lists ascending.  Only these rows are staged; the dataset then behaves
+        like one staged afresh with the resulting items (DotProduct: call preprocess_dot again)."""
+        rm, up = _u32(remove_ids), _u32(upsert_ids)
+        v = _update_rows(self.dimensions, up, vectors)
+        _lib.check(_lib.lib().ah_dataset_update_vectors(self._h, _ptr(rm), rm.size, _ptr(up), _ptr(v), up.size))
+
+    def update_records(self, remove_ids: Sequence[int], upsert_ids: Sequence[int], records: Sequence[bytes]) -> None:
+        """ah_dataset_update_records: update_vectors with stored records `[0u8][header][vector]` (see upload_records)."""
+        rm, up = _u32(remove_ids), _u32(upsert_ids)
+        ptrs, rec_len, _keep = _record_pointers(records)
+        _lib.check(_lib.lib().ah_dataset_update_records(self._h, _ptr(rm), rm.size, _ptr(up), ptrs, rec_len, up.size))
+
+    def update_paths(self) -> dict:
+        """ah_debug_update_paths: how the updates so far were applied (in place / appended / merged into new arrays)."""
+        a, b, c = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        _lib.check(_lib.lib().ah_debug_update_paths(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return {"in_place": a.value, "appended": b.value, "merged": c.value}
 
     def reserve_build(self, n_trees: int, split_after: int = 0) -> None:
         """ah_dataset_reserve_build: while the records are still being staged, obtain the device memory the first build will
@@ -385,6 +427,18 @@ class DatasetGroup:
 
     def flush(self) -> None:
         _lib.check(_lib.lib().ah_group_upload_flush(self._h))
+
+    def update_vectors(self, remove_ids: Sequence[int], upsert_ids: Sequence[int], vectors) -> None:
+        """Dataset.update_vectors for every member: the upserted rows are gathered once and sent to every device."""
+        rm, up = _u32(remove_ids), _u32(upsert_ids)
+        v = _update_rows(self.dimensions, up, vectors)
+        _lib.check(_lib.lib().ah_group_update_vectors(self._h, _ptr(rm), rm.size, _ptr(up), _ptr(v), up.size))
+
+    def update_records(self, remove_ids: Sequence[int], upsert_ids: Sequence[int], records: Sequence[bytes]) -> None:
+        """Dataset.update_records for every member."""
+        rm, up = _u32(remove_ids), _u32(upsert_ids)
+        ptrs, rec_len, _keep = _record_pointers(records)
+        _lib.check(_lib.lib().ah_group_update_records(self._h, _ptr(rm), rm.size, _ptr(up), ptrs, rec_len, up.size))
 
     def reserve_build(self, n_trees: int, split_after: int = 0) -> None:
         _lib.check(_lib.lib().ah_group_reserve_build(self._h, int(n_trees), int(split_after)))

@@ -359,10 +359,12 @@ class ArroyBuilder:
         ids = np.array(sorted(st.items), dtype=np.uint32)
         n = ids.size
         split_after = self._split_after or w.dimensions
+        if st.index is not None:
+            st.index.close()  # it holds row positions: the dataset can be updated only once it is gone
         st.index = None
-        ds = None
         self._group = None
-        if n and self._devices is not None:
+        ds = self._update_dataset(st) if n else None  # the last build's dataset with this build's item changes, if any
+        if ds is None and n and self._devices is not None:
             from .dataset import DatasetGroup
             vecs = np.stack([st.items[int(i)] for i in ids])
             self._group = DatasetGroup(dist, w.dimensions, n, self._devices)
@@ -371,7 +373,7 @@ class ArroyBuilder:
                 self._group.preprocess_dot()
             self._group.finalize()
             ds = self._group.member(0)  # search and the incremental paths use member 0 (it keeps the group alive)
-        elif n:
+        elif ds is None and n:
             vecs = np.stack([st.items[int(i)] for i in ids])
             ds = Dataset(dist, w.dimensions, n)
             ds.upload_vectors(ids, vecs)
@@ -399,6 +401,31 @@ class ArroyBuilder:
         st.metadata = {"dimensions": w.dimensions, "items": [int(i) for i in ids], "roots": list(st.trees.roots),
                        "distance": dist.name}  # src/writer.rs:611-626
         st.updated.clear()
+
+    def _update_dataset(self, st: "_IndexState") -> Optional[Dataset]:
+        """The dataset (or device group) of the last build with this build's item changes applied (Dataset.update_vectors):
+        remove = updated, upsert = updated & items (src/writer.rs:497-505), so only the changed rows are staged.  None when
+        there is nothing to update — the first build, after `clear()`, another distance / dimension / device list — or
+        when the library refuses the update (e.g. another index on the dataset is still alive): the caller stages afresh."""
+        w, prev = self._w, st.dataset
+        dist = w.database.distance
+        if prev is None or not prev._h or prev.distance is not dist or prev.dimensions != w.dimensions:
+            return None
+        group = prev._owner
+        if (group is None) != (self._devices is None) or (group is not None and group.devices != self._devices):
+            return None
+        remove = np.array(sorted(st.updated), dtype=np.uint32)
+        upsert = np.array([i for i in remove if int(i) in st.items], dtype=np.uint32)
+        vecs = np.stack([st.items[int(i)] for i in upsert]) if upsert.size else np.zeros((0, w.dimensions), np.float32)
+        target = group if group is not None else prev
+        try:
+            target.update_vectors(remove, upsert, vecs)
+        except _lib.ArroyHipError:
+            return None
+        if dist.metric == 3:
+            target.preprocess_dot()  # pre_process_items, src/writer.rs:964-976
+        self._group = group
+        return prev
 
     def _seeds(self, count: int) -> List[int]:
         return [self._rng.getrandbits(64) for _ in range(count)]  # one RNG per task (src/writer.rs:575,795)

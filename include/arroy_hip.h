@@ -16,8 +16,9 @@
  *     src/error.rs:84-85);
  *   - the library never keeps a host pointer past the call that received it (LMDB pages
  *     move after writes, src/writer.rs:512-513); output buffers are caller-allocated;
- *   - a finalized dataset is immutable and may be used by any number of host threads
- *     concurrently (Reader is Sync); `ah_build_forest` is single-caller per dataset;
+ *   - a finalized dataset changes only through ah_dataset_update_* (exclusive calls); between
+ *     updates it is immutable and may be used by any number of host threads concurrently
+ *     (Reader is Sync); `ah_build_forest` is single-caller per dataset;
  *   - results never depend on thread / stream / workgroup scheduling.
  *
  * Numerics contract: every f32 result is bit-identical to arroy's x86-64 AVX+FMA tier
@@ -49,7 +50,9 @@ extern "C" {
                                   have no peer access;
                                   device groups (ah_group_*, ah_build_forest_group_stream): additions only, the number stays 7 —
                                   a caller that needs them looks the symbols up; so are ah_dataset_packed_info and the
-                                  test aid ah_debug_query_screen_verify */
+                                  test aid ah_debug_query_screen_verify;
+                                  v7 additions: updates of a finalized dataset (ah_dataset_update_vectors / _records,
+                                  ah_group_update_vectors / _records, the test aid ah_debug_update_paths) */
 
 /* every entry point is exported from the shared object (it is built with -fvisibility=hidden) */
 #if defined(__GNUC__)
@@ -164,6 +167,32 @@ AH_API int ah_dataset_destroy(ah_dataset *ds);
 /* `DotProduct::preprocess` (src/distance/dot_product.rs:119-165): max norm over all items, then
  * header.norm = max^2, header.extra_dim = sqrt(max^2 - |v|^2) for every item, on device. */
 AH_API int ah_preprocess_dot(ah_dataset *ds, float *out_max_norm);
+
+/* Updates of a finalized dataset (v7 additions): `Writer::build`'s item changes (src/writer.rs:497-505: to_delete = updated,
+ * to_insert = items & updated) applied to the dataset on its device, so that an incremental build re-sends only the
+ * changed rows instead of staging every item again.  First every id of remove_ids leaves (ids that are not present are
+ * ignored, as `descendants -= to_delete` ignores them), then every id of upsert_ids is written, replacing its row or adding
+ * a new one.  Both lists strictly ascending; an id may be in both.  Only the upserted rows cross PCIe, through the staging
+ * ring, codec and header kernels of ah_dataset_upload_vectors / _records.
+ *   - Afterwards the dataset behaves bit for bit like one freshly staged and finalized with the resulting items: rows in
+ *     ascending-id order, the same id -> row table, the same results of every call that reads it.  The copies the library
+ *     derives from the rows (binary16 / int8 screens, the packed scan copy) and its decisions about them are dropped and
+ *     rebuilt on demand; ah_dataset_rerank_stats restarts.
+ *   - DotProduct: the dataset needs ah_preprocess_dot again after every update (AH_ERR_NEED_PREPROCESS until then).
+ *   - All or nothing: bad arguments (unsorted or duplicate ids, a wrong record_len -> AH_ERR_INVALID_DIMENSION, a NULL
+ *     pointer with a non-zero count, a group member -> AH_ERR_INVALID_ARGUMENT, an unfinalized dataset ->
+ *     AH_ERR_NOT_FINALIZED) and failed allocations leave the dataset exactly as it was.
+ *   - Exclusive: refused (AH_ERR_INVALID_ARGUMENT) while any ah_index built on the dataset is alive — an index holds row
+ *     positions.  Any other call on the dataset concurrent with an update is the caller's to prevent, as for staging.
+ *   - The dataset may grow past the capacity given to ah_dataset_create, shrink to no items, and an empty dataset may be
+ *     updated.  A finalized dataset is therefore immutable between updates only. */
+AH_API int ah_dataset_update_vectors(ah_dataset *ds, const uint32_t *remove_ids, size_t n_remove, const uint32_t *upsert_ids,
+                                     const float *vectors, size_t n_upsert);
+AH_API int ah_dataset_update_records(ah_dataset *ds, const uint32_t *remove_ids, size_t n_remove, const uint32_t *upsert_ids,
+                                     const uint8_t *const *record_ptrs, size_t record_len, size_t n_upsert);
+/* Test aid (v7 addition): how the updates of this dataset were applied so far — rows written in place (the id set did not
+ * change), appended after the last row (every new id above the last one, room in the allocation), or merged into new arrays. */
+AH_API int ah_debug_update_paths(ah_dataset *ds, uint64_t *out_in_place, uint64_t *out_appended, uint64_t *out_merged);
 
 /* ------------------------------------------------------------------------------------------
  * Search side (src/reader.rs:376-400, 607-640)
@@ -498,6 +527,13 @@ AH_API int ah_group_size(const ah_group *group, uint32_t *out_n_members);
  * the group. */
 AH_API int ah_group_member(ah_group *group, uint32_t i, ah_dataset **out);
 AH_API int ah_group_destroy(ah_group *group);   /* the members, the pinned ring, everything */
+/* ah_dataset_update_vectors / _records for every member at once (v7 additions): the upserted rows go through the group's
+ * pinned ring once, one transfer per member, and each member merges on its own device.  Two phases: every member's
+ * buffers are obtained and filled first, then all members commit; a failure on any member leaves every member unchanged. */
+AH_API int ah_group_update_vectors(ah_group *group, const uint32_t *remove_ids, size_t n_remove, const uint32_t *upsert_ids,
+                                   const float *vectors, size_t n_upsert);
+AH_API int ah_group_update_records(ah_group *group, const uint32_t *remove_ids, size_t n_remove, const uint32_t *upsert_ids,
+                                   const uint8_t *const *record_ptrs, size_t record_len, size_t n_upsert);
 
 /* One forest on every member: `options->n_trees` / `tree_seeds` describe the WHOLE forest; tree t is built on member
  * t mod G by one host thread per member (each holds its own device; options->max_host_threads is split between them; the
