@@ -151,6 +151,7 @@ SIGNATURES = {
     "ah_dataset_reserve_build": (C.c_int, [_VP, C.c_uint32, C.c_uint32]),
     "ah_dataset_rerank_stats": (C.c_int, [_VP, C.POINTER(AhRerankStats), C.c_int]),
     "ah_dataset_packed_info": (C.c_int, [_VP, C.POINTER(C.c_int), C.POINTER(C.c_uint64)]),
+    "ah_dataset_packed_rows": (C.c_int, [_VP, C.POINTER(C.c_int), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "ah_debug_query_screen_verify": (C.c_int, [_VP, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int]),
     "ah_dataset_len": (C.c_int, [_VP, C.POINTER(C.c_uint64)]),
     "ah_dataset_item_vector": (C.c_int, [_VP, C.c_uint32, _F32P]),

@@ -2426,6 +2426,17 @@ int ah_dataset_packed_info(ah_dataset *ds, int *out_present, uint64_t *out_raw_r
     AH_GUARDED_END
 }
 
+int ah_dataset_packed_rows(ah_dataset *ds, int *out_present, uint64_t *out_raw_rows, uint64_t *out_grid_rows) {
+    AH_GUARDED("ah_dataset_packed_rows")
+    AH_REQUIRE(ds, AH_ERR_INVALID_ARGUMENT, "dataset is NULL");
+    std::lock_guard<std::mutex> lk(ds->mu);
+    if (out_present) *out_present = ds->d_packed ? 1 : 0;
+    if (out_raw_rows) *out_raw_rows = ds->d_packed ? ds->packed_raw_rows : 0;
+    if (out_grid_rows) *out_grid_rows = ds->d_packed ? ds->packed_grid_rows : 0;
+    return AH_OK;
+    AH_GUARDED_END
+}
+
 int ah_debug_query_screen_verify(ah_dataset *ds, uint64_t *out_checked, uint64_t *out_violations, int reset) {
     AH_GUARDED("ah_debug_query_screen_verify")
     AH_REQUIRE(ds, AH_ERR_INVALID_ARGUMENT, "dataset is NULL");

@@ -142,6 +142,7 @@ inline int guarded(const char *what, F &&f) noexcept {
     X(TAIL_RATIO, "AH_BUILD_TAIL_RATIO", 76)    /* ... each group this many percent of the trees of the group before it (100: equal groups): a group's ids and normals take ~0.76 of the time its kernels do, and what is left after the last launch is the LAST group's */ \
     X(SCAN_BLOCKS, "AH_SCAN_BLOCKS", 0)         /* grid cap of the distance scan (0 = built-in) */                        \
     X(SCAN_PACKED, "AH_SCAN_PACKED", -1)        /* f32 scan from the 28-bit packed copy: 0 never, 1 always, -1 where it saves bytes */ \
+    X(SCAN_GRID, "AH_SCAN_GRID", 1)             /* read when the packed copy is made: 0 = no row is stored in the 24-bit fixed-point (grid) form */ \
     X(MANHATTAN_ROWS, "AH_MANHATTAN_ROWS", 1)                                                                            \
     X(RERANK_INVERT, "AH_RERANK_INVERT", -1)    /* 0 / 1: never / always the row-major re-rank of big submissions */      \
     X(RERANK_SMALL, "AH_RERANK_SMALL", 1)       /* 0: ah_rerank_by_vector / _by_item never take the one-launch selection of short lists (k_topk_small) */ \
@@ -314,8 +315,16 @@ struct ScreenView {
 // Elements of a piece past block B - 1 are zeros.  row_exp[r] = e_max (the row's largest biased exponent) | kPackedZeros
 // when some element has exponent field 0, or kPackedRaw: the row holds an inf / NaN or a normal element 15 or more
 // binades below e_max and is read from rows_f32.
+// A GRID row (row_exp[r] = e_max | kPackedGrid; tunable AH_SCAN_GRID, decided per row when the copy is made) needs no code
+// plane: 25 <= e_max <= 253, no inf / NaN / non-zero denormal, and every element is +-0 or an integer multiple of the unit
+// 2^(e_max - 22) with a magnitude below 2^23 (a normal element of exponent e has the low e_max - e + 1 bits of its 24-bit
+// significand clear).  Its lo / hi planes hold sign | 23-bit magnitude (significand >> (e_max - e + 1); 0 for +-0) where a
+// plain row has sign | mantissa, its code pieces are never written and never read: the scan is served by the first
+// code_off bytes of the row.  Such a row may spread over 22 binades: rows that the 28-bit rule leaves raw can be grid rows.
 static constexpr uint16_t kPackedRaw = 0xFFu;
 static constexpr uint16_t kPackedZeros = 0x100u;
+static constexpr uint16_t kPackedGrid = 0x200u;
+static constexpr uint32_t kGridMinExp = 25u, kGridMaxExp = 253u;  // the unit is a normal number, 2^(e_max + 1) finite
 struct PackedView {
     const uint8_t *rows = nullptr;  // nullptr: no copy, the scan reads rows_f32
     const uint16_t *row_exp = nullptr;
@@ -430,6 +439,7 @@ struct ah_dataset {
     uint8_t *d_packed = nullptr;
     uint16_t *d_packed_exp = nullptr;
     uint64_t packed_raw_rows = 0;
+    uint64_t packed_grid_rows = 0;
     std::atomic<bool> packed_decided{false};
     std::atomic<bool> packed_ready{false};
     // AH_SCREEN_VERIFY=1: {candidates checked, candidates whose reference distance fell outside [L, U]} of the search and

@@ -293,6 +293,81 @@ __device__ __forceinline__ float octet_reduce_packed(const float4 *s_b4, const u
     return octet_finish(acc);
 }
 
+// One element of a grid row (common.h: kPackedGrid) back to its f32 bits.  The lo / hi planes hold sign | 23-bit magnitude m
+// and the value is m x 2^(e_max - 22 - 127).  two = the bits of 2^(e_max + 1): with m in its mantissa field that is
+// 2^(e_max + 1) + m x unit, and subtracting 2^(e_max + 1) leaves m x unit exactly (the difference is representable, and
+// its smallest non-zero magnitude, the unit, is a normal number).  m = 0 gives +0; the sign goes on last, so -0 survives.
+// Four VALU operations, as many as packed_value, and no code dword.
+template <uint32_t SEL>
+__device__ __forceinline__ float grid_value(uint32_t lo, uint32_t hi, uint32_t two) {
+    const uint32_t a = __builtin_amdgcn_perm(hi, lo, SEL);  // as packed_value: [lo16, hi byte, hi byte]
+    uint32_t r, s;
+    asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(r) : "s"(0x007FFFFFu), "v"(a), "v"(two));  // magnitude from a, exponent from two
+    const float f = f_sub(__uint_as_float(r), __uint_as_float(two));
+    asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(s) : "s"(0x80000000u), "v"(a), "v"(__float_as_uint(f)));  // sign from a
+    return __uint_as_float(s);
+}
+template <int T>
+__device__ __forceinline__ float4 grid_block(const uint4 (&lo)[4], const uint4 (&hi)[2], uint32_t two) {
+    constexpr int P = T & 1;
+    const uint4 l = lo[T >> 1];
+    const uint32_t l0 = P ? l.z : l.x, l1 = P ? l.w : l.y;
+    const uint4 h = hi[T >> 2];
+    const uint32_t hw = (T & 3) == 0 ? h.x : (T & 3) == 1 ? h.y : (T & 3) == 2 ? h.z : h.w;
+    return make_float4(grid_value<0x04040100u>(l0, hw, two), grid_value<0x05050302u>(l0, hw, two),
+                       grid_value<0x06060100u>(l1, hw, two), grid_value<0x07070302u>(l1, hw, two));
+}
+// octet_reduce_packed on a grid row: the same loads minus the code pieces (per 8 blocks 4 lo + 2 hi of 16 B per lane; a last
+// group of m < 8 blocks only the pieces that hold them), the same fma_step chain in the same order — the same bits.
+template <int OP>
+__device__ __forceinline__ float octet_reduce_packed_grid(const float4 *s_b4, const uint8_t *prow, uint32_t hi_off, uint32_t blocks,
+                                                          uint32_t emax, uint32_t j) {
+    const uint4 *lo4 = reinterpret_cast<const uint4 *>(prow) + j;
+    const uint4 *hi4 = reinterpret_cast<const uint4 *>(prow + hi_off) + j;
+    const float4 *b4 = s_b4 + j;
+    const uint32_t two = (emax + 1u) << 23;
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    const uint32_t full = blocks / 8;
+#pragma unroll 1
+    for (uint32_t o = 0; o < full; o++) {
+        uint4 lo[4], hi[2];
+#pragma unroll
+        for (int u = 0; u < 4; u++) lo[u] = ld_stream_u4(lo4 + (4 * o + u) * 8);
+#pragma unroll
+        for (int u = 0; u < 2; u++) hi[u] = ld_stream_u4(hi4 + (2 * o + u) * 8);
+        const float4 *bq = b4 + o * 64;
+        fma_step<OP>(acc, bq[0], grid_block<0>(lo, hi, two));
+        fma_step<OP>(acc, bq[8], grid_block<1>(lo, hi, two));
+        fma_step<OP>(acc, bq[16], grid_block<2>(lo, hi, two));
+        fma_step<OP>(acc, bq[24], grid_block<3>(lo, hi, two));
+        fma_step<OP>(acc, bq[32], grid_block<4>(lo, hi, two));
+        fma_step<OP>(acc, bq[40], grid_block<5>(lo, hi, two));
+        fma_step<OP>(acc, bq[48], grid_block<6>(lo, hi, two));
+        fma_step<OP>(acc, bq[56], grid_block<7>(lo, hi, two));
+    }
+    const uint32_t m = blocks - 8 * full;
+    if (m) {  // the last group of a row whose blocks are not a multiple of 8
+        const uint32_t o = full;
+        const uint4 z = make_uint4(0u, 0u, 0u, 0u);
+        uint4 lo[4] = {z, z, z, z}, hi[2] = {z, z};
+#pragma unroll
+        for (uint32_t u = 0; u < 4; u++)
+            if (2 * u < m) lo[u] = ld_stream_u4(lo4 + (4 * o + u) * 8);
+#pragma unroll
+        for (uint32_t u = 0; u < 2; u++)
+            if (4 * u < m) hi[u] = ld_stream_u4(hi4 + (2 * o + u) * 8);
+        const float4 *bq = b4 + o * 64;
+        fma_step<OP>(acc, bq[0], grid_block<0>(lo, hi, two));
+        if (m > 1) fma_step<OP>(acc, bq[8], grid_block<1>(lo, hi, two));
+        if (m > 2) fma_step<OP>(acc, bq[16], grid_block<2>(lo, hi, two));
+        if (m > 3) fma_step<OP>(acc, bq[24], grid_block<3>(lo, hi, two));
+        if (m > 4) fma_step<OP>(acc, bq[32], grid_block<4>(lo, hi, two));
+        if (m > 5) fma_step<OP>(acc, bq[40], grid_block<5>(lo, hi, two));
+        if (m > 6) fma_step<OP>(acc, bq[48], grid_block<6>(lo, hi, two));
+    }
+    return octet_finish(acc);
+}
+
 // SSE tier (16 <= dims < 32, simple_sse.rs) and scalar tier (dims < 16, simple.rs:49-51,81-83),
 // executed by ONE thread.  16 chains, multiply THEN add (never fused); hsum128 = (x0+x2)+(x1+x3).
 template <int OP>

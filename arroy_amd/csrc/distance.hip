@@ -96,7 +96,8 @@ __device__ __forceinline__ float f32_epilogue(float r, const float *qhdr, const 
     return r;                                 // euclidean.rs:45-47 / manhattan.rs:44-46
 }
 
-// PACKED (ungathered only): rows with a packed copy (PackedView) are read from it, raw rows from rows_f32, octet by octet.
+// PACKED (ungathered only): rows with a packed copy (PackedView) are read from it — grid rows from its lo / hi planes alone —
+// raw rows from rows_f32, octet by octet.
 // Without it the kernel is the plain f32 scan — a separate instantiation, so that scans with no copy keep its registers
 // (62 VGPRs, 8 waves per SIMD; the packed one needs 98).
 template <int METRIC, bool GATHER, bool PACKED>
@@ -132,7 +133,9 @@ __device__ __forceinline__ void f32_scan(const DataView &dv, const PackedView &p
         } else if constexpr (PACKED) {
             const uint32_t ex = pk.row_exp[row];
             const uint8_t *pr = pk.rows + row * pk.pitch;
-            if (ex == kPackedRaw)
+            if (ex & kPackedGrid)
+                r = octet_reduce_packed_grid<OP>(s_q4, pr, pk.hi_off, dv.dims >> 5, ex & 0xFFu, j);
+            else if (ex == kPackedRaw)
                 r = octet_reduce_stream<OP>(s_q4, rp, dv.dims, j);
             else if (ex & kPackedZeros)
                 r = octet_reduce_packed<OP, true>(s_q4, pr, pk.hi_off, pk.code_off, dv.dims >> 5, ex & 0xFFu, j);
@@ -487,26 +490,33 @@ int launch_distances(const DataView &dv, const void *d_qvec, const float *d_qhdr
 // The packed copy of the rows (common.h: PackedView).  One octet per row, lane j on the elements octet_reduce_packed gives
 // it: a first pass finds e_max, the smallest exponent of a normal element, inf / NaN and exponent-0 elements; a second
 // writes lane j's 16-byte share of every piece (elements past the last block as zeros).  Raw rows get only their row_exp.
+// grid != 0: the first pass also finds the lowest set significand bit of the row on the scale of e_max (a normal element of
+// exponent e whose significand has z trailing zeros: e + z); a row is a grid row (common.h: kPackedGrid) when that is at
+// least e_max + 1 — which also keeps every element within 22 binades of e_max — and gets the fixed-point lo / hi planes and
+// no code pieces.  counts[0] += raw rows, counts[1] += grid rows.
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kBlock) void k_pack_rows(DataView dv, uint8_t *__restrict__ rows, uint16_t *__restrict__ row_exp,
-                                                      PackedView lay, unsigned long long *raw_rows) {
+                                                      PackedView lay, int grid, unsigned long long *counts) {
     const uint32_t j = threadIdx.x & 7u;
     const uint32_t blocks = dv.dims >> 5;
     const uint64_t n_octets = ((uint64_t)gridDim.x * blockDim.x) >> 3;
-    uint32_t raw_here = 0;
+    uint32_t raw_here = 0, grid_here = 0;
     for (uint64_t r = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 3; r < dv.n; r += n_octets) {
         const float4 *src = reinterpret_cast<const float4 *>(dv.rows_f32 + r * dv.pitch) + j;
-        uint32_t emax = 0, emin = 255, special = 0, zeros = 0;
+        uint32_t emax = 0, emin = 255, special = 0, zeros = 0, lowbit = 0xFFFFu, denormal = 0;
         for (uint32_t k = 0; k < blocks; k++) {
             const float4 x = src[k * 8];
             const float v[4] = {x.x, x.y, x.z, x.w};
 #pragma unroll
             for (int i = 0; i < 4; i++) {
-                const uint32_t e = (__float_as_uint(v[i]) >> 23) & 255u;
+                const uint32_t b = __float_as_uint(v[i]);
+                const uint32_t e = (b >> 23) & 255u;
                 emax = max(emax, e);
                 if (e != 0u) emin = min(emin, e);
                 special |= e == 255u;
                 zeros |= e == 0u;
+                if (e != 0u) lowbit = min(lowbit, e + (uint32_t)__builtin_ctz(b | 0x800000u));
+                denormal |= e == 0u && (b & 0x7FFFFFu) != 0u;
             }
         }
 #pragma unroll
@@ -515,6 +525,45 @@ __global__ __launch_bounds__(kBlock) void k_pack_rows(DataView dv, uint8_t *__re
             emin = min(emin, (uint32_t)__shfl_xor((int)emin, m));
             special |= (uint32_t)__shfl_xor((int)special, m);
             zeros |= (uint32_t)__shfl_xor((int)zeros, m);
+            lowbit = min(lowbit, (uint32_t)__shfl_xor((int)lowbit, m));
+            denormal |= (uint32_t)__shfl_xor((int)denormal, m);
+        }
+        uint8_t *dst = rows + r * lay.pitch;
+        if (grid && !special && !denormal && emax >= kGridMinExp && emax <= kGridMaxExp && lowbit >= emax + 1u) {
+            if (j == 0) row_exp[r] = (uint16_t)(emax | kPackedGrid);
+            grid_here += j == 0;
+            for (uint32_t o = 0; o < (blocks + 7) / 8; o++) {
+                uint32_t lo[16], hi[8];
+#pragma unroll
+                for (int w = 0; w < 16; w++) lo[w] = 0u;
+#pragma unroll
+                for (int w = 0; w < 8; w++) hi[w] = 0u;
+#pragma unroll
+                for (int t = 0; t < 8; t++) {
+                    const uint32_t k = 8 * o + t;
+                    const float4 x = k < blocks ? src[k * 8] : make_float4(0.f, 0.f, 0.f, 0.f);
+                    const float v[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+                    for (int i = 0; i < 4; i++) {
+                        const uint32_t b = __float_as_uint(v[i]);
+                        const uint32_t e = (b >> 23) & 255u;
+                        // (e_max - e + 1 is 1 .. 23 for a normal element of a grid row; exponent field 0 is +-0 here)
+                        const uint32_t mag = e == 0u ? 0u : ((b & 0x7FFFFFu) | 0x800000u) >> ((emax - e + 1u) & 31u);
+                        const int u = (t & 1) * 4 + i;
+                        lo[(t >> 1) * 4 + u / 2] |= (mag & 0xFFFFu) << (16 * (u & 1));
+                        hi[t] |= (((b >> 24) & 0x80u) | (mag >> 16)) << (8 * i);
+                    }
+                }
+                uint4 *lo4 = reinterpret_cast<uint4 *>(dst) + j;
+                uint4 *hi4 = reinterpret_cast<uint4 *>(dst + lay.hi_off) + j;
+#pragma unroll
+                for (uint32_t u = 0; u < 4; u++)
+                    if (8 * o + 2 * u < blocks) lo4[(4 * o + u) * 8] = make_uint4(lo[4 * u], lo[4 * u + 1], lo[4 * u + 2], lo[4 * u + 3]);
+#pragma unroll
+                for (uint32_t u = 0; u < 2; u++)
+                    if (8 * o + 4 * u < blocks) hi4[(2 * o + u) * 8] = make_uint4(hi[4 * u], hi[4 * u + 1], hi[4 * u + 2], hi[4 * u + 3]);
+            }
+            continue;
         }
         const bool raw = special || (int)emax - (int)emin >= 15;
         if (j == 0) row_exp[r] = raw ? kPackedRaw : (uint16_t)(emax | (zeros ? kPackedZeros : 0u));
@@ -522,7 +571,6 @@ __global__ __launch_bounds__(kBlock) void k_pack_rows(DataView dv, uint8_t *__re
             raw_here += j == 0;
             continue;
         }
-        uint8_t *dst = rows + r * lay.pitch;
         for (uint32_t o = 0; o < (blocks + 7) / 8; o++) {
             uint32_t lo[16], hi[8], cd[4];
 #pragma unroll
@@ -560,13 +608,14 @@ __global__ __launch_bounds__(kBlock) void k_pack_rows(DataView dv, uint8_t *__re
             c4[o * 8] = make_uint4(cd[0], cd[1], cd[2], cd[3]);
         }
     }
-    if (raw_here) atomicAdd(raw_rows, (unsigned long long)raw_here);
+    if (raw_here) atomicAdd(counts, (unsigned long long)raw_here);
+    if (grid_here) atomicAdd(counts + 1, (unsigned long long)grid_here);
 }
 
-static int launch_pack_rows(const DataView &dv, uint8_t *rows, uint16_t *row_exp, const PackedView &lay,
-                            unsigned long long *d_raw, hipStream_t s) {
+static int launch_pack_rows(const DataView &dv, uint8_t *rows, uint16_t *row_exp, const PackedView &lay, bool grid_rows,
+                            unsigned long long *d_counts, hipStream_t s) {
     const unsigned grid = (unsigned)std::min<uint64_t>((dv.n + 31) / 32, 1u << 16);
-    hipLaunchKernelGGL(k_pack_rows, dim3(grid), dim3(kBlock), 0, s, dv, rows, row_exp, lay, d_raw);
+    hipLaunchKernelGGL(k_pack_rows, dim3(grid), dim3(kBlock), 0, s, dv, rows, row_exp, lay, grid_rows ? 1 : 0, d_counts);
     AH_HIP(hipGetLastError());
     return AH_OK;
 }
@@ -577,6 +626,8 @@ static int launch_pack_rows(const DataView &dv, uint8_t *rows, uint16_t *row_exp
 // the pieces' rounding eats the saving — and keeps it while at most a quarter of the rows are raw.  1 makes and keeps it
 // for any Cosine / Euclidean / DotProduct dataset with dims % 32 == 0, whatever the size and the data.  The cheap checks
 // come before the dataset lock; a decision against the copy (or a failed allocation) is remembered by the automatic mode.
+// AH_SCAN_GRID (default 1) is read when the copy is made: 0 classifies no row as a grid row, and the copy is the 28-bit one
+// for every row.  Grid rows do not count as raw.
 static constexpr uint64_t kPackedMinRows = 65536;
 static bool packed_pays(uint32_t dims) { return 16ull * (packed_layout(dims).pitch + 2) <= 15ull * 4 * dims; }
 PackedView ensure_packed(ah_dataset *ds, hipStream_t s) {
@@ -594,15 +645,17 @@ PackedView ensure_packed(ah_dataset *ds, hipStream_t s) {
             ds->packed_decided.store(true, std::memory_order_release);
             uint8_t *rows = nullptr;
             uint16_t *row_exp = nullptr;
-            unsigned long long *d_raw = nullptr, h_raw = 0;
+            unsigned long long *d_raw = nullptr, h_counts[2] = {0, 0};  // raw rows, grid rows
+            const bool grid_rows = tun(TUN_SCAN_GRID) != 0;
             // (optional allocations: a full device does not make them empty the cache)
             bool ok = dev_malloc((void **)&rows, ds->n * (size_t)pk.pitch, true) == hipSuccess &&
                       dev_malloc((void **)&row_exp, ds->n * 2, true) == hipSuccess &&
-                      dev_malloc((void **)&d_raw, 8, true) == hipSuccess && hipMemsetAsync(d_raw, 0, 8, s) == hipSuccess;
-            ok = ok && launch_pack_rows(ds->view(), rows, row_exp, pk, d_raw, s) == AH_OK;
-            ok = ok && hipMemcpyAsync(&h_raw, d_raw, 8, hipMemcpyDeviceToHost, s) == hipSuccess;
+                      dev_malloc((void **)&d_raw, 16, true) == hipSuccess && hipMemsetAsync(d_raw, 0, 16, s) == hipSuccess;
+            ok = ok && launch_pack_rows(ds->view(), rows, row_exp, pk, grid_rows, d_raw, s) == AH_OK;
+            ok = ok && hipMemcpyAsync(h_counts, d_raw, 16, hipMemcpyDeviceToHost, s) == hipSuccess;
             // (other contexts' streams read the copy once it is published: it is complete before that)
             ok = hipStreamSynchronize(s) == hipSuccess && ok;
+            const unsigned long long h_raw = h_counts[0];
             ok = ok && (mode == 1 || h_raw <= ds->n / 4);
             if (d_raw) (void)dev_free(d_raw);
             if (!ok) {
@@ -614,6 +667,7 @@ PackedView ensure_packed(ah_dataset *ds, hipStream_t s) {
             ds->d_packed = rows;
             ds->d_packed_exp = row_exp;
             ds->packed_raw_rows = h_raw;
+            ds->packed_grid_rows = h_counts[1];
             ds->packed_ready.store(true, std::memory_order_release);
         }
     }

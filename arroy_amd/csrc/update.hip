@@ -500,6 +500,7 @@ void commit(MemberUpdate *mu, const Plan &p) {
     ds->screen8_decided = false;
     ds->screen_alloc_failed = false;
     ds->packed_raw_rows = 0;
+    ds->packed_grid_rows = 0;
     ds->packed_decided.store(false, std::memory_order_release);
     ds->rerank8_fails.store(0, std::memory_order_relaxed);
     ds->rerank8_seen.store(0, std::memory_order_relaxed);

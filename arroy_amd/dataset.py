@@ -217,6 +217,12 @@ class Dataset:
         _lib.check(_lib.lib().ah_dataset_packed_info(self._h, C.byref(present), C.byref(raw)))
         return {"present": bool(present.value), "raw_rows": raw.value}
 
+    def packed_rows(self) -> dict:
+        """ah_dataset_packed_rows: packed_info plus the rows of the copy stored in the 24-bit fixed-point (grid) form."""
+        present, raw, grid = C.c_int(0), C.c_uint64(0), C.c_uint64(0)
+        _lib.check(_lib.lib().ah_dataset_packed_rows(self._h, C.byref(present), C.byref(raw), C.byref(grid)))
+        return {"present": bool(present.value), "raw_rows": raw.value, "grid_rows": grid.value}
+
     def query_screen_verify(self, reset: bool = False) -> dict:
         """ah_debug_query_screen_verify: under the tunable AH_SCREEN_VERIFY=1, the candidates of the search and re-rank screens
         checked in f32, and those whose reference distance fell outside the screen's interval (must be 0)."""

@@ -49,8 +49,8 @@ extern "C" {
                                   ah_dataset_replicate falls back to a copy through pinned host memory when the two devices
                                   have no peer access;
                                   device groups (ah_group_*, ah_build_forest_group_stream): additions only, the number stays 7 —
-                                  a caller that needs them looks the symbols up; so are ah_dataset_packed_info and the
-                                  test aid ah_debug_query_screen_verify;
+                                  a caller that needs them looks the symbols up; so are ah_dataset_packed_info,
+                                  ah_dataset_packed_rows and the test aid ah_debug_query_screen_verify;
                                   v7 additions: updates of a finalized dataset (ah_dataset_update_vectors / _records,
                                   ah_group_update_vectors / _records, the test aid ah_debug_update_paths) */
 
@@ -248,6 +248,10 @@ AH_API int ah_dataset_rerank_stats(ah_dataset *ds, ah_rerank_stats *out, int res
  * *out_raw_rows = its rows kept in f32 (an inf / NaN, or an exponent spread of 15 binades or more).  Either pointer may be
  * NULL.  Made by the first ah_distances_by_* / ah_bench_scan call over all rows, never by a build or a search. */
 AH_API int ah_dataset_packed_info(ah_dataset *ds, int *out_present, uint64_t *out_raw_rows);
+/* The same, plus *out_grid_rows = the rows of the copy stored in the 24-bit fixed-point form (tunable AH_SCAN_GRID, read when
+ * the copy is made: rows whose elements are all integer multiples of one power of two, magnitudes below 2^23); they are not
+ * among the raw rows.  Any pointer may be NULL.  An addition to v7: a caller that needs it looks the symbol up. */
+AH_API int ah_dataset_packed_rows(ah_dataset *ds, int *out_present, uint64_t *out_raw_rows, uint64_t *out_grid_rows);
 /* Test aid: the counters of the tunable AH_SCREEN_VERIFY=1 for the query-side screens (the certified top-k screen of
  * ah_search_batch and ah_rerank_batch on this dataset).  Under it every candidate with a finite screen value is also evaluated
  * in the reference's f32 arithmetic: *out_checked counts those candidates, *out_violations the ones whose reference distance
