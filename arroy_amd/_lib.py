@@ -116,6 +116,15 @@ class AhSearchStats(C.Structure):
         "screen8_retried_chunks", "descent_multi")]
 
 
+class AhFilterStats(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in (
+        "calls", "uniform_batches", "mixed_batches", "uniform_queries", "mixed_queries", "filters_created", "filters_alive",
+        "leaf_kept_passes")]
+
+
+NO_FILTER = 0xFFFFFFFF  # AH_NO_FILTER: a query of ah_search_batch_filters under no filter
+
+
 class AhStreamNode(C.Structure):
     _fields_ = [("id", C.c_uint32), ("tree", C.c_uint32), ("kind", C.c_uint8), ("has_normal", C.c_uint8), ("reserved", C.c_uint16),
                 ("left", C.c_uint32), ("right", C.c_uint32), ("count", C.c_uint32), ("depth", C.c_uint32),
@@ -193,6 +202,13 @@ SIGNATURES = {
                                   C.c_int, _U32P, _F32P, _U32P]),
     "ah_index_search_stats": (C.c_int, [_VP, C.POINTER(AhSearchStats), C.c_int]),
     "ah_route_items": (C.c_int, [_VP, _U32P, C.c_size_t, _U64P, _U32P]),
+    # resident candidate filters, one per query in a batched call
+    "ah_filter_create": (C.c_int, [_VP, _U32P, C.c_size_t, C.POINTER(C.c_void_p)]),
+    "ah_filter_info": (C.c_int, [_VP, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "ah_filter_destroy": (C.c_int, [_VP]),
+    "ah_search_batch_filters": (C.c_int, [_VP, _F32P, _U32P, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t,
+                                          C.POINTER(C.c_void_p), C.c_size_t, _U32P, _U32P, _F32P, _U32P]),
+    "ah_index_filter_stats": (C.c_int, [_VP, C.POINTER(AhFilterStats), C.c_int]),
     "ah_bench_scan": (C.c_int, [_VP, C.c_uint32, C.c_uint64, C.c_uint32, _F32P, C.POINTER(C.c_double)]),
     "ah_bench_memcpy": (C.c_int, [C.c_int, C.c_uint64, C.c_uint32, C.POINTER(C.c_double)]),
     "ah_bench_read": (C.c_int, [C.c_int, C.c_uint64, C.c_uint32, C.POINTER(C.c_double)]),

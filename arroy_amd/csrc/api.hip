@@ -360,6 +360,13 @@ size_t dev_cache_live_bytes(int device) {
     return n;
 }
 
+size_t dev_block_bytes(const void *p) {
+    std::lock_guard<std::mutex> lk(g_dev_mu);
+    for (const DevBlock &b : g_dev_live)
+        if (b.p == p) return b.bytes;
+    return 0;
+}
+
 size_t dev_cache_trim(int device) {
     NoFailScope no_fail;
     std::vector<DevBlock> drop;

@@ -178,6 +178,7 @@ inline int guarded(const char *what, F &&f) noexcept {
     X(REPLICATE_HOST_BOUNCE, "AH_REPLICATE_HOST_BOUNCE", 0) /* 1: ah_dataset_replicate copies through pinned host memory even where peer access works (test aid) */ \
     X(RERANK_TIMING, "AH_RERANK_TIMING", 0)     /* 1: ah_rerank_batch accounts its wall time by phase (ah_dataset_rerank_stats) */ \
     X(SEARCH_SCREEN, "AH_SEARCH_SCREEN", 1)     /* 0: the re-rank of ah_search_batch never screens its candidates (f32 rows for all) */ \
+    X(SEARCH_FILTER_GROUP_MIN, "AH_SEARCH_FILTER_GROUP_MIN", 16) /* ah_search_batch_filters: the queries of one filter form a sub-batch of their own from this many on; fewer share a mixed sub-batch */ \
     X(HOST_THREADS, "AH_HOST_THREADS", 8)       /* host threads one build may use at a time for its output path */        \
     X(DEVICE_CACHE_MB, "AH_DEVICE_CACHE_MB", 98304) /* idle HBM the caching allocator keeps while a dataset lives on the device */ \
     X(HOST_CACHE_MB, "AH_HOST_CACHE_MB", 16384) /* committed host memory of destroyed forests kept for the next build */   \
@@ -243,6 +244,7 @@ void numa_prefer_node(void *p, size_t bytes, int node);
 void pinned_spare_fill(int device, size_t bytes);  // api.hip: a pinned block obtained ahead of the context that will want it
 size_t pinned_spare_trim();                  // ... given back if nobody took it; returns its bytes
 size_t dev_cache_live_bytes(int device);     // bytes handed out and not yet freed (ah_device_cache_stats)
+size_t dev_block_bytes(const void *p);       // ... those of them behind one live block (a recycled block may exceed what was asked for)
 // test aid (AH_FAIL_ALLOC_AFTER): true when THIS allocation is the one that must fail
 bool fail_alloc_tick();
 hipError_t dev_free(void *p);

@@ -15,6 +15,7 @@
 // once).
 #include <algorithm>
 #include <chrono>
+#include <memory>
 #include <new>
 
 #include "common.h"
@@ -55,6 +56,11 @@ enum SearchStatSlot {
     SS_SCREENED, SS_SURVIVORS, SS_BLOCK, SS_VISIT_TOTAL, SS_N_UNITS, SS_DONE, SS_MULTI, SS_WORDS = 16
 };
 
+struct FilterSlot {  // what an ah_filter holds on the device
+    const uint32_t *bits;
+    uint64_t len_bits;
+    const uint32_t *leaf_kept;
+};
 struct SearchParams {
     uint32_t *stats;              // SS_WORDS words (may be nullptr)
     const DNode *nodes;
@@ -66,7 +72,22 @@ struct SearchParams {
     uint32_t search_k;            // already multiplied by the oversampling, clamped to the blob size
     uint32_t nns_stride;          // capacity of one query's candidate buffer
     const uint32_t *leaf_kept;    // per node: ids of the leaf the filter keeps (k_leaf_kept), or nullptr
+    // A MIXED sub-batch of ah_search_batch_filters (filter_bits / leaf_kept above are null then): the filters of the call and,
+    // per query of the sub-batch, which of them it is under (AH_NO_FILTER: none).  Every descent resolves its own query's
+    // filter into its copy of this struct before it starts (resolve_filter).
+    const FilterSlot *filter_table;
+    const uint32_t *filter_of_query;
 };
+// The filter of query q of a mixed sub-batch -> sp.filter_bits / filter_len_bits / leaf_kept.  q is uniform over a block
+// (k_descend_wave, k_descend_block: scalar loads) or over an octet (k_descend<.., true>).
+__device__ __forceinline__ void resolve_filter(SearchParams &sp, uint32_t q) {
+    const uint32_t slot = sp.filter_of_query[q];
+    if (slot == AH_NO_FILTER) return;  // (all three are null / 0 in a mixed sub-batch)
+    const FilterSlot f = sp.filter_table[slot];
+    sp.filter_bits = f.bits;
+    sp.filter_len_bits = f.len_bits;
+    sp.leaf_kept = f.leaf_kept;
+}
 
 __device__ __forceinline__ float key_to_dist(uint32_t k) {
     if (k == 0xFFFFFFFFu) return __uint_as_float(0x7FC00000u);
@@ -175,7 +196,8 @@ __device__ __forceinline__ uint32_t copy_filtered(const SearchParams &sp, const 
 
 // One octet per query.  HEAP_GLOBAL = false: queue in LDS (kHeapLds entries), overflow reported;
 // true: queue in global memory with `heap_cap` entries per query (re-run of the overflowed queries).
-template <bool HEAP_GLOBAL>
+// MIXED: the octets of a wave may be under different candidate filters (a mixed sub-batch: SearchParams::filter_table).
+template <bool HEAP_GLOBAL, bool MIXED = false>
 __global__ __launch_bounds__(64) void k_descend(DataView nv, SearchParams sp, const uint32_t *__restrict__ query_list,
                                                 uint32_t n_list, const uint8_t *__restrict__ qvecs, uint64_t qstride,
                                                 const float *__restrict__ qhdrs, uint32_t *__restrict__ nns,
@@ -188,6 +210,7 @@ __global__ __launch_bounds__(64) void k_descend(DataView nv, SearchParams sp, co
     bool live = slot < n_list;
     const uint32_t q = live ? (query_list ? query_list[slot] : slot) : 0u;
     if (only_flagged && live) live = overflow[q] != 0;  // the queries k_descend_wave left (its capacities, ties)
+    if (MIXED && live) resolve_filter(sp, q);  // (copy_filtered keeps to the octet: its comment)
     uint64_t *heap = HEAP_GLOBAL ? heap_global + (uint64_t)slot * heap_cap : s_heap + o * kHeapLds;
     const uint32_t cap = HEAP_GLOBAL ? heap_cap : kHeapLds;
     const void *qvec = qvecs + (uint64_t)q * qstride;
@@ -304,6 +327,7 @@ __global__ __launch_bounds__(64) void k_descend_wave(DataView nv, SearchParams s
     uint32_t *s_pos = s_sorted_n + 8 * kWaveLeaves, *s_sorted_node = s_pos + 8 * kWaveLeaves;
     const uint32_t q = blockIdx.x, o = threadIdx.x >> 3, j = threadIdx.x & 7u, lane = threadIdx.x;
     if (q >= nq) return;
+    if (sp.filter_table) resolve_filter(sp, q);  // a mixed sub-batch: this query's own filter (wave-uniform)
     uint64_t *heap = s_heap[o];
     // the query leaf in LDS (behind the queues; qstride bytes): every margin of the descent reads it
     uint4 *s_q4 = reinterpret_cast<uint4 *>(reinterpret_cast<uint8_t *>(s_wave_lds) + wave_lds_bytes(kWaveHeap, kWaveLeaves));
@@ -603,6 +627,7 @@ __global__ __launch_bounds__(8 * kOct) void k_descend_block(DataView nv, SearchP
     uint32_t(*s_leaf_a)[kLeaves] = reinterpret_cast<uint32_t(*)[kLeaves]>(s_red + 64);  // first id of the leaf in the blob (DNode::a)
     const uint32_t q = blockIdx.x, tid = threadIdx.x, o = tid >> 3, j = tid & 7u, wave = tid >> 6, wl = tid & 63u;
     if (q >= nq) return;
+    if (sp.filter_table) resolve_filter(sp, q);  // a mixed sub-batch: this query's own filter (block-uniform)
     // block-wide max / sum / or of one value per thread (all threads call; two barriers each)
     auto block_max = [&](uint32_t v) {
         for (uint32_t d = 32; d > 0; d >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, d, 64));
@@ -3476,6 +3501,17 @@ __global__ void k_filter_bitmap(const uint32_t *__restrict__ ids, uint64_t n, ui
         atomicOr(&bits[ids[g] >> 5], 1u << (ids[g] & 31));
 }
 
+// How many of the listed ids are rows of the dataset, by its id -> row table (ah_filter_create on sparse ids; identity ids
+// need no kernel: the ids below n).  One partial sum per wave.
+__global__ __launch_bounds__(256) void k_filter_stored(DataView dv, const uint32_t *__restrict__ ids, uint64_t n,
+                                                       unsigned long long *__restrict__ out) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    uint32_t c = 0;
+    for (uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; g < n; g += stride) c += row_of_id(dv, ids[g]) != ~0ull ? 1u : 0u;
+    for (uint32_t d = 32; d > 0; d >>= 1) c += __shfl_xor(c, d, 64);
+    if ((threadIdx.x & 63u) == 0 && c) atomicAdd(out, (unsigned long long)c);
+}
+
 // normal records [vector (row_bytes)][header (16)] -> row matrix + header array of the normals view
 // Only the `valid_words32` words of the stored vector (ah_vector_size bytes) are read from the record: caller views are
 // compact ([header][vector], stride hs + vs), so the device pitch beyond them is zero-filled, never copied.
@@ -3581,6 +3617,15 @@ struct ah_index {
     std::atomic<uint32_t> search8_seen{0};   // ... among this many it served (screen8_window_note: windows of 64) ...
     std::atomic<bool> search8_off{false};    // ... eight in one window: the index's tile re-rank starts on the binary16 rows from now on
     bool counted = false;                    // counted in ds->live_indexes (an update of the dataset refuses meanwhile)
+    ah_filter_stats fstats{};                // under stats_mu; filters_alive is a level (ah_index_destroy refuses above 0)
+};
+
+// `QueryBuilder::candidates` resident on the device of its index: one block [bitmap over 0 .. largest stored id][per node:
+// |descendants & candidates|].  Immutable after ah_filter_create.
+struct ah_filter {
+    ah_index *ix = nullptr;
+    uint32_t *d_bits = nullptr, *d_leaf_kept = nullptr;
+    uint64_t len_bits = 0, listed = 0, stored = 0, device_bytes = 0;
 };
 
 extern "C" {
@@ -3590,6 +3635,11 @@ int ah_index_create_from_view(ah_dataset *ds, const ah_forest_view *view, ah_ind
 int ah_index_destroy(ah_index *ix) {
     AH_GUARDED("ah_index_destroy")
     if (!ix) return AH_OK;
+    {
+        std::lock_guard<std::mutex> lk(ix->stats_mu);
+        AH_REQUIRE(ix->fstats.filters_alive == 0, AH_ERR_INVALID_ARGUMENT, "the index has %llu live filters: ah_filter_destroy them first",
+                   (unsigned long long)ix->fstats.filters_alive);
+    }
     NoFailScope no_fail;
     if (ix->ds) (void)hipSetDevice(ix->ds->device);
     (void)hipDeviceSynchronize();
@@ -3792,6 +3842,15 @@ struct HostTile2 {
     uint32_t query, first;
 };
 
+// A mixed sub-batch of ah_search_batch_filters: the filters of the call on the device, the slot of every query of the
+// sub-batch (host), the smallest stored share among its filters and how many of its queries have one.
+struct MixedFilters {
+    const FilterSlot *d_table;
+    const uint32_t *slots;
+    double min_share;
+    size_t n_filtered;
+};
+
 // Counters of one sub-batch -> the index's ah_search_stats.
 struct ChunkStats {
     ah_search_stats s{};
@@ -3820,8 +3879,12 @@ struct ChunkStats {
 static int search_chunk(ah_index *ix, Context *ctx, const float *queries, const uint32_t *query_rows, size_t nq,
                         size_t count, uint32_t search_k, uint32_t nns_stride, const uint32_t *d_filter_bits,
                         uint64_t filter_len_bits, double filter_share, bool wave_descent, const uint32_t *d_leaf_kept,
-                        uint32_t *out_ids, float *out_dists, uint32_t *out_counts, bool allow8 = true) {
+                        uint32_t *out_ids, float *out_dists, uint32_t *out_counts, bool allow8 = true,
+                        const MixedFilters *mixed = nullptr) {
     ah_dataset *ds = ix->ds;
+    // `filtered`: what the host's path choices ask; d_filter_bits stays the one bitmap of a uniform sub-batch (null in a mixed one)
+    const bool filtered = d_filter_bits || mixed;
+    if (mixed) filter_share = mixed->min_share;
     hipStream_t s = ctx->stream;
     const size_t qstride = (ds->row_bytes() + 255) & ~(size_t)255;
     const size_t k = count;
@@ -3835,7 +3898,7 @@ static int search_chunk(ah_index *ix, Context *ctx, const float *queries, const 
     const uint32_t heap_cap = ix->n_nodes + ix->n_trees + 2;
     size_t dev_bytes = pad(nq * (size_t)ds->dims * 4) + pad(nq * 4) + nq * qstride + pad(nq * 8) + pad(nq * (size_t)nns_stride * 4) * 2 +
                        pad(nq * 4) * 3 + pad(nq * sizeof(HostSeg2)) + pad((size_t)max_tiles_bound * sizeof(HostTile2)) +
-                       2 * pad(nq * kstride * 8) + pad(nq * k * 4) * 2 + pad(SS_WORDS * 4) + pad(nq * 4) + 4096;
+                       2 * pad(nq * kstride * 8) + pad(nq * k * 4) * 2 + pad(SS_WORDS * 4) + pad(nq * 4) + 4096 + (mixed ? pad(nq * 4) : 0);
     // counters of the row-major re-rank, reserved when the candidate lists could be long enough for it
     const size_t inv_bytes = batch_invert_wanted(ds->view(), (uint64_t)nq * nns_stride) ? batch_invert_counter_bytes(ds->n, (uint64_t)nq * nns_stride) : 0;
     dev_bytes += pad(inv_bytes);
@@ -3845,7 +3908,9 @@ static int search_chunk(ah_index *ix, Context *ctx, const float *queries, const 
     const bool bitmap_fits = tun(TUN_SEARCH_BITMAP) != 0 && bitmap_words <= kBitmapMaxWords;
     // nns.dedup() of the tiles: the LDS bitmap, or a hash set of the candidates when the id space is too big for it
     const bool hash_fits = nns_stride <= kHashMaxCandidates && max_id != 0xFFFFFFFFu;
-    const bool tiles = tun(TUN_SEARCH_TILES) != 0 && (bitmap_fits || hash_fits) && !big_k && ds->dims >= 32 &&
+    // (never in a mixed sub-batch: the tiles read the kept ids of a leaf from ONE of its visits for all of them, k_leaf_tiles;
+    // without them no descent is a last pass, so k_descend_multi and the units of a single query are out as well)
+    const bool tiles = !mixed && tun(TUN_SEARCH_TILES) != 0 && (bitmap_fits || hash_fits) && !big_k && ds->dims >= 32 &&
                        ix->max_desc <= 65535u * kTileSlab &&
                        (ds->metric == AH_EUCLIDEAN || ds->metric == AH_COSINE || ds->metric == AH_DOT_PRODUCT);
     const uint32_t visit_cap = (uint32_t)std::min<uint64_t>((uint64_t)nq * nns_stride, 2u << 20);
@@ -3873,7 +3938,7 @@ static int search_chunk(ah_index *ix, Context *ctx, const float *queries, const 
     void *const clean_status = ctx->clean_status;  // (ensure_device forgets it: see Context)
     AH_TRY(ctx->ensure_device(dev_bytes));
     const size_t pin_bytes = pad(nq * (size_t)ds->dims * 4) + pad(nq * 4) * 4 + pad(nq * sizeof(HostSeg2)) +
-                             pad((size_t)max_tiles_bound * sizeof(HostTile2)) + pad(nq * k * 4) * 2 + 4096;
+                             pad((size_t)max_tiles_bound * sizeof(HostTile2)) + pad(nq * k * 4) * 2 + 4096 + (mixed ? pad(nq * 4) : 0);
     AH_TRY(ctx->ensure_pinned(pin_bytes));
     uint8_t *dbase = reinterpret_cast<uint8_t *>(ctx->d_scratch);
     size_t doff = 0;
@@ -3960,6 +4025,7 @@ static int search_chunk(ah_index *ix, Context *ctx, const float *queries, const 
     cs.s.chunks = 1;
     cs.s.queries = nq;
     if (d_filter_bits) cs.s.filtered_queries = nq;
+    if (mixed) cs.s.filtered_queries = mixed->n_filtered;
 
     const DataView dv = ds->view();
     // 1. query leaves (src/reader.rs:46-51 by_item, :64-75 by_vector)
@@ -3975,7 +4041,7 @@ static int search_chunk(ah_index *ix, Context *ctx, const float *queries, const 
     // fall-backs with it).
     bool block_fits = true, small_units_fit = true;
     if (tun(TUN_SEARCH_SMALL_GATE) != 0 && ix->n_leaves) {
-        const double mean_leaf = std::max(1.0, (double)ix->desc_len / ix->n_leaves * (d_filter_bits ? std::max(filter_share, 1e-3) : 1.0));
+        const double mean_leaf = std::max(1.0, (double)ix->desc_len / ix->n_leaves * (filtered ? std::max(filter_share, 1e-3) : 1.0));
         const double est_leaves = 1.25 * (double)search_k / mean_leaf + 2.0;
         // (measured, round 6: 64 queries x ~18 estimated leaves per octet overflowed the block kernel — the best-first order does
         // not spread a query's leaves evenly over the trees; the benchmarked shapes sit near 1 per octet)
@@ -4005,13 +4071,20 @@ static int search_chunk(ah_index *ix, Context *ctx, const float *queries, const 
     sp.filter_len_bits = filter_len_bits;
     sp.search_k = search_k;
     sp.nns_stride = nns_stride;
+    if (mixed) {
+        uint32_t *d_slots = (uint32_t *)dtake(nq * 4), *h_slots = (uint32_t *)ptake(nq * 4);
+        memcpy(h_slots, mixed->slots, nq * 4);
+        AH_HIP(hipMemcpyAsync(d_slots, h_slots, nq * 4, hipMemcpyHostToDevice, s));
+        sp.filter_table = mixed->d_table;
+        sp.filter_of_query = d_slots;
+    }
     // (... and when the block descent is the first kernel to want the leaves, it prepares them itself)
     // (a small submission on the leaf-tile path makes the binary16 copies of its queries in the launch that places its visits)
     const bool small_units = tiles && small_units_fit && (long long)nq <= tun(TUN_SEARCH_SMALL_UNITS_MAX_QUERIES);
     // (small_units: otherwise k_queries_h16 below wants the leaves BEFORE the descent — until round 6 a call with the block
     // descent on and k_units_small off screened against copies of unprepared leaves and was saved by the fall-back only)
     const bool fuse_prepare = zero_copy_queries && tiles && small_units && wave_descent && !metric_is_bq_dev(ds->metric) &&
-                              (!d_filter_bits || filter_share >= 0.35) && block_ok && tun(TUN_SEARCH_FUSED_PREPARE) != 0;
+                              (!filtered || filter_share >= 0.35) && block_ok && tun(TUN_SEARCH_FUSED_PREPARE) != 0;
     if (queries && !fuse_prepare)
         AH_TRY(launch_prepare_queries_only(dv, zero_copy_queries ? h_q : d_qf32, (uint32_t)nq, d_qvecs, qstride, d_qhdrs, s));
     if (screened && !small_units)
@@ -4029,7 +4102,7 @@ static int search_chunk(ah_index *ix, Context *ctx, const float *queries, const 
     auto launch_wave = [&](const VisitSink &sink) -> int {
         // a query pops about 1 / (kept share) as many nodes under a filter: start with the big queues (one query per CU
         // at a time) only then; otherwise they take what the small ones (four per CU) could not hold
-        const bool small_first = !d_filter_bits || filter_share >= 0.35;
+        const bool small_first = !filtered || filter_share >= 0.35;
         // few queries: a block of 32 octets per query (one tree per octet: a third of the chain of dependent pops) while the
         // device has the room — arroy's own API is one query per call (src/reader.rs:46-75)
         static std::atomic<bool> lds_opt_in[64];  // once per device: the kernels that want more than 64 KiB of LDS
@@ -4105,6 +4178,8 @@ static int search_chunk(ah_index *ix, Context *ctx, const float *queries, const 
         static std::atomic<bool> heap_opt_in[64];  // once per device (a runtime call per search is microseconds of a 0.2 ms call)
         if (!heap_opt_in[ds->device & 63].load(std::memory_order_acquire)) {
             AH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_descend<false>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)heap_lds));
+            AH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_descend<false, true>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)heap_lds));
             heap_opt_in[ds->device & 63].store(true, std::memory_order_release);
         }
@@ -4345,9 +4420,14 @@ static int search_chunk(ah_index *ix, Context *ctx, const float *queries, const 
         if (queries && fuse_prepare) AH_TRY(launch_prepare_queries_only(dv, h_q, (uint32_t)nq, d_qvecs, qstride, d_qhdrs, s));
     }
     if (wave_descent) AH_TRY(launch_wave(VisitSink{}));
-    hipLaunchKernelGGL((k_descend<false>), dim3((unsigned)((nq + 7) / 8)), dim3(64), heap_lds, s, ix->nv, sp,
-                       (const uint32_t *)nullptr, (uint32_t)nq, d_qvecs, qstride, d_qhdrs, d_nns, d_counts, d_overflow,
-                       (uint64_t *)nullptr, 0u, VisitSink{}, wave_descent);
+    if (mixed)  // (octets of one wave under different filters)
+        hipLaunchKernelGGL((k_descend<false, true>), dim3((unsigned)((nq + 7) / 8)), dim3(64), heap_lds, s, ix->nv, sp,
+                           (const uint32_t *)nullptr, (uint32_t)nq, d_qvecs, qstride, d_qhdrs, d_nns, d_counts, d_overflow,
+                           (uint64_t *)nullptr, 0u, VisitSink{}, wave_descent);
+    else
+        hipLaunchKernelGGL((k_descend<false>), dim3((unsigned)((nq + 7) / 8)), dim3(64), heap_lds, s, ix->nv, sp,
+                           (const uint32_t *)nullptr, (uint32_t)nq, d_qvecs, qstride, d_qhdrs, d_nns, d_counts, d_overflow,
+                           (uint64_t *)nullptr, 0u, VisitSink{}, wave_descent);
     AH_HIP(hipMemcpyAsync(h_overflow, d_overflow, nq * 4, hipMemcpyDeviceToHost, s));
     AH_HIP(hipStreamSynchronize(s));
     uint32_t n_over = 0;
@@ -4357,9 +4437,14 @@ static int search_chunk(ah_index *ix, Context *ctx, const float *queries, const 
         DevMem heap;
         AH_HIP(dev_malloc(&heap.p, (size_t)n_over * heap_cap * 8));
         AH_HIP(hipMemcpyAsync(d_list, h_list, n_over * 4, hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL((k_descend<true>), dim3((n_over + 7) / 8), dim3(64), 0, s, ix->nv, sp, (const uint32_t *)d_list,
-                           n_over, d_qvecs, qstride, d_qhdrs, d_nns, d_counts, d_overflow, heap.as<uint64_t>(), heap_cap,
-                           VisitSink{}, false);
+        if (mixed)
+            hipLaunchKernelGGL((k_descend<true, true>), dim3((n_over + 7) / 8), dim3(64), 0, s, ix->nv, sp, (const uint32_t *)d_list,
+                               n_over, d_qvecs, qstride, d_qhdrs, d_nns, d_counts, d_overflow, heap.as<uint64_t>(), heap_cap,
+                               VisitSink{}, false);
+        else
+            hipLaunchKernelGGL((k_descend<true>), dim3((n_over + 7) / 8), dim3(64), 0, s, ix->nv, sp, (const uint32_t *)d_list,
+                               n_over, d_qvecs, qstride, d_qhdrs, d_nns, d_counts, d_overflow, heap.as<uint64_t>(), heap_cap,
+                               VisitSink{}, false);
         AH_HIP(hipStreamSynchronize(s));
     }
     // 3. sort + dedup
@@ -4493,6 +4578,54 @@ int ah_route_items(ah_index *ix, const uint32_t *item_ids, size_t n, const uint6
     AH_GUARDED_END
 }
 
+// What both batched entry points derive from their arguments: the effective search_k, the capacity of one query's candidate
+// buffer, the rows of by_item queries and the most queries of one sub-batch.
+struct SearchShape {
+    uint64_t sk_eff = 0, stride = 0;
+    std::vector<uint32_t> rows;
+    size_t chunk = 1;
+};
+static int search_shape(ah_index *ix, const uint32_t *query_items, size_t nq, size_t count, size_t search_k, size_t oversampling,
+                        SearchShape &out) {
+    ah_dataset *ds = ix->ds;
+    // search_k: reader.rs:330-335; nns can never exceed the blob (every Descendants node is popped at most once)
+    unsigned __int128 sk = search_k ? (unsigned __int128)search_k : (unsigned __int128)count * ix->n_trees;
+    sk *= oversampling ? oversampling : (metric_is_bq(ds->metric) ? 3u : 1u);
+    const uint64_t sk_eff = (uint64_t)std::min<unsigned __int128>(sk, (unsigned __int128)ix->desc_len);
+    uint64_t stride = std::min<uint64_t>(sk_eff + ix->max_desc, ix->desc_len);
+    if (stride > kSortLds) {  // the global sort path pads to a power of two
+        uint64_t p = 2;
+        while (p < stride) p <<= 1;
+        stride = p;
+    }
+    AH_REQUIRE(stride < 0x7FFFFFFFull, AH_ERR_INVALID_ARGUMENT, "search_k too large");
+    std::vector<uint32_t> &rows = out.rows;
+    if (query_items) {
+        rows.resize(nq);
+        for (size_t q = 0; q < nq; q++) {
+            if (ds->identity_ids) {
+                AH_REQUIRE(query_items[q] < ds->n, AH_ERR_MISSING_ITEM, "item %u does not exist", query_items[q]);
+                rows[q] = query_items[q];
+            } else {
+                auto it = std::lower_bound(ds->h_ids.begin(), ds->h_ids.end(), query_items[q]);
+                AH_REQUIRE(it != ds->h_ids.end() && *it == query_items[q], AH_ERR_MISSING_ITEM, "item %u does not exist",
+                           query_items[q]);
+                rows[q] = (uint32_t)(it - ds->h_ids.begin());
+            }
+        }
+    }
+    // sub-batches bounded by scratch (~1.5 GiB of candidate buffers)
+    const size_t key_bytes = batch_supported((uint32_t)std::min<size_t>(count, 0xFFFFFFFFu))
+                                 ? 2 * batch_key_stride((uint32_t)stride) * 8
+                                 : topk_scratch_bytes(stride, std::min<size_t>(count, stride)) + 64;
+    const size_t per_query = (size_t)stride * 8 + key_bytes + count * 8 + ds->row_bytes() + 4096;
+    size_t chunk = std::max<size_t>(1, std::min<size_t>(nq, (1536ull << 20) / per_query));
+    out.chunk = std::min<size_t>(chunk, 4096);
+    out.sk_eff = sk_eff;
+    out.stride = stride;
+    return AH_OK;
+}
+
 // `QueryBuilder::{by_vector, by_item}` for a batch (src/reader.rs:46-75, 317-401).
 //   queries      nq x dims f32 (by_vector), or NULL with query_items = nq item ids (by_item)
 //   search_k     0 = count * n_trees (reader.rs:330); oversampling 0 = D::DEFAULT_OVERSAMPLING (1, or 3 for 1-bit)
@@ -4518,32 +4651,10 @@ int ah_search_batch(ah_index *ix, const float *queries, const uint32_t *query_it
     for (size_t q = 0; q < nq; q++) out_counts[q] = 0;
     AH_REQUIRE(!have_filter || n_filter == 0 || filter_sorted, AH_ERR_INVALID_ARGUMENT, "filter_sorted is NULL");
     if (ds->n == 0 || ix->n_trees == 0) return AH_OK;  // reader.rs:323-325
-    // search_k: reader.rs:330-335; nns can never exceed the blob (every Descendants node is popped at most once)
-    unsigned __int128 sk = search_k ? (unsigned __int128)search_k : (unsigned __int128)count * ix->n_trees;
-    sk *= oversampling ? oversampling : (metric_is_bq(ds->metric) ? 3u : 1u);
-    const uint64_t sk_eff = (uint64_t)std::min<unsigned __int128>(sk, (unsigned __int128)ix->desc_len);
-    uint64_t stride = std::min<uint64_t>(sk_eff + ix->max_desc, ix->desc_len);
-    if (stride > kSortLds) {  // the global sort path pads to a power of two
-        uint64_t p = 2;
-        while (p < stride) p <<= 1;
-        stride = p;
-    }
-    AH_REQUIRE(stride < 0x7FFFFFFFull, AH_ERR_INVALID_ARGUMENT, "search_k too large");
-    std::vector<uint32_t> rows;
-    if (query_items) {
-        rows.resize(nq);
-        for (size_t q = 0; q < nq; q++) {
-            if (ds->identity_ids) {
-                AH_REQUIRE(query_items[q] < ds->n, AH_ERR_MISSING_ITEM, "item %u does not exist", query_items[q]);
-                rows[q] = query_items[q];
-            } else {
-                auto it = std::lower_bound(ds->h_ids.begin(), ds->h_ids.end(), query_items[q]);
-                AH_REQUIRE(it != ds->h_ids.end() && *it == query_items[q], AH_ERR_MISSING_ITEM, "item %u does not exist",
-                           query_items[q]);
-                rows[q] = (uint32_t)(it - ds->h_ids.begin());
-            }
-        }
-    }
+    SearchShape shape;
+    AH_TRY(search_shape(ix, query_items, nq, count, search_k, oversampling, shape));
+    const uint64_t sk_eff = shape.sk_eff, stride = shape.stride;
+    const std::vector<uint32_t> &rows = shape.rows;
     ContextLease lease(ds);
     AH_REQUIRE(lease.c, AH_ERR_DEVICE, "cannot create a HIP stream");
     Context *ctx = lease.c;
@@ -4593,13 +4704,7 @@ int ah_search_batch(ah_index *ix, const float *queries, const uint32_t *query_it
         ix->stats.calls++;
         ix->stats.leaf_kept_passes += leaf_kept_passes;
     }
-    // sub-batches bounded by scratch (~1.5 GiB of candidate buffers)
-    const size_t key_bytes = batch_supported((uint32_t)std::min<size_t>(count, 0xFFFFFFFFu))
-                                 ? 2 * batch_key_stride((uint32_t)stride) * 8
-                                 : topk_scratch_bytes(stride, std::min<size_t>(count, stride)) + 64;
-    const size_t per_query = (size_t)stride * 8 + key_bytes + count * 8 + ds->row_bytes() + 4096;
-    size_t chunk = std::max<size_t>(1, std::min<size_t>(nq, (1536ull << 20) / per_query));
-    chunk = std::min<size_t>(chunk, 4096);
+    const size_t chunk = shape.chunk;
     auto run_range = [&](Context *c, size_t qa, size_t qb) -> int {
         int st = AH_OK;
         for (size_t q0 = qa; q0 < qb && st == AH_OK; q0 += chunk) {
@@ -4621,6 +4726,298 @@ int ah_index_search_stats(ah_index *ix, ah_search_stats *out, int reset) {
     std::lock_guard<std::mutex> lk(ix->stats_mu);
     *out = ix->stats;
     if (reset) ix->stats = ah_search_stats{};
+    return AH_OK;
+    AH_GUARDED_END
+}
+
+// ---- resident candidate filters (include/arroy_hip.h) ---------------------------------------------------------------------
+
+int ah_filter_create(ah_index *ix, const uint32_t *sorted_ids, size_t n, ah_filter **out) {
+    AH_GUARDED("ah_filter_create")
+    AH_REQUIRE(out, AH_ERR_INVALID_ARGUMENT, "out is NULL");
+    *out = nullptr;
+    AH_REQUIRE(n == 0 || sorted_ids, AH_ERR_INVALID_ARGUMENT, "sorted_ids is NULL");
+    for (size_t i = 1; i < n; i++)
+        AH_REQUIRE(sorted_ids[i - 1] < sorted_ids[i], AH_ERR_INVALID_ARGUMENT, "sorted_ids is not strictly ascending at position %zu (%u after %u)",
+                   i, sorted_ids[i], sorted_ids[i - 1]);
+    AH_REQUIRE(ix && ix->ds, AH_ERR_INVALID_ARGUMENT, "index is NULL");
+    ah_dataset *ds = ix->ds;
+    AH_HIP(hipSetDevice(ds->device));
+    std::unique_ptr<ah_filter> f(new ah_filter);
+    f->ix = ix;
+    f->listed = n;
+    // bitmap over item ids (ids beyond the largest stored id cannot match: the list is ascending), then one word per node
+    size_t n_keep = 0;
+    if (ds->n) {
+        const uint32_t max_id = ds->identity_ids ? (uint32_t)(ds->n - 1) : ds->last_id;
+        f->len_bits = (uint64_t)max_id + 1;
+        n_keep = n ? (size_t)(std::upper_bound(sorted_ids, sorted_ids + n, max_id) - sorted_ids) : 0;
+    }
+    const size_t words = (((size_t)f->len_bits + 31) / 32 + 63) & ~(size_t)63;
+    const size_t bytes = words * 4 + (size_t)ix->n_nodes * 4 + 256;
+    DevMem block, list;  // (list: [stored count (8 bytes)][the ids], gone when this call returns)
+    AH_HIP(dev_malloc(&block.p, bytes));
+    if (n_keep) AH_HIP(dev_malloc(&list.p, 8 + n_keep * 4));
+    ContextLease lease(ds);
+    AH_REQUIRE(lease.c, AH_ERR_DEVICE, "cannot create a HIP stream");
+    hipStream_t s = lease.c->stream;
+    uint32_t *d_bits = block.as<uint32_t>(), *d_kept = d_bits + words;
+    AH_HIP(hipMemsetAsync(d_bits, 0, bytes, s));
+    unsigned long long stored = 0;
+    const bool count_on_device = n_keep && !ds->identity_ids;
+    if (n_keep) {
+        unsigned long long *d_stored = list.as<unsigned long long>();
+        uint32_t *d_list = reinterpret_cast<uint32_t *>(d_stored + 1);
+        AH_HIP(hipMemsetAsync(d_stored, 0, 8, s));
+        AH_HIP(hipMemcpyAsync(d_list, sorted_ids, n_keep * 4, hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(k_filter_bitmap, dim3(256), dim3(256), 0, s, d_list, (uint64_t)n_keep, d_bits);
+        if (count_on_device) {
+            hipLaunchKernelGGL(k_filter_stored, dim3(256), dim3(256), 0, s, ds->view(), d_list, (uint64_t)n_keep, d_stored);
+            AH_HIP(hipMemcpyAsync(&stored, d_stored, 8, hipMemcpyDeviceToHost, s));
+        } else {
+            stored = n_keep;  // identity ids: every id up to n - 1 is a row
+        }
+    }
+    if (ix->n_nodes) {
+        SearchParams lp{};
+        lp.nodes = ix->d_nodes;
+        lp.desc = ix->d_desc;
+        lp.filter_bits = d_bits;
+        lp.filter_len_bits = f->len_bits;
+        hipLaunchKernelGGL(k_leaf_kept, dim3(1024), dim3(256), 0, s, lp, ix->n_nodes, d_kept);
+    }
+    AH_HIP(hipGetLastError());
+    AH_HIP(hipStreamSynchronize(s));
+    f->stored = stored;
+    f->d_bits = d_bits;
+    f->d_leaf_kept = d_kept;
+    f->device_bytes = dev_block_bytes(block.p);  // (what the allocator accounts for it: ah_device_cache_stats)
+    {
+        std::lock_guard<std::mutex> lk(ix->stats_mu);
+        ix->fstats.filters_created++;
+        ix->fstats.filters_alive++;
+        ix->fstats.leaf_kept_passes += ix->n_nodes ? 1 : 0;
+    }
+    block.p = nullptr;  // the filter owns it from here
+    *out = f.release();
+    return AH_OK;
+    AH_GUARDED_END
+}
+
+int ah_filter_info(const ah_filter *f, uint64_t *out_listed, uint64_t *out_stored, uint64_t *out_device_bytes) {
+    AH_GUARDED("ah_filter_info")
+    AH_REQUIRE(f, AH_ERR_INVALID_ARGUMENT, "filter is NULL");
+    if (out_listed) *out_listed = f->listed;
+    if (out_stored) *out_stored = f->stored;
+    if (out_device_bytes) *out_device_bytes = f->device_bytes;
+    return AH_OK;
+    AH_GUARDED_END
+}
+
+int ah_filter_destroy(ah_filter *f) {
+    AH_GUARDED("ah_filter_destroy")
+    if (!f) return AH_OK;
+    NoFailScope no_fail;
+    ah_index *ix = f->ix;
+    if (ix && ix->ds) (void)hipSetDevice(ix->ds->device);
+    if (f->d_bits) (void)dev_free(f->d_bits);  // (waits for the device: no queued search still reads it)
+    if (ix) {
+        std::lock_guard<std::mutex> lk(ix->stats_mu);
+        if (ix->fstats.filters_alive) ix->fstats.filters_alive--;
+    }
+    delete f;
+    return AH_OK;
+    AH_GUARDED_END
+}
+
+int ah_index_filter_stats(ah_index *ix, ah_filter_stats *out, int reset) {
+    AH_GUARDED("ah_index_filter_stats")
+    AH_REQUIRE(ix && out, AH_ERR_INVALID_ARGUMENT, "NULL argument");
+    std::lock_guard<std::mutex> lk(ix->stats_mu);
+    *out = ix->fstats;
+    if (reset) {
+        const uint64_t alive = ix->fstats.filters_alive;
+        ix->fstats = ah_filter_stats{};
+        ix->fstats.filters_alive = alive;
+    }
+    return AH_OK;
+    AH_GUARDED_END
+}
+
+// ah_search_batch with a filter per query.  The query indices are ordered stably by filter slot, unfiltered first; a run of at
+// least AH_SEARCH_FILTER_GROUP_MIN queries of one slot is cut into UNIFORM sub-batches, which go through search_chunk exactly
+// as a single-filter call does (same descents, leaf tiles and screens) with the filter's resident bitmap and per-node array;
+// the queries of the shorter runs are packed, in that order, into MIXED sub-batches (SearchParams::filter_table; sorted
+// re-rank).  A mixed sub-batch whose queries happen to share one slot is a uniform one.  (tests/test_search_filters_cpu.py
+// restates the rule in numpy.)
+int ah_search_batch_filters(ah_index *ix, const float *queries, const uint32_t *query_items, size_t nq, size_t count, size_t search_k,
+                            size_t oversampling, ah_filter *const *filters, size_t n_filters, const uint32_t *filter_of_query,
+                            uint32_t *out_ids, float *out_distances, uint32_t *out_counts) {
+    AH_GUARDED("ah_search_batch_filters")
+    // (what can be judged without the index first)
+    AH_REQUIRE((queries != nullptr) != (query_items != nullptr), AH_ERR_INVALID_ARGUMENT,
+               "exactly one of queries / query_items must be given");
+    AH_REQUIRE(out_ids && out_distances && out_counts, AH_ERR_INVALID_ARGUMENT, "NULL output");
+    AH_REQUIRE(n_filters == 0 || filters, AH_ERR_INVALID_ARGUMENT, "filters is NULL");
+    AH_REQUIRE(n_filters < AH_NO_FILTER && nq < 0xFFFFFFFFull, AH_ERR_INVALID_ARGUMENT, "too many filters or queries");
+    AH_REQUIRE(filter_of_query || n_filters <= 1, AH_ERR_INVALID_ARGUMENT, "filter_of_query is NULL with %zu filters", n_filters);
+    if (filter_of_query)
+        for (size_t q = 0; q < nq; q++)
+            AH_REQUIRE(filter_of_query[q] == AH_NO_FILTER || filter_of_query[q] < n_filters, AH_ERR_INVALID_ARGUMENT,
+                       "filter_of_query[%zu] = %u names no filter (n_filters = %zu)", q, filter_of_query[q], n_filters);
+    AH_REQUIRE(ix && ix->ds, AH_ERR_INVALID_ARGUMENT, "index is NULL");
+    for (size_t i = 0; i < n_filters; i++) {
+        AH_REQUIRE(filters[i], AH_ERR_INVALID_ARGUMENT, "filters[%zu] is NULL", i);
+        AH_REQUIRE(filters[i]->ix == ix, AH_ERR_INVALID_ARGUMENT, "filters[%zu] belongs to another index", i);
+    }
+    ah_dataset *ds = ix->ds;
+    if (nq == 0) return AH_OK;
+    AH_REQUIRE(count > 0 && count < 0x7FFFFFFFull, AH_ERR_INVALID_ARGUMENT, "count must be > 0");
+    AH_HIP(hipSetDevice(ds->device));
+    for (size_t i = 0; i < nq * count; i++) {
+        out_ids[i] = 0xFFFFFFFFu;
+        const uint32_t nan_bits = 0xFFFFFFFFu;
+        memcpy(&out_distances[i], &nan_bits, 4);
+    }
+    for (size_t q = 0; q < nq; q++) out_counts[q] = 0;
+    if (ds->n == 0 || ix->n_trees == 0) return AH_OK;  // reader.rs:323-325
+    SearchShape shape;
+    AH_TRY(search_shape(ix, query_items, nq, count, search_k, oversampling, shape));
+    const size_t chunk = shape.chunk;
+    // 1. the order: stable by slot, unfiltered first
+    auto slot_of = [&](size_t q) -> uint32_t { return filter_of_query ? filter_of_query[q] : (n_filters ? 0u : AH_NO_FILTER); };
+    // (keys `slot + 1 (mod 2^32)` << 32 | query: stable by construction, and no temporary buffer whose allocation std::stable_sort
+    // would survive failing — every allocation of this call that fails gives a status)
+    std::vector<uint32_t> order(nq);
+    {
+        std::vector<uint64_t> keyed(nq);
+        for (size_t q = 0; q < nq; q++) keyed[q] = ((uint64_t)(uint32_t)(slot_of(q) + 1u) << 32) | (uint32_t)q;
+        std::sort(keyed.begin(), keyed.end());
+        for (size_t q = 0; q < nq; q++) order[q] = (uint32_t)keyed[q];
+    }
+    // 2. the sub-batches, as ranges of `perm`: the uniform ones first, then what is left over
+    struct SubBatch {
+        size_t a, b;
+        bool mixed;
+    };
+    const size_t group_min = (size_t)std::max<long long>(1, tun(TUN_SEARCH_FILTER_GROUP_MIN));
+    std::vector<uint32_t> perm, rest;
+    std::vector<SubBatch> batches;
+    perm.reserve(nq);
+    for (size_t r0 = 0; r0 < nq;) {
+        size_t r1 = r0 + 1;
+        while (r1 < nq && slot_of(order[r1]) == slot_of(order[r0])) r1++;
+        if (r1 - r0 >= group_min) {
+            for (size_t c0 = r0; c0 < r1; c0 += chunk) {
+                const size_t c1 = std::min(r1, c0 + chunk);
+                batches.push_back(SubBatch{perm.size(), perm.size() + (c1 - c0), false});
+                perm.insert(perm.end(), order.begin() + c0, order.begin() + c1);
+            }
+        } else {
+            rest.insert(rest.end(), order.begin() + r0, order.begin() + r1);
+        }
+        r0 = r1;
+    }
+    bool any_mixed = false;
+    for (size_t c0 = 0; c0 < rest.size(); c0 += chunk) {
+        const size_t c1 = std::min(rest.size(), c0 + chunk);
+        bool one_slot = true;
+        for (size_t i = c0 + 1; i < c1; i++) one_slot = one_slot && slot_of(rest[i]) == slot_of(rest[c0]);
+        batches.push_back(SubBatch{perm.size(), perm.size() + (c1 - c0), !one_slot});
+        any_mixed = any_mixed || !one_slot;
+        perm.insert(perm.end(), rest.begin() + c0, rest.begin() + c1);
+    }
+    // 3. queries and outputs in that order (nothing to move when the order is the caller's)
+    bool identity = true;
+    for (size_t i = 0; i < nq && identity; i++) identity = perm[i] == i;
+    std::vector<float> pq, pd;
+    std::vector<uint32_t> prow, pi, pc, pslot(nq);
+    for (size_t i = 0; i < nq; i++) pslot[i] = slot_of(perm[i]);
+    const float *qsrc = queries;
+    const uint32_t *rsrc = query_items ? shape.rows.data() : nullptr;
+    uint32_t *oi = out_ids, *oc = out_counts;
+    float *od = out_distances;
+    if (!identity) {
+        if (queries) {
+            pq.resize(nq * (size_t)ds->dims);
+            for (size_t i = 0; i < nq; i++) memcpy(&pq[i * (size_t)ds->dims], queries + perm[i] * (size_t)ds->dims, (size_t)ds->dims * 4);
+            qsrc = pq.data();
+        } else {
+            prow.resize(nq);
+            for (size_t i = 0; i < nq; i++) prow[i] = shape.rows[perm[i]];
+            rsrc = prow.data();
+        }
+        pi.resize(nq * count);
+        pd.resize(nq * count);
+        pc.resize(nq);
+        oi = pi.data();
+        od = pd.data();
+        oc = pc.data();
+    }
+    ContextLease lease(ds);
+    AH_REQUIRE(lease.c, AH_ERR_DEVICE, "cannot create a HIP stream");
+    Context *ctx = lease.c;
+    const bool wave_ok = tun(TUN_SEARCH_WAVE) != 0 && ((ds->row_bytes() + 255) & ~(size_t)255) <= (32u << 10);
+    auto share_of = [&](uint32_t slot) { return (double)filters[slot]->stored / (double)ds->n; };  // exact: ah_filter_info
+    std::vector<FilterSlot> table;
+    if (any_mixed) {  // the filters of the call, for the descents of the mixed sub-batches
+        table.resize(n_filters);
+        for (size_t i = 0; i < n_filters; i++) table[i] = FilterSlot{filters[i]->d_bits, filters[i]->len_bits, filters[i]->d_leaf_kept};
+        AH_TRY(ctx->ensure_filter(n_filters * sizeof(FilterSlot)));
+        AH_HIP(hipMemcpyAsync(ctx->d_filter, table.data(), n_filters * sizeof(FilterSlot), hipMemcpyHostToDevice, ctx->stream));
+    }
+    ah_filter_stats fs{};
+    fs.calls = 1;
+    {
+        std::lock_guard<std::mutex> lk(ix->stats_mu);
+        ix->stats.calls++;
+    }
+    int st = AH_OK;
+    for (const SubBatch &sb : batches) {
+        const size_t cn = sb.b - sb.a;
+        const float *q_at = qsrc ? qsrc + sb.a * (size_t)ds->dims : nullptr;
+        const uint32_t *r_at = rsrc ? rsrc + sb.a : nullptr;
+        if (!sb.mixed) {
+            // Descent: one wave per query unless the filter keeps under 5 % of the items (ah_search_batch); the per-node array is
+            // resident, so no call is too small for it
+            const uint32_t slot = pslot[sb.a];
+            const ah_filter *f = slot == AH_NO_FILTER ? nullptr : filters[slot];
+            const double share = f ? share_of(slot) : 1.0;
+            st = search_chunk(ix, ctx, q_at, r_at, cn, count, (uint32_t)shape.sk_eff, (uint32_t)shape.stride, f ? f->d_bits : nullptr,
+                              f ? f->len_bits : 0, share, wave_ok && (!f || share >= 0.05), f ? f->d_leaf_kept : nullptr,
+                              oi + sb.a * count, od + sb.a * count, oc + sb.a);
+            fs.uniform_batches++;
+            fs.uniform_queries += cn;
+        } else {
+            // today's rules on the SMALLEST stored share among the sub-batch's filters
+            MixedFilters mf{reinterpret_cast<const FilterSlot *>(ctx->d_filter), pslot.data() + sb.a, 1.0, 0};
+            for (size_t i = sb.a; i < sb.b; i++)
+                if (pslot[i] != AH_NO_FILTER) {
+                    mf.min_share = std::min(mf.min_share, share_of(pslot[i]));
+                    mf.n_filtered++;
+                }
+            st = search_chunk(ix, ctx, q_at, r_at, cn, count, (uint32_t)shape.sk_eff, (uint32_t)shape.stride, nullptr, 0, mf.min_share,
+                              wave_ok && mf.min_share >= 0.05, nullptr, oi + sb.a * count, od + sb.a * count, oc + sb.a, true, &mf);
+            fs.mixed_batches++;
+            fs.mixed_queries += cn;
+        }
+        if (st != AH_OK) break;
+    }
+    {
+        std::lock_guard<std::mutex> lk(ix->stats_mu);
+        ix->fstats.calls += fs.calls;
+        ix->fstats.uniform_batches += fs.uniform_batches;
+        ix->fstats.mixed_batches += fs.mixed_batches;
+        ix->fstats.uniform_queries += fs.uniform_queries;
+        ix->fstats.mixed_queries += fs.mixed_queries;
+    }
+    AH_TRY(st);
+    if (!identity)
+        for (size_t i = 0; i < nq; i++) {
+            memcpy(out_ids + perm[i] * count, oi + i * count, count * 4);
+            memcpy(out_distances + perm[i] * count, od + i * count, count * 4);
+            out_counts[perm[i]] = oc[i];
+        }
     return AH_OK;
     AH_GUARDED_END
 }

@@ -6,6 +6,7 @@ every method is one C-ABI call, all arithmetic happens in HIP kernels.
 from __future__ import annotations
 
 import ctypes as C
+import weakref
 from typing import Optional, Sequence
 
 import numpy as np
@@ -543,17 +544,25 @@ class Index:
     def __init__(self, dataset: Dataset, forest: Optional["Forest"], view=None):
         self.dataset = dataset
         self._h = C.c_void_p()
+        self._filters = weakref.WeakSet()  # the live Filter objects of this index: closed before it
         if view is not None:  # caller-owned arrays in the ah_forest_view shape (ah_index_create_from_view)
             _lib.check(_lib.lib().ah_index_create_from_view(dataset._h, C.cast(C.byref(view), C.POINTER(_lib.AhForestView)),
                                                             C.byref(self._h)))
         else:
             _lib.check(_lib.lib().ah_index_create(dataset._h, forest._h, C.byref(self._h)))
 
+    def make_filter(self, ids, sorted: bool = False) -> "Filter":
+        """ah_filter_create: `QueryBuilder::candidates` as an object resident on the device, for any number of searches.
+        sorted=True: `ids` is already an ascending array of distinct ids (what a RoaringBitmap iterates)."""
+        return Filter(self, ids, sorted)
+
     def search(self, count: int, queries=None, items=None, search_k: int = 0, oversampling: int = 0, candidates=None,
-               raw: bool = False, candidates_sorted: bool = False):
+               raw: bool = False, candidates_sorted: bool = False, filters=None, filter_of_query=None):
         """Batch of `QueryBuilder::by_vector` (queries: nq x dims) or `by_item` (items: nq ids).
         Returns a list (one entry per query) of [(id, distance), ...]; with raw=True the (ids, distances, counts)
-        arrays of the C ABI (no per-result Python objects).  `candidates` = `QueryBuilder::candidates`."""
+        arrays of the C ABI (no per-result Python objects).  `candidates` = `QueryBuilder::candidates` as an id list for the
+        whole call, or a `Filter`; `filters` (a list of `Filter`) with `filter_of_query` (per query an index into it, or
+        NO_FILTER / -1) gives every query its own (ah_search_batch_filters)."""
         ds = self.dataset
         if queries is not None:
             q = _f32(queries)
@@ -566,21 +575,45 @@ class Index:
         else:
             it = _u32(items).ravel()
             nq, q = it.size, None
-        if candidates is None:
-            filt = None
-        elif candidates_sorted:  # already an ascending array of distinct ids (what a RoaringBitmap iterates)
-            filt = _u32(candidates)
-        else:
-            filt = _u32(sorted(set(int(c) for c in candidates)))
+        if isinstance(candidates, Filter):
+            if filters is not None:
+                raise ValueError("candidates= as a Filter and filters= exclude each other")
+            filters, filter_of_query, candidates = [candidates], None, None
         oi = np.zeros((nq, count), dtype=np.uint32)
         od = np.zeros((nq, count), dtype=np.float32)
         oc = np.zeros(nq, dtype=np.uint32)
-        _lib.check(_lib.lib().ah_search_batch(self._h, _ptr(q), _ptr(it), nq, int(count), int(min(search_k, 2**62)),
-                                              int(oversampling), _ptr(filt), 0 if filt is None else filt.size,
-                                              0 if filt is None else 1, _ptr(oi), _ptr(od), _ptr(oc)))
+        if filters is not None or filter_of_query is not None:
+            if candidates is not None:
+                raise ValueError("candidates= as an id list and filters= exclude each other")
+            filters = list(filters or [])
+            handles = (C.c_void_p * max(1, len(filters)))(*[f._handle() for f in filters])
+            foq = None
+            if filter_of_query is not None:
+                foq = np.ascontiguousarray(np.asarray(filter_of_query, dtype=np.int64) & 0xFFFFFFFF, dtype=np.uint32).ravel()
+                if foq.size != nq:
+                    raise ValueError(f"filter_of_query has {foq.size} entries for {nq} queries")
+            _lib.check(_lib.lib().ah_search_batch_filters(self._h, _ptr(q), _ptr(it), nq, int(count), int(min(search_k, 2**62)),
+                                                          int(oversampling), handles, len(filters), _ptr(foq), _ptr(oi),
+                                                          _ptr(od), _ptr(oc)))
+        else:
+            if candidates is None:
+                filt = None
+            elif candidates_sorted:  # already an ascending array of distinct ids (what a RoaringBitmap iterates)
+                filt = _u32(candidates)
+            else:
+                filt = _u32(sorted(set(int(c) for c in candidates)))
+            _lib.check(_lib.lib().ah_search_batch(self._h, _ptr(q), _ptr(it), nq, int(count), int(min(search_k, 2**62)),
+                                                  int(oversampling), _ptr(filt), 0 if filt is None else filt.size,
+                                                  0 if filt is None else 1, _ptr(oi), _ptr(od), _ptr(oc)))
         if raw:
             return oi, od, oc
         return [[(int(oi[i, j]), float(od[i, j])) for j in range(int(oc[i]))] for i in range(nq)]
+
+    def filter_stats(self, reset: bool = False) -> dict:
+        """ah_index_filter_stats: how ah_search_batch_filters cut its calls, and the filters of this index."""
+        st = _lib.AhFilterStats()
+        _lib.check(_lib.lib().ah_index_filter_stats(self._h, C.byref(st), 1 if reset else 0))
+        return {f: int(getattr(st, f)) for f, _ in _lib.AhFilterStats._fields_}
 
     def stats(self, reset: bool = False) -> dict:
         """ah_index_search_stats: which descent tier / dedup path / re-rank path served the searches so far."""
@@ -598,8 +631,51 @@ class Index:
 
     def close(self) -> None:
         if self._h:
+            for f in list(self._filters):  # (ah_index_destroy refuses while one is alive)
+                f.close()
             _lib.lib().ah_index_destroy(self._h)
             self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Filter:
+    """`QueryBuilder::candidates` resident next to an Index (ah_filter_create): the bitmap over the stored ids and what it keeps of
+    every leaf, made once.  Immutable; any number of threads may search under it.  Closed with its index at the latest."""
+
+    def __init__(self, index: Index, ids, sorted_ids: bool = False):
+        self.index = index
+        self._h = C.c_void_p()
+        arr = _u32(ids) if sorted_ids else _u32(sorted(set(int(c) for c in ids)))
+        _lib.check(_lib.lib().ah_filter_create(index._h, _ptr(arr), arr.size, C.byref(self._h)))
+        index._filters.add(self)
+
+    def _handle(self):
+        if not self._h:
+            raise ValueError("the filter is closed")
+        return self._h.value
+
+    def info(self) -> dict:
+        """ah_filter_info: ids listed, those of them that are stored (exact), bytes of HBM held."""
+        listed, stored, nbytes = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        _lib.check(_lib.lib().ah_filter_info(self._handle(), C.byref(listed), C.byref(stored), C.byref(nbytes)))
+        return {"listed": listed.value, "stored": stored.value, "device_bytes": nbytes.value}
+
+    def close(self) -> None:
+        if self._h:
+            _lib.lib().ah_filter_destroy(self._h)
+            self._h = C.c_void_p()
+            self.index._filters.discard(self)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
     def __del__(self):
         try:

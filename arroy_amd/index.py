@@ -18,7 +18,7 @@ from typing import Callable, Dict, Iterable, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
-from .dataset import Dataset, Forest
+from .dataset import Dataset, Filter, Forest
 from .distances import Distance
 
 ItemId = int
@@ -570,6 +570,10 @@ class Reader:
     def nns(self, count: int) -> "QueryBuilder":  # src/reader.rs:296-298
         return QueryBuilder(self, int(count))
 
+    def make_filter(self, ids) -> "Filter":
+        """A candidate set resident on the device for `nns(..).candidates(filter)`: made once, used by any number of queries."""
+        return self._st.index.make_filter(ids)
+
 
 class QueryBuilder:
     """`QueryBuilder` (src/reader.rs:26-124)."""
@@ -578,7 +582,7 @@ class QueryBuilder:
         self._r, self._count = reader, count
         self._search_k: Optional[int] = None
         self._oversampling: Optional[int] = None
-        self._candidates: Optional[set] = None
+        self._candidates = None  # a set of ids, or a Filter
 
     def search_k(self, n: int) -> "QueryBuilder":
         self._search_k = int(n)
@@ -588,8 +592,9 @@ class QueryBuilder:
         self._oversampling = int(n)
         return self
 
-    def candidates(self, ids: Iterable[int]) -> "QueryBuilder":
-        self._candidates = set(int(i) for i in ids)
+    def candidates(self, ids) -> "QueryBuilder":
+        """An iterable of item ids, or a `Filter` of this reader's index (`Reader.make_filter`) kept across queries."""
+        self._candidates = ids if isinstance(ids, Filter) else set(int(i) for i in ids)
         return self
 
     def by_item(self, item: ItemId) -> Optional[List[Tuple[int, float]]]:  # src/reader.rs:46-51

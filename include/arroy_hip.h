@@ -632,6 +632,46 @@ typedef struct ah_search_stats {
 } ah_search_stats;
 AH_API int ah_index_search_stats(ah_index *index, ah_search_stats *out, int reset);
 
+/* ------------------------------------------------------------------------------------------
+ * Resident candidate filters (ABI v7 addition: look the symbols up).  `QueryBuilder::candidates` (src/reader.rs:110-123)
+ * as an object that lives on the device next to its index: the bitmap over [0, largest stored id] and
+ * |descendants & candidates| of every node, which ah_search_batch makes anew for every call that carries an id list,
+ * are made once.  A host keeps one filter per tenant or facet bitmap and names it in any number of searches.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct ah_filter ah_filter;
+/* sorted_ids: strictly ascending; ids that are not stored are legal and match nothing (a RoaringBitmap may hold anything).
+ * The filter is immutable and may serve concurrent searches of any number of threads.  It must be destroyed before its
+ * index (ah_index_destroy refuses while one is alive). */
+AH_API int ah_filter_create(ah_index *index, const uint32_t *sorted_ids, size_t n, ah_filter **out);
+/* out_listed: ids given; out_stored: those of them that are rows of the dataset (exact); out_device_bytes: HBM the filter
+ * holds.  Any pointer may be NULL. */
+AH_API int ah_filter_info(const ah_filter *f, uint64_t *out_listed, uint64_t *out_stored, uint64_t *out_device_bytes);
+AH_API int ah_filter_destroy(ah_filter *f);
+
+#define AH_NO_FILTER 0xFFFFFFFFu
+/* ah_search_batch in which every query names its filter: filter_of_query[q] is an index into `filters` or AH_NO_FILTER;
+ * NULL = every query under filters[0] (n_filters == 1) or unfiltered (n_filters == 0).  Query q returns exactly what
+ * ah_search_batch returns for it alone under the id list of its filter — the same ids and distance bits, whatever else is
+ * in the call.  Runs of at least AH_SEARCH_FILTER_GROUP_MIN queries with one filter are served like a single-filter call
+ * (uniform sub-batches); the rest share mixed sub-batches whose descents look up every query's own filter. */
+AH_API int ah_search_batch_filters(ah_index *index, const float *queries, const uint32_t *query_items, size_t nq, size_t count,
+                                   size_t search_k, size_t oversampling, ah_filter *const *filters, size_t n_filters,
+                                   const uint32_t *filter_of_query, uint32_t *out_ids, float *out_distances,
+                                   uint32_t *out_counts);
+/* How ah_search_batch_filters cut its calls, and the filters of the index.  Counts since the index was created or since the
+ * last call with reset != 0 (filters_alive is a level, never reset). */
+typedef struct ah_filter_stats {
+    uint64_t calls;                 /* ah_search_batch_filters calls that reached the device                           */
+    uint64_t uniform_batches;       /* sub-batches of one filter (or of unfiltered queries): the paths of ah_search_batch */
+    uint64_t mixed_batches;         /* sub-batches whose queries are under different filters: sorted re-rank           */
+    uint64_t uniform_queries;
+    uint64_t mixed_queries;
+    uint64_t filters_created;
+    uint64_t filters_alive;
+    uint64_t leaf_kept_passes;      /* passes over every Descendants id at filter creation (one per filter)            */
+} ah_filter_stats;
+AH_API int ah_index_filter_stats(ah_index *index, ah_filter_stats *out, int reset);
+
 /* Incremental insert routing, `insert_items_in_descendants_from_frozen_reader` (src/writer.rs:1398-1459), for
  * every tree of the index at once: each of the `n` items (they must already be rows of the index's dataset — the
  * reference also re-creates `ImmutableLeafs` over all current items for every build, src/writer.rs:530) walks from
