@@ -61,6 +61,12 @@ class AhForestView(C.Structure):
                 ("descendants_len", C.c_uint64)]
 
 
+class AhIndexDeltaView(C.Structure):
+    _fields_ = [("n_removed", C.c_uint64), ("removed", C.POINTER(C.c_uint32)), ("n_put", C.c_uint64),
+                ("put_index", C.POINTER(C.c_uint32)), ("put", C.POINTER(AhNode)), ("desc", C.POINTER(C.c_uint32)),
+                ("desc_len", C.c_uint64), ("n_trees", C.c_uint32), ("roots", C.POINTER(C.c_uint32))]
+
+
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64)
 
 
@@ -209,6 +215,12 @@ SIGNATURES = {
     "ah_search_batch_filters": (C.c_int, [_VP, _F32P, _U32P, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t,
                                           C.POINTER(C.c_void_p), C.c_size_t, _U32P, _U32P, _F32P, _U32P]),
     "ah_index_filter_stats": (C.c_int, [_VP, C.POINTER(AhFilterStats), C.c_int]),
+    # deletes on a resident index; an index kept across an update of its dataset
+    "ah_index_delete_items": (C.c_int, [_VP, _U32P, C.c_size_t, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "ah_index_delta_get": (C.c_int, [_VP, C.POINTER(AhIndexDeltaView)]),
+    "ah_index_delta_destroy": (C.c_int, [_VP]),
+    "ah_index_suspend": (C.c_int, [_VP]),
+    "ah_index_resume": (C.c_int, [_VP, _VP]),
     "ah_bench_scan": (C.c_int, [_VP, C.c_uint32, C.c_uint64, C.c_uint32, _F32P, C.POINTER(C.c_double)]),
     "ah_bench_memcpy": (C.c_int, [C.c_int, C.c_uint64, C.c_uint32, C.POINTER(C.c_double)]),
     "ah_bench_read": (C.c_int, [C.c_int, C.c_uint64, C.c_uint32, C.POINTER(C.c_double)]),

@@ -19,6 +19,7 @@
 #include <new>
 
 #include "common.h"
+#include "index_device.h"
 #include "split_device.h"
 #include "screen_device.h"
 
@@ -26,13 +27,6 @@ namespace ah {
 
 static constexpr uint32_t kHeapLds = 1024;   // queue entries per query in LDS (8 KiB)
 static constexpr uint32_t kSortLds = 16384;  // candidate ids sorted in LDS per query (64 KiB)
-
-struct DNode {
-    uint32_t kind;  // AH_NODE_*; bit 8 = has_normal
-    uint32_t a;     // SPLIT: left            DESCENDANTS: first id (index into the blob)
-    uint32_t b;     // SPLIT: right           DESCENDANTS: count
-    uint32_t c;     // SPLIT: normal row      DESCENDANTS: unused
-};
 
 // One popped Descendants node of one query: the leaf-tile re-rank groups these by node.
 struct Visit {
@@ -3454,6 +3448,7 @@ __global__ void k_load_items_as_queries(DataView dv, const uint32_t *__restrict_
 // insert_items_in_descendants_from_frozen_reader (src/writer.rs:1398-1459) for every (tree, new item) pair at once:
 // each pair walks from the root to the Descendants node the item lands in.  One octet per pair.
 __global__ __launch_bounds__(256) void k_route_items(DataView dv, DataView nv, const DNode *__restrict__ nodes,
+                                                     const uint32_t *__restrict__ rank,
                                                      const uint32_t *__restrict__ roots, uint32_t n_trees,
                                                      const uint32_t *__restrict__ ids, uint64_t n,
                                                      const uint64_t *__restrict__ seeds, uint32_t *__restrict__ out_leaf,
@@ -3490,15 +3485,9 @@ __global__ __launch_bounds__(256) void k_route_items(DataView dv, DataView nv, c
         }
         uint32_t right;
         if (nd.kind & 0x100u) right = side_of_margin(descent_margin(nv, nd.c, leaf_vec, lh, j));  // D::side
-        else right = ah_route_side_is_left(seeds[t], node, id) ^ 1u;                               // Side::random
+        else right = ah_route_side_is_left(seeds[t], rank ? rank[node] : node, id) ^ 1u;           // Side::random
         node = right ? nd.b : nd.a;
     }
-}
-
-__global__ void k_filter_bitmap(const uint32_t *__restrict__ ids, uint64_t n, uint32_t *bits) {
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; g < n; g += stride)
-        atomicOr(&bits[ids[g] >> 5], 1u << (ids[g] & 31));
 }
 
 // How many of the listed ids are rows of the dataset, by its id -> row table (ah_filter_create on sparse ids; identity ids
@@ -3597,28 +3586,19 @@ int launch_rerank_screened(ah_dataset *ds, uint32_t nq, const uint8_t *d_qvecs, 
     return AH_OK;
 }
 
+// the binary16 shadow of the rows for the certified top-k screen of the re-rank (made once per dataset; the forest build
+// of an f32 dataset has usually made it already).  No memory for it = no screen, not an error.
+void index_prepare_screens(ah_dataset *ds) {
+    if (tun(TUN_SEARCH_SCREEN) != 0 && (ds->metric == AH_COSINE || ds->metric == AH_DOT_PRODUCT) && ds->dims >= 32 && ds->n) {
+        ContextLease lease(ds);
+        if (lease.c && ensure_screen(ds, lease.c->stream, false) && tun(TUN_SEARCH_SCREEN8) != 0)
+            (void)ensure_screen8_search(ds, lease.c->stream);  // ... and the int8 copy in front of it (round 6), likewise
+    }
+}
+
 }  // namespace ah
 
 using namespace ah;
-
-struct ah_index {
-    ah_dataset *ds = nullptr;
-    DataView nv{};  // the normals as a row matrix
-    DNode *d_nodes = nullptr;
-    uint32_t *d_roots = nullptr, *d_desc = nullptr;
-    void *d_nrows = nullptr;
-    float *d_nhdrs = nullptr;
-    uint32_t n_trees = 0, n_nodes = 0, n_normals = 0, max_desc = 0;
-    uint32_t n_leaves = 0;  // Descendants nodes (desc_len / n_leaves: the mean leaf, what the small-submission gate estimates with)
-    uint64_t desc_len = 0;
-    std::mutex stats_mu;       // ah_search_batch may run on any number of threads
-    ah_search_stats stats{};
-    std::atomic<uint32_t> search8_fails{0};  // sub-batches whose int8 stage left too many survivors ...
-    std::atomic<uint32_t> search8_seen{0};   // ... among this many it served (screen8_window_note: windows of 64) ...
-    std::atomic<bool> search8_off{false};    // ... eight in one window: the index's tile re-rank starts on the binary16 rows from now on
-    bool counted = false;                    // counted in ds->live_indexes (an update of the dataset refuses meanwhile)
-    ah_filter_stats fstats{};                // under stats_mu; filters_alive is a level (ah_index_destroy refuses above 0)
-};
 
 // `QueryBuilder::candidates` resident on the device of its index: one block [bitmap over 0 .. largest stored id][per node:
 // |descendants & candidates|].  Immutable after ah_filter_create.
@@ -3646,6 +3626,7 @@ int ah_index_destroy(ah_index *ix) {
     if (ix->d_nodes) (void)dev_free(ix->d_nodes);
     if (ix->d_roots) (void)dev_free(ix->d_roots);
     if (ix->d_desc) (void)dev_free(ix->d_desc);
+    if (ix->d_rank) (void)dev_free(ix->d_rank);
     if (ix->d_nrows) (void)dev_free(ix->d_nrows);
     if (ix->d_nhdrs) (void)dev_free(ix->d_nhdrs);
     if (ix->counted) ix->ds->live_indexes.fetch_sub(1, std::memory_order_acq_rel);
@@ -3807,13 +3788,7 @@ int ah_index_create_from_view(ah_dataset *ds, const ah_forest_view *view, ah_ind
     }
 #undef AH_IX
     (void)st;
-    // the binary16 shadow of the rows for the certified top-k screen of the re-rank (made once per dataset; the forest build
-    // of an f32 dataset has usually made it already).  No memory for it = no screen, not an error.
-    if (tun(TUN_SEARCH_SCREEN) != 0 && (ds->metric == AH_COSINE || ds->metric == AH_DOT_PRODUCT) && ds->dims >= 32 && ds->n) {
-        ContextLease lease(ds);
-        if (lease.c && ensure_screen(ds, lease.c->stream, false) && tun(TUN_SEARCH_SCREEN8) != 0)
-            (void)ensure_screen8_search(ds, lease.c->stream);  // ... and the int8 copy in front of it (round 6), likewise
-    }
+    index_prepare_screens(ds);
     ix->nv.metric = ds->metric;
     ix->nv.dims = ds->dims;
     ix->nv.pitch = ds->pitch;
@@ -4539,6 +4514,7 @@ static int search_chunk(ah_index *ix, Context *ctx, const float *queries, const 
 int ah_route_items(ah_index *ix, const uint32_t *item_ids, size_t n, const uint64_t *tree_seeds, uint32_t *out_leaf) {
     AH_GUARDED("ah_route_items")
     AH_REQUIRE(ix && ix->ds, AH_ERR_INVALID_ARGUMENT, "index is NULL");
+    AH_INDEX_LIVE(ix);
     AH_REQUIRE((item_ids && out_leaf && tree_seeds) || n == 0, AH_ERR_INVALID_ARGUMENT, "NULL argument");
     if (n == 0 || ix->n_trees == 0) return AH_OK;
     ah_dataset *ds = ix->ds;
@@ -4566,8 +4542,8 @@ int ah_route_items(ah_index *ix, const uint32_t *item_ids, size_t n, const uint6
     AH_HIP(hipMemcpyAsync(d_seeds, h_seeds, (size_t)ix->n_trees * 8, hipMemcpyHostToDevice, s));
     AH_HIP(hipMemsetAsync(d_err, 0, 4, s));
     const unsigned grid = (unsigned)((pairs * 8 + 255) / 256);
-    hipLaunchKernelGGL(k_route_items, dim3(grid), dim3(256), 0, s, ds->view(), ix->nv, ix->d_nodes, ix->d_roots, ix->n_trees,
-                       d_ids, (uint64_t)n, d_seeds, d_leaf, d_err);
+    hipLaunchKernelGGL(k_route_items, dim3(grid), dim3(256), 0, s, ds->view(), ix->nv, ix->d_nodes, (const uint32_t *)ix->d_rank,
+                       ix->d_roots, ix->n_trees, d_ids, (uint64_t)n, d_seeds, d_leaf, d_err);
     AH_HIP(hipGetLastError());
     AH_HIP(hipMemcpyAsync(h_leaf, d_leaf, pairs * 4, hipMemcpyDeviceToHost, s));
     AH_HIP(hipMemcpyAsync(h_err, d_err, 4, hipMemcpyDeviceToHost, s));
@@ -4636,6 +4612,7 @@ int ah_search_batch(ah_index *ix, const float *queries, const uint32_t *query_it
                     uint32_t *out_ids, float *out_distances, uint32_t *out_counts) {
     AH_GUARDED("ah_search_batch")
     AH_REQUIRE(ix && ix->ds, AH_ERR_INVALID_ARGUMENT, "index is NULL");
+    AH_INDEX_LIVE(ix);
     ah_dataset *ds = ix->ds;
     AH_REQUIRE((queries != nullptr) != (query_items != nullptr), AH_ERR_INVALID_ARGUMENT,
                "exactly one of queries / query_items must be given");
@@ -4650,7 +4627,7 @@ int ah_search_batch(ah_index *ix, const float *queries, const uint32_t *query_it
     }
     for (size_t q = 0; q < nq; q++) out_counts[q] = 0;
     AH_REQUIRE(!have_filter || n_filter == 0 || filter_sorted, AH_ERR_INVALID_ARGUMENT, "filter_sorted is NULL");
-    if (ds->n == 0 || ix->n_trees == 0) return AH_OK;  // reader.rs:323-325
+    if (ds->n == 0 || ix->n_trees == 0 || ix->desc_len == 0) return AH_OK;  // reader.rs:323-325; trees that hold no id
     SearchShape shape;
     AH_TRY(search_shape(ix, query_items, nq, count, search_k, oversampling, shape));
     const uint64_t sk_eff = shape.sk_eff, stride = shape.stride;
@@ -4741,6 +4718,7 @@ int ah_filter_create(ah_index *ix, const uint32_t *sorted_ids, size_t n, ah_filt
         AH_REQUIRE(sorted_ids[i - 1] < sorted_ids[i], AH_ERR_INVALID_ARGUMENT, "sorted_ids is not strictly ascending at position %zu (%u after %u)",
                    i, sorted_ids[i], sorted_ids[i - 1]);
     AH_REQUIRE(ix && ix->ds, AH_ERR_INVALID_ARGUMENT, "index is NULL");
+    AH_INDEX_LIVE(ix);
     ah_dataset *ds = ix->ds;
     AH_HIP(hipSetDevice(ds->device));
     std::unique_ptr<ah_filter> f(new ah_filter);
@@ -4866,6 +4844,7 @@ int ah_search_batch_filters(ah_index *ix, const float *queries, const uint32_t *
             AH_REQUIRE(filter_of_query[q] == AH_NO_FILTER || filter_of_query[q] < n_filters, AH_ERR_INVALID_ARGUMENT,
                        "filter_of_query[%zu] = %u names no filter (n_filters = %zu)", q, filter_of_query[q], n_filters);
     AH_REQUIRE(ix && ix->ds, AH_ERR_INVALID_ARGUMENT, "index is NULL");
+    AH_INDEX_LIVE(ix);
     for (size_t i = 0; i < n_filters; i++) {
         AH_REQUIRE(filters[i], AH_ERR_INVALID_ARGUMENT, "filters[%zu] is NULL", i);
         AH_REQUIRE(filters[i]->ix == ix, AH_ERR_INVALID_ARGUMENT, "filters[%zu] belongs to another index", i);
@@ -4880,7 +4859,7 @@ int ah_search_batch_filters(ah_index *ix, const float *queries, const uint32_t *
         memcpy(&out_distances[i], &nan_bits, 4);
     }
     for (size_t q = 0; q < nq; q++) out_counts[q] = 0;
-    if (ds->n == 0 || ix->n_trees == 0) return AH_OK;  // reader.rs:323-325
+    if (ds->n == 0 || ix->n_trees == 0 || ix->desc_len == 0) return AH_OK;  // reader.rs:323-325; trees that hold no id
     SearchShape shape;
     AH_TRY(search_shape(ix, query_items, nq, count, search_k, oversampling, shape));
     const size_t chunk = shape.chunk;

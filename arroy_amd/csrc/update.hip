@@ -18,14 +18,13 @@
 #include <vector>
 
 #include "common.h"
+#include "scan_device.h"
 
 using namespace ah;
 
 namespace {
 
 constexpr unsigned kUpBlock = 256;                          // 4 waves
-constexpr uint32_t kScanPer = 16;                           // elements per thread of the scan
-constexpr uint32_t kScanTile = kUpBlock * kScanPer;         // elements per block of the scan
 enum Path { kInPlace = 0, kAppend = 1, kMerge = 2 };
 const char *const kPathName[3] = {"in place", "append", "merge"};
 
@@ -57,71 +56,6 @@ __global__ __launch_bounds__(kUpBlock) void k_update_flags(const uint32_t *__res
         keep[r] = leaves ? 0u : 1u;
         ins[r] = (uint32_t)u;
     }
-}
-
-// inclusive sum over the 64 lanes of a wave
-__device__ __forceinline__ uint32_t wave_inclusive_sum(uint32_t x) {
-    const uint32_t lane = threadIdx.x & 63u;
-#pragma unroll
-    for (uint32_t off = 1; off < 64; off <<= 1) {
-        const uint32_t t = __shfl_up(x, off, 64);
-        if (lane >= off) x += t;
-    }
-    return x;
-}
-
-// plan, step 2: exclusive scan of the keep flags in place, tile by tile (kScanTile elements a block) ...
-__global__ __launch_bounds__(kUpBlock) void k_scan_tiles(uint32_t *__restrict__ v, uint64_t n, uint32_t *__restrict__ tile_sums) {
-    __shared__ uint32_t wave_sums[kUpBlock / 64];
-    const uint64_t base = (uint64_t)blockIdx.x * kScanTile + (uint64_t)threadIdx.x * kScanPer;
-    uint32_t x[kScanPer];
-    uint32_t sum = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < kScanPer; k++) {
-        x[k] = base + k < n ? v[base + k] : 0u;
-        sum += x[k];
-    }
-    const uint32_t incl = wave_inclusive_sum(sum);
-    const uint32_t wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63u) == 63u) wave_sums[wave] = incl;
-    __syncthreads();
-    uint32_t run = incl - sum;
-    for (uint32_t w = 0; w < wave; w++) run += wave_sums[w];
-    if (threadIdx.x == kUpBlock - 1) tile_sums[blockIdx.x] = run + sum;
-#pragma unroll
-    for (uint32_t k = 0; k < kScanPer; k++) {
-        if (base + k < n) v[base + k] = run;
-        run += x[k];
-    }
-}
-// ... the tiles' sums scanned by one block (their exclusive prefix in place, the grand total into *total) ...
-__global__ __launch_bounds__(1024) void k_scan_sums(uint32_t *__restrict__ sums, uint64_t nb, uint32_t *__restrict__ total) {
-    __shared__ uint32_t wave_sums[16];
-    __shared__ uint32_t carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (uint64_t c0 = 0; c0 < nb; c0 += 1024) {
-        const uint64_t i = c0 + threadIdx.x;
-        const uint32_t x = i < nb ? sums[i] : 0u;
-        const uint32_t incl = wave_inclusive_sum(x);
-        const uint32_t wave = threadIdx.x >> 6;
-        if ((threadIdx.x & 63u) == 63u) wave_sums[wave] = incl;
-        __syncthreads();
-        uint32_t off = carry;
-        for (uint32_t w = 0; w < wave; w++) off += wave_sums[w];
-        if (i < nb) sums[i] = off + incl - x;
-        __syncthreads();  // (every thread has read `carry` and `wave_sums`)
-        if (threadIdx.x == 1023) carry = off + incl;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *total = carry;
-}
-// ... and added back to every element of its tile
-__global__ __launch_bounds__(kUpBlock) void k_scan_add(uint32_t *__restrict__ v, uint64_t n, const uint32_t *__restrict__ tile_sums) {
-    const uint32_t add = tile_sums[blockIdx.x];
-    const uint64_t base = (uint64_t)blockIdx.x * kScanTile;
-    for (uint32_t k = threadIdx.x; k < kScanTile; k += kUpBlock)
-        if (base + k < n) v[base + k] += add;
 }
 
 // the row each upserted item goes to: merge: j + the kept old rows below its id; in place: the old row holding its id;
@@ -380,15 +314,11 @@ int launch_plan(MemberUpdate *mu, const Plan &p, const UpdateArgs &a) {
     uint32_t *keep_rank = mu->keep_rank.as<uint32_t>();
     if (p.path == kMerge) {
         if (a.n_rm) AH_HIP(hipMemcpyAsync(mu->rm.p, a.rm, a.n_rm * 4, hipMemcpyHostToDevice, s));
-        const uint64_t nb = (p.n_old + kScanTile - 1) / kScanTile;
-        if (p.n_old) {
+        if (p.n_old)
             hipLaunchKernelGGL(k_update_flags, dim3(grid_of(p.n_old, kUpBlock, 1u << 16)), dim3(kUpBlock), 0, s, ds->d_ids, p.n_old,
                                mu->rm.as<const uint32_t>(), (uint64_t)a.n_rm, mu->side_ids.as<const uint32_t>(), (uint64_t)a.n_up,
                                keep_rank, mu->ins.as<uint32_t>());
-            hipLaunchKernelGGL(k_scan_tiles, dim3((unsigned)nb), dim3(kUpBlock), 0, s, keep_rank, p.n_old, mu->tile_sums.as<uint32_t>());
-        }
-        hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(1024), 0, s, mu->tile_sums.as<uint32_t>(), nb, keep_rank + p.n_old);
-        if (p.n_old) hipLaunchKernelGGL(k_scan_add, dim3((unsigned)nb), dim3(kUpBlock), 0, s, keep_rank, p.n_old, mu->tile_sums.as<const uint32_t>());
+        launch_exclusive_scan(keep_rank, p.n_old, mu->tile_sums.as<uint32_t>(), keep_rank + p.n_old, s);
     }
     if (a.n_up)
         hipLaunchKernelGGL(k_upsert_dest, dim3(grid_of(a.n_up, kUpBlock, 4096)), dim3(kUpBlock), 0, s, mu->side_ids.as<const uint32_t>(),

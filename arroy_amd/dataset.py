@@ -629,6 +629,42 @@ class Index:
         _lib.check(_lib.lib().ah_route_items(self._h, _ptr(ids), ids.size, _ptr(seeds), _ptr(out)))
         return out
 
+    def delete_items(self, sorted_ids, split_after: int) -> dict:
+        """ah_index_delete_items: `delete_items_from_trees` (src/writer.rs:978-1114) on the resident index.  `sorted_ids`
+        ascending and distinct.  Returns the delta for the host's store (TreeStore.apply_delta), in index-local node indices:
+        removed, put_index, put (kind / has_normal / left / right, or offset / count into desc), desc, roots."""
+        arr = _u32(sorted_ids).ravel()
+        h = C.c_void_p()
+        _lib.check(_lib.lib().ah_index_delete_items(self._h, _ptr(arr), arr.size, int(split_after), C.byref(h)))
+        try:
+            v = _lib.AhIndexDeltaView()
+            _lib.check(_lib.lib().ah_index_delta_get(h, C.byref(v)))
+
+            def u32s(p, n):
+                return np.ctypeslib.as_array(p, shape=(n,)).copy() if n else np.zeros(0, np.uint32)
+            node_dt = np.dtype([("kind", "u1"), ("has_normal", "u1"), ("reserved", "<u2"), ("tree", "<u4"), ("left", "<u4"),
+                                ("right", "<u4"), ("offset", "<u8"), ("count", "<u4"), ("depth", "<u4")], align=True)
+            assert node_dt.itemsize == C.sizeof(_lib.AhNode)
+            n_put = int(v.n_put)
+            put = np.frombuffer(C.string_at(v.put, n_put * node_dt.itemsize), dtype=node_dt).copy() if n_put else np.zeros(0, node_dt)
+            return {"removed": u32s(v.removed, int(v.n_removed)), "put_index": u32s(v.put_index, n_put), "put": put,
+                    "desc": u32s(v.desc, int(v.desc_len)), "roots": u32s(v.roots, int(v.n_trees))}
+        finally:
+            _lib.lib().ah_index_delta_destroy(h)
+
+    def suspend(self) -> None:
+        """ah_index_suspend: give up the hold on the dataset, so that Dataset.update_vectors goes through; until resume()
+        every search, route, filter or delete call on this index is refused.  The live filters of the index are closed first,
+        as close() does (ah_index_suspend refuses while one is alive)."""
+        for f in list(self._filters):
+            f.close()
+        _lib.check(_lib.lib().ah_index_suspend(self._h))
+
+    def resume(self, dataset: Optional[Dataset] = None) -> None:
+        """ah_index_resume on the dataset the index was made on (the default), after its update."""
+        ds = self.dataset if dataset is None else dataset
+        _lib.check(_lib.lib().ah_index_resume(self._h, ds._h))
+
     def close(self) -> None:
         if self._h:
             for f in list(self._filters):  # (ah_index_destroy refuses while one is alive)

@@ -136,6 +136,24 @@ class TreeStore:
             self.nodes[node] = ("S", new_left, new_right, hdr, vec)
         return node, None
 
+    def apply_delta(self, delta: dict, dense: Dict[int, int]) -> None:
+        """What Index.delete_items did to the resident index, done to this store: `delta` speaks in the dense node indices of
+        the view the index was made from, `dense` (store id -> index, `to_view`'s keep[4]) maps them back.  A node that
+        became a Descendants node loses its plane; a split node keeps its own."""
+        back = {i: nid for nid, i in dense.items()}
+        for i in delta["removed"]:
+            del self.nodes[back[int(i)]]
+        desc = delta["desc"]
+        for i, nd in zip(delta["put_index"], delta["put"]):
+            nid = back[int(i)]
+            if int(nd["kind"]) == 1:
+                off, cnt = int(nd["offset"]), int(nd["count"])
+                self.nodes[nid] = ("D", np.array(desc[off:off + cnt], dtype=np.uint32))
+            else:
+                old = self.nodes[nid]
+                self.nodes[nid] = ("S", back[int(nd["left"])], back[int(nd["right"])], old[3], old[4])
+        self.roots = [back[int(r)] for r in delta["roots"]]
+
     def import_tree(self, forest: Forest, tree: int, root_id: Optional[int] = None) -> int:
         """Copy tree `tree` of a freshly built ah_forest; children get fresh ids before their parent (the order
         `make_tree_in_file` allocates them, src/writer.rs:1235-1258), the root takes `root_id` when given
@@ -254,6 +272,7 @@ class _IndexState:
         self.trees: Optional[TreeStore] = None
         self.index = None    # arroy_amd.Index: dataset + tree nodes resident in HBM
         self._keep = None    # arrays the index view was built from
+        self.device_deletes = 0  # builds that took the updated items out of the trees on the device (Index.delete_items)
 
 
 class Database:
@@ -327,6 +346,7 @@ class ArroyBuilder:
         self._split_after: Optional[int] = None
         self._cancel: Optional[Callable[[], bool]] = None
         self._progress: Optional[Callable] = None
+        self.device_delete = True  # False: the removal of updated items always on the host (what the tests compare with)
 
     def n_trees(self, n: int) -> "ArroyBuilder":
         self._n_trees = int(n)
@@ -359,41 +379,62 @@ class ArroyBuilder:
         ids = np.array(sorted(st.items), dtype=np.uint32)
         n = ids.size
         split_after = self._split_after or w.dimensions
-        if st.index is not None:
-            st.index.close()  # it holds row positions: the dataset can be updated only once it is gone
+        # The index of the last build stays for this build's delete and routing (suspended while the dataset is updated)
+        # when this will be an incremental build on the same dataset that drops no tree: `delete_extra_trees` runs before
+        # the removal, and the resident index would still hold the dropped trees.
+        resident = st.index
         st.index = None
-        self._group = None
-        ds = self._update_dataset(st) if n else None  # the last build's dataset with this build's item changes, if any
-        if ds is None and n and self._devices is not None:
-            from .dataset import DatasetGroup
-            vecs = np.stack([st.items[int(i)] for i in ids])
-            self._group = DatasetGroup(dist, w.dimensions, n, self._devices)
-            self._group.upload_vectors(ids, vecs)
-            if dist.metric == 3:
-                self._group.preprocess_dot()
-            self._group.finalize()
-            ds = self._group.member(0)  # search and the incremental paths use member 0 (it keeps the group alive)
-        elif ds is None and n:
-            vecs = np.stack([st.items[int(i)] for i in ids])
-            ds = Dataset(dist, w.dimensions, n)
-            ds.upload_vectors(ids, vecs)
-            if dist.metric == 3:
-                ds.preprocess_dot()  # pre_process_items, src/writer.rs:964-976
-            ds.finalize()
-        st.dataset = ds
-        if n <= split_after:
-            # clear_db_and_create_a_single_leaf (src/writer.rs:916-962): ONE Descendants root, whatever n_trees says
-            st.trees = TreeStore()
-            if n:
-                root = st.trees.next_id()
-                st.trees.nodes[root] = ("D", ids.copy())
-                st.trees.roots = [root]
-        elif st.trees is None or not st.trees.roots or st.metadata is None:
-            st.trees = TreeStore()
-            n_trees = target_n_trees(self._n_trees, w.dimensions, n, 0)
-            self._add_trees(ds, st.trees, n_trees, split_after)
-        else:
-            self._incremental(ds, st, ids, split_after)
+        keep = (resident is not None and self.device_delete and n > split_after and st.trees is not None
+                and bool(st.trees.roots) and st.metadata is not None
+                and target_n_trees(self._n_trees, w.dimensions, n, len(st.trees.roots)) >= len(st.trees.roots))
+        try:  # (whatever happens in between, the kept index does not linger suspended with its normals in HBM)
+            if resident is not None:
+                if keep:
+                    resident.suspend()
+                else:
+                    resident.close()  # (an update of the dataset refuses while an index holds it)
+                    resident = None
+            self._group = None
+            ds = self._update_dataset(st) if n else None  # the last build's dataset with this build's item changes, if any
+            if resident is not None:
+                if ds is not None:
+                    resident.resume(ds)
+                else:  # staged afresh: the index is of the old dataset
+                    resident.close()
+                    resident = None
+            if ds is None and n and self._devices is not None:
+                from .dataset import DatasetGroup
+                vecs = np.stack([st.items[int(i)] for i in ids])
+                self._group = DatasetGroup(dist, w.dimensions, n, self._devices)
+                self._group.upload_vectors(ids, vecs)
+                if dist.metric == 3:
+                    self._group.preprocess_dot()
+                self._group.finalize()
+                ds = self._group.member(0)  # search and the incremental paths use member 0 (it keeps the group alive)
+            elif ds is None and n:
+                vecs = np.stack([st.items[int(i)] for i in ids])
+                ds = Dataset(dist, w.dimensions, n)
+                ds.upload_vectors(ids, vecs)
+                if dist.metric == 3:
+                    ds.preprocess_dot()  # pre_process_items, src/writer.rs:964-976
+                ds.finalize()
+            st.dataset = ds
+            if n <= split_after:
+                # clear_db_and_create_a_single_leaf (src/writer.rs:916-962): ONE Descendants root, whatever n_trees says
+                st.trees = TreeStore()
+                if n:
+                    root = st.trees.next_id()
+                    st.trees.nodes[root] = ("D", ids.copy())
+                    st.trees.roots = [root]
+            elif st.trees is None or not st.trees.roots or st.metadata is None:
+                st.trees = TreeStore()
+                n_trees = target_n_trees(self._n_trees, w.dimensions, n, 0)
+                self._add_trees(ds, st.trees, n_trees, split_after)
+            else:
+                self._incremental(ds, st, ids, split_after, resident)
+        finally:
+            if resident is not None:
+                resident.close()  # (a second close is a no-op: _incremental closes it when it is done with it)
         if n:
             view, keep = st.trees.to_view(dist, w.dimensions)
             from .dataset import Index
@@ -476,7 +517,10 @@ class ArroyBuilder:
             if watcher_stop is not None:
                 watcher_stop.set()
 
-    def _incremental(self, ds: Dataset, st: "_IndexState", ids: np.ndarray, split_after: int) -> None:
+    def _incremental(self, ds: Dataset, st: "_IndexState", ids: np.ndarray, split_after: int, resident=None) -> None:
+        """`resident`: the last build's Index, resumed on the updated dataset (build() has checked that no tree is dropped): the
+        removal and the routing run on it and it is closed here.  None: the removal on the host, the routing on a throw-away
+        index of the store's view."""
         from .dataset import Index
         w, trees, dist = self._w, st.trees, self._w.database.distance
         present = set(int(i) for i in ids)
@@ -493,19 +537,32 @@ class ArroyBuilder:
             trees.roots.pop()
             trees.delete_tree(root)
         # delete_items_from_trees (:525, 979-1114): updated ids leave the trees, emptied / shrunken branches collapse
-        if to_delete.size:
+        if resident is not None:
+            try:
+                dense = st._keep[4]
+                if to_delete.size:
+                    trees.apply_delta(resident.delete_items(to_delete, split_after), dense)
+                    st.device_deletes += 1
+            except BaseException:
+                resident.close()
+                raise
+        elif to_delete.size:
             gone = set(int(i) for i in to_delete)
             trees.roots = [trees.delete_items(root, gone, split_after)[0] for root in trees.roots]
         trees.roots.sort()
         # insert_items_in_current_trees (:541-542): one ah_route_items call for all trees
         grown: Dict[int, List[int]] = {}
         if to_insert.size and trees.roots:
-            view, keep = trees.to_view(dist, w.dimensions)
-            dense = keep[4]
+            if resident is None:
+                view, keep = trees.to_view(dist, w.dimensions)
+                dense = keep[4]
+                resident = Index(ds, None, view=view)
             back = {i: nid for nid, i in dense.items()}
-            old = Index(ds, None, view=view)
-            leaf_of = old.route_items(to_insert, self._seeds(len(trees.roots)))
-            old.close()
+            try:
+                leaf_of = resident.route_items(to_insert, self._seeds(len(trees.roots)))
+            finally:
+                resident.close()
+                resident = None
             for t in range(leaf_of.shape[0]):
                 for i, leaf in enumerate(leaf_of[t]):
                     grown.setdefault(back[int(leaf)], []).append(int(to_insert[i]))
@@ -518,6 +575,8 @@ class ArroyBuilder:
             forest = ds.build_subtrees([trees.nodes[nid][1] for nid in large], self._seeds(len(large)), split_after)
             for t, nid in enumerate(large):
                 trees.import_tree(forest, t, root_id=nid)  # the sub-tree's root keeps the descendant's id (:693-702)
+        if resident is not None:
+            resident.close()
         # missing trees (:556-561)
         self._add_trees(ds, trees, want - len(trees.roots), split_after)
 

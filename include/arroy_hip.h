@@ -683,6 +683,74 @@ AH_API int ah_route_items(ah_index *index, const uint32_t *item_ids, size_t n, c
                           uint32_t *out_leaf);
 
 /* ------------------------------------------------------------------------------------------
+ * Deletes on a resident index (ABI v7 addition: look the symbols up).  `delete_items_from_trees` (src/writer.rs:978-1114),
+ * the first tree step of an incremental `Writer::build`, applied to the index where it lives, so that the index of the last
+ * build serves this build's ah_route_items instead of being uploaded again.
+ *
+ * `sorted_ids` strictly ascending; ids that are in no tree are legal (a RoaringBitmap may hold anything), 0xFFFFFFFF is a
+ * legal id, n == 0 is legal.  `split_after` is the bound of `fit_in_descendant` (n <= split_after, src/writer.rs:474-477).
+ * Bottom-up, as `delete_items_in_file` does, every node yields (replacement node, Some(ids) | None):
+ *   - a Descendants node keeps descendants - sorted_ids, ascending; it is put only if its length changed; Some(kept);
+ *   - a split node whose new children are (L, l) and (R, r), first case that matches:
+ *       l is Some and empty      L and the node are removed, (R, r) takes its place (with both empty the right child stays,
+ *                                as an empty Descendants node);
+ *       r is Some and empty      R and the node are removed, (L, l) takes its place;
+ *       both Some and |l| + |r| <= split_after
+ *                                L and R are removed, the node becomes Descendants of l U r (always put), and may merge
+ *                                again with its sibling one level up;
+ *       otherwise                it stays a split node, put only if a child changed; None.
+ *   A root that is a Descendants node stays, even empty.  Afterwards the roots are in ascending node order
+ *   (`roots.sort_unstable()`, src/writer.rs:1001).  An id is expected at most once per tree, as in every forest the
+ *   reference writes.  With n == 0 the delta is empty unless the forest holds siblings that fit together.  A merged node
+ *   of more than 4096 ids (a split_after that large) is sorted by one block in device memory, as are more than 4096 roots:
+ *   correct, and slow only there.
+ *
+ * The index afterwards: node indices are stable, removed nodes (and nodes no root reaches) are free slots, the roots are
+ * in the new order, the descendants are rewritten into new memory, the normals are not touched.  ah_search_batch* and
+ * ah_route_items return what an ah_index_create_from_view of the forest after the delete returns on the same dataset: the
+ * same ids, distance bits and counts, the same landing nodes (a hole never changes the relative order of the surviving
+ * node indices, so every (distance, node) tie-break holds).
+ *
+ * The delta is what the host writes to its store (the final state of `TmpNodes`): `removed` node indices ascending; `put`,
+ * the nodes that stay and whose content changed, ascending by `put_index`, each an ah_node with kind and has_normal and
+ * either left / right or (offset, count) into `desc` (ascending ids); `roots` in the index's new tree order.  A node put
+ * and later removed by its parent's merge is in `removed` only.  ah_node.tree and .depth are 0.
+ *
+ * All or nothing: a bad argument or a failed allocation leaves the index as it was, searchable.  Refused
+ * (AH_ERR_INVALID_ARGUMENT) while the index has live filters (their per-node counts would be stale) or is suspended.
+ * Not concurrent with any other call on the same index: searches of other threads must have returned.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct ah_index_delta ah_index_delta;
+typedef struct ah_index_delta_view {
+    uint64_t n_removed;
+    const uint32_t *removed;
+    uint64_t n_put;
+    const uint32_t *put_index;
+    const ah_node *put;
+    const uint32_t *desc;
+    uint64_t desc_len;
+    uint32_t n_trees;
+    const uint32_t *roots;
+} ah_index_delta_view;
+AH_API int ah_index_delete_items(ah_index *index, const uint32_t *sorted_ids, size_t n, uint32_t split_after,
+                                 ah_index_delta **out_delta);
+/* Pointers into the delta, valid until ah_index_delta_destroy. */
+AH_API int ah_index_delta_get(const ah_index_delta *d, ah_index_delta_view *out);
+AH_API int ah_index_delta_destroy(ah_index_delta *d);
+
+/* An index outlives an update of its dataset.  An ah_index stores ITEM IDS, never row positions — its descendants are a
+ * copy of the view's ids and every kernel goes from an id to its row through the dataset as it is at the time of the
+ * call — so nothing in it goes stale when ah_dataset_update_* moves rows.  ah_index_suspend gives up the index's hold on
+ * the dataset (the update's "no live index" rule then lets the update through); until ah_index_resume every search, route,
+ * filter or delete call on the index is refused (AH_ERR_INVALID_ARGUMENT), ah_index_destroy is not.  Refused while the index
+ * has live filters.  ah_index_resume takes the hold again on the SAME dataset handle, which must be finalized (and has by
+ * construction the metric, dimensions and device of the index; each is checked and named when it differs).  Ids of the
+ * index that the update removed from the dataset must leave the index (ah_index_delete_items) before it is searched: a
+ * search expects every id of its index to be a row of the dataset.  Host code only. */
+AH_API int ah_index_suspend(ah_index *index);
+AH_API int ah_index_resume(ah_index *index, ah_dataset *ds);
+
+/* ------------------------------------------------------------------------------------------
  * Measurement helpers (bench.py).  They time with hipEvents recorded on the same stream the
  * kernels run on and never touch the host data path.
  * ---------------------------------------------------------------------------------------- */
