@@ -546,12 +546,18 @@ __host__ __device__ inline uint32_t tour_rounds(uint32_t n, uint32_t k) {
     return r;
 }
 
-__device__ __forceinline__ uint64_t batch_make_key(float d, uint32_t pos, uint32_t id, uint64_t two_k) {
+// The reference's skip (reader.rs:611,619-621) is a moving threshold, not a property of a position: the first 2k items are
+// buffered unchecked; after them an item >= (f32::MAX, u32::MAX) is skipped only while the threshold still has that first
+// value, i.e. until the first item below it arrives at a position >= 2k (`skip_end`).  That item compacts the buffer and
+// the threshold becomes the k-th smallest key so far: from then on a skipped item could not have been among the k smallest
+// anyway, so every later item counts, +inf and NaN included.  skip_end = 0xFFFFFFFF when no such item exists.
+static constexpr uint32_t kMaxWord = 0xFF7FFFFFu;  // orderable_key(f32::MAX)
+__device__ __forceinline__ bool batch_key_skippable(uint32_t ok, uint32_t id) {
+    return ok > kMaxWord || (ok == kMaxWord && id == 0xFFFFFFFFu);
+}
+__device__ __forceinline__ uint64_t batch_make_key(float d, uint32_t pos, uint32_t id, uint64_t two_k, uint32_t skip_end) {
     const uint32_t ok = orderable_key(d);
-    if (pos >= two_k) {  // reader.rs:611,619-621: items >= (f32::MAX, u32::MAX) are skipped once 2k are buffered
-        const uint32_t max_key = 0xFF7FFFFFu;
-        if (ok > max_key || (ok == max_key && id == 0xFFFFFFFFu)) return kSentinel;
-    }
+    if (pos >= two_k && pos < skip_end && batch_key_skippable(ok, id)) return kSentinel;
     return ((uint64_t)ok << 32) | (uint64_t)pos;
 }
 
@@ -582,13 +588,15 @@ __device__ __forceinline__ void batch_bitonic_sort(uint64_t *s) {
 // Exactly the k smallest (OrderedFloat(distance), position) keys in ascending order — the tournament's result; a query whose
 // selected set does not fit the small sort (> 1024 keys: many equal distances, or a huge k) raises its flag and is left to
 // the tournament, whose blocks return at once for all other queries.  The flag of query q lives in the last word of its
-// slice of keys_b (the tournament uses at most the lower half of a slice).
+// slice of keys_b (the tournament uses at most the lower half of a slice): 0 = served here, else kFlagRaised | skip_end
+// (this kernel sees the whole list, so it finds skip_end for the tournament's first round too).
 constexpr uint32_t kSelBins = 2048, kSelCap = 1024;
+constexpr uint64_t kFlagRaised = 1ull << 32;  // flag word of a query left to the tournament: kFlagRaised | skip_end
 __device__ __forceinline__ uint64_t select_key(const float *__restrict__ dist, const uint32_t *__restrict__ ids, uint64_t off,
-                                               uint32_t g, uint64_t two_k) {
+                                               uint32_t g, uint64_t two_k, uint32_t skip_end) {
     const uint32_t ok = orderable_key(dist[off + g]);
-    if (g >= two_k && ok >= 0xFF7FFFFFu) {  // reader.rs:611,619-621 (see batch_make_key): needs the id only here
-        if (ok > 0xFF7FFFFFu || ids[off + g] == 0xFFFFFFFFu) return kSentinel;
+    if (g >= two_k && g < skip_end && ok >= kMaxWord) {  // see batch_make_key: needs the id only here
+        if (batch_key_skippable(ok, ids[off + g])) return kSentinel;
     }
     return ((uint64_t)ok << 32) | (uint64_t)g;
 }
@@ -597,7 +605,7 @@ __global__ __launch_bounds__(kBlock) void k_batch_topk_select(const Seg *__restr
                                                               uint64_t *keys_b, uint64_t kstride) {
     __shared__ uint32_t s_hist[kSelBins];
     __shared__ uint64_t s_cand[kSelCap];
-    __shared__ uint32_t s_min, s_max, s_wave[kBlock / 64], s_bin, s_count, s_n;
+    __shared__ uint32_t s_min, s_max, s_wave[kBlock / 64], s_bin, s_count, s_n, s_skip_end, s_skippable;
     const uint32_t q = blockIdx.x;
     const Seg sg = segs[q];
     uint64_t *flag = keys_b + (uint64_t)q * kstride + (kstride - 1);
@@ -614,23 +622,54 @@ __global__ __launch_bounds__(kBlock) void k_batch_topk_select(const Seg *__restr
         s_min = 0xFFFFFFFFu;
         s_max = 0u;
         s_n = 0u;
+        s_skip_end = 0xFFFFFFFFu;
+        s_skippable = 0u;
     }
     __syncthreads();
-    uint32_t lo = 0xFFFFFFFFu, hi = 0u;
+    uint32_t lo = 0xFFFFFFFFu, hi = 0u, first_below = 0xFFFFFFFFu;
     for (uint32_t g = threadIdx.x; g < sg.n; g += kBlock) {
-        const uint32_t w = (uint32_t)(select_key(dist, ids, sg.off, g, two_k) >> 32);
+        const uint32_t w = orderable_key(dist[sg.off + g]);
         lo = min(lo, w);
         hi = max(hi, w);
+        if (g >= two_k) {
+            if (w >= kMaxWord && batch_key_skippable(w, ids[sg.off + g])) s_skippable = 1u;  // rare: same value from every writer
+            else first_below = min(first_below, g);
+        }
     }
     for (int off = 32; off > 0; off >>= 1) {
         lo = min(lo, (uint32_t)__shfl_xor((int)lo, off));
         hi = max(hi, (uint32_t)__shfl_xor((int)hi, off));
+        first_below = min(first_below, (uint32_t)__shfl_xor((int)first_below, off));
     }
     if ((threadIdx.x & 63u) == 0) {
         atomicMin(&s_min, lo);
         atomicMax(&s_max, hi);
+        atomicMin(&s_skip_end, first_below);
     }
     __syncthreads();
+    const uint32_t skip_end = s_skip_end;
+    if (s_skippable != 0u) {  // block-uniform, rare (non-finite distances past 2k): the words once more, skipped keys as sentinels
+        if (threadIdx.x == 0) {
+            s_min = 0xFFFFFFFFu;
+            s_max = 0u;
+        }
+        __syncthreads();
+        lo = 0xFFFFFFFFu, hi = 0u;
+        for (uint32_t g = threadIdx.x; g < sg.n; g += kBlock) {
+            const uint32_t w = (uint32_t)(select_key(dist, ids, sg.off, g, two_k, skip_end) >> 32);
+            lo = min(lo, w);
+            hi = max(hi, w);
+        }
+        for (int off = 32; off > 0; off >>= 1) {
+            lo = min(lo, (uint32_t)__shfl_xor((int)lo, off));
+            hi = max(hi, (uint32_t)__shfl_xor((int)hi, off));
+        }
+        if ((threadIdx.x & 63u) == 0) {
+            atomicMin(&s_min, lo);
+            atomicMax(&s_max, hi);
+        }
+        __syncthreads();
+    }
     const uint32_t w_min = s_min;
     const uint64_t span = (uint64_t)(s_max - w_min) + 1ull;
     // bin(w) = floor((w - w_min) * scale / 2^32), scale = floor(2048 * 2^32 / span): monotone, < 2048; one 64-bit division
@@ -641,7 +680,7 @@ __global__ __launch_bounds__(kBlock) void k_batch_topk_select(const Seg *__restr
         return direct ? w - w_min : (uint32_t)(((uint64_t)(w - w_min) * scale) >> 32);
     };
     for (uint32_t g = threadIdx.x; g < sg.n; g += kBlock) {
-        const uint32_t w = (uint32_t)(select_key(dist, ids, sg.off, g, two_k) >> 32);
+        const uint32_t w = (uint32_t)(select_key(dist, ids, sg.off, g, two_k, skip_end) >> 32);
         atomicAdd(&s_hist[bin_of(w)], 1u);
     }
     __syncthreads();
@@ -673,12 +712,12 @@ __global__ __launch_bounds__(kBlock) void k_batch_topk_select(const Seg *__restr
     __syncthreads();
     const uint32_t n_sel = s_count, bin_k = s_bin;
     if (n_sel > kSelCap) {  // block-uniform: leave this query to the tournament
-        if (threadIdx.x == 0) *flag = 1;
+        if (threadIdx.x == 0) *flag = kFlagRaised | skip_end;
         return;
     }
     if (threadIdx.x == 0) *flag = 0;
     for (uint32_t g = threadIdx.x; g < sg.n; g += kBlock) {
-        const uint64_t key = select_key(dist, ids, sg.off, g, two_k);
+        const uint64_t key = select_key(dist, ids, sg.off, g, two_k, skip_end);
         const uint32_t w = (uint32_t)(key >> 32);
         if (bin_of(w) <= bin_k) s_cand[atomicAdd(&s_n, 1u)] = key;
     }
@@ -713,7 +752,9 @@ __global__ __launch_bounds__(kBlock) void k_batch_topk_round(const Seg *__restri
     const uint32_t q = blockIdx.y, c = blockIdx.x;
     const Seg sg = segs[q];
     if (sg.k == 0) return;
-    if (keys_b[(uint64_t)q * kstride + (kstride - 1)] == 0) return;  // k_batch_topk_select served this query
+    const uint64_t flag = keys_b[(uint64_t)q * kstride + (kstride - 1)];
+    if (flag == 0) return;  // k_batch_topk_select served this query
+    const uint32_t skip_end = (uint32_t)flag;
     const Tournament before = tour_after(sg.n, sg.k, round);
     if (before.blocks == 1) return;  // this query finished in an earlier round
     const uint32_t blocks = (before.n_in + kChunk - 1) / kChunk;
@@ -725,7 +766,7 @@ __global__ __launch_bounds__(kBlock) void k_batch_topk_round(const Seg *__restri
     for (uint32_t t = threadIdx.x; t < kChunk; t += blockDim.x) {
         const uint32_t g = c * kChunk + t;
         uint64_t key = kSentinel;
-        if (g < before.n_in) key = round == 0 ? batch_make_key(dist[sg.off + g], g, ids[sg.off + g], two_k) : src[g];
+        if (g < before.n_in) key = round == 0 ? batch_make_key(dist[sg.off + g], g, ids[sg.off + g], two_k, skip_end) : src[g];
         s[t] = key;
     }
     batch_bitonic_sort(s);
