@@ -67,6 +67,14 @@ class AhIndexDeltaView(C.Structure):
                 ("desc_len", C.c_uint64), ("n_trees", C.c_uint32), ("roots", C.POINTER(C.c_uint32))]
 
 
+class AhIndexInfo(C.Structure):
+    _fields_ = [("n_nodes", C.c_uint64), ("desc_len", C.c_uint64), ("n_trees", C.c_uint32), ("n_normals", C.c_uint32),
+                ("normal_row_bytes", C.c_uint64), ("normal_header_floats", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+NEW_ROOT = 0xFFFFFFFF  # AH_NEW_ROOT: a tree of ah_index_graft that becomes a new root
+
+
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64)
 
 
@@ -219,6 +227,11 @@ SIGNATURES = {
     "ah_index_delete_items": (C.c_int, [_VP, _U32P, C.c_size_t, C.c_uint32, C.POINTER(C.c_void_p)]),
     "ah_index_delta_get": (C.c_int, [_VP, C.POINTER(AhIndexDeltaView)]),
     "ah_index_delta_destroy": (C.c_int, [_VP]),
+    # inserts and grafts on a resident index; the index as it is on the device
+    "ah_index_insert_items": (C.c_int, [_VP, _U32P, C.c_size_t, _U64P, C.POINTER(C.c_void_p)]),
+    "ah_index_graft": (C.c_int, [_VP, C.POINTER(AhForestView), _U32P, _U32P, _U32P]),
+    "ah_index_export_info": (C.c_int, [_VP, C.POINTER(AhIndexInfo)]),
+    "ah_index_export": (C.c_int, [_VP, _VP, _U32P, _U32P, _VP, _F32P]),
     "ah_index_suspend": (C.c_int, [_VP]),
     "ah_index_resume": (C.c_int, [_VP, _VP]),
     "ah_bench_scan": (C.c_int, [_VP, C.c_uint32, C.c_uint64, C.c_uint32, _F32P, C.POINTER(C.c_double)]),

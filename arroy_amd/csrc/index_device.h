@@ -1,5 +1,5 @@
-// index_device.h — what search.hip (the searches and the routing of an ah_index) and index_update.hip (its deletes, suspend /
-// resume) share: the device node record, the index handle and the id-list -> bitmap kernel.
+// index_device.h — what search.hip (the searches and the routing of an ah_index) and index_update.hip (its deletes, inserts,
+// grafts, export, suspend / resume) share: the device node record, the index handle and the id-list -> bitmap kernel.
 #pragma once
 
 #include "common.h"
@@ -35,6 +35,8 @@ struct ah_index {
     uint32_t *d_rank = nullptr;
     void *d_nrows = nullptr;
     float *d_nhdrs = nullptr;
+    // rows d_nrows / d_nhdrs have room for (>= n_normals): ah_index_graft appends into the spare ones and grows geometrically
+    uint32_t normals_cap = 0;
     uint32_t n_trees = 0, n_nodes = 0, n_normals = 0, max_desc = 0;
     uint32_t n_leaves = 0;  // Descendants nodes (desc_len / n_leaves: the mean leaf, what the small-submission gate estimates with)
     uint64_t desc_len = 0;
@@ -56,4 +58,14 @@ namespace ah {
 // search.hip: the copies of the rows the certified top-k screen of the searches reads, made when an index starts to serve a
 // dataset (ah_index_create*, ah_index_resume).  No memory for them = no screen, not an error.
 void index_prepare_screens(ah_dataset *ds);
+// search.hip: what ah_index_create_from_view and ah_index_graft ask of a view before they touch anything (pointers, record
+// geometry, node ranges, every node reachable at most once)
+int validate_forest_view(const ah_dataset *ds, const ah_forest_view &v);
+// search.hip: k_route_items for n ids (on the device) down every tree of the index, queued on `s`; d_leaf[t * n + i], bit 0 of
+// *d_err (zeroed by the caller) when an id is no row of the dataset
+int launch_route_items(ah_index *ix, const uint32_t *d_ids, uint64_t n, const uint64_t *d_seeds, uint32_t *d_leaf, uint32_t *d_err,
+                       hipStream_t s);
+// search.hip: k_unpack_normals, queued on `s`: n records (recs + offsets[r]) -> rows / headers of the normals
+int launch_unpack_normals(const ah_dataset *ds, const uint8_t *d_recs, const uint64_t *d_offsets, uint32_t n, uint64_t vec_off,
+                          uint64_t hdr_off, void *d_rows, float *d_headers, hipStream_t s);
 }  // namespace ah

@@ -1,4 +1,5 @@
-// index_update.hip — ah_index_delete_items / ah_index_suspend / ah_index_resume (include/arroy_hip.h): the part of an
+// index_update.hip — ah_index_delete_items / ah_index_insert_items / ah_index_graft / ah_index_export / ah_index_suspend /
+// ah_index_resume (include/arroy_hip.h).  The inserts and grafts are described above their kernels; the delete is the part of an
 // incremental `Writer::build` that takes the updated ids out of every tree (`delete_items_from_trees`, src/writer.rs:978-1114)
 // done where the forest lives, so that the index of the last build serves the routing of the next one instead of being
 // uploaded again.
@@ -24,6 +25,7 @@
 #include <vector>
 
 #include "common.h"
+#include "device_math.h"
 #include "index_device.h"
 #include "scan_device.h"
 
@@ -333,11 +335,425 @@ __global__ __launch_bounds__(kIxBlock) void k_delete_gather(DeleteArgs a, const 
     }
 }
 
+// ---- inserts ------------------------------------------------------------------------------------------------------------------
+// ah_index_insert_items: `insert_items_in_descendants_from_frozen_reader` (src/writer.rs:1398-1459) for every tree at once, the
+// lists included ("Inserts and grafts on a resident index"); every pass reads the index and writes new memory only:
+//   1. check     every id is a row of the dataset (the first that is not is named);
+//   2. route     k_route_items (search.hip), AH_LAUNCH_MAX_ITEMS pairs a launch: the landing node of every (tree, id) pair;
+//   3. count     pairs per landing node (atomics), scanned into the segments of `landed`; the touched nodes, ascending;
+//   4. scatter   every id into its node's segment; a block sorts each segment (LDS up to 4096 ids);
+//   5. fresh     a wave per touched node drops from its segment the ids its list already holds (binary search, ballot +
+//                popcount, 64 ids a step); the new lengths, scanned into the offsets of the new blob and of the delta;
+//   6. write     a wave per Descendants node: an untouched list is copied, a touched one merged with its segment, every id
+//                going to (its position in its own list) + (ids below it in the other);
+//   7. apply     the new node array and the delta; read back; the index's pointers are swapped last.
+enum ICtl { ICTL_ERR = 0, ICTL_FIRST_BAD, ICTL_TOUCHED, ICTL_DESC_LEN, ICTL_DELTA_DESC, ICTL_LEAVES, ICTL_MAX_DESC, ICTL_WORDS };
+
+struct InsertArgs {
+    const DNode *nodes;
+    uint32_t n_nodes;
+    const uint32_t *desc;
+    uint64_t old_desc_len;
+    // per node, zeroed before the first kernel
+    uint32_t *cnt;      // pairs that landed in the node
+    uint32_t *seg;      // (cnt, scanned) where the node's pairs start in `landed`
+    uint32_t *cursor;   // pairs already placed there
+    uint32_t *chg;      // 1 for a touched node -> (scan) its position in the delta
+    uint32_t *fresh;    // ids of the node's segment that its list does not hold yet
+    uint32_t *nlen;     // ids the node holds afterwards -> (scan) where they start in the new blob
+    uint32_t *dlen;     // the same of the touched nodes only -> (scan) where they start in the delta's ids
+    uint32_t *touched;  // the touched nodes, ascending
+    uint32_t *landed;   // n_pairs ids, by landing node
+    uint32_t *ctl;
+    uint64_t n_pairs;
+    // what the scans gave (set before the passes that store through them)
+    uint32_t n_touched, new_desc_len, delta_desc_len;
+};
+
+// positions of v[0, m) (ascending) that hold a value below x
+__device__ __forceinline__ uint32_t lower_bound_u32(const uint32_t *v, uint32_t m, uint32_t x) {
+    uint32_t lo = 0, hi = m;
+    while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (v[mid] < x) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(kIxBlock) void k_insert_check(DataView dv, const uint32_t *__restrict__ ids, uint64_t n, uint32_t *ctl) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
+        if (row_of_id(dv, ids[i]) == ~0ull) atomicMin(&ctl[ICTL_FIRST_BAD], (uint32_t)i);
+}
+
+// count: the m pairs of one routing launch
+__global__ __launch_bounds__(kIxBlock) void k_insert_count(InsertArgs a, const uint32_t *__restrict__ leaf, uint64_t m) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; p < m; p += stride) {
+        const uint32_t node = leaf[p];
+        if (node >= a.n_nodes || (a.nodes[node].kind & 0xFFu) != AH_NODE_DESCENDANTS) atomicOr(&a.ctl[ICTL_ERR], 1u);
+        else atomicAdd(&a.cnt[node], 1u);
+    }
+}
+
+// per node: touched or not, and the length an untouched list keeps
+__global__ __launch_bounds__(kIxBlock) void k_insert_flags(InsertArgs a) {
+    const uint32_t stride = gridDim.x * blockDim.x;
+    for (uint64_t node = blockIdx.x * blockDim.x + threadIdx.x; node < a.n_nodes; node += stride) {
+        const DNode nd = a.nodes[node];
+        a.chg[node] = a.cnt[node] ? 1u : 0u;
+        a.nlen[node] = (nd.kind & 0xFFu) == AH_NODE_DESCENDANTS ? nd.b : 0u;
+    }
+}
+
+// the touched nodes in node order (chg: scanned)
+__global__ __launch_bounds__(kIxBlock) void k_insert_touched(InsertArgs a) {
+    const uint32_t stride = gridDim.x * blockDim.x;
+    for (uint64_t node = blockIdx.x * blockDim.x + threadIdx.x; node < a.n_nodes; node += stride)
+        if (a.cnt[node]) a.touched[a.chg[node]] = (uint32_t)node;  // (chg[node] < touched nodes <= n_nodes)
+}
+
+// scatter: the m pairs of one routing launch (ids: the cn ids of that launch) into the segments (seg: scanned)
+__global__ __launch_bounds__(kIxBlock) void k_insert_scatter(InsertArgs a, const uint32_t *__restrict__ ids, uint64_t cn,
+                                                             const uint32_t *__restrict__ leaf, uint64_t m) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; p < m; p += stride) {
+        const uint32_t node = leaf[p];
+        if (node >= a.n_nodes) continue;  // (the count pass has flagged it)
+        const uint64_t at = (uint64_t)a.seg[node] + atomicAdd(&a.cursor[node], 1u);
+        if (at < a.n_pairs) a.landed[at] = ids[p % cn];
+        else atomicOr(&a.ctl[ICTL_ERR], 2u);
+    }
+}
+
+// the segments ascending, a block each
+__global__ __launch_bounds__(kIxBlock) void k_insert_sort(InsertArgs a) {
+    __shared__ uint32_t lds[kSortLds];
+    for (uint32_t i = blockIdx.x; i < a.n_touched; i += gridDim.x) {
+        const uint32_t node = a.touched[i];
+        if (node >= a.n_nodes || (uint64_t)a.seg[node] + a.cnt[node] > a.n_pairs) continue;  // (block-uniform; flagged by the next pass)
+        block_sort_segment(a.landed + a.seg[node], a.cnt[node], lds);
+    }
+}
+
+// fresh: touched[lo, hi), a wave each: `descendants | to_insert` adds only what the list does not hold; the segment is
+// compacted in place (a step stores at or below the positions it has read)
+__global__ __launch_bounds__(kIxBlock) void k_insert_fresh(InsertArgs a, uint32_t lo, uint32_t hi) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t n_waves = (gridDim.x * blockDim.x) >> 6;
+    for (uint32_t i = lo + ((blockIdx.x * blockDim.x + threadIdx.x) >> 6); i < hi; i += n_waves) {
+        const uint32_t node = a.touched[i];
+        if (node >= a.n_nodes) {  // (wave-uniform, as is every branch below)
+            if (lane == 0) atomicOr(&a.ctl[ICTL_ERR], 4u);
+            continue;
+        }
+        const DNode nd = a.nodes[node];
+        const uint32_t m = a.cnt[node];
+        if ((uint64_t)a.seg[node] + m > a.n_pairs || (uint64_t)nd.a + nd.b > a.old_desc_len) {
+            if (lane == 0) atomicOr(&a.ctl[ICTL_ERR], 4u);
+            continue;
+        }
+        uint32_t *seg = a.landed + a.seg[node];
+        const uint32_t *list = a.desc + nd.a;
+        uint32_t kept = 0;
+        for (uint32_t j0 = 0; j0 < m; j0 += 64) {
+            bool keep = false;
+            uint32_t id = 0;
+            if (j0 + lane < m) {
+                id = seg[j0 + lane];
+                const uint32_t at = lower_bound_u32(list, nd.b, id);
+                keep = !(at < nd.b && list[at] == id);
+            }
+            const unsigned long long mask = __ballot(keep);
+            if (keep) seg[kept + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull))] = id;
+            kept += (uint32_t)__popcll(mask);
+        }
+        if (lane == 0) {
+            a.fresh[node] = kept;
+            a.nlen[node] = nd.b + kept;
+            a.dlen[node] = nd.b + kept;
+        }
+    }
+}
+
+// write: the Descendants nodes among [lo, hi), a wave each (nlen: scanned)
+__global__ __launch_bounds__(kIxBlock) void k_insert_write(InsertArgs a, uint32_t lo, uint32_t hi, uint32_t *__restrict__ out) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t n_waves = (gridDim.x * blockDim.x) >> 6;
+    for (uint32_t node = lo + ((blockIdx.x * blockDim.x + threadIdx.x) >> 6); node < hi; node += n_waves) {
+        const DNode nd = a.nodes[node];
+        if ((nd.kind & 0xFFu) != AH_NODE_DESCENDANTS) continue;  // (wave-uniform, as is every branch below)
+        const uint32_t f = a.cnt[node] ? a.fresh[node] : 0u;
+        const uint64_t base = a.nlen[node];
+        if (base + nd.b + f > a.new_desc_len || (uint64_t)nd.a + nd.b > a.old_desc_len || (uint64_t)a.seg[node] + f > a.n_pairs) {
+            if (lane == 0) atomicOr(&a.ctl[ICTL_ERR], 8u);
+            continue;
+        }
+        const uint32_t *list = a.desc + nd.a;
+        const uint32_t *seg = a.landed + a.seg[node];
+        for (uint32_t j = lane; j < nd.b; j += 64) {
+            const uint32_t id = list[j];
+            out[base + j + (f ? lower_bound_u32(seg, f, id) : 0u)] = id;
+        }
+        for (uint32_t j = lane; j < f; j += 64) {
+            const uint32_t id = seg[j];
+            out[base + j + lower_bound_u32(list, nd.b, id)] = id;
+        }
+    }
+}
+
+// apply: every node as it is afterwards, the touched ones into the delta as well (chg / dlen / nlen: scanned)
+__global__ __launch_bounds__(kIxBlock) void k_insert_apply(InsertArgs a, DNode *__restrict__ out, DeltaEntry *__restrict__ entries) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t stride = gridDim.x * blockDim.x;
+    const uint32_t rounds = (a.n_nodes + stride - 1) / stride;
+    uint32_t leaves = 0, largest = 0;
+    for (uint32_t r = 0; r < rounds; r++) {
+        const uint64_t node = (uint64_t)r * stride + blockIdx.x * blockDim.x + threadIdx.x;
+        if (node >= a.n_nodes) break;
+        DNode nd = a.nodes[node];
+        if ((nd.kind & 0xFFu) == AH_NODE_DESCENDANTS) {
+            nd.a = a.nlen[node];
+            if (a.cnt[node]) {
+                nd.b += a.fresh[node];
+                if (a.chg[node] < a.n_touched) entries[a.chg[node]] = DeltaEntry{(uint32_t)node, AH_NODE_DESCENDANTS, a.dlen[node], nd.b};
+                else atomicOr(&a.ctl[ICTL_ERR], 16u);
+            }
+            leaves++;
+            largest = max(largest, nd.b);
+        }
+        out[node] = nd;
+    }
+    for (uint32_t d = 32; d > 0; d >>= 1) {
+        leaves += __shfl_xor(leaves, d, 64);
+        largest = max(largest, (uint32_t)__shfl_xor(largest, d, 64));
+    }
+    if (lane == 0 && leaves) {
+        atomicAdd(&a.ctl[ICTL_LEAVES], leaves);
+        atomicMax(&a.ctl[ICTL_MAX_DESC], largest);
+    }
+}
+
+// the new lists of the touched nodes, node after node, for the host; a wave per touched node
+__global__ __launch_bounds__(kIxBlock) void k_insert_gather(InsertArgs a, const DeltaEntry *__restrict__ entries,
+                                                            const uint32_t *__restrict__ blob, uint32_t *__restrict__ out) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t n_waves = (gridDim.x * blockDim.x) >> 6;
+    for (uint32_t i = (blockIdx.x * blockDim.x + threadIdx.x) >> 6; i < a.n_touched; i += n_waves) {
+        const DeltaEntry e = entries[i];
+        if (e.node >= a.n_nodes || (uint64_t)e.a + e.b > a.delta_desc_len || (uint64_t)a.nlen[e.node] + e.b > a.new_desc_len) {
+            if (lane == 0) atomicOr(&a.ctl[ICTL_ERR], 32u);
+            continue;
+        }
+        const uint32_t *src = blob + a.nlen[e.node];
+        for (uint32_t j = lane; j < e.b; j += 64) out[e.a + j] = src[j];
+    }
+}
+
+// ---- grafts -------------------------------------------------------------------------------------------------------------------
+// ah_index_graft: the trees of a view become part of the index, each root in place of a Descendants node or as a new root, and
+// every node gets the index it has in a fresh view of the host's store:
+//   1. named     one flag per final position a new node names; its scan gives every unnamed position p the old node of rank
+//                p - named_before(p), hence every old node its new index;
+//   2. lengths   per final position the ids it holds, scanned into the offsets of the new blob;
+//   3. nodes     the new node array, children remapped; the new roots;
+//   4. lists     a wave per Descendants node copies its ids, from the old blob or from the view's;
+//   5. normals   the view's records are unpacked (k_unpack_normals, search.hip) into the rows behind the index's own.
+enum GCtl { GCTL_ERR = 0, GCTL_NAMED, GCTL_DESC_LEN, GCTL_LEAVES, GCTL_MAX_DESC, GCTL_WORDS };
+
+struct GraftArgs {
+    const DNode *nodes;    // the index as it is
+    uint32_t n_old, n_used;
+    const uint32_t *rank;  // nullptr: no holes
+    const uint32_t *desc;
+    uint64_t old_desc_len;
+    const DNode *vnodes;   // the view's nodes: children and offsets in the view's own numbering, c = the normal's ordinal
+    uint32_t n_view;
+    const uint32_t *vfin;  // the final index a new node names, kNone for a replacing root
+    const uint32_t *vtgt;  // the node a replacing root replaces, else kNone
+    const uint32_t *vdesc;
+    uint64_t vdesc_len;
+    uint32_t n_new;        // nodes afterwards
+    uint32_t first_row;    // the normal row of the view's first normal
+    uint32_t *named;       // n_new + 1: flags -> (scan) named positions below
+    uint32_t *pos_of_rank; // n_used
+    uint32_t *new_of_old;  // n_old; kNone for a free slot
+    uint32_t *replaced;    // n_old: 1 for a target
+    uint32_t *fin;         // n_view: the final index of every view node
+    uint32_t *len;         // n_new + 1: ids per final position -> (scan) offsets
+    uint32_t *ctl;
+    uint32_t new_desc_len;
+};
+
+__global__ __launch_bounds__(kIxBlock) void k_graft_named(GraftArgs a) {
+    const uint32_t stride = gridDim.x * blockDim.x;
+    for (uint64_t k = blockIdx.x * blockDim.x + threadIdx.x; k < a.n_view; k += stride) {
+        const uint32_t p = a.vfin[k], t = a.vtgt[k];
+        if (t != kNone) {
+            if (t < a.n_old) a.replaced[t] = 1u;
+            else atomicOr(&a.ctl[GCTL_ERR], 1u);
+        } else if (p < a.n_new) {
+            a.named[p] = 1u;
+        } else {
+            atomicOr(&a.ctl[GCTL_ERR], 1u);
+        }
+    }
+}
+
+// (named: scanned, the total behind it) the p-th unnamed position belongs to the old node of rank p - named_before(p)
+__global__ __launch_bounds__(kIxBlock) void k_graft_positions(GraftArgs a) {
+    const uint32_t stride = gridDim.x * blockDim.x;
+    for (uint64_t p = blockIdx.x * blockDim.x + threadIdx.x; p < a.n_new; p += stride) {
+        if (a.named[p + 1] != a.named[p]) continue;
+        const uint64_t r = p - a.named[p];
+        if (r < a.n_used) a.pos_of_rank[r] = (uint32_t)p;
+        else atomicOr(&a.ctl[GCTL_ERR], 2u);
+    }
+}
+
+__global__ __launch_bounds__(kIxBlock) void k_graft_old_map(GraftArgs a) {
+    const uint32_t stride = gridDim.x * blockDim.x;
+    for (uint64_t o = blockIdx.x * blockDim.x + threadIdx.x; o < a.n_old; o += stride) {
+        uint32_t p = kNone;
+        if (a.nodes[o].kind != 0) {
+            const uint32_t r = a.rank ? a.rank[o] : (uint32_t)o;
+            if (r < a.n_used) p = a.pos_of_rank[r];
+            else atomicOr(&a.ctl[GCTL_ERR], 4u);
+        }
+        a.new_of_old[o] = p;
+    }
+}
+
+__global__ __launch_bounds__(kIxBlock) void k_graft_fin(GraftArgs a) {
+    const uint32_t stride = gridDim.x * blockDim.x;
+    for (uint64_t k = blockIdx.x * blockDim.x + threadIdx.x; k < a.n_view; k += stride) {
+        const uint32_t t = a.vtgt[k];
+        a.fin[k] = t == kNone ? a.vfin[k] : (t < a.n_old ? a.new_of_old[t] : kNone);
+    }
+}
+
+// The final position and the node of work item w: the old nodes first, then the view's.  false: nothing moves (a free slot, a
+// replaced node)
+__device__ __forceinline__ bool graft_item(const GraftArgs &a, uint64_t w, uint32_t *p, DNode *nd, bool *from_view) {
+    *from_view = w >= a.n_old;
+    if (!*from_view) {
+        *nd = a.nodes[w];
+        if (nd->kind == 0 || a.replaced[w]) return false;
+        *p = a.new_of_old[w];
+    } else {
+        *nd = a.vnodes[w - a.n_old];
+        *p = a.fin[w - a.n_old];
+    }
+    if (*p >= a.n_new) {
+        atomicOr(&a.ctl[GCTL_ERR], 8u);
+        return false;
+    }
+    return true;
+}
+
+__global__ __launch_bounds__(kIxBlock) void k_graft_len(GraftArgs a) {
+    const uint32_t stride = gridDim.x * blockDim.x;
+    const uint64_t work = (uint64_t)a.n_old + a.n_view;
+    for (uint64_t w = blockIdx.x * blockDim.x + threadIdx.x; w < work; w += stride) {
+        uint32_t p;
+        DNode nd;
+        bool from_view;
+        if (!graft_item(a, w, &p, &nd, &from_view)) continue;
+        a.len[p] = (nd.kind & 0xFFu) == AH_NODE_DESCENDANTS ? nd.b : 0u;
+    }
+}
+
+// nodes (len: scanned); every position of the new array is written by exactly one work item
+__global__ __launch_bounds__(kIxBlock) void k_graft_nodes(GraftArgs a, DNode *__restrict__ out) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t stride = gridDim.x * blockDim.x;
+    const uint64_t work = (uint64_t)a.n_old + a.n_view;
+    const uint32_t rounds = (uint32_t)((work + stride - 1) / stride);
+    uint32_t leaves = 0, largest = 0;
+    for (uint32_t r = 0; r < rounds; r++) {
+        const uint64_t w = (uint64_t)r * stride + blockIdx.x * blockDim.x + threadIdx.x;
+        if (w >= work) break;
+        uint32_t p;
+        DNode nd;
+        bool from_view;
+        if (!graft_item(a, w, &p, &nd, &from_view)) continue;
+        if ((nd.kind & 0xFFu) == AH_NODE_DESCENDANTS) {
+            nd = DNode{AH_NODE_DESCENDANTS, a.len[p], nd.b, 0};
+            leaves++;
+            largest = max(largest, nd.b);
+        } else {
+            const uint32_t limit = from_view ? a.n_view : a.n_old;
+            if (nd.a >= limit || nd.b >= limit) {
+                atomicOr(&a.ctl[GCTL_ERR], 16u);
+                continue;
+            }
+            nd.a = from_view ? a.fin[nd.a] : a.new_of_old[nd.a];
+            nd.b = from_view ? a.fin[nd.b] : a.new_of_old[nd.b];
+            if (from_view) nd.c = (nd.kind & 0x100u) ? a.first_row + nd.c : 0u;
+            if (nd.a >= a.n_new || nd.b >= a.n_new) atomicOr(&a.ctl[GCTL_ERR], 16u);
+        }
+        out[p] = nd;
+    }
+    for (uint32_t d = 32; d > 0; d >>= 1) {
+        leaves += __shfl_xor(leaves, d, 64);
+        largest = max(largest, (uint32_t)__shfl_xor(largest, d, 64));
+    }
+    if (lane == 0 && leaves) {
+        atomicAdd(&a.ctl[GCTL_LEAVES], leaves);
+        atomicMax(&a.ctl[GCTL_MAX_DESC], largest);
+    }
+}
+
+// lists: work items [lo, hi), a wave each
+__global__ __launch_bounds__(kIxBlock) void k_graft_lists(GraftArgs a, uint64_t lo, uint64_t hi, uint32_t *__restrict__ out) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t n_waves = (gridDim.x * blockDim.x) >> 6;
+    for (uint64_t w = lo + ((blockIdx.x * blockDim.x + threadIdx.x) >> 6); w < hi; w += n_waves) {
+        uint32_t p;
+        DNode nd;
+        bool from_view;
+        if (!graft_item(a, w, &p, &nd, &from_view)) continue;  // (wave-uniform, as is every branch below)
+        if ((nd.kind & 0xFFu) != AH_NODE_DESCENDANTS) continue;
+        const uint64_t base = a.len[p];
+        if (base + nd.b > a.new_desc_len || (uint64_t)nd.a + nd.b > (from_view ? a.vdesc_len : a.old_desc_len)) {
+            if (lane == 0) atomicOr(&a.ctl[GCTL_ERR], 32u);
+            continue;
+        }
+        const uint32_t *src = (from_view ? a.vdesc : a.desc) + nd.a;
+        for (uint32_t j = lane; j < nd.b; j += 64) out[base + j] = src[j];
+    }
+}
+
+// the roots: the index's own in their order, then the view's new roots in view order
+__global__ __launch_bounds__(kIxBlock) void k_graft_roots(GraftArgs a, const uint32_t *__restrict__ roots, uint32_t n_trees,
+                                                          const uint32_t *__restrict__ new_roots, uint32_t n_added,
+                                                          uint32_t *__restrict__ out) {
+    const uint32_t stride = gridDim.x * blockDim.x;
+    for (uint64_t t = blockIdx.x * blockDim.x + threadIdx.x; t < (uint64_t)n_trees + n_added; t += stride) {
+        uint32_t p = kNone;
+        if (t < n_trees) {
+            if (roots[t] < a.n_old) p = a.new_of_old[roots[t]];
+        } else if (new_roots[t - n_trees] < a.n_view) {
+            p = a.fin[new_roots[t - n_trees]];
+        }
+        if (p >= a.n_new) atomicOr(&a.ctl[GCTL_ERR], 64u);
+        out[t] = p;
+    }
+}
+
+// what the host must know of the targets before anything is touched
+__global__ __launch_bounds__(kIxBlock) void k_graft_peek(const DNode *__restrict__ nodes, const uint32_t *__restrict__ which, uint32_t n,
+                                                         uint32_t *__restrict__ kinds) {
+    const uint32_t stride = gridDim.x * blockDim.x;
+    for (uint64_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) kinds[i] = nodes[which[i]].kind;
+}
+
 int alloc(DevMem *m, size_t bytes) {
     const hipError_t e = dev_malloc(&m->p, std::max<size_t>(bytes, 1));
     if (e != hipSuccess) {
         (void)hipGetLastError();
-        set_error("device allocation of %zu bytes for the index delete failed: %s", bytes, hipGetErrorString(e));
+        set_error("device allocation of %zu bytes for the index update failed: %s", bytes, hipGetErrorString(e));
         set_error_status(e == hipErrorOutOfMemory ? AH_ERR_OUT_OF_MEMORY : AH_ERR_DEVICE);
         return e == hipErrorOutOfMemory ? AH_ERR_OUT_OF_MEMORY : AH_ERR_DEVICE;
     }
@@ -528,6 +944,401 @@ int delete_impl(ah_index *ix, const uint32_t *ids, size_t n, uint32_t split_afte
     return AH_OK;
 }
 
+// what the three updates ask of an index before they look at it
+int index_updatable(ah_index *ix) {
+    AH_REQUIRE(ix && ix->ds, AH_ERR_INVALID_ARGUMENT, "index is NULL");
+    AH_INDEX_LIVE(ix);
+    std::lock_guard<std::mutex> lk(ix->stats_mu);
+    AH_REQUIRE(ix->fstats.filters_alive == 0, AH_ERR_INVALID_ARGUMENT, "the index has %llu live filters: ah_filter_destroy them first",
+               (unsigned long long)ix->fstats.filters_alive);
+    return AH_OK;
+}
+
+int insert_impl(ah_index *ix, const uint32_t *ids, size_t n, const uint64_t *seeds, ah_index_delta *delta) {
+    ah_dataset *ds = ix->ds;
+    AH_HIP(hipSetDevice(ds->device));
+    ContextLease lease(ds);
+    AH_REQUIRE(lease.c, AH_ERR_DEVICE, "cannot create a HIP stream");
+    const hipStream_t s = lease.c->stream;
+    const uint32_t nn = ix->n_nodes, n_trees = ix->n_trees;
+    const uint64_t old_desc_len = ix->desc_len;
+    const uint64_t pairs = (uint64_t)n * n_trees;
+    AH_REQUIRE(old_desc_len + pairs < 0xFFFFFFFFull, AH_ERR_INVALID_ARGUMENT,
+               "%llu stored ids + %llu inserted ones are too many for 32-bit descendant offsets", (unsigned long long)old_desc_len,
+               (unsigned long long)pairs);
+    // every buffer whose size is known now; kernels write only into these
+    const size_t per_node = (size_t)nn + 1;
+    const size_t scan_tiles = (nn + kScanTile - 1) / kScanTile + 1;
+    const size_t seed_words = 2 * (size_t)n_trees;
+    const size_t work_words = 8 * per_node + scan_tiles + ICTL_WORDS + seed_words + n + 2 * pairs;
+    DevMem work, new_nodes, new_desc, out;
+    AH_TRY(alloc(&work, work_words * 4));
+    AH_TRY(alloc(&new_nodes, (size_t)nn * sizeof(DNode)));
+    delta->roots.resize(n_trees);
+    // [seeds][8 arrays per node][scan tiles][ctl][ids][leaf of every pair][landed]
+    uint64_t *d_seeds = work.as<uint64_t>();
+    uint32_t *w = work.as<uint32_t>() + seed_words;
+    InsertArgs a{};
+    a.nodes = ix->d_nodes;
+    a.n_nodes = nn;
+    a.desc = ix->d_desc;
+    a.old_desc_len = old_desc_len;
+    a.n_pairs = pairs;
+    uint32_t **fields[8] = {&a.cnt, &a.seg, &a.cursor, &a.chg, &a.fresh, &a.nlen, &a.dlen, &a.touched};
+    for (int i = 0; i < 8; i++) *fields[i] = w + (size_t)i * per_node;
+    uint32_t *tile_sums = w + 8 * per_node;
+    a.ctl = tile_sums + scan_tiles;
+    uint32_t *d_ids = a.ctl + ICTL_WORDS;
+    uint32_t *d_leaf = d_ids + n;
+    a.landed = d_leaf + pairs;
+    AH_HIP(hipMemsetAsync(w, 0, (8 * per_node + scan_tiles + ICTL_WORDS) * 4, s));
+    AH_HIP(hipMemsetAsync(a.ctl + ICTL_FIRST_BAD, 0xFF, 4, s));
+    uint32_t ctl[ICTL_WORDS] = {};
+    // 1. check
+    if (n) {
+        AH_HIP(hipMemcpyAsync(d_ids, ids, n * 4, hipMemcpyHostToDevice, s));
+        if (n_trees) AH_HIP(hipMemcpyAsync(d_seeds, seeds, (size_t)n_trees * 8, hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(k_insert_check, dim3(grid_of(n, kIxBlock, 4096)), dim3(kIxBlock), 0, s, ds->view(), (const uint32_t *)d_ids, (uint64_t)n,
+                           a.ctl);
+        AH_HIP(hipGetLastError());
+        AH_HIP(hipMemcpyAsync(ctl, a.ctl, sizeof(ctl), hipMemcpyDeviceToHost, s));
+        AH_HIP(hipStreamSynchronize(s));
+        AH_REQUIRE(ctl[ICTL_FIRST_BAD] >= n, AH_ERR_INVALID_ARGUMENT, "item %u (position %u of sorted_ids) is not a row of the dataset",
+                   ids[std::min<size_t>(ctl[ICTL_FIRST_BAD], n - 1)], ctl[ICTL_FIRST_BAD]);
+    }
+    const uint64_t span = (uint64_t)std::max<long long>(1, tun(TUN_LAUNCH_MAX_ITEMS));
+    if (pairs) {
+        // 2. route, 3. count: the ids in runs of at most AH_LAUNCH_MAX_ITEMS pairs; the pairs of ids [i0, i0 + cn) are
+        // d_leaf[i0 * n_trees, (i0 + cn) * n_trees), tree-major
+        const uint64_t run = std::max<uint64_t>(1, std::min<uint64_t>(n, span / n_trees));
+        uint32_t *d_route_err = a.ctl + ICTL_ERR;  // (bit 0, as the count pass: an id without a row, refused above)
+        for (uint64_t i0 = 0; i0 < n; i0 += run) {
+            const uint64_t cn = std::min<uint64_t>(run, n - i0), m = cn * n_trees;
+            AH_TRY(launch_route_items(ix, d_ids + i0, cn, d_seeds, d_leaf + i0 * n_trees, d_route_err, s));
+            hipLaunchKernelGGL(k_insert_count, dim3(grid_of(m, kIxBlock, 4096)), dim3(kIxBlock), 0, s, a, (const uint32_t *)(d_leaf + i0 * n_trees), m);
+        }
+        AH_HIP(hipGetLastError());
+        AH_HIP(hipMemcpyAsync(a.seg, a.cnt, (size_t)nn * 4, hipMemcpyDeviceToDevice, s));
+        launch_exclusive_scan(a.seg, nn, tile_sums, a.ctl + ICTL_DESC_LEN, s);  // (the total, n_pairs, is overwritten below)
+    }
+    if (nn) hipLaunchKernelGGL(k_insert_flags, dim3(grid_of(nn, kIxBlock, 4096)), dim3(kIxBlock), 0, s, a);
+    launch_exclusive_scan(a.chg, nn, tile_sums, a.ctl + ICTL_TOUCHED, s);
+    if (pairs) {
+        hipLaunchKernelGGL(k_insert_touched, dim3(grid_of(nn, kIxBlock, 4096)), dim3(kIxBlock), 0, s, a);
+        // 4. scatter
+        const uint64_t run = std::max<uint64_t>(1, std::min<uint64_t>(n, span / n_trees));
+        for (uint64_t i0 = 0; i0 < n; i0 += run) {
+            const uint64_t cn = std::min<uint64_t>(run, n - i0), m = cn * n_trees;
+            hipLaunchKernelGGL(k_insert_scatter, dim3(grid_of(m, kIxBlock, 4096)), dim3(kIxBlock), 0, s, a, (const uint32_t *)(d_ids + i0), cn,
+                               (const uint32_t *)(d_leaf + i0 * n_trees), m);
+        }
+    }
+    AH_HIP(hipGetLastError());
+    AH_HIP(hipMemcpyAsync(ctl, a.ctl, sizeof(ctl), hipMemcpyDeviceToHost, s));
+    AH_HIP(hipStreamSynchronize(s));
+    AH_REQUIRE(ctl[ICTL_ERR] == 0 && ctl[ICTL_TOUCHED] <= nn && ctl[ICTL_TOUCHED] <= pairs, AH_ERR_DEVICE,
+               "the index insert routed an id to a node that is no Descendants node (%u): the index is unchanged", ctl[ICTL_ERR]);
+    const uint32_t n_touched = ctl[ICTL_TOUCHED];
+    a.n_touched = n_touched;
+    // 5. fresh and the scans
+    if (n_touched) {
+        hipLaunchKernelGGL(k_insert_sort, dim3(grid_of(n_touched, 1, 1u << 16)), dim3(kIxBlock), 0, s, a);
+        for (uint64_t lo = 0; lo < n_touched; lo += span) {
+            const uint32_t hi = (uint32_t)std::min<uint64_t>(n_touched, lo + span);
+            hipLaunchKernelGGL(k_insert_fresh, dim3(grid_of(hi - lo, kIxBlock / 64, 1u << 16)), dim3(kIxBlock), 0, s, a, (uint32_t)lo, hi);
+        }
+    }
+    launch_exclusive_scan(a.nlen, nn, tile_sums, a.ctl + ICTL_DESC_LEN, s);
+    launch_exclusive_scan(a.dlen, nn, tile_sums, a.ctl + ICTL_DELTA_DESC, s);
+    AH_HIP(hipGetLastError());
+    AH_HIP(hipMemcpyAsync(ctl, a.ctl, sizeof(ctl), hipMemcpyDeviceToHost, s));
+    AH_HIP(hipStreamSynchronize(s));
+    const uint32_t desc_len = ctl[ICTL_DESC_LEN], delta_desc = ctl[ICTL_DELTA_DESC];
+    AH_REQUIRE(ctl[ICTL_ERR] == 0 && desc_len <= old_desc_len + pairs && delta_desc <= desc_len, AH_ERR_DEVICE, "the index insert found its own counts inconsistent (%u): the index is unchanged", ctl[ICTL_ERR]);
+    a.new_desc_len = desc_len;
+    a.delta_desc_len = delta_desc;
+    // the buffers whose size the scans have just given, and the host's
+    AH_TRY(alloc(&new_desc, (size_t)desc_len * 4));
+    AH_TRY(alloc(&out, (size_t)n_touched * sizeof(DeltaEntry) + (size_t)delta_desc * 4));
+    std::vector<DeltaEntry> entries(n_touched);
+    delta->desc.resize(delta_desc);
+    delta->put_index.reserve(n_touched);
+    delta->put.reserve(n_touched);
+    DeltaEntry *d_entries = out.as<DeltaEntry>();
+    uint32_t *d_delta_desc = reinterpret_cast<uint32_t *>(d_entries + n_touched);
+    // 6. write, 7. apply
+    for (uint64_t lo = 0; lo < nn; lo += span) {
+        const uint32_t hi = (uint32_t)std::min<uint64_t>(nn, lo + span);
+        hipLaunchKernelGGL(k_insert_write, dim3(grid_of(hi - lo, kIxBlock / 64, 1u << 16)), dim3(kIxBlock), 0, s, a, (uint32_t)lo, hi,
+                           new_desc.as<uint32_t>());
+    }
+    if (nn) hipLaunchKernelGGL(k_insert_apply, dim3(grid_of(nn, kIxBlock, 4096)), dim3(kIxBlock), 0, s, a, new_nodes.as<DNode>(), d_entries);
+    if (n_touched)
+        hipLaunchKernelGGL(k_insert_gather, dim3(grid_of(n_touched, kIxBlock / 64, 1u << 16)), dim3(kIxBlock), 0, s, a, (const DeltaEntry *)d_entries,
+                           new_desc.as<const uint32_t>(), d_delta_desc);
+    AH_HIP(hipGetLastError());
+    // read back
+    if (n_touched) AH_HIP(hipMemcpyAsync(entries.data(), d_entries, (size_t)n_touched * sizeof(DeltaEntry), hipMemcpyDeviceToHost, s));
+    if (delta_desc) AH_HIP(hipMemcpyAsync(delta->desc.data(), d_delta_desc, (size_t)delta_desc * 4, hipMemcpyDeviceToHost, s));
+    if (n_trees) AH_HIP(hipMemcpyAsync(delta->roots.data(), ix->d_roots, (size_t)n_trees * 4, hipMemcpyDeviceToHost, s));
+    AH_HIP(hipMemcpyAsync(ctl, a.ctl, sizeof(ctl), hipMemcpyDeviceToHost, s));
+    AH_HIP(hipStreamSynchronize(s));
+    AH_REQUIRE(ctl[ICTL_ERR] == 0, AH_ERR_DEVICE, "the index insert found its own counts inconsistent (%u): the index is unchanged", ctl[ICTL_ERR]);
+    for (const DeltaEntry &e : entries) {
+        ah_node nd{};
+        nd.kind = AH_NODE_DESCENDANTS;
+        nd.offset = e.a;
+        nd.count = e.b;
+        delta->put_index.push_back(e.node);
+        delta->put.push_back(nd);
+    }
+    {
+        // commit: nothing here can fail.  The old arrays go into the DevMems, which free them (dev_free waits for the device).
+        NoFailScope no_fail;
+        void *old_nodes = ix->d_nodes, *old_desc = ix->d_desc;
+        ix->d_nodes = new_nodes.as<DNode>();
+        ix->d_desc = new_desc.as<uint32_t>();
+        new_nodes.p = old_nodes;
+        new_desc.p = old_desc;
+        ix->desc_len = desc_len;
+        ix->n_leaves = ctl[ICTL_LEAVES];
+        ix->max_desc = ctl[ICTL_MAX_DESC];
+    }
+    if (tun(TUN_TIMING) != 0)
+        fprintf(stderr, "[ah] index insert: %zu ids x %u trees into %u of %u nodes, %llu -> %u stored ids\n", n, n_trees, n_touched, nn,
+                (unsigned long long)old_desc_len, desc_len);
+    return AH_OK;
+}
+
+int graft_impl(ah_index *ix, const ah_forest_view &v, const uint32_t *targets, const uint32_t *new_index, uint32_t *out_new_of_old) {
+    ah_dataset *ds = ix->ds;
+    AH_HIP(hipSetDevice(ds->device));
+    ContextLease lease(ds);
+    AH_REQUIRE(lease.c, AH_ERR_DEVICE, "cannot create a HIP stream");
+    const hipStream_t s = lease.c->stream;
+    const uint32_t n_old = ix->n_nodes, n_trees = ix->n_trees, n_view = (uint32_t)v.n_nodes;
+    const uint64_t span = (uint64_t)std::max<long long>(1, tun(TUN_LAUNCH_MAX_ITEMS));
+    // ---- validation: nothing is touched before it is through
+    uint32_t n_used = n_old;
+    if (ix->d_rank) {
+        AH_HIP(hipMemcpyAsync(&n_used, ix->d_rank + n_old, 4, hipMemcpyDeviceToHost, s));
+        AH_HIP(hipStreamSynchronize(s));
+        AH_REQUIRE(n_used <= n_old, AH_ERR_DEVICE, "the index counts more nodes in use than it has");
+    }
+    std::vector<uint32_t> vtgt(n_view, kNone), vfin(n_view, kNone), added_roots, repl;
+    for (uint32_t t = 0; t < v.n_trees; t++) {
+        if (targets[t] == AH_NEW_ROOT) {
+            added_roots.push_back(v.roots[t]);
+            continue;
+        }
+        AH_REQUIRE(targets[t] < n_old, AH_ERR_INVALID_ARGUMENT, "targets[%u] = %u is no node of the index (%u nodes)", t, targets[t], n_old);
+        vtgt[v.roots[t]] = targets[t];
+        repl.push_back(targets[t]);
+    }
+    const uint32_t n_repl = (uint32_t)repl.size();
+    {
+        std::vector<uint32_t> sorted(repl);
+        std::sort(sorted.begin(), sorted.end());
+        for (size_t i = 1; i < sorted.size(); i++)
+            AH_REQUIRE(sorted[i - 1] != sorted[i], AH_ERR_INVALID_ARGUMENT, "node %u is the target of two trees", sorted[i]);
+    }
+    const uint64_t n_new64 = (uint64_t)n_used + n_view - n_repl;
+    AH_REQUIRE(n_new64 < 0xFFFFFFFFull && ix->desc_len + v.descendants_len < 0xFFFFFFFFull, AH_ERR_INVALID_ARGUMENT,
+               "the index would outgrow 32-bit node / descendant offsets");
+    const uint32_t n_new = (uint32_t)n_new64;
+    {
+        uint32_t next = n_used;
+        std::vector<uint32_t> named;
+        named.reserve(n_view - n_repl);
+        for (uint32_t k = 0; k < n_view; k++) {
+            if (vtgt[k] != kNone) {
+                AH_REQUIRE(!new_index || new_index[k] == kNone, AH_ERR_INVALID_ARGUMENT,
+                           "new_index[%u] = %u: a root that replaces a node takes that node's place and must be given as 0xFFFFFFFF", k,
+                           new_index[k]);
+                continue;
+            }
+            vfin[k] = new_index ? new_index[k] : next++;
+            AH_REQUIRE(vfin[k] < n_new, AH_ERR_INVALID_ARGUMENT, "new_index[%u] = %u is not below the %u nodes the index will have", k, vfin[k],
+                       n_new);
+            named.push_back(vfin[k]);
+        }
+        std::sort(named.begin(), named.end());
+        for (size_t i = 1; i < named.size(); i++)
+            AH_REQUIRE(named[i - 1] != named[i], AH_ERR_INVALID_ARGUMENT, "new_index names position %u twice", named[i]);
+    }
+    // the view's nodes in the device's shape: c of a split node with a plane = the ordinal of its record
+    std::vector<DNode> vnodes(n_view);
+    std::vector<uint64_t> offsets;
+    for (uint32_t k = 0; k < n_view; k++) {
+        const ah_node &nd = v.nodes[k];
+        DNode d{};
+        d.kind = nd.kind;
+        if (nd.kind == AH_NODE_SPLIT) {
+            d.a = nd.left;
+            d.b = nd.right;
+            if (nd.has_normal) {
+                d.kind |= 0x100u;
+                d.c = (uint32_t)offsets.size();
+                offsets.push_back(nd.offset);
+            }
+        } else {
+            d.a = (uint32_t)nd.offset;
+            d.b = nd.count;
+        }
+        vnodes[k] = d;
+    }
+    const uint32_t n_vnormals = (uint32_t)offsets.size(), n_added = (uint32_t)added_roots.size();
+    AH_REQUIRE((uint64_t)ix->n_normals + n_vnormals < 0xFFFFFFFFull, AH_ERR_INVALID_ARGUMENT, "too many normals for 32-bit rows");
+    // ---- buffers
+    const uint32_t hf = header_floats(ds->metric);
+    const size_t row_bytes = ds->row_bytes();
+    const size_t scan_tiles = ((size_t)n_new + kScanTile - 1) / kScanTile + 1;
+    // [named n_new + 1][len n_new + 1][pos_of_rank n_used][new_of_old n_old][replaced n_old][fin n_view][tiles][ctl]
+    // [vfin n_view][vtgt n_view][repl n_repl][kinds n_repl][added n_added][view ids][vnodes]
+    const size_t zeroed = 2 * ((size_t)n_new + 1) + n_used + 2 * (size_t)n_old + n_view + scan_tiles + GCTL_WORDS;
+    const size_t words = zeroed + 2 * (size_t)n_view + 2 * (size_t)n_repl + n_added + v.descendants_len + 4 * (size_t)n_view;
+    DevMem work, new_nodes, new_roots, new_desc, recs, offs, grown_rows, grown_hdrs;
+    AH_TRY(alloc(&work, words * 4));
+    AH_TRY(alloc(&new_nodes, (size_t)n_new * sizeof(DNode)));
+    AH_TRY(alloc(&new_roots, ((size_t)n_trees + n_added) * 4));
+    uint32_t *w = work.as<uint32_t>();
+    GraftArgs a{};
+    a.nodes = ix->d_nodes;
+    a.n_old = n_old;
+    a.n_used = n_used;
+    a.rank = ix->d_rank;
+    a.desc = ix->d_desc;
+    a.old_desc_len = ix->desc_len;
+    a.n_view = n_view;
+    a.vdesc_len = v.descendants_len;
+    a.n_new = n_new;
+    a.first_row = ix->n_normals;
+    a.named = w;
+    a.len = a.named + n_new + 1;
+    a.pos_of_rank = a.len + n_new + 1;
+    a.new_of_old = a.pos_of_rank + n_used;
+    a.replaced = a.new_of_old + n_old;
+    a.fin = a.replaced + n_old;
+    uint32_t *tile_sums = a.fin + n_view;
+    a.ctl = tile_sums + scan_tiles;
+    uint32_t *d_vfin = a.ctl + GCTL_WORDS, *d_vtgt = d_vfin + n_view, *d_repl = d_vtgt + n_view, *d_kinds = d_repl + n_repl;
+    uint32_t *d_added = d_kinds + n_repl, *d_vdesc = d_added + n_added;
+    DNode *d_vnodes = reinterpret_cast<DNode *>(d_vdesc + v.descendants_len);  // (4-byte members only)
+    a.vfin = d_vfin;
+    a.vtgt = d_vtgt;
+    a.vdesc = d_vdesc;
+    a.vnodes = d_vnodes;
+    AH_HIP(hipMemsetAsync(work.p, 0, zeroed * 4, s));
+    if (n_view) {
+        AH_HIP(hipMemcpyAsync(d_vfin, vfin.data(), (size_t)n_view * 4, hipMemcpyHostToDevice, s));
+        AH_HIP(hipMemcpyAsync(d_vtgt, vtgt.data(), (size_t)n_view * 4, hipMemcpyHostToDevice, s));
+        AH_HIP(hipMemcpyAsync(d_vnodes, vnodes.data(), (size_t)n_view * sizeof(DNode), hipMemcpyHostToDevice, s));
+    }
+    if (n_repl) AH_HIP(hipMemcpyAsync(d_repl, repl.data(), (size_t)n_repl * 4, hipMemcpyHostToDevice, s));
+    if (n_added) AH_HIP(hipMemcpyAsync(d_added, added_roots.data(), (size_t)n_added * 4, hipMemcpyHostToDevice, s));
+    if (v.descendants_len) AH_HIP(hipMemcpyAsync(d_vdesc, v.descendants, v.descendants_len * 4, hipMemcpyHostToDevice, s));
+    if (n_repl) {  // the targets: in use and Descendants nodes
+        std::vector<uint32_t> kinds(n_repl);
+        hipLaunchKernelGGL(k_graft_peek, dim3(grid_of(n_repl, kIxBlock, 1024)), dim3(kIxBlock), 0, s, (const DNode *)ix->d_nodes,
+                           (const uint32_t *)d_repl, n_repl, d_kinds);
+        AH_HIP(hipGetLastError());
+        AH_HIP(hipMemcpyAsync(kinds.data(), d_kinds, (size_t)n_repl * 4, hipMemcpyDeviceToHost, s));
+        AH_HIP(hipStreamSynchronize(s));
+        for (uint32_t i = 0; i < n_repl; i++)
+            AH_REQUIRE((kinds[i] & 0xFFu) == AH_NODE_DESCENDANTS, AH_ERR_INVALID_ARGUMENT, "target %u is %s", repl[i],
+                       kinds[i] == 0 ? "a free slot of the index" : "a split node, not a Descendants node");
+    }
+    // ---- 1. named, 2. lengths
+    if (n_view) hipLaunchKernelGGL(k_graft_named, dim3(grid_of(n_view, kIxBlock, 4096)), dim3(kIxBlock), 0, s, a);
+    launch_exclusive_scan(a.named, n_new, tile_sums, a.named + n_new, s);
+    if (n_new) hipLaunchKernelGGL(k_graft_positions, dim3(grid_of(n_new, kIxBlock, 4096)), dim3(kIxBlock), 0, s, a);
+    if (n_old) hipLaunchKernelGGL(k_graft_old_map, dim3(grid_of(n_old, kIxBlock, 4096)), dim3(kIxBlock), 0, s, a);
+    if (n_view) hipLaunchKernelGGL(k_graft_fin, dim3(grid_of(n_view, kIxBlock, 4096)), dim3(kIxBlock), 0, s, a);
+    const uint64_t items = (uint64_t)n_old + n_view;
+    if (items) hipLaunchKernelGGL(k_graft_len, dim3(grid_of(items, kIxBlock, 4096)), dim3(kIxBlock), 0, s, a);
+    launch_exclusive_scan(a.len, n_new, tile_sums, a.ctl + GCTL_DESC_LEN, s);
+    AH_HIP(hipGetLastError());
+    uint32_t ctl[GCTL_WORDS] = {};
+    AH_HIP(hipMemcpyAsync(ctl, a.ctl, sizeof(ctl), hipMemcpyDeviceToHost, s));
+    AH_HIP(hipMemcpyAsync(&ctl[GCTL_NAMED], a.named + n_new, 4, hipMemcpyDeviceToHost, s));
+    AH_HIP(hipStreamSynchronize(s));
+    AH_REQUIRE(ctl[GCTL_ERR] == 0 && ctl[GCTL_NAMED] == n_view - n_repl && ctl[GCTL_DESC_LEN] <= ix->desc_len + v.descendants_len,
+               AH_ERR_DEVICE, "the index graft found its own counts inconsistent (%u): the index is unchanged", ctl[GCTL_ERR]);
+    const uint32_t desc_len = ctl[GCTL_DESC_LEN];
+    a.new_desc_len = desc_len;
+    AH_TRY(alloc(&new_desc, (size_t)desc_len * 4));
+    // ---- 5. normals: into the spare rows, or into arrays grown geometrically
+    const uint32_t need = ix->n_normals + n_vnormals;
+    uint32_t cap = ix->normals_cap;
+    void *rows = ix->d_nrows;
+    float *hdrs = ix->d_nhdrs;
+    if (need > cap) {
+        cap = (uint32_t)std::min<uint64_t>(0xFFFFFFFFull, std::max<uint64_t>(need, 2 * (uint64_t)cap));
+        AH_TRY(alloc(&grown_rows, (size_t)cap * row_bytes));
+        AH_TRY(alloc(&grown_hdrs, (size_t)cap * hf * 4));
+        rows = grown_rows.p;
+        hdrs = grown_hdrs.as<float>();
+        if (ix->n_normals) {
+            AH_HIP(hipMemcpyAsync(rows, ix->d_nrows, (size_t)ix->n_normals * row_bytes, hipMemcpyDeviceToDevice, s));
+            AH_HIP(hipMemcpyAsync(hdrs, ix->d_nhdrs, (size_t)ix->n_normals * hf * 4, hipMemcpyDeviceToDevice, s));
+        }
+    }
+    if (n_vnormals) {
+        AH_TRY(alloc(&recs, v.normals_len));
+        AH_TRY(alloc(&offs, offsets.size() * 8));
+        AH_HIP(hipMemcpyAsync(recs.p, v.normals, v.normals_len, hipMemcpyHostToDevice, s));
+        AH_HIP(hipMemcpyAsync(offs.p, offsets.data(), offsets.size() * 8, hipMemcpyHostToDevice, s));
+        AH_TRY(launch_unpack_normals(ds, recs.as<uint8_t>(), offs.as<uint64_t>(), n_vnormals, v.normal_vector_offset, v.normal_header_offset,
+                                     static_cast<uint8_t *>(rows) + (size_t)ix->n_normals * row_bytes, hdrs + (size_t)ix->n_normals * hf, s));
+    }
+    // ---- 3. nodes, 4. lists
+    if (items) hipLaunchKernelGGL(k_graft_nodes, dim3(grid_of(items, kIxBlock, 4096)), dim3(kIxBlock), 0, s, a, new_nodes.as<DNode>());
+    for (uint64_t lo = 0; lo < items; lo += span) {
+        const uint64_t hi = std::min<uint64_t>(items, lo + span);
+        hipLaunchKernelGGL(k_graft_lists, dim3(grid_of(hi - lo, kIxBlock / 64, 1u << 16)), dim3(kIxBlock), 0, s, a, lo, hi, new_desc.as<uint32_t>());
+    }
+    if (n_trees + n_added)
+        hipLaunchKernelGGL(k_graft_roots, dim3(grid_of((uint64_t)n_trees + n_added, kIxBlock, 1024)), dim3(kIxBlock), 0, s, a,
+                           (const uint32_t *)ix->d_roots, n_trees, (const uint32_t *)d_added, n_added, new_roots.as<uint32_t>());
+    AH_HIP(hipGetLastError());
+    std::vector<uint32_t> map_out(out_new_of_old ? n_old : 0);
+    if (out_new_of_old && n_old) AH_HIP(hipMemcpyAsync(map_out.data(), a.new_of_old, (size_t)n_old * 4, hipMemcpyDeviceToHost, s));
+    AH_HIP(hipMemcpyAsync(ctl, a.ctl, sizeof(ctl), hipMemcpyDeviceToHost, s));
+    AH_HIP(hipStreamSynchronize(s));
+    AH_REQUIRE(ctl[GCTL_ERR] == 0, AH_ERR_DEVICE, "the index graft found its own counts inconsistent (%u): the index is unchanged", ctl[GCTL_ERR]);
+    {
+        // commit: nothing here can fail.  The old arrays go into the DevMems, which free them (dev_free waits for the device).
+        NoFailScope no_fail;
+        if (out_new_of_old && n_old) memcpy(out_new_of_old, map_out.data(), (size_t)n_old * 4);
+        std::swap(new_nodes.p, *reinterpret_cast<void **>(&ix->d_nodes));
+        std::swap(new_roots.p, *reinterpret_cast<void **>(&ix->d_roots));
+        std::swap(new_desc.p, *reinterpret_cast<void **>(&ix->d_desc));
+        DevMem old_rank;
+        old_rank.p = ix->d_rank;
+        ix->d_rank = nullptr;
+        if (grown_rows.p) {
+            std::swap(grown_rows.p, ix->d_nrows);
+            std::swap(grown_hdrs.p, *reinterpret_cast<void **>(&ix->d_nhdrs));
+            ix->normals_cap = cap;
+            const bool bq = metric_is_bq(ds->metric);
+            ix->nv.rows_f32 = bq ? nullptr : reinterpret_cast<const float *>(ix->d_nrows);
+            ix->nv.rows_bq = bq ? reinterpret_cast<const uint64_t *>(ix->d_nrows) : nullptr;
+            ix->nv.headers = ix->d_nhdrs;
+        }
+        ix->n_normals = need;
+        ix->nv.n = need;
+        ix->n_nodes = n_new;
+        ix->n_trees = n_trees + n_added;
+        ix->desc_len = desc_len;
+        ix->n_leaves = ctl[GCTL_LEAVES];
+        ix->max_desc = ctl[GCTL_MAX_DESC];
+    }
+    if (tun(TUN_TIMING) != 0)
+        fprintf(stderr, "[ah] index graft: %u view nodes (%u replacing roots, %u new roots, %u normals) into %u nodes -> %u nodes, %u stored ids\n",
+                n_view, n_repl, n_added, n_vnormals, n_used, n_new, desc_len);
+    return AH_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -553,6 +1364,90 @@ int ah_index_delete_items(ah_index *ix, const uint32_t *sorted_ids, size_t n, ui
     std::unique_ptr<ah_index_delta> delta(new ah_index_delta);
     AH_TRY(delete_impl(ix, sorted_ids, n, split_after, delta.get()));
     *out_delta = delta.release();
+    return AH_OK;
+    AH_GUARDED_END
+}
+
+int ah_index_insert_items(ah_index *ix, const uint32_t *sorted_ids, size_t n, const uint64_t *tree_seeds, ah_index_delta **out_delta) {
+    AH_GUARDED("ah_index_insert_items")
+    AH_REQUIRE(out_delta, AH_ERR_INVALID_ARGUMENT, "out_delta is NULL");
+    *out_delta = nullptr;
+    // (what can be judged without the index first)
+    AH_REQUIRE(n == 0 || sorted_ids, AH_ERR_INVALID_ARGUMENT, "sorted_ids is NULL");
+    AH_REQUIRE(n < 0xFFFFFFFFull, AH_ERR_INVALID_ARGUMENT, "more ids than the u32 item-id space holds");
+    for (size_t i = 1; i < n; i++)
+        AH_REQUIRE(sorted_ids[i - 1] < sorted_ids[i], AH_ERR_INVALID_ARGUMENT, "sorted_ids is not strictly ascending at position %zu (%u after %u)",
+                   i, sorted_ids[i], sorted_ids[i - 1]);
+    AH_TRY(index_updatable(ix));
+    AH_REQUIRE(n == 0 || ix->n_trees == 0 || tree_seeds, AH_ERR_INVALID_ARGUMENT, "tree_seeds is NULL");
+    DeviceRestore restore_device;
+    std::unique_ptr<ah_index_delta> delta(new ah_index_delta);
+    AH_TRY(insert_impl(ix, sorted_ids, n, tree_seeds, delta.get()));
+    *out_delta = delta.release();
+    return AH_OK;
+    AH_GUARDED_END
+}
+
+int ah_index_graft(ah_index *ix, const ah_forest_view *view, const uint32_t *targets, const uint32_t *new_index, uint32_t *out_new_of_old) {
+    AH_GUARDED("ah_index_graft")
+    AH_TRY(index_updatable(ix));
+    AH_REQUIRE(view, AH_ERR_INVALID_ARGUMENT, "view is NULL");
+    const ah_forest_view v = *view;
+    AH_TRY(validate_forest_view(ix->ds, v));
+    AH_REQUIRE(v.n_trees == 0 || targets, AH_ERR_INVALID_ARGUMENT, "targets is NULL");
+    DeviceRestore restore_device;
+    return graft_impl(ix, v, targets, new_index, out_new_of_old);
+    AH_GUARDED_END
+}
+
+int ah_index_export_info(const ah_index *ix, ah_index_info *out) {
+    AH_GUARDED("ah_index_export_info")
+    AH_REQUIRE(ix && ix->ds && out, AH_ERR_INVALID_ARGUMENT, "NULL argument");
+    out->n_nodes = ix->n_nodes;
+    out->desc_len = ix->desc_len;
+    out->n_trees = ix->n_trees;
+    out->n_normals = ix->n_normals;
+    out->normal_row_bytes = ix->ds->row_bytes();
+    out->normal_header_floats = header_floats(ix->ds->metric);
+    out->reserved = 0;
+    return AH_OK;
+    AH_GUARDED_END
+}
+
+int ah_index_export(ah_index *ix, ah_node *nodes, uint32_t *roots, uint32_t *descendants, void *normal_rows, float *normal_headers) {
+    AH_GUARDED("ah_index_export")
+    AH_REQUIRE(ix && ix->ds, AH_ERR_INVALID_ARGUMENT, "index is NULL");
+    AH_INDEX_LIVE(ix);
+    DeviceRestore restore_device;
+    ah_dataset *ds = ix->ds;
+    AH_HIP(hipSetDevice(ds->device));
+    ContextLease lease(ds);
+    AH_REQUIRE(lease.c, AH_ERR_DEVICE, "cannot create a HIP stream");
+    const hipStream_t s = lease.c->stream;
+    std::vector<DNode> raw(nodes ? ix->n_nodes : 0);
+    if (!raw.empty()) AH_HIP(hipMemcpyAsync(raw.data(), ix->d_nodes, raw.size() * sizeof(DNode), hipMemcpyDeviceToHost, s));
+    if (roots && ix->n_trees) AH_HIP(hipMemcpyAsync(roots, ix->d_roots, (size_t)ix->n_trees * 4, hipMemcpyDeviceToHost, s));
+    if (descendants && ix->desc_len) AH_HIP(hipMemcpyAsync(descendants, ix->d_desc, ix->desc_len * 4, hipMemcpyDeviceToHost, s));
+    if (normal_rows && ix->n_normals)
+        AH_HIP(hipMemcpyAsync(normal_rows, ix->d_nrows, (size_t)ix->n_normals * ds->row_bytes(), hipMemcpyDeviceToHost, s));
+    if (normal_headers && ix->n_normals)
+        AH_HIP(hipMemcpyAsync(normal_headers, ix->d_nhdrs, (size_t)ix->n_normals * header_floats(ds->metric) * 4, hipMemcpyDeviceToHost, s));
+    AH_HIP(hipStreamSynchronize(s));
+    for (size_t i = 0; i < raw.size(); i++) {
+        const DNode &d = raw[i];
+        ah_node nd{};
+        nd.kind = (uint8_t)(d.kind & 0xFFu);
+        if (nd.kind == AH_NODE_SPLIT) {
+            nd.has_normal = (d.kind & 0x100u) ? 1 : 0;
+            nd.left = d.a;
+            nd.right = d.b;
+            nd.offset = d.c;
+        } else if (nd.kind == AH_NODE_DESCENDANTS) {
+            nd.offset = d.a;
+            nd.count = d.b;
+        }
+        nodes[i] = nd;
+    }
     return AH_OK;
     AH_GUARDED_END
 }

@@ -3596,65 +3596,30 @@ void index_prepare_screens(ah_dataset *ds) {
     }
 }
 
-}  // namespace ah
-
-using namespace ah;
-
-// `QueryBuilder::candidates` resident on the device of its index: one block [bitmap over 0 .. largest stored id][per node:
-// |descendants & candidates|].  Immutable after ah_filter_create.
-struct ah_filter {
-    ah_index *ix = nullptr;
-    uint32_t *d_bits = nullptr, *d_leaf_kept = nullptr;
-    uint64_t len_bits = 0, listed = 0, stored = 0, device_bytes = 0;
-};
-
-extern "C" {
-
-int ah_index_create_from_view(ah_dataset *ds, const ah_forest_view *view, ah_index **out);
-
-int ah_index_destroy(ah_index *ix) {
-    AH_GUARDED("ah_index_destroy")
-    if (!ix) return AH_OK;
-    {
-        std::lock_guard<std::mutex> lk(ix->stats_mu);
-        AH_REQUIRE(ix->fstats.filters_alive == 0, AH_ERR_INVALID_ARGUMENT, "the index has %llu live filters: ah_filter_destroy them first",
-                   (unsigned long long)ix->fstats.filters_alive);
-    }
-    NoFailScope no_fail;
-    if (ix->ds) (void)hipSetDevice(ix->ds->device);
-    (void)hipDeviceSynchronize();
-    if (ix->d_nodes) (void)dev_free(ix->d_nodes);
-    if (ix->d_roots) (void)dev_free(ix->d_roots);
-    if (ix->d_desc) (void)dev_free(ix->d_desc);
-    if (ix->d_rank) (void)dev_free(ix->d_rank);
-    if (ix->d_nrows) (void)dev_free(ix->d_nrows);
-    if (ix->d_nhdrs) (void)dev_free(ix->d_nhdrs);
-    if (ix->counted) ix->ds->live_indexes.fetch_sub(1, std::memory_order_acq_rel);
-    delete ix;
+// k_route_items over ids that are on the device already (ah_route_items, ah_index_insert_items)
+int launch_route_items(ah_index *ix, const uint32_t *d_ids, uint64_t n, const uint64_t *d_seeds, uint32_t *d_leaf, uint32_t *d_err,
+                       hipStream_t s) {
+    const uint64_t pairs = n * (uint64_t)ix->n_trees;
+    if (pairs == 0) return AH_OK;
+    const unsigned grid = (unsigned)((pairs * 8 + 255) / 256);
+    hipLaunchKernelGGL(k_route_items, dim3(grid), dim3(256), 0, s, ix->ds->view(), ix->nv, ix->d_nodes, (const uint32_t *)ix->d_rank,
+                       ix->d_roots, ix->n_trees, d_ids, n, d_seeds, d_leaf, d_err);
+    AH_HIP(hipGetLastError());
     return AH_OK;
-    AH_GUARDED_END
 }
 
-// Mirror a forest in HBM next to its dataset.  The forest handle may be destroyed afterwards.
-int ah_index_create(ah_dataset *ds, const ah_forest *forest, ah_index **out) {
-    AH_GUARDED("ah_index_create")
-    AH_REQUIRE(out, AH_ERR_INVALID_ARGUMENT, "out is NULL");
-    *out = nullptr;
-    AH_REQUIRE(forest, AH_ERR_INVALID_ARGUMENT, "NULL argument");
-    ah_forest_view v;
-    AH_TRY(ah_forest_view_get(forest, &v));
-    return ah_index_create_from_view(ds, &v, out);
-    AH_GUARDED_END
+int launch_unpack_normals(const ah_dataset *ds, const uint8_t *d_recs, const uint64_t *d_offsets, uint32_t n, uint64_t vec_off,
+                          uint64_t hdr_off, void *d_rows, float *d_headers, hipStream_t s) {
+    if (n == 0) return AH_OK;
+    hipLaunchKernelGGL(k_unpack_normals, dim3(n), dim3(256), 0, s, d_recs, d_offsets, n, vec_off, hdr_off,
+                       (uint32_t)(ah_vector_size(ds->metric, ds->dims) / 4), (uint32_t)(ds->row_bytes() / 4), header_floats(ds->metric),
+                       reinterpret_cast<uint32_t *>(d_rows), d_headers);
+    AH_HIP(hipGetLastError());
+    return AH_OK;
 }
 
-// Same from caller-owned arrays (e.g. tree nodes decoded from LMDB by `Reader::open`); nothing is retained.
-int ah_index_create_from_view(ah_dataset *ds, const ah_forest_view *view, ah_index **out) {
-    AH_GUARDED("ah_index_create_from_view")
-    AH_REQUIRE(out, AH_ERR_INVALID_ARGUMENT, "out is NULL");
-    *out = nullptr;
-    AH_REQUIRE(ds && view, AH_ERR_INVALID_ARGUMENT, "NULL argument");
-    AH_REQUIRE(ds->finalized, AH_ERR_NOT_FINALIZED, "dataset not finalized");
-    const ah_forest_view v = *view;
+// What a view must be before ah_index_create_from_view mirrors it or ah_index_graft adds it to an index.
+int validate_forest_view(const ah_dataset *ds, const ah_forest_view &v) {
     AH_REQUIRE(v.n_nodes == 0 || v.nodes, AH_ERR_INVALID_ARGUMENT, "nodes is NULL");
     AH_REQUIRE(v.n_trees == 0 || v.roots, AH_ERR_INVALID_ARGUMENT, "roots is NULL");
     AH_REQUIRE(v.descendants_len == 0 || v.descendants, AH_ERR_INVALID_ARGUMENT, "descendants is NULL");
@@ -3716,6 +3681,69 @@ int ah_index_create_from_view(ah_dataset *ds, const ah_forest_view *view, ah_ind
                    "the Descendants nodes hold %llu ids but the blob has %llu: ranges overlap",
                    (unsigned long long)total_desc, (unsigned long long)v.descendants_len);
     }
+    return AH_OK;
+}
+
+}  // namespace ah
+
+using namespace ah;
+
+// `QueryBuilder::candidates` resident on the device of its index: one block [bitmap over 0 .. largest stored id][per node:
+// |descendants & candidates|].  Immutable after ah_filter_create.
+struct ah_filter {
+    ah_index *ix = nullptr;
+    uint32_t *d_bits = nullptr, *d_leaf_kept = nullptr;
+    uint64_t len_bits = 0, listed = 0, stored = 0, device_bytes = 0;
+};
+
+extern "C" {
+
+int ah_index_create_from_view(ah_dataset *ds, const ah_forest_view *view, ah_index **out);
+
+int ah_index_destroy(ah_index *ix) {
+    AH_GUARDED("ah_index_destroy")
+    if (!ix) return AH_OK;
+    {
+        std::lock_guard<std::mutex> lk(ix->stats_mu);
+        AH_REQUIRE(ix->fstats.filters_alive == 0, AH_ERR_INVALID_ARGUMENT, "the index has %llu live filters: ah_filter_destroy them first",
+                   (unsigned long long)ix->fstats.filters_alive);
+    }
+    NoFailScope no_fail;
+    if (ix->ds) (void)hipSetDevice(ix->ds->device);
+    (void)hipDeviceSynchronize();
+    if (ix->d_nodes) (void)dev_free(ix->d_nodes);
+    if (ix->d_roots) (void)dev_free(ix->d_roots);
+    if (ix->d_desc) (void)dev_free(ix->d_desc);
+    if (ix->d_rank) (void)dev_free(ix->d_rank);
+    if (ix->d_nrows) (void)dev_free(ix->d_nrows);
+    if (ix->d_nhdrs) (void)dev_free(ix->d_nhdrs);
+    if (ix->counted) ix->ds->live_indexes.fetch_sub(1, std::memory_order_acq_rel);
+    delete ix;
+    return AH_OK;
+    AH_GUARDED_END
+}
+
+// Mirror a forest in HBM next to its dataset.  The forest handle may be destroyed afterwards.
+int ah_index_create(ah_dataset *ds, const ah_forest *forest, ah_index **out) {
+    AH_GUARDED("ah_index_create")
+    AH_REQUIRE(out, AH_ERR_INVALID_ARGUMENT, "out is NULL");
+    *out = nullptr;
+    AH_REQUIRE(forest, AH_ERR_INVALID_ARGUMENT, "NULL argument");
+    ah_forest_view v;
+    AH_TRY(ah_forest_view_get(forest, &v));
+    return ah_index_create_from_view(ds, &v, out);
+    AH_GUARDED_END
+}
+
+// Same from caller-owned arrays (e.g. tree nodes decoded from LMDB by `Reader::open`); nothing is retained.
+int ah_index_create_from_view(ah_dataset *ds, const ah_forest_view *view, ah_index **out) {
+    AH_GUARDED("ah_index_create_from_view")
+    AH_REQUIRE(out, AH_ERR_INVALID_ARGUMENT, "out is NULL");
+    *out = nullptr;
+    AH_REQUIRE(ds && view, AH_ERR_INVALID_ARGUMENT, "NULL argument");
+    AH_REQUIRE(ds->finalized, AH_ERR_NOT_FINALIZED, "dataset not finalized");
+    const ah_forest_view v = *view;
+    AH_TRY(validate_forest_view(ds, v));
     AH_HIP(hipSetDevice(ds->device));
     ah_index *ix = new (std::nothrow) ah_index();
     AH_REQUIRE(ix, AH_ERR_OUT_OF_MEMORY, "host allocation failed");
@@ -3752,6 +3780,7 @@ int ah_index_create_from_view(ah_dataset *ds, const ah_forest_view *view, ah_ind
         nodes[i] = d;
     }
     ix->n_normals = (uint32_t)offsets.size();
+    ix->normals_cap = std::max<uint32_t>(1, ix->n_normals);
     const bool bq = metric_is_bq(ds->metric);
     const uint32_t hf = header_floats(ds->metric);
     const size_t row_bytes = ds->row_bytes();
@@ -3780,10 +3809,8 @@ int ah_index_create_from_view(ah_dataset *ds, const ah_forest_view *view, ah_ind
         AH_IX(dev_malloc(&offs.p, offsets.size() * 8));
         AH_IX(hipMemcpy(recs.p, v.normals, v.normals_len, hipMemcpyHostToDevice));
         AH_IX(hipMemcpy(offs.p, offsets.data(), offsets.size() * 8, hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(k_unpack_normals, dim3(ix->n_normals), dim3(256), 0, 0, recs.as<uint8_t>(), offs.as<uint64_t>(),
-                           ix->n_normals, v.normal_vector_offset, v.normal_header_offset,
-                           (uint32_t)(ah_vector_size(ds->metric, ds->dims) / 4), (uint32_t)(row_bytes / 4), hf,
-                           reinterpret_cast<uint32_t *>(ix->d_nrows), ix->d_nhdrs);
+        AH_TRY(launch_unpack_normals(ds, recs.as<uint8_t>(), offs.as<uint64_t>(), ix->n_normals, v.normal_vector_offset,
+                                     v.normal_header_offset, ix->d_nrows, ix->d_nhdrs, 0));
         AH_IX(hipDeviceSynchronize());
     }
 #undef AH_IX
@@ -4541,10 +4568,7 @@ int ah_route_items(ah_index *ix, const uint32_t *item_ids, size_t n, const uint6
     AH_HIP(hipMemcpyAsync(d_ids, h_ids, n * 4, hipMemcpyHostToDevice, s));
     AH_HIP(hipMemcpyAsync(d_seeds, h_seeds, (size_t)ix->n_trees * 8, hipMemcpyHostToDevice, s));
     AH_HIP(hipMemsetAsync(d_err, 0, 4, s));
-    const unsigned grid = (unsigned)((pairs * 8 + 255) / 256);
-    hipLaunchKernelGGL(k_route_items, dim3(grid), dim3(256), 0, s, ds->view(), ix->nv, ix->d_nodes, (const uint32_t *)ix->d_rank,
-                       ix->d_roots, ix->n_trees, d_ids, (uint64_t)n, d_seeds, d_leaf, d_err);
-    AH_HIP(hipGetLastError());
+    AH_TRY(launch_route_items(ix, d_ids, (uint64_t)n, d_seeds, d_leaf, d_err, s));
     AH_HIP(hipMemcpyAsync(h_leaf, d_leaf, pairs * 4, hipMemcpyDeviceToHost, s));
     AH_HIP(hipMemcpyAsync(h_err, d_err, 4, hipMemcpyDeviceToHost, s));
     AH_HIP(hipStreamSynchronize(s));

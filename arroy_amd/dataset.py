@@ -538,6 +538,12 @@ class DatasetGroup:
             pass
 
 
+# the ah_node record (include/arroy_hip.h) as a numpy dtype
+_NODE_DT = np.dtype([("kind", "u1"), ("has_normal", "u1"), ("reserved", "<u2"), ("tree", "<u4"), ("left", "<u4"), ("right", "<u4"),
+                     ("offset", "<u8"), ("count", "<u4"), ("depth", "<u4")], align=True)
+assert _NODE_DT.itemsize == C.sizeof(_lib.AhNode)
+
+
 class Index:
     """Dataset + forest resident in HBM: the whole `Reader::nns_by_leaf` runs on device (ah_search_batch)."""
 
@@ -636,21 +642,72 @@ class Index:
         arr = _u32(sorted_ids).ravel()
         h = C.c_void_p()
         _lib.check(_lib.lib().ah_index_delete_items(self._h, _ptr(arr), arr.size, int(split_after), C.byref(h)))
+        return self._take_delta(h)
+
+    @staticmethod
+    def _take_delta(h) -> dict:
+        """ah_index_delta_get as numpy arrays; the delta is destroyed."""
         try:
             v = _lib.AhIndexDeltaView()
             _lib.check(_lib.lib().ah_index_delta_get(h, C.byref(v)))
 
             def u32s(p, n):
                 return np.ctypeslib.as_array(p, shape=(n,)).copy() if n else np.zeros(0, np.uint32)
-            node_dt = np.dtype([("kind", "u1"), ("has_normal", "u1"), ("reserved", "<u2"), ("tree", "<u4"), ("left", "<u4"),
-                                ("right", "<u4"), ("offset", "<u8"), ("count", "<u4"), ("depth", "<u4")], align=True)
-            assert node_dt.itemsize == C.sizeof(_lib.AhNode)
             n_put = int(v.n_put)
-            put = np.frombuffer(C.string_at(v.put, n_put * node_dt.itemsize), dtype=node_dt).copy() if n_put else np.zeros(0, node_dt)
+            put = np.frombuffer(C.string_at(v.put, n_put * _NODE_DT.itemsize), dtype=_NODE_DT).copy() if n_put else np.zeros(0, _NODE_DT)
             return {"removed": u32s(v.removed, int(v.n_removed)), "put_index": u32s(v.put_index, n_put), "put": put,
                     "desc": u32s(v.desc, int(v.desc_len)), "roots": u32s(v.roots, int(v.n_trees))}
         finally:
             _lib.lib().ah_index_delta_destroy(h)
+
+    def insert_items(self, sorted_ids, tree_seeds: Sequence[int]) -> dict:
+        """ah_index_insert_items: `insert_items_in_descendants_from_frozen_reader` (src/writer.rs:1398-1459) on the resident
+        index, the lists included: every id (ascending, distinct, a row of the dataset) is routed as route_items routes it and
+        joins the Descendants node it lands in.  Returns a delta in the shape of delete_items: `removed` is empty, `put` are
+        the nodes an id landed in with their new lists."""
+        arr = _u32(sorted_ids).ravel()
+        seeds = np.ascontiguousarray(tree_seeds, dtype=np.uint64)
+        h = C.c_void_p()
+        _lib.check(_lib.lib().ah_index_insert_items(self._h, _ptr(arr), arr.size, _ptr(seeds), C.byref(h)))
+        return self._take_delta(h)
+
+    def graft(self, view, targets, new_index=None, want_map: bool = False) -> Optional[np.ndarray]:
+        """ah_index_graft: the trees of `view` (an ah_forest_view: Forest.view_struct() or TreeStore.to_view) join the index,
+        tree t in place of the Descendants node targets[t] or, with NEW_ROOT, as a new root.  new_index[k]: the final
+        index of view node k (0xFFFFFFFF for a replacing root); None: the new nodes follow the existing ones.  The index is
+        renumbered and has no free slots afterwards.  want_map: return the new index of every old node slot."""
+        tg = _u32(targets).ravel()
+        if tg.size != int(view.n_trees):
+            raise ValueError(f"{tg.size} targets for the {int(view.n_trees)} trees of the view")
+        ni = None if new_index is None else _u32(new_index).ravel()
+        if ni is not None and ni.size != int(view.n_nodes):
+            raise ValueError(f"new_index has {ni.size} entries for the {int(view.n_nodes)} nodes of the view")
+        out = np.zeros(self.export_info()["n_nodes"], dtype=np.uint32) if want_map else None
+        _lib.check(_lib.lib().ah_index_graft(self._h, C.cast(C.byref(view), C.POINTER(_lib.AhForestView)), _ptr(tg), _ptr(ni),
+                                             _ptr(out)))
+        return out
+
+    def export_info(self) -> dict:
+        """ah_index_export_info: n_nodes, desc_len, n_trees, n_normals and the geometry of the normal rows."""
+        info = _lib.AhIndexInfo()
+        _lib.check(_lib.lib().ah_index_export_info(self._h, C.byref(info)))
+        return {f: int(getattr(info, f)) for f, _ in _lib.AhIndexInfo._fields_ if f != "reserved"}
+
+    def export(self, normals: bool = True) -> dict:
+        """ah_index_export: the index as it is on the device — nodes (the ah_node record: kind 0 is a free slot, `offset` of a
+        split node is its normal row), roots, descendants and, with normals=True, normal_rows (n_normals x row bytes, u8) and
+        normal_headers (n_normals x header floats)."""
+        info = self.export_info()
+        nodes = np.zeros(info["n_nodes"], dtype=_NODE_DT)
+        roots = np.zeros(info["n_trees"], dtype=np.uint32)
+        desc = np.zeros(info["desc_len"], dtype=np.uint32)
+        rows = np.zeros((info["n_normals"], info["normal_row_bytes"]), dtype=np.uint8) if normals else None
+        hdrs = np.zeros((info["n_normals"], info["normal_header_floats"]), dtype=np.float32) if normals else None
+        _lib.check(_lib.lib().ah_index_export(self._h, _ptr(nodes), _ptr(roots), _ptr(desc), _ptr(rows), _ptr(hdrs)))
+        out = {"nodes": nodes, "roots": roots, "descendants": desc}
+        if normals:
+            out["normal_rows"], out["normal_headers"] = rows, hdrs
+        return out
 
     def suspend(self) -> None:
         """ah_index_suspend: give up the hold on the dataset, so that Dataset.update_vectors goes through; until resume()

@@ -87,6 +87,7 @@ class TreeStore:
         self.roots: List[int] = []
         self._next = 0
         self._available: List[int] = []
+        self.last_import: Dict[int, int] = {}  # import_tree: forest node -> store id of the tree it imported last
 
     def begin_build(self) -> None:
         """`ConcurrentNodeIds::new(used_tree_node)` (src/parallel.rs:222-237, src/writer.rs:516-518): taken BEFORE the
@@ -177,6 +178,7 @@ class TreeStore:
                 hdr, vec = normal if normal is not None else (np.zeros(forest.distance.header_size() // 4, np.float32), None)
                 self.nodes[ids[i]] = ("S", ids[int(nd["left"])], ids[int(nd["right"])], hdr,
                                       None if vec is None else vec.tobytes())
+        self.last_import = ids
         return ids[int(forest.roots[tree])]
 
     def import_streamed_tree(self, streamed, tree: int, root_id: Optional[int] = None) -> int:
@@ -273,6 +275,8 @@ class _IndexState:
         self.index = None    # arroy_amd.Index: dataset + tree nodes resident in HBM
         self._keep = None    # arrays the index view was built from
         self.device_deletes = 0  # builds that took the updated items out of the trees on the device (Index.delete_items)
+        self.device_inserts = 0  # builds that ended with the resident index still serving (Index.insert_items / graft)
+        self.index_uploads = 0   # indexes made from a whole view of the store (every node, id and normal uploaded)
 
 
 class Database:
@@ -347,6 +351,8 @@ class ArroyBuilder:
         self._cancel: Optional[Callable[[], bool]] = None
         self._progress: Optional[Callable] = None
         self.device_delete = True  # False: the removal of updated items always on the host (what the tests compare with)
+        # False: the index that serves the searches after an incremental build is always made from a view of the whole store
+        self.device_insert = True
 
     def n_trees(self, n: int) -> "ArroyBuilder":
         self._n_trees = int(n)
@@ -431,14 +437,18 @@ class ArroyBuilder:
                 n_trees = target_n_trees(self._n_trees, w.dimensions, n, 0)
                 self._add_trees(ds, st.trees, n_trees, split_after)
             else:
-                self._incremental(ds, st, ids, split_after, resident)
+                kept = self._incremental(ds, st, ids, split_after, resident)
+                if kept is not None:  # the resident index has followed the store: it serves the searches from here on
+                    st.index, st._keep, resident = resident, kept, None
+                    st.device_inserts += 1
         finally:
             if resident is not None:
                 resident.close()  # (a second close is a no-op: _incremental closes it when it is done with it)
-        if n:
+        if n and st.index is None:
             view, keep = st.trees.to_view(dist, w.dimensions)
             from .dataset import Index
             st.index, st._keep = Index(ds, None, view=view), keep
+            st.index_uploads += 1
         st.metadata = {"dimensions": w.dimensions, "items": [int(i) for i in ids], "roots": list(st.trees.roots),
                        "distance": dist.name}  # src/writer.rs:611-626
         st.updated.clear()
@@ -471,7 +481,9 @@ class ArroyBuilder:
     def _seeds(self, count: int) -> List[int]:
         return [self._rng.getrandbits(64) for _ in range(count)]  # one RNG per task (src/writer.rs:575,795)
 
-    def _add_trees(self, ds: Dataset, trees: TreeStore, count: int, split_after: int) -> None:
+    def _add_trees(self, ds: Dataset, trees: TreeStore, count: int, split_after: int, grafted=None) -> None:
+        """`grafted(forest, maps)`: called after the trees of every forest are in the store, with the forest node -> store id
+        map of each of its trees (the one-device path only)."""
         if count <= 0:
             return
         # arroy's formula (src/writer.rs:1371-1380) explodes for >= 10 000 items of fewer than 768 dimensions
@@ -484,11 +496,17 @@ class ArroyBuilder:
         for lo in range(0, count, 4096):
             forest = ds.build_forest(seeds[lo:lo + 4096], split_after=split_after, cancel=self._cancel,
                                      progress=self._progress)
-            for t in range(forest.n_trees):
-                root = trees.next_id()  # roots are allocated before their subtree (src/writer.rs:556-561)
-                trees.import_tree(forest, t, root_id=root)
-                trees.roots.append(root)
-            forest.close()
+            maps = []
+            try:
+                for t in range(forest.n_trees):
+                    root = trees.next_id()  # roots are allocated before their subtree (src/writer.rs:556-561)
+                    trees.import_tree(forest, t, root_id=root)
+                    trees.roots.append(root)
+                    maps.append(trees.last_import)
+                if grafted is not None:
+                    grafted(forest, maps)
+            finally:
+                forest.close()
 
     def _add_trees_group(self, trees: TreeStore, seeds: List[int], split_after: int) -> None:
         """_add_trees on the device group: one streamed build over all members, imported tree by tree in tree order."""
@@ -517,10 +535,11 @@ class ArroyBuilder:
             if watcher_stop is not None:
                 watcher_stop.set()
 
-    def _incremental(self, ds: Dataset, st: "_IndexState", ids: np.ndarray, split_after: int, resident=None) -> None:
+    def _incremental(self, ds: Dataset, st: "_IndexState", ids: np.ndarray, split_after: int, resident=None):
         """`resident`: the last build's Index, resumed on the updated dataset (build() has checked that no tree is dropped): the
-        removal and the routing run on it and it is closed here.  None: the removal on the host, the routing on a throw-away
-        index of the store's view."""
+        removal and the routing run on it.  None: the removal on the host, the routing on a throw-away index of the store's
+        view.  Returns the new `_keep` when `resident` has followed every step and is the index of the store as it is now
+        (device_insert); None when it has been closed here and the caller makes an index from the view."""
         from .dataset import Index
         w, trees, dist = self._w, st.trees, self._w.database.distance
         present = set(int(i) for i in ids)
@@ -550,7 +569,11 @@ class ArroyBuilder:
             gone = set(int(i) for i in to_delete)
             trees.roots = [trees.delete_items(root, gone, split_after)[0] for root in trees.roots]
         trees.roots.sort()
-        # insert_items_in_current_trees (:541-542): one ah_route_items call for all trees
+        # insert_items_in_current_trees (:541-542): one call for all trees.  On the device path (Index.insert_items) the
+        # resident index takes the ids into its lists itself and then follows the store through every later step
+        # (Index.graft), so that it serves the searches after this build; any failure of that path leaves the host path,
+        # which ends with an index made from the view.
+        follow = resident is not None and self.device_insert
         grown: Dict[int, List[int]] = {}
         if to_insert.size and trees.roots:
             if resident is None:
@@ -558,27 +581,70 @@ class ArroyBuilder:
                 dense = keep[4]
                 resident = Index(ds, None, view=view)
             back = {i: nid for nid, i in dense.items()}
+            seeds = self._seeds(len(trees.roots))
+            delta = None
+            if follow:
+                try:
+                    delta = resident.insert_items(to_insert, seeds)
+                except _lib.ArroyHipError:
+                    follow = False
+            if delta is not None:
+                trees.apply_delta(delta, dense)
+                grown = {back[int(i)]: [] for i in delta["put_index"]}
+            else:
+                try:
+                    leaf_of = resident.route_items(to_insert, seeds)
+                finally:
+                    resident.close()
+                    resident = None
+                for t in range(leaf_of.shape[0]):
+                    for i, leaf in enumerate(leaf_of[t]):
+                        grown.setdefault(back[int(leaf)], []).append(int(to_insert[i]))
+                for nid, extra in grown.items():
+                    trees.nodes[nid] = ("D", np.union1d(trees.nodes[nid][1], np.array(extra, dtype=np.uint32)).astype(np.uint32))
+        follow = follow and resident is not None
+        state = {"dense": dense if follow else None, "ok": follow}
+
+        def graft(forest, maps, targets):
+            """The trees of `forest`, imported with `maps`, join the resident index; its numbering becomes the store's."""
+            if not state["ok"]:
+                return
+            new_dense = {nid: i for i, nid in enumerate(sorted(trees.nodes))}
+            new_index = np.full(len(forest.nodes), 0xFFFFFFFF, dtype=np.uint32)
+            tg = np.full(len(maps), _lib.NEW_ROOT, dtype=np.uint32)
+            for t, ids_of in enumerate(maps):
+                for k, nid in ids_of.items():
+                    new_index[k] = new_dense[nid]
+                if targets is not None:
+                    tg[t] = state["dense"][targets[t]]
+                    new_index[int(forest.roots[t])] = 0xFFFFFFFF
             try:
-                leaf_of = resident.route_items(to_insert, self._seeds(len(trees.roots)))
-            finally:
-                resident.close()
-                resident = None
-            for t in range(leaf_of.shape[0]):
-                for i, leaf in enumerate(leaf_of[t]):
-                    grown.setdefault(back[int(leaf)], []).append(int(to_insert[i]))
-            for nid, extra in grown.items():
-                trees.nodes[nid] = ("D", np.union1d(trees.nodes[nid][1], np.array(extra, dtype=np.uint32)).astype(np.uint32))
+                resident.graft(forest.view_struct(), tg, new_index)
+                state["dense"] = new_dense
+            except _lib.ArroyHipError:
+                state["ok"] = False
         # the descendants the routing touched and that no longer fit (`fit_in_descendant`, :474-477, 787-795) are
         # re-split (incremental_index_large_descendant, :660-739); untouched ones are left alone, whatever their size
         large = [nid for nid in sorted(grown) if len(trees.nodes[nid][1]) > split_after]
         if large:
             forest = ds.build_subtrees([trees.nodes[nid][1] for nid in large], self._seeds(len(large)), split_after)
+            maps = []
             for t, nid in enumerate(large):
                 trees.import_tree(forest, t, root_id=nid)  # the sub-tree's root keeps the descendant's id (:693-702)
+                maps.append(trees.last_import)
+            graft(forest, maps, large)
+            forest.close()
+        # missing trees (:556-561)
+        missing = want - len(trees.roots)
+        if missing > 0 and self._group is not None:
+            state["ok"] = False  # (a group build streams its trees: the index is made from the view afterwards)
+        self._add_trees(ds, trees, missing, split_after, grafted=(lambda f, m: graft(f, m, None)) if state["ok"] else None)
+        if state["ok"]:
+            live = state["dense"]
+            return (None, None, None, None, {nid: live[nid] for nid in trees.nodes})
         if resident is not None:
             resident.close()
-        # missing trees (:556-561)
-        self._add_trees(ds, trees, want - len(trees.roots), split_after)
+        return None
 
 
 class Reader:

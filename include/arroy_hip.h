@@ -738,6 +738,71 @@ AH_API int ah_index_delete_items(ah_index *index, const uint32_t *sorted_ids, si
 AH_API int ah_index_delta_get(const ah_index_delta *d, ah_index_delta_view *out);
 AH_API int ah_index_delta_destroy(ah_index_delta *d);
 
+/* ------------------------------------------------------------------------------------------
+ * Inserts and grafts on a resident index (ABI v7 additions: look the symbols up).  The other tree steps of an incremental
+ * `Writer::build`, applied to the index where it lives: with ah_index_delete_items they make the index of build N serve
+ * build N + 1 and the searches after it, and only the normals of the new split nodes ever travel to the device.
+ *
+ * The rules of ah_index_delete_items hold for both calls: all or nothing (a bad argument or a failed allocation leaves the
+ * index as it was, searchable); refused (AH_ERR_INVALID_ARGUMENT) while the index has live filters or is suspended; not
+ * concurrent with any other call on the same index.
+ *
+ * ah_index_insert_items — `insert_items_in_descendants_from_frozen_reader` (src/writer.rs:1398-1459) for every tree at once.
+ * Every id is routed exactly as ah_route_items routes it (the same landing nodes, the same coin at `normal: None` nodes,
+ * keyed by tree_seeds[t]), and every Descendants node an id landed in becomes `descendants | to_insert`
+ * (src/writer.rs:1412): ascending, an id the list already holds is not added twice.  `sorted_ids` strictly ascending; every
+ * id must be a row of the index's dataset (the first that is not is named, AH_ERR_INVALID_ARGUMENT); 0xFFFFFFFF is a legal
+ * id; n == 0 is legal and gives an empty delta.  The descendants are rewritten into new memory; node indices, free slots,
+ * roots and normals do not change.  The delta (ah_index_delta_get): n_removed = 0; `put` / `put_index` are the Descendants
+ * nodes an id landed in, ascending, with their new lists in `desc` — a node is put even when it held every id it received,
+ * as the reference inserts it into `descendants_to_update` regardless; `roots` is the current order.  Which nodes outgrew
+ * `split_after` the host reads from the counts.  A node that receives more than 4096 ids in one call is sorted by one block
+ * in device memory: correct, and slow only there.
+ *
+ * ah_index_graft — adds the trees of `view` (typically what ah_forest_view_get returns for the forest of
+ * ah_build_subtrees or ah_build_forest) to the index: `incremental_index_large_descendant` (src/writer.rs:660-739, the
+ * sub-tree's root keeping the descendant's id, :693-702) and the added trees (:556-561) in one operation.  targets[t] is
+ * the index of an in-use Descendants node that the root of tree t replaces, or AH_NEW_ROOT: new roots are appended
+ * to the index's roots in view order.  Node identity is the tie-break of every descent and the host hands node ids out
+ * through `ConcurrentNodeIds`, which reuses freed ids first (src/parallel.rs:222-254), so new nodes interleave with old
+ * ones: the graft renumbers.  new_index[k] is the final index of view node k; the final indices run over [0, N'),
+ * N' = nodes in use before the call + view nodes that are not replacing roots; a replacing root takes its target's place
+ * and its new_index entry must be 0xFFFFFFFF; the existing in-use nodes fill the positions not named, in their current
+ * relative order.  new_index == NULL: the new nodes follow all existing ones, in view order.  Afterwards the index has no
+ * free slots and is what ah_index_create_from_view makes of the host's store listed in ascending id order: the same nodes,
+ * roots and descendants (the normals are the same rows under other row numbers: the new ones are appended behind the old
+ * ones, and rows orphaned by earlier deletes or grafts are not reclaimed).  out_new_of_old (may be NULL): one word per
+ * node slot before the call, the node's new index, 0xFFFFFFFF for a free slot and for nothing else (a replaced target maps
+ * to the place its sub-tree's root took).
+ * Checked before anything is touched: the view (as ah_index_create_from_view checks it); targets distinct, in use and
+ * Descendants nodes; new_index values distinct and < N'.  NOT checked: that the ids of a replaced node are the ids of its
+ * sub-tree — that is the host's contract, as in the reference.
+ * ---------------------------------------------------------------------------------------- */
+AH_API int ah_index_insert_items(ah_index *index, const uint32_t *sorted_ids, size_t n, const uint64_t *tree_seeds,
+                                 ah_index_delta **out_delta);
+#define AH_NEW_ROOT 0xFFFFFFFFu
+AH_API int ah_index_graft(ah_index *index, const ah_forest_view *view, const uint32_t *targets, const uint32_t *new_index,
+                          uint32_t *out_new_of_old);
+
+/* The index as it is on the device, for tests that compare structure and for a host that audits a long-lived index.  Reads
+ * only; refused while the index is suspended.  ah_index_export_info gives the sizes of the caller's buffers;
+ * ah_index_export fills those that are not NULL: nodes[n_nodes] (kind 0 = a free slot; a split node's `offset` is its
+ * normal ROW, not a byte offset; a Descendants node's `offset` / `count` index `descendants`; tree and depth are 0),
+ * roots[n_trees], descendants[desc_len], normal_rows[n_normals x normal_row_bytes] (the device's padded rows) and
+ * normal_headers[n_normals x normal_header_floats]. */
+typedef struct ah_index_info {
+    uint64_t n_nodes;
+    uint64_t desc_len;
+    uint32_t n_trees;
+    uint32_t n_normals;
+    uint64_t normal_row_bytes;
+    uint32_t normal_header_floats;
+    uint32_t reserved;
+} ah_index_info;
+AH_API int ah_index_export_info(const ah_index *index, ah_index_info *out);
+AH_API int ah_index_export(ah_index *index, ah_node *nodes, uint32_t *roots, uint32_t *descendants, void *normal_rows,
+                           float *normal_headers);
+
 /* An index outlives an update of its dataset.  An ah_index stores ITEM IDS, never row positions — its descendants are a
  * copy of the view's ids and every kernel goes from an id to its row through the dataset as it is at the time of the
  * call — so nothing in it goes stale when ah_dataset_update_* moves rows.  ah_index_suspend gives up the index's hold on
