@@ -67,6 +67,18 @@ class AhIndexDeltaView(C.Structure):
                 ("desc_len", C.c_uint64), ("n_trees", C.c_uint32), ("roots", C.POINTER(C.c_uint32))]
 
 
+class AhIndexFootprint(C.Structure):
+    _fields_ = [("n_nodes", C.c_uint64), ("free_slots", C.c_uint64), ("n_normals", C.c_uint64), ("live_normals", C.c_uint64),
+                ("normals_cap", C.c_uint64), ("desc_len", C.c_uint64), ("device_bytes", C.c_uint64)]
+
+
+class AhIndexCompactStats(C.Structure):
+    _fields_ = [("nodes_before", C.c_uint64), ("nodes_after", C.c_uint64), ("normals_before", C.c_uint64),
+                ("normals_after", C.c_uint64), ("normals_cap_before", C.c_uint64), ("normals_cap_after", C.c_uint64),
+                ("device_bytes_before", C.c_uint64), ("device_bytes_after", C.c_uint64), ("moved", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
 class AhIndexInfo(C.Structure):
     _fields_ = [("n_nodes", C.c_uint64), ("desc_len", C.c_uint64), ("n_trees", C.c_uint32), ("n_normals", C.c_uint32),
                 ("normal_row_bytes", C.c_uint64), ("normal_header_floats", C.c_uint32), ("reserved", C.c_uint32)]
@@ -232,6 +244,9 @@ SIGNATURES = {
     "ah_index_graft": (C.c_int, [_VP, C.POINTER(AhForestView), _U32P, _U32P, _U32P]),
     "ah_index_export_info": (C.c_int, [_VP, C.POINTER(AhIndexInfo)]),
     "ah_index_export": (C.c_int, [_VP, _VP, _U32P, _U32P, _VP, _F32P]),
+    # what a resident index holds, and the removal of its free slots and orphaned normal rows
+    "ah_index_footprint_get": (C.c_int, [_VP, C.POINTER(AhIndexFootprint)]),
+    "ah_index_compact": (C.c_int, [_VP, _U32P, C.POINTER(AhIndexCompactStats)]),
     "ah_index_suspend": (C.c_int, [_VP]),
     "ah_index_resume": (C.c_int, [_VP, _VP]),
     "ah_bench_scan": (C.c_int, [_VP, C.c_uint32, C.c_uint64, C.c_uint32, _F32P, C.POINTER(C.c_double)]),

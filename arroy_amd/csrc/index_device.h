@@ -37,6 +37,9 @@ struct ah_index {
     float *d_nhdrs = nullptr;
     // rows d_nrows / d_nhdrs have room for (>= n_normals): ah_index_graft appends into the spare ones and grows geometrically
     uint32_t normals_cap = 0;
+    // the index is what ah_index_create_from_view makes of its forest (no free slot, no orphaned or spare normal row, every row
+    // in node order): true from its creation and after ah_index_compact, until a delete or a graft
+    bool compacted = true;
     uint32_t n_trees = 0, n_nodes = 0, n_normals = 0, max_desc = 0;
     uint32_t n_leaves = 0;  // Descendants nodes (desc_len / n_leaves: the mean leaf, what the small-submission gate estimates with)
     uint64_t desc_len = 0;

@@ -1,5 +1,6 @@
-// index_update.hip — ah_index_delete_items / ah_index_insert_items / ah_index_graft / ah_index_export / ah_index_suspend /
-// ah_index_resume (include/arroy_hip.h).  The inserts and grafts are described above their kernels; the delete is the part of an
+// index_update.hip — ah_index_delete_items / ah_index_insert_items / ah_index_graft / ah_index_compact / ah_index_footprint_get /
+// ah_index_export / ah_index_suspend / ah_index_resume (include/arroy_hip.h).  The inserts, the grafts and the compaction are
+// described above their kernels; the delete is the part of an
 // incremental `Writer::build` that takes the updated ids out of every tree (`delete_items_from_trees`, src/writer.rs:978-1114)
 // done where the forest lives, so that the index of the last build serves the routing of the next one instead of being
 // uploaded again.
@@ -749,6 +750,136 @@ __global__ __launch_bounds__(kIxBlock) void k_graft_peek(const DNode *__restrict
     for (uint64_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) kinds[i] = nodes[which[i]].kind;
 }
 
+// ---- compaction ---------------------------------------------------------------------------------------------------------------
+// ah_index_compact: the free node slots, the normal rows no node names any more and the spare rows go, and the index becomes what
+// ah_index_create_from_view makes of the forest as it is ("Compaction of a resident index"); every pass reads the
+// index and writes new memory only:
+//   1. flags     per node slot: in use, and in-use split node with a normal; two exclusive scans give every node its new index
+//                (the rank d_rank holds) and every such node its new row; how many rows are not where a fresh index has them.
+//                ah_index_footprint_get stops here;
+//   2. nodes     a thread per in-use node writes it at its new index, children and row remapped; the roots; the old row of
+//                every new row;
+//   3. rows      a wave per new row copies row and header from the old arrays.
+enum CCtl { CCTL_ERR = 0, CCTL_USED, CCTL_LIVE, CCTL_MISPLACED, CCTL_WORDS };
+
+struct CompactArgs {
+    const DNode *nodes;
+    uint32_t n_nodes;
+    uint32_t old_rows;     // n_normals before the call
+    uint32_t *new_index;   // n_nodes + 1: in-use flags -> (scan) in-use nodes below
+    uint32_t *new_row;     // n_nodes + 1: flags of the in-use split nodes with a normal -> (scan) such nodes below
+    uint32_t *ctl;
+    uint32_t n_used, n_live;  // what the scans gave (set before the passes that store through them)
+};
+
+typedef uint32_t u32x4_c __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ bool owns_row(uint32_t kind) { return (kind & 0xFFu) == AH_NODE_SPLIT && (kind & 0x100u); }
+
+__global__ __launch_bounds__(kIxBlock) void k_compact_flags(CompactArgs a) {
+    const uint32_t stride = gridDim.x * blockDim.x;
+    for (uint64_t node = blockIdx.x * blockDim.x + threadIdx.x; node < a.n_nodes; node += stride) {
+        const uint32_t kind = a.nodes[node].kind;
+        a.new_index[node] = kind != 0 ? 1u : 0u;
+        a.new_row[node] = owns_row(kind) ? 1u : 0u;
+    }
+}
+
+// (new_row: scanned) the nodes whose row is not the row a fresh index gives them
+__global__ __launch_bounds__(kIxBlock) void k_compact_placed(CompactArgs a) {
+    const uint32_t stride = gridDim.x * blockDim.x;
+    for (uint64_t node = blockIdx.x * blockDim.x + threadIdx.x; node < a.n_nodes; node += stride) {
+        const DNode nd = a.nodes[node];
+        if (owns_row(nd.kind) && nd.c != a.new_row[node]) atomicOr(&a.ctl[CCTL_MISPLACED], 1u);
+    }
+}
+
+// nodes: the slots [lo, hi); every position of the new array is written by exactly one in-use node
+__global__ __launch_bounds__(kIxBlock) void k_compact_nodes(CompactArgs a, uint32_t lo, uint32_t hi, DNode *__restrict__ out,
+                                                            uint32_t *__restrict__ src_of_row, uint32_t *__restrict__ map) {
+    const uint32_t stride = gridDim.x * blockDim.x;
+    for (uint64_t node = (uint64_t)lo + blockIdx.x * blockDim.x + threadIdx.x; node < hi; node += stride) {
+        DNode nd = a.nodes[node];
+        if (nd.kind == 0) {
+            if (map) map[node] = kNone;
+            continue;
+        }
+        const uint32_t p = a.new_index[node];
+        if (map) map[node] = p;
+        if (p >= a.n_used) {
+            atomicOr(&a.ctl[CCTL_ERR], 1u);
+            continue;
+        }
+        if ((nd.kind & 0xFFu) == AH_NODE_SPLIT) {
+            if (nd.a >= a.n_nodes || nd.b >= a.n_nodes || a.nodes[nd.a].kind == 0 || a.nodes[nd.b].kind == 0) {  // (a child in a free slot)
+                atomicOr(&a.ctl[CCTL_ERR], 2u);
+                continue;
+            }
+            nd.a = a.new_index[nd.a];
+            nd.b = a.new_index[nd.b];
+            if (nd.kind & 0x100u) {
+                const uint32_t r = a.new_row[node];
+                if (r >= a.n_live || nd.c >= a.old_rows) {
+                    atomicOr(&a.ctl[CCTL_ERR], 4u);
+                    continue;
+                }
+                src_of_row[r] = nd.c;
+                nd.c = r;
+            } else {
+                nd.c = 0;
+            }
+        } else {
+            nd.c = 0;
+        }
+        out[p] = nd;
+    }
+}
+
+__global__ __launch_bounds__(kIxBlock) void k_compact_roots(CompactArgs a, const uint32_t *__restrict__ roots, uint32_t n_trees,
+                                                            uint32_t *__restrict__ out) {
+    const uint32_t stride = gridDim.x * blockDim.x;
+    for (uint64_t t = blockIdx.x * blockDim.x + threadIdx.x; t < n_trees; t += stride) {
+        const uint32_t r = roots[t];
+        uint32_t p = kNone;
+        if (r < a.n_nodes && a.nodes[r].kind != 0) p = a.new_index[r];
+        if (p >= a.n_used) atomicOr(&a.ctl[CCTL_ERR], 8u);
+        out[t] = p;
+    }
+}
+
+// rows: the new rows [lo, hi), a wave each: 16 bytes a lane a step, four steps in flight, the last one partial (rb is a multiple
+// of 16: f32 rows are whole 128-byte lines, 1-bit rows an even number of 64-bit words); the header floats ride along
+__global__ __launch_bounds__(kIxBlock) void k_compact_rows(const uint8_t *__restrict__ old_rows, const float *__restrict__ old_hdr,
+                                                           const uint32_t *__restrict__ src_of_row, uint32_t n_old_rows, uint64_t lo,
+                                                           uint64_t hi, uint64_t rb, uint32_t hf, uint8_t *__restrict__ rows,
+                                                           float *__restrict__ hdr, uint32_t *ctl) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t n_waves = (uint64_t)gridDim.x * (kIxBlock / 64);
+    for (uint64_t q = lo + (((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6); q < hi; q += n_waves) {
+        const uint32_t from = src_of_row[q];
+        if (from >= n_old_rows) {  // (wave-uniform; the node pass has flagged it)
+            if (lane == 0) atomicOr(&ctl[CCTL_ERR], 16u);
+            continue;
+        }
+        const uint8_t *src = old_rows + (uint64_t)from * rb;
+        uint8_t *dst = rows + q * rb;
+        for (uint64_t c0 = (uint64_t)lane * 16; c0 < rb; c0 += 4 * 64 * 16) {
+            u32x4_c v[4];
+#pragma unroll
+            for (uint32_t k = 0; k < 4; k++) {
+                const uint64_t c = c0 + (uint64_t)k * 64 * 16;
+                if (c < rb) v[k] = __builtin_nontemporal_load(reinterpret_cast<const u32x4_c *>(src + c));
+            }
+#pragma unroll
+            for (uint32_t k = 0; k < 4; k++) {
+                const uint64_t c = c0 + (uint64_t)k * 64 * 16;
+                if (c < rb) __builtin_nontemporal_store(v[k], reinterpret_cast<u32x4_c *>(dst + c));
+            }
+        }
+        if (lane < hf) hdr[q * hf + lane] = old_hdr[(uint64_t)from * hf + lane];
+    }
+}
+
 int alloc(DevMem *m, size_t bytes) {
     const hipError_t e = dev_malloc(&m->p, std::max<size_t>(bytes, 1));
     if (e != hipSuccess) {
@@ -930,6 +1061,7 @@ int delete_impl(ah_index *ix, const uint32_t *ids, size_t n, uint32_t split_afte
         ix->desc_len = desc_len;
         ix->n_leaves = ctl[CTL_LEAVES];
         ix->max_desc = ctl[CTL_MAX_DESC];
+        ix->compacted = false;
     }
     if (timing) {
         auto secs = [](std::chrono::steady_clock::time_point x, std::chrono::steady_clock::time_point y) {
@@ -1332,10 +1464,185 @@ int graft_impl(ah_index *ix, const ah_forest_view &v, const uint32_t *targets, c
         ix->desc_len = desc_len;
         ix->n_leaves = ctl[GCTL_LEAVES];
         ix->max_desc = ctl[GCTL_MAX_DESC];
+        ix->compacted = false;
     }
     if (tun(TUN_TIMING) != 0)
         fprintf(stderr, "[ah] index graft: %u view nodes (%u replacing roots, %u new roots, %u normals) into %u nodes -> %u nodes, %u stored ids\n",
                 n_view, n_repl, n_added, n_vnormals, n_used, n_new, desc_len);
+    return AH_OK;
+}
+
+// HBM an index of these sizes holds: what ah_index_create_from_view obtains, plus the ranks when a delete has left some
+uint64_t index_device_bytes(const ah_index *ix, uint64_t n_nodes, bool rank, uint64_t normals_cap) {
+    const uint64_t per_row = ix->ds->row_bytes() + (uint64_t)header_floats(ix->ds->metric) * 4;
+    return std::max<uint64_t>(1, n_nodes) * sizeof(DNode) + std::max<uint64_t>(1, ix->n_trees) * 4 + (rank ? (n_nodes + 1) * 4 : 0) +
+           std::max<uint64_t>(1, ix->desc_len) * 4 + normals_cap * per_row;
+}
+
+// pass 1 of the compaction, which is all of ah_index_footprint_get: `work` gets [new_index n + 1][new_row n + 1][scan tiles][ctl]
+// [extra words]; ctl[CCTL_*] is read back
+int compact_count(ah_index *ix, hipStream_t s, DevMem *work, size_t extra_words, CompactArgs *a, uint32_t **extra, uint32_t *ctl) {
+    const uint32_t nn = ix->n_nodes;
+    const size_t per_node = (size_t)nn + 1;
+    const size_t scan_tiles = (nn + kScanTile - 1) / kScanTile + 1;
+    AH_TRY(alloc(work, (2 * per_node + scan_tiles + CCTL_WORDS + extra_words) * 4));
+    uint32_t *w = work->as<uint32_t>();
+    a->nodes = ix->d_nodes;
+    a->n_nodes = nn;
+    a->old_rows = ix->n_normals;
+    a->new_index = w;
+    a->new_row = w + per_node;
+    uint32_t *tile_sums = w + 2 * per_node;
+    a->ctl = tile_sums + scan_tiles;
+    *extra = a->ctl + CCTL_WORDS;
+    AH_HIP(hipMemsetAsync(a->ctl, 0, CCTL_WORDS * 4, s));
+    if (nn) hipLaunchKernelGGL(k_compact_flags, dim3(grid_of(nn, kIxBlock, 4096)), dim3(kIxBlock), 0, s, *a);
+    launch_exclusive_scan(a->new_index, nn, tile_sums, a->ctl + CCTL_USED, s);
+    launch_exclusive_scan(a->new_row, nn, tile_sums, a->ctl + CCTL_LIVE, s);
+    if (nn) hipLaunchKernelGGL(k_compact_placed, dim3(grid_of(nn, kIxBlock, 4096)), dim3(kIxBlock), 0, s, *a);
+    AH_HIP(hipGetLastError());
+    AH_HIP(hipMemcpyAsync(ctl, a->ctl, CCTL_WORDS * 4, hipMemcpyDeviceToHost, s));
+    AH_HIP(hipStreamSynchronize(s));
+    AH_REQUIRE(ctl[CCTL_USED] <= nn && ctl[CCTL_LIVE] <= ctl[CCTL_USED], AH_ERR_DEVICE, "the index counts more nodes in use than it has");
+    a->n_used = ctl[CCTL_USED];
+    a->n_live = ctl[CCTL_LIVE];
+    return AH_OK;
+}
+
+int footprint_impl(ah_index *ix, ah_index_footprint *out) {
+    ah_dataset *ds = ix->ds;
+    AH_HIP(hipSetDevice(ds->device));
+    ContextLease lease(ds);
+    AH_REQUIRE(lease.c, AH_ERR_DEVICE, "cannot create a HIP stream");
+    DevMem work;
+    CompactArgs a{};
+    uint32_t *extra = nullptr;
+    uint32_t ctl[CCTL_WORDS] = {};
+    AH_TRY(compact_count(ix, lease.c->stream, &work, 0, &a, &extra, ctl));
+    out->n_nodes = ix->n_nodes;
+    out->free_slots = ix->n_nodes - a.n_used;
+    out->n_normals = ix->n_normals;
+    out->live_normals = a.n_live;
+    out->normals_cap = ix->normals_cap;
+    out->desc_len = ix->desc_len;
+    out->device_bytes = index_device_bytes(ix, ix->n_nodes, ix->d_rank != nullptr, ix->normals_cap);
+    return AH_OK;
+}
+
+int compact_impl(ah_index *ix, uint32_t *out_new_of_old, ah_index_compact_stats *stats) {
+    auto now = [] { return std::chrono::steady_clock::now(); };
+    const bool timing = tun(TUN_TIMING) != 0;
+    ah_dataset *ds = ix->ds;
+    AH_HIP(hipSetDevice(ds->device));
+    ContextLease lease(ds);
+    AH_REQUIRE(lease.c, AH_ERR_DEVICE, "cannot create a HIP stream");
+    const hipStream_t s = lease.c->stream;
+    auto phase_end = [&]() -> std::chrono::steady_clock::time_point {
+        if (timing) (void)hipStreamSynchronize(s);
+        return now();
+    };
+    const auto t0 = now();
+    const uint32_t nn = ix->n_nodes, n_trees = ix->n_trees, old_rows = ix->n_normals, old_cap = ix->normals_cap;
+    ah_index_compact_stats st{};
+    st.nodes_before = st.nodes_after = nn;
+    st.normals_before = st.normals_after = old_rows;
+    st.normals_cap_before = st.normals_cap_after = old_cap;
+    st.device_bytes_before = st.device_bytes_after = index_device_bytes(ix, nn, ix->d_rank != nullptr, old_cap);
+    auto nothing_to_do = [&]() {
+        if (out_new_of_old)
+            for (uint32_t i = 0; i < nn; i++) out_new_of_old[i] = i;
+        if (stats) *stats = st;
+        return AH_OK;
+    };
+    // a fresh index, or one compacted and not deleted from or grafted on since: the host knows, and nothing is allocated
+    if (ix->compacted) return nothing_to_do();
+    // 1. flags and scans
+    DevMem work, new_nodes, new_roots, new_rows, new_hdrs, row_src;
+    CompactArgs a{};
+    uint32_t *d_map = nullptr;
+    uint32_t ctl[CCTL_WORDS] = {};
+    AH_TRY(compact_count(ix, s, &work, out_new_of_old ? nn : 0, &a, &d_map, ctl));
+    if (!out_new_of_old) d_map = nullptr;
+    const uint32_t n_used = a.n_used, n_live = a.n_live;
+    const uint32_t new_cap = std::max<uint32_t>(1, n_live);
+    const auto t_count = now();
+    if (n_used == nn && n_live == old_rows && ctl[CCTL_MISPLACED] == 0 && old_cap == new_cap && !ix->d_rank) {
+        // no free slot, no dead row, every row where a fresh index has it, no spare row, no ranks: nothing but the scratch of
+        // the count was obtained, and it goes back here
+        ix->compacted = true;
+        return nothing_to_do();
+    }
+    // every other buffer; kernels write only into these
+    const uint32_t hf = header_floats(ds->metric);
+    const size_t row_bytes = ds->row_bytes();
+    AH_TRY(alloc(&new_nodes, std::max<size_t>(1, n_used) * sizeof(DNode)));
+    AH_TRY(alloc(&new_roots, std::max<size_t>(1, n_trees) * 4));
+    AH_TRY(alloc(&new_rows, (size_t)new_cap * row_bytes));
+    AH_TRY(alloc(&new_hdrs, (size_t)new_cap * hf * 4));
+    AH_TRY(alloc(&row_src, (size_t)new_cap * 4));
+    std::vector<uint32_t> map_out(out_new_of_old ? nn : 0);
+    AH_HIP(hipMemsetAsync(row_src.p, 0, (size_t)new_cap * 4, s));
+    // 2. nodes, in launches of at most AH_LAUNCH_MAX_ITEMS slots
+    const uint64_t span = (uint64_t)std::max<long long>(1, tun(TUN_LAUNCH_MAX_ITEMS));
+    for (uint64_t lo = 0; lo < nn; lo += span) {
+        const uint32_t hi = (uint32_t)std::min<uint64_t>(nn, lo + span);
+        hipLaunchKernelGGL(k_compact_nodes, dim3(grid_of(hi - lo, kIxBlock, 4096)), dim3(kIxBlock), 0, s, a, (uint32_t)lo, hi, new_nodes.as<DNode>(),
+                           row_src.as<uint32_t>(), d_map);
+    }
+    if (n_trees)
+        hipLaunchKernelGGL(k_compact_roots, dim3(grid_of(n_trees, kIxBlock, 1024)), dim3(kIxBlock), 0, s, a, (const uint32_t *)ix->d_roots, n_trees,
+                           new_roots.as<uint32_t>());
+    AH_HIP(hipGetLastError());
+    const auto t_nodes = phase_end();
+    // 3. rows, in launches of at most AH_LAUNCH_MAX_ITEMS rows
+    for (uint64_t lo = 0; lo < n_live; lo += span) {
+        const uint64_t hi = std::min<uint64_t>(n_live, lo + span);
+        hipLaunchKernelGGL(k_compact_rows, dim3(grid_of(hi - lo, kIxBlock / 64, 8192)), dim3(kIxBlock), 0, s, (const uint8_t *)ix->d_nrows,
+                           (const float *)ix->d_nhdrs, row_src.as<const uint32_t>(), old_rows, lo, hi, (uint64_t)row_bytes, hf, new_rows.as<uint8_t>(),
+                           new_hdrs.as<float>(), a.ctl);
+    }
+    AH_HIP(hipGetLastError());
+    if (out_new_of_old && nn) AH_HIP(hipMemcpyAsync(map_out.data(), d_map, (size_t)nn * 4, hipMemcpyDeviceToHost, s));
+    AH_HIP(hipMemcpyAsync(ctl, a.ctl, sizeof(ctl), hipMemcpyDeviceToHost, s));
+    AH_HIP(hipStreamSynchronize(s));
+    AH_REQUIRE(ctl[CCTL_ERR] == 0, AH_ERR_DEVICE, "the index compaction found the index inconsistent (%u): the index is unchanged", ctl[CCTL_ERR]);
+    const auto t_rows = now();
+    {
+        // commit: nothing here can fail.  The old arrays go into the DevMems, which free them (dev_free waits for the device).
+        NoFailScope no_fail;
+        if (out_new_of_old && nn) memcpy(out_new_of_old, map_out.data(), (size_t)nn * 4);
+        std::swap(new_nodes.p, *reinterpret_cast<void **>(&ix->d_nodes));
+        std::swap(new_roots.p, *reinterpret_cast<void **>(&ix->d_roots));
+        std::swap(new_rows.p, ix->d_nrows);
+        std::swap(new_hdrs.p, *reinterpret_cast<void **>(&ix->d_nhdrs));
+        DevMem old_rank;
+        old_rank.p = ix->d_rank;
+        ix->d_rank = nullptr;
+        const bool bq = metric_is_bq(ds->metric);
+        ix->nv.rows_f32 = bq ? nullptr : reinterpret_cast<const float *>(ix->d_nrows);
+        ix->nv.rows_bq = bq ? reinterpret_cast<const uint64_t *>(ix->d_nrows) : nullptr;
+        ix->nv.headers = ix->d_nhdrs;
+        ix->n_nodes = n_used;
+        ix->n_normals = n_live;
+        ix->nv.n = n_live;
+        ix->normals_cap = new_cap;
+        ix->compacted = true;
+    }
+    st.nodes_after = n_used;
+    st.normals_after = n_live;
+    st.normals_cap_after = new_cap;
+    st.device_bytes_after = index_device_bytes(ix, n_used, false, new_cap);
+    st.moved = 1;
+    if (stats) *stats = st;
+    if (timing) {
+        auto secs = [](std::chrono::steady_clock::time_point x, std::chrono::steady_clock::time_point y) {
+            return std::chrono::duration<double>(y - x).count();
+        };
+        fprintf(stderr, "[ah] index compact: %u -> %u nodes, %u -> %u normal rows (room for %u -> %u), %llu -> %llu bytes: "
+                        "flags and scans %.6f s, nodes %.6f s, rows %.6f s, swap %.6f s\n",
+                nn, n_used, old_rows, n_live, old_cap, new_cap, (unsigned long long)st.device_bytes_before,
+                (unsigned long long)st.device_bytes_after, secs(t0, t_count), secs(t_count, t_nodes), secs(t_nodes, t_rows), secs(t_rows, now()));
+    }
     return AH_OK;
 }
 
@@ -1397,6 +1704,24 @@ int ah_index_graft(ah_index *ix, const ah_forest_view *view, const uint32_t *tar
     AH_REQUIRE(v.n_trees == 0 || targets, AH_ERR_INVALID_ARGUMENT, "targets is NULL");
     DeviceRestore restore_device;
     return graft_impl(ix, v, targets, new_index, out_new_of_old);
+    AH_GUARDED_END
+}
+
+int ah_index_footprint_get(ah_index *ix, ah_index_footprint *out) {
+    AH_GUARDED("ah_index_footprint_get")
+    AH_REQUIRE(ix && ix->ds, AH_ERR_INVALID_ARGUMENT, "index is NULL");
+    AH_REQUIRE(out, AH_ERR_INVALID_ARGUMENT, "out is NULL");
+    AH_INDEX_LIVE(ix);
+    DeviceRestore restore_device;
+    return footprint_impl(ix, out);
+    AH_GUARDED_END
+}
+
+int ah_index_compact(ah_index *ix, uint32_t *out_new_of_old, ah_index_compact_stats *out_stats) {
+    AH_GUARDED("ah_index_compact")
+    AH_TRY(index_updatable(ix));
+    DeviceRestore restore_device;
+    return compact_impl(ix, out_new_of_old, out_stats);
     AH_GUARDED_END
 }
 

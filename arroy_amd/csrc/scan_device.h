@@ -1,5 +1,6 @@
 // scan_device.h — an exclusive scan of 32-bit counts in global memory, in three launches: the keep flags of a dataset update
-// (update.hip), the segment sizes and change flags of an index delete (index_update.hip).
+// (update.hip), the segment sizes and change flags of an index delete, the in-use and row flags of an index compaction
+// (index_update.hip).
 #pragma once
 
 #include "common.h"

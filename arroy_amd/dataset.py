@@ -709,6 +709,23 @@ class Index:
             out["normal_rows"], out["normal_headers"] = rows, hdrs
         return out
 
+    def footprint(self) -> dict:
+        """ah_index_footprint_get: node slots and the free ones among them, normal rows in use / live / room for, desc_len and
+        the bytes of HBM the index holds (counted on the device; legal with live filters)."""
+        fp = _lib.AhIndexFootprint()
+        _lib.check(_lib.lib().ah_index_footprint_get(self._h, C.byref(fp)))
+        return {f: int(getattr(fp, f)) for f, _ in _lib.AhIndexFootprint._fields_}
+
+    def compact(self, want_map: bool = False):
+        """ah_index_compact: free node slots, orphaned normal rows and spare rows go; the index becomes what a fresh Index of
+        the forest as it is now would be, node for node and row for row.  Returns the stats (sizes before / after, `moved`: 0
+        when there was nothing to do); with want_map (stats, the new index of every old node slot, 0xFFFFFFFF for a free one)."""
+        st = _lib.AhIndexCompactStats()
+        out = np.zeros(self.export_info()["n_nodes"], dtype=np.uint32) if want_map else None
+        _lib.check(_lib.lib().ah_index_compact(self._h, _ptr(out), C.byref(st)))
+        stats = {f: int(getattr(st, f)) for f, _ in _lib.AhIndexCompactStats._fields_ if f != "reserved"}
+        return (stats, out) if want_map else stats
+
     def suspend(self) -> None:
         """ah_index_suspend: give up the hold on the dataset, so that Dataset.update_vectors goes through; until resume()
         every search, route, filter or delete call on this index is refused.  The live filters of the index are closed first,

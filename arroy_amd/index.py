@@ -277,6 +277,18 @@ class _IndexState:
         self.device_deletes = 0  # builds that took the updated items out of the trees on the device (Index.delete_items)
         self.device_inserts = 0  # builds that ended with the resident index still serving (Index.insert_items / graft)
         self.index_uploads = 0   # indexes made from a whole view of the store (every node, id and normal uploaded)
+        self.device_compactions = 0  # builds that ended with a compaction of the resident index (Index.compact)
+
+
+def compaction_due(fp: dict) -> bool:
+    """Whether a resident index with this footprint (Index.footprint) is compacted at the end of a build: more dead normal rows
+    than live ones, more free node slots than nodes in use, or room for more than twice the live rows.  The 1x threshold bounds
+    the normals at twice a fresh index's (apart from the graft's own geometric head-room) and makes the work amortised O(1): a
+    compaction copies `live` rows only after at least `live` rows have died, each of which was uploaded once over a link far
+    slower than HBM.  Derived, not measured."""
+    live = fp["live_normals"]
+    in_use = fp["n_nodes"] - fp["free_slots"]
+    return fp["n_normals"] - live > live or fp["free_slots"] > in_use or fp["normals_cap"] > 2 * max(1, live)
 
 
 class Database:
@@ -353,6 +365,8 @@ class ArroyBuilder:
         self.device_delete = True  # False: the removal of updated items always on the host (what the tests compare with)
         # False: the index that serves the searches after an incremental build is always made from a view of the whole store
         self.device_insert = True
+        # False: the resident index keeps its free node slots and orphaned normal rows whatever they amount to
+        self.device_compact = True
 
     def n_trees(self, n: int) -> "ArroyBuilder":
         self._n_trees = int(n)
@@ -641,7 +655,20 @@ class ArroyBuilder:
         self._add_trees(ds, trees, missing, split_after, grafted=(lambda f, m: graft(f, m, None)) if state["ok"] else None)
         if state["ok"]:
             live = state["dense"]
-            return (None, None, None, None, {nid: live[nid] for nid in trees.nodes})
+            kept = {nid: live[nid] for nid in trees.nodes}
+            if self.device_compact:
+                # the waste of the resident index (Index.footprint) is taken out once it outweighs what is live.  A refusal
+                # (a filter of a Reader still alive) or any other failure is not a failure of the build: Index.compact is
+                # all or nothing, the index stays as it was and stays correct
+                try:
+                    if compaction_due(resident.footprint()):
+                        stats, new_of_old = resident.compact(want_map=True)
+                        if stats["moved"]:
+                            kept = {nid: int(new_of_old[i]) for nid, i in kept.items()}
+                            st.device_compactions += 1
+                except _lib.ArroyHipError:
+                    pass
+            return (None, None, None, None, kept)
         if resident is not None:
             resident.close()
         return None

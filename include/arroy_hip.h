@@ -52,7 +52,8 @@ extern "C" {
                                   a caller that needs them looks the symbols up; so are ah_dataset_packed_info,
                                   ah_dataset_packed_rows and the test aid ah_debug_query_screen_verify;
                                   v7 additions: updates of a finalized dataset (ah_dataset_update_vectors / _records,
-                                  ah_group_update_vectors / _records, the test aid ah_debug_update_paths) */
+                                  ah_group_update_vectors / _records, the test aid ah_debug_update_paths);
+                                  ah_index_footprint_get / ah_index_compact */
 
 /* every entry point is exported from the shared object (it is built with -fvisibility=hidden) */
 #if defined(__GNUC__)
@@ -771,9 +772,9 @@ AH_API int ah_index_delta_destroy(ah_index_delta *d);
  * relative order.  new_index == NULL: the new nodes follow all existing ones, in view order.  Afterwards the index has no
  * free slots and is what ah_index_create_from_view makes of the host's store listed in ascending id order: the same nodes,
  * roots and descendants (the normals are the same rows under other row numbers: the new ones are appended behind the old
- * ones, and rows orphaned by earlier deletes or grafts are not reclaimed).  out_new_of_old (may be NULL): one word per
- * node slot before the call, the node's new index, 0xFFFFFFFF for a free slot and for nothing else (a replaced target maps
- * to the place its sub-tree's root took).
+ * ones, and rows orphaned by earlier deletes or grafts stay until ah_index_compact reclaims them).  out_new_of_old (may be
+ * NULL): one word per node slot before the call, the node's new index, 0xFFFFFFFF for a free slot and for nothing else (a
+ * replaced target maps to the place its sub-tree's root took).
  * Checked before anything is touched: the view (as ah_index_create_from_view checks it); targets distinct, in use and
  * Descendants nodes; new_index values distinct and < N'.  NOT checked: that the ids of a replaced node are the ids of its
  * sub-tree — that is the host's contract, as in the reference.
@@ -802,6 +803,67 @@ typedef struct ah_index_info {
 AH_API int ah_index_export_info(const ah_index *index, ah_index_info *out);
 AH_API int ah_index_export(ah_index *index, ah_node *nodes, uint32_t *roots, uint32_t *descendants, void *normal_rows,
                            float *normal_headers);
+
+/* ------------------------------------------------------------------------------------------
+ * Compaction of a resident index (ABI v7 additions: look the symbols up).  An index that deletes, inserts and grafts keep
+ * resident across builds collects waste no upload clears any more: every split node a delete removes leaves its normal row
+ * behind (3 KB at 768 dimensions), a replaced sub-tree likewise; a delete that no graft follows leaves free node slots, which
+ * every coin of ah_route_items pays for through the ranks and ah_index_export shows as kind 0; and a graft grows the rows
+ * geometrically and never shrinks them.
+ *
+ * ah_index_footprint_get — what the index holds and how much of it is waste.  Reads only: one counting pass over the node
+ * array on the device (a scratch of a few words per node slot for its duration).  Legal with live filters; refused while
+ * the index is suspended.  `device_bytes` is the sum of the arrays as the index asks for them (nodes, roots, the ranks a
+ * delete left, descendants, normal rows and headers at capacity), not what an allocator rounds them to.
+ *
+ * ah_index_compact — removes the waste on the device.  Afterwards the index is what ah_index_create_from_view makes of the
+ * forest as it is now, listed in ascending node order:
+ *   - no free slots; the in-use nodes keep their relative order, a node's new index is the number of in-use nodes below it
+ *     (its rank); children and roots are remapped, the order of the roots stays; the ranks are freed;
+ *   - normal rows are 1:1 with the split nodes that have a normal, in node order: the row of such a node moves to "number
+ *     of in-use split nodes with a normal and a smaller index", the row a fresh index gives it (also when no row is dead
+ *     but a graft appended rows of nodes that interleave with older ones); row and header bytes are copied unchanged;
+ *     n_normals = live rows, and the arrays have room for max(1, n_normals) rows;
+ *   - the descendants are not touched: delete, insert and graft write them in node order with the exact length, and
+ *     removing holes does not change that order;
+ *   - n_leaves, max_desc, desc_len, the search statistics and the int8-stage window stay as they are.
+ * ah_search_batch*, ah_route_items, ah_index_insert_items, ah_index_delete_items and ah_index_graft afterwards return what
+ * they return on that fresh index: ids, distance bits, counts, landing nodes and the coins at `normal: None` nodes (keyed
+ * by the rank, which is now the index).  out_new_of_old (may be NULL): one word per node slot before the call, the node's
+ * new index, 0xFFFFFFFF for a free slot and for nothing else — the convention of ah_index_graft.  out_stats (may be NULL).
+ *
+ * Nothing to do — no free slot, no dead or misplaced row, no spare row, no ranks: AH_OK, moved = 0, out_new_of_old is the
+ * identity.  On a fresh index and directly after a compaction the host knows that, and nothing is allocated or launched;
+ * otherwise the counting pass finds it and gives its scratch back.
+ *
+ * The compaction is NOT in place: rows move towards the front, and a wave would write over a row another wave has yet to
+ * read.  For the duration of the call the index therefore holds, next to its own arrays, the new ones: the live rows and
+ * headers, the in-use nodes and the roots a second time, plus scratch of three words per node slot and one per live row.
+ *
+ * The rules of ah_index_delete_items hold: all or nothing (every buffer is obtained before the first kernel that fills it,
+ * the kernels write new memory only, the pointers are swapped after the last copy has landed; a bad argument or a failed
+ * allocation leaves the index as it was, searchable, holding no extra memory); refused (AH_ERR_INVALID_ARGUMENT) while the
+ * index has live filters or is suspended; not concurrent with any other call on the same index.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct ah_index_footprint {
+    uint64_t n_nodes;        /* node slots */
+    uint64_t free_slots;     /* of them kind == 0 */
+    uint64_t n_normals;      /* normal rows in use by the arrays (what ah_index_export_info reports) */
+    uint64_t live_normals;   /* rows named by an in-use split node with a normal */
+    uint64_t normals_cap;    /* rows the arrays have room for */
+    uint64_t desc_len;
+    uint64_t device_bytes;   /* HBM the index holds: nodes, roots, ranks, descendants, normal rows and headers at capacity */
+} ah_index_footprint;
+AH_API int ah_index_footprint_get(ah_index *index, ah_index_footprint *out);
+typedef struct ah_index_compact_stats {
+    uint64_t nodes_before, nodes_after;
+    uint64_t normals_before, normals_after;     /* n_normals */
+    uint64_t normals_cap_before, normals_cap_after;
+    uint64_t device_bytes_before, device_bytes_after;
+    uint32_t moved;          /* 0: there was nothing to do and nothing was written */
+    uint32_t reserved;
+} ah_index_compact_stats;
+AH_API int ah_index_compact(ah_index *index, uint32_t *out_new_of_old, ah_index_compact_stats *out_stats);
 
 /* An index outlives an update of its dataset.  An ah_index stores ITEM IDS, never row positions — its descendants are a
  * copy of the view's ids and every kernel goes from an id to its row through the dataset as it is at the time of the
