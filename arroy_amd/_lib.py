@@ -151,6 +151,16 @@ class AhFilterStats(C.Structure):
 NO_FILTER = 0xFFFFFFFF  # AH_NO_FILTER: a query of ah_search_batch_filters under no filter
 
 
+class AhFilterCombineStats(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("words", "leaves", "leaves_walked", "ids_walked")]
+
+
+# ah_filter_op (include/arroy_hip.h)
+FILTER_AND, FILTER_OR, FILTER_ANDNOT, FILTER_NOT = 0, 1, 2, 3
+FILTER_OPS = {"and": FILTER_AND, "or": FILTER_OR, "andnot": FILTER_ANDNOT, "not": FILTER_NOT}
+FILTER_COMBINE_MAX = 64
+
+
 class AhStreamNode(C.Structure):
     _fields_ = [("id", C.c_uint32), ("tree", C.c_uint32), ("kind", C.c_uint8), ("has_normal", C.c_uint8), ("reserved", C.c_uint16),
                 ("left", C.c_uint32), ("right", C.c_uint32), ("count", C.c_uint32), ("depth", C.c_uint32),
@@ -235,6 +245,11 @@ SIGNATURES = {
     "ah_search_batch_filters": (C.c_int, [_VP, _F32P, _U32P, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t,
                                           C.POINTER(C.c_void_p), C.c_size_t, _U32P, _U32P, _F32P, _U32P]),
     "ah_index_filter_stats": (C.c_int, [_VP, C.POINTER(AhFilterStats), C.c_int]),
+    # filter expressions on the device, filters from bitmaps
+    "ah_filter_combine": (C.c_int, [C.c_int, C.POINTER(C.c_void_p), C.c_size_t, C.POINTER(C.c_void_p),
+                                    C.POINTER(AhFilterCombineStats)]),
+    "ah_filter_create_bitmap": (C.c_int, [_VP, _U64P, C.c_uint64, C.POINTER(C.c_void_p)]),
+    "ah_filter_export": (C.c_int, [_VP, C.POINTER(C.c_uint64), _U32P, _U32P]),
     # deletes on a resident index; an index kept across an update of its dataset
     "ah_index_delete_items": (C.c_int, [_VP, _U32P, C.c_size_t, C.c_uint32, C.POINTER(C.c_void_p)]),
     "ah_index_delta_get": (C.c_int, [_VP, C.POINTER(AhIndexDeltaView)]),

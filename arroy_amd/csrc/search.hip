@@ -14,6 +14,7 @@
 // with the queue in global memory (capacity = number of nodes, a hard bound: every node is pushed at most
 // once).
 #include <algorithm>
+#include <cassert>
 #include <chrono>
 #include <memory>
 #include <new>
@@ -3501,6 +3502,158 @@ __global__ __launch_bounds__(256) void k_filter_stored(DataView dv, const uint32
     if ((threadIdx.x & 63u) == 0 && c) atomicAdd(out, (unsigned long long)c);
 }
 
+// ---- filter expressions (ah_filter_combine) ----------------------------------------------------------------------------
+// The operands of one ah_filter_combine call, by value in the kernel arguments: their bitmaps (k_filter_combine) or their
+// per-node arrays (k_leaf_kept_combine).  Indexed by a wave-uniform i < n only: scalar loads from the argument segment.
+struct CombineTable {
+    const uint32_t *p[AH_FILTER_COMBINE_MAX];
+};
+// What one ah_filter_combine call counts on the device, in the tail of the new filter's block (8-byte aligned, zeroed with the
+// block): the set bits of the new bitmap, those of them that are rows (sparse ids), and ah_filter_combine_stats.
+enum CombineSlot { CB_LISTED = 0, CB_STORED, CB_LEAVES, CB_LEAVES_WALKED, CB_IDS_WALKED, CB_WORDS };
+
+// The sum of v over the block into *out: reduced per wave, then one 64-bit atomic per block.  Every thread of the block calls.
+__device__ __forceinline__ void block_add_u64(unsigned long long v, unsigned long long *out, unsigned long long *s_part) {
+    for (uint32_t d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
+    const uint32_t wave = threadIdx.x >> 6, n_waves = (blockDim.x + 63u) >> 6;
+    __syncthreads();  // (s_part may still be read from the call before)
+    if ((threadIdx.x & 63u) == 0) s_part[wave] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long t = 0;
+        for (uint32_t w = 0; w < n_waves; w++) t += s_part[w];
+        if (t) atomicAdd(out, t);
+    }
+}
+
+// Four words of operand 0 combined with the same four of the operands 1 .. n - 1.
+template <int OP>
+__device__ __forceinline__ uint4 combine_quad(const CombineTable &t, uint32_t n, uint64_t quad) {
+    uint4 r = reinterpret_cast<const uint4 *>(t.p[0])[quad];
+    for (uint32_t i = 1; i < n; i++) {
+        const uint4 x = reinterpret_cast<const uint4 *>(t.p[i])[quad];
+        if (OP == AH_FILTER_AND) r = make_uint4(r.x & x.x, r.y & x.y, r.z & x.z, r.w & x.w);
+        else if (OP == AH_FILTER_OR) r = make_uint4(r.x | x.x, r.y | x.y, r.z | x.z, r.w | x.w);
+        else r = make_uint4(r.x & ~x.x, r.y & ~x.y, r.z & ~x.z, r.w & ~x.w);  // AH_FILTER_ANDNOT
+    }
+    return r;
+}
+// The bits of word `w` of a bitmap of len_bits bits that lie below len_bits (the last word's tail and the padding words: 0).
+__device__ __forceinline__ uint32_t word_mask(uint64_t w, uint64_t len_bits) {
+    const uint64_t first = w << 5;
+    if (first + 32 <= len_bits) return 0xFFFFFFFFu;
+    if (first >= len_bits) return 0u;
+    return (1u << (uint32_t)(len_bits - first)) - 1u;
+}
+template <int OP>
+__device__ __forceinline__ unsigned long long combine_words(const CombineTable &t, uint32_t n, uint64_t n_quads, uint64_t len_bits,
+                                                            uint32_t *__restrict__ out) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    unsigned long long set = 0;
+    for (uint64_t quad = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; quad < n_quads; quad += stride) {
+        uint4 r;
+        if (OP == AH_FILTER_NOT) {  // the one op that can set a bit at or above len_bits
+            const uint4 a = reinterpret_cast<const uint4 *>(t.p[0])[quad];
+            r = make_uint4(~a.x & word_mask(4 * quad, len_bits), ~a.y & word_mask(4 * quad + 1, len_bits),
+                           ~a.z & word_mask(4 * quad + 2, len_bits), ~a.w & word_mask(4 * quad + 3, len_bits));
+        } else {
+            r = combine_quad<OP>(t, n, quad);
+        }
+        reinterpret_cast<uint4 *>(out)[quad] = r;
+        set += (uint32_t)(__popc(r.x) + __popc(r.y) + __popc(r.z) + __popc(r.w));
+    }
+    return set;
+}
+// The bitmap of an expression over resident filters: n_quads x 16 bytes (the blocks are 128-byte aligned, their word counts
+// multiples of 64), every operand read once with 16-byte loads, and the number of set bits (which can pass 2^32: NOT of a small
+// set where id u32::MAX is stored).  The operands keep "no bit at or above len_bits", so only NOT has to mask.
+__global__ __launch_bounds__(256) void k_filter_combine(CombineTable t, uint32_t n, int op, uint64_t n_quads, uint64_t len_bits,
+                                                        uint32_t *__restrict__ out, unsigned long long *__restrict__ counters) {
+    __shared__ unsigned long long s_part[4];
+    unsigned long long set = 0;
+    switch (op) {  // (uniform over the launch)
+    case AH_FILTER_AND: set = combine_words<AH_FILTER_AND>(t, n, n_quads, len_bits, out); break;
+    case AH_FILTER_OR: set = combine_words<AH_FILTER_OR>(t, n, n_quads, len_bits, out); break;
+    case AH_FILTER_ANDNOT: set = combine_words<AH_FILTER_ANDNOT>(t, n, n_quads, len_bits, out); break;
+    default: set = combine_words<AH_FILTER_NOT>(t, n, n_quads, len_bits, out); break;
+    }
+    block_add_u64(set, &counters[CB_LISTED], s_part);
+}
+
+// How many rows of the dataset a bitmap over [0, len_bits) holds, by the dataset's ascending id array (sparse ids; with identity
+// ids every set bit is a row): n loads, not a walk of a bitmap that may be 512 MiB.  Every id is below len_bits (the largest + 1).
+__global__ __launch_bounds__(256) void k_filter_stored_rows(const uint32_t *__restrict__ ids, uint64_t n,
+                                                            const uint32_t *__restrict__ bits, unsigned long long *__restrict__ out) {
+    __shared__ unsigned long long s_part[4];
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    unsigned long long c = 0;
+    for (uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; g < n; g += stride) {
+        const uint32_t id = ids[g];
+        c += (bits[id >> 5] >> (id & 31)) & 1u;
+    }
+    block_add_u64(c, out, s_part);
+}
+
+// |descendants & candidates| of every node under the NEW bitmap (sp.filter_bits), one octet per node slot as k_leaf_kept.  With
+// c the leaf's length and k_i what operand i keeps of it, the count follows from the k_i alone wherever all operands but at most
+// one keep all or nothing of the leaf (`shortcut`; DESIGN.md 4 "Combined filters" has the rules and why they hold); only the
+// other leaves are walked, with the arithmetic of copy_filtered.  A free slot, a split node or an empty leaf gives 0.
+__global__ __launch_bounds__(256) void k_leaf_kept_combine(SearchParams sp, uint32_t n_nodes, CombineTable kept_of, uint32_t n, int op,
+                                                           int shortcut, uint32_t *__restrict__ kept,
+                                                           unsigned long long *__restrict__ counters) {
+    __shared__ unsigned long long s_part[4];
+    const uint32_t j = threadIdx.x & 7u;
+    const uint32_t octets = (gridDim.x * blockDim.x) >> 3;
+    uint32_t leaves = 0, walked = 0;  // (counted by lane 0 of the octet)
+    unsigned long long ids_walked = 0;
+    for (uint32_t node = (blockIdx.x * blockDim.x + threadIdx.x) >> 3; node < n_nodes; node += octets) {
+        const DNode nd = sp.nodes[node];
+        const uint32_t c = (nd.kind & 0xFFu) == AH_NODE_DESCENDANTS ? nd.b : 0u;
+        uint32_t r = 0;
+        bool walk = c != 0;
+        if (c != 0 && shortcut) {
+            const uint32_t k0 = kept_of.p[0][node];
+            if (op == AH_FILTER_NOT) {
+                r = c - k0;
+                walk = false;
+            } else if (op == AH_FILTER_ANDNOT) {  // k0 minus what the subtrahends take: nothing if they are all empty here
+                bool any_full = false, all_zero = true;
+                for (uint32_t i = 1; i < n; i++) {
+                    const uint32_t k = kept_of.p[i][node];
+                    any_full |= k == c;
+                    all_zero &= k == 0;
+                }
+                if (k0 == 0 || any_full) r = 0, walk = false;
+                else if (all_zero) r = k0, walk = false;
+            } else {
+                // AND: `settled` = an operand keeps nothing, `part` = operands that keep less than all, `ext` = the smallest count;
+                // OR, the mirror image: an operand keeps all, operands that keep something, the largest count
+                const bool is_and = op == AH_FILTER_AND;
+                bool settled = false;
+                uint32_t part = 0, ext = is_and ? c : 0u;
+                for (uint32_t i = 0; i < n; i++) {
+                    const uint32_t k = i ? kept_of.p[i][node] : k0;
+                    settled |= k == (is_and ? 0u : c);
+                    part += is_and ? (k < c) : (k > 0);
+                    ext = is_and ? min(ext, k) : max(ext, k);
+                }
+                if (settled) r = is_and ? 0u : c, walk = false;
+                else if (part <= 1) r = ext, walk = false;
+            }
+        }
+        if (walk) r = copy_filtered(sp, sp.desc + nd.a, c, nullptr, j);
+        if (j == 0) {
+            kept[node] = r;
+            leaves += c != 0;
+            walked += walk;
+            ids_walked += walk ? c : 0u;
+        }
+    }
+    block_add_u64(leaves, &counters[CB_LEAVES], s_part);
+    block_add_u64(walked, &counters[CB_LEAVES_WALKED], s_part);
+    block_add_u64(ids_walked, &counters[CB_IDS_WALKED], s_part);
+}
+
 // normal records [vector (row_bytes)][header (16)] -> row matrix + header array of the normals view
 // Only the `valid_words32` words of the stored vector (ah_vector_size bytes) are read from the record: caller views are
 // compact ([header][vector], stride hs + vs), so the device pitch beyond them is zero-filled, never copied.
@@ -3689,7 +3842,8 @@ int validate_forest_view(const ah_dataset *ds, const ah_forest_view &v) {
 using namespace ah;
 
 // `QueryBuilder::candidates` resident on the device of its index: one block [bitmap over 0 .. largest stored id][per node:
-// |descendants & candidates|].  Immutable after ah_filter_create.
+// |descendants & candidates|].  Immutable after ah_filter_create / ah_filter_create_bitmap / ah_filter_combine.  The bitmap has
+// no bit set at or above len_bits, its padding words included: ah_filter_combine reads its operands' words whole.
 struct ah_filter {
     ah_index *ix = nullptr;
     uint32_t *d_bits = nullptr, *d_leaf_kept = nullptr;
@@ -4802,6 +4956,191 @@ int ah_filter_create(ah_index *ix, const uint32_t *sorted_ids, size_t n, ah_filt
     }
     block.p = nullptr;  // the filter owns it from here
     *out = f.release();
+    return AH_OK;
+    AH_GUARDED_END
+}
+
+// The block of a filter of `ix` as ah_filter_create lays it out: [bitmap: `words` 32-bit words, a multiple of 64, zero from
+// len_bits on][n_nodes per-node counts][256 bytes].  ah_filter_combine and ah_filter_create_bitmap count on the device into
+// the first 8-byte aligned words of that tail (CombineSlot), which no search reads.
+struct FilterBlock {
+    uint64_t len_bits;
+    size_t words, counters_off, bytes;
+    FilterBlock(const ah_index *ix, uint64_t bits) : len_bits(bits) {
+        words = (((size_t)len_bits + 31) / 32 + 63) & ~(size_t)63;
+        counters_off = (words * 4 + (size_t)ix->n_nodes * 4 + 7) & ~(size_t)7;
+        bytes = words * 4 + (size_t)ix->n_nodes * 4 + 256;
+        static_assert(CB_WORDS * 8 + 8 <= 256, "the counters live in the block's tail");
+    }
+};
+// Largest stored id + 1: the length of every filter of an index over this dataset (0: no rows).
+static uint64_t filter_len_bits(const ah_dataset *ds) {
+    if (!ds->n) return 0;
+    return (uint64_t)(ds->identity_ids ? (uint32_t)(ds->n - 1) : ds->last_id) + 1;
+}
+// A finished filter joins its index: the counters of ah_filter_stats move, the block is the filter's from here.
+static void filter_adopt(ah_filter *f, ah_index *ix, DevMem &block, const FilterBlock &fb, uint64_t listed, uint64_t stored) {
+    f->listed = listed;
+    f->stored = stored;
+    f->d_bits = block.as<uint32_t>();
+    f->d_leaf_kept = f->d_bits + fb.words;
+    f->device_bytes = dev_block_bytes(block.p);  // (what the allocator accounts for it: ah_device_cache_stats)
+    {
+        std::lock_guard<std::mutex> lk(ix->stats_mu);
+        ix->fstats.filters_created++;
+        ix->fstats.filters_alive++;
+        ix->fstats.leaf_kept_passes += ix->n_nodes ? 1 : 0;
+    }
+    block.p = nullptr;
+}
+
+// An expression over resident filters as a new resident filter (include/arroy_hip.h): one streaming pass over the operands'
+// bitmaps, `stored` from the popcount (identity ids) or the dataset's id array, the per-node counts derived from the operands'
+// wherever they settle it.  Works on the calling thread's leased context; one synchronisation, at the end.
+int ah_filter_combine(int op, ah_filter *const *operands, size_t n, ah_filter **out, ah_filter_combine_stats *out_stats) {
+    AH_GUARDED("ah_filter_combine")
+    AH_REQUIRE(out, AH_ERR_INVALID_ARGUMENT, "out is NULL");
+    *out = nullptr;
+    AH_REQUIRE(op >= AH_FILTER_AND && op <= AH_FILTER_NOT, AH_ERR_INVALID_ARGUMENT, "unknown op %d (AH_FILTER_AND = 0 .. AH_FILTER_NOT = 3)", op);
+    AH_REQUIRE(n >= 1 && n <= AH_FILTER_COMBINE_MAX, AH_ERR_INVALID_ARGUMENT, "n = %zu operands: 1 .. %d are legal", n,
+               AH_FILTER_COMBINE_MAX);
+    AH_REQUIRE(op != AH_FILTER_NOT || n == 1, AH_ERR_INVALID_ARGUMENT, "AH_FILTER_NOT takes exactly one operand (n = %zu)", n);
+    AH_REQUIRE(operands, AH_ERR_INVALID_ARGUMENT, "operands is NULL");
+    for (size_t i = 0; i < n; i++) AH_REQUIRE(operands[i], AH_ERR_INVALID_ARGUMENT, "operands[%zu] is NULL", i);
+    ah_index *ix = operands[0]->ix;
+    for (size_t i = 1; i < n; i++)
+        AH_REQUIRE(operands[i]->ix == ix, AH_ERR_INVALID_ARGUMENT, "operands[%zu] belongs to another index than operands[0]", i);
+    AH_REQUIRE(ix && ix->ds, AH_ERR_INVALID_ARGUMENT, "index is NULL");
+    AH_INDEX_LIVE(ix);
+    ah_dataset *ds = ix->ds;
+    AH_HIP(hipSetDevice(ds->device));
+    std::unique_ptr<ah_filter> f(new ah_filter);
+    f->ix = ix;
+    f->len_bits = operands[0]->len_bits;
+    // (all filters of an index have one length: a dataset cannot change under a live index, an index not be suspended under a
+    // live filter)
+    for (size_t i = 0; i < n; i++) assert(operands[i]->len_bits == f->len_bits);
+    const FilterBlock fb(ix, f->len_bits);
+    DevMem block;
+    AH_HIP(dev_malloc(&block.p, fb.bytes));
+    ContextLease lease(ds);
+    AH_REQUIRE(lease.c, AH_ERR_DEVICE, "cannot create a HIP stream");
+    hipStream_t s = lease.c->stream;
+    uint32_t *d_bits = block.as<uint32_t>(), *d_kept = d_bits + fb.words;
+    unsigned long long *d_counters = reinterpret_cast<unsigned long long *>(block.as<uint8_t>() + fb.counters_off);
+    // (the kernels write every bitmap word and every node's count; what they leave is the tail with the counters)
+    AH_HIP(hipMemsetAsync(d_kept + ix->n_nodes, 0, 256, s));
+    CombineTable bits_of{}, kept_of{};
+    for (size_t i = 0; i < n; i++) {
+        bits_of.p[i] = operands[i]->d_bits;
+        kept_of.p[i] = operands[i]->d_leaf_kept;
+    }
+    const uint64_t n_quads = fb.words / 4;
+    if (n_quads)
+        hipLaunchKernelGGL(k_filter_combine, dim3((uint32_t)std::min<uint64_t>((n_quads + 255) / 256, 2048)), dim3(256), 0, s, bits_of,
+                           (uint32_t)n, op, n_quads, f->len_bits, d_bits, d_counters);
+    const bool count_rows = !ds->identity_ids && ds->n;  // identity ids: every set bit is a row
+    if (count_rows)
+        hipLaunchKernelGGL(k_filter_stored_rows, dim3((uint32_t)std::min<uint64_t>((ds->n + 255) / 256, 2048)), dim3(256), 0, s, ds->view().ids,
+                           (uint64_t)ds->n, d_bits, d_counters + CB_STORED);
+    if (ix->n_nodes) {
+        SearchParams lp{};
+        lp.nodes = ix->d_nodes;
+        lp.desc = ix->d_desc;
+        lp.filter_bits = d_bits;
+        lp.filter_len_bits = f->len_bits;
+        hipLaunchKernelGGL(k_leaf_kept_combine, dim3((uint32_t)std::min<uint64_t>(((uint64_t)ix->n_nodes + 31) / 32, 1024)), dim3(256), 0, s, lp, ix->n_nodes,
+                           kept_of, (uint32_t)n, op, tun(TUN_FILTER_COMBINE_SHORTCUT) != 0 ? 1 : 0, d_kept, d_counters);
+    }
+    AH_HIP(hipGetLastError());
+    unsigned long long h[CB_WORDS] = {};
+    AH_HIP(hipMemcpyAsync(h, d_counters, sizeof(h), hipMemcpyDeviceToHost, s));
+    AH_HIP(hipStreamSynchronize(s));
+    if (out_stats) *out_stats = ah_filter_combine_stats{fb.words, h[CB_LEAVES], h[CB_LEAVES_WALKED], h[CB_IDS_WALKED]};
+    filter_adopt(f.get(), ix, block, fb, h[CB_LISTED], count_rows ? h[CB_STORED] : h[CB_LISTED]);
+    *out = f.release();
+    return AH_OK;
+    AH_GUARDED_END
+}
+
+// A filter from the host's own bitmap (include/arroy_hip.h): the bits up to the largest stored id travel as they are, `stored`
+// and the per-node counts as ah_filter_combine / ah_filter_create make them.
+int ah_filter_create_bitmap(ah_index *ix, const uint64_t *words, uint64_t n_bits, ah_filter **out) {
+    AH_GUARDED("ah_filter_create_bitmap")
+    AH_REQUIRE(out, AH_ERR_INVALID_ARGUMENT, "out is NULL");
+    *out = nullptr;
+    AH_REQUIRE(n_bits == 0 || words, AH_ERR_INVALID_ARGUMENT, "words is NULL");
+    AH_REQUIRE(ix && ix->ds, AH_ERR_INVALID_ARGUMENT, "index is NULL");
+    AH_INDEX_LIVE(ix);
+    ah_dataset *ds = ix->ds;
+    AH_HIP(hipSetDevice(ds->device));
+    std::unique_ptr<ah_filter> f(new ah_filter);
+    f->ix = ix;
+    f->len_bits = filter_len_bits(ds);
+    const FilterBlock fb(ix, f->len_bits);
+    // the set bits among the first `upto`
+    auto popcount_below = [&](uint64_t upto) {
+        uint64_t c = 0;
+        for (uint64_t w = 0; w < (upto >> 6); w++) c += (uint64_t)__builtin_popcountll(words[w]);
+        if (upto & 63) c += (uint64_t)__builtin_popcountll(words[upto >> 6] & ((1ull << (upto & 63)) - 1));
+        return c;
+    };
+    const uint64_t n_travel = std::min(n_bits, f->len_bits);  // bits above the largest stored id match nothing: they stay behind
+    const uint64_t inside = popcount_below(n_travel);
+    const uint64_t listed = n_travel == n_bits ? inside : popcount_below(n_bits);
+    DevMem block;
+    AH_HIP(dev_malloc(&block.p, fb.bytes));
+    ContextLease lease(ds);
+    AH_REQUIRE(lease.c, AH_ERR_DEVICE, "cannot create a HIP stream");
+    hipStream_t s = lease.c->stream;
+    uint32_t *d_bits = block.as<uint32_t>(), *d_kept = d_bits + fb.words;
+    unsigned long long *d_counters = reinterpret_cast<unsigned long long *>(block.as<uint8_t>() + fb.counters_off);
+    AH_HIP(hipMemsetAsync(d_bits, 0, fb.bytes, s));
+    // whole 32-bit words as they are (little-endian: bit i of the 64-bit layout is bit i of the 32-bit one), the last one masked
+    const size_t whole = (size_t)(n_travel >> 5);
+    uint32_t last = 0;
+    if (whole) AH_HIP(hipMemcpyAsync(d_bits, words, whole * 4, hipMemcpyHostToDevice, s));
+    if (n_travel & 31) {
+        memcpy(&last, reinterpret_cast<const uint8_t *>(words) + whole * 4, 4);
+        last &= (1u << (uint32_t)(n_travel & 31)) - 1u;
+        AH_HIP(hipMemcpyAsync(d_bits + whole, &last, 4, hipMemcpyHostToDevice, s));
+    }
+    const bool count_rows = !ds->identity_ids && ds->n && inside;  // identity ids: every bit below len_bits = n is a row
+    if (count_rows)
+        hipLaunchKernelGGL(k_filter_stored_rows, dim3((uint32_t)std::min<uint64_t>((ds->n + 255) / 256, 2048)), dim3(256), 0, s, ds->view().ids,
+                           (uint64_t)ds->n, d_bits, d_counters + CB_STORED);
+    if (ix->n_nodes) {
+        SearchParams lp{};
+        lp.nodes = ix->d_nodes;
+        lp.desc = ix->d_desc;
+        lp.filter_bits = d_bits;
+        lp.filter_len_bits = f->len_bits;
+        hipLaunchKernelGGL(k_leaf_kept, dim3(1024), dim3(256), 0, s, lp, ix->n_nodes, d_kept);
+    }
+    AH_HIP(hipGetLastError());
+    unsigned long long stored = inside;
+    if (count_rows) AH_HIP(hipMemcpyAsync(&stored, d_counters + CB_STORED, 8, hipMemcpyDeviceToHost, s));
+    AH_HIP(hipStreamSynchronize(s));
+    filter_adopt(f.get(), ix, block, fb, listed, stored);
+    *out = f.release();
+    return AH_OK;
+    AH_GUARDED_END
+}
+
+// Test aid: the filter as it is on the device.  Reads only.
+int ah_filter_export(const ah_filter *f, uint64_t *out_len_bits, uint32_t *out_bits, uint32_t *out_leaf_kept) {
+    AH_GUARDED("ah_filter_export")
+    AH_REQUIRE(f && f->ix && f->ix->ds, AH_ERR_INVALID_ARGUMENT, "filter is NULL");
+    if (out_len_bits) *out_len_bits = f->len_bits;
+    const ah_index *ix = f->ix;
+    AH_HIP(hipSetDevice(ix->ds->device));
+    ContextLease lease(ix->ds);
+    AH_REQUIRE(lease.c, AH_ERR_DEVICE, "cannot create a HIP stream");
+    hipStream_t s = lease.c->stream;
+    const size_t words = ((size_t)f->len_bits + 31) / 32;
+    if (out_bits && words) AH_HIP(hipMemcpyAsync(out_bits, f->d_bits, words * 4, hipMemcpyDeviceToHost, s));
+    if (out_leaf_kept && ix->n_nodes) AH_HIP(hipMemcpyAsync(out_leaf_kept, f->d_leaf_kept, (size_t)ix->n_nodes * 4, hipMemcpyDeviceToHost, s));
+    AH_HIP(hipStreamSynchronize(s));
     return AH_OK;
     AH_GUARDED_END
 }

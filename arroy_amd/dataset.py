@@ -562,6 +562,28 @@ class Index:
         sorted=True: `ids` is already an ascending array of distinct ids (what a RoaringBitmap iterates)."""
         return Filter(self, ids, sorted)
 
+    def make_filter_bitmap(self, words, n_bits: int) -> "Filter":
+        """ah_filter_create_bitmap: a resident filter from a bitmap as the host holds it — bit i (bit i & 63 of the uint64
+        words[i >> 6]) set = id i is a candidate.  Equal to make_filter of the set bits among the first `n_bits`."""
+        w = np.ascontiguousarray(words, dtype=np.uint64).ravel()
+        if int(n_bits) < 0 or int(n_bits) > w.size * 64:
+            raise ValueError(f"n_bits = {n_bits} for {w.size} words")
+        h = C.c_void_p()
+        _lib.check(_lib.lib().ah_filter_create_bitmap(self._h, _ptr(w) if w.size else None, int(n_bits), C.byref(h)))
+        return Filter._adopt(self, h)
+
+    def combine_filters(self, op, filters, want_stats: bool = False):
+        """ah_filter_combine: "and" / "or" / "andnot" (filters[0] minus the others) / "not" (one filter) of resident filters of
+        this index as a new resident filter, computed on the device; bit for bit the filter make_filter gives for the id list of
+        the result.  want_stats: (filter, ah_filter_combine_stats as a dict)."""
+        code = _lib.FILTER_OPS[op.lower()] if isinstance(op, str) else int(op)
+        filters = list(filters)
+        handles = (C.c_void_p * max(1, len(filters)))(*[f._handle() for f in filters])
+        h, st = C.c_void_p(), _lib.AhFilterCombineStats()
+        _lib.check(_lib.lib().ah_filter_combine(code, handles, len(filters), C.byref(h), C.byref(st)))
+        f = Filter._adopt(self, h)
+        return (f, {k: int(getattr(st, k)) for k, _ in _lib.AhFilterCombineStats._fields_}) if want_stats else f
+
     def search(self, count: int, queries=None, items=None, search_k: int = 0, oversampling: int = 0, candidates=None,
                raw: bool = False, candidates_sorted: bool = False, filters=None, filter_of_query=None):
         """Batch of `QueryBuilder::by_vector` (queries: nq x dims) or `by_item` (items: nq ids).
@@ -755,7 +777,8 @@ class Index:
 
 class Filter:
     """`QueryBuilder::candidates` resident next to an Index (ah_filter_create): the bitmap over the stored ids and what it keeps of
-    every leaf, made once.  Immutable; any number of threads may search under it.  Closed with its index at the latest."""
+    every leaf, made once.  Immutable; any number of threads may search under it.  Closed with its index at the latest.
+    `a & b`, `a | b`, `a - b` and `~a` make the filter of the expression on the device (Index.combine_filters)."""
 
     def __init__(self, index: Index, ids, sorted_ids: bool = False):
         self.index = index
@@ -764,16 +787,47 @@ class Filter:
         _lib.check(_lib.lib().ah_filter_create(index._h, _ptr(arr), arr.size, C.byref(self._h)))
         index._filters.add(self)
 
+    @classmethod
+    def _adopt(cls, index: Index, handle: C.c_void_p) -> "Filter":
+        """A Filter around an ah_filter handle the library has just made (Index.combine_filters, Index.make_filter_bitmap)."""
+        self = cls.__new__(cls)
+        self.index, self._h = index, handle
+        index._filters.add(self)
+        return self
+
     def _handle(self):
         if not self._h:
             raise ValueError("the filter is closed")
         return self._h.value
 
     def info(self) -> dict:
-        """ah_filter_info: ids listed, those of them that are stored (exact), bytes of HBM held."""
+        """ah_filter_info: ids listed (a combined or bitmap-made filter: bits set), those of them that are stored (exact),
+        bytes of HBM held."""
         listed, stored, nbytes = C.c_uint64(), C.c_uint64(), C.c_uint64()
         _lib.check(_lib.lib().ah_filter_info(self._handle(), C.byref(listed), C.byref(stored), C.byref(nbytes)))
         return {"listed": listed.value, "stored": stored.value, "device_bytes": nbytes.value}
+
+    def export(self) -> dict:
+        """ah_filter_export (test aid): len_bits (largest stored id + 1), bits (its ceil(len_bits / 32) bitmap words) and
+        leaf_kept (per node slot of the index: the ids of the leaf the filter keeps), read back from the device."""
+        len_bits = C.c_uint64()
+        _lib.check(_lib.lib().ah_filter_export(self._handle(), C.byref(len_bits), None, None))
+        bits = np.zeros((len_bits.value + 31) // 32, dtype=np.uint32)
+        kept = np.zeros(self.index.export_info()["n_nodes"], dtype=np.uint32)
+        _lib.check(_lib.lib().ah_filter_export(self._handle(), None, _ptr(bits), _ptr(kept)))
+        return {"len_bits": int(len_bits.value), "bits": bits, "leaf_kept": kept}
+
+    def __and__(self, other: "Filter") -> "Filter":
+        return self.index.combine_filters("and", [self, other])
+
+    def __or__(self, other: "Filter") -> "Filter":
+        return self.index.combine_filters("or", [self, other])
+
+    def __sub__(self, other: "Filter") -> "Filter":
+        return self.index.combine_filters("andnot", [self, other])
+
+    def __invert__(self) -> "Filter":
+        return self.index.combine_filters("not", [self])
 
     def close(self) -> None:
         if self._h:

@@ -726,6 +726,11 @@ class Reader:
         """A candidate set resident on the device for `nns(..).candidates(filter)`: made once, used by any number of queries."""
         return self._st.index.make_filter(ids)
 
+    def make_filter_bitmap(self, words, n_bits: int) -> "Filter":
+        """The same from a bitmap (uint64 words, bit i of the set = id i): a dense set need not be expanded into an id list.
+        Filters of one reader combine on the device with `&`, `|`, `-` and `~`."""
+        return self._st.index.make_filter_bitmap(words, n_bits)
+
 
 class QueryBuilder:
     """`QueryBuilder` (src/reader.rs:26-124)."""

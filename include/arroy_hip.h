@@ -649,6 +649,40 @@ AH_API int ah_filter_create(ah_index *index, const uint32_t *sorted_ids, size_t 
 AH_API int ah_filter_info(const ah_filter *f, uint64_t *out_listed, uint64_t *out_stored, uint64_t *out_device_bytes);
 AH_API int ah_filter_destroy(ah_filter *f);
 
+/* Filter expressions on the device (ABI v7 addition: look the symbols up).  The filters of an index are plain bitmaps of one
+ * length, so tenant AND facet, facet A OR facet B, everything NOT deleted are one streaming pass over (largest id + 1) / 8
+ * bytes instead of an id list evaluated, walked and uploaded by the host.
+ *   AH_FILTER_AND / _OR   1 <= n <= AH_FILTER_COMBINE_MAX operands
+ *   AH_FILTER_ANDNOT      operands[0] minus the union of the others, n >= 1
+ *   AH_FILTER_NOT         n == 1: every id of [0, largest stored id] the operand does not hold (ids that are not stored match
+ *                         nothing, as in every filter)
+ * An operand may be named more than once; with n == 1 AND, OR and ANDNOT give a copy.  The result is a new, independent,
+ * immutable filter of the operands' index (they may be destroyed before it), counted like a created one, and bit for bit the
+ * filter ah_filter_create makes from the ascending id list of the expression's result: the same bitmap, the same per-node
+ * counts, the same `stored`, hence the same path choices in every search.  Its `listed` (ah_filter_info) is the number of set
+ * bits; a list-made filter also counts the listed ids above the largest stored id, which no bitmap holds.  All or nothing
+ * (AH_ERR_OUT_OF_MEMORY leaves nothing held and no counter moved); may run concurrently with searches under its operands.
+ * Refused (AH_ERR_INVALID_ARGUMENT, the offending position named): out NULL, n out of range, an unknown op, a NULL operand,
+ * an operand of another index, a suspended index. */
+typedef enum ah_filter_op { AH_FILTER_AND = 0, AH_FILTER_OR = 1, AH_FILTER_ANDNOT = 2, AH_FILTER_NOT = 3 } ah_filter_op;
+#define AH_FILTER_COMBINE_MAX 64
+typedef struct ah_filter_combine_stats {
+    uint64_t words;          /* 32-bit bitmap words written                                                             */
+    uint64_t leaves;         /* Descendants nodes in use with at least one id                                           */
+    uint64_t leaves_walked;  /* ... whose ids were tested against the new bitmap (the rest: derived from the operands' counts) */
+    uint64_t ids_walked;     /* ids of those leaves                                                                     */
+} ah_filter_combine_stats;
+AH_API int ah_filter_combine(int op, ah_filter *const *operands, size_t n, ah_filter **out, ah_filter_combine_stats *out_stats);
+/* A filter from a bitmap as the host holds it: bit i (bit i & 63 of words[i >> 6]) set = id i is a candidate.  n_bits is
+ * arbitrary: bits of the last word at or above n_bits are ignored, and so are bits above the largest stored id — those are
+ * still counted in `listed`, the set bits among the first n_bits.  Only the bits up to the largest stored id travel to the
+ * device.  The result equals ah_filter_create of the list of set bits.  n_bits == 0 gives an empty filter; `words` is not
+ * used after return. */
+AH_API int ah_filter_create_bitmap(ah_index *index, const uint64_t *words, uint64_t n_bits, ah_filter **out);
+/* Test aid: the filter as it is on the device — out_len_bits: largest stored id + 1; out_bits: its ceil(len_bits / 32) bitmap
+ * words; out_leaf_kept: the n_nodes (ah_index_export_info) per-node counts.  Any pointer may be NULL. */
+AH_API int ah_filter_export(const ah_filter *f, uint64_t *out_len_bits, uint32_t *out_bits, uint32_t *out_leaf_kept);
+
 #define AH_NO_FILTER 0xFFFFFFFFu
 /* ah_search_batch in which every query names its filter: filter_of_query[q] is an index into `filters` or AH_NO_FILTER;
  * NULL = every query under filters[0] (n_filters == 1) or unfiltered (n_filters == 0).  Query q returns exactly what
