@@ -695,20 +695,66 @@ int launch_load_item_as_query(const DataView &dv, uint32_t row, void *d_qvec, fl
 // is used as the tie-break word: same order as the id, and it recovers the original distance and id.
 // Key = orderable(dist) << 32 | position.  A tournament of LDS bitonic sorts: every block sorts a chunk
 // of kChunk keys and keeps its `keep` smallest; rounds repeat until one block is left.
-// Faithful quirk: the reference skips items >= (f32::MAX, u32::MAX) once its 2k prefill buffer is full
-// (reader.rs:611,619-621); such items at positions >= 2k get the sentinel key and are never selected.
+// Faithful quirk: the reference skips items >= (f32::MAX, u32::MAX) once its 2k prefill buffer is full, but only while its
+// threshold still has that first value (reader.rs:611,619-621), i.e. up to `skip_end`: the first position >= 2k whose item
+// is below it (0xFFFFFFFF when there is none).  That item compacts the buffer, the threshold becomes the k-th smallest key so
+// far, and no later skip can change the answer: every later item counts, +inf and NaN included.  Skippable items at
+// positions in [2k, skip_end) get the sentinel key and are never selected (the rule of batch_make_key, batch.hip).
+// The kernels that make the keys find skip_end themselves, and only where it matters: a block that holds no skippable item at
+// a position >= 2k (every block of a list of finite distances, and of a list of n <= 2k) makes plain keys and pays one barrier;
+// any other block looks for the first item below the threshold from position 2k up to its own last position (block_skip_end).
+// Worst case: a list whose distances are ALL +inf / NaN from position 2k on (a query with an inf component over "all items").
+// Every block then walks [2k, its own end): n^2 / 8192 reads in the tournament and n^2 / 512 in k_make_keys instead of n.  At
+// n = 1M they come from L2 and cost milliseconds; at tens of millions of items it is seconds, for an answer made of NaNs.
+// Lists with a finite distance here and there stop at the first stretch.
 // ------------------------------------------------------------------------------------------------
 static constexpr uint32_t kChunk = 4096;
 static constexpr uint64_t kSentinel = ~0ull;
 
-__device__ __forceinline__ uint64_t make_key(float d, uint64_t pos, uint32_t id, uint64_t two_k) {
+// item >= threshold (OrderedFloat(f32::MAX), u32::MAX)
+__device__ __forceinline__ bool key_skippable(uint32_t ok, uint32_t id) {
+    const uint32_t max_key = 0xFF7FFFFFu;  // orderable_key(f32::MAX)
+    return ok > max_key || (ok == max_key && id == 0xFFFFFFFFu);
+}
+__device__ __forceinline__ uint64_t make_key(float d, uint64_t pos, uint32_t id, uint64_t two_k, uint32_t skip_end) {
     uint32_t ok = orderable_key(d);
-    if (pos >= two_k) {
-        // item >= threshold (OrderedFloat(f32::MAX), u32::MAX)
-        const uint32_t max_key = 0xFF7FFFFFu;  // orderable_key(f32::MAX)
-        if (ok > max_key || (ok == max_key && id == 0xFFFFFFFFu)) return kSentinel;
-    }
+    if (pos >= two_k && pos < skip_end && key_skippable(ok, id)) return kSentinel;
     return ((uint64_t)ok << 32) | (uint64_t)(uint32_t)pos;
+}
+
+__device__ __forceinline__ uint32_t key_id(const uint32_t *ids, const uint32_t *row_ids, int have_ids, uint64_t g) {
+    return have_ids ? ids[g] : (row_ids ? row_ids[g] : (uint32_t)g);
+}
+// Does this item ask for skip_end?  (The id decides for f32::MAX alone and is read only then.)
+__device__ __forceinline__ bool key_wants_skip_end(uint32_t ok, uint64_t pos, uint64_t two_k, const uint32_t *ids,
+                                                   const uint32_t *row_ids, int have_ids) {
+    return pos >= two_k && ok >= 0xFF7FFFFFu && key_skippable(ok, key_id(ids, row_ids, have_ids, pos));
+}
+
+// skip_end as far as one block needs it; every thread of the block calls it once.  `wanted`: this thread holds a skippable
+// item at a position >= 2k.  No such item in the block: 0, and nothing was read.  Otherwise the positions [2k, end) are walked,
+// kSkipPer per thread and step, up to the first stretch that holds an item below the threshold; `end` is one past the block's
+// last position, so "none before end" (0xFFFFFFFF) skips all the block's skippable items, as the true skip_end would.
+static constexpr uint32_t kSkipPer = 4;
+__device__ __forceinline__ uint32_t block_skip_end(bool wanted, const float *__restrict__ dist, const uint32_t *__restrict__ ids,
+                                                   const uint32_t *__restrict__ row_ids, int have_ids, uint64_t two_k, uint64_t end) {
+    __shared__ uint32_t s_first;
+    if (!__syncthreads_or(wanted)) return 0u;  // (block-uniform, as everything below)
+    if (threadIdx.x == 0) s_first = 0xFFFFFFFFu;
+    uint32_t first = 0xFFFFFFFFu;
+    for (uint64_t base = two_k; base < end; base += (uint64_t)blockDim.x * kSkipPer) {
+#pragma unroll
+        for (uint32_t u = 0; u < kSkipPer; u++) {
+            const uint64_t g = base + (uint64_t)u * blockDim.x + threadIdx.x;
+            if (g < end && !key_wants_skip_end(orderable_key(dist[g]), g, two_k, ids, row_ids, have_ids)) first = min(first, (uint32_t)g);
+        }
+        if (__syncthreads_or(first != 0xFFFFFFFFu)) break;
+    }
+    for (int off = 32; off > 0; off >>= 1) first = min(first, (uint32_t)__shfl_xor((int)first, off));
+    __syncthreads();  // s_first is set
+    if ((threadIdx.x & 63u) == 0) atomicMin(&s_first, first);
+    __syncthreads();
+    return s_first;
 }
 
 __device__ __forceinline__ void bitonic_sort_lds(uint64_t *s, uint32_t n_pow2) {
@@ -738,18 +784,27 @@ __global__ __launch_bounds__(kBlock) void k_topk_round(const float *__restrict__
                                                        uint64_t two_k, uint32_t keep, uint64_t *__restrict__ keys_out) {
     __shared__ uint64_t s[kChunk];
     const uint64_t base = (uint64_t)blockIdx.x * kChunk;
+    bool wanted = false;
     for (uint32_t t = threadIdx.x; t < kChunk; t += blockDim.x) {
         uint64_t g = base + t;
         uint64_t key = kSentinel;
         if (g < n_in) {
             if (FIRST) {
-                uint32_t id = have_ids ? ids[g] : (row_ids ? row_ids[g] : (uint32_t)g);
-                key = make_key(dist[g], g, id, two_k);
+                const uint32_t ok = orderable_key(dist[g]);
+                key = ((uint64_t)ok << 32) | (uint64_t)(uint32_t)g;  // make_key with nothing skipped
+                wanted |= key_wants_skip_end(ok, g, two_k, ids, row_ids, have_ids);
             } else {
                 key = keys_in[g];
             }
         }
         s[t] = key;
+    }
+    if (FIRST) {
+        const uint64_t end = min(n_in, base + kChunk);
+        const uint32_t skip_end = block_skip_end(wanted, dist, ids, row_ids, have_ids, two_k, end);
+        if (skip_end != 0u)  // rare (non-finite distances past 2k): this thread's keys once more, with the skip
+            for (uint32_t t = threadIdx.x; base + t < end; t += blockDim.x)
+                s[t] = make_key(dist[base + t], base + t, key_id(ids, row_ids, have_ids, base + t), two_k, skip_end);
     }
     bitonic_sort_lds(s, kChunk);
     for (uint32_t t = threadIdx.x; t < keep; t += blockDim.x) keys_out[(uint64_t)blockIdx.x * keep + t] = s[t];
@@ -770,14 +825,18 @@ __global__ void k_bitonic_global(uint64_t *keys, uint64_t n_pow2, uint64_t size,
 }
 __global__ void k_make_keys(const float *dist, const uint32_t *ids, const uint32_t *row_ids, int have_ids, uint64_t n,
                             uint64_t n_pow2, uint64_t two_k, uint64_t *keys) {
-    uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= n_pow2) return;
+    const uint64_t base = (uint64_t)blockIdx.x * blockDim.x, g = base + threadIdx.x;
     uint64_t key = kSentinel;
+    bool wanted = false;
     if (g < n) {
-        uint32_t id = have_ids ? ids[g] : (row_ids ? row_ids[g] : (uint32_t)g);
-        key = make_key(dist[g], g, id, two_k);
+        const uint32_t ok = orderable_key(dist[g]);
+        key = ((uint64_t)ok << 32) | (uint64_t)(uint32_t)g;  // make_key with nothing skipped
+        wanted = key_wants_skip_end(ok, g, two_k, ids, row_ids, have_ids);
     }
-    keys[g] = key;
+    // (every thread of the block arrives here: no early return above)
+    const uint32_t skip_end = block_skip_end(wanted, dist, ids, row_ids, have_ids, two_k, min(n, base + blockDim.x));
+    if (skip_end != 0u && g < n) key = make_key(dist[g], g, key_id(ids, row_ids, have_ids, g), two_k, skip_end);
+    if (g < n_pow2) keys[g] = key;
 }
 
 // Final: sorted keys -> (id, normalized distance).  src/reader.rs:396-399.
@@ -845,7 +904,11 @@ __global__ __launch_bounds__(1024) void k_topk_small(DataView dv, const float *_
     }
     __syncthreads();
     const uint32_t w_min = s_min;
-    uint32_t fail = s_max > 0xFF7FFFFFu ? 4u : 0u;  // +inf / NaN somewhere
+    // +inf / NaN somewhere: bit 2, and the general path applies the skip of src/reader.rs:611-621.  This kernel needs no skip:
+    // with every distance finite the only skippable key is the one item (f32::MAX, id 0xFFFFFFFF); ids ascend, so it is the
+    // last position; where that is at or past 2k, at least 2k > k keys before it are smaller (a word <= f32::MAX's at an
+    // earlier position), so it is never among the k smallest whether it is skipped or not.
+    uint32_t fail = s_max > 0xFF7FFFFFu ? 4u : 0u;
     uint32_t n_sel = 0;
     if (!fail) {
         const uint64_t span = (uint64_t)(s_max - w_min) + 1ull;

@@ -12,15 +12,7 @@ def oracle_of(case):
     return O.Data(O.MANHATTAN, case.vectors, ids=case.ids)
 
 
-def agree(case, ks, picks=None):
-    od = oracle_of(case)
-    qv, qh = od.query_leaf(case.query)
-    for i in (range(len(case)) if picks is None else picks):
-        for k in ks:
-            wi, wd = od.rerank(qv, qh, case.rows[i], k)
-            ei, ed = case.expect(i, k)
-            assert wi.tolist() == ei.tolist(), (case.names[i], k)
-            assert B.canonical_bits(wd).tolist() == B.canonical_bits(ed).tolist(), (case.names[i], k)
+agree = B.agree   # (the oracle against the numpy reference; shared with test_single_topk_cpu.py)
 
 
 def test_the_distance_of_a_row_is_its_first_component_bit_for_bit():
