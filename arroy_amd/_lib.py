@@ -394,15 +394,22 @@ def synth_rows_host(seed: int, distribution: int, n: int, dims: int, first_item:
     return out
 
 
+def dense_tiles(n_rows: int, n_cols: int) -> tuple[int, int]:
+    """ah_debug_dense_tiles: (rows, columns) of one tile of the dense MFMA screen of a level of `n_cols` nodes over `n_rows`
+    rows under the current tunables — 160 x 64 / 160 x 128: the narrow kernel, 256 x 128 / 256 x 256: the wide one."""
+    tr, tc = C.c_uint32(0), C.c_uint32(0)
+    check(lib().ah_debug_dense_tiles(n_rows, n_cols, C.byref(tr), C.byref(tc)))
+    return int(tr.value), int(tc.value)
+
+
 def launch_coverage(kind: int, n_rows: int, dims: int, a: int, b: int = 0, device: int = 0):
     """ah_debug_launch_coverage: how often the block -> work-item map of a build launch serves every work item."""
     import numpy as np
     if kind == 0:
         shape = (b, n_rows)
     elif kind == 1:
-        tr, tc = C.c_uint32(0), C.c_uint32(0)
-        check(lib().ah_debug_dense_tiles(n_rows, a, C.byref(tr), C.byref(tc)))
-        shape = ((n_rows + tr.value - 1) // tr.value, (a + tc.value - 1) // tc.value)
+        tr, tc = dense_tiles(n_rows, a)
+        shape = ((n_rows + tr - 1) // tr, (a + tc - 1) // tc)
     else:
         shape = (a, (n_rows + 1023) // 1024)
     out = np.zeros(shape, dtype=np.uint32)

@@ -386,3 +386,73 @@ def test_search_accepts_counts_beyond_the_batched_top_k():
         ids_raw, d_raw, counts = index.search(count, queries=queries, search_k=search_k, raw=True)
         for qi in range(len(queries)):
             assert np.all(ids_raw[qi, counts[qi]:] == 0xFFFFFFFF) and np.all(np.isnan(d_raw[qi, counts[qi]:]))
+
+
+def _same_dataset(a, b, ids, queries, what):
+    """Item vectors, headers, ids (through a re-rank, which reports them) and a full scan of two datasets, bit for bit."""
+    assert len(a) == len(b) == len(ids), what
+    assert a.read_headers().tobytes() == b.read_headers().tobytes(), f"{what}: headers"
+    for i in (0, 1, len(ids) // 2, len(ids) - 2, len(ids) - 1):
+        assert_bit_equal(a.item_vector(int(ids[i])), b.item_vector(int(ids[i])), f"{what}: vector of item {int(ids[i])}")
+    for q in queries:
+        assert_bit_equal(a.distances(query=q), b.distances(query=q), f"{what}: scan")
+        ia, da = a.rerank(50, query=q)
+        ib, db = b.rerank(50, query=q)
+        assert np.array_equal(ia, ib) and np.isin(ia, ids).all(), f"{what}: ids"
+        assert_bit_equal(da, db, f"{what}: top-k distances")
+
+
+@pytest.mark.parametrize("metric,dims,n", [(D.Cosine, 768, 30_000), (D.Euclidean, 70, 50_000), (D.DotProduct, 130, 40_000),
+                                           (D.BinaryQuantizedCosine, 200, 40_000)], ids=["cosine768", "euclidean70", "dot130", "bq_cosine200"])
+def test_upload_through_the_ring_with_plain_memcpy_stages_the_same_bytes(metric, dims, n):
+    """AH_STAGE_MEMCPY=1: the staging ring is filled with memcpy instead of the non-temporal AVX2 row copy (rows of >= 512
+    bytes into a 32-byte-aligned slot take that one by default; shorter rows are memcpy either way).  Several chunks per call,
+    sparse ids, rows re-pitched (70, 130) or not (768)."""
+    from arroy_amd import Dataset
+    rng = np.random.default_rng(dims)
+    vecs = rng.standard_normal((n, dims)).astype(np.float32)
+    ids = np.sort(rng.choice(4 * n, n, replace=False)).astype(np.uint32)
+    sets = []
+    for memcpy in (0, 1):
+        ds = Dataset(metric, dims, n)
+        with _lib.tuning(AH_STAGE_MEMCPY=memcpy):
+            ds.upload_vectors(ids[: n // 3], vecs[: n // 3])
+            ds.upload_vectors(ids[n // 3:], vecs[n // 3:])
+        if metric is D.DotProduct:
+            ds.preprocess_dot()
+        ds.finalize()
+        sets.append(ds)
+    _same_dataset(sets[0], sets[1], ids, [vecs[7], rng.standard_normal(dims).astype(np.float32)], f"AH_STAGE_MEMCPY, {metric.name} x {dims}")
+    if metric in (D.Cosine, D.Euclidean):  # ... and they are the caller's rows
+        for i in (0, n // 3, n - 1):
+            assert_bit_equal(sets[1].item_vector(int(ids[i])), vecs[i])
+    for ds in sets:
+        ds.close()
+
+
+@pytest.mark.parametrize("metric", [D.Euclidean, D.Cosine], ids=["euclidean", "cosine"])
+def test_upload_from_registered_caller_memory_stages_the_same_bytes(metric):
+    """AH_STAGE_REGISTER=1: rows that need no re-pitching (dims == pitch) travel straight from the caller's buffer, page-locked
+    for the duration of the call, from 64 MiB a call on — 65 536 x 256 f32 is exactly that — with the headers made on the device.
+    Where hipHostRegister refuses, the call falls through to the ring: the comparison holds either way."""
+    from arroy_amd import Dataset
+    n, dims = 65_536, 256
+    assert n * dims * 4 == 64 << 20
+    rng = np.random.default_rng(256 + metric.metric)
+    vecs = rng.standard_normal((n, dims)).astype(np.float32)
+    ids = np.arange(n, dtype=np.uint32) * 3 + 1
+    sets = []
+    for register in (0, 1):
+        ds = Dataset(metric, dims, n)
+        with _lib.tuning(AH_STAGE_REGISTER=register):
+            ds.upload_vectors(ids, vecs)
+        ds.finalize()
+        sets.append(ds)
+    _same_dataset(sets[0], sets[1], ids, [vecs[11], rng.standard_normal(dims).astype(np.float32)], f"AH_STAGE_REGISTER, {metric.name}")
+    for i in (0, 40_000, n - 1):
+        assert_bit_equal(sets[1].item_vector(int(ids[i])), vecs[i])
+    od = O.Data(metric.metric, vecs)
+    q, qh = od.query_leaf(vecs[11])
+    assert_bit_equal(sets[1].distances(query=vecs[11]), od.distances(q, qh), "registered upload vs the oracle")
+    for ds in sets:
+        ds.close()

@@ -98,3 +98,50 @@ def test_grouped_tail_with_caller_ids_and_a_cancel_flag():
             ds.build_forest(seeds, cancel=lambda: len(seen) >= plain.stats["levels"] - 2, progress=progress)
         assert ds.build_forest(seeds).digest()[0] == plain.digest()[0]  # and the dataset builds again afterwards
     ds.close()
+
+
+TAIL_CUTS = [(nodes, ratio) for nodes in (1, 8) for ratio in (10, 100)]
+
+
+@pytest.mark.parametrize("cls,dims,n,trees", [CASES[0], CASES[3], CASES[4]], ids=[c[0].__name__ for c in (CASES[0], CASES[3], CASES[4])])
+def test_where_the_tail_is_cut_and_how_its_groups_shrink_never_change_the_forest(cls, dims, n, trees):
+    """AH_BUILD_TAIL_NODE_ITEMS moves the level the tail starts at: the first node-major level whose nodes hold at most that many
+    x split_after items on average.  8: several levels earlier than the default 2.  1: never — the nodes of a level are the
+    ones with MORE than split_after items, so their average is never that small and the build stays level by level
+    (tail_groups == 0: the switch's way of saying "no tail").  AH_BUILD_TAIL_RATIO sizes the groups: 100 = equal groups,
+    10 = every group a tenth of the one before, i.e. the first group takes all trees but one each for the others.  Same forest
+    as the ungrouped build's and the oracle's, materialised and streamed."""
+    ds, oracle, _vecs, _ids = make_data(cls, n, dims, seed=3 * dims + n)
+    seeds = list(range(4100, 4100 + trees))
+    with _lib.tuning(AH_BUILD_TAIL_GROUPS=0):
+        plain = ds.build_forest(seeds)
+    assert plain.stats["tail_groups"] == 0
+    want = [plain.canonical(t) for t in range(trees)]
+    for t in (0, trees // 2, trees - 1):
+        assert want[t] == oracle.build_tree(0, seeds[t]).canonical(), t
+    digest = plain.digest()[0]
+    bq = cls.metric >= 4
+    # (tunables, must the tail run in groups at AH_BUILD_TAIL_NODE_ITEMS=8?) — as in the test above
+    configs = [({}, False), ({"AH_ROWMAJOR": 0}, True)]
+    for nodes, ratio in TAIL_CUTS:
+        for groups in (3, 32):
+            for knobs, must in configs:
+                what = (nodes, ratio, groups, knobs)
+                with _lib.tuning(AH_BUILD_TAIL_GROUPS=groups, AH_BUILD_TAIL_MIN_MB=0, AH_SCREEN_VERIFY=1, AH_BUILD_TAIL_NODE_ITEMS=nodes,
+                                 AH_BUILD_TAIL_RATIO=ratio, **knobs):
+                    forest = ds.build_forest(seeds)
+                    _roots, stats, got = ds.build_forest_stream(seeds)
+                if nodes == 1:
+                    assert forest.stats["tail_groups"] == 0, (what, forest.stats["tail_groups"])
+                elif must or bq:
+                    assert forest.stats["tail_groups"] == min(groups, trees), (what, forest.stats["tail_groups"])
+                assert forest.stats["screen_violations"] == 0
+                assert forest.digest()[0] == digest, what
+                assert forest.stats["margin_evaluations"] == plain.stats["margin_evaluations"]
+                assert forest.stats["split_nodes"] == plain.stats["split_nodes"]
+                assert [forest.canonical(t) for t in range(trees)] == want, what
+                assert stats["tail_groups"] == forest.stats["tail_groups"]
+                assert [got.canonical(t) for t in range(trees)] == want, what
+                forest.close()
+    plain.close()
+    ds.close()

@@ -99,7 +99,9 @@ def stage_int8(X, nv, dims, bias=None, second_digit=False):
     return mval, e
 
 
-def stage_binary16(X, nv, dims, bias=None):
+def stage_binary16(X, nv, dims, bias=None, gamma_s=None):
+    """(screen value, bound) of the binary16 stage.  gamma_s: None = the row-order kernels' (screen_device.h), or the value of
+    another product over the same copies (the dense MFMA screen's, forest.hip: `da.gamma_s`)."""
     hpitch = (dims + 63) // 64 * 64
     def shadow(v):
         h = v.astype(np.float16)
@@ -111,7 +113,7 @@ def stage_binary16(X, nv, dims, bias=None):
     xm = np.abs(X).max(axis=1)
     tiny = (xm != 0) & (xm < TINY)  # k_shadow_rows: f32 squares of such rows underflow -> stats +inf -> never decided
     ax, bx, cx = (np.where(tiny, F(np.inf), v).astype(F) for v in (ax, bx, cx))
-    gamma_s = F(4.0 * (2.0 * (hpitch // 16) + 8.0) * 5.9604645e-8)
+    gamma_s = F(4.0 * (2.0 * (hpitch // 16) + 8.0) * 5.9604645e-8) if gamma_s is None else F(gamma_s)
     s = (Xh.astype(np.float64) @ nh.astype(np.float64)).astype(F)  # any accumulation order: covered by gamma_s
     with np.errstate(invalid="ignore", over="ignore"):
         e = (bn * ax + cn * bx + gamma_s * (an * ax) + gamma_r(dims) * (cn * cx)).astype(F)
