@@ -9,7 +9,7 @@ Layout
 """
 from . import distances
 from ._lib import ArroyHipError, BuildCancelled, InvalidVecDimension, MissingKey, device_count, device_name
-from .dataset import Dataset, DatasetGroup, Filter, Forest, Index
+from .dataset import Dataset, DatasetGroup, Filter, Forest, Index, audit_view
 
-__all__ = ["distances", "Dataset", "DatasetGroup", "Filter", "Forest", "Index", "ArroyHipError", "BuildCancelled", "InvalidVecDimension", "MissingKey",
+__all__ = ["distances", "Dataset", "DatasetGroup", "Filter", "Forest", "Index", "audit_view", "ArroyHipError", "BuildCancelled", "InvalidVecDimension", "MissingKey",
            "device_count", "device_name"]

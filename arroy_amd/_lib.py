@@ -79,6 +79,24 @@ class AhIndexCompactStats(C.Structure):
                 ("reserved", C.c_uint32)]
 
 
+class AhTreeStats(C.Structure):
+    _fields_ = [("root", C.c_uint32), ("depth", C.c_uint32), ("split_nodes", C.c_uint32), ("dummy_normals", C.c_uint32),
+                ("descendants", C.c_uint32), ("reserved", C.c_uint32), ("items", C.c_uint64)]
+
+
+# AH_AUDIT_*: the classes of ah_index_audit_report.count / first_node, in order
+AUDIT_CLASSES = ("bad_root", "bad_link", "linked_twice", "floating", "bad_normal", "bad_list", "unsorted", "foreign", "duplicate",
+                 "missing")
+AUDIT_STRUCTURE = AUDIT_CLASSES[:6]
+
+
+class AhIndexAuditReport(C.Structure):
+    _fields_ = [("n_items", C.c_uint64), ("n_trees", C.c_uint64), ("nodes_in_use", C.c_uint64), ("nodes_reached", C.c_uint64),
+                ("count", C.c_uint64 * len(AUDIT_CLASSES)), ("first_node", C.c_uint32 * len(AUDIT_CLASSES)),
+                ("first_missing_tree", C.c_uint32), ("first_missing_id", C.c_uint32), ("first_duplicate_tree", C.c_uint32),
+                ("first_duplicate_id", C.c_uint32), ("valid", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class AhIndexInfo(C.Structure):
     _fields_ = [("n_nodes", C.c_uint64), ("desc_len", C.c_uint64), ("n_trees", C.c_uint32), ("n_normals", C.c_uint32),
                 ("normal_row_bytes", C.c_uint64), ("normal_header_floats", C.c_uint32), ("reserved", C.c_uint32)]
@@ -262,6 +280,9 @@ SIGNATURES = {
     # what a resident index holds, and the removal of its free slots and orphaned normal rows
     "ah_index_footprint_get": (C.c_int, [_VP, C.POINTER(AhIndexFootprint)]),
     "ah_index_compact": (C.c_int, [_VP, _U32P, C.POINTER(AhIndexCompactStats)]),
+    # `Reader::assert_validity` / `Reader::stats` of a resident index, and of a view the host holds
+    "ah_index_audit": (C.c_int, [_VP, C.POINTER(AhIndexAuditReport), C.POINTER(AhTreeStats)]),
+    "ah_forest_view_audit": (C.c_int, [_VP, C.POINTER(AhForestView), C.POINTER(AhIndexAuditReport), C.POINTER(AhTreeStats)]),
     "ah_index_suspend": (C.c_int, [_VP]),
     "ah_index_resume": (C.c_int, [_VP, _VP]),
     "ah_bench_scan": (C.c_int, [_VP, C.c_uint32, C.c_uint64, C.c_uint32, _F32P, C.POINTER(C.c_double)]),

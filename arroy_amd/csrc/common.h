@@ -180,7 +180,8 @@ inline int guarded(const char *what, F &&f) noexcept {
     X(SEARCH_SCREEN, "AH_SEARCH_SCREEN", 1)     /* 0: the re-rank of ah_search_batch never screens its candidates (f32 rows for all) */ \
     X(SEARCH_FILTER_GROUP_MIN, "AH_SEARCH_FILTER_GROUP_MIN", 16) /* ah_search_batch_filters: the queries of one filter form a sub-batch of their own from this many on; fewer share a mixed sub-batch */ \
     X(FILTER_COMBINE_SHORTCUT, "AH_FILTER_COMBINE_SHORTCUT", 1) /* 0: ah_filter_combine walks the ids of every leaf against the new bitmap, never derives a leaf's count from the operands' counts (DESIGN.md 4 "Combined filters") */ \
-    X(HOST_THREADS, "AH_HOST_THREADS", 8)      /* host threads one build may use at a time for its output path */        \
+    X(AUDIT_COVER_MB, "AH_AUDIT_COVER_MB", 64) /* ah_index_audit: budget for the coverage words (one bit per row and tree) of the trees audited in one pass, MiB; 0: one tree a pass (not measured: DESIGN.md 4 "Audit of a resident index") */ \
+    X(HOST_THREADS, "AH_HOST_THREADS", 8)     /* host threads one build may use at a time for its output path */        \
     X(DEVICE_CACHE_MB, "AH_DEVICE_CACHE_MB", 98304) /* idle HBM the caching allocator keeps while a dataset lives on the device */ \
     X(HOST_CACHE_MB, "AH_HOST_CACHE_MB", 16384) /* committed host memory of destroyed forests kept for the next build */   \
     X(CACHE_KEEP_IDLE, "AH_CACHE_KEEP_IDLE", 0) /* 1: keep both caches even when the last dataset (of a device / of the process) is destroyed */ \

@@ -738,6 +738,22 @@ class Index:
         _lib.check(_lib.lib().ah_index_footprint_get(self._h, C.byref(fp)))
         return {f: int(getattr(fp, f)) for f, _ in _lib.AhIndexFootprint._fields_}
 
+    def audit(self, trees: bool = False) -> dict:
+        """ah_index_audit: `Reader::assert_validity` of the index as it is on the device, nothing exported.  Returns the
+        counts by lower-case class name (_lib.AUDIT_CLASSES), `valid`, n_items / n_trees / nodes_in_use / nodes_reached,
+        `first_node` (class -> smallest offending node, BAD_ROOT: position in the roots; None: none) and the first_missing_* /
+        first_duplicate_* pairs (None: none); with trees=True also `tree_stats`, one dict per tree in the shape of
+        TreeStore.stats plus `root` and `items`.  Reads only; a finding is a result, not an error."""
+        rep = _lib.AhIndexAuditReport()
+        n_trees = self.export_info()["n_trees"] if trees else 0
+        ts = (_lib.AhTreeStats * max(1, n_trees))() if trees else None
+        _lib.check(_lib.lib().ah_index_audit(self._h, C.byref(rep), ts))
+        return _audit_dict(rep, ts, n_trees if trees else None)
+
+    def tree_stats(self) -> list:
+        """`Reader::stats` per tree (src/reader.rs:210-252), counted on the device: audit(trees=True)["tree_stats"]."""
+        return self.audit(trees=True)["tree_stats"]
+
     def compact(self, want_map: bool = False):
         """ah_index_compact: free node slots, orphaned normal rows and spare rows go; the index becomes what a fresh Index of
         the forest as it is now would be, node for node and row for row.  Returns the stats (sizes before / after, `moved`: 0
@@ -773,6 +789,47 @@ class Index:
             self.close()
         except Exception:
             pass
+
+
+def _audit_dict(rep, ts, n_trees) -> dict:
+    def some(v):
+        return None if int(v) == 0xFFFFFFFF else int(v)
+    out = {name: int(rep.count[c]) for c, name in enumerate(_lib.AUDIT_CLASSES)}
+    out.update(valid=int(rep.valid), n_items=int(rep.n_items), n_trees=int(rep.n_trees), nodes_in_use=int(rep.nodes_in_use),
+               nodes_reached=int(rep.nodes_reached),
+               first_node={name: some(rep.first_node[c]) for c, name in enumerate(_lib.AUDIT_CLASSES)})
+    # (0xFFFFFFFF is a legal id: whether there is a first pair is said by the count)
+    for cls, key in (("missing", "first_missing"), ("duplicate", "first_duplicate")):
+        has = out[cls] > 0
+        out[key + "_tree"] = int(getattr(rep, key + "_tree")) if has else None
+        out[key + "_id"] = int(getattr(rep, key + "_id")) if has else None
+    if n_trees is not None:
+        out["tree_stats"] = [{"root": int(t.root), "depth": int(t.depth), "split_nodes": int(t.split_nodes),
+                              "dummy_normals": int(t.dummy_normals), "descendants": int(t.descendants), "items": int(t.items)}
+                             for t in ts[:n_trees]]
+    return out
+
+
+def audit_view(ds: Dataset, view, trees: bool = False) -> dict:
+    """ah_forest_view_audit: Index.audit of arrays the host holds (an ah_forest_view: Forest.view_struct() or
+    TreeStore.to_view), without making an index of them.  What Index(ds, None, view=view) would refuse is counted."""
+    rep = _lib.AhIndexAuditReport()
+    n_trees = int(view.n_trees)
+    ts = (_lib.AhTreeStats * max(1, n_trees))() if trees else None
+    _lib.check(_lib.lib().ah_forest_view_audit(ds._h, C.cast(C.byref(view), C.POINTER(_lib.AhForestView)), C.byref(rep), ts))
+    return _audit_dict(rep, ts, n_trees if trees else None)
+
+
+def audit_findings(report: dict) -> str:
+    """The non-zero classes of an audit report and their first offenders, for an error message ('' when valid)."""
+    parts = []
+    for name in _lib.AUDIT_CLASSES:
+        if report[name]:
+            where = f"first at {'root position' if name == 'bad_root' else 'node'} {report['first_node'][name]}"
+            if name in ("missing", "duplicate"):
+                where = f"first: tree {report['first_' + name + '_tree']}, id {report['first_' + name + '_id']}"
+            parts.append(f"{name} {report[name]} ({where})")
+    return "; ".join(parts)
 
 
 class Filter:

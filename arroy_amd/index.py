@@ -367,6 +367,9 @@ class ArroyBuilder:
         self.device_insert = True
         # False: the resident index keeps its free node slots and orphaned normal rows whatever they amount to
         self.device_compact = True
+        # True: the index that serves the searches is audited on the device at the end of build() (Index.audit: validity
+        # and the per-tree stats against the store's); a finding raises AssertionError
+        self.device_audit = False
 
     def n_trees(self, n: int) -> "ArroyBuilder":
         self._n_trees = int(n)
@@ -463,6 +466,8 @@ class ArroyBuilder:
             from .dataset import Index
             st.index, st._keep = Index(ds, None, view=view), keep
             st.index_uploads += 1
+        if self.device_audit and st.index is not None:
+            _assert_audit(st.index.audit(trees=True), st.trees)
         st.metadata = {"dimensions": w.dimensions, "items": [int(i) for i in ids], "roots": list(st.trees.roots),
                        "distance": dist.name}  # src/writer.rs:611-626
         st.updated.clear()
@@ -674,6 +679,19 @@ class ArroyBuilder:
         return None
 
 
+def _assert_audit(report: dict, trees: Optional[TreeStore]) -> None:
+    """Raise AssertionError for an audit report (Index.audit / audit_view) with findings, or whose per-tree stats are not
+    those of the host's store."""
+    from .dataset import audit_findings
+    if not report["valid"]:
+        raise AssertionError("the index is not valid: " + audit_findings(report))
+    if trees is not None and "tree_stats" in report:
+        want = [trees.stats(r) for r in trees.roots]
+        got = [{k: t[k] for k in ("depth", "split_nodes", "dummy_normals", "descendants")} for t in report["tree_stats"]]
+        if got != want:
+            raise AssertionError(f"the tree stats of the index differ from the store's: {got} != {want}")
+
+
 class Reader:
     """`Reader<D>` (src/reader.rs:128-298)."""
 
@@ -718,6 +736,23 @@ class Reader:
     def stats(self) -> dict:  # src/reader.rs:210-252
         tr = self._st.trees
         return {"leaf": self.n_items(), "tree_stats": [tr.stats(r) for r in tr.roots] if tr else []}
+
+    def assert_validity(self) -> None:  # src/reader.rs:509-589
+        """Every tree reaches every item once, every list is ascending and holds only stored ids, and no tree node floats:
+        counted on the device, on the resident index when there is one (Index.audit), else on a view of the store
+        (audit_view).  Raises AssertionError with the non-zero classes and their first offenders."""
+        st = self._st
+        if st.index is not None:
+            report = st.index.audit()
+        elif st.dataset is not None and st.trees is not None:
+            from .dataset import audit_view
+            view, keep = st.trees.to_view(self.distance, self.dimensions())
+            report = audit_view(st.dataset, view)
+            del keep
+        else:  # no items: the reference checks that no tree node is left
+            assert st.trees is None or not st.trees.nodes, "tree nodes floating around in an index without items"
+            return
+        _assert_audit(report, None)
 
     def nns(self, count: int) -> "QueryBuilder":  # src/reader.rs:296-298
         return QueryBuilder(self, int(count))

@@ -53,7 +53,7 @@ extern "C" {
                                   ah_dataset_packed_rows and the test aid ah_debug_query_screen_verify;
                                   v7 additions: updates of a finalized dataset (ah_dataset_update_vectors / _records,
                                   ah_group_update_vectors / _records, the test aid ah_debug_update_paths);
-                                  ah_index_footprint_get / ah_index_compact */
+                                  ah_index_footprint_get / ah_index_compact; ah_index_audit / ah_forest_view_audit */
 
 /* every entry point is exported from the shared object (it is built with -fvisibility=hidden) */
 #if defined(__GNUC__)
@@ -898,6 +898,86 @@ typedef struct ah_index_compact_stats {
     uint32_t reserved;
 } ah_index_compact_stats;
 AH_API int ah_index_compact(ah_index *index, uint32_t *out_new_of_old, ah_index_compact_stats *out_stats);
+
+/* ------------------------------------------------------------------------------------------
+ * Audit of a resident index (ABI v7 additions: look the symbols up): `Reader::assert_validity` (src/reader.rs:509-589) and
+ * `Reader::stats` (src/reader.rs:210-252) where the forest lives.  After its first upload the host never sees an index
+ * again — deletes, inserts, grafts and compactions rewrite it in HBM, suspend / resume carry it across an update of the
+ * dataset — and three contracts of this header are stated, not checked: ids an update removed must leave the index before
+ * it is searched (ah_index_resume), the ids of a grafted sub-tree must be those of the node it replaces (ah_index_graft),
+ * and a view's lists must hold ascending ids that are rows of the dataset, every item once per tree
+ * (ah_index_create_from_view checks ranges and reachability only).  The audit answers "is this still a forest that
+ * reaches every item once per tree" without exporting anything: one level walk over the nodes and one read of the
+ * descendants, on the device.
+ *
+ * A node is IN USE when its kind is AH_NODE_SPLIT or AH_NODE_DESCENDANTS (0 is a free slot a delete left; anything else
+ * is an unknown kind: neither in use nor a legal target of a link).  A node is REACHED when a chain of valid links leads
+ * to it from a valid entry of roots[]; it is accounted once, under the tree (position in roots[]) that claimed it first.
+ * The classes, each a property of the arrays and not of the order the kernels ran in:
+ *   BAD_ROOT      entries of roots[] that are out of range or name a node that is not in use.  first_node: the smallest
+ *                 such POSITION in roots[].
+ *   BAD_LINK      child links of reached split nodes that are out of range or name a node that is not in use.
+ *                 first_node: the smallest split node holding one.
+ *   LINKED_TWICE  per node, links = valid root entries + valid child links of reached split nodes that name it; the class
+ *                 is the sum of (links - 1) over nodes with more than one, = links followed - nodes reached: a shared
+ *                 sub-tree, a cycle, a root that is also a child, a root named twice.  first_node: the smallest node with
+ *                 more than one link.
+ *   FLOATING      nodes in use that are not reached ("tree nodes floating around").
+ *   BAD_NORMAL    reached split nodes with a normal whose row is >= n_normals; for a view: whose record is out of the
+ *                 blob or misaligned.
+ *   BAD_LIST      reached Descendants nodes with offset + count > the length of the descendants.  Their ids are not read.
+ *   UNSORTED      reached Descendants nodes whose ids are not strictly ascending (equal neighbours count).
+ *   FOREIGN       id occurrences in reached lists that are no row of the dataset (0xFFFFFFFF is a legal id: foreign only
+ *                 when it is not stored).  first_node: the smallest node holding one.
+ *   DUPLICATE     per tree, occurrences of a stored id beyond its first.
+ *   MISSING       (tree, stored item) pairs where the tree holds no occurrence of the item.
+ * first_node of DUPLICATE / MISSING is the root of first_duplicate_tree / first_missing_tree.
+ *
+ * With the six structure counts (BAD_ROOT .. BAD_LIST) at 0, the list and coverage counts, the first_* fields and
+ * out_trees are exact.  With a structure violation only valid == 0, n_trees, nodes_in_use, nodes_reached, the structure
+ * counts, their first_node and out_trees[t].root are promised (a shared leaf is read under one of its trees).  With
+ * n_trees == 0 only FLOATING can be non-zero, as in the reference.
+ *
+ * ah_index_audit reads only, like ah_index_footprint_get: legal with live filters and concurrently with searches, not
+ * concurrent with a mutating call on the same index, refused while the index is suspended.  All or nothing about
+ * memory: every scratch block (three words per node slot, a few per tree, and the coverage words: one bit per row and
+ * tree of a group of trees, at most AH_AUDIT_COVER_MB MiB, default 64, or one tree's) is obtained before the first
+ * launch; a failed allocation returns AH_ERR_OUT_OF_MEMORY and holds nothing.  *out and out_trees are untouched on any
+ * error.  AH_OK whatever the findings: the report is the result, not a status.  out_trees: n_trees entries or NULL.
+ *
+ * ah_forest_view_audit audits arrays the host holds (nodes decoded from LMDB before ah_index_create_from_view, the view
+ * of a build) without making an index of them: it uploads nodes, roots and ids into scratch (not the normals: their
+ * offsets are judged on the host), runs the same kernels and frees the scratch.  It refuses only NULL pointers, sizes
+ * beyond 32 bits, a normal vector / header that does not fit the record stride and an unfinalized dataset; everything
+ * else ah_index_create_from_view refuses it COUNTS, so no ah_index with a broken structure ever exists.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct ah_tree_stats {     /* `TreeStats`, src/reader.rs:216-240 */
+    uint32_t root;                 /* node index of the tree's root */
+    uint32_t depth;                /* a root that is a Descendants node: 1 */
+    uint32_t split_nodes;
+    uint32_t dummy_normals;        /* split nodes with `normal: None` */
+    uint32_t descendants;          /* Descendants NODES, as in the reference */
+    uint32_t reserved;
+    uint64_t items;                /* ids in those nodes, with multiplicity */
+} ah_tree_stats;
+
+enum { AH_AUDIT_BAD_ROOT, AH_AUDIT_BAD_LINK, AH_AUDIT_LINKED_TWICE, AH_AUDIT_FLOATING, AH_AUDIT_BAD_NORMAL,
+       AH_AUDIT_BAD_LIST, AH_AUDIT_UNSORTED, AH_AUDIT_FOREIGN, AH_AUDIT_DUPLICATE, AH_AUDIT_MISSING, AH_AUDIT_CLASSES };
+
+/* (the report cannot carry the name of the call that fills it: in C a typedef and a function share one name space) */
+typedef struct ah_index_audit_report {
+    uint64_t n_items;              /* rows of the dataset */
+    uint64_t n_trees, nodes_in_use, nodes_reached;
+    uint64_t count[AH_AUDIT_CLASSES];
+    uint32_t first_node[AH_AUDIT_CLASSES]; /* smallest offending node index (BAD_ROOT: smallest position in roots[]); 0xFFFFFFFF: none */
+    uint32_t first_missing_tree, first_missing_id;   /* smallest (tree position, id) pair counted under MISSING */
+    uint32_t first_duplicate_tree, first_duplicate_id;
+    uint32_t valid;                /* 1 iff every count is 0 */
+    uint32_t reserved;
+} ah_index_audit_report;
+
+AH_API int ah_index_audit(ah_index *index, ah_index_audit_report *out, ah_tree_stats *out_trees);
+AH_API int ah_forest_view_audit(ah_dataset *ds, const ah_forest_view *view, ah_index_audit_report *out, ah_tree_stats *out_trees);
 
 /* An index outlives an update of its dataset.  An ah_index stores ITEM IDS, never row positions — its descendants are a
  * copy of the view's ids and every kernel goes from an id to its row through the dataset as it is at the time of the
