@@ -4066,7 +4066,12 @@ static int search_chunk(ah_index *ix, Context *ctx, const float *queries, const 
     const bool hash_fits = nns_stride <= kHashMaxCandidates && max_id != 0xFFFFFFFFu;
     // (never in a mixed sub-batch: the tiles read the kept ids of a leaf from ONE of its visits for all of them, k_leaf_tiles;
     // without them no descent is a last pass, so k_descend_multi and the units of a single query are out as well)
-    const bool tiles = !mixed && tun(TUN_SEARCH_TILES) != 0 && (bitmap_fits || hash_fits) && !big_k && ds->dims >= 32 &&
+    // (count <= kSelectCap: the selections behind the tiles hold kSelectCap keys and select at least min(count, distinct
+    // candidates) of them, so a larger count could only do the whole tile pass, overflow and be redone — after an int8 pass and
+    // its binary16 retry where that stage is on, each noted as a failure of the int8 stage in its window of 64 sub-batches.
+    // Unless a query cannot have more than kSelectCap candidates at all: a count meant as "everything" under a small search_k)
+    const bool tiles = !mixed && tun(TUN_SEARCH_TILES) != 0 && (bitmap_fits || hash_fits) && !big_k &&
+                       (k <= kSelectCap || nns_stride <= kSelectCap) && ds->dims >= 32 &&
                        ix->max_desc <= 65535u * kTileSlab &&
                        (ds->metric == AH_EUCLIDEAN || ds->metric == AH_COSINE || ds->metric == AH_DOT_PRODUCT);
     const uint32_t visit_cap = (uint32_t)std::min<uint64_t>((uint64_t)nq * nns_stride, 2u << 20);

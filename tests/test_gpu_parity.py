@@ -755,7 +755,12 @@ def test_device_search_sort_dedup_paths_agree(last_id):
 def test_device_search_leaf_tiles_equal_the_sorted_path(metric, dims):
     """ah_search_batch by leaf tiles (rows of a leaf x the queries that reached it, duplicates flagged, order by
     (distance, id)) and by sort + dedup + row-major re-rank: the same bits.  Queries in clusters of 1..7 near copies so
-    that leaves are shared by 1, 2, 3, 4 and more queries; equal vectors under different ids for the ties."""
+    that leaves are shared by 1, 2, 3, 4 and more queries; equal vectors under different ids for the ties.
+    The stats of the tile call say that the tiles served it (a call they silently left to the sorted path would compare that
+    path with itself): always for count <= 100; for count = 1000 of 6000 candidates, which is near the 1024 keys the
+    selection holds, what search_select_inputs.selection says of the oracle's candidate distances (Euclidean: the other two
+    are screened first); count = 1500 is beyond that capacity and starts on the sorted path (test_gpu_search_select.py)."""
+    import search_select_inputs as S
     from arroy_amd._lib import tuning
     cls = D.BY_METRIC[metric]
     n = 30000
@@ -776,7 +781,25 @@ def test_device_search_leaf_tiles_equal_the_sorted_path(metric, dims):
         res = {}
         for t in (1, 0, 2):  # 2: the tiles after the descent of one octet per query
             with tuning(AH_SEARCH_TILES=min(t, 1), AH_SEARCH_WAVE=1 if t < 2 else 0):
+                index.stats(reset=True)
                 res[t] = index.search(count, queries=queries, search_k=sk, candidates=cand, raw=True)
+                if t == 1:
+                    st = index.stats()
+        nq = len(queries)
+        if count <= 100:
+            assert st["rerank_tiles"] == nq and st["fallback_chunks"] == 0 and st["rerank_sorted"] == 0, (count, sk, st)
+        elif count > S.CAP:
+            assert st["rerank_sorted"] == nq and st["rerank_tiles"] == 0 and st["fallback_chunks"] == 0, (count, sk, st)
+        elif metric == 0:
+            fits = True
+            for q in queries:
+                qv, qh = oracle.query_leaf(q)
+                _, cands = O.search(oracle, forest, qv, qh, count, sk)
+                fits = fits and S.selection(S.ordered_words(oracle.distances(qv, qh, cands)), count)["served"]
+            if fits:
+                assert st["rerank_tiles"] == nq and st["fallback_chunks"] == 0, (count, sk, st)
+            else:
+                assert st["fallback_chunks"] == 1 and st["fallback_select"] == 1 and st["rerank_sorted"] == nq, (count, sk, st)
         for t in (0, 2):
             assert np.array_equal(res[1][2], res[t][2]) and np.array_equal(res[1][0], res[t][0]), (count, sk, t)
             assert np.array_equal(res[1][1].view(np.uint32), res[t][1].view(np.uint32)), (count, sk, t)
@@ -815,7 +838,10 @@ def test_device_search_leaf_tiles_leave_non_finite_distances_to_the_sorted_path(
     res = {}
     for t in (1, 0):
         with tuning(AH_SEARCH_TILES=t):
+            index.stats(reset=True)
             res[t] = index.search(40, queries=queries, search_k=2000, raw=True)
+            st = index.stats()
+            assert st["fallback_non_finite"] == t and st["fallback_chunks"] == t and st["rerank_sorted"] == 4, (t, st)
     assert np.array_equal(res[1][0], res[0][0]) and np.array_equal(res[1][1].view(np.uint32), res[0][1].view(np.uint32))
     assert np.isinf(res[1][1]).any()
     for qi in range(4):

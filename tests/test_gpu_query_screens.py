@@ -11,6 +11,7 @@ import pytest
 from arroy_amd import Dataset, _lib, shard
 from arroy_amd import distances as D
 from oracle import oracle as O
+from search_select_inputs import clustered  # (shared with test_gpu_search_select.py: one definition of the near-tie cluster)
 
 pytestmark = pytest.mark.gpu
 
@@ -135,13 +136,6 @@ def test_rerank_thresholds_of_the_screened_path():
     out, st, v = run(ds2, qs5[:3], lists, 10)
     assert st["queries_screened"] == 0 and v["checked"] == 0, (st, v)
     check_oracle(oracle2, qs5[:3], lists, 10, out, [0, 2])
-
-
-def clustered(rng, n_far, n_near, dims, spread):
-    centre = rng.standard_normal(dims).astype(np.float32)
-    near = centre + (rng.standard_normal((n_near, dims)) * spread).astype(np.float32)
-    far = rng.standard_normal((n_far, dims)).astype(np.float32)
-    return np.concatenate([near, far]).astype(np.float32), centre
 
 
 @pytest.mark.parametrize("cls", METRICS, ids=["cosine", "dot"])
