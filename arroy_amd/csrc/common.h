@@ -4,6 +4,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -546,6 +547,23 @@ struct ContextLease {
         if (c) ds->release(c);
     }
 };
+
+// blocks of `per_block` items for `work` of them: at least one, at most `cap` (the kernels stride over the rest)
+inline unsigned grid_of(uint64_t work, uint64_t per_block, unsigned cap) {
+    return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((work + per_block - 1) / per_block, cap));
+}
+
+// a block of the device allocator for a short-lived buffer of `what` ("the update", "the index update", ...); never 0 bytes
+inline int alloc(DevMem *m, size_t bytes, const char *what) {
+    const hipError_t e = dev_malloc(&m->p, std::max<size_t>(bytes, 1));
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        set_error("device allocation of %zu bytes for %s failed: %s", bytes, what, hipGetErrorString(e));
+        set_error_status(e == hipErrorOutOfMemory ? AH_ERR_OUT_OF_MEMORY : AH_ERR_DEVICE);
+        return e == hipErrorOutOfMemory ? AH_ERR_OUT_OF_MEMORY : AH_ERR_DEVICE;
+    }
+    return AH_OK;
+}
 
 // ---- launchers implemented in the kernel translation units ------------------------------------
 // distance.hip

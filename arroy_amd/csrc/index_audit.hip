@@ -21,6 +21,7 @@
 #include "common.h"
 #include "device_math.h"
 #include "index_device.h"
+#include "index_workspace.h"
 
 using namespace ah;
 
@@ -58,10 +59,6 @@ struct AuditArgs {
     unsigned long long *tree_items;
     AuditCtl *ctl;
 };
-
-unsigned grid_of(uint64_t work, uint64_t per_block, unsigned cap) {
-    return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((work + per_block - 1) / per_block, cap));
-}
 
 __device__ __forceinline__ bool kind_valid(uint32_t kind) {
     const uint32_t k = kind & 0xFFu;
@@ -304,16 +301,7 @@ __global__ __launch_bounds__(kAuBlock) void k_audit_compare(AuditCtl *ctl, DataV
     }
 }
 
-int alloc(DevMem *m, size_t bytes) {
-    const hipError_t e = dev_malloc(&m->p, std::max<size_t>(bytes, 1));
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        set_error("device allocation of %zu bytes for the index audit failed: %s", bytes, hipGetErrorString(e));
-        set_error_status(e == hipErrorOutOfMemory ? AH_ERR_OUT_OF_MEMORY : AH_ERR_DEVICE);
-        return e == hipErrorOutOfMemory ? AH_ERR_OUT_OF_MEMORY : AH_ERR_DEVICE;
-    }
-    return AH_OK;
-}
+int alloc(DevMem *m, size_t bytes) { return ah::alloc(m, bytes, "the index audit"); }
 
 // the forest to audit; on the device unless the up_* pointers say where the host holds it (a view: uploaded into scratch)
 struct AuditIn {
@@ -326,10 +314,9 @@ struct AuditIn {
 };
 
 int audit_run(ah_dataset *ds, const AuditIn &in, ah_index_audit_report *out, ah_tree_stats *out_trees) {
-    AH_HIP(hipSetDevice(ds->device));
-    ContextLease lease(ds);
-    AH_REQUIRE(lease.c, AH_ERR_DEVICE, "cannot create a HIP stream");
-    const hipStream_t s = lease.c->stream;
+    IndexCall call;
+    AH_TRY(call.begin(ds));
+    const hipStream_t s = call.stream();
     const DataView dv = ds->view();
     const uint32_t nn = in.n_nodes, n_trees = in.n_trees;
     // the tree groups: as many trees' coverage words as fit the budget
@@ -338,10 +325,11 @@ int audit_run(ah_dataset *ds, const AuditIn &in, ah_index_audit_report *out, ah_
     uint32_t group = n_trees;
     if (words) group = (uint32_t)std::min<uint64_t>(n_trees, std::max<uint64_t>(1, budget / (words * 4)));
     // every block the audit needs, before the first launch or copy
-    const size_t tree_bytes = (size_t)n_trees * (sizeof(TreeWords) + 8);
-    const size_t work_bytes = sizeof(AuditCtl) + tree_bytes + 3 * (size_t)nn * 4;
+    AuditArgs a{};
+    const Workspace ws = audit_workspace(a, nn, n_trees, sizeof(AuditCtl) / 4, sizeof(TreeWords) / 4);
     DevMem work, cover, up_nodes, up_roots, up_desc;
-    AH_TRY(alloc(&work, work_bytes));
+    AH_TRY(alloc(&work, ws.bytes()));
+    ws.carve(work.p, ws.bytes());
     AH_TRY(alloc(&cover, (size_t)(words * group) * 4));
     if (in.up_nodes) AH_TRY(alloc(&up_nodes, (size_t)nn * sizeof(DNode)));
     if (in.up_roots) AH_TRY(alloc(&up_roots, (size_t)n_trees * 4));
@@ -349,7 +337,6 @@ int audit_run(ah_dataset *ds, const AuditIn &in, ah_index_audit_report *out, ah_
     std::vector<TreeWords> tree_words(n_trees);
     std::vector<unsigned long long> tree_items(n_trees);
     std::vector<uint32_t> roots(n_trees);
-    AuditArgs a{};
     a.nodes = in.up_nodes ? up_nodes.as<const DNode>() : in.nodes;
     a.roots = in.up_roots ? up_roots.as<const uint32_t>() : in.roots;
     a.desc = in.up_desc ? up_desc.as<const uint32_t>() : in.desc;
@@ -357,34 +344,23 @@ int audit_run(ah_dataset *ds, const AuditIn &in, ah_index_audit_report *out, ah_
     a.n_trees = n_trees;
     a.desc_len = in.desc_len;
     a.n_normals = in.n_normals;
-    uint8_t *w = work.as<uint8_t>();
-    a.ctl = reinterpret_cast<AuditCtl *>(w);
-    a.tree_items = reinterpret_cast<unsigned long long *>(w + sizeof(AuditCtl));
-    a.tree = reinterpret_cast<TreeWords *>(w + sizeof(AuditCtl) + (size_t)n_trees * 8);
-    a.owner = reinterpret_cast<uint32_t *>(w + sizeof(AuditCtl) + tree_bytes);
-    a.links = a.owner + nn;
-    a.order = a.links + nn;
     if (in.up_nodes && nn) AH_HIP(hipMemcpyAsync(up_nodes.p, in.up_nodes, (size_t)nn * sizeof(DNode), hipMemcpyHostToDevice, s));
     if (in.up_roots && n_trees) AH_HIP(hipMemcpyAsync(up_roots.p, in.up_roots, (size_t)n_trees * 4, hipMemcpyHostToDevice, s));
     if (in.up_desc && in.desc_len) AH_HIP(hipMemcpyAsync(up_desc.p, in.up_desc, (size_t)in.desc_len * 4, hipMemcpyHostToDevice, s));
-    AH_HIP(hipMemsetAsync(work.p, 0, work_bytes, s));
+    AH_HIP(hipMemsetAsync(work.p, 0, ws.zeroed_bytes(), s));
     AH_HIP(hipMemsetAsync(&a.ctl->first_node[0], 0xFF, sizeof(AuditCtl) - offsetof(AuditCtl, first_node), s));
     // 1. walk
     AuditCtl ctl{};
     uint32_t begin = 0, end = 0;
     if (n_trees) {
         hipLaunchKernelGGL(k_audit_seed, dim3(grid_of(n_trees, kAuBlock, 1024)), dim3(kAuBlock), 0, s, a);
-        AH_HIP(hipGetLastError());
-        AH_HIP(hipMemcpyAsync(&end, &a.ctl->tail, 4, hipMemcpyDeviceToHost, s));
-        AH_HIP(hipStreamSynchronize(s));
+        AH_TRY(read_back(&end, &a.ctl->tail, 1, s));
         AH_REQUIRE(end <= nn, AH_ERR_DEVICE, "the audit's walk claimed more nodes than the forest has");
     }
     for (uint32_t depth = 1; begin < end; depth++) {
         hipLaunchKernelGGL(k_audit_level, dim3(grid_of(end - begin, kAuBlock, 4096)), dim3(kAuBlock), 0, s, a, begin, end, depth);
-        AH_HIP(hipGetLastError());
         uint32_t tail = 0;
-        AH_HIP(hipMemcpyAsync(&tail, &a.ctl->tail, 4, hipMemcpyDeviceToHost, s));
-        AH_HIP(hipStreamSynchronize(s));
+        AH_TRY(read_back(&tail, &a.ctl->tail, 1, s));
         AH_REQUIRE(tail >= end && tail <= nn, AH_ERR_DEVICE, "the audit's walk claimed more nodes than the forest has");
         begin = end;
         end = tail;
@@ -393,15 +369,13 @@ int audit_run(ah_dataset *ds, const AuditIn &in, ah_index_audit_report *out, ah_
     if (nn) hipLaunchKernelGGL(k_audit_nodes, dim3(grid_of(nn, kAuBlock, 4096)), dim3(kAuBlock), 0, s, a);
     AH_HIP(hipGetLastError());
     // 3. lists and 4. compare, tree group by tree group
-    const uint32_t span = (uint32_t)std::min<long long>(std::max<uint32_t>(nn, 1), std::max<long long>(1, tun(TUN_LAUNCH_MAX_ITEMS)));
     for (uint32_t t0 = 0; t0 < n_trees; t0 += group) {
         const uint32_t n_group = std::min(group, n_trees - t0);
         if (words) AH_HIP(hipMemsetAsync(cover.p, 0, (size_t)(words * n_group) * 4, s));
-        for (uint32_t lo = 0; lo < nn; lo += span) {
-            const uint32_t hi = std::min(nn - lo, span) + lo;
-            hipLaunchKernelGGL(k_audit_lists, dim3(grid_of(hi - lo, kAuBlock / 64, 1u << 16)), dim3(kAuBlock), 0, s, a, dv, lo, hi, t0, t0 + n_group,
-                               cover.as<uint32_t>(), words);
-        }
+        for_spans(nn, call.span(), [&](uint64_t lo, uint64_t hi) {
+            hipLaunchKernelGGL(k_audit_lists, dim3(grid_of(hi - lo, kAuBlock / 64, 1u << 16)), dim3(kAuBlock), 0, s, a, dv, (uint32_t)lo, (uint32_t)hi,
+                               t0, t0 + n_group, cover.as<uint32_t>(), words);
+        });
         if (words)
             hipLaunchKernelGGL(k_audit_compare, dim3(grid_of(words * n_group, kAuBlock, 4096)), dim3(kAuBlock), 0, s, a.ctl, dv,
                                cover.as<const uint32_t>(), words, t0, n_group);
@@ -507,20 +481,12 @@ int ah_forest_view_audit(ah_dataset *ds, const ah_forest_view *view, ah_index_au
     uint32_t n_normals = 0;
     for (uint64_t i = 0; i < v.n_nodes; i++) {
         const ah_node &nd = v.nodes[i];
-        DNode d{};
-        d.kind = nd.kind;
-        if (nd.kind == AH_NODE_SPLIT) {
-            d.a = nd.left;
-            d.b = nd.right;
-            if (nd.has_normal) {
-                d.kind |= 0x100u;
-                const bool ok = (nd.offset & 3) == 0 && nd.offset <= v.normals_len && v.normal_stride <= v.normals_len - nd.offset;
-                d.c = ok ? n_normals++ : kNone;
-            }
-        } else if (nd.kind == AH_NODE_DESCENDANTS) {
-            const bool ok = nd.offset <= v.descendants_len && nd.count <= v.descendants_len - nd.offset;
-            d.a = ok ? (uint32_t)nd.offset : kNone;
-            d.b = nd.count;
+        DNode d = to_device_node(nd, n_normals);
+        if (d.kind & 0x100u) {
+            if ((nd.offset & 3) == 0 && nd.offset <= v.normals_len && v.normal_stride <= v.normals_len - nd.offset) n_normals++;
+            else d.c = kNone;
+        } else if (nd.kind == AH_NODE_DESCENDANTS && !(nd.offset <= v.descendants_len && nd.count <= v.descendants_len - nd.offset)) {
+            d.a = kNone;
         }
         nodes[i] = d;
     }

@@ -1,6 +1,13 @@
-// index_device.h — what search.hip (the searches and the routing of an ah_index) and index_update.hip (its deletes, inserts,
-// grafts, export, suspend / resume) share: the device node record, the index handle and the id-list -> bitmap kernel.
+// index_device.h — what search.hip (the searches and the routing of an ah_index), index_update.hip (its deletes, inserts,
+// grafts, compaction, export, suspend / resume) and index_audit.hip (its audit) share.  Device side: the node record and the
+// id-list -> bitmap kernel.  Host side: the index handle, the two conversions between the ABI's ah_node and the node record,
+// and the scaffolding of a maintenance call — IndexCall (device, stream lease, launch span, phase clock), for_spans,
+// read_back, and IndexCommit / index_commit, the one place where new arrays are swapped into an index and its normals view
+// is derived from them.  The layouts of the calls' workspaces are in index_workspace.h.
 #pragma once
+
+#include <chrono>
+#include <optional>
 
 #include "common.h"
 
@@ -12,6 +19,30 @@ struct DNode {
     uint32_t b;     // SPLIT: right           DESCENDANTS: count
     uint32_t c;     // SPLIT: normal row      DESCENDANTS: unused
 };
+
+// The ABI's node -> the device's.  `row`: the normal row a split node with a plane gets (c; the caller counts the rows).  A
+// record that is neither kind keeps its kind and nothing else: the views the index calls take hold none (validate_forest_view),
+// the audit counts them.
+inline DNode to_device_node(const ah_node &nd, uint32_t row) {
+    if (nd.kind == AH_NODE_SPLIT) return nd.has_normal ? DNode{nd.kind | 0x100u, nd.left, nd.right, row} : DNode{nd.kind, nd.left, nd.right, 0};
+    if (nd.kind == AH_NODE_DESCENDANTS) return DNode{nd.kind, (uint32_t)nd.offset, nd.count, 0};
+    return DNode{nd.kind, 0, 0, 0};
+}
+// ... and back: `offset` of a split node is its normal row, a free slot (kind 0) is all zeros
+inline ah_node to_host_node(const DNode &d) {
+    ah_node nd{};
+    nd.kind = (uint8_t)(d.kind & 0xFFu);
+    if (nd.kind == AH_NODE_SPLIT) {
+        nd.has_normal = (d.kind & 0x100u) ? 1 : 0;
+        nd.left = d.a;
+        nd.right = d.b;
+        nd.offset = d.c;
+    } else if (nd.kind == AH_NODE_DESCENDANTS) {
+        nd.offset = d.a;
+        nd.count = d.b;
+    }
+    return nd;
+}
 
 // one bit per listed id (ah_filter_create, the candidate list of ah_search_batch, the ids of ah_index_delete_items)
 static __global__ void k_filter_bitmap(const uint32_t *__restrict__ ids, uint64_t n, uint32_t *bits) {
@@ -58,6 +89,98 @@ struct ah_index {
     AH_REQUIRE(!(ix)->suspended, AH_ERR_INVALID_ARGUMENT, "the index is suspended (ah_index_suspend): ah_index_resume it first")
 
 namespace ah {
+// ---- the scaffolding of a maintenance call.  IndexCall: the device of the dataset made current, a stream context leased from
+// it for the call, and what every call reads off them
+struct IndexCall {
+    using Clock = std::chrono::steady_clock;
+    std::optional<ContextLease> lease;
+    bool timing = false;  // AH_TIMING: the phases are timed, and phase_end() waits for the stream
+    Clock::time_point t0;
+
+    int begin(ah_dataset *ds) {
+        AH_HIP(hipSetDevice(ds->device));
+        lease.emplace(ds);
+        AH_REQUIRE(lease->c, AH_ERR_DEVICE, "cannot create a HIP stream");
+        timing = tun(TUN_TIMING) != 0;
+        t0 = Clock::now();
+        return AH_OK;
+    }
+    hipStream_t stream() const { return lease->c->stream; }
+    // items a launch of a pass takes at most (AH_LAUNCH_MAX_ITEMS)
+    static uint64_t span() { return (uint64_t)std::max<long long>(1, tun(TUN_LAUNCH_MAX_ITEMS)); }
+    static Clock::time_point now() { return Clock::now(); }
+    Clock::time_point phase_end() const {
+        if (timing) (void)hipStreamSynchronize(stream());
+        return now();
+    }
+    static double secs(Clock::time_point x, Clock::time_point y) { return std::chrono::duration<double>(y - x).count(); }
+};
+
+// fn(lo, hi) for [0, total) in runs of at most `span`
+template <class F>
+inline void for_spans(uint64_t total, uint64_t span, F &&fn) {
+    for (uint64_t lo = 0; lo < total; lo += span) fn(lo, std::min<uint64_t>(total, lo + span));
+}
+
+// what the launches queued so far left in `words` 32-bit words on the device, once they are through
+inline int read_back(void *host, const void *dev, size_t words, hipStream_t s) {
+    AH_HIP(hipGetLastError());
+    AH_HIP(hipMemcpyAsync(host, dev, words * 4, hipMemcpyDeviceToHost, s));
+    AH_HIP(hipStreamSynchronize(s));
+    return AH_OK;
+}
+
+// the normals view of an index from its arrays and counts: after EVERY change of d_nrows / d_nhdrs / n_normals
+inline void index_derive_normals_view(ah_index *ix) {
+    const bool bq = metric_is_bq(ix->ds->metric);
+    ix->nv.rows_f32 = bq ? nullptr : reinterpret_cast<const float *>(ix->d_nrows);
+    ix->nv.rows_bq = bq ? reinterpret_cast<const uint64_t *>(ix->d_nrows) : nullptr;
+    ix->nv.headers = ix->d_nhdrs;
+    ix->nv.n = ix->n_normals;
+}
+
+// What a call made of an index: the new arrays (nullptr: that array stays; the normal rows and headers come together, with the
+// rows they have room for) and the counts afterwards, which start as the index's own.
+struct IndexCommit {
+    DevMem *nodes, *roots, *desc, *rank, *nrows, *nhdrs;
+    bool drop_rank = false;  // the call has renumbered the nodes: no holes, no ranks
+    uint32_t normals_cap, n_trees, n_nodes, n_normals, max_desc, n_leaves;
+    uint64_t desc_len;
+    bool compacted;
+    IndexCommit(const ah_index *ix, DevMem *nodes, DevMem *roots, DevMem *desc, DevMem *rank, DevMem *nrows = nullptr, DevMem *nhdrs = nullptr)
+        : nodes(nodes), roots(roots), desc(desc), rank(rank), nrows(nrows), nhdrs(nhdrs), normals_cap(ix->normals_cap), n_trees(ix->n_trees),
+          n_nodes(ix->n_nodes), n_normals(ix->n_normals), max_desc(ix->max_desc), n_leaves(ix->n_leaves), desc_len(ix->desc_len),
+          compacted(ix->compacted) {}
+};
+// The commit: nothing here can fail.  The old arrays go into the DevMems the new ones came in, which free them when the call
+// returns (dev_free waits for the device).
+inline void index_commit(ah_index *ix, const IndexCommit &c) {
+    NoFailScope no_fail;
+    auto swap_in = [](auto *&mine, DevMem *theirs) {
+        if (!theirs) return;
+        void *old = mine;
+        mine = static_cast<decltype(+mine)>(theirs->p);
+        theirs->p = old;
+    };
+    swap_in(ix->d_nodes, c.nodes);
+    swap_in(ix->d_roots, c.roots);
+    swap_in(ix->d_desc, c.desc);
+    swap_in(ix->d_rank, c.rank);
+    swap_in(ix->d_nrows, c.nrows);
+    swap_in(ix->d_nhdrs, c.nhdrs);
+    DevMem no_rank;
+    if (c.drop_rank) swap_in(ix->d_rank, &no_rank);
+    ix->normals_cap = c.normals_cap;
+    ix->n_trees = c.n_trees;
+    ix->n_nodes = c.n_nodes;
+    ix->n_normals = c.n_normals;
+    ix->max_desc = c.max_desc;
+    ix->n_leaves = c.n_leaves;
+    ix->desc_len = c.desc_len;
+    ix->compacted = c.compacted;
+    index_derive_normals_view(ix);
+}
+
 // search.hip: the copies of the rows the certified top-k screen of the searches reads, made when an index starts to serve a
 // dataset (ah_index_create*, ah_index_resume).  No memory for them = no screen, not an error.
 void index_prepare_screens(ah_dataset *ds);

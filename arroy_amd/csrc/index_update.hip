@@ -1,6 +1,9 @@
 // index_update.hip — ah_index_delete_items / ah_index_insert_items / ah_index_graft / ah_index_compact / ah_index_footprint_get /
-// ah_index_export / ah_index_suspend / ah_index_resume (include/arroy_hip.h).  The inserts, the grafts and the compaction are
-// described above their kernels; the delete is the part of an
+// ah_index_export / ah_index_suspend / ah_index_resume (include/arroy_hip.h): the kernels of the four updates, each call's host
+// function (delete_impl, insert_impl, graft_impl, compact_count / footprint_impl / compact_impl) and the entry points.  What the
+// host functions share is not here: the call scope, the span loop, the read-back, the commit and the node conversions are in
+// index_device.h, the workspace layouts in index_workspace.h, grid_of and the allocation helper in common.h.  The inserts, the
+// grafts and the compaction are described above their kernels; the delete is the part of an
 // incremental `Writer::build` that takes the updated ids out of every tree (`delete_items_from_trees`, src/writer.rs:978-1114)
 // done where the forest lives, so that the index of the last build serves the routing of the next one instead of being
 // uploaded again.
@@ -21,13 +24,13 @@
 //                fresh view, which the coin of ah_route_items is keyed by), the sorted roots and the delta; read back; the
 //                index's pointers are swapped last.
 #include <algorithm>
-#include <chrono>
 #include <memory>
 #include <vector>
 
 #include "common.h"
 #include "device_math.h"
 #include "index_device.h"
+#include "index_workspace.h"
 #include "scan_device.h"
 
 using namespace ah;
@@ -72,10 +75,6 @@ struct DeleteArgs {
     // what the scans gave (set before the write pass): every store into the new blob and the delta is checked against them
     uint32_t new_desc_len, n_changed, delta_desc_len;
 };
-
-unsigned grid_of(uint64_t work, uint64_t per_block, unsigned cap) {
-    return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((work + per_block - 1) / per_block, cap));
-}
 
 __global__ __launch_bounds__(kIxBlock) void k_delete_seed(DeleteArgs a, const uint32_t *__restrict__ roots, uint32_t n_trees) {
     const uint32_t stride = gridDim.x * blockDim.x;
@@ -880,58 +879,35 @@ __global__ __launch_bounds__(kIxBlock) void k_compact_rows(const uint8_t *__rest
     }
 }
 
-int alloc(DevMem *m, size_t bytes) {
-    const hipError_t e = dev_malloc(&m->p, std::max<size_t>(bytes, 1));
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        set_error("device allocation of %zu bytes for the index update failed: %s", bytes, hipGetErrorString(e));
-        set_error_status(e == hipErrorOutOfMemory ? AH_ERR_OUT_OF_MEMORY : AH_ERR_DEVICE);
-        return e == hipErrorOutOfMemory ? AH_ERR_OUT_OF_MEMORY : AH_ERR_DEVICE;
-    }
-    return AH_OK;
-}
+int alloc(DevMem *m, size_t bytes) { return ah::alloc(m, bytes, "the index update"); }
 
 int delete_impl(ah_index *ix, const uint32_t *ids, size_t n, uint32_t split_after, ah_index_delta *delta) {
-    auto now = [] { return std::chrono::steady_clock::now(); };
-    const bool timing = tun(TUN_TIMING) != 0;
-    ah_dataset *ds = ix->ds;
-    AH_HIP(hipSetDevice(ds->device));
-    ContextLease lease(ds);
-    AH_REQUIRE(lease.c, AH_ERR_DEVICE, "cannot create a HIP stream");
-    const hipStream_t s = lease.c->stream;
-    auto phase_end = [&]() -> std::chrono::steady_clock::time_point {
-        if (timing) (void)hipStreamSynchronize(s);
-        return now();
-    };
-    const auto t0 = now();
+    IndexCall call;
+    AH_TRY(call.begin(ix->ds));
+    const hipStream_t s = call.stream();
     const uint32_t nn = ix->n_nodes, n_trees = ix->n_trees;
     const uint64_t old_desc_len = ix->desc_len;
     // every buffer whose size is known now; kernels write only into these
     const uint64_t len_bits = n ? (uint64_t)ids[n - 1] + 1 : 0;
     const size_t bit_words = (size_t)((len_bits + 31) / 32);
-    const size_t per_node = (size_t)nn + 1;
-    const size_t scan_tiles = (nn + kScanTile - 1) / kScanTile + 1;
-    const size_t work_words = 10 * per_node + scan_tiles + CTL_WORDS;
-    DevMem bitmap, work, new_nodes, new_roots, new_rank, new_desc, out;
-    AH_TRY(alloc(&bitmap, (bit_words + n) * 4));
-    AH_TRY(alloc(&work, work_words * 4));
-    AH_TRY(alloc(&new_nodes, (size_t)nn * sizeof(DNode)));
-    AH_TRY(alloc(&new_roots, (size_t)n_trees * 4));
-    AH_TRY(alloc(&new_rank, per_node * 4));
-    delta->roots.resize(n_trees);
-    uint32_t *w = work.as<uint32_t>();
     DeleteArgs a{};
     a.nodes = ix->d_nodes;
     a.n_nodes = nn;
     a.desc = ix->d_desc;
-    a.bits = n ? bitmap.as<const uint32_t>() : nullptr;
     a.len_bits = len_bits;
     a.split_after = split_after;
-    uint32_t **fields[10] = {&a.order, &a.rep, &a.cnt, &a.flags, &a.own, &a.seg, &a.chg, &a.dseg, &a.cursor, &a.merged};
-    for (int i = 0; i < 10; i++) *fields[i] = w + (size_t)i * per_node;
-    uint32_t *tile_sums = w + 10 * per_node;
-    a.ctl = tile_sums + scan_tiles;
-    AH_HIP(hipMemsetAsync(work.p, 0, work_words * 4, s));
+    uint32_t *tile_sums = nullptr;
+    const Workspace ws = delete_workspace(a, &tile_sums, nn, kScanTile, CTL_WORDS);
+    DevMem bitmap, work, new_nodes, new_roots, new_rank, new_desc, out;
+    AH_TRY(alloc(&bitmap, (bit_words + n) * 4));
+    AH_TRY(alloc(&work, ws.bytes()));
+    ws.carve(work.p, ws.bytes());
+    AH_TRY(alloc(&new_nodes, (size_t)nn * sizeof(DNode)));
+    AH_TRY(alloc(&new_roots, (size_t)n_trees * 4));
+    AH_TRY(alloc(&new_rank, ((size_t)nn + 1) * 4));
+    delta->roots.resize(n_trees);
+    a.bits = n ? bitmap.as<const uint32_t>() : nullptr;
+    AH_HIP(hipMemsetAsync(work.p, 0, ws.zeroed_bytes(), s));
     // 1. bitmap
     if (n) {
         uint32_t *d_ids = bitmap.as<uint32_t>() + bit_words;
@@ -941,7 +917,7 @@ int delete_impl(ah_index *ix, const uint32_t *ids, size_t n, uint32_t split_afte
                            bitmap.as<uint32_t>());
     }
     AH_HIP(hipGetLastError());
-    const auto t_bitmap = phase_end();
+    const auto t_bitmap = call.phase_end();
     // 2. levels
     uint32_t ctl[CTL_WORDS];
     std::vector<uint32_t> level_begin;
@@ -950,9 +926,7 @@ int delete_impl(ah_index *ix, const uint32_t *ids, size_t n, uint32_t split_afte
     while (begin < end) {
         level_begin.push_back(begin);
         hipLaunchKernelGGL(k_delete_level, dim3(grid_of(end - begin, kIxBlock, 4096)), dim3(kIxBlock), 0, s, a, begin, end);
-        AH_HIP(hipGetLastError());
-        AH_HIP(hipMemcpyAsync(ctl, a.ctl, 2 * 4, hipMemcpyDeviceToHost, s));
-        AH_HIP(hipStreamSynchronize(s));
+        AH_TRY(read_back(ctl, a.ctl, 2, s));
         AH_REQUIRE(ctl[CTL_ERR] == 0 && ctl[CTL_TAIL] >= end && ctl[CTL_TAIL] <= nn, AH_ERR_DEVICE,
                    "the nodes of the index are not a forest (a node is reachable twice)");
         begin = end;
@@ -961,16 +935,14 @@ int delete_impl(ah_index *ix, const uint32_t *ids, size_t n, uint32_t split_afte
     level_begin.push_back(end);
     const uint32_t reached = end;
     const size_t levels = level_begin.size() - 1;
-    const auto t_levels = now();
+    const auto t_levels = call.now();
     // the passes over every reachable node, a wave each, in launches of at most AH_LAUNCH_MAX_ITEMS nodes
-    const uint32_t span = (uint32_t)std::min<long long>(std::max<uint32_t>(reached, 1), std::max<long long>(1, tun(TUN_LAUNCH_MAX_ITEMS)));
     // 3. count
-    for (uint32_t lo = 0; lo < reached; lo += span) {
-        const uint32_t hi = std::min(reached - lo, span) + lo;
-        hipLaunchKernelGGL(k_delete_count, dim3(grid_of(hi - lo, kIxBlock / 64, 1u << 16)), dim3(kIxBlock), 0, s, a, lo, hi);
-    }
+    for_spans(reached, call.span(), [&](uint64_t lo, uint64_t hi) {
+        hipLaunchKernelGGL(k_delete_count, dim3(grid_of(hi - lo, kIxBlock / 64, 1u << 16)), dim3(kIxBlock), 0, s, a, (uint32_t)lo, (uint32_t)hi);
+    });
     AH_HIP(hipGetLastError());
-    const auto t_count = phase_end();
+    const auto t_count = call.phase_end();
     // 4. resolve, 5. owners and the scans
     for (size_t l = levels; l-- > 0;)
         hipLaunchKernelGGL(k_delete_resolve, dim3(grid_of(level_begin[l + 1] - level_begin[l], kIxBlock, 4096)), dim3(kIxBlock), 0, s, a,
@@ -981,10 +953,8 @@ int delete_impl(ah_index *ix, const uint32_t *ids, size_t n, uint32_t split_afte
     launch_exclusive_scan(a.seg, nn, tile_sums, a.ctl + CTL_DESC_LEN, s);
     launch_exclusive_scan(a.chg, nn, tile_sums, a.ctl + CTL_CHANGED, s);
     launch_exclusive_scan(a.dseg, nn, tile_sums, a.ctl + CTL_DELTA_DESC, s);
-    AH_HIP(hipGetLastError());
-    AH_HIP(hipMemcpyAsync(ctl, a.ctl, sizeof(ctl), hipMemcpyDeviceToHost, s));
-    AH_HIP(hipStreamSynchronize(s));
-    const auto t_resolve = now();
+    AH_TRY(read_back(ctl, a.ctl, CTL_WORDS, s));
+    const auto t_resolve = call.now();
     const uint32_t desc_len = ctl[CTL_DESC_LEN], n_changed = ctl[CTL_CHANGED], delta_desc = ctl[CTL_DELTA_DESC], n_merged = ctl[CTL_MERGED];
     AH_REQUIRE(desc_len <= old_desc_len && n_changed <= nn && delta_desc <= desc_len && n_merged <= nn, AH_ERR_DEVICE,
                "the index delete counted more ids or nodes than the index holds");
@@ -999,10 +969,10 @@ int delete_impl(ah_index *ix, const uint32_t *ids, size_t n, uint32_t split_afte
     DeltaEntry *d_entries = out.as<DeltaEntry>();
     uint32_t *d_delta_desc = reinterpret_cast<uint32_t *>(d_entries + n_changed);
     // 6. write
-    for (uint32_t lo = 0; lo < reached; lo += span) {
-        const uint32_t hi = std::min(reached - lo, span) + lo;
-        hipLaunchKernelGGL(k_delete_write, dim3(grid_of(hi - lo, kIxBlock / 64, 1u << 16)), dim3(kIxBlock), 0, s, a, lo, hi, new_desc.as<uint32_t>());
-    }
+    for_spans(reached, call.span(), [&](uint64_t lo, uint64_t hi) {
+        hipLaunchKernelGGL(k_delete_write, dim3(grid_of(hi - lo, kIxBlock / 64, 1u << 16)), dim3(kIxBlock), 0, s, a, (uint32_t)lo, (uint32_t)hi,
+                           new_desc.as<uint32_t>());
+    });
     if (n_merged) hipLaunchKernelGGL(k_delete_sort, dim3(grid_of(n_merged, 1, 1u << 16)), dim3(kIxBlock), 0, s, a, n_merged, new_desc.as<uint32_t>());
     // 7. apply
     if (n_trees) hipLaunchKernelGGL(k_delete_roots, dim3(1), dim3(kIxBlock), 0, s, a, (const uint32_t *)ix->d_roots, n_trees, new_roots.as<uint32_t>());
@@ -1014,13 +984,12 @@ int delete_impl(ah_index *ix, const uint32_t *ids, size_t n, uint32_t split_afte
         hipLaunchKernelGGL(k_delete_gather, dim3(grid_of(n_changed, kIxBlock / 64, 1u << 16)), dim3(kIxBlock), 0, s, a, (const DeltaEntry *)d_entries,
                            n_changed, new_desc.as<const uint32_t>(), d_delta_desc);
     AH_HIP(hipGetLastError());
-    const auto t_write = phase_end();
+    const auto t_write = call.phase_end();
     // read back
     if (n_changed) AH_HIP(hipMemcpyAsync(entries.data(), d_entries, (size_t)n_changed * sizeof(DeltaEntry), hipMemcpyDeviceToHost, s));
     if (delta_desc) AH_HIP(hipMemcpyAsync(delta->desc.data(), d_delta_desc, (size_t)delta_desc * 4, hipMemcpyDeviceToHost, s));
     if (n_trees) AH_HIP(hipMemcpyAsync(delta->roots.data(), new_roots.p, (size_t)n_trees * 4, hipMemcpyDeviceToHost, s));
-    AH_HIP(hipMemcpyAsync(ctl, a.ctl, sizeof(ctl), hipMemcpyDeviceToHost, s));
-    AH_HIP(hipStreamSynchronize(s));
+    AH_TRY(read_back(ctl, a.ctl, CTL_WORDS, s));
     AH_REQUIRE(ctl[CTL_ERR] == 0, AH_ERR_DEVICE, "the index delete found its own counts inconsistent (%u): the index is unchanged", ctl[CTL_ERR]);
     size_t n_removed = 0;
     for (const DeltaEntry &e : entries) n_removed += e.kind == 0;
@@ -1032,51 +1001,26 @@ int delete_impl(ah_index *ix, const uint32_t *ids, size_t n, uint32_t split_afte
             delta->removed.push_back(e.node);
             continue;
         }
-        ah_node nd{};
-        nd.kind = (uint8_t)(e.kind & 0xFFu);
-        if (nd.kind == AH_NODE_SPLIT) {
-            nd.has_normal = (e.kind & 0x100u) ? 1 : 0;
-            nd.left = e.a;
-            nd.right = e.b;
-        } else {
-            nd.offset = e.a;
-            nd.count = e.b;
-        }
         delta->put_index.push_back(e.node);
-        delta->put.push_back(nd);
+        delta->put.push_back(to_host_node(DNode{e.kind, e.a, e.b, 0}));
     }
-    const auto t_read = now();
-    {
-        // commit: nothing here can fail.  The old arrays go into the DevMems, which free them (dev_free waits for the device).
-        NoFailScope no_fail;
-        void *old_nodes = ix->d_nodes, *old_roots = ix->d_roots, *old_desc = ix->d_desc, *old_rank = ix->d_rank;
-        ix->d_rank = new_rank.as<uint32_t>();
-        new_rank.p = old_rank;
-        ix->d_nodes = new_nodes.as<DNode>();
-        ix->d_roots = new_roots.as<uint32_t>();
-        ix->d_desc = new_desc.as<uint32_t>();
-        new_nodes.p = old_nodes;
-        new_roots.p = old_roots;
-        new_desc.p = old_desc;
-        ix->desc_len = desc_len;
-        ix->n_leaves = ctl[CTL_LEAVES];
-        ix->max_desc = ctl[CTL_MAX_DESC];
-        ix->compacted = false;
-    }
-    if (timing) {
-        auto secs = [](std::chrono::steady_clock::time_point x, std::chrono::steady_clock::time_point y) {
-            return std::chrono::duration<double>(y - x).count();
-        };
+    const auto t_read = call.now();
+    IndexCommit c(ix, &new_nodes, &new_roots, &new_desc, &new_rank);
+    c.desc_len = desc_len;
+    c.n_leaves = ctl[CTL_LEAVES];
+    c.max_desc = ctl[CTL_MAX_DESC];
+    c.compacted = false;
+    index_commit(ix, c);
+    if (call.timing)
         fprintf(stderr, "[ah] index delete: %zu ids, %u of %u nodes reachable in %zu levels, %llu -> %u stored ids, %zu removed + %zu put nodes: "
                         "bitmap %.6f s, levels %.6f s, count %.6f s, resolve %.6f s, write %.6f s, read-back %.6f s\n",
-                n, reached, nn, levels, (unsigned long long)old_desc_len, desc_len,
-                delta->removed.size(), delta->put.size(), secs(t0, t_bitmap), secs(t_bitmap, t_levels), secs(t_levels, t_count),
-                secs(t_count, t_resolve), secs(t_resolve, t_write), secs(t_write, t_read));
-    }
+                n, reached, nn, levels, (unsigned long long)old_desc_len, desc_len, delta->removed.size(), delta->put.size(),
+                call.secs(call.t0, t_bitmap), call.secs(t_bitmap, t_levels), call.secs(t_levels, t_count), call.secs(t_count, t_resolve),
+                call.secs(t_resolve, t_write), call.secs(t_write, t_read));
     return AH_OK;
 }
 
-// what the three updates ask of an index before they look at it
+// what the updates and ah_index_suspend ask of an index before they look at it
 int index_updatable(ah_index *ix) {
     AH_REQUIRE(ix && ix->ds, AH_ERR_INVALID_ARGUMENT, "index is NULL");
     AH_INDEX_LIVE(ix);
@@ -1088,10 +1032,9 @@ int index_updatable(ah_index *ix) {
 
 int insert_impl(ah_index *ix, const uint32_t *ids, size_t n, const uint64_t *seeds, ah_index_delta *delta) {
     ah_dataset *ds = ix->ds;
-    AH_HIP(hipSetDevice(ds->device));
-    ContextLease lease(ds);
-    AH_REQUIRE(lease.c, AH_ERR_DEVICE, "cannot create a HIP stream");
-    const hipStream_t s = lease.c->stream;
+    IndexCall call;
+    AH_TRY(call.begin(ds));
+    const hipStream_t s = call.stream();
     const uint32_t nn = ix->n_nodes, n_trees = ix->n_trees;
     const uint64_t old_desc_len = ix->desc_len;
     const uint64_t pairs = (uint64_t)n * n_trees;
@@ -1099,31 +1042,21 @@ int insert_impl(ah_index *ix, const uint32_t *ids, size_t n, const uint64_t *see
                "%llu stored ids + %llu inserted ones are too many for 32-bit descendant offsets", (unsigned long long)old_desc_len,
                (unsigned long long)pairs);
     // every buffer whose size is known now; kernels write only into these
-    const size_t per_node = (size_t)nn + 1;
-    const size_t scan_tiles = (nn + kScanTile - 1) / kScanTile + 1;
-    const size_t seed_words = 2 * (size_t)n_trees;
-    const size_t work_words = 8 * per_node + scan_tiles + ICTL_WORDS + seed_words + n + 2 * pairs;
-    DevMem work, new_nodes, new_desc, out;
-    AH_TRY(alloc(&work, work_words * 4));
-    AH_TRY(alloc(&new_nodes, (size_t)nn * sizeof(DNode)));
-    delta->roots.resize(n_trees);
-    // [seeds][8 arrays per node][scan tiles][ctl][ids][leaf of every pair][landed]
-    uint64_t *d_seeds = work.as<uint64_t>();
-    uint32_t *w = work.as<uint32_t>() + seed_words;
     InsertArgs a{};
     a.nodes = ix->d_nodes;
     a.n_nodes = nn;
     a.desc = ix->d_desc;
     a.old_desc_len = old_desc_len;
     a.n_pairs = pairs;
-    uint32_t **fields[8] = {&a.cnt, &a.seg, &a.cursor, &a.chg, &a.fresh, &a.nlen, &a.dlen, &a.touched};
-    for (int i = 0; i < 8; i++) *fields[i] = w + (size_t)i * per_node;
-    uint32_t *tile_sums = w + 8 * per_node;
-    a.ctl = tile_sums + scan_tiles;
-    uint32_t *d_ids = a.ctl + ICTL_WORDS;
-    uint32_t *d_leaf = d_ids + n;
-    a.landed = d_leaf + pairs;
-    AH_HIP(hipMemsetAsync(w, 0, (8 * per_node + scan_tiles + ICTL_WORDS) * 4, s));
+    uint64_t *d_seeds = nullptr;
+    uint32_t *tile_sums = nullptr, *d_ids = nullptr, *d_leaf = nullptr;
+    const Workspace ws = insert_workspace(a, &d_seeds, &tile_sums, &d_ids, &d_leaf, nn, n_trees, n, kScanTile, ICTL_WORDS);
+    DevMem work, new_nodes, new_desc, out;
+    AH_TRY(alloc(&work, ws.bytes()));
+    ws.carve(work.p, ws.bytes());
+    AH_TRY(alloc(&new_nodes, (size_t)nn * sizeof(DNode)));
+    delta->roots.resize(n_trees);
+    AH_HIP(hipMemsetAsync(a.cnt, 0, ws.zeroed_bytes(), s));  // (a.cnt: the first array behind the seeds)
     AH_HIP(hipMemsetAsync(a.ctl + ICTL_FIRST_BAD, 0xFF, 4, s));
     uint32_t ctl[ICTL_WORDS] = {};
     // 1. check
@@ -1132,19 +1065,17 @@ int insert_impl(ah_index *ix, const uint32_t *ids, size_t n, const uint64_t *see
         if (n_trees) AH_HIP(hipMemcpyAsync(d_seeds, seeds, (size_t)n_trees * 8, hipMemcpyHostToDevice, s));
         hipLaunchKernelGGL(k_insert_check, dim3(grid_of(n, kIxBlock, 4096)), dim3(kIxBlock), 0, s, ds->view(), (const uint32_t *)d_ids, (uint64_t)n,
                            a.ctl);
-        AH_HIP(hipGetLastError());
-        AH_HIP(hipMemcpyAsync(ctl, a.ctl, sizeof(ctl), hipMemcpyDeviceToHost, s));
-        AH_HIP(hipStreamSynchronize(s));
+        AH_TRY(read_back(ctl, a.ctl, ICTL_WORDS, s));
         AH_REQUIRE(ctl[ICTL_FIRST_BAD] >= n, AH_ERR_INVALID_ARGUMENT, "item %u (position %u of sorted_ids) is not a row of the dataset",
                    ids[std::min<size_t>(ctl[ICTL_FIRST_BAD], n - 1)], ctl[ICTL_FIRST_BAD]);
     }
-    const uint64_t span = (uint64_t)std::max<long long>(1, tun(TUN_LAUNCH_MAX_ITEMS));
+    const uint64_t span = call.span();
+    // the ids in runs of at most AH_LAUNCH_MAX_ITEMS pairs; the pairs of ids [i0, i1) are d_leaf[i0 * n_trees, i1 * n_trees), tree-major
+    const uint64_t run = pairs ? std::max<uint64_t>(1, std::min<uint64_t>(n, span / n_trees)) : 1;
     if (pairs) {
-        // 2. route, 3. count: the ids in runs of at most AH_LAUNCH_MAX_ITEMS pairs; the pairs of ids [i0, i0 + cn) are
-        // d_leaf[i0 * n_trees, (i0 + cn) * n_trees), tree-major
-        const uint64_t run = std::max<uint64_t>(1, std::min<uint64_t>(n, span / n_trees));
+        // 2. route, 3. count
         uint32_t *d_route_err = a.ctl + ICTL_ERR;  // (bit 0, as the count pass: an id without a row, refused above)
-        for (uint64_t i0 = 0; i0 < n; i0 += run) {
+        for (uint64_t i0 = 0; i0 < n; i0 += run) {  // (no for_spans: the routing may refuse)
             const uint64_t cn = std::min<uint64_t>(run, n - i0), m = cn * n_trees;
             AH_TRY(launch_route_items(ix, d_ids + i0, cn, d_seeds, d_leaf + i0 * n_trees, d_route_err, s));
             hipLaunchKernelGGL(k_insert_count, dim3(grid_of(m, kIxBlock, 4096)), dim3(kIxBlock), 0, s, a, (const uint32_t *)(d_leaf + i0 * n_trees), m);
@@ -1158,16 +1089,13 @@ int insert_impl(ah_index *ix, const uint32_t *ids, size_t n, const uint64_t *see
     if (pairs) {
         hipLaunchKernelGGL(k_insert_touched, dim3(grid_of(nn, kIxBlock, 4096)), dim3(kIxBlock), 0, s, a);
         // 4. scatter
-        const uint64_t run = std::max<uint64_t>(1, std::min<uint64_t>(n, span / n_trees));
-        for (uint64_t i0 = 0; i0 < n; i0 += run) {
-            const uint64_t cn = std::min<uint64_t>(run, n - i0), m = cn * n_trees;
+        for_spans(n, run, [&](uint64_t i0, uint64_t i1) {
+            const uint64_t cn = i1 - i0, m = cn * n_trees;
             hipLaunchKernelGGL(k_insert_scatter, dim3(grid_of(m, kIxBlock, 4096)), dim3(kIxBlock), 0, s, a, (const uint32_t *)(d_ids + i0), cn,
                                (const uint32_t *)(d_leaf + i0 * n_trees), m);
-        }
+        });
     }
-    AH_HIP(hipGetLastError());
-    AH_HIP(hipMemcpyAsync(ctl, a.ctl, sizeof(ctl), hipMemcpyDeviceToHost, s));
-    AH_HIP(hipStreamSynchronize(s));
+    AH_TRY(read_back(ctl, a.ctl, ICTL_WORDS, s));
     AH_REQUIRE(ctl[ICTL_ERR] == 0 && ctl[ICTL_TOUCHED] <= nn && ctl[ICTL_TOUCHED] <= pairs, AH_ERR_DEVICE,
                "the index insert routed an id to a node that is no Descendants node (%u): the index is unchanged", ctl[ICTL_ERR]);
     const uint32_t n_touched = ctl[ICTL_TOUCHED];
@@ -1175,16 +1103,13 @@ int insert_impl(ah_index *ix, const uint32_t *ids, size_t n, const uint64_t *see
     // 5. fresh and the scans
     if (n_touched) {
         hipLaunchKernelGGL(k_insert_sort, dim3(grid_of(n_touched, 1, 1u << 16)), dim3(kIxBlock), 0, s, a);
-        for (uint64_t lo = 0; lo < n_touched; lo += span) {
-            const uint32_t hi = (uint32_t)std::min<uint64_t>(n_touched, lo + span);
-            hipLaunchKernelGGL(k_insert_fresh, dim3(grid_of(hi - lo, kIxBlock / 64, 1u << 16)), dim3(kIxBlock), 0, s, a, (uint32_t)lo, hi);
-        }
+        for_spans(n_touched, span, [&](uint64_t lo, uint64_t hi) {
+            hipLaunchKernelGGL(k_insert_fresh, dim3(grid_of(hi - lo, kIxBlock / 64, 1u << 16)), dim3(kIxBlock), 0, s, a, (uint32_t)lo, (uint32_t)hi);
+        });
     }
     launch_exclusive_scan(a.nlen, nn, tile_sums, a.ctl + ICTL_DESC_LEN, s);
     launch_exclusive_scan(a.dlen, nn, tile_sums, a.ctl + ICTL_DELTA_DESC, s);
-    AH_HIP(hipGetLastError());
-    AH_HIP(hipMemcpyAsync(ctl, a.ctl, sizeof(ctl), hipMemcpyDeviceToHost, s));
-    AH_HIP(hipStreamSynchronize(s));
+    AH_TRY(read_back(ctl, a.ctl, ICTL_WORDS, s));
     const uint32_t desc_len = ctl[ICTL_DESC_LEN], delta_desc = ctl[ICTL_DELTA_DESC];
     AH_REQUIRE(ctl[ICTL_ERR] == 0 && desc_len <= old_desc_len + pairs && delta_desc <= desc_len, AH_ERR_DEVICE, "the index insert found its own counts inconsistent (%u): the index is unchanged", ctl[ICTL_ERR]);
     a.new_desc_len = desc_len;
@@ -1199,43 +1124,29 @@ int insert_impl(ah_index *ix, const uint32_t *ids, size_t n, const uint64_t *see
     DeltaEntry *d_entries = out.as<DeltaEntry>();
     uint32_t *d_delta_desc = reinterpret_cast<uint32_t *>(d_entries + n_touched);
     // 6. write, 7. apply
-    for (uint64_t lo = 0; lo < nn; lo += span) {
-        const uint32_t hi = (uint32_t)std::min<uint64_t>(nn, lo + span);
-        hipLaunchKernelGGL(k_insert_write, dim3(grid_of(hi - lo, kIxBlock / 64, 1u << 16)), dim3(kIxBlock), 0, s, a, (uint32_t)lo, hi,
+    for_spans(nn, span, [&](uint64_t lo, uint64_t hi) {
+        hipLaunchKernelGGL(k_insert_write, dim3(grid_of(hi - lo, kIxBlock / 64, 1u << 16)), dim3(kIxBlock), 0, s, a, (uint32_t)lo, (uint32_t)hi,
                            new_desc.as<uint32_t>());
-    }
+    });
     if (nn) hipLaunchKernelGGL(k_insert_apply, dim3(grid_of(nn, kIxBlock, 4096)), dim3(kIxBlock), 0, s, a, new_nodes.as<DNode>(), d_entries);
     if (n_touched)
         hipLaunchKernelGGL(k_insert_gather, dim3(grid_of(n_touched, kIxBlock / 64, 1u << 16)), dim3(kIxBlock), 0, s, a, (const DeltaEntry *)d_entries,
                            new_desc.as<const uint32_t>(), d_delta_desc);
-    AH_HIP(hipGetLastError());
     // read back
     if (n_touched) AH_HIP(hipMemcpyAsync(entries.data(), d_entries, (size_t)n_touched * sizeof(DeltaEntry), hipMemcpyDeviceToHost, s));
     if (delta_desc) AH_HIP(hipMemcpyAsync(delta->desc.data(), d_delta_desc, (size_t)delta_desc * 4, hipMemcpyDeviceToHost, s));
     if (n_trees) AH_HIP(hipMemcpyAsync(delta->roots.data(), ix->d_roots, (size_t)n_trees * 4, hipMemcpyDeviceToHost, s));
-    AH_HIP(hipMemcpyAsync(ctl, a.ctl, sizeof(ctl), hipMemcpyDeviceToHost, s));
-    AH_HIP(hipStreamSynchronize(s));
+    AH_TRY(read_back(ctl, a.ctl, ICTL_WORDS, s));
     AH_REQUIRE(ctl[ICTL_ERR] == 0, AH_ERR_DEVICE, "the index insert found its own counts inconsistent (%u): the index is unchanged", ctl[ICTL_ERR]);
     for (const DeltaEntry &e : entries) {
-        ah_node nd{};
-        nd.kind = AH_NODE_DESCENDANTS;
-        nd.offset = e.a;
-        nd.count = e.b;
         delta->put_index.push_back(e.node);
-        delta->put.push_back(nd);
+        delta->put.push_back(to_host_node(DNode{e.kind, e.a, e.b, 0}));
     }
-    {
-        // commit: nothing here can fail.  The old arrays go into the DevMems, which free them (dev_free waits for the device).
-        NoFailScope no_fail;
-        void *old_nodes = ix->d_nodes, *old_desc = ix->d_desc;
-        ix->d_nodes = new_nodes.as<DNode>();
-        ix->d_desc = new_desc.as<uint32_t>();
-        new_nodes.p = old_nodes;
-        new_desc.p = old_desc;
-        ix->desc_len = desc_len;
-        ix->n_leaves = ctl[ICTL_LEAVES];
-        ix->max_desc = ctl[ICTL_MAX_DESC];
-    }
+    IndexCommit c(ix, &new_nodes, nullptr, &new_desc, nullptr);
+    c.desc_len = desc_len;
+    c.n_leaves = ctl[ICTL_LEAVES];
+    c.max_desc = ctl[ICTL_MAX_DESC];
+    index_commit(ix, c);
     if (tun(TUN_TIMING) != 0)
         fprintf(stderr, "[ah] index insert: %zu ids x %u trees into %u of %u nodes, %llu -> %u stored ids\n", n, n_trees, n_touched, nn,
                 (unsigned long long)old_desc_len, desc_len);
@@ -1244,12 +1155,10 @@ int insert_impl(ah_index *ix, const uint32_t *ids, size_t n, const uint64_t *see
 
 int graft_impl(ah_index *ix, const ah_forest_view &v, const uint32_t *targets, const uint32_t *new_index, uint32_t *out_new_of_old) {
     ah_dataset *ds = ix->ds;
-    AH_HIP(hipSetDevice(ds->device));
-    ContextLease lease(ds);
-    AH_REQUIRE(lease.c, AH_ERR_DEVICE, "cannot create a HIP stream");
-    const hipStream_t s = lease.c->stream;
+    IndexCall call;
+    AH_TRY(call.begin(ds));
+    const hipStream_t s = call.stream();
     const uint32_t n_old = ix->n_nodes, n_trees = ix->n_trees, n_view = (uint32_t)v.n_nodes;
-    const uint64_t span = (uint64_t)std::max<long long>(1, tun(TUN_LAUNCH_MAX_ITEMS));
     // ---- validation: nothing is touched before it is through
     uint32_t n_used = n_old;
     if (ix->d_rank) {
@@ -1302,38 +1211,14 @@ int graft_impl(ah_index *ix, const ah_forest_view &v, const uint32_t *targets, c
     std::vector<DNode> vnodes(n_view);
     std::vector<uint64_t> offsets;
     for (uint32_t k = 0; k < n_view; k++) {
-        const ah_node &nd = v.nodes[k];
-        DNode d{};
-        d.kind = nd.kind;
-        if (nd.kind == AH_NODE_SPLIT) {
-            d.a = nd.left;
-            d.b = nd.right;
-            if (nd.has_normal) {
-                d.kind |= 0x100u;
-                d.c = (uint32_t)offsets.size();
-                offsets.push_back(nd.offset);
-            }
-        } else {
-            d.a = (uint32_t)nd.offset;
-            d.b = nd.count;
-        }
-        vnodes[k] = d;
+        vnodes[k] = to_device_node(v.nodes[k], (uint32_t)offsets.size());
+        if (vnodes[k].kind & 0x100u) offsets.push_back(v.nodes[k].offset);
     }
     const uint32_t n_vnormals = (uint32_t)offsets.size(), n_added = (uint32_t)added_roots.size();
     AH_REQUIRE((uint64_t)ix->n_normals + n_vnormals < 0xFFFFFFFFull, AH_ERR_INVALID_ARGUMENT, "too many normals for 32-bit rows");
     // ---- buffers
     const uint32_t hf = header_floats(ds->metric);
     const size_t row_bytes = ds->row_bytes();
-    const size_t scan_tiles = ((size_t)n_new + kScanTile - 1) / kScanTile + 1;
-    // [named n_new + 1][len n_new + 1][pos_of_rank n_used][new_of_old n_old][replaced n_old][fin n_view][tiles][ctl]
-    // [vfin n_view][vtgt n_view][repl n_repl][kinds n_repl][added n_added][view ids][vnodes]
-    const size_t zeroed = 2 * ((size_t)n_new + 1) + n_used + 2 * (size_t)n_old + n_view + scan_tiles + GCTL_WORDS;
-    const size_t words = zeroed + 2 * (size_t)n_view + 2 * (size_t)n_repl + n_added + v.descendants_len + 4 * (size_t)n_view;
-    DevMem work, new_nodes, new_roots, new_desc, recs, offs, grown_rows, grown_hdrs;
-    AH_TRY(alloc(&work, words * 4));
-    AH_TRY(alloc(&new_nodes, (size_t)n_new * sizeof(DNode)));
-    AH_TRY(alloc(&new_roots, ((size_t)n_trees + n_added) * 4));
-    uint32_t *w = work.as<uint32_t>();
     GraftArgs a{};
     a.nodes = ix->d_nodes;
     a.n_old = n_old;
@@ -1345,37 +1230,33 @@ int graft_impl(ah_index *ix, const ah_forest_view &v, const uint32_t *targets, c
     a.vdesc_len = v.descendants_len;
     a.n_new = n_new;
     a.first_row = ix->n_normals;
-    a.named = w;
-    a.len = a.named + n_new + 1;
-    a.pos_of_rank = a.len + n_new + 1;
-    a.new_of_old = a.pos_of_rank + n_used;
-    a.replaced = a.new_of_old + n_old;
-    a.fin = a.replaced + n_old;
-    uint32_t *tile_sums = a.fin + n_view;
-    a.ctl = tile_sums + scan_tiles;
-    uint32_t *d_vfin = a.ctl + GCTL_WORDS, *d_vtgt = d_vfin + n_view, *d_repl = d_vtgt + n_view, *d_kinds = d_repl + n_repl;
-    uint32_t *d_added = d_kinds + n_repl, *d_vdesc = d_added + n_added;
-    DNode *d_vnodes = reinterpret_cast<DNode *>(d_vdesc + v.descendants_len);  // (4-byte members only)
-    a.vfin = d_vfin;
-    a.vtgt = d_vtgt;
-    a.vdesc = d_vdesc;
-    a.vnodes = d_vnodes;
-    AH_HIP(hipMemsetAsync(work.p, 0, zeroed * 4, s));
+    uint32_t *tile_sums = nullptr;
+    GraftUploads<DNode> u{};
+    const Workspace ws = graft_workspace(a, &tile_sums, u, GraftSizes{n_old, n_used, n_view, n_new, n_repl, n_added, v.descendants_len},
+                                         kScanTile, GCTL_WORDS);
+    DevMem work, new_nodes, new_roots, new_desc, recs, offs, grown_rows, grown_hdrs;
+    AH_TRY(alloc(&work, ws.bytes()));
+    ws.carve(work.p, ws.bytes());
+    a.vfin = u.vfin;  // (the kernels read what the host uploads through these)
+    a.vtgt = u.vtgt;
+    a.vdesc = u.vdesc;
+    a.vnodes = u.vnodes;
+    AH_TRY(alloc(&new_nodes, (size_t)n_new * sizeof(DNode)));
+    AH_TRY(alloc(&new_roots, ((size_t)n_trees + n_added) * 4));
+    AH_HIP(hipMemsetAsync(work.p, 0, ws.zeroed_bytes(), s));
     if (n_view) {
-        AH_HIP(hipMemcpyAsync(d_vfin, vfin.data(), (size_t)n_view * 4, hipMemcpyHostToDevice, s));
-        AH_HIP(hipMemcpyAsync(d_vtgt, vtgt.data(), (size_t)n_view * 4, hipMemcpyHostToDevice, s));
-        AH_HIP(hipMemcpyAsync(d_vnodes, vnodes.data(), (size_t)n_view * sizeof(DNode), hipMemcpyHostToDevice, s));
+        AH_HIP(hipMemcpyAsync(u.vfin, vfin.data(), (size_t)n_view * 4, hipMemcpyHostToDevice, s));
+        AH_HIP(hipMemcpyAsync(u.vtgt, vtgt.data(), (size_t)n_view * 4, hipMemcpyHostToDevice, s));
+        AH_HIP(hipMemcpyAsync(u.vnodes, vnodes.data(), (size_t)n_view * sizeof(DNode), hipMemcpyHostToDevice, s));
     }
-    if (n_repl) AH_HIP(hipMemcpyAsync(d_repl, repl.data(), (size_t)n_repl * 4, hipMemcpyHostToDevice, s));
-    if (n_added) AH_HIP(hipMemcpyAsync(d_added, added_roots.data(), (size_t)n_added * 4, hipMemcpyHostToDevice, s));
-    if (v.descendants_len) AH_HIP(hipMemcpyAsync(d_vdesc, v.descendants, v.descendants_len * 4, hipMemcpyHostToDevice, s));
+    if (n_repl) AH_HIP(hipMemcpyAsync(u.repl, repl.data(), (size_t)n_repl * 4, hipMemcpyHostToDevice, s));
+    if (n_added) AH_HIP(hipMemcpyAsync(u.added, added_roots.data(), (size_t)n_added * 4, hipMemcpyHostToDevice, s));
+    if (v.descendants_len) AH_HIP(hipMemcpyAsync(u.vdesc, v.descendants, v.descendants_len * 4, hipMemcpyHostToDevice, s));
     if (n_repl) {  // the targets: in use and Descendants nodes
         std::vector<uint32_t> kinds(n_repl);
         hipLaunchKernelGGL(k_graft_peek, dim3(grid_of(n_repl, kIxBlock, 1024)), dim3(kIxBlock), 0, s, (const DNode *)ix->d_nodes,
-                           (const uint32_t *)d_repl, n_repl, d_kinds);
-        AH_HIP(hipGetLastError());
-        AH_HIP(hipMemcpyAsync(kinds.data(), d_kinds, (size_t)n_repl * 4, hipMemcpyDeviceToHost, s));
-        AH_HIP(hipStreamSynchronize(s));
+                           (const uint32_t *)u.repl, n_repl, u.kinds);
+        AH_TRY(read_back(kinds.data(), u.kinds, n_repl, s));
         for (uint32_t i = 0; i < n_repl; i++)
             AH_REQUIRE((kinds[i] & 0xFFu) == AH_NODE_DESCENDANTS, AH_ERR_INVALID_ARGUMENT, "target %u is %s", repl[i],
                        kinds[i] == 0 ? "a free slot of the index" : "a split node, not a Descendants node");
@@ -1389,11 +1270,9 @@ int graft_impl(ah_index *ix, const ah_forest_view &v, const uint32_t *targets, c
     const uint64_t items = (uint64_t)n_old + n_view;
     if (items) hipLaunchKernelGGL(k_graft_len, dim3(grid_of(items, kIxBlock, 4096)), dim3(kIxBlock), 0, s, a);
     launch_exclusive_scan(a.len, n_new, tile_sums, a.ctl + GCTL_DESC_LEN, s);
-    AH_HIP(hipGetLastError());
     uint32_t ctl[GCTL_WORDS] = {};
     AH_HIP(hipMemcpyAsync(ctl, a.ctl, sizeof(ctl), hipMemcpyDeviceToHost, s));
-    AH_HIP(hipMemcpyAsync(&ctl[GCTL_NAMED], a.named + n_new, 4, hipMemcpyDeviceToHost, s));
-    AH_HIP(hipStreamSynchronize(s));
+    AH_TRY(read_back(&ctl[GCTL_NAMED], a.named + n_new, 1, s));
     AH_REQUIRE(ctl[GCTL_ERR] == 0 && ctl[GCTL_NAMED] == n_view - n_repl && ctl[GCTL_DESC_LEN] <= ix->desc_len + v.descendants_len,
                AH_ERR_DEVICE, "the index graft found its own counts inconsistent (%u): the index is unchanged", ctl[GCTL_ERR]);
     const uint32_t desc_len = ctl[GCTL_DESC_LEN];
@@ -1425,47 +1304,29 @@ int graft_impl(ah_index *ix, const ah_forest_view &v, const uint32_t *targets, c
     }
     // ---- 3. nodes, 4. lists
     if (items) hipLaunchKernelGGL(k_graft_nodes, dim3(grid_of(items, kIxBlock, 4096)), dim3(kIxBlock), 0, s, a, new_nodes.as<DNode>());
-    for (uint64_t lo = 0; lo < items; lo += span) {
-        const uint64_t hi = std::min<uint64_t>(items, lo + span);
+    for_spans(items, call.span(), [&](uint64_t lo, uint64_t hi) {
         hipLaunchKernelGGL(k_graft_lists, dim3(grid_of(hi - lo, kIxBlock / 64, 1u << 16)), dim3(kIxBlock), 0, s, a, lo, hi, new_desc.as<uint32_t>());
-    }
+    });
     if (n_trees + n_added)
         hipLaunchKernelGGL(k_graft_roots, dim3(grid_of((uint64_t)n_trees + n_added, kIxBlock, 1024)), dim3(kIxBlock), 0, s, a,
-                           (const uint32_t *)ix->d_roots, n_trees, (const uint32_t *)d_added, n_added, new_roots.as<uint32_t>());
-    AH_HIP(hipGetLastError());
+                           (const uint32_t *)ix->d_roots, n_trees, (const uint32_t *)u.added, n_added, new_roots.as<uint32_t>());
     std::vector<uint32_t> map_out(out_new_of_old ? n_old : 0);
     if (out_new_of_old && n_old) AH_HIP(hipMemcpyAsync(map_out.data(), a.new_of_old, (size_t)n_old * 4, hipMemcpyDeviceToHost, s));
-    AH_HIP(hipMemcpyAsync(ctl, a.ctl, sizeof(ctl), hipMemcpyDeviceToHost, s));
-    AH_HIP(hipStreamSynchronize(s));
+    AH_TRY(read_back(ctl, a.ctl, GCTL_WORDS, s));
     AH_REQUIRE(ctl[GCTL_ERR] == 0, AH_ERR_DEVICE, "the index graft found its own counts inconsistent (%u): the index is unchanged", ctl[GCTL_ERR]);
-    {
-        // commit: nothing here can fail.  The old arrays go into the DevMems, which free them (dev_free waits for the device).
-        NoFailScope no_fail;
-        if (out_new_of_old && n_old) memcpy(out_new_of_old, map_out.data(), (size_t)n_old * 4);
-        std::swap(new_nodes.p, *reinterpret_cast<void **>(&ix->d_nodes));
-        std::swap(new_roots.p, *reinterpret_cast<void **>(&ix->d_roots));
-        std::swap(new_desc.p, *reinterpret_cast<void **>(&ix->d_desc));
-        DevMem old_rank;
-        old_rank.p = ix->d_rank;
-        ix->d_rank = nullptr;
-        if (grown_rows.p) {
-            std::swap(grown_rows.p, ix->d_nrows);
-            std::swap(grown_hdrs.p, *reinterpret_cast<void **>(&ix->d_nhdrs));
-            ix->normals_cap = cap;
-            const bool bq = metric_is_bq(ds->metric);
-            ix->nv.rows_f32 = bq ? nullptr : reinterpret_cast<const float *>(ix->d_nrows);
-            ix->nv.rows_bq = bq ? reinterpret_cast<const uint64_t *>(ix->d_nrows) : nullptr;
-            ix->nv.headers = ix->d_nhdrs;
-        }
-        ix->n_normals = need;
-        ix->nv.n = need;
-        ix->n_nodes = n_new;
-        ix->n_trees = n_trees + n_added;
-        ix->desc_len = desc_len;
-        ix->n_leaves = ctl[GCTL_LEAVES];
-        ix->max_desc = ctl[GCTL_MAX_DESC];
-        ix->compacted = false;
-    }
+    if (out_new_of_old && n_old) memcpy(out_new_of_old, map_out.data(), (size_t)n_old * 4);
+    const bool grown = grown_rows.p != nullptr;  // (the rows moved into larger arrays: cap is their room)
+    IndexCommit c(ix, &new_nodes, &new_roots, &new_desc, nullptr, grown ? &grown_rows : nullptr, grown ? &grown_hdrs : nullptr);
+    c.drop_rank = true;
+    c.normals_cap = cap;
+    c.n_normals = need;
+    c.n_nodes = n_new;
+    c.n_trees = n_trees + n_added;
+    c.desc_len = desc_len;
+    c.n_leaves = ctl[GCTL_LEAVES];
+    c.max_desc = ctl[GCTL_MAX_DESC];
+    c.compacted = false;
+    index_commit(ix, c);
     if (tun(TUN_TIMING) != 0)
         fprintf(stderr, "[ah] index graft: %u view nodes (%u replacing roots, %u new roots, %u normals) into %u nodes -> %u nodes, %u stored ids\n",
                 n_view, n_repl, n_added, n_vnormals, n_used, n_new, desc_len);
@@ -1479,30 +1340,23 @@ uint64_t index_device_bytes(const ah_index *ix, uint64_t n_nodes, bool rank, uin
            std::max<uint64_t>(1, ix->desc_len) * 4 + normals_cap * per_row;
 }
 
-// pass 1 of the compaction, which is all of ah_index_footprint_get: `work` gets [new_index n + 1][new_row n + 1][scan tiles][ctl]
-// [extra words]; ctl[CCTL_*] is read back
+// pass 1 of the compaction, which is all of ah_index_footprint_get: `work` gets the workspace (compact_workspace, `extra` words
+// behind it); ctl[CCTL_*] is read back
 int compact_count(ah_index *ix, hipStream_t s, DevMem *work, size_t extra_words, CompactArgs *a, uint32_t **extra, uint32_t *ctl) {
     const uint32_t nn = ix->n_nodes;
-    const size_t per_node = (size_t)nn + 1;
-    const size_t scan_tiles = (nn + kScanTile - 1) / kScanTile + 1;
-    AH_TRY(alloc(work, (2 * per_node + scan_tiles + CCTL_WORDS + extra_words) * 4));
-    uint32_t *w = work->as<uint32_t>();
     a->nodes = ix->d_nodes;
     a->n_nodes = nn;
     a->old_rows = ix->n_normals;
-    a->new_index = w;
-    a->new_row = w + per_node;
-    uint32_t *tile_sums = w + 2 * per_node;
-    a->ctl = tile_sums + scan_tiles;
-    *extra = a->ctl + CCTL_WORDS;
+    uint32_t *tile_sums = nullptr;
+    const Workspace ws = compact_workspace(*a, &tile_sums, extra, nn, extra_words, kScanTile, CCTL_WORDS);
+    AH_TRY(alloc(work, ws.bytes()));
+    ws.carve(work->p, ws.bytes());
     AH_HIP(hipMemsetAsync(a->ctl, 0, CCTL_WORDS * 4, s));
     if (nn) hipLaunchKernelGGL(k_compact_flags, dim3(grid_of(nn, kIxBlock, 4096)), dim3(kIxBlock), 0, s, *a);
     launch_exclusive_scan(a->new_index, nn, tile_sums, a->ctl + CCTL_USED, s);
     launch_exclusive_scan(a->new_row, nn, tile_sums, a->ctl + CCTL_LIVE, s);
     if (nn) hipLaunchKernelGGL(k_compact_placed, dim3(grid_of(nn, kIxBlock, 4096)), dim3(kIxBlock), 0, s, *a);
-    AH_HIP(hipGetLastError());
-    AH_HIP(hipMemcpyAsync(ctl, a->ctl, CCTL_WORDS * 4, hipMemcpyDeviceToHost, s));
-    AH_HIP(hipStreamSynchronize(s));
+    AH_TRY(read_back(ctl, a->ctl, CCTL_WORDS, s));
     AH_REQUIRE(ctl[CCTL_USED] <= nn && ctl[CCTL_LIVE] <= ctl[CCTL_USED], AH_ERR_DEVICE, "the index counts more nodes in use than it has");
     a->n_used = ctl[CCTL_USED];
     a->n_live = ctl[CCTL_LIVE];
@@ -1510,15 +1364,13 @@ int compact_count(ah_index *ix, hipStream_t s, DevMem *work, size_t extra_words,
 }
 
 int footprint_impl(ah_index *ix, ah_index_footprint *out) {
-    ah_dataset *ds = ix->ds;
-    AH_HIP(hipSetDevice(ds->device));
-    ContextLease lease(ds);
-    AH_REQUIRE(lease.c, AH_ERR_DEVICE, "cannot create a HIP stream");
+    IndexCall call;
+    AH_TRY(call.begin(ix->ds));
     DevMem work;
     CompactArgs a{};
     uint32_t *extra = nullptr;
     uint32_t ctl[CCTL_WORDS] = {};
-    AH_TRY(compact_count(ix, lease.c->stream, &work, 0, &a, &extra, ctl));
+    AH_TRY(compact_count(ix, call.stream(), &work, 0, &a, &extra, ctl));
     out->n_nodes = ix->n_nodes;
     out->free_slots = ix->n_nodes - a.n_used;
     out->n_normals = ix->n_normals;
@@ -1530,18 +1382,10 @@ int footprint_impl(ah_index *ix, ah_index_footprint *out) {
 }
 
 int compact_impl(ah_index *ix, uint32_t *out_new_of_old, ah_index_compact_stats *stats) {
-    auto now = [] { return std::chrono::steady_clock::now(); };
-    const bool timing = tun(TUN_TIMING) != 0;
     ah_dataset *ds = ix->ds;
-    AH_HIP(hipSetDevice(ds->device));
-    ContextLease lease(ds);
-    AH_REQUIRE(lease.c, AH_ERR_DEVICE, "cannot create a HIP stream");
-    const hipStream_t s = lease.c->stream;
-    auto phase_end = [&]() -> std::chrono::steady_clock::time_point {
-        if (timing) (void)hipStreamSynchronize(s);
-        return now();
-    };
-    const auto t0 = now();
+    IndexCall call;
+    AH_TRY(call.begin(ds));
+    const hipStream_t s = call.stream();
     const uint32_t nn = ix->n_nodes, n_trees = ix->n_trees, old_rows = ix->n_normals, old_cap = ix->normals_cap;
     ah_index_compact_stats st{};
     st.nodes_before = st.nodes_after = nn;
@@ -1565,7 +1409,7 @@ int compact_impl(ah_index *ix, uint32_t *out_new_of_old, ah_index_compact_stats 
     if (!out_new_of_old) d_map = nullptr;
     const uint32_t n_used = a.n_used, n_live = a.n_live;
     const uint32_t new_cap = std::max<uint32_t>(1, n_live);
-    const auto t_count = now();
+    const auto t_count = call.now();
     if (n_used == nn && n_live == old_rows && ctl[CCTL_MISPLACED] == 0 && old_cap == new_cap && !ix->d_rank) {
         // no free slot, no dead row, every row where a fresh index has it, no spare row, no ranks: nothing but the scratch of
         // the count was obtained, and it goes back here
@@ -1583,66 +1427,56 @@ int compact_impl(ah_index *ix, uint32_t *out_new_of_old, ah_index_compact_stats 
     std::vector<uint32_t> map_out(out_new_of_old ? nn : 0);
     AH_HIP(hipMemsetAsync(row_src.p, 0, (size_t)new_cap * 4, s));
     // 2. nodes, in launches of at most AH_LAUNCH_MAX_ITEMS slots
-    const uint64_t span = (uint64_t)std::max<long long>(1, tun(TUN_LAUNCH_MAX_ITEMS));
-    for (uint64_t lo = 0; lo < nn; lo += span) {
-        const uint32_t hi = (uint32_t)std::min<uint64_t>(nn, lo + span);
-        hipLaunchKernelGGL(k_compact_nodes, dim3(grid_of(hi - lo, kIxBlock, 4096)), dim3(kIxBlock), 0, s, a, (uint32_t)lo, hi, new_nodes.as<DNode>(),
-                           row_src.as<uint32_t>(), d_map);
-    }
+    const uint64_t span = call.span();
+    for_spans(nn, span, [&](uint64_t lo, uint64_t hi) {
+        hipLaunchKernelGGL(k_compact_nodes, dim3(grid_of(hi - lo, kIxBlock, 4096)), dim3(kIxBlock), 0, s, a, (uint32_t)lo, (uint32_t)hi,
+                           new_nodes.as<DNode>(), row_src.as<uint32_t>(), d_map);
+    });
     if (n_trees)
         hipLaunchKernelGGL(k_compact_roots, dim3(grid_of(n_trees, kIxBlock, 1024)), dim3(kIxBlock), 0, s, a, (const uint32_t *)ix->d_roots, n_trees,
                            new_roots.as<uint32_t>());
     AH_HIP(hipGetLastError());
-    const auto t_nodes = phase_end();
+    const auto t_nodes = call.phase_end();
     // 3. rows, in launches of at most AH_LAUNCH_MAX_ITEMS rows
-    for (uint64_t lo = 0; lo < n_live; lo += span) {
-        const uint64_t hi = std::min<uint64_t>(n_live, lo + span);
+    for_spans(n_live, span, [&](uint64_t lo, uint64_t hi) {
         hipLaunchKernelGGL(k_compact_rows, dim3(grid_of(hi - lo, kIxBlock / 64, 8192)), dim3(kIxBlock), 0, s, (const uint8_t *)ix->d_nrows,
                            (const float *)ix->d_nhdrs, row_src.as<const uint32_t>(), old_rows, lo, hi, (uint64_t)row_bytes, hf, new_rows.as<uint8_t>(),
                            new_hdrs.as<float>(), a.ctl);
-    }
-    AH_HIP(hipGetLastError());
+    });
     if (out_new_of_old && nn) AH_HIP(hipMemcpyAsync(map_out.data(), d_map, (size_t)nn * 4, hipMemcpyDeviceToHost, s));
-    AH_HIP(hipMemcpyAsync(ctl, a.ctl, sizeof(ctl), hipMemcpyDeviceToHost, s));
-    AH_HIP(hipStreamSynchronize(s));
+    AH_TRY(read_back(ctl, a.ctl, CCTL_WORDS, s));
     AH_REQUIRE(ctl[CCTL_ERR] == 0, AH_ERR_DEVICE, "the index compaction found the index inconsistent (%u): the index is unchanged", ctl[CCTL_ERR]);
-    const auto t_rows = now();
-    {
-        // commit: nothing here can fail.  The old arrays go into the DevMems, which free them (dev_free waits for the device).
-        NoFailScope no_fail;
-        if (out_new_of_old && nn) memcpy(out_new_of_old, map_out.data(), (size_t)nn * 4);
-        std::swap(new_nodes.p, *reinterpret_cast<void **>(&ix->d_nodes));
-        std::swap(new_roots.p, *reinterpret_cast<void **>(&ix->d_roots));
-        std::swap(new_rows.p, ix->d_nrows);
-        std::swap(new_hdrs.p, *reinterpret_cast<void **>(&ix->d_nhdrs));
-        DevMem old_rank;
-        old_rank.p = ix->d_rank;
-        ix->d_rank = nullptr;
-        const bool bq = metric_is_bq(ds->metric);
-        ix->nv.rows_f32 = bq ? nullptr : reinterpret_cast<const float *>(ix->d_nrows);
-        ix->nv.rows_bq = bq ? reinterpret_cast<const uint64_t *>(ix->d_nrows) : nullptr;
-        ix->nv.headers = ix->d_nhdrs;
-        ix->n_nodes = n_used;
-        ix->n_normals = n_live;
-        ix->nv.n = n_live;
-        ix->normals_cap = new_cap;
-        ix->compacted = true;
-    }
+    const auto t_rows = call.now();
+    if (out_new_of_old && nn) memcpy(out_new_of_old, map_out.data(), (size_t)nn * 4);
+    IndexCommit c(ix, &new_nodes, &new_roots, nullptr, nullptr, &new_rows, &new_hdrs);
+    c.drop_rank = true;
+    c.n_nodes = n_used;
+    c.n_normals = n_live;
+    c.normals_cap = new_cap;
+    c.compacted = true;
+    index_commit(ix, c);
     st.nodes_after = n_used;
     st.normals_after = n_live;
     st.normals_cap_after = new_cap;
     st.device_bytes_after = index_device_bytes(ix, n_used, false, new_cap);
     st.moved = 1;
     if (stats) *stats = st;
-    if (timing) {
-        auto secs = [](std::chrono::steady_clock::time_point x, std::chrono::steady_clock::time_point y) {
-            return std::chrono::duration<double>(y - x).count();
-        };
+    if (call.timing)
         fprintf(stderr, "[ah] index compact: %u -> %u nodes, %u -> %u normal rows (room for %u -> %u), %llu -> %llu bytes: "
                         "flags and scans %.6f s, nodes %.6f s, rows %.6f s, swap %.6f s\n",
                 nn, n_used, old_rows, n_live, old_cap, new_cap, (unsigned long long)st.device_bytes_before,
-                (unsigned long long)st.device_bytes_after, secs(t0, t_count), secs(t_count, t_nodes), secs(t_nodes, t_rows), secs(t_rows, now()));
-    }
+                (unsigned long long)st.device_bytes_after, call.secs(call.t0, t_count), call.secs(t_count, t_nodes), call.secs(t_nodes, t_rows),
+                call.secs(t_rows, call.now()));
+    return AH_OK;
+}
+
+// what the delete and the insert ask of their id list (judged before the index is looked at)
+int check_sorted_ids(const uint32_t *sorted_ids, size_t n) {
+    AH_REQUIRE(n == 0 || sorted_ids, AH_ERR_INVALID_ARGUMENT, "sorted_ids is NULL");
+    AH_REQUIRE(n < 0xFFFFFFFFull, AH_ERR_INVALID_ARGUMENT, "more ids than the u32 item-id space holds");
+    for (size_t i = 1; i < n; i++)
+        AH_REQUIRE(sorted_ids[i - 1] < sorted_ids[i], AH_ERR_INVALID_ARGUMENT, "sorted_ids is not strictly ascending at position %zu (%u after %u)",
+                   i, sorted_ids[i], sorted_ids[i - 1]);
     return AH_OK;
 }
 
@@ -1655,18 +1489,8 @@ int ah_index_delete_items(ah_index *ix, const uint32_t *sorted_ids, size_t n, ui
     AH_REQUIRE(out_delta, AH_ERR_INVALID_ARGUMENT, "out_delta is NULL");
     *out_delta = nullptr;
     // (what can be judged without the index first)
-    AH_REQUIRE(n == 0 || sorted_ids, AH_ERR_INVALID_ARGUMENT, "sorted_ids is NULL");
-    AH_REQUIRE(n < 0xFFFFFFFFull, AH_ERR_INVALID_ARGUMENT, "more ids than the u32 item-id space holds");
-    for (size_t i = 1; i < n; i++)
-        AH_REQUIRE(sorted_ids[i - 1] < sorted_ids[i], AH_ERR_INVALID_ARGUMENT, "sorted_ids is not strictly ascending at position %zu (%u after %u)",
-                   i, sorted_ids[i], sorted_ids[i - 1]);
-    AH_REQUIRE(ix && ix->ds, AH_ERR_INVALID_ARGUMENT, "index is NULL");
-    AH_INDEX_LIVE(ix);
-    {
-        std::lock_guard<std::mutex> lk(ix->stats_mu);
-        AH_REQUIRE(ix->fstats.filters_alive == 0, AH_ERR_INVALID_ARGUMENT, "the index has %llu live filters: ah_filter_destroy them first",
-                   (unsigned long long)ix->fstats.filters_alive);
-    }
+    AH_TRY(check_sorted_ids(sorted_ids, n));
+    AH_TRY(index_updatable(ix));
     DeviceRestore restore_device;
     std::unique_ptr<ah_index_delta> delta(new ah_index_delta);
     AH_TRY(delete_impl(ix, sorted_ids, n, split_after, delta.get()));
@@ -1680,11 +1504,7 @@ int ah_index_insert_items(ah_index *ix, const uint32_t *sorted_ids, size_t n, co
     AH_REQUIRE(out_delta, AH_ERR_INVALID_ARGUMENT, "out_delta is NULL");
     *out_delta = nullptr;
     // (what can be judged without the index first)
-    AH_REQUIRE(n == 0 || sorted_ids, AH_ERR_INVALID_ARGUMENT, "sorted_ids is NULL");
-    AH_REQUIRE(n < 0xFFFFFFFFull, AH_ERR_INVALID_ARGUMENT, "more ids than the u32 item-id space holds");
-    for (size_t i = 1; i < n; i++)
-        AH_REQUIRE(sorted_ids[i - 1] < sorted_ids[i], AH_ERR_INVALID_ARGUMENT, "sorted_ids is not strictly ascending at position %zu (%u after %u)",
-                   i, sorted_ids[i], sorted_ids[i - 1]);
+    AH_TRY(check_sorted_ids(sorted_ids, n));
     AH_TRY(index_updatable(ix));
     AH_REQUIRE(n == 0 || ix->n_trees == 0 || tree_seeds, AH_ERR_INVALID_ARGUMENT, "tree_seeds is NULL");
     DeviceRestore restore_device;
@@ -1745,10 +1565,9 @@ int ah_index_export(ah_index *ix, ah_node *nodes, uint32_t *roots, uint32_t *des
     AH_INDEX_LIVE(ix);
     DeviceRestore restore_device;
     ah_dataset *ds = ix->ds;
-    AH_HIP(hipSetDevice(ds->device));
-    ContextLease lease(ds);
-    AH_REQUIRE(lease.c, AH_ERR_DEVICE, "cannot create a HIP stream");
-    const hipStream_t s = lease.c->stream;
+    IndexCall call;
+    AH_TRY(call.begin(ds));
+    const hipStream_t s = call.stream();
     std::vector<DNode> raw(nodes ? ix->n_nodes : 0);
     if (!raw.empty()) AH_HIP(hipMemcpyAsync(raw.data(), ix->d_nodes, raw.size() * sizeof(DNode), hipMemcpyDeviceToHost, s));
     if (roots && ix->n_trees) AH_HIP(hipMemcpyAsync(roots, ix->d_roots, (size_t)ix->n_trees * 4, hipMemcpyDeviceToHost, s));
@@ -1758,21 +1577,7 @@ int ah_index_export(ah_index *ix, ah_node *nodes, uint32_t *roots, uint32_t *des
     if (normal_headers && ix->n_normals)
         AH_HIP(hipMemcpyAsync(normal_headers, ix->d_nhdrs, (size_t)ix->n_normals * header_floats(ds->metric) * 4, hipMemcpyDeviceToHost, s));
     AH_HIP(hipStreamSynchronize(s));
-    for (size_t i = 0; i < raw.size(); i++) {
-        const DNode &d = raw[i];
-        ah_node nd{};
-        nd.kind = (uint8_t)(d.kind & 0xFFu);
-        if (nd.kind == AH_NODE_SPLIT) {
-            nd.has_normal = (d.kind & 0x100u) ? 1 : 0;
-            nd.left = d.a;
-            nd.right = d.b;
-            nd.offset = d.c;
-        } else if (nd.kind == AH_NODE_DESCENDANTS) {
-            nd.offset = d.a;
-            nd.count = d.b;
-        }
-        nodes[i] = nd;
-    }
+    for (size_t i = 0; i < raw.size(); i++) nodes[i] = to_host_node(raw[i]);
     return AH_OK;
     AH_GUARDED_END
 }
@@ -1803,13 +1608,7 @@ int ah_index_delta_destroy(ah_index_delta *d) {
 
 int ah_index_suspend(ah_index *ix) {
     AH_GUARDED("ah_index_suspend")
-    AH_REQUIRE(ix && ix->ds, AH_ERR_INVALID_ARGUMENT, "index is NULL");
-    AH_INDEX_LIVE(ix);
-    {
-        std::lock_guard<std::mutex> lk(ix->stats_mu);
-        AH_REQUIRE(ix->fstats.filters_alive == 0, AH_ERR_INVALID_ARGUMENT, "the index has %llu live filters: ah_filter_destroy them first",
-                   (unsigned long long)ix->fstats.filters_alive);
-    }
+    AH_TRY(index_updatable(ix));
     {
         // no queued search of this index reads the rows any more
         DeviceRestore restore_device;

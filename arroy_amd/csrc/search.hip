@@ -3915,27 +3915,15 @@ int ah_index_create_from_view(ah_dataset *ds, const ah_forest_view *view, ah_ind
     std::vector<uint64_t> offsets;
     for (uint64_t i = 0; i < v.n_nodes; i++) {
         const ah_node &nd = v.nodes[i];
-        DNode d{};
-        d.kind = nd.kind;
-        if (nd.kind == AH_NODE_SPLIT) {
-            d.a = nd.left;
-            d.b = nd.right;
-            if (nd.has_normal) {
-                d.kind |= 0x100u;
-                d.c = (uint32_t)offsets.size();
-                offsets.push_back(nd.offset);
-            }
-        } else {
-            d.a = (uint32_t)nd.offset;
-            d.b = nd.count;
+        nodes[i] = to_device_node(nd, (uint32_t)offsets.size());
+        if (nodes[i].kind & 0x100u) offsets.push_back(nd.offset);
+        if (nd.kind != AH_NODE_SPLIT) {
             ix->max_desc = std::max(ix->max_desc, nd.count);
             ix->n_leaves++;
         }
-        nodes[i] = d;
     }
     ix->n_normals = (uint32_t)offsets.size();
     ix->normals_cap = std::max<uint32_t>(1, ix->n_normals);
-    const bool bq = metric_is_bq(ds->metric);
     const uint32_t hf = header_floats(ds->metric);
     const size_t row_bytes = ds->row_bytes();
     int st = AH_OK;
@@ -3974,10 +3962,7 @@ int ah_index_create_from_view(ah_dataset *ds, const ah_forest_view *view, ah_ind
     ix->nv.dims = ds->dims;
     ix->nv.pitch = ds->pitch;
     ix->nv.words = ds->words;
-    ix->nv.n = ix->n_normals;
-    ix->nv.rows_f32 = bq ? nullptr : reinterpret_cast<const float *>(ix->d_nrows);
-    ix->nv.rows_bq = bq ? reinterpret_cast<const uint64_t *>(ix->d_nrows) : nullptr;
-    ix->nv.headers = ix->d_nhdrs;
+    index_derive_normals_view(ix);
     ix->nv.ids = nullptr;
     ix->nv.lut = nullptr;
     ix->nv.lut_len = 0;

@@ -28,10 +28,6 @@ constexpr unsigned kUpBlock = 256;                          // 4 waves
 enum Path { kInPlace = 0, kAppend = 1, kMerge = 2 };
 const char *const kPathName[3] = {"in place", "append", "merge"};
 
-unsigned grid_of(uint64_t work, uint64_t per_block, unsigned cap) {
-    return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((work + per_block - 1) / per_block, cap));
-}
-
 __device__ __forceinline__ uint64_t lower_bound_u32(const uint32_t *a, uint64_t n, uint32_t x) {
     uint64_t lo = 0, hi = n;
     while (lo < hi) {
@@ -252,16 +248,7 @@ void merge_ids(const ah_dataset *ds, const UpdateArgs &a, const Plan &p, std::ve
     while (j < a.n_up) out->push_back(a.up[j++]);
 }
 
-int alloc(DevMem *m, size_t bytes) {
-    const hipError_t e = dev_malloc(&m->p, std::max<size_t>(bytes, 1));
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        set_error("device allocation of %zu bytes for the update failed: %s", bytes, hipGetErrorString(e));
-        set_error_status(e == hipErrorOutOfMemory ? AH_ERR_OUT_OF_MEMORY : AH_ERR_DEVICE);
-        return e == hipErrorOutOfMemory ? AH_ERR_OUT_OF_MEMORY : AH_ERR_DEVICE;
-    }
-    return AH_OK;
-}
+int alloc(DevMem *m, size_t bytes) { return ah::alloc(m, bytes, "the update"); }
 
 // One member's share of an update: everything it allocates before the commit, owned until then.
 struct MemberUpdate {
