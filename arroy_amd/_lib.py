@@ -103,6 +103,7 @@ class AhIndexInfo(C.Structure):
 
 
 NEW_ROOT = 0xFFFFFFFF  # AH_NEW_ROOT: a tree of ah_index_graft that becomes a new root
+DROP_SORT_ROOTS = 1    # AH_DROP_SORT_ROOTS: ah_index_drop_trees leaves the surviving roots ascending
 
 
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64)
@@ -272,6 +273,8 @@ SIGNATURES = {
     "ah_index_delete_items": (C.c_int, [_VP, _U32P, C.c_size_t, C.c_uint32, C.POINTER(C.c_void_p)]),
     "ah_index_delta_get": (C.c_int, [_VP, C.POINTER(AhIndexDeltaView)]),
     "ah_index_delta_destroy": (C.c_int, [_VP]),
+    # `delete_extra_trees` on a resident index
+    "ah_index_drop_trees": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
     # inserts and grafts on a resident index; the index as it is on the device
     "ah_index_insert_items": (C.c_int, [_VP, _U32P, C.c_size_t, _U64P, C.POINTER(C.c_void_p)]),
     "ah_index_graft": (C.c_int, [_VP, C.POINTER(AhForestView), _U32P, _U32P, _U32P]),

@@ -1,9 +1,10 @@
-// index_update.hip — ah_index_delete_items / ah_index_insert_items / ah_index_graft / ah_index_compact / ah_index_footprint_get /
-// ah_index_export / ah_index_suspend / ah_index_resume (include/arroy_hip.h): the kernels of the four updates, each call's host
-// function (delete_impl, insert_impl, graft_impl, compact_count / footprint_impl / compact_impl) and the entry points.  What the
+// index_update.hip — ah_index_delete_items / ah_index_drop_trees / ah_index_insert_items / ah_index_graft / ah_index_compact /
+// ah_index_footprint_get / ah_index_export / ah_index_suspend / ah_index_resume (include/arroy_hip.h): the kernels of the five
+// updates, each call's host function (delete_impl, drop_impl, insert_impl, graft_impl, compact_count / footprint_impl /
+// compact_impl) and the entry points.  What the
 // host functions share is not here: the call scope, the span loop, the read-back, the commit and the node conversions are in
-// index_device.h, the workspace layouts in index_workspace.h, grid_of and the allocation helper in common.h.  The inserts, the
-// grafts and the compaction are described above their kernels; the delete is the part of an
+// index_device.h, the workspace layouts in index_workspace.h, grid_of and the allocation helper in common.h.  The dropped trees,
+// the inserts, the grafts and the compaction are described above their kernels; the delete is the part of an
 // incremental `Writer::build` that takes the updated ids out of every tree (`delete_items_from_trees`, src/writer.rs:978-1114)
 // done where the forest lives, so that the index of the last build serves the routing of the next one instead of being
 // uploaded again.
@@ -332,6 +333,139 @@ __global__ __launch_bounds__(kIxBlock) void k_delete_gather(DeleteArgs a, const 
         }
         const uint32_t *src = blob + a.seg[e.node];
         for (uint32_t j = lane; j < e.b; j += 64) out[e.a + j] = src[j];
+    }
+}
+
+// ---- dropped trees ------------------------------------------------------------------------------------------------------------
+// ah_index_drop_trees: `delete_extra_trees` (src/writer.rs:631-655), the tree step of an incremental `Writer::build` that runs
+// before the delete: n_drop times `root = roots.swap_remove(0); delete_tree(root)` ("Dropped trees on a resident
+// index").  Which roots go and the order of those that stay is a host computation on the n_trees words read back from d_roots;
+// every pass reads the index and writes new memory only:
+//   1. levels    the nodes of the dropped trees in breadth-first order from the dropped roots only, one launch per level, as the
+//                delete walks the whole forest: `dropped[node]`;
+//   2. lengths   per node: the ids it holds if it is an in-use Descendants node that stays, whether it is dropped, whether it is
+//                in use afterwards; three exclusive scans (scan_device.h) turn them into the offsets of the new blob, the
+//                positions of the dropped nodes in the delta's `removed` and every node's rank among the nodes in use;
+//   3. copy      a wave per Descendants node that stays copies its ids to the new offset, 64 ids a step: the lists end up in
+//                ascending node order with their exact lengths, the invariant ah_index_compact relies on;
+//   4. apply     the new node array (a dropped node becomes a free slot, a list that stays gets its new offset, everything else
+//                is copied bit for bit) and the `removed` list; read back; the index's pointers are swapped last.
+// The normal rows are not touched: those of the dropped split nodes are orphaned until ah_index_compact.
+enum DCtl { DCTL_TAIL = 0, DCTL_ERR, DCTL_LEAVES, DCTL_MAX_DESC, DCTL_DESC_LEN, DCTL_REMOVED, DCTL_WORDS };
+
+struct DropArgs {
+    const DNode *nodes;
+    uint32_t n_nodes;
+    const uint32_t *desc;
+    uint64_t old_desc_len;
+    // per node, zeroed before the first kernel
+    uint32_t *order;    // the nodes of the dropped trees, level by level
+    uint32_t *dropped;  // 1 for a node of a dropped tree
+    uint32_t *len;      // ids a Descendants node that stays holds -> (scan) where they start in the new blob
+    uint32_t *rpos;     // `dropped` again -> (scan) the node's position in `removed`
+    uint32_t *ctl;
+    // what the scans gave (set before the passes that store through them)
+    uint32_t new_desc_len, n_removed;
+};
+
+// the roots of the dropped trees (the host has checked that each is a node of the index)
+__global__ __launch_bounds__(kIxBlock) void k_drop_seed(DropArgs a, const uint32_t *__restrict__ roots, uint32_t n_drop) {
+    const uint32_t stride = gridDim.x * blockDim.x;
+    for (uint32_t t = blockIdx.x * blockDim.x + threadIdx.x; t < n_drop; t += stride) {
+        a.order[t] = roots[t];
+        if (atomicExch(&a.dropped[roots[t]], 1u)) atomicOr(&a.ctl[DCTL_ERR], 1u);  // (a root listed twice)
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) a.ctl[DCTL_TAIL] = n_drop;
+}
+
+// levels: the children of order[begin, end) are appended behind the tail
+__global__ __launch_bounds__(kIxBlock) void k_drop_level(DropArgs a, uint32_t begin, uint32_t end) {
+    const uint32_t stride = gridDim.x * blockDim.x;
+    for (uint32_t i = begin + blockIdx.x * blockDim.x + threadIdx.x; i < end; i += stride) {
+        const DNode nd = a.nodes[a.order[i]];
+        if ((nd.kind & 0xFFu) != AH_NODE_SPLIT) continue;
+        const uint64_t pos = atomicAdd(&a.ctl[DCTL_TAIL], 2u);
+        if (pos + 2 > a.n_nodes || nd.a >= a.n_nodes || nd.b >= a.n_nodes) {  // (not a forest: create_from_view has refused it)
+            atomicOr(&a.ctl[DCTL_ERR], 1u);
+            continue;
+        }
+        a.order[pos] = nd.a;
+        a.order[pos + 1] = nd.b;
+        if (atomicExch(&a.dropped[nd.a], 1u) | atomicExch(&a.dropped[nd.b], 1u)) atomicOr(&a.ctl[DCTL_ERR], 1u);  // (reachable twice)
+    }
+}
+
+// lengths: what the three scans start from
+__global__ __launch_bounds__(kIxBlock) void k_drop_lengths(DropArgs a, uint32_t *__restrict__ in_use) {
+    const uint32_t stride = gridDim.x * blockDim.x;
+    for (uint64_t node = blockIdx.x * blockDim.x + threadIdx.x; node < a.n_nodes; node += stride) {
+        const DNode nd = a.nodes[node];
+        const uint32_t d = a.dropped[node];
+        const bool stays = nd.kind != 0 && !d;
+        if (d && nd.kind == 0) atomicOr(&a.ctl[DCTL_ERR], 2u);  // (a dropped tree led into a free slot)
+        a.len[node] = stays && (nd.kind & 0xFFu) == AH_NODE_DESCENDANTS ? nd.b : 0u;
+        a.rpos[node] = d;
+        in_use[node] = stays ? 1u : 0u;
+    }
+}
+
+// copy: the Descendants nodes that stay among [lo, hi), a wave each (len: scanned): 64 ids a step, four steps in flight
+__global__ __launch_bounds__(kIxBlock) void k_drop_copy(DropArgs a, uint32_t lo, uint32_t hi, uint32_t *__restrict__ out) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t n_waves = (gridDim.x * blockDim.x) >> 6;
+    for (uint32_t node = lo + ((blockIdx.x * blockDim.x + threadIdx.x) >> 6); node < hi; node += n_waves) {
+        const DNode nd = a.nodes[node];
+        if ((nd.kind & 0xFFu) != AH_NODE_DESCENDANTS || a.dropped[node]) continue;  // (wave-uniform, as is every branch below)
+        if ((uint64_t)nd.a + nd.b > a.old_desc_len) {
+            if (lane == 0) atomicOr(&a.ctl[DCTL_ERR], 4u);
+            continue;
+        }
+        const uint32_t *src = a.desc + nd.a;
+        const uint64_t base = a.len[node];
+        for (uint64_t j0 = lane; j0 < nd.b; j0 += 4 * 64) {
+            uint32_t id[4] = {0, 0, 0, 0};
+#pragma unroll
+            for (uint32_t k = 0; k < 4; k++)
+                if (j0 + k * 64 < nd.b) id[k] = src[j0 + k * 64];
+#pragma unroll
+            for (uint32_t k = 0; k < 4; k++) {
+                if (j0 + k * 64 >= nd.b) continue;
+                const uint64_t at = base + j0 + k * 64;
+                if (at < a.new_desc_len) out[at] = id[k];
+                else atomicOr(&a.ctl[DCTL_ERR], 8u);
+            }
+        }
+    }
+}
+
+// apply: every node as it is afterwards, the dropped ones into `removed` (len / rpos: scanned)
+__global__ __launch_bounds__(kIxBlock) void k_drop_apply(DropArgs a, DNode *__restrict__ out, uint32_t *__restrict__ removed) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t stride = gridDim.x * blockDim.x;
+    const uint32_t rounds = (a.n_nodes + stride - 1) / stride;
+    uint32_t leaves = 0, largest = 0;
+    for (uint32_t r = 0; r < rounds; r++) {
+        const uint64_t node = (uint64_t)r * stride + blockIdx.x * blockDim.x + threadIdx.x;
+        if (node >= a.n_nodes) break;
+        DNode nd = a.nodes[node];
+        if (a.dropped[node]) {
+            nd = DNode{0, 0, 0, 0};
+            if (a.rpos[node] < a.n_removed) removed[a.rpos[node]] = (uint32_t)node;
+            else atomicOr(&a.ctl[DCTL_ERR], 16u);
+        } else if ((nd.kind & 0xFFu) == AH_NODE_DESCENDANTS) {
+            nd.a = a.len[node];
+            leaves++;
+            largest = max(largest, nd.b);
+        }
+        out[node] = nd;
+    }
+    for (uint32_t d = 32; d > 0; d >>= 1) {
+        leaves += __shfl_xor(leaves, d, 64);
+        largest = max(largest, (uint32_t)__shfl_xor(largest, d, 64));
+    }
+    if (lane == 0 && leaves) {
+        atomicAdd(&a.ctl[DCTL_LEAVES], leaves);
+        atomicMax(&a.ctl[DCTL_MAX_DESC], largest);
     }
 }
 
@@ -1030,6 +1164,109 @@ int index_updatable(ah_index *ix) {
     return AH_OK;
 }
 
+int drop_impl(ah_index *ix, uint32_t n_drop, bool sort_roots, ah_index_delta *delta) {
+    IndexCall call;
+    AH_TRY(call.begin(ix->ds));
+    const hipStream_t s = call.stream();
+    const uint32_t nn = ix->n_nodes, n_trees = ix->n_trees;
+    const uint64_t old_desc_len = ix->desc_len;
+    n_drop = std::min(n_drop, n_trees);
+    // the roots: `roots.swap_remove(0)` n_drop times on the host's copy
+    std::vector<uint32_t> roots(n_trees), gone;
+    if (n_trees) AH_TRY(read_back(roots.data(), ix->d_roots, n_trees, s));
+    if (n_drop == 0) {  // nothing to do: the current roots, and the index keeps its arrays
+        delta->roots = std::move(roots);
+        return AH_OK;
+    }
+    AH_REQUIRE(n_trees <= nn, AH_ERR_DEVICE, "the index has more trees (%u) than nodes (%u)", n_trees, nn);
+    gone.reserve(n_drop);
+    for (uint32_t k = 0; k < n_drop; k++) {
+        AH_REQUIRE(roots[0] < nn, AH_ERR_DEVICE, "root %u of the index is no node of it (%u nodes)", roots[0], nn);
+        gone.push_back(roots[0]);
+        roots[0] = roots.back();
+        roots.pop_back();
+    }
+    if (sort_roots) std::sort(roots.begin(), roots.end());  // roots.sort_unstable() (src/writer.rs:1001)
+    const uint32_t kept = n_trees - n_drop;
+    // every buffer whose size is known now; kernels write only into these
+    DropArgs a{};
+    a.nodes = ix->d_nodes;
+    a.n_nodes = nn;
+    a.desc = ix->d_desc;
+    a.old_desc_len = old_desc_len;
+    uint32_t *tile_sums = nullptr, *d_gone = nullptr;
+    const Workspace ws = drop_workspace(a, &tile_sums, &d_gone, nn, n_drop, kScanTile, DCTL_WORDS);
+    DevMem work, new_nodes, new_roots, new_rank, new_desc, out;
+    AH_TRY(alloc(&work, ws.bytes()));
+    ws.carve(work.p, ws.bytes());
+    AH_TRY(alloc(&new_nodes, (size_t)nn * sizeof(DNode)));
+    AH_TRY(alloc(&new_roots, (size_t)kept * 4));
+    AH_TRY(alloc(&new_rank, ((size_t)nn + 1) * 4));
+    AH_HIP(hipMemsetAsync(work.p, 0, ws.zeroed_bytes(), s));
+    AH_HIP(hipMemcpyAsync(d_gone, gone.data(), (size_t)n_drop * 4, hipMemcpyHostToDevice, s));
+    if (kept) AH_HIP(hipMemcpyAsync(new_roots.p, roots.data(), (size_t)kept * 4, hipMemcpyHostToDevice, s));
+    // 1. levels
+    uint32_t ctl[DCTL_WORDS];
+    uint32_t begin = 0, end = n_drop;
+    size_t levels = 0;
+    hipLaunchKernelGGL(k_drop_seed, dim3(grid_of(n_drop, kIxBlock, 1024)), dim3(kIxBlock), 0, s, a, (const uint32_t *)d_gone, n_drop);
+    while (begin < end) {
+        levels++;
+        hipLaunchKernelGGL(k_drop_level, dim3(grid_of(end - begin, kIxBlock, 4096)), dim3(kIxBlock), 0, s, a, begin, end);
+        AH_TRY(read_back(ctl, a.ctl, 2, s));
+        AH_REQUIRE(ctl[DCTL_ERR] == 0 && ctl[DCTL_TAIL] >= end && ctl[DCTL_TAIL] <= nn, AH_ERR_DEVICE,
+                   "the nodes of the index are not a forest (a node is reachable twice)");
+        begin = end;
+        end = ctl[DCTL_TAIL];
+    }
+    const uint32_t reached = end;
+    const auto t_levels = call.now();
+    // 2. lengths and the scans
+    hipLaunchKernelGGL(k_drop_lengths, dim3(grid_of(nn, kIxBlock, 4096)), dim3(kIxBlock), 0, s, a, new_rank.as<uint32_t>());
+    launch_exclusive_scan(a.len, nn, tile_sums, a.ctl + DCTL_DESC_LEN, s);
+    launch_exclusive_scan(a.rpos, nn, tile_sums, a.ctl + DCTL_REMOVED, s);
+    launch_exclusive_scan(new_rank.as<uint32_t>(), nn, tile_sums, new_rank.as<uint32_t>() + nn, s);
+    AH_TRY(read_back(ctl, a.ctl, DCTL_WORDS, s));
+    const auto t_lengths = call.now();
+    const uint32_t desc_len = ctl[DCTL_DESC_LEN], n_removed = ctl[DCTL_REMOVED];
+    AH_REQUIRE(ctl[DCTL_ERR] == 0 && desc_len <= old_desc_len && n_removed == reached, AH_ERR_DEVICE,
+               "the index drop found the index inconsistent (%u): the index is unchanged", ctl[DCTL_ERR]);
+    a.new_desc_len = desc_len;
+    a.n_removed = n_removed;
+    // the buffers whose size the scans have just given, and the host's
+    AH_TRY(alloc(&new_desc, (size_t)desc_len * 4));
+    AH_TRY(alloc(&out, (size_t)n_removed * 4));
+    delta->removed.resize(n_removed);
+    // 3. copy, in launches of at most AH_LAUNCH_MAX_ITEMS nodes
+    for_spans(nn, call.span(), [&](uint64_t lo, uint64_t hi) {
+        hipLaunchKernelGGL(k_drop_copy, dim3(grid_of(hi - lo, kIxBlock / 64, 1u << 16)), dim3(kIxBlock), 0, s, a, (uint32_t)lo, (uint32_t)hi,
+                           new_desc.as<uint32_t>());
+    });
+    AH_HIP(hipGetLastError());
+    const auto t_copy = call.phase_end();
+    // 4. apply
+    hipLaunchKernelGGL(k_drop_apply, dim3(grid_of(nn, kIxBlock, 4096)), dim3(kIxBlock), 0, s, a, new_nodes.as<DNode>(), out.as<uint32_t>());
+    // read back
+    AH_HIP(hipMemcpyAsync(delta->removed.data(), out.p, (size_t)n_removed * 4, hipMemcpyDeviceToHost, s));
+    AH_TRY(read_back(ctl, a.ctl, DCTL_WORDS, s));
+    AH_REQUIRE(ctl[DCTL_ERR] == 0, AH_ERR_DEVICE, "the index drop found its own counts inconsistent (%u): the index is unchanged", ctl[DCTL_ERR]);
+    delta->roots = std::move(roots);
+    const auto t_apply = call.now();
+    IndexCommit c(ix, &new_nodes, &new_roots, &new_desc, &new_rank);
+    c.n_trees = kept;
+    c.desc_len = desc_len;
+    c.n_leaves = ctl[DCTL_LEAVES];
+    c.max_desc = ctl[DCTL_MAX_DESC];
+    c.compacted = false;
+    index_commit(ix, c);
+    if (call.timing)
+        fprintf(stderr, "[ah] index drop: %u of %u trees, %u of %u nodes freed in %zu levels, %llu -> %u stored ids: "
+                        "levels %.6f s, lengths %.6f s, copy %.6f s, apply and read-back %.6f s\n",
+                n_drop, n_trees, n_removed, nn, levels, (unsigned long long)old_desc_len, desc_len, call.secs(call.t0, t_levels),
+                call.secs(t_levels, t_lengths), call.secs(t_lengths, t_copy), call.secs(t_copy, t_apply));
+    return AH_OK;
+}
+
 int insert_impl(ah_index *ix, const uint32_t *ids, size_t n, const uint64_t *seeds, ah_index_delta *delta) {
     ah_dataset *ds = ix->ds;
     IndexCall call;
@@ -1494,6 +1731,21 @@ int ah_index_delete_items(ah_index *ix, const uint32_t *sorted_ids, size_t n, ui
     DeviceRestore restore_device;
     std::unique_ptr<ah_index_delta> delta(new ah_index_delta);
     AH_TRY(delete_impl(ix, sorted_ids, n, split_after, delta.get()));
+    *out_delta = delta.release();
+    return AH_OK;
+    AH_GUARDED_END
+}
+
+int ah_index_drop_trees(ah_index *ix, uint32_t n_drop, uint32_t flags, ah_index_delta **out_delta) {
+    AH_GUARDED("ah_index_drop_trees")
+    AH_REQUIRE(out_delta, AH_ERR_INVALID_ARGUMENT, "out_delta is NULL");
+    *out_delta = nullptr;
+    // (what can be judged without the index first)
+    AH_REQUIRE((flags & ~AH_DROP_SORT_ROOTS) == 0, AH_ERR_INVALID_ARGUMENT, "flags = 0x%x: only AH_DROP_SORT_ROOTS is known", flags);
+    AH_TRY(index_updatable(ix));
+    DeviceRestore restore_device;
+    std::unique_ptr<ah_index_delta> delta(new ah_index_delta);
+    AH_TRY(drop_impl(ix, n_drop, (flags & AH_DROP_SORT_ROOTS) != 0, delta.get()));
     *out_delta = delta.release();
     return AH_OK;
     AH_GUARDED_END

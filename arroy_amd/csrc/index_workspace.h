@@ -1,7 +1,8 @@
 // index_workspace.h — the device workspaces of the maintenance calls of a resident index (index_update.hip, index_audit.hip): one
 // block each, carved into arrays of 32-bit words.  A layout is written down ONCE, as the list of (pointer to carve, words) in
 // the order the arrays lie in the block; the bytes to allocate, the part the call zeroes and the pointers all come from that
-// list.  Plain C++ with no device call, so that tests/index_workspace_check.cpp can put the layouts through a sanitizer.
+// list.  Plain C++ with no device call, so that tests/index_workspace_check.cpp and tests/index_drop_workspace_check.cpp can put the
+// layouts through a sanitizer.
 #pragma once
 
 #include <cassert>
@@ -59,6 +60,17 @@ Workspace delete_workspace(Args &a, uint32_t **tile_sums, uint32_t n_nodes, uint
     Workspace ws;
     for (uint32_t **f : {&a.order, &a.rep, &a.cnt, &a.flags, &a.own, &a.seg, &a.chg, &a.dseg, &a.cursor, &a.merged}) ws.add(f, per_node);
     return ws.add(tile_sums, scan_tile_words(n_nodes, scan_tile)).add(&a.ctl, ctl_words);
+}
+
+// ah_index_drop_trees: four arrays per node, zeroed; the dropped roots the host uploads are written whole
+template <class Args>
+Workspace drop_workspace(Args &a, uint32_t **tile_sums, uint32_t **seed_roots, uint32_t n_nodes, uint32_t n_drop, uint32_t scan_tile,
+                         size_t ctl_words) {
+    const size_t per_node = (size_t)n_nodes + 1;
+    Workspace ws;
+    for (uint32_t **f : {&a.order, &a.dropped, &a.len, &a.rpos}) ws.add(f, per_node);
+    ws.add(tile_sums, scan_tile_words(n_nodes, scan_tile)).add(&a.ctl, ctl_words).zeroed_to_here();
+    return ws.add(seed_roots, n_drop);
 }
 
 // ah_index_insert_items: the tree seeds (8 bytes each) first; the ids, the leaf of every pair and `landed` are written whole

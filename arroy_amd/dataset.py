@@ -666,6 +666,17 @@ class Index:
         _lib.check(_lib.lib().ah_index_delete_items(self._h, _ptr(arr), arr.size, int(split_after), C.byref(h)))
         return self._take_delta(h)
 
+    def drop_trees(self, n_drop: int, sort_roots: bool = False) -> dict:
+        """ah_index_drop_trees: `delete_extra_trees` (src/writer.rs:631-655) on the resident index, `n_drop` times
+        `roots.swap_remove(0)` + `delete_tree`.  Returns a delta in the shape of delete_items (TreeStore.apply_delta applies
+        it unchanged): `removed` is every node of the dropped trees, `put` is empty, `roots` the surviving roots in the order
+        the swap_removes leave them, or ascending with sort_roots (for a build that calls no delete_items afterwards)."""
+        if n_drop < 0:
+            raise ValueError(f"n_drop = {n_drop}")
+        h = C.c_void_p()
+        _lib.check(_lib.lib().ah_index_drop_trees(self._h, int(n_drop), _lib.DROP_SORT_ROOTS if sort_roots else 0, C.byref(h)))
+        return self._take_delta(h)
+
     @staticmethod
     def _take_delta(h) -> dict:
         """ah_index_delta_get as numpy arrays; the delta is destroyed."""

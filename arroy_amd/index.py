@@ -78,6 +78,20 @@ def target_n_trees(n_trees: Optional[int], dimensions: int, n_items: int, n_root
     return nb_trees
 
 
+def roots_after_drop(roots: Sequence[int], n_drop: int) -> Tuple[List[int], List[int]]:
+    """`delete_extra_trees` (src/writer.rs:631-655) on the roots alone: `n_drop` times `roots.swap_remove(0)`, stopping when
+    the roots run out.  Returns (the roots that stay, in the order the swap_removes leave them; the dropped roots, in the order
+    they were dropped).  From [r0 .. r5] and 4: ([r2, r1], [r0, r5, r4, r3])."""
+    kept, dropped = list(roots), []
+    for _ in range(max(0, int(n_drop))):
+        if not kept:
+            break
+        dropped.append(kept[0])
+        kept[0] = kept[-1]
+        kept.pop()
+    return kept, dropped
+
+
 class TreeStore:
     """Host-side tree nodes — what arroy keeps in LMDB under `Key::tree` (src/node.rs:216-241):
     id -> ("D", ascending ids) | ("S", left, right, header f32[], vector bytes or None)."""
@@ -278,6 +292,7 @@ class _IndexState:
         self.device_inserts = 0  # builds that ended with the resident index still serving (Index.insert_items / graft)
         self.index_uploads = 0   # indexes made from a whole view of the store (every node, id and normal uploaded)
         self.device_compactions = 0  # builds that ended with a compaction of the resident index (Index.compact)
+        self.device_drops = 0    # builds that dropped their extra trees on the resident index (Index.drop_trees)
 
 
 def compaction_due(fp: dict) -> bool:
@@ -370,6 +385,11 @@ class ArroyBuilder:
         # True: the index that serves the searches is audited on the device at the end of build() (Index.audit: validity
         # and the per-tree stats against the store's); a finding raises AssertionError
         self.device_audit = False
+        # True: a build that drops trees keeps its resident index and drops them there (Index.drop_trees) instead of closing
+        # it and uploading an index from the whole view.  OFF by default: tests/test_gpu_index_insert.py
+        # (test_writer_keeps_the_index_and_builds_the_same_trees) pins the fall-back counts of a tree-dropping build, so the
+        # default can only flip in a change that may touch that test
+        self.device_drop = False
 
     def n_trees(self, n: int) -> "ArroyBuilder":
         self._n_trees = int(n)
@@ -403,13 +423,15 @@ class ArroyBuilder:
         n = ids.size
         split_after = self._split_after or w.dimensions
         # The index of the last build stays for this build's delete and routing (suspended while the dataset is updated)
-        # when this will be an incremental build on the same dataset that drops no tree: `delete_extra_trees` runs before
-        # the removal, and the resident index would still hold the dropped trees.
+        # when this will be an incremental build on the same dataset that drops no tree, or drops them on the index
+        # (device_drop): `delete_extra_trees` runs before the removal, and without Index.drop_trees the resident index would
+        # still hold the dropped trees.
         resident = st.index
         st.index = None
         keep = (resident is not None and self.device_delete and n > split_after and st.trees is not None
                 and bool(st.trees.roots) and st.metadata is not None
-                and target_n_trees(self._n_trees, w.dimensions, n, len(st.trees.roots)) >= len(st.trees.roots))
+                and (self.device_drop
+                     or target_n_trees(self._n_trees, w.dimensions, n, len(st.trees.roots)) >= len(st.trees.roots)))
         try:  # (whatever happens in between, the kept index does not linger suspended with its normals in HBM)
             if resident is not None:
                 if keep:
@@ -555,9 +577,9 @@ class ArroyBuilder:
                 watcher_stop.set()
 
     def _incremental(self, ds: Dataset, st: "_IndexState", ids: np.ndarray, split_after: int, resident=None):
-        """`resident`: the last build's Index, resumed on the updated dataset (build() has checked that no tree is dropped): the
-        removal and the routing run on it.  None: the removal on the host, the routing on a throw-away index of the store's
-        view.  Returns the new `_keep` when `resident` has followed every step and is the index of the store as it is now
+        """`resident`: the last build's Index, resumed on the updated dataset (build() has checked that no tree is dropped, or
+        that device_drop is on): the dropped trees, the removal and the routing run on it.  None: the removal on the host, the
+        routing on a throw-away index of the store's view.  Returns the new `_keep` when `resident` has followed every step and is the index of the store as it is now
         (device_insert); None when it has been closed here and the caller makes an index from the view."""
         from .dataset import Index
         w, trees, dist = self._w, st.trees, self._w.database.distance
@@ -569,11 +591,22 @@ class ArroyBuilder:
         trees.begin_build()  # node ids in use are snapshotted before anything is deleted (:516-518)
         # target_n_trees / delete_extra_trees (:521-522, 631-655): the oldest tree first, `roots.swap_remove(0)`
         want = target_n_trees(self._n_trees, w.dimensions, len(ids), len(trees.roots))
-        while len(trees.roots) > want:
-            root = trees.roots[0]
-            trees.roots[0] = trees.roots[-1]
-            trees.roots.pop()
-            trees.delete_tree(root)
+        n_drop = max(0, len(trees.roots) - want)
+        if n_drop and resident is not None:
+            # on the resident index (build() keeps it for a tree-dropping build only with device_drop); the roots come back
+            # sorted when no delete, which sorts them itself, follows.  A failure leaves the index unchanged: it is closed and
+            # the build goes on on the host path, as after a failed insert
+            try:
+                trees.apply_delta(resident.drop_trees(n_drop, sort_roots=not to_delete.size), st._keep[4])
+                st.device_drops += 1
+                n_drop = 0
+            except _lib.ArroyHipError:
+                resident.close()
+                resident = None
+        if n_drop:
+            trees.roots, dropped = roots_after_drop(trees.roots, n_drop)
+            for root in dropped:
+                trees.delete_tree(root)
         # delete_items_from_trees (:525, 979-1114): updated ids leave the trees, emptied / shrunken branches collapse
         if resident is not None:
             try:

@@ -53,7 +53,8 @@ extern "C" {
                                   ah_dataset_packed_rows and the test aid ah_debug_query_screen_verify;
                                   v7 additions: updates of a finalized dataset (ah_dataset_update_vectors / _records,
                                   ah_group_update_vectors / _records, the test aid ah_debug_update_paths);
-                                  ah_index_footprint_get / ah_index_compact; ah_index_audit / ah_forest_view_audit */
+                                  ah_index_footprint_get / ah_index_compact; ah_index_audit / ah_forest_view_audit;
+                                  ah_index_drop_trees */
 
 /* every entry point is exported from the shared object (it is built with -fvisibility=hidden) */
 #if defined(__GNUC__)
@@ -772,6 +773,46 @@ AH_API int ah_index_delete_items(ah_index *index, const uint32_t *sorted_ids, si
 /* Pointers into the delta, valid until ah_index_delta_destroy. */
 AH_API int ah_index_delta_get(const ah_index_delta *d, ah_index_delta_view *out);
 AH_API int ah_index_delta_destroy(ah_index_delta *d);
+
+/* ------------------------------------------------------------------------------------------
+ * Dropped trees on a resident index (ABI v7 addition: look the symbol up).  `delete_extra_trees` (src/writer.rs:631-655,
+ * called at :522), the tree step of an incremental `Writer::build` that runs BEFORE the delete, applied to the index where
+ * it lives: a build that shrinks the forest (a lower n_trees, or `target_n_trees` following the item count) keeps its index
+ * resident instead of uploading every node, id and normal again.
+ *
+ * The call does min(n_drop, n_trees) times what the reference does: `root = roots.swap_remove(0); delete_tree(root)`.
+ * n_drop >= n_trees leaves an index of zero trees, which is legal: the searches and ah_route_items answer it with nothing.
+ * n_drop == 0 does nothing: the delta is empty and carries the current roots, nothing is allocated beyond the delta and the
+ * index's arrays are not replaced.
+ *   Roots        the surviving roots are left in the order the repeated swap_remove(0) leaves them: from [r0 .. r5] with
+ *                n_drop = 4 that is [r2, r1].  With AH_DROP_SORT_ROOTS they are left ascending by node index instead, what
+ *                `roots.sort_unstable()` (src/writer.rs:1001) makes of them: for a host that calls no ah_index_delete_items
+ *                (which sorts them itself) in the same build.
+ *   Nodes        every node reachable from a dropped root becomes a free slot (kind 0, all zeros, as a delete leaves them);
+ *                node indices are stable; the nodes of the surviving trees are bit-unchanged, except that the offset of a
+ *                Descendants node moves.
+ *   Descendants  rewritten into new memory: the lists of the surviving Descendants nodes in ascending node order with their
+ *                exact lengths (what ah_index_compact relies on).
+ *   Ranks        rebuilt, as ah_index_delete_items leaves them: per node the number of in-use nodes below it, which the coins
+ *                of ah_route_items at `normal: None` nodes are keyed by.
+ *   Normals      not touched: the rows of the dropped split nodes are orphaned, ah_index_footprint_get reports them and the
+ *                free slots, ah_index_compact reclaims both.
+ * Afterwards ah_search_batch*, ah_route_items, ah_index_insert_items, ah_index_delete_items, ah_index_graft,
+ * ah_index_compact and ah_index_audit return what they return on an ah_index_create_from_view of the store after the drop, on
+ * the same dataset with the roots in the same order: ids, distance bits, counts, landing nodes and coins.
+ *
+ * The delta (ah_index_delta_get): `removed` holds every node of the dropped trees, ascending — what the host deletes from
+ * its store; n_put = 0 and desc_len = 0; `roots` is the new order.
+ *
+ * The rules of ah_index_delete_items hold: all or nothing (every buffer is obtained before the kernel that fills it, the
+ * kernels write new memory only, the pointers are swapped after the last read-back; a bad argument — unknown bits in `flags`
+ * among them — or a failed allocation leaves the index as it was, searchable, holding nothing extra); refused
+ * (AH_ERR_INVALID_ARGUMENT) while the index has live filters or is suspended; not concurrent with any other call on the
+ * same index.  For the duration of the call the index holds its nodes, ranks and the surviving ids a second time, plus
+ * scratch of four words per node slot.
+ * ---------------------------------------------------------------------------------------- */
+#define AH_DROP_SORT_ROOTS 1u
+AH_API int ah_index_drop_trees(ah_index *index, uint32_t n_drop, uint32_t flags, ah_index_delta **out_delta);
 
 /* ------------------------------------------------------------------------------------------
  * Inserts and grafts on a resident index (ABI v7 additions: look the symbols up).  The other tree steps of an incremental
