@@ -178,6 +178,15 @@ class AhFilterCombineStats(C.Structure):
 FILTER_AND, FILTER_OR, FILTER_ANDNOT, FILTER_NOT = 0, 1, 2, 3
 FILTER_OPS = {"and": FILTER_AND, "or": FILTER_OR, "andnot": FILTER_ANDNOT, "not": FILTER_NOT}
 FILTER_COMBINE_MAX = 64
+FILTER_RESUME_GROUP = 16  # AH_FILTER_RESUME_GROUP
+
+
+class AhFilterEdit(C.Structure):
+    _fields_ = [("remove_sorted", C.c_void_p), ("n_remove", C.c_size_t), ("add_sorted", C.c_void_p), ("n_add", C.c_size_t)]
+
+
+class AhFilterResumeStats(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("filters", "groups", "words", "ids_removed", "ids_added", "leaves", "ids_walked")]
 
 
 class AhStreamNode(C.Structure):
@@ -269,6 +278,11 @@ SIGNATURES = {
                                     C.POINTER(AhFilterCombineStats)]),
     "ah_filter_create_bitmap": (C.c_int, [_VP, _U64P, C.c_uint64, C.POINTER(C.c_void_p)]),
     "ah_filter_export": (C.c_int, [_VP, C.POINTER(C.c_uint64), _U32P, _U32P]),
+    # filters across index maintenance
+    "ah_filter_suspend": (C.c_int, [_VP]),
+    "ah_filter_resume_batch": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(AhFilterEdit), C.c_size_t,
+                                         C.POINTER(AhFilterResumeStats)]),
+    "ah_index_filters_suspended": (C.c_int, [_VP, C.POINTER(C.c_uint64)]),
     # deletes on a resident index; an index kept across an update of its dataset
     "ah_index_delete_items": (C.c_int, [_VP, _U32P, C.c_size_t, C.c_uint32, C.POINTER(C.c_void_p)]),
     "ah_index_delta_get": (C.c_int, [_VP, C.POINTER(AhIndexDeltaView)]),

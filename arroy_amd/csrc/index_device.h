@@ -82,6 +82,9 @@ struct ah_index {
     bool counted = false;                    // counted in ds->live_indexes (an update of the dataset refuses meanwhile)
     bool suspended = false;                  // ah_index_suspend: not counted, and every call that reads the dataset refuses
     ah_filter_stats fstats{};                // under stats_mu; filters_alive is a level (ah_index_destroy refuses above 0)
+    // under stats_mu: filters ah_filter_suspend took out of filters_alive (the maintenance calls and ah_index_suspend do not
+    // see them; ah_index_destroy refuses above 0, their `ix` would dangle)
+    uint64_t filters_suspended = 0;
 };
 
 // every entry point that reads the dataset through the index

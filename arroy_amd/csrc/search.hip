@@ -3654,6 +3654,175 @@ __global__ __launch_bounds__(256) void k_leaf_kept_combine(SearchParams sp, uint
     block_add_u64(ids_walked, &counters[CB_IDS_WALKED], s_part);
 }
 
+// ---- filters across index maintenance (ah_filter_resume_batch) ----------------------------------------------------------
+// One filter of a call, in device memory, indexed by the wave-uniform blockIdx.y (scalar loads): where its old bitmap is and
+// how long, its new block, and its two edit lists as ranges of the call's one upload of ids.
+struct ResumeSlot {
+    const uint32_t *old_bits;
+    uint64_t old_len_bits;
+    uint32_t *bits;
+    uint64_t remove_off, n_remove, add_off, n_add;
+};
+// What one call counts on the device: the four totals of ah_filter_resume_stats, then RC_PER_FILTER words per filter.
+enum ResumeCounter { RC_REMOVED = 0, RC_ADDED, RC_LEAVES, RC_IDS_WALKED, RC_TOTALS, RC_LISTED = 0, RC_STORED, RC_PER_FILTER };
+
+// 1. re-cut: the new block of every filter whole — the old words below min(old, new) len_bits (the last one masked), zero above
+// (the padding words, the per-node counts k_leaf_kept_group writes afterwards, the tail).  Grid over (word, filter).
+__global__ __launch_bounds__(256) void k_filter_recut(const ResumeSlot *__restrict__ slots, uint64_t len_bits, uint64_t words,
+                                                      uint64_t block_words) {
+    const ResumeSlot sl = slots[blockIdx.y];
+    const uint64_t keep_bits = min(sl.old_len_bits, len_bits);  // (below it every word index is inside the old bitmap too)
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x, first = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    for (uint64_t quad = first; quad < words / 4; quad += stride) {  // (words: a multiple of 64, the blocks 128-byte aligned)
+        uint4 r = make_uint4(0, 0, 0, 0);
+        if ((quad << 7) < keep_bits) {
+            const uint4 a = reinterpret_cast<const uint4 *>(sl.old_bits)[quad];
+            r = make_uint4(a.x & word_mask(4 * quad, keep_bits), a.y & word_mask(4 * quad + 1, keep_bits),
+                           a.z & word_mask(4 * quad + 2, keep_bits), a.w & word_mask(4 * quad + 3, keep_bits));
+        }
+        reinterpret_cast<uint4 *>(sl.bits)[quad] = r;
+    }
+    for (uint64_t w = words + first; w < block_words; w += stride) sl.bits[w] = 0;
+}
+
+// 2. the host's delta: SET = false clears the bits of every filter's remove list, SET = true (the launch after it: an id in both
+// lists ends up set) sets those of its add list.  Ids at or above len_bits match nothing and are skipped.  The lists are
+// strictly ascending, so no two lanes flip the same bit and the number of bits that flipped is exact.
+template <bool SET>
+__global__ __launch_bounds__(256) void k_filter_edit(const ResumeSlot *__restrict__ slots, const uint32_t *__restrict__ ids,
+                                                     uint64_t len_bits, unsigned long long *__restrict__ counters) {
+    __shared__ unsigned long long s_part[4];
+    const ResumeSlot sl = slots[blockIdx.y];
+    const uint32_t *list = ids + (SET ? sl.add_off : sl.remove_off);
+    const uint64_t n = SET ? sl.n_add : sl.n_remove;
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    unsigned long long flipped = 0;
+    for (uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; g < n; g += stride) {
+        const uint32_t id = list[g];
+        if (id >= len_bits) continue;
+        const uint32_t bit = 1u << (id & 31);
+        const uint32_t old = SET ? atomicOr(&sl.bits[id >> 5], bit) : atomicAnd(&sl.bits[id >> 5], ~bit);
+        flipped += ((old & bit) != 0) != SET;
+    }
+    block_add_u64(flipped, &counters[SET ? RC_ADDED : RC_REMOVED], s_part);
+}
+
+// 3. `listed` of every filter: the set bits of its new bitmap; with identity ids that is `stored` too.
+__global__ __launch_bounds__(256) void k_filter_popcount(const ResumeSlot *__restrict__ slots, uint64_t words,
+                                                         unsigned long long *__restrict__ counters) {
+    __shared__ unsigned long long s_part[4];
+    const uint4 *bits = reinterpret_cast<const uint4 *>(slots[blockIdx.y].bits);
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    unsigned long long set = 0;
+    for (uint64_t quad = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; quad < words / 4; quad += stride) {
+        const uint4 r = bits[quad];
+        set += (uint32_t)(__popc(r.x) + __popc(r.y) + __popc(r.z) + __popc(r.w));
+    }
+    block_add_u64(set, &counters[RC_TOTALS + RC_PER_FILTER * blockIdx.y + RC_LISTED], s_part);
+}
+// ... and `stored` on sparse ids: k_filter_stored_rows with a filter per blockIdx.y
+__global__ __launch_bounds__(256) void k_filter_stored_rows_batch(const ResumeSlot *__restrict__ slots, const uint32_t *__restrict__ ids,
+                                                                  uint64_t n, unsigned long long *__restrict__ counters) {
+    __shared__ unsigned long long s_part[4];
+    const uint32_t *bits = slots[blockIdx.y].bits;
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    unsigned long long c = 0;
+    for (uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; g < n; g += stride) {
+        const uint32_t id = ids[g];
+        c += (bits[id >> 5] >> (id & 31)) & 1u;
+    }
+    block_add_u64(c, &counters[RC_TOTALS + RC_PER_FILTER * blockIdx.y + RC_STORED], s_part);
+}
+
+// 4. the per-node counts of up to AH_FILTER_RESUME_GROUP filters of one length in ONE pass over the Descendants ids.  The
+// table travels in the kernel arguments and is indexed by unrolled constants only: the pointers are scalar loads.
+struct ResumeGroup {
+    uint32_t *block[AH_FILTER_RESUME_GROUP];  // FilterBlock: [bitmap: `words` words][the per-node counts]
+};
+// A gather of one word per id and filter is what a count pass costs (measured: DESIGN.md 4 "Filters across index maintenance"),
+// and word w of 16 filters lies in 16 different cache lines.  So a group's bitmaps are first written side by side, word w of
+// filter f at mixed[16 w + f]: the 16 words an id needs are then ONE 64-byte line.  One thread per word index, the 16 reads
+// coalesced over the threads.  A short group is filled up with copies of its first filter (the host: ah_filter_resume_batch).
+__global__ __launch_bounds__(256) void k_filter_interleave(ResumeGroup t, uint64_t used_words, uint4 *__restrict__ mixed) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; w < used_words; w += stride) {
+#pragma unroll
+        for (int q = 0; q < AH_FILTER_RESUME_GROUP / 4; q++)
+            mixed[4 * w + q] = make_uint4(t.block[4 * q][w], t.block[4 * q + 1][w], t.block[4 * q + 2][w], t.block[4 * q + 3][w]);
+    }
+}
+// One octet per node slot and 32 ids a step, as k_leaf_kept (copy_filtered): every id is loaded once and tested against the GN
+// bitmaps into GN per-lane counters, summed over the octet at the end of the leaf.  The count of node slot `node` under filter f
+// goes behind f's bitmap and is what k_leaf_kept writes: 0 for a free slot, a split node or an empty leaf.
+//   <1, false>                       the bitmap of filter 0 itself: a pass per filter (AH_FILTER_RESUME_GROUP = 1, or bitmaps
+//                                    too long to lay side by side)
+//   <AH_FILTER_RESUME_GROUP, true>   `mixed` (k_filter_interleave): four 16-byte loads per id serve the whole group
+// GN is a compile-time constant: the counters stay in registers.  Copies of a filter in the table have their counts written
+// more than once, by the same lane.  count_leaves: this pass also counts the leaves (the first pass of a call); the ids are
+// counted by every pass.
+template <int GN, bool MIXED>
+__global__ __launch_bounds__(256) void k_leaf_kept_group(const DNode *__restrict__ nodes, const uint32_t *__restrict__ desc,
+                                                         uint32_t n_nodes, uint64_t len_bits, uint64_t words, ResumeGroup t,
+                                                         const uint4 *__restrict__ mixed, int count_leaves,
+                                                         unsigned long long *__restrict__ counters) {
+    __shared__ unsigned long long s_part[4];
+    static_assert(MIXED ? GN == AH_FILTER_RESUME_GROUP : GN == 1, "see above");
+    const uint32_t j = threadIdx.x & 7u;
+    const uint32_t octets = (gridDim.x * blockDim.x) >> 3;
+    uint32_t leaves = 0;  // (counted by lane 0 of the octet)
+    unsigned long long ids_walked = 0;
+    for (uint32_t node = (blockIdx.x * blockDim.x + threadIdx.x) >> 3; node < n_nodes; node += octets) {
+        const DNode nd = nodes[node];
+        const uint32_t c = (nd.kind & 0xFFu) == AH_NODE_DESCENDANTS ? nd.b : 0u;
+        const uint32_t *ids = desc + nd.a;
+        uint32_t cnt[GN];
+#pragma unroll
+        for (int f = 0; f < GN; f++) cnt[f] = 0;
+        for (uint32_t base = 0; base < c; base += 32) {
+            uint32_t word[4], shift[4];
+            bool in[4];
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                const uint32_t i = base + 8 * u + j;
+                const uint32_t id = i < c ? ids[i] : 0u;
+                in[u] = i < c && id < len_bits;
+                word[u] = in[u] ? id >> 5 : 0u;  // (a lane past the leaf or the bitmap reads word 0 and counts nothing)
+                shift[u] = id & 31u;
+            }
+            if (MIXED) {
+#pragma unroll
+                for (int u = 0; u < 4; u++) {
+#pragma unroll
+                    for (int q = 0; q < GN / 4; q++) {
+                        const uint4 x = mixed[4 * (uint64_t)word[u] + q];
+                        cnt[4 * q] += in[u] ? (x.x >> shift[u]) & 1u : 0u;
+                        cnt[4 * q + 1] += in[u] ? (x.y >> shift[u]) & 1u : 0u;
+                        cnt[4 * q + 2] += in[u] ? (x.z >> shift[u]) & 1u : 0u;
+                        cnt[4 * q + 3] += in[u] ? (x.w >> shift[u]) & 1u : 0u;
+                    }
+                }
+            } else {
+#pragma unroll
+                for (int u = 0; u < 4; u++) cnt[0] += in[u] ? (t.block[0][word[u]] >> shift[u]) & 1u : 0u;
+            }
+        }
+#pragma unroll
+        for (int f = 0; f < GN; f++) {
+            uint32_t v = cnt[f];
+            v += __shfl_xor(v, 1, 8);
+            v += __shfl_xor(v, 2, 8);
+            v += __shfl_xor(v, 4, 8);
+            if (j == 0) t.block[f][words + node] = v;
+        }
+        if (j == 0) {
+            leaves += c != 0;
+            ids_walked += c;
+        }
+    }
+    if (count_leaves) block_add_u64(leaves, &counters[RC_LEAVES], s_part);
+    block_add_u64(ids_walked, &counters[RC_IDS_WALKED], s_part);
+}
+
 // normal records [vector (row_bytes)][header (16)] -> row matrix + header array of the normals view
 // Only the `valid_words32` words of the stored vector (ah_vector_size bytes) are read from the record: caller views are
 // compact ([header][vector], stride hs + vs), so the device pitch beyond them is zero-filled, never copied.
@@ -3848,6 +4017,9 @@ struct ah_filter {
     ah_index *ix = nullptr;
     uint32_t *d_bits = nullptr, *d_leaf_kept = nullptr;
     uint64_t len_bits = 0, listed = 0, stored = 0, device_bytes = 0;
+    // ah_filter_suspend: counted in ix->filters_suspended instead of filters_alive.  It keeps its block; only d_bits / len_bits
+    // still mean something (d_leaf_kept is of the node array as it was), and only ah_filter_resume_batch reads them
+    bool suspended = false;
 };
 
 extern "C" {
@@ -3861,6 +4033,8 @@ int ah_index_destroy(ah_index *ix) {
         std::lock_guard<std::mutex> lk(ix->stats_mu);
         AH_REQUIRE(ix->fstats.filters_alive == 0, AH_ERR_INVALID_ARGUMENT, "the index has %llu live filters: ah_filter_destroy them first",
                    (unsigned long long)ix->fstats.filters_alive);
+        AH_REQUIRE(ix->filters_suspended == 0, AH_ERR_INVALID_ARGUMENT, "the index has %llu suspended filters: ah_filter_destroy them first",
+                   (unsigned long long)ix->filters_suspended);
     }
     NoFailScope no_fail;
     if (ix->ds) (void)hipSetDevice(ix->ds->device);
@@ -5002,6 +5176,8 @@ int ah_filter_combine(int op, ah_filter *const *operands, size_t n, ah_filter **
         AH_REQUIRE(operands[i]->ix == ix, AH_ERR_INVALID_ARGUMENT, "operands[%zu] belongs to another index than operands[0]", i);
     AH_REQUIRE(ix && ix->ds, AH_ERR_INVALID_ARGUMENT, "index is NULL");
     AH_INDEX_LIVE(ix);
+    for (size_t i = 0; i < n; i++)
+        AH_REQUIRE(!operands[i]->suspended, AH_ERR_INVALID_ARGUMENT, "operands[%zu] is suspended (ah_filter_suspend): ah_filter_resume_batch it first", i);
     ah_dataset *ds = ix->ds;
     AH_HIP(hipSetDevice(ds->device));
     std::unique_ptr<ah_filter> f(new ah_filter);
@@ -5121,6 +5297,7 @@ int ah_filter_create_bitmap(ah_index *ix, const uint64_t *words, uint64_t n_bits
 int ah_filter_export(const ah_filter *f, uint64_t *out_len_bits, uint32_t *out_bits, uint32_t *out_leaf_kept) {
     AH_GUARDED("ah_filter_export")
     AH_REQUIRE(f && f->ix && f->ix->ds, AH_ERR_INVALID_ARGUMENT, "filter is NULL");
+    AH_REQUIRE(!f->suspended, AH_ERR_INVALID_ARGUMENT, "the filter is suspended (ah_filter_suspend): ah_filter_resume_batch it first");
     if (out_len_bits) *out_len_bits = f->len_bits;
     const ah_index *ix = f->ix;
     AH_HIP(hipSetDevice(ix->ds->device));
@@ -5154,9 +5331,195 @@ int ah_filter_destroy(ah_filter *f) {
     if (f->d_bits) (void)dev_free(f->d_bits);  // (waits for the device: no queued search still reads it)
     if (ix) {
         std::lock_guard<std::mutex> lk(ix->stats_mu);
-        if (ix->fstats.filters_alive) ix->fstats.filters_alive--;
+        uint64_t &level = f->suspended ? ix->filters_suspended : ix->fstats.filters_alive;
+        if (level) level--;
     }
     delete f;
+    return AH_OK;
+    AH_GUARDED_END
+}
+
+// ---- filters across index maintenance (include/arroy_hip.h) ---------------------------------------------------------------
+
+int ah_filter_suspend(ah_filter *f) {
+    AH_GUARDED("ah_filter_suspend")
+    AH_REQUIRE(f && f->ix && f->ix->ds, AH_ERR_INVALID_ARGUMENT, "filter is NULL");
+    AH_REQUIRE(!f->suspended, AH_ERR_INVALID_ARGUMENT, "the filter is suspended already");
+    ah_index *ix = f->ix;
+    AH_INDEX_LIVE(ix);
+    {
+        // no queued search reads the per-node counts any more (ah_index_suspend, for the rows)
+        DeviceRestore restore_device;
+        AH_HIP(hipSetDevice(ix->ds->device));
+        AH_HIP(hipDeviceSynchronize());
+    }
+    std::lock_guard<std::mutex> lk(ix->stats_mu);
+    f->suspended = true;
+    if (ix->fstats.filters_alive) ix->fstats.filters_alive--;
+    ix->filters_suspended++;
+    return AH_OK;
+    AH_GUARDED_END
+}
+
+int ah_index_filters_suspended(ah_index *ix, uint64_t *out) {
+    AH_GUARDED("ah_index_filters_suspended")
+    AH_REQUIRE(ix && out, AH_ERR_INVALID_ARGUMENT, "NULL argument");
+    std::lock_guard<std::mutex> lk(ix->stats_mu);
+    *out = ix->filters_suspended;
+    return AH_OK;
+    AH_GUARDED_END
+}
+
+// Suspended filters back on their index as it is now (include/arroy_hip.h).  Everything is queued on the calling thread's leased
+// context — re-cut, clears, sets, `listed` / `stored`, then one k_leaf_kept_group per group — with one synchronisation at the
+// end; the filters change hands only after it, where nothing can fail any more.
+int ah_filter_resume_batch(ah_filter *const *filters, const ah_filter_edit *edits, size_t n, ah_filter_resume_stats *out_stats) {
+    AH_GUARDED("ah_filter_resume_batch")
+    if (out_stats) *out_stats = ah_filter_resume_stats{};
+    if (n == 0) return AH_OK;
+    // (what can be judged without a filter first)
+    AH_REQUIRE(filters, AH_ERR_INVALID_ARGUMENT, "filters is NULL");
+    AH_REQUIRE(n < 0xFFFFFFFFull, AH_ERR_INVALID_ARGUMENT, "too many filters");
+    uint64_t n_edit_ids = 0;
+    if (edits)
+        for (size_t i = 0; i < n; i++) {
+            const ah_filter_edit &e = edits[i];
+            AH_REQUIRE(e.n_remove == 0 || e.remove_sorted, AH_ERR_INVALID_ARGUMENT, "edits[%zu].remove_sorted is NULL", i);
+            AH_REQUIRE(e.n_add == 0 || e.add_sorted, AH_ERR_INVALID_ARGUMENT, "edits[%zu].add_sorted is NULL", i);
+            for (size_t k = 1; k < e.n_remove; k++)
+                AH_REQUIRE(e.remove_sorted[k - 1] < e.remove_sorted[k], AH_ERR_INVALID_ARGUMENT,
+                           "edits[%zu].remove_sorted is not strictly ascending at position %zu (%u after %u)", i, k, e.remove_sorted[k],
+                           e.remove_sorted[k - 1]);
+            for (size_t k = 1; k < e.n_add; k++)
+                AH_REQUIRE(e.add_sorted[k - 1] < e.add_sorted[k], AH_ERR_INVALID_ARGUMENT,
+                           "edits[%zu].add_sorted is not strictly ascending at position %zu (%u after %u)", i, k, e.add_sorted[k],
+                           e.add_sorted[k - 1]);
+            n_edit_ids += (uint64_t)e.n_remove + e.n_add;
+        }
+    for (size_t i = 0; i < n; i++) AH_REQUIRE(filters[i], AH_ERR_INVALID_ARGUMENT, "filters[%zu] is NULL", i);
+    ah_index *ix = filters[0]->ix;
+    for (size_t i = 1; i < n; i++)
+        AH_REQUIRE(filters[i]->ix == ix, AH_ERR_INVALID_ARGUMENT, "filters[%zu] belongs to another index than filters[0]", i);
+    AH_REQUIRE(ix && ix->ds, AH_ERR_INVALID_ARGUMENT, "index is NULL");
+    AH_INDEX_LIVE(ix);
+    for (size_t i = 0; i < n; i++)
+        AH_REQUIRE(filters[i]->suspended, AH_ERR_INVALID_ARGUMENT, "filters[%zu] is not suspended (ah_filter_suspend)", i);
+    {
+        std::vector<std::pair<const ah_filter *, size_t>> seen(n);
+        for (size_t i = 0; i < n; i++) seen[i] = {filters[i], i};
+        std::sort(seen.begin(), seen.end());
+        for (size_t i = 1; i < n; i++)
+            AH_REQUIRE(seen[i].first != seen[i - 1].first, AH_ERR_INVALID_ARGUMENT, "filters[%zu] names the same filter as filters[%zu]",
+                       seen[i].second, seen[i - 1].second);
+    }
+    ah_dataset *ds = ix->ds;
+    AH_HIP(hipSetDevice(ds->device));
+    const FilterBlock fb(ix, filter_len_bits(ds));
+    const uint32_t n_nodes = ix->n_nodes;
+    // A group's bitmaps side by side (k_filter_interleave) take 64 bytes per bitmap word: where that passes the budget (256 MiB: ids
+    // beyond 2^27) the counts are made a filter a pass, as ah_filter_create makes them
+    const uint64_t used_words = (fb.len_bits + 31) / 32;
+    const size_t mixed_bytes = std::max<size_t>(1, (size_t)used_words) * AH_FILTER_RESUME_GROUP * 4;
+    size_t group = (size_t)std::min<long long>(AH_FILTER_RESUME_GROUP, std::max<long long>(1, tun(TUN_FILTER_RESUME_GROUP)));
+    if (mixed_bytes > ((size_t)std::max<long long>(0, tun(TUN_FILTER_RESUME_MIXED_MB)) << 20)) group = 1;
+    const size_t n_groups = (n + group - 1) / group;
+    // the call's one upload: [counters][slots][the edit ids, list after list]
+    const size_t counters_bytes = (RC_TOTALS + RC_PER_FILTER * n) * 8, slots_bytes = n * sizeof(ResumeSlot);
+    std::vector<unsigned long long> h((RC_TOTALS + RC_PER_FILTER * n));
+    std::vector<uint8_t> up(slots_bytes + (size_t)n_edit_ids * 4);
+    std::vector<DevMem> blocks(n);
+    DevMem work, mixed;
+    for (size_t i = 0; i < n; i++) AH_HIP(dev_malloc(&blocks[i].p, fb.bytes));
+    if (group > 1 && n_nodes) AH_HIP(dev_malloc(&mixed.p, mixed_bytes));
+    AH_HIP(dev_malloc(&work.p, counters_bytes + up.size()));
+    unsigned long long *d_counters = work.as<unsigned long long>();
+    const ResumeSlot *d_slots = reinterpret_cast<const ResumeSlot *>(work.as<uint8_t>() + counters_bytes);
+    const uint32_t *d_edit_ids = reinterpret_cast<const uint32_t *>(work.as<uint8_t>() + counters_bytes + slots_bytes);
+    {
+        ResumeSlot *slots = reinterpret_cast<ResumeSlot *>(up.data());
+        uint32_t *ids = reinterpret_cast<uint32_t *>(up.data() + slots_bytes);
+        uint64_t at = 0;
+        for (size_t i = 0; i < n; i++) {
+            const ah_filter_edit e = edits ? edits[i] : ah_filter_edit{nullptr, 0, nullptr, 0};
+            slots[i] = ResumeSlot{filters[i]->d_bits, filters[i]->len_bits, blocks[i].as<uint32_t>(), at, e.n_remove, at + e.n_remove, e.n_add};
+            if (e.n_remove) memcpy(ids + at, e.remove_sorted, e.n_remove * 4);
+            if (e.n_add) memcpy(ids + at + e.n_remove, e.add_sorted, e.n_add * 4);
+            at += (uint64_t)e.n_remove + e.n_add;
+        }
+    }
+    ContextLease lease(ds);
+    AH_REQUIRE(lease.c, AH_ERR_DEVICE, "cannot create a HIP stream");
+    hipStream_t s = lease.c->stream;
+    AH_HIP(hipMemsetAsync(d_counters, 0, counters_bytes, s));
+    AH_HIP(hipMemcpyAsync(work.as<uint8_t>() + counters_bytes, up.data(), up.size(), hipMemcpyHostToDevice, s));
+    const bool count_rows = !ds->identity_ids && ds->n;  // identity ids: every set bit is a row
+    size_t max_remove = 0, max_add = 0;
+    if (edits)
+        for (size_t i = 0; i < n; i++) {
+            max_remove = std::max(max_remove, edits[i].n_remove);
+            max_add = std::max(max_add, edits[i].n_add);
+        }
+    // blockIdx.y names the filter: at most 65 535 of them a launch, every launch on its own part of the slots and counters
+    for (size_t y0 = 0; y0 < n; y0 += 65535) {
+        const uint32_t ny = (uint32_t)std::min<size_t>(n - y0, 65535);
+        unsigned long long *per_filter = d_counters + RC_PER_FILTER * y0;  // (the kernels add RC_TOTALS themselves)
+        hipLaunchKernelGGL(k_filter_recut, dim3(grid_of(fb.bytes / 4, 1024, 512), ny), dim3(256), 0, s, d_slots + y0, fb.len_bits,
+                           (uint64_t)fb.words, (uint64_t)(fb.bytes / 4));
+        if (max_remove)
+            hipLaunchKernelGGL(k_filter_edit<false>, dim3(grid_of(max_remove, 256, 256), ny), dim3(256), 0, s, d_slots + y0, d_edit_ids,
+                               fb.len_bits, d_counters);
+        if (max_add)
+            hipLaunchKernelGGL(k_filter_edit<true>, dim3(grid_of(max_add, 256, 256), ny), dim3(256), 0, s, d_slots + y0, d_edit_ids, fb.len_bits,
+                               d_counters);
+        if (fb.words)
+            hipLaunchKernelGGL(k_filter_popcount, dim3(grid_of(fb.words / 4, 256, 256), ny), dim3(256), 0, s, d_slots + y0, (uint64_t)fb.words,
+                               per_filter);
+        if (count_rows)
+            hipLaunchKernelGGL(k_filter_stored_rows_batch, dim3(grid_of(ds->n, 256, 256), ny), dim3(256), 0, s, d_slots + y0, ds->view().ids,
+                               (uint64_t)ds->n, per_filter);
+    }
+    if (n_nodes)
+        for (size_t g0 = 0; g0 < n; g0 += group) {
+            const size_t g = std::min(group, n - g0);
+            ResumeGroup t{};
+            for (size_t f = 0; f < AH_FILTER_RESUME_GROUP; f++) t.block[f] = blocks[g0 + (f < g ? f : 0)].as<uint32_t>();
+            const dim3 grid(grid_of(n_nodes, 32, 2048));
+            if (group == 1) {
+                hipLaunchKernelGGL((k_leaf_kept_group<1, false>), grid, dim3(256), 0, s, ix->d_nodes, ix->d_desc, n_nodes, fb.len_bits,
+                                   (uint64_t)fb.words, t, (const uint4 *)nullptr, g0 == 0 ? 1 : 0, d_counters);
+                continue;
+            }
+            // (one stream: the pass before has read `mixed` before this group's words are written over it)
+            if (used_words)
+                hipLaunchKernelGGL(k_filter_interleave, dim3(grid_of(used_words, 256, 2048)), dim3(256), 0, s, t, used_words, mixed.as<uint4>());
+            hipLaunchKernelGGL((k_leaf_kept_group<AH_FILTER_RESUME_GROUP, true>), grid, dim3(256), 0, s, ix->d_nodes, ix->d_desc, n_nodes,
+                               fb.len_bits, (uint64_t)fb.words, t, mixed.as<const uint4>(), g0 == 0 ? 1 : 0, d_counters);
+        }
+    AH_HIP(hipGetLastError());
+    AH_HIP(hipMemcpyAsync(h.data(), d_counters, counters_bytes, hipMemcpyDeviceToHost, s));
+    AH_HIP(hipStreamSynchronize(s));
+    // the hand-over: nothing below can fail
+    NoFailScope no_fail;
+    for (size_t i = 0; i < n; i++) {
+        ah_filter *f = filters[i];
+        (void)dev_free(f->d_bits);  // (the old block; no kernel reads it any more)
+        f->len_bits = fb.len_bits;
+        f->listed = h[RC_TOTALS + RC_PER_FILTER * i + RC_LISTED];
+        f->stored = count_rows ? h[RC_TOTALS + RC_PER_FILTER * i + RC_STORED] : f->listed;
+        f->d_bits = blocks[i].as<uint32_t>();
+        f->d_leaf_kept = f->d_bits + fb.words;
+        f->device_bytes = dev_block_bytes(blocks[i].p);
+        f->suspended = false;
+        blocks[i].p = nullptr;
+    }
+    {
+        std::lock_guard<std::mutex> lk(ix->stats_mu);
+        ix->filters_suspended -= std::min<uint64_t>(ix->filters_suspended, n);
+        ix->fstats.filters_alive += n;
+        ix->fstats.leaf_kept_passes += n_nodes ? n_groups : 0;
+    }
+    if (out_stats)
+        *out_stats = ah_filter_resume_stats{n, n_groups, (uint64_t)fb.words * n, h[RC_REMOVED], h[RC_ADDED], h[RC_LEAVES], h[RC_IDS_WALKED]};
     return AH_OK;
     AH_GUARDED_END
 }
@@ -5201,6 +5564,7 @@ int ah_search_batch_filters(ah_index *ix, const float *queries, const uint32_t *
     for (size_t i = 0; i < n_filters; i++) {
         AH_REQUIRE(filters[i], AH_ERR_INVALID_ARGUMENT, "filters[%zu] is NULL", i);
         AH_REQUIRE(filters[i]->ix == ix, AH_ERR_INVALID_ARGUMENT, "filters[%zu] belongs to another index", i);
+        AH_REQUIRE(!filters[i]->suspended, AH_ERR_INVALID_ARGUMENT, "filters[%zu] is suspended (ah_filter_suspend): ah_filter_resume_batch it first", i);
     }
     ah_dataset *ds = ix->ds;
     if (nq == 0) return AH_OK;

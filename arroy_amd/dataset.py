@@ -584,6 +584,46 @@ class Index:
         f = Filter._adopt(self, h)
         return (f, {k: int(getattr(st, k)) for k, _ in _lib.AhFilterCombineStats._fields_}) if want_stats else f
 
+    def resume_filters(self, filters, edits=None, want_stats: bool = False, edits_sorted: bool = False):
+        """ah_filter_resume_batch: suspended filters of this index (Filter.suspend) back on the index as it is now, after any
+        number of maintenance calls and dataset updates.  `edits`: per filter None or (remove_ids, add_ids), either of them None
+        or any iterable of ids — what the host's update did to that filter's set.  Filter i becomes the filter make_filter gives
+        now for ((old set - remove) | add) cut at the largest stored id; the per-node counts of up to FILTER_RESUME_GROUP filters
+        are made in one pass over the ids of the forest.  All or nothing.  edits_sorted: every list is already an ascending
+        array of distinct ids.  want_stats: ah_filter_resume_stats as a dict."""
+        filters = list(filters)
+        n = len(filters)
+        if edits is not None and len(edits) != n:
+            raise ValueError(f"{len(edits)} edits for {n} filters")
+        for f in filters:
+            if f.index is not self:
+                raise ValueError("a filter of another index")
+        handles = (C.c_void_p * max(1, n))(*[f._handle() for f in filters])
+        keep, arr = [], None
+        if edits is not None:
+            arr = (_lib.AhFilterEdit * max(1, n))()
+            for i, e in enumerate(edits):
+                for k, ids in enumerate(e if e is not None else ()):
+                    if ids is None:
+                        continue
+                    a = _u32(ids).ravel() if edits_sorted else _u32(sorted(set(int(c) for c in ids)))
+                    keep.append(a)
+                    if a.size:
+                        setattr(arr[i], ("remove_sorted", "add_sorted")[k], a.ctypes.data)
+                        setattr(arr[i], ("n_remove", "n_add")[k], a.size)
+        st = _lib.AhFilterResumeStats()
+        _lib.check(_lib.lib().ah_filter_resume_batch(handles, arr, n, C.byref(st)))
+        for f in filters:
+            f._suspended = False
+        if want_stats:
+            return {k: int(getattr(st, k)) for k, _ in _lib.AhFilterResumeStats._fields_}
+
+    def filters_suspended(self) -> int:
+        """ah_index_filters_suspended: the suspended filters of this index (a level, like filter_stats()["filters_alive"])."""
+        out = C.c_uint64()
+        _lib.check(_lib.lib().ah_index_filters_suspended(self._h, C.byref(out)))
+        return int(out.value)
+
     def search(self, count: int, queries=None, items=None, search_k: int = 0, oversampling: int = 0, candidates=None,
                raw: bool = False, candidates_sorted: bool = False, filters=None, filter_of_query=None):
         """Batch of `QueryBuilder::by_vector` (queries: nq x dims) or `by_item` (items: nq ids).
@@ -775,12 +815,18 @@ class Index:
         stats = {f: int(getattr(st, f)) for f, _ in _lib.AhIndexCompactStats._fields_ if f != "reserved"}
         return (stats, out) if want_map else stats
 
-    def suspend(self) -> None:
+    def suspend(self, keep_filters: bool = False) -> None:
         """ah_index_suspend: give up the hold on the dataset, so that Dataset.update_vectors goes through; until resume()
         every search, route, filter or delete call on this index is refused.  The live filters of the index are closed first,
-        as close() does (ah_index_suspend refuses while one is alive)."""
+        as close() does (ah_index_suspend refuses while one is alive), or with keep_filters suspended (Filter.suspend), for
+        resume_filters once the index is resumed and maintained.  Filters that are suspended already are left alone."""
         for f in list(self._filters):
-            f.close()
+            if f.suspended:
+                continue
+            if keep_filters:
+                f.suspend()
+            else:
+                f.close()
         _lib.check(_lib.lib().ah_index_suspend(self._h))
 
     def resume(self, dataset: Optional[Dataset] = None) -> None:
@@ -852,6 +898,7 @@ class Filter:
         self.index = index
         self._h = C.c_void_p()
         arr = _u32(ids) if sorted_ids else _u32(sorted(set(int(c) for c in ids)))
+        self._suspended = False
         _lib.check(_lib.lib().ah_filter_create(index._h, _ptr(arr), arr.size, C.byref(self._h)))
         index._filters.add(self)
 
@@ -859,9 +906,20 @@ class Filter:
     def _adopt(cls, index: Index, handle: C.c_void_p) -> "Filter":
         """A Filter around an ah_filter handle the library has just made (Index.combine_filters, Index.make_filter_bitmap)."""
         self = cls.__new__(cls)
-        self.index, self._h = index, handle
+        self.index, self._h, self._suspended = index, handle, False
         index._filters.add(self)
         return self
+
+    def suspend(self) -> None:
+        """ah_filter_suspend: the filter keeps its bitmap and stops counting as alive, so that the maintenance calls of its index
+        (delete_items, insert_items, graft, drop_trees, compact) and Index.suspend go through; until Index.resume_filters it is
+        refused by search, the expressions, export and suspend.  info() and close() stay legal."""
+        _lib.check(_lib.lib().ah_filter_suspend(self._handle()))
+        self._suspended = True
+
+    @property
+    def suspended(self) -> bool:
+        return bool(self._h) and self._suspended
 
     def _handle(self):
         if not self._h:

@@ -390,6 +390,10 @@ class ArroyBuilder:
         # (test_writer_keeps_the_index_and_builds_the_same_trees) pins the fall-back counts of a tree-dropping build, so the
         # default can only flip in a change that may touch that test
         self.device_drop = False
+        # True: a build that keeps its resident index suspends the index's live filters (Filter.suspend) instead of closing
+        # them, and leaves them suspended for the caller to resume with its delta (Index.resume_filters); the compaction at
+        # the end of the build is then no longer skipped on their account
+        self.keep_filters = False
 
     def n_trees(self, n: int) -> "ArroyBuilder":
         self._n_trees = int(n)
@@ -435,7 +439,7 @@ class ArroyBuilder:
         try:  # (whatever happens in between, the kept index does not linger suspended with its normals in HBM)
             if resident is not None:
                 if keep:
-                    resident.suspend()
+                    resident.suspend(keep_filters=self.keep_filters)
                 else:
                     resident.close()  # (an update of the dataset refuses while an index holds it)
                     resident = None

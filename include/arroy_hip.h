@@ -708,6 +708,48 @@ typedef struct ah_filter_stats {
 } ah_filter_stats;
 AH_API int ah_index_filter_stats(ah_index *index, ah_filter_stats *out, int reset);
 
+/* Filters across index maintenance (ABI v7 addition: look the symbols up).  A live filter blocks ah_index_delete_items /
+ * _insert_items / _graft / _drop_trees / _compact and ah_index_suspend, because its per-node counts would go stale.  What
+ * does not go stale is its bitmap, apart from the ids the host's update touched.  ah_filter_suspend keeps the filter and
+ * takes it out of filters_alive: it no longer blocks anything, and every call that would read it (ah_search_batch_filters,
+ * ah_filter_combine, ah_filter_export, a second ah_filter_suspend) refuses it by name (AH_ERR_INVALID_ARGUMENT, "suspended").
+ * It waits until no queued search reads the filter.  ah_filter_info (the old listed / stored; device_bytes: the block it
+ * still holds) and ah_filter_destroy stay legal; ah_index_destroy refuses while a suspended filter exists.  Legal on a live
+ * index only.
+ *
+ * ah_filter_resume_batch brings n suspended filters of ONE index back on that index as it is now (not suspended).  Filter i
+ * becomes, bit for bit, the filter ah_filter_create makes now from the ascending list of
+ *     ((old set \ edits[i].remove) | edits[i].add) & [0, largest stored id now]
+ * — the same length, bitmap words (zero up to the 64-word multiple), per-node counts for every node slot of the current node
+ * array, and `stored`; `listed` is the number of set bits, as for a combined filter.  An id in both lists ends up set; ids
+ * that are not stored, or above the largest stored id, are legal in both lists.  The per-node counts of up to
+ * AH_FILTER_RESUME_GROUP filters are made in ONE pass over the Descendants ids (ah_filter_create: one pass per filter); for
+ * its duration the call holds a copy of one group's bitmaps laid side by side (64 bytes per 32 ids of the id range).  Where
+ * that copy would pass 256 MiB (ids beyond 2^27) the counts are made a filter a pass, and `groups` is `filters`.
+ * All or nothing: on any failure every filter is still suspended with its old bitmap, no counter has moved, nothing is held.
+ * filters_created does not move, filters_alive rises by n, leaf_kept_passes by `groups` (an index with nodes).  May run next
+ * to searches under other filters; not concurrent with maintenance of the same index.  n == 0 is AH_OK.  Refused
+ * (AH_ERR_INVALID_ARGUMENT, the offending position named): filters NULL, an edit list that is NULL with a length or not
+ * strictly ascending, a NULL filter, a filter of another index than filters[0]'s, a suspended index, a filter that is not
+ * suspended, a filter named twice. */
+#define AH_FILTER_RESUME_GROUP 16   /* filters whose per-node counts one pass over the Descendants ids serves */
+typedef struct ah_filter_edit {      /* the host's delta of one filter; either list may be NULL with n == 0 */
+    const uint32_t *remove_sorted; size_t n_remove;   /* strictly ascending */
+    const uint32_t *add_sorted;    size_t n_add;      /* strictly ascending */
+} ah_filter_edit;
+typedef struct ah_filter_resume_stats {
+    uint64_t filters, groups;        /* groups = ceil(filters / AH_FILTER_RESUME_GROUP) = passes over the Descendants ids */
+                                     /* (`filters` where the id range is too long for grouped passes: above)             */
+    uint64_t words;                  /* 32-bit bitmap words written, all filters                                        */
+    uint64_t ids_removed, ids_added; /* bits the clears cleared, then bits the sets set (an id in both lists that was set: both) */
+    uint64_t leaves, ids_walked;     /* Descendants nodes with >= 1 id; their ids, counted once per group                */
+} ah_filter_resume_stats;
+AH_API int ah_filter_suspend(ah_filter *f);
+AH_API int ah_filter_resume_batch(ah_filter *const *filters, const ah_filter_edit *edits /* NULL = no edits */, size_t n,
+                                  ah_filter_resume_stats *out_stats /* may be NULL */);
+/* Suspended filters of the index: a level, like filters_alive. */
+AH_API int ah_index_filters_suspended(ah_index *index, uint64_t *out);
+
 /* Incremental insert routing, `insert_items_in_descendants_from_frozen_reader` (src/writer.rs:1398-1459), for
  * every tree of the index at once: each of the `n` items (they must already be rows of the index's dataset — the
  * reference also re-creates `ImmutableLeafs` over all current items for every build, src/writer.rs:530) walks from
