@@ -167,6 +167,15 @@ class AhFilterStats(C.Structure):
         "leaf_kept_passes")]
 
 
+class AhQueryParams(C.Structure):  # ah_query_params: one per query of ah_search_batch_params (16 bytes)
+    _fields_ = [("search_k", C.c_uint64), ("count", C.c_uint32), ("oversampling", C.c_uint32)]
+
+
+class AhParamsStats(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in (
+        "calls", "batches", "varied_batches", "queries", "varied_queries", "big_count_queries")]
+
+
 NO_FILTER = 0xFFFFFFFF  # AH_NO_FILTER: a query of ah_search_batch_filters under no filter
 
 
@@ -273,6 +282,10 @@ SIGNATURES = {
     "ah_search_batch_filters": (C.c_int, [_VP, _F32P, _U32P, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t,
                                           C.POINTER(C.c_void_p), C.c_size_t, _U32P, _U32P, _F32P, _U32P]),
     "ah_index_filter_stats": (C.c_int, [_VP, C.POINTER(AhFilterStats), C.c_int]),
+    # per-query count, search_k and oversampling in a batched call
+    "ah_search_batch_params": (C.c_int, [_VP, _F32P, _U32P, C.c_size_t, C.POINTER(AhQueryParams), C.c_size_t,
+                                         C.POINTER(C.c_void_p), C.c_size_t, _U32P, _U32P, _F32P, _U32P]),
+    "ah_index_params_stats": (C.c_int, [_VP, C.POINTER(AhParamsStats), C.c_int]),
     # filter expressions on the device, filters from bitmaps
     "ah_filter_combine": (C.c_int, [C.c_int, C.POINTER(C.c_void_p), C.c_size_t, C.POINTER(C.c_void_p),
                                     C.POINTER(AhFilterCombineStats)]),

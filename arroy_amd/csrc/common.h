@@ -180,6 +180,7 @@ inline int guarded(const char *what, F &&f) noexcept {
     X(RERANK_TIMING, "AH_RERANK_TIMING", 0)     /* 1: ah_rerank_batch accounts its wall time by phase (ah_dataset_rerank_stats) */ \
     X(SEARCH_SCREEN, "AH_SEARCH_SCREEN", 1)     /* 0: the re-rank of ah_search_batch never screens its candidates (f32 rows for all) */ \
     X(SEARCH_FILTER_GROUP_MIN, "AH_SEARCH_FILTER_GROUP_MIN", 16) /* ah_search_batch_filters: the queries of one filter form a sub-batch of their own from this many on; fewer share a mixed sub-batch */ \
+    X(SEARCH_PARAMS_SORT, "AH_SEARCH_PARAMS_SORT", 1) /* ah_search_batch_params: inside a run of one filter the queries are ordered by the stride of their candidate buffer, so a sub-batch is sized by its own largest; 0: the caller's order (schedule only: the results are bit-identical; DESIGN.md 4 "Per-query search parameters") */ \
     X(FILTER_COMBINE_SHORTCUT, "AH_FILTER_COMBINE_SHORTCUT", 1) /* 0: ah_filter_combine walks the ids of every leaf against the new bitmap, never derives a leaf's count from the operands' counts (DESIGN.md 4 "Combined filters") */ \
     X(FILTER_RESUME_GROUP, "AH_FILTER_RESUME_GROUP", 16) /* ah_filter_resume_batch: filters one pass over the Descendants ids counts for, 1 .. 16 (the header's AH_FILTER_RESUME_GROUP); 1: a pass per filter, what the measurement compares with (DESIGN.md 4 "Filters across index maintenance") */ \
     X(FILTER_RESUME_MIXED_MB, "AH_FILTER_RESUME_MIXED_MB", 256) /* ah_filter_resume_batch: most MiB for a group's bitmaps laid side by side (64 bytes per 32 ids of the id range); above it the counts are made a filter a pass */ \

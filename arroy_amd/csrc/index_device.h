@@ -81,6 +81,7 @@ struct ah_index {
     std::atomic<bool> search8_off{false};    // ... eight in one window: the index's tile re-rank starts on the binary16 rows from now on
     bool counted = false;                    // counted in ds->live_indexes (an update of the dataset refuses meanwhile)
     bool suspended = false;                  // ah_index_suspend: not counted, and every call that reads the dataset refuses
+    ah_params_stats pstats{};                // under stats_mu: how ah_search_batch_params cut its calls
     ah_filter_stats fstats{};                // under stats_mu; filters_alive is a level (ah_index_destroy refuses above 0)
     // under stats_mu: filters ah_filter_suspend took out of filters_alive (the maintenance calls and ah_index_suspend do not
     // see them; ah_index_destroy refuses above 0, their `ix` would dangle)

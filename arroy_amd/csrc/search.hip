@@ -72,6 +72,11 @@ struct SearchParams {
     // filter into its copy of this struct before it starts (resolve_filter).
     const FilterSlot *filter_table;
     const uint32_t *filter_of_query;
+    // A VARIED sub-batch of ah_search_batch_params (null otherwise): per query of the sub-batch its own search_k (effective, as
+    // above) and its own count.  Every descent resolves its query's search_k into its copy of this struct before it starts
+    // (resolve_params); search_k above is then the sub-batch's largest, which sized nns_stride.  The selections read count_of.
+    const uint32_t *search_k_of;
+    const uint32_t *count_of;
 };
 // The filter of query q of a mixed sub-batch -> sp.filter_bits / filter_len_bits / leaf_kept.  q is uniform over a block
 // (k_descend_wave, k_descend_block: scalar loads) or over an octet (k_descend<.., true>).
@@ -82,6 +87,11 @@ __device__ __forceinline__ void resolve_filter(SearchParams &sp, uint32_t q) {
     sp.filter_bits = f.bits;
     sp.filter_len_bits = f.len_bits;
     sp.leaf_kept = f.leaf_kept;
+}
+
+// The search_k of query q of a varied sub-batch -> sp.search_k.  q is uniform over a block or over an octet, as for resolve_filter.
+__device__ __forceinline__ void resolve_params(SearchParams &sp, uint32_t q) {
+    if (sp.search_k_of) sp.search_k = sp.search_k_of[q];
 }
 
 __device__ __forceinline__ float key_to_dist(uint32_t k) {
@@ -206,6 +216,7 @@ __global__ __launch_bounds__(64) void k_descend(DataView nv, SearchParams sp, co
     const uint32_t q = live ? (query_list ? query_list[slot] : slot) : 0u;
     if (only_flagged && live) live = overflow[q] != 0;  // the queries k_descend_wave left (its capacities, ties)
     if (MIXED && live) resolve_filter(sp, q);  // (copy_filtered keeps to the octet: its comment)
+    if (live) resolve_params(sp, q);           // (octet-uniform: the eight queries of a wave may stop at different search_k)
     uint64_t *heap = HEAP_GLOBAL ? heap_global + (uint64_t)slot * heap_cap : s_heap + o * kHeapLds;
     const uint32_t cap = HEAP_GLOBAL ? heap_cap : kHeapLds;
     const void *qvec = qvecs + (uint64_t)q * qstride;
@@ -323,6 +334,7 @@ __global__ __launch_bounds__(64) void k_descend_wave(DataView nv, SearchParams s
     const uint32_t q = blockIdx.x, o = threadIdx.x >> 3, j = threadIdx.x & 7u, lane = threadIdx.x;
     if (q >= nq) return;
     if (sp.filter_table) resolve_filter(sp, q);  // a mixed sub-batch: this query's own filter (wave-uniform)
+    resolve_params(sp, q);                       // a varied sub-batch: this query's own search_k (wave-uniform)
     uint64_t *heap = s_heap[o];
     // the query leaf in LDS (behind the queues; qstride bytes): every margin of the descent reads it
     uint4 *s_q4 = reinterpret_cast<uint4 *>(reinterpret_cast<uint8_t *>(s_wave_lds) + wave_lds_bytes(kWaveHeap, kWaveLeaves));
@@ -623,6 +635,7 @@ __global__ __launch_bounds__(8 * kOct) void k_descend_block(DataView nv, SearchP
     const uint32_t q = blockIdx.x, tid = threadIdx.x, o = tid >> 3, j = tid & 7u, wave = tid >> 6, wl = tid & 63u;
     if (q >= nq) return;
     if (sp.filter_table) resolve_filter(sp, q);  // a mixed sub-batch: this query's own filter (block-uniform)
+    resolve_params(sp, q);                       // a varied sub-batch: this query's own search_k (block-uniform)
     // block-wide max / sum / or of one value per thread (all threads call; two barriers each)
     auto block_max = [&](uint32_t v) {
         for (uint32_t d = 32; d > 0; d >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, d, 64));
@@ -1084,6 +1097,7 @@ __global__ __launch_bounds__(256) void k_descend_multi(DataView nv, SearchParams
     uint32_t *s_mw = s_red + 64;                             // 32 control words (MultiWord)
     const uint32_t q = blockIdx.x / G, g = blockIdx.x - q * G, tid = threadIdx.x, o = (tid >> 3) & 7u, j = tid & 7u, wave = tid >> 6, wl = tid & 63u;
     if (q >= nq) return;
+    resolve_params(sp, q);  // a varied sub-batch: this query's own search_k (the G blocks of a query agree: q is block-uniform)
     MultiCtl *ctl = ctls + q;
     const uint64_t t_start = trace_on ? wall_clock64() : 0ull;
     auto stamp = [&](uint32_t slot) {  // (AH_SEARCH_MULTI_TRACE; thread 0 of the block; never read by the kernels)
@@ -2854,7 +2868,8 @@ __device__ __forceinline__ void search_select_screened_body(DataView dv, ScreenS
                                                                  uint32_t *__restrict__ out_ids, float *__restrict__ out_dist,
                                                                  uint32_t *err, const PairSeg *__restrict__ segs,
                                                                  uint32_t flag_words, uint32_t id_limit,
-                                                                 uint32_t *__restrict__ unique_out, uint32_t *__restrict__ trace = nullptr) {
+                                                                 uint32_t *__restrict__ unique_out, uint32_t *__restrict__ trace = nullptr,
+                                                                 const uint32_t *__restrict__ count_of = nullptr) {
     const uint64_t t_start = trace ? wall_clock64() : 0ull;
     auto stamp = [&](uint32_t slot) {  // (AH_SEARCH_MULTI_TRACE: where a single query's selection spends its time)
         if (trace && threadIdx.x == 0 && blockIdx.x == 0) trace[slot] = (uint32_t)(wall_clock64() - t_start);
@@ -2873,7 +2888,9 @@ __device__ __forceinline__ void search_select_screened_body(DataView dv, ScreenS
     // candidates of query q: a slot of `stride` entries (ah_search_batch), or a segment of the caller's lists (ah_rerank_batch)
     const uint64_t first = segs ? segs[q].off : (uint64_t)q * stride;
     const uint32_t n = segs ? segs[q].n : counts[q];
-    uint32_t kk = FLAG ? 0u : (segs ? min(k_out, segs[q].k) : min(k_out, unique[q]));
+    // (a varied sub-batch of ah_search_batch_params: the query's own count, block-uniform; rows stay k_out wide, padded)
+    const uint32_t k_q = count_of ? min(k_out, count_of[q]) : k_out;
+    uint32_t kk = FLAG ? 0u : (segs ? min(k_out, segs[q].k) : min(k_q, unique[q]));
     const uint32_t *ids = nns + first;
     const float *sd = dist_all + first;
     uint32_t *s_bits = reinterpret_cast<uint32_t *>(s_qf4 + (dv.pitch >> 2));  // FLAG: one bit per item id
@@ -2963,7 +2980,7 @@ __device__ __forceinline__ void search_select_screened_body(DataView dv, ScreenS
             if ((tid & 63u) == 0 && mine) atomicAdd(&s_bin, mine);
             __syncthreads();
             const uint32_t n_unique = s_bin;
-            kk = min(k_out, n_unique);
+            kk = min(k_q, n_unique);
             if (tid == 0) unique_out[q] = n_unique;
             for (uint32_t t = kk + tid; t < k_out; t += kThreads) {
                 out_ids[(uint64_t)q * k_out + t] = 0xFFFFFFFFu;
@@ -3135,10 +3152,11 @@ __global__ __launch_bounds__(1024) void k_search_select_screened(DataView dv, Sc
                                                                  uint32_t flag_words = 0, uint32_t id_limit = 0,
                                                                  uint32_t *__restrict__ unique_out = nullptr,
                                                                  uint32_t *__restrict__ host_status = nullptr,
-                                                                 uint32_t *__restrict__ trace = nullptr) {
+                                                                 uint32_t *__restrict__ trace = nullptr,
+                                                                 const uint32_t *__restrict__ count_of = nullptr) {
     const uint64_t t_start = trace ? wall_clock64() : 0ull;
     search_select_screened_body<METRIC, FLAG>(dv, ss, nns, dist_all, stride, counts, unique, k_out, qvecs, qstride, qhdrs, out_ids, out_dist,
-                                              err, segs, flag_words, id_limit, unique_out, trace);
+                                              err, segs, flag_words, id_limit, unique_out, trace, count_of);
     if (host_status) {  // (every return of the body is block-uniform)
         // The results went to the caller's pinned buffers: system-scope fences, and word 0 of the status LAST — the host may be
         // polling that word instead of waiting for the stream (AH_SEARCH_SPIN_WAIT), and what it reads after it must be there.
@@ -3257,13 +3275,14 @@ __global__ __launch_bounds__(kSelectThreads) void k_search_select(DataView dv, c
                                                        const uint32_t *__restrict__ counts,
                                                        const uint32_t *__restrict__ unique, uint32_t k_out,
                                                        uint32_t *__restrict__ out_ids, float *__restrict__ out_dist,
-                                                       uint32_t *err) {
+                                                       uint32_t *err, const uint32_t *__restrict__ count_of = nullptr) {
     __shared__ uint32_t s_hist[kSelectBins];
     __shared__ uint64_t s_key[kSelectCap];
     __shared__ uint32_t s_pos[kSelectCap];
     __shared__ uint32_t s_min, s_max, s_wave[kSelectThreads / 64], s_bin, s_count, s_n;
     const uint32_t q = blockIdx.x, tid = threadIdx.x;
-    const uint32_t n = counts[q], kk = min(k_out, unique[q]);
+    // (count_of: the query's own count in a varied sub-batch of ah_search_batch_params; rows stay k_out wide, padded)
+    const uint32_t n = counts[q], kk = min(count_of ? min(k_out, count_of[q]) : k_out, unique[q]);
     const uint32_t *ids = nns + (uint64_t)q * stride;
     const float *dist = dist_all + (uint64_t)q * stride;
     for (uint32_t t = kk + tid; t < k_out; t += kSelectThreads) {
@@ -4166,6 +4185,14 @@ struct MixedFilters {
     size_t n_filtered;
 };
 
+// A varied sub-batch of ah_search_batch_params: the count and the effective search_k of every query of the sub-batch (host).
+// `count`, `search_k` and `nns_stride` of search_chunk are then the sub-batch's largest: they size the scratch and decide the
+// paths; the results are staged in rows of `count`, each padded behind its own query's min(count_q, candidates).
+struct VariedParams {
+    const uint32_t *counts;
+    const uint32_t *search_ks;
+};
+
 // Counters of one sub-batch -> the index's ah_search_stats.
 struct ChunkStats {
     ah_search_stats s{};
@@ -4195,7 +4222,7 @@ static int search_chunk(ah_index *ix, Context *ctx, const float *queries, const 
                         size_t count, uint32_t search_k, uint32_t nns_stride, const uint32_t *d_filter_bits,
                         uint64_t filter_len_bits, double filter_share, bool wave_descent, const uint32_t *d_leaf_kept,
                         uint32_t *out_ids, float *out_dists, uint32_t *out_counts, bool allow8 = true,
-                        const MixedFilters *mixed = nullptr) {
+                        const MixedFilters *mixed = nullptr, const VariedParams *varied = nullptr) {
     ah_dataset *ds = ix->ds;
     // `filtered`: what the host's path choices ask; d_filter_bits stays the one bitmap of a uniform sub-batch (null in a mixed one)
     const bool filtered = d_filter_bits || mixed;
@@ -4213,7 +4240,8 @@ static int search_chunk(ah_index *ix, Context *ctx, const float *queries, const 
     const uint32_t heap_cap = ix->n_nodes + ix->n_trees + 2;
     size_t dev_bytes = pad(nq * (size_t)ds->dims * 4) + pad(nq * 4) + nq * qstride + pad(nq * 8) + pad(nq * (size_t)nns_stride * 4) * 2 +
                        pad(nq * 4) * 3 + pad(nq * sizeof(HostSeg2)) + pad((size_t)max_tiles_bound * sizeof(HostTile2)) +
-                       2 * pad(nq * kstride * 8) + pad(nq * k * 4) * 2 + pad(SS_WORDS * 4) + pad(nq * 4) + 4096 + (mixed ? pad(nq * 4) : 0);
+                       2 * pad(nq * kstride * 8) + pad(nq * k * 4) * 2 + pad(SS_WORDS * 4) + pad(nq * 4) + 4096 + (mixed ? pad(nq * 4) : 0) +
+                       (varied ? 2 * pad(nq * 4) : 0);
     // counters of the row-major re-rank, reserved when the candidate lists could be long enough for it
     const size_t inv_bytes = batch_invert_wanted(ds->view(), (uint64_t)nq * nns_stride) ? batch_invert_counter_bytes(ds->n, (uint64_t)nq * nns_stride) : 0;
     dev_bytes += pad(inv_bytes);
@@ -4258,7 +4286,7 @@ static int search_chunk(ah_index *ix, Context *ctx, const float *queries, const 
     void *const clean_status = ctx->clean_status;  // (ensure_device forgets it: see Context)
     AH_TRY(ctx->ensure_device(dev_bytes));
     const size_t pin_bytes = pad(nq * (size_t)ds->dims * 4) + pad(nq * 4) * 4 + pad(nq * sizeof(HostSeg2)) +
-                             pad((size_t)max_tiles_bound * sizeof(HostTile2)) + pad(nq * k * 4) * 2 + 4096 + (mixed ? pad(nq * 4) : 0);
+                             pad((size_t)max_tiles_bound * sizeof(HostTile2)) + pad(nq * k * 4) * 2 + 4096 + (mixed ? pad(nq * 4) : 0) + (varied ? 2 * pad(nq * 4) : 0);
     AH_TRY(ctx->ensure_pinned(pin_bytes));
     uint8_t *dbase = reinterpret_cast<uint8_t *>(ctx->d_scratch);
     size_t doff = 0;
@@ -4398,6 +4426,17 @@ static int search_chunk(ah_index *ix, Context *ctx, const float *queries, const 
         sp.filter_table = mixed->d_table;
         sp.filter_of_query = d_slots;
     }
+    if (varied) {  // one copy: the two tables lie back to back on both sides
+        uint32_t *d_sks = (uint32_t *)dtake(nq * 4), *d_cnt = (uint32_t *)dtake(nq * 4);
+        uint32_t *h_sks = (uint32_t *)ptake(nq * 4), *h_cnt = (uint32_t *)ptake(nq * 4);
+        memcpy(h_sks, varied->search_ks, nq * 4);
+        memcpy(h_cnt, varied->counts, nq * 4);
+        AH_HIP(hipMemcpyAsync(d_sks, h_sks, pad(nq * 4) + nq * 4, hipMemcpyHostToDevice, s));
+        sp.search_k_of = d_sks;
+        sp.count_of = d_cnt;
+    }
+    // the count of query q of this sub-batch
+    auto count_of = [&](size_t q) -> size_t { return varied ? (size_t)varied->counts[q] : k; };
     // (... and when the block descent is the first kernel to want the leaves, it prepares them itself)
     // (a small submission on the leaf-tile path makes the binary16 copies of its queries in the launch that places its visits)
     const bool small_units = tiles && small_units_fit && (long long)nq <= tun(TUN_SEARCH_SMALL_UNITS_MAX_QUERIES);
@@ -4642,20 +4681,22 @@ static int search_chunk(ah_index *ix, Context *ctx, const float *queries, const 
         if (fused_flag && ds->metric == AH_COSINE)
             hipLaunchKernelGGL((k_search_select_screened<AH_COSINE, true>), dim3((unsigned)nq), dim3(1024), fused_lds, s, dv, ss, d_nns, d_dist,
                                nns_stride, d_counts, d_unique, (uint32_t)k, d_qvecs, qstride, d_qhdrs, h_oi, h_od, d_err, (const PairSeg *)nullptr,
-                               bitmap_words, max_id + 1, h_counts, h_err, sel_trace);
+                               bitmap_words, max_id + 1, h_counts, h_err, sel_trace, sp.count_of);
         else if (fused_flag)
             hipLaunchKernelGGL((k_search_select_screened<AH_DOT_PRODUCT, true>), dim3((unsigned)nq), dim3(1024), fused_lds, s, dv, ss, d_nns,
                                d_dist, nns_stride, d_counts, d_unique, (uint32_t)k, d_qvecs, qstride, d_qhdrs, h_oi, h_od, d_err,
-                               (const PairSeg *)nullptr, bitmap_words, max_id + 1, h_counts, h_err, sel_trace);
+                               (const PairSeg *)nullptr, bitmap_words, max_id + 1, h_counts, h_err, sel_trace, sp.count_of);
         else if (screened && ds->metric == AH_COSINE)
             hipLaunchKernelGGL((k_search_select_screened<AH_COSINE>), dim3((unsigned)nq), dim3(1024), sel_lds, s, dv, ss, d_nns, d_dist,
-                               nns_stride, d_counts, d_unique, (uint32_t)k, d_qvecs, qstride, d_qhdrs, d_oi, d_od, d_err, (const PairSeg *)nullptr);
+                               nns_stride, d_counts, d_unique, (uint32_t)k, d_qvecs, qstride, d_qhdrs, d_oi, d_od, d_err, (const PairSeg *)nullptr, 0u, 0u,
+                               (uint32_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr, sp.count_of);
         else if (screened)
             hipLaunchKernelGGL((k_search_select_screened<AH_DOT_PRODUCT>), dim3((unsigned)nq), dim3(1024), sel_lds, s, dv, ss, d_nns, d_dist,
-                               nns_stride, d_counts, d_unique, (uint32_t)k, d_qvecs, qstride, d_qhdrs, d_oi, d_od, d_err, (const PairSeg *)nullptr);
+                               nns_stride, d_counts, d_unique, (uint32_t)k, d_qvecs, qstride, d_qhdrs, d_oi, d_od, d_err, (const PairSeg *)nullptr, 0u, 0u,
+                               (uint32_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr, sp.count_of);
         else
             hipLaunchKernelGGL(k_search_select, dim3((unsigned)nq), dim3(kSelectThreads), 0, s, dv, d_nns, d_dist, nns_stride, d_counts,
-                               d_unique, (uint32_t)k, d_oi, d_od, d_err);
+                               d_unique, (uint32_t)k, d_oi, d_od, d_err, sp.count_of);
         // a launch the runtime rejected (dynamic LDS beyond the limit, another architecture) would leave *err = 0 over
         // uninitialised results: such a submission takes the sorted path as well
         const hipError_t launch_err = hipGetLastError();
@@ -4705,7 +4746,7 @@ static int search_chunk(ah_index *ix, Context *ctx, const float *queries, const 
         AH_REQUIRE((*h_err & 1u) == 0 || *h_err == 0xFFFFFFFFu, AH_ERR_MISSING_ITEM, "a descendant id does not exist in the dataset");
         if ((*h_err & ~1u) == 0 && launch_err == hipSuccess) {
             if (fused_flag) ctx->clean_status = d_err;  // (its selection kernel ran to its end and wiped the block behind itself)
-            for (size_t q = 0; q < nq; q++) out_counts[q] = (uint32_t)std::min<size_t>(k, h_counts[q]);
+            for (size_t q = 0; q < nq; q++) out_counts[q] = (uint32_t)std::min<size_t>(count_of(q), h_counts[q]);
             memcpy(out_ids, h_oi, nq * k * 4);
             memcpy(out_dists, h_od, nq * k * 4);
             cs.device_words(h_err);
@@ -4725,7 +4766,7 @@ static int search_chunk(ah_index *ix, Context *ctx, const float *queries, const 
                 ix->stats.screen8_retried_chunks += 1;
             }
             return search_chunk(ix, ctx, queries, query_rows, nq, count, search_k, nns_stride, d_filter_bits, filter_len_bits, filter_share,
-                                wave_descent, d_leaf_kept, out_ids, out_dists, out_counts, false);
+                                wave_descent, d_leaf_kept, out_ids, out_dists, out_counts, false, nullptr, varied);
         }
         // a case the tiles do not reproduce (bits 2..5 of *err, see k_search_select / VisitSink): redo it the long way
         cs.s.fallback_chunks = 1;
@@ -4814,7 +4855,7 @@ static int search_chunk(ah_index *ix, Context *ctx, const float *queries, const 
     for (size_t q = 0; q < nq; q++) {
         const uint32_t n = h_counts[q];
         n_candidates += n;
-        h_segs[q] = HostSeg2{(uint64_t)q * nns_stride, n, (uint32_t)std::min<size_t>(k, n)};
+        h_segs[q] = HostSeg2{(uint64_t)q * nns_stride, n, (uint32_t)std::min<size_t>(count_of(q), n)};
         out_counts[q] = h_segs[q].k;
         max_n = std::max(max_n, n);
         if (big_k) continue;
@@ -4903,21 +4944,30 @@ struct SearchShape {
     std::vector<uint32_t> rows;
     size_t chunk = 1;
 };
-static int search_shape(ah_index *ix, const uint32_t *query_items, size_t nq, size_t count, size_t search_k, size_t oversampling,
-                        SearchShape &out) {
-    ah_dataset *ds = ix->ds;
+// The effective search_k of one query and the capacity of its candidate buffer (no refusal here: the callers name the query).
+static void search_extent(const ah_index *ix, size_t count, uint64_t search_k, uint64_t oversampling, uint64_t &sk_eff, uint64_t &stride) {
     // search_k: reader.rs:330-335; nns can never exceed the blob (every Descendants node is popped at most once)
     unsigned __int128 sk = search_k ? (unsigned __int128)search_k : (unsigned __int128)count * ix->n_trees;
-    sk *= oversampling ? oversampling : (metric_is_bq(ds->metric) ? 3u : 1u);
-    const uint64_t sk_eff = (uint64_t)std::min<unsigned __int128>(sk, (unsigned __int128)ix->desc_len);
-    uint64_t stride = std::min<uint64_t>(sk_eff + ix->max_desc, ix->desc_len);
+    sk *= oversampling ? oversampling : (metric_is_bq(ix->ds->metric) ? 3u : 1u);
+    sk_eff = (uint64_t)std::min<unsigned __int128>(sk, (unsigned __int128)ix->desc_len);
+    stride = std::min<uint64_t>(sk_eff + ix->max_desc, ix->desc_len);
     if (stride > kSortLds) {  // the global sort path pads to a power of two
         uint64_t p = 2;
         while (p < stride) p <<= 1;
         stride = p;
     }
-    AH_REQUIRE(stride < 0x7FFFFFFFull, AH_ERR_INVALID_ARGUMENT, "search_k too large");
-    std::vector<uint32_t> &rows = out.rows;
+}
+// Scratch one query of a sub-batch costs at that stride and count (sub-batches are bounded by ~1.5 GiB of it, and 4096 queries)
+static size_t search_query_bytes(const ah_dataset *ds, uint64_t stride, size_t count) {
+    const size_t key_bytes = batch_supported((uint32_t)std::min<size_t>(count, 0xFFFFFFFFu))
+                                 ? 2 * batch_key_stride((uint32_t)stride) * 8
+                                 : topk_scratch_bytes(stride, std::min<size_t>(count, stride)) + 64;
+    return (size_t)stride * 8 + key_bytes + count * 8 + ds->row_bytes() + 4096;
+}
+static constexpr size_t kSearchChunkBytes = 1536ull << 20, kSearchChunkQueries = 4096;
+// The rows of by_item queries (left empty for by_vector ones).
+static int search_rows(ah_index *ix, const uint32_t *query_items, size_t nq, std::vector<uint32_t> &rows) {
+    ah_dataset *ds = ix->ds;
     if (query_items) {
         rows.resize(nq);
         for (size_t q = 0; q < nq; q++) {
@@ -4932,13 +4982,19 @@ static int search_shape(ah_index *ix, const uint32_t *query_items, size_t nq, si
             }
         }
     }
+    return AH_OK;
+}
+static int search_shape(ah_index *ix, const uint32_t *query_items, size_t nq, size_t count, size_t search_k, size_t oversampling,
+                        SearchShape &out) {
+    ah_dataset *ds = ix->ds;
+    uint64_t sk_eff = 0, stride = 0;
+    search_extent(ix, count, search_k, oversampling, sk_eff, stride);
+    AH_REQUIRE(stride < 0x7FFFFFFFull, AH_ERR_INVALID_ARGUMENT, "search_k too large");
+    AH_TRY(search_rows(ix, query_items, nq, out.rows));
     // sub-batches bounded by scratch (~1.5 GiB of candidate buffers)
-    const size_t key_bytes = batch_supported((uint32_t)std::min<size_t>(count, 0xFFFFFFFFu))
-                                 ? 2 * batch_key_stride((uint32_t)stride) * 8
-                                 : topk_scratch_bytes(stride, std::min<size_t>(count, stride)) + 64;
-    const size_t per_query = (size_t)stride * 8 + key_bytes + count * 8 + ds->row_bytes() + 4096;
-    size_t chunk = std::max<size_t>(1, std::min<size_t>(nq, (1536ull << 20) / per_query));
-    out.chunk = std::min<size_t>(chunk, 4096);
+    const size_t per_query = search_query_bytes(ds, stride, count);
+    size_t chunk = std::max<size_t>(1, std::min<size_t>(nq, kSearchChunkBytes / per_query));
+    out.chunk = std::min<size_t>(chunk, kSearchChunkQueries);
     out.sk_eff = sk_eff;
     out.stride = stride;
     return AH_OK;
@@ -5538,16 +5594,27 @@ int ah_index_filter_stats(ah_index *ix, ah_filter_stats *out, int reset) {
     AH_GUARDED_END
 }
 
-// ah_search_batch with a filter per query.  The query indices are ordered stably by filter slot, unfiltered first; a run of at
-// least AH_SEARCH_FILTER_GROUP_MIN queries of one slot is cut into UNIFORM sub-batches, which go through search_chunk exactly
-// as a single-filter call does (same descents, leaf tiles and screens) with the filter's resident bitmap and per-node array;
-// the queries of the shorter runs are packed, in that order, into MIXED sub-batches (SearchParams::filter_table; sorted
-// re-rank).  A mixed sub-batch whose queries happen to share one slot is a uniform one.  (tests/test_search_filters_cpu.py
-// restates the rule in numpy.)
-int ah_search_batch_filters(ah_index *ix, const float *queries, const uint32_t *query_items, size_t nq, size_t count, size_t search_k,
-                            size_t oversampling, ah_filter *const *filters, size_t n_filters, const uint32_t *filter_of_query,
-                            uint32_t *out_ids, float *out_distances, uint32_t *out_counts) {
-    AH_GUARDED("ah_search_batch_filters")
+// What ah_search_batch_filters and ah_search_batch_params share: a batched search with a filter per query and, when `params` is
+// given, a (count, search_k, oversampling) per query as well (the scalars are then unused; out_stride = count otherwise).
+//
+// The order: stable by filter slot, unfiltered first; inside a slot the queries whose count leaves the batched top-k
+// (batch_supported false) come last and never share a sub-batch with the others; inside such a RUN the queries are ordered
+// stably by the stride of their candidate buffer (AH_SEARCH_PARAMS_SORT=0: the caller's order).  A run of at least
+// AH_SEARCH_FILTER_GROUP_MIN queries is cut into UNIFORM sub-batches, which go through search_chunk exactly as a single-filter call
+// does (same descents, leaf tiles and screens) with the filter's resident bitmap and per-node array; the queries of the shorter
+// runs are packed, in that order, into MIXED sub-batches (SearchParams::filter_table; sorted re-rank).  A mixed sub-batch whose
+// queries happen to share one slot is a uniform one.  Every sub-batch is cut greedily under its OWN largest stride and largest
+// count: it grows while it holds at most 4096 queries and its scratch at those maxima stays within 1.5 GiB.  A sub-batch whose
+// queries do not all share one (count, effective search_k) is VARIED: search_chunk gets the two tables (VariedParams) and its
+// largest values.  With one (count, search_k, oversampling) for all queries the rule is the one ah_search_batch_filters always had.
+// (tests/test_search_filters_cpu.py and tests/test_search_params_cpu.py restate the rule in numpy.)
+struct QueryExtent {
+    uint32_t count, sk_eff, stride;
+};
+static int search_batch_cut(ah_index *ix, const float *queries, const uint32_t *query_items, size_t nq, size_t count, size_t search_k,
+                            size_t oversampling, const ah_query_params *params, size_t out_stride, ah_filter *const *filters,
+                            size_t n_filters, const uint32_t *filter_of_query, uint32_t *out_ids, float *out_distances,
+                            uint32_t *out_counts) {
     // (what can be judged without the index first)
     AH_REQUIRE((queries != nullptr) != (query_items != nullptr), AH_ERR_INVALID_ARGUMENT,
                "exactly one of queries / query_items must be given");
@@ -5568,69 +5635,113 @@ int ah_search_batch_filters(ah_index *ix, const float *queries, const uint32_t *
     }
     ah_dataset *ds = ix->ds;
     if (nq == 0) return AH_OK;
-    AH_REQUIRE(count > 0 && count < 0x7FFFFFFFull, AH_ERR_INVALID_ARGUMENT, "count must be > 0");
+    if (!params) AH_REQUIRE(count > 0 && count < 0x7FFFFFFFull, AH_ERR_INVALID_ARGUMENT, "count must be > 0");
     AH_HIP(hipSetDevice(ds->device));
-    for (size_t i = 0; i < nq * count; i++) {
+    for (size_t i = 0; i < nq * out_stride; i++) {
         out_ids[i] = 0xFFFFFFFFu;
         const uint32_t nan_bits = 0xFFFFFFFFu;
         memcpy(&out_distances[i], &nan_bits, 4);
     }
     for (size_t q = 0; q < nq; q++) out_counts[q] = 0;
     if (ds->n == 0 || ix->n_trees == 0 || ix->desc_len == 0) return AH_OK;  // reader.rs:323-325; trees that hold no id
-    SearchShape shape;
-    AH_TRY(search_shape(ix, query_items, nq, count, search_k, oversampling, shape));
-    const size_t chunk = shape.chunk;
-    // 1. the order: stable by slot, unfiltered first
+    // 0. every query's count, effective search_k and candidate-buffer stride (one of each without `params`)
+    QueryExtent one{};
+    std::vector<QueryExtent> ext;
+    if (params) {
+        ext.resize(nq);
+        for (size_t q = 0; q < nq; q++) {
+            uint64_t sk_eff = 0, stride = 0;
+            search_extent(ix, params[q].count, params[q].search_k, params[q].oversampling, sk_eff, stride);
+            AH_REQUIRE(stride < 0x7FFFFFFFull, AH_ERR_INVALID_ARGUMENT, "params[%zu]: search_k too large", q);
+            ext[q] = QueryExtent{params[q].count, (uint32_t)sk_eff, (uint32_t)stride};
+        }
+    } else {
+        uint64_t sk_eff = 0, stride = 0;
+        search_extent(ix, count, search_k, oversampling, sk_eff, stride);
+        AH_REQUIRE(stride < 0x7FFFFFFFull, AH_ERR_INVALID_ARGUMENT, "search_k too large");
+        one = QueryExtent{(uint32_t)count, (uint32_t)sk_eff, (uint32_t)stride};
+    }
+    auto ext_of = [&](size_t q) -> const QueryExtent & { return params ? ext[q] : one; };
+    std::vector<uint32_t> rows;
+    AH_TRY(search_rows(ix, query_items, nq, rows));
+    // 1. the order: stable by (slot, big count, stride)
     auto slot_of = [&](size_t q) -> uint32_t { return filter_of_query ? filter_of_query[q] : (n_filters ? 0u : AH_NO_FILTER); };
-    // (keys `slot + 1 (mod 2^32)` << 32 | query: stable by construction, and no temporary buffer whose allocation std::stable_sort
-    // would survive failing — every allocation of this call that fails gives a status)
+    // (keys `slot + 1 (mod 2^32)` << 32 | big << 31 | stride, then the query: stable by construction, and no temporary buffer whose
+    // allocation std::stable_sort would survive failing — every allocation of this call that fails gives a status)
+    const bool sort_params = params && tun(TUN_SEARCH_PARAMS_SORT) != 0;
+    auto run_of = [&](size_t q) -> uint64_t {  // (slot, big): the queries of one run share it
+        return ((uint64_t)(uint32_t)(slot_of(q) + 1u) << 1) | (batch_supported(ext_of(q).count) ? 0u : 1u);
+    };
     std::vector<uint32_t> order(nq);
     {
-        std::vector<uint64_t> keyed(nq);
-        for (size_t q = 0; q < nq; q++) keyed[q] = ((uint64_t)(uint32_t)(slot_of(q) + 1u) << 32) | (uint32_t)q;
+        std::vector<std::pair<uint64_t, uint32_t>> keyed(nq);
+        for (size_t q = 0; q < nq; q++) keyed[q] = {(run_of(q) << 31) | (sort_params ? ext_of(q).stride : 0u), (uint32_t)q};
         std::sort(keyed.begin(), keyed.end());
-        for (size_t q = 0; q < nq; q++) order[q] = (uint32_t)keyed[q];
+        for (size_t q = 0; q < nq; q++) order[q] = keyed[q].second;
     }
-    // 2. the sub-batches, as ranges of `perm`: the uniform ones first, then what is left over
+    // 2. the sub-batches, as ranges of `perm`: the uniform ones first, then what is left over (batched counts, then big ones)
     struct SubBatch {
-        size_t a, b;
-        bool mixed;
+        size_t a, b, off;  // perm[a, b); its results are staged from element `off`, in rows of `count`
+        bool mixed, varied;
+        uint32_t count, sk_eff, stride;  // the largest of its queries
     };
     const size_t group_min = (size_t)std::max<long long>(1, tun(TUN_SEARCH_FILTER_GROUP_MIN));
-    std::vector<uint32_t> perm, rest;
+    std::vector<uint32_t> perm, rest[2];
     std::vector<SubBatch> batches;
     perm.reserve(nq);
+    size_t staged = 0;
+    bool any_mixed = false;
+    auto cut = [&](const uint32_t *list, size_t n_list, bool may_mix) {
+        for (size_t c0 = 0; c0 < n_list;) {
+            SubBatch sb{perm.size(), 0, staged, false, false, 0, 0, 0};
+            size_t c1 = c0;
+            while (c1 < n_list && c1 - c0 < kSearchChunkQueries) {
+                const QueryExtent &e = ext_of(list[c1]);
+                const uint32_t st = std::max(sb.stride, e.stride), cn = std::max(sb.count, e.count);
+                if (c1 > c0 && (c1 - c0 + 1) * search_query_bytes(ds, st, cn) > kSearchChunkBytes) break;
+                sb.stride = st;
+                sb.count = cn;
+                sb.sk_eff = std::max(sb.sk_eff, e.sk_eff);
+                c1++;
+            }
+            for (size_t i = c0 + 1; i < c1; i++) {
+                sb.mixed = sb.mixed || (may_mix && slot_of(list[i]) != slot_of(list[c0]));
+                sb.varied = sb.varied || ext_of(list[i]).count != ext_of(list[c0]).count || ext_of(list[i]).sk_eff != ext_of(list[c0]).sk_eff;
+            }
+            sb.b = sb.a + (c1 - c0);
+            staged += (c1 - c0) * (size_t)sb.count;
+            any_mixed = any_mixed || sb.mixed;
+            batches.push_back(sb);
+            perm.insert(perm.end(), list + c0, list + c1);
+            c0 = c1;
+        }
+    };
     for (size_t r0 = 0; r0 < nq;) {
         size_t r1 = r0 + 1;
-        while (r1 < nq && slot_of(order[r1]) == slot_of(order[r0])) r1++;
-        if (r1 - r0 >= group_min) {
-            for (size_t c0 = r0; c0 < r1; c0 += chunk) {
-                const size_t c1 = std::min(r1, c0 + chunk);
-                batches.push_back(SubBatch{perm.size(), perm.size() + (c1 - c0), false});
-                perm.insert(perm.end(), order.begin() + c0, order.begin() + c1);
-            }
-        } else {
-            rest.insert(rest.end(), order.begin() + r0, order.begin() + r1);
-        }
+        while (r1 < nq && run_of(order[r1]) == run_of(order[r0])) r1++;
+        if (r1 - r0 >= group_min) cut(order.data() + r0, r1 - r0, false);
+        else rest[run_of(order[r0]) & 1u].insert(rest[run_of(order[r0]) & 1u].end(), order.begin() + r0, order.begin() + r1);
         r0 = r1;
     }
-    bool any_mixed = false;
-    for (size_t c0 = 0; c0 < rest.size(); c0 += chunk) {
-        const size_t c1 = std::min(rest.size(), c0 + chunk);
-        bool one_slot = true;
-        for (size_t i = c0 + 1; i < c1; i++) one_slot = one_slot && slot_of(rest[i]) == slot_of(rest[c0]);
-        batches.push_back(SubBatch{perm.size(), perm.size() + (c1 - c0), !one_slot});
-        any_mixed = any_mixed || !one_slot;
-        perm.insert(perm.end(), rest.begin() + c0, rest.begin() + c1);
-    }
-    // 3. queries and outputs in that order (nothing to move when the order is the caller's)
-    bool identity = true;
-    for (size_t i = 0; i < nq && identity; i++) identity = perm[i] == i;
+    for (const std::vector<uint32_t> &r : rest) cut(r.data(), r.size(), true);
+    // 3. queries and outputs in that order (nothing to move when the order is the caller's and every row is out_stride wide)
+    bool direct = true;
+    for (size_t i = 0; i < nq && direct; i++) direct = perm[i] == i;
+    bool identity = direct;
+    for (const SubBatch &sb : batches) direct = direct && sb.count == out_stride;
     std::vector<float> pq, pd;
-    std::vector<uint32_t> prow, pi, pc, pslot(nq);
+    std::vector<uint32_t> prow, pi, pc, pslot(nq), pcount, psk;
     for (size_t i = 0; i < nq; i++) pslot[i] = slot_of(perm[i]);
+    if (params) {
+        pcount.resize(nq);
+        psk.resize(nq);
+        for (size_t i = 0; i < nq; i++) {
+            pcount[i] = ext[perm[i]].count;
+            psk[i] = ext[perm[i]].sk_eff;
+        }
+    }
     const float *qsrc = queries;
-    const uint32_t *rsrc = query_items ? shape.rows.data() : nullptr;
+    const uint32_t *rsrc = query_items ? rows.data() : nullptr;
     uint32_t *oi = out_ids, *oc = out_counts;
     float *od = out_distances;
     if (!identity) {
@@ -5640,11 +5751,13 @@ int ah_search_batch_filters(ah_index *ix, const float *queries, const uint32_t *
             qsrc = pq.data();
         } else {
             prow.resize(nq);
-            for (size_t i = 0; i < nq; i++) prow[i] = shape.rows[perm[i]];
+            for (size_t i = 0; i < nq; i++) prow[i] = rows[perm[i]];
             rsrc = prow.data();
         }
-        pi.resize(nq * count);
-        pd.resize(nq * count);
+    }
+    if (!direct) {
+        pi.resize(staged);
+        pd.resize(staged);
         pc.resize(nq);
         oi = pi.data();
         od = pd.data();
@@ -5664,6 +5777,9 @@ int ah_search_batch_filters(ah_index *ix, const float *queries, const uint32_t *
     }
     ah_filter_stats fs{};
     fs.calls = 1;
+    ah_params_stats ps{};
+    ps.calls = 1;
+    ps.queries = nq;
     {
         std::lock_guard<std::mutex> lk(ix->stats_mu);
         ix->stats.calls++;
@@ -5673,15 +5789,18 @@ int ah_search_batch_filters(ah_index *ix, const float *queries, const uint32_t *
         const size_t cn = sb.b - sb.a;
         const float *q_at = qsrc ? qsrc + sb.a * (size_t)ds->dims : nullptr;
         const uint32_t *r_at = rsrc ? rsrc + sb.a : nullptr;
+        const VariedParams vp{sb.varied ? pcount.data() + sb.a : nullptr, sb.varied ? psk.data() + sb.a : nullptr};
+        const VariedParams *varied = sb.varied ? &vp : nullptr;
+        uint32_t *oi_at = direct ? oi + sb.a * out_stride : oi + sb.off;
+        float *od_at = direct ? od + sb.a * out_stride : od + sb.off;
         if (!sb.mixed) {
             // Descent: one wave per query unless the filter keeps under 5 % of the items (ah_search_batch); the per-node array is
             // resident, so no call is too small for it
             const uint32_t slot = pslot[sb.a];
             const ah_filter *f = slot == AH_NO_FILTER ? nullptr : filters[slot];
             const double share = f ? share_of(slot) : 1.0;
-            st = search_chunk(ix, ctx, q_at, r_at, cn, count, (uint32_t)shape.sk_eff, (uint32_t)shape.stride, f ? f->d_bits : nullptr,
-                              f ? f->len_bits : 0, share, wave_ok && (!f || share >= 0.05), f ? f->d_leaf_kept : nullptr,
-                              oi + sb.a * count, od + sb.a * count, oc + sb.a);
+            st = search_chunk(ix, ctx, q_at, r_at, cn, sb.count, sb.sk_eff, sb.stride, f ? f->d_bits : nullptr, f ? f->len_bits : 0, share,
+                              wave_ok && (!f || share >= 0.05), f ? f->d_leaf_kept : nullptr, oi_at, od_at, oc + sb.a, true, nullptr, varied);
             fs.uniform_batches++;
             fs.uniform_queries += cn;
         } else {
@@ -5692,11 +5811,17 @@ int ah_search_batch_filters(ah_index *ix, const float *queries, const uint32_t *
                     mf.min_share = std::min(mf.min_share, share_of(pslot[i]));
                     mf.n_filtered++;
                 }
-            st = search_chunk(ix, ctx, q_at, r_at, cn, count, (uint32_t)shape.sk_eff, (uint32_t)shape.stride, nullptr, 0, mf.min_share,
-                              wave_ok && mf.min_share >= 0.05, nullptr, oi + sb.a * count, od + sb.a * count, oc + sb.a, true, &mf);
+            st = search_chunk(ix, ctx, q_at, r_at, cn, sb.count, sb.sk_eff, sb.stride, nullptr, 0, mf.min_share,
+                              wave_ok && mf.min_share >= 0.05, nullptr, oi_at, od_at, oc + sb.a, true, &mf, varied);
             fs.mixed_batches++;
             fs.mixed_queries += cn;
         }
+        ps.batches++;
+        if (sb.varied) {
+            ps.varied_batches++;
+            ps.varied_queries += cn;
+        }
+        if (!batch_supported(sb.count)) ps.big_count_queries += cn;
         if (st != AH_OK) break;
     }
     {
@@ -5706,14 +5831,64 @@ int ah_search_batch_filters(ah_index *ix, const float *queries, const uint32_t *
         ix->fstats.mixed_batches += fs.mixed_batches;
         ix->fstats.uniform_queries += fs.uniform_queries;
         ix->fstats.mixed_queries += fs.mixed_queries;
+        if (params) {
+            ix->pstats.calls += ps.calls;
+            ix->pstats.batches += ps.batches;
+            ix->pstats.varied_batches += ps.varied_batches;
+            ix->pstats.queries += ps.queries;
+            ix->pstats.varied_queries += ps.varied_queries;
+            ix->pstats.big_count_queries += ps.big_count_queries;
+        }
     }
     AH_TRY(st);
-    if (!identity)
-        for (size_t i = 0; i < nq; i++) {
-            memcpy(out_ids + perm[i] * count, oi + i * count, count * 4);
-            memcpy(out_distances + perm[i] * count, od + i * count, count * 4);
-            out_counts[perm[i]] = oc[i];
-        }
+    if (!direct)
+        for (const SubBatch &sb : batches)
+            for (size_t i = sb.a; i < sb.b; i++) {
+                const size_t cq = ext_of(perm[i]).count, at = sb.off + (i - sb.a) * (size_t)sb.count;
+                memcpy(out_ids + perm[i] * out_stride, oi + at, cq * 4);
+                memcpy(out_distances + perm[i] * out_stride, od + at, cq * 4);
+                out_counts[perm[i]] = oc[i];
+            }
+    return AH_OK;
+}
+
+// ah_search_batch with a filter per query (the cutting rule: search_batch_cut).
+int ah_search_batch_filters(ah_index *ix, const float *queries, const uint32_t *query_items, size_t nq, size_t count, size_t search_k,
+                            size_t oversampling, ah_filter *const *filters, size_t n_filters, const uint32_t *filter_of_query,
+                            uint32_t *out_ids, float *out_distances, uint32_t *out_counts) {
+    AH_GUARDED("ah_search_batch_filters")
+    return search_batch_cut(ix, queries, query_items, nq, count, search_k, oversampling, nullptr, count, filters, n_filters, filter_of_query,
+                            out_ids, out_distances, out_counts);
+    AH_GUARDED_END
+}
+
+// ah_search_batch_filters with a (count, search_k, oversampling) per query as well: query q gets exactly what ah_search_batch
+// gives it alone with params[q] under its filter's id list, in row q of nq x out_stride outputs (padded with 0xFFFFFFFF / NaN).
+int ah_search_batch_params(ah_index *ix, const float *queries, const uint32_t *query_items, size_t nq, const ah_query_params *params,
+                           size_t out_stride, ah_filter *const *filters, size_t n_filters, const uint32_t *filter_of_query,
+                           uint32_t *out_ids, float *out_distances, uint32_t *out_counts) {
+    AH_GUARDED("ah_search_batch_params")
+    AH_REQUIRE(params || nq == 0, AH_ERR_INVALID_ARGUMENT, "params is NULL");
+    AH_REQUIRE(nq < 0xFFFFFFFFull, AH_ERR_INVALID_ARGUMENT, "too many filters or queries");
+    size_t max_count = 0;
+    for (size_t q = 0; q < nq; q++) {
+        AH_REQUIRE(params[q].count > 0 && params[q].count < 0x80000000u, AH_ERR_INVALID_ARGUMENT,
+                   "params[%zu].count = %u: count must be > 0 and below 2^31", q, params[q].count);
+        max_count = std::max<size_t>(max_count, params[q].count);
+    }
+    AH_REQUIRE(out_stride >= max_count, AH_ERR_INVALID_ARGUMENT, "out_stride = %zu is below the largest count, %zu", out_stride, max_count);
+    return search_batch_cut(ix, queries, query_items, nq, 0, 0, 0, params, out_stride, filters, n_filters, filter_of_query, out_ids,
+                            out_distances, out_counts);
+    AH_GUARDED_END
+}
+
+// How ah_search_batch_params cut its calls; reset != 0 zeroes the counters after the copy.
+int ah_index_params_stats(ah_index *ix, ah_params_stats *out, int reset) {
+    AH_GUARDED("ah_index_params_stats")
+    AH_REQUIRE(ix && out, AH_ERR_INVALID_ARGUMENT, "NULL argument");
+    std::lock_guard<std::mutex> lk(ix->stats_mu);
+    *out = ix->pstats;
+    if (reset) ix->pstats = ah_params_stats{};
     return AH_OK;
     AH_GUARDED_END
 }

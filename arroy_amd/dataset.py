@@ -677,6 +677,65 @@ class Index:
             return oi, od, oc
         return [[(int(oi[i, j]), float(od[i, j])) for j in range(int(oc[i]))] for i in range(nq)]
 
+    def search_params(self, counts, queries=None, items=None, search_ks=None, oversamplings=None, filters=None,
+                      filter_of_query=None, raw: bool = False):
+        """`search` in which every query has its own count, search_k and oversampling (ah_search_batch_params): each of the
+        three is a scalar for all queries or an array of one value per query (search_ks / oversamplings None or 0: the
+        reference's defaults).  Query q gets what `search` gives it alone with its values.  `filters` / `filter_of_query` as in
+        `search`.  Returns a list (one entry per query) of [(id, distance), ...]; with raw=True the (ids, distances, counts)
+        arrays of the C ABI, nq x max(counts), short rows padded with 0xFFFFFFFF / NaN."""
+        ds = self.dataset
+        if queries is not None:
+            q = _f32(queries)
+            if q.ndim == 1:
+                q = q[None, :]
+            if q.shape[1] != ds.dimensions:
+                raise _lib.InvalidVecDimension(1, f"Invalid vector dimensions. Got {q.shape[1]} but expected "
+                                                  f"{ds.dimensions}")
+            nq, it = q.shape[0], None
+        else:
+            it = _u32(items).ravel()
+            nq, q = it.size, None
+
+        def per_query(values, name, limit):
+            a = np.asarray(0 if values is None else values)
+            if a.dtype.kind not in "iu":
+                raise TypeError(f"{name} must be integers")
+            a = np.full(nq, a[()]) if a.ndim == 0 else a.ravel()
+            if a.size != nq:
+                raise ValueError(f"{name} has {a.size} entries for {nq} queries")
+            if nq and ((a.dtype.kind == "i" and (a < 0).any()) or (limit is not None and (a > limit).any())):
+                raise ValueError(f"{name} must lie in 0 .. {limit if limit is not None else 2**64 - 1}")
+            return a
+
+        params = np.zeros(nq, dtype=np.dtype([("search_k", "<u8"), ("count", "<u4"), ("oversampling", "<u4")]))
+        params["count"] = per_query(counts, "counts", 0xFFFFFFFF)
+        params["search_k"] = per_query(search_ks, "search_ks", None)
+        params["oversampling"] = per_query(oversamplings, "oversamplings", 0xFFFFFFFF)
+        stride = int(params["count"].max()) if nq else 0
+        oi = np.zeros((nq, stride), dtype=np.uint32)
+        od = np.zeros((nq, stride), dtype=np.float32)
+        oc = np.zeros(nq, dtype=np.uint32)
+        filters = list(filters or [])
+        handles = (C.c_void_p * max(1, len(filters)))(*[f._handle() for f in filters])
+        foq = None
+        if filter_of_query is not None:
+            foq = np.ascontiguousarray(np.asarray(filter_of_query, dtype=np.int64) & 0xFFFFFFFF, dtype=np.uint32).ravel()
+            if foq.size != nq:
+                raise ValueError(f"filter_of_query has {foq.size} entries for {nq} queries")
+        _lib.check(_lib.lib().ah_search_batch_params(self._h, _ptr(q), _ptr(it), nq,
+                                                     C.cast(params.ctypes.data, C.POINTER(_lib.AhQueryParams)), stride, handles,
+                                                     len(filters), _ptr(foq), _ptr(oi), _ptr(od), _ptr(oc)))
+        if raw:
+            return oi, od, oc
+        return [[(int(oi[i, j]), float(od[i, j])) for j in range(int(oc[i]))] for i in range(nq)]
+
+    def params_stats(self, reset: bool = False) -> dict:
+        """ah_index_params_stats: how ah_search_batch_params cut its calls."""
+        st = _lib.AhParamsStats()
+        _lib.check(_lib.lib().ah_index_params_stats(self._h, C.byref(st), 1 if reset else 0))
+        return {f: int(getattr(st, f)) for f, _ in _lib.AhParamsStats._fields_}
+
     def filter_stats(self, reset: bool = False) -> dict:
         """ah_index_filter_stats: how ah_search_batch_filters cut its calls, and the filters of this index."""
         st = _lib.AhFilterStats()

@@ -708,6 +708,38 @@ typedef struct ah_filter_stats {
 } ah_filter_stats;
 AH_API int ah_index_filter_stats(ah_index *index, ah_filter_stats *out, int reset);
 
+/* Per-query search parameters (ABI v7 addition: look the symbols up).  ah_search_batch_filters in which every query also names
+ * its own count, search_k and oversampling: the three knobs of `QueryBuilder` a host's coalesced requests differ in. */
+typedef struct ah_query_params {      /* 16 bytes; one per query */
+    uint64_t search_k;                /* 0 = count * n_trees (src/reader.rs:330) */
+    uint32_t count;                   /* Reader::nns(count); > 0 */
+    uint32_t oversampling;            /* 0 = D::DEFAULT_OVERSAMPLING */
+} ah_query_params;
+/* Query q returns exactly what ah_search_batch returns for it alone with params[q] under the id list of its filter — the same
+ * ids, the same distance bits and the same out_counts[q] — whatever else is in the call and however the call is cut (counts
+ * above the batched top-k's 2048 and the positional rule for non-finite distances included).  The outputs are nq x out_stride,
+ * out_stride >= the largest count; row q holds out_counts[q] = min(count_q, candidates_q) results, the rest of it is padded
+ * with 0xFFFFFFFF / NaN.  filters, n_filters and filter_of_query are those of ah_search_batch_filters.  The call is cut into
+ * sub-batches by filter as there; inside a filter's run the queries are ordered by the size of their candidate buffer
+ * (AH_SEARCH_PARAMS_SORT), a sub-batch's scratch is sized by its own largest search_k and count, and counts beyond the batched
+ * top-k share no sub-batch with the others.  Refused (AH_ERR_INVALID_ARGUMENT, the position named): params NULL, a count of 0
+ * or >= 2^31, out_stride below the largest count, then what ah_search_batch_filters refuses, then a search_k whose candidate
+ * buffer does not fit.  nq == 0 is AH_OK. */
+AH_API int ah_search_batch_params(ah_index *index, const float *queries, const uint32_t *query_items, size_t nq,
+                                  const ah_query_params *params, size_t out_stride, ah_filter *const *filters, size_t n_filters,
+                                  const uint32_t *filter_of_query, uint32_t *out_ids, float *out_distances, uint32_t *out_counts);
+/* How ah_search_batch_params cut its calls.  Counts since the index was created or since the last call with reset != 0.  (The
+ * sub-batches also count in ah_search_stats and ah_filter_stats, like those of ah_search_batch_filters.) */
+typedef struct ah_params_stats {
+    uint64_t calls;                 /* ah_search_batch_params calls that reached the device                             */
+    uint64_t batches;               /* their sub-batches                                                                */
+    uint64_t varied_batches;        /* sub-batches whose queries do not all share one (count, effective search_k)       */
+    uint64_t queries;
+    uint64_t varied_queries;        /* queries of the varied sub-batches                                                */
+    uint64_t big_count_queries;     /* queries of sub-batches whose counts leave the batched top-k (single-query kernels) */
+} ah_params_stats;
+AH_API int ah_index_params_stats(ah_index *index, ah_params_stats *out, int reset);
+
 /* Filters across index maintenance (ABI v7 addition: look the symbols up).  A live filter blocks ah_index_delete_items /
  * _insert_items / _graft / _drop_trees / _compact and ah_index_suspend, because its per-node counts would go stale.  What
  * does not go stale is its bitmap, apart from the ids the host's update touched.  ah_filter_suspend keeps the filter and
