@@ -563,20 +563,6 @@ void Context::destroy() {
     stream = nullptr;
 }
 
-// carve `bytes` (256-byte aligned) out of a linear scratch region
-struct Carver {
-    uint8_t *base;
-    size_t off = 0;
-    explicit Carver(void *b) : base(reinterpret_cast<uint8_t *>(b)) {}
-    template <typename T>
-    T *take(size_t count) {
-        T *p = reinterpret_cast<T *>(base + off);
-        off += (count * sizeof(T) + 255) & ~(size_t)255;
-        return p;
-    }
-};
-static inline size_t pad256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 // The host side of staging is a gather of records out of (unaligned) storage pages into pinned memory; one core
 // cannot keep a PCIe Gen5 link busy (a 32 MiB chunk takes 0.6 ms on the wire), so chunks are spread over a small
 // process-wide pool of persistent workers (spawning threads per chunk costs as much as the copy itself).
@@ -2089,13 +2075,6 @@ int ah_rerank_by_item(ah_dataset *ds, uint32_t query_item, const uint32_t *sorte
 
 // Many queries in one submission.  Fast path (k <= 2048): five launches for the whole batch (batch.hip).
 // Fallback (huge k): the single-query kernels queued back to back on one stream.
-struct HostSeg {
-    uint64_t off;
-    uint32_t n, k;
-};
-struct HostTile {
-    uint32_t query, first;
-};
 
 // AH_RERANK_TIMING=1: the wall time of one sub-batch of ah_rerank_batch by phase (include/arroy_hip.h: ah_rerank_stats).  The
 // phases are disjoint stretches of the calling thread's time; the destructor runs after the last synchronisation of whichever
@@ -2149,226 +2128,193 @@ struct RerankProbe {
         r.seconds_device_span += ms * 1e-3;
     }
 };
-#define AH_RR_SYNC(stream_)                       \
-    do {                                          \
-        probe.lap(&RerankProbe::enqueue);         \
-        AH_HIP(hipStreamSynchronize(stream_));    \
-        probe.lap(&RerankProbe::wait);            \
-    } while (0)
 
-static int rerank_batch_chunk(ah_dataset *ds, Context *ctx, const float *queries, size_t nq, const uint32_t *ids,
-                              const uint64_t *offsets, size_t k, uint32_t *out_ids, float *out_distances,
-                              uint32_t *out_counts) {
-    const uint64_t base = offsets[0];
-    const uint64_t total = offsets[nq] - base;
-    RerankProbe probe(ds, ctx, nq, total);
+// One sub-batch of ah_rerank_batch, in three parts: the plan and its scratch (rerank_plan), the candidate ids on their way to
+// the device (slice by slice, or rerank_ids_pipelined), and the one path every sub-batch ends on (rerank_finish).
+struct RerankJob {
+    ah_dataset *ds;
+    Context *ctx;
+    const uint32_t *ids;  // the sub-batch's first candidate id
+    size_t nq, k;
+    uint64_t total;
+    std::vector<RerankSeg> segs;
+    std::vector<RerankTile> tiles;
     uint32_t max_n = 0, max_rounds = 0;
-    std::vector<HostSeg> segs(nq);
-    std::vector<HostTile> tiles;
+    bool screened = false, screened8 = false;  // which stages of the certified screen apply
+    RerankBufs dev{};
+    RerankPinned<RerankSeg, RerankTile> pin{};
+};
+
+// Part 1: segs and tiles, which stages apply, the scratch (rerank_workspace.h) and the host's copies of what is uploaded first.
+static int rerank_plan(RerankJob &j, const float *queries, const uint64_t *offsets, uint32_t *out_counts) {
+    ah_dataset *ds = j.ds;
+    const size_t nq = j.nq, k = j.k;
     const uint32_t tc = batch_tile_candidates();
+    j.segs.resize(nq);
     for (size_t q = 0; q < nq; q++) {
         const uint64_t nq_items = offsets[q + 1] - offsets[q];
         AH_REQUIRE(nq_items < 0xFFFFFFFFull, AH_ERR_INVALID_ARGUMENT, "candidate list too long");
-        segs[q] = HostSeg{offsets[q] - base, (uint32_t)nq_items, (uint32_t)std::min<uint64_t>(k, nq_items)};
-        out_counts[q] = segs[q].k;
-        max_n = std::max(max_n, segs[q].n);
-        max_rounds = std::max(max_rounds, batch_rounds(segs[q].n, segs[q].k));
-        for (uint32_t f = 0; f < segs[q].n; f += tc) tiles.push_back(HostTile{(uint32_t)q, f});
+        const RerankSeg sg = j.segs[q] = RerankSeg{offsets[q] - offsets[0], (uint32_t)nq_items, (uint32_t)std::min<uint64_t>(k, nq_items)};
+        out_counts[q] = sg.k;
+        j.max_n = std::max(j.max_n, sg.n);
+        j.max_rounds = std::max(j.max_rounds, batch_rounds(sg.n, sg.k));
+        for (uint32_t f = 0; f < sg.n; f += tc) j.tiles.push_back(RerankTile{(uint32_t)q, f});
     }
-    const size_t qstride = pad256(ds->row_bytes());
-    const size_t kstride = batch_key_stride(std::max<uint32_t>(max_n, 1));
-    const size_t inv_bytes = batch_invert_wanted(ds->view(), total) ? batch_invert_counter_bytes(ds->n, total) : 0;
+    const size_t kstride = batch_key_stride(std::max<uint32_t>(j.max_n, 1));
+    const size_t inv_bytes = batch_invert_wanted(ds->view(), j.total) ? batch_invert_counter_bytes(ds->n, j.total) : 0;
     // Certified top-k screen (search.hip: k_search_select_screened): Cosine / DotProduct lists long enough for the screen to
     // pay (the candidates on the binary16 copy of the rows — made by the first call that wants it — and only the few whose
     // proven distance interval reaches the top k in f32).  Submissions the row-major re-rank takes are left to it.
-    bool screened = tun(TUN_RERANK_SCREEN) != 0 && (ds->metric == AH_COSINE || ds->metric == AH_DOT_PRODUCT) && ds->dims >= 32 &&
-                    inv_bytes == 0 && k <= 256 && total >= 8 * k * nq && !tiles.empty();
-    if (screened) screened = ensure_screen(ds, ctx->stream, false);
+    j.screened = tun(TUN_RERANK_SCREEN) != 0 && (ds->metric == AH_COSINE || ds->metric == AH_DOT_PRODUCT) && ds->dims >= 32 &&
+                 inv_bytes == 0 && k <= 256 && j.total >= 8 * k * nq && !j.tiles.empty();
+    if (j.screened) j.screened = ensure_screen(ds, j.ctx->stream, false);
     // ... and, round 6, on the int8 copy before that: half the bytes again per candidate, a wider band of survivors
-    const bool screened8 = screened && tun(TUN_RERANK_SCREEN8) != 0 && !ds->rerank8_off.load(std::memory_order_relaxed) &&
-                           ensure_screen8_search(ds, ctx->stream);
-    const size_t screen_bytes = (screened ? pad256(nq * (size_t)ds->hpitch * 2) + pad256(nq * 16) + pad256(total * 4) : 0) +
-                                (screened8 ? pad256(nq * (size_t)ds->pitch8 * 2) + pad256(nq * 16) + pad256(total * 4) : 0);
-    const size_t dev_bytes = pad256(nq * (size_t)ds->dims * 4) + nq * qstride + pad256(nq * 8) + pad256(nq * sizeof(HostSeg)) +
-                             pad256(tiles.size() * sizeof(HostTile)) + pad256(total * 4) * 2 + 2 * pad256(nq * kstride * 8) +
-                             pad256(nq * k * 4) * 2 + pad256(inv_bytes) + screen_bytes + 4096;
-    const size_t pin_bytes = pad256(nq * (size_t)ds->dims * 4) + pad256(nq * sizeof(HostSeg)) +
-                             pad256(tiles.size() * sizeof(HostTile)) + pad256(total * 4) + pad256(nq * k * 4) * 2 + 4096;
-    AH_TRY(ctx->ensure_device(dev_bytes));
-    AH_TRY(ctx->ensure_pinned(pin_bytes));
-    Carver dev(ctx->d_scratch), pin(ctx->h_pinned);
-    float *d_qf32 = dev.take<float>(nq * (size_t)ds->dims);
-    uint8_t *d_qvecs = dev.take<uint8_t>(nq * qstride);
-    float *d_qhdrs = dev.take<float>(nq * 2);
-    HostSeg *d_segs = dev.take<HostSeg>(nq);
-    HostTile *d_tiles = dev.take<HostTile>(tiles.size());
-    uint32_t *d_ids = dev.take<uint32_t>(total);
-    float *d_dist = dev.take<float>(total);
-    uint64_t *d_ka = dev.take<uint64_t>(nq * kstride);
-    uint64_t *d_kb = dev.take<uint64_t>(nq * kstride);
-    uint32_t *d_oi = dev.take<uint32_t>(nq * k);
-    float *d_od = dev.take<float>(nq * k);
-    uint32_t *d_err = dev.take<uint32_t>(16);  // [error bits][counters of the screened selection]
-    uint32_t *d_inv = inv_bytes ? dev.take<uint32_t>(inv_bytes / 4) : nullptr;
-    uint16_t *d_q16 = screened ? dev.take<uint16_t>(nq * (size_t)ds->hpitch) : nullptr;
-    float4 *d_qstats = screened ? dev.take<float4>(nq) : nullptr;
-    float *d_aux = screened ? dev.take<float>(total) : nullptr;
-    int8_t *d_q8 = screened8 ? dev.take<int8_t>(nq * (size_t)ds->pitch8 * 2) : nullptr;
-    float4 *d_q8stats = screened8 ? dev.take<float4>(nq) : nullptr;
-    float *d_aux8 = screened8 ? dev.take<float>(total) : nullptr;
-    float *h_q = pin.take<float>(nq * (size_t)ds->dims);
-    HostSeg *h_segs = pin.take<HostSeg>(nq);
-    HostTile *h_tiles = pin.take<HostTile>(tiles.size());
-    uint32_t *h_ids = pin.take<uint32_t>(total);
-    uint32_t *h_oi = pin.take<uint32_t>(nq * k);
-    float *h_od = pin.take<float>(nq * k);
-    uint32_t *h_err = pin.take<uint32_t>(16);  // [error bits][the selection's counters: words 9, 10 of search.hip's SearchStatSlot]
-    // More survivors than the selection holds (bit 3) on the int8 stage is not a reason to leave the screen: the same lists once
-    // more on the binary16 rows.  A dataset where that keeps happening (candidates closer together than the int8 error) stops
-    // trying: `rerank8_off` after 8 such sub-batches within one window of 64 the stage served (screen8_window_note).
-    bool retried8 = false;
-    auto note_screened = [&](const uint32_t *words) {  // ah_rerank_stats: how the screen went (always kept: three additions)
-        std::lock_guard<std::mutex> lk(ds->mu);
-        ds->rr_stats.queries_screened += words[9];
-        ds->rr_stats.survivors += words[10];
-        ds->rr_stats.chunks_int8 += screened8 && !retried8 ? 1 : 0;
-    };
-    auto retry_on_binary16 = [&](uint32_t err_bits) -> int {
-        if (!screened8) return AH_OK;
-        const bool overflow = (err_bits & ~1u) == 8u;
-        if (screen8_window_note(ds->rerank8_seen, ds->rerank8_fails, overflow)) ds->rerank8_off.store(true, std::memory_order_relaxed);
-        if (!overflow) return AH_OK;
-        retried8 = true;
-        {  // (counted whatever the retry leads to: a retry that ends on the exact path ran all the same)
-            std::lock_guard<std::mutex> lk(ds->mu);
-            ds->rr_stats.chunks_int8_retried += 1;
+    j.screened8 = j.screened && tun(TUN_RERANK_SCREEN8) != 0 && !ds->rerank8_off.load(std::memory_order_relaxed) &&
+                  ensure_screen8_search(ds, j.ctx->stream);
+    const RerankSizes z{nq, ds->dims, ds->row_bytes(), k, j.total, j.tiles.size(), kstride, inv_bytes, ds->hpitch, ds->pitch8, j.screened, j.screened8};
+    Carver dev_bytes(nullptr), pin_bytes(nullptr);  // (counting)
+    rerank_device_layout(dev_bytes, z, j.dev);
+    rerank_pinned_layout(pin_bytes, z, j.pin);
+    AH_TRY(j.ctx->ensure_device(dev_bytes.off));
+    AH_TRY(j.ctx->ensure_pinned(pin_bytes.off));
+    Carver dev(j.ctx->d_scratch), pin(j.ctx->h_pinned);
+    rerank_device_layout(dev, z, j.dev);
+    rerank_pinned_layout(pin, z, j.pin);
+    j.dev.n_queries = (uint32_t)nq, j.dev.n_tiles = (uint32_t)j.tiles.size();
+    j.dev.qstride = pad256(z.row_bytes), j.dev.kstride = kstride;
+    memcpy(j.pin.q, queries, nq * (size_t)ds->dims * 4);
+    memcpy(j.pin.segs, j.segs.data(), nq * sizeof(RerankSeg));
+    if (!j.tiles.empty()) memcpy(j.pin.tiles, j.tiles.data(), j.tiles.size() * sizeof(RerankTile));
+    return AH_OK;
+}
+
+// Part 2: the candidate ids, tens of MB for a big submission.  `len` ids from `lo` are copied into the pinned buffer by several
+// cores (like the staging gather) and sent on `via` right away.
+static int rerank_send_ids(RerankJob &j, RerankProbe &probe, uint64_t lo, uint64_t len, hipStream_t via) {
+    probe.lap(&RerankProbe::enqueue);
+    parallel_rows(len, 4, [&](size_t a, size_t b) { memcpy(j.pin.ids + lo + a, j.ids + lo + a, (b - a) * 4); });
+    probe.lap(&RerankProbe::ids);
+    AH_HIP(hipMemcpyAsync(j.dev.d_ids + lo, j.pin.ids + lo, len * 4, hipMemcpyHostToDevice, via));
+    return AH_OK;
+}
+// The screened path takes the lists group by group: while the screen kernel of group g runs on the context's stream,
+// the host copies the ids of group g + 1 into the pinned buffer and the copy stream sends them (review item 6: the
+// upload of a submission used to run to its end before the first kernel started).
+static int rerank_ids_pipelined(RerankJob &j, RerankProbe &probe, uint64_t n_groups) {
+    Context *ctx = j.ctx;
+    hipStream_t s = ctx->stream;
+    AH_TRY(launch_prepare_queries_only(j.ds->view(), j.dev.d_q_f32, j.dev.n_queries, j.dev.d_qvecs, j.dev.qstride, j.dev.d_qhdrs, s));
+    const uint64_t group_ids = (j.total + n_groups - 1) / n_groups;
+    const std::vector<RerankSeg> &segs = j.segs;
+    size_t qa = 0;
+    uint32_t ta = 0;
+    while (qa < j.nq) {
+        size_t qb = qa + 1;
+        while (qb < j.nq && segs[qb].off + segs[qb].n - segs[qa].off <= group_ids) qb++;
+        const uint64_t lo = segs[qa].off, len = segs[qb - 1].off + segs[qb - 1].n - lo;
+        uint32_t tb = ta;
+        while (tb < j.tiles.size() && j.tiles[tb].query < qb) tb++;
+        if (len) {
+            AH_TRY(rerank_send_ids(j, probe, lo, len, ctx->copy_stream));
+            AH_HIP(hipEventRecord(ctx->ev0, ctx->copy_stream));
+            AH_HIP(hipStreamWaitEvent(s, ctx->ev0, 0));
         }
-        AH_HIP(hipMemsetAsync(d_err, 0, 64, ctx->stream));
-        AH_TRY(launch_rerank_screened(ds, (uint32_t)nq, d_qvecs, qstride, d_qhdrs, d_segs, d_tiles, 0u, (uint32_t)tiles.size(), tc, d_ids,
-                                      d_dist, d_aux, d_q16, d_qstats, (uint32_t)k, d_oi, d_od, d_err, ctx->stream, true, true));
-        AH_HIP(hipMemcpyAsync(h_oi, d_oi, nq * k * 4, hipMemcpyDeviceToHost, ctx->stream));
-        AH_HIP(hipMemcpyAsync(h_od, d_od, nq * k * 4, hipMemcpyDeviceToHost, ctx->stream));
-        AH_HIP(hipMemcpyAsync(h_err, d_err, 64, hipMemcpyDeviceToHost, ctx->stream));
-        AH_HIP(hipStreamSynchronize(ctx->stream));
-        return AH_OK;
+        AH_TRY(launch_rerank_screened(j.ds, j.dev, ta, tb - ta, (uint32_t)j.k, qa == 0, qb == j.nq, j.screened8, s));
+        qa = qb;
+        ta = tb;
+    }
+    return AH_OK;
+}
+
+// Part 3: read back and check; a screened sub-batch is then accepted, tried once more on the binary16 rows, or redone on the
+// exact path from the prepared queries.
+static int rerank_finish(RerankJob &j, RerankProbe &probe, uint32_t *out_ids, float *out_distances) {
+    ah_dataset *ds = j.ds;
+    hipStream_t s = j.ctx->stream;
+    const RerankBufs &b = j.dev;
+    const size_t out_bytes = j.nq * j.k * 4;
+    const uint32_t *h_err = j.pin.err;
+    // results and flags into the pinned mirrors; a missing id or a list that is not ascending and unique fails here: no other
+    // pass changes that.  (`timed`: the wait is its own phase of the probe; the retry's stays with what is enqueued around it)
+    auto read_back = [&](bool timed) -> int {
+        AH_HIP(hipMemcpyAsync(j.pin.out_ids, b.d_out_ids, out_bytes, hipMemcpyDeviceToHost, s));
+        AH_HIP(hipMemcpyAsync(j.pin.out_dist, b.d_out_dist, out_bytes, hipMemcpyDeviceToHost, s));
+        AH_HIP(hipMemcpyAsync(j.pin.err, b.d_err, 64, hipMemcpyDeviceToHost, s));
+        if (timed) probe.lap(&RerankProbe::enqueue);
+        AH_HIP(hipStreamSynchronize(s));
+        if (timed) probe.lap(&RerankProbe::wait);
+        return check_err_flags(*h_err, true);
     };
-    memcpy(h_q, queries, nq * (size_t)ds->dims * 4);
-    memcpy(h_segs, segs.data(), nq * sizeof(HostSeg));
-    if (!tiles.empty()) memcpy(h_tiles, tiles.data(), tiles.size() * sizeof(HostTile));
+    bool pending = !j.screened;  // results of the last launch not read back yet
+    if (j.screened) {
+        AH_TRY(read_back(true));
+        // More survivors than the selection holds (bit 3) on the int8 stage is not a reason to leave the screen: the same lists
+        // once more on the binary16 rows.  A dataset where that keeps happening (candidates closer together than the int8 error)
+        // stops trying: `rerank8_off` after 8 such sub-batches within one window of 64 the stage served (screen8_window_note).
+        bool retried8 = false;
+        if (j.screened8) {
+            retried8 = (*h_err & ~1u) == 8u;
+            if (screen8_window_note(ds->rerank8_seen, ds->rerank8_fails, retried8)) ds->rerank8_off.store(true, std::memory_order_relaxed);
+        }
+        if (retried8) {
+            {  // (counted whatever the retry leads to: a retry that ends on the exact path ran all the same)
+                std::lock_guard<std::mutex> lk(ds->mu);
+                ds->rr_stats.chunks_int8_retried += 1;
+            }
+            AH_HIP(hipMemsetAsync(b.d_err, 0, 64, s));
+            AH_TRY(launch_rerank_screened(ds, b, 0u, b.n_tiles, (uint32_t)j.k, true, true, false, s));
+            AH_TRY(read_back(false));
+        }
+        if ((*h_err & ~1u) == 0) {  // ah_rerank_stats: how the screen went (always kept: three additions)
+            std::lock_guard<std::mutex> lk(ds->mu);
+            ds->rr_stats.queries_screened += h_err[9];
+            ds->rr_stats.survivors += h_err[10];
+            ds->rr_stats.chunks_int8 += j.screened8 && !retried8 ? 1 : 0;
+        } else {  // a non-finite value, or more survivors than the selection holds: the exact path, from the prepared queries
+            AH_HIP(hipMemsetAsync(b.d_err, 0, 64, s));
+            AH_TRY(launch_rerank_batch_prepared(ds->view(), b, j.max_n, (uint32_t)j.k, j.max_rounds, j.total, s));
+            pending = true;
+        }
+    }
+    if (pending) AH_TRY(read_back(true));
+    memcpy(out_ids, j.pin.out_ids, out_bytes);
+    memcpy(out_distances, j.pin.out_dist, out_bytes);
+    return AH_OK;
+}
+
+static int rerank_batch_chunk(ah_dataset *ds, Context *ctx, const float *queries, size_t nq, const uint32_t *ids,
+                              const uint64_t *offsets, size_t k, uint32_t *out_ids, float *out_distances, uint32_t *out_counts) {
+    RerankJob j{ds, ctx, ids + offsets[0], nq, k, offsets[nq] - offsets[0]};
+    RerankProbe probe(ds, ctx, nq, j.total);
+    AH_TRY(rerank_plan(j, queries, offsets, out_counts));
+    const RerankBufs &b = j.dev;
     hipStream_t s = ctx->stream;
     probe.lap(&RerankProbe::prep);
     probe.first_enqueue(s);
-    AH_HIP(hipMemcpyAsync(d_qf32, h_q, nq * (size_t)ds->dims * 4, hipMemcpyHostToDevice, s));
-    AH_HIP(hipMemcpyAsync(d_segs, h_segs, nq * sizeof(HostSeg), hipMemcpyHostToDevice, s));
-    if (!tiles.empty()) AH_HIP(hipMemcpyAsync(d_tiles, h_tiles, tiles.size() * sizeof(HostTile), hipMemcpyHostToDevice, s));
-    AH_HIP(hipMemsetAsync(d_err, 0, 64, s));
-    // candidate ids: tens of MB for a big submission.  Slices of 2M ids are copied into the pinned buffer by several
-    // cores (like the staging gather) and sent right away, so the DMA of one slice overlaps the host copy of the next.
+    AH_HIP(hipMemcpyAsync(b.d_q_f32, j.pin.q, nq * (size_t)ds->dims * 4, hipMemcpyHostToDevice, s));
+    AH_HIP(hipMemcpyAsync(b.d_segs, j.pin.segs, nq * sizeof(RerankSeg), hipMemcpyHostToDevice, s));
+    if (b.n_tiles) AH_HIP(hipMemcpyAsync(b.d_tiles, j.pin.tiles, b.n_tiles * sizeof(RerankTile), hipMemcpyHostToDevice, s));
+    AH_HIP(hipMemsetAsync(b.d_err, 0, 64, s));
     const uint64_t n_groups = (uint64_t)std::max<long long>(1, tun(TUN_RERANK_GROUPS));
-    const bool pipelined = screened && n_groups > 1 && total >= (512u << 10);
+    const bool pipelined = j.screened && n_groups > 1 && j.total >= (512u << 10);
     if (pipelined && !ctx->copy_stream && create_copy_stream(&ctx->copy_stream) != hipSuccess) {
         (void)hipGetLastError();
         ctx->copy_stream = nullptr;
     }
     if (pipelined && ctx->copy_stream) {
-        // The screened path takes the lists group by group: while the screen kernel of group g runs on the context's stream,
-        // the host copies the ids of group g + 1 into the pinned buffer and the copy stream sends them (review item 6: the
-        // upload of a submission used to run to its end before the first kernel started).
-        AH_TRY(launch_prepare_queries_only(ds->view(), d_qf32, (uint32_t)nq, d_qvecs, qstride, d_qhdrs, s));
-        const uint64_t group_ids = (total + n_groups - 1) / n_groups;
-        size_t qa = 0;
-        uint32_t ta = 0;
-        bool first = true;
-        while (qa < nq) {
-            size_t qb = qa + 1;
-            while (qb < nq && segs[qb].off + segs[qb].n - segs[qa].off <= group_ids) qb++;
-            const uint64_t lo = segs[qa].off, len = segs[qb - 1].off + segs[qb - 1].n - lo;
-            uint32_t tb = ta;
-            while (tb < tiles.size() && tiles[tb].query < qb) tb++;
-            if (len) {
-                probe.lap(&RerankProbe::enqueue);
-                parallel_rows(len, 4, [&](size_t a, size_t b) { memcpy(h_ids + lo + a, ids + base + lo + a, (b - a) * 4); });
-                probe.lap(&RerankProbe::ids);
-                AH_HIP(hipMemcpyAsync(d_ids + lo, h_ids + lo, len * 4, hipMemcpyHostToDevice, ctx->copy_stream));
-                AH_HIP(hipEventRecord(ctx->ev0, ctx->copy_stream));
-                AH_HIP(hipStreamWaitEvent(s, ctx->ev0, 0));
-            }
-            AH_TRY(launch_rerank_screened(ds, (uint32_t)nq, d_qvecs, qstride, d_qhdrs, d_segs, d_tiles, ta, tb - ta, tc, d_ids, d_dist,
-                                          d_aux, d_q16, d_qstats, (uint32_t)k, d_oi, d_od, d_err, s, first, qb == nq, d_q8, d_q8stats,
-                                          d_aux8));
-            first = false;
-            qa = qb;
-            ta = tb;
-        }
-        AH_HIP(hipMemcpyAsync(h_oi, d_oi, nq * k * 4, hipMemcpyDeviceToHost, s));
-        AH_HIP(hipMemcpyAsync(h_od, d_od, nq * k * 4, hipMemcpyDeviceToHost, s));
-        AH_HIP(hipMemcpyAsync(h_err, d_err, 64, hipMemcpyDeviceToHost, s));
-        AH_RR_SYNC(s);
-        AH_TRY(check_err_flags(*h_err, true));  // a missing id or a list that is not ascending and unique: no other pass changes that
-        AH_TRY(retry_on_binary16(*h_err));
-        if ((*h_err & ~1u) == 0) {
-            note_screened(h_err);
-            AH_TRY(check_err_flags(*h_err, true));
-            memcpy(out_ids, h_oi, nq * k * 4);
-            memcpy(out_distances, h_od, nq * k * 4);
-            return AH_OK;
-        }
-        // a non-finite value, or more survivors than the selection holds: the exact path, from the prepared queries
-        AH_HIP(hipMemsetAsync(d_err, 0, 64, s));
-        AH_TRY(launch_rerank_batch_prepared(ds->view(), (uint32_t)nq, d_qvecs, qstride, d_qhdrs, d_segs, d_tiles, (uint32_t)tiles.size(),
-                                            d_ids, d_dist, d_ka, d_kb, kstride, max_n, (uint32_t)k, max_rounds, d_oi, d_od, d_err, s,
-                                            total, d_inv));
-        AH_HIP(hipMemcpyAsync(h_oi, d_oi, nq * k * 4, hipMemcpyDeviceToHost, s));
-        AH_HIP(hipMemcpyAsync(h_od, d_od, nq * k * 4, hipMemcpyDeviceToHost, s));
-        AH_HIP(hipMemcpyAsync(h_err, d_err, 64, hipMemcpyDeviceToHost, s));
-        AH_RR_SYNC(s);
-        AH_TRY(check_err_flags(*h_err, true));
-        memcpy(out_ids, h_oi, nq * k * 4);
-        memcpy(out_distances, h_od, nq * k * 4);
-        return AH_OK;
-    }
-    for (uint64_t lo = 0; lo < total; lo += (2u << 20)) {
-        const uint64_t len = std::min<uint64_t>(2u << 20, total - lo);
-        probe.lap(&RerankProbe::enqueue);
-        parallel_rows(len, 4, [&](size_t a, size_t b) { memcpy(h_ids + lo + a, ids + base + lo + a, (b - a) * 4); });
-        probe.lap(&RerankProbe::ids);
-        AH_HIP(hipMemcpyAsync(d_ids + lo, h_ids + lo, len * 4, hipMemcpyHostToDevice, s));
-    }
-    if (screened) {
-        AH_TRY(launch_prepare_queries_only(ds->view(), d_qf32, (uint32_t)nq, d_qvecs, qstride, d_qhdrs, s));
-        AH_TRY(launch_rerank_screened(ds, (uint32_t)nq, d_qvecs, qstride, d_qhdrs, d_segs, d_tiles, 0u, (uint32_t)tiles.size(), tc, d_ids,
-                                      d_dist, d_aux, d_q16, d_qstats, (uint32_t)k, d_oi, d_od, d_err, s, true, true, d_q8, d_q8stats, d_aux8));
-        AH_HIP(hipMemcpyAsync(h_oi, d_oi, nq * k * 4, hipMemcpyDeviceToHost, s));
-        AH_HIP(hipMemcpyAsync(h_od, d_od, nq * k * 4, hipMemcpyDeviceToHost, s));
-        AH_HIP(hipMemcpyAsync(h_err, d_err, 64, hipMemcpyDeviceToHost, s));
-        AH_RR_SYNC(s);
-        AH_TRY(check_err_flags(*h_err, true));  // a missing id or a list that is not ascending and unique: no other pass changes that
-        AH_TRY(retry_on_binary16(*h_err));
-        if ((*h_err & ~1u) == 0) {
-            note_screened(h_err);
-            AH_TRY(check_err_flags(*h_err, true));
-            memcpy(out_ids, h_oi, nq * k * 4);
-            memcpy(out_distances, h_od, nq * k * 4);
-            return AH_OK;
-        }
-        // a non-finite value, or more survivors than the selection holds: the exact path, from the prepared queries
-        AH_HIP(hipMemsetAsync(d_err, 0, 64, s));
-        AH_TRY(launch_rerank_batch_prepared(ds->view(), (uint32_t)nq, d_qvecs, qstride, d_qhdrs, d_segs, d_tiles, (uint32_t)tiles.size(),
-                                            d_ids, d_dist, d_ka, d_kb, kstride, max_n, (uint32_t)k, max_rounds, d_oi, d_od, d_err, s,
-                                            total, d_inv));
+        AH_TRY(rerank_ids_pipelined(j, probe, n_groups));
     } else {
-        AH_TRY(launch_rerank_batch(ds->view(), d_qf32, (uint32_t)nq, d_qvecs, qstride, d_qhdrs, d_segs, d_tiles,
-                                   (uint32_t)tiles.size(), d_ids, d_dist, d_ka, d_kb, kstride, max_n, (uint32_t)k, max_rounds,
-                                   d_oi, d_od, d_err, s, total, d_inv));
+        // the straight upload: slices of 2M ids on the context's stream, so the DMA of one slice overlaps the host copy of the next
+        for (uint64_t lo = 0; lo < j.total; lo += (2u << 20))
+            AH_TRY(rerank_send_ids(j, probe, lo, std::min<uint64_t>(2u << 20, j.total - lo), s));
+        if (j.screened) {
+            AH_TRY(launch_prepare_queries_only(ds->view(), b.d_q_f32, b.n_queries, b.d_qvecs, b.qstride, b.d_qhdrs, s));
+            AH_TRY(launch_rerank_screened(ds, b, 0u, b.n_tiles, (uint32_t)k, true, true, j.screened8, s));
+        } else {
+            AH_TRY(launch_rerank_batch(ds->view(), b, j.max_n, (uint32_t)k, j.max_rounds, j.total, s));
+        }
     }
-    AH_HIP(hipMemcpyAsync(h_oi, d_oi, nq * k * 4, hipMemcpyDeviceToHost, s));
-    AH_HIP(hipMemcpyAsync(h_od, d_od, nq * k * 4, hipMemcpyDeviceToHost, s));
-    AH_HIP(hipMemcpyAsync(h_err, d_err, 64, hipMemcpyDeviceToHost, s));
-    AH_RR_SYNC(s);
-    AH_TRY(check_err_flags(*h_err, true));
-    memcpy(out_ids, h_oi, nq * k * 4);
-    memcpy(out_distances, h_od, nq * k * 4);
-    return AH_OK;
+    return rerank_finish(j, probe, out_ids, out_distances);
 }
 
 int ah_rerank_batch(ah_dataset *ds, const float *queries, size_t n_queries, const uint32_t *ids,

@@ -18,16 +18,6 @@ static constexpr uint32_t kChunk = 4096;   // keys per LDS sort (32 KiB)
 static constexpr uint32_t kTileCand = 512;  // candidates of one query per block (1024: 125-query submissions 3 % slower, 5.4 blocks per CU)
 static constexpr uint64_t kSentinel = ~0ull;
 
-struct Seg {          // one query's slice of the concatenated candidate list
-    uint64_t off;     // first candidate
-    uint32_t n;       // candidates
-    uint32_t k;       // min(count, n)
-};
-struct BTile {
-    uint32_t query;
-    uint32_t first;   // offset inside the query's candidate list
-};
-
 // `QueryBuilder::by_vector` for every query of the batch (src/reader.rs:64-75).
 __global__ void k_prepare_queries(DataView dv, const float *__restrict__ q_f32, uint8_t *qvecs, uint64_t qstride,
                                   float *qhdrs) {
@@ -64,8 +54,8 @@ __global__ void k_prepare_queries(DataView dv, const float *__restrict__ q_f32, 
 template <int METRIC>
 __global__ __launch_bounds__(kBlock) void k_batch_distances_f32(DataView dv, const uint8_t *__restrict__ qvecs,
                                                                 uint64_t qstride, const float *__restrict__ qhdrs,
-                                                                const Seg *__restrict__ segs,
-                                                                const BTile *__restrict__ tiles, uint32_t n_tiles,
+                                                                const RerankSeg *__restrict__ segs,
+                                                                const RerankTile *__restrict__ tiles, uint32_t n_tiles,
                                                                 const uint32_t *__restrict__ ids,
                                                                 float *__restrict__ out, uint32_t *err) {
     constexpr int OP = METRIC == AH_EUCLIDEAN ? OP_EUCLID : OP_DOT;
@@ -75,8 +65,8 @@ __global__ __launch_bounds__(kBlock) void k_batch_distances_f32(DataView dv, con
     const uint32_t o = threadIdx.x >> 3, j = threadIdx.x & 7u;
     uint32_t loaded_query = 0xFFFFFFFFu;
     for (uint32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const BTile tl = tiles[tile];
-        const Seg sg = segs[tl.query];
+        const RerankTile tl = tiles[tile];
+        const RerankSeg sg = segs[tl.query];
         if (tl.query != loaded_query) {  // block-uniform
             __syncthreads();
             const float4 *g = reinterpret_cast<const float4 *>(qvecs + tl.query * qstride);
@@ -122,16 +112,16 @@ __global__ __launch_bounds__(kBlock) void k_batch_distances_f32(DataView dv, con
 
 __global__ __launch_bounds__(kBlock) void k_batch_distances_bq(DataView dv, const uint8_t *__restrict__ qvecs,
                                                                uint64_t qstride, const float *__restrict__ qhdrs,
-                                                               const Seg *__restrict__ segs,
-                                                               const BTile *__restrict__ tiles, uint32_t n_tiles,
+                                                               const RerankSeg *__restrict__ segs,
+                                                               const RerankTile *__restrict__ tiles, uint32_t n_tiles,
                                                                const uint32_t *__restrict__ ids,
                                                                float *__restrict__ out, uint32_t *err) {
     extern __shared__ uint64_t s_qw[];
     __shared__ float s_hdr[2];
     uint32_t loaded_query = 0xFFFFFFFFu;
     for (uint32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const BTile tl = tiles[tile];
-        const Seg sg = segs[tl.query];
+        const RerankTile tl = tiles[tile];
+        const RerankSeg sg = segs[tl.query];
         if (tl.query != loaded_query) {
             __syncthreads();
             const uint64_t *g = reinterpret_cast<const uint64_t *>(qvecs + tl.query * qstride);
@@ -179,13 +169,13 @@ static constexpr int kPairGroup = 4;   // pairs per octet (measured on 10M pairs
 static constexpr uint32_t kScanItems = 2048;  // counters per scan block (256 threads x 8)
 
 // pass 1: validate the candidates exactly like the query-major kernel and histogram them by row
-__global__ __launch_bounds__(kBlock) void k_inv_count(DataView dv, const Seg *__restrict__ segs,
-                                                      const BTile *__restrict__ tiles, uint32_t n_tiles,
+__global__ __launch_bounds__(kBlock) void k_inv_count(DataView dv, const RerankSeg *__restrict__ segs,
+                                                      const RerankTile *__restrict__ tiles, uint32_t n_tiles,
                                                       const uint32_t *__restrict__ ids, uint32_t *__restrict__ count,
                                                       float *__restrict__ out, uint32_t *err) {
     for (uint32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const BTile tl = tiles[tile];
-        const Seg sg = segs[tl.query];
+        const RerankTile tl = tiles[tile];
+        const RerankSeg sg = segs[tl.query];
         const uint32_t in_tile = min(kTileCand, sg.n - tl.first);
         const uint64_t base = sg.off + tl.first;
         for (uint32_t p = threadIdx.x; p < in_tile; p += blockDim.x) {
@@ -265,13 +255,13 @@ __global__ __launch_bounds__(256) void k_scan_add(uint32_t *__restrict__ data, u
 }
 
 // pass 2: scatter (row, query, position) into row order; `start` holds the exclusive scan and is advanced
-__global__ __launch_bounds__(kBlock) void k_inv_scatter(DataView dv, const Seg *__restrict__ segs,
-                                                        const BTile *__restrict__ tiles, uint32_t n_tiles,
+__global__ __launch_bounds__(kBlock) void k_inv_scatter(DataView dv, const RerankSeg *__restrict__ segs,
+                                                        const RerankTile *__restrict__ tiles, uint32_t n_tiles,
                                                         const uint32_t *__restrict__ ids, uint32_t *__restrict__ start,
                                                         uint64_t *__restrict__ pair_rq, uint32_t *__restrict__ pair_pos) {
     for (uint32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const BTile tl = tiles[tile];
-        const Seg sg = segs[tl.query];
+        const RerankTile tl = tiles[tile];
+        const RerankSeg sg = segs[tl.query];
         const uint32_t in_tile = min(kTileCand, sg.n - tl.first);
         const uint64_t base = sg.off + tl.first;
         for (uint32_t p = threadIdx.x; p < in_tile; p += blockDim.x) {
@@ -462,23 +452,20 @@ bool batch_invert_wanted(const DataView &dv, uint64_t n_candidates) {
 // The pair lists live in the tournament buffers, which are idle until the distances exist:
 // keys_a: pair_rq (8 B x pairs); keys_b: pair_pos (4 B x pairs).  The counters are caller-provided scratch.
 template <int METRIC>
-static int launch_inverted(const DataView &dv, uint32_t /*n_queries*/, const uint8_t *d_qvecs, uint64_t qstride,
-                            const float *d_qhdrs, const Seg *d_segs, const BTile *d_tiles, uint32_t n_tiles,
-                            const uint32_t *d_ids, uint64_t n_pairs, float *d_dist, uint64_t *d_keys_a, uint64_t *d_keys_b,
-                            uint32_t *d_counters, uint32_t *d_err, hipStream_t s) {
-    uint64_t *pair_rq = d_keys_a;
-    uint32_t *pair_pos = reinterpret_cast<uint32_t *>(d_keys_b);
-    uint32_t *count = d_counters;
+static int launch_inverted(const DataView &dv, const RerankBufs &b, uint64_t n_pairs, hipStream_t s) {
+    uint64_t *pair_rq = b.d_keys_a;
+    uint32_t *pair_pos = reinterpret_cast<uint32_t *>(b.d_keys_b);
+    uint32_t *count = b.d_inv_counters;
     const uint32_t n_sums = (uint32_t)((dv.n + kScanItems - 1) / kScanItems);
     uint32_t *sums = count + dv.n;
     uint32_t *total = sums + n_sums;  // valid pairs, known to the device only
-    const unsigned grid = n_tiles < 4096u ? n_tiles : 4096u;
+    const unsigned grid = b.n_tiles < 4096u ? b.n_tiles : 4096u;
     AH_HIP(hipMemsetAsync(count, 0, (size_t)dv.n * 4, s));
-    hipLaunchKernelGGL(k_inv_count, dim3(grid), dim3(kBlock), 0, s, dv, d_segs, d_tiles, n_tiles, d_ids, count, d_dist, d_err);
+    hipLaunchKernelGGL(k_inv_count, dim3(grid), dim3(kBlock), 0, s, dv, b.d_segs, b.d_tiles, b.n_tiles, b.d_ids, count, b.d_dist, b.d_err);
     hipLaunchKernelGGL(k_scan_block, dim3(n_sums), dim3(256), 0, s, count, dv.n, sums);
     hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(256), 0, s, sums, n_sums, total);
     hipLaunchKernelGGL(k_scan_add, dim3(n_sums), dim3(256), 0, s, count, dv.n, sums);
-    hipLaunchKernelGGL(k_inv_scatter, dim3(grid), dim3(kBlock), 0, s, dv, d_segs, d_tiles, n_tiles, d_ids, count, pair_rq,
+    hipLaunchKernelGGL(k_inv_scatter, dim3(grid), dim3(kBlock), 0, s, dv, b.d_segs, b.d_tiles, b.n_tiles, b.d_ids, count, pair_rq,
                        pair_pos);
     // row-run items pay one row operand + kRunGroup query operands each; with < 3 pairs per row most items are short and
     // the plain pair-per-slot kernel moves fewer operands through L1
@@ -494,8 +481,8 @@ static int launch_inverted(const DataView &dv, uint32_t /*n_queries*/, const uin
         hipLaunchKernelGGL(k_inv_item_fill, dim3(rgrid), dim3(256), 0, s, count, dv.n, icount, items);
         const uint64_t max_items = n_pairs / kRunGroup + std::min<uint64_t>(dv.n, n_pairs);
         const unsigned igrid = (unsigned)std::min<uint64_t>((max_items + kBlock / 8 - 1) / (kBlock / 8), 32768);
-        hipLaunchKernelGGL((k_pairs_distances_runs<METRIC>), dim3(igrid), dim3(kBlock), 0, s, dv, d_qvecs, qstride, d_qhdrs,
-                           pair_rq, pair_pos, items, itotal, d_dist);
+        hipLaunchKernelGGL((k_pairs_distances_runs<METRIC>), dim3(igrid), dim3(kBlock), 0, s, dv, b.d_qvecs, b.qstride, b.d_qhdrs,
+                           pair_rq, pair_pos, items, itotal, b.d_dist);
         AH_HIP(hipGetLastError());
         return AH_OK;
     }
@@ -503,14 +490,14 @@ static int launch_inverted(const DataView &dv, uint32_t /*n_queries*/, const uin
     const uint64_t octets = (n_pairs + group - 1) / group;
     const unsigned pgrid = (unsigned)std::min<uint64_t>((octets + kBlock / 8 - 1) / (kBlock / 8), 32768);
     if (group == 8)
-        hipLaunchKernelGGL((k_pairs_distances<METRIC, 8>), dim3(pgrid), dim3(kBlock), 0, s, dv, d_qvecs, qstride, d_qhdrs,
-                           pair_rq, pair_pos, total, d_dist);
+        hipLaunchKernelGGL((k_pairs_distances<METRIC, 8>), dim3(pgrid), dim3(kBlock), 0, s, dv, b.d_qvecs, b.qstride, b.d_qhdrs,
+                           pair_rq, pair_pos, total, b.d_dist);
     else if (group == 2)
-        hipLaunchKernelGGL((k_pairs_distances<METRIC, 2>), dim3(pgrid), dim3(kBlock), 0, s, dv, d_qvecs, qstride, d_qhdrs,
-                           pair_rq, pair_pos, total, d_dist);
+        hipLaunchKernelGGL((k_pairs_distances<METRIC, 2>), dim3(pgrid), dim3(kBlock), 0, s, dv, b.d_qvecs, b.qstride, b.d_qhdrs,
+                           pair_rq, pair_pos, total, b.d_dist);
     else
-        hipLaunchKernelGGL((k_pairs_distances<METRIC, kPairGroup>), dim3(pgrid), dim3(kBlock), 0, s, dv, d_qvecs, qstride,
-                           d_qhdrs, pair_rq, pair_pos, total, d_dist);
+        hipLaunchKernelGGL((k_pairs_distances<METRIC, kPairGroup>), dim3(pgrid), dim3(kBlock), 0, s, dv, b.d_qvecs, b.qstride,
+                           b.d_qhdrs, pair_rq, pair_pos, total, b.d_dist);
     AH_HIP(hipGetLastError());
     return AH_OK;
 }
@@ -600,14 +587,14 @@ __device__ __forceinline__ uint64_t select_key(const float *__restrict__ dist, c
     }
     return ((uint64_t)ok << 32) | (uint64_t)g;
 }
-__global__ __launch_bounds__(kBlock) void k_batch_topk_select(const Seg *__restrict__ segs, const float *__restrict__ dist,
+__global__ __launch_bounds__(kBlock) void k_batch_topk_select(const RerankSeg *__restrict__ segs, const float *__restrict__ dist,
                                                               const uint32_t *__restrict__ ids, uint64_t *keys_a,
                                                               uint64_t *keys_b, uint64_t kstride) {
     __shared__ uint32_t s_hist[kSelBins];
     __shared__ uint64_t s_cand[kSelCap];
     __shared__ uint32_t s_min, s_max, s_wave[kBlock / 64], s_bin, s_count, s_n, s_skip_end, s_skippable;
     const uint32_t q = blockIdx.x;
-    const Seg sg = segs[q];
+    const RerankSeg sg = segs[q];
     uint64_t *flag = keys_b + (uint64_t)q * kstride + (kstride - 1);
     if (sg.k == 0) {
         if (threadIdx.x == 0) *flag = 0;
@@ -744,13 +731,13 @@ __global__ __launch_bounds__(kBlock) void k_batch_topk_select(const Seg *__restr
 }
 
 // round r reads buffer (r odd ? B : A) ... round 0 reads the distances; it writes buffer (r even ? A : B).
-__global__ __launch_bounds__(kBlock) void k_batch_topk_round(const Seg *__restrict__ segs, uint32_t round,
+__global__ __launch_bounds__(kBlock) void k_batch_topk_round(const RerankSeg *__restrict__ segs, uint32_t round,
                                                              const float *__restrict__ dist,
                                                              const uint32_t *__restrict__ ids, uint64_t *keys_a,
                                                              uint64_t *keys_b, uint64_t kstride) {
     __shared__ uint64_t s[kChunk];
     const uint32_t q = blockIdx.y, c = blockIdx.x;
-    const Seg sg = segs[q];
+    const RerankSeg sg = segs[q];
     if (sg.k == 0) return;
     const uint64_t flag = keys_b[(uint64_t)q * kstride + (kstride - 1)];
     if (flag == 0) return;  // k_batch_topk_select served this query
@@ -773,13 +760,13 @@ __global__ __launch_bounds__(kBlock) void k_batch_topk_round(const Seg *__restri
     for (uint32_t t = threadIdx.x; t < keep; t += blockDim.x) dst[(uint64_t)c * keep + t] = s[t];
 }
 
-__global__ void k_batch_topk_emit(DataView dv, const Seg *__restrict__ segs, const float *__restrict__ dist,
+__global__ void k_batch_topk_emit(DataView dv, const RerankSeg *__restrict__ segs, const float *__restrict__ dist,
                                   const uint32_t *__restrict__ ids, const uint64_t *keys_a, const uint64_t *keys_b,
                                   uint64_t kstride, uint32_t k_out, uint32_t *out_ids, float *out_dist) {
     const uint32_t q = blockIdx.y;
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= k_out) return;
-    const Seg sg = segs[q];
+    const RerankSeg sg = segs[q];
     uint32_t id = 0xFFFFFFFFu;
     float d = __uint_as_float(0xFFFFFFFFu);  // NaN padding
     if (t < sg.k) {
@@ -794,7 +781,7 @@ __global__ void k_batch_topk_emit(DataView dv, const Seg *__restrict__ segs, con
 }
 
 // ---- host driver --------------------------------------------------------------------------------------
-// All device pointers are caller-carved scratch.  `h_segs` / `h_tiles` are host arrays already filled.
+// All device pointers are caller-carved scratch (common.h: RerankBufs).
 size_t batch_key_stride(uint32_t max_n) { return (size_t)((max_n + kChunk - 1) / kChunk) * kChunk; }
 uint32_t batch_tile_candidates() { return kTileCand; }
 bool batch_supported(uint32_t k) { return k <= kChunk / 2; }
@@ -809,40 +796,25 @@ int launch_prepare_queries_only(const DataView &dv, const float *d_q_f32, uint32
 }
 
 // distances + tournament top-k + emit for queries whose leaves (qvecs / qhdrs) are already on the device
-int launch_rerank_batch_prepared(const DataView &dv, uint32_t n_queries, const uint8_t *d_qvecs, uint64_t qstride,
-                                 const float *d_qhdrs, const void *d_segs_v, const void *d_tiles_v, uint32_t n_tiles,
-                                 const uint32_t *d_ids, float *d_dist, uint64_t *d_keys_a, uint64_t *d_keys_b,
-                                 uint64_t kstride, uint32_t max_n, uint32_t k_out, uint32_t max_rounds,
-                                 uint32_t *d_out_ids, float *d_out_dist, uint32_t *d_err, hipStream_t s,
-                                 uint64_t n_candidates, uint32_t *d_inv_counters) {
-    const Seg *d_segs = reinterpret_cast<const Seg *>(d_segs_v);
-    const BTile *d_tiles = reinterpret_cast<const BTile *>(d_tiles_v);
+int launch_rerank_batch_prepared(const DataView &dv, const RerankBufs &b, uint32_t max_n, uint32_t k_out, uint32_t max_rounds,
+                                 uint64_t n_candidates, hipStream_t s) {
+    const uint32_t n_queries = b.n_queries, n_tiles = b.n_tiles;
     if (n_tiles) {
         const unsigned grid = n_tiles < 4096u ? n_tiles : 4096u;
-        const bool invert = d_inv_counters != nullptr && batch_invert_wanted(dv, n_candidates);
-        if (invert) {
+        if (b.d_inv_counters != nullptr && batch_invert_wanted(dv, n_candidates)) {  // row-major
             switch (dv.metric) {
-            case AH_EUCLIDEAN:
-                AH_TRY(launch_inverted<AH_EUCLIDEAN>(dv, n_queries, d_qvecs, qstride, d_qhdrs, d_segs, d_tiles, n_tiles, d_ids,
-                                              n_candidates, d_dist, d_keys_a, d_keys_b, d_inv_counters, d_err, s));
-                break;
-            case AH_COSINE:
-                AH_TRY(launch_inverted<AH_COSINE>(dv, n_queries, d_qvecs, qstride, d_qhdrs, d_segs, d_tiles, n_tiles, d_ids,
-                                           n_candidates, d_dist, d_keys_a, d_keys_b, d_inv_counters, d_err, s));
-                break;
-            default:
-                AH_TRY(launch_inverted<AH_DOT_PRODUCT>(dv, n_queries, d_qvecs, qstride, d_qhdrs, d_segs, d_tiles, n_tiles, d_ids,
-                                                n_candidates, d_dist, d_keys_a, d_keys_b, d_inv_counters, d_err, s));
-                break;
+            case AH_EUCLIDEAN: AH_TRY(launch_inverted<AH_EUCLIDEAN>(dv, b, n_candidates, s)); break;
+            case AH_COSINE: AH_TRY(launch_inverted<AH_COSINE>(dv, b, n_candidates, s)); break;
+            default: AH_TRY(launch_inverted<AH_DOT_PRODUCT>(dv, b, n_candidates, s)); break;
             }
         } else if (metric_is_bq(dv.metric)) {
-            hipLaunchKernelGGL(k_batch_distances_bq, dim3(grid), dim3(kBlock), dv.pitch * 8, s, dv, d_qvecs, qstride,
-                               d_qhdrs, d_segs, d_tiles, n_tiles, d_ids, d_dist, d_err);
+            hipLaunchKernelGGL(k_batch_distances_bq, dim3(grid), dim3(kBlock), dv.pitch * 8, s, dv, b.d_qvecs, b.qstride, b.d_qhdrs,
+                               b.d_segs, b.d_tiles, n_tiles, b.d_ids, b.d_dist, b.d_err);
         } else {
             const size_t sh = (size_t)dv.pitch * 4;
-#define AH_LAUNCH(M)                                                                                          \
-    hipLaunchKernelGGL((k_batch_distances_f32<M>), dim3(grid), dim3(kBlock), sh, s, dv, d_qvecs, qstride,      \
-                       d_qhdrs, d_segs, d_tiles, n_tiles, d_ids, d_dist, d_err)
+#define AH_LAUNCH(M)                                                                                               \
+    hipLaunchKernelGGL((k_batch_distances_f32<M>), dim3(grid), dim3(kBlock), sh, s, dv, b.d_qvecs, b.qstride, b.d_qhdrs, \
+                       b.d_segs, b.d_tiles, n_tiles, b.d_ids, b.d_dist, b.d_err)
             switch (dv.metric) {
             case AH_EUCLIDEAN: AH_LAUNCH(AH_EUCLIDEAN); break;
             case AH_MANHATTAN: AH_LAUNCH(AH_MANHATTAN); break;
@@ -851,32 +823,26 @@ int launch_rerank_batch_prepared(const DataView &dv, uint32_t n_queries, const u
             }
 #undef AH_LAUNCH
         }
-        hipLaunchKernelGGL(k_batch_topk_select, dim3(n_queries), dim3(kBlock), 0, s, d_segs, d_dist, d_ids, d_keys_a, d_keys_b,
-                           kstride);
-        const uint32_t max_blocks = (max_n + kChunk - 1) / kChunk;
-        uint32_t blocks_bound = max_blocks;
+        hipLaunchKernelGGL(k_batch_topk_select, dim3(n_queries), dim3(kBlock), 0, s, b.d_segs, b.d_dist, b.d_ids, b.d_keys_a,
+                           b.d_keys_b, b.kstride);
+        uint32_t blocks_bound = (max_n + kChunk - 1) / kChunk;
         for (uint32_t r = 0; r < max_rounds; r++) {
-            hipLaunchKernelGGL(k_batch_topk_round, dim3(blocks_bound, n_queries), dim3(kBlock), 0, s, d_segs, r, d_dist,
-                               d_ids, d_keys_a, d_keys_b, kstride);
+            hipLaunchKernelGGL(k_batch_topk_round, dim3(blocks_bound, n_queries), dim3(kBlock), 0, s, b.d_segs, r, b.d_dist, b.d_ids,
+                               b.d_keys_a, b.d_keys_b, b.kstride);
             blocks_bound = (blocks_bound * (kChunk / 2) + kChunk - 1) / kChunk;  // every round at least halves
             if (blocks_bound < 1) blocks_bound = 1;
         }
     }
-    hipLaunchKernelGGL(k_batch_topk_emit, dim3((k_out + 255) / 256, n_queries), dim3(256), 0, s, dv, d_segs, d_dist,
-                       d_ids, d_keys_a, d_keys_b, kstride, k_out, d_out_ids, d_out_dist);
+    hipLaunchKernelGGL(k_batch_topk_emit, dim3((k_out + 255) / 256, n_queries), dim3(256), 0, s, dv, b.d_segs, b.d_dist, b.d_ids,
+                       b.d_keys_a, b.d_keys_b, b.kstride, k_out, b.d_out_ids, b.d_out_dist);
     AH_HIP(hipGetLastError());
     return AH_OK;
 }
 
-int launch_rerank_batch(const DataView &dv, const float *d_q_f32, uint32_t n_queries, uint8_t *d_qvecs, uint64_t qstride,
-                        float *d_qhdrs, const void *d_segs_v, const void *d_tiles_v, uint32_t n_tiles,
-                        const uint32_t *d_ids, float *d_dist, uint64_t *d_keys_a, uint64_t *d_keys_b, uint64_t kstride,
-                        uint32_t max_n, uint32_t k_out, uint32_t max_rounds, uint32_t *d_out_ids, float *d_out_dist,
-                        uint32_t *d_err, hipStream_t s, uint64_t n_candidates, uint32_t *d_inv_counters) {
-    AH_TRY(launch_prepare_queries_only(dv, d_q_f32, n_queries, d_qvecs, qstride, d_qhdrs, s));
-    return launch_rerank_batch_prepared(dv, n_queries, d_qvecs, qstride, d_qhdrs, d_segs_v, d_tiles_v, n_tiles, d_ids,
-                                        d_dist, d_keys_a, d_keys_b, kstride, max_n, k_out, max_rounds, d_out_ids,
-                                        d_out_dist, d_err, s, n_candidates, d_inv_counters);
+int launch_rerank_batch(const DataView &dv, const RerankBufs &b, uint32_t max_n, uint32_t k_out, uint32_t max_rounds,
+                        uint64_t n_candidates, hipStream_t s) {
+    AH_TRY(launch_prepare_queries_only(dv, b.d_q_f32, b.n_queries, b.d_qvecs, b.qstride, b.d_qhdrs, s));
+    return launch_rerank_batch_prepared(dv, b, max_n, k_out, max_rounds, n_candidates, s);
 }
 
 uint32_t batch_rounds(uint32_t n, uint32_t k) { return (n == 0 || k == 0) ? 0u : tour_rounds(n, k); }

@@ -18,6 +18,7 @@
 
 #include "../../include/arroy_hip.h"
 #include "../../include/arroy_hip_policy.h"
+#include "rerank_workspace.h"
 
 namespace ah {
 
@@ -602,20 +603,50 @@ size_t batch_key_stride(uint32_t max_n);
 uint32_t batch_tile_candidates();
 bool batch_supported(uint32_t k);
 uint32_t batch_rounds(uint32_t n, uint32_t k);
-int launch_rerank_batch(const DataView &dv, const float *d_q_f32, uint32_t n_queries, uint8_t *d_qvecs, uint64_t qstride,
-                        float *d_qhdrs, const void *d_segs, const void *d_tiles, uint32_t n_tiles, const uint32_t *d_ids,
-                        float *d_dist, uint64_t *d_keys_a, uint64_t *d_keys_b, uint64_t kstride, uint32_t max_n,
-                        uint32_t k_out, uint32_t max_rounds, uint32_t *d_out_ids, float *d_out_dist, uint32_t *d_err,
-                        hipStream_t s, uint64_t n_candidates, uint32_t *d_inv_counters);
+// One query's slice of the concatenated candidate list of a batched re-rank (ah_rerank_batch: ids[off, off + n); step 4 of
+// ah_search_batch: the query's row of the candidate matrix), and one block's share of such a list: the host fills them, the
+// kernels of batch.hip and search.hip read them.
+struct RerankSeg {
+    uint64_t off;    // first candidate
+    uint32_t n, k;   // candidates; min(count, n)
+};
+struct RerankTile {         // batch_tile_candidates() candidates of one list
+    uint32_t query, first;  // first: offset inside the query's candidate list
+};
+static_assert(sizeof(RerankSeg) == 16 && sizeof(RerankTile) == 8, "the kernels index arrays of these");
+
+// The device buffers of one sub-batch of a batched re-rank, all caller-carved scratch (rerank_workspace.h has the layout of
+// ah_rerank_batch's; search_chunk fills one from its own scratch).  The launchers below take what they need from it.
+struct RerankBufs {
+    float *d_q_f32;    // the queries as the caller gave them (launch_rerank_batch prepares them; null where they already are)
+    uint8_t *d_qvecs;  // the prepared queries: a leaf of `qstride` bytes and two header floats each
+    float *d_qhdrs;
+    uint64_t qstride;
+    uint32_t n_queries, n_tiles;
+    RerankSeg *d_segs;  // one per query
+    RerankTile *d_tiles;
+    uint32_t *d_ids;  // the concatenated candidate lists, and a distance for each
+    float *d_dist;
+    uint64_t *d_keys_a, *d_keys_b, kstride;  // the tournament's keys, `kstride` per query
+    uint32_t *d_out_ids;  // n_queries x k_out, and their distances
+    float *d_out_dist;
+    uint32_t *d_err;           // 16 words: [error bits][counters of the screened selection]
+    uint32_t *d_inv_counters;  // the row-major re-rank's counters (null: not reserved)
+    // scratch of the certified screen (null without that stage): nq x hpitch halves, nq float4, (Cosine) a float per candidate;
+    // nq x 2 x pitch8 int8 digits, nq float4, a float per candidate
+    uint16_t *d_q16;
+    int8_t *d_q8;
+    float4 *d_qstats, *d_q8stats;
+    float *d_aux, *d_aux8;
+};
 
 int launch_prepare_queries_only(const DataView &dv, const float *d_q_f32, uint32_t n_queries, uint8_t *d_qvecs,
                                 uint64_t qstride, float *d_qhdrs, hipStream_t s);
-int launch_rerank_batch_prepared(const DataView &dv, uint32_t n_queries, const uint8_t *d_qvecs, uint64_t qstride,
-                                 const float *d_qhdrs, const void *d_segs, const void *d_tiles, uint32_t n_tiles,
-                                 const uint32_t *d_ids, float *d_dist, uint64_t *d_keys_a, uint64_t *d_keys_b,
-                                 uint64_t kstride, uint32_t max_n, uint32_t k_out, uint32_t max_rounds,
-                                 uint32_t *d_out_ids, float *d_out_dist, uint32_t *d_err, hipStream_t s,
-                                 uint64_t n_candidates, uint32_t *d_inv_counters);
+// distances + top-k + emit for queries whose leaves are already on the device; launch_rerank_batch prepares them first
+int launch_rerank_batch_prepared(const DataView &dv, const RerankBufs &b, uint32_t max_n, uint32_t k_out, uint32_t max_rounds,
+                                 uint64_t n_candidates, hipStream_t s);
+int launch_rerank_batch(const DataView &dv, const RerankBufs &b, uint32_t max_n, uint32_t k_out, uint32_t max_rounds,
+                        uint64_t n_candidates, hipStream_t s);
 // row-major ("inverted") re-rank of big submissions: policy + the counter scratch it needs (see batch.hip)
 bool batch_invert_wanted(const DataView &dv, uint64_t n_candidates);
 size_t batch_invert_counter_bytes(uint64_t n_rows, uint64_t n_candidates);
@@ -631,11 +662,9 @@ bool ensure_screen8_search(ah_dataset *ds, hipStream_t s);
 // search.hip: the certified top-k screen for the candidate lists of ah_rerank_batch (binary16 rows first, f32 for the survivors)
 // (tile_first .. tile_first + n_tiles: the tiles this call screens — the caller may launch the lists group by group while the
 // ids of the next group are still on their way; select = also run the per-query selection, i.e. this was the last group)
-int launch_rerank_screened(ah_dataset *ds, uint32_t nq, const uint8_t *d_qvecs, uint64_t qstride, const float *d_qhdrs,
-                           const void *d_segs, const void *d_tiles, uint32_t tile_first, uint32_t n_tiles, uint32_t tile_candidates,
-                           const uint32_t *d_ids, float *d_dist, float *d_aux, uint16_t *d_q16, float4 *d_qstats, uint32_t k_out,
-                           uint32_t *d_out_ids, float *d_out_dist, uint32_t *d_err, hipStream_t s, bool first, bool select,
-                           int8_t *d_q8 = nullptr, float4 *d_q8stats = nullptr, float *d_aux8 = nullptr);
+// (int8: start on the int8 copy of the rows — the caller has made sure it exists, ensure_screen8_search)
+int launch_rerank_screened(ah_dataset *ds, const RerankBufs &b, uint32_t tile_first, uint32_t n_tiles, uint32_t k_out, bool first,
+                           bool select, bool int8, hipStream_t s);
 
 // split.hip
 int launch_split_sides(const DataView &dv, const void *d_nvec, const float *d_nhdr, const uint32_t *d_ids, uint64_t n,

@@ -2333,13 +2333,6 @@ __global__ __launch_bounds__(256) void k_leaf_tiles(DataView dv, const uint32_t 
 // candidates within 2 E of them) are evaluated in the reference's f32 arithmetic, from their f32 rows, and ordered by
 // (OrderedFloat(d), id): the same bits as the unscreened path, by construction and by test (every search test runs both).
 // A non-finite screen value, or more survivors than the selection holds, sends the submission to the exact paths.
-struct PairSeg {   // candidate list of one query of ah_rerank_batch: ids[off, off + n), k = min(count, n)  (api.hip: HostSeg)
-    uint64_t off;
-    uint32_t n, k;
-};
-struct PairTile {  // kPairTile candidates of one list, starting at `first`  (api.hip: HostTile)
-    uint32_t query, first;
-};
 struct ScreenSearch {
     const uint16_t *rows16;     // n x hpitch halves (ah_dataset::d_rows_h16)
     float4 max_stats;           // component-wise maximum over the rows of {|x~|, |x - x~|, |x|}, rounded up: the bound built
@@ -2737,12 +2730,12 @@ __global__ __launch_bounds__(256) void k_leaf_tiles8(DataView dv, ScreenSearch s
 
 // Screen values of the candidate lists of ah_rerank_batch: one block per tile of a list, the query's binary16 copy in LDS, one
 // octet per candidate gathers its binary16 row (2 x dims bytes instead of the 4 x dims of k_batch_distances_f32).
-__global__ __launch_bounds__(256) void k_pairs_screen16(DataView dv, ScreenSearch ss, const PairSeg *__restrict__ segs,
-                                                        const PairTile *__restrict__ tiles, uint32_t tile_candidates,
+__global__ __launch_bounds__(256) void k_pairs_screen16(DataView dv, ScreenSearch ss, const RerankSeg *__restrict__ segs,
+                                                        const RerankTile *__restrict__ tiles, uint32_t tile_candidates,
                                                         const uint32_t *__restrict__ ids, float *__restrict__ dist, uint32_t *err) {
     extern __shared__ uint4 s_q4[];  // hpitch / 8
-    const PairTile tl = tiles[blockIdx.x];
-    const PairSeg seg = segs[tl.query];
+    const RerankTile tl = tiles[blockIdx.x];
+    const RerankSeg seg = segs[tl.query];
     const uint4 *g_q4 = reinterpret_cast<const uint4 *>(ss.q16 + (uint64_t)tl.query * ss.hpitch);
     for (uint32_t i = threadIdx.x; i < (ss.hpitch >> 3); i += blockDim.x) s_q4[i] = g_q4[i];
     __syncthreads();
@@ -2778,12 +2771,12 @@ __global__ __launch_bounds__(256) void k_pairs_screen16(DataView dv, ScreenSearc
 
 // The same on the int8 copy of the rows (round 6): the query's two int8 digits in LDS, one octet per candidate gathers
 // pitch8 bytes — the row's scale travels with the value (aux8) for the candidate's own error bound.
-__global__ __launch_bounds__(256) void k_pairs_screen8(DataView dv, ScreenSearch ss, const PairSeg *__restrict__ segs,
-                                                       const PairTile *__restrict__ tiles, uint32_t tile_candidates,
+__global__ __launch_bounds__(256) void k_pairs_screen8(DataView dv, ScreenSearch ss, const RerankSeg *__restrict__ segs,
+                                                       const RerankTile *__restrict__ tiles, uint32_t tile_candidates,
                                                        const uint32_t *__restrict__ ids, float *__restrict__ dist, uint32_t *err) {
     extern __shared__ uint4 s_q4[];  // 2 x pitch8 / 16: hi digits, lo digits
-    const PairTile tl = tiles[blockIdx.x];
-    const PairSeg seg = segs[tl.query];
+    const RerankTile tl = tiles[blockIdx.x];
+    const RerankSeg seg = segs[tl.query];
     const uint4 *g_q4 = reinterpret_cast<const uint4 *>(ss.q8 + (uint64_t)tl.query * 2 * ss.pitch8);
     for (uint32_t i = threadIdx.x; i < (ss.pitch8 >> 3); i += blockDim.x) s_q4[i] = g_q4[i];
     __syncthreads();
@@ -2866,7 +2859,7 @@ __device__ __forceinline__ void search_select_screened_body(DataView dv, ScreenS
                                                                  const uint8_t *__restrict__ qvecs, uint64_t qstride,
                                                                  const float *__restrict__ qhdrs,
                                                                  uint32_t *__restrict__ out_ids, float *__restrict__ out_dist,
-                                                                 uint32_t *err, const PairSeg *__restrict__ segs,
+                                                                 uint32_t *err, const RerankSeg *__restrict__ segs,
                                                                  uint32_t flag_words, uint32_t id_limit,
                                                                  uint32_t *__restrict__ unique_out, uint32_t *__restrict__ trace = nullptr,
                                                                  const uint32_t *__restrict__ count_of = nullptr) {
@@ -3148,7 +3141,7 @@ __global__ __launch_bounds__(1024) void k_search_select_screened(DataView dv, Sc
                                                                  const uint8_t *__restrict__ qvecs, uint64_t qstride,
                                                                  const float *__restrict__ qhdrs,
                                                                  uint32_t *__restrict__ out_ids, float *__restrict__ out_dist,
-                                                                 uint32_t *err, const PairSeg *__restrict__ segs,
+                                                                 uint32_t *err, const RerankSeg *__restrict__ segs,
                                                                  uint32_t flag_words = 0, uint32_t id_limit = 0,
                                                                  uint32_t *__restrict__ unique_out = nullptr,
                                                                  uint32_t *__restrict__ host_status = nullptr,
@@ -3192,7 +3185,7 @@ __global__ __launch_bounds__(1024) void k_search_select_screened(DataView dv, Sc
 template <int METRIC>
 __global__ __launch_bounds__(256) void k_screen_verify(DataView dv, ScreenSearch ss, const uint32_t *__restrict__ nns,
                                                        const float *__restrict__ dist_all, uint32_t stride,
-                                                       const uint32_t *__restrict__ counts, const PairSeg *__restrict__ segs,
+                                                       const uint32_t *__restrict__ counts, const RerankSeg *__restrict__ segs,
                                                        const uint8_t *__restrict__ qvecs, uint64_t qstride,
                                                        const float *__restrict__ qhdrs, unsigned long long *__restrict__ out) {
     extern __shared__ float4 s_qf4[];  // the query leaf in f32 (row pitch)
@@ -3238,7 +3231,7 @@ __global__ __launch_bounds__(256) void k_screen_verify(DataView dv, ScreenSearch
 // Launches k_screen_verify over a screened submission when AH_SCREEN_VERIFY is 1 (otherwise nothing).  The counters live in
 // the dataset (ah_debug_query_screen_verify) and are made by the first verified submission.
 static int launch_screen_verify(ah_dataset *ds, const ScreenSearch &ss, const uint32_t *nns, const float *dist, uint32_t stride,
-                                const uint32_t *counts, const PairSeg *segs, uint32_t nq, const uint8_t *qvecs, uint64_t qstride,
+                                const uint32_t *counts, const RerankSeg *segs, uint32_t nq, const uint8_t *qvecs, uint64_t qstride,
                                 const float *qhdrs, hipStream_t s) {
     if (tun(TUN_SCREEN_VERIFY) == 0 || nq == 0) return AH_OK;
     unsigned long long *ctr = nullptr;
@@ -3857,57 +3850,53 @@ __global__ void k_unpack_normals(const uint8_t *__restrict__ recs, const uint64_
         headers[(uint64_t)r * hf + threadIdx.x] = reinterpret_cast<const float *>(recs + offsets[r] + hdr_off)[threadIdx.x];
 }
 
-// The certified top-k screen for the candidate lists of ah_rerank_batch (api.hip): screen values of every (query, candidate)
-// pair from the binary16 rows, then per query the survivors in f32 and their order.  The queries are already prepared
-// (d_qvecs / d_qhdrs).  d_q16 / d_qstats / d_aux: scratch of nq x hpitch halves, nq float4, and (Cosine) one float per candidate.
-// err bits as k_search_select_screened: the caller redoes the submission on the exact path when 4 or 8 is raised.
-int launch_rerank_screened(ah_dataset *ds, uint32_t nq, const uint8_t *d_qvecs, uint64_t qstride, const float *d_qhdrs,
-                           const void *d_segs, const void *d_tiles, uint32_t tile_first, uint32_t n_tiles, uint32_t tile_candidates,
-                           const uint32_t *d_ids, float *d_dist, float *d_aux, uint16_t *d_q16, float4 *d_qstats, uint32_t k_out,
-                           uint32_t *d_out_ids, float *d_out_dist, uint32_t *d_err, hipStream_t s, bool first, bool select,
-                           int8_t *d_q8, float4 *d_q8stats, float *d_aux8) {
-    const DataView dv = ds->view();
+// The dataset's half of a ScreenSearch — the binary16 rows, their maxima and the accumulation-error factors the proof of the
+// screen rests on; with `int8`, the int8 copy of the rows as well.  The callers add their scratch.
+static ScreenSearch screen_of_dataset(const ah_dataset *ds, bool int8) {
     ScreenSearch ss{};
     ss.rows16 = ds->d_rows_h16;
     ss.max_stats = make_float4(ds->screen_max[0], ds->screen_max[1], ds->screen_max[2], 0.0f);
-    ss.aux = ds->metric == AH_COSINE ? d_aux : nullptr;
     ss.hpitch = ds->hpitch;
+    // accumulation-error factors as in the forest build (forest.hip: build_batch), 4x over the standard model
     ss.gamma_s = (float)(4.0 * (2.0 * (ds->hpitch / 16) + 8.0) * 5.9604645e-8);
     ss.gamma_r = (float)(4.0 * ((double)(ds->dims / 32) + 6.0 + 62.0) * 5.9604645e-8);
-    ss.q16 = d_q16;
-    ss.qstats = d_qstats;
-    if (d_q8) {  // the int8 copy of the rows first (the caller has made sure it exists: ensure_screen8_search)
+    if (int8) {
         ss.rows8 = ds->d_rows_i8;
         ss.row_scale8 = ds->d_scale8_rows;
         ss.dim_scale = ds->d_dim_scale;
         ss.pitch8 = ds->pitch8;
         ss.max8 = make_float4(ds->screen8_max[0], ds->screen8_max[1], ds->screen8_max[2], 0.0f);
-        ss.q8 = d_q8;
-        ss.q8stats = d_q8stats;
-        ss.aux8 = d_aux8;
-        ss.qstats = nullptr;  // (every candidate of a list is screened on the int8 rows: no binary16 copy of the queries is made)
-        if (first) hipLaunchKernelGGL(k_queries_i8, dim3(nq), dim3(64), 0, s, d_qvecs, qstride, ds->dims, ss);
-        const size_t sh8 = (size_t)ds->pitch8 * 2;
-        if (sh8 > 48 * 1024)
-            AH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_pairs_screen8), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh8));
-        if (n_tiles)
-            hipLaunchKernelGGL(k_pairs_screen8, dim3(n_tiles), dim3(256), sh8, s, dv, ss, reinterpret_cast<const PairSeg *>(d_segs),
-                               reinterpret_cast<const PairTile *>(d_tiles) + tile_first, tile_candidates, d_ids, d_dist, d_err);
-    } else {
-        if (first) hipLaunchKernelGGL(k_queries_h16, dim3(nq), dim3(64), 0, s, d_qvecs, qstride, ds->dims, ds->hpitch, d_q16, d_qstats);
-        const size_t sh = (size_t)ds->hpitch * 2;
-        if (sh > 48 * 1024)
-            AH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_pairs_screen16), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
-        if (n_tiles)
-            hipLaunchKernelGGL(k_pairs_screen16, dim3(n_tiles), dim3(256), sh, s, dv, ss, reinterpret_cast<const PairSeg *>(d_segs),
-                               reinterpret_cast<const PairTile *>(d_tiles) + tile_first, tile_candidates, d_ids, d_dist, d_err);
     }
+    return ss;
+}
+
+// The certified top-k screen for the candidate lists of ah_rerank_batch (api.hip): screen values of every (query, candidate)
+// pair from the binary16 rows (`int8`: from the int8 rows), then per query the survivors in f32 and their order.  The queries
+// are already prepared (b.d_qvecs / b.d_qhdrs).
+// err bits as k_search_select_screened: the caller redoes the submission on the exact path when 4 or 8 is raised.
+int launch_rerank_screened(ah_dataset *ds, const RerankBufs &b, uint32_t tile_first, uint32_t n_tiles, uint32_t k_out, bool first,
+                           bool select, bool int8, hipStream_t s) {
+    const DataView dv = ds->view();
+    const uint32_t nq = b.n_queries, tile_candidates = batch_tile_candidates();
+    ScreenSearch ss = screen_of_dataset(ds, int8);
+    ss.aux = ds->metric == AH_COSINE ? b.d_aux : nullptr;
+    ss.q16 = b.d_q16;
+    ss.qstats = int8 ? nullptr : b.d_qstats;  // (int8: every candidate of a list is screened on those rows, no binary16 copy of the queries is made)
+    if (int8) ss.q8 = b.d_q8, ss.q8stats = b.d_q8stats, ss.aux8 = b.d_aux8;
+    if (first && int8) hipLaunchKernelGGL(k_queries_i8, dim3(nq), dim3(64), 0, s, b.d_qvecs, b.qstride, ds->dims, ss);
+    if (first && !int8) hipLaunchKernelGGL(k_queries_h16, dim3(nq), dim3(64), 0, s, b.d_qvecs, b.qstride, ds->dims, ds->hpitch, b.d_q16, b.d_qstats);
+    const auto k_pairs_screen = int8 ? k_pairs_screen8 : k_pairs_screen16;  // (the query's int8 digits / halves in LDS)
+    const size_t sh = (size_t)(int8 ? ds->pitch8 : ds->hpitch) * 2;
+    if (sh > 48 * 1024)
+        AH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_pairs_screen), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
+    if (n_tiles)
+        hipLaunchKernelGGL(k_pairs_screen, dim3(n_tiles), dim3(256), sh, s, dv, ss, b.d_segs, b.d_tiles + tile_first, tile_candidates, b.d_ids,
+                           b.d_dist, b.d_err);
     if (!select) {
         AH_HIP(hipGetLastError());
         return AH_OK;
     }
-    AH_TRY(launch_screen_verify(ds, ss, d_ids, d_dist, 0u, nullptr, reinterpret_cast<const PairSeg *>(d_segs), nq, d_qvecs, qstride,
-                                d_qhdrs, s));
+    AH_TRY(launch_screen_verify(ds, ss, b.d_ids, b.d_dist, 0u, nullptr, b.d_segs, nq, b.d_qvecs, b.qstride, b.d_qhdrs, s));
     const size_t sel_lds = (size_t)ds->pitch * 4;
     if (sel_lds > 32 * 1024) {
         AH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_search_select_screened<AH_COSINE>),
@@ -3915,14 +3904,14 @@ int launch_rerank_screened(ah_dataset *ds, uint32_t nq, const uint8_t *d_qvecs, 
         AH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_search_select_screened<AH_DOT_PRODUCT>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)sel_lds));
     }
+#define AH_LAUNCH(M)                                                                                                             \
+    hipLaunchKernelGGL((k_search_select_screened<M>), dim3(nq), dim3(1024), sel_lds, s, dv, ss, b.d_ids, b.d_dist, 0u, (const uint32_t *)nullptr, \
+                       (const uint32_t *)nullptr, k_out, b.d_qvecs, b.qstride, b.d_qhdrs, b.d_out_ids, b.d_out_dist, b.d_err, b.d_segs)
     if (ds->metric == AH_COSINE)
-        hipLaunchKernelGGL((k_search_select_screened<AH_COSINE>), dim3(nq), dim3(1024), sel_lds, s, dv, ss, d_ids, d_dist, 0u,
-                           (const uint32_t *)nullptr, (const uint32_t *)nullptr, k_out, d_qvecs, qstride, d_qhdrs, d_out_ids,
-                           d_out_dist, d_err, reinterpret_cast<const PairSeg *>(d_segs));
+        AH_LAUNCH(AH_COSINE);
     else
-        hipLaunchKernelGGL((k_search_select_screened<AH_DOT_PRODUCT>), dim3(nq), dim3(1024), sel_lds, s, dv, ss, d_ids, d_dist, 0u,
-                           (const uint32_t *)nullptr, (const uint32_t *)nullptr, k_out, d_qvecs, qstride, d_qhdrs, d_out_ids,
-                           d_out_dist, d_err, reinterpret_cast<const PairSeg *>(d_segs));
+        AH_LAUNCH(AH_DOT_PRODUCT);
+#undef AH_LAUNCH
     AH_HIP(hipGetLastError());
     return AH_OK;
 }
@@ -4168,14 +4157,6 @@ int ah_index_create_from_view(ah_dataset *ds, const ah_forest_view *view, ah_ind
     AH_GUARDED_END
 }
 
-struct HostSeg2 {
-    uint64_t off;
-    uint32_t n, k;
-};
-struct HostTile2 {
-    uint32_t query, first;
-};
-
 // A mixed sub-batch of ah_search_batch_filters: the filters of the call on the device, the slot of every query of the
 // sub-batch (host), the smallest stored share among its filters and how many of its queries have one.
 struct MixedFilters {
@@ -4239,7 +4220,7 @@ static int search_chunk(ah_index *ix, Context *ctx, const float *queries, const 
     const size_t kstride = big_k ? (topk_scratch_bytes(nns_stride, std::min<size_t>(k, nns_stride)) + 15) / 16 : batch_key_stride(nns_stride);
     const uint32_t heap_cap = ix->n_nodes + ix->n_trees + 2;
     size_t dev_bytes = pad(nq * (size_t)ds->dims * 4) + pad(nq * 4) + nq * qstride + pad(nq * 8) + pad(nq * (size_t)nns_stride * 4) * 2 +
-                       pad(nq * 4) * 3 + pad(nq * sizeof(HostSeg2)) + pad((size_t)max_tiles_bound * sizeof(HostTile2)) +
+                       pad(nq * 4) * 3 + pad(nq * sizeof(RerankSeg)) + pad((size_t)max_tiles_bound * sizeof(RerankTile)) +
                        2 * pad(nq * kstride * 8) + pad(nq * k * 4) * 2 + pad(SS_WORDS * 4) + pad(nq * 4) + 4096 + (mixed ? pad(nq * 4) : 0) +
                        (varied ? 2 * pad(nq * 4) : 0);
     // counters of the row-major re-rank, reserved when the candidate lists could be long enough for it
@@ -4285,8 +4266,8 @@ static int search_chunk(ah_index *ix, Context *ctx, const float *queries, const 
                      pad(items_cap * 4) + pad(nq * 4);
     void *const clean_status = ctx->clean_status;  // (ensure_device forgets it: see Context)
     AH_TRY(ctx->ensure_device(dev_bytes));
-    const size_t pin_bytes = pad(nq * (size_t)ds->dims * 4) + pad(nq * 4) * 4 + pad(nq * sizeof(HostSeg2)) +
-                             pad((size_t)max_tiles_bound * sizeof(HostTile2)) + pad(nq * k * 4) * 2 + 4096 + (mixed ? pad(nq * 4) : 0) + (varied ? 2 * pad(nq * 4) : 0);
+    const size_t pin_bytes = pad(nq * (size_t)ds->dims * 4) + pad(nq * 4) * 4 + pad(nq * sizeof(RerankSeg)) +
+                             pad((size_t)max_tiles_bound * sizeof(RerankTile)) + pad(nq * k * 4) * 2 + 4096 + (mixed ? pad(nq * 4) : 0) + (varied ? 2 * pad(nq * 4) : 0);
     AH_TRY(ctx->ensure_pinned(pin_bytes));
     uint8_t *dbase = reinterpret_cast<uint8_t *>(ctx->d_scratch);
     size_t doff = 0;
@@ -4311,8 +4292,8 @@ static int search_chunk(ah_index *ix, Context *ctx, const float *queries, const 
     uint32_t *d_counts = (uint32_t *)dtake(nq * 4);
     uint32_t *d_overflow = (uint32_t *)dtake(nq * 4);
     uint32_t *d_list = (uint32_t *)dtake(nq * 4);
-    HostSeg2 *d_segs = (HostSeg2 *)dtake(nq * sizeof(HostSeg2));
-    HostTile2 *d_tiles = (HostTile2 *)dtake((size_t)max_tiles_bound * sizeof(HostTile2));
+    RerankSeg *d_segs = (RerankSeg *)dtake(nq * sizeof(RerankSeg));
+    RerankTile *d_tiles = (RerankTile *)dtake((size_t)max_tiles_bound * sizeof(RerankTile));
     uint64_t *d_ka = (uint64_t *)dtake(nq * kstride * 8);
     uint64_t *d_kb = (uint64_t *)dtake(nq * kstride * 8);
     uint32_t *d_oi = (uint32_t *)dtake(nq * k * 4);
@@ -4339,22 +4320,12 @@ static int search_chunk(ah_index *ix, Context *ctx, const float *queries, const 
     }
     ScreenSearch ss{};
     if (screened) {
-        ss.rows16 = ds->d_rows_h16;
-        ss.max_stats = make_float4(ds->screen_max[0], ds->screen_max[1], ds->screen_max[2], 0.0f);
+        ss = screen_of_dataset(ds, screened8);
         ss.aux = ds->metric == AH_COSINE ? (float *)dtake(nq * (size_t)nns_stride * 4) : nullptr;
-        ss.hpitch = ds->hpitch;
-        // accumulation-error factors as in the forest build (forest.hip: build_batch), 4x over the standard model
-        ss.gamma_s = (float)(4.0 * (2.0 * (ds->hpitch / 16) + 8.0) * 5.9604645e-8);
-        ss.gamma_r = (float)(4.0 * ((double)(ds->dims / 32) + 6.0 + 62.0) * 5.9604645e-8);
         ss.q16 = (const uint16_t *)dtake(nq * (size_t)ds->hpitch * 2);
         ss.qstats = (const float4 *)dtake(nq * sizeof(float4));
     }
     if (screened8) {
-        ss.rows8 = ds->d_rows_i8;
-        ss.row_scale8 = ds->d_scale8_rows;
-        ss.dim_scale = ds->d_dim_scale;
-        ss.pitch8 = ds->pitch8;
-        ss.max8 = make_float4(ds->screen8_max[0], ds->screen8_max[1], ds->screen8_max[2], 0.0f);
         ss.q8 = (const int8_t *)dtake(nq * (size_t)ds->pitch8 * 2);
         ss.q8stats = (const float4 *)dtake(nq * sizeof(float4));
         ss.aux8 = (float *)dtake(nq * (size_t)nns_stride * 4);
@@ -4363,8 +4334,8 @@ static int search_chunk(ah_index *ix, Context *ctx, const float *queries, const 
     uint32_t *h_qrows = (uint32_t *)ptake(nq * 4);
     uint32_t *h_overflow = (uint32_t *)ptake(nq * 4);
     uint32_t *h_list = (uint32_t *)ptake(nq * 4);
-    HostSeg2 *h_segs = (HostSeg2 *)ptake(nq * sizeof(HostSeg2));
-    HostTile2 *h_tiles = (HostTile2 *)ptake((size_t)max_tiles_bound * sizeof(HostTile2));
+    RerankSeg *h_segs = (RerankSeg *)ptake(nq * sizeof(RerankSeg));
+    RerankTile *h_tiles = (RerankTile *)ptake((size_t)max_tiles_bound * sizeof(RerankTile));
     uint32_t *h_oi = (uint32_t *)ptake(nq * k * 4);
     float *h_od = (float *)ptake(nq * k * 4);
     uint32_t *h_err = (uint32_t *)ptake(SS_WORDS * 4);
@@ -4680,19 +4651,19 @@ static int search_chunk(ah_index *ix, Context *ctx, const float *queries, const 
         if (screened) AH_TRY(launch_screen_verify(ds, ss, d_nns, d_dist, nns_stride, d_counts, nullptr, (uint32_t)nq, d_qvecs, qstride, d_qhdrs, s));
         if (fused_flag && ds->metric == AH_COSINE)
             hipLaunchKernelGGL((k_search_select_screened<AH_COSINE, true>), dim3((unsigned)nq), dim3(1024), fused_lds, s, dv, ss, d_nns, d_dist,
-                               nns_stride, d_counts, d_unique, (uint32_t)k, d_qvecs, qstride, d_qhdrs, h_oi, h_od, d_err, (const PairSeg *)nullptr,
+                               nns_stride, d_counts, d_unique, (uint32_t)k, d_qvecs, qstride, d_qhdrs, h_oi, h_od, d_err, (const RerankSeg *)nullptr,
                                bitmap_words, max_id + 1, h_counts, h_err, sel_trace, sp.count_of);
         else if (fused_flag)
             hipLaunchKernelGGL((k_search_select_screened<AH_DOT_PRODUCT, true>), dim3((unsigned)nq), dim3(1024), fused_lds, s, dv, ss, d_nns,
                                d_dist, nns_stride, d_counts, d_unique, (uint32_t)k, d_qvecs, qstride, d_qhdrs, h_oi, h_od, d_err,
-                               (const PairSeg *)nullptr, bitmap_words, max_id + 1, h_counts, h_err, sel_trace, sp.count_of);
+                               (const RerankSeg *)nullptr, bitmap_words, max_id + 1, h_counts, h_err, sel_trace, sp.count_of);
         else if (screened && ds->metric == AH_COSINE)
             hipLaunchKernelGGL((k_search_select_screened<AH_COSINE>), dim3((unsigned)nq), dim3(1024), sel_lds, s, dv, ss, d_nns, d_dist,
-                               nns_stride, d_counts, d_unique, (uint32_t)k, d_qvecs, qstride, d_qhdrs, d_oi, d_od, d_err, (const PairSeg *)nullptr, 0u, 0u,
+                               nns_stride, d_counts, d_unique, (uint32_t)k, d_qvecs, qstride, d_qhdrs, d_oi, d_od, d_err, (const RerankSeg *)nullptr, 0u, 0u,
                                (uint32_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr, sp.count_of);
         else if (screened)
             hipLaunchKernelGGL((k_search_select_screened<AH_DOT_PRODUCT>), dim3((unsigned)nq), dim3(1024), sel_lds, s, dv, ss, d_nns, d_dist,
-                               nns_stride, d_counts, d_unique, (uint32_t)k, d_qvecs, qstride, d_qhdrs, d_oi, d_od, d_err, (const PairSeg *)nullptr, 0u, 0u,
+                               nns_stride, d_counts, d_unique, (uint32_t)k, d_qvecs, qstride, d_qhdrs, d_oi, d_od, d_err, (const RerankSeg *)nullptr, 0u, 0u,
                                (uint32_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr, sp.count_of);
         else
             hipLaunchKernelGGL(k_search_select, dim3((unsigned)nq), dim3(kSelectThreads), 0, s, dv, d_nns, d_dist, nns_stride, d_counts,
@@ -4855,12 +4826,12 @@ static int search_chunk(ah_index *ix, Context *ctx, const float *queries, const 
     for (size_t q = 0; q < nq; q++) {
         const uint32_t n = h_counts[q];
         n_candidates += n;
-        h_segs[q] = HostSeg2{(uint64_t)q * nns_stride, n, (uint32_t)std::min<size_t>(count_of(q), n)};
+        h_segs[q] = RerankSeg{(uint64_t)q * nns_stride, n, (uint32_t)std::min<size_t>(count_of(q), n)};
         out_counts[q] = h_segs[q].k;
         max_n = std::max(max_n, n);
         if (big_k) continue;
         max_rounds = std::max(max_rounds, batch_rounds(n, h_segs[q].k));
-        for (uint32_t f = 0; f < n; f += tc) h_tiles[n_tiles++] = HostTile2{(uint32_t)q, f};
+        for (uint32_t f = 0; f < n; f += tc) h_tiles[n_tiles++] = RerankTile{(uint32_t)q, f};
     }
     if (big_k) {
         // d_ka (2 x nq x kstride x 8 bytes >= the single-query scratch) is free: the batch path is not used
@@ -4875,11 +4846,13 @@ static int search_chunk(ah_index *ix, Context *ctx, const float *queries, const 
             AH_TRY(launch_topk(dv, dist_q, ids_q, n, kk, d_ka, d_oi + q * k, d_od + q * k, s));
         }
     } else {
-        AH_HIP(hipMemcpyAsync(d_segs, h_segs, nq * sizeof(HostSeg2), hipMemcpyHostToDevice, s));
-        if (n_tiles) AH_HIP(hipMemcpyAsync(d_tiles, h_tiles, (size_t)n_tiles * sizeof(HostTile2), hipMemcpyHostToDevice, s));
-        AH_TRY(launch_rerank_batch_prepared(dv, (uint32_t)nq, d_qvecs, qstride, d_qhdrs, d_segs, d_tiles, n_tiles, d_nns, d_dist,
-                                            d_ka, d_kb, kstride, max_n, (uint32_t)k, max_rounds, d_oi, d_od, d_err, s,
-                                            n_candidates, d_inv));
+        AH_HIP(hipMemcpyAsync(d_segs, h_segs, nq * sizeof(RerankSeg), hipMemcpyHostToDevice, s));
+        if (n_tiles) AH_HIP(hipMemcpyAsync(d_tiles, h_tiles, (size_t)n_tiles * sizeof(RerankTile), hipMemcpyHostToDevice, s));
+        RerankBufs b{};  // (no screen here: its scratch stays null)
+        b.n_queries = (uint32_t)nq, b.d_qvecs = d_qvecs, b.qstride = qstride, b.d_qhdrs = d_qhdrs, b.d_segs = d_segs, b.d_tiles = d_tiles;
+        b.n_tiles = n_tiles, b.d_ids = d_nns, b.d_dist = d_dist, b.d_keys_a = d_ka, b.d_keys_b = d_kb, b.kstride = kstride;
+        b.d_out_ids = d_oi, b.d_out_dist = d_od, b.d_err = d_err, b.d_inv_counters = d_inv;
+        AH_TRY(launch_rerank_batch_prepared(dv, b, max_n, (uint32_t)k, max_rounds, n_candidates, s));
     }
     AH_HIP(hipMemcpyAsync(h_oi, d_oi, nq * k * 4, hipMemcpyDeviceToHost, s));
     AH_HIP(hipMemcpyAsync(h_od, d_od, nq * k * 4, hipMemcpyDeviceToHost, s));

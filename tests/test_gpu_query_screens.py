@@ -258,6 +258,41 @@ def test_long_lists_and_pipelined_groups():
     check_oracle(oracle, qs, lists, k, res[1], [0, 1, 2, len(sizes) - 1])  # lists of 100 000, 20 000 and 17 000 (> 16 384)
 
 
+def test_pipelined_groups_retry_and_fall_back():
+    """A near-tie list inside a submission big enough for the pipelined upload (>= 512 Ki ids, in 3 groups): the int8 stage
+    overflows and the binary16 rows answer (loose), or overflow as well and the exact path answers (tight) — the retry and
+    the fall-back behind the groups, which no other test reaches.  List 0 and its rows are those of
+    test_near_ties_retry_on_binary16_then_the_exact_path (same seed, same draws, same spreads 0.15 / 0.01); 266 000
+    standard-normal rows and 53 lists of 10 000 of them follow.  (53, not 52: 4000 + 520 000 ids are fewer than 512 Ki =
+    524 288, so the upload would not be pipelined; 534 000 are, and still fewer than 2 n = 540 000, where the row-major
+    re-rank would take the submission.)  The spreads needed no change with the maxima of 270 000 rows; the commit before the
+    two tails became one gave, with these inputs — loose: chunks_int8 0, chunks_int8_retried 1, queries_screened 54,
+    survivors 901; tight: chunks_int8 0, chunks_int8_retried 1, queries_screened 0, survivors 0; 1 068 000 candidates
+    checked against their intervals and no violation in either."""
+    rng = np.random.default_rng(17)
+    dims, k, n, n_far_lists = 256, 10, 270_000, 53
+    near = [clustered(rng, 1000, 3000, dims, spread) for spread in (0.15, 0.01)]  # (loose, tight: the draws of that test)
+    vecs = np.concatenate([near[0][0], rng.standard_normal((n - 4000, dims), dtype=np.float32)])
+    lists = [np.arange(4000, dtype=np.uint32)]
+    lists += [np.sort(rng.choice(np.arange(4000, n), 10_000, replace=False)).astype(np.uint32) for _ in range(n_far_lists)]
+    qs = rng.standard_normal((len(lists), dims)).astype(np.float32)
+    total = sum(len(l) for l in lists)
+    assert 512 << 10 <= total < 2 * n
+    for (rows, centre), screened in zip(near, (len(lists), 0)):
+        vecs[:4000] = rows  # (only the cluster changes)
+        qs[0] = centre
+        ds, oracle = make(D.Cosine, vecs)
+        out, st, v = run(ds, qs, lists, k, AH_RERANK_GROUPS=3, AH_SCREEN8=1)
+        print("pipelined near ties", screened, st["chunks_int8"], st["chunks_int8_retried"], st["queries_screened"], st["survivors"], v)
+        assert st["chunks_int8_retried"] == 1 and st["queries_screened"] == screened, st
+        assert v["violations"] == 0, v
+        one, _, _ = run(ds, qs, lists, k, AH_RERANK_GROUPS=1, AH_SCREEN8=1)
+        same(out, one, "3 groups vs 1")
+        ref, _, _ = run(ds, qs, lists, k, AH_RERANK_SCREEN=0)
+        same(out, ref, "screened vs unscreened")
+        check_oracle(oracle, qs, lists, k, out, [0, 1, len(lists) - 1])
+
+
 @pytest.mark.parametrize("cls", METRICS, ids=["cosine", "dot"])
 def test_unsorted_or_repeated_ids_are_rejected_on_every_path(cls):
     rng = np.random.default_rng(37)
