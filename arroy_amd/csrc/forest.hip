@@ -19,7 +19,10 @@
 #include <chrono>
 #include <condition_variable>
 #include <deque>
+#include <array>
 #include <thread>
+#include <type_traits>
+#include <unordered_map>
 #include <cstdlib>
 #include <immintrin.h>
 #include <sys/mman.h>
@@ -30,6 +33,7 @@
 #include "common.h"
 #include "split_device.h"
 #include "screen_device.h"
+#include "level_plan.h"
 
 namespace ah {
 
@@ -1956,7 +1960,6 @@ struct Arena {
 // Measurement and test aids: the tunables of common.h (environment variable at load time, ah_tuning_set at run time).
 // The per-call knob is ah_build_options.margin_mode; the tunables only steer AH_MARGIN_AUTO and the schedule of a level.
 // None of them changes a result.
-constexpr size_t kLdsNormalsBytes = 128u << 10;  // LDS given to the normals of one tree group (of 160 KiB per CU)
 #define AH_DBG(s, what)                                                       \
     do {                                                                      \
         if (tun(TUN_DEBUG)) {                                                 \
@@ -1989,40 +1992,6 @@ struct BatchCleanup {  // events / side stream of one batch
         if (side) (void)hipStreamDestroy(side);
     }
 };
-
-// Measured cost of one row-major pass in ns per row, as a function of the tree-group size and of the bytes of normals
-// the group streams in the level (profiles/r02_*: 10M x 768 x 100 trees, every level forced to one group size), for
-// the f32 kernels (rows of 3072 bytes) and for the screened kernels (binary16 rows of 1536 bytes).  While the normals fit
-// the L2s a pass is bound by the vector-memory pipeline — one 16-byte load per 4 FMAs / 4 dot2c — and costs more as the
-// octets of a wave stop sharing normals (deeper levels); beyond ~10 MB they come through the fabric and every group size
-// converges to (1 + tc) rows' worth of traffic at ~8 TB/s.  Linear interpolation between the measured points.
-struct CostPt {
-    double mb, ns;
-};
-template <size_t N>
-double interp(const CostPt (&t)[N], double mb) {
-    if (mb <= t[0].mb) return t[0].ns;
-    for (size_t i = 1; i < N; i++)
-        if (mb <= t[i].mb) return t[i - 1].ns + (t[i].ns - t[i - 1].ns) * (mb - t[i - 1].mb) / (t[i].mb - t[i - 1].mb);
-    return t[N - 1].ns;
-}
-double rows_pass_ns_per_row(uint32_t tc, double ws_mb, bool screened) {
-    static const CostPt e16[] = {{0.4, 1.60}, {3.2, 1.83}, {6.3, 2.05}, {12.6, 2.33}, {25, 5.08}, {50, 6.05}, {100, 6.5}, {400, 6.8}};
-    static const CostPt e8[] = {{0.2, 1.16}, {1.6, 1.22}, {3.2, 2.0}, {6.3, 2.5}, {12.6, 3.1}, {25, 3.5}, {100, 3.7}};
-    static const CostPt e4[] = {{0.1, 0.73}, {0.8, 0.85}, {3.2, 0.88}, {6.3, 1.07}, {12.6, 1.45}, {25, 1.85}, {50, 2.05}, {100, 2.14}};
-    static const CostPt e2[] = {{0.05, 0.49}, {0.8, 0.60}, {3.1, 0.62}, {6.3, 0.74}, {12.6, 0.99}, {25, 1.14}, {50, 1.21}};
-    // screened kernels, chunk-major launches, epilogue on owner lanes (gpurun r02w: 96 trees, every level forced)
-    static const CostPt s16[] = {{0.025, 1.11}, {0.2, 1.13}, {0.4, 1.20}, {0.8, 1.25}, {1.6, 1.30}, {3.2, 1.45}, {6.4, 1.99},
-                                 {12.7, 2.94}, {25, 3.57}, {51, 3.92}, {102, 4.10}, {203, 4.21}};
-    static const CostPt s8[] = {{0.012, 0.58}, {0.1, 0.61}, {0.2, 0.67}, {0.4, 0.71}, {0.8, 0.74}, {1.6, 0.77}, {3.2, 0.85},
-                                {6.4, 1.24}, {12.7, 1.66}, {25, 1.94}, {51, 2.09}, {102, 2.15}};
-    static const CostPt s4[] = {{0.025, 0.325}, {0.05, 0.353}, {0.1, 0.415}, {0.2, 0.463}, {0.4, 0.493}, {0.8, 0.511},
-                                {1.7, 0.45}, {3.4, 0.50}, {6.8, 0.69}, {13.6, 0.90}, {27, 1.03}, {54, 1.10}};  // one XCD per group, nt rows > 5 MB
-    static const CostPt s2[] = {{0.003, 0.235}, {0.05, 0.243}, {0.1, 0.261}, {0.2, 0.274}, {0.4, 0.284}, {0.8, 0.292},
-                                {1.6, 0.314}, {3.2, 0.389}, {6.4, 0.49}, {12.7, 0.56}, {25, 0.60}};
-    if (screened) return tc >= 16 ? interp(s16, ws_mb) : tc == 8 ? interp(s8, ws_mb) : tc == 4 ? interp(s4, ws_mb) : interp(s2, ws_mb);
-    return tc >= 16 ? interp(e16, ws_mb) : tc == 8 ? interp(e8, ws_mb) : tc == 4 ? interp(e4, ws_mb) : interp(e2, ws_mb);
-}
 
 // index into ah_build_stats.margin_mode_launches
 enum { MM_NODE = 0, MM_ROWS2 = 1, MM_ROWS4 = 2, MM_ROWS8 = 3, MM_ROWS16 = 4, MM_LDS8 = 5, MM_LDS16 = 6, MM_BQ = 7 };
@@ -2477,58 +2446,92 @@ struct Readback {
     }
 };
 
-// Launch one instantiation of k_forest_screen_rows (metric x trees per group x LDS-resident normals).
+// What the launchers of one level share: the level's tables and the buffers its margin kernels read and write.
 namespace {
-struct ScreenRowsArgs {
+struct LevelBufs {
     DataView dv;
     ScreenView sv;
-    const uint32_t *node_of;
-    uint32_t tree_base, n_pass;
-    const uint8_t *normals;
+    int metric, device;
+    hipStream_t s;
+    uint64_t N;
+    uint32_t n_trees, n_nodes, n_tiles;
+    FNode *nodes;  // the level's node table, its tiles, the permutation it reads
+    FTile *tiles;
+    uint32_t *perm;
+    uint8_t *normals;  // the level's chunk of normal records, then its binary16 and int8 shadows
     uint64_t nstride, hdr_off;
-    const uint8_t *shadow;
+    uint8_t *shadow;
     uint64_t hstride;
+    uint8_t *shadow8;
+    uint64_t stride8;
+    uint64_t *masks;
+    uint32_t *tile_left, *node_of;  // (row-major levels: node index and side per (tree, row))
     uint8_t *side_bytes;
-    RowsSchedule sch;
-    AbortFlags abort_flag;
+    uint32_t *side_bits;
     ScreenCounters *counters;
+    AbortFlags abort_all, abort_gated;  // the cancel word alone; with the gate of the attempt (attempts 1-3: nodes left pending)
     uint32_t verify;
 };
-template <int M, int TC, bool LDS>
-int launch_screen_rows_inst(const ScreenRowsArgs &a, unsigned grid, size_t sh, hipStream_t s, int device) {
-    const unsigned threads = LDS ? (TC >= 16 ? 512u : 1024u) : (unsigned)kBlock;
-    if (LDS) {
-        static std::atomic<bool> opt_in[64];  // once per instantiation and device
-        if (!opt_in[device & 63].load(std::memory_order_acquire)) {
-            AH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_forest_screen_rows<M, TC, LDS>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsNormalsBytes));
-            opt_in[device & 63].store(true, std::memory_order_release);
-        }
+
+// The dispatch over the metric of every margin-kernel family: f(std::integral_constant<int, metric>).
+template <class F>
+int with_metric(int metric, F &&f) {
+    switch (metric) {
+    case AH_EUCLIDEAN: return f(std::integral_constant<int, AH_EUCLIDEAN>{});
+    case AH_MANHATTAN: return f(std::integral_constant<int, AH_MANHATTAN>{});
+    case AH_COSINE: return f(std::integral_constant<int, AH_COSINE>{});
+    default: return f(std::integral_constant<int, AH_DOT_PRODUCT>{});
     }
-    hipLaunchKernelGGL((k_forest_screen_rows<M, TC, LDS>), dim3(grid), dim3(threads), LDS ? sh : 0, s, a.dv, a.sv, a.node_of,
-                       a.tree_base, a.n_pass, a.normals, a.nstride, a.hdr_off, a.shadow, a.hstride, a.side_bytes, a.sch,
-                       a.abort_flag, a.counters, a.verify);
+}
+
+// Opt a kernel in to `bytes` of dynamic LDS.  Per kernel instantiation and device the largest size granted is remembered
+// (the default limit of 48 KiB to begin with), and the runtime is asked only when a launch needs more.
+int lds_opt_in(const void *kernel, int device, size_t bytes) {
+    static std::mutex mu;
+    static std::unordered_map<const void *, std::array<size_t, 64>> granted;
+    if (bytes <= 48 * 1024) return AH_OK;
+    std::lock_guard<std::mutex> lk(mu);
+    size_t &g = granted[kernel][device & 63];
+    if (bytes <= g) return AH_OK;
+    AH_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    g = bytes;
     return AH_OK;
 }
-template <int M>
-int launch_screen_rows_metric(uint32_t tc, bool lds, const ScreenRowsArgs &a, unsigned grid, size_t sh, hipStream_t s, int device) {
-    if (lds) return tc >= 16 ? launch_screen_rows_inst<M, 16, true>(a, grid, sh, s, device)
-                             : launch_screen_rows_inst<M, 8, true>(a, grid, sh, s, device);
-    switch (tc) {
-    case 16: return launch_screen_rows_inst<M, 16, false>(a, grid, sh, s, device);
-    case 8: return launch_screen_rows_inst<M, 8, false>(a, grid, sh, s, device);
-    case 4: return launch_screen_rows_inst<M, 4, false>(a, grid, sh, s, device);
-    default: return launch_screen_rows_inst<M, 2, false>(a, grid, sh, s, device);
-    }
+
+// k_forest_create_split of an attempt (`metric`: the f32 space the two-means run in).
+int launch_create_split(const LevelBufs &b, int metric, unsigned grid, size_t cs_shared) {
+    return with_metric(metric, [&](auto m) -> int {
+        constexpr int M = decltype(m)::value;
+        AH_TRY(lds_opt_in(reinterpret_cast<const void *>(k_forest_create_split<M>), b.device, cs_shared));
+        hipLaunchKernelGGL(k_forest_create_split<M>, dim3(grid), dim3(64), cs_shared, b.s, b.dv, b.nodes, b.n_nodes, b.perm, b.N,
+                           b.normals, b.nstride, b.hdr_off, b.abort_gated.gate);
+        return AH_OK;
+    });
 }
-int launch_screen_rows(int metric, uint32_t tc, bool lds, const ScreenRowsArgs &a, unsigned grid, size_t sh, hipStream_t s,
-                       int device) {
-    switch (metric) {
-    case AH_EUCLIDEAN: return launch_screen_rows_metric<AH_EUCLIDEAN>(tc, lds, a, grid, sh, s, device);
-    case AH_MANHATTAN: return launch_screen_rows_metric<AH_MANHATTAN>(tc, lds, a, grid, sh, s, device);
-    case AH_COSINE: return launch_screen_rows_metric<AH_COSINE>(tc, lds, a, grid, sh, s, device);
-    default: return launch_screen_rows_metric<AH_DOT_PRODUCT>(tc, lds, a, grid, sh, s, device);
-    }
+
+// One launch of k_forest_screen_rows (metric x trees per group x LDS-resident normals).
+template <int M, int TC, bool LDS>
+int launch_screen_rows_inst(const LevelBufs &b, const RowsLaunch &l, const RowsSchedule &sch, unsigned grid, size_t sh, size_t lds_grant) {
+    const unsigned threads = LDS ? (TC >= 16 ? 512u : 1024u) : (unsigned)kBlock;
+    if (LDS) AH_TRY(lds_opt_in(reinterpret_cast<const void *>(k_forest_screen_rows<M, TC, LDS>), b.device, lds_grant));
+    hipLaunchKernelGGL((k_forest_screen_rows<M, TC, LDS>), dim3(grid), dim3(threads), LDS ? sh : 0, b.s, b.dv, b.sv, b.node_of,
+                       l.t0, l.np, b.normals, b.nstride, b.hdr_off, b.shadow, b.hstride, b.side_bytes, sch, b.abort_all,
+                       b.counters, b.verify);
+    return AH_OK;
+}
+int launch_screen_rows(const LevelBufs &b, const RowsLaunch &l, bool lds, const RowsSchedule &sch, unsigned grid, size_t sh,
+                       size_t lds_grant) {
+    return with_metric(b.metric, [&](auto m) -> int {
+        constexpr int M = decltype(m)::value;
+        if (lds) return l.tcv >= 16 ? launch_screen_rows_inst<M, 16, true>(b, l, sch, grid, sh, lds_grant)
+                                    : launch_screen_rows_inst<M, 8, true>(b, l, sch, grid, sh, lds_grant);
+        switch (l.tcv) {
+        case 16: return launch_screen_rows_inst<M, 16, false>(b, l, sch, grid, sh, lds_grant);
+        case 8: return launch_screen_rows_inst<M, 8, false>(b, l, sch, grid, sh, lds_grant);
+        case 4: return launch_screen_rows_inst<M, 4, false>(b, l, sch, grid, sh, lds_grant);
+        default: return launch_screen_rows_inst<M, 2, false>(b, l, sch, grid, sh, lds_grant);
+        }
+    });
 }
 }  // namespace
 
@@ -2623,6 +2626,210 @@ int plan_rows_launches(uint64_t N, uint32_t hpitch, uint32_t tcv, uint32_t group
 }
 }  // namespace
 
+// The margin pass of a level's first attempt, one launcher per kernel family.  Each launches what the level's plan
+// (plan_level, level_plan.h) says and counts it in the build's statistics.
+namespace {
+// The dense product on the matrix units (wide, narrow or streaming narrow: dense_plan), then k_forest_exact_pairs for the
+// pairs it left open.
+template <int M, int WN>
+int launch_dense_wide(const LevelBufs &b, const DensePlan &dp, const DenseArgs &da) {
+    AH_TRY(lds_opt_in(reinterpret_cast<const void *>(k_forest_dense_screen<M, WN>), b.device, kDenseLds));
+    hipLaunchKernelGGL((k_forest_dense_screen<M, WN>), dim3((unsigned)dp.grid), dim3(DenseShape<WN>::kThreads), kDenseLds, b.s, da,
+                       b.abort_all);
+    return AH_OK;
+}
+template <int M, int NT>
+int launch_dense_narrow(const LevelBufs &b, const DensePlan &dp, const DenseArgs &da) {
+    if (dp.stream)
+        hipLaunchKernelGGL((k_forest_dense_narrow<M, NT, true>), dim3((unsigned)dp.grid), dim3(kNarrowThreads), NarrowShape<NT>::kLds,
+                           b.s, da, b.abort_all);
+    else
+        hipLaunchKernelGGL((k_forest_dense_narrow<M, NT, false>), dim3((unsigned)dp.grid), dim3(kNarrowThreads), NarrowShape<NT>::kLds,
+                           b.s, da, b.abort_all);
+    return AH_OK;
+}
+int launch_dense(const LevelBufs &b, const DensePlan &dp, bool exact_wide, ah_build_stats &st) {
+    DenseArgs da{};
+    da.rows = b.sv.rows;
+    da.stats = b.sv.stats;
+    da.headers = b.dv.headers;
+    da.n = b.N;
+    da.hpitch = b.sv.hpitch;
+    da.shadow = b.shadow;
+    da.hstride = b.hstride;
+    da.n_cols = b.n_nodes;
+    da.nodes = b.nodes;
+    da.node_of = b.node_of;
+    da.side_bytes = b.side_bytes;
+    // accumulation error of the product: every one of the hpitch exact binary16 products enters one f32
+    // chain; whatever the order and the rounding mode of the matrix unit's adders (nearest or truncating,
+    // aligned to the largest addend of a 16-wide step or not), the sum is off by less than
+    // (hpitch + hpitch / 16) * 2^-23 * sum |x~_i n~_i|; taken twice over
+    da.gamma_s = (float)(2.0 * ((double)b.sv.hpitch + (double)b.sv.hpitch / 16 + 16.0) * 1.1920929e-7);
+    da.gamma_r = b.sv.gamma_r;
+    da.n_row_tiles = dp.n_row_tiles;
+    da.n_col_tiles = dp.n_col_tiles;
+    da.group = dp.group;
+    da.verify = b.verify;
+    AH_REQUIRE(dp.grid < 0x7FFFFFFFull, AH_ERR_INVALID_ARGUMENT, "forest build: too many tiles for one launch");
+    const unsigned egrid = exact_pairs_grid(b.N, b.n_trees);
+    AH_TRY(with_metric(b.metric, [&](auto m) -> int {
+        constexpr int M = decltype(m)::value;
+        if (dp.narrow == 2) AH_TRY((launch_dense_narrow<M, 2>(b, dp, da)));
+        else if (dp.narrow == 4) AH_TRY((launch_dense_narrow<M, 4>(b, dp, da)));
+        else if (dp.wide) AH_TRY((launch_dense_wide<M, 4>(b, dp, da)));
+        else AH_TRY((launch_dense_wide<M, 2>(b, dp, da)));
+        if (exact_wide)
+            hipLaunchKernelGGL((k_forest_exact_pairs<M, true>), dim3(egrid), dim3(256), 0, b.s, b.dv, b.node_of, b.side_bytes,
+                               b.n_trees, b.normals, b.nstride, b.hdr_off, b.counters, b.abort_all);
+        else
+            hipLaunchKernelGGL((k_forest_exact_pairs<M>), dim3(egrid), dim3(256), 0, b.s, b.dv, b.node_of, b.side_bytes, b.n_trees,
+                               b.normals, b.nstride, b.hdr_off, b.counters, b.abort_all);
+        return AH_OK;
+    }));
+    st.dense_launches++;
+    st.dense_columns += b.n_nodes;
+    return AH_OK;
+}
+
+// The screened row-major pass.  Chunk-major launches (RowsSchedule): all full groups of the level in ONE launch, so that the
+// passes over a chunk of rows run back to back and find it in the Infinity Cache; the last trees (fewer than a group) in
+// launches of their own.  The LDS variant reads the first node of every tree from a device copy (`d_tree_first`).
+int launch_rows_screened(const LevelBufs &b, const LevelPlan &plan, uint64_t nodes_per_tree, uint64_t rec_bytes,
+                         const uint32_t *d_tree_first, size_t lds_grant, ah_build_stats &st) {
+    const bool lds = plan.lds_tc != 0;
+    const size_t lds_sh = (size_t)plan.lds_worst * rec_bytes;
+    for (const RowsLaunch &l : plan.launches) {
+        RowsPlan rp;
+        AH_TRY(plan_rows_launches(b.N, b.sv.hpitch, l.tcv, l.groups, lds, (uint64_t)l.tcv * nodes_per_tree * rec_bytes, &rp));
+        rp.sch.tree_first = d_tree_first;
+        for (const auto &c : rp.launches) {
+            rp.sch.chunk0 = c.first;
+            AH_TRY(launch_screen_rows(b, l, lds, rp.sch, c.second, lds_sh, lds_grant));
+        }
+        st.margin_mode_launches[lds ? (l.tcv >= 16 ? MM_LDS16 : MM_LDS8) : mm_rows(l.tcv)]++;
+        st.rows_xcd_launches += rp.xcd ? rp.launches.size() : 0;
+        st.rows_nt_launches += rp.nt ? rp.launches.size() : 0;
+        st.rows_split_launches += rp.launches.size() - 1;
+    }
+    return AH_OK;
+}
+
+// The f32 row-major pass: one launch per group of the plan's list, LDS-resident (a group without a node in the level is
+// skipped) or plain.
+template <int M, int TC>
+int launch_rows_lds_inst(const LevelBufs &b, uint32_t t0, uint32_t np, uint32_t first, uint32_t cnt, size_t sh, size_t lds_grant) {
+    const unsigned per_cu = (unsigned)std::max<size_t>(1, std::min<size_t>(2, (150u << 10) / std::max<size_t>(sh, 1)));
+    const unsigned threads = TC >= 16 ? 512u : 1024u;
+    const unsigned grid = (unsigned)std::min<uint64_t>((b.N * 8 + threads - 1) / threads, 256u * per_cu);
+    AH_TRY(lds_opt_in(reinterpret_cast<const void *>(k_forest_margin_rows_lds<M, TC>), b.device, lds_grant));
+    hipLaunchKernelGGL((k_forest_margin_rows_lds<M, TC>), dim3(grid), dim3(threads), sh, b.s, b.dv, b.node_of, t0, np, b.normals,
+                       b.nstride, b.hdr_off, b.side_bytes, first, cnt, b.abort_all);
+    return AH_OK;
+}
+template <int M, int TC>
+int launch_rows_inst(const LevelBufs &b, uint32_t t0, uint32_t np, unsigned row_grid) {
+    hipLaunchKernelGGL((k_forest_margin_rows<M, TC>), dim3(row_grid), dim3(kBlock), 0, b.s, b.dv, b.node_of, t0, np, b.normals,
+                       b.nstride, b.hdr_off, b.side_bytes, b.abort_all);
+    return AH_OK;
+}
+int launch_rows_f32(const LevelBufs &b, const LevelPlan &plan, uint64_t rec_bytes, unsigned row_grid, size_t lds_grant,
+                    ah_build_stats &st) {
+    for (const RowsLaunch &l : plan.launches)
+        for (uint32_t g = 0; g < l.groups; g++) {
+            const uint32_t t0 = l.t0 + g * l.tcv;
+            if (plan.lds_tc) {
+                const uint32_t first = plan.tree_first[t0], cnt = plan.tree_first[t0 + l.np] - first;
+                if (cnt == 0) continue;
+                const size_t sh = (size_t)cnt * rec_bytes;
+                AH_TRY(with_metric(b.metric, [&](auto m) -> int {
+                    constexpr int M = decltype(m)::value;
+                    return l.tcv >= 16 ? launch_rows_lds_inst<M, 16>(b, t0, l.np, first, cnt, sh, lds_grant)
+                                       : launch_rows_lds_inst<M, 8>(b, t0, l.np, first, cnt, sh, lds_grant);
+                }));
+                st.margin_mode_launches[l.tcv >= 16 ? MM_LDS16 : MM_LDS8]++;
+            } else {
+                AH_TRY(with_metric(b.metric, [&](auto m) -> int {
+                    constexpr int M = decltype(m)::value;
+                    switch (l.tcv) {
+                    case 16: return launch_rows_inst<M, 16>(b, t0, l.np, row_grid);
+                    case 8: return launch_rows_inst<M, 8>(b, t0, l.np, row_grid);
+                    case 4: return launch_rows_inst<M, 4>(b, t0, l.np, row_grid);
+                    default: return launch_rows_inst<M, 2>(b, t0, l.np, row_grid);
+                    }
+                }));
+                st.margin_mode_launches[mm_rows(l.tcv)]++;
+            }
+        }
+    return AH_OK;
+}
+
+// The node-major pass of an attempt on a persistent grid: binary-quantised, screened (`node_pre`: the pipelined variant of
+// the int8 stage) or f32.  Very long vectors need more dynamic LDS than the default limit.
+int launch_node_major(const LevelBufs &b, bool bq, bool screen, bool screen8, bool node_pre, unsigned node_grid, ah_build_stats &st) {
+    if (bq) {
+        hipLaunchKernelGGL(k_forest_margin_bq, dim3(node_grid), dim3(kBlock), b.dv.pitch * 8, b.s, b.dv, b.nodes, b.tiles, b.n_tiles,
+                           b.perm, b.N, b.normals, b.nstride, b.hdr_off, b.masks, b.tile_left, b.abort_gated);
+        st.margin_mode_launches[MM_BQ]++;
+        return AH_OK;
+    }
+    if (screen) {
+        const size_t sh = (size_t)b.dv.pitch * 4 + (size_t)b.sv.hpitch * 2 + (screen8 ? 2 * (size_t)b.sv.pitch8 : 0);
+        auto launch = [&](auto m, auto pre) -> int {
+            constexpr int M = decltype(m)::value, PRE = decltype(pre)::value;
+            AH_TRY(lds_opt_in(reinterpret_cast<const void *>(k_forest_screen_node<M, PRE>), b.device, sh));
+            hipLaunchKernelGGL((k_forest_screen_node<M, PRE>), dim3(node_grid), dim3(kBlock), sh, b.s, b.dv, b.sv, b.nodes, b.tiles,
+                               b.n_tiles, b.perm, b.normals, b.nstride, b.hdr_off, b.shadow, b.hstride, b.shadow8, b.stride8, b.masks,
+                               b.tile_left, b.abort_gated, b.counters, b.verify);
+            return AH_OK;
+        };
+        AH_TRY(with_metric(b.metric, [&](auto m) -> int {
+            return node_pre ? launch(m, std::integral_constant<int, 6>{}) : launch(m, std::integral_constant<int, 0>{});
+        }));
+        st.margin_mode_launches[MM_NODE]++;
+        st.screened_launches++;
+        return AH_OK;
+    }
+    const size_t sh = (size_t)b.dv.pitch * 4;
+    AH_TRY(with_metric(b.metric, [&](auto m) -> int {
+        constexpr int M = decltype(m)::value;
+        AH_TRY(lds_opt_in(reinterpret_cast<const void *>(k_forest_margin_f32<M>), b.device, sh));
+        hipLaunchKernelGGL((k_forest_margin_f32<M>), dim3(node_grid), dim3(kBlock), sh, b.s, b.dv, b.nodes, b.tiles, b.n_tiles, b.perm,
+                           b.N, b.normals, b.nstride, b.hdr_off, b.masks, b.tile_left, b.abort_gated);
+        return AH_OK;
+    }));
+    st.margin_mode_launches[MM_NODE]++;
+    return AH_OK;
+}
+
+// The tunables (common.h) a level reads, once per batch.
+LevelKnobs read_level_knobs() {
+    LevelKnobs k{};
+    k.screen = tun(TUN_SCREEN) != 0;
+    k.screen_verify = tun(TUN_SCREEN_VERIFY) != 0;
+    k.rows_force = (int)tun(TUN_ROWMAJOR);
+    k.dense = (int)tun(TUN_DENSE);
+    k.tile_blocks = (uint32_t)std::max<long long>(1, tun(TUN_FOREST_TILE_BLOCKS));
+    k.node_blocks = (uint32_t)std::max<long long>(0, tun(TUN_FOREST_NODE_BLOCKS));
+    k.split_blocks = (uint32_t)std::max<long long>(1, tun(TUN_FOREST_SPLIT_BLOCKS));
+    k.row_blocks = (uint32_t)std::max<long long>(1, tun(TUN_FOREST_ROW_BLOCKS));
+    k.rows_advance = tun(TUN_ROWMAJOR_ADVANCE) != 0;
+    k.rows_lds = tun(TUN_ROWMAJOR_LDS) != 0;
+    k.rows_max_tc = (uint32_t)std::max<long long>(2, tun(TUN_ROWMAJOR_MAX_TC));
+    k.rows_cache_mb = (double)tun(TUN_ROWMAJOR_CACHE_MB);
+    k.dense_max_cols = (uint32_t)std::max<long long>(0, tun(TUN_DENSE_MAX_COLS));
+    k.dense_gmacs = (double)std::max<long long>(1, tun(TUN_DENSE_GMACS));
+    k.retry_gate = tun(TUN_RETRY_GATE) != 0;
+    k.mask_bits = tun(TUN_MASK_BITS);
+    k.exact_wide = tun(TUN_EXACT_WIDE) != 0;
+    k.node_prefetch = tun(TUN_NODE_PREFETCH) != 0;
+    k.tail_groups = (uint32_t)std::min<long long>(32, std::max<long long>(0, tun(TUN_TAIL_GROUPS)));
+    k.tail_node_items = (double)std::max<long long>(1, tun(TUN_TAIL_NODE_ITEMS));
+    k.tail_min_items = (uint64_t)std::max<long long>(0, tun(TUN_TAIL_MIN_MB)) * (1u << 20) / 4;
+    return k;
+}
+}  // namespace
+
 // `subset_ids` == nullptr: every tree covers all items (Writer::build with missing trees).  Otherwise tree t covers
 // the ascending id list subset_ids[subset_offsets[first_tree + t] .. subset_offsets[first_tree + t + 1]) — the
 // "descendants that became too large" of an incremental build (src/writer.rs:660-739).
@@ -2663,24 +2870,12 @@ static int build_batch(ah_dataset *ds, const ah_build_options *opt, uint32_t fir
     const bool bq = metric_is_bq(ds->metric);
     const uint64_t hdr_off = ds->row_bytes();
     const uint64_t nstride = normal_record_stride(ds);
-    // the tunables (common.h), read once per batch
-    const bool g_screen = tun(TUN_SCREEN) != 0, g_screen_verify = tun(TUN_SCREEN_VERIFY) != 0;
-    const int g_rows_force = (int)tun(TUN_ROWMAJOR), g_dense = (int)tun(TUN_DENSE);
-    const uint32_t g_tile_blocks = (uint32_t)std::max<long long>(1, tun(TUN_FOREST_TILE_BLOCKS));
-    const uint32_t g_node_blocks = (uint32_t)std::max<long long>(0, tun(TUN_FOREST_NODE_BLOCKS));
-    const uint32_t g_split_blocks = (uint32_t)std::max<long long>(1, tun(TUN_FOREST_SPLIT_BLOCKS));
-    const uint32_t g_row_blocks = (uint32_t)std::max<long long>(1, tun(TUN_FOREST_ROW_BLOCKS));
-    const bool g_rows_advance = tun(TUN_ROWMAJOR_ADVANCE) != 0, g_rows_lds = tun(TUN_ROWMAJOR_LDS) != 0;
-    const uint32_t g_rows_max_tc = (uint32_t)std::max<long long>(2, tun(TUN_ROWMAJOR_MAX_TC));
-    const double g_rows_cache_mb = (double)tun(TUN_ROWMAJOR_CACHE_MB);
-    const uint32_t g_dense_max_cols = (uint32_t)std::max<long long>(0, tun(TUN_DENSE_MAX_COLS));
-    const double g_dense_gmacs = (double)std::max<long long>(1, tun(TUN_DENSE_GMACS));
+    const LevelKnobs knobs = read_level_knobs();  // the tunables (common.h), read once per batch
     const int timing = (int)tun(TUN_TIMING);
-    const bool g_retry_gate = tun(TUN_RETRY_GATE) != 0;
     // AH_MARGIN_MODE (measurement aid): the kernel family for callers that leave the choice to the library
     const uint32_t env_mode = (uint32_t)tun(TUN_MARGIN_MODE) & 0xFFFu;
     const uint32_t mode_req = (opt->margin_mode & 0xFFFu) ? (opt->margin_mode & 0xFFFu) : env_mode;
-    const bool exact_only = (opt->margin_mode & AH_MARGIN_EXACT_ONLY) != 0 || !g_screen;
+    const bool exact_only = (opt->margin_mode & AH_MARGIN_EXACT_ONLY) != 0 || !knobs.screen;
 
     // Upper bounds known up front (every split node owns > split_after items), so nothing is reallocated
     // between levels: nodes per level <= n_trees * N / (split_after + 1), tiles <= items / kTile + nodes.
@@ -2746,7 +2941,7 @@ static int build_batch(ah_dataset *ds, const ah_build_options *opt, uint32_t fir
 
     // row-major margin mode (full-dataset trees, f32 metrics): node index and side byte per (tree, row)
     const bool rows_allowed = !subset_ids && !bq && ds->dims >= 32 && n_trees >= 2 &&
-                              (mode_req != AH_MARGIN_AUTO ? mode_req != AH_MARGIN_NODE_MAJOR : g_rows_force != 0);
+                              (mode_req != AH_MARGIN_AUTO ? mode_req != AH_MARGIN_NODE_MAJOR : knobs.rows_force != 0);
     DevBuf<uint32_t> node_of;
     DevBuf<uint8_t> side_bytes;
     DevBuf<uint32_t> side_bits;
@@ -2757,7 +2952,7 @@ static int build_batch(ah_dataset *ds, const ah_build_options *opt, uint32_t fir
         AH_HIP(hipMemsetAsync(side_bytes.p, 0, (size_t)n_trees * N + 1024 + 16, s));
         // the same sides one bit each for the permutation-order gather of k_forest_masks_from_bytes (worth its pass from
         // the size on at which a tree's bytes no longer sit in an L2)
-        if ((tun(TUN_MASK_BITS) > 0 || (tun(TUN_MASK_BITS) < 0 && N >= (1u << 20))) &&
+        if ((knobs.mask_bits > 0 || (knobs.mask_bits < 0 && N >= (1u << 20))) &&
             side_bits.ensure(((size_t)n_trees * N + 31) / 32 + 4) != AH_OK)
             (void)hipGetLastError();  // no room: the tiles gather the bytes
     }
@@ -2786,7 +2981,7 @@ static int build_batch(ah_dataset *ds, const ah_build_options *opt, uint32_t fir
         sv.gamma_r = (float)(4.0 * ((double)(ds->dims / 32) + 6.0 + 62.0) * 5.9604645e-8);
         hstride = ((uint64_t)ds->hpitch * 2 + 16 + 127) & ~(uint64_t)127;  // whole lines, see normal_record_stride
     }
-    const uint32_t verify = screen && g_screen_verify ? 1u : 0u;
+    const uint32_t verify = screen && knobs.screen_verify ? 1u : 0u;
     const bool screen8 = screen && sv.rows8 != nullptr;
     const uint64_t stride8 = screen8 ? ((2 * (uint64_t)sv.pitch8 + sizeof(NormalStats8) + 127) & ~(uint64_t)127) : 0;
     if (!subset_ids) {
@@ -2942,18 +3137,6 @@ static int build_batch(ah_dataset *ds, const ah_build_options *opt, uint32_t fir
     AH_REQUIRE(cs_shared <= 150 * 1024, AH_ERR_INVALID_DIMENSION, "dimensions %u too large for the LDS-resident two-means",
                ds->dims);
     const int split_metric = f32_space_metric(ds->metric);
-#define AH_SPLIT_KERNEL(DO)                                              \
-    switch (split_metric) {                                              \
-    case AH_EUCLIDEAN: DO(k_forest_create_split<AH_EUCLIDEAN>); break;   \
-    case AH_MANHATTAN: DO(k_forest_create_split<AH_MANHATTAN>); break;   \
-    case AH_COSINE: DO(k_forest_create_split<AH_COSINE>); break;         \
-    default: DO(k_forest_create_split<AH_DOT_PRODUCT>); break;           \
-    }
-    if (cs_shared > 48 * 1024) {
-#define AH_SPLIT_OPT_IN(K) AH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(K), hipFuncAttributeMaxDynamicSharedMemorySize, (int)cs_shared))
-        AH_SPLIT_KERNEL(AH_SPLIT_OPT_IN)
-#undef AH_SPLIT_OPT_IN
-    }
     const uint64_t normals_base = forest->normals_len;  // this batch appends its levels after earlier batches
     uint64_t normals_bytes = 0;
     // The host blob gets lazily committed head-room (splits in total ~1.3-1.6 x items / split_after) so that finished
@@ -3182,9 +3365,6 @@ static int build_batch(ah_dataset *ds, const ah_build_options *opt, uint32_t fir
     // levels always node-major (they are by then), its records digested like any level's.  The forest is the same node
     // for node — trees never interact — only the order of the normals in the blob (and the ids of a streaming build)
     // follows the order of the launches.
-    const uint32_t g_tail_groups = (uint32_t)std::min<long long>(32, std::max<long long>(0, tun(TUN_TAIL_GROUPS)));
-    const double g_tail_node_items = (double)std::max<long long>(1, tun(TUN_TAIL_NODE_ITEMS));
-    const uint64_t g_tail_min_items = (uint64_t)std::max<long long>(0, tun(TUN_TAIL_MIN_MB)) * (1u << 20) / 4;
     bool grouped = false, fork_now = false, group_first_level = false;
     uint32_t group_n0 = 0;
     std::vector<uint32_t> level_rec_full;
@@ -3370,6 +3550,21 @@ static int build_batch(ah_dataset *ds, const ah_build_options *opt, uint32_t fir
         return AH_OK;
     };
     group_complete = [&](uint32_t tA, uint32_t tB) -> int { return sb ? push_leaves_job(tA, tB) : emit_range(tA, tB); };
+    LevelShape shape{};  // the batch's part of every level's shape
+    shape.N = N;
+    shape.n_trees = n_trees;
+    shape.split_after = split_after;
+    shape.rec_bytes = screen ? hstride : nstride;  // bytes of one normal as the margin pass streams it
+    shape.row_bytes = ds->row_bytes();
+    shape.hpitch = ds->hpitch;
+    shape.metric = ds->metric;
+    shape.screen = screen;
+    shape.screen8 = screen8;
+    shape.rows8_lo = sv.rows8_lo != nullptr;
+    shape.screen8_quality = ds->screen8_quality;
+    shape.rows_allowed = rows_allowed;
+    shape.subset = subset_ids != nullptr;
+    shape.mode_req = mode_req;
     auto run_levels = [&]() -> int {
     while (info.n_nodes) {
         if (opt->cancel && *opt->cancel) {
@@ -3382,153 +3577,36 @@ static int build_batch(ah_dataset *ds, const ah_build_options *opt, uint32_t fir
         const double ms_tail_prev = std::chrono::duration<double, std::milli>(t_level_top - t_prev_waited).count();
         const uint32_t n_nodes = info.n_nodes, n_tiles = info.n_tiles;
         AH_REQUIRE(n_nodes <= max_nodes && n_tiles <= max_tiles, AH_ERR_DEVICE, "forest build: node / tile bound exceeded");
-        const unsigned tile_grid = std::min<uint32_t>(n_tiles, g_tile_blocks);
+        const unsigned tile_grid = std::min<uint32_t>(n_tiles, knobs.tile_blocks);
         // The node-major margin kernels walk their tiles with a persistent grid: at the deep levels a tile is ~1200 items
         // (~2 MB of rows) and launching one workgroup per tile — 819 000 of them at level 13 of the 10M x 100 build — cost
         // 20 % of the level (measured: 306 -> 236 ms, the same 1.70 TB of fabric reads, TCC_EA0_RDREQ).  The small
         // bookkeeping kernels keep one tile per block (their random 1-byte / 4-byte gathers want every block in flight),
         // except the byte -> mask conversion of the top levels, whose reads are still nearly sequential.
-        const unsigned node_grid = g_node_blocks ? std::min<uint32_t>(n_tiles, g_node_blocks)
+        const unsigned node_grid = knobs.node_blocks ? std::min<uint32_t>(n_tiles, knobs.node_blocks)
                                                  : std::min<uint32_t>(n_tiles, std::max<uint32_t>(2048u, std::min<uint32_t>(65536u, n_tiles / 16u)));
         const unsigned masks_grid = n_nodes <= 4 * n_trees ? std::min<uint32_t>(tile_grid, 32768u) : tile_grid;
 
-        // ---- margin mode of the first attempt ------------------------------------------------------------------------
-        // Row-major streams all N rows once per group of row_tc trees; node-major reads only the still-active items, once
-        // per tree.  A forced mode (ah_build_options.margin_mode) pins the kernel family wherever it is legal.
-        const uint64_t rec_bytes = screen ? hstride : nstride;  // bytes of one normal as the margin pass streams it
+        // ---- plan the level (level_plan.h): the margin mode of its first attempt, its row-major launches, the tail in groups?
+        const uint64_t rec_bytes = shape.rec_bytes;
         const uint64_t nodes_per_tree = (n_nodes + n_trees - 1) / n_trees;
-        uint32_t row_tc = 0, lds_tc = 0, lds_worst = 0;
-        double best_cost = -1.0;  // AUTO: modelled cost in ns of the cheapest of node-major / row-major for this level
-        if (grouped) {
-            // a tree group of the tail: node-major (what the level it was cut from had chosen)
-        } else if (rows_allowed && mode_req == AH_MARGIN_AUTO) {
-            // Cost model in ns per row of 3072 bytes, fitted to per-level rocprofv3 traces of the 10M x 768 x 100-tree
-            // build (profiles/): node-major = one HBM read of the row per (item, tree) pair; row-major = per pass and
-            // row the HBM read of the row plus row_tc normals through the vector memory pipeline (L2 while the group's
-            // normals of the level fit, the fabric beyond), scaled by the share of (row, tree) pairs still splitting,
-            // plus the node_of / mask conversion of the level.
-            // costs in ns, for rows of this dataset's size: node-major = one HBM read of the row per (item, tree) pair
-            // (0.47 ns per 3072-byte row at 6.7 TB/s; the screen reads half the bytes)
-            const double scale = screen ? (double)ds->hpitch * 2 / 1536.0 : (double)ds->row_bytes() / 3072.0;
-            // (with the int8 first stage: 768 bytes + ~10 % x 768 (second digit) per pair on data that quantises like the
-            // benchmark's; worse data decide less there: scaled by the quality figure ensure_screen8 measured)
-            // (measured, 10M x 768 x 100 trees: 0.130-0.142 ns per pair on uniform rows, quality 0.12, 0.140-0.151 on ~N(0,1)
-            // rows, quality 0.18, with the rows' second digit as stage 1; 0.152-0.170 / 0.170-0.186 with the binary16 row)
-            // (+0.02: the row-major entries of the tables below carry their mask conversion twice — level 9 of that build,
-            // measured both ways, takes 130.7 ms row-major and 136.9 ms node-major, and this keeps it row-major)
-            const double node8_ns = sv.rows8_lo ? std::min(0.24, 0.135 + 0.15 * ds->screen8_quality)
-                                                : std::min(0.24, 0.155 + 0.125 * ds->screen8_quality);
-            const double node_ns = screen ? (screen8 && ds->metric != AH_DOT_PRODUCT ? node8_ns : 0.24) : 0.47;
-            const double active = (double)info.pairs / ((double)n_trees * (double)N);
-            const double cost_node = (double)info.pairs * node_ns * scale;
-            const double convert = (double)n_trees * (double)N *
-                                   ((prev_rows && g_rows_advance ? 0.007 : 0.01 + 0.03 * std::min(1.0, (double)nodes_per_tree / 256.0)) +
-                                    0.012 * std::min(1.0, (double)nodes_per_tree / 512.0));
-            // A tc-slot schedule costs what its launches cost: the full groups in one chunk-major launch, then the groups the
-            // launch loop below forms for the last trees (16 + ... + 4, or one more full group when only a few of its slots
-            // would idle: idle slots cost what busy ones cost), each a launch of its own and priced as the pass of ITS size.
-            // The table of pass costs was fitted on 96-tree builds, six or more groups in flight; a launch of one or two
-            // 16-slot groups has the L2s to itself and behaves like one with half the normals (13-tree share, levels 6-9
-            // forced both ways: 13.1 / 13.5 / 15.5 / 21.7 ms as one 16-slot pass — the table says 12.5 / 13.1 / 14.7 / 20.5
-            // that way — and 16.9 / 17.2 / 17.8 / 20.7 as 8 + 4 + 1, which the table prices as it stands).
-            // Counting 13 trees as 13/16 of a 16-slot pass and 13/8 of an 8-slot one kept level 5 of that share row-major
-            // (13 ms; the dense product takes 11), level 8 on 8 + 4 + 1 and level 9 row-major (19.5; node-major 18.3).
-            double best = 0.97 * cost_node;
-            const double floor_ns = screen ? 0.15 : 0.45;  // the read of the row alone (screened: mostly Infinity Cache)
-            auto launch_ns_per_row = [&](uint32_t tcv, uint32_t groups) {
-                double ws_mb = (double)((uint64_t)tcv * nodes_per_tree * rec_bytes) / 1e6;
-                if (groups <= 2 && tcv >= 16) ws_mb *= 0.5;
-                return groups * (floor_ns + (rows_pass_ns_per_row(tcv, ws_mb, screen) - floor_ns) * std::min(1.0, active * 1.05));
-            };
-            for (uint32_t tc = std::min(16u, g_rows_max_tc); tc >= 2; tc >>= 1) {
-                if (tc > 2 && tc / 2 >= n_trees) continue;  // do not instantiate more slots than trees
-                const double ws_mb = (double)((uint64_t)tc * nodes_per_tree * rec_bytes) / 1e6;
-                if (g_rows_cache_mb > 0 && ws_mb > g_rows_cache_mb) continue;
-                double ns_per_row = n_trees / tc ? launch_ns_per_row(tc, n_trees / tc) : 0.0;
-                for (uint32_t t0 = n_trees / tc * tc; t0 < n_trees;) {
-                    const uint32_t rem = n_trees - t0;
-                    uint32_t tcv = tc;
-                    while (tcv > 2 && tcv > rem) tcv >>= 1;
-                    for (uint32_t up = tcv << 1; up <= tc && tcv < rem; up <<= 1)
-                        if (up >= rem && up - rem <= (up >= 16 ? 3u : 1u)) tcv = up;
-                    ns_per_row += launch_ns_per_row(tcv, 1);
-                    t0 += std::min(tcv, rem);
-                }
-                const double cost_rows = (double)N * ns_per_row * scale + convert;
-                if (cost_rows < best || (g_rows_force == 1 && row_tc == 0)) {
-                    best = std::min(best, cost_rows);
-                    row_tc = tc;
-                }
-            }
-            best_cost = best;
-        } else if (rows_allowed && mode_req != AH_MARGIN_DENSE_MFMA) {
-            row_tc = mode_req & 0xFFu;
-        }
-        // Dense screen of the level on the matrix units (dense_device.h): one product rows x normals^T instead of
-        // n_trees / tc passes.  Cost: the rows leave HBM once (binary16), hpitch multiply-adds per (row, column) at the
-        // sustained MFMA rate, an epilogue per (row, tree), and the reference arithmetic for the pairs left open.
-        bool dense = false;
+        shape.n_nodes = n_nodes;
+        shape.pairs = info.pairs;
+        shape.prev_rows = prev_rows;
+        shape.grouped = grouped;
+        shape.fork_now = fork_now;
         // (a launch carries at most 2^32 - 1 work-items: threads x row tiles x column tiles of the shape the level would take)
         const DensePlan dp_legal = dense_plan(N, std::max(n_nodes, 1u));
-        const bool dense_legal = !grouped && rows_allowed && screen && g_dense != 0 && n_nodes <= g_dense_max_cols &&
-                                 (dp_legal.grid + 64) * (uint64_t)dp_legal.threads < 0xFFFFFFFFull && dp_legal.grid < 0x7FFFFFFFull;
-        if (dense_legal && mode_req == AH_MARGIN_DENSE_MFMA) {
-            dense = true;
-        } else if (dense_legal && mode_req == AH_MARGIN_AUTO) {
-            // measured (10M x 768, 100 and 13 trees, gpurun_out/dense): the product itself 0.17 ns per row + 0.0023 ns per
-            // (row, tree) of epilogue + hpitch multiply-adds per (row, padded column) at 495e3 MAC/ns (990 TF), never below
-            // the 0.40 ns per row of the narrow kernel; 0.008 ns per pair for k_forest_exact_pairs
-            const uint32_t bn = n_nodes > 128 ? 256u : 128u;
-            const double cols = (double)(((uint64_t)n_nodes + bn - 1) / bn * bn);
-            const double hscale = (double)ds->hpitch / 768.0;
-            // (short rows: a tile's k-loop is a few latency-bound steps and the epilogue does not shrink with the row — never
-            // below 0.25 ns per row; the exact pass scans a byte per pair whatever the row length)
-            const double per_row = std::max(std::max(0.40 * hscale, 0.25), 0.17 * hscale + 0.0023 * n_trees + cols * (double)ds->hpitch / g_dense_gmacs);
-            const double convert = (double)n_trees * (double)N * (prev_rows && g_rows_advance ? 0.007 : 0.04);
-            const double cost_dense = (double)N * per_row + (double)info.pairs * (0.002 + 0.006 * (double)ds->row_bytes() / 3072.0) + convert;
-            dense = g_dense == 1 || best_cost < 0 || cost_dense < best_cost;
+        shape.dense_grid_legal = (dp_legal.grid + 64) * (uint64_t)dp_legal.threads < 0xFFFFFFFFull && dp_legal.grid < 0x7FFFFFFFull;
+        shape.tree_first = tree_first.data();
+        const LevelPlan plan = plan_level(shape, knobs);
+        tree_first = plan.tree_first;  // (with its gaps closed where the LDS variant was wanted)
+        if (plan.fork) {  // the level is handed back unlaunched: run_tail_groups cuts it into groups of trees
+            fork_now = true;
+            return AH_OK;
         }
-        if (dense) row_tc = 16;  // the level is row-major as far as node_of / side_bytes / the next level are concerned
-        // Top levels: all normals of a group of >= 8 trees fit in LDS -> the LDS-resident variant of the row-major pass.
-        const bool want_lds = dense ? false : mode_req == AH_MARGIN_AUTO ? g_rows_lds && row_tc >= 2 : (mode_req & 0x100u) != 0;
-        if (!grouped && rows_allowed && want_lds && (rec_bytes & 15) == 0) {
-            tree_first[n_trees] = n_nodes;  // trees without a node in this level start where the next tree starts
-            for (uint32_t t = n_trees; t-- > 0;) tree_first[t] = std::min(tree_first[t], tree_first[t + 1]);
-            // measured per tree and row: screened 0.039 ns for 16-tree groups, 0.040 for 8-tree groups; f32 0.061 / 0.070
-            const uint32_t tc_hi = mode_req == AH_MARGIN_AUTO ? std::min<uint32_t>(16, g_rows_max_tc) : (mode_req & 0xFFu);
-            const uint32_t tc_lo = mode_req == AH_MARGIN_AUTO ? 8u : tc_hi;
-            for (uint32_t tc = tc_hi; tc >= tc_lo && tc >= 8; tc >>= 1) {
-                uint32_t worst = 0;
-                for (uint32_t t0 = 0; t0 < n_trees; t0 += tc)
-                    worst = std::max(worst, tree_first[std::min(n_trees, t0 + tc)] - tree_first[t0]);
-                if ((uint64_t)worst * rec_bytes <= kLdsNormalsBytes) {
-                    lds_tc = tc;
-                    lds_worst = worst;
-                    break;
-                }
-            }
-            if (lds_tc) row_tc = lds_tc;
-            else if (mode_req != AH_MARGIN_AUTO) row_tc = 0;  // a forced LDS mode that does not fit: node-major
-        }
-
-        // ---- the tail in groups? (see above) ---------------------------------------------------------------------------
-        // This level would run node-major, most of its children will be Descendants nodes (fewer than 2 x split_after
-        // items per node on average), every tree still has nodes in it, and the ids under them are worth the trouble:
-        // hand the level back unlaunched; the caller cuts it into groups of trees.
-        // (Skewed data — clusters of duplicates that keep a few nodes large for another thirty levels while most of the
-        // forest is done — never meet the first condition and stay level by level: cut at the level where a tenth of the
-        // ids is final, the 10M x 100-tree build on AH_SYNTH_CLUSTERED rows ran 29 levels five times over, 2.56 s against
-        // 2.46: every level carries four attempts' launches whatever its size.)
-        if (!grouped && !fork_now && g_tail_groups >= 2 && n_trees >= 2 && !subset_ids && row_tc < 2 && !dense &&
-            info.pairs >= g_tail_min_items && (double)info.pairs <= g_tail_node_items * (double)split_after * (double)n_nodes) {
-            bool all = true;
-            for (uint32_t t = 0; t < n_trees && all; t++)
-                all = tree_first[t] != 0xFFFFFFFFu && (t == 0 ? tree_first[0] == 0 : tree_first[t] > tree_first[t - 1]);
-            if (all) {
-                fork_now = true;
-                return AH_OK;
-            }
-        }
+        const uint32_t row_tc = plan.row_tc, lds_tc = plan.lds_tc;
+        const bool dense = plan.dense;
         hipLaunchKernelGGL(k_build_tiles, dim3(std::min<uint32_t>((n_nodes + 3) / 4, kMaxBlocks)), dim3(256), 0, s, d_cur,
                            n_nodes, d_tiles.p);
         uint8_t *chunk_d = nullptr, *shadow_d = nullptr, *shadow8_d = nullptr;
@@ -3553,15 +3631,14 @@ static int build_batch(ah_dataset *ds, const ah_build_options *opt, uint32_t fir
             const uint64_t next_len = normals_cap > next_begin ? std::min<uint64_t>(normals_cap - next_begin, predicted) : 0;
             touch_normals[(step + 1) & 1].start(forest->normals_blob, next_begin, (size_t)next_len);
         }
+        LevelBufs lb{dv, sv, ds->metric, ds->device, s, N, n_trees, n_nodes, n_tiles, d_cur, d_tiles.p, cur, chunk_d, nstride, hdr_off,
+                     shadow_d, hstride, shadow8_d, stride8, masks.p, tile_left.p, node_of.p, side_bytes.p, side_bits.p, d_counters,
+                     d_abort, d_abort, verify};
         for (int attempt = 0; attempt < 4; attempt++) {
             // (attempts 1-3: gated by the number of nodes the attempt before left pending, d_small[attempt])
-            const uint32_t *gate = attempt && g_retry_gate ? d_small.p + attempt : nullptr;
-            const AbortFlags abort_a{d_small.p, gate};
-#define AH_SPLIT_LAUNCH(K)                                                                                             \
-    hipLaunchKernelGGL(K, dim3(std::min<uint32_t>(n_nodes, g_split_blocks)), dim3(64), cs_shared, s, dv, d_cur, n_nodes, cur, N, \
-                       chunk_d, nstride, hdr_off, gate)
-            AH_SPLIT_KERNEL(AH_SPLIT_LAUNCH)
-#undef AH_SPLIT_LAUNCH
+            const uint32_t *gate = attempt && knobs.retry_gate ? d_small.p + attempt : nullptr;
+            lb.abort_gated = AbortFlags{d_small.p, gate};
+            AH_TRY(launch_create_split(lb, split_metric, std::min<uint32_t>(n_nodes, knobs.split_blocks), cs_shared));
             AH_DBG(s, "create_split");
             if (screen)
                 hipLaunchKernelGGL(k_forest_shadow_normals, dim3(std::min<uint32_t>(n_nodes, attempt ? 65536u : 1u << 20)), dim3(64), 0, s,
@@ -3573,7 +3650,7 @@ static int build_batch(ah_dataset *ds, const ah_build_options *opt, uint32_t fir
             AH_HIP(hipEventRecord(bc.ev_attempt[2 * attempt], s));
             if (attempt == 0 && row_tc >= 2) {
                 // one pass over the rows serves up to row_tc trees (see k_forest_margin_rows)
-                if (prev_rows && g_rows_advance) {
+                if (prev_rows && knobs.rows_advance) {
                     hipLaunchKernelGGL(k_forest_advance_node_of, dim3(kMaxBlocks), dim3(kBlock), 0, s, node_of.p, side_bytes.p,
                                        d_child.p, (uint64_t)n_trees * N);
                     if (info.n_fix)
@@ -3584,198 +3661,19 @@ static int build_batch(ah_dataset *ds, const ah_build_options *opt, uint32_t fir
                     hipLaunchKernelGGL(k_forest_assign_node_of, dim3(tile_grid), dim3(kBlock), 0, s, d_cur, d_tiles.p, n_tiles,
                                        cur, N, node_of.p, 0u);
                 }
-                uint32_t passes = 0;
+                uint32_t passes = dense ? 1u : 0u;  // (row-major: one per group of trees)
+                for (const RowsLaunch &l : plan.launches) passes += l.groups;
                 if (dense) {
-                    DenseArgs da{};
-                    da.rows = sv.rows;
-                    da.stats = sv.stats;
-                    da.headers = dv.headers;
-                    da.n = N;
-                    da.hpitch = sv.hpitch;
-                    da.shadow = shadow_d;
-                    da.hstride = hstride;
-                    da.n_cols = n_nodes;
-                    da.nodes = d_cur;
-                    da.node_of = node_of.p;
-                    da.side_bytes = side_bytes.p;
-                    // accumulation error of the product: every one of the hpitch exact binary16 products enters one f32
-                    // chain; whatever the order and the rounding mode of the matrix unit's adders (nearest or truncating,
-                    // aligned to the largest addend of a 16-wide step or not), the sum is off by less than
-                    // (hpitch + hpitch / 16) * 2^-23 * sum |x~_i n~_i|; taken twice over
-                    da.gamma_s = (float)(2.0 * ((double)sv.hpitch + (double)sv.hpitch / 16 + 16.0) * 1.1920929e-7);
-                    da.gamma_r = sv.gamma_r;
-                    const DensePlan dp = dense_plan(N, n_nodes);
-                    da.n_row_tiles = dp.n_row_tiles;
-                    da.n_col_tiles = dp.n_col_tiles;
-                    da.group = dp.group;
-                    da.verify = verify;
-                    const bool wide = dp.wide;
-                    const uint64_t dgrid = dp.grid;
-                    AH_REQUIRE(dgrid < 0x7FFFFFFFull, AH_ERR_INVALID_ARGUMENT, "forest build: too many tiles for one launch");
-                    const unsigned egrid = exact_pairs_grid(N, n_trees);
-#define AH_DENSE_WN(M, WNV)                                                                                              \
-    do {                                                                                                                 \
-        static std::atomic<bool> dense_opt_in[64]; /* once per instantiation and device */                              \
-        if (!dense_opt_in[ds->device & 63].load(std::memory_order_acquire)) {                                            \
-            AH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_forest_dense_screen<M, WNV>),                    \
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)kDenseLds));                     \
-            dense_opt_in[ds->device & 63].store(true, std::memory_order_release);                                        \
-        }                                                                                                                \
-        hipLaunchKernelGGL((k_forest_dense_screen<M, WNV>), dim3((unsigned)dgrid), dim3(DenseShape<WNV>::kThreads),      \
-                           kDenseLds, s, da, d_abort);                                                                   \
-    } while (0)
-#define AH_DENSE_NARROW(M, NTV)                                                                                          \
-    do {                                                                                                                 \
-        if (dp.stream)                                                                                                   \
-            hipLaunchKernelGGL((k_forest_dense_narrow<M, NTV, true>), dim3((unsigned)dgrid), dim3(kNarrowThreads),       \
-                               NarrowShape<NTV>::kLds, s, da, d_abort);                                                  \
-        else                                                                                                             \
-            hipLaunchKernelGGL((k_forest_dense_narrow<M, NTV, false>), dim3((unsigned)dgrid), dim3(kNarrowThreads),      \
-                               NarrowShape<NTV>::kLds, s, da, d_abort);                                                  \
-    } while (0)
-#define AH_DENSE(M)                                                                                                      \
-    do {                                                                                                                 \
-        if (dp.narrow == 2) AH_DENSE_NARROW(M, 2);                                                                       \
-        else if (dp.narrow == 4) AH_DENSE_NARROW(M, 4);                                                                  \
-        else if (wide) AH_DENSE_WN(M, 4);                                                                                \
-        else AH_DENSE_WN(M, 2);                                                                                          \
-        if (tun(TUN_EXACT_WIDE) != 0)                                                                                    \
-            hipLaunchKernelGGL((k_forest_exact_pairs<M, true>), dim3(egrid), dim3(256), 0, s, dv, node_of.p, side_bytes.p, \
-                               n_trees, chunk_d, nstride, hdr_off, d_counters, d_abort);                                 \
-        else                                                                                                             \
-            hipLaunchKernelGGL((k_forest_exact_pairs<M>), dim3(egrid), dim3(256), 0, s, dv, node_of.p, side_bytes.p,     \
-                               n_trees, chunk_d, nstride, hdr_off, d_counters, d_abort);                                 \
-    } while (0)
-                    switch (ds->metric) {
-                    case AH_EUCLIDEAN: AH_DENSE(AH_EUCLIDEAN); break;
-                    case AH_MANHATTAN: AH_DENSE(AH_MANHATTAN); break;
-                    case AH_COSINE: AH_DENSE(AH_COSINE); break;
-                    default: AH_DENSE(AH_DOT_PRODUCT); break;
-                    }
-#undef AH_DENSE_WN
-#undef AH_DENSE_NARROW
-#undef AH_DENSE
-                    forest->stats.dense_launches++;
-                    forest->stats.dense_columns += n_nodes;
-                    passes = 1;
+                    AH_TRY(launch_dense(lb, dense_plan(N, n_nodes), knobs.exact_wide, forest->stats));
                 } else if (screen) {
-                    // Chunk-major launches (RowsSchedule): all full groups of the level in ONE launch, so that the passes over a
-                    // chunk of rows run back to back and find it in the Infinity Cache; the last trees (fewer than a group) in
-                    // launches of their own.  The LDS variant reads the first node of every tree from a device copy.
-                    const uint32_t gtc = lds_tc ? lds_tc : row_tc;
-                    ScreenRowsArgs ra{dv, sv, node_of.p, 0, 0, chunk_d, nstride, hdr_off, shadow_d, hstride, side_bytes.p,
-                                      RowsSchedule{}, d_abort, d_counters, verify};
                     if (lds_tc) {
                         memcpy(h_tree_first, tree_first.data(), ((size_t)n_trees + 1) * 4);
                         AH_HIP(hipMemcpyAsync(d_tree_first_fixed, h_tree_first, ((size_t)n_trees + 1) * 4, hipMemcpyHostToDevice, s));
                     }
-                    const size_t lds_sh = (size_t)lds_worst * rec_bytes;
-                    auto launch = [&](uint32_t tcv, uint32_t t0, uint32_t groups, uint32_t np) -> int {
-                        RowsPlan plan;
-                        AH_TRY(plan_rows_launches(N, sv.hpitch, tcv, groups, lds_tc != 0, (uint64_t)tcv * nodes_per_tree * rec_bytes, &plan));
-                        ra.tree_base = t0;
-                        ra.n_pass = np;
-                        ra.sch = plan.sch;
-                        ra.sch.tree_first = d_tree_first_fixed;
-                        for (const auto &l : plan.launches) {
-                            ra.sch.chunk0 = l.first;
-                            AH_TRY(launch_screen_rows(ds->metric, tcv, lds_tc != 0, ra, l.second, lds_sh, s, ds->device));
-                        }
-                        forest->stats.margin_mode_launches[lds_tc ? (tcv >= 16 ? MM_LDS16 : MM_LDS8) : mm_rows(tcv)]++;
-                        forest->stats.rows_xcd_launches += plan.xcd ? plan.launches.size() : 0;
-                        forest->stats.rows_nt_launches += plan.nt ? plan.launches.size() : 0;
-                        forest->stats.rows_split_launches += plan.launches.size() - 1;
-                        passes += groups;
-                        return AH_OK;
-                    };
-                    const uint32_t full = n_trees / gtc;
-                    if (full) AH_TRY(launch(gtc, 0, full, gtc));
-                    for (uint32_t t0 = full * gtc; t0 < n_trees;) {
-                        // The last trees take the largest instantiation that they fill, or the next larger one when only a few
-                        // of its slots would idle (13 trees: one 16-slot pass, measured 15 ms, instead of 8 + 4 + 1: 18-23 ms;
-                        // spare slots repeat the last tree).  LDS groups exist for 8 and 16 trees only.
-                        const uint32_t rem = n_trees - t0;
-                        uint32_t tcv = gtc;
-                        if (!lds_tc) {
-                            while (tcv > 2 && tcv > rem) tcv >>= 1;
-                            for (uint32_t up = tcv << 1; up <= gtc && tcv < rem; up <<= 1)
-                                if (up >= rem && up - rem <= (up >= 16 ? 3u : 1u)) tcv = up;
-                        }
-                        const uint32_t np = std::min<uint32_t>(tcv, rem);
-                        AH_TRY(launch(tcv, t0, 1, np));
-                        t0 += np;
-                    }
-                }
-                const unsigned row_grid = (unsigned)std::min<uint64_t>((N + 31) / 32, g_row_blocks);
-                for (uint32_t t0 = 0; t0 < n_trees && lds_tc && !screen; t0 += lds_tc) {
-                    const uint32_t np = std::min<uint32_t>(lds_tc, n_trees - t0);
-                    const uint32_t first = tree_first[t0], cnt = tree_first[t0 + np] - first;
-                    if (cnt == 0) continue;
-                    const size_t sh = (size_t)cnt * rec_bytes;
-                    const unsigned per_cu = (unsigned)std::max<size_t>(1, std::min<size_t>(2, (150u << 10) / std::max<size_t>(sh, 1)));
-                    const unsigned lthreads = lds_tc >= 16 ? 512u : 1024u;
-                    const unsigned lgrid = (unsigned)std::min<uint64_t>((N * 8 + lthreads - 1) / lthreads, 256u * per_cu);
-#define AH_LDS_OPT_IN(KERNEL)                                                                                          \
-    do {                                                                                                               \
-        static std::atomic<bool> lds_opt_in[64]; /* once per instantiation and device */                               \
-        if (!lds_opt_in[ds->device & 63].load(std::memory_order_acquire)) {                                            \
-            AH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                       (int)kLdsNormalsBytes));                                                        \
-            lds_opt_in[ds->device & 63].store(true, std::memory_order_release);                                        \
-        }                                                                                                              \
-    } while (0)
-#define AH_ROWS_LDS(M, TCV)                                                                                              \
-    do {                                                                                                                 \
-        AH_LDS_OPT_IN((k_forest_margin_rows_lds<M, TCV>));                                                               \
-        hipLaunchKernelGGL((k_forest_margin_rows_lds<M, TCV>), dim3(lgrid), dim3(lthreads), sh, s, dv, node_of.p, t0, np,  \
-                           chunk_d, nstride, hdr_off, side_bytes.p, first, cnt, d_abort);                                \
-    } while (0)
-#define AH_ROWS_LDS_TC(M)                  \
-    if (lds_tc == 16) AH_ROWS_LDS(M, 16);  \
-    else AH_ROWS_LDS(M, 8)
-                    switch (ds->metric) {
-                    case AH_EUCLIDEAN: AH_ROWS_LDS_TC(AH_EUCLIDEAN); break;
-                    case AH_MANHATTAN: AH_ROWS_LDS_TC(AH_MANHATTAN); break;
-                    case AH_COSINE: AH_ROWS_LDS_TC(AH_COSINE); break;
-                    default: AH_ROWS_LDS_TC(AH_DOT_PRODUCT); break;
-                    }
-#undef AH_ROWS_LDS_TC
-#undef AH_ROWS_LDS
-                    forest->stats.margin_mode_launches[lds_tc == 16 ? MM_LDS16 : MM_LDS8]++;
-                }
-                for (uint32_t t0 = 0; t0 < n_trees && !lds_tc && !screen;) {
-                    // The last trees of the forest take the largest instantiation that they fill (16 + 16 + ... + 4), or the
-                    // next larger one when only a few of its slots would idle (13 trees: one 16-slot pass, measured 15 ms,
-                    // instead of 8 + 4 + 1: 18-23 ms; spare slots repeat the last tree).
-                    const uint32_t rem = n_trees - t0;
-                    uint32_t tcv = row_tc;
-                    while (tcv > 2 && tcv > rem) tcv >>= 1;
-                    for (uint32_t up = tcv << 1; up <= row_tc && tcv < rem; up <<= 1)
-                        if (up >= rem && up - rem <= (up >= 16 ? 3u : 1u)) tcv = up;
-                    const uint32_t np = std::min<uint32_t>(tcv, rem);
-#define AH_ROWS(M, TCV)                                                                                                    \
-    do {                                                                                                                   \
-        hipLaunchKernelGGL((k_forest_margin_rows<M, TCV>), dim3(row_grid), dim3(kBlock), 0, s, dv, node_of.p, t0, np,      \
-                           chunk_d, nstride, hdr_off, side_bytes.p, d_abort);                                              \
-    } while (0)
-#define AH_ROWS_TC(M)                       \
-    switch (tcv) {                          \
-    case 16: AH_ROWS(M, 16); break;         \
-    case 8: AH_ROWS(M, 8); break;           \
-    case 4: AH_ROWS(M, 4); break;           \
-    default: AH_ROWS(M, 2); break;          \
-    }
-                    switch (ds->metric) {
-                    case AH_EUCLIDEAN: AH_ROWS_TC(AH_EUCLIDEAN); break;
-                    case AH_MANHATTAN: AH_ROWS_TC(AH_MANHATTAN); break;
-                    case AH_COSINE: AH_ROWS_TC(AH_COSINE); break;
-                    default: AH_ROWS_TC(AH_DOT_PRODUCT); break;
-                    }
-#undef AH_ROWS_TC
-#undef AH_ROWS
-                    forest->stats.margin_mode_launches[mm_rows(tcv)]++;
-                    passes++;
-                    t0 += np;
+                    AH_TRY(launch_rows_screened(lb, plan, nodes_per_tree, rec_bytes, d_tree_first_fixed, knobs.lds_normals_bytes, forest->stats));
+                } else {
+                    AH_TRY(launch_rows_f32(lb, plan, rec_bytes, (unsigned)std::min<uint64_t>((N + 31) / 32, knobs.row_blocks),
+                                           knobs.lds_normals_bytes, forest->stats));
                 }
                 if (side_bits.p) {
                     const uint64_t n_words = ((uint64_t)n_trees * N + 31) / 32;
@@ -3784,59 +3682,12 @@ static int build_batch(ah_dataset *ds, const ah_build_options *opt, uint32_t fir
                 }
                 hipLaunchKernelGGL(k_forest_masks_from_bytes, dim3(masks_grid), dim3(kBlock), 0, s, d_cur, d_tiles.p, n_tiles,
                                    cur, N, side_bytes.p, side_bits.p, masks.p, tile_left.p);
-                if (lds_tc && !screen) passes = (n_trees + lds_tc - 1) / lds_tc;
                 forest->stats.margin_row_passes += passes;
                 if (screen) forest->stats.screened_launches += passes;
-            } else if (bq) {
-                hipLaunchKernelGGL(k_forest_margin_bq, dim3(node_grid), dim3(kBlock), dv.pitch * 8, s, dv, d_cur, d_tiles.p,
-                                   n_tiles, cur, N, chunk_d, nstride, hdr_off, masks.p, tile_left.p, abort_a);
-                forest->stats.margin_mode_launches[MM_BQ]++;
-            } else if (screen) {
-                const size_t sh = (size_t)dv.pitch * 4 + (size_t)sv.hpitch * 2 + (screen8 ? 2 * (size_t)sv.pitch8 : 0);
-                // rows of at most six 128-byte int8 steps (768 dimensions): the pipelined variant of the int8 stage
-                const bool node_pre = screen8 && ds->metric != AH_DOT_PRODUCT && sv.pitch8 <= 6 * 128 && tun(TUN_NODE_PREFETCH) != 0;
-#define AH_LAUNCH_PRE(M, PRE)                                                                                            \
-    do {                                                                                                                  \
-        if (sh > 48 * 1024) /* very long vectors: opt in to more dynamic LDS than the default limit */                    \
-            AH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_forest_screen_node<M, PRE>),                      \
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));                             \
-        hipLaunchKernelGGL((k_forest_screen_node<M, PRE>), dim3(node_grid), dim3(kBlock), sh, s, dv, sv, d_cur, d_tiles.p, \
-                           n_tiles, cur, chunk_d, nstride, hdr_off, shadow_d, hstride, shadow8_d, stride8, masks.p,       \
-                           tile_left.p, abort_a, d_counters, verify);                                                     \
-    } while (0)
-#define AH_LAUNCH(M)                          \
-    do {                                      \
-        if (node_pre) AH_LAUNCH_PRE(M, 6);    \
-        else AH_LAUNCH_PRE(M, 0);             \
-    } while (0)
-                switch (ds->metric) {
-                case AH_EUCLIDEAN: AH_LAUNCH(AH_EUCLIDEAN); break;
-                case AH_MANHATTAN: AH_LAUNCH(AH_MANHATTAN); break;
-                case AH_COSINE: AH_LAUNCH(AH_COSINE); break;
-                default: AH_LAUNCH(AH_DOT_PRODUCT); break;
-                }
-#undef AH_LAUNCH
-#undef AH_LAUNCH_PRE
-                forest->stats.margin_mode_launches[MM_NODE]++;
-                forest->stats.screened_launches++;
             } else {
-                const size_t sh = (size_t)dv.pitch * 4;
-#define AH_LAUNCH(M)                                                                                                \
-    do {                                                                                                            \
-        if (sh > 48 * 1024)                                                                                         \
-            AH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_forest_margin_f32<M>),                      \
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));                       \
-        hipLaunchKernelGGL((k_forest_margin_f32<M>), dim3(node_grid), dim3(kBlock), sh, s, dv, d_cur, d_tiles.p,    \
-                           n_tiles, cur, N, chunk_d, nstride, hdr_off, masks.p, tile_left.p, abort_a);              \
-    } while (0)
-                switch (ds->metric) {
-                case AH_EUCLIDEAN: AH_LAUNCH(AH_EUCLIDEAN); break;
-                case AH_MANHATTAN: AH_LAUNCH(AH_MANHATTAN); break;
-                case AH_COSINE: AH_LAUNCH(AH_COSINE); break;
-                default: AH_LAUNCH(AH_DOT_PRODUCT); break;
-                }
-#undef AH_LAUNCH
-                forest->stats.margin_mode_launches[MM_NODE]++;
+                // rows of at most six 128-byte int8 steps (768 dimensions): the pipelined variant of the int8 stage
+                const bool node_pre = screen8 && ds->metric != AH_DOT_PRODUCT && sv.pitch8 <= 6 * 128 && knobs.node_prefetch;
+                AH_TRY(launch_node_major(lb, bq, screen, screen8, node_pre, node_grid, forest->stats));
             }
             AH_HIP(hipEventRecord(bc.ev_attempt[2 * attempt + 1], s));
             AH_DBG(s, "margin");
@@ -3940,7 +3791,7 @@ static int build_batch(ah_dataset *ds, const ah_build_options *opt, uint32_t fir
     };
     auto run_tail_groups = [&]() -> int {
         if (!fork_now) return AH_OK;
-        const uint32_t K = std::min(g_tail_groups, n_trees);
+        const uint32_t K = std::min(knobs.tail_groups, n_trees);
         group_tree.resize(K + 1);
         GroupCuts cuts{};
         // shrinking groups: group g + 1 computes while group g's ids and normals travel (~0.76 of the time its kernels took at
