@@ -176,6 +176,11 @@ class AhParamsStats(C.Structure):
         "calls", "batches", "varied_batches", "queries", "varied_queries", "big_count_queries")]
 
 
+class AhExhaustedStats(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in (
+        "queries", "batches", "empty_queries", "lists_made", "list_ids", "leaves_walked")]
+
+
 NO_FILTER = 0xFFFFFFFF  # AH_NO_FILTER: a query of ah_search_batch_filters under no filter
 
 
@@ -286,6 +291,10 @@ SIGNATURES = {
     "ah_search_batch_params": (C.c_int, [_VP, _F32P, _U32P, C.c_size_t, C.POINTER(AhQueryParams), C.c_size_t,
                                          C.POINTER(C.c_void_p), C.c_size_t, _U32P, _U32P, _F32P, _U32P]),
     "ah_index_params_stats": (C.c_int, [_VP, C.POINTER(AhParamsStats), C.c_int]),
+    # exhausted filters (AH_SEARCH_EXHAUSTED)
+    "ah_filter_kept_total": (C.c_int, [_VP, C.POINTER(C.c_uint64)]),
+    "ah_filter_kept_ids": (C.c_int, [_VP, _U32P, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "ah_index_exhausted_stats": (C.c_int, [_VP, C.POINTER(AhExhaustedStats), C.c_int]),
     # filter expressions on the device, filters from bitmaps
     "ah_filter_combine": (C.c_int, [C.c_int, C.POINTER(C.c_void_p), C.c_size_t, C.POINTER(C.c_void_p),
                                     C.POINTER(AhFilterCombineStats)]),

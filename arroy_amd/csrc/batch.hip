@@ -154,6 +154,145 @@ __global__ __launch_bounds__(kBlock) void k_batch_distances_bq(DataView dv, cons
     }
 }
 
+// ---- one candidate list shared by every query of a sub-batch (the exhausted filters of search.hip) ---------------------
+// The dense block [rows of `list`] x [queries of the sub-batch].  A block takes kSharedSlab list rows against a group of up to
+// kSharedGroup queries, the group's leaves in LDS: a row leaves HBM once per group, not once per query.  Every accumulator
+// sees the operations of octet_reduce_stream (k_batch_distances_f32) in their order, so the distances carry its bits; the
+// Manhattan and the narrow (dims < 32) reductions are that kernel's, a query at a time.  Writes out[q * stride + i] and
+// replicates ids[q * stride + i] = list[i]: the top-k stage then reads one RerankSeg{q * stride, m, k} per query.
+static constexpr uint32_t kSharedSlab = 64;
+static constexpr int kSharedGroup = 16;
+
+template <int METRIC>
+__global__ __launch_bounds__(kBlock) void k_shared_list_distances(DataView dv, const uint8_t *__restrict__ qvecs, uint64_t qstride,
+                                                                  const float *__restrict__ qhdrs, uint32_t n_queries, uint32_t group,
+                                                                  const uint32_t *__restrict__ list, uint32_t m, uint64_t stride,
+                                                                  uint32_t *__restrict__ ids, float *__restrict__ out, uint32_t *err) {
+    constexpr int OP = METRIC == AH_EUCLIDEAN ? OP_EUCLID : OP_DOT;
+    extern __shared__ float4 s_q4[];
+    __shared__ float s_hdr[kSharedGroup];
+    const float *s_q = reinterpret_cast<const float *>(s_q4);
+    const uint32_t o = threadIdx.x >> 3, j = threadIdx.x & 7u;
+    const uint32_t q0 = blockIdx.y * group;
+    const uint32_t ng = min(group, n_queries - q0);  // block-uniform, 1 .. kSharedGroup
+    const uint32_t p4 = dv.pitch >> 2;
+    for (uint32_t g = 0; g < ng; g++) {
+        const float4 *src = reinterpret_cast<const float4 *>(qvecs + (uint64_t)(q0 + g) * qstride);
+        for (uint32_t i = threadIdx.x; i < p4; i += blockDim.x) s_q4[g * p4 + i] = src[i];
+    }
+    if (threadIdx.x < ng) s_hdr[threadIdx.x] = qhdrs[2 * (uint64_t)(q0 + threadIdx.x)];
+    __syncthreads();
+    const uint32_t first = blockIdx.x * kSharedSlab;
+    const uint32_t in_slab = min(kSharedSlab, m - first);
+    for (uint32_t p = o; p < in_slab; p += kBlock / 8) {
+        const uint32_t i = first + p;
+        const uint32_t id = list[i];
+        for (uint32_t g = j; g < ng; g += 8) ids[(uint64_t)(q0 + g) * stride + i] = id;
+        const uint64_t row = row_of_id(dv, id);
+        if (row == ~0ull) {  // octet-uniform
+            if (j == 0) atomicOr(err, 1u);
+            for (uint32_t g = j; g < ng; g += 8) out[(uint64_t)(q0 + g) * stride + i] = __uint_as_float(0x7FC00000u);
+            continue;
+        }
+        const float *rp = dv.rows_f32 + row * dv.pitch;
+        float r[kSharedGroup];
+        if (dv.dims >= 32 && METRIC != AH_MANHATTAN) {
+            const uint32_t blocks = dv.dims >> 5;
+            const float4 *r4 = reinterpret_cast<const float4 *>(rp) + j;
+            float4 acc[kSharedGroup];
+#pragma unroll
+            for (int g = 0; g < kSharedGroup; g++) acc[g] = make_float4(0.f, 0.f, 0.f, 0.f);
+            uint32_t k = 0;
+            for (; k + 8 <= blocks; k += 8) {
+                float4 x[8];
+#pragma unroll
+                for (int u = 0; u < 8; u++) x[u] = ld_stream(r4 + (k + u) * 8);
+#pragma unroll
+                for (int g = 0; g < kSharedGroup; g++)
+                    if ((uint32_t)g < ng) {
+                        const float4 *b4 = s_q4 + g * p4 + j;
+#pragma unroll
+                        for (int u = 0; u < 8; u++) fma_step<OP>(acc[g], b4[(k + u) * 8], x[u]);
+                    }
+            }
+            for (; k < blocks; k++) {
+                const float4 x = r4[k * 8];
+#pragma unroll
+                for (int g = 0; g < kSharedGroup; g++)
+                    if ((uint32_t)g < ng) fma_step<OP>(acc[g], s_q4[g * p4 + j + k * 8], x);
+            }
+#pragma unroll
+            for (int g = 0; g < kSharedGroup; g++)
+                if ((uint32_t)g < ng) r[g] = scalar_tail<OP>(octet_finish(acc[g]), s_q + g * dv.pitch, rp, blocks << 5, dv.dims);
+        } else {
+#pragma unroll
+            for (int g = 0; g < kSharedGroup; g++)
+                if ((uint32_t)g < ng) {
+                    const float *qg = s_q + g * dv.pitch;
+                    if (METRIC == AH_MANHATTAN && dv.dims >= 32) {
+                        r[g] = octet_manhattan(qg, rp, dv.dims, j);
+                    } else if (METRIC == AH_MANHATTAN) {
+                        float a = 0.0f;
+                        for (uint32_t e = 0; e < dv.dims; e++) a = f_add(a, fabsf(f_sub(qg[e], rp[e])));
+                        r[g] = a;
+                    } else {
+                        r[g] = thread_reduce_small<OP>(qg, rp, dv.dims);
+                    }
+                }
+        }
+        if (j == 0) {
+            const float rn = METRIC == AH_COSINE ? dv.headers[row] : 0.0f;
+#pragma unroll
+            for (int g = 0; g < kSharedGroup; g++)
+                if ((uint32_t)g < ng) {
+                    float d = r[g];
+                    if (METRIC == AH_COSINE) d = cosine_from_dot(r[g], s_hdr[g], rn);
+                    if (METRIC == AH_DOT_PRODUCT) d = -r[g];
+                    out[(uint64_t)(q0 + g) * stride + i] = d;
+                }
+        }
+    }
+}
+
+// The 1-bit variant: thread t takes list row t mod kSharedSlab against the queries g = t / kSharedSlab (mod 4) of the group.
+__global__ __launch_bounds__(kBlock) void k_shared_list_distances_bq(DataView dv, const uint8_t *__restrict__ qvecs, uint64_t qstride,
+                                                                     const float *__restrict__ qhdrs, uint32_t n_queries, uint32_t group,
+                                                                     const uint32_t *__restrict__ list, uint32_t m, uint64_t stride,
+                                                                     uint32_t *__restrict__ ids, float *__restrict__ out, uint32_t *err) {
+    extern __shared__ uint64_t s_qw[];
+    __shared__ float s_hdr[kSharedGroup];
+    const uint32_t q0 = blockIdx.y * group;
+    const uint32_t ng = min(group, n_queries - q0);
+    for (uint32_t g = 0; g < ng; g++) {
+        const uint64_t *src = reinterpret_cast<const uint64_t *>(qvecs + (uint64_t)(q0 + g) * qstride);
+        for (uint32_t i = threadIdx.x; i < dv.pitch; i += blockDim.x) s_qw[g * dv.pitch + i] = src[i];
+    }
+    if (threadIdx.x < ng) s_hdr[threadIdx.x] = qhdrs[2 * (uint64_t)(q0 + threadIdx.x)];
+    __syncthreads();
+    const uint32_t p = threadIdx.x & (kSharedSlab - 1u), sub = threadIdx.x / kSharedSlab;
+    const uint32_t i = blockIdx.x * kSharedSlab + p;
+    if (i >= m) return;
+    const uint32_t id = list[i];
+    const uint64_t row = row_of_id(dv, id);
+    if (row == ~0ull && sub == 0) atomicOr(err, 1u);
+    const uint64_t *rp = dv.rows_bq + (row == ~0ull ? 0 : row) * dv.pitch;
+    for (uint32_t g = sub; g < ng; g += kBlock / kSharedSlab) {
+        const uint64_t at = (uint64_t)(q0 + g) * stride + i;
+        ids[at] = id;
+        if (row == ~0ull) {
+            out[at] = __uint_as_float(0x7FC00000u);
+            continue;
+        }
+        uint32_t ham = 0;
+        for (uint32_t w = 0; w < dv.pitch; w++) ham += (uint32_t)__popcll(rp[w] ^ s_qw[g * dv.pitch + w]);
+        float d;
+        if (dv.metric == AH_BQ_EUCLIDEAN) d = (float)(ham * 4u);
+        else if (dv.metric == AH_BQ_MANHATTAN) d = (float)(ham * 2u);
+        else d = bq_cosine_from_dot((float)bq_dot_from_hamming(ham, dv.words), s_hdr[g], dv.headers[row]);
+        out[at] = d;
+    }
+}
+
 // ---- row-major ("inverted") distances -------------------------------------------------------------------
 // A big submission re-reads the same rows many times: 1000 queries x ~10.8k candidates over 1M items touch every
 // row ~11 times, and the query-major kernel above pays one HBM read of the row (4*dims bytes) per candidate.
@@ -795,10 +934,69 @@ int launch_prepare_queries_only(const DataView &dv, const float *d_q_f32, uint32
     return AH_OK;
 }
 
+// the top-k half: selection, tournament rounds and emit over distances that are already there (`any`: some list is not empty)
+int launch_batch_topk(const DataView &dv, const RerankBufs &b, bool any, uint32_t max_n, uint32_t k_out, uint32_t max_rounds,
+                      hipStream_t s) {
+    const uint32_t n_queries = b.n_queries;
+    if (any) {
+        hipLaunchKernelGGL(k_batch_topk_select, dim3(n_queries), dim3(kBlock), 0, s, b.d_segs, b.d_dist, b.d_ids, b.d_keys_a,
+                           b.d_keys_b, b.kstride);
+        uint32_t blocks_bound = (max_n + kChunk - 1) / kChunk;
+        for (uint32_t r = 0; r < max_rounds; r++) {
+            hipLaunchKernelGGL(k_batch_topk_round, dim3(blocks_bound, n_queries), dim3(kBlock), 0, s, b.d_segs, r, b.d_dist, b.d_ids,
+                               b.d_keys_a, b.d_keys_b, b.kstride);
+            blocks_bound = (blocks_bound * (kChunk / 2) + kChunk - 1) / kChunk;  // every round at least halves
+            if (blocks_bound < 1) blocks_bound = 1;
+        }
+    }
+    hipLaunchKernelGGL(k_batch_topk_emit, dim3((k_out + 255) / 256, n_queries), dim3(256), 0, s, dv, b.d_segs, b.d_dist, b.d_ids,
+                       b.d_keys_a, b.d_keys_b, b.kstride, k_out, b.d_out_ids, b.d_out_dist);
+    AH_HIP(hipGetLastError());
+    return AH_OK;
+}
+
+// The distances of `list` (m ascending ids) for every query of a sub-batch, replicated per query at `stride` (k_shared_list_distances).
+uint32_t shared_list_slab() { return kSharedSlab; }
+int launch_shared_list_distances(const DataView &dv, const uint8_t *d_qvecs, uint64_t qstride, const float *d_qhdrs, uint32_t n_queries,
+                                 const uint32_t *d_list, uint32_t m, uint64_t stride, uint32_t *d_ids, float *d_dist, uint32_t *d_err,
+                                 hipStream_t s) {
+    if (n_queries == 0 || m == 0) return AH_OK;
+    // the group's leaves share the 64 KiB of LDS a block may have without asking (the headers take 64 bytes of it)
+    const size_t leaf = metric_is_bq(dv.metric) ? (size_t)dv.pitch * 8 : (size_t)dv.pitch * 4;
+    const uint32_t group = (uint32_t)std::max<size_t>(1, std::min<size_t>(kSharedGroup, ((63u << 10) / leaf)));
+    const dim3 grid((m + kSharedSlab - 1) / kSharedSlab, (n_queries + group - 1) / group);
+    AH_REQUIRE(grid.y <= 65535u, AH_ERR_DEVICE, "internal: %u query groups in one launch", grid.y);
+    const size_t sh = group * leaf;
+    if (metric_is_bq(dv.metric)) {
+        hipLaunchKernelGGL(k_shared_list_distances_bq, grid, dim3(kBlock), sh, s, dv, d_qvecs, qstride, d_qhdrs, n_queries, group, d_list, m,
+                           stride, d_ids, d_dist, d_err);
+    } else {
+#define AH_LAUNCH(M)                                                                                                            \
+    hipLaunchKernelGGL((k_shared_list_distances<M>), grid, dim3(kBlock), sh, s, dv, d_qvecs, qstride, d_qhdrs, n_queries, group, d_list, \
+                       m, stride, d_ids, d_dist, d_err)
+        switch (dv.metric) {
+        case AH_EUCLIDEAN: AH_LAUNCH(AH_EUCLIDEAN); break;
+        case AH_MANHATTAN: AH_LAUNCH(AH_MANHATTAN); break;
+        case AH_COSINE: AH_LAUNCH(AH_COSINE); break;
+        default: AH_LAUNCH(AH_DOT_PRODUCT); break;
+        }
+#undef AH_LAUNCH
+    }
+    AH_HIP(hipGetLastError());
+    return AH_OK;
+}
+
+// the exclusive scan of up to a few hundred thousand block sums in place, their total to *d_total (k_scan_sums)
+int launch_scan_sums(uint32_t *d_sums, uint32_t n_sums, uint32_t *d_total, hipStream_t s) {
+    hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(256), 0, s, d_sums, n_sums, d_total);
+    AH_HIP(hipGetLastError());
+    return AH_OK;
+}
+
 // distances + tournament top-k + emit for queries whose leaves (qvecs / qhdrs) are already on the device
 int launch_rerank_batch_prepared(const DataView &dv, const RerankBufs &b, uint32_t max_n, uint32_t k_out, uint32_t max_rounds,
                                  uint64_t n_candidates, hipStream_t s) {
-    const uint32_t n_queries = b.n_queries, n_tiles = b.n_tiles;
+    const uint32_t n_tiles = b.n_tiles;
     if (n_tiles) {
         const unsigned grid = n_tiles < 4096u ? n_tiles : 4096u;
         if (b.d_inv_counters != nullptr && batch_invert_wanted(dv, n_candidates)) {  // row-major
@@ -823,20 +1021,8 @@ int launch_rerank_batch_prepared(const DataView &dv, const RerankBufs &b, uint32
             }
 #undef AH_LAUNCH
         }
-        hipLaunchKernelGGL(k_batch_topk_select, dim3(n_queries), dim3(kBlock), 0, s, b.d_segs, b.d_dist, b.d_ids, b.d_keys_a,
-                           b.d_keys_b, b.kstride);
-        uint32_t blocks_bound = (max_n + kChunk - 1) / kChunk;
-        for (uint32_t r = 0; r < max_rounds; r++) {
-            hipLaunchKernelGGL(k_batch_topk_round, dim3(blocks_bound, n_queries), dim3(kBlock), 0, s, b.d_segs, r, b.d_dist, b.d_ids,
-                               b.d_keys_a, b.d_keys_b, b.kstride);
-            blocks_bound = (blocks_bound * (kChunk / 2) + kChunk - 1) / kChunk;  // every round at least halves
-            if (blocks_bound < 1) blocks_bound = 1;
-        }
     }
-    hipLaunchKernelGGL(k_batch_topk_emit, dim3((k_out + 255) / 256, n_queries), dim3(256), 0, s, dv, b.d_segs, b.d_dist, b.d_ids,
-                       b.d_keys_a, b.d_keys_b, b.kstride, k_out, b.d_out_ids, b.d_out_dist);
-    AH_HIP(hipGetLastError());
-    return AH_OK;
+    return launch_batch_topk(dv, b, n_tiles != 0, max_n, k_out, max_rounds, s);
 }
 
 int launch_rerank_batch(const DataView &dv, const RerankBufs &b, uint32_t max_n, uint32_t k_out, uint32_t max_rounds,

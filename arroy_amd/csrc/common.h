@@ -182,6 +182,7 @@ inline int guarded(const char *what, F &&f) noexcept {
     X(SEARCH_SCREEN, "AH_SEARCH_SCREEN", 1)     /* 0: the re-rank of ah_search_batch never screens its candidates (f32 rows for all) */ \
     X(SEARCH_FILTER_GROUP_MIN, "AH_SEARCH_FILTER_GROUP_MIN", 16) /* ah_search_batch_filters: the queries of one filter form a sub-batch of their own from this many on; fewer share a mixed sub-batch */ \
     X(SEARCH_PARAMS_SORT, "AH_SEARCH_PARAMS_SORT", 1) /* ah_search_batch_params: inside a run of one filter the queries are ordered by the stride of their candidate buffer, so a sub-batch is sized by its own largest; 0: the caller's order (schedule only: the results are bit-identical; DESIGN.md 4 "Per-query search parameters") */ \
+    X(SEARCH_EXHAUSTED, "AH_SEARCH_EXHAUSTED", 0) /* 1: a query of ah_search_batch_filters / _params whose resident filter keeps at most its effective search_k ids over all leaves (ah_filter_kept_total) is answered from the filter's kept list, without the descent: the same bits (DESIGN.md 4 "Exhausted filters"); 0 (default): no call changes, existing statistics stay as they are */ \
     X(FILTER_COMBINE_SHORTCUT, "AH_FILTER_COMBINE_SHORTCUT", 1) /* 0: ah_filter_combine walks the ids of every leaf against the new bitmap, never derives a leaf's count from the operands' counts (DESIGN.md 4 "Combined filters") */ \
     X(FILTER_RESUME_GROUP, "AH_FILTER_RESUME_GROUP", 16) /* ah_filter_resume_batch: filters one pass over the Descendants ids counts for, 1 .. 16 (the header's AH_FILTER_RESUME_GROUP); 1: a pass per filter, what the measurement compares with (DESIGN.md 4 "Filters across index maintenance") */ \
     X(FILTER_RESUME_MIXED_MB, "AH_FILTER_RESUME_MIXED_MB", 256) /* ah_filter_resume_batch: most MiB for a group's bitmaps laid side by side (64 bytes per 32 ids of the id range); above it the counts are made a filter a pass */ \
@@ -647,6 +648,18 @@ int launch_rerank_batch_prepared(const DataView &dv, const RerankBufs &b, uint32
                                  uint64_t n_candidates, hipStream_t s);
 int launch_rerank_batch(const DataView &dv, const RerankBufs &b, uint32_t max_n, uint32_t k_out, uint32_t max_rounds,
                         uint64_t n_candidates, hipStream_t s);
+// the top-k half of launch_rerank_batch_prepared alone (selection, rounds, emit): the distances of every seg are in b.d_dist
+int launch_batch_topk(const DataView &dv, const RerankBufs &b, bool any, uint32_t max_n, uint32_t k_out, uint32_t max_rounds,
+                      hipStream_t s);
+// One ascending id list against every query of a sub-batch (the exhausted filters of search.hip): d_dist[q * stride + i] and
+// d_ids[q * stride + i] = d_list[i] for i < m, the bits of launch_rerank_batch_prepared's distances.  shared_list_slab(): the
+// list rows one block takes.
+uint32_t shared_list_slab();
+int launch_shared_list_distances(const DataView &dv, const uint8_t *d_qvecs, uint64_t qstride, const float *d_qhdrs, uint32_t n_queries,
+                                 const uint32_t *d_list, uint32_t m, uint64_t stride, uint32_t *d_ids, float *d_dist, uint32_t *d_err,
+                                 hipStream_t s);
+// exclusive scan of n_sums block sums in place (one block), their total to *d_total
+int launch_scan_sums(uint32_t *d_sums, uint32_t n_sums, uint32_t *d_total, hipStream_t s);
 // row-major ("inverted") re-rank of big submissions: policy + the counter scratch it needs (see batch.hip)
 bool batch_invert_wanted(const DataView &dv, uint64_t n_candidates);
 size_t batch_invert_counter_bytes(uint64_t n_rows, uint64_t n_candidates);

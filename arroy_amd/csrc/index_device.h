@@ -86,6 +86,7 @@ struct ah_index {
     // under stats_mu: filters ah_filter_suspend took out of filters_alive (the maintenance calls and ah_index_suspend do not
     // see them; ah_index_destroy refuses above 0, their `ix` would dangle)
     uint64_t filters_suspended = 0;
+    ah_exhausted_stats xstats{};             // under stats_mu: queries answered from their filter's kept list (AH_SEARCH_EXHAUSTED)
 };
 
 // every entry point that reads the dataset through the index

@@ -4014,6 +4014,99 @@ int validate_forest_view(const ah_dataset *ds, const ah_forest_view &v) {
     return AH_OK;
 }
 
+// ---- exhausted filters: kept_total and the kept list K(f) of a resident filter (DESIGN.md 4 "Exhausted filters") ----------
+// One 64-bit sum per block: a wave reduce, the four waves' sums through LDS, one atomic.
+__device__ __forceinline__ void block_add_u64(unsigned long long v, unsigned long long *dst) {
+    __shared__ unsigned long long s_wave[4];
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d);
+    if ((threadIdx.x & 63u) == 0) s_wave[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const unsigned long long sum = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+        if (sum) atomicAdd(dst, sum);
+    }
+}
+// kept_total(f): the sum of the per-node counts (k_leaf_kept), grid-stride.
+__global__ __launch_bounds__(256) void k_kept_total(const uint32_t *__restrict__ leaf_kept, uint32_t n_nodes, unsigned long long *total) {
+    unsigned long long v = 0;
+    const uint64_t step = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_nodes; i += step) v += leaf_kept[i];
+    block_add_u64(v, total);
+}
+// The ids the filter keeps of EVERY in-use leaf, as bits of `mark` (zeroed, over [0, filter_len_bits)): one octet per node slot,
+// the launch shape of k_leaf_kept.  A node whose count is 0 (free slot, split node, leaf the filter keeps nothing of) is
+// skipped; the ids of the others are tested as copy_filtered tests them.  walked: the leaves whose ids were tested.
+__global__ __launch_bounds__(256) void k_kept_mark(SearchParams sp, uint32_t n_nodes, const uint32_t *__restrict__ leaf_kept,
+                                                   uint32_t *__restrict__ mark, unsigned long long *walked) {
+    const uint32_t j = threadIdx.x & 7u;
+    const uint32_t octets = (gridDim.x * blockDim.x) >> 3;
+    unsigned long long mine = 0;
+    for (uint32_t node = (blockIdx.x * blockDim.x + threadIdx.x) >> 3; node < n_nodes; node += octets) {
+        if (leaf_kept[node] == 0) continue;
+        const DNode nd = sp.nodes[node];
+        if ((nd.kind & 0xFFu) != AH_NODE_DESCENDANTS) continue;
+        const uint32_t *ids = sp.desc + nd.a;
+        for (uint32_t i = j; i < nd.b; i += 8) {
+            const uint32_t id = ids[i];
+            if (id < sp.filter_len_bits && ((sp.filter_bits[id >> 5] >> (id & 31)) & 1u)) atomicOr(&mark[id >> 5], 1u << (id & 31));
+        }
+        if (j == 0) mine++;
+    }
+    block_add_u64(mine, walked);
+}
+// The set bits of a bitmap as an ascending id list, kBitmapListWords words a block: k_bitmap_count leaves every block's
+// popcount, launch_scan_sums makes them offsets, k_bitmap_list counts again and writes the ids behind its block's offset.
+// block0: the first block of this launch (the passes run in spans of AH_LAUNCH_MAX_ITEMS words).
+static constexpr uint32_t kBitmapListWords = 2048;  // 256 threads x 8 words
+__global__ __launch_bounds__(256) void k_bitmap_count(const uint32_t *__restrict__ bits, uint64_t words, uint32_t block0,
+                                                      uint32_t *__restrict__ sums) {
+    __shared__ uint32_t s_wave[4];
+    const uint32_t block = block0 + blockIdx.x;
+    const uint64_t base = (uint64_t)block * kBitmapListWords + (uint64_t)threadIdx.x * 8;
+    uint32_t c = 0;
+#pragma unroll
+    for (int e = 0; e < 8; e++) c += base + e < words ? (uint32_t)__popc(bits[base + e]) : 0u;
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) c += __shfl_down(c, d);
+    if ((threadIdx.x & 63u) == 0) s_wave[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) sums[block] = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+}
+__global__ __launch_bounds__(256) void k_bitmap_list(const uint32_t *__restrict__ bits, uint64_t words, uint32_t block0,
+                                                     const uint32_t *__restrict__ offsets, uint64_t n, uint32_t *__restrict__ out) {
+    __shared__ uint32_t s_wave[4];
+    const uint32_t block = block0 + blockIdx.x;
+    const uint64_t base = (uint64_t)block * kBitmapListWords + (uint64_t)threadIdx.x * 8;
+    uint32_t w[8], local = 0;
+#pragma unroll
+    for (int e = 0; e < 8; e++) {
+        w[e] = base + e < words ? bits[base + e] : 0u;
+        local += (uint32_t)__popc(w[e]);
+    }
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    uint32_t incl = local;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t up = __shfl_up(incl, d);
+        if ((int)lane >= d) incl += up;
+    }
+    if (lane == 63) s_wave[wave] = incl;
+    __syncthreads();
+    uint64_t pos = (uint64_t)offsets[block] + incl - local;
+    for (uint32_t v = 0; v < wave; v++) pos += s_wave[v];
+#pragma unroll
+    for (int e = 0; e < 8; e++) {
+        uint32_t left = w[e];
+        while (left) {
+            const uint32_t bit = (uint32_t)__ffs((int)left) - 1u;
+            if (pos < n) out[pos] = (uint32_t)((base + e) << 5) + bit;  // (pos < n: the bitmap is the one that was counted)
+            pos++;
+            left &= left - 1u;
+        }
+    }
+}
+
 }  // namespace ah
 
 using namespace ah;
@@ -4024,11 +4117,114 @@ using namespace ah;
 struct ah_filter {
     ah_index *ix = nullptr;
     uint32_t *d_bits = nullptr, *d_leaf_kept = nullptr;
-    uint64_t len_bits = 0, listed = 0, stored = 0, device_bytes = 0;
+    uint64_t len_bits = 0, listed = 0, stored = 0;
+    std::atomic<uint64_t> device_bytes{0};  // the block, and the kept list's block from the moment it exists
     // ah_filter_suspend: counted in ix->filters_suspended instead of filters_alive.  It keeps its block; only d_bits / len_bits
     // still mean something (d_leaf_kept is of the node array as it was), and only ah_filter_resume_batch reads them
     bool suspended = false;
+    // Exhausted filters: kept_total (the sum of d_leaf_kept) and the kept list K(f) (d_list: n_list ascending ids, a block of
+    // its own, none while n_list is 0), each made on first request under list_mu and published by its flag (release / acquire):
+    // any number of searching threads, one list.  ah_filter_suspend drops both; ah_filter_destroy frees the list.
+    std::mutex list_mu;
+    std::atomic<bool> total_ready{false}, list_ready{false};
+    uint64_t kept_total = 0, n_list = 0, list_bytes = 0;
+    uint32_t *d_list = nullptr;
 };
+
+// kept_total(f), made on `ctx` the first time (one reduction over the per-node counts).
+static int filter_kept_total(ah_filter *f, Context *ctx, uint64_t &out) {
+    if (!f->total_ready.load(std::memory_order_acquire)) {
+        std::lock_guard<std::mutex> lk(f->list_mu);
+        if (!f->total_ready.load(std::memory_order_relaxed)) {
+            const ah_index *ix = f->ix;
+            unsigned long long total = 0;
+            if (ix->n_nodes) {
+                AH_TRY(ctx->ensure_device(256));
+                unsigned long long *d_total = reinterpret_cast<unsigned long long *>(ctx->d_scratch);
+                AH_HIP(hipMemsetAsync(d_total, 0, 8, ctx->stream));
+                hipLaunchKernelGGL(k_kept_total, dim3(grid_of(ix->n_nodes, 1024, 1024)), dim3(256), 0, ctx->stream, f->d_leaf_kept, ix->n_nodes,
+                                   d_total);
+                AH_HIP(hipGetLastError());
+                AH_HIP(hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, ctx->stream));
+                AH_HIP(hipStreamSynchronize(ctx->stream));
+            }
+            f->kept_total = total;
+            f->total_ready.store(true, std::memory_order_release);
+        }
+    }
+    out = f->kept_total;
+    return AH_OK;
+}
+
+// K(f), made on `ctx` the first time: k_kept_mark into a transient bitmap, then its set bits as a list (k_bitmap_count,
+// launch_scan_sums, k_bitmap_list).  Nothing of a failed attempt stays: the next request starts again.
+static int filter_kept_list(ah_filter *f, Context *ctx) {
+    if (f->list_ready.load(std::memory_order_acquire)) return AH_OK;
+    std::lock_guard<std::mutex> lk(f->list_mu);
+    if (f->list_ready.load(std::memory_order_relaxed)) return AH_OK;
+    ah_index *ix = f->ix;
+    hipStream_t s = ctx->stream;
+    const uint64_t words = (f->len_bits + 31) / 32;
+    unsigned long long walked = 0;
+    uint32_t n = 0;
+    DevMem list;
+    if (words && ix->n_nodes) {
+        const uint32_t n_blocks = (uint32_t)((words + kBitmapListWords - 1) / kBitmapListWords);
+        // [mark: words][block sums: n_blocks][the total][pad to 8][leaves walked: 8 bytes]
+        const size_t sums_off = (size_t)words * 4, total_off = sums_off + (size_t)n_blocks * 4, walked_off = (total_off + 4 + 7) & ~(size_t)7;
+        DevMem work;
+        AH_TRY(alloc(&work, walked_off + 8, "the kept list of a filter"));
+        uint32_t *d_mark = work.as<uint32_t>(), *d_sums = reinterpret_cast<uint32_t *>(work.as<uint8_t>() + sums_off);
+        uint32_t *d_n = reinterpret_cast<uint32_t *>(work.as<uint8_t>() + total_off);
+        unsigned long long *d_walked = reinterpret_cast<unsigned long long *>(work.as<uint8_t>() + walked_off);
+        AH_HIP(hipMemsetAsync(work.p, 0, walked_off + 8, s));
+        SearchParams lp{};
+        lp.nodes = ix->d_nodes;
+        lp.desc = ix->d_desc;
+        lp.filter_bits = f->d_bits;
+        lp.filter_len_bits = f->len_bits;
+        hipLaunchKernelGGL(k_kept_mark, dim3(1024), dim3(256), 0, s, lp, ix->n_nodes, f->d_leaf_kept, d_mark, d_walked);
+        const uint32_t span = (uint32_t)std::max<long long>(1, std::min<long long>(tun(TUN_LAUNCH_MAX_ITEMS), 0xFFFFFFFFll) / kBitmapListWords);
+        for (uint32_t b0 = 0; b0 < n_blocks; b0 += span)
+            hipLaunchKernelGGL(k_bitmap_count, dim3(std::min(span, n_blocks - b0)), dim3(256), 0, s, d_mark, words, b0, d_sums);
+        AH_HIP(hipGetLastError());
+        AH_TRY(launch_scan_sums(d_sums, n_blocks, d_n, s));
+        AH_HIP(hipMemcpyAsync(&n, d_n, 4, hipMemcpyDeviceToHost, s));
+        AH_HIP(hipMemcpyAsync(&walked, d_walked, 8, hipMemcpyDeviceToHost, s));
+        AH_HIP(hipStreamSynchronize(s));
+        if (n) {
+            AH_TRY(alloc(&list, (size_t)n * 4, "the kept list of a filter"));
+            for (uint32_t b0 = 0; b0 < n_blocks; b0 += span)
+                hipLaunchKernelGGL(k_bitmap_list, dim3(std::min(span, n_blocks - b0)), dim3(256), 0, s, d_mark, words, b0, d_sums, (uint64_t)n,
+                                   list.as<uint32_t>());
+            AH_HIP(hipGetLastError());
+            AH_HIP(hipStreamSynchronize(s));
+        }
+    }
+    f->n_list = n;
+    f->d_list = list.as<uint32_t>();
+    f->list_bytes = n ? dev_block_bytes(list.p) : 0;
+    f->device_bytes.fetch_add(f->list_bytes, std::memory_order_relaxed);
+    list.p = nullptr;  // the filter owns it from here
+    {
+        std::lock_guard<std::mutex> sl(ix->stats_mu);
+        ix->xstats.lists_made += n ? 1 : 0;
+        ix->xstats.list_ids += n;
+        ix->xstats.leaves_walked += walked;
+    }
+    f->list_ready.store(true, std::memory_order_release);
+    return AH_OK;
+}
+// ah_filter_suspend / ah_filter_destroy: the list goes, and with it what was derived from the per-node counts
+static void filter_drop_list(ah_filter *f) {
+    std::lock_guard<std::mutex> lk(f->list_mu);
+    if (f->d_list) (void)dev_free(f->d_list);
+    f->device_bytes.fetch_sub(f->list_bytes, std::memory_order_relaxed);
+    f->d_list = nullptr;
+    f->n_list = f->list_bytes = f->kept_total = 0;
+    f->list_ready.store(false, std::memory_order_release);
+    f->total_ready.store(false, std::memory_order_release);
+}
 
 extern "C" {
 
@@ -5357,6 +5553,7 @@ int ah_filter_destroy(ah_filter *f) {
     NoFailScope no_fail;
     ah_index *ix = f->ix;
     if (ix && ix->ds) (void)hipSetDevice(ix->ds->device);
+    filter_drop_list(f);
     if (f->d_bits) (void)dev_free(f->d_bits);  // (waits for the device: no queued search still reads it)
     if (ix) {
         std::lock_guard<std::mutex> lk(ix->stats_mu);
@@ -5381,6 +5578,8 @@ int ah_filter_suspend(ah_filter *f) {
         DeviceRestore restore_device;
         AH_HIP(hipSetDevice(ix->ds->device));
         AH_HIP(hipDeviceSynchronize());
+        NoFailScope no_fail;
+        filter_drop_list(f);  // (made from the per-node counts, which go stale: remade on first use after the resume)
     }
     std::lock_guard<std::mutex> lk(ix->stats_mu);
     f->suspended = true;
@@ -5567,6 +5766,107 @@ int ah_index_filter_stats(ah_index *ix, ah_filter_stats *out, int reset) {
     AH_GUARDED_END
 }
 
+// An EXHAUSTED sub-batch (AH_SEARCH_EXHAUSTED; search_batch_cut): nq queries of the call, qlist[i] their positions in it, all
+// under the resident filter f with kept_total(f) <= their effective search_k.  The reference's loop then drains its queue, and
+// its candidates after sort + dedup are K(f) whatever the query: no descent, the distances of K(f) for all queries in one dense
+// launch (k_shared_list_distances), then the top-k stage of the sorted re-rank over one RerankSeg{i * m, m, min(count, m)} a
+// query.  k: the sub-batch's largest EFFECTIVE count min(count, m); beyond the batched top-k the single-query kernel takes
+// the queries one after the other, as the big_k branch of search_chunk does.  Results go straight to the call's outputs (the
+// padding is already there).
+static int search_exhausted(ah_index *ix, Context *ctx, const ah_filter *f, const float *queries, const uint32_t *rows, const uint32_t *qlist,
+                            size_t nq, const uint32_t *counts, uint32_t k, size_t out_stride, uint32_t *out_ids, float *out_dists,
+                            uint32_t *out_counts) {
+    ah_dataset *ds = ix->ds;
+    hipStream_t s = ctx->stream;
+    const uint32_t m = (uint32_t)f->n_list;
+    const size_t qstride = (ds->row_bytes() + 255) & ~(size_t)255;
+    auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const bool big_k = !batch_supported(k);
+    const size_t kstride = big_k ? (topk_scratch_bytes(m, k) + 15) / 16 : batch_key_stride(m);
+    const size_t dev_bytes = pad(nq * (size_t)ds->dims * 4) + pad(nq * 4) + nq * qstride + pad(nq * 8) + 2 * pad(nq * (size_t)m * 4) +
+                             pad(nq * sizeof(RerankSeg)) + 2 * pad(nq * kstride * 8) + 2 * pad(nq * (size_t)k * 4) + pad(SS_WORDS * 4) + 4096;
+    AH_TRY(ctx->ensure_device(dev_bytes));
+    const size_t pin_bytes = pad(nq * (size_t)ds->dims * 4) + pad(nq * 4) + pad(nq * sizeof(RerankSeg)) + 2 * pad(nq * (size_t)k * 4) +
+                             pad(SS_WORDS * 4) + 4096;
+    AH_TRY(ctx->ensure_pinned(pin_bytes));
+    uint8_t *dbase = reinterpret_cast<uint8_t *>(ctx->d_scratch), *pbase = reinterpret_cast<uint8_t *>(ctx->h_pinned);
+    size_t doff = 0, poff = 0;
+    auto dtake = [&](size_t bytes) {
+        void *p = dbase + doff;
+        doff += pad(bytes);
+        return p;
+    };
+    auto ptake = [&](size_t bytes) {
+        void *p = pbase + poff;
+        poff += pad(bytes);
+        return p;
+    };
+    float *d_qf32 = (float *)dtake(nq * (size_t)ds->dims * 4);
+    uint32_t *d_qrows = (uint32_t *)dtake(nq * 4);
+    uint8_t *d_qvecs = (uint8_t *)dtake(nq * qstride);
+    float *d_qhdrs = (float *)dtake(nq * 8);
+    uint32_t *d_ids = (uint32_t *)dtake(nq * (size_t)m * 4);
+    float *d_dist = (float *)dtake(nq * (size_t)m * 4);
+    RerankSeg *d_segs = (RerankSeg *)dtake(nq * sizeof(RerankSeg));
+    uint64_t *d_ka = (uint64_t *)dtake(nq * kstride * 8);
+    uint64_t *d_kb = (uint64_t *)dtake(nq * kstride * 8);
+    uint32_t *d_oi = (uint32_t *)dtake(nq * (size_t)k * 4);
+    float *d_od = (float *)dtake(nq * (size_t)k * 4);
+    uint32_t *d_err = (uint32_t *)dtake(SS_WORDS * 4);
+    float *h_q = (float *)ptake(nq * (size_t)ds->dims * 4);
+    uint32_t *h_qrows = (uint32_t *)ptake(nq * 4);
+    RerankSeg *h_segs = (RerankSeg *)ptake(nq * sizeof(RerankSeg));
+    uint32_t *h_oi = (uint32_t *)ptake(nq * (size_t)k * 4);
+    float *h_od = (float *)ptake(nq * (size_t)k * 4);
+    uint32_t *h_err = (uint32_t *)ptake(SS_WORDS * 4);
+    const DataView dv = ds->view();
+    // 1. query leaves, as search_chunk prepares them
+    if (queries) {
+        for (size_t i = 0; i < nq; i++) memcpy(h_q + i * (size_t)ds->dims, queries + qlist[i] * (size_t)ds->dims, (size_t)ds->dims * 4);
+        AH_HIP(hipMemcpyAsync(d_qf32, h_q, nq * (size_t)ds->dims * 4, hipMemcpyHostToDevice, s));
+        AH_TRY(launch_prepare_queries_only(dv, d_qf32, (uint32_t)nq, d_qvecs, qstride, d_qhdrs, s));
+    } else {
+        for (size_t i = 0; i < nq; i++) h_qrows[i] = rows[qlist[i]];
+        AH_HIP(hipMemcpyAsync(d_qrows, h_qrows, nq * 4, hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(k_load_items_as_queries, dim3((unsigned)nq), dim3(64), 0, s, dv, d_qrows, d_qvecs, qstride, d_qhdrs);
+    }
+    AH_HIP(hipMemsetAsync(d_err, 0, SS_WORDS * 4, s));
+    // 2. the dense block K(f) x queries
+    AH_TRY(launch_shared_list_distances(dv, d_qvecs, qstride, d_qhdrs, (uint32_t)nq, f->d_list, m, m, d_ids, d_dist, d_err, s));
+    // 3. top-k + normalized distances
+    uint32_t max_rounds = 0;
+    for (size_t i = 0; i < nq; i++) {
+        h_segs[i] = RerankSeg{(uint64_t)i * m, m, std::min(counts[i], m)};
+        if (!big_k) max_rounds = std::max(max_rounds, batch_rounds(m, h_segs[i].k));
+    }
+    if (big_k) {
+        AH_HIP(hipMemsetAsync(d_oi, 0xFF, nq * (size_t)k * 4, s));
+        AH_HIP(hipMemsetAsync(d_od, 0xFF, nq * (size_t)k * 4, s));
+        for (size_t i = 0; i < nq; i++)
+            AH_TRY(launch_topk(dv, d_dist + i * (size_t)m, d_ids + i * (size_t)m, m, h_segs[i].k, d_ka, d_oi + i * (size_t)k, d_od + i * (size_t)k, s));
+    } else {
+        AH_HIP(hipMemcpyAsync(d_segs, h_segs, nq * sizeof(RerankSeg), hipMemcpyHostToDevice, s));
+        RerankBufs b{};
+        b.n_queries = (uint32_t)nq, b.d_qvecs = d_qvecs, b.qstride = qstride, b.d_qhdrs = d_qhdrs, b.d_segs = d_segs;
+        b.d_ids = d_ids, b.d_dist = d_dist, b.d_keys_a = d_ka, b.d_keys_b = d_kb, b.kstride = kstride;
+        b.d_out_ids = d_oi, b.d_out_dist = d_od, b.d_err = d_err;
+        AH_TRY(launch_batch_topk(dv, b, true, m, k, max_rounds, s));
+    }
+    AH_HIP(hipMemcpyAsync(h_oi, d_oi, nq * (size_t)k * 4, hipMemcpyDeviceToHost, s));
+    AH_HIP(hipMemcpyAsync(h_od, d_od, nq * (size_t)k * 4, hipMemcpyDeviceToHost, s));
+    AH_HIP(hipGetLastError());
+    AH_HIP(hipMemcpyAsync(h_err, d_err, SS_WORDS * 4, hipMemcpyDeviceToHost, s));
+    AH_HIP(hipStreamSynchronize(s));
+    AH_REQUIRE((*h_err & 1u) == 0, AH_ERR_MISSING_ITEM, "a descendant id does not exist in the dataset");
+    for (size_t i = 0; i < nq; i++) {
+        const size_t q = qlist[i], kk = h_segs[i].k;
+        memcpy(out_ids + q * out_stride, h_oi + i * (size_t)k, kk * 4);
+        memcpy(out_dists + q * out_stride, h_od + i * (size_t)k, kk * 4);
+        out_counts[q] = (uint32_t)kk;
+    }
+    return AH_OK;
+}
+
 // What ah_search_batch_filters and ah_search_batch_params share: a batched search with a filter per query and, when `params` is
 // given, a (count, search_k, oversampling) per query as well (the scalars are then unused; out_stride = count otherwise).
 //
@@ -5637,20 +5937,84 @@ static int search_batch_cut(ah_index *ix, const float *queries, const uint32_t *
     auto ext_of = [&](size_t q) -> const QueryExtent & { return params ? ext[q] : one; };
     std::vector<uint32_t> rows;
     AH_TRY(search_rows(ix, query_items, nq, rows));
-    // 1. the order: stable by (slot, big count, stride)
     auto slot_of = [&](size_t q) -> uint32_t { return filter_of_query ? filter_of_query[q] : (n_filters ? 0u : AH_NO_FILTER); };
+    // 0b. AH_SEARCH_EXHAUSTED: the queries whose filter keeps at most their effective search_k ids over all leaves leave the order
+    // here.  Grouped by filter slot in the caller's order, effective counts within the batched top-k first, they are cut into
+    // sub-batches of one filter (at most 4096 queries, scratch at stride |K(f)| and the largest effective count within the
+    // chunk budget); a query whose K(f) is empty is answered by the padding.  `live`: what is left, cut exactly as ever below.
+    std::optional<ContextLease> lease;
+    struct ExhaustedBatch {
+        uint32_t slot, k;  // k: the largest effective count
+        size_t a, b;       // xq[a, b)
+    };
+    std::vector<uint32_t> live, xq, xcount;
+    std::vector<ExhaustedBatch> xbatches;
+    ah_exhausted_stats xs{};
+    const bool exhaust = tun(TUN_SEARCH_EXHAUSTED) != 0 && n_filters != 0;
+    if (exhaust) {
+        lease.emplace(ds);
+        AH_REQUIRE(lease->c, AH_ERR_DEVICE, "cannot create a HIP stream");
+        std::vector<uint64_t> total(n_filters);
+        std::vector<uint8_t> known(n_filters, 0);
+        std::vector<std::pair<uint32_t, uint32_t>> gone;  // (slot, query): ascending = by slot, the caller's order inside
+        for (size_t q = 0; q < nq; q++) {
+            const uint32_t slot = slot_of(q);
+            if (slot != AH_NO_FILTER && !known[slot]) {
+                AH_TRY(filter_kept_total(filters[slot], lease->c, total[slot]));
+                known[slot] = 1;
+            }
+            if (slot != AH_NO_FILTER && total[slot] <= ext_of(q).sk_eff) gone.push_back({slot, (uint32_t)q});
+            else live.push_back((uint32_t)q);
+        }
+        std::sort(gone.begin(), gone.end());
+        for (size_t g0 = 0; g0 < gone.size();) {
+            size_t g1 = g0 + 1;
+            while (g1 < gone.size() && gone[g1].first == gone[g0].first) g1++;
+            ah_filter *f = filters[gone[g0].first];
+            AH_TRY(filter_kept_list(f, lease->c));
+            const uint32_t m = (uint32_t)f->n_list;
+            xs.queries += g1 - g0;
+            if (m == 0) xs.empty_queries += g1 - g0;
+            for (int big = 0; big < 2 && m; big++) {
+                std::vector<uint32_t> part;
+                for (size_t g = g0; g < g1; g++)
+                    if ((int)!batch_supported(std::min(ext_of(gone[g].second).count, m)) == big) part.push_back(gone[g].second);
+                for (size_t c0 = 0; c0 < part.size();) {
+                    ExhaustedBatch xb{gone[g0].first, 0, xq.size(), 0};
+                    size_t c1 = c0;
+                    while (c1 < part.size() && c1 - c0 < kSearchChunkQueries) {
+                        const uint32_t kk = std::max(xb.k, std::min(ext_of(part[c1]).count, m));
+                        if (c1 > c0 && (c1 - c0 + 1) * search_query_bytes(ds, m, kk) > kSearchChunkBytes) break;
+                        xb.k = kk;
+                        c1++;
+                    }
+                    for (size_t c = c0; c < c1; c++) {
+                        xq.push_back(part[c]);
+                        xcount.push_back(ext_of(part[c]).count);
+                    }
+                    xb.b = xq.size();
+                    xbatches.push_back(xb);
+                    c0 = c1;
+                }
+            }
+            g0 = g1;
+        }
+    }
+    const size_t nl = exhaust ? live.size() : nq;  // the queries of the order below
+    auto live_q = [&](size_t i) -> uint32_t { return exhaust ? live[i] : (uint32_t)i; };
+    // 1. the order: stable by (slot, big count, stride)
     // (keys `slot + 1 (mod 2^32)` << 32 | big << 31 | stride, then the query: stable by construction, and no temporary buffer whose
     // allocation std::stable_sort would survive failing — every allocation of this call that fails gives a status)
     const bool sort_params = params && tun(TUN_SEARCH_PARAMS_SORT) != 0;
     auto run_of = [&](size_t q) -> uint64_t {  // (slot, big): the queries of one run share it
         return ((uint64_t)(uint32_t)(slot_of(q) + 1u) << 1) | (batch_supported(ext_of(q).count) ? 0u : 1u);
     };
-    std::vector<uint32_t> order(nq);
+    std::vector<uint32_t> order(nl);
     {
-        std::vector<std::pair<uint64_t, uint32_t>> keyed(nq);
-        for (size_t q = 0; q < nq; q++) keyed[q] = {(run_of(q) << 31) | (sort_params ? ext_of(q).stride : 0u), (uint32_t)q};
+        std::vector<std::pair<uint64_t, uint32_t>> keyed(nl);
+        for (size_t i = 0; i < nl; i++) keyed[i] = {(run_of(live_q(i)) << 31) | (sort_params ? ext_of(live_q(i)).stride : 0u), live_q(i)};
         std::sort(keyed.begin(), keyed.end());
-        for (size_t q = 0; q < nq; q++) order[q] = keyed[q].second;
+        for (size_t i = 0; i < nl; i++) order[i] = keyed[i].second;
     }
     // 2. the sub-batches, as ranges of `perm`: the uniform ones first, then what is left over (batched counts, then big ones)
     struct SubBatch {
@@ -5689,9 +6053,9 @@ static int search_batch_cut(ah_index *ix, const float *queries, const uint32_t *
             c0 = c1;
         }
     };
-    for (size_t r0 = 0; r0 < nq;) {
+    for (size_t r0 = 0; r0 < nl;) {
         size_t r1 = r0 + 1;
-        while (r1 < nq && run_of(order[r1]) == run_of(order[r0])) r1++;
+        while (r1 < nl && run_of(order[r1]) == run_of(order[r0])) r1++;
         if (r1 - r0 >= group_min) cut(order.data() + r0, r1 - r0, false);
         else rest[run_of(order[r0]) & 1u].insert(rest[run_of(order[r0]) & 1u].end(), order.begin() + r0, order.begin() + r1);
         r0 = r1;
@@ -5699,16 +6063,16 @@ static int search_batch_cut(ah_index *ix, const float *queries, const uint32_t *
     for (const std::vector<uint32_t> &r : rest) cut(r.data(), r.size(), true);
     // 3. queries and outputs in that order (nothing to move when the order is the caller's and every row is out_stride wide)
     bool direct = true;
-    for (size_t i = 0; i < nq && direct; i++) direct = perm[i] == i;
+    for (size_t i = 0; i < nl && direct; i++) direct = perm[i] == i;
     bool identity = direct;
     for (const SubBatch &sb : batches) direct = direct && sb.count == out_stride;
     std::vector<float> pq, pd;
-    std::vector<uint32_t> prow, pi, pc, pslot(nq), pcount, psk;
-    for (size_t i = 0; i < nq; i++) pslot[i] = slot_of(perm[i]);
+    std::vector<uint32_t> prow, pi, pc, pslot(nl), pcount, psk;
+    for (size_t i = 0; i < nl; i++) pslot[i] = slot_of(perm[i]);
     if (params) {
-        pcount.resize(nq);
-        psk.resize(nq);
-        for (size_t i = 0; i < nq; i++) {
+        pcount.resize(nl);
+        psk.resize(nl);
+        for (size_t i = 0; i < nl; i++) {
             pcount[i] = ext[perm[i]].count;
             psk[i] = ext[perm[i]].sk_eff;
         }
@@ -5719,26 +6083,26 @@ static int search_batch_cut(ah_index *ix, const float *queries, const uint32_t *
     float *od = out_distances;
     if (!identity) {
         if (queries) {
-            pq.resize(nq * (size_t)ds->dims);
-            for (size_t i = 0; i < nq; i++) memcpy(&pq[i * (size_t)ds->dims], queries + perm[i] * (size_t)ds->dims, (size_t)ds->dims * 4);
+            pq.resize(nl * (size_t)ds->dims);
+            for (size_t i = 0; i < nl; i++) memcpy(&pq[i * (size_t)ds->dims], queries + perm[i] * (size_t)ds->dims, (size_t)ds->dims * 4);
             qsrc = pq.data();
         } else {
-            prow.resize(nq);
-            for (size_t i = 0; i < nq; i++) prow[i] = rows[perm[i]];
+            prow.resize(nl);
+            for (size_t i = 0; i < nl; i++) prow[i] = rows[perm[i]];
             rsrc = prow.data();
         }
     }
     if (!direct) {
         pi.resize(staged);
         pd.resize(staged);
-        pc.resize(nq);
+        pc.resize(nl);
         oi = pi.data();
         od = pd.data();
         oc = pc.data();
     }
-    ContextLease lease(ds);
-    AH_REQUIRE(lease.c, AH_ERR_DEVICE, "cannot create a HIP stream");
-    Context *ctx = lease.c;
+    if (!lease) lease.emplace(ds);
+    AH_REQUIRE(lease->c, AH_ERR_DEVICE, "cannot create a HIP stream");
+    Context *ctx = lease->c;
     const bool wave_ok = tun(TUN_SEARCH_WAVE) != 0 && ((ds->row_bytes() + 255) & ~(size_t)255) <= (32u << 10);
     auto share_of = [&](uint32_t slot) { return (double)filters[slot]->stored / (double)ds->n; };  // exact: ah_filter_info
     std::vector<FilterSlot> table;
@@ -5758,7 +6122,14 @@ static int search_batch_cut(ah_index *ix, const float *queries, const uint32_t *
         ix->stats.calls++;
     }
     int st = AH_OK;
+    for (const ExhaustedBatch &xb : xbatches) {
+        st = search_exhausted(ix, ctx, filters[xb.slot], queries, query_items ? rows.data() : nullptr, xq.data() + xb.a, xb.b - xb.a,
+                              xcount.data() + xb.a, xb.k, out_stride, out_ids, out_distances, out_counts);
+        xs.batches++;
+        if (st != AH_OK) break;
+    }
     for (const SubBatch &sb : batches) {
+        if (st != AH_OK) break;
         const size_t cn = sb.b - sb.a;
         const float *q_at = qsrc ? qsrc + sb.a * (size_t)ds->dims : nullptr;
         const uint32_t *r_at = rsrc ? rsrc + sb.a : nullptr;
@@ -5804,6 +6175,9 @@ static int search_batch_cut(ah_index *ix, const float *queries, const uint32_t *
         ix->fstats.mixed_batches += fs.mixed_batches;
         ix->fstats.uniform_queries += fs.uniform_queries;
         ix->fstats.mixed_queries += fs.mixed_queries;
+        ix->xstats.queries += xs.queries;
+        ix->xstats.batches += xs.batches;
+        ix->xstats.empty_queries += xs.empty_queries;
         if (params) {
             ix->pstats.calls += ps.calls;
             ix->pstats.batches += ps.batches;
@@ -5862,6 +6236,55 @@ int ah_index_params_stats(ah_index *ix, ah_params_stats *out, int reset) {
     std::lock_guard<std::mutex> lk(ix->stats_mu);
     *out = ix->pstats;
     if (reset) ix->pstats = ah_params_stats{};
+    return AH_OK;
+    AH_GUARDED_END
+}
+
+// kept_total(f) (include/arroy_hip.h): made on first request, cached until the filter is suspended.
+int ah_filter_kept_total(ah_filter *f, uint64_t *out) {
+    AH_GUARDED("ah_filter_kept_total")
+    AH_REQUIRE(f && f->ix && f->ix->ds, AH_ERR_INVALID_ARGUMENT, "filter is NULL");
+    AH_REQUIRE(out, AH_ERR_INVALID_ARGUMENT, "out is NULL");
+    AH_REQUIRE(!f->suspended, AH_ERR_INVALID_ARGUMENT, "the filter is suspended (ah_filter_suspend): ah_filter_resume_batch it first");
+    AH_INDEX_LIVE(f->ix);
+    ah_dataset *ds = f->ix->ds;
+    AH_HIP(hipSetDevice(ds->device));
+    ContextLease lease(ds);
+    AH_REQUIRE(lease.c, AH_ERR_DEVICE, "cannot create a HIP stream");
+    return filter_kept_total(f, lease.c, *out);
+    AH_GUARDED_END
+}
+
+// Test aid: K(f) as the exhausted queries of the filter read it.
+int ah_filter_kept_ids(ah_filter *f, uint32_t *out_ids, uint64_t cap, uint64_t *out_n) {
+    AH_GUARDED("ah_filter_kept_ids")
+    AH_REQUIRE(f && f->ix && f->ix->ds, AH_ERR_INVALID_ARGUMENT, "filter is NULL");
+    AH_REQUIRE(out_n, AH_ERR_INVALID_ARGUMENT, "out_n is NULL");
+    AH_REQUIRE(!f->suspended, AH_ERR_INVALID_ARGUMENT, "the filter is suspended (ah_filter_suspend): ah_filter_resume_batch it first");
+    AH_INDEX_LIVE(f->ix);
+    ah_dataset *ds = f->ix->ds;
+    AH_HIP(hipSetDevice(ds->device));
+    ContextLease lease(ds);
+    AH_REQUIRE(lease.c, AH_ERR_DEVICE, "cannot create a HIP stream");
+    AH_TRY(filter_kept_list(f, lease.c));
+    *out_n = f->n_list;
+    if (out_ids && f->n_list) {
+        AH_REQUIRE(cap >= f->n_list, AH_ERR_INVALID_ARGUMENT, "cap = %llu is below the list's %llu ids", (unsigned long long)cap,
+                   (unsigned long long)f->n_list);
+        AH_HIP(hipMemcpyAsync(out_ids, f->d_list, (size_t)f->n_list * 4, hipMemcpyDeviceToHost, lease.c->stream));
+        AH_HIP(hipStreamSynchronize(lease.c->stream));
+    }
+    return AH_OK;
+    AH_GUARDED_END
+}
+
+// What AH_SEARCH_EXHAUSTED served; reset != 0 zeroes the counters after the copy.
+int ah_index_exhausted_stats(ah_index *ix, ah_exhausted_stats *out, int reset) {
+    AH_GUARDED("ah_index_exhausted_stats")
+    AH_REQUIRE(ix && out, AH_ERR_INVALID_ARGUMENT, "NULL argument");
+    std::lock_guard<std::mutex> lk(ix->stats_mu);
+    *out = ix->xstats;
+    if (reset) ix->xstats = ah_exhausted_stats{};
     return AH_OK;
     AH_GUARDED_END
 }

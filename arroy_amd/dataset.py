@@ -736,6 +736,12 @@ class Index:
         _lib.check(_lib.lib().ah_index_params_stats(self._h, C.byref(st), 1 if reset else 0))
         return {f: int(getattr(st, f)) for f, _ in _lib.AhParamsStats._fields_}
 
+    def exhausted_stats(self, reset: bool = False) -> dict:
+        """ah_index_exhausted_stats: the queries AH_SEARCH_EXHAUSTED=1 answered from their filter's kept list, and the lists made."""
+        st = _lib.AhExhaustedStats()
+        _lib.check(_lib.lib().ah_index_exhausted_stats(self._h, C.byref(st), 1 if reset else 0))
+        return {f: int(getattr(st, f)) for f, _ in _lib.AhExhaustedStats._fields_}
+
     def filter_stats(self, reset: bool = False) -> dict:
         """ah_index_filter_stats: how ah_search_batch_filters cut its calls, and the filters of this index."""
         st = _lib.AhFilterStats()
@@ -991,6 +997,23 @@ class Filter:
         listed, stored, nbytes = C.c_uint64(), C.c_uint64(), C.c_uint64()
         _lib.check(_lib.lib().ah_filter_info(self._handle(), C.byref(listed), C.byref(stored), C.byref(nbytes)))
         return {"listed": listed.value, "stored": stored.value, "device_bytes": nbytes.value}
+
+    def kept_total(self) -> int:
+        """ah_filter_kept_total: the ids the filter keeps summed over every leaf, duplicates across trees included — what a
+        descent that drains its queue collects.  A query whose effective search_k is at least this is exhausted."""
+        out = C.c_uint64()
+        _lib.check(_lib.lib().ah_filter_kept_total(self._handle(), C.byref(out)))
+        return int(out.value)
+
+    def kept_ids(self) -> np.ndarray:
+        """ah_filter_kept_ids (test aid): the ascending distinct ids the filter keeps and some leaf holds; makes the list on the
+        device if it does not exist yet."""
+        n = C.c_uint64()
+        _lib.check(_lib.lib().ah_filter_kept_ids(self._handle(), None, 0, C.byref(n)))
+        ids = np.zeros(n.value, dtype=np.uint32)
+        if n.value:
+            _lib.check(_lib.lib().ah_filter_kept_ids(self._handle(), _ptr(ids), n.value, C.byref(n)))
+        return ids
 
     def export(self) -> dict:
         """ah_filter_export (test aid): len_bits (largest stored id + 1), bits (its ceil(len_bits / 32) bitmap words) and

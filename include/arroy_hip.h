@@ -740,6 +740,28 @@ typedef struct ah_params_stats {
 } ah_params_stats;
 AH_API int ah_index_params_stats(ah_index *index, ah_params_stats *out, int reset);
 
+/* Exhausted filters (ABI v7 addition: look the symbols up).  The reference's loop counts only kept ids towards search_k
+ * (src/reader.rs:341-374): under a filter whose kept ids over ALL leaves, duplicates across trees included, number at most
+ * the effective search_k, it cannot stop before its queue is empty, and the candidates are exactly K(f), the distinct ids the
+ * filter keeps and some leaf holds, whatever the query.  With the tunable AH_SEARCH_EXHAUSTED=1 (default 0: nothing changes)
+ * ah_search_batch_filters and ah_search_batch_params answer such a query from K(f) without the descent: the same ids, distance
+ * bits and counts.  K(f) is made on the device on first use, once per filter and residence (ah_filter_suspend frees it), and
+ * counts in ah_filter_info's device_bytes from then on.  Both filter calls refuse a suspended filter by name. */
+/* sum over the nodes of |descendants & candidates|: what a drained descent collects, duplicates across trees included */
+AH_API int ah_filter_kept_total(ah_filter *f, uint64_t *out);
+/* test aid: K(f), ascending; out_ids may be NULL (count only); makes the list if it does not exist */
+AH_API int ah_filter_kept_ids(ah_filter *f, uint32_t *out_ids, uint64_t cap, uint64_t *out_n);
+/* Counts since the index was created or since the last call with reset != 0.  Exhausted queries count in none of ah_search_stats
+ * (`calls` apart), uniform_* / mixed_* of ah_filter_stats, or batches / varied_* / big_count_queries of ah_params_stats. */
+typedef struct ah_exhausted_stats {
+    uint64_t queries;        /* answered from their filter's list */
+    uint64_t batches;        /* their sub-batches */
+    uint64_t empty_queries;  /* ... of `queries`, answered without a launch (empty list) */
+    uint64_t lists_made, list_ids;   /* kept lists made, ids in them */
+    uint64_t leaves_walked;  /* leaves whose ids k_kept_mark tested */
+} ah_exhausted_stats;
+AH_API int ah_index_exhausted_stats(ah_index *index, ah_exhausted_stats *out, int reset);
+
 /* Filters across index maintenance (ABI v7 addition: look the symbols up).  A live filter blocks ah_index_delete_items /
  * _insert_items / _graft / _drop_trees / _compact and ah_index_suspend, because its per-node counts would go stale.  What
  * does not go stale is its bitmap, apart from the ids the host's update touched.  ah_filter_suspend keeps the filter and
