@@ -10,6 +10,8 @@
 #include <immintrin.h>
 #include <new>
 #include <thread>
+#include <array>
+#include <unordered_map>
 #include <cctype>
 #include <cstdio>
 #include <mutex>
@@ -92,6 +94,20 @@ TunableSlot *tunable_table() {
 }
 }  // namespace
 long long tun(int id) { return tunable_table()[id].value.load(std::memory_order_relaxed); }
+
+// Opt a kernel in to `bytes` of dynamic LDS.  Per kernel instantiation and device the largest size granted is remembered
+// (`floor` to begin with: what a launch may ask for without the opt-in), and the runtime is asked only when a launch needs more.
+int lds_opt_in(const void *kernel, int device, size_t bytes, size_t floor) {
+    static std::mutex mu;
+    static std::unordered_map<const void *, std::array<size_t, 64>> granted;
+    if (bytes <= floor) return AH_OK;
+    std::lock_guard<std::mutex> lk(mu);
+    size_t &g = granted[kernel][device & 63];
+    if (bytes <= g) return AH_OK;
+    AH_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    g = bytes;
+    return AH_OK;
+}
 
 int Context::ensure_device(size_t bytes) {
     clean_status = nullptr;  // (whoever carves the scratch next may write anywhere in it)

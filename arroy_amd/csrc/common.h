@@ -203,6 +203,19 @@ enum Tunable {
 };
 long long tun(int id);  // current value (api.hip)
 
+// The dispatch of a kernel family over its metrics: f(std::integral_constant<int, M>) for the M among those listed that
+// `metric` is, the last one for any other.
+template <int M, int... Rest, class F>
+int with_metric_of(int metric, F &&f) {
+    if constexpr (sizeof...(Rest) == 0)
+        return f(std::integral_constant<int, M>{});
+    else
+        return metric == M ? f(std::integral_constant<int, M>{}) : with_metric_of<Rest...>(metric, f);
+}
+
+// Opt a kernel in to `bytes` of dynamic LDS: the runtime is asked once per kernel instantiation, device and size (api.hip).
+int lds_opt_in(const void *kernel, int device, size_t bytes, size_t floor = 48 * 1024);
+
 // fn(0) .. fn(n - 1), fn(0) on the calling thread and the others on threads of their own.  A thread that cannot be created
 // (std::system_error) must not cross the C ABI: its share simply runs on the caller.
 template <class F>

@@ -2473,29 +2473,10 @@ struct LevelBufs {
     uint32_t verify;
 };
 
-// The dispatch over the metric of every margin-kernel family: f(std::integral_constant<int, metric>).
+// The dispatch over the metric of every margin-kernel family.
 template <class F>
 int with_metric(int metric, F &&f) {
-    switch (metric) {
-    case AH_EUCLIDEAN: return f(std::integral_constant<int, AH_EUCLIDEAN>{});
-    case AH_MANHATTAN: return f(std::integral_constant<int, AH_MANHATTAN>{});
-    case AH_COSINE: return f(std::integral_constant<int, AH_COSINE>{});
-    default: return f(std::integral_constant<int, AH_DOT_PRODUCT>{});
-    }
-}
-
-// Opt a kernel in to `bytes` of dynamic LDS.  Per kernel instantiation and device the largest size granted is remembered
-// (the default limit of 48 KiB to begin with), and the runtime is asked only when a launch needs more.
-int lds_opt_in(const void *kernel, int device, size_t bytes) {
-    static std::mutex mu;
-    static std::unordered_map<const void *, std::array<size_t, 64>> granted;
-    if (bytes <= 48 * 1024) return AH_OK;
-    std::lock_guard<std::mutex> lk(mu);
-    size_t &g = granted[kernel][device & 63];
-    if (bytes <= g) return AH_OK;
-    AH_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    g = bytes;
-    return AH_OK;
+    return with_metric_of<AH_EUCLIDEAN, AH_MANHATTAN, AH_COSINE, AH_DOT_PRODUCT>(metric, f);
 }
 
 // k_forest_create_split of an attempt (`metric`: the f32 space the two-means run in).

@@ -23,11 +23,11 @@
 #include "index_device.h"
 #include "split_device.h"
 #include "screen_device.h"
+#include "search_plan.h"
 
 namespace ah {
 
 static constexpr uint32_t kHeapLds = 1024;   // queue entries per query in LDS (8 KiB)
-static constexpr uint32_t kSortLds = 16384;  // candidate ids sorted in LDS per query (64 KiB)
 
 // One popped Descendants node of one query: the leaf-tile re-rank groups these by node.
 struct Visit {
@@ -50,6 +50,19 @@ enum SearchStatSlot {
     SS_ERR = 0, SS_WAVE_SMALL, SS_WAVE_BIG, SS_OCTET_LDS, SS_OCTET_GLOBAL, SS_UNITS_16, SS_UNITS_8, SS_UNITS_4, SS_VISITS,
     SS_SCREENED, SS_SURVIVORS, SS_BLOCK, SS_VISIT_TOTAL, SS_N_UNITS, SS_DONE, SS_MULTI, SS_WORDS = 16
 };
+static_assert(SS_WORDS == kStatusWords, "the status block as search_plan.h lays it out");
+
+// The metrics the leaf tiles serve, and those of the certified screen (with_metric_of: common.h).
+template <class F>
+int with_tile_metric(int metric, F &&f) {
+    return with_metric_of<AH_EUCLIDEAN, AH_COSINE, AH_DOT_PRODUCT>(metric, f);
+}
+template <class F>
+int with_screen_metric(int metric, F &&f) {
+    return with_metric_of<AH_COSINE, AH_DOT_PRODUCT>(metric, f);
+}
+// (k_search_select_screened holds its keys in static LDS: beyond 32 KiB of dynamic LDS for the query leaf it asks for the opt-in)
+static constexpr size_t kSelectLdsFloor = 32 * 1024;
 
 struct FilterSlot {  // what an ah_filter holds on the device
     const uint32_t *bits;
@@ -533,8 +546,6 @@ static constexpr uint32_t kUnitVisits = 16;
 struct TileUnit {
     uint32_t node, first, n_vis, pad;  // sorted[first .. first + n_vis)
 };
-static constexpr uint32_t kTileSlab = 128;       // rows per block and unit of more than 8 visits (twice that up to 8): k_leaf_tiles*
-static constexpr uint32_t kTileSmallSlab = 64;   // rows per block of k_leaf_tiles16 in a small submission (32 octets x 2 rows)
 // rows of a unit's leaf one block of k_leaf_tiles16 takes (small: the small submissions' variant of the kernel)
 __host__ __device__ constexpr uint32_t tile_slab_rows(uint32_t n_vis, bool small) {
     return small && n_vis <= 2 ? kTileSmallSlab : (n_vis > 8 ? kTileSlab : 2 * kTileSlab);
@@ -1049,8 +1060,7 @@ __global__ __launch_bounds__(8 * kOct) void k_descend_block(DataView nv, SearchP
 // known leaves in LDS and recomputes x.  The last block to finish (a counter) gathers every list, orders the leaves as
 // k_descend_block does (octet order inside a list, equal keys of two lists across the cut -> the sequential descent) and
 // copies the ids; it also wipes what the query wrote, so the control block (Context::d_multi) is zero between calls.
-static constexpr uint32_t kMultiMaxBlocks = 16, kMultiLeaves = 32, kMultiLists = kMultiMaxBlocks * 8, kMultiMaxQueries = 32;
-static constexpr uint32_t kMultiKnown = 1024, kMultiCap = 1024;
+static constexpr uint32_t kMultiLeaves = 32, kMultiLists = kMultiMaxBlocks * 8, kMultiKnown = 1024;  // (kMultiMaxBlocks, kMultiMaxQueries, kMultiCap: search_plan.h)
 struct MultiCtl {
     uint32_t done, failed, pad[14];
     unsigned long long leaf[kMultiLists][kMultiLeaves];  // key word << 32 | ids the leaf adds (never 0); list = block * 8 + octet
@@ -1690,7 +1700,6 @@ __global__ __launch_bounds__(256) void k_sort_dedup_lds(uint32_t *__restrict__ n
 // words per step, a wave prefix sum of the popcounts gives every lane its place, so one store instruction of the wave
 // lands in a few adjacent lines of the output.
 // An id beyond `id_limit` cannot be an item of the dataset: bit 0 of *err, the same error the re-rank would raise.
-static constexpr uint32_t kBitmapMaxWords = 39 * 1024;  // 156 KiB of the 160 KiB of LDS: 1 277 952 ids
 __global__ __launch_bounds__(1024) void k_dedup_bitmap_lds(uint32_t *__restrict__ nns, uint32_t stride,
                                                            uint32_t *__restrict__ counts, uint32_t n_words,
                                                            uint32_t id_limit, uint32_t *__restrict__ err) {
@@ -1767,7 +1776,6 @@ __global__ __launch_bounds__(1024) void k_dedup_bitmap_lds(uint32_t *__restrict_
 // Two exclusive scans over the per-node visit counters in one pass (3 launches): `cursor` = first slot of the node's
 // visits in the sorted list, `ustart` = first work unit of the node (a unit = <= 16 visits of one node).  The last
 // launch also writes the units.
-static constexpr uint32_t kLeafScanItems = 2048;  // 256 threads x 8
 __device__ __forceinline__ uint2 block_exclusive_scan2(uint2 local, uint2 *s_wave, uint2 &block_total) {
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     uint2 incl = local;
@@ -1881,7 +1889,6 @@ __global__ __launch_bounds__(256) void k_visit_scatter(const Visit *__restrict__
 // counter per node of the index (and a fourth launch zeroes them) to place what for one query is a dozen visits.  One block
 // sorts the visits by node in LDS instead — runs of one node are the node's visits, every 16 of a run a unit.  More than
 // kSmallVisits visits: bit 5 of *err, the submission takes the long way like any other overflow of the visit list.
-static constexpr uint32_t kSmallVisits = 2048;
 __global__ __launch_bounds__(256) void k_units_small(const Visit *__restrict__ visits, const uint32_t *__restrict__ total,
                                                      uint32_t cap, Visit *__restrict__ sorted, TileUnit *__restrict__ units,
                                                      uint32_t *__restrict__ n_units, uint32_t *__restrict__ stats, QueriesH16 h16,
@@ -2045,7 +2052,7 @@ __global__ __launch_bounds__(1024) void k_flag_duplicates(uint32_t *__restrict__
 // candidates in LDS, 32768 slots for <= 24576 candidates (a submission with longer lists takes the sorted path).  The
 // first insertion of an id wins its slot; a later one finds it there and is flagged.  0xFFFFFFFF marks an empty slot, so the
 // path is not taken when that id is stored.
-static constexpr uint32_t kHashSlots = 32768, kHashMaxCandidates = 24576;
+static constexpr uint32_t kHashSlots = 32768;  // (kHashMaxCandidates: search_plan.h)
 __global__ __launch_bounds__(1024) void k_flag_duplicates_hash(uint32_t *__restrict__ nns, uint32_t stride,
                                                                const uint32_t *__restrict__ counts,
                                                                uint32_t *__restrict__ unique, uint32_t *__restrict__ err) {
@@ -3245,10 +3252,8 @@ static int launch_screen_verify(ah_dataset *ds, const ScreenSearch &ss, const ui
     }
     const DataView dv = ds->view();
     const size_t lds = (size_t)ds->pitch * 4;
-    if (lds > 48 * 1024) {
-        AH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_screen_verify<AH_COSINE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        AH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_screen_verify<AH_DOT_PRODUCT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    }
+    AH_TRY(lds_opt_in(ds->metric == AH_COSINE ? reinterpret_cast<const void *>(k_screen_verify<AH_COSINE>)
+                                              : reinterpret_cast<const void *>(k_screen_verify<AH_DOT_PRODUCT>), ds->device, lds));
     const dim3 grid(64, nq);
     if (ds->metric == AH_COSINE)
         hipLaunchKernelGGL(k_screen_verify<AH_COSINE>, grid, dim3(256), lds, s, dv, ss, nns, dist, stride, counts, segs, qvecs, qstride, qhdrs, ctr);
@@ -3262,7 +3267,7 @@ static int launch_screen_verify(ah_dataset *ds, const ScreenSearch &ss, const ui
 // distance); the slots beyond min(k, unique) are padded with 0xFFFFFFFF / NaN like k_batch_topk_emit does.  Selection as
 // in k_batch_topk_select (batch.hip): 2048 linear bins over the distance words, the bin of the k-th key by a scan, a
 // bitonic sort of the <= 1024 keys up to that bin.  err bit 2: a non-finite distance; bit 3: the selection does not fit.
-static constexpr uint32_t kSelectBins = 2048, kSelectCap = 1024, kSelectThreads = 1024;
+static constexpr uint32_t kSelectBins = 2048, kSelectThreads = 1024;  // (kSelectCap: search_plan.h)
 __global__ __launch_bounds__(kSelectThreads) void k_search_select(DataView dv, const uint32_t *__restrict__ nns,
                                                        const float *__restrict__ dist_all, uint32_t stride,
                                                        const uint32_t *__restrict__ counts,
@@ -3887,8 +3892,7 @@ int launch_rerank_screened(ah_dataset *ds, const RerankBufs &b, uint32_t tile_fi
     if (first && !int8) hipLaunchKernelGGL(k_queries_h16, dim3(nq), dim3(64), 0, s, b.d_qvecs, b.qstride, ds->dims, ds->hpitch, b.d_q16, b.d_qstats);
     const auto k_pairs_screen = int8 ? k_pairs_screen8 : k_pairs_screen16;  // (the query's int8 digits / halves in LDS)
     const size_t sh = (size_t)(int8 ? ds->pitch8 : ds->hpitch) * 2;
-    if (sh > 48 * 1024)
-        AH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_pairs_screen), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
+    AH_TRY(lds_opt_in(reinterpret_cast<const void *>(k_pairs_screen), ds->device, sh));
     if (n_tiles)
         hipLaunchKernelGGL(k_pairs_screen, dim3(n_tiles), dim3(256), sh, s, dv, ss, b.d_segs, b.d_tiles + tile_first, tile_candidates, b.d_ids,
                            b.d_dist, b.d_err);
@@ -3898,20 +3902,13 @@ int launch_rerank_screened(ah_dataset *ds, const RerankBufs &b, uint32_t tile_fi
     }
     AH_TRY(launch_screen_verify(ds, ss, b.d_ids, b.d_dist, 0u, nullptr, b.d_segs, nq, b.d_qvecs, b.qstride, b.d_qhdrs, s));
     const size_t sel_lds = (size_t)ds->pitch * 4;
-    if (sel_lds > 32 * 1024) {
-        AH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_search_select_screened<AH_COSINE>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)sel_lds));
-        AH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_search_select_screened<AH_DOT_PRODUCT>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)sel_lds));
-    }
-#define AH_LAUNCH(M)                                                                                                             \
-    hipLaunchKernelGGL((k_search_select_screened<M>), dim3(nq), dim3(1024), sel_lds, s, dv, ss, b.d_ids, b.d_dist, 0u, (const uint32_t *)nullptr, \
-                       (const uint32_t *)nullptr, k_out, b.d_qvecs, b.qstride, b.d_qhdrs, b.d_out_ids, b.d_out_dist, b.d_err, b.d_segs)
-    if (ds->metric == AH_COSINE)
-        AH_LAUNCH(AH_COSINE);
-    else
-        AH_LAUNCH(AH_DOT_PRODUCT);
-#undef AH_LAUNCH
+    AH_TRY(with_screen_metric(ds->metric, [&](auto m) -> int {
+        constexpr int M = decltype(m)::value;
+        AH_TRY(lds_opt_in(reinterpret_cast<const void *>(k_search_select_screened<M>), ds->device, sel_lds, kSelectLdsFloor));
+        hipLaunchKernelGGL((k_search_select_screened<M>), dim3(nq), dim3(1024), sel_lds, s, dv, ss, b.d_ids, b.d_dist, 0u, (const uint32_t *)nullptr,
+                           (const uint32_t *)nullptr, k_out, b.d_qvecs, b.qstride, b.d_qhdrs, b.d_out_ids, b.d_out_dist, b.d_err, b.d_segs);
+        return AH_OK;
+    }));
     AH_HIP(hipGetLastError());
     return AH_OK;
 }
@@ -4395,673 +4392,670 @@ struct ChunkStats {
     }
 };
 
-static int search_chunk(ah_index *ix, Context *ctx, const float *queries, const uint32_t *query_rows, size_t nq,
-                        size_t count, uint32_t search_k, uint32_t nns_stride, const uint32_t *d_filter_bits,
-                        uint64_t filter_len_bits, double filter_share, bool wave_descent, const uint32_t *d_leaf_kept,
-                        uint32_t *out_ids, float *out_dists, uint32_t *out_counts, bool allow8 = true,
-                        const MixedFilters *mixed = nullptr, const VariedParams *varied = nullptr) {
-    ah_dataset *ds = ix->ds;
-    // `filtered`: what the host's path choices ask; d_filter_bits stays the one bitmap of a uniform sub-batch (null in a mixed one)
-    const bool filtered = d_filter_bits || mixed;
-    if (mixed) filter_share = mixed->min_share;
-    hipStream_t s = ctx->stream;
-    const size_t qstride = (ds->row_bytes() + 255) & ~(size_t)255;
-    const size_t k = count;
-    // device scratch (one carve for the whole chunk)
-    auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const uint32_t max_tiles_bound = (uint32_t)(nq * ((size_t)nns_stride / batch_tile_candidates() + 1));
-    // count <= 2048: the batched tournament top-k; beyond: the single-query kernels, one query after the other (the
-    // reference accepts any count, `Reader::nns(count)`; large counts are rare and not a throughput path)
-    const bool big_k = !batch_supported((uint32_t)std::min<size_t>(k, 0xFFFFFFFFu));
-    const size_t kstride = big_k ? (topk_scratch_bytes(nns_stride, std::min<size_t>(k, nns_stride)) + 15) / 16 : batch_key_stride(nns_stride);
-    const uint32_t heap_cap = ix->n_nodes + ix->n_trees + 2;
-    size_t dev_bytes = pad(nq * (size_t)ds->dims * 4) + pad(nq * 4) + nq * qstride + pad(nq * 8) + pad(nq * (size_t)nns_stride * 4) * 2 +
-                       pad(nq * 4) * 3 + pad(nq * sizeof(RerankSeg)) + pad((size_t)max_tiles_bound * sizeof(RerankTile)) +
-                       2 * pad(nq * kstride * 8) + pad(nq * k * 4) * 2 + pad(SS_WORDS * 4) + pad(nq * 4) + 4096 + (mixed ? pad(nq * 4) : 0) +
-                       (varied ? 2 * pad(nq * 4) : 0);
-    // counters of the row-major re-rank, reserved when the candidate lists could be long enough for it
-    const size_t inv_bytes = batch_invert_wanted(ds->view(), (uint64_t)nq * nns_stride) ? batch_invert_counter_bytes(ds->n, (uint64_t)nq * nns_stride) : 0;
-    dev_bytes += pad(inv_bytes);
-    // leaf-tile re-rank (see k_leaf_tiles): which submissions take it, and its scratch
-    const uint32_t max_id = ds->identity_ids ? (uint32_t)(ds->n - 1) : ds->last_id;
-    const uint32_t bitmap_words = (uint32_t)(((uint64_t)max_id / 32 + 1 + 1023) / 1024 * 1024);
-    const bool bitmap_fits = tun(TUN_SEARCH_BITMAP) != 0 && bitmap_words <= kBitmapMaxWords;
-    // nns.dedup() of the tiles: the LDS bitmap, or a hash set of the candidates when the id space is too big for it
-    const bool hash_fits = nns_stride <= kHashMaxCandidates && max_id != 0xFFFFFFFFu;
-    // (never in a mixed sub-batch: the tiles read the kept ids of a leaf from ONE of its visits for all of them, k_leaf_tiles;
-    // without them no descent is a last pass, so k_descend_multi and the units of a single query are out as well)
-    // (count <= kSelectCap: the selections behind the tiles hold kSelectCap keys and select at least min(count, distinct
-    // candidates) of them, so a larger count could only do the whole tile pass, overflow and be redone — after an int8 pass and
-    // its binary16 retry where that stage is on, each noted as a failure of the int8 stage in its window of 64 sub-batches.
-    // Unless a query cannot have more than kSelectCap candidates at all: a count meant as "everything" under a small search_k)
-    const bool tiles = !mixed && tun(TUN_SEARCH_TILES) != 0 && (bitmap_fits || hash_fits) && !big_k &&
-                       (k <= kSelectCap || nns_stride <= kSelectCap) && ds->dims >= 32 &&
-                       ix->max_desc <= 65535u * kTileSlab &&
-                       (ds->metric == AH_EUCLIDEAN || ds->metric == AH_COSINE || ds->metric == AH_DOT_PRODUCT);
-    const uint32_t visit_cap = (uint32_t)std::min<uint64_t>((uint64_t)nq * nns_stride, 2u << 20);
-    const uint32_t n_leaf_sums = (ix->n_nodes + kLeafScanItems - 1) / kLeafScanItems;
-    // certified top-k screen of the tile re-rank: the binary16 shadow of the rows must exist (ah_index_create makes it)
-    const bool screened = tiles && tun(TUN_SEARCH_SCREEN) != 0 && (ds->metric == AH_COSINE || ds->metric == AH_DOT_PRODUCT) &&
-                          ds->screen_ready.load(std::memory_order_acquire);  // (published: common.h)
-    if (screened) dev_bytes += pad(nq * (size_t)ds->hpitch * 2) + pad(nq * sizeof(float4)) + pad(nq * (size_t)nns_stride * 4);
-    // ... and on the int8 copy before that (round 6): the submissions of at least AH_SEARCH_SCREEN8_MIN_QUERIES queries (65: past
-    // the small ones' unit builder).  From 9 queries a call the leaf tiles are bound by the bytes of their rows (64 queries: 294 of
-    // the call's 508 us) and the int8 rows do cut them to 249 — but the wider band of survivors costs the selection 65 -> 95 us
-    // and the queries' digits a launch: 511 us against 502, measured, so the default leaves those calls on binary16; see ScreenSearch
-    const bool screened8 = screened && allow8 && tun(TUN_SEARCH_SCREEN8) != 0 && !ix->search8_off.load(std::memory_order_relaxed) &&
-                           (long long)nq > std::max(tun(TUN_SEARCH_SMALL_TILES_MAX_QUERIES), tun(TUN_SEARCH_SCREEN8_MIN_QUERIES) - 1) &&
-                           ds->screen8_ready.load(std::memory_order_acquire);
-    if (screened8) dev_bytes += pad(nq * (size_t)ds->pitch8 * 2) + pad(nq * sizeof(float4)) + pad(nq * (size_t)nns_stride * 4);
-    // (a few queries a call: the list of (unit, slab) pairs k_units_small leaves for the tile launch)
-    const size_t items_cap = tiles && (long long)nq <= tun(TUN_SEARCH_SMALL_UNITS_MAX_QUERIES) && tun(TUN_SEARCH_ITEM_LIST) != 0
-                                 ? nq * ((size_t)nns_stride / kTileSmallSlab + 1) + kSmallVisits + 1
-                                 : 0;
-    if (tiles)
-        dev_bytes += pad((size_t)visit_cap * sizeof(Visit)) * 2 + pad((size_t)visit_cap * sizeof(TileUnit)) +
-                     pad((size_t)ix->n_nodes * 4 + 8) + 2 * pad((size_t)ix->n_nodes * 4) + pad((size_t)n_leaf_sums * 8) + pad(nq * 4) +
-                     pad(items_cap * 4) + pad(nq * 4);
-    void *const clean_status = ctx->clean_status;  // (ensure_device forgets it: see Context)
-    AH_TRY(ctx->ensure_device(dev_bytes));
-    const size_t pin_bytes = pad(nq * (size_t)ds->dims * 4) + pad(nq * 4) * 4 + pad(nq * sizeof(RerankSeg)) +
-                             pad((size_t)max_tiles_bound * sizeof(RerankTile)) + pad(nq * k * 4) * 2 + 4096 + (mixed ? pad(nq * 4) : 0) + (varied ? 2 * pad(nq * 4) : 0);
-    AH_TRY(ctx->ensure_pinned(pin_bytes));
-    uint8_t *dbase = reinterpret_cast<uint8_t *>(ctx->d_scratch);
-    size_t doff = 0;
-    auto dtake = [&](size_t bytes) {
-        void *p = dbase + doff;
-        doff += pad(bytes);
-        return p;
-    };
-    uint8_t *pbase = reinterpret_cast<uint8_t *>(ctx->h_pinned);
-    size_t poff = 0;
-    auto ptake = [&](size_t bytes) {
-        void *p = pbase + poff;
-        poff += pad(bytes);
-        return p;
-    };
-    float *d_qf32 = (float *)dtake(nq * (size_t)ds->dims * 4);
-    uint32_t *d_qrows = (uint32_t *)dtake(nq * 4);
-    uint8_t *d_qvecs = (uint8_t *)dtake(nq * qstride);
-    float *d_qhdrs = (float *)dtake(nq * 8);
-    uint32_t *d_nns = (uint32_t *)dtake(nq * (size_t)nns_stride * 4);
-    float *d_dist = (float *)dtake(nq * (size_t)nns_stride * 4);
-    uint32_t *d_counts = (uint32_t *)dtake(nq * 4);
-    uint32_t *d_overflow = (uint32_t *)dtake(nq * 4);
-    uint32_t *d_list = (uint32_t *)dtake(nq * 4);
-    RerankSeg *d_segs = (RerankSeg *)dtake(nq * sizeof(RerankSeg));
-    RerankTile *d_tiles = (RerankTile *)dtake((size_t)max_tiles_bound * sizeof(RerankTile));
-    uint64_t *d_ka = (uint64_t *)dtake(nq * kstride * 8);
-    uint64_t *d_kb = (uint64_t *)dtake(nq * kstride * 8);
-    uint32_t *d_oi = (uint32_t *)dtake(nq * k * 4);
-    float *d_od = (float *)dtake(nq * k * 4);
-    uint32_t *d_err = (uint32_t *)dtake(SS_WORDS * 4);  // [error bits][SearchStatSlot counters]
-    // (d_oi, d_od, d_err, d_unique lie back to back, and so do their pinned mirrors below: the tile path reads all four
-    // back with ONE copy — a call of one query is a dozen launches and copies of ~5 us each)
-    uint32_t *d_unique = (uint32_t *)dtake(nq * 4);
-    uint32_t *d_inv = inv_bytes ? (uint32_t *)dtake(inv_bytes) : nullptr;
-    Visit *d_visits = nullptr, *d_sorted = nullptr;
-    TileUnit *d_units = nullptr;
-    uint32_t *d_leaf_count = nullptr, *d_cursor = nullptr, *d_ustart = nullptr, *d_items = nullptr, *d_unit_counts = nullptr;
-    uint2 *d_leaf_sums = nullptr;
-    if (tiles) {
-        d_visits = (Visit *)dtake((size_t)visit_cap * sizeof(Visit));
-        d_sorted = (Visit *)dtake((size_t)visit_cap * sizeof(Visit));
-        d_units = (TileUnit *)dtake((size_t)visit_cap * sizeof(TileUnit));
-        d_leaf_count = (uint32_t *)dtake((size_t)ix->n_nodes * 4 + 8);  // + the number of visits, + the number of units
-        d_cursor = (uint32_t *)dtake((size_t)ix->n_nodes * 4);
-        d_ustart = (uint32_t *)dtake((size_t)ix->n_nodes * 4);
-        d_leaf_sums = (uint2 *)dtake((size_t)n_leaf_sums * 8);
-        if (items_cap) d_items = (uint32_t *)dtake(items_cap * 4);
-        d_unit_counts = (uint32_t *)dtake(nq * 4);
-    }
-    ScreenSearch ss{};
-    if (screened) {
-        ss = screen_of_dataset(ds, screened8);
-        ss.aux = ds->metric == AH_COSINE ? (float *)dtake(nq * (size_t)nns_stride * 4) : nullptr;
-        ss.q16 = (const uint16_t *)dtake(nq * (size_t)ds->hpitch * 2);
-        ss.qstats = (const float4 *)dtake(nq * sizeof(float4));
-    }
-    if (screened8) {
-        ss.q8 = (const int8_t *)dtake(nq * (size_t)ds->pitch8 * 2);
-        ss.q8stats = (const float4 *)dtake(nq * sizeof(float4));
-        ss.aux8 = (float *)dtake(nq * (size_t)nns_stride * 4);
-    }
-    float *h_q = (float *)ptake(nq * (size_t)ds->dims * 4);
-    uint32_t *h_qrows = (uint32_t *)ptake(nq * 4);
-    uint32_t *h_overflow = (uint32_t *)ptake(nq * 4);
-    uint32_t *h_list = (uint32_t *)ptake(nq * 4);
-    RerankSeg *h_segs = (RerankSeg *)ptake(nq * sizeof(RerankSeg));
-    RerankTile *h_tiles = (RerankTile *)ptake((size_t)max_tiles_bound * sizeof(RerankTile));
-    uint32_t *h_oi = (uint32_t *)ptake(nq * k * 4);
-    float *h_od = (float *)ptake(nq * k * 4);
-    uint32_t *h_err = (uint32_t *)ptake(SS_WORDS * 4);
-    uint32_t *h_counts = (uint32_t *)ptake(nq * 4);
-    ChunkStats cs;
-    cs.s.chunks = 1;
-    cs.s.queries = nq;
-    if (d_filter_bits) cs.s.filtered_queries = nq;
-    if (mixed) cs.s.filtered_queries = mixed->n_filtered;
+// The tunables of the sub-batch path, read once per API call: nothing below this function reads one.
+static SearchKnobs search_knobs() {
+    SearchKnobs kn{};
+    kn.bitmap = tun(TUN_SEARCH_BITMAP) != 0, kn.tiles = tun(TUN_SEARCH_TILES) != 0, kn.screen = tun(TUN_SEARCH_SCREEN) != 0;
+    kn.screen8 = tun(TUN_SEARCH_SCREEN8) != 0, kn.item_list = tun(TUN_SEARCH_ITEM_LIST) != 0, kn.small_gate = tun(TUN_SEARCH_SMALL_GATE) != 0;
+    kn.status_wipe = tun(TUN_SEARCH_STATUS_WIPE) != 0, kn.fused_prepare = tun(TUN_SEARCH_FUSED_PREPARE) != 0, kn.multi = tun(TUN_SEARCH_MULTI) != 0;
+    kn.multi_own_units = tun(TUN_SEARCH_MULTI_OWN_UNITS) != 0, kn.flat_tiles = tun(TUN_SEARCH_FLAT_TILES) != 0;
+    kn.single_fused = tun(TUN_SEARCH_SINGLE_FUSED) != 0, kn.multi_ids_by_tiles = tun(TUN_SEARCH_MULTI_IDS_BY_TILES) != 0;
+    kn.multi_trace = tun(TUN_SEARCH_MULTI_TRACE) != 0, kn.fused_flag = tun(TUN_SEARCH_FUSED_FLAG) != 0, kn.spin_wait = tun(TUN_SEARCH_SPIN_WAIT) != 0;
+    kn.wave = tun(TUN_SEARCH_WAVE) != 0, kn.debug = tun(TUN_DEBUG) != 0;
+    kn.small_tiles_max_queries = tun(TUN_SEARCH_SMALL_TILES_MAX_QUERIES), kn.screen8_min_queries = tun(TUN_SEARCH_SCREEN8_MIN_QUERIES);
+    kn.small_units_max_queries = tun(TUN_SEARCH_SMALL_UNITS_MAX_QUERIES), kn.block_max_queries = tun(TUN_SEARCH_BLOCK_MAX_QUERIES);
+    kn.multi_trees_per_block = tun(TUN_SEARCH_MULTI_TREES_PER_BLOCK), kn.multi_max_queries = tun(TUN_SEARCH_MULTI_MAX_QUERIES);
+    kn.screen8_max_visits = tun(TUN_SEARCH_SCREEN8_MAX_VISITS);
+    return kn;
+}
 
-    const DataView dv = ds->view();
-    // 1. query leaves (src/reader.rs:46-51 by_item, :64-75 by_vector)
-    // (a small submission: the kernel that prepares the query leaves reads the pinned staging buffer itself — 6 KB over the link
-    // cost less than the copy engine's launch)
-    const bool zero_copy_queries = queries && (long long)nq <= tun(TUN_SEARCH_SMALL_UNITS_MAX_QUERIES);
-    // The small-submission kernels have hard capacities and, on the leaf-tile path, nothing behind them: k_descend_block holds 32
-    // leaves per octet (trees t = octet mod 32), k_units_small kSmallVisits visits per call; past either the whole chunk is
-    // redone the long way — correct, and more than twice the latency (round-5 advice: 128-d data at search_k = 10 000 opens
-    // ~100 leaves per query, a 3-tree index more than 32 per tree).  So: an estimate of the leaves one query opens — search_k
-    // items at the index's mean leaf size (what a filter keeps of it), a quarter more for leaves smaller than the mean — decides
-    // on the host whether a call starts there at all (at most 8 estimated leaves per octet, 0.8 x kSmallVisits visits per call).  AH_SEARCH_SMALL_GATE=0: as before (the overflow tests force the
-    // fall-backs with it).
-    bool block_fits = true, small_units_fit = true;
-    if (tun(TUN_SEARCH_SMALL_GATE) != 0 && ix->n_leaves) {
-        const double mean_leaf = std::max(1.0, (double)ix->desc_len / ix->n_leaves * (filtered ? std::max(filter_share, 1e-3) : 1.0));
-        const double est_leaves = 1.25 * (double)search_k / mean_leaf + 2.0;
-        // (measured, round 6: 64 queries x ~18 estimated leaves per octet overflowed the block kernel — the best-first order does
-        // not spread a query's leaves evenly over the trees; the benchmarked shapes sit near 1 per octet)
-        block_fits = est_leaves / std::max(1u, std::min(ix->n_trees, 32u)) <= 8.0;
-        small_units_fit = (double)nq * est_leaves <= 0.8 * kSmallVisits;
+// One sub-batch as its caller hands it over.  `count`, `search_k` and `nns_stride` are the sub-batch's largest under `varied`.
+// d_filter_bits stays the one bitmap of a uniform sub-batch (null in a mixed one).
+struct ChunkArgs {
+    const SearchKnobs *knobs;
+    const float *queries;
+    const uint32_t *query_rows;
+    size_t nq, count;
+    uint32_t search_k, nns_stride;
+    const uint32_t *d_filter_bits;
+    uint64_t filter_len_bits;
+    double filter_share;
+    bool wave_descent;
+    const uint32_t *d_leaf_kept;
+    uint32_t *out_ids;
+    float *out_dists;
+    uint32_t *out_counts;
+    const MixedFilters *mixed = nullptr;
+    const VariedParams *varied = nullptr;
+    bool allow8 = true;  // false: the binary16 retry of a sub-batch whose int8 stage held more survivors than the selection takes
+};
+
+// The scratch of one sub-batch, laid out by search_device_layout / search_pinned_layout (search_plan.h).
+struct SearchBufs {
+    float *d_qf32;
+    uint32_t *d_qrows;
+    uint8_t *d_qvecs;
+    float *d_qhdrs;
+    uint32_t *d_nns;
+    float *d_dist;
+    uint32_t *d_counts, *d_overflow, *d_list;
+    RerankSeg *d_segs;
+    RerankTile *d_tiles;
+    uint64_t *d_ka, *d_kb;
+    uint32_t *d_oi;
+    float *d_od;
+    uint32_t *d_err, *d_unique, *d_inv;
+    Visit *d_visits, *d_sorted;
+    TileUnit *d_units;
+    uint32_t *d_leaf_count, *d_cursor, *d_ustart;
+    uint2 *d_leaf_sums;
+    uint32_t *d_items, *d_unit_counts;
+    float *d_aux;
+    uint16_t *d_q16;
+    float4 *d_qstats;
+    int8_t *d_q8;
+    float4 *d_q8stats;
+    float *d_aux8;
+    uint32_t *d_slots, *d_sks, *d_cnt;
+    float *h_q;
+    uint32_t *h_qrows, *h_overflow, *h_list;
+    RerankSeg *h_segs;
+    RerankTile *h_tiles;
+    uint32_t *h_oi;
+    float *h_od;
+    uint32_t *h_err, *h_counts, *h_slots, *h_sks, *h_cnt;
+};
+
+// What every stage of search_chunk works on.
+struct ChunkCtx {
+    ah_index *ix;
+    Context *ctx;
+    const ChunkArgs &a;
+    const SearchKnobs &kn;
+    const ChunkShape &shape;
+    const ChunkPlan &plan;
+    SearchBufs &b;
+    SearchParams &sp;
+    ScreenSearch &ss;
+    ChunkStats &cs;
+    ah_dataset *ds() const { return ix->ds; }
+    hipStream_t stream() const { return ctx->stream; }
+    size_t qstride() const { return pad256(shape.row_bytes); }
+    // the count of query q of this sub-batch
+    size_t count_of(size_t q) const { return a.varied ? (size_t)a.varied->counts[q] : a.count; }
+    uint32_t *d_total() const { return b.d_err + SS_VISIT_TOTAL; }  // (the visit and unit counters live in spare words of the
+    uint32_t *d_n_units() const { return b.d_err + SS_N_UNITS; }    // status block: one memset clears them with it)
+    MultiCtl *multi_trace() const {  // AH_SEARCH_MULTI_TRACE, and k_descend_multi was the descent
+        return kn.multi_trace && plan.multi_blocks ? reinterpret_cast<MultiCtl *>(ctx->d_multi) : nullptr;
     }
-    const bool block_ok = block_fits && (long long)nq <= tun(TUN_SEARCH_BLOCK_MAX_QUERIES);
-    if (queries) {
-        memcpy(h_q, queries, nq * (size_t)ds->dims * 4);
-        if (!zero_copy_queries) AH_HIP(hipMemcpyAsync(d_qf32, h_q, nq * (size_t)ds->dims * 4, hipMemcpyHostToDevice, s));
+};
+
+static ChunkShape chunk_shape(const ah_index *ix, const ChunkArgs &a) {
+    const ah_dataset *ds = ix->ds;
+    ChunkShape z{};
+    z.nq = a.nq, z.count = a.count, z.search_k = a.search_k, z.nns_stride = a.nns_stride;
+    z.by_vector = a.queries != nullptr;
+    // `filtered`: what the host's path choices ask
+    z.filtered = a.d_filter_bits || a.mixed;
+    z.mixed = a.mixed != nullptr, z.varied = a.varied != nullptr, z.uniform_filter = a.d_filter_bits != nullptr;
+    z.filter_share = a.mixed ? a.mixed->min_share : a.filter_share;
+    z.wave_descent = a.wave_descent, z.allow8 = a.allow8;
+    z.n_nodes = ix->n_nodes, z.n_trees = ix->n_trees, z.n_leaves = ix->n_leaves, z.desc_len = ix->desc_len, z.max_desc = ix->max_desc;
+    z.metric = ds->metric, z.dims = ds->dims, z.pitch = ds->pitch, z.hpitch = ds->hpitch, z.pitch8 = ds->pitch8;
+    z.row_bytes = ds->row_bytes(), z.n = ds->n;
+    z.max_id = ds->identity_ids ? (uint32_t)(ds->n - 1) : ds->last_id;
+    z.screen_ready = ds->screen_ready.load(std::memory_order_acquire);  // (published: common.h)
+    z.screen8_ready = ds->screen8_ready.load(std::memory_order_acquire);
+    z.search8_off = ix->search8_off.load(std::memory_order_relaxed);
+    z.tile_candidates = batch_tile_candidates();
+    // counters of the row-major re-rank, reserved when the candidate lists could be long enough for it
+    z.inv_bytes = batch_invert_wanted(ds->view(), (uint64_t)a.nq * a.nns_stride) ? batch_invert_counter_bytes(ds->n, (uint64_t)a.nq * a.nns_stride) : 0;
+    z.batch_count = batch_supported((uint32_t)std::min<size_t>(a.count, 0xFFFFFFFFu));
+    z.kstride_batch = batch_key_stride(a.nns_stride);
+    z.kstride_single = z.batch_count ? 0 : (topk_scratch_bytes(a.nns_stride, std::min<size_t>(a.count, a.nns_stride)) + 15) / 16;
+    return z;
+}
+
+// 1. query leaves (src/reader.rs:46-51 by_item, :64-75 by_vector), the status block, the parameters of the descents
+static int stage_queries(ChunkCtx &c, const void *clean_status) {
+    const ChunkArgs &a = c.a;
+    const ChunkPlan &plan = c.plan;
+    const SearchBufs &b = c.b;
+    ah_dataset *ds = c.ds();
+    const DataView dv = ds->view();
+    hipStream_t s = c.stream();
+    const size_t nq = a.nq, qstride = c.qstride();
+    if (a.queries) {
+        memcpy(b.h_q, a.queries, nq * (size_t)ds->dims * 4);
+        if (!plan.zero_copy_queries) AH_HIP(hipMemcpyAsync(b.d_qf32, b.h_q, nq * (size_t)ds->dims * 4, hipMemcpyHostToDevice, s));
     } else {
-        memcpy(h_qrows, query_rows, nq * 4);
-        AH_HIP(hipMemcpyAsync(d_qrows, h_qrows, nq * 4, hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(k_load_items_as_queries, dim3((unsigned)nq), dim3(64), 0, s, dv, d_qrows, d_qvecs, qstride, d_qhdrs);
+        memcpy(b.h_qrows, a.query_rows, nq * 4);
+        AH_HIP(hipMemcpyAsync(b.d_qrows, b.h_qrows, nq * 4, hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(k_load_items_as_queries, dim3((unsigned)nq), dim3(64), 0, s, dv, b.d_qrows, b.d_qvecs, qstride, b.d_qhdrs);
     }
     // (the selection kernel of the previous small submission wiped its status block after copying it out: same place, same stream
     // — no memset node in front of this call's first kernel)
-    if (!(clean_status == (void *)d_err && tun(TUN_SEARCH_STATUS_WIPE) != 0)) AH_HIP(hipMemsetAsync(d_err, 0, SS_WORDS * 4, s));
+    if (!(clean_status == (void *)b.d_err && c.kn.status_wipe)) AH_HIP(hipMemsetAsync(b.d_err, 0, SS_WORDS * 4, s));
     // (by_vector leaves are prepared by the batch launcher below; the descent needs them first)
-    SearchParams sp{};
-    sp.stats = d_err;
-    sp.nodes = ix->d_nodes;
-    sp.roots = ix->d_roots;
-    sp.n_trees = ix->n_trees;
-    sp.desc = ix->d_desc;
-    sp.filter_bits = d_filter_bits;
-    sp.filter_len_bits = filter_len_bits;
-    sp.search_k = search_k;
-    sp.nns_stride = nns_stride;
-    if (mixed) {
-        uint32_t *d_slots = (uint32_t *)dtake(nq * 4), *h_slots = (uint32_t *)ptake(nq * 4);
-        memcpy(h_slots, mixed->slots, nq * 4);
-        AH_HIP(hipMemcpyAsync(d_slots, h_slots, nq * 4, hipMemcpyHostToDevice, s));
-        sp.filter_table = mixed->d_table;
-        sp.filter_of_query = d_slots;
+    SearchParams &sp = c.sp;
+    sp.stats = b.d_err;
+    sp.nodes = c.ix->d_nodes;
+    sp.roots = c.ix->d_roots;
+    sp.n_trees = c.ix->n_trees;
+    sp.desc = c.ix->d_desc;
+    sp.filter_bits = a.d_filter_bits;
+    sp.filter_len_bits = a.filter_len_bits;
+    sp.search_k = a.search_k;
+    sp.nns_stride = a.nns_stride;
+    if (a.mixed) {
+        memcpy(b.h_slots, a.mixed->slots, nq * 4);
+        AH_HIP(hipMemcpyAsync(b.d_slots, b.h_slots, nq * 4, hipMemcpyHostToDevice, s));
+        sp.filter_table = a.mixed->d_table;
+        sp.filter_of_query = b.d_slots;
     }
-    if (varied) {  // one copy: the two tables lie back to back on both sides
-        uint32_t *d_sks = (uint32_t *)dtake(nq * 4), *d_cnt = (uint32_t *)dtake(nq * 4);
-        uint32_t *h_sks = (uint32_t *)ptake(nq * 4), *h_cnt = (uint32_t *)ptake(nq * 4);
-        memcpy(h_sks, varied->search_ks, nq * 4);
-        memcpy(h_cnt, varied->counts, nq * 4);
-        AH_HIP(hipMemcpyAsync(d_sks, h_sks, pad(nq * 4) + nq * 4, hipMemcpyHostToDevice, s));
-        sp.search_k_of = d_sks;
-        sp.count_of = d_cnt;
+    if (a.varied) {  // one copy: the two tables lie back to back on both sides
+        memcpy(b.h_sks, a.varied->search_ks, nq * 4);
+        memcpy(b.h_cnt, a.varied->counts, nq * 4);
+        AH_HIP(hipMemcpyAsync(b.d_sks, b.h_sks, pad256(nq * 4) + nq * 4, hipMemcpyHostToDevice, s));
+        sp.search_k_of = b.d_sks;
+        sp.count_of = b.d_cnt;
     }
-    // the count of query q of this sub-batch
-    auto count_of = [&](size_t q) -> size_t { return varied ? (size_t)varied->counts[q] : k; };
-    // (... and when the block descent is the first kernel to want the leaves, it prepares them itself)
-    // (a small submission on the leaf-tile path makes the binary16 copies of its queries in the launch that places its visits)
-    const bool small_units = tiles && small_units_fit && (long long)nq <= tun(TUN_SEARCH_SMALL_UNITS_MAX_QUERIES);
-    // (small_units: otherwise k_queries_h16 below wants the leaves BEFORE the descent — until round 6 a call with the block
-    // descent on and k_units_small off screened against copies of unprepared leaves and was saved by the fall-back only)
-    const bool fuse_prepare = zero_copy_queries && tiles && small_units && wave_descent && !metric_is_bq_dev(ds->metric) &&
-                              (!filtered || filter_share >= 0.35) && block_ok && tun(TUN_SEARCH_FUSED_PREPARE) != 0;
-    if (queries && !fuse_prepare)
-        AH_TRY(launch_prepare_queries_only(dv, zero_copy_queries ? h_q : d_qf32, (uint32_t)nq, d_qvecs, qstride, d_qhdrs, s));
-    if (screened && !small_units)
-        hipLaunchKernelGGL(k_queries_h16, dim3((unsigned)nq), dim3(64), 0, s, d_qvecs, qstride, ds->dims, ds->hpitch,
-                           const_cast<uint16_t *>(ss.q16), const_cast<float4 *>(ss.qstats));
-    // 2. descent: one wave per query, then one octet per query for what that left, queue in LDS
+    if (a.queries && !plan.fuse_prepare)
+        AH_TRY(launch_prepare_queries_only(dv, plan.zero_copy_queries ? b.h_q : b.d_qf32, (uint32_t)nq, b.d_qvecs, qstride, b.d_qhdrs, s));
+    if (plan.screened && !plan.small_units)
+        hipLaunchKernelGGL(k_queries_h16, dim3((unsigned)nq), dim3(64), 0, s, b.d_qvecs, qstride, ds->dims, ds->hpitch, b.d_q16, b.d_qstats);
     // (ah_search_batch decides: a filter that keeps under 5 % of the items makes a query pop more nodes than the queues of
     // a wave hold; under a filter the wave descent reads what the filter keeps of every leaf, computed once per submission)
-    if (wave_descent && d_filter_bits) sp.leaf_kept = d_leaf_kept;
-    uint32_t multi_launched = 0;  // blocks per query of k_descend_multi, when that was the descent
-    bool passes_done = false;  // set by launch_wave: the block descent was the whole descent
-    bool units_done = false;   // ... and it wrote the leaf tiles' work units as well (one query)
-    bool items_made = false;   // k_units_small left the list of (unit, slab) pairs for the tile launch
-    uint32_t units_per_query_used = 0;  // > 0: every query's descent wrote its own units (SingleQueryOut::per_query)
-    auto launch_wave = [&](const VisitSink &sink) -> int {
-        // a query pops about 1 / (kept share) as many nodes under a filter: start with the big queues (one query per CU
-        // at a time) only then; otherwise they take what the small ones (four per CU) could not hold
-        const bool small_first = !filtered || filter_share >= 0.35;
+    if (a.wave_descent && a.d_filter_bits) sp.leaf_kept = a.d_leaf_kept;
+    return AH_OK;
+}
+
+// 2. descent: one wave per query (a block, or several, for the few queries of a small submission), then one octet per query
+// for what that left, queue in LDS.  last_pass_allowed (the tile pass): the block / multi descent is the whole descent.
+static int launch_descent(ChunkCtx &c, const VisitSink &sink, bool last_pass_allowed) {
+    const ChunkArgs &a = c.a;
+    const ChunkPlan &plan = c.plan;
+    const SearchBufs &b = c.b;
+    const SearchParams &sp = c.sp;
+    ah_index *ix = c.ix;
+    ah_dataset *ds = c.ds();
+    hipStream_t s = c.stream();
+    const size_t nq = a.nq, qstride = c.qstride();
+    if (a.wave_descent) {
         // few queries: a block of 32 octets per query (one tree per octet: a third of the chain of dependent pops) while the
         // device has the room — arroy's own API is one query per call (src/reader.rs:46-75)
-        static std::atomic<bool> lds_opt_in[64];  // once per device: the kernels that want more than 64 KiB of LDS
-        // (+ qstride bytes each: the query leaf's copy in LDS; a leaf of more than 32 KiB is refused above)
-        const size_t block_lds = block_descend_lds_bytes<32, 128, 32>() + qstride;
-        const void *wave_big = reinterpret_cast<const void *>(k_descend_wave<1024, 128>);
-        const void *block_fn = reinterpret_cast<const void *>(k_descend_block<32, 128, 32, 2>);
-        const void *multi_fn = reinterpret_cast<const void *>(k_descend_multi<128, 1>);
-        if (!lds_opt_in[ds->device & 63].load(std::memory_order_acquire)) {
-            AH_HIP(hipFuncSetAttribute(multi_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(multi_descend_lds_bytes<128>() + (32u << 10))));
-            AH_HIP(hipFuncSetAttribute(wave_big, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(wave_lds_bytes(1024, 128) + (32u << 10))));
-            AH_HIP(hipFuncSetAttribute(block_fn, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)(block_descend_lds_bytes<32, 128, 32>() + (32u << 10))));
-            lds_opt_in[ds->device & 63].store(true, std::memory_order_release);
-        }
-        if (small_first && block_ok) {
-            // On the leaf-tile path nothing runs behind the block kernel: what it cannot hold (rare: its capacities, equal keys
-            // of two octets across the cut) raises bit 4 of *err and the submission is redone the long way, instead of every
-            // small call paying two more launches for passes that find nothing to do.
-            const bool last_pass = sink.visits != nullptr;
-            // (one query: its units and its binary16 copy come out of the descent itself, see SingleQueryOut)
-            // A handful of queries, more trees than one wave has octets: the trees of a query dealt over G blocks of one descent wave
-            // each (k_descend_multi) — one query on G compute units.  Only as the last pass (what it cannot hold takes the long way).
-            const uint32_t per_block = (uint32_t)std::min<long long>(8, std::max<long long>(1, tun(TUN_SEARCH_MULTI_TREES_PER_BLOCK)));
-            const uint32_t multi_blocks = std::min<uint32_t>(kMultiMaxBlocks, (ix->n_trees + per_block - 1) / per_block);
-            const bool multi = last_pass && tun(TUN_SEARCH_MULTI) != 0 && multi_blocks >= 2 &&
-                               (long long)nq <= std::min<long long>(tun(TUN_SEARCH_MULTI_MAX_QUERIES), kMultiMaxQueries);
-            // ... and a few queries whose descents write their own units, query by query (the flat tile launch reads them with
-            // blockIdx.y = query): no launch that sorts a hundred visits of all queries by leaf.  Queries that open the same leaf
-            // read its rows once each.
-            const uint32_t units_per_query = (uint32_t)(visit_cap / std::max<size_t>(nq, 1));
-            const bool own_units = multi && nq > 1 && screened && units_per_query >= kMultiCap && tun(TUN_SEARCH_MULTI_OWN_UNITS) != 0 &&
-                                   (long long)nq <= tun(TUN_SEARCH_SMALL_TILES_MAX_QUERIES) && tun(TUN_SEARCH_FLAT_TILES) != 0 &&
-                                   std::max(1u, (ix->max_desc + kTileSmallSlab - 1) / kTileSmallSlab) <= 65535u;
+        // (+ qstride bytes each: the query leaf's copy in LDS; a leaf of more than 32 KiB is refused by wave_descent_wanted, so the
+        // grant of 32 KiB more covers it)
+        if (plan.small_first && plan.block_ok) {
+            const bool multi = last_pass_allowed && plan.descent == Descent::Multi;
             SingleQueryOut single{};
-            if (last_pass && (nq == 1 || own_units) && small_units && tun(TUN_SEARCH_SINGLE_FUSED) != 0) {
-                single.units = d_units;
-                single.sorted = d_sorted;
-                single.n_units = nq == 1 ? d_err + SS_N_UNITS : d_unit_counts;
-                single.per_query = nq == 1 ? 0u : units_per_query;
-                units_per_query_used = single.per_query;
-                if (screened)
-                    single.h16 = QueriesH16{d_qvecs, qstride, ds->dims, ds->hpitch, const_cast<uint16_t *>(ss.q16), const_cast<float4 *>(ss.qstats)};
-                units_done = true;
-                // (k_leaf_tiles16<true> will be the tile launch: the condition of `small_tiles` below)
-                single.ids_by_tiles = screened && !d_filter_bits && tun(TUN_SEARCH_MULTI_IDS_BY_TILES) != 0 &&
-                                      (long long)nq <= tun(TUN_SEARCH_SMALL_TILES_MAX_QUERIES) &&
-                                      std::max(1u, (ix->max_desc + kTileSmallSlab - 1) / kTileSmallSlab) <= 65535u;
+            if (last_pass_allowed && plan.single_fused) {
+                single.units = b.d_units;
+                single.sorted = b.d_sorted;
+                single.n_units = nq == 1 ? c.d_n_units() : b.d_unit_counts;
+                single.per_query = plan.units_per_query;
+                if (plan.screened) single.h16 = QueriesH16{b.d_qvecs, qstride, ds->dims, ds->hpitch, b.d_q16, b.d_qstats};
+                single.ids_by_tiles = plan.ids_by_tiles;
             }
-            const float *raw = (last_pass && fuse_prepare) ? (const float *)h_q : (const float *)nullptr;
+            const float *raw = (last_pass_allowed && plan.fuse_prepare) ? (const float *)b.h_q : (const float *)nullptr;
             if (multi) {
-                AH_TRY(ctx->ensure_multi(multi_ctl_bytes()));
-                hipLaunchKernelGGL((k_descend_multi<128, 1>), dim3((unsigned)nq * multi_blocks), dim3(256), multi_descend_lds_bytes<128>() + qstride,
-                                   s, ix->nv, sp, (uint32_t)nq, d_qvecs, qstride, d_qhdrs, d_nns, d_counts, d_overflow, sink, raw, d_qhdrs, single,
-                                   reinterpret_cast<MultiCtl *>(ctx->d_multi), multi_blocks, tun(TUN_SEARCH_MULTI_TRACE) != 0 ? 1u : 0u);
-                multi_launched = multi_blocks;
-            } else
-                hipLaunchKernelGGL((k_descend_block<32, 128, 32, 2>), dim3((unsigned)nq), dim3(256), block_lds, s, ix->nv, sp, (uint32_t)nq,
-                                   d_qvecs, qstride, d_qhdrs, d_nns, d_counts, d_overflow, sink, last_pass, raw, d_qhdrs, single);
-            if (last_pass) {
-                passes_done = true;
-                return AH_OK;
+                AH_TRY(lds_opt_in(reinterpret_cast<const void *>(k_descend_multi<128, 1>), ds->device, multi_descend_lds_bytes<128>() + (32u << 10)));
+                AH_TRY(c.ctx->ensure_multi(multi_ctl_bytes()));
+                hipLaunchKernelGGL((k_descend_multi<128, 1>), dim3((unsigned)nq * plan.multi_blocks), dim3(256), multi_descend_lds_bytes<128>() + qstride,
+                                   s, ix->nv, sp, (uint32_t)nq, b.d_qvecs, qstride, b.d_qhdrs, b.d_nns, b.d_counts, b.d_overflow, sink, raw, b.d_qhdrs, single,
+                                   reinterpret_cast<MultiCtl *>(c.ctx->d_multi), plan.multi_blocks, c.kn.multi_trace ? 1u : 0u);
+            } else {
+                const size_t block_lds = block_descend_lds_bytes<32, 128, 32>();
+                AH_TRY(lds_opt_in(reinterpret_cast<const void *>(k_descend_block<32, 128, 32, 2>), ds->device, block_lds + (32u << 10)));
+                hipLaunchKernelGGL((k_descend_block<32, 128, 32, 2>), dim3((unsigned)nq), dim3(256), block_lds + qstride, s, ix->nv, sp, (uint32_t)nq,
+                                   b.d_qvecs, qstride, b.d_qhdrs, b.d_nns, b.d_counts, b.d_overflow, sink, last_pass_allowed, raw, b.d_qhdrs, single);
             }
-        } else if (small_first)
+            if (last_pass_allowed) return AH_OK;
+        } else if (plan.small_first)
             hipLaunchKernelGGL((k_descend_wave<256, 64>), dim3((unsigned)nq), dim3(64), wave_lds_bytes(256, 64) + qstride, s, ix->nv, sp,
-                               (uint32_t)nq, d_qvecs, qstride, d_qhdrs, d_nns, d_counts, d_overflow, sink, false);
+                               (uint32_t)nq, b.d_qvecs, qstride, b.d_qhdrs, b.d_nns, b.d_counts, b.d_overflow, sink, false);
+        AH_TRY(lds_opt_in(reinterpret_cast<const void *>(k_descend_wave<1024, 128>), ds->device, wave_lds_bytes(1024, 128) + (32u << 10)));
         hipLaunchKernelGGL((k_descend_wave<1024, 128>), dim3((unsigned)nq), dim3(64), wave_lds_bytes(1024, 128) + qstride, s, ix->nv, sp,
-                           (uint32_t)nq, d_qvecs, qstride, d_qhdrs, d_nns, d_counts, d_overflow, sink, small_first);
-        return AH_OK;
-    };
+                           (uint32_t)nq, b.d_qvecs, qstride, b.d_qhdrs, b.d_nns, b.d_counts, b.d_overflow, sink, plan.small_first);
+    }
     const size_t heap_lds = (size_t)8 * kHeapLds * 8;
-    {
-        static std::atomic<bool> heap_opt_in[64];  // once per device (a runtime call per search is microseconds of a 0.2 ms call)
-        if (!heap_opt_in[ds->device & 63].load(std::memory_order_acquire)) {
-            AH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_descend<false>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)heap_lds));
-            AH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_descend<false, true>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)heap_lds));
-            heap_opt_in[ds->device & 63].store(true, std::memory_order_release);
-        }
-    }
-    if (tiles) {  // 2'. the leaf-tile path: descent with its visits recorded, no host round trip before the results
-        // (the visit and unit counters live in spare words of the status block: one memset clears them with it)
-        uint32_t *d_total = d_err + SS_VISIT_TOTAL, *d_n_units = d_err + SS_N_UNITS;
-        // a small submission places its visits with one block (k_units_small) and needs no counter per node
-        if (!small_units) AH_HIP(hipMemsetAsync(d_leaf_count, 0, (size_t)ix->n_nodes * 4, s));
-        const VisitSink sink{d_visits, d_total, visit_cap, small_units ? nullptr : d_leaf_count, d_err};
-        if (wave_descent) AH_TRY(launch_wave(sink));
-        if (!passes_done)
-            hipLaunchKernelGGL((k_descend<false>), dim3((unsigned)((nq + 7) / 8)), dim3(64), heap_lds, s, ix->nv, sp,
-                               (const uint32_t *)nullptr, (uint32_t)nq, d_qvecs, qstride, d_qhdrs, d_nns, d_counts, d_overflow,
-                               (uint64_t *)nullptr, 0u, sink, wave_descent);
-        if (units_done) {
-            // (nothing to place)
-        } else if (small_units) {
-            const QueriesH16 h16{d_qvecs, qstride, ds->dims, ds->hpitch, const_cast<uint16_t *>(ss.q16), const_cast<float4 *>(ss.qstats)};
-            hipLaunchKernelGGL(k_units_small, dim3(1u + (screened ? (unsigned)nq : 0u)), dim3(256), 0, s, d_visits, d_total, visit_cap,
-                               d_sorted, d_units, d_n_units, d_err, h16, d_items, (uint32_t)items_cap);
-            items_made = d_items != nullptr;
-        } else {
-            hipLaunchKernelGGL(k_leaf_scan_block, dim3(n_leaf_sums), dim3(256), 0, s, d_leaf_count, ix->n_nodes, d_cursor, d_ustart,
-                               d_leaf_sums);
-            hipLaunchKernelGGL(k_leaf_scan_sums, dim3(1), dim3(256), 0, s, d_leaf_sums, n_leaf_sums, d_n_units);
-            hipLaunchKernelGGL(k_leaf_scan_add, dim3(n_leaf_sums), dim3(256), 0, s, d_leaf_count, ix->n_nodes, d_cursor, d_ustart,
-                               d_leaf_sums, d_units, d_err);
-            hipLaunchKernelGGL(k_visit_scatter, dim3(256), dim3(256), 0, s, d_visits, d_total, visit_cap, d_cursor, d_sorted);
-        }
-        const unsigned tile_slabs = std::max(1u, (ix->max_desc + kTileSlab - 1) / kTileSlab);
-#define AH_TILES(M)                                                                                                        \
-    do {                                                                                                                   \
-        AH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_leaf_tiles<M>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                   (int)(4 * kRingBytesPerWave)));                                                         \
-        hipLaunchKernelGGL((k_leaf_tiles<M>), dim3(2048, tile_slabs), dim3(256), 4 * kRingBytesPerWave, s, dv, d_nns, d_sorted, \
-                           d_units, d_n_units, d_qvecs, qstride, d_qhdrs, d_dist, nns_stride, d_err);                       \
-    } while (0)
-        if (screened8) {
-            // the leaves few queries reached on the int8 copy (a quarter of the f32 bytes, a wider band of survivors), the leaves
-            // many queries share on the binary16 copy as before; the selection takes every candidate's bound from its own stage
-            // (the queries' int8 digits here, behind the descent: a small submission's query leaves are prepared BY its descent)
-            hipLaunchKernelGGL(k_queries_i8, dim3((unsigned)nq), dim3(64), 0, s, d_qvecs, qstride, ds->dims, ss);
-            const uint32_t max_vis8 = (uint32_t)std::max<long long>(1, tun(TUN_SEARCH_SCREEN8_MAX_VISITS));
-            hipLaunchKernelGGL(k_leaf_tiles8, dim3(2048, tile_slabs), dim3(256), 0, s, dv, ss, d_nns, d_sorted, d_units, d_n_units, d_dist,
-                               nns_stride, d_err, max_vis8);
-            hipLaunchKernelGGL((k_leaf_tiles16<false>), dim3(2048, tile_slabs), dim3(256), 0, s, dv, ss, d_nns, d_sorted, d_units,
-                               d_n_units, d_dist, nns_stride, d_err, max_vis8 + 1);
-        } else if (screened) {  // the candidates on the binary16 copies first: half the bytes (see k_search_select_screened)
-            // a small submission: slabs of 64 rows (a dozen leaves then fill 150 CUs instead of 50) and a grid that does not
-            // dispatch 24 000 blocks to find 12 units
-            const unsigned small_slabs = std::max(1u, (ix->max_desc + kTileSmallSlab - 1) / kTileSmallSlab);
-            const bool small_tiles = (long long)nq <= tun(TUN_SEARCH_SMALL_TILES_MAX_QUERIES) && small_slabs <= 65535u;
-            // (one query whose units came out of its descent: a flat list of (leaf, slab) items, see the kernel)
-            const bool flat_tiles = small_tiles && units_done && (nq == 1 || units_per_query_used) && visit_cap >= 128u &&
-                                    tun(TUN_SEARCH_FLAT_TILES) != 0;
-            uint32_t *tile_trace =
-                multi_launched && tun(TUN_SEARCH_MULTI_TRACE) != 0 ? &reinterpret_cast<MultiCtl *>(ctx->d_multi)->tile_trace[0] : nullptr;
-            if (flat_tiles)
-                hipLaunchKernelGGL((k_leaf_tiles16<true>), dim3(nns_stride / kTileSmallSlab + 129u, (unsigned)nq), dim3(256), 0, s, dv, ss, d_nns,
-                                   d_sorted, d_units, nq == 1 ? d_n_units : d_unit_counts, d_dist, nns_stride, d_err, 0u, ix->d_desc, 0u, tile_trace,
-                                   1u, (const uint32_t *)nullptr, units_per_query_used);
-            else if (small_tiles && items_made)  // one block per listed (unit, slab) pair (grid.y = 1: an overflowed list is walked)
-                hipLaunchKernelGGL((k_leaf_tiles16<true>), dim3((unsigned)std::min<size_t>(items_cap, 2048)), dim3(256), 0, s, dv, ss, d_nns,
-                                   d_sorted, d_units, d_n_units, d_dist, nns_stride, d_err, 0u, ix->d_desc, 0u, tile_trace, 0u, d_items);
-            else if (small_tiles)
-                hipLaunchKernelGGL((k_leaf_tiles16<true>), dim3(std::min<unsigned>(2048u, 32u * (unsigned)nq), small_slabs), dim3(256), 0, s,
-                                   dv, ss, d_nns, d_sorted, d_units, d_n_units, d_dist, nns_stride, d_err, 0u, ix->d_desc,
-                                   visit_cap >= std::min<unsigned>(2048u, 32u * (unsigned)nq) ? 1u : 0u, tile_trace);
-            else
-                hipLaunchKernelGGL((k_leaf_tiles16<false>), dim3(2048, tile_slabs), dim3(256), 0, s, dv, ss, d_nns, d_sorted, d_units,
-                                   d_n_units, d_dist, nns_stride, d_err);
-        } else {
-            switch (ds->metric) {
-            case AH_EUCLIDEAN: AH_TILES(AH_EUCLIDEAN); break;
-            case AH_COSINE: AH_TILES(AH_COSINE); break;
-            default: AH_TILES(AH_DOT_PRODUCT); break;
-            }
-        }
-#undef AH_TILES
-        if (tun(TUN_DEBUG)) {
-            AH_HIP(hipStreamSynchronize(s));
-            uint32_t nv = 0, np = 0;
-            AH_HIP(hipMemcpy(&nv, d_total, 4, hipMemcpyDeviceToHost));
-            AH_HIP(hipMemcpy(&np, d_n_units, 4, hipMemcpyDeviceToHost));
-            std::vector<Visit> hv(std::min(nv, visit_cap));
-            AH_HIP(hipMemcpy(hv.data(), d_visits, hv.size() * sizeof(Visit), hipMemcpyDeviceToHost));
-            std::vector<uint32_t> per(ix->n_nodes, 0);
-            for (auto &v : hv) per[v.node]++;
-            uint32_t hist[9] = {0}, leaves = 0;
-            for (uint32_t c : per)
-                if (c) { leaves++; hist[std::min(c, 8u)]++; }
-            fprintf(stderr, "[ah] search tiles: %u visits, %u leaves, %u units; visits per leaf 1..8+: %u %u %u %u %u %u %u %u\n", nv,
-                    leaves, np, hist[1], hist[2], hist[3], hist[4], hist[5], hist[6], hist[7], hist[8]);
-        }
-        // (after the tiles: they read the leaves' ids from the candidate buffers)
-        // a small submission: nns.dedup() inside the selection kernel (FLAG), when the bitmap fits beside its other LDS
-        const size_t sel_lds = (size_t)ds->pitch * 4;  // the query leaf in f32
-        const size_t fused_lds = sel_lds + (size_t)bitmap_words * 4;
-        const bool fused_flag = small_units && screened && bitmap_fits && nns_stride <= 16384 && fused_lds + (26u << 10) <= (160u << 10) &&
-                                tun(TUN_SEARCH_FUSED_FLAG) != 0;
-        if (fused_flag) {
-            *h_err = 0xFFFFFFFFu;  // (overwritten by the selection kernel's last block: a launch that never ran reads as a failure)
-            static std::atomic<uint32_t> fused_opt_in[64][2];  // [device][metric]: largest dynamic LDS opted in for
-            const int mi = ds->metric == AH_COSINE ? 0 : 1;
-            if (fused_opt_in[ds->device & 63][mi].load(std::memory_order_acquire) < fused_lds) {
-                const void *fn = mi == 0 ? reinterpret_cast<const void *>(k_search_select_screened<AH_COSINE, true>)
-                                         : reinterpret_cast<const void *>(k_search_select_screened<AH_DOT_PRODUCT, true>);
-                AH_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fused_lds));
-                fused_opt_in[ds->device & 63][mi].store((uint32_t)fused_lds, std::memory_order_release);
-            }
-        } else if (bitmap_fits) {
-            const size_t sh = (size_t)bitmap_words * 4;
-            static std::atomic<uint32_t> flag_lds[64];  // largest bitmap this device's kernel has been opted in for
-            if (sh > 48 * 1024 && flag_lds[ds->device & 63].load(std::memory_order_acquire) < sh) {
-                AH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_flag_duplicates),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
-                flag_lds[ds->device & 63].store((uint32_t)sh, std::memory_order_release);
-            }
-            hipLaunchKernelGGL(k_flag_duplicates, dim3((unsigned)nq), dim3(1024), sh, s, d_nns, nns_stride, d_counts, bitmap_words,
-                               max_id + 1, d_unique, d_err);
-        } else {
-            static std::atomic<bool> hash_opt_in[64];
-            if (!hash_opt_in[ds->device & 63].load(std::memory_order_acquire)) {
-                AH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_flag_duplicates_hash),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kHashSlots * 4)));
-                hash_opt_in[ds->device & 63].store(true, std::memory_order_release);
-            }
-            hipLaunchKernelGGL(k_flag_duplicates_hash, dim3((unsigned)nq), dim3(1024), kHashSlots * 4, s, d_nns, nns_stride, d_counts,
-                               d_unique, d_err);
-        }
-        if (screened && sel_lds > 32 * 1024 && !fused_flag) {
-            AH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_search_select_screened<AH_COSINE>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)sel_lds));
-            AH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_search_select_screened<AH_DOT_PRODUCT>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)sel_lds));
-        }
-        uint32_t *sel_trace = multi_launched && tun(TUN_SEARCH_MULTI_TRACE) != 0 ? &reinterpret_cast<MultiCtl *>(ctx->d_multi)->sel_trace[0] : nullptr;
-        if (screened) AH_TRY(launch_screen_verify(ds, ss, d_nns, d_dist, nns_stride, d_counts, nullptr, (uint32_t)nq, d_qvecs, qstride, d_qhdrs, s));
-        if (fused_flag && ds->metric == AH_COSINE)
-            hipLaunchKernelGGL((k_search_select_screened<AH_COSINE, true>), dim3((unsigned)nq), dim3(1024), fused_lds, s, dv, ss, d_nns, d_dist,
-                               nns_stride, d_counts, d_unique, (uint32_t)k, d_qvecs, qstride, d_qhdrs, h_oi, h_od, d_err, (const RerankSeg *)nullptr,
-                               bitmap_words, max_id + 1, h_counts, h_err, sel_trace, sp.count_of);
-        else if (fused_flag)
-            hipLaunchKernelGGL((k_search_select_screened<AH_DOT_PRODUCT, true>), dim3((unsigned)nq), dim3(1024), fused_lds, s, dv, ss, d_nns,
-                               d_dist, nns_stride, d_counts, d_unique, (uint32_t)k, d_qvecs, qstride, d_qhdrs, h_oi, h_od, d_err,
-                               (const RerankSeg *)nullptr, bitmap_words, max_id + 1, h_counts, h_err, sel_trace, sp.count_of);
-        else if (screened && ds->metric == AH_COSINE)
-            hipLaunchKernelGGL((k_search_select_screened<AH_COSINE>), dim3((unsigned)nq), dim3(1024), sel_lds, s, dv, ss, d_nns, d_dist,
-                               nns_stride, d_counts, d_unique, (uint32_t)k, d_qvecs, qstride, d_qhdrs, d_oi, d_od, d_err, (const RerankSeg *)nullptr, 0u, 0u,
-                               (uint32_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr, sp.count_of);
-        else if (screened)
-            hipLaunchKernelGGL((k_search_select_screened<AH_DOT_PRODUCT>), dim3((unsigned)nq), dim3(1024), sel_lds, s, dv, ss, d_nns, d_dist,
-                               nns_stride, d_counts, d_unique, (uint32_t)k, d_qvecs, qstride, d_qhdrs, d_oi, d_od, d_err, (const RerankSeg *)nullptr, 0u, 0u,
-                               (uint32_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr, sp.count_of);
-        else
-            hipLaunchKernelGGL(k_search_select, dim3((unsigned)nq), dim3(kSelectThreads), 0, s, dv, d_nns, d_dist, nns_stride, d_counts,
-                               d_unique, (uint32_t)k, d_oi, d_od, d_err, sp.count_of);
-        // a launch the runtime rejected (dynamic LDS beyond the limit, another architecture) would leave *err = 0 over
-        // uninitialised results: such a submission takes the sorted path as well
-        const hipError_t launch_err = hipGetLastError();
-        // ids, distances, status words and counts: one copy (the four buffers are carved back to back on both sides)
-        // (fused_flag: the selection kernel wrote ids, distances, counts and status into the pinned buffers itself)
-        if (!fused_flag) AH_HIP(hipMemcpyAsync(h_oi, d_oi, 2 * pad(nq * k * 4) + pad(SS_WORDS * 4) + nq * 4, hipMemcpyDeviceToHost, s));
-        // fused_flag: the selection's last block writes the status into pinned memory as the last thing the submission does (word 0
-        // after everything else, system-scope release).  Polling that word returns as soon as it lands; the runtime's own wait adds
-        // the end-of-kernel bookkeeping and its wake-up (AH_SEARCH_SPIN_WAIT=0: hipStreamSynchronize as before; it is also what
-        // happens after 2 ms without an answer — a launch that never ran).  Everything queued later runs behind this submission in
-        // stream order, so its scratch is safe to reuse.
-        bool answered = false;
-        if (fused_flag && launch_err == hipSuccess && tun(TUN_SEARCH_SPIN_WAIT) != 0) {
-            const auto t_spin = std::chrono::steady_clock::now();
-            for (uint32_t spin = 0;; spin++) {
-                if (__atomic_load_n(h_err, __ATOMIC_ACQUIRE) != 0xFFFFFFFFu) {
-                    answered = true;
-                    break;
-                }
-                __builtin_ia32_pause();
-                if ((spin & 1023u) == 1023u && std::chrono::steady_clock::now() - t_spin > std::chrono::milliseconds(2)) break;
-            }
-        }
-        if (!answered) AH_HIP(hipStreamSynchronize(s));
-        if (multi_launched && tun(TUN_SEARCH_MULTI_TRACE) != 0) {  // where the blocks of query 0 spent their time (10 ns ticks -> us)
-            std::vector<uint32_t> tr((size_t)kMultiMaxBlocks * 8);
-            AH_HIP(hipMemcpy(tr.data(), &reinterpret_cast<MultiCtl *>(ctx->d_multi)->trace[0][0], tr.size() * 4, hipMemcpyDeviceToHost));
-            for (uint32_t b = 0; b < multi_launched; b++)
-                fprintf(stderr, "[ah] multi block %u: query in LDS %.2f us, descent left %.2f, counted %.2f%s\n", b, tr[b * 8] * 0.01, tr[b * 8 + 1] * 0.01,
-                        tr[b * 8 + 2] * 0.01, tr[b * 8 + 5] > tr[b * 8 + 2] ? "  <- last" : "");
-            for (uint32_t b = 0; b < multi_launched; b++)
-                if (tr[b * 8 + 5] > tr[b * 8 + 2])
-                    fprintf(stderr, "[ah]   (stale unless marked) last block %u: lists gathered %.2f us, ordered %.2f, ids copied %.2f (%u leaves known, %u taken)\n", b,
-                            tr[b * 8 + 3] * 0.01, tr[b * 8 + 4] * 0.01, tr[b * 8 + 5] * 0.01, tr[b * 8 + 6], tr[b * 8 + 7]);
-        }
-        if (multi_launched && tun(TUN_SEARCH_MULTI_TRACE) != 0) {
-            uint32_t st[16];
-            AH_HIP(hipMemcpy(st, &reinterpret_cast<MultiCtl *>(ctx->d_multi)->sel_trace[0], sizeof(st), hipMemcpyDeviceToHost));
-            uint32_t tt[8];
-            AH_HIP(hipMemcpy(tt, &reinterpret_cast<MultiCtl *>(ctx->d_multi)->tile_trace[0], sizeof(tt), hipMemcpyDeviceToHost));
-            AH_HIP(hipMemset(&reinterpret_cast<MultiCtl *>(ctx->d_multi)->tile_trace[0], 0, sizeof(tt)));
-            fprintf(stderr, "[ah] tiles (latest block since ITS start): unit + visit known %.2f us, slab done %.2f us\n", tt[0] * 0.01, tt[1] * 0.01);
-            fprintf(stderr, "[ah] selection: leaf + tables in LDS %.2f us, candidates in registers %.2f, duplicates flagged %.2f, key range %.2f, "
-                    "k-th bin %.2f, survivors listed %.2f (%u), f32 distances %.2f, ranked + written %.2f, status written %.2f\n", st[0] * 0.01,
-                    st[1] * 0.01, st[2] * 0.01, st[3] * 0.01, st[4] * 0.01, st[5] * 0.01, st[9], st[6] * 0.01, st[7] * 0.01, st[8] * 0.01);
-        }
-        AH_REQUIRE((*h_err & 1u) == 0 || *h_err == 0xFFFFFFFFu, AH_ERR_MISSING_ITEM, "a descendant id does not exist in the dataset");
-        if ((*h_err & ~1u) == 0 && launch_err == hipSuccess) {
-            if (fused_flag) ctx->clean_status = d_err;  // (its selection kernel ran to its end and wiped the block behind itself)
-            for (size_t q = 0; q < nq; q++) out_counts[q] = (uint32_t)std::min<size_t>(count_of(q), h_counts[q]);
-            memcpy(out_ids, h_oi, nq * k * 4);
-            memcpy(out_dists, h_od, nq * k * 4);
-            cs.device_words(h_err);
-            cs.s.rerank_tiles = nq;
-            cs.s.rerank_screened8 = screened8 ? h_err[SS_SCREENED] : 0;
-            if (screened8) (void)screen8_window_note(ix->search8_seen, ix->search8_fails, false);
-            (bitmap_fits ? cs.s.dedup_flag_bitmap : cs.s.dedup_flag_hash) = nq;
-            cs.commit(ix);
-            return AH_OK;
-        }
-        if (screened8 && launch_err == hipSuccess && (*h_err & ~1u) == 8u) {
-            // more survivors than the selection holds on the int8 stage (candidates closer together than its error bound): the
-            // same sub-batch once more with the binary16 rows first — not the long way
-            if (screen8_window_note(ix->search8_seen, ix->search8_fails, true)) ix->search8_off.store(true, std::memory_order_relaxed);
-            {
-                std::lock_guard<std::mutex> lk(ix->stats_mu);
-                ix->stats.screen8_retried_chunks += 1;
-            }
-            return search_chunk(ix, ctx, queries, query_rows, nq, count, search_k, nns_stride, d_filter_bits, filter_len_bits, filter_share,
-                                wave_descent, d_leaf_kept, out_ids, out_dists, out_counts, false, nullptr, varied);
-        }
-        // a case the tiles do not reproduce (bits 2..5 of *err, see k_search_select / VisitSink): redo it the long way
-        cs.s.fallback_chunks = 1;
-        cs.s.fallback_non_finite = (*h_err & 4u) ? 1 : 0;
-        cs.s.fallback_select = (*h_err & 8u) ? 1 : 0;
-        cs.s.fallback_queue = (*h_err & 16u) ? 1 : 0;
-        cs.s.fallback_visits = (*h_err & 32u) ? 1 : 0;
-        cs.s.fallback_launch = launch_err != hipSuccess ? 1 : 0;
-        AH_HIP(hipMemsetAsync(d_err, 0, SS_WORDS * 4, s));
-        // (the block descent was the only writer of the query leaves under fuse_prepare: a launch the runtime rejected has left them
-        // unprepared — the passes below read them; preparing them again when it did run changes nothing)
-        if (queries && fuse_prepare) AH_TRY(launch_prepare_queries_only(dv, h_q, (uint32_t)nq, d_qvecs, qstride, d_qhdrs, s));
-    }
-    if (wave_descent) AH_TRY(launch_wave(VisitSink{}));
-    if (mixed)  // (octets of one wave under different filters)
+    if (a.mixed) {  // (octets of one wave under different filters)
+        AH_TRY(lds_opt_in(reinterpret_cast<const void *>(k_descend<false, true>), ds->device, heap_lds));
         hipLaunchKernelGGL((k_descend<false, true>), dim3((unsigned)((nq + 7) / 8)), dim3(64), heap_lds, s, ix->nv, sp,
-                           (const uint32_t *)nullptr, (uint32_t)nq, d_qvecs, qstride, d_qhdrs, d_nns, d_counts, d_overflow,
-                           (uint64_t *)nullptr, 0u, VisitSink{}, wave_descent);
-    else
+                           (const uint32_t *)nullptr, (uint32_t)nq, b.d_qvecs, qstride, b.d_qhdrs, b.d_nns, b.d_counts, b.d_overflow,
+                           (uint64_t *)nullptr, 0u, sink, a.wave_descent);
+    } else {
+        AH_TRY(lds_opt_in(reinterpret_cast<const void *>(k_descend<false>), ds->device, heap_lds));
         hipLaunchKernelGGL((k_descend<false>), dim3((unsigned)((nq + 7) / 8)), dim3(64), heap_lds, s, ix->nv, sp,
-                           (const uint32_t *)nullptr, (uint32_t)nq, d_qvecs, qstride, d_qhdrs, d_nns, d_counts, d_overflow,
-                           (uint64_t *)nullptr, 0u, VisitSink{}, wave_descent);
-    AH_HIP(hipMemcpyAsync(h_overflow, d_overflow, nq * 4, hipMemcpyDeviceToHost, s));
+                           (const uint32_t *)nullptr, (uint32_t)nq, b.d_qvecs, qstride, b.d_qhdrs, b.d_nns, b.d_counts, b.d_overflow,
+                           (uint64_t *)nullptr, 0u, sink, a.wave_descent);
+    }
+    return AH_OK;
+}
+
+// 2'. the leaf-tile path: the descent with its visits recorded ...
+static int launch_tile_descent(ChunkCtx &c) {
+    const ChunkPlan &plan = c.plan;
+    // a small submission places its visits with one block (k_units_small) and needs no counter per node
+    if (!plan.small_units) AH_HIP(hipMemsetAsync(c.b.d_leaf_count, 0, (size_t)c.ix->n_nodes * 4, c.stream()));
+    return launch_descent(c, VisitSink{c.b.d_visits, c.d_total(), plan.visit_cap, plan.small_units ? nullptr : c.b.d_leaf_count, c.b.d_err}, true);
+}
+
+// 3. ... the visits grouped by leaf into the tiles' work units, where the descent did not write them itself
+static int launch_units(ChunkCtx &c) {
+    const ChunkPlan &plan = c.plan;
+    const SearchBufs &b = c.b;
+    ah_index *ix = c.ix;
+    ah_dataset *ds = c.ds();
+    hipStream_t s = c.stream();
+    const size_t nq = c.a.nq;
+    if (plan.units == UnitBuilder::UnitsSmall) {
+        const QueriesH16 h16{b.d_qvecs, c.qstride(), ds->dims, ds->hpitch, b.d_q16, b.d_qstats};
+        hipLaunchKernelGGL(k_units_small, dim3(1u + (plan.screened ? (unsigned)nq : 0u)), dim3(256), 0, s, b.d_visits, c.d_total(), plan.visit_cap,
+                           b.d_sorted, b.d_units, c.d_n_units(), b.d_err, h16, b.d_items, (uint32_t)plan.items_cap);
+    } else if (plan.units == UnitBuilder::LeafScan) {
+        hipLaunchKernelGGL(k_leaf_scan_block, dim3(plan.n_leaf_sums), dim3(256), 0, s, b.d_leaf_count, ix->n_nodes, b.d_cursor, b.d_ustart,
+                           b.d_leaf_sums);
+        hipLaunchKernelGGL(k_leaf_scan_sums, dim3(1), dim3(256), 0, s, b.d_leaf_sums, plan.n_leaf_sums, c.d_n_units());
+        hipLaunchKernelGGL(k_leaf_scan_add, dim3(plan.n_leaf_sums), dim3(256), 0, s, b.d_leaf_count, ix->n_nodes, b.d_cursor, b.d_ustart,
+                           b.d_leaf_sums, b.d_units, b.d_err);
+        hipLaunchKernelGGL(k_visit_scatter, dim3(256), dim3(256), 0, s, b.d_visits, c.d_total(), plan.visit_cap, b.d_cursor, b.d_sorted);
+    }
+    return AH_OK;
+}
+
+// 4. ... and the distances of every unit's rows to the queries that visited its leaf
+static int launch_tiles(ChunkCtx &c) {
+    const ChunkPlan &plan = c.plan;
+    const SearchBufs &b = c.b;
+    const ScreenSearch &ss = c.ss;
+    ah_dataset *ds = c.ds();
+    const DataView dv = ds->view();
+    hipStream_t s = c.stream();
+    const size_t nq = c.a.nq, qstride = c.qstride();
+    const uint32_t nns_stride = c.a.nns_stride;
+    const dim3 grid(plan.tile_grid_x, plan.tile_grid_y);
+    uint32_t *const d_n_units = c.d_n_units();
+    uint32_t *tile_trace = c.multi_trace() ? &c.multi_trace()->tile_trace[0] : nullptr;
+    switch (plan.tile_launch) {
+    case TileLaunch::Tiles8And16:
+        // (the queries' int8 digits here, behind the descent: a small submission's query leaves are prepared BY its descent)
+        hipLaunchKernelGGL(k_queries_i8, dim3((unsigned)nq), dim3(64), 0, s, b.d_qvecs, qstride, ds->dims, ss);
+        hipLaunchKernelGGL(k_leaf_tiles8, grid, dim3(256), 0, s, dv, ss, b.d_nns, b.d_sorted, b.d_units, d_n_units, b.d_dist, nns_stride, b.d_err,
+                           plan.max_vis8);
+        hipLaunchKernelGGL((k_leaf_tiles16<false>), grid, dim3(256), 0, s, dv, ss, b.d_nns, b.d_sorted, b.d_units, d_n_units, b.d_dist, nns_stride,
+                           b.d_err, plan.max_vis8 + 1);
+        break;
+    case TileLaunch::Flat:
+        hipLaunchKernelGGL((k_leaf_tiles16<true>), grid, dim3(256), 0, s, dv, ss, b.d_nns, b.d_sorted, b.d_units, nq == 1 ? d_n_units : b.d_unit_counts,
+                           b.d_dist, nns_stride, b.d_err, 0u, c.ix->d_desc, 0u, tile_trace, 1u, (const uint32_t *)nullptr, plan.units_per_query);
+        break;
+    case TileLaunch::ItemList:
+        hipLaunchKernelGGL((k_leaf_tiles16<true>), grid, dim3(256), 0, s, dv, ss, b.d_nns, b.d_sorted, b.d_units, d_n_units, b.d_dist, nns_stride,
+                           b.d_err, 0u, c.ix->d_desc, 0u, tile_trace, 0u, b.d_items);
+        break;
+    case TileLaunch::Small2D:
+        hipLaunchKernelGGL((k_leaf_tiles16<true>), grid, dim3(256), 0, s, dv, ss, b.d_nns, b.d_sorted, b.d_units, d_n_units, b.d_dist, nns_stride,
+                           b.d_err, 0u, c.ix->d_desc, plan.visit_cap >= plan.tile_grid_x ? 1u : 0u, tile_trace);
+        break;
+    case TileLaunch::Big2D:
+        hipLaunchKernelGGL((k_leaf_tiles16<false>), grid, dim3(256), 0, s, dv, ss, b.d_nns, b.d_sorted, b.d_units, d_n_units, b.d_dist, nns_stride,
+                           b.d_err);
+        break;
+    default:
+        AH_TRY(with_tile_metric(ds->metric, [&](auto m) -> int {
+            constexpr int M = decltype(m)::value;
+            AH_TRY(lds_opt_in(reinterpret_cast<const void *>(k_leaf_tiles<M>), ds->device, 4 * kRingBytesPerWave));
+            hipLaunchKernelGGL((k_leaf_tiles<M>), grid, dim3(256), 4 * kRingBytesPerWave, s, dv, b.d_nns, b.d_sorted, b.d_units, d_n_units, b.d_qvecs,
+                               qstride, b.d_qhdrs, b.d_dist, nns_stride, b.d_err);
+            return AH_OK;
+        }));
+    }
+    return AH_OK;
+}
+
+// AH_DEBUG: how the visits of the sub-batch spread over the leaves (stderr)
+static int print_tile_visits(ChunkCtx &c) {
+    const uint32_t visit_cap = c.plan.visit_cap;
+    AH_HIP(hipStreamSynchronize(c.stream()));
+    uint32_t nv = 0, np = 0;
+    AH_HIP(hipMemcpy(&nv, c.d_total(), 4, hipMemcpyDeviceToHost));
+    AH_HIP(hipMemcpy(&np, c.d_n_units(), 4, hipMemcpyDeviceToHost));
+    std::vector<Visit> hv(std::min(nv, visit_cap));
+    AH_HIP(hipMemcpy(hv.data(), c.b.d_visits, hv.size() * sizeof(Visit), hipMemcpyDeviceToHost));
+    std::vector<uint32_t> per(c.ix->n_nodes, 0);
+    for (auto &v : hv) per[v.node]++;
+    uint32_t hist[9] = {0}, leaves = 0;
+    for (uint32_t n : per)
+        if (n) { leaves++; hist[std::min(n, 8u)]++; }
+    fprintf(stderr, "[ah] search tiles: %u visits, %u leaves, %u units; visits per leaf 1..8+: %u %u %u %u %u %u %u %u\n", nv,
+            leaves, np, hist[1], hist[2], hist[3], hist[4], hist[5], hist[6], hist[7], hist[8]);
+    return AH_OK;
+}
+
+// AH_SEARCH_MULTI_TRACE: where the blocks of query 0 spent their time (10 ns ticks -> us; stderr)
+static int print_multi_trace(ChunkCtx &c) {
+    MultiCtl *ctl = c.multi_trace();
+    const uint32_t multi_launched = c.plan.multi_blocks;
+    std::vector<uint32_t> tr((size_t)kMultiMaxBlocks * 8);
+    AH_HIP(hipMemcpy(tr.data(), &ctl->trace[0][0], tr.size() * 4, hipMemcpyDeviceToHost));
+    for (uint32_t b = 0; b < multi_launched; b++)
+        fprintf(stderr, "[ah] multi block %u: query in LDS %.2f us, descent left %.2f, counted %.2f%s\n", b, tr[b * 8] * 0.01, tr[b * 8 + 1] * 0.01,
+                tr[b * 8 + 2] * 0.01, tr[b * 8 + 5] > tr[b * 8 + 2] ? "  <- last" : "");
+    for (uint32_t b = 0; b < multi_launched; b++)
+        if (tr[b * 8 + 5] > tr[b * 8 + 2])
+            fprintf(stderr, "[ah]   (stale unless marked) last block %u: lists gathered %.2f us, ordered %.2f, ids copied %.2f (%u leaves known, %u taken)\n", b,
+                    tr[b * 8 + 3] * 0.01, tr[b * 8 + 4] * 0.01, tr[b * 8 + 5] * 0.01, tr[b * 8 + 6], tr[b * 8 + 7]);
+    uint32_t st[16];
+    AH_HIP(hipMemcpy(st, &ctl->sel_trace[0], sizeof(st), hipMemcpyDeviceToHost));
+    uint32_t tt[8];
+    AH_HIP(hipMemcpy(tt, &ctl->tile_trace[0], sizeof(tt), hipMemcpyDeviceToHost));
+    AH_HIP(hipMemset(&ctl->tile_trace[0], 0, sizeof(tt)));
+    fprintf(stderr, "[ah] tiles (latest block since ITS start): unit + visit known %.2f us, slab done %.2f us\n", tt[0] * 0.01, tt[1] * 0.01);
+    fprintf(stderr, "[ah] selection: leaf + tables in LDS %.2f us, candidates in registers %.2f, duplicates flagged %.2f, key range %.2f, "
+            "k-th bin %.2f, survivors listed %.2f (%u), f32 distances %.2f, ranked + written %.2f, status written %.2f\n", st[0] * 0.01,
+            st[1] * 0.01, st[2] * 0.01, st[3] * 0.01, st[4] * 0.01, st[5] * 0.01, st[9], st[6] * 0.01, st[7] * 0.01, st[8] * 0.01);
+    return AH_OK;
+}
+
+// 5. nns.dedup() of the candidates, the screen's f32 pass, the selection, the one read-back, the wait.
+// (after the tiles: they read the leaves' ids from the candidate buffers)
+static int launch_select_and_wait(ChunkCtx &c, hipError_t &launch_err) {
+    const ChunkPlan &plan = c.plan;
+    const SearchBufs &b = c.b;
+    const ScreenSearch &ss = c.ss;
+    const SearchParams &sp = c.sp;
+    ah_dataset *ds = c.ds();
+    const DataView dv = ds->view();
+    hipStream_t s = c.stream();
+    const size_t nq = c.a.nq, k = c.a.count, qstride = c.qstride();
+    const uint32_t nns_stride = c.a.nns_stride, bitmap_words = plan.bitmap_words, max_id = c.shape.max_id;
+    const bool fused_flag = plan.fused_flag;
+    uint32_t *const h_err = b.h_err;
+    if (plan.flagger == Flagger::Fused) {
+        *h_err = 0xFFFFFFFFu;  // (overwritten by the selection kernel's last block: a launch that never ran reads as a failure)
+    } else if (plan.flagger == Flagger::Bitmap) {
+        const size_t sh = (size_t)bitmap_words * 4;
+        AH_TRY(lds_opt_in(reinterpret_cast<const void *>(k_flag_duplicates), ds->device, sh));
+        hipLaunchKernelGGL(k_flag_duplicates, dim3((unsigned)nq), dim3(1024), sh, s, b.d_nns, nns_stride, b.d_counts, bitmap_words,
+                           max_id + 1, b.d_unique, b.d_err);
+    } else {
+        AH_TRY(lds_opt_in(reinterpret_cast<const void *>(k_flag_duplicates_hash), ds->device, kHashSlots * 4));
+        hipLaunchKernelGGL(k_flag_duplicates_hash, dim3((unsigned)nq), dim3(1024), kHashSlots * 4, s, b.d_nns, nns_stride, b.d_counts,
+                           b.d_unique, b.d_err);
+    }
+    uint32_t *sel_trace = c.multi_trace() ? &c.multi_trace()->sel_trace[0] : nullptr;
+    if (plan.screened) AH_TRY(launch_screen_verify(ds, ss, b.d_nns, b.d_dist, nns_stride, b.d_counts, nullptr, (uint32_t)nq, b.d_qvecs, qstride, b.d_qhdrs, s));
+    if (fused_flag)
+        AH_TRY(with_screen_metric(ds->metric, [&](auto m) -> int {
+            constexpr int M = decltype(m)::value;
+            AH_TRY(lds_opt_in(reinterpret_cast<const void *>(k_search_select_screened<M, true>), ds->device, plan.fused_lds, 0));
+            hipLaunchKernelGGL((k_search_select_screened<M, true>), dim3((unsigned)nq), dim3(1024), plan.fused_lds, s, dv, ss, b.d_nns, b.d_dist,
+                               nns_stride, b.d_counts, b.d_unique, (uint32_t)k, b.d_qvecs, qstride, b.d_qhdrs, b.h_oi, b.h_od, b.d_err,
+                               (const RerankSeg *)nullptr, bitmap_words, max_id + 1, b.h_counts, h_err, sel_trace, sp.count_of);
+            return AH_OK;
+        }));
+    else if (plan.screened)
+        AH_TRY(with_screen_metric(ds->metric, [&](auto m) -> int {
+            constexpr int M = decltype(m)::value;
+            AH_TRY(lds_opt_in(reinterpret_cast<const void *>(k_search_select_screened<M>), ds->device, plan.sel_lds, kSelectLdsFloor));
+            hipLaunchKernelGGL((k_search_select_screened<M>), dim3((unsigned)nq), dim3(1024), plan.sel_lds, s, dv, ss, b.d_nns, b.d_dist,
+                               nns_stride, b.d_counts, b.d_unique, (uint32_t)k, b.d_qvecs, qstride, b.d_qhdrs, b.d_oi, b.d_od, b.d_err,
+                               (const RerankSeg *)nullptr, 0u, 0u, (uint32_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr, sp.count_of);
+            return AH_OK;
+        }));
+    else
+        hipLaunchKernelGGL(k_search_select, dim3((unsigned)nq), dim3(kSelectThreads), 0, s, dv, b.d_nns, b.d_dist, nns_stride, b.d_counts,
+                           b.d_unique, (uint32_t)k, b.d_oi, b.d_od, b.d_err, sp.count_of);
+    // a launch the runtime rejected (dynamic LDS beyond the limit, another architecture) would leave *err = 0 over
+    // uninitialised results: such a submission takes the sorted path as well
+    launch_err = hipGetLastError();
+    // ids, distances, status words and counts: one copy (the four buffers lie back to back on both sides: search_plan.h)
+    // (fused_flag: the selection kernel wrote ids, distances, counts and status into the pinned buffers itself)
+    if (!fused_flag) AH_HIP(hipMemcpyAsync(b.h_oi, b.d_oi, 2 * pad256(nq * k * 4) + pad256(SS_WORDS * 4) + nq * 4, hipMemcpyDeviceToHost, s));
+    // fused_flag: the selection's last block writes the status into pinned memory as the last thing the submission does (word 0
+    // after everything else, system-scope release).  Polling that word returns as soon as it lands; the runtime's own wait adds
+    // the end-of-kernel bookkeeping and its wake-up (AH_SEARCH_SPIN_WAIT=0: hipStreamSynchronize as before; it is also what
+    // happens after 2 ms without an answer — a launch that never ran).  Everything queued later runs behind this submission in
+    // stream order, so its scratch is safe to reuse.
+    bool answered = false;
+    if (fused_flag && launch_err == hipSuccess && c.kn.spin_wait) {
+        const auto t_spin = std::chrono::steady_clock::now();
+        for (uint32_t spin = 0;; spin++) {
+            if (__atomic_load_n(h_err, __ATOMIC_ACQUIRE) != 0xFFFFFFFFu) {
+                answered = true;
+                break;
+            }
+            __builtin_ia32_pause();
+            if ((spin & 1023u) == 1023u && std::chrono::steady_clock::now() - t_spin > std::chrono::milliseconds(2)) break;
+        }
+    }
+    if (!answered) AH_HIP(hipStreamSynchronize(s));
+    return AH_OK;
+}
+
+// 6. what the tile pass came to: the results are out, the sub-batch runs once more with the binary16 rows first, or it is
+// redone the long way
+enum class TileOutcome { Done, RetryWithout8, SortedPath };
+static int finish_tiles(ChunkCtx &c, hipError_t launch_err, TileOutcome &outcome) {
+    const ChunkArgs &a = c.a;
+    const ChunkPlan &plan = c.plan;
+    const SearchBufs &b = c.b;
+    ChunkStats &cs = c.cs;
+    ah_index *ix = c.ix;
+    hipStream_t s = c.stream();
+    const size_t nq = a.nq, k = a.count;
+    const uint32_t *const h_err = b.h_err;
+    AH_REQUIRE((*h_err & 1u) == 0 || *h_err == 0xFFFFFFFFu, AH_ERR_MISSING_ITEM, "a descendant id does not exist in the dataset");
+    if ((*h_err & ~1u) == 0 && launch_err == hipSuccess) {
+        if (plan.fused_flag) c.ctx->clean_status = b.d_err;  // (its selection kernel ran to its end and wiped the block behind itself)
+        for (size_t q = 0; q < nq; q++) a.out_counts[q] = (uint32_t)std::min<size_t>(c.count_of(q), b.h_counts[q]);
+        memcpy(a.out_ids, b.h_oi, nq * k * 4);
+        memcpy(a.out_dists, b.h_od, nq * k * 4);
+        cs.device_words(h_err);
+        cs.s.rerank_tiles = nq;
+        cs.s.rerank_screened8 = plan.screened8 ? h_err[SS_SCREENED] : 0;
+        if (plan.screened8) (void)screen8_window_note(ix->search8_seen, ix->search8_fails, false);
+        (plan.bitmap_fits ? cs.s.dedup_flag_bitmap : cs.s.dedup_flag_hash) = nq;
+        cs.commit(ix);
+        outcome = TileOutcome::Done;
+        return AH_OK;
+    }
+    if (plan.screened8 && launch_err == hipSuccess && (*h_err & ~1u) == 8u) {
+        // more survivors than the selection holds on the int8 stage (candidates closer together than its error bound): the
+        // same sub-batch once more with the binary16 rows first — not the long way
+        if (screen8_window_note(ix->search8_seen, ix->search8_fails, true)) ix->search8_off.store(true, std::memory_order_relaxed);
+        {
+            std::lock_guard<std::mutex> lk(ix->stats_mu);
+            ix->stats.screen8_retried_chunks += 1;
+        }
+        outcome = TileOutcome::RetryWithout8;
+        return AH_OK;
+    }
+    // a case the tiles do not reproduce (bits 2..5 of *err, see k_search_select / VisitSink): redo it the long way
+    cs.s.fallback_chunks = 1;
+    cs.s.fallback_non_finite = (*h_err & 4u) ? 1 : 0;
+    cs.s.fallback_select = (*h_err & 8u) ? 1 : 0;
+    cs.s.fallback_queue = (*h_err & 16u) ? 1 : 0;
+    cs.s.fallback_visits = (*h_err & 32u) ? 1 : 0;
+    cs.s.fallback_launch = launch_err != hipSuccess ? 1 : 0;
+    AH_HIP(hipMemsetAsync(b.d_err, 0, SS_WORDS * 4, s));
+    // (the block descent was the only writer of the query leaves under fuse_prepare: a launch the runtime rejected has left them
+    // unprepared — the passes below read them; preparing them again when it did run changes nothing)
+    if (a.queries && plan.fuse_prepare)
+        AH_TRY(launch_prepare_queries_only(c.ds()->view(), b.h_q, (uint32_t)nq, b.d_qvecs, c.qstride(), b.d_qhdrs, s));
+    outcome = TileOutcome::SortedPath;
+    return AH_OK;
+}
+
+// 7. the sorted path: descent -> sort + dedup -> re-rank + top-k (batch.hip) -> read-back, with host round trips in between
+static int run_sorted_path(ChunkCtx &c) {
+    const ChunkArgs &a = c.a;
+    const ChunkPlan &plan = c.plan;
+    const SearchBufs &b = c.b;
+    const SearchParams &sp = c.sp;
+    ChunkStats &cs = c.cs;
+    ah_index *ix = c.ix;
+    ah_dataset *ds = c.ds();
+    const DataView dv = ds->view();
+    hipStream_t s = c.stream();
+    const size_t nq = a.nq, k = a.count, qstride = c.qstride();
+    const uint32_t nns_stride = a.nns_stride, bitmap_words = plan.bitmap_words, heap_cap = plan.heap_cap;
+    AH_TRY(launch_descent(c, VisitSink{}, false));
+    AH_HIP(hipMemcpyAsync(b.h_overflow, b.d_overflow, nq * 4, hipMemcpyDeviceToHost, s));
     AH_HIP(hipStreamSynchronize(s));
     uint32_t n_over = 0;
     for (size_t q = 0; q < nq; q++)
-        if (h_overflow[q]) h_list[n_over++] = (uint32_t)q;
+        if (b.h_overflow[q]) b.h_list[n_over++] = (uint32_t)q;
     if (n_over) {  // 2b. the rare big queues: re-run with the queue in global memory (hard capacity bound)
         DevMem heap;
         AH_HIP(dev_malloc(&heap.p, (size_t)n_over * heap_cap * 8));
-        AH_HIP(hipMemcpyAsync(d_list, h_list, n_over * 4, hipMemcpyHostToDevice, s));
-        if (mixed)
-            hipLaunchKernelGGL((k_descend<true, true>), dim3((n_over + 7) / 8), dim3(64), 0, s, ix->nv, sp, (const uint32_t *)d_list,
-                               n_over, d_qvecs, qstride, d_qhdrs, d_nns, d_counts, d_overflow, heap.as<uint64_t>(), heap_cap,
+        AH_HIP(hipMemcpyAsync(b.d_list, b.h_list, n_over * 4, hipMemcpyHostToDevice, s));
+        if (a.mixed)
+            hipLaunchKernelGGL((k_descend<true, true>), dim3((n_over + 7) / 8), dim3(64), 0, s, ix->nv, sp, (const uint32_t *)b.d_list,
+                               n_over, b.d_qvecs, qstride, b.d_qhdrs, b.d_nns, b.d_counts, b.d_overflow, heap.as<uint64_t>(), heap_cap,
                                VisitSink{}, false);
         else
-            hipLaunchKernelGGL((k_descend<true>), dim3((n_over + 7) / 8), dim3(64), 0, s, ix->nv, sp, (const uint32_t *)d_list,
-                               n_over, d_qvecs, qstride, d_qhdrs, d_nns, d_counts, d_overflow, heap.as<uint64_t>(), heap_cap,
+            hipLaunchKernelGGL((k_descend<true>), dim3((n_over + 7) / 8), dim3(64), 0, s, ix->nv, sp, (const uint32_t *)b.d_list,
+                               n_over, b.d_qvecs, qstride, b.d_qhdrs, b.d_nns, b.d_counts, b.d_overflow, heap.as<uint64_t>(), heap_cap,
                                VisitSink{}, false);
         AH_HIP(hipStreamSynchronize(s));
     }
     // 3. sort + dedup
     uint32_t max_nn = 0;
-    const bool by_bitmap = bitmap_fits;
-    if (!by_bitmap) {
-        AH_HIP(hipMemcpyAsync(h_counts, d_counts, nq * 4, hipMemcpyDeviceToHost, s));
+    if (!plan.bitmap_fits) {
+        AH_HIP(hipMemcpyAsync(b.h_counts, b.d_counts, nq * 4, hipMemcpyDeviceToHost, s));
         AH_HIP(hipStreamSynchronize(s));
-        for (size_t q = 0; q < nq; q++) max_nn = std::max(max_nn, h_counts[q]);
+        for (size_t q = 0; q < nq; q++) max_nn = std::max(max_nn, b.h_counts[q]);
     }
-    if (by_bitmap) {
+    uint32_t np2 = 2;
+    while (np2 < max_nn) np2 <<= 1;
+    switch (sorted_dedup_kind(plan.bitmap_fits, max_nn)) {
+    case SortedDedup::Bitmap: {
         const size_t sh = (size_t)bitmap_words * 4;
-        if (sh > 48 * 1024)
-            AH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_dedup_bitmap_lds),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
-        hipLaunchKernelGGL(k_dedup_bitmap_lds, dim3((unsigned)nq), dim3(1024), sh, s, d_nns, nns_stride, d_counts,
-                           bitmap_words, max_id + 1, d_err);
+        AH_TRY(lds_opt_in(reinterpret_cast<const void *>(k_dedup_bitmap_lds), ds->device, sh));
+        hipLaunchKernelGGL(k_dedup_bitmap_lds, dim3((unsigned)nq), dim3(1024), sh, s, b.d_nns, nns_stride, b.d_counts,
+                           bitmap_words, c.shape.max_id + 1, b.d_err);
         cs.s.dedup_sorted_bitmap = nq;
-    } else if (max_nn <= kSortLds) {
+        break;
+    }
+    case SortedDedup::SortLds: {
         cs.s.dedup_sort_lds = nq;
-        uint32_t np2 = 2;
-        while (np2 < max_nn) np2 <<= 1;
         const size_t sh = (size_t)np2 * 4;
-        if (sh > 48 * 1024)
-            AH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_sort_dedup_lds),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
-        hipLaunchKernelGGL(k_sort_dedup_lds, dim3((unsigned)nq), dim3(256), sh, s, d_nns, nns_stride, d_counts);
-    } else {
-        uint32_t np2 = 2;
-        while (np2 < max_nn) np2 <<= 1;
+        AH_TRY(lds_opt_in(reinterpret_cast<const void *>(k_sort_dedup_lds), ds->device, sh));
+        hipLaunchKernelGGL(k_sort_dedup_lds, dim3((unsigned)nq), dim3(256), sh, s, b.d_nns, nns_stride, b.d_counts);
+        break;
+    }
+    case SortedDedup::SortGlobal:
         cs.s.dedup_sort_global = nq;
         // the stride was sized to the next power of two by the caller when this path is possible
         AH_REQUIRE(np2 <= nns_stride, AH_ERR_DEVICE, "internal: candidate stride %u < %u", nns_stride, np2);
-        hipLaunchKernelGGL(k_pad_ids, dim3((np2 + 255) / 256, (unsigned)nq), dim3(256), 0, s, d_nns, nns_stride, d_counts, np2);
+        hipLaunchKernelGGL(k_pad_ids, dim3((np2 + 255) / 256, (unsigned)nq), dim3(256), 0, s, b.d_nns, nns_stride, b.d_counts, np2);
         for (uint32_t size = 2; size <= np2; size <<= 1)
             for (uint32_t str = size >> 1; str > 0; str >>= 1)
-                hipLaunchKernelGGL(k_bitonic_ids, dim3(((np2 >> 1) + 255) / 256, (unsigned)nq), dim3(256), 0, s, d_nns,
+                hipLaunchKernelGGL(k_bitonic_ids, dim3(((np2 >> 1) + 255) / 256, (unsigned)nq), dim3(256), 0, s, b.d_nns,
                                    nns_stride, np2, size, str);
-        hipLaunchKernelGGL(k_dedup_sorted, dim3((unsigned)nq), dim3(256), 0, s, d_nns, nns_stride, d_counts);
+        hipLaunchKernelGGL(k_dedup_sorted, dim3((unsigned)nq), dim3(256), 0, s, b.d_nns, nns_stride, b.d_counts);
+        break;
     }
-    AH_HIP(hipMemcpyAsync(h_counts, d_counts, nq * 4, hipMemcpyDeviceToHost, s));
+    AH_HIP(hipMemcpyAsync(b.h_counts, b.d_counts, nq * 4, hipMemcpyDeviceToHost, s));
     AH_HIP(hipStreamSynchronize(s));
     // 4. re-rank + top-k + normalized distances (batch.hip), candidates already resident
     uint32_t n_tiles = 0, max_n = 0, max_rounds = 0;
     uint64_t n_candidates = 0;
-    const uint32_t tc = batch_tile_candidates();
+    const uint32_t tc = c.shape.tile_candidates;
     for (size_t q = 0; q < nq; q++) {
-        const uint32_t n = h_counts[q];
+        const uint32_t n = b.h_counts[q];
         n_candidates += n;
-        h_segs[q] = RerankSeg{(uint64_t)q * nns_stride, n, (uint32_t)std::min<size_t>(count_of(q), n)};
-        out_counts[q] = h_segs[q].k;
+        b.h_segs[q] = RerankSeg{(uint64_t)q * nns_stride, n, (uint32_t)std::min<size_t>(c.count_of(q), n)};
+        a.out_counts[q] = b.h_segs[q].k;
         max_n = std::max(max_n, n);
-        if (big_k) continue;
-        max_rounds = std::max(max_rounds, batch_rounds(n, h_segs[q].k));
-        for (uint32_t f = 0; f < n; f += tc) h_tiles[n_tiles++] = RerankTile{(uint32_t)q, f};
+        if (plan.big_k) continue;
+        max_rounds = std::max(max_rounds, batch_rounds(n, b.h_segs[q].k));
+        for (uint32_t f = 0; f < n; f += tc) b.h_tiles[n_tiles++] = RerankTile{(uint32_t)q, f};
     }
-    if (big_k) {
+    if (plan.big_k) {
         // d_ka (2 x nq x kstride x 8 bytes >= the single-query scratch) is free: the batch path is not used
-        AH_HIP(hipMemsetAsync(d_oi, 0xFF, nq * k * 4, s));  // padding: id 0xFFFFFFFF / NaN
-        AH_HIP(hipMemsetAsync(d_od, 0xFF, nq * k * 4, s));
+        AH_HIP(hipMemsetAsync(b.d_oi, 0xFF, nq * k * 4, s));  // padding: id 0xFFFFFFFF / NaN
+        AH_HIP(hipMemsetAsync(b.d_od, 0xFF, nq * k * 4, s));
         for (size_t q = 0; q < nq; q++) {
-            const uint32_t n = h_counts[q], kk = h_segs[q].k;
+            const uint32_t n = b.h_counts[q], kk = b.h_segs[q].k;
             if (kk == 0) continue;
-            const uint32_t *ids_q = d_nns + q * (size_t)nns_stride;
-            float *dist_q = d_dist + q * (size_t)nns_stride;
-            AH_TRY(launch_distances(dv, d_qvecs + q * qstride, d_qhdrs + 2 * q, ids_q, n, dist_q, d_err, s));
-            AH_TRY(launch_topk(dv, dist_q, ids_q, n, kk, d_ka, d_oi + q * k, d_od + q * k, s));
+            const uint32_t *ids_q = b.d_nns + q * (size_t)nns_stride;
+            float *dist_q = b.d_dist + q * (size_t)nns_stride;
+            AH_TRY(launch_distances(dv, b.d_qvecs + q * qstride, b.d_qhdrs + 2 * q, ids_q, n, dist_q, b.d_err, s));
+            AH_TRY(launch_topk(dv, dist_q, ids_q, n, kk, b.d_ka, b.d_oi + q * k, b.d_od + q * k, s));
         }
     } else {
-        AH_HIP(hipMemcpyAsync(d_segs, h_segs, nq * sizeof(RerankSeg), hipMemcpyHostToDevice, s));
-        if (n_tiles) AH_HIP(hipMemcpyAsync(d_tiles, h_tiles, (size_t)n_tiles * sizeof(RerankTile), hipMemcpyHostToDevice, s));
-        RerankBufs b{};  // (no screen here: its scratch stays null)
-        b.n_queries = (uint32_t)nq, b.d_qvecs = d_qvecs, b.qstride = qstride, b.d_qhdrs = d_qhdrs, b.d_segs = d_segs, b.d_tiles = d_tiles;
-        b.n_tiles = n_tiles, b.d_ids = d_nns, b.d_dist = d_dist, b.d_keys_a = d_ka, b.d_keys_b = d_kb, b.kstride = kstride;
-        b.d_out_ids = d_oi, b.d_out_dist = d_od, b.d_err = d_err, b.d_inv_counters = d_inv;
-        AH_TRY(launch_rerank_batch_prepared(dv, b, max_n, (uint32_t)k, max_rounds, n_candidates, s));
+        AH_HIP(hipMemcpyAsync(b.d_segs, b.h_segs, nq * sizeof(RerankSeg), hipMemcpyHostToDevice, s));
+        if (n_tiles) AH_HIP(hipMemcpyAsync(b.d_tiles, b.h_tiles, (size_t)n_tiles * sizeof(RerankTile), hipMemcpyHostToDevice, s));
+        RerankBufs rb{};  // (no screen here: its scratch stays null)
+        rb.n_queries = (uint32_t)nq, rb.d_qvecs = b.d_qvecs, rb.qstride = qstride, rb.d_qhdrs = b.d_qhdrs, rb.d_segs = b.d_segs, rb.d_tiles = b.d_tiles;
+        rb.n_tiles = n_tiles, rb.d_ids = b.d_nns, rb.d_dist = b.d_dist, rb.d_keys_a = b.d_ka, rb.d_keys_b = b.d_kb, rb.kstride = plan.kstride;
+        rb.d_out_ids = b.d_oi, rb.d_out_dist = b.d_od, rb.d_err = b.d_err, rb.d_inv_counters = b.d_inv;
+        AH_TRY(launch_rerank_batch_prepared(dv, rb, max_n, (uint32_t)k, max_rounds, n_candidates, s));
     }
-    AH_HIP(hipMemcpyAsync(h_oi, d_oi, nq * k * 4, hipMemcpyDeviceToHost, s));
-    AH_HIP(hipMemcpyAsync(h_od, d_od, nq * k * 4, hipMemcpyDeviceToHost, s));
+    AH_HIP(hipMemcpyAsync(b.h_oi, b.d_oi, nq * k * 4, hipMemcpyDeviceToHost, s));
+    AH_HIP(hipMemcpyAsync(b.h_od, b.d_od, nq * k * 4, hipMemcpyDeviceToHost, s));
     AH_HIP(hipGetLastError());
-    AH_HIP(hipMemcpyAsync(h_err, d_err, SS_WORDS * 4, hipMemcpyDeviceToHost, s));
+    AH_HIP(hipMemcpyAsync(b.h_err, b.d_err, SS_WORDS * 4, hipMemcpyDeviceToHost, s));
     AH_HIP(hipStreamSynchronize(s));
-    AH_REQUIRE((*h_err & 1u) == 0, AH_ERR_MISSING_ITEM, "a descendant id does not exist in the dataset");
-    memcpy(out_ids, h_oi, nq * k * 4);
-    memcpy(out_dists, h_od, nq * k * 4);
-    cs.device_words(h_err);
+    AH_REQUIRE((*b.h_err & 1u) == 0, AH_ERR_MISSING_ITEM, "a descendant id does not exist in the dataset");
+    memcpy(a.out_ids, b.h_oi, nq * k * 4);
+    memcpy(a.out_dists, b.h_od, nq * k * 4);
+    cs.device_words(b.h_err);
     cs.s.rerank_sorted = nq;
     cs.commit(ix);
     return AH_OK;
+}
+
+// One sub-batch of ah_search_batch / _filters / _params: plan it, lay out its scratch, run the stages.
+static int search_chunk(ah_index *ix, Context *ctx, const ChunkArgs &a) {
+    const ChunkShape shape = chunk_shape(ix, a);
+    const ChunkPlan plan = plan_chunk(shape, *a.knobs);
+    // device and pinned scratch (one carve each for the whole chunk)
+    SearchBufs b{};
+    Carver dev_size(nullptr), pin_size(nullptr);
+    search_device_layout(dev_size, shape, plan, b);
+    search_pinned_layout(pin_size, shape, plan, b);
+    void *const clean_status = ctx->clean_status;  // (ensure_device forgets it: see Context)
+    AH_TRY(ctx->ensure_device(dev_size.off + kSearchDeviceSlack));
+    AH_TRY(ctx->ensure_pinned(pin_size.off + kSearchPinnedSlack));
+    Carver dev(ctx->d_scratch), pin(ctx->h_pinned);
+    search_device_layout(dev, shape, plan, b);
+    search_pinned_layout(pin, shape, plan, b);
+    ScreenSearch ss{};
+    if (plan.screened) {
+        ss = screen_of_dataset(ix->ds, plan.screened8);
+        ss.aux = b.d_aux, ss.q16 = b.d_q16, ss.qstats = b.d_qstats;
+        ss.q8 = b.d_q8, ss.q8stats = b.d_q8stats, ss.aux8 = b.d_aux8;
+    }
+    ChunkStats cs;
+    cs.s.chunks = 1;
+    cs.s.queries = a.nq;
+    if (a.d_filter_bits) cs.s.filtered_queries = a.nq;
+    if (a.mixed) cs.s.filtered_queries = a.mixed->n_filtered;
+    SearchParams sp{};
+    ChunkCtx c{ix, ctx, a, *a.knobs, shape, plan, b, sp, ss, cs};
+    AH_TRY(stage_queries(c, clean_status));
+    if (plan.tiles) {  // no host round trip before the results
+        AH_TRY(launch_tile_descent(c));
+        AH_TRY(launch_units(c));
+        AH_TRY(launch_tiles(c));
+        if (c.kn.debug) AH_TRY(print_tile_visits(c));
+        hipError_t launch_err = hipSuccess;
+        AH_TRY(launch_select_and_wait(c, launch_err));
+        if (c.multi_trace()) AH_TRY(print_multi_trace(c));
+        TileOutcome outcome;
+        AH_TRY(finish_tiles(c, launch_err, outcome));
+        if (outcome == TileOutcome::Done) return AH_OK;
+        if (outcome == TileOutcome::RetryWithout8) {  // (a new plan for the whole sub-batch)
+            ChunkArgs again = a;
+            again.allow8 = false;
+            return search_chunk(ix, ctx, again);
+        }
+    }
+    return run_sorted_path(c);
 }
 
 // Route `n` items (already present in the index's dataset) down every tree of the index.
@@ -5227,7 +5221,8 @@ int ah_search_batch(ah_index *ix, const float *queries, const uint32_t *query_it
     // ONCE per submission by a pass over all Descendants ids (4 GB at 10M x 100 trees): a small submission on a big forest
     // is cheaper by the sequential descent, which looks only at the leaves it pops.
     // (the wave / block descents keep the query leaf in LDS: up to 32 KiB of it, i.e. 8192 f32 dimensions)
-    bool wave_descent = tun(TUN_SEARCH_WAVE) != 0 && (!d_bits || filter_share >= 0.05) && ((ds->row_bytes() + 255) & ~(size_t)255) <= (32u << 10);
+    const SearchKnobs knobs = search_knobs();
+    bool wave_descent = wave_descent_wanted(knobs, pad256(ds->row_bytes()), d_bits != nullptr, filter_share);
     uint64_t leaf_kept_passes = 0;
     if (wave_descent && d_bits) {
         if (nq >= 16 || ix->desc_len <= (32ull << 20)) {
@@ -5253,9 +5248,9 @@ int ah_search_batch(ah_index *ix, const float *queries, const uint32_t *query_it
         int st = AH_OK;
         for (size_t q0 = qa; q0 < qb && st == AH_OK; q0 += chunk) {
             const size_t cn = std::min(chunk, qb - q0);
-            st = search_chunk(ix, c, queries ? queries + q0 * (size_t)ds->dims : nullptr, query_items ? rows.data() + q0 : nullptr, cn, count,
-                              (uint32_t)sk_eff, (uint32_t)stride, d_bits, bits_len, filter_share, wave_descent, d_leaf_kept,
-                              out_ids + q0 * count, out_distances + q0 * count, out_counts + q0);
+            st = search_chunk(ix, c, ChunkArgs{&knobs, queries ? queries + q0 * (size_t)ds->dims : nullptr, query_items ? rows.data() + q0 : nullptr, cn,
+                                               count, (uint32_t)sk_eff, (uint32_t)stride, d_bits, bits_len, filter_share, wave_descent, d_leaf_kept,
+                                               out_ids + q0 * count, out_distances + q0 * count, out_counts + q0});
         }
         return st;
     };
@@ -6103,7 +6098,8 @@ static int search_batch_cut(ah_index *ix, const float *queries, const uint32_t *
     if (!lease) lease.emplace(ds);
     AH_REQUIRE(lease->c, AH_ERR_DEVICE, "cannot create a HIP stream");
     Context *ctx = lease->c;
-    const bool wave_ok = tun(TUN_SEARCH_WAVE) != 0 && ((ds->row_bytes() + 255) & ~(size_t)255) <= (32u << 10);
+    const SearchKnobs knobs = search_knobs();
+    const size_t padded_row = pad256(ds->row_bytes());
     auto share_of = [&](uint32_t slot) { return (double)filters[slot]->stored / (double)ds->n; };  // exact: ah_filter_info
     std::vector<FilterSlot> table;
     if (any_mixed) {  // the filters of the call, for the descents of the mixed sub-batches
@@ -6143,8 +6139,9 @@ static int search_batch_cut(ah_index *ix, const float *queries, const uint32_t *
             const uint32_t slot = pslot[sb.a];
             const ah_filter *f = slot == AH_NO_FILTER ? nullptr : filters[slot];
             const double share = f ? share_of(slot) : 1.0;
-            st = search_chunk(ix, ctx, q_at, r_at, cn, sb.count, sb.sk_eff, sb.stride, f ? f->d_bits : nullptr, f ? f->len_bits : 0, share,
-                              wave_ok && (!f || share >= 0.05), f ? f->d_leaf_kept : nullptr, oi_at, od_at, oc + sb.a, true, nullptr, varied);
+            st = search_chunk(ix, ctx, ChunkArgs{&knobs, q_at, r_at, cn, sb.count, sb.sk_eff, sb.stride, f ? f->d_bits : nullptr, f ? f->len_bits : 0, share,
+                                                 wave_descent_wanted(knobs, padded_row, f != nullptr, share), f ? f->d_leaf_kept : nullptr, oi_at, od_at,
+                                                 oc + sb.a, nullptr, varied});
             fs.uniform_batches++;
             fs.uniform_queries += cn;
         } else {
@@ -6155,8 +6152,8 @@ static int search_batch_cut(ah_index *ix, const float *queries, const uint32_t *
                     mf.min_share = std::min(mf.min_share, share_of(pslot[i]));
                     mf.n_filtered++;
                 }
-            st = search_chunk(ix, ctx, q_at, r_at, cn, sb.count, sb.sk_eff, sb.stride, nullptr, 0, mf.min_share,
-                              wave_ok && mf.min_share >= 0.05, nullptr, oi_at, od_at, oc + sb.a, true, &mf, varied);
+            st = search_chunk(ix, ctx, ChunkArgs{&knobs, q_at, r_at, cn, sb.count, sb.sk_eff, sb.stride, nullptr, 0, mf.min_share,
+                                                 wave_descent_wanted(knobs, padded_row, true, mf.min_share), nullptr, oi_at, od_at, oc + sb.a, &mf, varied});
             fs.mixed_batches++;
             fs.mixed_queries += cn;
         }
