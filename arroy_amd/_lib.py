@@ -218,6 +218,10 @@ class AhNodeBatch(C.Structure):
 NODE_BATCH_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(AhNodeBatch))
 
 
+class AhEncodeOptions(C.Structure):
+    _fields_ = [("node_id_base", C.c_uint32), ("flags", C.c_uint32)]
+
+
 # name -> (restype, argtypes): exactly the declarations of include/arroy_hip.h
 _VP, _U32P, _F32P, _U64P = C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p
 SIGNATURES = {
@@ -348,6 +352,10 @@ SIGNATURES = {
     "ah_group_update_vectors": (C.c_int, [_VP, _U32P, C.c_size_t, _U32P, _F32P, C.c_size_t]),
     "ah_group_update_records": (C.c_int, [_VP, _U32P, C.c_size_t, _U32P, _VP, C.c_size_t, C.c_size_t]),
     "ah_debug_update_paths": (C.c_int, [_VP, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    # encoded node stream
+    "ah_build_forest_stream_encoded": (C.c_int, [_VP, C.POINTER(AhBuildOptions), C.POINTER(AhEncodeOptions), NODE_BATCH_FN, _VP, _U32P,
+                                                 C.POINTER(AhBuildStats)]),
+    "ah_encode_descendants": (C.c_int, [_VP, _U32P, _U64P, C.c_size_t, _VP, C.c_uint64, _U64P]),
 }
 
 _lib = None

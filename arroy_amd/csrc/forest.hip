@@ -34,6 +34,8 @@
 #include "split_device.h"
 #include "screen_device.h"
 #include "level_plan.h"
+#include "encode.h"
+#include "node_codec.h"
 
 namespace ah {
 
@@ -2191,6 +2193,31 @@ struct StreamJob {
     ah_node_batch head{};                // kind, level, record geometry
     StreamNodeList nodes;                // payload_offset: byte offset from the job's device address, ascending, contiguous
     uint64_t fixed_len = 0;              // bytes of one payload (split planes), or 0: count * 4 (item ids)
+    // ah_build_forest_stream_encoded: the payloads above are the SOURCE of an encode on the worker's stream; the sink gets
+    // NodeCodec values of explicit lengths (Readback::deliver_encoded)
+    bool encoded = false;
+    uint32_t header_size = 0, vector_size = 0;
+};
+// Device side of an encoded streaming build, obtained once per batch of trees (the worker never allocates or frees device
+// memory: a free waits for the whole device).  Values are encoded piece by piece into `out`, the twin of the pinned double
+// buffer; node descriptions and value offsets go through `nodes` / `off` in chunks of `chunk` nodes.  64 MiB + 40 bytes per
+// node of a chunk, whatever the size of the forest: no second copy of the item ids.
+struct EncodeScratch {
+    DevBuf<uint8_t> out;
+    DevBuf<EncNode> nodes;
+    DevBuf<uint64_t> off, sums;
+    DevBuf<uint32_t> info, err;
+    size_t chunk = 0;
+    int ensure(size_t half) {
+        chunk = std::min<size_t>(std::max<size_t>(half / 256, 1024), (size_t)1 << 18);
+        AH_TRY(out.ensure(2 * half));
+        AH_TRY(nodes.ensure(chunk));
+        AH_TRY(off.ensure(chunk + 1));
+        AH_TRY(sums.ensure(enc_scan_sums(chunk)));
+        AH_TRY(info.ensure(chunk));
+        AH_TRY(err.ensure(1));
+        return AH_OK;
+    }
 };
 struct StreamTarget {
     ah_node_batch_fn sink = nullptr;
@@ -2300,6 +2327,7 @@ struct Readback {
     }
     // device -> pinned half -> sink, piece by piece: the DMA of piece p + 1 is in flight while the sink looks at piece p
     hipError_t deliver(StreamJob &job, const uint8_t *src, hipStream_t cs, hipEvent_t *ev) {
+        if (job.encoded) return deliver_encoded(job, src, cs, ev);
         struct Piece {
             size_t a = 0, b = 0;      // nodes [a, b)
             uint64_t off = 0, len = 0;
@@ -2351,6 +2379,102 @@ struct Readback {
             }
             prev = cur;
         }
+        return e;
+    }
+    // The encoded stream: the job's payloads are encoded on this stream, piece by piece, into the device twin of the pinned
+    // half that then carries them to the sink.  A chunk of nodes first gets its value offsets — split values from
+    // has_normal on the host, Descendants from the measure + scan kernels — so that pieces are cut at explicit lengths:
+    // whole values that fit one half.  The encode and the DMA of piece p + 1 are in flight while the sink looks at piece p.
+    EncodeScratch *enc = nullptr;
+    hipError_t deliver_encoded(StreamJob &job, const uint8_t *src, hipStream_t cs, hipEvent_t *ev) {
+        struct Piece {
+            size_t a = 0, b = 0;  // nodes [a, b) of the job
+            uint64_t len = 0;
+            int buf = 0;
+            bool live = false;
+        } prev;
+        const bool leaves = job.head.kind == AH_NODE_DESCENDANTS;
+        const size_t n = job.nodes.size();
+        ah_node_batch head = job.head;
+        head.normal_stride = head.normal_vector_offset = head.normal_header_offset = 0;  // the mark of an encoded batch
+        const uint32_t hdr_off = (uint32_t)job.head.normal_header_offset;
+        std::vector<EncNode> meta;
+        std::vector<uint64_t> off;
+        hipError_t e = hipSuccess;
+        int b = 0;
+        auto stopped = [&] { return target->sink_rc.load() != 0 || target->too_big.load() != 0; };
+        auto hand_over = [&](const Piece &p) -> hipError_t {
+            const hipError_t w = hipEventSynchronize(ev[p.buf]);
+            if (w != hipSuccess || target->sink_rc.load()) return w;
+            ah_node_batch batch = head;
+            batch.n_nodes = p.b - p.a;
+            batch.nodes = job.nodes.data() + p.a;
+            batch.payload = pin + (size_t)p.buf * half;
+            batch.payload_len = p.len;
+            const int rc = target->sink(target->user, &batch);
+            target->batches++;
+            target->bytes += p.len;
+            if (rc != 0) target->sink_rc.store(rc);
+            return hipSuccess;
+        };
+        auto status = [](int st) { return st == AH_OK ? hipSuccess : hipErrorLaunchFailure; };  // (the launchers report through set_error)
+        for (size_t c0 = 0; c0 < n && e == hipSuccess && !stopped(); c0 += enc->chunk) {
+            const size_t cn = std::min(enc->chunk, n - c0);
+            try {
+                meta.resize(cn);
+                off.resize(cn + 1);
+            } catch (const std::bad_alloc &) {  // (nobody catches for this thread)
+                return hipErrorOutOfMemory;
+            }
+            off[0] = 0;
+            for (size_t i = 0; i < cn; i++) {
+                const ah_stream_node &nd = job.nodes[c0 + i];
+                meta[i] = leaves ? EncNode{nd.payload_offset, nd.count, 0u} : EncNode{nd.payload_offset, nd.left, nd.right};
+                if (!leaves) off[i + 1] = off[i] + codec::split_value_len(nd.has_normal != 0, job.header_size, job.vector_size);
+            }
+            uint32_t flags = 0;
+            e = hipMemcpyAsync(enc->nodes.p, meta.data(), cn * sizeof(EncNode), hipMemcpyHostToDevice, cs);
+            if (leaves) {
+                if (e == hipSuccess) e = hipMemsetAsync(enc->err.p, 0, 4, cs);
+                if (e == hipSuccess) e = status(launch_measure_descendants(src, enc->nodes.p, cn, enc->off.p, enc->info.p, enc->sums.p, enc->err.p, cs));
+                if (e == hipSuccess) e = hipMemcpyAsync(off.data(), enc->off.p, (cn + 1) * 8, hipMemcpyDeviceToHost, cs);
+                if (e == hipSuccess) e = hipMemcpyAsync(&flags, enc->err.p, 4, hipMemcpyDeviceToHost, cs);
+            } else if (e == hipSuccess) {
+                e = hipMemcpyAsync(enc->off.p, off.data(), (cn + 1) * 8, hipMemcpyHostToDevice, cs);
+            }
+            // (the host vectors are pageable: they change hands only once the stream has drained)
+            if (e == hipSuccess) e = hipStreamSynchronize(cs);
+            if (e == hipSuccess && (flags & kEncErrOrder)) e = hipErrorInvalidValue;  // the build's own lists ascend: internal error
+            size_t next = 0;
+            while (next < cn && e == hipSuccess && !stopped()) {
+                size_t k = next;
+                while (k < cn && off[k + 1] - off[next] <= half) k++;
+                if (k == next) {  // one value alone does not fit: nothing sensible to hand over
+                    target->too_big.store(1);
+                    break;
+                }
+                Piece cur;
+                cur.a = c0 + next;
+                cur.b = c0 + k;
+                cur.len = off[k] - off[next];
+                cur.buf = b;
+                cur.live = true;
+                uint8_t *d_out = enc->out.p + (size_t)b * half;
+                e = status(leaves ? launch_write_descendants(src, enc->nodes.p + next, k - next, enc->off.p + next, enc->info.p + next, off[next],
+                                                             d_out, (flags & kEncHasBitmap) != 0, cs)
+                                  : launch_write_splits(src, enc->nodes.p + next, k - next, enc->off.p + next, off[next], d_out, hdr_off,
+                                                        job.header_size, cs));
+                if (e == hipSuccess && cur.len) e = hipMemcpyAsync(pin + (size_t)b * half, d_out, cur.len, hipMemcpyDeviceToHost, cs);
+                if (e == hipSuccess) e = hipEventRecord(ev[b], cs);
+                for (size_t i = next; i < k; i++) job.nodes[c0 + i].payload_offset = off[i] - off[next];
+                if (prev.live && e == hipSuccess) e = hand_over(prev);
+                prev = cur;
+                next = k;
+                b ^= 1;
+            }
+            // (the next chunk reuses `nodes` / `off` in stream order, behind this chunk's last write kernel)
+        }
+        if (prev.live && e == hipSuccess) e = hand_over(prev);
         return e;
     }
     void run() {
@@ -2831,6 +2955,7 @@ struct StreamBuild {
     StreamTarget target;
     uint32_t id_base = 0;       // node ids handed out by earlier batches
     uint32_t *roots = nullptr;  // the caller's out_roots
+    bool encoded = false;       // ah_build_forest_stream_encoded: id_base starts at the caller's node_id_base
 };
 struct LeafRec {  // a Descendants node of a streaming build: its ids are final_perm[start, start + count)
     uint64_t start;
@@ -3038,7 +3163,10 @@ static int build_batch(ah_dataset *ds, const ah_build_options *opt, uint32_t fir
     shadow8_arena.block_bytes = std::max<uint64_t>(16ull << 20, std::min<uint64_t>(max_nodes * std::max<uint64_t>(stride8, 16), 4ull << 30));
     BatchCleanup bc;
     AH_TRY(bc.create());
+    EncodeScratch enc_scratch;  // (declared before the read-back worker: it is joined before the buffers it encodes into are freed)
+    if (sb && sb->encoded) AH_TRY(enc_scratch.ensure(kBounce / 2));
     Readback rb;
+    rb.enc = &enc_scratch;
     rb.target = sb ? &sb->target : nullptr;
     rb.copy_threads = host_threads;
     rb.numa_node = numa_node;
@@ -3173,6 +3301,13 @@ static int build_batch(ah_dataset *ds, const ah_build_options *opt, uint32_t fir
             job->head.normal_vector_offset = 0;
             job->head.normal_header_offset = hdr_off;
             job->fixed_len = nstride;
+            job->encoded = sb->encoded;
+            job->header_size = (uint32_t)ah_header_size(ds->metric);
+            job->vector_size = (uint32_t)ah_vector_size(ds->metric, ds->dims);
+            if (sb->encoded && (uint64_t)id_base + base + 2 * (uint64_t)n_nodes > 0xFFFFFFFFull) {
+                delete job;  // (the children's ids are written into the values: they must not wrap)
+                AH_REQUIRE(false, AH_ERR_INVALID_ARGUMENT, "node_id_base + the nodes of this build pass 2^32 - 1");
+            }
             job->nodes.resize(n_nodes);
         }
         auto walk = [&](unsigned t) {
@@ -3401,6 +3536,7 @@ static int build_batch(ah_dataset *ds, const ah_build_options *opt, uint32_t fir
         job->head.kind = AH_NODE_DESCENDANTS;
         job->head.normal_stride = nstride;
         job->head.normal_header_offset = hdr_off;
+        job->encoded = sb->encoded;
         // per tree: where its leaves start in every level's list, and in the output
         const size_t n_lv = stream_leaves.size();
         const uint32_t nt = tB - tA;
@@ -3887,7 +4023,9 @@ static int build_batch(ah_dataset *ds, const ah_build_options *opt, uint32_t fir
         for (uint32_t t = 0; t < n_trees; t++) sb->roots[first_tree + t] = id_base + tree_root[t];
         AH_REQUIRE((uint64_t)id_base + n_recs < 0xFFFFFFFFull, AH_ERR_INVALID_ARGUMENT, "more than 2^32 tree nodes in one build");
         sb->id_base = id_base + (uint32_t)n_recs;
-        AH_REQUIRE(rb.drain() == hipSuccess, AH_ERR_DEVICE, "device -> host copy of the forest failed");
+        const hipError_t rb_err = rb.drain();
+        AH_REQUIRE(rb_err != hipErrorOutOfMemory, AH_ERR_OUT_OF_MEMORY, "host allocation failed in the encoded stream");
+        AH_REQUIRE(rb_err == hipSuccess, AH_ERR_DEVICE, "device -> host copy of the forest failed");
         AH_REQUIRE(!sb->target.too_big.load(), AH_ERR_INVALID_ARGUMENT,
                    "a Descendants node holds more item ids than the streaming buffer (split_after too large for ah_build_forest_stream)");
         AH_REQUIRE(!sb->target.sink_rc.load(), AH_ERR_CANCELLED, "node sink asked to stop (code %d)", sb->target.sink_rc.load());
@@ -3971,9 +4109,20 @@ static int build_forest_impl(ah_dataset *ds, const ah_build_options *options, co
         forest->descendants_len = total;
         if (sb) {
             for (uint64_t i = 0; i < ds->n; i++) forest->descendants[i] = ds->identity_ids ? (uint32_t)i : ds->h_ids[i];
+            // encoded stream: the one list every tree shares becomes one value (the same kernels as ah_encode_descendants)
+            std::vector<uint8_t> value;
+            if (sb->encoded && options->n_trees) {
+                const uint64_t lists[2] = {0, ds->n};
+                uint64_t ends[2] = {0, 0};
+                st = encode_id_lists(ds, forest->descendants, lists, 1, nullptr, 0, ends);
+                if (st == AH_OK) {
+                    value.resize(ends[1]);
+                    st = encode_id_lists(ds, forest->descendants, lists, 1, value.data(), value.size(), ends);
+                }
+            }
             for (uint32_t t = 0; t < options->n_trees && st == AH_OK; t++) {
                 ah_stream_node sn{};
-                sn.id = t;
+                sn.id = sb->id_base + t;
                 sn.tree = t;
                 sn.kind = AH_NODE_DESCENDANTS;
                 sn.count = (uint32_t)ds->n;
@@ -3985,12 +4134,17 @@ static int build_forest_impl(ah_dataset *ds, const ah_build_options *options, co
                 batch.payload_len = ds->n * 4;
                 batch.normal_stride = forest->normal_stride;
                 batch.normal_header_offset = forest->normal_header_offset;
+                if (sb->encoded) {
+                    batch.payload = value.data();
+                    batch.payload_len = value.size();
+                    batch.normal_stride = batch.normal_header_offset = 0;
+                }
                 const int rc = sb->target.sink(sb->target.user, &batch);
                 if (rc != 0) {
                     set_error("node sink asked to stop (code %d)", rc);
                     st = AH_ERR_CANCELLED;
                 }
-                sb->roots[t] = t;
+                sb->roots[t] = sb->id_base + t;
                 forest->stats.descendant_nodes++;
             }
         }
@@ -4173,6 +4327,29 @@ int ah_build_forest_stream(ah_dataset *ds, const ah_build_options *options, ah_n
     sb.target.sink = sink;
     sb.target.user = user;
     sb.roots = out_roots;
+    ah_forest *forest = nullptr;
+    const int st = build_forest_impl(ds, options, nullptr, nullptr, &forest, &sb);
+    if (st == AH_OK && out_stats) *out_stats = forest->stats;
+    delete forest;
+    return st;
+    AH_GUARDED_END
+}
+
+// The streaming build with the NodeCodec values encoded on the device (include/arroy_hip.h, "Encoded node stream").
+int ah_build_forest_stream_encoded(ah_dataset *ds, const ah_build_options *options, const ah_encode_options *enc,
+                                   ah_node_batch_fn sink, void *user, uint32_t *out_roots, ah_build_stats *out_stats) {
+    AH_GUARDED("ah_build_forest_stream_encoded")
+    AH_REQUIRE(sink, AH_ERR_INVALID_ARGUMENT, "sink is NULL");
+    AH_REQUIRE(enc && options && (out_roots || options->n_trees == 0), AH_ERR_INVALID_ARGUMENT, "NULL argument");
+    AH_REQUIRE(enc->flags == 0, AH_ERR_INVALID_ARGUMENT, "ah_encode_options.flags must be 0");
+    AH_REQUIRE((uint64_t)enc->node_id_base + options->n_trees <= 0x100000000ull, AH_ERR_INVALID_ARGUMENT,
+               "node_id_base + the nodes of this build pass 2^32 - 1");
+    StreamBuild sb;
+    sb.target.sink = sink;
+    sb.target.user = user;
+    sb.roots = out_roots;
+    sb.encoded = true;
+    sb.id_base = enc->node_id_base;
     ah_forest *forest = nullptr;
     const int st = build_forest_impl(ds, options, nullptr, nullptr, &forest, &sb);
     if (st == AH_OK && out_stats) *out_stats = forest->stats;

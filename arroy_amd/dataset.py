@@ -307,10 +307,14 @@ class Dataset:
         return Forest(h, self.distance, self.dimensions)
 
     def build_forest_stream(self, tree_seeds: Sequence[int], sink=None, split_after: int = 0, margin_mode: int = 0,
-                            max_trees_in_flight: int = 0, max_host_threads: int = 0):
+                            max_trees_in_flight: int = 0, max_host_threads: int = 0, encoded: bool = False, node_id_base: int = 0):
         """ah_build_forest_stream: the node sink DURING the build (`TmpNodes::put`, src/parallel.rs:130-147).  `sink(batch)`
         receives every `_lib.AhNodeBatch` (valid only during the call; return non-zero to stop the build); with sink=None the
-        batches are collected into a `StreamedForest`.  Returns (roots, stats, collected or None)."""
+        batches are collected into a `StreamedForest`.  Returns (roots, stats, collected or None).
+        encoded=True: ah_build_forest_stream_encoded — the payloads are NodeCodec values encoded on the device and every node
+        id has `node_id_base` added (`roots` too; a StreamedForest keeps ids minus the base)."""
+        if node_id_base and not encoded:
+            raise ValueError("node_id_base belongs to the encoded stream")
         seeds = np.ascontiguousarray(tree_seeds, dtype=np.uint64)
         opt = _lib.AhBuildOptions()
         opt.n_trees = seeds.size
@@ -319,7 +323,7 @@ class Dataset:
         opt.margin_mode = int(margin_mode)
         opt.max_trees_in_flight = int(max_trees_in_flight)
         opt.max_host_threads = int(max_host_threads)
-        collected = StreamedForest(self.distance, self.dimensions) if sink is None else None
+        collected = StreamedForest(self.distance, self.dimensions, node_id_base=int(node_id_base)) if sink is None else None
         fn = collected.take if sink is None else sink
         failure = []
 
@@ -332,15 +336,38 @@ class Dataset:
         cb = _lib.NODE_BATCH_FN(_cb)
         roots = np.zeros(seeds.size, dtype=np.uint32)
         st = _lib.AhBuildStats()
-        code = _lib.lib().ah_build_forest_stream(self._h, C.byref(opt), cb, None, _ptr(roots), C.byref(st))
+        if encoded:
+            enc = _lib.AhEncodeOptions(int(node_id_base), 0)
+            code = _lib.lib().ah_build_forest_stream_encoded(self._h, C.byref(opt), C.byref(enc), cb, None, _ptr(roots), C.byref(st))
+        else:
+            code = _lib.lib().ah_build_forest_stream(self._h, C.byref(opt), cb, None, _ptr(roots), C.byref(st))
         if failure:
             raise failure[0]
         _lib.check(code)
         stats = {f: getattr(st, f) for f, _ in _lib.AhBuildStats._fields_}
         stats["margin_mode_launches"] = list(st.margin_mode_launches)
         if collected is not None:
-            collected.roots = roots
+            collected.roots = roots - np.uint32(node_id_base)
         return roots, stats, collected
+
+    def encode_descendants(self, id_lists: Sequence[Sequence[int]], sizes_only: bool = False, out_cap: int | None = None):
+        """ah_encode_descendants: the Descendants values (tag byte included) of ascending id lists, encoded on the device.
+        Returns a list of bytes, or with sizes_only the value offsets (len(id_lists) + 1, uint64)."""
+        n = len(id_lists)
+        offsets = np.zeros(n + 1, dtype=np.uint64)
+        offsets[1:] = np.cumsum([len(l) for l in id_lists])
+        ids = _u32(np.concatenate([_u32(l) for l in id_lists])) if n else np.zeros(0, np.uint32)
+        if ids.size == 0:
+            ids = np.zeros(1, np.uint32)
+        ends = np.zeros(n + 1, dtype=np.uint64)
+        _lib.check(_lib.lib().ah_encode_descendants(self._h, _ptr(ids), _ptr(offsets), n, None, 0, _ptr(ends)))
+        if sizes_only:
+            return ends
+        cap = int(ends[n]) if out_cap is None else int(out_cap)
+        out = np.full(int(ends[n]) + 64, 0xA5, dtype=np.uint8)  # (the tail shows a write past the cap)
+        _lib.check(_lib.lib().ah_encode_descendants(self._h, _ptr(ids), _ptr(offsets), n, _ptr(out), cap, _ptr(ends)))
+        assert bool(np.all(out[int(ends[n]):] == 0xA5)), "ah_encode_descendants wrote past the end of its values"
+        return [out[int(ends[i]): int(ends[i + 1])].tobytes() for i in range(n)]
 
     def build_subtrees(self, id_lists: Sequence[Sequence[int]], tree_seeds: Sequence[int], split_after: int = 0) -> "Forest":
         """`incremental_index_large_descendant` for many item subsets at once (ah_build_subtrees)."""
@@ -1059,15 +1086,41 @@ class Filter:
 class StreamedForest:
     """What a sink of ah_build_forest_stream has seen, kept as dictionaries (test aid: small forests)."""
 
-    def __init__(self, distance, dimensions):
-        self.distance, self.dimensions = distance, dimensions
+    def __init__(self, distance, dimensions, node_id_base: int = 0):
+        self.distance, self.dimensions, self.node_id_base = distance, dimensions, node_id_base
         self.splits, self.leaves, self.roots = {}, {}, None
         self.batches = []  # (kind, level, n_nodes, payload_len) in arrival order
+        self.values = {}   # encoded batches: node id (minus the base) -> the value's bytes as they arrived
+
+    def _take_encoded(self, b, payload) -> int:
+        """A batch of NodeCodec values (normal_stride == 0): the same dictionaries, ids minus node_id_base."""
+        from . import node_codec
+        n, base = int(b.n_nodes), self.node_id_base
+        for i in range(n):
+            nd = b.nodes[i]
+            assert nd.kind == b.kind, f"node {nd.id} of kind {nd.kind} in a batch of kind {b.kind}"
+            nid = int(nd.id) - base
+            assert nid >= 0 and nid not in self.splits and nid not in self.leaves, f"node {nd.id} arrives twice or lies below the base"
+            lo = int(nd.payload_offset)
+            hi = int(b.nodes[i + 1].payload_offset) if i + 1 < n else int(b.payload_len)
+            value = payload[lo:hi].tobytes()
+            self.values[nid] = value
+            dec = node_codec.decode_value(self.distance, self.dimensions, value)
+            if nd.kind == 2:
+                assert dec[0] == "S" and (dec[1], dec[2]) == (int(nd.left), int(nd.right)), (nd.id, dec[:3], nd.left, nd.right)
+                assert (dec[3] is not None) == bool(nd.has_normal), nd.id
+                self.splits[nid] = (dec[3], dec[1] - base, dec[2] - base, int(nd.tree), int(nd.depth), int(nd.count))
+            else:
+                assert dec[0] == "D" and dec[1].size == int(nd.count), (nd.id, dec[1].size, nd.count)
+                self.leaves[nid] = (tuple(int(x) for x in dec[1]), int(nd.tree), int(nd.depth))
+        return 0
 
     def take(self, b) -> int:
         n = int(b.n_nodes)
         self.batches.append((int(b.kind), int(b.level), n, int(b.payload_len)))
         payload = np.ctypeslib.as_array(b.payload, shape=(int(b.payload_len),)) if b.payload_len else np.zeros(0, np.uint8)
+        if int(b.normal_stride) == 0 and int(b.normal_vector_offset) == 0 and int(b.normal_header_offset) == 0:
+            return self._take_encoded(b, payload)
         hs, vs = self.distance.header_size(), self.distance.vector_size(self.dimensions)
         for i in range(n):
             nd = b.nodes[i]

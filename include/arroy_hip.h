@@ -497,6 +497,35 @@ AH_API int ah_build_forest_stream(ah_dataset *ds, const ah_build_options *option
                                   uint32_t *out_roots, ah_build_stats *out_stats);
 
 /* ------------------------------------------------------------------------------------------
+ * Encoded node stream (v7 additions; callers look the symbols up): the same streaming build, but every node arrives as
+ * the bytes `NodeCodec::bytes_encode` would produce (src/node.rs:229-241), encoded on the device, so a Writer only has to
+ * `put(key, slice)`:
+ *   split        [2][left u32 BE][right u32 BE], then [D::Header][vector] (ah_header_size + ah_vector_size bytes) unless
+ *                `normal: None`
+ *   Descendants  [1] + RoaringBitmap::serialize_into of the item ids (portable format, no run containers)
+ * Same forest, same batch order and same ah_stream_node metadata as ah_build_forest_stream for the same seeds, except:
+ *   - id, left, right, out_roots and the child ids inside the values have `node_id_base` added (reserve the range with one
+ *     bump of the id generator); a build whose ids would pass 2^32 - 1 is refused with AH_ERR_INVALID_ARGUMENT;
+ *   - a batch has normal_stride = normal_vector_offset = normal_header_offset = 0 (the mark of an encoded batch), and node
+ *     i's value is payload[nodes[i].payload_offset, nodes[i + 1].payload_offset); the last one ends at payload_len.
+ * The values are encoded piece by piece on the read-back worker's stream into a device buffer as large as the pinned
+ * double buffer; if that buffer cannot be had the call returns AH_ERR_OUT_OF_MEMORY (there is no unencoded fall-back).
+ * ah_build_forest_group_stream has no encoded twin.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct ah_encode_options {
+    uint32_t node_id_base;   /* added to every node id of the call */
+    uint32_t flags;          /* 0 */
+} ah_encode_options;
+AH_API int ah_build_forest_stream_encoded(ah_dataset *ds, const ah_build_options *options, const ah_encode_options *enc,
+                                          ah_node_batch_fn sink, void *user, uint32_t *out_roots, ah_build_stats *out_stats);
+/* Descendants values of `n_lists` ascending id lists, ids[offsets[i] .. offsets[i + 1]), encoded on ds's device (the tag byte
+ * included).  out_value_offsets[0 .. n_lists]: value i is out_values[out_value_offsets[i], out_value_offsets[i + 1]).
+ * out_values == NULL: only the offsets (the sizes).  A list that does not ascend strictly, or an out_cap smaller than
+ * out_value_offsets[n_lists], is AH_ERR_INVALID_ARGUMENT; nothing is written past out_cap. */
+AH_API int ah_encode_descendants(ah_dataset *ds, const uint32_t *ids, const uint64_t *offsets, size_t n_lists,
+                                 uint8_t *out_values, uint64_t out_cap, uint64_t *out_value_offsets);
+
+/* ------------------------------------------------------------------------------------------
  * Device groups: one replica of the dataset per listed device, staged from ONE host pass, and one forest built on all of
  * them.  Trees are independent given the read-only dataset (`Writer::build` runs one task per root over ONE shared
  * ImmutableLeafs, src/writer.rs:530,556-591), so a group shards TREES: tree t of a build is built on member t mod G, and
