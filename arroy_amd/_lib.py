@@ -203,6 +203,11 @@ class AhFilterResumeStats(C.Structure):
     _fields_ = [(f, C.c_uint64) for f in ("filters", "groups", "words", "ids_removed", "ids_added", "leaves", "ids_walked")]
 
 
+class AhFilterRoaringStats(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("filters", "groups", "array_containers", "bitmap_containers", "run_containers",
+                                          "skipped_containers", "bytes_uploaded", "leaves", "ids_walked")]
+
+
 class AhStreamNode(C.Structure):
     _fields_ = [("id", C.c_uint32), ("tree", C.c_uint32), ("kind", C.c_uint8), ("has_normal", C.c_uint8), ("reserved", C.c_uint16),
                 ("left", C.c_uint32), ("right", C.c_uint32), ("count", C.c_uint32), ("depth", C.c_uint32),
@@ -309,6 +314,10 @@ SIGNATURES = {
     "ah_filter_resume_batch": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(AhFilterEdit), C.c_size_t,
                                          C.POINTER(AhFilterResumeStats)]),
     "ah_index_filters_suspended": (C.c_int, [_VP, C.POINTER(C.c_uint64)]),
+    # filters from serialized RoaringBitmaps
+    "ah_filter_create_roaring": (C.c_int, [_VP, _VP, C.c_size_t, C.POINTER(C.c_void_p)]),
+    "ah_filter_create_roaring_batch": (C.c_int, [_VP, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_size_t, C.POINTER(C.c_void_p),
+                                                 C.POINTER(AhFilterRoaringStats)]),
     # deletes on a resident index; an index kept across an update of its dataset
     "ah_index_delete_items": (C.c_int, [_VP, _U32P, C.c_size_t, C.c_uint32, C.POINTER(C.c_void_p)]),
     "ah_index_delta_get": (C.c_int, [_VP, C.POINTER(AhIndexDeltaView)]),

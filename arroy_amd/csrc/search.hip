@@ -21,6 +21,7 @@
 
 #include "common.h"
 #include "index_device.h"
+#include "roaring_parse.h"
 #include "split_device.h"
 #include "screen_device.h"
 #include "search_plan.h"
@@ -3840,6 +3841,138 @@ __global__ __launch_bounds__(256) void k_leaf_kept_group(const DNode *__restrict
     block_add_u64(ids_walked, &counters[RC_IDS_WALKED], s_part);
 }
 
+// ---- filters from serialized RoaringBitmaps (ah_filter_create_roaring_batch) --------------------------------------------------
+// One travelling container of a call: whose it is, what the blob's headers say about it (roaring_parse.h), and where its payload
+// lies in the call's staging buffer.  The host puts every payload at a 16-byte boundary and allots it whole 16-byte units, so a
+// 16-byte load that begins inside a payload ends inside its allotment.
+struct RoaringItem {
+    uint32_t filter;       // the blob, and the slot of its filter in the call's ResumeSlot table
+    uint32_t container;    // its position in the blob (for the error code)
+    uint32_t key;          // id >> 16 of its span; at most (len_bits - 1) >> 16 (the host leaves the others behind)
+    uint32_t kind;         // roaring::Kind
+    uint32_t cardinality;  // 1 .. 65536; a KIND_ARRAY has at most 4096 (the kind follows from it)
+    uint32_t n_runs;       // KIND_RUN: the runs behind the payload's first u16 (which the host has read)
+    uint64_t payload;      // byte offset in the staging buffer, a multiple of 16
+};
+static_assert(sizeof(RoaringItem) == 32, "laid out by hand in the call's one upload");
+// Why a payload was refused, in the low byte of the error code ((blob << 24) | (container << 8) | reason: the smallest code of a
+// call is the one reported, hence the lowest (blob, container)).
+enum RoaringReason : uint32_t { RR_ARRAY_ORDER = 1, RR_BITMAP_CARDINALITY, RR_RUN_ORDER, RR_RUN_PAST_END, RR_RUN_CARDINALITY };
+constexpr uint32_t kRoaringSpanWords = 2048;  // the 32-bit words of a container's 64Ki ids
+
+// One block per travelling container.  The container owns the 2048 words of its span in its filter's bitmap (the keys of a blob
+// ascend strictly, every blob has its own filter), which the block writes with plain 16-byte stores over the zeroes of the
+// call's memset: array and run containers through an 8 KiB image in LDS, bitmap containers straight through registers.  Nothing
+// indexes by an unchecked value: array values and run bounds are 16 bits wide and address the image only, run ends are clamped
+// to 65535 before use, and what leaves the block is masked against len_bits and never lies at or past the bitmap's used words.
+// Counted: the bits written into `inside` of the filter (RC_LISTED of its counters; `stored` on identity ids), and all bits of
+// the image against the cardinality the header states.  What fails a check goes into *err by one atomicMin.
+__global__ __launch_bounds__(256) void k_roaring_expand(const RoaringItem *__restrict__ items, const uint8_t *__restrict__ staging,
+                                                        const ResumeSlot *__restrict__ slots, uint64_t len_bits,
+                                                        unsigned long long *__restrict__ counters, unsigned long long *__restrict__ err) {
+    __shared__ __attribute__((aligned(16))) uint32_t s_img[kRoaringSpanWords];
+    __shared__ unsigned long long s_part[4];
+    __shared__ uint32_t s_all[4], s_bad;
+    const RoaringItem it = items[blockIdx.x];  // (wave-uniform: scalar loads)
+    const uint32_t t = threadIdx.x;
+    const uint8_t *payload = staging + it.payload;
+    const uint4 *payload16 = reinterpret_cast<const uint4 *>(payload);
+    const uint16_t *payload2 = reinterpret_cast<const uint16_t *>(payload);
+    uint32_t *bits = slots[it.filter].bits;
+    const uint64_t word0 = (uint64_t)it.key * kRoaringSpanWords, used_words = (len_bits + 31) >> 5;
+    uint32_t bad = 0xFFFFFFFFu;  // the smallest reason this thread found
+    if (t == 0) s_bad = 0xFFFFFFFFu;
+    uint4 q[2];  // this thread's eight words of the span: quads t and t + 256
+    if (it.kind == roaring::KIND_BITMAP) {
+        q[0] = payload16[t];
+        q[1] = payload16[t + 256];
+        __syncthreads();  // (s_bad)
+    } else {
+        reinterpret_cast<uint4 *>(s_img)[t] = make_uint4(0, 0, 0, 0);
+        reinterpret_cast<uint4 *>(s_img)[t + 256] = make_uint4(0, 0, 0, 0);
+        __syncthreads();
+        if (it.kind == roaring::KIND_ARRAY) {
+            // sixteen values a thread (two 16-byte loads); a value is compared with the one before it, the first of a thread with
+            // the last of the thread before, read from the payload again
+            const uint32_t first = 16 * t, card = min(it.cardinality, 4096u);
+            uint32_t prev = first > 0 && first < card ? payload2[first - 1] : 0u;
+            bool has_prev = first > 0;
+#pragma unroll
+            for (uint32_t h = 0; h < 2; h++) {
+                if (first + 8 * h >= card) break;
+                const uint4 x = payload16[2 * t + h];
+                const uint32_t w[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+                for (uint32_t k = 0; k < 8; k++) {
+                    if (first + 8 * h + k >= card) break;
+                    const uint32_t v = (w[k >> 1] >> (16 * (k & 1))) & 0xFFFFu;
+                    if (has_prev && v <= prev) bad = min(bad, (uint32_t)RR_ARRAY_ORDER);
+                    atomicOr(&s_img[v >> 5], 1u << (v & 31));
+                    prev = v;
+                    has_prev = true;
+                }
+            }
+        } else {
+            // the runs dealt over the threads: edge words by atomic OR of masks, interior words whole (they are this run's alone
+            // unless runs overlap, which is refused)
+            for (uint32_t r = t; r < it.n_runs; r += 256) {
+                const uint32_t start = payload2[1 + 2 * r];
+                uint32_t end = start + payload2[2 + 2 * r];  // inclusive
+                if (end > 0xFFFFu) {
+                    bad = min(bad, (uint32_t)RR_RUN_PAST_END);
+                    end = 0xFFFFu;
+                }
+                if (r > 0 && start <= (uint32_t)payload2[2 * r - 1] + (uint32_t)payload2[2 * r]) bad = min(bad, (uint32_t)RR_RUN_ORDER);
+                const uint32_t fw = start >> 5, lw = end >> 5;
+                const uint32_t head = 0xFFFFFFFFu << (start & 31), tail = 0xFFFFFFFFu >> (31 - (end & 31));
+                if (fw == lw) {
+                    atomicOr(&s_img[fw], head & tail);
+                } else {
+                    atomicOr(&s_img[fw], head);
+                    for (uint32_t w = fw + 1; w < lw; w++) s_img[w] = 0xFFFFFFFFu;
+                    atomicOr(&s_img[lw], tail);
+                }
+            }
+        }
+        __syncthreads();
+        q[0] = reinterpret_cast<const uint4 *>(s_img)[t];
+        q[1] = reinterpret_cast<const uint4 *>(s_img)[t + 256];
+    }
+    // the write-out: masked against len_bits, no word at or past the used words
+    uint32_t all = 0;
+    unsigned long long inside = 0;
+#pragma unroll
+    for (uint32_t h = 0; h < 2; h++) {
+        const uint64_t w = word0 + 4 * (uint64_t)(t + 256 * h);
+        all += (uint32_t)(__popc(q[h].x) + __popc(q[h].y) + __popc(q[h].z) + __popc(q[h].w));
+        if (w >= used_words) continue;
+        const uint4 r = make_uint4(q[h].x & word_mask(w, len_bits), q[h].y & word_mask(w + 1, len_bits), q[h].z & word_mask(w + 2, len_bits),
+                                   q[h].w & word_mask(w + 3, len_bits));
+        inside += (uint32_t)(__popc(r.x) + __popc(r.y) + __popc(r.z) + __popc(r.w));
+        if (w + 4 <= used_words) {
+            *reinterpret_cast<uint4 *>(bits + w) = r;  // (the block is 128-byte aligned, w a multiple of 4)
+        } else {
+            bits[w] = r.x;
+            if (w + 1 < used_words) bits[w + 1] = r.y;
+            if (w + 2 < used_words) bits[w + 2] = r.z;
+        }
+    }
+    block_add_u64(inside, &counters[RC_TOTALS + RC_PER_FILTER * it.filter + RC_LISTED], s_part);
+    for (uint32_t d = 32; d > 0; d >>= 1) all += __shfl_xor(all, d, 64);
+    if ((t & 63u) == 0) s_all[t >> 6] = all;
+    if (bad != 0xFFFFFFFFu) atomicMin(&s_bad, bad);
+    __syncthreads();
+    if (t == 0) {
+        uint32_t reason = s_bad;
+        if (s_all[0] + s_all[1] + s_all[2] + s_all[3] != it.cardinality)
+            reason = min(reason, (uint32_t)(it.kind == roaring::KIND_BITMAP ? RR_BITMAP_CARDINALITY
+                                             : it.kind == roaring::KIND_RUN  ? RR_RUN_CARDINALITY
+                                                                              : RR_ARRAY_ORDER));  // (an array: a value twice)
+        if (reason != 0xFFFFFFFFu)
+            atomicMin(err, ((unsigned long long)it.filter << 24) | ((unsigned long long)it.container << 8) | reason);
+    }
+}
+
 // normal records [vector (row_bytes)][header (16)] -> row matrix + header array of the normals view
 // Only the `valid_words32` words of the stored vector (ah_vector_size bytes) are read from the record: caller views are
 // compact ([header][vector], stride hs + vs), so the device pitch beyond them is zero-filled, never copied.
@@ -5362,8 +5495,48 @@ static uint64_t filter_len_bits(const ah_dataset *ds) {
     if (!ds->n) return 0;
     return (uint64_t)(ds->identity_ids ? (uint32_t)(ds->n - 1) : ds->last_id) + 1;
 }
-// A finished filter joins its index: the counters of ah_filter_stats move, the block is the filter's from here.
-static void filter_adopt(ah_filter *f, ah_index *ix, DevMem &block, const FilterBlock &fb, uint64_t listed, uint64_t stored) {
+// How a call that makes the per-node counts of many filters of one length groups them (ah_filter_resume_batch,
+// ah_filter_create_roaring_batch).  A group's bitmaps side by side (k_filter_interleave) take 64 bytes per bitmap word: where that
+// passes the budget (256 MiB: ids beyond 2^27) the counts are made a filter a pass, as ah_filter_create makes them.
+struct GroupPlan {
+    uint64_t used_words;
+    size_t mixed_bytes, group;
+    explicit GroupPlan(const FilterBlock &fb) : used_words((fb.len_bits + 31) / 32) {
+        mixed_bytes = std::max<size_t>(1, (size_t)used_words) * AH_FILTER_RESUME_GROUP * 4;
+        group = (size_t)std::min<long long>(AH_FILTER_RESUME_GROUP, std::max<long long>(1, tun(TUN_FILTER_RESUME_GROUP)));
+        if (mixed_bytes > ((size_t)std::max<long long>(0, tun(TUN_FILTER_RESUME_MIXED_MB)) << 20)) group = 1;
+    }
+    size_t groups_of(size_t n) const { return (n + group - 1) / group; }
+};
+// The per-node counts of the filters in `blocks` (FilterBlock layout, bitmaps finished on the stream), a group a pass;
+// `mixed`: gp.mixed_bytes where gp.group > 1.  RC_LEAVES and RC_IDS_WALKED of `d_counters` are counted.
+static void launch_leaf_kept_groups(const ah_index *ix, const FilterBlock &fb, const GroupPlan &gp, const std::vector<DevMem> &blocks,
+                                    const DevMem &mixed, unsigned long long *d_counters, hipStream_t s) {
+    const uint32_t n_nodes = ix->n_nodes;
+    const size_t n = blocks.size();
+    if (!n_nodes) return;
+    for (size_t g0 = 0; g0 < n; g0 += gp.group) {
+        const size_t g = std::min(gp.group, n - g0);
+        ResumeGroup t{};
+        for (size_t f = 0; f < AH_FILTER_RESUME_GROUP; f++) t.block[f] = blocks[g0 + (f < g ? f : 0)].as<uint32_t>();
+        const dim3 grid(grid_of(n_nodes, 32, 2048));
+        if (gp.group == 1 || g == 1) {  // (a group of one reads its own bitmap: nothing to lay side by side)
+            hipLaunchKernelGGL((k_leaf_kept_group<1, false>), grid, dim3(256), 0, s, ix->d_nodes, ix->d_desc, n_nodes, fb.len_bits,
+                               (uint64_t)fb.words, t, (const uint4 *)nullptr, g0 == 0 ? 1 : 0, d_counters);
+            continue;
+        }
+        // (one stream: the pass before has read `mixed` before this group's words are written over it)
+        if (gp.used_words)
+            hipLaunchKernelGGL(k_filter_interleave, dim3(grid_of(gp.used_words, 256, 2048)), dim3(256), 0, s, t, gp.used_words, mixed.as<uint4>());
+        hipLaunchKernelGGL((k_leaf_kept_group<AH_FILTER_RESUME_GROUP, true>), grid, dim3(256), 0, s, ix->d_nodes, ix->d_desc, n_nodes,
+                           fb.len_bits, (uint64_t)fb.words, t, mixed.as<const uint4>(), g0 == 0 ? 1 : 0, d_counters);
+    }
+}
+
+// A finished filter joins its index: the counters of ah_filter_stats move, the block is the filter's from here.  `passes`: what
+// its per-node counts cost in passes over the Descendants ids (a batched call charges its groups to its first filter).
+static void filter_adopt(ah_filter *f, ah_index *ix, DevMem &block, const FilterBlock &fb, uint64_t listed, uint64_t stored,
+                         uint64_t passes = 1) {
     f->listed = listed;
     f->stored = stored;
     f->d_bits = block.as<uint32_t>();
@@ -5373,7 +5546,7 @@ static void filter_adopt(ah_filter *f, ah_index *ix, DevMem &block, const Filter
         std::lock_guard<std::mutex> lk(ix->stats_mu);
         ix->fstats.filters_created++;
         ix->fstats.filters_alive++;
-        ix->fstats.leaf_kept_passes += ix->n_nodes ? 1 : 0;
+        ix->fstats.leaf_kept_passes += ix->n_nodes ? passes : 0;
     }
     block.p = nullptr;
 }
@@ -5639,13 +5812,8 @@ int ah_filter_resume_batch(ah_filter *const *filters, const ah_filter_edit *edit
     AH_HIP(hipSetDevice(ds->device));
     const FilterBlock fb(ix, filter_len_bits(ds));
     const uint32_t n_nodes = ix->n_nodes;
-    // A group's bitmaps side by side (k_filter_interleave) take 64 bytes per bitmap word: where that passes the budget (256 MiB: ids
-    // beyond 2^27) the counts are made a filter a pass, as ah_filter_create makes them
-    const uint64_t used_words = (fb.len_bits + 31) / 32;
-    const size_t mixed_bytes = std::max<size_t>(1, (size_t)used_words) * AH_FILTER_RESUME_GROUP * 4;
-    size_t group = (size_t)std::min<long long>(AH_FILTER_RESUME_GROUP, std::max<long long>(1, tun(TUN_FILTER_RESUME_GROUP)));
-    if (mixed_bytes > ((size_t)std::max<long long>(0, tun(TUN_FILTER_RESUME_MIXED_MB)) << 20)) group = 1;
-    const size_t n_groups = (n + group - 1) / group;
+    const GroupPlan gp(fb);
+    const size_t group = gp.group, mixed_bytes = gp.mixed_bytes, n_groups = gp.groups_of(n);
     // the call's one upload: [counters][slots][the edit ids, list after list]
     const size_t counters_bytes = (RC_TOTALS + RC_PER_FILTER * n) * 8, slots_bytes = n * sizeof(ResumeSlot);
     std::vector<unsigned long long> h((RC_TOTALS + RC_PER_FILTER * n));
@@ -5701,23 +5869,7 @@ int ah_filter_resume_batch(ah_filter *const *filters, const ah_filter_edit *edit
             hipLaunchKernelGGL(k_filter_stored_rows_batch, dim3(grid_of(ds->n, 256, 256), ny), dim3(256), 0, s, d_slots + y0, ds->view().ids,
                                (uint64_t)ds->n, per_filter);
     }
-    if (n_nodes)
-        for (size_t g0 = 0; g0 < n; g0 += group) {
-            const size_t g = std::min(group, n - g0);
-            ResumeGroup t{};
-            for (size_t f = 0; f < AH_FILTER_RESUME_GROUP; f++) t.block[f] = blocks[g0 + (f < g ? f : 0)].as<uint32_t>();
-            const dim3 grid(grid_of(n_nodes, 32, 2048));
-            if (group == 1) {
-                hipLaunchKernelGGL((k_leaf_kept_group<1, false>), grid, dim3(256), 0, s, ix->d_nodes, ix->d_desc, n_nodes, fb.len_bits,
-                                   (uint64_t)fb.words, t, (const uint4 *)nullptr, g0 == 0 ? 1 : 0, d_counters);
-                continue;
-            }
-            // (one stream: the pass before has read `mixed` before this group's words are written over it)
-            if (used_words)
-                hipLaunchKernelGGL(k_filter_interleave, dim3(grid_of(used_words, 256, 2048)), dim3(256), 0, s, t, used_words, mixed.as<uint4>());
-            hipLaunchKernelGGL((k_leaf_kept_group<AH_FILTER_RESUME_GROUP, true>), grid, dim3(256), 0, s, ix->d_nodes, ix->d_desc, n_nodes,
-                               fb.len_bits, (uint64_t)fb.words, t, mixed.as<const uint4>(), g0 == 0 ? 1 : 0, d_counters);
-        }
+    launch_leaf_kept_groups(ix, fb, gp, blocks, mixed, d_counters, s);
     AH_HIP(hipGetLastError());
     AH_HIP(hipMemcpyAsync(h.data(), d_counters, counters_bytes, hipMemcpyDeviceToHost, s));
     AH_HIP(hipStreamSynchronize(s));
@@ -5744,6 +5896,143 @@ int ah_filter_resume_batch(ah_filter *const *filters, const ah_filter_edit *edit
     if (out_stats)
         *out_stats = ah_filter_resume_stats{n, n_groups, (uint64_t)fb.words * n, h[RC_REMOVED], h[RC_ADDED], h[RC_LEAVES], h[RC_IDS_WALKED]};
     return AH_OK;
+    AH_GUARDED_END
+}
+
+// ---- filters from serialized RoaringBitmaps (include/arroy_hip.h) ---------------------------------------------------------
+
+// The headers of every blob are judged on the host (roaring_parse.h) before the index is looked at.  Then everything is obtained
+// — the n handles and blocks, the call's one device buffer [counters][error word][slots][items][payloads], the interleave
+// buffer, the pinned staging — and queued on the calling thread's leased context: a memset per block, ONE upload, k_roaring_expand
+// over the travelling containers of the whole call, `stored` on sparse ids, the grouped per-node counts.  One synchronisation;
+// the filters join their index after it, where nothing can fail any more.
+static int filter_create_roaring(ah_index *ix, const uint8_t *const *blobs, const size_t *lens, size_t n, ah_filter **out,
+                                 ah_filter_roaring_stats *out_stats) {
+    if (out_stats) *out_stats = ah_filter_roaring_stats{};
+    AH_REQUIRE(out, AH_ERR_INVALID_ARGUMENT, "out is NULL");
+    for (size_t i = 0; i < n; i++) out[i] = nullptr;
+    if (n == 0) return AH_OK;
+    AH_REQUIRE(blobs && lens, AH_ERR_INVALID_ARGUMENT, "%s is NULL", blobs ? "lens" : "blobs");
+    AH_REQUIRE(n < (1u << 24), AH_ERR_INVALID_ARGUMENT, "too many blobs (%zu)", n);
+    for (size_t i = 0; i < n; i++) AH_REQUIRE(blobs[i], AH_ERR_INVALID_ARGUMENT, "blobs[%zu] is NULL", i);
+    std::vector<std::vector<roaring::Container>> parsed(n);
+    std::vector<uint64_t> listed(n);
+    for (size_t i = 0; i < n; i++) {
+        char why[200];
+        AH_REQUIRE(roaring::parse(blobs[i], lens[i], parsed[i], &listed[i], why, sizeof why), AH_ERR_INVALID_ARGUMENT, "blobs[%zu]: %s", i, why);
+    }
+    AH_REQUIRE(ix && ix->ds, AH_ERR_INVALID_ARGUMENT, "index is NULL");
+    AH_INDEX_LIVE(ix);
+    ah_dataset *ds = ix->ds;
+    AH_HIP(hipSetDevice(ds->device));
+    const FilterBlock fb(ix, filter_len_bits(ds));
+    const GroupPlan gp(fb);
+    const size_t n_groups = gp.groups_of(n);
+    // what travels: the containers whose span begins below len_bits, each at a 16-byte boundary of the staging and in whole
+    // 16-byte units
+    ah_filter_roaring_stats st{};
+    st.filters = n, st.groups = n_groups;
+    std::vector<RoaringItem> items;
+    uint64_t staging_bytes = 0;
+    for (size_t i = 0; i < n; i++)
+        for (size_t c = 0; c < parsed[i].size(); c++) {
+            const roaring::Container &k = parsed[i][c];
+            if (fb.len_bits == 0 || k.key > ((fb.len_bits - 1) >> 16)) {
+                st.skipped_containers++;
+                continue;
+            }
+            (k.kind == roaring::KIND_ARRAY ? st.array_containers : k.kind == roaring::KIND_BITMAP ? st.bitmap_containers : st.run_containers)++;
+            st.bytes_uploaded += k.bytes;
+            items.push_back(RoaringItem{(uint32_t)i, (uint32_t)c, k.key, k.kind, k.cardinality, k.n_runs, staging_bytes});
+            staging_bytes += (k.bytes + 15) & ~(uint64_t)15;
+        }
+    AH_REQUIRE(items.size() < 0x7FFFFFFFull, AH_ERR_INVALID_ARGUMENT, "too many containers (%zu)", items.size());
+    // the call's one device buffer: [counters][error word (8)][slots][items][payloads], every part a multiple of 16 bytes
+    const size_t err_word = (RC_TOTALS + RC_PER_FILTER * n + 1) & ~(size_t)1, counters_bytes = (err_word + 2) * 8;
+    const size_t slots_bytes = (n * sizeof(ResumeSlot) + 15) & ~(size_t)15, items_bytes = items.size() * sizeof(RoaringItem);
+    const size_t up_bytes = slots_bytes + items_bytes + (size_t)staging_bytes;
+    std::vector<unsigned long long> h(err_word + 2);
+    std::vector<std::unique_ptr<ah_filter>> fs(n);
+    for (size_t i = 0; i < n; i++) {
+        fs[i].reset(new ah_filter);
+        fs[i]->ix = ix;
+        fs[i]->len_bits = fb.len_bits;
+    }
+    std::vector<DevMem> blocks(n);
+    DevMem work, mixed;
+    for (size_t i = 0; i < n; i++) AH_HIP(dev_malloc(&blocks[i].p, fb.bytes));
+    if (gp.group > 1 && n > 1 && ix->n_nodes) AH_HIP(dev_malloc(&mixed.p, gp.mixed_bytes));  // (one filter: a pass on its own bitmap)
+    AH_HIP(dev_malloc(&work.p, counters_bytes + up_bytes));
+    ContextLease lease(ds);
+    AH_REQUIRE(lease.c, AH_ERR_DEVICE, "cannot create a HIP stream");
+    AH_TRY(lease.c->ensure_pinned(up_bytes));
+    hipStream_t s = lease.c->stream;
+    unsigned long long *d_counters = work.as<unsigned long long>();
+    uint8_t *d_up = work.as<uint8_t>() + counters_bytes;
+    const ResumeSlot *d_slots = reinterpret_cast<const ResumeSlot *>(d_up);
+    const RoaringItem *d_items = reinterpret_cast<const RoaringItem *>(d_up + slots_bytes);
+    const uint8_t *d_staging = d_up + slots_bytes + items_bytes;
+    {
+        uint8_t *pin = reinterpret_cast<uint8_t *>(lease.c->h_pinned);
+        ResumeSlot *slots = reinterpret_cast<ResumeSlot *>(pin);
+        for (size_t i = 0; i < n; i++) slots[i] = ResumeSlot{nullptr, 0, blocks[i].as<uint32_t>(), 0, 0, 0, 0};
+        if (!items.empty()) memcpy(pin + slots_bytes, items.data(), items_bytes);
+        uint8_t *staging = pin + slots_bytes + items_bytes;
+        for (const RoaringItem &it : items) {
+            const roaring::Container &k = parsed[it.filter][it.container];
+            memcpy(staging + it.payload, blobs[it.filter] + k.offset, (size_t)k.bytes);
+            const size_t pad = (size_t)(((k.bytes + 15) & ~(uint64_t)15) - k.bytes);
+            if (pad) memset(staging + it.payload + k.bytes, 0, pad);
+        }
+    }
+    AH_HIP(hipMemsetAsync(d_counters, 0, err_word * 8, s));
+    AH_HIP(hipMemsetAsync(d_counters + err_word, 0xFF, 16, s));  // (the error word: "nothing found")
+    for (size_t i = 0; i < n; i++) AH_HIP(hipMemsetAsync(blocks[i].p, 0, fb.bytes, s));
+    AH_HIP(hipMemcpyAsync(d_up, lease.c->h_pinned, up_bytes, hipMemcpyHostToDevice, s));
+    if (!items.empty())
+        hipLaunchKernelGGL(k_roaring_expand, dim3((uint32_t)items.size()), dim3(256), 0, s, d_items, d_staging, d_slots, fb.len_bits, d_counters,
+                           d_counters + err_word);
+    const bool count_rows = !ds->identity_ids && ds->n;  // identity ids: every bit below len_bits = n is a row
+    if (count_rows)
+        for (size_t y0 = 0; y0 < n; y0 += 65535)  // (blockIdx.y names the filter)
+            hipLaunchKernelGGL(k_filter_stored_rows_batch, dim3(grid_of(ds->n, 256, 256), (uint32_t)std::min<size_t>(n - y0, 65535)), dim3(256), 0, s,
+                               d_slots + y0, ds->view().ids, (uint64_t)ds->n, d_counters + RC_PER_FILTER * y0);
+    launch_leaf_kept_groups(ix, fb, gp, blocks, mixed, d_counters, s);
+    AH_HIP(hipGetLastError());
+    AH_HIP(hipMemcpyAsync(h.data(), d_counters, h.size() * 8, hipMemcpyDeviceToHost, s));
+    AH_HIP(hipStreamSynchronize(s));
+    if (h[err_word] != ~0ull) {
+        static const char *const kWhy[] = {"", "the array does not ascend strictly", "the bitmap's popcount is not the cardinality",
+                                           "the runs overlap or are out of order", "a run reaches past 65535",
+                                           "the runs' total length is not the cardinality"};
+        const unsigned reason = (unsigned)(h[err_word] & 0xFF);
+        AH_REQUIRE(false, AH_ERR_INVALID_ARGUMENT, "blobs[%llu]: container %llu: %s", h[err_word] >> 24, (h[err_word] >> 8) & 0xFFFF,
+                   reason < sizeof kWhy / sizeof kWhy[0] ? kWhy[reason] : "malformed");
+    }
+    // the hand-over: nothing below can fail
+    NoFailScope no_fail;
+    for (size_t i = 0; i < n; i++) {
+        const uint64_t inside = h[RC_TOTALS + RC_PER_FILTER * i + RC_LISTED];
+        filter_adopt(fs[i].get(), ix, blocks[i], fb, listed[i], count_rows ? h[RC_TOTALS + RC_PER_FILTER * i + RC_STORED] : inside,
+                     i == 0 ? n_groups : 0);
+        out[i] = fs[i].release();
+    }
+    st.leaves = h[RC_LEAVES], st.ids_walked = h[RC_IDS_WALKED];
+    if (out_stats) *out_stats = st;
+    return AH_OK;
+}
+
+int ah_filter_create_roaring_batch(ah_index *ix, const uint8_t *const *blobs, const size_t *lens, size_t n, ah_filter **out,
+                                   ah_filter_roaring_stats *out_stats) {
+    AH_GUARDED("ah_filter_create_roaring_batch")
+    return filter_create_roaring(ix, blobs, lens, n, out, out_stats);
+    AH_GUARDED_END
+}
+
+// The batch of one.
+int ah_filter_create_roaring(ah_index *ix, const uint8_t *bytes, size_t len, ah_filter **out) {
+    AH_GUARDED("ah_filter_create_roaring")
+    return filter_create_roaring(ix, &bytes, &len, 1, out, nullptr);
     AH_GUARDED_END
 }
 

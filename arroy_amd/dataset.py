@@ -27,6 +27,15 @@ def _ptr(a: Optional[np.ndarray]):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def _blob_u8(blob) -> np.ndarray:
+    """The bytes of a serialized bitmap where they lie (bytes, bytearray, memoryview, a contiguous uint8 array at any address)."""
+    if isinstance(blob, np.ndarray):
+        if blob.dtype != np.uint8 or not blob.flags.c_contiguous:
+            raise ValueError("a serialized bitmap as an array is contiguous uint8")
+        return blob.ravel()
+    return np.frombuffer(blob, dtype=np.uint8)
+
+
 def _update_rows(dimensions: int, up: np.ndarray, vectors) -> Optional[np.ndarray]:
     if up.size == 0:
         return None
@@ -598,6 +607,28 @@ class Index:
         h = C.c_void_p()
         _lib.check(_lib.lib().ah_filter_create_bitmap(self._h, _ptr(w) if w.size else None, int(n_bits), C.byref(h)))
         return Filter._adopt(self, h)
+
+    def make_filter_roaring(self, blob) -> "Filter":
+        """ah_filter_create_roaring: a resident filter from the bytes of one serialized RoaringBitmap (`serialize_into`; the
+        format: arroy_amd/roaring.py), expanded on the device.  Equal to make_filter of the ids the bitmap holds."""
+        a = _blob_u8(blob)
+        h = C.c_void_p()
+        _lib.check(_lib.lib().ah_filter_create_roaring(self._h, a.ctypes.data, a.size, C.byref(h)))
+        return Filter._adopt(self, h)
+
+    def make_filters_roaring(self, blobs):
+        """ah_filter_create_roaring_batch: one resident filter per serialized RoaringBitmap in ONE call — one upload, one
+        expansion launch, the per-node counts of up to FILTER_RESUME_GROUP filters in one pass over the ids of the forest.  All
+        or nothing.  -> (the filters, ah_filter_roaring_stats as a dict)."""
+        arrs = [_blob_u8(b) for b in blobs]
+        n = len(arrs)
+        ptrs = (C.c_void_p * max(1, n))(*[a.ctypes.data for a in arrs])
+        lens = (C.c_size_t * max(1, n))(*[a.size for a in arrs])
+        handles = (C.c_void_p * max(1, n))()
+        st = _lib.AhFilterRoaringStats()
+        _lib.check(_lib.lib().ah_filter_create_roaring_batch(self._h, ptrs, lens, n, handles, C.byref(st)))
+        filters = [Filter._adopt(self, C.c_void_p(handles[i])) for i in range(n)]
+        return filters, {k: int(getattr(st, k)) for k, _ in _lib.AhFilterRoaringStats._fields_}
 
     def combine_filters(self, op, filters, want_stats: bool = False):
         """ah_filter_combine: "and" / "or" / "andnot" (filters[0] minus the others) / "not" (one filter) of resident filters of

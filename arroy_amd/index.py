@@ -803,6 +803,15 @@ class Reader:
         Filters of one reader combine on the device with `&`, `|`, `-` and `~`."""
         return self._st.index.make_filter_bitmap(words, n_bits)
 
+    def make_filter_roaring(self, blob) -> "Filter":
+        """The same from the bytes of a serialized RoaringBitmap (`RoaringBitmap::serialize_into`): no walk over the ids on the
+        host, the containers are expanded on the device."""
+        return self._st.index.make_filter_roaring(blob)
+
+    def make_filters_roaring(self, blobs):
+        """One filter per serialized RoaringBitmap in one call -> (filters, stats): Index.make_filters_roaring."""
+        return self._st.index.make_filters_roaring(blobs)
+
 
 class QueryBuilder:
     """`QueryBuilder` (src/reader.rs:26-124)."""
@@ -822,8 +831,10 @@ class QueryBuilder:
         return self
 
     def candidates(self, ids) -> "QueryBuilder":
-        """An iterable of item ids, or a `Filter` of this reader's index (`Reader.make_filter`) kept across queries."""
-        self._candidates = ids if isinstance(ids, Filter) else set(int(i) for i in ids)
+        """An iterable of item ids, a `Filter` of this reader's index (`Reader.make_filter`) kept across queries, or the bytes
+        of a serialized RoaringBitmap (bytes / bytearray / memoryview: `Reader.make_filter_roaring` for this query, closed
+        after it)."""
+        self._candidates = ids if isinstance(ids, (Filter, bytes, bytearray, memoryview)) else set(int(i) for i in ids)
         return self
 
     def by_item(self, item: ItemId) -> Optional[List[Tuple[int, float]]]:  # src/reader.rs:46-51
@@ -842,9 +853,16 @@ class QueryBuilder:
         r, st = self._r, self._r._st
         if r.is_empty():
             return []
-        res = st.index.search(self._count, queries=None if vector is None else vector[None, :],
-                              items=None if item is None else [item],
-                              search_k=0 if self._search_k is None else self._search_k,
-                              oversampling=0 if self._oversampling is None else self._oversampling,
-                              candidates=self._candidates)
+        cand, own = self._candidates, None
+        if isinstance(cand, (bytes, bytearray, memoryview)):  # a serialized RoaringBitmap: a filter for this query alone
+            cand = own = st.index.make_filter_roaring(cand)
+        try:
+            res = st.index.search(self._count, queries=None if vector is None else vector[None, :],
+                                  items=None if item is None else [item],
+                                  search_k=0 if self._search_k is None else self._search_k,
+                                  oversampling=0 if self._oversampling is None else self._oversampling,
+                                  candidates=cand)
+        finally:
+            if own is not None:
+                own.close()
         return res[0]

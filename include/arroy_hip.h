@@ -833,6 +833,43 @@ AH_API int ah_filter_resume_batch(ah_filter *const *filters, const ah_filter_edi
 /* Suspended filters of the index: a level, like filters_alive. */
 AH_API int ah_index_filters_suspended(ah_index *index, uint64_t *out);
 
+/* Filters from serialized RoaringBitmaps (ABI v7 addition: look the symbols up).  `QueryBuilder::candidates` takes a
+ * `&RoaringBitmap`; what `RoaringBitmap::serialize_into` writes becomes a resident filter without the host walking the ids or
+ * expanding a dense bitmap: the headers are parsed on the host (O(containers)), the container payloads travel in one copy
+ * and are expanded on the device, and the per-node counts of up to AH_FILTER_RESUME_GROUP filters are made in ONE pass over
+ * the Descendants ids, as in ah_filter_resume_batch (a pass per filter where the id range is too long for that: there).
+ * Accepted: the portable Roaring serialisation, little-endian, at any byte address —
+ *   u32 cookie    12346 (no run containers; what roaring 0.10 writes), then u32 nc; or low 16 bits 12347, nc = (cookie >> 16) + 1,
+ *                 then ceil(nc / 8) bytes of run flags (bit i & 7 of byte i >> 3: container i is a run container)
+ *   nc x (u16 key, u16 cardinality - 1), keys strictly ascending
+ *   nc x u32 byte offset from the start of the blob: always with 12346, with 12347 only when nc >= 4
+ *   the containers in key order, back to back: run (u16 n_runs, n_runs x (u16 start, u16 length - 1)), array (cardinality
+ *   <= 4096: ascending u16) or bitmap (8192 bytes, bit v & 63 of 64-bit word v >> 6)
+ * Filter i is, bit for bit, the filter ah_filter_create makes from the ascending list of the ids blob i holds: the same
+ * length, bitmap, per-node counts and `stored`; `listed` is the bitmap's cardinality, ids above the largest stored id
+ * included.  Ids that are not stored are legal and match nothing; containers wholly above the largest stored id never
+ * travel.  The filters are immutable and independent of each other and of the blobs, which are not used after return.
+ * All or nothing: on any failure no filter exists, no counter has moved, nothing is held and every out[i] is NULL.  On
+ * success filters_created and filters_alive rise by n, leaf_kept_passes by `groups` (an index with nodes).  n == 0 is AH_OK.
+ * May run next to searches; not concurrent with maintenance of the same index.  Refused (AH_ERR_INVALID_ARGUMENT, the blob and,
+ * where there is one, the container named), from the headers alone and in this order: out NULL, blobs / lens NULL, a NULL
+ * blob, a blob shorter than its headers, an unknown cookie, keys that do not ascend strictly, a container past `len`, an
+ * offset entry that disagrees with the sizes, `len` that is not the end of the last container; then what ah_filter_create
+ * refuses about the index; then, found on the device in the containers that travelled (the lowest (blob, container) is the
+ * one named): an array that does not ascend strictly, a bitmap container whose popcount is not its cardinality, runs that
+ * overlap, are out of order or reach past 65535, runs whose total length is not the cardinality. */
+typedef struct ah_filter_roaring_stats {
+    uint64_t filters, groups;        /* groups = passes over the Descendants ids: ceil(filters / AH_FILTER_RESUME_GROUP), or */
+                                     /* `filters` where the id range is too long for grouped passes (ah_filter_resume_batch) */
+    uint64_t array_containers, bitmap_containers, run_containers;   /* expanded on the device                              */
+    uint64_t skipped_containers;     /* key wholly above the largest stored id: never uploaded                             */
+    uint64_t bytes_uploaded;         /* container payload bytes that travelled                                             */
+    uint64_t leaves, ids_walked;     /* as ah_filter_resume_stats                                                          */
+} ah_filter_roaring_stats;
+AH_API int ah_filter_create_roaring(ah_index *index, const uint8_t *bytes, size_t len, ah_filter **out);
+AH_API int ah_filter_create_roaring_batch(ah_index *index, const uint8_t *const *blobs, const size_t *lens, size_t n,
+                                          ah_filter **out /* n handles */, ah_filter_roaring_stats *out_stats /* may be NULL */);
+
 /* Incremental insert routing, `insert_items_in_descendants_from_frozen_reader` (src/writer.rs:1398-1459), for
  * every tree of the index at once: each of the `n` items (they must already be rows of the index's dataset — the
  * reference also re-creates `ImmutableLeafs` over all current items for every build, src/writer.rs:530) walks from
