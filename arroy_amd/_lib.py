@@ -208,6 +208,12 @@ class AhFilterRoaringStats(C.Structure):
                                           "skipped_containers", "bytes_uploaded", "leaves", "ids_walked")]
 
 
+class AhIndexDecodeStats(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("values", "split_values", "normals", "descendants_values", "ids", "containers_array",
+                                          "containers_bitmap", "containers_run", "wave_values", "block_containers", "bytes_staged",
+                                          "chunks")] + [("seconds_total", C.c_double), ("seconds_host_copy", C.c_double)]
+
+
 class AhStreamNode(C.Structure):
     _fields_ = [("id", C.c_uint32), ("tree", C.c_uint32), ("kind", C.c_uint8), ("has_normal", C.c_uint8), ("reserved", C.c_uint16),
                 ("left", C.c_uint32), ("right", C.c_uint32), ("count", C.c_uint32), ("depth", C.c_uint32),
@@ -284,6 +290,9 @@ SIGNATURES = {
     "ah_forest_destroy": (C.c_int, [_VP]),
     "ah_index_create": (C.c_int, [_VP, _VP, C.POINTER(C.c_void_p)]),
     "ah_index_create_from_view": (C.c_int, [_VP, C.POINTER(AhForestView), C.POINTER(C.c_void_p)]),
+    # a resident index from the NodeCodec bytes LMDB stores
+    "ah_index_create_from_encoded": (C.c_int, [_VP, _U32P, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_size_t, _U32P, C.c_uint32,
+                                               C.POINTER(C.c_void_p), C.POINTER(AhIndexDecodeStats)]),
     "ah_index_destroy": (C.c_int, [_VP]),
     "ah_search_batch": (C.c_int, [_VP, _F32P, _U32P, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, _U32P, C.c_size_t,
                                   C.c_int, _U32P, _F32P, _U32P]),

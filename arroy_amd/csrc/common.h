@@ -186,6 +186,7 @@ inline int guarded(const char *what, F &&f) noexcept {
     X(FILTER_COMBINE_SHORTCUT, "AH_FILTER_COMBINE_SHORTCUT", 1) /* 0: ah_filter_combine walks the ids of every leaf against the new bitmap, never derives a leaf's count from the operands' counts (DESIGN.md 4 "Combined filters") */ \
     X(FILTER_RESUME_GROUP, "AH_FILTER_RESUME_GROUP", 16) /* ah_filter_resume_batch: filters one pass over the Descendants ids counts for, 1 .. 16 (the header's AH_FILTER_RESUME_GROUP); 1: a pass per filter, what the measurement compares with (DESIGN.md 4 "Filters across index maintenance") */ \
     X(FILTER_RESUME_MIXED_MB, "AH_FILTER_RESUME_MIXED_MB", 256) /* ah_filter_resume_batch: most MiB for a group's bitmaps laid side by side (64 bytes per 32 ids of the id range); above it the counts are made a filter a pass */ \
+    X(DECODE_CHUNK_BYTES, "AH_DECODE_CHUNK_BYTES", 64 << 20) /* ah_index_create_from_encoded: bytes of values (in whole 16-byte units) one staged chunk holds; never below the largest value (DESIGN.md 4 "Opening a resident index from encoded nodes") */ \
     X(AUDIT_COVER_MB, "AH_AUDIT_COVER_MB", 64) /* ah_index_audit: budget for the coverage words (one bit per row and tree) of the trees audited in one pass, MiB; 0: one tree a pass (not measured: DESIGN.md 4 "Audit of a resident index") */ \
     X(HOST_THREADS, "AH_HOST_THREADS", 8)     /* host threads one build may use at a time for its output path */        \
     X(DEVICE_CACHE_MB, "AH_DEVICE_CACHE_MB", 98304) /* idle HBM the caching allocator keeps while a dataset lives on the device */ \

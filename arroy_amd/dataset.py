@@ -593,6 +593,31 @@ class Index:
         else:
             _lib.check(_lib.lib().ah_index_create(dataset._h, forest._h, C.byref(self._h)))
 
+    @classmethod
+    def from_encoded(cls, dataset: Dataset, node_ids, values, roots, want_stats: bool = False):
+        """ah_index_create_from_encoded: a resident index from the `NodeCodec` values LMDB stores for the tree nodes, as a
+        cursor over the tree keys yields them — `node_ids` strictly ascending, `values[i]` the bytes of node_ids[i] (bytes or
+        a uint8 array, at any address), `roots` the root node ids.  The values are decoded on the device; node i of the index
+        is the value of the i-th id.  Returns the index, with want_stats (index, ah_index_decode_stats as a dict)."""
+        ids = _u32(node_ids)
+        arrs = [_blob_u8(v) for v in values]
+        if len(arrs) != ids.size:
+            raise ValueError(f"{len(arrs)} values for {ids.size} node ids")
+        rt = _u32(roots)
+        n = len(arrs)
+        ptrs = (C.c_void_p * max(1, n))(*[a.ctypes.data for a in arrs])
+        lens = (C.c_size_t * max(1, n))(*[a.size for a in arrs])
+        self = cls.__new__(cls)
+        self.dataset = dataset
+        self._h = C.c_void_p()
+        self._filters = weakref.WeakSet()
+        st = _lib.AhIndexDecodeStats()
+        _lib.check(_lib.lib().ah_index_create_from_encoded(dataset._h, _ptr(ids) if n else None, ptrs, lens, n,
+                                                           _ptr(rt) if rt.size else None, int(rt.size), C.byref(self._h), C.byref(st)))
+        if not want_stats:
+            return self
+        return self, {k: (float if k.startswith("seconds") else int)(getattr(st, k)) for k, _ in _lib.AhIndexDecodeStats._fields_}
+
     def make_filter(self, ids, sorted: bool = False) -> "Filter":
         """ah_filter_create: `QueryBuilder::candidates` as an object resident on the device, for any number of searches.
         sorted=True: `ids` is already an ascending array of distinct ids (what a RoaringBitmap iterates)."""

@@ -54,7 +54,7 @@ extern "C" {
                                   v7 additions: updates of a finalized dataset (ah_dataset_update_vectors / _records,
                                   ah_group_update_vectors / _records, the test aid ah_debug_update_paths);
                                   ah_index_footprint_get / ah_index_compact; ah_index_audit / ah_forest_view_audit;
-                                  ah_index_drop_trees */
+                                  ah_index_drop_trees; ah_index_create_from_encoded */
 
 /* every entry point is exported from the shared object (it is built with -fvisibility=hidden) */
 #if defined(__GNUC__)
@@ -1181,6 +1181,43 @@ typedef struct ah_index_audit_report {
 
 AH_API int ah_index_audit(ah_index *index, ah_index_audit_report *out, ah_tree_stats *out_trees);
 AH_API int ah_forest_view_audit(ah_dataset *ds, const ah_forest_view *view, ah_index_audit_report *out, ah_tree_stats *out_trees);
+
+/* A resident index from the bytes LMDB stores for the tree nodes (ABI v7 addition: look the symbol up).  A process that opens
+ * an existing database (`Reader::open`) passes the `(key, value)` pairs of its cursor over the tree keys straight through:
+ * node_ids[i] is the node id of the key, values[i] / lens[i] the `NodeCodec` value (src/node.rs:229-241) as it lies in the
+ * map, at any byte address.  The host copies the values into pinned memory in chunks and reads none of their bytes; they
+ * are measured, linked, unpacked and expanded on the device.
+ *   split node    9 bytes (`normal: None`) or 9 + ah_header_size + ah_vector_size: [2][left u32 BE][right u32 BE][header][vector]
+ *   Descendants   [1] + what `RoaringBitmap::deserialize_from` accepts: the serialisation ah_filter_create_roaring documents,
+ *                 cookie 12346 or 12347 (run containers, the offset header from 4 containers on)
+ * Only these v0.7 layouts are read; tag 0 (an item) and unknown tags are refused.
+ * node_ids ascend strictly (the order the cursor yields); node i of the index is the value of the i-th id, and every left,
+ * right and root id is replaced by its rank among node_ids.  The index is, array for array under ah_index_export /
+ * ah_index_export_info / ah_index_footprint_get, the index ah_index_create_from_view makes of the decoded view: children
+ * and roots as ranks, the descendants concatenated in node order, the normal rows in node order.  Nodes no root reaches are
+ * legal, as in a view.  Values and arrays are not retained.  n_nodes == 0 with n_trees == 0 gives a legal empty index.
+ * All or nothing: on any error nothing stays allocated and *out is NULL.  May run while other indexes of the dataset
+ * serve searches.
+ * Refused (AH_ERR_INVALID_ARGUMENT; the node id and the reason in ah_last_error, the smallest node position when several
+ * values are bad): a NULL argument, node_ids that do not ascend strictly, a value that is empty or whose tag is neither 1 nor
+ * 2, a split value of any other length, a Descendants value shorter than its headers, an unknown cookie, keys that do not
+ * ascend strictly, a container past the end, an offset entry that disagrees with the sizes, bytes behind the last
+ * container; a child or root id that is not among node_ids; an array container that does not ascend strictly, a bitmap
+ * container whose popcount is not its cardinality, runs that overlap, are out of order or reach past 65535, runs whose
+ * total length is not the cardinality; a node reachable twice, 2^32 - 1 or more nodes or ids.  A dataset that is not
+ * finalized: AH_ERR_NOT_FINALIZED.
+ * AH_DECODE_CHUNK_BYTES (tunable, default 64 MiB): the bytes of values one staged chunk holds, never below the largest value. */
+typedef struct ah_index_decode_stats {
+    uint64_t values, split_values, normals, descendants_values, ids;
+    uint64_t containers_array, containers_bitmap, containers_run;
+    uint64_t wave_values, block_containers;   /* which expansion path served what: Descendants values a wavefront expanded, */
+                                              /* containers of the values a block expanded (bitmap / run containers among them) */
+    uint64_t bytes_staged, chunks;            /* descriptors and values in whole 16-byte units; uploads                      */
+    double seconds_total, seconds_host_copy;
+} ah_index_decode_stats;
+AH_API int ah_index_create_from_encoded(ah_dataset *ds, const uint32_t *node_ids, const uint8_t *const *values, const size_t *lens,
+                                        size_t n_nodes, const uint32_t *root_ids, uint32_t n_trees, ah_index **out,
+                                        ah_index_decode_stats *out_stats /* may be NULL */);
 
 /* An index outlives an update of its dataset.  An ah_index stores ITEM IDS, never row positions — its descendants are a
  * copy of the view's ids and every kernel goes from an id to its row through the dataset as it is at the time of the
