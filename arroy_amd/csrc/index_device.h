@@ -1,5 +1,5 @@
-// index_device.h — what search.hip (the searches and the routing of an ah_index), index_update.hip (its deletes, inserts,
-// grafts, compaction, export, suspend / resume) and index_audit.hip (its audit) share.  Device side: the node record and the
+// index_device.h — what search.hip (the searches and the routing of an ah_index), filter.hip (its resident filters),
+// index_update.hip (its deletes, inserts, grafts, compaction, export, suspend / resume) and index_audit.hip (its audit) share.  Device side: the node record and the
 // id-list -> bitmap kernel.  Host side: the index handle, the two conversions between the ABI's ah_node and the node record,
 // and the scaffolding of a maintenance call — IndexCall (device, stream lease, launch span, phase clock), for_spans,
 // read_back, and IndexCommit / index_commit, the one place where new arrays are swapped into an index and its normals view

@@ -32,7 +32,7 @@ enum Reason : uint32_t {
     R_OFFSET,        // an offset entry that disagrees with the sizes
     R_TRAILING,      // bytes behind the last container
     R_TOO_MANY_IDS,  // more ids than a 32-bit count holds
-    // the content of the containers, in the order of RoaringReason (search.hip)
+    // the content of the containers, in the order of RoaringReason (filter.hip)
     R_ARRAY_ORDER,
     R_BITMAP_CARDINALITY,
     R_RUN_ORDER,

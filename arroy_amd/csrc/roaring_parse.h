@@ -1,7 +1,7 @@
 // The headers of one serialized RoaringBitmap (the portable serialisation, little-endian), read on the host: which containers
 // the blob holds and where their payloads lie.  No HIP, no allocation beyond the descriptor vector, O(containers) — never a
 // walk over ids.  Every byte is read through memcpy, so a blob may start at any address.  ah_filter_create_roaring_batch
-// (search.hip) parses with this and expands the payloads on the device (k_roaring_expand), which checks their content;
+// (filter.hip) parses with this and expands the payloads on the device (k_roaring_expand), which checks their content;
 // tests/roaring_parse_check.cpp runs it under AddressSanitizer / UBSan over prefixes and mutations of a valid corpus.
 //
 //   u32 cookie   12346: no run containers; then u32 nc

@@ -15,7 +15,7 @@ import functools
 import numpy as np
 import pytest
 
-from arroy_amd import Index, _lib, shard
+from arroy_amd import Index, _lib, roaring, shard
 from arroy_amd import Dataset
 from arroy_amd import distances as D
 from test_filter_combine_cpu import AND, ANDNOT, NOT, OR, WALK, derive
@@ -426,3 +426,87 @@ def test_combine_and_create_bitmap_survive_every_allocation_failure():
     finally:
         _lib.tuning_set("AH_FAIL_ALLOC_AFTER", 0)
         w.close()
+
+
+# ---- one block layout, one counter layout: the five ways to make a filter agree -----------------------------------------------
+# (name, rows, largest id or None for identity ids, trees).  The bitmap of a block is padded to 2048 bits, and the counters of a
+# call sit 8-byte aligned behind n_nodes 32-bit counts: len_bits one bit short of and one bit into a second 2048-bit span,
+# identity and sparse, each with an even and an odd n_nodes.  A tree of L leaves has 2L - 1 nodes, so the parity of n_nodes is
+# that of the number of trees and no item count changes it: two trees for the even worlds, three for the odd ones.
+LAYOUT_WORLDS = [("id2048", 2048, None, 2), ("id2049", 2049, None, 3), ("sp4095", 600, 4095, 3), ("sp4096", 600, 4096, 2)]
+
+
+def fresh(make):
+    """make() on an empty allocator cache: its first block is a new one, as large as the allocator rounds what was asked for."""
+    _lib.device_cache_trim()
+    return make()
+
+
+def test_the_five_creators_lay_out_one_filter():
+    """The same id set through ah_filter_create, ah_filter_create_bitmap, ah_filter_combine (OR of two halves),
+    ah_filter_create_roaring and ah_filter_suspend + ah_filter_resume_batch (another set, edited into this one): identical
+    ah_filter_export (bits, per-node counts) and identical ah_filter_info.  `device_bytes` is also held against the layout itself
+    (bitmap words rounded to 64, n_nodes counts, 256 bytes, as the allocator rounds a fresh block: every creator starts from an
+    empty allocator cache).  One exception, as everywhere in this module: of listed ids ABOVE the largest stored id, which no
+    bitmap holds, the list, the host bitmap and the Roaring blob count in `listed` what they were given, an expression and a
+    resume the bits they set — so `listed` is compared across all five for the set without such ids, and held to each
+    creator's own rule for the set with them."""
+    parities = {five_creators_agree(*w) for w in LAYOUT_WORLDS}
+    assert parities == {0, 1}, f"n_nodes of the layout worlds: parities {parities}"
+
+
+def five_creators_agree(name, n, top, trees):
+    """-> n_nodes % 2 of the world's index."""
+    rng = np.random.default_rng(5)
+    sparse = top is not None
+    ids = np.arange(n, dtype=np.uint32)
+    if sparse:  # ascending, id % 6 in {0, 1, 2}: id + 3 is never stored
+        ids = (np.arange(n, dtype=np.uint32) * 6 + np.arange(n, dtype=np.uint32) % 3).astype(np.uint32)
+        ids[-1] = top
+    len_bits = int(ids[-1]) + 1
+    ds = Dataset(D.Euclidean, 8, n)
+    ds.upload_vectors(ids, rng.standard_normal((n, 8)).astype(np.float32))
+    ds.finalize()
+    forest = ds.build_forest(shard.tree_seeds(5, range(trees)), split_after=SPLIT_AFTER)
+    index = ds.create_index(forest)
+    try:
+        n_nodes = index.export_info()["n_nodes"]
+        words = ((len_bits + 31) // 32 + 63) // 64 * 64
+        want_bytes = (words * 4 + n_nodes * 4 + 256 + 4095) // 4096 * 4096
+        gaps = (ids[1:-1:4] + np.uint32(3)) if sparse else np.zeros(0, np.uint32)  # (in the gaps: listed, never stored)
+        inside = np.union1d(np.union1d(ids[::2], ids[-1:]), gaps).astype(np.uint32)  # the largest stored id is in the set
+        above = (len_bits + np.array([0, 4, 70000])).astype(np.uint32)
+        other = np.union1d(ids[::3], (ids[2:-1:5] + np.uint32(3)) if sparse else ids[:0]).astype(np.uint32)  # what the resume starts from
+        for what, want in (("inside", inside), ("with ids above", np.concatenate([inside, above]))):
+            n_in = int(inside.size)
+            made = {}
+            made["list"] = fresh(lambda: index.make_filter(want, sorted=True))
+            n_bits = int(want[-1]) + 1
+            made["bitmap"] = fresh(lambda: index.make_filter_bitmap(bitmap_of(want, n_bits), n_bits))
+            halves = [index.make_filter(want[0::2], sorted=True), index.make_filter(want[1::2], sorted=True)]
+            made["or"] = fresh(lambda: index.combine_filters("or", halves))
+            made["roaring"] = fresh(lambda: index.make_filter_roaring(roaring.serialize(want)))
+            made["resume"] = index.make_filter(other, sorted=True)
+            made["resume"].suspend()
+            fresh(lambda: index.resume_filters([made["resume"]], [(np.setdiff1d(other, want), np.setdiff1d(want, other))], edits_sorted=True))
+            listed_rule = {"list": want.size, "bitmap": want.size, "roaring": want.size, "or": n_in, "resume": n_in}
+            ref_e, ref_i = made["list"].export(), made["list"].info()
+            assert ref_e["len_bits"] == len_bits and ref_i["stored"] == int(np.isin(inside, ids).sum()), (what, ref_i)
+            assert popcount(ref_e["bits"]) == n_in and ref_i["device_bytes"] == want_bytes, (what, ref_i, want_bytes)
+            for how, f in made.items():
+                e, i = f.export(), f.info()
+                print(name, what, how, i, "n_nodes", n_nodes)
+                assert e["len_bits"] == len_bits, (what, how)
+                assert np.array_equal(e["bits"], ref_e["bits"]), (what, how)
+                assert np.array_equal(e["leaf_kept"], ref_e["leaf_kept"]), (what, how)
+                assert (i["stored"], i["device_bytes"]) == (ref_i["stored"], ref_i["device_bytes"]), (what, how, i, ref_i)
+                assert i["listed"] == listed_rule[how], (what, how, i)
+                if what == "inside":
+                    assert i == ref_i, (how, i, ref_i)
+            for f in list(made.values()) + halves:
+                f.close()
+        return n_nodes % 2
+    finally:
+        index.close()
+        forest.close()
+        ds.close()
