@@ -1,5 +1,5 @@
-// api.hip — the C ABI (include/arroy_hip.h): dataset staging, search-side and split-side entry points.
-// The forest build lives in forest.hip.  Host code only orchestrates: every arithmetic result comes from
+// api.hip — the C ABI (include/arroy_hip.h): the runtime, the life cycle of datasets and groups, search-side and split-side
+// entry points.  Staging lives in stage.hip, the forest build in forest.hip.  Host code only orchestrates: every arithmetic result comes from
 // a HIP kernel; there is no CPU fallback.
 #include <algorithm>
 #include <atomic>
@@ -7,7 +7,6 @@
 #include <cmath>
 #include <condition_variable>
 #include <functional>
-#include <immintrin.h>
 #include <new>
 #include <thread>
 #include <array>
@@ -579,7 +578,7 @@ void Context::destroy() {
     stream = nullptr;
 }
 
-// The host side of staging is a gather of records out of (unaligned) storage pages into pinned memory; one core
+// The host side of staging (stage.hip) is a gather of records out of (unaligned) storage pages into pinned memory; one core
 // cannot keep a PCIe Gen5 link busy (a 32 MiB chunk takes 0.6 ms on the wire), so chunks are spread over a small
 // process-wide pool of persistent workers (spawning threads per chunk costs as much as the copy itself).
 class WorkerPool {
@@ -671,47 +670,20 @@ class WorkerPool {
     bool stop_ = false;
 };
 
-// Row copy into the pinned ring with non-temporal stores: the ring is written once and read by the DMA engine, so the
-// destination lines need not be read for ownership nor kept in the host caches (a plain memcpy of 3 KB rows moves 3 bytes
-// per byte staged; this moves 2).  `dst` is 32-byte aligned (ring rows start on 128-byte lines), `src` is arbitrary —
-// LMDB hands out vectors at odd offsets (src/parallel.rs:296-311).
-__attribute__((target("avx2"))) static void copy_row_stream_avx2(uint8_t *dst, const uint8_t *src, size_t bytes) {
-    size_t i = 0;
-    for (; i + 128 <= bytes; i += 128) {
-        const __m256i a = _mm256_loadu_si256(reinterpret_cast<const __m256i *>(src + i));
-        const __m256i b = _mm256_loadu_si256(reinterpret_cast<const __m256i *>(src + i + 32));
-        const __m256i c = _mm256_loadu_si256(reinterpret_cast<const __m256i *>(src + i + 64));
-        const __m256i d = _mm256_loadu_si256(reinterpret_cast<const __m256i *>(src + i + 96));
-        _mm256_stream_si256(reinterpret_cast<__m256i *>(dst + i), a);
-        _mm256_stream_si256(reinterpret_cast<__m256i *>(dst + i + 32), b);
-        _mm256_stream_si256(reinterpret_cast<__m256i *>(dst + i + 64), c);
-        _mm256_stream_si256(reinterpret_cast<__m256i *>(dst + i + 96), d);
-    }
-    for (; i + 32 <= bytes; i += 32)
-        _mm256_stream_si256(reinterpret_cast<__m256i *>(dst + i), _mm256_loadu_si256(reinterpret_cast<const __m256i *>(src + i)));
-    if (i < bytes) memcpy(dst + i, src + i, bytes - i);
-}
-static inline void copy_row(uint8_t *dst, const uint8_t *src, size_t bytes) {
-    static const bool avx2 = __builtin_cpu_supports("avx2");
-    if (avx2 && !tun(TUN_STAGE_MEMCPY) && bytes >= 512 && (reinterpret_cast<uintptr_t>(dst) & 31u) == 0) copy_row_stream_avx2(dst, src, bytes);
-    else memcpy(dst, src, bytes);
-}
-static inline void copy_fence() { _mm_sfence(); }  // non-temporal stores are ordered before the DMA is enqueued
-
-// rows / ids worth a thread: below ~2 MiB in total the copy runs inline (waking workers costs more than it saves)
-template <typename F>
-static void parallel_rows(size_t n, size_t bytes_per_item, F &&fn) {
+// fn(arg, lo, hi) over slices of [0, n): rows / ids worth a thread; below ~2 MiB in total the copy runs inline (waking workers
+// costs more than it saves)
+void parallel_rows_run(size_t n, size_t bytes_per_item, void (*fn)(void *, size_t, size_t), void *arg) {
     WorkerPool &pool = WorkerPool::get();
     const size_t total = n * bytes_per_item;
     const size_t parts = total < (2u << 20) ? 1 : std::min<size_t>(pool.size(), total >> 19);
     if (parts <= 1) {
-        fn((size_t)0, n);
+        fn(arg, 0, n);
         return;
     }
     const size_t per = (n + parts - 1) / parts;
     pool.run(parts, [&](size_t p) {
         const size_t lo = p * per, hi = std::min(n, lo + per);
-        if (lo < hi) fn(lo, hi);
+        if (lo < hi) fn(arg, lo, hi);
     });
 }
 
@@ -936,7 +908,6 @@ int ah_dataset_create(int metric, uint32_t dimensions, uint64_t capacity, int de
     AH_GUARDED_END
 }
 
-static int upload_flush(ah_dataset *ds);
 static int finalize_impl(ah_dataset *ds);
 static int preprocess_dot_impl(ah_dataset *ds, float *out_max_norm);
 
@@ -946,7 +917,7 @@ int ah_dataset_destroy(ah_dataset *ds) {
     AH_REQUIRE(!ds->group_member, AH_ERR_INVALID_ARGUMENT, "the dataset is a member of a device group (ah_group_destroy frees it)");
     NoFailScope no_fail;
     ds->join_reserve();
-    (void)upload_flush(ds);
+    (void)flush_staging(ds);
     (void)hipSetDevice(ds->device);
     (void)hipDeviceSynchronize();
     if (ds->up_ctx) {
@@ -987,308 +958,6 @@ int ah_dataset_destroy(ah_dataset *ds) {
     delete ds;
     if (counted) dataset_gone(device);  // the last dataset of the device / the process: the caches go back (common.h)
     return AH_OK;
-    AH_GUARDED_END
-}
-
-static int check_ids(ah_dataset *ds, const uint32_t *item_ids, size_t n) {
-    AH_REQUIRE(!ds->finalized, AH_ERR_INVALID_ARGUMENT, "dataset already finalized");
-    AH_REQUIRE(item_ids || n == 0, AH_ERR_INVALID_ARGUMENT, "item_ids is NULL");
-    AH_REQUIRE(ds->n + n <= ds->capacity, AH_ERR_INVALID_ARGUMENT, "upload of %zu items exceeds capacity %llu", n,
-               (unsigned long long)ds->capacity);
-    for (size_t i = 0; i < n; i++) {
-        const bool first = ds->n == 0 && i == 0;
-        const uint32_t prev = i == 0 ? ds->last_id : item_ids[i - 1];
-        AH_REQUIRE(first || item_ids[i] > prev, AH_ERR_INVALID_ARGUMENT,
-                   "item ids must be strictly ascending (id %u after %u)", item_ids[i], prev);
-    }
-    return AH_OK;
-}
-static int check_append(ah_dataset *ds, const uint32_t *item_ids, size_t n) {
-    AH_REQUIRE(ds, AH_ERR_INVALID_ARGUMENT, "dataset is NULL");
-    AH_REQUIRE(!ds->group_member, AH_ERR_INVALID_ARGUMENT, "the dataset is a member of a device group: stage through ah_group_upload_*");
-    return check_ids(ds, item_ids, n);
-}
-
-// room for n more ids in the host mirror, grown geometrically; called before a group's uploads touch any member, so that
-// note_ids (which then allocates nothing) cannot leave one member's ids recorded and another's not
-static void reserve_ids(ah_dataset *ds, size_t n) {
-    const size_t need = ds->h_ids.size() + n;
-    if (ds->h_ids.capacity() < need) ds->h_ids.reserve(std::max(need, 2 * ds->h_ids.capacity()));
-}
-
-static void note_ids(ah_dataset *ds, const uint32_t *item_ids, size_t n) {
-    for (size_t i = 0; i < n; i++) {
-        if (item_ids[i] != (uint32_t)(ds->n + i)) ds->identity_ids = false;
-        ds->h_ids.push_back(item_ids[i]);
-    }
-    if (n) ds->last_id = item_ids[n - 1];
-    ds->n += n;
-}
-
-// ---- staging ring ---------------------------------------------------------------------------------------------------
-// Uploads are asynchronous until ah_dataset_finalize: the dataset keeps one Context (stream + pinned ring of kRing
-// buffers) for all its upload calls; a call returns once its records are COPIED OUT of the caller's pages (the contract:
-// no host pointer is used after return) while the last DMA transfers may still be in flight.  The host-side gather of a
-// chunk is spread over the worker pool (one core cannot keep a PCIe Gen5 link busy), chunk c+1 is gathered while chunk c
-// and c-1 travel.
-static constexpr int kRing = 3;
-static constexpr size_t kStageBytes = 32u << 20;
-
-static int upload_flush(ah_dataset *ds) {
-    std::lock_guard<std::mutex> lk(ds->up_mu);  // (several threads replicating one unfinalized source flush it together)
-    if (!ds->up_ctx) return AH_OK;
-    Context *c = ds->up_ctx;
-    const hipError_t e = hipStreamSynchronize(c->stream);
-    ds->up_ctx = nullptr;
-    for (bool &u : ds->up_used) u = false;
-    ds->up_buf = 0;
-    ds->release(c);
-    if (e != hipSuccess) {
-        set_error("staging copy failed: %s", hipGetErrorString(e));
-        set_error_status(AH_ERR_DEVICE);
-        return AH_ERR_DEVICE;
-    }
-    return AH_OK;
-}
-
-// the dataset's upload context with a pinned ring of kRing x buf_bytes (grown only when idle)
-static int upload_context(ah_dataset *ds, size_t buf_bytes, Context **out) {
-    AH_HIP(hipSetDevice(ds->device));
-    if (!ds->up_ctx) {
-        ds->up_ctx = ds->acquire();
-        AH_REQUIRE(ds->up_ctx, AH_ERR_DEVICE, "cannot create a HIP stream");
-    }
-    Context *c = ds->up_ctx;
-    for (hipEvent_t &e : c->ev_ring)
-        if (!e) AH_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    if (c->h_cap < (size_t)kRing * buf_bytes) {
-        AH_HIP(hipStreamSynchronize(c->stream));  // the old ring may still be a DMA source
-        for (bool &u : ds->up_used) u = false;
-        AH_TRY(c->ensure_pinned((size_t)kRing * buf_bytes));
-    }
-    *out = c;
-    return AH_OK;
-}
-
-// One chunk of an upload in a pinned slot, and the two steps every chunk takes: the gather out of the caller's pages
-// (once, whatever the number of datasets it goes to — ah_group_upload_*) and the send to one dataset on one of its streams.
-struct RecordSlot {  // stored records: rows re-pitched to whole lines, headers and ids apart
-    uint8_t *rows, *hdr, *ids;
-    RecordSlot(uint8_t *base, size_t chunk, size_t rb, size_t hs)
-        : rows(base), hdr(base + pad256(chunk * rb)), ids(base + pad256(chunk * rb) + pad256(chunk * hs)) {}
-    static size_t bytes(size_t chunk, size_t rb, size_t hs) { return pad256(chunk * rb) + pad256(chunk * hs) + pad256(chunk * 4); }
-};
-static int gather_records(const RecordSlot &slot, const uint8_t *const *record_ptrs, const uint32_t *item_ids, size_t c,
-                          size_t rb, size_t hs, size_t vs, size_t first_index) {
-    for (size_t i = 0; i < c; i++) {
-        const uint8_t *rec = record_ptrs[i];
-        AH_REQUIRE(rec && rec[0] == 0, AH_ERR_INVALID_ARGUMENT, "record %zu is not a leaf (tag %d)", first_index + i,
-                   rec ? rec[0] : -1);
-    }
-    parallel_rows(c, rb + hs, [&](size_t lo, size_t hi) {
-        for (size_t i = lo; i < hi; i++) {
-            const uint8_t *rec = record_ptrs[i];
-            memcpy(slot.hdr + i * hs, rec + 1, hs);
-            copy_row(slot.rows + i * rb, rec + 1 + hs, vs);
-            if (rb > vs) memset(slot.rows + i * rb + vs, 0, rb - vs);
-        }
-        copy_fence();
-    });
-    memcpy(slot.ids, item_ids, c * 4);
-    return AH_OK;
-}
-static int send_records(ah_dataset *ds, const StageDst &dst, const RecordSlot &slot, uint64_t row0, size_t c, hipStream_t s) {
-    const size_t rb = ds->row_bytes(), hs = ah_header_size(ds->metric);
-    AH_HIP(hipMemcpyAsync(dst.rows + row0 * rb, slot.rows, c * rb, hipMemcpyHostToDevice, s));
-    AH_HIP(hipMemcpyAsync(reinterpret_cast<uint8_t *>(dst.headers) + row0 * hs, slot.hdr, c * hs, hipMemcpyHostToDevice, s));
-    AH_HIP(hipMemcpyAsync(dst.ids + row0, slot.ids, c * 4, hipMemcpyHostToDevice, s));
-    return AH_OK;
-}
-struct VectorSlot {  // f32 vectors at the staging pitch, then the ids
-    float *rows;
-    uint8_t *ids;
-    VectorSlot(uint8_t *base, size_t chunk, size_t frb) : rows(reinterpret_cast<float *>(base)), ids(base + pad256(chunk * frb)) {}
-    static size_t bytes(size_t chunk, size_t frb) { return pad256(chunk * frb) + pad256(chunk * 4); }
-};
-static void gather_vectors(const VectorSlot &slot, const float *vectors, const uint32_t *item_ids, size_t c, uint32_t dims,
-                           uint32_t fpitch) {
-    parallel_rows(c, (size_t)fpitch * 4, [&](size_t lo, size_t hi) {
-        for (size_t i = lo; i < hi; i++) {
-            copy_row(reinterpret_cast<uint8_t *>(slot.rows + i * fpitch), reinterpret_cast<const uint8_t *>(vectors + i * (size_t)dims),
-                     (size_t)dims * 4);
-            for (uint32_t e = dims; e < fpitch; e++) slot.rows[i * fpitch + e] = 0.0f;
-        }
-        copy_fence();
-    });
-    memcpy(slot.ids, item_ids, c * 4);
-}
-// BQ metrics: the f32 rows land in d_tmp (one ring slot of the context's device scratch) and are quantised from there
-static int send_vectors(ah_dataset *ds, const StageDst &dst, const VectorSlot &slot, uint64_t row0, size_t c, uint32_t fpitch,
-                        float *d_tmp, hipStream_t s) {
-    const size_t frb = (size_t)fpitch * 4;
-    DataView dv = ds->view();  // (the codec and header kernels write into `dst`)
-    dv.rows_f32 = metric_is_bq(ds->metric) ? nullptr : reinterpret_cast<const float *>(dst.rows);
-    dv.rows_bq = metric_is_bq(ds->metric) ? reinterpret_cast<const uint64_t *>(dst.rows) : nullptr;
-    dv.headers = dst.headers;
-    if (!metric_is_bq(ds->metric)) {
-        AH_HIP(hipMemcpyAsync(dst.rows + row0 * frb, slot.rows, c * frb, hipMemcpyHostToDevice, s));
-    } else {
-        AH_HIP(hipMemcpyAsync(d_tmp, slot.rows, c * frb, hipMemcpyHostToDevice, s));
-        AH_TRY(launch_quantize_rows(d_tmp, fpitch, ds->dims, reinterpret_cast<uint64_t *>(dst.rows) + row0 * ds->pitch, ds->pitch,
-                                    ds->words, c, s));
-    }
-    AH_HIP(hipMemcpyAsync(dst.ids + row0, slot.ids, c * 4, hipMemcpyHostToDevice, s));
-    AH_TRY(launch_headers_from_vectors(dv, row0, c, s));
-    return AH_OK;
-}
-
-// The ring loops of ah_dataset_upload_records / _vectors: n items into rows row0 .. row0 + n of `dst` (the dataset's own
-// arrays, or the side buffers of an update, update.hip); the caller has checked the ids and keeps the books.
-static int stage_records_loop(ah_dataset *ds, const StageDst &dst, uint64_t row0, const uint32_t *item_ids,
-                              const uint8_t *const *record_ptrs, size_t n) {
-    const size_t hs = ah_header_size(ds->metric), vs = ah_vector_size(ds->metric, ds->dims);
-    const size_t rb = ds->row_bytes();
-    const size_t chunk = std::max<size_t>(1, std::min<size_t>(n, kStageBytes / (rb + hs + 4)));
-    const size_t buf_bytes = RecordSlot::bytes(chunk, rb, hs);
-    Context *ctx = nullptr;
-    AH_TRY(upload_context(ds, buf_bytes, &ctx));
-    const size_t ring_stride = ctx->h_cap / kRing & ~(size_t)255;
-    size_t done = 0;
-    while (done < n) {
-        const size_t c = std::min(chunk, n - done);
-        const int b = ds->up_buf;
-        uint8_t *base = reinterpret_cast<uint8_t *>(ctx->h_pinned) + (size_t)b * ring_stride;
-        if (ds->up_used[b]) AH_HIP(hipEventSynchronize(ctx->ev_ring[b]));
-        const RecordSlot slot(base, chunk, rb, hs);
-        AH_TRY(gather_records(slot, record_ptrs + done, item_ids + done, c, rb, hs, vs, done));
-        AH_TRY(send_records(ds, dst, slot, row0 + done, c, ctx->stream));
-        AH_HIP(hipEventRecord(ctx->ev_ring[b], ctx->stream));
-        ds->up_used[b] = true;
-        ds->up_buf = (b + 1) % kRing;
-        done += c;
-    }
-    return AH_OK;
-}
-struct StageTimes {
-    double ctx = 0, gather = 0, wait = 0;  // seconds: context + pinned ring, the gathers, waiting for ring slots
-};
-static double secs_between(std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
-    return std::chrono::duration<double>(b - a).count();
-}
-static int stage_vectors_loop(ah_dataset *ds, const StageDst &dst, uint64_t row0, const uint32_t *item_ids, const float *vectors,
-                              size_t n, StageTimes *tm) {
-    const bool bq = metric_is_bq(ds->metric);
-    const uint32_t fpitch = bq ? ((ds->dims + 3u) & ~3u) : ds->pitch;  // staging pitch in floats
-    const size_t frb = (size_t)fpitch * 4;
-    const size_t chunk = std::max<size_t>(1, std::min<size_t>(n, kStageBytes / (frb + 4)));
-    const size_t buf_bytes = VectorSlot::bytes(chunk, frb);
-    auto now = [] { return std::chrono::steady_clock::now(); };
-    const auto t_begin = now();
-    Context *ctx = nullptr;
-    AH_TRY(upload_context(ds, buf_bytes, &ctx));
-    tm->ctx = secs_between(t_begin, now());
-    const size_t ring_stride = ctx->h_cap / kRing & ~(size_t)255;
-    if (bq) {
-        if (ctx->d_cap < (size_t)kRing * pad256(chunk * frb)) AH_HIP(hipStreamSynchronize(ctx->stream));
-        AH_TRY(ctx->ensure_device((size_t)kRing * pad256(chunk * frb)));
-    }
-    size_t done = 0;
-    while (done < n) {
-        const size_t c = std::min(chunk, n - done);
-        const int b = ds->up_buf;
-        uint8_t *base = reinterpret_cast<uint8_t *>(ctx->h_pinned) + (size_t)b * ring_stride;
-        const auto t0 = now();
-        if (ds->up_used[b]) AH_HIP(hipEventSynchronize(ctx->ev_ring[b]));
-        const auto t1 = now();
-        const VectorSlot slot(base, chunk, frb);
-        gather_vectors(slot, vectors + done * (size_t)ds->dims, item_ids + done, c, ds->dims, fpitch);
-        tm->wait += secs_between(t0, t1);
-        tm->gather += secs_between(t1, now());
-        float *d_tmp = bq ? reinterpret_cast<float *>(reinterpret_cast<uint8_t *>(ctx->d_scratch) + (size_t)b * pad256(chunk * frb))
-                          : nullptr;
-        AH_TRY(send_vectors(ds, dst, slot, row0 + done, c, fpitch, d_tmp, ctx->stream));
-        AH_HIP(hipEventRecord(ctx->ev_ring[b], ctx->stream));
-        ds->up_used[b] = true;
-        ds->up_buf = (b + 1) % kRing;
-        done += c;
-    }
-    return AH_OK;
-}
-
-// LMDB pages -> pinned staging (header and vector split apart, rows re-pitched to 128-byte lines) -> hipMemcpyAsync.
-int ah_dataset_upload_records(ah_dataset *ds, const uint32_t *item_ids, const uint8_t *const *record_ptrs,
-                              size_t record_len, size_t n) {
-    AH_GUARDED("ah_dataset_upload_records")
-    AH_TRY(check_append(ds, item_ids, n));
-    if (n == 0) return AH_OK;
-    AH_REQUIRE(item_ids && record_ptrs, AH_ERR_INVALID_ARGUMENT, "NULL input");
-    const size_t hs = ah_header_size(ds->metric), vs = ah_vector_size(ds->metric, ds->dims);
-    // src/node.rs:252-258: [LEAF_TAG=0][header][vector]; a length mismatch is what UnalignedVector::from_bytes
-    // / the dimension check reports as InvalidVecDimension
-    if (record_len != 1 + hs + vs) {
-        set_error("record length %zu does not match 1 + %zu + %zu for %u dimensions", record_len, hs, vs, ds->dims);
-        set_error_status(AH_ERR_INVALID_DIMENSION);
-        set_error_detail(0, 1 + hs + vs, record_len);
-        return AH_ERR_INVALID_DIMENSION;
-    }
-    AH_TRY(stage_records_loop(ds, own_dst(ds), ds->n, item_ids, record_ptrs, n));
-    note_ids(ds, item_ids, n);
-    // The stored DotProduct headers are taken as they are: items written by `Writer::add_item` carry {0, 0} until
-    // `DotProduct::preprocess` ran over the database (src/distance/dot_product.rs:119-165), so the dataset still needs
-    // ah_preprocess_dot unless the caller states that the database was preprocessed (ah_dataset_set_preprocessed).
-    return AH_OK;
-    AH_GUARDED_END
-}
-
-// Writer::add_item for a batch: stage f32 rows, then codec + new_header on device.
-int ah_dataset_upload_vectors(ah_dataset *ds, const uint32_t *item_ids, const float *vectors, size_t n) {
-    AH_GUARDED("ah_dataset_upload_vectors")
-    AH_TRY(check_append(ds, item_ids, n));
-    if (n == 0) return AH_OK;
-    AH_REQUIRE(item_ids && vectors, AH_ERR_INVALID_ARGUMENT, "NULL input");
-    const bool bq = metric_is_bq(ds->metric);
-    const uint32_t fpitch = bq ? ((ds->dims + 3u) & ~3u) : ds->pitch;  // staging pitch in floats
-    const size_t frb = (size_t)fpitch * 4;
-    DataView dv = ds->view();
-    // Rows that need no re-pitching can travel straight from the caller's memory when it is (or can be) page-locked:
-    // AH_STAGE_REGISTER=1 registers the caller's buffer for the duration of the call (measurement aid).
-    const bool try_register = tun(TUN_STAGE_REGISTER) != 0;
-    if (try_register && !bq && fpitch == ds->dims && n * frb >= (64u << 20)) {
-        Context *ctx = nullptr;
-        AH_TRY(upload_context(ds, pad256(std::min<size_t>(n, kStageBytes / 4) * 4), &ctx));
-        if (hipHostRegister(const_cast<float *>(vectors), n * frb, hipHostRegisterDefault) == hipSuccess) {
-            const uint64_t row0 = ds->n;
-            hipError_t e = hipMemcpyAsync(ds->d_rows_f32 + row0 * ds->pitch, vectors, n * frb, hipMemcpyHostToDevice, ctx->stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(ds->d_ids + row0, item_ids, n * 4, hipMemcpyHostToDevice, ctx->stream);
-            int st = e == hipSuccess ? launch_headers_from_vectors(dv, row0, n, ctx->stream) : AH_ERR_DEVICE;
-            const hipError_t es = hipStreamSynchronize(ctx->stream);  // the caller's pages are the DMA source
-            (void)hipHostUnregister(const_cast<float *>(vectors));
-            AH_REQUIRE(e == hipSuccess && es == hipSuccess && st == AH_OK, AH_ERR_DEVICE, "registered staging copy failed");
-            note_ids(ds, item_ids, n);
-            return AH_OK;
-        }
-        (void)hipGetLastError();  // not registrable: fall through to the bounce path
-    }
-    const bool timing = tun(TUN_TIMING) != 0;
-    auto now = [] { return std::chrono::steady_clock::now(); };
-    const auto t_begin = now();
-    StageTimes tm;
-    AH_TRY(stage_vectors_loop(ds, own_dst(ds), ds->n, item_ids, vectors, n, &tm));
-    const auto t_loop = now();
-    note_ids(ds, item_ids, n);
-    if (timing)
-        fprintf(stderr, "[ah] upload_vectors %zu x %u: context + pinned ring %.4f s, gather %.4f s, waiting for the ring %.4f s, "
-                        "launch/other %.4f s, note_ids %.4f s\n",
-                n, ds->dims, tm.ctx, tm.gather, tm.wait, secs_between(t_begin, t_loop) - tm.ctx - tm.gather - tm.wait,
-                secs_between(t_loop, now()));
-    return AH_OK;
-    AH_GUARDED_END
-}
-
-int ah_dataset_upload_flush(ah_dataset *ds) {
-    AH_GUARDED("ah_dataset_upload_flush")
-    AH_REQUIRE(ds, AH_ERR_INVALID_ARGUMENT, "dataset is NULL");
-    return upload_flush(ds);
     AH_GUARDED_END
 }
 
@@ -1347,7 +1016,7 @@ int ah_dataset_finalize(ah_dataset *ds) {
 // ah_dataset_finalize, and ah_group_finalize for every member
 static int finalize_impl(ah_dataset *ds) {
     if (ds->finalized) return AH_OK;
-    AH_TRY(upload_flush(ds));  // every staged record has landed
+    AH_TRY(flush_staging(ds));  // every staged record has landed
     AH_LEASE(ds, ctx);
     if (ds->identity_ids) {
         // ids 0..n-1: no table needed; the id array is still materialised for uniform kernels
@@ -1473,7 +1142,7 @@ int ah_dataset_replicate(ah_dataset *src, int device, ah_dataset **out) {
     AH_REQUIRE(out, AH_ERR_INVALID_ARGUMENT, "out is NULL");
     *out = nullptr;
     AH_REQUIRE(src, AH_ERR_INVALID_ARGUMENT, "dataset is NULL");
-    AH_TRY(upload_flush(src));  // (under the source's staging lock: several threads may replicate one unfinalized source)
+    AH_TRY(flush_staging(src));  // (under the source's staging lock: several threads may replicate one unfinalized source)
     DeviceRestore restore_device;  // (the calling thread may hold another device current: a host thread per GPU)
     ah_dataset *dst = nullptr;
     AH_TRY(ah_dataset_create(src->metric, src->dims, std::max<uint64_t>(src->capacity, 1), device, &dst));
@@ -1531,52 +1200,8 @@ int ah_dataset_replicate(ah_dataset *src, int device, ah_dataset **out) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// device groups (include/arroy_hip.h, "Device groups"): staging.  The build is in group.hip.
+// device groups (include/arroy_hip.h, "Device groups"): the life cycle.  Staging is in stage.hip, the build in group.hip.
 // ---------------------------------------------------------------------------------------------
-namespace {
-// wait until no member's transfer out of ring slot b is in flight
-int group_wait_slot(ah_group *g, int b) {
-    if (!g->slot_used[b]) return AH_OK;
-    for (ah_dataset *m : g->members)
-        if (m->up_ctx && m->up_ctx->ev_ring[b]) AH_HIP(hipEventSynchronize(m->up_ctx->ev_ring[b]));
-    g->slot_used[b] = false;
-    return AH_OK;
-}
-
-// the pinned ring (kRing slots of at least slot_bytes; grown only when idle) and every member's upload context: its stream,
-// its ring events and, for the 1-bit metrics, device scratch for one f32 chunk per slot
-int group_stage_begin(ah_group *g, size_t slot_bytes, size_t member_scratch) {
-    if (g->slot_bytes < slot_bytes) {
-        for (int b = 0; b < ah_group::kRing; b++) AH_TRY(group_wait_slot(g, b));
-        if (g->h_ring) AH_HIP(hipHostFree(g->h_ring));
-        g->h_ring = nullptr;
-        g->slot_bytes = 0;
-        const size_t slot = (slot_bytes + 4095) & ~(size_t)4095;
-        AH_REQUIRE(!fail_alloc_tick(), AH_ERR_OUT_OF_MEMORY, "pinned host allocation of %zu bytes failed (AH_FAIL_ALLOC_AFTER)",
-                   slot * ah_group::kRing);
-        // portable: every member's device may use the slot as its DMA source
-        AH_HIP(hipHostMalloc(&g->h_ring, slot * ah_group::kRing, hipHostMallocPortable));
-        g->slot_bytes = slot;
-    }
-    for (ah_dataset *m : g->members) {
-        AH_HIP(hipSetDevice(m->device));
-        std::lock_guard<std::mutex> lk(m->up_mu);
-        if (!m->up_ctx) {
-            m->up_ctx = m->acquire();
-            AH_REQUIRE(m->up_ctx, AH_ERR_DEVICE, "cannot create a HIP stream");
-        }
-        Context *c = m->up_ctx;
-        for (hipEvent_t &e : c->ev_ring)
-            if (!e) AH_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        if (member_scratch && c->d_cap < member_scratch) {
-            AH_HIP(hipStreamSynchronize(c->stream));  // the old scratch may still be a quantize source
-            AH_TRY(c->ensure_device(member_scratch));
-        }
-    }
-    return AH_OK;
-}
-}  // namespace
-
 int ah_group_create(int metric, uint32_t dimensions, uint64_t capacity, const int *devices, uint32_t n_devices,
                     ah_group **out) {
     AH_GUARDED("ah_group_create")
@@ -1626,149 +1251,13 @@ int ah_group_destroy(ah_group *g) {
     NoFailScope no_fail;
     DeviceRestore restore_device;
     for (ah_dataset *m : g->members) {
-        (void)upload_flush(m);  // (every transfer out of the ring has landed before the ring goes)
+        (void)flush_staging(m);  // (every transfer out of the ring has landed before the ring goes)
         m->group_member = false;
         (void)ah_dataset_destroy(m);
     }
-    if (g->h_ring) (void)hipHostFree(g->h_ring);
+    (void)g->ring.release();
     delete g;
     return AH_OK;
-    AH_GUARDED_END
-}
-
-// The ring loops of ah_group_upload_vectors / _records: n items into rows row0 .. row0 + n of dst[i] on member i (the members'
-// own arrays, or the side buffers of an update).
-static int group_stage_vectors_loop(ah_group *g, const StageDst *dst, uint64_t row0, const uint32_t *item_ids, const float *vectors,
-                                    size_t n, StageTimes *tm) {
-    const bool bq = metric_is_bq(g->metric);
-    const uint32_t fpitch = bq ? ((g->dims + 3u) & ~3u) : g->members[0]->pitch;
-    const size_t frb = (size_t)fpitch * 4;
-    const size_t chunk = std::max<size_t>(1, std::min<size_t>(n, kStageBytes / (frb + 4)));
-    auto now = [] { return std::chrono::steady_clock::now(); };
-    const auto t_begin = now();
-    AH_TRY(group_stage_begin(g, VectorSlot::bytes(chunk, frb), bq ? (size_t)ah_group::kRing * pad256(chunk * frb) : 0));
-    tm->ctx = secs_between(t_begin, now());
-    size_t done = 0;
-    while (done < n) {
-        const size_t c = std::min(chunk, n - done);
-        const int b = g->next_slot;
-        const auto t0 = now();
-        AH_TRY(group_wait_slot(g, b));
-        const auto t1 = now();
-        const VectorSlot slot(reinterpret_cast<uint8_t *>(g->h_ring) + (size_t)b * g->slot_bytes, chunk, frb);
-        gather_vectors(slot, vectors + done * (size_t)g->dims, item_ids + done, c, g->dims, fpitch);
-        tm->wait += secs_between(t0, t1);
-        tm->gather += secs_between(t1, now());
-        for (size_t i = 0; i < g->members.size(); i++) {
-            ah_dataset *m = g->members[i];
-            Context *ctx = m->up_ctx;
-            AH_HIP(hipSetDevice(m->device));
-            float *d_tmp = bq ? reinterpret_cast<float *>(reinterpret_cast<uint8_t *>(ctx->d_scratch) + (size_t)b * pad256(chunk * frb))
-                              : nullptr;
-            g->slot_used[b] = true;
-            AH_TRY(send_vectors(m, dst[i], slot, row0 + done, c, fpitch, d_tmp, ctx->stream));
-            AH_HIP(hipEventRecord(ctx->ev_ring[b], ctx->stream));
-        }
-        g->next_slot = (b + 1) % ah_group::kRing;
-        done += c;
-    }
-    return AH_OK;
-}
-static int group_stage_records_loop(ah_group *g, const StageDst *dst, uint64_t row0, const uint32_t *item_ids,
-                                    const uint8_t *const *record_ptrs, size_t n) {
-    const size_t hs = ah_header_size(g->metric), vs = ah_vector_size(g->metric, g->dims);
-    const size_t rb = g->members[0]->row_bytes();
-    const size_t chunk = std::max<size_t>(1, std::min<size_t>(n, kStageBytes / (rb + hs + 4)));
-    AH_TRY(group_stage_begin(g, RecordSlot::bytes(chunk, rb, hs), 0));
-    size_t done = 0;
-    while (done < n) {
-        const size_t c = std::min(chunk, n - done);
-        const int b = g->next_slot;
-        AH_TRY(group_wait_slot(g, b));
-        const RecordSlot slot(reinterpret_cast<uint8_t *>(g->h_ring) + (size_t)b * g->slot_bytes, chunk, rb, hs);
-        AH_TRY(gather_records(slot, record_ptrs + done, item_ids + done, c, rb, hs, vs, done));
-        for (size_t i = 0; i < g->members.size(); i++) {
-            ah_dataset *m = g->members[i];
-            Context *ctx = m->up_ctx;
-            AH_HIP(hipSetDevice(m->device));
-            g->slot_used[b] = true;
-            AH_TRY(send_records(m, dst[i], slot, row0 + done, c, ctx->stream));
-            AH_HIP(hipEventRecord(ctx->ev_ring[b], ctx->stream));
-        }
-        g->next_slot = (b + 1) % ah_group::kRing;
-        done += c;
-    }
-    return AH_OK;
-}
-
-// Writer::add_item for a batch, on every member: the chunk is gathered once into the group's pinned ring and sent from that
-// same slot to every member, each on its own stream, where the codec / header kernels run on the member's device.
-int ah_group_upload_vectors(ah_group *g, const uint32_t *item_ids, const float *vectors, size_t n) {
-    AH_GUARDED("ah_group_upload_vectors")
-    AH_REQUIRE(g, AH_ERR_INVALID_ARGUMENT, "group is NULL");
-    ah_dataset *m0 = g->members[0];
-    AH_TRY(check_ids(m0, item_ids, n));  // (the members are in the same state)
-    if (n == 0) return AH_OK;
-    AH_REQUIRE(item_ids && vectors, AH_ERR_INVALID_ARGUMENT, "NULL input");
-    DeviceRestore restore_device;
-    for (ah_dataset *m : g->members) reserve_ids(m, n);
-    // AH_TIMING=1: where the call's time went, in the form of ah_dataset_upload_vectors' line (scripts/exp_group.py reads
-    // the gather: it is paid once whatever the number of members)
-    const bool timing = tun(TUN_TIMING) != 0;
-    auto now = [] { return std::chrono::steady_clock::now(); };
-    const auto t_begin = now();
-    StageTimes tm;
-    std::vector<StageDst> dst;
-    for (ah_dataset *m : g->members) dst.push_back(own_dst(m));
-    AH_TRY(group_stage_vectors_loop(g, dst.data(), m0->n, item_ids, vectors, n, &tm));
-    const auto t_loop = now();
-    for (ah_dataset *m : g->members) note_ids(m, item_ids, n);
-    if (timing)
-        fprintf(stderr, "[ah] group upload_vectors %zu x %u to %zu members: context + pinned ring %.4f s, gather %.4f s, waiting for "
-                        "the ring %.4f s, launch/other %.4f s, note_ids %.4f s\n",
-                n, g->dims, g->members.size(), tm.ctx, tm.gather, tm.wait, secs_between(t_begin, t_loop) - tm.ctx - tm.gather - tm.wait,
-                secs_between(t_loop, now()));
-    return AH_OK;
-    AH_GUARDED_END
-}
-
-// LMDB pages -> the group's pinned ring (once) -> every member.
-int ah_group_upload_records(ah_group *g, const uint32_t *item_ids, const uint8_t *const *record_ptrs, size_t record_len,
-                            size_t n) {
-    AH_GUARDED("ah_group_upload_records")
-    AH_REQUIRE(g, AH_ERR_INVALID_ARGUMENT, "group is NULL");
-    ah_dataset *m0 = g->members[0];
-    AH_TRY(check_ids(m0, item_ids, n));
-    if (n == 0) return AH_OK;
-    AH_REQUIRE(item_ids && record_ptrs, AH_ERR_INVALID_ARGUMENT, "NULL input");
-    const size_t hs = ah_header_size(g->metric), vs = ah_vector_size(g->metric, g->dims);
-    if (record_len != 1 + hs + vs) {
-        set_error("record length %zu does not match 1 + %zu + %zu for %u dimensions", record_len, hs, vs, g->dims);
-        set_error_status(AH_ERR_INVALID_DIMENSION);
-        set_error_detail(0, 1 + hs + vs, record_len);
-        return AH_ERR_INVALID_DIMENSION;
-    }
-    DeviceRestore restore_device;
-    for (ah_dataset *m : g->members) reserve_ids(m, n);
-    std::vector<StageDst> dst;
-    for (ah_dataset *m : g->members) dst.push_back(own_dst(m));
-    AH_TRY(group_stage_records_loop(g, dst.data(), m0->n, item_ids, record_ptrs, n));
-    for (ah_dataset *m : g->members) note_ids(m, item_ids, n);
-    return AH_OK;
-    AH_GUARDED_END
-}
-
-int ah_group_upload_flush(ah_group *g) {
-    AH_GUARDED("ah_group_upload_flush")
-    AH_REQUIRE(g, AH_ERR_INVALID_ARGUMENT, "group is NULL");
-    DeviceRestore restore_device;
-    int st = AH_OK;
-    for (ah_dataset *m : g->members) {
-        const int s = upload_flush(m);
-        if (st == AH_OK) st = s;
-    }
-    for (bool &u : g->slot_used) u = false;
-    return st;
     AH_GUARDED_END
 }
 
@@ -1785,7 +1274,7 @@ int ah_group_finalize(ah_group *g) {
     AH_GUARDED("ah_group_finalize")
     AH_REQUIRE(g, AH_ERR_INVALID_ARGUMENT, "group is NULL");
     DeviceRestore restore_device;
-    AH_TRY(ah_group_upload_flush(g));
+    AH_TRY(flush_staging(g));
     for (ah_dataset *m : g->members) AH_TRY(finalize_impl(m));
     return AH_OK;
     AH_GUARDED_END
@@ -1795,7 +1284,7 @@ int ah_group_preprocess_dot(ah_group *g, float *out_max_norm) {
     AH_GUARDED("ah_group_preprocess_dot")
     AH_REQUIRE(g, AH_ERR_INVALID_ARGUMENT, "group is NULL");
     DeviceRestore restore_device;
-    AH_TRY(ah_group_upload_flush(g));
+    AH_TRY(flush_staging(g));
     float first = 0.0f;
     for (size_t i = 0; i < g->members.size(); i++) {
         float m = 0.0f;
@@ -1892,7 +1381,7 @@ int ah_dataset_read_headers(ah_dataset *ds, uint64_t first_row, uint64_t n, void
     AH_GUARDED("ah_dataset_read_headers")
     AH_REQUIRE(ds && out_headers, AH_ERR_INVALID_ARGUMENT, "NULL argument");
     AH_REQUIRE(first_row + n <= ds->n, AH_ERR_INVALID_ARGUMENT, "row range out of bounds");
-    AH_TRY(upload_flush(ds));
+    AH_TRY(flush_staging(ds));
     AH_HIP(hipSetDevice(ds->device));
     const size_t hs = ah_header_size(ds->metric);
     AH_HIP(hipMemcpy(out_headers, reinterpret_cast<uint8_t *>(ds->d_headers) + first_row * hs, n * hs,
@@ -1912,7 +1401,7 @@ int ah_preprocess_dot(ah_dataset *ds, float *out_max_norm) {
 // ah_preprocess_dot, and ah_group_preprocess_dot for every member
 static int preprocess_dot_impl(ah_dataset *ds, float *out_max_norm) {
     AH_REQUIRE(ds->metric == AH_DOT_PRODUCT, AH_ERR_INVALID_ARGUMENT, "preprocess is only defined for DotProduct");
-    AH_TRY(upload_flush(ds));
+    AH_TRY(flush_staging(ds));
     AH_LEASE(ds, ctx);
     AH_TRY(ctx->ensure_device(256));
     AH_TRY(launch_preprocess_dot(ds->view(), reinterpret_cast<float *>(ctx->d_scratch), ctx->stream));
@@ -2648,27 +2137,3 @@ int ah_bench_read(int device, uint64_t bytes, uint32_t iterations, double *out_m
 }
 
 }  // extern "C"
-
-// The staging loops for the updates of a finalized dataset (update.hip): the upserted items go through the same rings, codec
-// and header kernels as ah_dataset_upload_* / ah_group_upload_*, into the update's side buffers.
-namespace ah {
-int stage_vectors(ah_dataset *ds, const StageDst &dst, const uint32_t *item_ids, const float *vectors, size_t n) {
-    StageTimes tm;
-    AH_TRY(stage_vectors_loop(ds, dst, 0, item_ids, vectors, n, &tm));
-    return upload_flush(ds);
-}
-int stage_records(ah_dataset *ds, const StageDst &dst, const uint32_t *item_ids, const uint8_t *const *record_ptrs, size_t n) {
-    AH_TRY(stage_records_loop(ds, dst, 0, item_ids, record_ptrs, n));
-    return upload_flush(ds);
-}
-int group_stage_vectors(ah_group *g, const StageDst *dst, const uint32_t *item_ids, const float *vectors, size_t n) {
-    StageTimes tm;
-    AH_TRY(group_stage_vectors_loop(g, dst, 0, item_ids, vectors, n, &tm));
-    return ah_group_upload_flush(g);
-}
-int group_stage_records(ah_group *g, const StageDst *dst, const uint32_t *item_ids, const uint8_t *const *record_ptrs, size_t n) {
-    AH_TRY(group_stage_records_loop(g, dst, 0, item_ids, record_ptrs, n));
-    return ah_group_upload_flush(g);
-}
-int flush_staging(ah_dataset *ds) { return upload_flush(ds); }
-}  // namespace ah

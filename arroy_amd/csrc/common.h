@@ -365,13 +365,21 @@ inline PackedView packed_layout(uint32_t dims) {
     return pk;
 }
 
+// The state of a staging ring (stage.hip): kRing pinned slots, each gathered into while the others travel.  A dataset has one
+// for the ring of its upload context, a group one for the ring all its members read.
+struct StageRing {
+    static constexpr int kRing = 3;
+    int next = 0;                             // the slot the next chunk is gathered into
+    bool used[kRing] = {false, false, false};  // a transfer out of the slot may still be in flight (its ring events tell)
+};
+
 // One per concurrently calling host thread: a stream plus growable device / pinned scratch.
 struct Context {
     hipStream_t stream = nullptr;
     hipStream_t copy_stream = nullptr;  // uploads that run under the kernels of `stream` (created on first use)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr;  // AH_RERANK_TIMING: first enqueue .. stream idle of one submission (created on first use)
-    hipEvent_t ev_ring[4] = {nullptr, nullptr, nullptr, nullptr};  // staging ring (created on first use)
+    hipEvent_t ev_ring[StageRing::kRing] = {nullptr, nullptr, nullptr};  // staging ring (created on first use)
     void *d_scratch = nullptr;
     size_t d_cap = 0;
     void *h_pinned = nullptr;
@@ -448,9 +456,8 @@ struct ah_dataset {
     // staging in flight (ah_dataset_upload_*): the context whose stream / pinned ring the uploads use until
     // ah_dataset_finalize (or ah_dataset_upload_flush) waits for them
     ah::Context *up_ctx = nullptr;
-    int up_buf = 0;
-    bool up_used[4] = {false, false, false, false};
-    std::mutex up_mu;                            // upload_flush: concurrent flushes (replication of an unstaged source) take turns
+    ah::StageRing up_ring;                       // ... and the state of that context's pinned ring
+    std::mutex up_mu;                            // up_ctx: concurrent flushes (replication of an unstaged source) take turns
     bool group_member = false;                   // a member of an ah_group: borrowed handle, no staging / destroy of its own
     std::mutex mu;
     std::vector<ah::Context *> pool;
@@ -499,16 +506,22 @@ struct ah_dataset {
 };
 
 // ah_group (include/arroy_hip.h, "Device groups"): the member datasets and the pinned ring every upload chunk is gathered into
-// once.  The staging calls live in api.hip, the build in group.hip.
+// once.  The life cycle lives in api.hip, the staging calls in stage.hip, the build in group.hip.
 struct ah_group {
-    static constexpr int kRing = 3;
     int metric = 0;
     uint32_t dims = 0;
     std::vector<ah_dataset *> members;
-    void *h_ring = nullptr;                      // kRing slots of `slot_bytes`, hipHostMallocPortable (every member's DMA source)
-    size_t slot_bytes = 0;
-    int next_slot = 0;
-    bool slot_used[kRing] = {false, false, false};  // a member's transfer out of the slot may still be in flight
+    struct Ring {
+        void *base = nullptr;                    // kRing slots of `slot_bytes`, hipHostMallocPortable (every member's DMA source)
+        size_t slot_bytes = 0;
+        ah::StageRing state;
+        hipError_t release() {                   // (the caller has waited for every transfer out of it)
+            const hipError_t e = base ? hipHostFree(base) : hipSuccess;
+            base = nullptr;
+            slot_bytes = 0;
+            return e;
+        }
+    } ring;
 };
 
 namespace ah {
@@ -535,13 +548,19 @@ inline StageDst own_dst(ah_dataset *ds) {
     uint8_t *rows = ds->d_rows_f32 ? reinterpret_cast<uint8_t *>(ds->d_rows_f32) : reinterpret_cast<uint8_t *>(ds->d_rows_bq);
     return StageDst{rows, ds->d_headers, ds->d_ids};
 }
-// api.hip: n items staged into rows 0 .. n of `dst` through the dataset's (the group's) pinned ring, codec and header
-// kernels included; returns once every transfer has landed
-int stage_vectors(ah_dataset *ds, const StageDst &dst, const uint32_t *item_ids, const float *vectors, size_t n);
-int stage_records(ah_dataset *ds, const StageDst &dst, const uint32_t *item_ids, const uint8_t *const *record_ptrs, size_t n);
-int group_stage_vectors(ah_group *g, const StageDst *dst, const uint32_t *item_ids, const float *vectors, size_t n);
-int group_stage_records(ah_group *g, const StageDst *dst, const uint32_t *item_ids, const uint8_t *const *record_ptrs, size_t n);
-int flush_staging(ah_dataset *ds);  // wait for a dataset's staging transfers (upload_flush)
+// stage.hip: n items (f32 `vectors`, or stored records if `vectors` is NULL) staged into rows 0 .. n of dst[i] on members[i],
+// through the dataset's pinned ring (g == NULL: one member) or the group's, codec and header kernels included; returns once
+// every transfer has landed or, after a failure, none is in flight any more
+int stage_items(const std::vector<ah_dataset *> &members, ah_group *g, const StageDst *dst, const uint32_t *item_ids,
+                const float *vectors, const uint8_t *const *record_ptrs, size_t n);
+int flush_staging(ah_dataset *ds);  // wait for a dataset's staging transfers and give its upload context back
+int flush_staging(ah_group *g);     // ... for every member's
+// api.hip: fn(lo, hi) over slices of [0, n) on the worker pool and the calling thread (n x bytes_per_item below ~2 MiB: inline)
+void parallel_rows_run(size_t n, size_t bytes_per_item, void (*fn)(void *, size_t, size_t), void *arg);
+template <typename F>
+inline void parallel_rows(size_t n, size_t bytes_per_item, F &&fn) {
+    parallel_rows_run(n, bytes_per_item, [](void *f, size_t lo, size_t hi) { (*static_cast<std::remove_reference_t<F> *>(f))(lo, hi); }, &fn);
+}
 
 // owning device pointer for short-lived buffers on paths with early error returns
 struct DevMem {

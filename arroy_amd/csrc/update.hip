@@ -449,20 +449,11 @@ int update_impl(const std::vector<ah_dataset *> &members, ah_group *g, const Upd
     for (MemberUpdate &mu : mus) AH_TRY(prepare(&mu, p, a));
     const auto t_alloc = now();
     // the upserted rows cross PCIe once: into every member's side buffers through the dataset's (the group's) pinned ring
+    // (stage.hip), and have landed when the call returns
     if (a.n_up) {
-        int st;
-        if (g) {
-            std::vector<StageDst> dst;
-            for (MemberUpdate &mu : mus) dst.push_back(mu.side());
-            st = a.vectors ? group_stage_vectors(g, dst.data(), a.up, a.vectors, a.n_up)
-                           : group_stage_records(g, dst.data(), a.up, a.records, a.n_up);
-            if (st != AH_OK) (void)ah_group_upload_flush(g);
-        } else {
-            st = a.vectors ? stage_vectors(ds0, mus[0].side(), a.up, a.vectors, a.n_up)
-                           : stage_records(ds0, mus[0].side(), a.up, a.records, a.n_up);
-            if (st != AH_OK) (void)flush_staging(ds0);
-        }
-        AH_TRY(st);
+        std::vector<StageDst> dst;
+        for (MemberUpdate &mu : mus) dst.push_back(mu.side());
+        AH_TRY(stage_items(members, g, dst.data(), a.up, a.vectors, a.records, a.n_up));
     }
     const auto t_stage = now();
     for (MemberUpdate &mu : mus) AH_TRY(launch_plan(&mu, p, a));

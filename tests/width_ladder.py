@@ -25,7 +25,7 @@ PITCH8_ALIGN = 128      # forest.hip:2133 pitch8 = round_up(dims, 128)
 PAIR_LINES = 2          # batch.hip:402 k_pairs_distances_runs: lines in pairs, :416 the odd one
 
 BQ_WORD_BITS = 64       # binary_quantized.rs:67-69 words = ceil(dims / 64)
-BQ_PITCH_ALIGN = 2      # api.hip:912 pitch = round_up(words, 2): rows of whole 16-byte chunks, an odd word count gets a zero word
+BQ_PITCH_ALIGN = 2      # ah_dataset_create: pitch = round_up(words, 2): rows of whole 16-byte chunks, an odd word count gets a zero word
 BQ_UNROLL = 8           # distance.hip:291 kBqUnroll: chunk loads in flight per trip
 BQ_MAX_CHUNKS = 32      # distance.hip:290 kBqMaxChunks (:433 wider rows take k_distances_bq_wide)
 BQ_TILE_ROWS = 64       # distance.hip:321 a wave's tile: step_r = 64 / C rows, step_p = 64 % C parts per load
