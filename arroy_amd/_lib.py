@@ -214,6 +214,11 @@ class AhIndexDecodeStats(C.Structure):
                                           "chunks")] + [("seconds_total", C.c_double), ("seconds_host_copy", C.c_double)]
 
 
+class AhIndexEncodeStats(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("n_values", "n_split", "n_descendants", "n_free", "value_bytes", "pieces")] + [
+        ("seconds", C.c_double)]
+
+
 class AhStreamNode(C.Structure):
     _fields_ = [("id", C.c_uint32), ("tree", C.c_uint32), ("kind", C.c_uint8), ("has_normal", C.c_uint8), ("reserved", C.c_uint16),
                 ("left", C.c_uint32), ("right", C.c_uint32), ("count", C.c_uint32), ("depth", C.c_uint32),
@@ -293,6 +298,9 @@ SIGNATURES = {
     # a resident index from the NodeCodec bytes LMDB stores
     "ah_index_create_from_encoded": (C.c_int, [_VP, _U32P, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_size_t, _U32P, C.c_uint32,
                                                C.POINTER(C.c_void_p), C.POINTER(AhIndexDecodeStats)]),
+    # ... and the nodes of a resident index as those bytes
+    "ah_index_encode_nodes": (C.c_int, [_VP, _U32P, C.c_size_t, _U32P, C.c_uint32, _VP, C.c_uint64, _U64P,
+                                        C.POINTER(AhIndexEncodeStats)]),
     "ah_index_destroy": (C.c_int, [_VP]),
     "ah_search_batch": (C.c_int, [_VP, _F32P, _U32P, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, _U32P, C.c_size_t,
                                   C.c_int, _U32P, _F32P, _U32P]),

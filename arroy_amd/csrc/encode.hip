@@ -40,10 +40,11 @@ __device__ __forceinline__ ChunkScan scan_step(const uint32_t *ids, uint32_t cou
 // the list); one that starts and ends inside a step has at most 64 ids.  So only the carried one can be a bitmap.
 __global__ __launch_bounds__(kEncBlock) void k_enc_measure(const uint8_t *__restrict__ src, const EncNode *__restrict__ nodes, uint64_t n,
                                                           uint64_t *__restrict__ len_out, uint32_t *__restrict__ info,
-                                                          uint32_t *__restrict__ err) {
+                                                          uint32_t *__restrict__ err, bool mixed) {
     const uint32_t lane = threadIdx.x & (kWave - 1);
     const uint64_t n_waves = (uint64_t)gridDim.x * (kEncBlock / kWave);
     for (uint64_t node = ((uint64_t)blockIdx.x * kEncBlock + threadIdx.x) / kWave; node < n; node += n_waves) {
+        if (mixed && info[node] >= kEncInfoFree) continue;  // no Descendants node: its length is its caller's
         const EncNode nd = nodes[node];
         const uint32_t *ids = reinterpret_cast<const uint32_t *>(src + nd.src);
         const uint32_t count = nd.a;
@@ -186,7 +187,7 @@ __global__ __launch_bounds__(kEncBlock) void k_enc_write_desc_big(const uint8_t 
     const uint32_t t = threadIdx.x;
     for (uint64_t node = blockIdx.x; node < n; node += gridDim.x) {
         const uint32_t inf = info[node];
-        if (!(inf >> 31)) continue;
+        if (!(inf >> 31) || inf >= kEncInfoFree) continue;
         const uint32_t nc = inf & 0x7FFFFFFFu;
         const EncNode nd = nodes[node];
         const uint32_t *ids = reinterpret_cast<const uint32_t *>(src + nd.src);
@@ -263,15 +264,25 @@ unsigned wave_grid(uint64_t n) { return grid_of(n, kEncBlock / kWave, 256u * 16u
 
 }  // namespace
 
-int launch_measure_descendants(const uint8_t *src, const EncNode *nodes, uint64_t n, uint64_t *off, uint32_t *info, uint64_t *sums,
-                               uint32_t *err, hipStream_t s) {
-    if (n) hipLaunchKernelGGL(k_enc_measure, dim3(wave_grid(n)), dim3(kEncBlock), 0, s, src, nodes, n, off, info, err);
+static int measure_and_scan(const uint8_t *src, const EncNode *nodes, uint64_t n, uint64_t *off, uint32_t *info, uint64_t *sums, uint32_t *err,
+                            bool mixed, hipStream_t s) {
+    if (n) hipLaunchKernelGGL(k_enc_measure, dim3(wave_grid(n)), dim3(kEncBlock), 0, s, src, nodes, n, off, info, err, mixed);
     const uint64_t nb = (n + kEncScanTile - 1) / kEncScanTile;
     if (nb) hipLaunchKernelGGL(k_enc_scan_sums, dim3((unsigned)nb), dim3(kEncBlock), 0, s, off, n, sums);
     hipLaunchKernelGGL(k_enc_scan_top, dim3(1), dim3(kEncBlock), 0, s, sums, nb, off, n);
     if (nb) hipLaunchKernelGGL(k_enc_scan_apply, dim3((unsigned)nb), dim3(kEncBlock), 0, s, off, n, sums);
     AH_HIP(hipGetLastError());
     return AH_OK;
+}
+
+int launch_measure_descendants(const uint8_t *src, const EncNode *nodes, uint64_t n, uint64_t *off, uint32_t *info, uint64_t *sums,
+                               uint32_t *err, hipStream_t s) {
+    return measure_and_scan(src, nodes, n, off, info, sums, err, false, s);
+}
+
+int launch_measure_mixed(const uint8_t *src, const EncNode *nodes, uint64_t n, uint64_t *off, uint32_t *info, uint64_t *sums, uint32_t *err,
+                         hipStream_t s) {
+    return measure_and_scan(src, nodes, n, off, info, sums, err, true, s);
 }
 
 int launch_write_descendants(const uint8_t *src, const EncNode *nodes, uint64_t n, const uint64_t *off, const uint32_t *info,

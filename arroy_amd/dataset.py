@@ -930,6 +930,36 @@ class Index:
             out["normal_rows"], out["normal_headers"] = rows, hdrs
         return out
 
+    def encode_nodes(self, indices=None, node_ids=None, base: int = 0, sizes_only: bool = False, out_cap: int | None = None,
+                     want_stats: bool = False):
+        """ah_index_encode_nodes: the `NodeCodec` values (what LMDB stores) of the node slots `indices` of the index as it is on
+        the device, in the order listed; None: of every slot, a free one giving b"".  Children are written as the store's ids:
+        node_ids[slot] (one per node slot of the index) or base + slot.  Returns a list of bytes, or with sizes_only the value
+        offsets (len + 1, uint64); with want_stats (that, ah_index_encode_stats as a dict)."""
+        idx = None if indices is None else _u32(indices).ravel()
+        n = self.export_info()["n_nodes"] if idx is None else idx.size
+        ids = None if node_ids is None else _u32(node_ids).ravel()
+        if ids is not None and ids.size != self.export_info()["n_nodes"]:
+            raise ValueError(f"node_ids has {ids.size} entries for the {self.export_info()['n_nodes']} node slots of the index")
+        st = _lib.AhIndexEncodeStats()
+        ends = np.zeros(n + 1, dtype=np.uint64)
+        fn = _lib.lib().ah_index_encode_nodes
+        # (an empty list still has a pointer: NULL means every slot)
+        held = None if idx is None else (idx if idx.size else np.zeros(1, np.uint32))  # (kept alive across both calls)
+        idx_p = None if held is None else held.ctypes.data
+        _lib.check(fn(self._h, idx_p, n, _ptr(ids), int(base), None, 0, _ptr(ends), C.byref(st)))
+        if not sizes_only:
+            cap = int(ends[n]) if out_cap is None else int(out_cap)
+            out = np.full(int(ends[n]) + 64, 0xA5, dtype=np.uint8)  # (the tail shows a write past the values)
+            try:
+                _lib.check(fn(self._h, idx_p, n, _ptr(ids), int(base), _ptr(out), cap, _ptr(ends), C.byref(st)))
+            finally:
+                assert bool(np.all(out[int(ends[n]):] == 0xA5)), "ah_index_encode_nodes wrote past the end of its values"
+        res = ends if sizes_only else [out[int(ends[i]): int(ends[i + 1])].tobytes() for i in range(n)]
+        if want_stats:
+            return res, {f: (float if f == "seconds" else int)(getattr(st, f)) for f, _ in _lib.AhIndexEncodeStats._fields_}
+        return res
+
     def footprint(self) -> dict:
         """ah_index_footprint_get: node slots and the free ones among them, normal rows in use / live / room for, desc_len and
         the bytes of HBM the index holds (counted on the device; legal with live filters)."""

@@ -293,6 +293,9 @@ class _IndexState:
         self.index_uploads = 0   # indexes made from a whole view of the store (every node, id and normal uploaded)
         self.device_compactions = 0  # builds that ended with a compaction of the resident index (Index.compact)
         self.device_drops = 0    # builds that dropped their extra trees on the resident index (Index.drop_trees)
+        # nodes whose values a build that kept its resident index encoded on the device for ArroyBuilder.encoded_store
+        # (Index.encode_nodes of the nodes its deltas put and its grafts added, not of the whole index)
+        self.device_encoded_nodes = 0
 
 
 def compaction_due(fp: dict) -> bool:
@@ -394,6 +397,48 @@ class ArroyBuilder:
         # them, and leaves them suspended for the caller to resume with its delta (Index.resume_filters); the compaction at
         # the end of the build is then no longer skipped on their account
         self.keep_filters = False
+        # A dict: build() keeps it equal to {node id: `NodeCodec` value} of the TreeStore — what the tree keys of LMDB would
+        # hold — written only from device encodes (Index.encode_nodes).  A build whose resident index has followed the store
+        # removes the ids its deltas removed and encodes only the nodes the deltas put and the grafts added; any other build
+        # replaces the content with the encoding of every node of the new index.  None: nothing is encoded
+        self.encoded_store: Optional[dict] = None
+        self._enc_removed: set = set()  # store ids the deltas of this build removed ...
+        self._enc_put: set = set()      # ... and the ones they put or a graft added
+
+    def _note_delta(self, delta: dict, dense: Dict[int, int], back: Optional[Dict[int, int]] = None) -> None:
+        """What a delta of the resident index means for encoded_store, in store ids (before TreeStore.apply_delta).  `back`:
+        the inverse of `dense` where the caller has it already."""
+        if self.encoded_store is None:
+            return
+        if back is None:
+            back = {i: nid for nid, i in dense.items()}
+        self._enc_removed.update(back[int(i)] for i in delta["removed"])
+        self._enc_put.update(back[int(i)] for i in delta["put_index"])
+
+    def _mirror_encoded(self, st: "_IndexState", followed: bool) -> None:
+        """encoded_store after a build: see __init__."""
+        store = self.encoded_store
+        if store is None:
+            return
+        if st.index is None:
+            store.clear()
+            return
+        dense = st._keep[4]  # store id -> node slot of the index, after any compaction
+        id_of = np.zeros(st.index.export_info()["n_nodes"], dtype=np.uint32)
+        for nid, i in dense.items():
+            id_of[i] = nid
+        if followed:
+            for nid in self._enc_removed:
+                store.pop(nid, None)
+            put = sorted(nid for nid in self._enc_put if nid in st.trees.nodes)
+            values = st.index.encode_nodes(np.array([dense[nid] for nid in put], dtype=np.uint32), node_ids=id_of)
+            store.update(zip(put, values))
+            st.device_encoded_nodes += len(put)
+        else:
+            order = sorted(dense, key=dense.get)
+            values = st.index.encode_nodes(np.array([dense[nid] for nid in order], dtype=np.uint32), node_ids=id_of)
+            store.clear()
+            store.update(zip(order, values))
 
     def n_trees(self, n: int) -> "ArroyBuilder":
         self._n_trees = int(n)
@@ -432,6 +477,8 @@ class ArroyBuilder:
         # still hold the dropped trees.
         resident = st.index
         st.index = None
+        followed = False
+        self._enc_removed, self._enc_put = set(), set()
         keep = (resident is not None and self.device_delete and n > split_after and st.trees is not None
                 and bool(st.trees.roots) and st.metadata is not None
                 and (self.device_drop
@@ -484,6 +531,7 @@ class ArroyBuilder:
                 if kept is not None:  # the resident index has followed the store: it serves the searches from here on
                     st.index, st._keep, resident = resident, kept, None
                     st.device_inserts += 1
+                    followed = True
         finally:
             if resident is not None:
                 resident.close()  # (a second close is a no-op: _incremental closes it when it is done with it)
@@ -492,6 +540,7 @@ class ArroyBuilder:
             from .dataset import Index
             st.index, st._keep = Index(ds, None, view=view), keep
             st.index_uploads += 1
+        self._mirror_encoded(st, followed)
         if self.device_audit and st.index is not None:
             _assert_audit(st.index.audit(trees=True), st.trees)
         st.metadata = {"dimensions": w.dimensions, "items": [int(i) for i in ids], "roots": list(st.trees.roots),
@@ -601,7 +650,9 @@ class ArroyBuilder:
             # sorted when no delete, which sorts them itself, follows.  A failure leaves the index unchanged: it is closed and
             # the build goes on on the host path, as after a failed insert
             try:
-                trees.apply_delta(resident.drop_trees(n_drop, sort_roots=not to_delete.size), st._keep[4])
+                delta = resident.drop_trees(n_drop, sort_roots=not to_delete.size)
+                self._note_delta(delta, st._keep[4])
+                trees.apply_delta(delta, st._keep[4])
                 st.device_drops += 1
                 n_drop = 0
             except _lib.ArroyHipError:
@@ -616,7 +667,9 @@ class ArroyBuilder:
             try:
                 dense = st._keep[4]
                 if to_delete.size:
-                    trees.apply_delta(resident.delete_items(to_delete, split_after), dense)
+                    delta = resident.delete_items(to_delete, split_after)
+                    self._note_delta(delta, dense)
+                    trees.apply_delta(delta, dense)
                     st.device_deletes += 1
             except BaseException:
                 resident.close()
@@ -645,6 +698,7 @@ class ArroyBuilder:
                 except _lib.ArroyHipError:
                     follow = False
             if delta is not None:
+                self._note_delta(delta, dense, back)
                 trees.apply_delta(delta, dense)
                 grown = {back[int(i)]: [] for i in delta["put_index"]}
             else:
@@ -677,6 +731,9 @@ class ArroyBuilder:
             try:
                 resident.graft(forest.view_struct(), tg, new_index)
                 state["dense"] = new_dense
+                if self.encoded_store is not None:
+                    for ids_of in maps:
+                        self._enc_put.update(ids_of.values())
             except _lib.ArroyHipError:
                 state["ok"] = False
         # the descendants the routing touched and that no longer fit (`fit_in_descendant`, :474-477, 787-795) are

@@ -58,6 +58,33 @@ def encode_descendants(ids) -> bytes:
     return bytes([TAG_DESCENDANTS]) + struct.pack("<II", ROARING_COOKIE, len(conts)) + pairs + offsets + b"".join(bodies)
 
 
+def values_of_export(export: dict, distance, dimensions: int, node_id_of=None) -> list:
+    """The value of every node slot of an `Index.export()` dict, in slot order: what Index.encode_nodes(None, node_ids=node_id_of)
+    returns, restated on the CPU.  A free slot (kind 0) gives b"".  Children are written as node_id_of[child] (None: the slot
+    number itself); a split node's normal is the header words of its row followed by the first vector_size bytes of the row."""
+    hs, vs = distance.header_size(), distance.vector_size(dimensions)
+    desc = export["descendants"]
+    ident = (lambda i: int(i)) if node_id_of is None else (lambda i: int(node_id_of[int(i)]))
+    out = []
+    for nd in export["nodes"]:
+        kind = int(nd["kind"])
+        if kind == 0:
+            out.append(b"")
+        elif kind == 1:
+            off = int(nd["offset"])
+            out.append(encode_descendants(desc[off:off + int(nd["count"])]))
+        elif kind == 2:
+            normal = None
+            if int(nd["has_normal"]):
+                row = int(nd["offset"])
+                hdr = np.ascontiguousarray(export["normal_headers"][row], dtype="<f4").tobytes()
+                normal = hdr.ljust(hs, b"\0")[:hs] + np.ascontiguousarray(export["normal_rows"][row], dtype=np.uint8).tobytes()[:vs]
+            out.append(encode_split(ident(nd["left"]), ident(nd["right"]), normal))
+        else:
+            raise ValueError(f"node of kind {kind}")
+    return out
+
+
 def decode_value(distance, dimensions: int, value: bytes):
     """("S", left, right, normal bytes or None) or ("D", ascending u32 array of item ids)."""
     value = bytes(value)

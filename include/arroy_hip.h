@@ -54,7 +54,7 @@ extern "C" {
                                   v7 additions: updates of a finalized dataset (ah_dataset_update_vectors / _records,
                                   ah_group_update_vectors / _records, the test aid ah_debug_update_paths);
                                   ah_index_footprint_get / ah_index_compact; ah_index_audit / ah_forest_view_audit;
-                                  ah_index_drop_trees; ah_index_create_from_encoded */
+                                  ah_index_drop_trees; ah_index_create_from_encoded; ah_index_encode_nodes */
 
 /* every entry point is exported from the shared object (it is built with -fvisibility=hidden) */
 #if defined(__GNUC__)
@@ -1218,6 +1218,39 @@ typedef struct ah_index_decode_stats {
 AH_API int ah_index_create_from_encoded(ah_dataset *ds, const uint32_t *node_ids, const uint8_t *const *values, const size_t *lens,
                                         size_t n_nodes, const uint32_t *root_ids, uint32_t n_trees, ah_index **out,
                                         ah_index_decode_stats *out_stats /* may be NULL */);
+
+/* The nodes of a resident index as the bytes LMDB stores for them (ABI v7 addition: look the symbol up) — the inverse of
+ * ah_index_create_from_encoded, for the host's store after ah_index_delete_items / ah_index_insert_items / ah_index_graft /
+ * ah_index_compact (the delta's put_index, the grafted indices) and for writing a whole resident index back.
+ * Value i is the `NodeCodec` v0.7 value (src/node.rs:229-241) of node slot node_indices[i]:
+ *   split node    [2][left u32 BE][right u32 BE] and, when the node has a normal, [D::Header][vector]
+ *                 (ah_header_size + ah_vector_size bytes, the words ah_index_export returns for its row, unchanged)
+ *   Descendants   [1] + the portable Roaring serialisation without run containers (cookie 12346)
+ * byte for byte what ah_build_forest_stream_encoded and ah_encode_descendants produce for the same node.  The children are
+ * written as the STORE's ids: node_id_of[child] (one word per node slot of the index; entries of free slots are not read)
+ * or, with node_id_of == NULL, node_id_base + child.
+ * The values lie back to back in out_values in the order listed, value i at out_value_offsets[i] ..
+ * out_value_offsets[i + 1] (n + 1 offsets, the last one the total).  The list may be in any order and may repeat an index.
+ * node_indices == NULL: every node slot 0 .. n_nodes - 1 (n is ignored, n_nodes + 1 offsets); a free slot (kind 0) gets a
+ * zero-length value.  out_values == NULL: the offsets only, as in ah_encode_descendants.
+ * Refused with AH_ERR_INVALID_ARGUMENT, all of it before the first byte is written to out_values: a listed index >= n_nodes
+ * or a listed free slot (the first offender by list position is named in ah_last_error); a split node with a child that is a
+ * free slot; a listed node or a child whose id node_id_base + index would pass 2^32 - 1; out_cap smaller than the total; a
+ * suspended index; a node whose list or normal row lies outside the index's arrays or a list that does not ascend (an index
+ * ah_index_audit does not find valid).
+ * The call reads only, like ah_index_audit: legal with live filters and concurrently with searches, not concurrent with a
+ * mutating call on the same index.  Memory: 28 bytes of device scratch per listed node (+ 4 per listed index, + 4 per node
+ * slot with node_id_of), and the values piece by piece — whole values that fit half of AH_READBACK_MB MiB, a longer value in
+ * a piece of its own — through two device halves and the calling thread's pinned buffer: never the total.  A failed
+ * allocation returns its status and holds nothing; out_value_offsets may then have been written, *out_stats not. */
+typedef struct ah_index_encode_stats {
+    uint64_t n_values, n_split, n_descendants, n_free;  /* listed values, and what they were                              */
+    uint64_t value_bytes, pieces;                       /* the total; device -> host pieces (0 with out_values == NULL)   */
+    double seconds;
+} ah_index_encode_stats;
+AH_API int ah_index_encode_nodes(ah_index *index, const uint32_t *node_indices, size_t n, const uint32_t *node_id_of,
+                                 uint32_t node_id_base, uint8_t *out_values, uint64_t out_cap,
+                                 uint64_t *out_value_offsets /* n + 1 */, ah_index_encode_stats *out_stats /* may be NULL */);
 
 /* An index outlives an update of its dataset.  An ah_index stores ITEM IDS, never row positions — its descendants are a
  * copy of the view's ids and every kernel goes from an id to its row through the dataset as it is at the time of the
