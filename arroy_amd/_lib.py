@@ -214,6 +214,15 @@ class AhIndexDecodeStats(C.Structure):
                                           "chunks")] + [("seconds_total", C.c_double), ("seconds_host_copy", C.c_double)]
 
 
+class AhIndexLegacyStats(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("split_values", "zero_normals", "headers_made", "item_children", "new_nodes")]
+
+
+# ah_node_layout by the version of the database ("v0.6" files have the v0.5 layout)
+NODE_LAYOUT_V0_7, NODE_LAYOUT_V0_5, NODE_LAYOUT_V0_4 = 0, 1, 2
+NODE_LAYOUTS = {"v0.7": NODE_LAYOUT_V0_7, "v0.6": NODE_LAYOUT_V0_5, "v0.5": NODE_LAYOUT_V0_5, "v0.4": NODE_LAYOUT_V0_4}
+
+
 class AhIndexEncodeStats(C.Structure):
     _fields_ = [(f, C.c_uint64) for f in ("n_values", "n_split", "n_descendants", "n_free", "value_bytes", "pieces")] + [
         ("seconds", C.c_double)]
@@ -298,6 +307,10 @@ SIGNATURES = {
     # a resident index from the NodeCodec bytes LMDB stores
     "ah_index_create_from_encoded": (C.c_int, [_VP, _U32P, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_size_t, _U32P, C.c_uint32,
                                                C.POINTER(C.c_void_p), C.POINTER(AhIndexDecodeStats)]),
+    # ... from the v0.4 - v0.6 node bytes, upgraded (layout: NODE_LAYOUTS)
+    "ah_index_create_from_legacy": (C.c_int, [_VP, C.c_int, _U32P, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_size_t, _U32P,
+                                              C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(AhIndexDecodeStats),
+                                              C.POINTER(AhIndexLegacyStats)]),
     # ... and the nodes of a resident index as those bytes
     "ah_index_encode_nodes": (C.c_int, [_VP, _U32P, C.c_size_t, _U32P, C.c_uint32, _VP, C.c_uint64, _U64P,
                                         C.POINTER(AhIndexEncodeStats)]),

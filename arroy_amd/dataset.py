@@ -594,11 +594,16 @@ class Index:
             _lib.check(_lib.lib().ah_index_create(dataset._h, forest._h, C.byref(self._h)))
 
     @classmethod
-    def from_encoded(cls, dataset: Dataset, node_ids, values, roots, want_stats: bool = False):
+    def from_encoded(cls, dataset: Dataset, node_ids, values, roots, want_stats: bool = False, layout="v0.7"):
         """ah_index_create_from_encoded: a resident index from the `NodeCodec` values LMDB stores for the tree nodes, as a
         cursor over the tree keys yields them — `node_ids` strictly ascending, `values[i]` the bytes of node_ids[i] (bytes or
         a uint8 array, at any address), `roots` the root node ids.  The values are decoded on the device; node i of the index
-        is the value of the i-th id.  Returns the index, with want_stats (index, ah_index_decode_stats as a dict)."""
+        is the value of the i-th id.  Returns the index, with want_stats (index, ah_index_decode_stats as a dict).
+        layout "v0.5" | "v0.6" (the same layout) | "v0.4": ah_index_create_from_legacy — the values of an older database, the
+        index the upgraded one (node_codec.upgrade_values: every Item child a new one-id Descendants node behind the nodes of
+        the values); want_stats then gives (index, decode stats, ah_index_legacy_stats as a dict)."""
+        from . import node_codec
+        layout = node_codec.layout_of(layout)
         ids = _u32(node_ids)
         arrs = [_blob_u8(v) for v in values]
         if len(arrs) != ids.size:
@@ -612,11 +617,18 @@ class Index:
         self._h = C.c_void_p()
         self._filters = weakref.WeakSet()
         st = _lib.AhIndexDecodeStats()
-        _lib.check(_lib.lib().ah_index_create_from_encoded(dataset._h, _ptr(ids) if n else None, ptrs, lens, n,
-                                                           _ptr(rt) if rt.size else None, int(rt.size), C.byref(self._h), C.byref(st)))
+        args = (_ptr(ids) if n else None, ptrs, lens, n, _ptr(rt) if rt.size else None, int(rt.size), C.byref(self._h), C.byref(st))
+        legacy = _lib.AhIndexLegacyStats()
+        if layout == node_codec.LAYOUT_V0_7:
+            _lib.check(_lib.lib().ah_index_create_from_encoded(dataset._h, *args))
+        else:
+            _lib.check(_lib.lib().ah_index_create_from_legacy(dataset._h, layout, *args, C.byref(legacy)))
         if not want_stats:
             return self
-        return self, {k: (float if k.startswith("seconds") else int)(getattr(st, k)) for k, _ in _lib.AhIndexDecodeStats._fields_}
+        stats = {k: (float if k.startswith("seconds") else int)(getattr(st, k)) for k, _ in _lib.AhIndexDecodeStats._fields_}
+        if layout == node_codec.LAYOUT_V0_7:
+            return self, stats
+        return self, stats, {k: int(getattr(legacy, k)) for k, _ in _lib.AhIndexLegacyStats._fields_}
 
     def make_filter(self, ids, sorted: bool = False) -> "Filter":
         """ah_filter_create: `QueryBuilder::candidates` as an object resident on the device, for any number of searches.

@@ -5,7 +5,8 @@ Scope: this mirror exists so that the parity tests read like the reference's own
 C ABI is exercised the way arroy's Rust host code would drive it.  It implements `Writer::build` — the full
 build, and the incremental one (updated items leave the trees, new ones are routed by `ah_route_items`,
 overgrown descendants are re-split by `ah_build_subtrees`, trees are added / dropped per `target_n_trees`) —
-and the search; LMDB, upgrades and `available_memory` batching are out of scope.  All distance / margin / split
+and the search; LMDB and `available_memory` batching are out of scope, the upgrades of the tree nodes are in
+upgrade.py, and a `Reader` opens the tree bytes of an older data file attached with `Database.attach_stored`.  All distance / margin / split
 arithmetic is done by libarroy_hip.so; the host only keeps dictionaries, a priority queue and id lists —
 exactly the split of work of the Rust integration.
 """
@@ -288,6 +289,7 @@ class _IndexState:
         self.trees: Optional[TreeStore] = None
         self.index = None    # arroy_amd.Index: dataset + tree nodes resident in HBM
         self._keep = None    # arrays the index view was built from
+        self.stored_trees = None  # (node ids, values): the tree bytes of an attached data file (Database.attach_stored)
         self.device_deletes = 0  # builds that took the updated items out of the trees on the device (Index.delete_items)
         self.device_inserts = 0  # builds that ended with the resident index still serving (Index.insert_items / graft)
         self.index_uploads = 0   # indexes made from a whole view of the store (every node, id and normal uploaded)
@@ -324,6 +326,18 @@ class Database:
 
     def _state(self, index: int) -> _IndexState:
         return self._indexes.setdefault(index, _IndexState())
+
+    def attach_stored(self, index: int, dataset: Dataset, items: Dict[ItemId, np.ndarray], roots: Sequence[int], node_ids, values) -> None:
+        """An index as an existing data file holds it: `dataset` has the items staged, `roots` are those of the metadata, and
+        `node_ids` / `values` are the tree keys and their bytes as a cursor yields them, of whatever version wrote the file.
+        Nothing is decoded here: `Reader.open(database, index, version)` opens the resident index from the bytes."""
+        st = self._state(index)
+        st.items = {int(i): np.ascontiguousarray(v, dtype=np.float32) for i, v in items.items()}
+        st.updated = set()
+        st.dataset, st.trees, st.index = dataset, None, None
+        st.stored_trees = ([int(i) for i in node_ids], list(values))
+        st.metadata = {"dimensions": dataset.dimensions, "items": sorted(st.items), "roots": [int(r) for r in roots],
+                       "distance": self.distance.name}
 
 
 class Writer:
@@ -794,7 +808,10 @@ class Reader:
         self.distance = database.distance
 
     @classmethod
-    def open(cls, database: Database, index: int) -> "Reader":  # src/reader.rs:138-200
+    def open(cls, database: Database, index: int, version="v0.7") -> "Reader":  # src/reader.rs:138-200
+        """`version`: of the database the tree bytes of an attached index (Database.attach_stored) come from — "v0.4" ..
+        "v0.7" or (major, minor, patch).  Below v0.7 the nodes are decoded from the old layout, as `Reader::database_get` does
+        through `GenericReadNodeCodecFromV0_4_0` (src/reader.rs:302-315), and the resident index is the upgraded one."""
         st = database._indexes.get(index)
         if st is None or st.metadata is None:
             raise MissingMetadata(index)
@@ -802,6 +819,13 @@ class Reader:
             raise UnmatchingDistance(st.metadata["distance"], database.distance.name)
         if st.updated:
             raise NeedBuild(index)
+        if st.index is None and st.stored_trees is not None and st.dataset is not None:
+            from .dataset import Index
+            if not isinstance(version, str):
+                major, minor = int(version[0]), int(version[1])
+                version = "v0.7" if (major, minor) >= (0, 7) else f"v{major}.{max(minor, 4)}"
+            node_ids, values = st.stored_trees
+            st.index = Index.from_encoded(st.dataset, node_ids, values, st.metadata["roots"], layout=version)
         return cls(database, index, st)
 
     def dimensions(self) -> int:
@@ -829,6 +853,9 @@ class Reader:
 
     def stats(self) -> dict:  # src/reader.rs:210-252
         tr = self._st.trees
+        if tr is None and self._st.index is not None:  # opened from stored bytes: counted on the device
+            keys = ("depth", "split_nodes", "dummy_normals", "descendants")
+            return {"leaf": self.n_items(), "tree_stats": [{k: t[k] for k in keys} for t in self._st.index.audit(trees=True)["tree_stats"]]}
         return {"leaf": self.n_items(), "tree_stats": [tr.stats(r) for r in tr.roots] if tr else []}
 
     def assert_validity(self) -> None:  # src/reader.rs:509-589

@@ -85,6 +85,117 @@ def values_of_export(export: dict, distance, dimensions: int, node_id_of=None) -
     return out
 
 
+# ---- the v0.4 - v0.6 layouts (`GenericReadNodeCodecFromV0_4_0`, src/node.rs:284-319; csrc/node_legacy.h) ------------------------
+#   split node    [2][left NodeId][right NodeId][vector], NodeId = [mode u8][item u32 BE]: 11 + vector_size bytes, no header;
+#                 `normal: None` is a vector `is_zero` accepts.  Leaf and Descendants values are those of v0.7.
+LAYOUT_V0_7, LAYOUT_V0_5, LAYOUT_V0_4 = 0, 1, 2
+LAYOUTS = {"v0.7": LAYOUT_V0_7, "v0.6": LAYOUT_V0_5, "v0.5": LAYOUT_V0_5, "v0.4": LAYOUT_V0_4}
+LEGACY_SPLIT_HEAD = 11
+
+
+def layout_of(layout) -> int:
+    """"v0.7" | "v0.6" | "v0.5" | "v0.4" or the ah_node_layout number -> the number."""
+    if isinstance(layout, str):
+        if layout not in LAYOUTS:
+            raise ValueError(f"unknown node layout {layout!r}: one of {sorted(LAYOUTS)}")
+        return LAYOUTS[layout]
+    if int(layout) not in (LAYOUT_V0_7, LAYOUT_V0_5, LAYOUT_V0_4):
+        raise ValueError(f"unknown node layout {layout}")
+    return int(layout)
+
+
+def legacy_modes(layout) -> dict:
+    """{"tree": mode byte, "item": mode byte} of a legacy layout (src/node_id.rs; v0.4: src/upgrade.rs:32-38)."""
+    layout = layout_of(layout)
+    if layout == LAYOUT_V0_7:
+        raise ValueError("the v0.7 layout has no child modes")
+    return {"tree": 1, "item": 0} if layout == LAYOUT_V0_4 else {"tree": 2, "item": 3}
+
+
+def encode_split_legacy(layout, left, right, vector_bytes: bytes) -> bytes:
+    """`left`, `right`: (mode, id) with mode "tree" | "item" (or the mode byte itself); the vector is never absent."""
+    modes = legacy_modes(layout)
+    out = bytes([TAG_SPLIT])
+    for mode, ident in (left, right):
+        out += struct.pack(">BI", modes[mode] if isinstance(mode, str) else int(mode), int(ident))
+    return out + bytes(vector_bytes)
+
+
+def vector_is_zero(distance, vector_bytes: bytes) -> bool:
+    """`is_zero`: every f32 element == 0.0 (-0.0 is zero, a NaN is not; src/unaligned_vector/f32.rs:54-56), every byte of a
+    binary-quantized vector 0 (binary_quantized.rs:71-73)."""
+    raw = np.frombuffer(bytes(vector_bytes), dtype=np.uint8)
+    if distance.binary_quantized:
+        return not bool(raw.any())
+    return not bool((raw.view("<u4") & np.uint32(0x7FFFFFFF)).any())
+
+
+def decode_legacy_value(layout, distance, dimensions: int, value: bytes):
+    """("S", (mode, left), (mode, right), vector bytes or None when is_zero accepts them) with mode "tree" | "item", or
+    ("D", ascending u32 array of item ids)."""
+    value = bytes(value)
+    if not value or value[0] != TAG_SPLIT:
+        return decode_value(distance, dimensions, value)
+    modes = {v: k for k, v in legacy_modes(layout).items()}
+    vs = distance.vector_size(dimensions)
+    if len(value) != LEGACY_SPLIT_HEAD + vs:
+        raise ValueError(f"legacy split value of {len(value)} bytes, expected {LEGACY_SPLIT_HEAD + vs}")
+    lm, left, rm, right = struct.unpack(">BIBI", value[1:11])
+    if lm not in modes or rm not in modes:
+        raise ValueError(f"child mode bytes {lm}, {rm}: neither Tree nor Item under the layout")
+    vector = value[11:]
+    return ("S", (modes[lm], left), (modes[rm], right), None if vector_is_zero(distance, vector) else vector)
+
+
+def _oracle_new_header(distance, dimensions: int):
+    """`D::new_header` of a stored vector as header bytes, by the project's CPU oracle (the reference's summation order)."""
+    from oracle import oracle as O
+
+    def new_header(vector_bytes: bytes) -> bytes:
+        v = np.frombuffer(bytes(vector_bytes), dtype=np.uint8).copy()
+        h = np.zeros(2, dtype=np.float32)
+        O.lib().ao_new_header(distance.metric, v.ctypes.data_as(O.C.c_void_p), dimensions, h.ctypes.data_as(O.C.c_void_p))
+        return h.astype("<f4").tobytes()[:distance.header_size()]
+    return new_header
+
+
+def upgrade_values(layout, node_ids, values, distance, dimensions: int, new_header=None):
+    """`upgrade::from_0_6_to_current` (src/upgrade.rs:183-270) on the tree values of one index, on the CPU: the split values are
+    visited in key order, left child before right; every Item child becomes a new Descendants node of that one id, numbered
+    last node id + 1, + 2, ... in that order; the split is rewritten in the v0.7 layout with the new ids, its normal None when
+    is_zero accepts the vector and [D::new_header(vector)][vector] otherwise.  `new_header`: vector bytes -> header bytes
+    (default: the CPU oracle's).  -> (new_node_ids, the v0.7 values of every node in that order, the ids that were put: the
+    split nodes and the new nodes, in the order of the puts)."""
+    node_ids = [int(x) for x in node_ids]
+    if len(node_ids) != len(values):
+        raise ValueError(f"{len(values)} values for {len(node_ids)} node ids")
+    if any(b <= a for a, b in zip(node_ids, node_ids[1:])):
+        raise ValueError("node ids must ascend strictly")
+    if layout_of(layout) == LAYOUT_V0_7:
+        return node_ids, [bytes(v) for v in values], []
+    new_header = new_header or _oracle_new_header(distance, dimensions)
+    last = node_ids[-1] if node_ids else 0
+    out, put, new_ids, new_values = [], [], [], []
+    for nid, value in zip(node_ids, values):
+        dec = decode_legacy_value(layout, distance, dimensions, value)
+        if dec[0] != "S":
+            out.append(bytes(value))
+            continue
+        children = []
+        for mode, ident in dec[1:3]:
+            if mode == "item":
+                last += 1
+                new_ids.append(last)
+                new_values.append(encode_descendants(np.array([ident], np.uint32)))
+                put.append(last)
+                ident = last
+            children.append(ident)
+        normal = None if dec[3] is None else new_header(dec[3]) + dec[3]
+        out.append(encode_split(children[0], children[1], normal))
+        put.append(nid)
+    return node_ids + new_ids, out + new_values, put
+
+
 def decode_value(distance, dimensions: int, value: bytes):
     """("S", left, right, normal bytes or None) or ("D", ascending u32 array of item ids)."""
     value = bytes(value)

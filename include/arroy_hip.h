@@ -54,7 +54,8 @@ extern "C" {
                                   v7 additions: updates of a finalized dataset (ah_dataset_update_vectors / _records,
                                   ah_group_update_vectors / _records, the test aid ah_debug_update_paths);
                                   ah_index_footprint_get / ah_index_compact; ah_index_audit / ah_forest_view_audit;
-                                  ah_index_drop_trees; ah_index_create_from_encoded; ah_index_encode_nodes */
+                                  ah_index_drop_trees; ah_index_create_from_encoded; ah_index_encode_nodes;
+                                  ah_index_create_from_legacy */
 
 /* every entry point is exported from the shared object (it is built with -fvisibility=hidden) */
 #if defined(__GNUC__)
@@ -1218,6 +1219,43 @@ typedef struct ah_index_decode_stats {
 AH_API int ah_index_create_from_encoded(ah_dataset *ds, const uint32_t *node_ids, const uint8_t *const *values, const size_t *lens,
                                         size_t n_nodes, const uint32_t *root_ids, uint32_t n_trees, ah_index **out,
                                         ah_index_decode_stats *out_stats /* may be NULL */);
+
+/* A resident index from the tree node bytes of an OLDER database, upgraded (ABI v7 addition: look the symbol up): what
+ * `Reader::open` decodes through `GenericReadNodeCodecFromV0_4_0` (src/node.rs:284-319) and `upgrade::from_0_6_to_current`
+ * (src/upgrade.rs:183-270) rewrites.  Arguments, guarantees, chunking (AH_DECODE_CHUNK_BYTES, AH_LAUNCH_MAX_ITEMS) and refusals
+ * are those of ah_index_create_from_encoded, and with AH_NODE_LAYOUT_V0_7 the call IS ah_index_create_from_encoded, through the
+ * same code.  Under the two legacy layouts Descendants values are unchanged and a split value is
+ *   [2][left NodeId][right NodeId][vector]     1 + 5 + 5 + ah_vector_size bytes, no header; NodeId = [mode u8][item u32 BE]
+ * A child's mode is Tree or Item — Tree = 2, Item = 3 under AH_NODE_LAYOUT_V0_5 (v0.5 and v0.6), Item = 0, Tree = 1 under
+ * AH_NODE_LAYOUT_V0_4 — and an Item child points straight at a stored item.  A normal is never absent: `normal: None` was stored
+ * as a vector `is_zero` accepts (f32: every element == 0.0, so -0.0 is zero and a NaN is not; binary-quantized: every byte 0).
+ * A normal that is not zero gets `D::new_header(vector)`, made by the code that makes the headers of ah_dataset_upload_vectors:
+ * the norm for Cosine and BinaryQuantizedCosine, all zeros for the other metrics (a Euclidean or Manhattan bias is 0, as in the
+ * reference on such files).
+ * The index is the UPGRADED one — array for array under ah_index_export / ah_index_export_info / ah_index_footprint_get what
+ * ah_index_create_from_encoded makes of the values `from_0_6_to_current` writes: node i < n_nodes is value i; every Item child,
+ * taken in node order and left before right, becomes a Descendants node of that one id at slot n_nodes + j (j = 0, 1, ...), its
+ * list appended to the descendants in that order; normal rows exist only for normals that are not zero.  Everything is done on
+ * the device: the host copies the bytes and reads none.
+ * Writing the upgraded database back needs no further entry point: ah_index_encode_nodes(index, NULL, ..., node_id_of) with
+ * node_id_of = node_ids followed by last node id + 1 + j for the new slots yields the v0.7 values, of which the split slots and
+ * the new slots are what `from_0_6_to_current` puts.
+ * Refused in addition (AH_ERR_INVALID_ARGUMENT, as above): an unknown layout; a split value that is not 11 + ah_vector_size
+ * bytes long; a child mode byte that is neither Tree nor Item under the layout; a Tree child or a root that is not among
+ * node_ids; n_nodes + new nodes, or the ids with those of the new nodes, reaching 2^32 - 1.
+ * *out_stats describes the values as given; *out_legacy (zeroed under AH_NODE_LAYOUT_V0_7) what the legacy layout added. */
+typedef enum ah_node_layout {
+    AH_NODE_LAYOUT_V0_7 = 0,  /* what ah_index_create_from_encoded reads */
+    AH_NODE_LAYOUT_V0_5 = 1,  /* v0.5 and v0.6 */
+    AH_NODE_LAYOUT_V0_4 = 2
+} ah_node_layout;
+typedef struct ah_index_legacy_stats {
+    uint64_t split_values, zero_normals, headers_made, item_children, new_nodes;
+} ah_index_legacy_stats;
+AH_API int ah_index_create_from_legacy(ah_dataset *ds, int layout, const uint32_t *node_ids, const uint8_t *const *values,
+                                       const size_t *lens, size_t n_nodes, const uint32_t *root_ids, uint32_t n_trees,
+                                       ah_index **out, ah_index_decode_stats *out_stats /* may be NULL */,
+                                       ah_index_legacy_stats *out_legacy /* may be NULL */);
 
 /* The nodes of a resident index as the bytes LMDB stores for them (ABI v7 addition: look the symbol up) — the inverse of
  * ah_index_create_from_encoded, for the host's store after ah_index_delete_items / ah_index_insert_items / ah_index_graft /
