@@ -10,11 +10,12 @@
 // Same arithmetic and the same (OrderedFloat(distance), position) keys as the single-query path.
 #include "common.h"
 #include "device_math.h"
+#include "search_call.h"  // kTopkSortKeys, topk_batch_key_stride, topk_batch_supported
 
 namespace ah {
 
 static constexpr int kBlock = 256;
-static constexpr uint32_t kChunk = 4096;   // keys per LDS sort (32 KiB)
+static constexpr uint32_t kChunk = kTopkSortKeys;  // keys per LDS sort (32 KiB)
 static constexpr uint32_t kTileCand = 512;  // candidates of one query per block (1024: 125-query submissions 3 % slower, 5.4 blocks per CU)
 static constexpr uint64_t kSentinel = ~0ull;
 
@@ -921,9 +922,9 @@ __global__ void k_batch_topk_emit(DataView dv, const RerankSeg *__restrict__ seg
 
 // ---- host driver --------------------------------------------------------------------------------------
 // All device pointers are caller-carved scratch (common.h: RerankBufs).
-size_t batch_key_stride(uint32_t max_n) { return (size_t)((max_n + kChunk - 1) / kChunk) * kChunk; }
+size_t batch_key_stride(uint32_t max_n) { return topk_batch_key_stride(max_n); }
 uint32_t batch_tile_candidates() { return kTileCand; }
-bool batch_supported(uint32_t k) { return k <= kChunk / 2; }
+bool batch_supported(uint32_t k) { return topk_batch_supported(k); }
 
 int launch_prepare_queries_only(const DataView &dv, const float *d_q_f32, uint32_t n_queries, uint8_t *d_qvecs,
                                 uint64_t qstride, float *d_qhdrs, hipStream_t s) {

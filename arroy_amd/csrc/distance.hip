@@ -8,6 +8,7 @@
 
 #include "common.h"
 #include "device_math.h"
+#include "search_call.h"  // kTopkSortKeys, topk_single_scratch_bytes, next_pow2
 
 namespace ah {
 
@@ -708,7 +709,7 @@ int launch_load_item_as_query(const DataView &dv, uint32_t row, void *d_qvec, fl
 // n = 1M they come from L2 and cost milliseconds; at tens of millions of items it is seconds, for an answer made of NaNs.
 // Lists with a finite distance here and there stop at the first stretch.
 // ------------------------------------------------------------------------------------------------
-static constexpr uint32_t kChunk = 4096;
+static constexpr uint32_t kChunk = kTopkSortKeys;
 static constexpr uint64_t kSentinel = ~0ull;
 
 // item >= threshold (OrderedFloat(f32::MAX), u32::MAX)
@@ -996,17 +997,7 @@ int launch_topk_small(const DataView &dv, const float *d_dist, const uint32_t *i
     return AH_OK;
 }
 
-static uint64_t next_pow2(uint64_t x) {
-    uint64_t p = 1;
-    while (p < x) p <<= 1;
-    return p;
-}
-
-size_t topk_scratch_bytes(uint64_t n, size_t k) {
-    if (k > kChunk / 2) return next_pow2(n) * 8 + 64;
-    uint64_t blocks = (n + kChunk - 1) / kChunk;
-    return (size_t)(blocks * (uint64_t)kChunk * 8 * 2 + 64);  // two ping-pong key buffers (upper bound)
-}
+size_t topk_scratch_bytes(uint64_t n, size_t k) { return topk_single_scratch_bytes(n, k); }
 
 // k = min(count, n) already; d_ids == nullptr means "positions are rows" (ids from the dataset).
 int launch_topk(const DataView &dv, const float *d_dist, const uint32_t *d_ids, uint64_t n, size_t k, void *d_scratch,

@@ -24,6 +24,7 @@
 #include "split_device.h"
 #include "screen_device.h"
 #include "search_plan.h"
+#include "search_call.h"
 
 namespace ah {
 
@@ -3632,6 +3633,15 @@ int validate_forest_view(const ah_dataset *ds, const ah_forest_view &v) {
     return AH_OK;
 }
 
+// dst += src, counter by counter: the stats blocks of arroy_hip.h are uint64_t words throughout.  Under ix->stats_mu.
+template <class Stats>
+static void add_stats(Stats &dst, const Stats &src) {
+    static_assert(sizeof(Stats) % 8 == 0 && alignof(Stats) == 8, "a block of uint64_t counters");
+    uint64_t *d = reinterpret_cast<uint64_t *>(&dst);
+    const uint64_t *s = reinterpret_cast<const uint64_t *>(&src);
+    for (size_t i = 0; i < sizeof(Stats) / 8; i++) d[i] += s[i];
+}
+
 }  // namespace ah
 
 using namespace ah;
@@ -3799,9 +3809,7 @@ struct ChunkStats {
     }
     void commit(ah_index *ix) {
         std::lock_guard<std::mutex> lk(ix->stats_mu);
-        uint64_t *dst = reinterpret_cast<uint64_t *>(&ix->stats);
-        const uint64_t *src = reinterpret_cast<const uint64_t *>(&s);
-        for (size_t i = 0; i < sizeof(ah_search_stats) / 8; i++) dst[i] += src[i];
+        add_stats(ix->stats, s);
     }
 };
 
@@ -4513,34 +4521,39 @@ int ah_route_items(ah_index *ix, const uint32_t *item_ids, size_t n, const uint6
     AH_GUARDED_END
 }
 
-// What both batched entry points derive from their arguments: the effective search_k, the capacity of one query's candidate
-// buffer, the rows of by_item queries and the most queries of one sub-batch.
-struct SearchShape {
-    uint64_t sk_eff = 0, stride = 0;
-    std::vector<uint32_t> rows;
-    size_t chunk = 1;
-};
-// The effective search_k of one query and the capacity of its candidate buffer (no refusal here: the callers name the query).
-static void search_extent(const ah_index *ix, size_t count, uint64_t search_k, uint64_t oversampling, uint64_t &sk_eff, uint64_t &stride) {
-    // search_k: reader.rs:330-335; nns can never exceed the blob (every Descendants node is popped at most once)
-    unsigned __int128 sk = search_k ? (unsigned __int128)search_k : (unsigned __int128)count * ix->n_trees;
-    sk *= oversampling ? oversampling : (metric_is_bq(ix->ds->metric) ? 3u : 1u);
-    sk_eff = (uint64_t)std::min<unsigned __int128>(sk, (unsigned __int128)ix->desc_len);
-    stride = std::min<uint64_t>(sk_eff + ix->max_desc, ix->desc_len);
-    if (stride > kSortLds) {  // the global sort path pads to a power of two
-        uint64_t p = 2;
-        while (p < stride) p <<= 1;
-        stride = p;
+// What the extent of a query (search_call.h: search_extent) reads of the index.
+static IndexExtent index_extent(const ah_index *ix) {
+    return IndexExtent{ix->n_trees, ix->desc_len, ix->max_desc, metric_is_bq(ix->ds->metric) ? 3u : 1u};
+}
+
+// The prologue ah_search_batch and search_batch_cut share, in two steps; what each entry point judges of its own (its index,
+// its filters) stands in it, in the order it always had.
+// 1. the refusals of the queries and the outputs, which need no index
+static int search_check_arguments(const float *queries, const uint32_t *query_items, const uint32_t *out_ids, const float *out_distances,
+                                  const uint32_t *out_counts) {
+    AH_REQUIRE((queries != nullptr) != (query_items != nullptr), AH_ERR_INVALID_ARGUMENT,
+               "exactly one of queries / query_items must be given");
+    AH_REQUIRE(out_ids && out_distances && out_counts, AH_ERR_INVALID_ARGUMENT, "NULL output");
+    return AH_OK;
+}
+// 2. for a call of nq > 0 queries on a live index: `count` (null: a count per query, judged by ah_search_batch_params), the
+// device, and the outputs padded in rows of `width` — the whole answer when search_nothing_to_do
+static int search_pad_outputs(const ah_index *ix, size_t nq, const size_t *count, size_t width, uint32_t *out_ids, float *out_distances,
+                              uint32_t *out_counts) {
+    if (count) AH_REQUIRE(*count > 0 && *count < 0x7FFFFFFFull, AH_ERR_INVALID_ARGUMENT, "count must be > 0");
+    AH_HIP(hipSetDevice(ix->ds->device));
+    for (size_t i = 0; i < nq * width; i++) {
+        out_ids[i] = 0xFFFFFFFFu;
+        const uint32_t nan_bits = 0xFFFFFFFFu;
+        memcpy(&out_distances[i], &nan_bits, 4);
     }
+    for (size_t q = 0; q < nq; q++) out_counts[q] = 0;
+    return AH_OK;
 }
-// Scratch one query of a sub-batch costs at that stride and count (sub-batches are bounded by ~1.5 GiB of it, and 4096 queries)
-static size_t search_query_bytes(const ah_dataset *ds, uint64_t stride, size_t count) {
-    const size_t key_bytes = batch_supported((uint32_t)std::min<size_t>(count, 0xFFFFFFFFu))
-                                 ? 2 * batch_key_stride((uint32_t)stride) * 8
-                                 : topk_scratch_bytes(stride, std::min<size_t>(count, stride)) + 64;
-    return (size_t)stride * 8 + key_bytes + count * 8 + ds->row_bytes() + 4096;
+static bool search_nothing_to_do(const ah_index *ix) {  // reader.rs:323-325; trees that hold no id
+    return ix->ds->n == 0 || ix->n_trees == 0 || ix->desc_len == 0;
 }
-static constexpr size_t kSearchChunkBytes = 1536ull << 20, kSearchChunkQueries = 4096;
+
 // The rows of by_item queries (left empty for by_vector ones).
 static int search_rows(ah_index *ix, const uint32_t *query_items, size_t nq, std::vector<uint32_t> &rows) {
     ah_dataset *ds = ix->ds;
@@ -4560,21 +4573,6 @@ static int search_rows(ah_index *ix, const uint32_t *query_items, size_t nq, std
     }
     return AH_OK;
 }
-static int search_shape(ah_index *ix, const uint32_t *query_items, size_t nq, size_t count, size_t search_k, size_t oversampling,
-                        SearchShape &out) {
-    ah_dataset *ds = ix->ds;
-    uint64_t sk_eff = 0, stride = 0;
-    search_extent(ix, count, search_k, oversampling, sk_eff, stride);
-    AH_REQUIRE(stride < 0x7FFFFFFFull, AH_ERR_INVALID_ARGUMENT, "search_k too large");
-    AH_TRY(search_rows(ix, query_items, nq, out.rows));
-    // sub-batches bounded by scratch (~1.5 GiB of candidate buffers)
-    const size_t per_query = search_query_bytes(ds, stride, count);
-    size_t chunk = std::max<size_t>(1, std::min<size_t>(nq, kSearchChunkBytes / per_query));
-    out.chunk = std::min<size_t>(chunk, kSearchChunkQueries);
-    out.sk_eff = sk_eff;
-    out.stride = stride;
-    return AH_OK;
-}
 
 // `QueryBuilder::{by_vector, by_item}` for a batch (src/reader.rs:46-75, 317-401).
 //   queries      nq x dims f32 (by_vector), or NULL with query_items = nq item ids (by_item)
@@ -4588,24 +4586,15 @@ int ah_search_batch(ah_index *ix, const float *queries, const uint32_t *query_it
     AH_REQUIRE(ix && ix->ds, AH_ERR_INVALID_ARGUMENT, "index is NULL");
     AH_INDEX_LIVE(ix);
     ah_dataset *ds = ix->ds;
-    AH_REQUIRE((queries != nullptr) != (query_items != nullptr), AH_ERR_INVALID_ARGUMENT,
-               "exactly one of queries / query_items must be given");
-    AH_REQUIRE(out_ids && out_distances && out_counts, AH_ERR_INVALID_ARGUMENT, "NULL output");
+    AH_TRY(search_check_arguments(queries, query_items, out_ids, out_distances, out_counts));
     if (nq == 0) return AH_OK;
-    AH_REQUIRE(count > 0 && count < 0x7FFFFFFFull, AH_ERR_INVALID_ARGUMENT, "count must be > 0");
-    AH_HIP(hipSetDevice(ds->device));
-    for (size_t i = 0; i < nq * count; i++) {
-        out_ids[i] = 0xFFFFFFFFu;
-        const uint32_t nan_bits = 0xFFFFFFFFu;
-        memcpy(&out_distances[i], &nan_bits, 4);
-    }
-    for (size_t q = 0; q < nq; q++) out_counts[q] = 0;
+    AH_TRY(search_pad_outputs(ix, nq, &count, count, out_ids, out_distances, out_counts));
     AH_REQUIRE(!have_filter || n_filter == 0 || filter_sorted, AH_ERR_INVALID_ARGUMENT, "filter_sorted is NULL");
-    if (ds->n == 0 || ix->n_trees == 0 || ix->desc_len == 0) return AH_OK;  // reader.rs:323-325; trees that hold no id
-    SearchShape shape;
-    AH_TRY(search_shape(ix, query_items, nq, count, search_k, oversampling, shape));
-    const uint64_t sk_eff = shape.sk_eff, stride = shape.stride;
-    const std::vector<uint32_t> &rows = shape.rows;
+    if (search_nothing_to_do(ix)) return AH_OK;
+    QueryExtent ext{};
+    AH_REQUIRE(search_extent(index_extent(ix), (uint32_t)count, search_k, oversampling, ext), AH_ERR_INVALID_ARGUMENT, "search_k too large");
+    std::vector<uint32_t> rows;
+    AH_TRY(search_rows(ix, query_items, nq, rows));
     ContextLease lease(ds);
     AH_REQUIRE(lease.c, AH_ERR_DEVICE, "cannot create a HIP stream");
     Context *ctx = lease.c;
@@ -4650,13 +4639,13 @@ int ah_search_batch(ah_index *ix, const float *queries, const uint32_t *query_it
         ix->stats.calls++;
         ix->stats.leaf_kept_passes += leaf_kept_passes;
     }
-    const size_t chunk = shape.chunk;
+    const size_t chunk = search_fixed_chunk(nq, ds->row_bytes(), ext);  // sub-batches bounded by scratch and kSearchChunkQueries
     auto run_range = [&](Context *c, size_t qa, size_t qb) -> int {
         int st = AH_OK;
         for (size_t q0 = qa; q0 < qb && st == AH_OK; q0 += chunk) {
             const size_t cn = std::min(chunk, qb - q0);
             st = search_chunk(ix, c, ChunkArgs{&knobs, queries ? queries + q0 * (size_t)ds->dims : nullptr, query_items ? rows.data() + q0 : nullptr, cn,
-                                               count, (uint32_t)sk_eff, (uint32_t)stride, d_bits, bits_len, filter_share, wave_descent, d_leaf_kept,
+                                               count, ext.sk_eff, ext.stride, d_bits, bits_len, filter_share, wave_descent, d_leaf_kept,
                                                out_ids + q0 * count, out_distances + q0 * count, out_counts + q0});
         }
         return st;
@@ -4676,6 +4665,27 @@ int ah_index_search_stats(ah_index *ix, ah_search_stats *out, int reset) {
     AH_GUARDED_END
 }
 
+// The scratch of one exhausted sub-batch, laid out by exhausted_device_layout / exhausted_pinned_layout (search_call.h).
+struct ExhaustedBufs {
+    float *d_qf32;
+    uint32_t *d_qrows;
+    uint8_t *d_qvecs;
+    float *d_qhdrs;
+    uint32_t *d_ids;
+    float *d_dist;
+    RerankSeg *d_segs;
+    uint64_t *d_ka, *d_kb;
+    uint32_t *d_oi;
+    float *d_od;
+    uint32_t *d_err;
+    float *h_q;
+    uint32_t *h_qrows;
+    RerankSeg *h_segs;
+    uint32_t *h_oi;
+    float *h_od;
+    uint32_t *h_err;
+};
+
 // An EXHAUSTED sub-batch (AH_SEARCH_EXHAUSTED; search_batch_cut): nq queries of the call, qlist[i] their positions in it, all
 // under the resident filter f with kept_total(f) <= their effective search_k.  The reference's loop then drains its queue, and
 // its candidates after sort + dedup are K(f) whatever the query: no descent, the distances of K(f) for all queries in one dense
@@ -4689,89 +4699,62 @@ static int search_exhausted(ah_index *ix, Context *ctx, const ah_filter *f, cons
     ah_dataset *ds = ix->ds;
     hipStream_t s = ctx->stream;
     const uint32_t m = (uint32_t)f->n_list;
-    const size_t qstride = (ds->row_bytes() + 255) & ~(size_t)255;
-    auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t qstride = pad256(ds->row_bytes());
     const bool big_k = !batch_supported(k);
     const size_t kstride = big_k ? (topk_scratch_bytes(m, k) + 15) / 16 : batch_key_stride(m);
-    const size_t dev_bytes = pad(nq * (size_t)ds->dims * 4) + pad(nq * 4) + nq * qstride + pad(nq * 8) + 2 * pad(nq * (size_t)m * 4) +
-                             pad(nq * sizeof(RerankSeg)) + 2 * pad(nq * kstride * 8) + 2 * pad(nq * (size_t)k * 4) + pad(SS_WORDS * 4) + 4096;
-    AH_TRY(ctx->ensure_device(dev_bytes));
-    const size_t pin_bytes = pad(nq * (size_t)ds->dims * 4) + pad(nq * 4) + pad(nq * sizeof(RerankSeg)) + 2 * pad(nq * (size_t)k * 4) +
-                             pad(SS_WORDS * 4) + 4096;
-    AH_TRY(ctx->ensure_pinned(pin_bytes));
-    uint8_t *dbase = reinterpret_cast<uint8_t *>(ctx->d_scratch), *pbase = reinterpret_cast<uint8_t *>(ctx->h_pinned);
-    size_t doff = 0, poff = 0;
-    auto dtake = [&](size_t bytes) {
-        void *p = dbase + doff;
-        doff += pad(bytes);
-        return p;
-    };
-    auto ptake = [&](size_t bytes) {
-        void *p = pbase + poff;
-        poff += pad(bytes);
-        return p;
-    };
-    float *d_qf32 = (float *)dtake(nq * (size_t)ds->dims * 4);
-    uint32_t *d_qrows = (uint32_t *)dtake(nq * 4);
-    uint8_t *d_qvecs = (uint8_t *)dtake(nq * qstride);
-    float *d_qhdrs = (float *)dtake(nq * 8);
-    uint32_t *d_ids = (uint32_t *)dtake(nq * (size_t)m * 4);
-    float *d_dist = (float *)dtake(nq * (size_t)m * 4);
-    RerankSeg *d_segs = (RerankSeg *)dtake(nq * sizeof(RerankSeg));
-    uint64_t *d_ka = (uint64_t *)dtake(nq * kstride * 8);
-    uint64_t *d_kb = (uint64_t *)dtake(nq * kstride * 8);
-    uint32_t *d_oi = (uint32_t *)dtake(nq * (size_t)k * 4);
-    float *d_od = (float *)dtake(nq * (size_t)k * 4);
-    uint32_t *d_err = (uint32_t *)dtake(SS_WORDS * 4);
-    float *h_q = (float *)ptake(nq * (size_t)ds->dims * 4);
-    uint32_t *h_qrows = (uint32_t *)ptake(nq * 4);
-    RerankSeg *h_segs = (RerankSeg *)ptake(nq * sizeof(RerankSeg));
-    uint32_t *h_oi = (uint32_t *)ptake(nq * (size_t)k * 4);
-    float *h_od = (float *)ptake(nq * (size_t)k * 4);
-    uint32_t *h_err = (uint32_t *)ptake(SS_WORDS * 4);
+    const ExhaustedSizes z{nq, ds->dims, ds->row_bytes(), m, k, kstride};
+    ExhaustedBufs b{};
+    Carver dev_size(nullptr), pin_size(nullptr);
+    exhausted_device_layout(dev_size, z, b);
+    exhausted_pinned_layout(pin_size, z, b);
+    AH_TRY(ctx->ensure_device(dev_size.off + kExhaustedSlack));
+    AH_TRY(ctx->ensure_pinned(pin_size.off + kExhaustedSlack));
+    Carver dev(ctx->d_scratch), pin(ctx->h_pinned);
+    exhausted_device_layout(dev, z, b);
+    exhausted_pinned_layout(pin, z, b);
     const DataView dv = ds->view();
     // 1. query leaves, as search_chunk prepares them
     if (queries) {
-        for (size_t i = 0; i < nq; i++) memcpy(h_q + i * (size_t)ds->dims, queries + qlist[i] * (size_t)ds->dims, (size_t)ds->dims * 4);
-        AH_HIP(hipMemcpyAsync(d_qf32, h_q, nq * (size_t)ds->dims * 4, hipMemcpyHostToDevice, s));
-        AH_TRY(launch_prepare_queries_only(dv, d_qf32, (uint32_t)nq, d_qvecs, qstride, d_qhdrs, s));
+        for (size_t i = 0; i < nq; i++) memcpy(b.h_q + i * (size_t)ds->dims, queries + qlist[i] * (size_t)ds->dims, (size_t)ds->dims * 4);
+        AH_HIP(hipMemcpyAsync(b.d_qf32, b.h_q, nq * (size_t)ds->dims * 4, hipMemcpyHostToDevice, s));
+        AH_TRY(launch_prepare_queries_only(dv, b.d_qf32, (uint32_t)nq, b.d_qvecs, qstride, b.d_qhdrs, s));
     } else {
-        for (size_t i = 0; i < nq; i++) h_qrows[i] = rows[qlist[i]];
-        AH_HIP(hipMemcpyAsync(d_qrows, h_qrows, nq * 4, hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(k_load_items_as_queries, dim3((unsigned)nq), dim3(64), 0, s, dv, d_qrows, d_qvecs, qstride, d_qhdrs);
+        for (size_t i = 0; i < nq; i++) b.h_qrows[i] = rows[qlist[i]];
+        AH_HIP(hipMemcpyAsync(b.d_qrows, b.h_qrows, nq * 4, hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(k_load_items_as_queries, dim3((unsigned)nq), dim3(64), 0, s, dv, b.d_qrows, b.d_qvecs, qstride, b.d_qhdrs);
     }
-    AH_HIP(hipMemsetAsync(d_err, 0, SS_WORDS * 4, s));
+    AH_HIP(hipMemsetAsync(b.d_err, 0, SS_WORDS * 4, s));
     // 2. the dense block K(f) x queries
-    AH_TRY(launch_shared_list_distances(dv, d_qvecs, qstride, d_qhdrs, (uint32_t)nq, f->d_list, m, m, d_ids, d_dist, d_err, s));
+    AH_TRY(launch_shared_list_distances(dv, b.d_qvecs, qstride, b.d_qhdrs, (uint32_t)nq, f->d_list, m, m, b.d_ids, b.d_dist, b.d_err, s));
     // 3. top-k + normalized distances
     uint32_t max_rounds = 0;
     for (size_t i = 0; i < nq; i++) {
-        h_segs[i] = RerankSeg{(uint64_t)i * m, m, std::min(counts[i], m)};
-        if (!big_k) max_rounds = std::max(max_rounds, batch_rounds(m, h_segs[i].k));
+        b.h_segs[i] = RerankSeg{(uint64_t)i * m, m, std::min(counts[i], m)};
+        if (!big_k) max_rounds = std::max(max_rounds, batch_rounds(m, b.h_segs[i].k));
     }
     if (big_k) {
-        AH_HIP(hipMemsetAsync(d_oi, 0xFF, nq * (size_t)k * 4, s));
-        AH_HIP(hipMemsetAsync(d_od, 0xFF, nq * (size_t)k * 4, s));
+        AH_HIP(hipMemsetAsync(b.d_oi, 0xFF, nq * (size_t)k * 4, s));
+        AH_HIP(hipMemsetAsync(b.d_od, 0xFF, nq * (size_t)k * 4, s));
         for (size_t i = 0; i < nq; i++)
-            AH_TRY(launch_topk(dv, d_dist + i * (size_t)m, d_ids + i * (size_t)m, m, h_segs[i].k, d_ka, d_oi + i * (size_t)k, d_od + i * (size_t)k, s));
+            AH_TRY(launch_topk(dv, b.d_dist + i * (size_t)m, b.d_ids + i * (size_t)m, m, b.h_segs[i].k, b.d_ka, b.d_oi + i * (size_t)k, b.d_od + i * (size_t)k, s));
     } else {
-        AH_HIP(hipMemcpyAsync(d_segs, h_segs, nq * sizeof(RerankSeg), hipMemcpyHostToDevice, s));
-        RerankBufs b{};
-        b.n_queries = (uint32_t)nq, b.d_qvecs = d_qvecs, b.qstride = qstride, b.d_qhdrs = d_qhdrs, b.d_segs = d_segs;
-        b.d_ids = d_ids, b.d_dist = d_dist, b.d_keys_a = d_ka, b.d_keys_b = d_kb, b.kstride = kstride;
-        b.d_out_ids = d_oi, b.d_out_dist = d_od, b.d_err = d_err;
-        AH_TRY(launch_batch_topk(dv, b, true, m, k, max_rounds, s));
+        AH_HIP(hipMemcpyAsync(b.d_segs, b.h_segs, nq * sizeof(RerankSeg), hipMemcpyHostToDevice, s));
+        RerankBufs rb{};
+        rb.n_queries = (uint32_t)nq, rb.d_qvecs = b.d_qvecs, rb.qstride = qstride, rb.d_qhdrs = b.d_qhdrs, rb.d_segs = b.d_segs;
+        rb.d_ids = b.d_ids, rb.d_dist = b.d_dist, rb.d_keys_a = b.d_ka, rb.d_keys_b = b.d_kb, rb.kstride = kstride;
+        rb.d_out_ids = b.d_oi, rb.d_out_dist = b.d_od, rb.d_err = b.d_err;
+        AH_TRY(launch_batch_topk(dv, rb, true, m, k, max_rounds, s));
     }
-    AH_HIP(hipMemcpyAsync(h_oi, d_oi, nq * (size_t)k * 4, hipMemcpyDeviceToHost, s));
-    AH_HIP(hipMemcpyAsync(h_od, d_od, nq * (size_t)k * 4, hipMemcpyDeviceToHost, s));
+    AH_HIP(hipMemcpyAsync(b.h_oi, b.d_oi, nq * (size_t)k * 4, hipMemcpyDeviceToHost, s));
+    AH_HIP(hipMemcpyAsync(b.h_od, b.d_od, nq * (size_t)k * 4, hipMemcpyDeviceToHost, s));
     AH_HIP(hipGetLastError());
-    AH_HIP(hipMemcpyAsync(h_err, d_err, SS_WORDS * 4, hipMemcpyDeviceToHost, s));
+    AH_HIP(hipMemcpyAsync(b.h_err, b.d_err, SS_WORDS * 4, hipMemcpyDeviceToHost, s));
     AH_HIP(hipStreamSynchronize(s));
-    AH_REQUIRE((*h_err & 1u) == 0, AH_ERR_MISSING_ITEM, "a descendant id does not exist in the dataset");
+    AH_REQUIRE((*b.h_err & 1u) == 0, AH_ERR_MISSING_ITEM, "a descendant id does not exist in the dataset");
     for (size_t i = 0; i < nq; i++) {
-        const size_t q = qlist[i], kk = h_segs[i].k;
-        memcpy(out_ids + q * out_stride, h_oi + i * (size_t)k, kk * 4);
-        memcpy(out_dists + q * out_stride, h_od + i * (size_t)k, kk * 4);
+        const size_t q = qlist[i], kk = b.h_segs[i].k;
+        memcpy(out_ids + q * out_stride, b.h_oi + i * (size_t)k, kk * 4);
+        memcpy(out_dists + q * out_stride, b.h_od + i * (size_t)k, kk * 4);
         out_counts[q] = (uint32_t)kk;
     }
     return AH_OK;
@@ -4780,28 +4763,20 @@ static int search_exhausted(ah_index *ix, Context *ctx, const ah_filter *f, cons
 // What ah_search_batch_filters and ah_search_batch_params share: a batched search with a filter per query and, when `params` is
 // given, a (count, search_k, oversampling) per query as well (the scalars are then unused; out_stride = count otherwise).
 //
-// The order: stable by filter slot, unfiltered first; inside a slot the queries whose count leaves the batched top-k
-// (batch_supported false) come last and never share a sub-batch with the others; inside such a RUN the queries are ordered
-// stably by the stride of their candidate buffer (AH_SEARCH_PARAMS_SORT=0: the caller's order).  A run of at least
-// AH_SEARCH_FILTER_GROUP_MIN queries is cut into UNIFORM sub-batches, which go through search_chunk exactly as a single-filter call
-// does (same descents, leaf tiles and screens) with the filter's resident bitmap and per-node array; the queries of the shorter
-// runs are packed, in that order, into MIXED sub-batches (SearchParams::filter_table; sorted re-rank).  A mixed sub-batch whose
-// queries happen to share one slot is a uniform one.  Every sub-batch is cut greedily under its OWN largest stride and largest
-// count: it grows while it holds at most 4096 queries and its scratch at those maxima stays within 1.5 GiB.  A sub-batch whose
-// queries do not all share one (count, effective search_k) is VARIED: search_chunk gets the two tables (VariedParams) and its
-// largest values.  With one (count, search_k, oversampling) for all queries the rule is the one ah_search_batch_filters always had.
-// (tests/test_search_filters_cpu.py and tests/test_search_params_cpu.py restate the rule in numpy.)
-struct QueryExtent {
-    uint32_t count, sk_eff, stride;
-};
+// Which queries go into which sub-batch, and in which order, is decided by search_call.h from integers alone (plan_split,
+// plan_exhausted, plan_live: the rule is written there, and tests/test_search_call_cpu.py holds it to its numpy restatements);
+// this function supplies the two facts that come from the device, moves queries and results, and dispatches.  The UNIFORM
+// sub-batches go through search_chunk exactly as a single-filter call does (same descents, leaf tiles and screens) with the
+// filter's resident bitmap and per-node array; the MIXED ones get the filters of the call as a table (SearchParams::filter_table;
+// sorted re-rank); a VARIED one gets the counts and search_ks of its queries (VariedParams) beside its largest values.  With
+// AH_SEARCH_EXHAUSTED the queries whose filter keeps at most their effective search_k ids over all leaves are answered by
+// search_exhausted, in sub-batches of one filter; a query whose K(f) is empty is answered by the padding.
 static int search_batch_cut(ah_index *ix, const float *queries, const uint32_t *query_items, size_t nq, size_t count, size_t search_k,
                             size_t oversampling, const ah_query_params *params, size_t out_stride, ah_filter *const *filters,
                             size_t n_filters, const uint32_t *filter_of_query, uint32_t *out_ids, float *out_distances,
                             uint32_t *out_counts) {
-    // (what can be judged without the index first)
-    AH_REQUIRE((queries != nullptr) != (query_items != nullptr), AH_ERR_INVALID_ARGUMENT,
-               "exactly one of queries / query_items must be given");
-    AH_REQUIRE(out_ids && out_distances && out_counts, AH_ERR_INVALID_ARGUMENT, "NULL output");
+    // 1. the prologue: what can be judged without the index first, then the index and its filters
+    AH_TRY(search_check_arguments(queries, query_items, out_ids, out_distances, out_counts));
     AH_REQUIRE(n_filters == 0 || filters, AH_ERR_INVALID_ARGUMENT, "filters is NULL");
     AH_REQUIRE(n_filters < AH_NO_FILTER && nq < 0xFFFFFFFFull, AH_ERR_INVALID_ARGUMENT, "too many filters or queries");
     AH_REQUIRE(filter_of_query || n_filters <= 1, AH_ERR_INVALID_ARGUMENT, "filter_of_query is NULL with %zu filters", n_filters);
@@ -4816,169 +4791,57 @@ static int search_batch_cut(ah_index *ix, const float *queries, const uint32_t *
         AH_REQUIRE(filters[i]->ix == ix, AH_ERR_INVALID_ARGUMENT, "filters[%zu] belongs to another index", i);
         AH_REQUIRE(!filters[i]->suspended, AH_ERR_INVALID_ARGUMENT, "filters[%zu] is suspended (ah_filter_suspend): ah_filter_resume_batch it first", i);
     }
-    ah_dataset *ds = ix->ds;
     if (nq == 0) return AH_OK;
-    if (!params) AH_REQUIRE(count > 0 && count < 0x7FFFFFFFull, AH_ERR_INVALID_ARGUMENT, "count must be > 0");
-    AH_HIP(hipSetDevice(ds->device));
-    for (size_t i = 0; i < nq * out_stride; i++) {
-        out_ids[i] = 0xFFFFFFFFu;
-        const uint32_t nan_bits = 0xFFFFFFFFu;
-        memcpy(&out_distances[i], &nan_bits, 4);
-    }
-    for (size_t q = 0; q < nq; q++) out_counts[q] = 0;
-    if (ds->n == 0 || ix->n_trees == 0 || ix->desc_len == 0) return AH_OK;  // reader.rs:323-325; trees that hold no id
-    // 0. every query's count, effective search_k and candidate-buffer stride (one of each without `params`)
+    AH_TRY(search_pad_outputs(ix, nq, params ? nullptr : &count, out_stride, out_ids, out_distances, out_counts));
+    if (search_nothing_to_do(ix)) return AH_OK;
+    ah_dataset *ds = ix->ds;
+    // 2. every query's count, effective search_k and candidate-buffer stride (one of each without `params`)
+    const IndexExtent index = index_extent(ix);
     QueryExtent one{};
     std::vector<QueryExtent> ext;
     if (params) {
         ext.resize(nq);
-        for (size_t q = 0; q < nq; q++) {
-            uint64_t sk_eff = 0, stride = 0;
-            search_extent(ix, params[q].count, params[q].search_k, params[q].oversampling, sk_eff, stride);
-            AH_REQUIRE(stride < 0x7FFFFFFFull, AH_ERR_INVALID_ARGUMENT, "params[%zu]: search_k too large", q);
-            ext[q] = QueryExtent{params[q].count, (uint32_t)sk_eff, (uint32_t)stride};
-        }
+        for (size_t q = 0; q < nq; q++)
+            AH_REQUIRE(search_extent(index, params[q].count, params[q].search_k, params[q].oversampling, ext[q]), AH_ERR_INVALID_ARGUMENT,
+                       "params[%zu]: search_k too large", q);
     } else {
-        uint64_t sk_eff = 0, stride = 0;
-        search_extent(ix, count, search_k, oversampling, sk_eff, stride);
-        AH_REQUIRE(stride < 0x7FFFFFFFull, AH_ERR_INVALID_ARGUMENT, "search_k too large");
-        one = QueryExtent{(uint32_t)count, (uint32_t)sk_eff, (uint32_t)stride};
+        AH_REQUIRE(search_extent(index, (uint32_t)count, search_k, oversampling, one), AH_ERR_INVALID_ARGUMENT, "search_k too large");
     }
-    auto ext_of = [&](size_t q) -> const QueryExtent & { return params ? ext[q] : one; };
+    const CallQueries cq{nq, params ? ext.data() : &one, params != nullptr, filter_of_query, n_filters, ds->row_bytes()};
     std::vector<uint32_t> rows;
     AH_TRY(search_rows(ix, query_items, nq, rows));
-    auto slot_of = [&](size_t q) -> uint32_t { return filter_of_query ? filter_of_query[q] : (n_filters ? 0u : AH_NO_FILTER); };
-    // 0b. AH_SEARCH_EXHAUSTED: the queries whose filter keeps at most their effective search_k ids over all leaves leave the order
-    // here.  Grouped by filter slot in the caller's order, effective counts within the batched top-k first, they are cut into
-    // sub-batches of one filter (at most 4096 queries, scratch at stride |K(f)| and the largest effective count within the
-    // chunk budget); a query whose K(f) is empty is answered by the padding.  `live`: what is left, cut exactly as ever below.
+    // 3. the plan.  AH_SEARCH_EXHAUSTED: kept_total of every filter a query names, in the order of first reference, decides which
+    // queries are exhausted; the kept list of every filter that has such a query, in the order of the slots, how they are cut
     std::optional<ContextLease> lease;
-    struct ExhaustedBatch {
-        uint32_t slot, k;  // k: the largest effective count
-        size_t a, b;       // xq[a, b)
-    };
-    std::vector<uint32_t> live, xq, xcount;
-    std::vector<ExhaustedBatch> xbatches;
-    ah_exhausted_stats xs{};
+    CallSplit split;
+    ExhaustedPlan xp;
     const bool exhaust = tun(TUN_SEARCH_EXHAUSTED) != 0 && n_filters != 0;
     if (exhaust) {
         lease.emplace(ds);
         AH_REQUIRE(lease->c, AH_ERR_DEVICE, "cannot create a HIP stream");
-        std::vector<uint64_t> total(n_filters);
-        std::vector<uint8_t> known(n_filters, 0);
-        std::vector<std::pair<uint32_t, uint32_t>> gone;  // (slot, query): ascending = by slot, the caller's order inside
-        for (size_t q = 0; q < nq; q++) {
-            const uint32_t slot = slot_of(q);
-            if (slot != AH_NO_FILTER && !known[slot]) {
-                AH_TRY(filter_kept_total(filters[slot], lease->c, total[slot]));
-                known[slot] = 1;
-            }
-            if (slot != AH_NO_FILTER && total[slot] <= ext_of(q).sk_eff) gone.push_back({slot, (uint32_t)q});
-            else live.push_back((uint32_t)q);
+        std::vector<uint64_t> kept_total(n_filters), list_len(n_filters);
+        std::vector<uint32_t> slots;
+        referenced_slots(cq, slots);
+        for (uint32_t slot : slots) AH_TRY(filter_kept_total(filters[slot], lease->c, kept_total[slot]));
+        plan_split(cq, kept_total.data(), split);
+        slots.clear();
+        split.exhausted_slots(slots);
+        for (uint32_t slot : slots) {
+            AH_TRY(filter_kept_list(filters[slot], lease->c));
+            list_len[slot] = filters[slot]->n_list;
         }
-        std::sort(gone.begin(), gone.end());
-        for (size_t g0 = 0; g0 < gone.size();) {
-            size_t g1 = g0 + 1;
-            while (g1 < gone.size() && gone[g1].first == gone[g0].first) g1++;
-            ah_filter *f = filters[gone[g0].first];
-            AH_TRY(filter_kept_list(f, lease->c));
-            const uint32_t m = (uint32_t)f->n_list;
-            xs.queries += g1 - g0;
-            if (m == 0) xs.empty_queries += g1 - g0;
-            for (int big = 0; big < 2 && m; big++) {
-                std::vector<uint32_t> part;
-                for (size_t g = g0; g < g1; g++)
-                    if ((int)!batch_supported(std::min(ext_of(gone[g].second).count, m)) == big) part.push_back(gone[g].second);
-                for (size_t c0 = 0; c0 < part.size();) {
-                    ExhaustedBatch xb{gone[g0].first, 0, xq.size(), 0};
-                    size_t c1 = c0;
-                    while (c1 < part.size() && c1 - c0 < kSearchChunkQueries) {
-                        const uint32_t kk = std::max(xb.k, std::min(ext_of(part[c1]).count, m));
-                        if (c1 > c0 && (c1 - c0 + 1) * search_query_bytes(ds, m, kk) > kSearchChunkBytes) break;
-                        xb.k = kk;
-                        c1++;
-                    }
-                    for (size_t c = c0; c < c1; c++) {
-                        xq.push_back(part[c]);
-                        xcount.push_back(ext_of(part[c]).count);
-                    }
-                    xb.b = xq.size();
-                    xbatches.push_back(xb);
-                    c0 = c1;
-                }
-            }
-            g0 = g1;
-        }
+        plan_exhausted(cq, split, list_len.data(), xp);
     }
-    const size_t nl = exhaust ? live.size() : nq;  // the queries of the order below
-    auto live_q = [&](size_t i) -> uint32_t { return exhaust ? live[i] : (uint32_t)i; };
-    // 1. the order: stable by (slot, big count, stride)
-    // (keys `slot + 1 (mod 2^32)` << 32 | big << 31 | stride, then the query: stable by construction, and no temporary buffer whose
-    // allocation std::stable_sort would survive failing — every allocation of this call that fails gives a status)
-    const bool sort_params = params && tun(TUN_SEARCH_PARAMS_SORT) != 0;
-    auto run_of = [&](size_t q) -> uint64_t {  // (slot, big): the queries of one run share it
-        return ((uint64_t)(uint32_t)(slot_of(q) + 1u) << 1) | (batch_supported(ext_of(q).count) ? 0u : 1u);
-    };
-    std::vector<uint32_t> order(nl);
-    {
-        std::vector<std::pair<uint64_t, uint32_t>> keyed(nl);
-        for (size_t i = 0; i < nl; i++) keyed[i] = {(run_of(live_q(i)) << 31) | (sort_params ? ext_of(live_q(i)).stride : 0u), live_q(i)};
-        std::sort(keyed.begin(), keyed.end());
-        for (size_t i = 0; i < nl; i++) order[i] = keyed[i].second;
-    }
-    // 2. the sub-batches, as ranges of `perm`: the uniform ones first, then what is left over (batched counts, then big ones)
-    struct SubBatch {
-        size_t a, b, off;  // perm[a, b); its results are staged from element `off`, in rows of `count`
-        bool mixed, varied;
-        uint32_t count, sk_eff, stride;  // the largest of its queries
-    };
-    const size_t group_min = (size_t)std::max<long long>(1, tun(TUN_SEARCH_FILTER_GROUP_MIN));
-    std::vector<uint32_t> perm, rest[2];
-    std::vector<SubBatch> batches;
-    perm.reserve(nq);
-    size_t staged = 0;
-    bool any_mixed = false;
-    auto cut = [&](const uint32_t *list, size_t n_list, bool may_mix) {
-        for (size_t c0 = 0; c0 < n_list;) {
-            SubBatch sb{perm.size(), 0, staged, false, false, 0, 0, 0};
-            size_t c1 = c0;
-            while (c1 < n_list && c1 - c0 < kSearchChunkQueries) {
-                const QueryExtent &e = ext_of(list[c1]);
-                const uint32_t st = std::max(sb.stride, e.stride), cn = std::max(sb.count, e.count);
-                if (c1 > c0 && (c1 - c0 + 1) * search_query_bytes(ds, st, cn) > kSearchChunkBytes) break;
-                sb.stride = st;
-                sb.count = cn;
-                sb.sk_eff = std::max(sb.sk_eff, e.sk_eff);
-                c1++;
-            }
-            for (size_t i = c0 + 1; i < c1; i++) {
-                sb.mixed = sb.mixed || (may_mix && slot_of(list[i]) != slot_of(list[c0]));
-                sb.varied = sb.varied || ext_of(list[i]).count != ext_of(list[c0]).count || ext_of(list[i]).sk_eff != ext_of(list[c0]).sk_eff;
-            }
-            sb.b = sb.a + (c1 - c0);
-            staged += (c1 - c0) * (size_t)sb.count;
-            any_mixed = any_mixed || sb.mixed;
-            batches.push_back(sb);
-            perm.insert(perm.end(), list + c0, list + c1);
-            c0 = c1;
-        }
-    };
-    for (size_t r0 = 0; r0 < nl;) {
-        size_t r1 = r0 + 1;
-        while (r1 < nl && run_of(order[r1]) == run_of(order[r0])) r1++;
-        if (r1 - r0 >= group_min) cut(order.data() + r0, r1 - r0, false);
-        else rest[run_of(order[r0]) & 1u].insert(rest[run_of(order[r0]) & 1u].end(), order.begin() + r0, order.begin() + r1);
-        r0 = r1;
-    }
-    for (const std::vector<uint32_t> &r : rest) cut(r.data(), r.size(), true);
-    // 3. queries and outputs in that order (nothing to move when the order is the caller's and every row is out_stride wide)
-    bool direct = true;
-    for (size_t i = 0; i < nl && direct; i++) direct = perm[i] == i;
-    bool identity = direct;
-    for (const SubBatch &sb : batches) direct = direct && sb.count == out_stride;
+    LivePlan lp;  // (exhaust and no live query: split.live.data() may be null, and no query is read through it)
+    plan_live(cq, exhaust ? split.live.data() : nullptr, exhaust ? split.live.size() : nq,
+              (size_t)std::max<long long>(1, tun(TUN_SEARCH_FILTER_GROUP_MIN)), params && tun(TUN_SEARCH_PARAMS_SORT) != 0, out_stride, lp);
+    const std::vector<uint32_t> &perm = lp.perm;
+    const size_t nl = perm.size();  // the live queries
+    const bool identity = lp.identity, direct = lp.direct;
+    // 4. queries and outputs in that order (nothing to move when the order is the caller's and every row is out_stride wide)
     std::vector<float> pq, pd;
     std::vector<uint32_t> prow, pi, pc, pslot(nl), pcount, psk;
-    for (size_t i = 0; i < nl; i++) pslot[i] = slot_of(perm[i]);
+    for (size_t i = 0; i < nl; i++) pslot[i] = cq.slot_of(perm[i]);
     if (params) {
         pcount.resize(nl);
         psk.resize(nl);
@@ -5003,8 +4866,8 @@ static int search_batch_cut(ah_index *ix, const float *queries, const uint32_t *
         }
     }
     if (!direct) {
-        pi.resize(staged);
-        pd.resize(staged);
+        pi.resize(lp.staged);
+        pd.resize(lp.staged);
         pc.resize(nl);
         oi = pi.data();
         od = pd.data();
@@ -5017,29 +4880,33 @@ static int search_batch_cut(ah_index *ix, const float *queries, const uint32_t *
     const size_t padded_row = pad256(ds->row_bytes());
     auto share_of = [&](uint32_t slot) { return (double)filters[slot]->stored / (double)ds->n; };  // exact: ah_filter_info
     std::vector<FilterSlot> table;
-    if (any_mixed) {  // the filters of the call, for the descents of the mixed sub-batches
+    if (lp.any_mixed) {  // the filters of the call, for the descents of the mixed sub-batches
         table.resize(n_filters);
         for (size_t i = 0; i < n_filters; i++) table[i] = FilterSlot{filters[i]->d_bits, filters[i]->len_bits, filters[i]->d_leaf_kept};
         AH_TRY(ctx->ensure_filter(n_filters * sizeof(FilterSlot)));
         AH_HIP(hipMemcpyAsync(ctx->d_filter, table.data(), n_filters * sizeof(FilterSlot), hipMemcpyHostToDevice, ctx->stream));
     }
+    // 5. the sub-batches: the exhausted ones, then the live ones
     ah_filter_stats fs{};
     fs.calls = 1;
     ah_params_stats ps{};
     ps.calls = 1;
     ps.queries = nq;
+    ah_exhausted_stats xs{};
+    xs.queries = xp.n_queries;
+    xs.empty_queries = xp.empty_queries;
     {
         std::lock_guard<std::mutex> lk(ix->stats_mu);
         ix->stats.calls++;
     }
     int st = AH_OK;
-    for (const ExhaustedBatch &xb : xbatches) {
-        st = search_exhausted(ix, ctx, filters[xb.slot], queries, query_items ? rows.data() : nullptr, xq.data() + xb.a, xb.b - xb.a,
-                              xcount.data() + xb.a, xb.k, out_stride, out_ids, out_distances, out_counts);
+    for (const ExhaustedBatch &xb : xp.batches) {
+        st = search_exhausted(ix, ctx, filters[xb.slot], queries, query_items ? rows.data() : nullptr, xp.queries.data() + xb.a, xb.b - xb.a,
+                              xp.counts.data() + xb.a, xb.k, out_stride, out_ids, out_distances, out_counts);
         xs.batches++;
         if (st != AH_OK) break;
     }
-    for (const SubBatch &sb : batches) {
+    for (const SubBatch &sb : lp.batches) {
         if (st != AH_OK) break;
         const size_t cn = sb.b - sb.a;
         const float *q_at = qsrc ? qsrc + sb.a * (size_t)ds->dims : nullptr;
@@ -5080,32 +4947,20 @@ static int search_batch_cut(ah_index *ix, const float *queries, const uint32_t *
         if (!batch_supported(sb.count)) ps.big_count_queries += cn;
         if (st != AH_OK) break;
     }
-    {
+    {  // 6. what was dispatched counts, whatever its status
         std::lock_guard<std::mutex> lk(ix->stats_mu);
-        ix->fstats.calls += fs.calls;
-        ix->fstats.uniform_batches += fs.uniform_batches;
-        ix->fstats.mixed_batches += fs.mixed_batches;
-        ix->fstats.uniform_queries += fs.uniform_queries;
-        ix->fstats.mixed_queries += fs.mixed_queries;
-        ix->xstats.queries += xs.queries;
-        ix->xstats.batches += xs.batches;
-        ix->xstats.empty_queries += xs.empty_queries;
-        if (params) {
-            ix->pstats.calls += ps.calls;
-            ix->pstats.batches += ps.batches;
-            ix->pstats.varied_batches += ps.varied_batches;
-            ix->pstats.queries += ps.queries;
-            ix->pstats.varied_queries += ps.varied_queries;
-            ix->pstats.big_count_queries += ps.big_count_queries;
-        }
+        add_stats(ix->fstats, fs);
+        add_stats(ix->xstats, xs);
+        if (params) add_stats(ix->pstats, ps);
     }
     AH_TRY(st);
+    // 7. the staged results, to where the caller wants them
     if (!direct)
-        for (const SubBatch &sb : batches)
+        for (const SubBatch &sb : lp.batches)
             for (size_t i = sb.a; i < sb.b; i++) {
-                const size_t cq = ext_of(perm[i]).count, at = sb.off + (i - sb.a) * (size_t)sb.count;
-                memcpy(out_ids + perm[i] * out_stride, oi + at, cq * 4);
-                memcpy(out_distances + perm[i] * out_stride, od + at, cq * 4);
+                const size_t n = cq.ext_of(perm[i]).count, at = sb.off + (i - sb.a) * (size_t)sb.count;
+                memcpy(out_ids + perm[i] * out_stride, oi + at, n * 4);
+                memcpy(out_distances + perm[i] * out_stride, od + at, n * 4);
                 out_counts[perm[i]] = oc[i];
             }
     return AH_OK;

@@ -315,6 +315,43 @@ def test_non_finite_distances_follow_the_positional_rule_per_query():
         w.close()
 
 
+def test_the_callers_order_with_rows_narrower_than_out_stride():
+    """A call whose sub-batches keep the caller's order but stage rows narrower than out_stride: the queries are read where the
+    caller put them and the results are copied back row by row.  Unfiltered queries, batched counts before big ones, strides
+    ascending inside each kind: two sub-batches, [0, 1] of rows 25 wide and [2, 3] of rows 3000 wide, in an output 3000 wide;
+    then the same four queries with the order switch off and an out_stride beyond the largest count, through the C ABI."""
+    w = World(D.Euclidean, O.EUCLIDEAN, False, n=400, dims=32, trees=5, nq=8)  # (the calls take its first four queries)
+    try:
+        w.slots[:] = NO_FILTER
+        w.counts[:] = [10, 25, 2049, 3000] * 2
+        w.sks[:] = [100, 400, 100, 400] * 2
+        w.overs[:] = 0
+        w.set_extents()
+        assert len(w.oracle_queries) == 8
+        for sort in (1, 0):
+            batches, want = w.planned(4, _lib.tuning_get("AH_SEARCH_FILTER_GROUP_MIN")[0], sort)
+            assert [b.tolist() for _k, b in batches] == [[0, 1], [2, 3]]  # the caller's order, and a sub-batch of rows 25 wide
+            got, pst, sst = w.call(4, AH_SEARCH_PARAMS_SORT=sort)
+            assert got[0].shape == (4, 3000)
+            w.check(got, np.arange(4), ("caller's order, narrow rows", sort))
+            assert pst == want and pst["batches"] == 2 and pst["varied_queries"] == 4 and pst["big_count_queries"] == 2, pst
+            assert sst["chunks"] == 2 and sst["queries"] == 4, sst
+        L = _lib.lib()
+        p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        params = (_lib.AhQueryParams * 4)()
+        for i in range(4):
+            params[i].search_k, params[i].count, params[i].oversampling = int(w.sks[i]), int(w.counts[i]), 0
+        q = np.ascontiguousarray(w.queries[:4])
+        stride = 3000 + 11
+        oi, od, oc = np.zeros((4, stride), np.uint32), np.zeros((4, stride), np.float32), np.full(4, 77, np.uint32)
+        with _lib.tuning(AH_SEARCH_PARAMS_SORT=0):
+            _lib.check(L.ah_search_batch_params(w.index._h, p(q), None, 4, params, stride, C.POINTER(C.c_void_p)(), 0, None, p(oi), p(od), p(oc)))
+        w.check((oi, od, oc), np.arange(4), "caller's order, out_stride beyond every count")
+        same((oi[:, :3000], od[:, :3000], oc), got, "the wider rows hold the same results")
+    finally:
+        w.close()
+
+
 def test_a_varied_call_survives_every_allocation_failure():
     """Injected allocation failures return a status by design (they are not device faults): every allocation of one varied
     ah_search_batch_params call fails once, the next call gives the right bits and no HBM is leaked."""
