@@ -19,6 +19,7 @@
 #include "../../include/arroy_hip.h"
 #include "../../include/arroy_hip_policy.h"
 #include "rerank_workspace.h"
+#include "host_parallel.h"  // parallel_run
 
 namespace ah {
 
@@ -216,22 +217,6 @@ int with_metric_of(int metric, F &&f) {
 
 // Opt a kernel in to `bytes` of dynamic LDS: the runtime is asked once per kernel instantiation, device and size (api.hip).
 int lds_opt_in(const void *kernel, int device, size_t bytes, size_t floor = 48 * 1024);
-
-// fn(0) .. fn(n - 1), fn(0) on the calling thread and the others on threads of their own.  A thread that cannot be created
-// (std::system_error) must not cross the C ABI: its share simply runs on the caller.
-template <class F>
-inline void parallel_run(unsigned n, F fn) {
-    std::vector<std::thread> pool;
-    unsigned started = 1;
-    try {
-        pool.reserve(n);
-        for (; started < n; started++) pool.emplace_back(fn, started);
-    } catch (...) {
-    }
-    if (n) fn(0u);
-    for (unsigned t = started; t < n; t++) fn(t);
-    for (auto &th : pool) th.join();
-}
 
 // ---------------------------------------------------------------------------------------------
 // Device memory: a caching allocator (api.hip).  HBM that the library has obtained is handed back to the driver only by

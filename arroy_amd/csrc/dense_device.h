@@ -17,7 +17,7 @@
 // columns wastes a factor 2^L of arithmetic, but the matrix units deliver ~50x the multiply-adds of the v_dot2c
 // row-major pass and the rows leave HBM once per LEVEL instead of once per group of 8-16 trees: 10M x 768, 100 trees,
 // level 0-3: ~3-10 ms instead of 66-70 ms.  Beyond ~64 nodes per tree the waste wins and the row-major / node-major
-// passes take over (cost model in build_batch).
+// passes take over (cost model: plan_level, level_plan.h).
 //
 // Sides stay bit-identical to the reference arithmetic: |S| > E (the same rigorous bound, with gamma_s for a chain of
 // hpitch roundings) decides the side, every other pair (~1.3 %) is marked and recomputed by k_forest_exact_pairs in the

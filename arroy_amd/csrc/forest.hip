@@ -34,16 +34,14 @@
 #include "split_device.h"
 #include "screen_device.h"
 #include "level_plan.h"
+#include "forest_records.h"  // FNode, LevelInfo, FTile, HostRec ...: the PODs host and kernels share
 #include "encode.h"
 #include "node_codec.h"
 
 namespace ah {
 
-static constexpr uint32_t kTile = 2048;  // items per tile = 32 octets x 64 items
 static constexpr int kBlock = 256;
 static constexpr int kMaxBlocks = 4096;
-
-enum { ST_PENDING = 0, ST_ACCEPTED = 1, ST_RANDOM = 2 };
 
 // The build's abort word (device memory, written by a DMA on the side stream when the caller's cancel flag turns
 // non-zero).  Every block of the margin kernels reads it first and drains if it is set: launches that start after the
@@ -63,32 +61,8 @@ struct AbortFlags {
 __device__ __forceinline__ bool abort_requested(const AbortFlags f) { return __builtin_nontemporal_load(f.dev) != 0u; }
 __device__ __forceinline__ bool gate_closed(const uint32_t *gate) { return gate != nullptr && __builtin_nontemporal_load(gate) == 0u; }
 
-struct FNode {
-    uint64_t key;      // ah_node_key_* of this node
-    uint64_t start;    // first position inside the batch permutation (absolute: tree base + offset)
-    uint32_t tree;     // tree index inside the batch
-    uint32_t count;    // items under the node
-    uint32_t n_left;   // accumulated by the margin kernel (integer atomics)
-    uint32_t attempt;  // current / final split attempt (0..3)
-    uint32_t state;    // ST_*
-    uint32_t tile_begin, n_tiles;
-    uint32_t fix;      // the parent's sides were re-drawn after its row-major pass (retry / random fallback): the rows of
-                       // this node cannot take their node index from k_forest_advance_node_of
-};
-// What the host needs to know about a level before it can launch it (written by the k_next_* kernels, read back
-// through pinned memory): sizes, the cost model's inputs, and the first node of every tree (nodes are ordered by tree).
-struct LevelInfo {
-    uint32_t n_nodes, n_tiles, n_fix, pad;
-    unsigned long long pairs;  // items under the level's nodes = margin evaluations of a first attempt
-    unsigned long long pad2;
-    // followed by uint32_t tree_first[n_trees + 1]
-};
 struct ScreenCounters {
     unsigned long long fallbacks, violations, stage8_pairs, stage8_decided, stage8b_decided, pad;
-};
-struct FTile {
-    uint32_t node;
-    uint32_t first;  // offset of the tile inside its node
 };
 
 __global__ void k_init_perm(uint32_t *perm, uint64_t n, uint32_t n_trees) {
@@ -779,12 +753,8 @@ __global__ __launch_bounds__(256) void k_stats_max(const float4 *__restrict__ st
 // units and fetch s_r (4 bytes per pair from a 40 MB array).  DotProduct has no int8 stage (its margin needs the row's header
 // anyway).  Rows that are all zero, not finite, or so small that f32 squares underflow (max|x| < 2^-40) get q = 0 and
 // s_r = inf: they are never decided here.  Sides stay identical by construction; AH_SCREEN_VERIFY checks every pair at
-// every stage.
+// every stage.  (NormalStats8, the tail of a normal's int8 record, is in forest_records.h: its size is part of a batch's sizes.)
 // ------------------------------------------------------------------------------------------------
-struct NormalStats8 {
-    float an, bn, cn, extra;    // |n~'|, |n' - n~'|, |n'| (in the column-scaled space), bias
-    float scale, cn0, pad0, pad1;  // s_n; |n| in the original space (for the reference's own rounding error)
-};
 
 // column-wise max |x| (as bits) over all rows: thread t of a block owns columns t, t + 256, ...
 __global__ __launch_bounds__(256) void k_col_maxabs(DataView dv, uint32_t *__restrict__ out_bits) {
@@ -1512,9 +1482,6 @@ __global__ __launch_bounds__(LDS_NORMALS ? (TC >= 16 ? 512 : 1024) : kBlock,
 // produce.  Three small kernels (count per block, scan of the block sums, emit) plus the tile list; the host reads back
 // only the LevelInfo block before it launches the level, the node tables follow asynchronously for the final node list.
 // ------------------------------------------------------------------------------------------------
-struct NextCounts {
-    uint32_t kids, tiles;
-};
 __device__ __forceinline__ void child_counts(const FNode &nd, uint32_t split_after, uint32_t cnt[2], uint32_t split[2]) {
     cnt[0] = nd.n_left;
     cnt[1] = nd.count - nd.n_left;
@@ -1653,7 +1620,7 @@ __global__ __launch_bounds__(256) void k_next_emit(const FNode *__restrict__ nod
     if (pairs) atomicAdd(&info->pairs, pairs);
     if (n_fix) atomicAdd(&info->n_fix, n_fix);
 }
-// A level cut into groups of trees (the tail of build_batch): per group the tiles and the items under its nodes, and its
+// A level cut into groups of trees (BatchBuild::run_tail_groups): per group the tiles and the items under its nodes, and its
 // nodes' tile indices rebased to the group's first tile — from there on the group is a level of its own over the shared
 // tile tables.  One block per group; nodes [first[g], first[g + 1]) of the level's table.
 struct GroupCuts {
@@ -1730,7 +1697,7 @@ struct HostBlob {
     size_t map_len = 0;
     int node = -1;         // host NUMA node its pages prefer (-1: none asked for)
 };
-// the host node of the device whose build is running on this thread (build_batch sets it): what fresh blobs prefer, and what
+// the host node of the device whose build is running on this thread (BatchBuild::setup_host sets it): what fresh blobs prefer, and what
 // the pool matches recycled blobs against
 static thread_local int tl_blob_node = -1;
 class HostBlobPool {
@@ -1859,15 +1826,6 @@ struct ah_forest {
 
 namespace {
 
-struct HostRec {  // one tree node, in creation (breadth-first) order
-    uint8_t kind, has_normal;
-    uint32_t tree;
-    uint32_t left = 0, right = 0;  // HostRec indices
-    uint64_t start;
-    uint32_t count;
-    uint32_t depth;
-    uint64_t normal_off = 0;  // byte offset of the normal record inside the forest's normals buffer
-};
 // The records of a build and their index vector, kept for the next build of the process like the forests' blobs (and under
 // the same switch, AH_HOST_CACHE_MB; ah_host_cache_trim frees them): 136 MB + 14 MB at 10M x 100 trees, whose fresh pages
 // used to be faulted in under the levels by the launching thread and unmapped — 11 ms — between the last copy and the return.
@@ -2957,306 +2915,374 @@ struct StreamBuild {
     uint32_t *roots = nullptr;  // the caller's out_roots
     bool encoded = false;       // ah_build_forest_stream_encoded: id_base starts at the caller's node_id_base
 };
-struct LeafRec {  // a Descendants node of a streaming build: its ids are final_perm[start, start + count)
-    uint64_t start;
-    uint32_t count, id, tree, depth;
+
+struct BlobNodeScope {  // the blobs this thread asks the pool for prefer the device's host node
+    int prev = -1;
+    bool entered = false;
+    void enter(int n) {
+        prev = tl_blob_node;
+        tl_blob_node = n;
+        entered = true;
+    }
+    ~BlobNodeScope() {
+        if (entered) tl_blob_node = prev;
+    }
+};
+struct Toucher {  // commits the pages of a fresh (still unwritten) host range in the background
+    std::thread th;
+    unsigned max_threads = 8;
+    int numa_node = -1;  // the pages are committed from the CPUs of the device's host node: first touch decides where they live
+    // [off, off + bytes) of `blob`; what a recycled blob already has committed needs no touch
+    void start(const HostBlob &blob, size_t off, size_t bytes) {
+        join();
+        const size_t lo_off = std::max(off, blob.committed), hi_off = std::min(off + bytes, blob.cap);
+        if (hi_off <= lo_off || hi_off - lo_off < (8u << 20)) return;
+        uint8_t *lo = blob.p + lo_off;
+        const size_t len = hi_off - lo_off;
+        const unsigned budget = max_threads;
+        const int node = numa_node;
+        try {
+            th = std::thread([lo, len, budget, node] {
+                (void)numa_bind_thread_to_node(node);
+                // (several threads: the 2.6 GB of the deepest level's normals must be committed within that level's
+                // ~140 ms, or the level loop waits for page faults before it can hand the chunk to the read-back worker)
+                const unsigned parts = (unsigned)std::min<size_t>(budget, std::max<size_t>(1, len >> 26));
+                parallel_run(parts, [=](unsigned p) {
+                    const size_t a = len * p / parts, b = len * (p + 1) / parts;
+                    for (size_t o = a; o < b; o += 4096) reinterpret_cast<volatile uint8_t *>(lo)[o] = 0;
+                });
+            });
+        } catch (...) {  // no thread to be had: the read-back worker faults the pages in itself
+        }
+    }
+    void join() {
+        if (th.joinable()) th.join();
+    }
+    ~Toucher() { join(); }
 };
 
-static int build_batch(ah_dataset *ds, const ah_build_options *opt, uint32_t first_tree, uint32_t n_trees,
-                       uint32_t split_after, ah_forest *forest, Context *ctx, const uint32_t *subset_ids,
-                       const uint64_t *subset_offsets, StreamBuild *sb = nullptr) {
-    const uint64_t N = ds->n;
-    const auto t_batch = std::chrono::steady_clock::now();
-    std::vector<uint64_t> tree_base(n_trees + 1, 0);
-    for (uint32_t t = 0; t < n_trees; t++)
-        tree_base[t + 1] = tree_base[t] + (subset_ids ? subset_offsets[first_tree + t + 1] - subset_offsets[first_tree + t] : N);
-    const uint64_t M = tree_base[n_trees];  // entries of the batch permutation
-    const DataView dv = ds->view();
-    hipStream_t s = ctx->stream;
-    const bool bq = metric_is_bq(ds->metric);
-    const uint64_t hdr_off = ds->row_bytes();
-    const uint64_t nstride = normal_record_stride(ds);
-    const LevelKnobs knobs = read_level_knobs();  // the tunables (common.h), read once per batch
-    const int timing = (int)tun(TUN_TIMING);
-    // AH_MARGIN_MODE (measurement aid): the kernel family for callers that leave the choice to the library
-    const uint32_t env_mode = (uint32_t)tun(TUN_MARGIN_MODE) & 0xFFFu;
-    const uint32_t mode_req = (opt->margin_mode & 0xFFFu) ? (opt->margin_mode & 0xFFFu) : env_mode;
-    const bool exact_only = (opt->margin_mode & AH_MARGIN_EXACT_ONLY) != 0 || !knobs.screen;
+using BuildClock = std::chrono::steady_clock::time_point;
+static double ms_of(BuildClock a, BuildClock b) { return std::chrono::duration<double, std::milli>(b - a).count(); }
+static double sec(BuildClock a, BuildClock b) { return std::chrono::duration<double>(b - a).count(); }
 
-    // Upper bounds known up front (every split node owns > split_after items), so nothing is reallocated
-    // between levels: nodes per level <= n_trees * N / (split_after + 1), tiles <= items / kTile + nodes.
-    const uint64_t max_nodes = M / ((uint64_t)split_after + 1) + n_trees;
-    const uint64_t max_tiles = M / kTile + n_trees + max_nodes;
+// One level from its plan to the hand-over of its node table.
+struct Level {
+    std::chrono::steady_clock::time_point t_top, t_launched, t_digested;
+    double ms_tail_prev = 0.0;
+    uint32_t n_nodes = 0, n_tiles = 0;
+    LevelPlan plan;
+    uint8_t *chunk_d = nullptr;  // its normal records on the device, and where they land in the forest's blob
+    uint64_t chunk_bytes = 0, chunk_host_off = 0;
+};
+// Where a tree group of the tail starts: a slice of the table of the level the groups were cut from.
+struct TailGroup {
+    LevelInfo info;
+    FNode *table, *other;  // the group's nodes; the table its next level is emitted into
+    uint32_t *cur, *nxt;
+    uint32_t depth, n0;    // n0: its first node in the whole level (its records: level_rec_full[n0 ...])
+};
+
+// One batch of trees, built level by level: the stages below, run in sequence by build_batch.  Its host bookkeeping (records,
+// ring, group cuts, buffer sizes) is forest_records.h; this struct owns the device side and the order of the HIP calls.
+struct BatchBuild {
+    // ---- the call and what is fixed for the batch
+    ah_dataset *ds;
+    const ah_build_options *opt;
+    uint32_t first_tree, n_trees, split_after;
+    ah_forest *forest;
+    Context *ctx;
+    const uint32_t *subset_ids;
+    const uint64_t *subset_offsets;
+    StreamBuild *sb;
+    std::chrono::steady_clock::time_point t_batch, t_setup_alloc, t_setup_pin, t_setup_rows, t_setup_screen, t_loop_end;
+    uint64_t N, M;  // rows; entries of the batch permutation
+    std::vector<uint64_t> tree_base;
+    DataView dv;
+    hipStream_t s;
+    bool bq;
+    uint64_t hdr_off, nstride;
+    LevelKnobs knobs;  // the tunables (common.h), read once per batch
+    int timing;
+    uint32_t mode_req;
+    bool exact_only, rows_allowed;
+    unsigned host_threads;
+    int numa_node = -1;
+    BatchSizes z;
+
+    // ---- what owns memory or threads.  MEMBER ORDER MATTERS: an early return (AH_TRY) destroys these in reverse order.
+    // The device buffers come first (freed last); the Touchers join before the blobs can move; Arenas and EncodeScratch are
+    // declared before the read-back worker, which is joined before the memory it reads is freed; BatchCleanup syncs the side
+    // stream before its events die; RecordsLease follows the records it hands back to the pool.
     DevBuf<uint32_t> perm_a, perm_b, final_perm, tile_left, tile_left_off, d_child, d_small;
     DevBuf<FNode> d_nodes_a, d_nodes_b, d_nodes_c;  // (c: the tail in groups of trees)
     DevBuf<GroupInfo> d_groups;
     DevBuf<FTile> d_tiles;
     DevBuf<uint64_t> masks;
     DevBuf<NextCounts> d_block_sums;
-    AH_TRY(perm_a.ensure(M));
-    AH_TRY(perm_b.ensure(M));
-    AH_TRY(final_perm.ensure(M));
-    AH_TRY(d_nodes_a.ensure(max_nodes));
-    AH_TRY(d_nodes_b.ensure(max_nodes));
-    AH_TRY(d_tiles.ensure(max_tiles));
-    AH_TRY(masks.ensure(max_tiles * 32));
-    AH_TRY(tile_left.ensure(max_tiles));
-    AH_TRY(tile_left_off.ensure(max_tiles));
-    AH_TRY(d_child.ensure(2 * max_nodes));
-    AH_TRY(d_block_sums.ensure(max_nodes / 256 + 2));
-    // small device block: [abort flag, 3 pad][ScreenCounters][LevelInfo + tree_first[n_trees + 1]]
-    const size_t info_words = (sizeof(LevelInfo) + ((size_t)n_trees + 1) * 4 + 3) / 4;
-    AH_TRY(d_small.ensure(4 + 12 + info_words));
-    const AbortFlags d_abort{d_small.p, nullptr};
-    ScreenCounters *d_counters = reinterpret_cast<ScreenCounters *>(d_small.p + 4);
-    LevelInfo *d_info = reinterpret_cast<LevelInfo *>(d_small.p + 16);
-    uint32_t *d_tree_first = reinterpret_cast<uint32_t *>(d_info + 1);
     DevBuf<uint32_t> d_tree_first_buf;  // first node of every tree of the level, gaps closed (LDS variant of the row pass)
-    AH_TRY(d_tree_first_buf.ensure((size_t)n_trees + 2));
-    // The control structures start from zeros.  Blocks come from the caching allocator with whatever their last user left in
-    // them, and a CANCELLED level lets its bookkeeping kernels run over tables its drained margin kernels never wrote: with
-    // zeros (what fresh device memory used to hold) those kernels find empty nodes and tiles; with the item indices of
-    // another build in a tile table they would scatter out of bounds.  ~0.7 GB of memsets: 0.2 ms.
-    AH_HIP(hipMemsetAsync(d_nodes_a.p, 0, max_nodes * sizeof(FNode), s));
-    AH_HIP(hipMemsetAsync(d_nodes_b.p, 0, max_nodes * sizeof(FNode), s));
-    AH_HIP(hipMemsetAsync(d_tiles.p, 0, max_tiles * sizeof(FTile), s));
-    AH_HIP(hipMemsetAsync(masks.p, 0, max_tiles * 32 * sizeof(uint64_t), s));
-    AH_HIP(hipMemsetAsync(tile_left.p, 0, max_tiles * 4, s));
-    AH_HIP(hipMemsetAsync(tile_left_off.p, 0, max_tiles * 4, s));
-    AH_HIP(hipMemsetAsync(d_child.p, 0, 2 * max_nodes * 4, s));
-    AH_HIP(hipMemsetAsync(d_block_sums.p, 0, (max_nodes / 256 + 2) * sizeof(NextCounts), s));
-    AH_HIP(hipMemsetAsync(d_tree_first_buf.p, 0, ((size_t)n_trees + 2) * 4, s));
-    const auto t_setup_alloc = std::chrono::steady_clock::now();
-    uint32_t *d_tree_first_fixed = d_tree_first_buf.p;
-    AH_HIP(hipMemsetAsync(d_small.p, 0, (16 + info_words) * 4, s));
-
-    // pinned host memory: [2 x LevelInfo block][one word for the abort flag][2 x node table][read-back bounce]
-    // pinned double buffer of the read-back worker (a streaming build hands a sink at most one half at a time)
-    const size_t kBounce = (size_t)std::min<long long>(4096, std::max<long long>(2, tun(TUN_READBACK_MB))) << 20;
-    const size_t pin_info = (info_words * 4 + 255) & ~(size_t)255;
-    const size_t pin_nodes = (max_nodes * sizeof(FNode) + 4095) & ~(size_t)4095;
-    const size_t pin_head = (3 * pin_info + 256 + 4095) & ~(size_t)4095;
-    AH_TRY(ctx->ensure_pinned(pin_head + 2 * pin_nodes + kBounce));
-    const auto t_setup_pin = std::chrono::steady_clock::now();
-    uint8_t *pin = reinterpret_cast<uint8_t *>(ctx->h_pinned);
-    LevelInfo *h_info[2] = {reinterpret_cast<LevelInfo *>(pin), reinterpret_cast<LevelInfo *>(pin + pin_info)};
-    uint32_t *h_one = reinterpret_cast<uint32_t *>(pin + 2 * pin_info);
-    *h_one = 1u;
-    uint32_t *h_tree_first = reinterpret_cast<uint32_t *>(pin + 2 * pin_info + 256);  // staging of d_tree_first_fixed
-    FNode *h_nodes[2] = {reinterpret_cast<FNode *>(pin + pin_head), reinterpret_cast<FNode *>(pin + pin_head + pin_nodes)};
-
-    // row-major margin mode (full-dataset trees, f32 metrics): node index and side byte per (tree, row)
-    const bool rows_allowed = !subset_ids && !bq && ds->dims >= 32 && n_trees >= 2 &&
-                              (mode_req != AH_MARGIN_AUTO ? mode_req != AH_MARGIN_NODE_MAJOR : knobs.rows_force != 0);
-    DevBuf<uint32_t> node_of;
+    DevBuf<uint32_t> node_of;           // row-major margin mode: node index and side byte per (tree, row)
     DevBuf<uint8_t> side_bytes;
     DevBuf<uint32_t> side_bits;
-    if (rows_allowed) {
-        AH_TRY(node_of.ensure((size_t)n_trees * N + 4));
-        // padded to whole 1 KiB windows and zeroed once: k_forest_exact_pairs scans it 16 bytes per lane for marks
-        AH_TRY(side_bytes.ensure((size_t)n_trees * N + 1024 + 16));
-        AH_HIP(hipMemsetAsync(side_bytes.p, 0, (size_t)n_trees * N + 1024 + 16, s));
-        // the same sides one bit each for the permutation-order gather of k_forest_masks_from_bytes (worth its pass from
-        // the size on at which a tree's bytes no longer sit in an L2)
-        if ((knobs.mask_bits > 0 || (knobs.mask_bits < 0 && N >= (1u << 20))) &&
-            side_bits.ensure(((size_t)n_trees * N + 31) / 32 + 4) != AH_OK)
-            (void)hipGetLastError();  // no room: the tiles gather the bytes
-    }
-    // certified binary16 screen: f32 metrics with AVX-tier rows, unless the caller (or AH_SCREEN=0) asks for f32 only
-    const auto t_setup_rows = std::chrono::steady_clock::now();
-    const bool screen = !exact_only && !bq && ds->dims >= 32 && ensure_screen(ds, s, true, true);
-    const auto t_setup_screen = std::chrono::steady_clock::now();
-    if (!exact_only && !screen && ds->screen_alloc_failed) forest->stats.screen_unavailable = 1;
-    ScreenView sv{};
-    uint64_t hstride = 0;
-    if (screen) {
-        sv.rows = ds->d_rows_h16;
-        sv.stats = ds->d_screen_stats;
-        sv.max_stats = make_float4(ds->screen_max[0], ds->screen_max[1], ds->screen_max[2], 0.0f);
-        sv.rows8 = tun(TUN_SCREEN8) != 0 ? ds->d_rows_i8 : nullptr;  // nullptr: no int8 first stage
-        sv.pitch8 = ds->pitch8;
-        sv.scale8_rows = ds->d_scale8_rows;
-        sv.max8 = make_float4(ds->screen8_max[0], ds->screen8_max[1], ds->screen8_max[2], 0.0f);
-        sv.rows8_lo = tun(TUN_SCREEN8_LO) != 0 ? ds->d_rows_i8_lo : nullptr;  // nullptr: stage 1 is the binary16 row
-        sv.max8b = make_float4(ds->screen8_max[3], ds->screen8_max[4], ds->screen8_max[2], 0.0f);
-        sv.hpitch = ds->hpitch;
-        // accumulation-error factors (screen_device.h), each with a 4x safety factor over the standard model:
-        //   screen: hpitch/16 dot2c per lane (2 roundings each) + 4 adds;  reference: dims/32 FMAs per chain, 6 adds of
-        //   the hsum tree, and a scalar tail of up to 31 multiply-adds (2 roundings each)
-        sv.gamma_s = (float)(4.0 * (2.0 * (ds->hpitch / 16) + 8.0) * 5.9604645e-8);
-        sv.gamma_r = (float)(4.0 * ((double)(ds->dims / 32) + 6.0 + 62.0) * 5.9604645e-8);
-        hstride = ((uint64_t)ds->hpitch * 2 + 16 + 127) & ~(uint64_t)127;  // whole lines, see normal_record_stride
-    }
-    const uint32_t verify = screen && knobs.screen_verify ? 1u : 0u;
-    const bool screen8 = screen && sv.rows8 != nullptr;
-    const uint64_t stride8 = screen8 ? ((2 * (uint64_t)sv.pitch8 + sizeof(NormalStats8) + 127) & ~(uint64_t)127) : 0;
-    if (!subset_ids) {
-        hipLaunchKernelGGL(k_init_perm, dim3(2048), dim3(256), 0, s, perm_a.p, N, n_trees);
-    } else if (M) {
-        const uint32_t *src = subset_ids + subset_offsets[first_tree];
-        AH_HIP(hipMemcpyAsync(perm_a.p, src, M * 4, hipMemcpyHostToDevice, s));
-        DevBuf<uint32_t> d_err;
-        AH_TRY(d_err.ensure(1));
-        AH_HIP(hipMemsetAsync(d_err.p, 0, 4, s));
-        hipLaunchKernelGGL(k_ids_to_rows, dim3(2048), dim3(256), 0, s, dv, perm_a.p, M, d_err.p);
-        uint32_t e = 0;
-        AH_HIP(hipMemcpyAsync(&e, d_err.p, 4, hipMemcpyDeviceToHost, s));
-        AH_HIP(hipStreamSynchronize(s));
-        AH_REQUIRE(e == 0, AH_ERR_MISSING_ITEM, "a sub-tree item id does not exist in the dataset");
-    }
-    AH_HIP(hipGetLastError());
-
-    // The item-id lists come back in one piece at the very end; their size is known now, so the host memory is
-    // allocated up front and its pages are touched in the background while the GPU works (first-touch faults of
-    // fresh memory, not the copy, bound a read-back of several GB).
-    const uint64_t desc_base = forest->descendants_len;
-    const int numa_node = numa_node_of_device(ds->device);
-    struct BlobNodeScope {  // the blobs this thread asks the pool for prefer the device's host node
-        int prev;
-        explicit BlobNodeScope(int n) : prev(tl_blob_node) { tl_blob_node = n; }
-        ~BlobNodeScope() { tl_blob_node = prev; }
-    } blob_node_scope(numa_node);
-    if (!sb) {  // (a streaming build hands the ids to the sink from the pinned ring: no blob)
-        AH_REQUIRE(host_blob_reserve(forest->desc_blob, (desc_base + M) * 4, desc_base * 4), AH_ERR_OUT_OF_MEMORY,
-                   "host allocation of the descendants failed");
-        forest->descendants = reinterpret_cast<uint32_t *>(forest->desc_blob.p);
-    }
-    struct Toucher {  // commits the pages of a fresh (still unwritten) host range in the background
-        std::thread th;
-        unsigned max_threads = 8;
-        int numa_node = -1;  // the pages are committed from the CPUs of the device's host node: first touch decides where they live
-        // [off, off + bytes) of `blob`; what a recycled blob already has committed needs no touch
-        void start(const HostBlob &blob, size_t off, size_t bytes) {
-            join();
-            const size_t lo_off = std::max(off, blob.committed), hi_off = std::min(off + bytes, blob.cap);
-            if (hi_off <= lo_off || hi_off - lo_off < (8u << 20)) return;
-            uint8_t *lo = blob.p + lo_off;
-            const size_t len = hi_off - lo_off;
-            const unsigned budget = max_threads;
-            const int node = numa_node;
-            try {
-                th = std::thread([lo, len, budget, node] {
-                    (void)numa_bind_thread_to_node(node);
-                    // (several threads: the 2.6 GB of the deepest level's normals must be committed within that level's
-                    // ~140 ms, or the level loop waits for page faults before it can hand the chunk to the read-back worker)
-                    const unsigned parts = (unsigned)std::min<size_t>(budget, std::max<size_t>(1, len >> 26));
-                    parallel_run(parts, [=](unsigned p) {
-                        const size_t a = len * p / parts, b = len * (p + 1) / parts;
-                        for (size_t o = a; o < b; o += 4096) reinterpret_cast<volatile uint8_t *>(lo)[o] = 0;
-                    });
-                });
-            } catch (...) {  // no thread to be had: the read-back worker faults the pages in itself
-            }
-        }
-        void join() {
-            if (th.joinable()) th.join();
-        }
-        ~Toucher() { join(); }
-    } prefault, touch_normals[2];  // [level & 1]: commits the level's normals, started one level ahead
-    const unsigned host_threads = host_thread_budget(opt);
-    prefault.max_threads = touch_normals[0].max_threads = touch_normals[1].max_threads = host_threads;
-    prefault.numa_node = touch_normals[0].numa_node = touch_normals[1].numa_node = numa_node;
-    if (!sb) prefault.start(forest->desc_blob, desc_base * 4, M * 4);
-    Arena arena, shadow_arena, shadow8_arena;  // declared before the read-back worker: it is joined before the chunks it reads are freed
-    arena.block_bytes = std::max<uint64_t>(32ull << 20, std::min<uint64_t>(2 * max_nodes * nstride, 16ull << 30));
-    shadow_arena.block_bytes = std::max<uint64_t>(16ull << 20, std::min<uint64_t>(max_nodes * std::max<uint64_t>(hstride, 16), 8ull << 30));
-    shadow8_arena.block_bytes = std::max<uint64_t>(16ull << 20, std::min<uint64_t>(max_nodes * std::max<uint64_t>(stride8, 16), 4ull << 30));
+    BlobNodeScope blob_node_scope;
+    Toucher prefault, touch_normals[2];  // [level & 1]: commits the level's normals, started one level ahead
+    Arena arena, shadow_arena, shadow8_arena;
     BatchCleanup bc;
-    AH_TRY(bc.create());
-    EncodeScratch enc_scratch;  // (declared before the read-back worker: it is joined before the buffers it encodes into are freed)
-    if (sb && sb->encoded) AH_TRY(enc_scratch.ensure(kBounce / 2));
+    EncodeScratch enc_scratch;
     Readback rb;
-    rb.enc = &enc_scratch;
-    rb.target = sb ? &sb->target : nullptr;
-    rb.copy_threads = host_threads;
-    rb.numa_node = numa_node;
-    rb.start(ds->device, pin + pin_head + 2 * pin_nodes, kBounce);
+    BatchRecords records;
+    RecordsLease records_lease;
+    TableRing ring;  // node tables on their way to the digest
 
-    // ---- level 0 on the host: the roots -----------------------------------------------------------------------------
-    std::vector<HostRec> recs;
-    std::vector<uint32_t> new_index;  // (emit_range's: record -> forest-local node index)
-    RecordsLease records_lease(recs, new_index);
-    std::vector<uint32_t> tree_root(n_trees);
-    std::vector<uint64_t> tree_count(n_trees, 1);  // nodes of every tree so far: its root, then two per digested split
-    std::vector<uint32_t> level_rec, next_rec;  // HostRec index of every node of the level being digested / of the next
-    // (room for every node of a balanced forest — leaves of split_after / 2 .. split_after items, as many split nodes — so that
-    // the vector never moves: at 10M x 100 trees the 1.7 M + 1.7 M records outgrew the former 4 / 3 x max_nodes at the last big
-    // level, and copying 136 MB of records held the launching thread for 38 ms with the device idle; untouched pages cost nothing)
-    try {
-        recs.reserve(4 * max_nodes + n_trees + 16);
-    } catch (const std::bad_alloc &) {  // (a tiny split_after on a huge dataset: grow as needed, as before)
-        recs.reserve(4 * max_nodes / 3 + 16);
-    }
-    size_t n_recs = 0;  // records in use; the vector itself is grown AHEAD of the digest (value-initialising 80 MB of fresh
-                        // pages on the thread that digests the deepest level was most of that digest's 35 ms)
+    // ---- views into d_small and the pinned block
+    AbortFlags d_abort{};
+    ScreenCounters *d_counters = nullptr;
+    LevelInfo *d_info = nullptr, *h_info[2] = {nullptr, nullptr};
+    uint32_t *d_tree_first = nullptr, *d_tree_first_fixed = nullptr, *h_one = nullptr, *h_tree_first = nullptr;
+    uint8_t *pin = nullptr, *ring_base = nullptr;
+
+    // ---- the screen
+    bool screen = false, screen8 = false;
+    ScreenView sv{};
+    uint64_t hstride = 0, stride8 = 0;
+    uint32_t verify = 0;
+
+    // ---- the level loop (run_levels); a tree group of the tail re-enters it through enter_group
     LevelInfo info{};
-    std::vector<uint32_t> tree_first(n_trees + 1, 0xFFFFFFFFu);
-    // streaming build: the Descendants nodes, one list per level of creation (each ascending in (tree, position))
-    std::vector<std::vector<LeafRec>> stream_leaves;
-    const uint32_t id_base = sb ? sb->id_base : 0u;
-    if (sb) stream_leaves.emplace_back();
-    {
-        FNode *lv = h_nodes[0];
-        for (uint32_t t = 0; t < n_trees; t++) {
-            const uint32_t cnt = (uint32_t)(tree_base[t + 1] - tree_base[t]);
-            HostRec r{};
-            r.tree = t;
-            r.start = tree_base[t];
-            r.count = cnt;
-            r.depth = 0;
-            tree_root[t] = (uint32_t)n_recs;
-            if (cnt <= split_after) {  // fit_in_descendant at the root: the tree is one Descendants node
-                r.kind = AH_NODE_DESCENDANTS;
-                if (sb) stream_leaves[0].push_back(LeafRec{r.start, cnt, id_base + (uint32_t)n_recs, first_tree + t, 0u});
-                recs.push_back(r);
-                n_recs++;
-                continue;
-            }
-            r.kind = AH_NODE_SPLIT;
-            FNode nd{};
-            nd.key = ah_node_key_root(opt->tree_seeds[first_tree + t]);
-            nd.start = tree_base[t];
-            nd.tree = t;
-            nd.count = cnt;
-            nd.tile_begin = info.n_tiles;
-            nd.n_tiles = (cnt + kTile - 1) / kTile;
-            tree_first[t] = info.n_nodes;
-            level_rec.push_back((uint32_t)n_recs);
-            recs.push_back(r);
-            n_recs++;
-            lv[info.n_nodes++] = nd;
-            info.n_tiles += nd.n_tiles;
-            info.pairs += cnt;
-        }
-        if (info.n_nodes) AH_HIP(hipMemcpyAsync(d_nodes_a.p, lv, info.n_nodes * sizeof(FNode), hipMemcpyHostToDevice, s));
+    std::vector<uint32_t> tree_first;
+    LevelShape shape{};  // the batch's part of every level's shape
+    uint32_t *cur = nullptr, *nxt = nullptr;
+    FNode *d_cur = nullptr, *d_next = nullptr;
+    uint32_t depth = 0;
+    uint32_t step = 0;  // levels launched so far: the parity of the double buffers (== depth until the tail runs in groups)
+    bool prev_rows = false;  // the previous level ran row-major: node_of / side_bytes describe it, d_child links it
+    bool abort_sent = false;
+    std::chrono::steady_clock::time_point t_prev_waited;
+    size_t cs_shared = 0;
+    int split_metric = 0;
+    uint64_t desc_base = 0, normals_base = 0, normals_bytes = 0, normals_cap = 0;
+    size_t roots_base = 0;
+
+    // ---- the tail in groups of trees (run_tail_groups)
+    bool grouped = false, fork_now = false, group_first_level = false;
+    uint32_t group_n0 = 0;
+    std::vector<uint32_t> group_tree;  // tree range of group g: [group_tree[g], group_tree[g + 1])
+    int pending_hand = -1;             // group whose item ids are final and still to be handed to the read-back worker
+    FNode *group_spare = nullptr;      // third node table of the grouped tail
+    std::deque<int> done_groups;       // groups whose tables are all digested and whose node list is still to be emitted
+
+    BatchBuild(ah_dataset *ds_, const ah_build_options *opt_, uint32_t first_tree_, uint32_t n_trees_, uint32_t split_after_,
+               ah_forest *forest_, Context *ctx_, const uint32_t *subset_ids_, const uint64_t *subset_offsets_, StreamBuild *sb_)
+        : ds(ds_), opt(opt_), first_tree(first_tree_), n_trees(n_trees_), split_after(split_after_), forest(forest_), ctx(ctx_),
+          subset_ids(subset_ids_), subset_offsets(subset_offsets_), sb(sb_), t_batch(std::chrono::steady_clock::now()), N(ds_->n),
+          tree_base(n_trees_ + 1, 0), records_lease(records.recs, records.new_index) {
+        for (uint32_t t = 0; t < n_trees; t++)
+            tree_base[t + 1] = tree_base[t] + (subset_ids ? subset_offsets[first_tree + t + 1] - subset_offsets[first_tree + t] : N);
+        M = tree_base[n_trees];
+        dv = ds->view();
+        s = ctx->stream;
+        bq = metric_is_bq(ds->metric);
+        hdr_off = ds->row_bytes();
+        nstride = normal_record_stride(ds);
+        knobs = read_level_knobs();
+        timing = (int)tun(TUN_TIMING);
+        // AH_MARGIN_MODE (measurement aid): the kernel family for callers that leave the choice to the library
+        const uint32_t env_mode = (uint32_t)tun(TUN_MARGIN_MODE) & 0xFFFu;
+        mode_req = (opt->margin_mode & 0xFFFu) ? (opt->margin_mode & 0xFFFu) : env_mode;
+        exact_only = (opt->margin_mode & AH_MARGIN_EXACT_ONLY) != 0 || !knobs.screen;
+        // row-major margin mode (full-dataset trees, f32 metrics)
+        rows_allowed = !subset_ids && !bq && ds->dims >= 32 && n_trees >= 2 &&
+                       (mode_req != AH_MARGIN_AUTO ? mode_req != AH_MARGIN_NODE_MAJOR : knobs.rows_force != 0);
+        host_threads = host_thread_budget(opt);
+        // (the shadow arenas' blocks are sized for the strides their records have WHEN a screen is up — ensure_screen decides
+        // that after the buffers exist; an arena nobody takes from never allocates)
+        const bool f32 = !bq && ds->dims >= 32;
+        z = batch_sizes(N, n_trees, M, split_after, nstride, f32 ? shadow_stride16(screen_hpitch(ds->dims)) : 0,
+                        f32 ? shadow_stride8(screen_pitch8(ds->dims)) : 0, rows_allowed,
+                        knobs.mask_bits > 0 || (knobs.mask_bits < 0 && N >= (1u << 20)), tun(TUN_READBACK_MB));
     }
 
-    uint32_t *cur = perm_a.p, *nxt = perm_b.p;
-    FNode *d_cur = d_nodes_a.p, *d_next = d_nodes_b.p;
-    AH_HIP(hipEventRecord(bc.ev_begin, s));
-    forest->stats.seconds_setup += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_batch).count();
-    if (timing) {
-        auto ms_of = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-        fprintf(stderr, "[ah] batch setup: device buffers %.1f ms, pinned %.1f ms, row-major buffers %.1f ms, screen copies %.1f ms, "
-                        "host blobs + workers + roots %.1f ms\n",
-                ms_of(t_batch, t_setup_alloc), ms_of(t_setup_alloc, t_setup_pin), ms_of(t_setup_pin, t_setup_rows),
-                ms_of(t_setup_rows, t_setup_screen), ms_of(t_setup_screen, std::chrono::steady_clock::now()));
+    // Device buffers (zeroed), the pinned block, the row-major buffers, the screen's copies, the first permutation.
+    int setup_device() {
+        AH_TRY(perm_a.ensure(z.perm));
+        AH_TRY(perm_b.ensure(z.perm));
+        AH_TRY(final_perm.ensure(z.perm));
+        AH_TRY(d_nodes_a.ensure(z.nodes));
+        AH_TRY(d_nodes_b.ensure(z.nodes));
+        AH_TRY(d_tiles.ensure(z.tiles));
+        AH_TRY(masks.ensure(z.masks));
+        AH_TRY(tile_left.ensure(z.tile_left));
+        AH_TRY(tile_left_off.ensure(z.tile_left));
+        AH_TRY(d_child.ensure(z.child));
+        AH_TRY(d_block_sums.ensure(z.block_sums));
+        // small device block: [abort flag, 3 pad][ScreenCounters][LevelInfo + tree_first[n_trees + 1]]
+        AH_TRY(d_small.ensure(4 + 12 + z.info_words));
+        d_abort = AbortFlags{d_small.p, nullptr};
+        d_counters = reinterpret_cast<ScreenCounters *>(d_small.p + 4);
+        d_info = reinterpret_cast<LevelInfo *>(d_small.p + 16);
+        d_tree_first = reinterpret_cast<uint32_t *>(d_info + 1);
+        AH_TRY(d_tree_first_buf.ensure((size_t)n_trees + 2));
+        // The control structures start from zeros.  Blocks come from the caching allocator with whatever their last user left in
+        // them, and a CANCELLED level lets its bookkeeping kernels run over tables its drained margin kernels never wrote: with
+        // zeros (what fresh device memory used to hold) those kernels find empty nodes and tiles; with the item indices of
+        // another build in a tile table they would scatter out of bounds.  ~0.7 GB of memsets: 0.2 ms.
+        AH_HIP(hipMemsetAsync(d_nodes_a.p, 0, z.nodes * sizeof(FNode), s));
+        AH_HIP(hipMemsetAsync(d_nodes_b.p, 0, z.nodes * sizeof(FNode), s));
+        AH_HIP(hipMemsetAsync(d_tiles.p, 0, z.tiles * sizeof(FTile), s));
+        AH_HIP(hipMemsetAsync(masks.p, 0, z.masks * sizeof(uint64_t), s));
+        AH_HIP(hipMemsetAsync(tile_left.p, 0, z.tile_left * 4, s));
+        AH_HIP(hipMemsetAsync(tile_left_off.p, 0, z.tile_left * 4, s));
+        AH_HIP(hipMemsetAsync(d_child.p, 0, z.child * 4, s));
+        AH_HIP(hipMemsetAsync(d_block_sums.p, 0, z.block_sums * sizeof(NextCounts), s));
+        AH_HIP(hipMemsetAsync(d_tree_first_buf.p, 0, ((size_t)n_trees + 2) * 4, s));
+        t_setup_alloc = std::chrono::steady_clock::now();
+        d_tree_first_fixed = d_tree_first_buf.p;
+        AH_HIP(hipMemsetAsync(d_small.p, 0, (16 + z.info_words) * 4, s));
+
+        // pinned host memory: [2 x LevelInfo block][one word for the abort flag][2 x node table][read-back bounce]
+        AH_TRY(ctx->ensure_pinned(z.pinned_bytes()));
+        t_setup_pin = std::chrono::steady_clock::now();
+        pin = reinterpret_cast<uint8_t *>(ctx->h_pinned);
+        h_info[0] = reinterpret_cast<LevelInfo *>(pin);
+        h_info[1] = reinterpret_cast<LevelInfo *>(pin + z.pin_info);
+        h_one = reinterpret_cast<uint32_t *>(pin + 2 * z.pin_info);
+        *h_one = 1u;
+        h_tree_first = reinterpret_cast<uint32_t *>(pin + 2 * z.pin_info + 256);  // staging of d_tree_first_fixed
+        ring_base = pin + z.pin_head;  // the two node tables, as one ring
+        ring.cap = 2 * z.pin_nodes;
+
+        if (rows_allowed) {
+            AH_TRY(node_of.ensure(z.node_of));
+            // zeroed once: k_forest_exact_pairs scans it 16 bytes per lane for marks
+            AH_TRY(side_bytes.ensure(z.side_bytes));
+            AH_HIP(hipMemsetAsync(side_bytes.p, 0, z.side_bytes, s));
+            // the same sides one bit each for the permutation-order gather of k_forest_masks_from_bytes (worth its pass from
+            // the size on at which a tree's bytes no longer sit in an L2)
+            if (z.side_bits && side_bits.ensure(z.side_bits) != AH_OK) (void)hipGetLastError();  // no room: the tiles gather the bytes
+        }
+        // certified binary16 screen: f32 metrics with AVX-tier rows, unless the caller (or AH_SCREEN=0) asks for f32 only
+        t_setup_rows = std::chrono::steady_clock::now();
+        screen = !exact_only && !bq && ds->dims >= 32 && ensure_screen(ds, s, true, true);
+        t_setup_screen = std::chrono::steady_clock::now();
+        if (!exact_only && !screen && ds->screen_alloc_failed) forest->stats.screen_unavailable = 1;
+        if (screen) {
+            sv.rows = ds->d_rows_h16;
+            sv.stats = ds->d_screen_stats;
+            sv.max_stats = make_float4(ds->screen_max[0], ds->screen_max[1], ds->screen_max[2], 0.0f);
+            sv.rows8 = tun(TUN_SCREEN8) != 0 ? ds->d_rows_i8 : nullptr;  // nullptr: no int8 first stage
+            sv.pitch8 = ds->pitch8;
+            sv.scale8_rows = ds->d_scale8_rows;
+            sv.max8 = make_float4(ds->screen8_max[0], ds->screen8_max[1], ds->screen8_max[2], 0.0f);
+            sv.rows8_lo = tun(TUN_SCREEN8_LO) != 0 ? ds->d_rows_i8_lo : nullptr;  // nullptr: stage 1 is the binary16 row
+            sv.max8b = make_float4(ds->screen8_max[3], ds->screen8_max[4], ds->screen8_max[2], 0.0f);
+            sv.hpitch = ds->hpitch;
+            // accumulation-error factors (screen_device.h), each with a 4x safety factor over the standard model:
+            //   screen: hpitch/16 dot2c per lane (2 roundings each) + 4 adds;  reference: dims/32 FMAs per chain, 6 adds of
+            //   the hsum tree, and a scalar tail of up to 31 multiply-adds (2 roundings each)
+            sv.gamma_s = (float)(4.0 * (2.0 * (ds->hpitch / 16) + 8.0) * 5.9604645e-8);
+            sv.gamma_r = (float)(4.0 * ((double)(ds->dims / 32) + 6.0 + 62.0) * 5.9604645e-8);
+            hstride = shadow_stride16(ds->hpitch);  // whole lines, see normal_record_stride
+        }
+        verify = screen && knobs.screen_verify ? 1u : 0u;
+        screen8 = screen && sv.rows8 != nullptr;
+        stride8 = screen8 ? shadow_stride8(sv.pitch8) : 0;
+        if (!subset_ids) {
+            hipLaunchKernelGGL(k_init_perm, dim3(2048), dim3(256), 0, s, perm_a.p, N, n_trees);
+        } else if (M) {
+            const uint32_t *src = subset_ids + subset_offsets[first_tree];
+            AH_HIP(hipMemcpyAsync(perm_a.p, src, M * 4, hipMemcpyHostToDevice, s));
+            DevBuf<uint32_t> d_err;
+            AH_TRY(d_err.ensure(1));
+            AH_HIP(hipMemsetAsync(d_err.p, 0, 4, s));
+            hipLaunchKernelGGL(k_ids_to_rows, dim3(2048), dim3(256), 0, s, dv, perm_a.p, M, d_err.p);
+            uint32_t e = 0;
+            AH_HIP(hipMemcpyAsync(&e, d_err.p, 4, hipMemcpyDeviceToHost, s));
+            AH_HIP(hipStreamSynchronize(s));
+            AH_REQUIRE(e == 0, AH_ERR_MISSING_ITEM, "a sub-tree item id does not exist in the dataset");
+        }
+        AH_HIP(hipGetLastError());
+        return AH_OK;
     }
-    const size_t cs_shared = (size_t)f32_space_pitch(ds->metric, ds->dims) * 4 * 3;
-    AH_REQUIRE(cs_shared <= 150 * 1024, AH_ERR_INVALID_DIMENSION, "dimensions %u too large for the LDS-resident two-means",
-               ds->dims);
-    const int split_metric = f32_space_metric(ds->metric);
-    const uint64_t normals_base = forest->normals_len;  // this batch appends its levels after earlier batches
-    uint64_t normals_bytes = 0;
-    // The host blob gets lazily committed head-room (splits in total ~1.3-1.6 x items / split_after) so that finished
-    // levels can land in their final place while the build continues; it only moves when no copy is in flight.
-    uint64_t normals_cap = forest->normals_blob.cap >= 16 ? forest->normals_blob.cap - 16 : 0;
-    auto reserve_normals = [&](uint64_t need, uint64_t landed) -> int {  // landed: bytes of earlier levels / batches to keep
+
+    // The forest's blobs, the page touchers, the arenas' block sizes, events and side stream, the read-back worker, the records.
+    int setup_host() {
+        // The item-id lists come back in one piece at the very end; their size is known now, so the host memory is
+        // allocated up front and its pages are touched in the background while the GPU works (first-touch faults of
+        // fresh memory, not the copy, bound a read-back of several GB).
+        desc_base = forest->descendants_len;
+        numa_node = numa_node_of_device(ds->device);
+        blob_node_scope.enter(numa_node);
+        if (!sb) {  // (a streaming build hands the ids to the sink from the pinned ring: no blob)
+            AH_REQUIRE(host_blob_reserve(forest->desc_blob, (desc_base + M) * 4, desc_base * 4), AH_ERR_OUT_OF_MEMORY,
+                       "host allocation of the descendants failed");
+            forest->descendants = reinterpret_cast<uint32_t *>(forest->desc_blob.p);
+        }
+        prefault.max_threads = touch_normals[0].max_threads = touch_normals[1].max_threads = host_threads;
+        prefault.numa_node = touch_normals[0].numa_node = touch_normals[1].numa_node = numa_node;
+        if (!sb) prefault.start(forest->desc_blob, desc_base * 4, M * 4);
+        arena.block_bytes = z.arena_block;
+        shadow_arena.block_bytes = z.shadow_block;
+        shadow8_arena.block_bytes = z.shadow8_block;
+        AH_TRY(bc.create());
+        if (sb && sb->encoded) AH_TRY(enc_scratch.ensure(z.bounce / 2));
+        rb.enc = &enc_scratch;
+        rb.target = sb ? &sb->target : nullptr;
+        rb.copy_threads = host_threads;
+        rb.numa_node = numa_node;
+        rb.start(ds->device, pin + z.pin_head + 2 * z.pin_nodes, z.bounce);
+        records.init(n_trees, first_tree, split_after, sb != nullptr, sb ? sb->id_base : 0u, nstride, forest->nodes.size());
+        records.reserve(z.max_nodes);
+        roots_base = forest->roots.size();
+        tree_first.assign(n_trees + 1, 0xFFFFFFFFu);
+        return AH_OK;
+    }
+
+    // Level 0 on the host (the roots), and what the level loop starts from.
+    int seed_roots() {
+        FNode *lv = reinterpret_cast<FNode *>(ring_base);
+        records.seed_roots(tree_base.data(), opt->tree_seeds + first_tree, lv, &info, tree_first.data());
+        if (info.n_nodes) AH_HIP(hipMemcpyAsync(d_nodes_a.p, lv, info.n_nodes * sizeof(FNode), hipMemcpyHostToDevice, s));
+        cur = perm_a.p, nxt = perm_b.p;
+        d_cur = d_nodes_a.p, d_next = d_nodes_b.p;
+        AH_HIP(hipEventRecord(bc.ev_begin, s));
+        forest->stats.seconds_setup += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_batch).count();
+        if (timing) {
+            fprintf(stderr, "[ah] batch setup: device buffers %.1f ms, pinned %.1f ms, row-major buffers %.1f ms, screen copies %.1f ms, "
+                            "host blobs + workers + roots %.1f ms\n",
+                    ms_of(t_batch, t_setup_alloc), ms_of(t_setup_alloc, t_setup_pin), ms_of(t_setup_pin, t_setup_rows),
+                    ms_of(t_setup_rows, t_setup_screen), ms_of(t_setup_screen, std::chrono::steady_clock::now()));
+        }
+        cs_shared = (size_t)f32_space_pitch(ds->metric, ds->dims) * 4 * 3;
+        AH_REQUIRE(cs_shared <= 150 * 1024, AH_ERR_INVALID_DIMENSION, "dimensions %u too large for the LDS-resident two-means",
+                   ds->dims);
+        split_metric = f32_space_metric(ds->metric);
+        normals_base = forest->normals_len;  // this batch appends its levels after earlier batches
+        // The host blob gets lazily committed head-room (splits in total ~1.3-1.6 x items / split_after) so that finished
+        // levels can land in their final place while the build continues; it only moves when no copy is in flight.
+        normals_cap = forest->normals_blob.cap >= 16 ? forest->normals_blob.cap - 16 : 0;
+        t_prev_waited = std::chrono::steady_clock::now();
+        shape.N = N;
+        shape.n_trees = n_trees;
+        shape.split_after = split_after;
+        shape.rec_bytes = screen ? hstride : nstride;  // bytes of one normal as the margin pass streams it
+        shape.row_bytes = ds->row_bytes();
+        shape.hpitch = ds->hpitch;
+        shape.metric = ds->metric;
+        shape.screen = screen;
+        shape.screen8 = screen8;
+        shape.rows8_lo = sv.rows8_lo != nullptr;
+        shape.screen8_quality = ds->screen8_quality;
+        shape.rows_allowed = rows_allowed;
+        shape.subset = subset_ids != nullptr;
+        shape.mode_req = mode_req;
+        return AH_OK;
+    }
+
+    int reserve_normals(uint64_t need, uint64_t landed) {  // landed: bytes of earlier levels / batches to keep
         if (need <= normals_cap) return AH_OK;
         touch_normals[0].join();  // the blob may move: nothing may be touching it
         touch_normals[1].join();
         AH_REQUIRE(rb.drain() == hipSuccess, AH_ERR_DEVICE, "device -> host copy of the normals failed");
-        uint64_t want = std::max<uint64_t>(need + need / 2, normals_base + 2 * max_nodes * nstride);
+        uint64_t want = std::max<uint64_t>(need + need / 2, normals_base + 2 * z.max_nodes * nstride);
         if (!host_blob_reserve(forest->normals_blob, want, landed)) {
             want = need;
             AH_REQUIRE(host_blob_reserve(forest->normals_blob, want, landed), AH_ERR_OUT_OF_MEMORY,
@@ -3265,38 +3291,22 @@ static int build_batch(ah_dataset *ds, const ah_build_options *opt, uint32_t fir
         forest->normals = forest->normals_blob.p;
         normals_cap = forest->normals_blob.cap - 16;
         return AH_OK;
-    };
+    }
 
-    // Digest the node table of a finished level (it arrived on the side stream): split records, children, statistics,
-    // and which HostRec every node of the next level belongs to — the same walk the device did in k_next_emit.
-    uint64_t items_routed = 0;
-    // `rec_of`: HostRec index of every node of the level (level_rec of the level-by-level loop; a slice of the parent
-    // level's list for the first level of a tree group of the tail)
-    auto digest_level = [&](uint32_t depth, uint32_t n_nodes, const FNode *tbl, uint64_t chunk_host_off, const uint8_t *chunk_dev,
-                            const uint32_t *rec_of) -> int {
-        // Children get the records base + 2 i (left) and base + 2 i + 1 (right) of node i, so the walk splits over a few
-        // threads (the deepest level of the 10M x 100-tree build has 819 000 nodes: 37 ms on one thread, more than the GPU
-        // needs for the level after it); the list of children that split again is concatenated in node order afterwards.
-        const size_t base = n_recs;
-        if (recs.size() < base + 2 * (size_t)n_nodes) recs.resize(base + 2 * (size_t)n_nodes);
-        n_recs = base + 2 * (size_t)n_nodes;
-        // (a streaming build also writes the level's 48-byte stream nodes and collects its leaves: twice the threads)
-        const unsigned n_threads = n_nodes >= 65536 ? std::min(sb ? 8u : 4u, host_threads) : 1u;
-        struct Part {
-            uint64_t evals = 0, retries = 0, routed = 0, dummies = 0;
-            uint32_t bad = 0xFFFFFFFFu;
-            std::vector<uint32_t> splits;
-            std::vector<LeafRec> leaves;  // streaming build: the children that are Descendants nodes, in node order
-            std::vector<std::pair<uint32_t, uint32_t>> runs;  // (tree, nodes of it in this part): the table is ordered by tree
-        };
-        std::vector<Part> parts(n_threads);
-        // streaming build: this level's split planes as one job for the read-back worker (record i <-> node i)
+    // ---- the node tables' way to the records ---------------------------------------------------------------------------
+    // Digest the oldest pending table (BatchRecords::digest_level), report it, and — a streaming build — send the level's
+    // split planes to the read-back worker as one job (record i <-> node i).
+    int digest_front() {
+        const PendingTable e = ring.tables.front();
+        // (copies on the side stream complete in order: the event of this parity was recorded by this table's copy or a later one)
+        AH_HIP(hipEventSynchronize(bc.ev_copy[e.step & 1]));
+        const uint32_t *rec_of = e.rec_off >= 0 ? records.level_rec_full.data() + e.rec_off : records.level_rec.data();
         StreamJob *job = nullptr;
         if (sb) {
             job = new (std::nothrow) StreamJob();
             AH_REQUIRE(job, AH_ERR_OUT_OF_MEMORY, "host allocation failed");
             job->head.kind = AH_NODE_SPLIT;
-            job->head.level = depth;
+            job->head.level = e.depth;
             job->head.normal_stride = nstride;
             job->head.normal_vector_offset = 0;
             job->head.normal_header_offset = hdr_off;
@@ -3304,101 +3314,100 @@ static int build_batch(ah_dataset *ds, const ah_build_options *opt, uint32_t fir
             job->encoded = sb->encoded;
             job->header_size = (uint32_t)ah_header_size(ds->metric);
             job->vector_size = (uint32_t)ah_vector_size(ds->metric, ds->dims);
-            if (sb->encoded && (uint64_t)id_base + base + 2 * (uint64_t)n_nodes > 0xFFFFFFFFull) {
+            if (sb->encoded && records.stream_ids_wrap(e.n_nodes)) {
                 delete job;  // (the children's ids are written into the values: they must not wrap)
                 AH_REQUIRE(false, AH_ERR_INVALID_ARGUMENT, "node_id_base + the nodes of this build pass 2^32 - 1");
             }
-            job->nodes.resize(n_nodes);
+            job->nodes.resize(e.n_nodes);
         }
-        auto walk = [&](unsigned t) {
-            Part &pt = parts[t];
-            const uint32_t lo = (uint32_t)((uint64_t)n_nodes * t / n_threads), hi = (uint32_t)((uint64_t)n_nodes * (t + 1) / n_threads);
-            pt.splits.reserve(2 * (size_t)(hi - lo));
-            if (sb) pt.leaves.reserve(2 * (size_t)(hi - lo));
-            for (uint32_t i = lo; i < hi; i++) {
-                const FNode nd = tbl[i];
-                if (nd.state == ST_PENDING || nd.n_left > nd.count) {
-                    pt.bad = std::min(pt.bad, i);
-                    continue;
-                }
-                if (pt.runs.empty() || pt.runs.back().first != nd.tree) pt.runs.push_back({nd.tree, 0u});
-                pt.runs.back().second++;
-                pt.evals += (uint64_t)(nd.attempt + 1) * nd.count;
-                pt.retries += nd.attempt;
-                pt.routed += nd.count;
-                const uint32_t rec_idx = rec_of[i];
-                recs[rec_idx].has_normal = nd.state == ST_ACCEPTED;
-                recs[rec_idx].normal_off = chunk_host_off + (uint64_t)i * nstride;
-                if (nd.state != ST_ACCEPTED) pt.dummies++;
-                const uint32_t child_cnt[2] = {nd.n_left, nd.count - nd.n_left};
-                const uint64_t child_start[2] = {nd.start, nd.start + nd.n_left};
-                for (uint32_t side = 0; side < 2; side++) {
-                    HostRec c{};
-                    c.tree = nd.tree;
-                    c.start = child_start[side];
-                    c.count = child_cnt[side];
-                    c.depth = depth + 1;
-                    const uint32_t cidx = (uint32_t)(base + 2 * (size_t)i + side);
-                    if (c.count <= split_after) {
-                        c.kind = AH_NODE_DESCENDANTS;
-                        if (sb) pt.leaves.push_back(LeafRec{c.start, c.count, id_base + cidx, first_tree + nd.tree, depth + 1});
-                    } else {
-                        c.kind = AH_NODE_SPLIT;
-                        pt.splits.push_back(cidx);
-                    }
-                    recs[cidx] = c;
-                    if (side == 0) recs[rec_idx].left = cidx;
-                    else recs[rec_idx].right = cidx;
-                }
-                if (sb) {
-                    ah_stream_node sn{};
-                    sn.id = id_base + rec_idx;
-                    sn.tree = first_tree + nd.tree;
-                    sn.kind = AH_NODE_SPLIT;
-                    sn.has_normal = nd.state == ST_ACCEPTED;
-                    sn.left = id_base + (uint32_t)(base + 2 * (size_t)i);
-                    sn.right = sn.left + 1;
-                    sn.count = nd.count;
-                    sn.depth = depth;
-                    sn.payload_offset = (uint64_t)i * nstride;
-                    job->nodes[i] = sn;
-                }
-            }
-        };
-        parallel_run(n_threads, walk);
-        if (sb) {
-            bool bad = false;
-            for (const Part &pt : parts) bad = bad || pt.bad != 0xFFFFFFFFu;
-            if (bad) {
-                delete job;
-            } else {
-                stream_leaves.emplace_back();
-                for (Part &pt : parts) stream_leaves.back().insert(stream_leaves.back().end(), pt.leaves.begin(), pt.leaves.end());
-                rb.push_stream(job, chunk_dev);  // the level's planes travel while the next levels are computed
-            }
+        const DigestResult r = records.digest_level(e.depth, e.n_nodes, reinterpret_cast<const FNode *>(ring_base + e.ring_off), e.host_off,
+                                                    rec_of, records.digest_threads(e.n_nodes, host_threads), job ? job->nodes.data() : nullptr);
+        if (r.bad != 0xFFFFFFFFu) delete job;
+        else if (job) rb.push_stream(job, e.chunk_dev);  // the level's planes travel while the next levels are computed
+        AH_REQUIRE(r.bad == 0xFFFFFFFFu, AH_ERR_DEVICE, "forest build: node %u of level %u left pending (internal error)", r.bad,
+                   e.depth);
+        forest->stats.margin_evaluations += r.evals;
+        forest->stats.retries += r.retries;
+        forest->stats.dummy_normals += r.dummies;
+        forest->stats.levels = std::max(forest->stats.levels, e.depth + 1);
+        if (opt->progress) opt->progress(opt->progress_user, e.depth + 1, records.n_recs, records.items_routed);
+        if (e.fork_parent) records.level_rec_full.swap(records.level_rec);
+        ring.tables.pop_front();
+        // a streaming build's leaves' job starts the transfer of the group's ids: at once; a node list only costs host time
+        if (e.group_done >= 0) {
+            if (sb) AH_TRY(group_complete(group_tree[e.group_done], group_tree[e.group_done + 1]));
+            else done_groups.push_back(e.group_done);
         }
-        next_rec.clear();
-        for (const Part &pt : parts) {
-            AH_REQUIRE(pt.bad == 0xFFFFFFFFu, AH_ERR_DEVICE, "forest build: node %u of level %u left pending (internal error)",
-                       pt.bad, depth);
-            forest->stats.margin_evaluations += pt.evals;
-            forest->stats.retries += pt.retries;
-            forest->stats.dummy_normals += pt.dummies;
-            items_routed += pt.routed;
-            next_rec.insert(next_rec.end(), pt.splits.begin(), pt.splits.end());
-            for (const auto &run : pt.runs) tree_count[run.first] += 2ull * run.second;
-        }
-        level_rec.swap(next_rec);
-        forest->stats.levels = std::max(forest->stats.levels, depth + 1);
-        if (opt->progress) opt->progress(opt->progress_user, depth + 1, n_recs, items_routed);
         return AH_OK;
-    };
+    }
+    // the tables a level of `pairs` margin evaluations covers (all of them: pairs = ~0)
+    int digest_under(uint64_t pairs) {
+        // host nanoseconds the level covers: 0.14 ns per pair on the device, three quarters of it at most; a table costs ~45 ns
+        // per node (four threads), a node list ~10 ns per node (eight) — both next to the read-back worker's copy threads
+        double budget = (double)pairs * 0.105;
+        // (a table of a few thousand nodes is a fraction of a millisecond: always — progress reports stay level by level)
+        while (!ring.tables.empty() && (45.0 * ring.tables.front().n_nodes <= budget || ring.tables.front().n_nodes < 16384u)) {
+            budget -= 45.0 * ring.tables.front().n_nodes;
+            AH_TRY(digest_front());
+        }
+        while (!done_groups.empty()) {
+            const uint32_t tA = group_tree[done_groups.front()], tB = group_tree[done_groups.front() + 1];
+            double nodes = 0.0;
+            for (uint32_t t = tA; t < tB; t++) nodes += (double)records.tree_count[t];
+            if (10.0 * nodes > budget) break;
+            budget -= 10.0 * nodes;
+            done_groups.pop_front();
+            AH_TRY(group_complete(tA, tB));
+        }
+        return AH_OK;
+    }
+    // Streaming build: the Descendants nodes of trees [tA, tB) as one job, in the order their ids lie in the final permutation.
+    int push_leaves_job(uint32_t tA, uint32_t tB) {
+        StreamJob *job = new (std::nothrow) StreamJob();
+        AH_REQUIRE(job, AH_ERR_OUT_OF_MEMORY, "host allocation failed");
+        job->head.kind = AH_NODE_DESCENDANTS;
+        job->head.normal_stride = nstride;
+        job->head.normal_header_offset = hdr_off;
+        job->encoded = sb->encoded;
+        records.leaves_of(tA, tB, host_threads, job->nodes);
+        rb.push_stream(job, final_perm.p);
+        return AH_OK;
+    }
+    // The item ids of trees [tA, tB) are final (every kernel that writes them has been waited for): rows -> item ids where the
+    // two differ (on the side stream: the main one is busy with the next group), then — the blob's slice of a materialised
+    // forest — to the worker.  (A streaming build hands them over as the leaves' job, once the group's tables are digested.)
+    int hand_over_ids(uint32_t tA, uint32_t tB) {
+        const uint64_t a = tree_base[tA], b = tree_base[tB];
+        if (b > a && !ds->identity_ids) {
+            hipLaunchKernelGGL(k_rows_to_ids, dim3(2048), dim3(256), 0, bc.side, final_perm.p + a, b - a, ds->d_ids);
+            AH_HIP(hipStreamSynchronize(bc.side));
+        }
+        if (sb) return AH_OK;
+        prefault.join();
+        rb.push(forest->descendants + desc_base + a, final_perm.p + a, (b - a) * 4);
+        return AH_OK;
+    }
+    int hand_over_pending() {
+        if (pending_hand < 0) return AH_OK;
+        const int g = pending_hand;
+        pending_hand = -1;
+        return hand_over_ids(group_tree[g], group_tree[g + 1]);
+    }
+    // the post-order node list of trees [tA, tB) (BatchRecords::emit_range); a streaming build has none
+    int emit_range(uint32_t tA, uint32_t tB) {
+        if (sb) return AH_OK;
+        AH_REQUIRE(records.emit_range(tA, tB, host_threads, forest->nodes, forest->roots, roots_base, desc_base), AH_ERR_DEVICE,
+                   "forest build: trees emitted out of order (internal error)");
+        return AH_OK;
+    }
+    // node list / leaves' job of a finished group
+    int group_complete(uint32_t tA, uint32_t tB) { return sb ? push_leaves_job(tA, tB) : emit_range(tA, tB); }
 
+    // ---- one level -------------------------------------------------------------------------------------------------------
     // Wait for the level on the stream.  With a cancel flag the wait polls it: a cancelled build raises the device-side
     // abort word (on the side stream), the margin kernels still queued or running drain without work, and the call
     // returns AH_ERR_CANCELLED as soon as the stream is idle (src/writer.rs:1178,1196 poll per node / per item).
-    bool abort_sent = false;
-    auto wait_level = [&]() -> int {
+    int wait_level() {
         if (!opt->cancel) {
             AH_HIP(hipEventSynchronize(bc.ev_level));
             return AH_OK;
@@ -3422,278 +3431,27 @@ static int build_batch(ah_dataset *ds, const ah_build_options *opt, uint32_t fir
             return AH_ERR_CANCELLED;
         }
         return AH_OK;
-    };
+    }
 
-    uint32_t depth = 0;
-    uint32_t step = 0;  // levels launched so far: the parity of the double buffers (== depth until the tail runs in groups)
-    auto t_prev_waited = std::chrono::steady_clock::now();
-    bool prev_rows = false;     // the previous level ran row-major: node_of / side_bytes describe it, d_child links it
-    // Node tables that arrived on the side stream and are still to be digested, oldest first.  A table is digested under a
-    // level that runs long enough to cover it (~45 ns per node on four threads against ~0.15 ns per pair on the device): the
-    // table of the last big level — 819 000 nodes, 35 ms — used to be digested under the 9 ms remnant level after it, and
-    // the loop, the hand-over of the ids and the next group of trees waited for it.  The tables live in a ring over the two
-    // pinned table buffers; a table that finds no room there forces the oldest digests first.
-    struct PendingTable {
-        uint32_t depth, step, n_nodes;
-        size_t ring_off;
-        uint64_t host_off;
-        const uint8_t *chunk_dev;
-        int64_t rec_off;      // >= 0: its record indices are level_rec_full[off ...] (first level of a tree group)
-        bool fork_parent;     // it is the level the groups were cut from: its children's list is kept whole
-        int group_done;       // >= 0: the last level of that tree group — its node list (its leaves' job) can follow
-    };
-    std::deque<PendingTable> tables;
-    uint8_t *const ring_base = reinterpret_cast<uint8_t *>(h_nodes[0]);
-    const size_t ring_cap = 2 * pin_nodes;
-    size_t ring_head = 0;
-    auto ring_alloc = [&](size_t bytes, size_t *off) -> bool {  // FIFO ring; head == tail only when nothing is live
-        if (tables.empty()) ring_head = 0;
-        const size_t tail = tables.empty() ? 0 : tables.front().ring_off;
-        if (tables.empty() || ring_head > tail) {
-            if (ring_head + bytes <= ring_cap) {
-                *off = ring_head;
-                ring_head += bytes;
-                return true;
-            }
-            if (!tables.empty() && bytes < tail) {
-                *off = 0;
-                ring_head = bytes;
-                return true;
-            }
-            return false;
-        }
-        if (ring_head + bytes < tail) {
-            *off = ring_head;
-            ring_head += bytes;
-            return true;
-        }
-        return false;
-    };
-    int lvl_status = AH_OK;
+    // plan the level (level_plan.h): the margin mode of its first attempt, its row-major launches, the tail in groups?
+    void plan_current(Level &lv) {
+        shape.n_nodes = lv.n_nodes;
+        shape.pairs = info.pairs;
+        shape.prev_rows = prev_rows;
+        shape.grouped = grouped;
+        shape.fork_now = fork_now;
+        // (a launch carries at most 2^32 - 1 work-items: threads x row tiles x column tiles of the shape the level would take)
+        const DensePlan dp_legal = dense_plan(N, std::max(lv.n_nodes, 1u));
+        shape.dense_grid_legal = (dp_legal.grid + 64) * (uint64_t)dp_legal.threads < 0xFFFFFFFFull && dp_legal.grid < 0x7FFFFFFFull;
+        shape.tree_first = tree_first.data();
+        lv.plan = plan_level(shape, knobs);
+        tree_first = lv.plan.tree_first;  // (with its gaps closed where the LDS variant was wanted)
+    }
 
-    // ---- the tail in groups of trees (AH_BUILD_TAIL_GROUPS) ----------------------------------------------------------
-    // The item ids of a tree are final with its last scatter, and 95 % of them (10M x 768 x 100 trees) are still under
-    // splitting nodes when the last big level starts: level by level, the 4 GB of ids and the 2.6 GB of that level's
-    // normals leave the device after the last launch — 0.10 s of 1.43.  So the last big level and whatever follows it
-    // run GROUP BY GROUP (contiguous ranges of trees, each to its end): the ids and normals of group g travel while
-    // group g + 1 computes, and only the last group's are left for the tail.  A group is a level-by-level build of fewer
-    // trees over the same tables: its nodes are a slice of the level's table (tile indices rebased by k_fork_groups), its
-    // levels always node-major (they are by then), its records digested like any level's.  The forest is the same node
-    // for node — trees never interact — only the order of the normals in the blob (and the ids of a streaming build)
-    // follows the order of the launches.
-    bool grouped = false, fork_now = false, group_first_level = false;
-    uint32_t group_n0 = 0;
-    std::vector<uint32_t> level_rec_full;
-    std::vector<uint32_t> group_tree;        // tree range of group g: [group_tree[g], group_tree[g + 1])
-    int pending_hand = -1;                   // group whose item ids are final and still to be handed to the read-back worker
-    FNode *group_spare = nullptr;            // third node table of the grouped tail
-    std::function<int(uint32_t, uint32_t)> hand_over_ids;  // (defined below, once the leaves' merge exists)
-    std::function<int(uint32_t, uint32_t)> group_complete;  // node list / leaves' job of a finished group (defined below)
-    std::deque<int> done_groups;  // groups whose tables are all digested and whose node list is still to be emitted
-    auto digest_front = [&]() -> int {
-        const PendingTable e = tables.front();
-        // (copies on the side stream complete in order: the event of this parity was recorded by this table's copy or a later one)
-        AH_HIP(hipEventSynchronize(bc.ev_copy[e.step & 1]));
-        const uint32_t *rec_of = e.rec_off >= 0 ? level_rec_full.data() + e.rec_off : level_rec.data();
-        AH_TRY(digest_level(e.depth, e.n_nodes, reinterpret_cast<const FNode *>(ring_base + e.ring_off), e.host_off, e.chunk_dev, rec_of));
-        if (e.fork_parent) level_rec_full.swap(level_rec);
-        tables.pop_front();
-        if (e.group_done >= 0) {
-            // a streaming build's leaves' job starts the transfer of the group's ids: at once; a node list only costs host time
-            if (sb) AH_TRY(group_complete(group_tree[e.group_done], group_tree[e.group_done + 1]));
-            else done_groups.push_back(e.group_done);
-        }
-        return AH_OK;
-    };
-    // the tables a level of `pairs` margin evaluations covers (all of them: pairs = ~0)
-    auto digest_under = [&](uint64_t pairs) -> int {
-        // host nanoseconds the level covers: 0.14 ns per pair on the device, three quarters of it at most; a table costs ~45 ns
-        // per node (four threads), a node list ~10 ns per node (eight) — both next to the read-back worker's copy threads
-        double budget = (double)pairs * 0.105;
-        // (a table of a few thousand nodes is a fraction of a millisecond: always — progress reports stay level by level)
-        while (!tables.empty() && (45.0 * tables.front().n_nodes <= budget || tables.front().n_nodes < 16384u)) {
-            budget -= 45.0 * tables.front().n_nodes;
-            AH_TRY(digest_front());
-        }
-        while (!done_groups.empty()) {
-            const uint32_t tA = group_tree[done_groups.front()], tB = group_tree[done_groups.front() + 1];
-            double nodes = 0.0;
-            for (uint32_t t = tA; t < tB; t++) nodes += (double)tree_count[t];
-            if (10.0 * nodes > budget) break;
-            budget -= 10.0 * nodes;
-            done_groups.pop_front();
-            AH_TRY(group_complete(tA, tB));
-        }
-        return AH_OK;
-    };
-    auto digest_pending = [&]() -> int { return digest_under(~0ull); };
-    // Streaming build: the Descendants nodes of trees [tA, tB), ascending in (tree, position) — i.e. in the order their ids lie
-    // in the final permutation — as one job.  Every level's list is already in that order; the levels of one tree are merged
-    // per tree (a few threads: 1.7 M leaves at 10M x 100 trees).
-    auto push_leaves_job = [&](uint32_t tA, uint32_t tB) -> int {
-        StreamJob *job = new (std::nothrow) StreamJob();
-        AH_REQUIRE(job, AH_ERR_OUT_OF_MEMORY, "host allocation failed");
-        job->head.kind = AH_NODE_DESCENDANTS;
-        job->head.normal_stride = nstride;
-        job->head.normal_header_offset = hdr_off;
-        job->encoded = sb->encoded;
-        // per tree: where its leaves start in every level's list, and in the output
-        const size_t n_lv = stream_leaves.size();
-        const uint32_t nt = tB - tA;
-        std::vector<size_t> cut((size_t)(nt + 1) * n_lv, 0), out_at(nt + 1, 0);
-        for (size_t l = 0; l < n_lv; l++) {
-            const auto &lv = stream_leaves[l];
-            // (by tree, not by position: an EMPTY child at the very end of a tree starts where the next tree does)
-            for (uint32_t t = 0; t <= nt; t++)
-                cut[(size_t)t * n_lv + l] = (size_t)(std::lower_bound(lv.begin(), lv.end(), first_tree + tA + t, [](const LeafRec &r, uint32_t v) { return r.tree < v; }) - lv.begin());
-        }
-        for (uint32_t t = 0; t < nt; t++) {
-            size_t c = 0;
-            for (size_t l = 0; l < n_lv; l++) c += cut[(size_t)(t + 1) * n_lv + l] - cut[(size_t)t * n_lv + l];
-            out_at[t + 1] = out_at[t] + c;
-        }
-        const size_t total = out_at[nt];
-        job->nodes.resize(total);
-        std::atomic<uint32_t> next_tree{0};
-        parallel_run(total < 100000 ? 1u : std::min(nt, host_threads), [&](unsigned) {
-            std::vector<LeafRec> mine;
-            for (;;) {
-                const uint32_t t = next_tree.fetch_add(1, std::memory_order_relaxed);
-                if (t >= nt) break;
-                mine.clear();
-                for (size_t l = 0; l < n_lv; l++)
-                    mine.insert(mine.end(), stream_leaves[l].begin() + (ptrdiff_t)cut[(size_t)t * n_lv + l],
-                                stream_leaves[l].begin() + (ptrdiff_t)cut[(size_t)(t + 1) * n_lv + l]);
-                // (an empty leaf shares its position with its sibling: it goes first, so that offsets never step back)
-                std::sort(mine.begin(), mine.end(), [](const LeafRec &a, const LeafRec &b) {
-                    return a.start != b.start ? a.start < b.start : a.count < b.count;
-                });
-                ah_stream_node *dst = job->nodes.data() + out_at[t];
-                for (const LeafRec &r : mine) {
-                    ah_stream_node sn{};
-                    sn.id = r.id;
-                    sn.tree = r.tree;
-                    sn.kind = AH_NODE_DESCENDANTS;
-                    sn.count = r.count;
-                    sn.depth = r.depth;
-                    sn.payload_offset = r.start * 4;
-                    *dst++ = sn;
-                }
-            }
-        });
-        rb.push_stream(job, final_perm.p);
-        return AH_OK;
-    };
-    // The item ids of trees [tA, tB) are final (every kernel that writes them has been waited for): rows -> item ids where the
-    // two differ (on the side stream: the main one is busy with the next group), then — the blob's slice of a materialised
-    // forest — to the worker.  (A streaming build hands them over as the leaves' job, once the group's tables are digested.)
-    hand_over_ids = [&](uint32_t tA, uint32_t tB) -> int {
-        const uint64_t a = tree_base[tA], b = tree_base[tB];
-        if (b > a && !ds->identity_ids) {
-            hipLaunchKernelGGL(k_rows_to_ids, dim3(2048), dim3(256), 0, bc.side, final_perm.p + a, b - a, ds->d_ids);
-            AH_HIP(hipStreamSynchronize(bc.side));
-        }
-        if (sb) return AH_OK;
-        prefault.join();
-        rb.push(forest->descendants + desc_base + a, final_perm.p + a, (b - a) * 4);
-        return AH_OK;
-    };
-    // Emit per tree in post-order (children before parents: the order TmpNodes::put receives them,
-    // src/writer.rs:1235-1258), with forest-local indices.  Trees are independent: the number of nodes of every tree
-    // is known (counted while the levels were digested), so each tree is written into its own slice by a few threads —
-    // all trees after the last level, or, when the tail runs in groups, a group's trees under the next group's kernels.
-    const size_t node_base = forest->nodes.size(), roots_base = forest->roots.size();
-    size_t emit_cursor = node_base;  // forest->nodes index of the next tree to be emitted
-    uint32_t emit_tree = 0;          // trees [0, emit_tree) are emitted
-    std::atomic<uint64_t> n_split{0}, n_desc{0};
-    auto emit_range = [&](uint32_t tA, uint32_t tB) -> int {
-        if (sb || tB <= tA) return AH_OK;
-        AH_REQUIRE(tA == emit_tree, AH_ERR_DEVICE, "forest build: trees emitted out of order (internal error)");
-        std::vector<uint64_t> off(tB - tA + 1, 0);
-        for (uint32_t t = tA; t < tB; t++) off[t - tA + 1] = off[t - tA] + tree_count[t];
-        const uint64_t total = off[tB - tA];
-        forest->nodes.resize(emit_cursor + total);
-        if (forest->roots.size() < roots_base + n_trees) forest->roots.resize(roots_base + n_trees);
-        new_index.resize(n_recs, 0xFFFFFFFFu);
-        uint32_t *roots_out = forest->roots.data() + roots_base;
-        std::atomic<uint32_t> next_tree{tA};
-        auto emit_trees = [&](unsigned) {
-            std::vector<std::pair<uint32_t, int>> stack;
-            uint64_t splits = 0, descs = 0;
-            for (;;) {
-                const uint32_t t = next_tree.fetch_add(1, std::memory_order_relaxed);
-                if (t >= tB) break;
-                uint64_t out = emit_cursor + off[t - tA];
-                stack.clear();
-                stack.push_back({tree_root[t], 0});
-                while (!stack.empty()) {
-                    const uint32_t ri = stack.back().first;
-                    const HostRec &r = recs[ri];
-                    if (r.kind == AH_NODE_SPLIT && stack.back().second == 0) {
-                        stack.back().second = 1;
-                        const uint32_t l = r.left, rr = r.right;
-                        stack.push_back({rr, 0});
-                        stack.push_back({l, 0});
-                        continue;
-                    }
-                    ah_node nd{};
-                    nd.kind = r.kind;
-                    nd.has_normal = r.has_normal;
-                    nd.tree = first_tree + t;
-                    nd.count = r.count;
-                    nd.depth = r.depth;
-                    if (r.kind == AH_NODE_SPLIT) {
-                        nd.left = new_index[r.left];
-                        nd.right = new_index[r.right];
-                        nd.offset = r.normal_off;
-                        splits++;
-                    } else {
-                        nd.offset = desc_base + r.start;
-                        descs++;
-                    }
-                    new_index[ri] = (uint32_t)out;
-                    forest->nodes[out++] = nd;
-                    stack.pop_back();
-                }
-                roots_out[t] = new_index[tree_root[t]];
-            }
-            n_split.fetch_add(splits, std::memory_order_relaxed);
-            n_desc.fetch_add(descs, std::memory_order_relaxed);
-        };
-        parallel_run(total < 200000 ? 1u : std::min({tB - tA, host_threads, std::max(1u, std::thread::hardware_concurrency())}),
-                     emit_trees);
-        emit_cursor += total;
-        emit_tree = tB;
-        return AH_OK;
-    };
-    group_complete = [&](uint32_t tA, uint32_t tB) -> int { return sb ? push_leaves_job(tA, tB) : emit_range(tA, tB); };
-    LevelShape shape{};  // the batch's part of every level's shape
-    shape.N = N;
-    shape.n_trees = n_trees;
-    shape.split_after = split_after;
-    shape.rec_bytes = screen ? hstride : nstride;  // bytes of one normal as the margin pass streams it
-    shape.row_bytes = ds->row_bytes();
-    shape.hpitch = ds->hpitch;
-    shape.metric = ds->metric;
-    shape.screen = screen;
-    shape.screen8 = screen8;
-    shape.rows8_lo = sv.rows8_lo != nullptr;
-    shape.screen8_quality = ds->screen8_quality;
-    shape.rows_allowed = rows_allowed;
-    shape.subset = subset_ids != nullptr;
-    shape.mode_req = mode_req;
-    auto run_levels = [&]() -> int {
-    while (info.n_nodes) {
-        if (opt->cancel && *opt->cancel) {
-            set_error("build cancelled");
-            return AH_ERR_CANCELLED;  // Error::BuildCancelled
-        }
-        AH_REQUIRE(depth < 100000, AH_ERR_DEVICE, "forest build: depth %u exceeded (internal error)", depth);
-        if (sb && (sb->target.sink_rc.load() || sb->target.too_big.load())) break;  // reported after the loop
-        const auto t_level_top = std::chrono::steady_clock::now();
-        const double ms_tail_prev = std::chrono::duration<double, std::milli>(t_level_top - t_prev_waited).count();
-        const uint32_t n_nodes = info.n_nodes, n_tiles = info.n_tiles;
-        AH_REQUIRE(n_nodes <= max_nodes && n_tiles <= max_tiles, AH_ERR_DEVICE, "forest build: node / tile bound exceeded");
+    // Everything the level puts on the stream: its tiles, up to four attempts, the scatter, the next level's table and sizes.
+    int launch_level(Level &lv) {
+        const uint32_t n_nodes = lv.n_nodes, n_tiles = lv.n_tiles;
+        const LevelPlan &plan = lv.plan;
         const unsigned tile_grid = std::min<uint32_t>(n_tiles, knobs.tile_blocks);
         // The node-major margin kernels walk their tiles with a persistent grid: at the deep levels a tile is ~1200 items
         // (~2 MB of rows) and launching one workgroup per tile — 819 000 of them at level 13 of the 10M x 100 build — cost
@@ -3701,27 +3459,10 @@ static int build_batch(ah_dataset *ds, const ah_build_options *opt, uint32_t fir
         // bookkeeping kernels keep one tile per block (their random 1-byte / 4-byte gathers want every block in flight),
         // except the byte -> mask conversion of the top levels, whose reads are still nearly sequential.
         const unsigned node_grid = knobs.node_blocks ? std::min<uint32_t>(n_tiles, knobs.node_blocks)
-                                                 : std::min<uint32_t>(n_tiles, std::max<uint32_t>(2048u, std::min<uint32_t>(65536u, n_tiles / 16u)));
+                                                     : std::min<uint32_t>(n_tiles, std::max<uint32_t>(2048u, std::min<uint32_t>(65536u, n_tiles / 16u)));
         const unsigned masks_grid = n_nodes <= 4 * n_trees ? std::min<uint32_t>(tile_grid, 32768u) : tile_grid;
-
-        // ---- plan the level (level_plan.h): the margin mode of its first attempt, its row-major launches, the tail in groups?
         const uint64_t rec_bytes = shape.rec_bytes;
         const uint64_t nodes_per_tree = (n_nodes + n_trees - 1) / n_trees;
-        shape.n_nodes = n_nodes;
-        shape.pairs = info.pairs;
-        shape.prev_rows = prev_rows;
-        shape.grouped = grouped;
-        shape.fork_now = fork_now;
-        // (a launch carries at most 2^32 - 1 work-items: threads x row tiles x column tiles of the shape the level would take)
-        const DensePlan dp_legal = dense_plan(N, std::max(n_nodes, 1u));
-        shape.dense_grid_legal = (dp_legal.grid + 64) * (uint64_t)dp_legal.threads < 0xFFFFFFFFull && dp_legal.grid < 0x7FFFFFFFull;
-        shape.tree_first = tree_first.data();
-        const LevelPlan plan = plan_level(shape, knobs);
-        tree_first = plan.tree_first;  // (with its gaps closed where the LDS variant was wanted)
-        if (plan.fork) {  // the level is handed back unlaunched: run_tail_groups cuts it into groups of trees
-            fork_now = true;
-            return AH_OK;
-        }
         const uint32_t row_tc = plan.row_tc, lds_tc = plan.lds_tc;
         const bool dense = plan.dense;
         hipLaunchKernelGGL(k_build_tiles, dim3(std::min<uint32_t>((n_nodes + 3) / 4, kMaxBlocks)), dim3(256), 0, s, d_cur,
@@ -3733,6 +3474,7 @@ static int build_batch(ah_dataset *ds, const ah_build_options *opt, uint32_t fir
         if (screen) AH_TRY(shadow_arena.take((uint64_t)n_nodes * hstride, &shadow_d));
         if (screen8) AH_TRY(shadow8_arena.take((uint64_t)n_nodes * stride8, &shadow8_d));
         normals_bytes += chunk_bytes;
+        lv.chunk_d = chunk_d, lv.chunk_bytes = chunk_bytes, lv.chunk_host_off = chunk_host_off;
         // Host side of the normals: reserved now; the pages of THIS level's records were started one level ago (a level has
         // about twice the nodes of the one before), those of the NEXT level start now — committing the 2.6 GB of the deepest
         // level takes longer than the ~160 ms that level runs, and the loop must not wait for page faults before it can
@@ -3834,27 +3576,28 @@ static int build_batch(ah_dataset *ds, const ah_build_options *opt, uint32_t fir
                            d_child.p, d_info, d_tree_first);
         AH_DBG(s, "next_level");
         AH_HIP(hipGetLastError());
-        LevelInfo *hi = h_info[step & 1];
-        AH_HIP(hipMemcpyAsync(hi, d_info, info_words * 4, hipMemcpyDeviceToHost, s));
+        AH_HIP(hipMemcpyAsync(h_info[step & 1], d_info, z.info_words * 4, hipMemcpyDeviceToHost, s));
         AH_HIP(hipEventRecord(bc.ev_level, s));
+        return AH_OK;
+    }
 
-        // while the level runs: room for the records of the two digests to come (the level before this one, now; this one,
-        // under the next level), then digest the node table of the level before it
-        {
-            size_t want = n_recs + 2 * (size_t)n_nodes;
-            for (const PendingTable &e : tables) want += 2 * (size_t)e.n_nodes;
-            if (recs.size() < want) recs.resize(want);
-        }
-        const auto t_launched = std::chrono::steady_clock::now();
+    // While the level runs: room for the records of the two digests to come (the level before this one, now; this one, under
+    // the next level), the ids of the group before this one, then the node tables (and node lists) the level covers.
+    int under_level(Level &lv) {
+        records.grow_ahead(lv.n_nodes, ring.tables);
+        lv.t_launched = std::chrono::steady_clock::now();
         // the group before this one is complete (its last level was waited for): its ids travel under this group's kernels
-        if (pending_hand >= 0) {
-            AH_TRY(hand_over_ids(group_tree[pending_hand], group_tree[pending_hand + 1]));
-            pending_hand = -1;
-        }
+        AH_TRY(hand_over_pending());
         AH_TRY(digest_under(info.pairs));
-        const auto t_digested = std::chrono::steady_clock::now();
-        lvl_status = wait_level();
-        if (lvl_status != AH_OK) return lvl_status;
+        lv.t_digested = std::chrono::steady_clock::now();
+        return AH_OK;
+    }
+
+    // The wait, the level's timings, its node table onto the side stream and its normals to the worker, the next level's sizes.
+    int after_level(const Level &lv) {
+        const uint32_t n_nodes = lv.n_nodes, row_tc = lv.plan.row_tc, lds_tc = lv.plan.lds_tc;
+        const bool dense = lv.plan.dense;
+        AH_TRY(wait_level());
         const auto t_waited = std::chrono::steady_clock::now();
         t_prev_waited = t_waited;
         float attempt_ms[4] = {0.f, 0.f, 0.f, 0.f};
@@ -3871,26 +3614,26 @@ static int build_batch(ah_dataset *ds, const ah_build_options *opt, uint32_t fir
                     dense ? "dense-mfma" : lds_tc ? "rows-lds" : row_tc >= 2 ? "rows" : "node-major", attempt_ms[0],
                     attempt_ms[1] + attempt_ms[2] + attempt_ms[3], info.pairs ? attempt_ms[0] * 1e6 / (double)info.pairs : 0.0);
         if (timing >= 3) {
-            auto ms_of = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
             fprintf(stderr, "[ah]          host: after the previous wait %.2f ms, launch %.2f ms, under the level (ids handed over, tables digested, node lists) %.2f ms, wait %.2f ms\n",
-                    ms_tail_prev, ms_of(t_level_top, t_launched), ms_of(t_launched, t_digested), ms_of(t_digested, t_waited));
+                    lv.ms_tail_prev, ms_of(lv.t_top, lv.t_launched), ms_of(lv.t_launched, lv.t_digested), ms_of(lv.t_digested, t_waited));
         }
         forest->stats.margin_launches += 4;
         // this level's node table follows on the side stream (the level is complete: no stream dependency needed)
         size_t table_off = 0;
         const size_t table_bytes = ((size_t)n_nodes * sizeof(FNode) + 4095) & ~(size_t)4095;
-        while (!ring_alloc(table_bytes, &table_off)) AH_TRY(digest_front());  // (no room: the oldest tables first)
+        while (!ring.alloc(table_bytes, &table_off)) AH_TRY(digest_front());  // (no room: the oldest tables first)
         AH_HIP(hipMemcpyAsync(ring_base + table_off, d_cur, n_nodes * sizeof(FNode), hipMemcpyDeviceToHost, bc.side));
         AH_HIP(hipEventRecord(bc.ev_copy[step & 1], bc.side));
         // (a millisecond at most — and it must not queue behind the gigabytes of normals the worker is about to request: the
         // digest of this table runs under the NEXT level, which at the bottom of the forest is a short one)
         if (n_nodes >= 65536) AH_HIP(hipEventSynchronize(bc.ev_copy[step & 1]));
-        tables.push_back(PendingTable{depth, step, n_nodes, table_off, chunk_host_off, chunk_d,
-                                      group_first_level ? (int64_t)group_n0 : -1, false, -1});
+        ring.tables.push_back(PendingTable{depth, step, n_nodes, table_off, lv.chunk_host_off, lv.chunk_d,
+                                           group_first_level ? (int64_t)group_n0 : -1, false, -1});
         // this level's normals are final: the worker copies them while the next level runs
         touch_normals[step & 1].join();  // never touch a page the worker may already have filled
-        if (!sb) rb.push(forest->normals + chunk_host_off, chunk_d, chunk_bytes);  // (streaming: pushed by the level's digest)
+        if (!sb) rb.push(forest->normals + lv.chunk_host_off, lv.chunk_d, lv.chunk_bytes);  // (streaming: pushed by the level's digest)
 
+        const LevelInfo *hi = h_info[step & 1];
         info = *hi;
         const uint32_t *tf = reinterpret_cast<const uint32_t *>(hi + 1);
         for (uint32_t t = 0; t <= n_trees; t++) tree_first[t] = tf[t];
@@ -3903,90 +3646,115 @@ static int build_batch(ah_dataset *ds, const ah_build_options *opt, uint32_t fir
         }
         depth++;
         step++;
+        return AH_OK;
     }
-    return AH_OK;
-    };
-    auto run_tail_groups = [&]() -> int {
-        if (!fork_now) return AH_OK;
-        const uint32_t K = std::min(knobs.tail_groups, n_trees);
-        group_tree.resize(K + 1);
-        GroupCuts cuts{};
-        // shrinking groups: group g + 1 computes while group g's ids and normals travel (~0.76 of the time its kernels took at
-        // PCIe rate), and only the last group's are left after the last launch — so the last one is the smallest
-        {
-            const double ratio = (double)std::min<long long>(100, std::max<long long>(10, tun(TUN_TAIL_RATIO))) / 100.0;
-            double total_w = 0.0, w = 1.0, cum = 0.0;
-            for (uint32_t g = 0; g < K; g++, w *= ratio) total_w += w;
-            group_tree[0] = 0;
-            w = 1.0;
-            for (uint32_t g = 1; g < K; g++, w *= ratio) {
-                cum += w;
-                const uint32_t at = (uint32_t)std::llround((double)n_trees * cum / total_w);
-                group_tree[g] = std::min(std::max(at, group_tree[g - 1] + 1), n_trees - (K - g));  // at least one tree each
+
+    // One level = one set of launches, and ONE host wait.  Ends with the forest (or the group) complete, or — fork_now — with
+    // a level handed back unlaunched for run_tail_groups to cut into groups of trees.
+    int run_levels() {
+        while (info.n_nodes) {
+            if (opt->cancel && *opt->cancel) {
+                set_error("build cancelled");
+                return AH_ERR_CANCELLED;  // Error::BuildCancelled
             }
-            group_tree[K] = n_trees;
+            AH_REQUIRE(depth < 100000, AH_ERR_DEVICE, "forest build: depth %u exceeded (internal error)", depth);
+            if (sb && (sb->target.sink_rc.load() || sb->target.too_big.load())) break;  // reported after the loop
+            Level lv;
+            lv.t_top = std::chrono::steady_clock::now();
+            lv.ms_tail_prev = std::chrono::duration<double, std::milli>(lv.t_top - t_prev_waited).count();
+            lv.n_nodes = info.n_nodes, lv.n_tiles = info.n_tiles;
+            AH_REQUIRE(lv.n_nodes <= z.max_nodes && lv.n_tiles <= z.max_tiles, AH_ERR_DEVICE, "forest build: node / tile bound exceeded");
+            plan_current(lv);
+            if (lv.plan.fork) {
+                fork_now = true;
+                return AH_OK;
+            }
+            AH_TRY(launch_level(lv));
+            AH_TRY(under_level(lv));
+            AH_TRY(after_level(lv));
         }
+        return AH_OK;
+    }
+
+    // ---- the tail in groups of trees (AH_BUILD_TAIL_GROUPS) ----------------------------------------------------------
+    // The item ids of a tree are final with its last scatter, and 95 % of them (10M x 768 x 100 trees) are still under
+    // splitting nodes when the last big level starts: level by level, the 4 GB of ids and the 2.6 GB of that level's
+    // normals leave the device after the last launch — 0.10 s of 1.43.  So the last big level and whatever follows it
+    // run GROUP BY GROUP (contiguous ranges of trees, each to its end): the ids and normals of group g travel while
+    // group g + 1 computes, and only the last group's are left for the tail.  A group is a level-by-level build of fewer
+    // trees over the same tables: its nodes are a slice of the level's table (tile indices rebased by k_fork_groups), its
+    // levels always node-major (they are by then), its records digested like any level's.  The forest is the same node
+    // for node — trees never interact — only the order of the normals in the blob (and the ids of a streaming build)
+    // follows the order of the launches.
+    void enter_group(const TailGroup &g) {  // everything the level loop reads that a group starts anew
+        info = g.info;
+        d_cur = g.table;
+        d_next = g.other;
+        cur = g.cur;
+        nxt = g.nxt;
+        depth = g.depth;
+        prev_rows = false;
+        grouped = true;
+        group_first_level = true;
+        group_n0 = g.n0;
+        group_spare = d_nodes_c.p;
+    }
+    int run_tail_groups() {
+        if (!fork_now) return AH_OK;
+        group_tree = tail_group_trees(n_trees, knobs.tail_groups, tun(TUN_TAIL_RATIO));
+        const uint32_t K = (uint32_t)group_tree.size() - 1;
+        GroupCuts cuts{};
         for (uint32_t g = 0; g <= K; g++) cuts.first[g] = g < K ? tree_first[group_tree[g]] : info.n_nodes;
-        AH_TRY(d_nodes_c.ensure(max_nodes));
+        AH_TRY(d_nodes_c.ensure(z.nodes));
         AH_TRY(d_groups.ensure(32));
-        AH_HIP(hipMemsetAsync(d_nodes_c.p, 0, max_nodes * sizeof(FNode), s));  // (zeros: see the tables above)
+        AH_HIP(hipMemsetAsync(d_nodes_c.p, 0, z.nodes * sizeof(FNode), s));  // (zeros: see the tables above)
         hipLaunchKernelGGL(k_fork_groups, dim3(K), dim3(256), 0, s, d_cur, cuts, d_groups.p);
         GroupInfo gi[32];
         AH_HIP(hipMemcpyAsync(gi, d_groups.p, K * sizeof(GroupInfo), hipMemcpyDeviceToHost, s));
         AH_HIP(hipStreamSynchronize(s));
         // the records of the level's nodes: the children's list of the level before it, digested under the first group
-        if (!tables.empty()) tables.back().fork_parent = true;
-        else level_rec_full.swap(level_rec);
-        FNode *const table = d_cur, *const other = d_next;
-        uint32_t *const cur_f = cur, *const nxt_f = nxt;
-        const uint32_t depth_f = depth;
-        grouped = true;
-        group_spare = d_nodes_c.p;
+        if (!ring.tables.empty()) ring.tables.back().fork_parent = true;
+        else records.level_rec_full.swap(records.level_rec);
+        TailGroup start{LevelInfo{}, d_cur, d_next, cur, nxt, depth, 0u};
         forest->stats.tail_groups += K;
         if (timing)
             fprintf(stderr, "[ah] tail: level %u on (%u nodes, %llu pairs) in %u groups of trees\n", depth, info.n_nodes,
                     (unsigned long long)info.pairs, K);
         for (uint32_t g = 0; g < K; g++) {
-            const uint32_t n0 = cuts.first[g], n1 = cuts.first[g + 1];
-            info = LevelInfo{};
-            info.n_nodes = n1 - n0;
-            info.n_tiles = gi[g].n_tiles;
-            info.n_fix = gi[g].n_fix;
-            info.pairs = gi[g].pairs;
-            d_cur = table + n0;
-            d_next = other;
-            cur = cur_f;
-            nxt = nxt_f;
-            depth = depth_f;
-            prev_rows = false;
-            group_first_level = true;
-            group_n0 = n0;
+            TailGroup grp = start;
+            grp.n0 = cuts.first[g];
+            grp.table = start.table + grp.n0;
+            grp.info.n_nodes = cuts.first[g + 1] - cuts.first[g];
+            grp.info.n_tiles = gi[g].n_tiles;
+            grp.info.n_fix = gi[g].n_fix;
+            grp.info.pairs = gi[g].pairs;
+            enter_group(grp);
             AH_TRY(run_levels());
             if (sb && (sb->target.sink_rc.load() || sb->target.too_big.load())) break;  // reported after the loop
             // its ids: handed over under the next group's first level (the last group's: after the loop); its node list (the
             // leaves' job of a streaming build): when its last table has been digested
             pending_hand = (int)g;
-            if (!tables.empty()) tables.back().group_done = (int)g;
+            if (!ring.tables.empty()) ring.tables.back().group_done = (int)g;
         }
         return AH_OK;
-    };
-    AH_TRY(run_levels());
-    AH_TRY(run_tail_groups());
-    AH_HIP(hipEventRecord(bc.ev_end, s));
-    const auto t_loop_end = std::chrono::steady_clock::now();
+    }
 
+    // ---- after the last launch ---------------------------------------------------------------------------------------------
     // Results come back with plain D2H copies straight into their final place — no host-side repacking:
     //   normals      one copy per level chunk (device record layout == caller-visible layout), already under way
     //   descendants  the final permutations themselves (rows -> item ids on device first)
-    auto t_tail_prefault = t_loop_end, t_tail_sync = t_loop_end;
-    {
+    std::chrono::steady_clock::time_point t_tail_prefault, t_tail_sync, t_levels;
+    float device_ms = 0.0f;
+    int finish_device() {
+        AH_HIP(hipEventRecord(bc.ev_end, s));
+        t_loop_end = std::chrono::steady_clock::now();
         prefault.join();
         t_tail_prefault = std::chrono::steady_clock::now();
         if (!sb) forest->descendants_len = desc_base + M;
         // trees that are a single Descendants node never went through a scatter: their list is the input itself
         // (a tail in groups has no such tree, and its ids were converted group by group)
         for (uint32_t t = 0; t < n_trees && !fork_now; t++)
-            if (recs[tree_root[t]].kind == AH_NODE_DESCENDANTS && tree_base[t + 1] > tree_base[t])
+            if (records.recs[records.tree_root[t]].kind == AH_NODE_DESCENDANTS && tree_base[t + 1] > tree_base[t])
                 AH_HIP(hipMemcpyAsync(final_perm.p + tree_base[t], perm_a.p + tree_base[t],
                                       (tree_base[t + 1] - tree_base[t]) * 4, hipMemcpyDeviceToDevice, s));
         if (!ds->identity_ids && M && !fork_now)
@@ -4001,28 +3769,24 @@ static int build_batch(ah_dataset *ds, const ah_build_options *opt, uint32_t fir
         forest->stats.screen8_decided += sc.stage8_decided;
         forest->stats.screen8b_decided += sc.stage8b_decided;
         if (!sb && !fork_now) rb.push(forest->descendants + desc_base, final_perm.p, M * 4);  // lands while the host emits the node list
-        if (fork_now && pending_hand >= 0) {  // (the last group's)
-            AH_TRY(hand_over_ids(group_tree[pending_hand], group_tree[pending_hand + 1]));
-            pending_hand = -1;
-        }
+        if (fork_now) AH_TRY(hand_over_pending());  // (the last group's)
+        // the last level's node table is digested only now: the 4 GB of item ids are already on their way
+        AH_TRY(digest_under(~0ull));
+        if (sb && !fork_now) AH_TRY(push_leaves_job(0, n_trees));  // (in groups: every group's job followed its last table)
+        t_levels = std::chrono::steady_clock::now();
+        AH_HIP(hipEventElapsedTime(&device_ms, bc.ev_begin, bc.ev_end));
+        forest->stats.seconds_device += device_ms * 1e-3;
+        return AH_OK;
     }
-    // the last level's node table is digested only now: the 4 GB of item ids are already on their way
-    AH_TRY(digest_pending());
-    if (sb && !fork_now) AH_TRY(push_leaves_job(0, n_trees));  // (in groups: every group's job followed its last table)
-    const auto t_levels = std::chrono::steady_clock::now();
-    float ms = 0.0f;
-    AH_HIP(hipEventElapsedTime(&ms, bc.ev_begin, bc.ev_end));
-    forest->stats.seconds_device += ms * 1e-3;
-    if (sb) {
-        // no node list, no blobs: the roots, the counts, and the worker's verdict
-        recs.resize(n_recs);
-        uint64_t splits = 0, descs = 0;
-        for (const HostRec &r : recs) (r.kind == AH_NODE_SPLIT ? splits : descs)++;
-        forest->stats.split_nodes += splits;
-        forest->stats.descendant_nodes += descs;
-        for (uint32_t t = 0; t < n_trees; t++) sb->roots[first_tree + t] = id_base + tree_root[t];
-        AH_REQUIRE((uint64_t)id_base + n_recs < 0xFFFFFFFFull, AH_ERR_INVALID_ARGUMENT, "more than 2^32 tree nodes in one build");
-        sb->id_base = id_base + (uint32_t)n_recs;
+    // no node list, no blobs: the roots, the counts, and the worker's verdict
+    int finish_streamed() {
+        const uint32_t id_base = records.id_base;
+        records.count_records();
+        forest->stats.split_nodes += records.n_split;
+        forest->stats.descendant_nodes += records.n_desc;
+        for (uint32_t t = 0; t < n_trees; t++) sb->roots[first_tree + t] = id_base + records.tree_root[t];
+        AH_REQUIRE((uint64_t)id_base + records.n_recs < 0xFFFFFFFFull, AH_ERR_INVALID_ARGUMENT, "more than 2^32 tree nodes in one build");
+        sb->id_base = id_base + (uint32_t)records.n_recs;
         const hipError_t rb_err = rb.drain();
         AH_REQUIRE(rb_err != hipErrorOutOfMemory, AH_ERR_OUT_OF_MEMORY, "host allocation failed in the encoded stream");
         AH_REQUIRE(rb_err == hipSuccess, AH_ERR_DEVICE, "device -> host copy of the forest failed");
@@ -4032,36 +3796,49 @@ static int build_batch(ah_dataset *ds, const ah_build_options *opt, uint32_t fir
         forest->stats.seconds_after_device += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_loop_end).count();
         if (timing)
             fprintf(stderr, "[ah] streamed batch of %u trees: %.3f s (device %.3f), %llu sink calls, %.2f GB handed over\n", n_trees,
-                    std::chrono::duration<double>(std::chrono::steady_clock::now() - t_batch).count(), ms * 1e-3,
+                    std::chrono::duration<double>(std::chrono::steady_clock::now() - t_batch).count(), device_ms * 1e-3,
                     (unsigned long long)sb->target.batches, sb->target.bytes / 1e9);
         return AH_OK;
     }
-
-    // the node list of the trees not emitted yet (all of them, unless the tail ran in groups)
-    AH_TRY(emit_range(emit_tree, n_trees));
-    AH_REQUIRE(emit_cursor - node_base == n_recs, AH_ERR_DEVICE, "forest build: %zu nodes emitted of %zu (internal error)",
-               emit_cursor - node_base, n_recs);
-    forest->stats.split_nodes += n_split.load();
-    forest->stats.descendant_nodes += n_desc.load();
-    const auto t_emitted = std::chrono::steady_clock::now();
-    AH_REQUIRE(rb.drain() == hipSuccess, AH_ERR_DEVICE, "device -> host copy of the forest failed");
-    forest->normals_len = normals_base + normals_bytes;
-    touch_normals[0].join();  // (the last level started the commit of a level that never came)
-    touch_normals[1].join();
-    // (the head-room of the blob stays mapped: untouched pages cost nothing, and the pool hands the whole blob to the next build)
-    forest->stats.host_blob_recycled += (forest->normals_blob.recycled ? 1u : 0u) + (forest->desc_blob.recycled ? 1u : 0u);
-    forest->stats.seconds_after_device += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_loop_end).count();
-    if (timing) {
-        const auto t_end = std::chrono::steady_clock::now();
-        auto sec = [](auto a, auto b) { return std::chrono::duration<double>(b - a).count(); };
-        fprintf(stderr, "[ah] batch of %u trees: levels %.3f s (device %.3f; after the last launch: ids' pages %.3f, stream %.3f, last "
-                        "digest %.3f), emit %.3f s, read-back still in flight after it %.3f s (%.2f GB normals%s, %.2f GB ids%s)\n",
-                n_trees, sec(t_batch, t_levels), ms * 1e-3, sec(t_loop_end, t_tail_prefault), sec(t_tail_prefault, t_tail_sync),
-                sec(t_tail_sync, t_levels), sec(t_levels, t_emitted), sec(t_emitted, t_end), normals_bytes / 1e9,
-                forest->normals_blob.committed ? ", recycled pages" : "", M * 4 / 1e9,
-                forest->desc_blob.committed ? ", recycled pages" : "");
+    // the node list of the trees not emitted yet (all of them, unless the tail ran in groups), then the copies still in flight
+    int finish_materialised() {
+        AH_TRY(emit_range(records.emit_tree, n_trees));
+        AH_REQUIRE(records.emit_cursor - records.node_base == records.n_recs, AH_ERR_DEVICE,
+                   "forest build: %zu nodes emitted of %zu (internal error)", records.emit_cursor - records.node_base, records.n_recs);
+        forest->stats.split_nodes += records.n_split;
+        forest->stats.descendant_nodes += records.n_desc;
+        const auto t_emitted = std::chrono::steady_clock::now();
+        AH_REQUIRE(rb.drain() == hipSuccess, AH_ERR_DEVICE, "device -> host copy of the forest failed");
+        forest->normals_len = normals_base + normals_bytes;
+        touch_normals[0].join();  // (the last level started the commit of a level that never came)
+        touch_normals[1].join();
+        // (the head-room of the blob stays mapped: untouched pages cost nothing, and the pool hands the whole blob to the next build)
+        forest->stats.host_blob_recycled += (forest->normals_blob.recycled ? 1u : 0u) + (forest->desc_blob.recycled ? 1u : 0u);
+        forest->stats.seconds_after_device += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_loop_end).count();
+        if (timing) {
+            const auto t_end = std::chrono::steady_clock::now();
+            fprintf(stderr, "[ah] batch of %u trees: levels %.3f s (device %.3f; after the last launch: ids' pages %.3f, stream %.3f, last "
+                            "digest %.3f), emit %.3f s, read-back still in flight after it %.3f s (%.2f GB normals%s, %.2f GB ids%s)\n",
+                    n_trees, sec(t_batch, t_levels), device_ms * 1e-3, sec(t_loop_end, t_tail_prefault), sec(t_tail_prefault, t_tail_sync),
+                    sec(t_tail_sync, t_levels), sec(t_levels, t_emitted), sec(t_emitted, t_end), normals_bytes / 1e9,
+                    forest->normals_blob.committed ? ", recycled pages" : "", M * 4 / 1e9,
+                    forest->desc_blob.committed ? ", recycled pages" : "");
+        }
+        return AH_OK;
     }
-    return AH_OK;
+};
+
+static int build_batch(ah_dataset *ds, const ah_build_options *opt, uint32_t first_tree, uint32_t n_trees,
+                       uint32_t split_after, ah_forest *forest, Context *ctx, const uint32_t *subset_ids,
+                       const uint64_t *subset_offsets, StreamBuild *sb = nullptr) {
+    BatchBuild b(ds, opt, first_tree, n_trees, split_after, forest, ctx, subset_ids, subset_offsets, sb);
+    AH_TRY(b.setup_device());
+    AH_TRY(b.setup_host());
+    AH_TRY(b.seed_roots());
+    AH_TRY(b.run_levels());
+    AH_TRY(b.run_tail_groups());
+    AH_TRY(b.finish_device());
+    return sb ? b.finish_streamed() : b.finish_materialised();
 }
 
 extern "C" {
@@ -4218,7 +3995,8 @@ static int build_forest_impl(ah_dataset *ds, const ah_build_options *options, co
 // Meant to be called right after ah_dataset_create, while the records are still being staged over PCIe: fresh HBM costs the
 // driver 20+ ms per GB on a box whose memory was recently released (r04: 59 GB of fresh blocks put 1.3 s in front of a cold
 // 10M x 100-tree build's first launch and stretched its kernels from 1.33 to 1.8 s); under the 0.6 s of staging it is free.
-// Sizes mirror build_batch / ensure_screen; a mismatch only costs the cache hit.
+// The batch's sizes are the build's own (batch_sizes, forest_records.h: one struct read by both); only the screen's copies
+// restate ensure_screen / ensure_screen8, where a mismatch would cost the cache hit and nothing else.
 int ah_dataset_reserve_build(ah_dataset *ds, uint32_t n_trees, uint32_t split_after_opt) {
     AH_GUARDED("ah_dataset_reserve_build")
     AH_REQUIRE(ds, AH_ERR_INVALID_ARGUMENT, "dataset is NULL");
@@ -4239,46 +4017,34 @@ int ah_dataset_reserve_build(ah_dataset *ds, uint32_t n_trees, uint32_t split_af
             sizes.push_back(N * sizeof(float));
         }
     }
-    {  // build_batch, one batch of n_trees full-dataset trees
-        const uint64_t M = (uint64_t)n_trees * N;
-        const uint64_t max_nodes = M / ((uint64_t)split_after + 1) + n_trees, max_tiles = M / kTile + n_trees + max_nodes;
-        auto buf = [&](uint64_t n, size_t elem) { sizes.push_back((size_t)std::max<uint64_t>(n, 1024) * elem); };
-        buf(M, 4); buf(M, 4); buf(M, 4);                                 // the three permutations
-        buf(max_nodes, sizeof(FNode)); buf(max_nodes, sizeof(FNode));
-        buf(max_tiles, sizeof(FTile));
-        buf(max_tiles * 32, 8);                                          // side masks
-        buf(max_tiles, 4); buf(max_tiles, 4);
-        buf(2 * max_nodes, 4);
-        buf(max_nodes / 256 + 2, sizeof(NextCounts));
-        if (f32 && n_trees >= 2) {
-            buf((uint64_t)n_trees * N + 4, 4);                           // node_of
-            buf((uint64_t)n_trees * N + 1024 + 16, 1);                   // side bytes
-            if (tun(TUN_MASK_BITS) > 0 || (tun(TUN_MASK_BITS) < 0 && N >= (1u << 20)))
-                buf(((uint64_t)n_trees * N + 31) / 32 + 4, 4);           // ... and bits
-        }
-        const uint64_t nstride = normal_record_stride(ds);
-        sizes.push_back((size_t)std::max<uint64_t>(32ull << 20, std::min<uint64_t>(2 * max_nodes * nstride, 16ull << 30)));
-        if (f32 && tun(TUN_SCREEN) != 0) {
-            const uint64_t hstride = ((uint64_t)hpitch * 2 + 16 + 127) & ~(uint64_t)127;
-            const uint64_t stride8 = (2 * (uint64_t)pitch8 + sizeof(NormalStats8) + 127) & ~(uint64_t)127;
-            const size_t sh = (size_t)std::max<uint64_t>(16ull << 20, std::min<uint64_t>(max_nodes * hstride, 8ull << 30));
-            sizes.push_back(sh);
-            sizes.push_back(sh);  // (a 100-tree 10M build takes a second block for its deepest levels)
-            if (ds->metric != AH_DOT_PRODUCT && tun(TUN_SCREEN8) != 0)
-                sizes.push_back((size_t)std::max<uint64_t>(16ull << 20, std::min<uint64_t>(max_nodes * stride8, 4ull << 30)));
-        }
-    }
-    // ... and the pinned host memory of that batch (node tables, level info, the read-back worker's double buffer)
-    size_t pinned_bytes = 0;
+    // one batch of n_trees full-dataset trees, in the order BatchBuild::setup_device and the level loop ask (the pinned host
+    // memory of that batch — node tables, level info, the read-back worker's double buffer — is z.pinned_bytes())
+    const bool f32_rows = f32 && n_trees >= 2;
+    const BatchSizes z = batch_sizes(N, n_trees, (uint64_t)n_trees * N, split_after, normal_record_stride(ds), shadow_stride16(hpitch),
+                                     shadow_stride8(pitch8), f32_rows, tun(TUN_MASK_BITS) > 0 || (tun(TUN_MASK_BITS) < 0 && N >= (1u << 20)),
+                                     tun(TUN_READBACK_MB));
     {
-        const uint64_t M = (uint64_t)n_trees * N;
-        const uint64_t max_nodes = M / ((uint64_t)split_after + 1) + n_trees;
-        const size_t info_words = (sizeof(LevelInfo) + ((size_t)n_trees + 1) * 4 + 3) / 4;
-        const size_t pin_info = (info_words * 4 + 255) & ~(size_t)255;
-        const size_t pin_nodes = (max_nodes * sizeof(FNode) + 4095) & ~(size_t)4095;
-        const size_t pin_head = (3 * pin_info + 256 + 4095) & ~(size_t)4095;
-        pinned_bytes = pin_head + 2 * pin_nodes + ((size_t)std::min<long long>(4096, std::max<long long>(2, tun(TUN_READBACK_MB))) << 20);
+        auto buf = [&](uint64_t n, size_t elem) { sizes.push_back((size_t)std::max<uint64_t>(n, 1024) * elem); };  // (DevBuf's floor)
+        buf(z.perm, 4); buf(z.perm, 4); buf(z.perm, 4);
+        buf(z.nodes, sizeof(FNode)); buf(z.nodes, sizeof(FNode));
+        buf(z.tiles, sizeof(FTile));
+        buf(z.masks, 8);
+        buf(z.tile_left, 4); buf(z.tile_left, 4);
+        buf(z.child, 4);
+        buf(z.block_sums, sizeof(NextCounts));
+        if (f32_rows) {
+            buf(z.node_of, 4);
+            buf(z.side_bytes, 1);
+            if (z.side_bits) buf(z.side_bits, 4);
+        }
+        sizes.push_back((size_t)z.arena_block);
+        if (f32 && tun(TUN_SCREEN) != 0) {
+            sizes.push_back((size_t)z.shadow_block);
+            sizes.push_back((size_t)z.shadow_block);  // (a 100-tree 10M build takes a second block for its deepest levels)
+            if (ds->metric != AH_DOT_PRODUCT && tun(TUN_SCREEN8) != 0) sizes.push_back((size_t)z.shadow8_block);
+        }
     }
+    const size_t pinned_bytes = z.pinned_bytes();
     const int device = ds->device;
     double *const took = &ds->reserve_seconds;  // (the handle outlives the helper: every build and the destroy join it)
     try {
@@ -4437,7 +4203,7 @@ static int forest_digest_impl(const ah_forest *forest, const uint64_t *tree_keys
     AH_REQUIRE(forest && (out_per_tree || out_total), AH_ERR_INVALID_ARGUMENT, "NULL argument");
     const uint32_t n_trees = (uint32_t)forest->roots.size();
     const size_t n_nodes = forest->nodes.size();
-    // the nodes of a tree are contiguous and the trees ascend (build_batch emits tree by tree)
+    // the nodes of a tree are contiguous and the trees ascend (BatchRecords::emit_range emits tree by tree)
     std::vector<size_t> first(n_trees + 1, n_nodes);
     for (size_t i = n_nodes; i-- > 0;) {
         const uint32_t t = forest->nodes[i].tree;

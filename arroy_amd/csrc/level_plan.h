@@ -1,4 +1,4 @@
-// level_plan.h — how one level of the forest build runs its first margin pass (build_batch in forest.hip): node-major,
+// level_plan.h — how one level of the forest build runs its first margin pass (BatchBuild in forest.hip): node-major,
 // row-major with TC trees per group, row-major with a group's normals resident in LDS, or the dense MFMA product; the
 // row-major launches the level is cut into; and whether the level is handed back so that the tail runs in groups of trees.
 // One pure function of the level's shape and of the tunables: the build launches exactly what plan_level returns.  Plain C++

@@ -3484,7 +3484,7 @@ static ScreenSearch screen_of_dataset(const ah_dataset *ds, bool int8) {
     ss.rows16 = ds->d_rows_h16;
     ss.max_stats = make_float4(ds->screen_max[0], ds->screen_max[1], ds->screen_max[2], 0.0f);
     ss.hpitch = ds->hpitch;
-    // accumulation-error factors as in the forest build (forest.hip: build_batch), 4x over the standard model
+    // accumulation-error factors as in the forest build (forest.hip: BatchBuild::setup_device), 4x over the standard model
     ss.gamma_s = (float)(4.0 * (2.0 * (ds->hpitch / 16) + 8.0) * 5.9604645e-8);
     ss.gamma_r = (float)(4.0 * ((double)(ds->dims / 32) + 6.0 + 62.0) * 5.9604645e-8);
     if (int8) {

@@ -1,5 +1,5 @@
 """What every level of a build chooses and launches (plan_level in arroy_amd/csrc/level_plan.h and the launchers of
-build_batch in forest.hip), pinned to the counts the build made before the plan was written down as one function.
+BatchBuild::launch_level in forest.hip), pinned to the counts the build made before the plan was written down as one function.
 
 Four shapes (those of test_gpu_margin_modes.py) x 16 / 13 / 7 trees x AUTO and seven forced modes, plus one build small enough
 for the tail to run in groups of trees: the decision-bearing part of ah_build_stats and the forest's digest equal the values in

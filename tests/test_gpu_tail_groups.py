@@ -1,4 +1,4 @@
-"""The tail of a build in groups of trees (AH_BUILD_TAIL_GROUPS; build_batch in arroy_amd/csrc/forest.hip): the last big
+"""The tail of a build in groups of trees (AH_BUILD_TAIL_GROUPS; BatchBuild::run_tail_groups in arroy_amd/csrc/forest.hip): the last big
 level and what follows it run tree group by tree group, so that a group's item ids and normals leave the device under
 the next group's kernels.  Trees never interact (src/writer.rs:556-561), so the forest must be the one the
 level-by-level loop builds and the oracle builds (`make_tree_in_file`, src/writer.rs:1167-1261), node for node, whatever
