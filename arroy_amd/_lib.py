@@ -362,6 +362,13 @@ SIGNATURES = {
     # what a resident index holds, and the removal of its free slots and orphaned normal rows
     "ah_index_footprint_get": (C.c_int, [_VP, C.POINTER(AhIndexFootprint)]),
     "ah_index_compact": (C.c_int, [_VP, _U32P, C.POINTER(AhIndexCompactStats)]),
+    # resident forests: a build that stays on the device, and the index calls that read it there
+    "ah_build_forest_resident": (C.c_int, [_VP, C.POINTER(AhBuildOptions), C.POINTER(C.c_void_p)]),
+    "ah_build_subtrees_resident": (C.c_int, [_VP, C.POINTER(AhBuildOptions), _U32P, _U64P, C.POINTER(C.c_void_p)]),
+    "ah_forest_resident_info": (C.c_int, [_VP, C.POINTER(C.c_int), C.POINTER(C.c_uint64)]),
+    "ah_forest_release_device": (C.c_int, [_VP]),
+    "ah_index_create_from_forest": (C.c_int, [_VP, _VP, _U32P, C.POINTER(C.c_int), C.POINTER(C.c_void_p)]),
+    "ah_index_graft_forest": (C.c_int, [_VP, _VP, _U32P, _U32P, _U32P, C.POINTER(C.c_int)]),
     # `Reader::assert_validity` / `Reader::stats` of a resident index, and of a view the host holds
     "ah_index_audit": (C.c_int, [_VP, C.POINTER(AhIndexAuditReport), C.POINTER(AhTreeStats)]),
     "ah_forest_view_audit": (C.c_int, [_VP, C.POINTER(AhForestView), C.POINTER(AhIndexAuditReport), C.POINTER(AhTreeStats)]),

@@ -35,6 +35,8 @@
 #include "screen_device.h"
 #include "level_plan.h"
 #include "forest_records.h"  // FNode, LevelInfo, FTile, HostRec ...: the PODs host and kernels share
+#include "forest_resident.h"  // a resident forest: which record becomes which row of its device copy
+#include "index_device.h"     // ForestDevice, for_spans, IndexCall::span
 #include "encode.h"
 #include "node_codec.h"
 
@@ -79,6 +81,28 @@ __global__ void k_ids_to_rows(DataView dv, uint32_t *perm, uint64_t total, uint3
         if (row == ~0ull) atomicOr(err, 1u);
         perm[g] = (uint32_t)row;
     }
+}
+
+// A resident forest's rows: entries [lo, hi), a block each.  The record of the entry (where its level left it: vector first,
+// header at hdr_off) -> row `row` of the forest's device rows and its header words, as k_unpack_normals (search.hip) writes
+// them from a view: the words of the stored vector are copied, the rest of the row pitch is zero.  W: uint4 where the record
+// stride, the row pitch and the vector are whole 16-byte pieces, else 32-bit words (a BQ row is made of uint64_t words).
+struct ResidentEntry {
+    const uint8_t *rec;
+    uint32_t row, pad;
+};
+template <typename W>
+__global__ __launch_bounds__(256) void k_resident_rows(const ResidentEntry *__restrict__ entries, uint32_t lo, uint32_t hi,
+                                                       uint64_t hdr_off, uint32_t valid_w, uint32_t row_w, uint32_t hf,
+                                                       uint32_t n_rows, W *__restrict__ rows, float *__restrict__ hdrs) {
+    const uint64_t e = (uint64_t)lo + blockIdx.x;
+    if (e >= hi) return;
+    const ResidentEntry en = entries[e];
+    if (en.row >= n_rows) return;  // (never: the host numbers the rows it allocated)
+    const W *src = reinterpret_cast<const W *>(en.rec);
+    W *dst = rows + (uint64_t)en.row * row_w;
+    for (uint32_t i = threadIdx.x; i < row_w; i += blockDim.x) dst[i] = i < valid_w ? src[i] : W{};
+    if (threadIdx.x < hf) hdrs[(uint64_t)en.row * hf + threadIdx.x] = reinterpret_cast<const float *>(en.rec + hdr_off)[threadIdx.x];
 }
 
 // One wave per pending node: sample 2+10 items with the policy RNG, run create_split.
@@ -1818,7 +1842,27 @@ struct ah_forest {
     uint64_t descendants_len = 0;
     uint64_t normal_stride = 0, normal_vector_offset = 0, normal_header_offset = 0;
     ah_build_stats stats{};
+    // A resident forest (ah_build_forest_resident / ah_build_subtrees_resident): next to the host content, the arrays an index
+    // of this forest holds, on the device it was built on.  want_device: the build is to leave them (cleared when it cannot);
+    // has_device: the build is over and they are complete — until ah_forest_release_device or an index call that consumes them.
+    ForestDevice dev;
+    uint32_t dev_rows_cap = 0;
+    bool want_device = false, has_device = false;
+    void release_device(bool keep_ids = false, bool keep_rows = false) {
+        NoFailScope no_fail;
+        if ((dev.ids && !keep_ids) || ((dev.rows || dev.hdrs) && !keep_rows)) {
+            DeviceRestore restore_device;
+            if (dev.device >= 0) (void)hipSetDevice(dev.device);
+            if (dev.ids && !keep_ids) (void)dev_free(dev.ids);
+            if (dev.rows && !keep_rows) (void)dev_free(dev.rows);
+            if (dev.hdrs && !keep_rows) (void)dev_free(dev.hdrs);
+        }
+        dev = ForestDevice{};
+        dev_rows_cap = 0;
+        want_device = has_device = false;
+    }
     ~ah_forest() {
+        release_device();
         host_pool().give(normals_blob, normals_len);
         host_pool().give(desc_blob, descendants_len * 4);
     }
@@ -3070,6 +3114,10 @@ struct BatchBuild {
     FNode *group_spare = nullptr;      // third node table of the grouped tail
     std::deque<int> done_groups;       // groups whose tables are all digested and whose node list is still to be emitted
 
+    // ---- a resident forest (resident_stage): where every level left its records, in launch order
+    std::vector<ResidentChunk> res_chunks;
+    std::vector<const uint8_t *> res_chunk_dev;
+
     BatchBuild(ah_dataset *ds_, const ah_build_options *opt_, uint32_t first_tree_, uint32_t n_trees_, uint32_t split_after_,
                ah_forest *forest_, Context *ctx_, const uint32_t *subset_ids_, const uint64_t *subset_offsets_, StreamBuild *sb_)
         : ds(ds_), opt(opt_), first_tree(first_tree_), n_trees(n_trees_), split_after(split_after_), forest(forest_), ctx(ctx_),
@@ -3475,6 +3523,10 @@ struct BatchBuild {
         if (screen8) AH_TRY(shadow8_arena.take((uint64_t)n_nodes * stride8, &shadow8_d));
         normals_bytes += chunk_bytes;
         lv.chunk_d = chunk_d, lv.chunk_bytes = chunk_bytes, lv.chunk_host_off = chunk_host_off;
+        if (forest->want_device) {  // (a resident forest: the records stay where they are until resident_stage has read them)
+            res_chunks.push_back(ResidentChunk{chunk_host_off, n_nodes});
+            res_chunk_dev.push_back(chunk_d);
+        }
         // Host side of the normals: reserved now; the pages of THIS level's records were started one level ago (a level has
         // about twice the nodes of the one before), those of the NEXT level start now — committing the 2.6 GB of the deepest
         // level takes longer than the ~160 ms that level runs, and the loop must not wait for page faults before it can
@@ -3800,11 +3852,98 @@ struct BatchBuild {
                     (unsigned long long)sb->target.batches, sb->target.bytes / 1e9);
         return AH_OK;
     }
+    // A resident forest: this batch's share of the device copy (ForestDevice), once its node list is complete and while the
+    // read-back of its last chunks is still under way.  The planes of every level, read where the level left them, become rows
+    // in view order — the host uploads one 16-byte entry per plane (forest_resident.h) — and the batch's permutation becomes
+    // the ids at desc_base.  No memory for it = no device copy: the forest is an ordinary one and the build goes on.
+    int resident_stage() {
+        if (!forest->want_device) return AH_OK;
+        ForestDevice &fd = forest->dev;
+        const uint32_t hf = header_floats(ds->metric);
+        const size_t row_bytes = ds->row_bytes();
+        ResidentPlan plan;
+        std::vector<ResidentEntry> entries;
+        DevMem table, grown_rows, grown_hdrs;
+        bool ok = desc_base + M <= fd.ids_len;
+        try {
+            ok = ok && resident_plan(forest->nodes.data() + records.node_base, forest->nodes.size() - records.node_base, res_chunks, nstride,
+                                     fd.n_rows, desc_base, M, &plan);
+            if (ok) {
+                entries.resize(plan.rows.size());
+                for (size_t i = 0; i < entries.size(); i++)
+                    entries[i] = ResidentEntry{res_chunk_dev[plan.rows[i].chunk] + (uint64_t)plan.rows[i].index * nstride, plan.rows[i].row, 0u};
+            }
+        } catch (const std::bad_alloc &) {
+            ok = false;
+        }
+        const uint32_t total = ok ? fd.n_rows + (uint32_t)entries.size() : 0u;
+        if (ok && total > forest->dev_rows_cap)  // exactly the rows so far: an index may adopt the blocks as its own
+            ok = dev_malloc(&grown_rows.p, (size_t)total * row_bytes, true) == hipSuccess &&
+                 dev_malloc(&grown_hdrs.p, (size_t)total * hf * 4, true) == hipSuccess;
+        if (ok && !entries.empty()) ok = dev_malloc(&table.p, entries.size() * sizeof(ResidentEntry), true) == hipSuccess;
+        if (!ok) {
+            (void)hipGetLastError();
+            forest->release_device();
+            return AH_OK;
+        }
+        // Everything below is queued on `s`; a failure waits for the stream before the blocks above are freed, and the forest's
+        // pointers change only after the last wait.
+        struct StreamWait {
+            hipStream_t s;
+            bool armed = true;
+            ~StreamWait() {
+                if (armed) (void)hipStreamSynchronize(s);
+            }
+        } wait_on_failure{s};
+        AH_HIP(hipEventRecord(bc.ev_attempt[0], s));
+        void *rows_to = grown_rows.p ? grown_rows.p : fd.rows;
+        float *hdrs_to = grown_rows.p ? grown_hdrs.as<float>() : fd.hdrs;
+        if (grown_rows.p && fd.n_rows) {  // (a later batch: the rows of the batches before it move)
+            AH_HIP(hipMemcpyAsync(rows_to, fd.rows, (size_t)fd.n_rows * row_bytes, hipMemcpyDeviceToDevice, s));
+            AH_HIP(hipMemcpyAsync(hdrs_to, fd.hdrs, (size_t)fd.n_rows * hf * 4, hipMemcpyDeviceToDevice, s));
+        }
+        if (M) AH_HIP(hipMemcpyAsync(fd.ids + desc_base, final_perm.p, M * 4, hipMemcpyDeviceToDevice, s));
+        if (!entries.empty()) {
+            AH_HIP(hipMemcpyAsync(table.p, entries.data(), entries.size() * sizeof(ResidentEntry), hipMemcpyHostToDevice, s));
+            const size_t valid_bytes = ah_vector_size(ds->metric, ds->dims);
+            const bool wide = (nstride % 16) == 0 && (row_bytes % 16) == 0 && (valid_bytes % 16) == 0;
+            const uint32_t unit = wide ? 16u : 4u;
+            for_spans(entries.size(), std::min<uint64_t>(IndexCall::span(), 1ull << 30), [&](uint64_t lo, uint64_t hi) {
+                if (wide)
+                    hipLaunchKernelGGL(k_resident_rows<uint4>, dim3((unsigned)(hi - lo)), dim3(256), 0, s, table.as<const ResidentEntry>(), (uint32_t)lo,
+                                       (uint32_t)hi, hdr_off, (uint32_t)(valid_bytes / unit), (uint32_t)(row_bytes / unit), hf, total,
+                                       reinterpret_cast<uint4 *>(rows_to), hdrs_to);
+                else
+                    hipLaunchKernelGGL(k_resident_rows<uint32_t>, dim3((unsigned)(hi - lo)), dim3(256), 0, s, table.as<const ResidentEntry>(),
+                                       (uint32_t)lo, (uint32_t)hi, hdr_off, (uint32_t)(valid_bytes / unit), (uint32_t)(row_bytes / unit), hf, total,
+                                       reinterpret_cast<uint32_t *>(rows_to), hdrs_to);
+            });
+            AH_HIP(hipGetLastError());
+        }
+        AH_HIP(hipEventRecord(bc.ev_attempt[1], s));
+        AH_HIP(hipStreamSynchronize(s));  // (the table and the levels' records are read no more)
+        wait_on_failure.armed = false;
+        if (grown_rows.p) {  // the grown blocks become the forest's; the old ones go when the stage returns
+            std::swap(grown_rows.p, fd.rows);
+            void *old_hdrs = fd.hdrs;
+            fd.hdrs = grown_hdrs.as<float>();
+            grown_hdrs.p = old_hdrs;
+            forest->dev_rows_cap = total;
+            fd.bytes = std::max<uint64_t>(1, fd.ids_len) * 4 + (uint64_t)total * (row_bytes + (uint64_t)hf * 4);
+        }
+        fd.n_rows = total;
+        float stage_ms = 0.0f;
+        if (hipEventElapsedTime(&stage_ms, bc.ev_attempt[0], bc.ev_attempt[1]) == hipSuccess) forest->stats.seconds_device += stage_ms * 1e-3;
+        if (timing)
+            fprintf(stderr, "[ah] resident stage: %zu planes -> rows, %llu ids: %.3f ms on the device\n", entries.size(), (unsigned long long)M, stage_ms);
+        return AH_OK;
+    }
     // the node list of the trees not emitted yet (all of them, unless the tail ran in groups), then the copies still in flight
     int finish_materialised() {
         AH_TRY(emit_range(records.emit_tree, n_trees));
         AH_REQUIRE(records.emit_cursor - records.node_base == records.n_recs, AH_ERR_DEVICE,
                    "forest build: %zu nodes emitted of %zu (internal error)", records.emit_cursor - records.node_base, records.n_recs);
+        AH_TRY(resident_stage());
         forest->stats.split_nodes += records.n_split;
         forest->stats.descendant_nodes += records.n_desc;
         const auto t_emitted = std::chrono::steady_clock::now();
@@ -3843,8 +3982,31 @@ static int build_batch(ah_dataset *ds, const ah_build_options *opt, uint32_t fir
 
 extern "C" {
 
+// The blocks of a resident forest's device copy: the ids whole (their number is known before the build), one row for the
+// batches to grow from.  false: no memory — the forest will be an ordinary one.
+static bool forest_device_begin(ah_forest *forest, const ah_dataset *ds, uint64_t total_ids) {
+    if (total_ids >= 0xFFFFFFFFull) return false;  // (no index takes such a forest)
+    ForestDevice &fd = forest->dev;
+    const uint32_t hf = header_floats(ds->metric);
+    fd.device = ds->device;
+    fd.metric = ds->metric;
+    fd.dims = ds->dims;
+    const bool ok = dev_malloc((void **)&fd.ids, std::max<uint64_t>(1, total_ids) * 4, true) == hipSuccess &&
+                    dev_malloc(&fd.rows, ds->row_bytes(), true) == hipSuccess && dev_malloc((void **)&fd.hdrs, (size_t)hf * 4, true) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        forest->release_device();
+        return false;
+    }
+    fd.ids_len = total_ids;
+    forest->dev_rows_cap = 1;
+    fd.bytes = std::max<uint64_t>(1, total_ids) * 4 + ds->row_bytes() + (uint64_t)hf * 4;
+    forest->want_device = true;
+    return true;
+}
+
 static int build_forest_impl(ah_dataset *ds, const ah_build_options *options, const uint32_t *subset_ids,
-                             const uint64_t *subset_offsets, ah_forest **out, StreamBuild *sb = nullptr) {
+                             const uint64_t *subset_offsets, ah_forest **out, StreamBuild *sb = nullptr, bool resident = false) {
     AH_REQUIRE(out, AH_ERR_INVALID_ARGUMENT, "out is NULL");
     *out = nullptr;
     AH_REQUIRE(ds && options, AH_ERR_INVALID_ARGUMENT, "NULL argument");
@@ -3874,6 +4036,9 @@ static int build_forest_impl(ah_dataset *ds, const ah_build_options *options, co
     forest->normal_header_offset = ds->row_bytes();
     forest->normal_stride = normal_record_stride(ds);
     int st = AH_OK;
+    if (resident && !sb)
+        (void)forest_device_begin(forest, ds, subset_ids ? (options->n_trees ? subset_offsets[options->n_trees] - subset_offsets[0] : 0)
+                                                         : ds->n * options->n_trees);
     if (!subset_ids && ds->n <= split_after) {
         // fit_in_descendant at the root (src/writer.rs:1183-1188): every tree is one Descendants node
         const uint64_t total = sb ? ds->n : ds->n * options->n_trees;  // (streaming: one copy of the id list serves every tree)
@@ -3937,6 +4102,17 @@ static int build_forest_impl(ah_dataset *ds, const ah_build_options *options, co
             forest->nodes.push_back(nd);
             forest->stats.descendant_nodes++;
         }
+        if (forest->want_device && total) {  // the same lists on the device: every tree's is the dataset's ids in row order
+            ContextLease lease(ds);
+            hipError_t e = lease.c ? hipSuccess : hipErrorUnknown;
+            if (e == hipSuccess) {
+                hipLaunchKernelGGL(k_init_perm, dim3(64), dim3(256), 0, lease.c->stream, forest->dev.ids, ds->n, options->n_trees);
+                if (!ds->identity_ids) hipLaunchKernelGGL(k_rows_to_ids, dim3(64), dim3(256), 0, lease.c->stream, forest->dev.ids, total, ds->d_ids);
+                e = hipGetLastError();
+                if (e == hipSuccess) e = hipStreamSynchronize(lease.c->stream);
+            }
+            if (e != hipSuccess) forest->release_device();
+        }
     } else if (options->n_trees) {
         ContextLease lease(ds);
         if (!lease.c) {
@@ -3952,8 +4128,10 @@ static int build_forest_impl(ah_dataset *ds, const ah_build_options *options, co
             free_b += dev_cache_idle_bytes(ds->device);  // idle blocks of the caching allocator are ours to use
             uint32_t batch = options->n_trees;
             if (!subset_ids) {
-                const uint64_t per_tree =
+                uint64_t per_tree =
                     ds->n * 18 + ((ds->n / ((uint64_t)split_after + 1)) + 2) * 3 * (ds->row_bytes() + 192) + (1u << 20);
+                // a resident forest: its rows while they grow (the old and the new block of a later batch) next to the arena
+                if (forest->want_device) per_tree += ((ds->n / ((uint64_t)split_after + 1)) + 2) * 2 * 2 * (ds->row_bytes() + 8);
                 uint64_t fit = (uint64_t)(free_b * 0.8) / per_tree;
                 if (fit < 1) fit = 1;
                 batch = (uint32_t)std::min<uint64_t>(fit, options->n_trees);
@@ -3979,6 +4157,7 @@ static int build_forest_impl(ah_dataset *ds, const ah_build_options *options, co
         delete forest;
         return st;
     }
+    forest->has_device = forest->want_device;  // (every batch has added its share)
     forest->stats.seconds_total = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     {  // the reserve helper's figures go to the first build that joined it
         std::lock_guard<std::mutex> lk(ds->mu);
@@ -4084,6 +4263,13 @@ int ah_build_forest(ah_dataset *ds, const ah_build_options *options, ah_forest *
 }
 
 // The same build with the node sink inside it (include/arroy_hip.h, "Streaming build"): nothing is materialised.
+// ... and with the device copy an index is made from kept (include/arroy_hip.h, "Resident forests")
+int ah_build_forest_resident(ah_dataset *ds, const ah_build_options *options, ah_forest **out) {
+    AH_GUARDED("ah_build_forest_resident")
+    return build_forest_impl(ds, options, nullptr, nullptr, out, nullptr, true);
+    AH_GUARDED_END
+}
+
 int ah_build_forest_stream(ah_dataset *ds, const ah_build_options *options, ah_node_batch_fn sink, void *user,
                            uint32_t *out_roots, ah_build_stats *out_stats) {
     AH_GUARDED("ah_build_forest_stream")
@@ -4126,9 +4312,8 @@ int ah_build_forest_stream_encoded(ah_dataset *ds, const ah_build_options *optio
 
 // `incremental_index_large_descendant` (src/writer.rs:660-739) for many descendants at once: tree t of the result is
 // `make_tree_in_file` over the ascending id list item_ids[offsets[t] .. offsets[t+1]).
-int ah_build_subtrees(ah_dataset *ds, const ah_build_options *options, const uint32_t *item_ids, const uint64_t *offsets,
-                      ah_forest **out) {
-    AH_GUARDED("ah_build_subtrees")
+static int build_subtrees_impl(ah_dataset *ds, const ah_build_options *options, const uint32_t *item_ids, const uint64_t *offsets,
+                               ah_forest **out, bool resident) {
     AH_REQUIRE(options, AH_ERR_INVALID_ARGUMENT, "NULL argument");
     AH_REQUIRE((item_ids && offsets) || options->n_trees == 0, AH_ERR_INVALID_ARGUMENT, "NULL id lists");
     for (uint32_t t = 0; t < options->n_trees; t++) {
@@ -4138,7 +4323,18 @@ int ah_build_subtrees(ah_dataset *ds, const ah_build_options *options, const uin
                        "sub-tree id lists must be strictly ascending (RoaringBitmap order)");
     }
     static const uint32_t dummy = 0;
-    return build_forest_impl(ds, options, item_ids ? item_ids : &dummy, offsets, out);
+    return build_forest_impl(ds, options, item_ids ? item_ids : &dummy, offsets, out, nullptr, resident);
+}
+int ah_build_subtrees(ah_dataset *ds, const ah_build_options *options, const uint32_t *item_ids, const uint64_t *offsets,
+                      ah_forest **out) {
+    AH_GUARDED("ah_build_subtrees")
+    return build_subtrees_impl(ds, options, item_ids, offsets, out, false);
+    AH_GUARDED_END
+}
+int ah_build_subtrees_resident(ah_dataset *ds, const ah_build_options *options, const uint32_t *item_ids, const uint64_t *offsets,
+                               ah_forest **out) {
+    AH_GUARDED("ah_build_subtrees_resident")
+    return build_subtrees_impl(ds, options, item_ids, offsets, out, true);
     AH_GUARDED_END
 }
 
@@ -4351,6 +4547,23 @@ int ah_forest_visit(const ah_forest *forest, ah_node_sink_fn sink, void *user) {
     AH_GUARDED_END
 }
 
+int ah_forest_resident_info(const ah_forest *forest, int *out_resident, uint64_t *out_device_bytes) {
+    AH_GUARDED("ah_forest_resident_info")
+    AH_REQUIRE(forest, AH_ERR_INVALID_ARGUMENT, "forest is NULL");
+    if (out_resident) *out_resident = forest->has_device ? 1 : 0;
+    if (out_device_bytes) *out_device_bytes = forest->has_device ? forest->dev.bytes : 0;
+    return AH_OK;
+    AH_GUARDED_END
+}
+
+int ah_forest_release_device(ah_forest *forest) {
+    AH_GUARDED("ah_forest_release_device")
+    AH_REQUIRE(forest, AH_ERR_INVALID_ARGUMENT, "forest is NULL");
+    forest->release_device();
+    return AH_OK;
+    AH_GUARDED_END
+}
+
 int ah_forest_destroy(ah_forest *forest) {
     AH_GUARDED("ah_forest_destroy")
     NoFailScope no_fail;
@@ -4414,3 +4627,9 @@ int ah_synth_rows_host(uint64_t seed, int distribution, uint64_t first_item, uin
 }
 
 }  // extern "C"
+
+namespace ah {
+// the index calls' side of a resident forest (index_device.h)
+const ForestDevice *forest_device(const ah_forest *forest) { return forest && forest->has_device ? &forest->dev : nullptr; }
+void forest_device_consume(ah_forest *forest, bool adopted_ids, bool adopted_rows) { forest->release_device(adopted_ids, adopted_rows); }
+}  // namespace ah

@@ -196,6 +196,28 @@ int validate_forest_view(const ah_dataset *ds, const ah_forest_view &v);
 // *d_err (zeroed by the caller) when an id is no row of the dataset
 int launch_route_items(ah_index *ix, const uint32_t *d_ids, uint64_t n, const uint64_t *d_seeds, uint32_t *d_leaf, uint32_t *d_err,
                        hipStream_t s);
+// The device copy of a resident forest (forest.hip, ah_build_forest_resident / ah_build_subtrees_resident): the arrays
+// ah_index_create_from_view would make of the forest's own view, on the device the forest was built on.  rows: n_rows rows at
+// the dataset's row pitch, row r the r-th split node with a plane in view order; hdrs: header_floats words per row; ids: the
+// view's descendants blob.  Every array is a block of dev_malloc of exactly max(1, count) elements.
+struct ForestDevice {
+    int device = -1, metric = 0;
+    uint32_t dims = 0;
+    uint32_t *ids = nullptr;
+    uint64_t ids_len = 0;
+    void *rows = nullptr;
+    float *hdrs = nullptr;
+    uint32_t n_rows = 0;
+    uint64_t bytes = 0;  // what the three blocks were asked for
+};
+// forest.hip: the device copy of `forest`, nullptr when it has none (an ordinary forest, a released or a consumed one)
+const ForestDevice *forest_device(const ah_forest *forest);
+// forest.hip: an index call has been served by the device copy: the forest is an ordinary forest from here on.  The blocks
+// named adopted now belong to the caller, the others are freed.  Nothing here can fail.
+void forest_device_consume(ah_forest *forest, bool adopted_ids, bool adopted_rows);
+// search.hip: the index of a view (ah_index_create_from_view); with `src`, the view of the resident forest whose device copy
+// it is: nothing is validated, uploaded or unpacked, and on success the index has adopted the blocks of `src`
+int index_create_impl(ah_dataset *ds, const ah_forest_view &v, const ForestDevice *src, ah_index **out);
 // search.hip: k_unpack_normals, queued on `s`: n records (recs + offsets[r]) -> rows / headers of the normals
 int launch_unpack_normals(const ah_dataset *ds, const uint8_t *d_recs, const uint64_t *d_offsets, uint32_t n, uint64_t vec_off,
                           uint64_t hdr_off, void *d_rows, float *d_headers, hipStream_t s);

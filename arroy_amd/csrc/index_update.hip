@@ -1390,7 +1390,11 @@ int insert_impl(ah_index *ix, const uint32_t *ids, size_t n, const uint64_t *see
     return AH_OK;
 }
 
-int graft_impl(ah_index *ix, const ah_forest_view &v, const uint32_t *targets, const uint32_t *new_index, uint32_t *out_new_of_old) {
+// `src` (ah_index_graft_forest, ah_index_create_from_forest): the view is the one of the resident forest whose device copy `src`
+// is.  The lists are gathered from its ids and its rows are copied behind the index's own, device to device: neither blob of the
+// view is read.  An index without a normal row ADOPTS the rows and headers instead (*adopted_rows: the blocks changed hands).
+int graft_impl(ah_index *ix, const ah_forest_view &v, const uint32_t *targets, const uint32_t *new_index, uint32_t *out_new_of_old,
+               const ForestDevice *src = nullptr, bool *adopted_rows = nullptr) {
     ah_dataset *ds = ix->ds;
     IndexCall call;
     AH_TRY(call.begin(ds));
@@ -1453,6 +1457,8 @@ int graft_impl(ah_index *ix, const ah_forest_view &v, const uint32_t *targets, c
     }
     const uint32_t n_vnormals = (uint32_t)offsets.size(), n_added = (uint32_t)added_roots.size();
     AH_REQUIRE((uint64_t)ix->n_normals + n_vnormals < 0xFFFFFFFFull, AH_ERR_INVALID_ARGUMENT, "too many normals for 32-bit rows");
+    AH_REQUIRE(!src || (src->n_rows == n_vnormals && src->ids_len == v.descendants_len), AH_ERR_DEVICE,
+               "the forest's device copy does not match its view (internal error)");
     // ---- buffers
     const uint32_t hf = header_floats(ds->metric);
     const size_t row_bytes = ds->row_bytes();
@@ -1469,14 +1475,14 @@ int graft_impl(ah_index *ix, const ah_forest_view &v, const uint32_t *targets, c
     a.first_row = ix->n_normals;
     uint32_t *tile_sums = nullptr;
     GraftUploads<DNode> u{};
-    const Workspace ws = graft_workspace(a, &tile_sums, u, GraftSizes{n_old, n_used, n_view, n_new, n_repl, n_added, v.descendants_len},
+    const Workspace ws = graft_workspace(a, &tile_sums, u, GraftSizes{n_old, n_used, n_view, n_new, n_repl, n_added, src ? 0 : v.descendants_len},
                                          kScanTile, GCTL_WORDS);
     DevMem work, new_nodes, new_roots, new_desc, recs, offs, grown_rows, grown_hdrs;
     AH_TRY(alloc(&work, ws.bytes()));
     ws.carve(work.p, ws.bytes());
     a.vfin = u.vfin;  // (the kernels read what the host uploads through these)
     a.vtgt = u.vtgt;
-    a.vdesc = u.vdesc;
+    a.vdesc = src ? src->ids : u.vdesc;
     a.vnodes = u.vnodes;
     AH_TRY(alloc(&new_nodes, (size_t)n_new * sizeof(DNode)));
     AH_TRY(alloc(&new_roots, ((size_t)n_trees + n_added) * 4));
@@ -1488,7 +1494,7 @@ int graft_impl(ah_index *ix, const ah_forest_view &v, const uint32_t *targets, c
     }
     if (n_repl) AH_HIP(hipMemcpyAsync(u.repl, repl.data(), (size_t)n_repl * 4, hipMemcpyHostToDevice, s));
     if (n_added) AH_HIP(hipMemcpyAsync(u.added, added_roots.data(), (size_t)n_added * 4, hipMemcpyHostToDevice, s));
-    if (v.descendants_len) AH_HIP(hipMemcpyAsync(u.vdesc, v.descendants, v.descendants_len * 4, hipMemcpyHostToDevice, s));
+    if (v.descendants_len && !src) AH_HIP(hipMemcpyAsync(u.vdesc, v.descendants, v.descendants_len * 4, hipMemcpyHostToDevice, s));
     if (n_repl) {  // the targets: in use and Descendants nodes
         std::vector<uint32_t> kinds(n_repl);
         hipLaunchKernelGGL(k_graft_peek, dim3(grid_of(n_repl, kIxBlock, 1024)), dim3(kIxBlock), 0, s, (const DNode *)ix->d_nodes,
@@ -1520,7 +1526,10 @@ int graft_impl(ah_index *ix, const ah_forest_view &v, const uint32_t *targets, c
     uint32_t cap = ix->normals_cap;
     void *rows = ix->d_nrows;
     float *hdrs = ix->d_nhdrs;
-    if (need > cap) {
+    const bool adopt = src && ix->n_normals == 0 && n_vnormals != 0;  // (the forest's blocks hold exactly its rows)
+    if (adopt) {
+        cap = n_vnormals;
+    } else if (need > cap) {
         cap = (uint32_t)std::min<uint64_t>(0xFFFFFFFFull, std::max<uint64_t>(need, 2 * (uint64_t)cap));
         AH_TRY(alloc(&grown_rows, (size_t)cap * row_bytes));
         AH_TRY(alloc(&grown_hdrs, (size_t)cap * hf * 4));
@@ -1531,7 +1540,11 @@ int graft_impl(ah_index *ix, const ah_forest_view &v, const uint32_t *targets, c
             AH_HIP(hipMemcpyAsync(hdrs, ix->d_nhdrs, (size_t)ix->n_normals * hf * 4, hipMemcpyDeviceToDevice, s));
         }
     }
-    if (n_vnormals) {
+    if (n_vnormals && src && !adopt) {
+        AH_HIP(hipMemcpyAsync(static_cast<uint8_t *>(rows) + (size_t)ix->n_normals * row_bytes, src->rows, (size_t)n_vnormals * row_bytes,
+                              hipMemcpyDeviceToDevice, s));
+        AH_HIP(hipMemcpyAsync(hdrs + (size_t)ix->n_normals * hf, src->hdrs, (size_t)n_vnormals * hf * 4, hipMemcpyDeviceToDevice, s));
+    } else if (n_vnormals && !src) {
         AH_TRY(alloc(&recs, v.normals_len));
         AH_TRY(alloc(&offs, offsets.size() * 8));
         AH_HIP(hipMemcpyAsync(recs.p, v.normals, v.normals_len, hipMemcpyHostToDevice, s));
@@ -1552,6 +1565,11 @@ int graft_impl(ah_index *ix, const ah_forest_view &v, const uint32_t *targets, c
     AH_TRY(read_back(ctl, a.ctl, GCTL_WORDS, s));
     AH_REQUIRE(ctl[GCTL_ERR] == 0, AH_ERR_DEVICE, "the index graft found its own counts inconsistent (%u): the index is unchanged", ctl[GCTL_ERR]);
     if (out_new_of_old && n_old) memcpy(out_new_of_old, map_out.data(), (size_t)n_old * 4);
+    if (adopt) {  // (nothing fails from here on: the blocks change hands, the index's own go when the call returns)
+        grown_rows.p = src->rows;
+        grown_hdrs.p = src->hdrs;
+        if (adopted_rows) *adopted_rows = true;
+    }
     const bool grown = grown_rows.p != nullptr;  // (the rows moved into larger arrays: cap is their room)
     IndexCommit c(ix, &new_nodes, &new_roots, &new_desc, nullptr, grown ? &grown_rows : nullptr, grown ? &grown_hdrs : nullptr);
     c.drop_rank = true;
@@ -1776,6 +1794,72 @@ int ah_index_graft(ah_index *ix, const ah_forest_view *view, const uint32_t *tar
     AH_REQUIRE(v.n_trees == 0 || targets, AH_ERR_INVALID_ARGUMENT, "targets is NULL");
     DeviceRestore restore_device;
     return graft_impl(ix, v, targets, new_index, out_new_of_old);
+    AH_GUARDED_END
+}
+
+// The forest's device copy when it can serve a call on `ds`, else nullptr (the call then takes the host view): resident, on the
+// dataset's device, of its metric and dimensions.
+static const ForestDevice *usable_forest_device(const ah_dataset *ds, const ah_forest *forest) {
+    const ForestDevice *fd = forest_device(forest);
+    return fd && fd->device == ds->device && fd->metric == ds->metric && fd->dims == ds->dims ? fd : nullptr;
+}
+
+int ah_index_graft_forest(ah_index *ix, ah_forest *forest, const uint32_t *targets, const uint32_t *new_index, uint32_t *out_new_of_old,
+                          int *out_from_device) {
+    AH_GUARDED("ah_index_graft_forest")
+    if (out_from_device) *out_from_device = 0;
+    AH_TRY(index_updatable(ix));
+    AH_REQUIRE(forest, AH_ERR_INVALID_ARGUMENT, "forest is NULL");
+    ah_forest_view v;
+    AH_TRY(ah_forest_view_get(forest, &v));
+    const ForestDevice *src = usable_forest_device(ix->ds, forest);
+    if (!src) AH_TRY(validate_forest_view(ix->ds, v));  // (a library-built forest: only the caller's arrays are judged on the device path)
+    AH_REQUIRE(v.n_trees == 0 || targets, AH_ERR_INVALID_ARGUMENT, "targets is NULL");
+    DeviceRestore restore_device;
+    bool adopted_rows = false;
+    AH_TRY(graft_impl(ix, v, targets, new_index, out_new_of_old, src, &adopted_rows));
+    if (src) {
+        forest_device_consume(forest, false, adopted_rows);
+        if (out_from_device) *out_from_device = 1;
+    }
+    return AH_OK;
+    AH_GUARDED_END
+}
+
+int ah_index_create_from_forest(ah_dataset *ds, ah_forest *forest, const uint32_t *new_index, int *out_from_device, ah_index **out) {
+    AH_GUARDED("ah_index_create_from_forest")
+    if (out_from_device) *out_from_device = 0;
+    AH_REQUIRE(out, AH_ERR_INVALID_ARGUMENT, "out is NULL");
+    *out = nullptr;
+    AH_REQUIRE(ds && forest, AH_ERR_INVALID_ARGUMENT, "NULL argument");
+    ah_forest_view v;
+    AH_TRY(ah_forest_view_get(forest, &v));
+    const ForestDevice *src = usable_forest_device(ds, forest);
+    DeviceRestore restore_device;
+    if (!new_index) {  // the forest's own numbering: the index of ah_index_create, on the forest's blocks
+        AH_TRY(index_create_impl(ds, v, src, out));
+        if (src) forest_device_consume(forest, true, true);
+    } else {
+        // the store's numbering: every tree grafted as a new root onto an index of nothing, under the graft's renumbering and checks
+        if (!src) AH_TRY(validate_forest_view(ds, v));
+        ah_forest_view none{};
+        none.normal_stride = v.normal_stride;
+        none.normal_vector_offset = v.normal_vector_offset;
+        none.normal_header_offset = v.normal_header_offset;
+        ah_index *ix = nullptr;
+        AH_TRY(index_create_impl(ds, none, nullptr, &ix));
+        std::vector<uint32_t> targets(v.n_trees, AH_NEW_ROOT);
+        bool adopted_rows = false;
+        const int st = graft_impl(ix, v, targets.data(), new_index, nullptr, src, &adopted_rows);
+        if (st != AH_OK) {
+            (void)ah_index_destroy(ix);
+            return st;
+        }
+        if (src) forest_device_consume(forest, false, adopted_rows);
+        *out = ix;
+    }
+    if (src && out_from_device) *out_from_device = 1;
+    return AH_OK;
     AH_GUARDED_END
 }
 

@@ -3693,9 +3693,19 @@ int ah_index_create_from_view(ah_dataset *ds, const ah_forest_view *view, ah_ind
     AH_REQUIRE(out, AH_ERR_INVALID_ARGUMENT, "out is NULL");
     *out = nullptr;
     AH_REQUIRE(ds && view, AH_ERR_INVALID_ARGUMENT, "NULL argument");
+    return index_create_impl(ds, *view, nullptr, out);
+    AH_GUARDED_END
+}
+
+}  // extern "C"
+
+namespace ah {
+// The index of a view.  `src` (ah_index_create_from_forest): the view is the one of the library-built forest whose device copy
+// `src` is — its nodes are not walked again, neither blob is uploaded and no record is unpacked: on success the index has
+// ADOPTED the blocks of `src` as its ids, rows and headers (the caller tells the forest), on failure they are untouched.
+int index_create_impl(ah_dataset *ds, const ah_forest_view &v, const ForestDevice *src, ah_index **out) {
     AH_REQUIRE(ds->finalized, AH_ERR_NOT_FINALIZED, "dataset not finalized");
-    const ah_forest_view v = *view;
-    AH_TRY(validate_forest_view(ds, v));
+    if (!src) AH_TRY(validate_forest_view(ds, v));
     AH_HIP(hipSetDevice(ds->device));
     ah_index *ix = new (std::nothrow) ah_index();
     AH_REQUIRE(ix, AH_ERR_OUT_OF_MEMORY, "host allocation failed");
@@ -3722,6 +3732,8 @@ int ah_index_create_from_view(ah_dataset *ds, const ah_forest_view *view, ah_ind
     }
     ix->n_normals = (uint32_t)offsets.size();
     ix->normals_cap = std::max<uint32_t>(1, ix->n_normals);
+    AH_REQUIRE(!src || (src->n_rows == ix->n_normals && src->ids_len == v.descendants_len), AH_ERR_DEVICE,
+               "the forest's device copy does not match its view (internal error)");
     const uint32_t hf = header_floats(ds->metric);
     const size_t row_bytes = ds->row_bytes();
     int st = AH_OK;
@@ -3736,14 +3748,16 @@ int ah_index_create_from_view(ah_dataset *ds, const ah_forest_view *view, ah_ind
     } while (0)
     AH_IX(dev_malloc((void **)&ix->d_nodes, std::max<size_t>(1, nodes.size()) * sizeof(DNode)));
     AH_IX(dev_malloc((void **)&ix->d_roots, std::max<size_t>(1, v.n_trees) * 4));
-    AH_IX(dev_malloc((void **)&ix->d_desc, std::max<uint64_t>(1, v.descendants_len) * 4));
-    AH_IX(dev_malloc(&ix->d_nrows, std::max<size_t>(1, ix->n_normals) * row_bytes));
-    AH_IX(dev_malloc((void **)&ix->d_nhdrs, std::max<size_t>(1, ix->n_normals) * hf * 4));
+    if (!src) {
+        AH_IX(dev_malloc((void **)&ix->d_desc, std::max<uint64_t>(1, v.descendants_len) * 4));
+        AH_IX(dev_malloc(&ix->d_nrows, std::max<size_t>(1, ix->n_normals) * row_bytes));
+        AH_IX(dev_malloc((void **)&ix->d_nhdrs, std::max<size_t>(1, ix->n_normals) * hf * 4));
+    }
     if (!nodes.empty()) AH_IX(hipMemcpy(ix->d_nodes, nodes.data(), nodes.size() * sizeof(DNode), hipMemcpyHostToDevice));
     if (v.n_trees) AH_IX(hipMemcpy(ix->d_roots, v.roots, v.n_trees * 4, hipMemcpyHostToDevice));
-    if (v.descendants_len)
+    if (v.descendants_len && !src)
         AH_IX(hipMemcpy(ix->d_desc, v.descendants, v.descendants_len * 4, hipMemcpyHostToDevice));
-    if (ix->n_normals) {
+    if (ix->n_normals && !src) {
         DevMem recs, offs;
         AH_IX(dev_malloc(&recs.p, v.normals_len));
         AH_IX(dev_malloc(&offs.p, offsets.size() * 8));
@@ -3756,6 +3770,11 @@ int ah_index_create_from_view(ah_dataset *ds, const ah_forest_view *view, ah_ind
 #undef AH_IX
     (void)st;
     index_prepare_screens(ds);
+    if (src) {  // (nothing fails from here on: the blocks change hands)
+        ix->d_desc = src->ids;
+        ix->d_nrows = src->rows;
+        ix->d_nhdrs = src->hdrs;
+    }
     ix->nv.metric = ds->metric;
     ix->nv.dims = ds->dims;
     ix->nv.pitch = ds->pitch;
@@ -3770,8 +3789,10 @@ int ah_index_create_from_view(ah_dataset *ds, const ah_forest_view *view, ah_ind
     guard.p = nullptr;
     *out = ix;
     return AH_OK;
-    AH_GUARDED_END
 }
+}  // namespace ah
+
+extern "C" {
 
 // A mixed sub-batch of ah_search_batch_filters: the filters of the call on the device, the slot of every query of the
 // sub-batch (host), the smallest stored share among its filters and how many of its queries have one.

@@ -275,7 +275,10 @@ class Dataset:
         _lib.check(_lib.lib().ah_dataset_upload_records(self._h, _ptr(ids), ptrs, int(record_len), ids.size))
 
     def build_forest(self, tree_seeds: Sequence[int], split_after: int = 0, cancel=None, progress=None,
-                     max_trees_in_flight: int = 0, margin_mode: int = 0, max_host_threads: int = 0) -> "Forest":
+                     max_trees_in_flight: int = 0, margin_mode: int = 0, max_host_threads: int = 0,
+                     resident: bool = False) -> "Forest":
+        """ah_build_forest; resident=True: ah_build_forest_resident — the same forest, which also keeps the arrays an index
+        holds of it on the device (Forest.resident) for Index.from_forest / Index.graft_forest."""
         seeds = np.ascontiguousarray(tree_seeds, dtype=np.uint64)
         opt = _lib.AhBuildOptions()
         opt.n_trees = seeds.size
@@ -309,7 +312,8 @@ class Dataset:
         opt.max_host_threads = int(max_host_threads)
         h = C.c_void_p()
         try:
-            _lib.check(_lib.lib().ah_build_forest(self._h, C.byref(opt), C.byref(h)))
+            build = _lib.lib().ah_build_forest_resident if resident else _lib.lib().ah_build_forest
+            _lib.check(build(self._h, C.byref(opt), C.byref(h)))
         finally:
             if watcher_stop is not None:
                 watcher_stop.set()
@@ -378,8 +382,10 @@ class Dataset:
         assert bool(np.all(out[int(ends[n]):] == 0xA5)), "ah_encode_descendants wrote past the end of its values"
         return [out[int(ends[i]): int(ends[i + 1])].tobytes() for i in range(n)]
 
-    def build_subtrees(self, id_lists: Sequence[Sequence[int]], tree_seeds: Sequence[int], split_after: int = 0) -> "Forest":
-        """`incremental_index_large_descendant` for many item subsets at once (ah_build_subtrees)."""
+    def build_subtrees(self, id_lists: Sequence[Sequence[int]], tree_seeds: Sequence[int], split_after: int = 0,
+                       resident: bool = False) -> "Forest":
+        """`incremental_index_large_descendant` for many item subsets at once (ah_build_subtrees; resident=True:
+        ah_build_subtrees_resident, see build_forest)."""
         seeds = np.ascontiguousarray(tree_seeds, dtype=np.uint64)
         assert seeds.size == len(id_lists)
         offsets = np.zeros(len(id_lists) + 1, dtype=np.uint64)
@@ -390,7 +396,8 @@ class Dataset:
         opt.split_after = int(split_after)
         opt.tree_seeds = seeds.ctypes.data_as(C.POINTER(C.c_uint64))
         h = C.c_void_p()
-        _lib.check(_lib.lib().ah_build_subtrees(self._h, C.byref(opt), _ptr(ids), _ptr(offsets), C.byref(h)))
+        build = _lib.lib().ah_build_subtrees_resident if resident else _lib.lib().ah_build_subtrees
+        _lib.check(build(self._h, C.byref(opt), _ptr(ids), _ptr(offsets), C.byref(h)))
         return Forest(h, self.distance, self.dimensions)
 
     def create_index(self, forest: "Forest") -> "Index":
@@ -592,6 +599,38 @@ class Index:
                                                             C.byref(self._h)))
         else:
             _lib.check(_lib.lib().ah_index_create(dataset._h, forest._h, C.byref(self._h)))
+
+    @classmethod
+    def from_forest(cls, dataset: Dataset, forest: "Forest", new_index=None) -> "Index":
+        """ah_index_create_from_forest: the index of `forest`, made from the forest's device copy where it has one (a resident
+        forest on this dataset's device; the copy is consumed) and from its host view otherwise — the same index either way.
+        new_index[k]: the final index of view node k (a permutation of the forest's nodes: the numbering of the host's store);
+        None: the forest's own numbering, the index of Index(dataset, forest).  `from_device` on the result tells which path ran."""
+        ni = None if new_index is None else _u32(new_index).ravel()
+        if ni is not None and ni.size != len(forest.nodes):
+            raise ValueError(f"new_index has {ni.size} entries for the {len(forest.nodes)} nodes of the forest")
+        self = cls.__new__(cls)
+        self.dataset = dataset
+        self._h = C.c_void_p()
+        self._filters = weakref.WeakSet()
+        from_device = C.c_int(0)
+        _lib.check(_lib.lib().ah_index_create_from_forest(dataset._h, forest._h, _ptr(ni), C.byref(from_device), C.byref(self._h)))
+        self.from_device = bool(from_device.value)
+        return self
+
+    def graft_forest(self, forest: "Forest", targets, new_index=None, want_map: bool = False):
+        """ah_index_graft_forest: graft() with the view of `forest`, read from the forest's device copy where it has one (consumed)
+        and from its host view otherwise.  Returns from_device, with want_map (from_device, the new index of every old slot)."""
+        tg = _u32(targets).ravel()
+        if tg.size != forest.n_trees:
+            raise ValueError(f"{tg.size} targets for the {forest.n_trees} trees of the forest")
+        ni = None if new_index is None else _u32(new_index).ravel()
+        if ni is not None and ni.size != len(forest.nodes):
+            raise ValueError(f"new_index has {ni.size} entries for the {len(forest.nodes)} nodes of the forest")
+        out = np.zeros(self.export_info()["n_nodes"], dtype=np.uint32) if want_map else None
+        from_device = C.c_int(0)
+        _lib.check(_lib.lib().ah_index_graft_forest(self._h, forest._h, _ptr(tg), _ptr(ni), _ptr(out), C.byref(from_device)))
+        return (bool(from_device.value), out) if want_map else bool(from_device.value)
 
     @classmethod
     def from_encoded(cls, dataset: Dataset, node_ids, values, roots, want_stats: bool = False, layout="v0.7"):
@@ -1291,6 +1330,24 @@ class Forest:
         v = _lib.AhForestView()
         _lib.check(_lib.lib().ah_forest_view_get(self._h, C.byref(v)))
         return v
+
+    @property
+    def resident(self) -> bool:
+        """The forest holds its device copy (ah_forest_resident_info): built with resident=True, and neither released nor
+        consumed by Index.from_forest / Index.graft_forest since."""
+        r = C.c_int(0)
+        _lib.check(_lib.lib().ah_forest_resident_info(self._h, C.byref(r), None))
+        return bool(r.value)
+
+    @property
+    def device_bytes(self) -> int:
+        b = C.c_uint64(0)
+        _lib.check(_lib.lib().ah_forest_resident_info(self._h, None, C.byref(b)))
+        return int(b.value)
+
+    def release_device(self) -> None:
+        """ah_forest_release_device: give the device copy back; the forest stays, as an ordinary one."""
+        _lib.check(_lib.lib().ah_forest_release_device(self._h))
 
     def digest(self):
         """(total, per-tree array) 64-bit content digests (ah_forest_digest): equal for equal forests whatever the

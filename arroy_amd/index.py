@@ -407,6 +407,11 @@ class ArroyBuilder:
         # (test_writer_keeps_the_index_and_builds_the_same_trees) pins the fall-back counts of a tree-dropping build, so the
         # default can only flip in a change that may touch that test
         self.device_drop = False
+        # True: the forests of this build stay on the device (Dataset.build_forest / build_subtrees with resident=True) and the
+        # index is made or extended from them there (Index.from_forest, Index.graft_forest) — the first full build makes its
+        # index in the store's numbering, slices after the first and the sub-trees of an incremental build are grafted — so no
+        # index is uploaded from a whole view (index_uploads stays).  OFF by default, like device_drop
+        self.device_forest = False
         # True: a build that keeps its resident index suspends the index's live filters (Filter.suspend) instead of closing
         # them, and leaves them suspended for the caller to resume with its delta (Index.resume_filters); the compaction at
         # the end of the build is then no longer skipped on their account
@@ -539,7 +544,11 @@ class ArroyBuilder:
             elif st.trees is None or not st.trees.roots or st.metadata is None:
                 st.trees = TreeStore()
                 n_trees = target_n_trees(self._n_trees, w.dimensions, n, 0)
-                self._add_trees(ds, st.trees, n_trees, split_after)
+                made = self._add_trees_on_device(ds, st.trees, n_trees, split_after) if self.device_forest and self._group is None else None
+                if made is not None:
+                    st.index, st._keep = made
+                elif not st.trees.roots:
+                    self._add_trees(ds, st.trees, n_trees, split_after)
             else:
                 kept = self._incremental(ds, st, ids, split_after, resident)
                 if kept is not None:  # the resident index has followed the store: it serves the searches from here on
@@ -589,7 +598,7 @@ class ArroyBuilder:
     def _seeds(self, count: int) -> List[int]:
         return [self._rng.getrandbits(64) for _ in range(count)]  # one RNG per task (src/writer.rs:575,795)
 
-    def _add_trees(self, ds: Dataset, trees: TreeStore, count: int, split_after: int, grafted=None) -> None:
+    def _add_trees(self, ds: Dataset, trees: TreeStore, count: int, split_after: int, grafted=None, resident: bool = False) -> None:
         """`grafted(forest, maps)`: called after the trees of every forest are in the store, with the forest node -> store id
         map of each of its trees (the one-device path only)."""
         if count <= 0:
@@ -603,7 +612,7 @@ class ArroyBuilder:
             return
         for lo in range(0, count, 4096):
             forest = ds.build_forest(seeds[lo:lo + 4096], split_after=split_after, cancel=self._cancel,
-                                     progress=self._progress)
+                                     progress=self._progress, resident=resident)
             maps = []
             try:
                 for t in range(forest.n_trees):
@@ -615,6 +624,41 @@ class ArroyBuilder:
                     grafted(forest, maps)
             finally:
                 forest.close()
+
+    def _add_trees_on_device(self, ds: Dataset, trees: TreeStore, count: int, split_after: int):
+        """_add_trees of a full build with device_forest: every slice is built resident; the first becomes the index in the
+        store's numbering (Index.from_forest), the others are grafted as new roots (Index.graft_forest).  -> (index, _keep), or
+        None when the library refused a step: the trees are in the store all the same and the caller makes the index from its view."""
+        from .dataset import Index
+        state = {"ix": None, "dense": None, "ok": True}
+
+        def grafted(forest, maps):
+            if not state["ok"]:
+                return
+            new_dense = {nid: i for i, nid in enumerate(sorted(trees.nodes))}
+            new_index = np.zeros(len(forest.nodes), dtype=np.uint32)
+            for ids_of in maps:
+                for k, nid in ids_of.items():
+                    new_index[k] = new_dense[nid]
+            try:
+                if state["ix"] is None:
+                    state["ix"] = Index.from_forest(ds, forest, new_index)
+                else:
+                    state["ix"].graft_forest(forest, np.full(len(maps), _lib.NEW_ROOT, dtype=np.uint32), new_index)
+                state["dense"] = new_dense
+            except _lib.ArroyHipError:
+                state["ok"] = False
+        try:
+            self._add_trees(ds, trees, count, split_after, grafted=grafted, resident=True)
+        except BaseException:
+            if state["ix"] is not None:
+                state["ix"].close()
+            raise
+        if not state["ok"] or state["ix"] is None:
+            if state["ix"] is not None:
+                state["ix"].close()
+            return None
+        return state["ix"], (None, None, None, None, {nid: state["dense"][nid] for nid in trees.nodes})
 
     def _add_trees_group(self, trees: TreeStore, seeds: List[int], split_after: int) -> None:
         """_add_trees on the device group: one streamed build over all members, imported tree by tree in tree order."""
@@ -743,7 +787,10 @@ class ArroyBuilder:
                     tg[t] = state["dense"][targets[t]]
                     new_index[int(forest.roots[t])] = 0xFFFFFFFF
             try:
-                resident.graft(forest.view_struct(), tg, new_index)
+                if self.device_forest:
+                    resident.graft_forest(forest, tg, new_index)
+                else:
+                    resident.graft(forest.view_struct(), tg, new_index)
                 state["dense"] = new_dense
                 if self.encoded_store is not None:
                     for ids_of in maps:
@@ -754,7 +801,8 @@ class ArroyBuilder:
         # re-split (incremental_index_large_descendant, :660-739); untouched ones are left alone, whatever their size
         large = [nid for nid in sorted(grown) if len(trees.nodes[nid][1]) > split_after]
         if large:
-            forest = ds.build_subtrees([trees.nodes[nid][1] for nid in large], self._seeds(len(large)), split_after)
+            forest = ds.build_subtrees([trees.nodes[nid][1] for nid in large], self._seeds(len(large)), split_after,
+                                       resident=self.device_forest and state["ok"])
             maps = []
             for t, nid in enumerate(large):
                 trees.import_tree(forest, t, root_id=nid)  # the sub-tree's root keeps the descendant's id (:693-702)
@@ -765,7 +813,8 @@ class ArroyBuilder:
         missing = want - len(trees.roots)
         if missing > 0 and self._group is not None:
             state["ok"] = False  # (a group build streams its trees: the index is made from the view afterwards)
-        self._add_trees(ds, trees, missing, split_after, grafted=(lambda f, m: graft(f, m, None)) if state["ok"] else None)
+        self._add_trees(ds, trees, missing, split_after, grafted=(lambda f, m: graft(f, m, None)) if state["ok"] else None,
+                        resident=self.device_forest and state["ok"])
         if state["ok"]:
             live = state["dense"]
             kept = {nid: live[nid] for nid in trees.nodes}

@@ -1104,6 +1104,53 @@ typedef struct ah_index_compact_stats {
 AH_API int ah_index_compact(ah_index *index, uint32_t *out_new_of_old, ah_index_compact_stats *out_stats);
 
 /* ------------------------------------------------------------------------------------------
+ * Resident forests (ABI v7 additions: look the symbols up).  A build ends with every normal and every item id in HBM;
+ * ah_index_create and ah_index_graft then upload both blobs of the forest's view again.  A RESIDENT forest keeps, next to
+ * its usual host content, a device copy of what an index holds of it — the normal rows at the dataset's row pitch, their
+ * headers and the descendants ids, exactly the arrays ah_index_create_from_view makes of the forest's own view (row r is the
+ * r-th split node with a normal in view order, the ids lie at the view's offsets) — and two calls make an index from it, or
+ * graft it into one, without uploading either.
+ *
+ * ah_build_forest_resident / ah_build_subtrees_resident — the arguments, the checks, the errors and the forest of
+ * ah_build_forest / ah_build_subtrees: ah_forest_view_get, ah_forest_digest, ah_forest_stats and ah_forest_visit give the same
+ * content bit for bit (seconds_device also counts the extra stage).  At the end of every batch one more stage reads the
+ * levels' records where they lie and writes rows and headers in view order, and copies the batch's ids device to device.
+ * Failing to obtain the device copy is NOT an error: the call returns AH_OK with an ordinary forest (the rule of the
+ * screen's copies).  The plain entry points enqueue what they always did.  The streaming builds have no resident form.
+ * ah_forest_resident_info — *out_resident = 1 while the forest holds its device copy, *out_device_bytes what it asked the
+ * device for (0 otherwise); either may be NULL.  ah_forest_release_device frees the copy and leaves an ordinary forest (legal
+ * on any forest); ah_forest_destroy frees it too.
+ *
+ * ah_index_create_from_forest — new_index == NULL: the index of ah_index_create(ds, forest); ah_index_export gives the same
+ * bytes.  new_index given: a permutation of [0, n_nodes), new_index[k] the final index of view node k — the numbering of the
+ * host's store (roots first, `ConcurrentNodeIds`), in the convention of ah_index_graft: the result is what
+ * ah_index_create_from_view makes of that renumbered store in nodes, roots and every node's ids, every split node resolves to
+ * the same row bytes and header; row numbers and blob offsets may differ as after a graft, and after ah_index_compact the
+ * export is byte-identical.  (It IS a graft of every tree as AH_NEW_ROOT onto an index of nothing; new_index is checked as
+ * there.)
+ * ah_index_graft_forest — ah_index_graft with the forest's view: the same arguments are checked before anything is touched,
+ * all or nothing, refused with live filters or on a suspended index.
+ *
+ * Both calls read rows, headers and ids from the forest's device arrays (device-to-device row copies and the graft's list
+ * gather); only the node records, the roots and the index tables come from the host, the nodes of a library-built forest are
+ * not walked again, and no second copy of the normals exists at any time.  A successful call CONSUMES the device copy — the
+ * forest is an ordinary forest afterwards; where no renumbering moves them the index adopts the blocks as its own —
+ * and sets *out_from_device = 1 (may be NULL).  When the forest is not resident (never was, released, consumed), lives on
+ * another device than the dataset, or was built for another metric or dimension count, the call silently takes the host
+ * view — ah_index_create / ah_index_graft, the same result — and sets *out_from_device = 0.  A failed call leaves the forest
+ * resident.  The forest may be destroyed as soon as the call returns.
+ * ---------------------------------------------------------------------------------------- */
+AH_API int ah_build_forest_resident(ah_dataset *ds, const ah_build_options *options, ah_forest **out);
+AH_API int ah_build_subtrees_resident(ah_dataset *ds, const ah_build_options *options, const uint32_t *item_ids,
+                                      const uint64_t *offsets, ah_forest **out);
+AH_API int ah_forest_resident_info(const ah_forest *forest, int *out_resident, uint64_t *out_device_bytes);
+AH_API int ah_forest_release_device(ah_forest *forest);
+AH_API int ah_index_create_from_forest(ah_dataset *ds, ah_forest *forest, const uint32_t *new_index, int *out_from_device,
+                                       ah_index **out);
+AH_API int ah_index_graft_forest(ah_index *index, ah_forest *forest, const uint32_t *targets, const uint32_t *new_index,
+                                 uint32_t *out_new_of_old, int *out_from_device);
+
+/* ------------------------------------------------------------------------------------------
  * Audit of a resident index (ABI v7 additions: look the symbols up): `Reader::assert_validity` (src/reader.rs:509-589) and
  * `Reader::stats` (src/reader.rs:210-252) where the forest lives.  After its first upload the host never sees an index
  * again — deletes, inserts, grafts and compactions rewrite it in HBM, suspend / resume carry it across an update of the
