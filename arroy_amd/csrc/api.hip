@@ -1980,8 +1980,8 @@ int ah_margins(ah_dataset *normals, const void *leaf_vector, const void *leaf_he
     AH_GUARDED("ah_margins")
     ah_dataset *ds = normals;
     AH_NEED_FINALIZED(ds);
+    if (!item_ids) n = ds->n;  // (before the check of out_margins: NULL ids with n == 0 still mean every normal)
     AH_REQUIRE(leaf_vector && leaf_header && (out_margins || n == 0), AH_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (!item_ids) n = ds->n;
     if (n == 0) return AH_OK;
     AH_LEASE(ds, ctx);
     const size_t vs = ah_vector_size(ds->metric, ds->dims), hs = ah_header_size(ds->metric);

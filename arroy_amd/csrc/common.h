@@ -73,6 +73,7 @@ inline int guarded(const char *what, F &&f) noexcept {
     do {                                                                                           \
         hipError_t _e = (expr);                                                                    \
         if (_e != hipSuccess) {                                                                    \
+            (void)hipGetLastError(); /* reported here: the next call's launch check must not find it */ \
             ::ah::set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
             ::ah::set_error_status((_e == hipErrorOutOfMemory) ? AH_ERR_OUT_OF_MEMORY : AH_ERR_DEVICE); \
             return (_e == hipErrorOutOfMemory) ? AH_ERR_OUT_OF_MEMORY : AH_ERR_DEVICE;             \

@@ -1115,7 +1115,7 @@ int launch_quantize_rows(const float *d_src, uint32_t src_pitch, uint32_t dims, 
 
 // Synthetic rows (include/arroy_hip_policy.h): one thread per float4 of the padded row.  The two structured distributions
 // compute the row's part (its cluster / its 32 factors) once per thread instead of once per component; the values are those
-// of ah_synth_value (tests/test_gpu_synth.py compares every component with the host's).
+// of ah_synth_value (tests/test_gpu_structured.py compares every component with the host's).
 __global__ void k_synth_fill(float *__restrict__ rows, uint32_t pitch, uint32_t dims, uint64_t first_item, uint64_t n,
                              uint64_t seed, int distribution) {
     const uint64_t per_row = pitch >> 2;

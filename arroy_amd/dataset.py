@@ -258,6 +258,21 @@ class Dataset:
         sides = np.unpackbits(bits, bitorder="little")[:n]
         return sides, int(nl.value), margins
 
+    def margins(self, leaf_vector: np.ndarray, leaf_header, item_ids=None) -> np.ndarray:
+        """ah_margins: `D::margin(&normal, query_leaf)` (src/reader.rs:366-369) where the ITEMS of this dataset are split-plane
+        normals (header = the normal's header).  The leaf is in the metric's codec: by_vector codec + `D::new_header`, by_item
+        the stored item.  item_ids None: every normal in row order."""
+        ids_a = None if item_ids is None else _u32(item_ids)
+        n = len(self) if ids_a is None else ids_a.size
+        lv = np.ascontiguousarray(leaf_vector).view(np.uint8)
+        assert lv.size == self.distance.vector_size(self.dimensions)
+        lh = np.zeros(2, dtype=np.float32)
+        h = _f32(leaf_header).ravel()
+        lh[: h.size] = h
+        out = np.zeros(n, dtype=np.float32)
+        _lib.check(_lib.lib().ah_margins(self._h, _ptr(lv), _ptr(lh), _ptr(ids_a), n, _ptr(out)))
+        return out
+
     def create_split(self, sample_ids: Sequence[int]):
         """`D::create_split` with host-supplied samples (choose_two + 10 x choose)."""
         s = _u32(sample_ids)

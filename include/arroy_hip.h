@@ -431,7 +431,15 @@ AH_API int ah_forest_view_get(const ah_forest *forest, ah_forest_view *out);
  * per tree, in the node order of ah_forest_view (post-order), kind / has_normal / children / count / depth of every
  * node, header + vector bytes of every split plane, item ids of every Descendants node.  Two builds of the same
  * dataset with the same seeds must agree whatever the margin mode or tuning: bench.py and the GPU tests compare the
- * screened and the f32-only build of the 10M x 100-tree forest this way.  out_per_tree: n_trees values or NULL. */
+ * screened and the f32-only build of the 10M x 100-tree forest this way.  out_per_tree: n_trees values or NULL.
+ * The recipe (tests/test_gpu_forest_witnesses.py restates it in Python and checks that every field below moves the value),
+ * with mix = ah_mix64 of arroy_hip_policy.h and H(bytes, seed) = the four-lane byte hash `hash_bytes` of forest.hip:
+ *   tree t, whose first node in the view is node b:  h = mix(0x61727279 + t); then for every node i of the tree, ascending,
+ *     h = mix(h ^ H(four u64 {kind | has_normal << 8 | depth << 32, count, left - b, right - b}, i - b))   (Descendants: 0, 0)
+ *     a split with a normal:  h = mix(h ^ H(record[normal_vector_offset, normal_header_offset), 1)), the vector and its zero
+ *                             padding, then h = mix(h ^ H(record[normal_header_offset, + 8), 2)), D::Header zero-padded
+ *     a Descendants node:     h = mix(h ^ H(its `count` u32 ids, 3))
+ *   per_tree[t] = h;  total = mix(n_trees), then total = mix(total ^ per_tree[t]) for t ascending. */
 AH_API int ah_forest_digest(const ah_forest *forest, uint64_t *out_per_tree, uint64_t *out_total);
 /* ABI v6: the per-tree digests with the caller's key in place of the tree's index inside THIS forest — e.g. the tree's
  * index in the whole index when the forest is one GPU's share of it (trees t = device mod G, src/writer.rs:556-591): the
