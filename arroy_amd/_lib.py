@@ -151,6 +151,10 @@ class AhRerankStats(C.Structure):
                 ("survivors", C.c_uint64), ("chunks_int8", C.c_uint64), ("chunks_int8_retried", C.c_uint64)]
 
 
+class AhRerankDiffStats(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("chunks_screened", "chunks_overflowed", "queries", "survivors", "switched_off")]
+
+
 class AhSearchStats(C.Structure):
     _fields_ = [(f, C.c_uint64) for f in (
         "calls", "chunks", "queries", "descent_wave_small", "descent_wave_big", "descent_octet_lds", "descent_octet_global",
@@ -266,6 +270,7 @@ SIGNATURES = {
     "ah_dataset_finalize": (C.c_int, [_VP]),
     "ah_dataset_reserve_build": (C.c_int, [_VP, C.c_uint32, C.c_uint32]),
     "ah_dataset_rerank_stats": (C.c_int, [_VP, C.POINTER(AhRerankStats), C.c_int]),
+    "ah_dataset_rerank_diff_stats": (C.c_int, [_VP, C.POINTER(AhRerankDiffStats), C.c_int]),
     "ah_dataset_packed_info": (C.c_int, [_VP, C.POINTER(C.c_int), C.POINTER(C.c_uint64)]),
     "ah_dataset_packed_rows": (C.c_int, [_VP, C.POINTER(C.c_int), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "ah_debug_query_screen_verify": (C.c_int, [_VP, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int]),

@@ -1646,6 +1646,7 @@ struct RerankJob {
     std::vector<RerankTile> tiles;
     uint32_t max_n = 0, max_rounds = 0;
     bool screened = false, screened8 = false;  // which stages of the certified screen apply
+    bool diff = false;                         // ... `screened` as the difference screen (Euclidean / Manhattan)
     RerankBufs dev{};
     RerankPinned<RerankSeg, RerankTile> pin{};
 };
@@ -1670,13 +1671,19 @@ static int rerank_plan(RerankJob &j, const float *queries, const uint64_t *offse
     // Certified top-k screen (search.hip: k_search_select_screened): Cosine / DotProduct lists long enough for the screen to
     // pay (the candidates on the binary16 copy of the rows — made by the first call that wants it — and only the few whose
     // proven distance interval reaches the top k in f32).  Submissions the row-major re-rank takes are left to it.
-    j.screened = tun(TUN_RERANK_SCREEN) != 0 && (ds->metric == AH_COSINE || ds->metric == AH_DOT_PRODUCT) && ds->dims >= 32 &&
+    // Euclidean / Manhattan lists under the same conditions, when AH_RERANK_SCREEN_DIFF asks for it: the difference screen
+    // (search.hip: k_pairs_screen_diff16) on the same copy, never an int8 stage (a difference of digits of two scales means nothing).
+    const bool diff = (ds->metric == AH_EUCLIDEAN || ds->metric == AH_MANHATTAN) && tun(TUN_RERANK_SCREEN_DIFF) != 0 &&
+                      !ds->rerank_diff_off.load(std::memory_order_relaxed);
+    j.screened = tun(TUN_RERANK_SCREEN) != 0 && (ds->metric == AH_COSINE || ds->metric == AH_DOT_PRODUCT || diff) && ds->dims >= 32 &&
                  inv_bytes == 0 && k <= 256 && j.total >= 8 * k * nq && !j.tiles.empty();
     if (j.screened) j.screened = ensure_screen(ds, j.ctx->stream, false);
+    j.diff = j.screened && diff;
     // ... and, round 6, on the int8 copy before that: half the bytes again per candidate, a wider band of survivors
-    j.screened8 = j.screened && tun(TUN_RERANK_SCREEN8) != 0 && !ds->rerank8_off.load(std::memory_order_relaxed) &&
+    j.screened8 = j.screened && !diff && tun(TUN_RERANK_SCREEN8) != 0 && !ds->rerank8_off.load(std::memory_order_relaxed) &&
                   ensure_screen8_search(ds, j.ctx->stream);
-    const RerankSizes z{nq, ds->dims, ds->row_bytes(), k, j.total, j.tiles.size(), kstride, inv_bytes, ds->hpitch, ds->pitch8, j.screened, j.screened8};
+    const RerankSizes z{nq, ds->dims, ds->row_bytes(), k, j.total, j.tiles.size(), kstride, inv_bytes, ds->hpitch, ds->pitch8, j.screened, j.screened8,
+                        j.diff};
     Carver dev_bytes(nullptr), pin_bytes(nullptr);  // (counting)
     rerank_device_layout(dev_bytes, z, j.dev);
     rerank_pinned_layout(pin_bytes, z, j.pin);
@@ -1769,6 +1776,17 @@ static int rerank_finish(RerankJob &j, RerankProbe &probe, uint32_t *out_ids, fl
             AH_HIP(hipMemsetAsync(b.d_err, 0, 64, s));
             AH_TRY(launch_rerank_screened(ds, b, 0u, b.n_tiles, (uint32_t)j.k, true, true, false, s));
             AH_TRY(read_back(false));
+        }
+        // The difference screen has no second stage: too many survivors (candidates closer together than delta) is the exact
+        // path below, and the same window rule — 8 such sub-batches within 64 it served — switches it off for the dataset.
+        const bool overflowed = j.diff && (*h_err & 8u) != 0;
+        if (j.diff && screen8_window_note(ds->rerank_diff_seen, ds->rerank_diff_fails, overflowed))
+            ds->rerank_diff_off.store(true, std::memory_order_relaxed);
+        if (j.diff) {
+            std::lock_guard<std::mutex> lk(ds->mu);
+            ds->rr_diff_stats.chunks_screened += 1;
+            ds->rr_diff_stats.chunks_overflowed += overflowed ? 1 : 0;
+            if ((*h_err & ~1u) == 0) ds->rr_diff_stats.queries += h_err[9], ds->rr_diff_stats.survivors += h_err[10];
         }
         if ((*h_err & ~1u) == 0) {  // ah_rerank_stats: how the screen went (always kept: three additions)
             std::lock_guard<std::mutex> lk(ds->mu);
@@ -1870,6 +1888,19 @@ int ah_dataset_rerank_stats(ah_dataset *ds, ah_rerank_stats *out, int reset) {
     std::lock_guard<std::mutex> lk(ds->mu);
     if (out) *out = ds->rr_stats;
     if (reset) ds->rr_stats = ah_rerank_stats{};
+    return AH_OK;
+    AH_GUARDED_END
+}
+
+int ah_dataset_rerank_diff_stats(ah_dataset *ds, ah_rerank_diff_stats *out, int reset) {
+    AH_GUARDED("ah_dataset_rerank_diff_stats")
+    AH_REQUIRE(ds, AH_ERR_INVALID_ARGUMENT, "dataset is NULL");
+    std::lock_guard<std::mutex> lk(ds->mu);
+    if (out) {
+        *out = ds->rr_diff_stats;
+        out->switched_off = ds->rerank_diff_off.load(std::memory_order_relaxed) ? 1 : 0;
+    }
+    if (reset) ds->rr_diff_stats = ah_rerank_diff_stats{};
     return AH_OK;
     AH_GUARDED_END
 }

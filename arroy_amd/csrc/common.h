@@ -179,6 +179,7 @@ inline int guarded(const char *what, F &&f) noexcept {
     X(SEARCH_SCREEN8_MIN_QUERIES, "AH_SEARCH_SCREEN8_MIN_QUERIES", 65) /* ... from this many queries a call (never the in-flight tiles of <= AH_SEARCH_SMALL_TILES_MAX_QUERIES queries; 9 .. 64 measured: no gain) */ \
     X(SEARCH_SCREEN8, "AH_SEARCH_SCREEN8", 1)   /* 0: the tile re-rank of ah_search_batch likewise */ \
     X(RERANK_SCREEN, "AH_RERANK_SCREEN", 1)     /* 0: ah_rerank_batch never screens its candidates (f32 rows for all) */ \
+    X(RERANK_SCREEN_DIFF, "AH_RERANK_SCREEN_DIFF", 0) /* 1: ah_rerank_batch screens Euclidean / Manhattan lists on the binary16 rows too, by the difference of the copies (DESIGN.md 2.5 "The difference screen"); 0 (default): those lists take the f32 gather, no call and no statistic changes; AH_RERANK_SCREEN=0 wins */ \
     X(REPLICATE_HOST_BOUNCE, "AH_REPLICATE_HOST_BOUNCE", 0) /* 1: ah_dataset_replicate copies through pinned host memory even where peer access works (test aid) */ \
     X(RERANK_TIMING, "AH_RERANK_TIMING", 0)     /* 1: ah_rerank_batch accounts its wall time by phase (ah_dataset_rerank_stats) */ \
     X(SEARCH_SCREEN, "AH_SEARCH_SCREEN", 1)     /* 0: the re-rank of ah_search_batch never screens its candidates (f32 rows for all) */ \
@@ -438,6 +439,9 @@ struct ah_dataset {
     std::atomic<uint32_t> rerank8_fails{0};      // ah_rerank_batch sub-batches whose int8 stage left too many survivors ...
     std::atomic<uint32_t> rerank8_seen{0};       // ... among this many it served (screen8_window_note: windows of 64)
     std::atomic<bool> rerank8_off{false};        // ... often enough that the dataset's re-rank starts on the binary16 rows from now on
+    // the difference screen of Euclidean / Manhattan lists (AH_RERANK_SCREEN_DIFF) switches itself off by the same window rule
+    std::atomic<uint32_t> rerank_diff_fails{0}, rerank_diff_seen{0};
+    std::atomic<bool> rerank_diff_off{false};
     std::atomic<bool> screen8_ready{false};      // ... and d_rows_i8 / d_scale8_rows / d_dim_scale / pitch8 / screen8_max likewise
     // staging in flight (ah_dataset_upload_*): the context whose stream / pinned ring the uploads use until
     // ah_dataset_finalize (or ah_dataset_upload_flush) waits for them
@@ -462,6 +466,7 @@ struct ah_dataset {
     // AH_SCREEN_VERIFY=1: {candidates checked, candidates whose reference distance fell outside [L, U]} of the search and
     // re-rank screens (k_screen_verify, search.hip), allocated by the first verified submission (ah_debug_query_screen_verify)
     unsigned long long *d_query_verify = nullptr;
+    ah_rerank_diff_stats rr_diff_stats{};        // what the difference screen served (under `mu`; switched_off: rerank_diff_off)
     ah_rerank_stats rr_stats{};                  // AH_RERANK_TIMING=1: where ah_rerank_batch's wall time went (under `mu`)
     double reserve_seconds = 0.0;                // ... how long that helper ran (written by it, read after the join)
     double reserve_wait_seconds = 0.0;           // ... and how long the first build then waited for it (ah_build_stats, ABI v7)

@@ -36,6 +36,7 @@ struct RerankSizes {  // what the layouts depend on
     size_t kstride, inv_bytes;   // tournament keys per query; counters of the row-major re-rank (0: not taken)
     size_t hpitch, pitch8;       // halves of a binary16 row, bytes of an int8 row
     bool screened, screened8;    // the certified screen on the binary16 rows / on the int8 rows before that
+    bool diff = false;           // ... as the difference screen (Euclidean / Manhattan): nothing lies next to a screen value
 };
 
 // Bufs: RerankBufs (common.h), or anything with members of those names.  The screen's scratch lies behind everything else.
@@ -56,7 +57,7 @@ void rerank_device_layout(Carver &c, const RerankSizes &z, Bufs &b) {
     c.take(&b.d_inv_counters, z.inv_bytes / 4, z.inv_bytes != 0);
     c.take(&b.d_q16, z.nq * z.hpitch, z.screened);
     c.take(&b.d_qstats, z.nq, z.screened);
-    c.take(&b.d_aux, z.total, z.screened);
+    c.take(&b.d_aux, z.total, z.screened && !z.diff);
     c.take(&b.d_q8, z.nq * z.pitch8 * 2, z.screened8);
     c.take(&b.d_q8stats, z.nq, z.screened8);
     c.take(&b.d_aux8, z.total, z.screened8);

@@ -422,7 +422,11 @@ void commit(MemberUpdate *mu, const Plan &p) {
     ds->rerank8_fails.store(0, std::memory_order_relaxed);
     ds->rerank8_seen.store(0, std::memory_order_relaxed);
     ds->rerank8_off.store(false, std::memory_order_relaxed);
+    ds->rerank_diff_fails.store(0, std::memory_order_relaxed);
+    ds->rerank_diff_seen.store(0, std::memory_order_relaxed);
+    ds->rerank_diff_off.store(false, std::memory_order_relaxed);
     ds->rr_stats = ah_rerank_stats{};
+    ds->rr_diff_stats = ah_rerank_diff_stats{};
     // DotProduct: the headers of the upserted rows are {0, 0} (or whatever the records held) and the max norm may have
     // changed: preprocess again (src/writer.rs:964-976 does so inside every build)
     if (ds->metric == AH_DOT_PRODUCT) ds->dot_preprocessed = false;

@@ -221,6 +221,13 @@ class Dataset:
         _lib.check(_lib.lib().ah_dataset_rerank_stats(self._h, C.byref(st), 1 if reset else 0))
         return {f: getattr(st, f) for f, _ in _lib.AhRerankStats._fields_}
 
+    def rerank_diff_stats(self, reset: bool = False) -> dict:
+        """ah_dataset_rerank_diff_stats: what the difference screen of Euclidean / Manhattan lists served (tunable
+        AH_RERANK_SCREEN_DIFF=1): sub-batches screened and overflowed, queries, survivors, and whether it switched itself off."""
+        st = _lib.AhRerankDiffStats()
+        _lib.check(_lib.lib().ah_dataset_rerank_diff_stats(self._h, C.byref(st), 1 if reset else 0))
+        return {f: getattr(st, f) for f, _ in _lib.AhRerankDiffStats._fields_}
+
     def packed_info(self) -> dict:
         """ah_dataset_packed_info: whether the scan's packed copy of the rows exists, and how many of its rows stay f32."""
         present, raw = C.c_int(0), C.c_uint64(0)

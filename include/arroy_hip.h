@@ -55,7 +55,8 @@ extern "C" {
                                   ah_group_update_vectors / _records, the test aid ah_debug_update_paths);
                                   ah_index_footprint_get / ah_index_compact; ah_index_audit / ah_forest_view_audit;
                                   ah_index_drop_trees; ah_index_create_from_encoded; ah_index_encode_nodes;
-                                  ah_index_create_from_legacy */
+                                  ah_index_create_from_legacy;
+                                  ah_dataset_rerank_diff_stats (the difference screen of Euclidean / Manhattan lists) */
 
 /* every entry point is exported from the shared object (it is built with -fvisibility=hidden) */
 #if defined(__GNUC__)
@@ -247,6 +248,18 @@ typedef struct ah_rerank_stats {
                                      stage off for the dataset) */
 } ah_rerank_stats;
 AH_API int ah_dataset_rerank_stats(ah_dataset *ds, ah_rerank_stats *out, int reset);
+/* The difference screen of ah_rerank_batch (tunable AH_RERANK_SCREEN_DIFF=1, default 0: Euclidean / Manhattan lists take the
+ * f32 gather).  With it those lists are scored on the binary16 copy of the rows first, s = |q~ - x~|_p, and only the candidates
+ * whose proven interval of the reference distance reaches the top k are read in f32: the same ids and distance bits.  Its
+ * queries and survivors also count in ah_rerank_stats.queries_screened / survivors.  reset != 0 zeroes the counters after the
+ * copy (not switched_off: a dataset update clears that).  An addition to v7: a caller that needs it looks the symbol up. */
+typedef struct ah_rerank_diff_stats {
+    uint64_t chunks_screened;    /* sub-batches the stage took                                                              */
+    uint64_t chunks_overflowed;  /* ... that left some query more than 1024 survivors: answered by the exact path instead   */
+    uint64_t queries, survivors; /* queries answered through the stage, and their candidates evaluated in f32               */
+    uint64_t switched_off;       /* 1: eight overflows within one window of 64 sub-batches switched the stage off           */
+} ah_rerank_diff_stats;
+AH_API int ah_dataset_rerank_diff_stats(ah_dataset *ds, ah_rerank_diff_stats *out, int reset);
 /* The packed copy of the rows that the ungathered f32 scan reads (tunable AH_SCAN_PACKED): *out_present = 1 when it exists,
  * *out_raw_rows = its rows kept in f32 (an inf / NaN, or an exponent spread of 15 binades or more).  Either pointer may be
  * NULL.  Made by the first ah_distances_by_* / ah_bench_scan call over all rows, never by a build or a search. */

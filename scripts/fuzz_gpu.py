@@ -64,6 +64,11 @@ def one(rng, it):
     with _tuning(AH_RERANK_SCREEN=0):  # the certified top-k screen of the lists (default) and the f32-only path: the same bits
         xi, xd, xc = ds.rerank_batch(qs, [ids[l] for l in lists], kb)
     assert np.array_equal(bc, xc) and np.array_equal(bi, xi) and np.array_equal(bd.view(np.uint32), xd.view(np.uint32)), desc + " batch screen on/off"
+    with _tuning(AH_RERANK_SCREEN_DIFF=1, AH_SCREEN_VERIFY=1):  # the difference screen of Euclidean / Manhattan lists (off by default)
+        ds.query_screen_verify(reset=True)
+        yi, yd, yc = ds.rerank_batch(qs, [ids[l] for l in lists], kb)
+        assert ds.query_screen_verify()["violations"] == 0, desc + " difference screen: a candidate outside its interval"
+    assert np.array_equal(bc, yc) and np.array_equal(bi, yi) and np.array_equal(bd.view(np.uint32), yd.view(np.uint32)), desc + " batch difference screen on/off"
     for i in range(nq):
         v, h = oracle.query_leaf(qs[i])
         ei, ed = oracle.rerank(v, h, lists[i], kb) if len(lists[i]) else (np.zeros(0, np.uint32), np.zeros(0, np.float32))
