@@ -155,6 +155,10 @@ class AhRerankDiffStats(C.Structure):
     _fields_ = [(f, C.c_uint64) for f in ("chunks_screened", "chunks_overflowed", "queries", "survivors", "switched_off")]
 
 
+class AhSearchDiffStats(C.Structure):  # ah_search_diff_stats: the same fields, of an index's tile pass
+    _fields_ = AhRerankDiffStats._fields_
+
+
 class AhSearchStats(C.Structure):
     _fields_ = [(f, C.c_uint64) for f in (
         "calls", "chunks", "queries", "descent_wave_small", "descent_wave_big", "descent_octet_lds", "descent_octet_global",
@@ -323,6 +327,7 @@ SIGNATURES = {
     "ah_search_batch": (C.c_int, [_VP, _F32P, _U32P, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, _U32P, C.c_size_t,
                                   C.c_int, _U32P, _F32P, _U32P]),
     "ah_index_search_stats": (C.c_int, [_VP, C.POINTER(AhSearchStats), C.c_int]),
+    "ah_index_search_diff_stats": (C.c_int, [_VP, C.POINTER(AhSearchDiffStats), C.c_int]),
     "ah_route_items": (C.c_int, [_VP, _U32P, C.c_size_t, _U64P, _U32P]),
     # resident candidate filters, one per query in a batched call
     "ah_filter_create": (C.c_int, [_VP, _U32P, C.c_size_t, C.POINTER(C.c_void_p)]),

@@ -79,6 +79,11 @@ struct ah_index {
     std::atomic<uint32_t> search8_fails{0};  // sub-batches whose int8 stage left too many survivors ...
     std::atomic<uint32_t> search8_seen{0};   // ... among this many it served (screen8_window_note: windows of 64) ...
     std::atomic<bool> search8_off{false};    // ... eight in one window: the index's tile re-rank starts on the binary16 rows from now on
+    // the difference screen of the tiles (AH_SEARCH_SCREEN_DIFF) switches itself off by the same window rule: overflowed
+    // sub-batches among those it took; Euclidean then returns to the f32 tiles, Manhattan to the sorted path
+    std::atomic<uint32_t> search_diff_fails{0}, search_diff_seen{0};
+    std::atomic<bool> search_diff_off{false};
+    ah_search_diff_stats diff_stats{};       // what that screen served (under stats_mu; switched_off: search_diff_off)
     bool counted = false;                    // counted in ds->live_indexes (an update of the dataset refuses meanwhile)
     bool suspended = false;                  // ah_index_suspend: not counted, and every call that reads the dataset refuses
     ah_params_stats pstats{};                // under stats_mu: how ah_search_batch_params cut its calls

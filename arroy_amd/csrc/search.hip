@@ -62,6 +62,10 @@ template <class F>
 int with_screen_metric(int metric, F &&f) {
     return with_metric_of<AH_COSINE, AH_DOT_PRODUCT>(metric, f);
 }
+template <class F>
+int with_diff_metric(int metric, F &&f) {  // the difference screen of the tiles (AH_SEARCH_SCREEN_DIFF)
+    return with_metric_of<AH_EUCLIDEAN, AH_MANHATTAN>(metric, f);
+}
 // ... and those of the re-rank's lists: the two above, and Euclidean / Manhattan through the difference screen
 template <class F>
 int with_rerank_screen_metric(int metric, F &&f) {
@@ -2461,14 +2465,24 @@ __device__ __forceinline__ void leaf_tile16(const ScreenSearch &ss, const DataVi
         }
     }
 }
-template <bool SMALL>
-__global__ __launch_bounds__(256) void k_leaf_tiles16(DataView dv, ScreenSearch ss, const uint32_t *__restrict__ nns,
-                                                      const Visit *__restrict__ sorted, const TileUnit *__restrict__ units,
-                                                      const uint32_t *__restrict__ n_units_p, float *__restrict__ dist,
-                                                      uint32_t stride, uint32_t *err, uint32_t min_vis = 0,
-                                                      const uint32_t *__restrict__ blob = nullptr, uint32_t speculate = 0,
-                                                      uint32_t *__restrict__ trace = nullptr, uint32_t flat = 0,
-                                                      const uint32_t *__restrict__ items = nullptr, uint32_t per_query = 0) {
+// The dot-product tile as the walk below takes it: TILE::run<R, Q, QO, KF> is the screen values of one slab of one unit.
+struct DotTile16 {
+    template <int R, int Q, int QO, int KF = 1>
+    static __device__ __forceinline__ void run(const ScreenSearch &ss, const DataView &dv, const uint32_t *__restrict__ leaf_ids, uint32_t row_begin,
+                                               uint32_t n_rows, const Visit *__restrict__ vis, uint32_t n_vis, float *__restrict__ dist, uint32_t stride,
+                                               uint32_t *err, uint32_t *__restrict__ copy_ids_to = nullptr, const Visit *only_visit = nullptr) {
+        leaf_tile16<R, Q, QO, KF>(ss, dv, leaf_ids, row_begin, n_rows, vis, n_vis, dist, stride, err, copy_ids_to, only_visit);
+    }
+};
+// The unit and slab walk of the binary16 leaf tiles, whatever TILE computes per (row, query) pair: which block takes which
+// (unit, slab) in each launch form, min_vis, the ids a single query's descent left in the blob, the trace stamps.
+template <bool SMALL, class TILE>
+__device__ __forceinline__ void leaf_tiles16_walk(const DataView &dv, const ScreenSearch &ss, const uint32_t *__restrict__ nns,
+                                                  const Visit *__restrict__ sorted, const TileUnit *__restrict__ units,
+                                                  const uint32_t *__restrict__ n_units_p, float *__restrict__ dist, uint32_t stride,
+                                                  uint32_t *err, uint32_t min_vis, const uint32_t *__restrict__ blob, uint32_t speculate,
+                                                  uint32_t *__restrict__ trace, uint32_t flat, const uint32_t *__restrict__ items,
+                                                  uint32_t per_query) {
     const uint64_t t_start = trace ? wall_clock64() : 0ull;
     auto stamp = [&](uint32_t slot) {  // (AH_SEARCH_MULTI_TRACE: the latest block's time at each point, 10 ns ticks)
         if (trace && threadIdx.x == 0) atomicMax(&trace[slot], (uint32_t)(wall_clock64() - t_start));
@@ -2491,7 +2505,7 @@ __global__ __launch_bounds__(256) void k_leaf_tiles16(DataView dv, ScreenSearch 
                 const uint32_t row_begin = slab_index * kTileSmallSlab, row_end = min(v0.n, row_begin + kTileSmallSlab);
                 const uint32_t *leaf_ids = nns + (uint64_t)v0.q * stride + v0.pos;
                 const bool from_blob = blob && pad != 0u;
-                leaf_tile16<2, 1, 1, 24>(ss, dv, from_blob ? blob + (pad - 1u) : leaf_ids, row_begin, row_end, sorted + e, 1u, dist, stride, err,
+                TILE::template run<2, 1, 1, 24>(ss, dv, from_blob ? blob + (pad - 1u) : leaf_ids, row_begin, row_end, sorted + e, 1u, dist, stride, err,
                                          from_blob ? const_cast<uint32_t *>(leaf_ids) : nullptr, &v0);
             };
             if (n_units > 128u) {
@@ -2573,18 +2587,18 @@ __global__ __launch_bounds__(256) void k_leaf_tiles16(DataView dv, ScreenSearch 
         const uint32_t row_begin = slab_index * slab;
         const uint32_t row_end = min(n_leaf, row_begin + slab);
         const uint32_t *leaf_ids = nns + (uint64_t)v0.q * stride + v0.pos;
-#define AH_TILE16(R, Q, QO) leaf_tile16<R, Q, QO, AH_TILES16_KF>(ss, dv, leaf_ids, row_begin, row_end, vis, n_vis, dist, stride, err)
+#define AH_TILE16(R, Q, QO) TILE::template run<R, Q, QO, AH_TILES16_KF>(ss, dv, leaf_ids, row_begin, row_end, vis, n_vis, dist, stride, err)
         if constexpr (SMALL) {
             if (fly && n_vis == 1) {
                 // (unit.pad != 0: the ids are still in the blob, this launch copies them — SingleQueryOut::ids_by_tiles)
                 const bool from_blob = blob && unit.pad != 0u;
-                leaf_tile16<2, 1, 1, 24>(ss, dv, from_blob ? blob + (unit.pad - 1u) : leaf_ids, row_begin, row_end, vis, n_vis, dist, stride, err,
+                TILE::template run<2, 1, 1, 24>(ss, dv, from_blob ? blob + (unit.pad - 1u) : leaf_ids, row_begin, row_end, vis, n_vis, dist, stride, err,
                                          from_blob ? const_cast<uint32_t *>(leaf_ids) : nullptr, &v0);
                 stamp(1);
                 continue;
             }
             if (fly) {
-                leaf_tile16<2, 2, 1, 12>(ss, dv, leaf_ids, row_begin, row_end, vis, n_vis, dist, stride, err);
+                TILE::template run<2, 2, 1, 12>(ss, dv, leaf_ids, row_begin, row_end, vis, n_vis, dist, stride, err);
                 continue;
             }
         }
@@ -2596,6 +2610,17 @@ __global__ __launch_bounds__(256) void k_leaf_tiles16(DataView dv, ScreenSearch 
 #undef AH_TILE16
         }
     }
+}
+template <bool SMALL>
+__global__ __launch_bounds__(256) void k_leaf_tiles16(DataView dv, ScreenSearch ss, const uint32_t *__restrict__ nns,
+                                                      const Visit *__restrict__ sorted, const TileUnit *__restrict__ units,
+                                                      const uint32_t *__restrict__ n_units_p, float *__restrict__ dist,
+                                                      uint32_t stride, uint32_t *err, uint32_t min_vis = 0,
+                                                      const uint32_t *__restrict__ blob = nullptr, uint32_t speculate = 0,
+                                                      uint32_t *__restrict__ trace = nullptr, uint32_t flat = 0,
+                                                      const uint32_t *__restrict__ items = nullptr, uint32_t per_query = 0) {
+    leaf_tiles16_walk<SMALL, DotTile16>(dv, ss, nns, sorted, units, n_units_p, dist, stride, err, min_vis, blob, speculate, trace, flat, items,
+                                        per_query);
 }
 
 // The leaf tile on the INT8 copy of the rows (round 6): R rows x Q queries per octet, both int8 digits of every query against the
@@ -2863,6 +2888,144 @@ __global__ __launch_bounds__(256) AH_NO_PACKED_F32 void k_pairs_screen_diff16(Da
     }
 }
 
+// ---- the difference screen inside the search's tile pass (AH_SEARCH_SCREEN_DIFF) ---------------------------------------
+// The leaf tile of k_leaf_tiles16 with |q~ - x~|_p^p as its screen value: R rows x Q queries per octet, lane j the 8 halves at
+// 64 k + 8 j of every row and query, the arithmetic of k_pairs_screen_diff16 (widen, subtract in f32, FMA or + |d|).
+//
+// A pair costs 16 VALU operations per uint4 (8 subtractions, 8 accumulations; |d| is an input modifier) against the 4 v_dot2c
+// of the dot-product tile, and a uint4 widens in 8 conversions.  So every loaded uint4 is widened ONCE per step and kept: the
+// Q query operands of the step stay widened in 8 Q registers while the R rows pass by one at a time, 8 registers each — the
+// conversions per pair are 8 (R + Q) / (R Q): 4 at <4, 4, *>, 6 at <4, 2, 1>, 9 at <8, 1, 1>, 12 at the small launches'
+// <2, 1, 1, 24> (whose 24 steps in flight are latency, not VALU: a dozen leaves in the launch).  The queries are NOT kept
+// widened in memory or LDS: a f32 copy next to d_q16 doubles the bytes every octet reads of its Q queries per step (they come
+// from L2, the rows' competitor) to save 8 Q of the 8 (R + Q) + 16 R Q operations — a ninth at <4, 4, *>, where the calls
+// with many queries spend their time; LDS holds one query (k_pairs_screen_diff16) but a unit has up to 16 and the walk of the
+// small launches has no barrier to fill it behind.  Live registers at <4, 4, *>: 32 + 8 widened, 16 sums, 32 of loads.
+// No MFMA: |q~|^2 + |x~|^2 - 2 <q~, x~> cancels on rows with a common offset, and a 1-norm is not a product.
+__device__ __forceinline__ void widen_halves8(const uint4 x, float (&w)[8]) {
+    const f16x2_t h0 = __builtin_bit_cast(f16x2_t, x.x), h1 = __builtin_bit_cast(f16x2_t, x.y), h2 = __builtin_bit_cast(f16x2_t, x.z),
+                  h3 = __builtin_bit_cast(f16x2_t, x.w);
+    w[0] = (float)h0.x, w[1] = (float)h0.y, w[2] = (float)h1.x, w[3] = (float)h1.y;
+    w[4] = (float)h2.x, w[5] = (float)h2.y, w[6] = (float)h3.x, w[7] = (float)h3.y;
+}
+// one step of the tile: acc[u][t] += |y[t] - x[u]|_p^p over the lane's 8 elements
+template <int METRIC, int R, int Q>
+__device__ __forceinline__ void diff_tile_step(const uint4 (&x)[R], const uint4 (&y)[Q], float (&acc)[R][Q]) {
+    float yw[Q][8];
+#pragma unroll
+    for (int t = 0; t < Q; t++) widen_halves8(y[t], yw[t]);
+#pragma unroll
+    for (int u = 0; u < R; u++) {
+        float xw[8];
+        widen_halves8(x[u], xw);
+#pragma unroll
+        for (int t = 0; t < Q; t++)
+#pragma unroll
+            for (int i = 0; i < 8; i++) {
+                const float d = yw[t][i] - xw[i];
+                acc[u][t] = METRIC == AH_EUCLIDEAN ? fmaf(d, d, acc[u][t]) : acc[u][t] + fabsf(d);
+            }
+    }
+}
+template <int METRIC, int R, int Q, int QO, int KF = 1>
+__device__ __forceinline__ void leaf_tile_diff16(const ScreenSearch &ss, const DataView &dv, const uint32_t *__restrict__ leaf_ids,
+                                                 uint32_t row_begin, uint32_t n_rows, const Visit *__restrict__ vis, uint32_t n_vis,
+                                                 float *__restrict__ dist, uint32_t stride, uint32_t *err,
+                                                 uint32_t *__restrict__ copy_ids_to = nullptr, const Visit *only_visit = nullptr) {
+    constexpr uint32_t RO = 8 / QO;  // octets of a wave side by side over the rows (QO: over the queries)
+    const uint32_t j = threadIdx.x & 7u, ow = (threadIdx.x >> 3) & 7u, wave = threadIdx.x >> 6;
+    const uint32_t q_oct = ow % QO, row_oct = wave * RO + ow / QO;
+    const uint32_t steps = ss.hpitch >> 6;
+    const uint4 *q4[Q];
+    uint64_t out[Q];
+#pragma unroll
+    for (int t = 0; t < Q; t++) {
+        const Visit v = only_visit ? *only_visit : vis[min(q_oct * Q + (uint32_t)t, n_vis - 1)];
+        q4[t] = reinterpret_cast<const uint4 *>(ss.q16 + (uint64_t)v.q * ss.hpitch) + j;
+        out[t] = (uint64_t)v.q * stride + v.pos;
+    }
+    for (uint32_t r0 = row_begin + row_oct * R; r0 < n_rows; r0 += 4 * RO * R) {
+        const uint4 *r4[R];
+        bool missing[R];
+#pragma unroll
+        for (int u = 0; u < R; u++) {
+            const uint32_t id_u = leaf_ids[min(r0 + u, n_rows - 1)];
+            if (copy_ids_to && q_oct == 0 && j == 0 && r0 + u < n_rows) copy_ids_to[r0 + u] = id_u;  // (SingleQueryOut::ids_by_tiles)
+            const uint64_t row = row_of_id(dv, id_u);
+            missing[u] = row == ~0ull;
+            r4[u] = reinterpret_cast<const uint4 *>(ss.rows16 + (missing[u] ? 0ull : row) * ss.hpitch) + j;
+        }
+        float acc[R][Q];
+#pragma unroll
+        for (int u = 0; u < R; u++)
+#pragma unroll
+            for (int t = 0; t < Q; t++) acc[u][t] = 0.f;
+        uint32_t k = 0;
+        if constexpr (KF > 1) {  // (the small launches: KF steps of every row and query requested before the first use)
+            for (; k + KF <= steps; k += KF) {
+                uint4 x[KF][R], y[KF][Q];
+#pragma unroll
+                for (int f = 0; f < KF; f++) {
+#pragma unroll
+                    for (int u = 0; u < R; u++) x[f][u] = r4[u][(k + f) * 8];
+#pragma unroll
+                    for (int t = 0; t < Q; t++) y[f][t] = q4[t][(k + f) * 8];
+                }
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int f = 0; f < KF; f++) diff_tile_step<METRIC, R, Q>(x[f], y[f], acc);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+        for (; k < steps; k++) {
+            uint4 x[R], y[Q];
+#pragma unroll
+            for (int u = 0; u < R; u++) x[u] = r4[u][k * 8];
+#pragma unroll
+            for (int t = 0; t < Q; t++) y[t] = q4[t][k * 8];
+            diff_tile_step<METRIC, R, Q>(x, y, acc);
+        }
+#pragma unroll
+        for (int u = 0; u < R; u++) {
+#pragma unroll
+            for (int t = 0; t < Q; t++) {
+                const float s = octet_sum(acc[u][t]);
+                if (r0 + u >= n_rows || q_oct * Q + (uint32_t)t >= n_vis || j != 0) continue;
+                if (missing[u]) atomicOr(err, 1u);
+                dist[out[t] + r0 + u] = missing[u] ? __uint_as_float(0x7FC00000u) : s;  // (inf / NaN: an entry beyond 65504 — not screened)
+            }
+        }
+    }
+}
+template <int METRIC>
+struct DiffTile16 {
+    template <int R, int Q, int QO, int KF = 1>
+    static __device__ __forceinline__ void run(const ScreenSearch &ss, const DataView &dv, const uint32_t *__restrict__ leaf_ids, uint32_t row_begin,
+                                               uint32_t n_rows, const Visit *__restrict__ vis, uint32_t n_vis, float *__restrict__ dist, uint32_t stride,
+                                               uint32_t *err, uint32_t *__restrict__ copy_ids_to = nullptr, const Visit *only_visit = nullptr) {
+        leaf_tile_diff16<METRIC, R, Q, QO, KF>(ss, dv, leaf_ids, row_begin, n_rows, vis, n_vis, dist, stride, err, copy_ids_to, only_visit);
+    }
+};
+// k_leaf_tiles16 with that tile: the same walk, launch forms and arguments (leaf_tiles16_walk).
+template <int METRIC, bool SMALL>
+__global__ __launch_bounds__(256) AH_NO_PACKED_F32 void k_leaf_tiles_diff16(DataView dv, ScreenSearch ss, const uint32_t *__restrict__ nns,
+                                                                           const Visit *__restrict__ sorted, const TileUnit *__restrict__ units,
+                                                                           const uint32_t *__restrict__ n_units_p, float *__restrict__ dist,
+                                                                           uint32_t stride, uint32_t *err, uint32_t min_vis = 0,
+                                                                           const uint32_t *__restrict__ blob = nullptr, uint32_t speculate = 0,
+                                                                           uint32_t *__restrict__ trace = nullptr, uint32_t flat = 0,
+                                                                           const uint32_t *__restrict__ items = nullptr, uint32_t per_query = 0) {
+    leaf_tiles16_walk<SMALL, DiffTile16<METRIC>>(dv, ss, nns, sorted, units, n_units_p, dist, stride, err, min_vis, blob, speculate, trace, flat,
+                                                 items, per_query);
+}
+// The binary16 tile kernel of a screened sub-batch: the dot product of the copies (Cosine, DotProduct) or their difference
+// (Euclidean, Manhattan) — one signature, so every launch form of launch_tiles names its arguments once.
+template <bool SMALL>
+static auto tiles16_kernel(int metric) -> decltype(&k_leaf_tiles16<SMALL>) {
+    return metric == AH_EUCLIDEAN ? k_leaf_tiles_diff16<AH_EUCLIDEAN, SMALL>
+           : metric == AH_MANHATTAN ? k_leaf_tiles_diff16<AH_MANHATTAN, SMALL> : k_leaf_tiles16<SMALL>;
+}
+
 // bounds of the reference distance of one candidate from its screen value (see above)
 // E >= |s - r_ref| for every row of the dataset: screen accumulation, the two quantisations (Cauchy-Schwarz on measured norms,
 // the rows' from their dataset-wide maxima: the bound is monotone in every one), the reference's own rounding
@@ -2935,7 +3098,8 @@ __device__ __forceinline__ float difference_distance(const float4 *s_qf4, const 
 
 // Selection of k_search_select with the screen in front: `dist_all` holds the SCREEN dot products of the candidates.
 // err bit 2: a non-finite screen value or distance; bit 3: more survivors than kSelectCap.
-template <int METRIC, bool FLAG>
+// (INSTANCE only tells two kernels' copies of one <METRIC, FLAG> apart: hipcc's inliner crashes on a body two kernels share)
+template <int METRIC, bool FLAG, int INSTANCE = 0>
 __device__ __forceinline__ void search_select_screened_body(DataView dv, ScreenSearch ss, const uint32_t *__restrict__ nns,
                                                                  const float *__restrict__ dist_all, uint32_t stride,
                                                                  const uint32_t *__restrict__ counts,
@@ -3220,6 +3384,32 @@ __device__ __forceinline__ void search_select_screened_body(DataView dv, ScreenS
     if (trace && threadIdx.x == 0 && blockIdx.x == 0) trace[9] = n_sel;
 }
 
+// The tail of a selection kernel of the search with host_status (see k_search_select_screened, k_search_select_diff).
+__device__ __forceinline__ void select_host_status_tail(uint32_t *err, uint32_t *__restrict__ host_status, uint32_t *__restrict__ trace,
+                                                        uint64_t t_start) {
+    // The results went to the caller's pinned buffers: system-scope fences, and word 0 of the status LAST — the host may be
+    // polling that word instead of waiting for the stream (AH_SEARCH_SPIN_WAIT), and what it reads after it must be there.
+    __threadfence_system();
+    __syncthreads();
+    // (one query: this block is the last one by construction — no counter, no second fence)
+    // The first wave of the last block: lane w carries status word w (sixteen loads and stores side by side, not one after the
+    // other), word 0 after a fence of its own, then the wipe for the next submission (Context::clean_status).
+    if (threadIdx.x < 64u) {
+        uint32_t last = 0;
+        if (threadIdx.x == 0) last = (gridDim.x == 1u || atomicAdd(&err[SS_DONE], 1u) + 1u == gridDim.x) ? 1u : 0u;
+        last = (uint32_t)__shfl((int)last, 0, 64);
+        if (last) {  // wave-uniform
+            if (gridDim.x != 1u) __threadfence_system();
+            const uint32_t w = threadIdx.x;
+            const uint32_t word = w < SS_WORDS ? __hip_atomic_load(&err[w], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
+            if (w >= 1u && w < SS_WORDS) host_status[w] = word;
+            __threadfence_system();
+            if (w == 0u) __hip_atomic_store(&host_status[0], word, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+            if (w < SS_WORDS) __hip_atomic_store(&err[w], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (trace && w == 0u) trace[8] = (uint32_t)(wall_clock64() - t_start);
+        }
+    }
+}
 // host_status != nullptr (a small submission; out_ids / out_dist / unique_out are then the caller's pinned buffers): the block
 // that finishes last copies the status words there as well, and the call needs no copy back — only the wait for this kernel.
 template <int METRIC, bool FLAG = false>
@@ -3239,30 +3429,7 @@ __global__ __launch_bounds__(1024) void k_search_select_screened(DataView dv, Sc
     const uint64_t t_start = trace ? wall_clock64() : 0ull;
     search_select_screened_body<METRIC, FLAG>(dv, ss, nns, dist_all, stride, counts, unique, k_out, qvecs, qstride, qhdrs, out_ids, out_dist,
                                               err, segs, flag_words, id_limit, unique_out, trace, count_of);
-    if (host_status) {  // (every return of the body is block-uniform)
-        // The results went to the caller's pinned buffers: system-scope fences, and word 0 of the status LAST — the host may be
-        // polling that word instead of waiting for the stream (AH_SEARCH_SPIN_WAIT), and what it reads after it must be there.
-        __threadfence_system();
-        __syncthreads();
-        // (one query: this block is the last one by construction — no counter, no second fence)
-        // The first wave of the last block: lane w carries status word w (sixteen loads and stores side by side, not one after the
-        // other), word 0 after a fence of its own, then the wipe for the next submission (Context::clean_status).
-        if (threadIdx.x < 64u) {
-            uint32_t last = 0;
-            if (threadIdx.x == 0) last = (gridDim.x == 1u || atomicAdd(&err[SS_DONE], 1u) + 1u == gridDim.x) ? 1u : 0u;
-            last = (uint32_t)__shfl((int)last, 0, 64);
-            if (last) {  // wave-uniform
-                if (gridDim.x != 1u) __threadfence_system();
-                const uint32_t w = threadIdx.x;
-                const uint32_t word = w < SS_WORDS ? __hip_atomic_load(&err[w], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
-                if (w >= 1u && w < SS_WORDS) host_status[w] = word;
-                __threadfence_system();
-                if (w == 0u) __hip_atomic_store(&host_status[0], word, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-                if (w < SS_WORDS) __hip_atomic_store(&err[w], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (trace && w == 0u) trace[8] = (uint32_t)(wall_clock64() - t_start);
-            }
-        }
-    }
+    if (host_status) select_host_status_tail(err, host_status, trace, t_start);  // (every return of the body is block-uniform)
 }
 
 // The same selection for the lists of the difference screen (Euclidean / Manhattan; `segs` only, no host status).
@@ -3275,6 +3442,24 @@ __global__ __launch_bounds__(1024) AH_NO_PACKED_F32 void k_rerank_select_diff(Da
                                                                               const RerankSeg *__restrict__ segs) {
     search_select_screened_body<METRIC, false>(dv, ss, ids, dist_all, 0u, nullptr, nullptr, k_out, qvecs, qstride, qhdrs, out_ids, out_dist, err,
                                                segs, 0u, 0u, nullptr);
+}
+// ... and for the search's tile pass on the difference screen (k_leaf_tiles_diff16): k_search_select_screened's arguments and
+// host_status tail, a kernel of its own so that the Cosine / DotProduct selections are compiled as they were.
+template <int METRIC, bool FLAG = false>
+__global__ __launch_bounds__(1024) AH_NO_PACKED_F32 void k_search_select_diff(DataView dv, ScreenSearch ss, const uint32_t *__restrict__ nns,
+                                                                              const float *__restrict__ dist_all, uint32_t stride,
+                                                                              const uint32_t *__restrict__ counts,
+                                                                              const uint32_t *__restrict__ unique, uint32_t k_out,
+                                                                              const uint8_t *__restrict__ qvecs, uint64_t qstride,
+                                                                              const float *__restrict__ qhdrs, uint32_t *__restrict__ out_ids,
+                                                                              float *__restrict__ out_dist, uint32_t *err, uint32_t flag_words,
+                                                                              uint32_t id_limit, uint32_t *__restrict__ unique_out,
+                                                                              uint32_t *__restrict__ host_status, uint32_t *__restrict__ trace,
+                                                                              const uint32_t *__restrict__ count_of) {
+    const uint64_t t_start = trace ? wall_clock64() : 0ull;
+    search_select_screened_body<METRIC, FLAG, 1>(dv, ss, nns, dist_all, stride, counts, unique, k_out, qvecs, qstride, qhdrs, out_ids, out_dist,
+                                                 err, nullptr, flag_words, id_limit, unique_out, trace, count_of);
+    if (host_status) select_host_status_tail(err, host_status, trace, t_start);  // (every return of the body is block-uniform)
 }
 
 // AH_SCREEN_VERIFY=1 (a test aid; the host launches it only under that tunable, in front of the selection, which it leaves as
@@ -3341,14 +3526,15 @@ __global__ __launch_bounds__(256) void k_screen_verify(DataView dv, ScreenSearch
                                                        const float *__restrict__ qhdrs, unsigned long long *__restrict__ out) {
     screen_verify_body<METRIC>(dv, ss, nns, dist_all, stride, counts, segs, qvecs, qstride, qhdrs, out);
 }
-template <int METRIC>  // (the lists of the difference screen)
+template <int METRIC>  // (the difference screen: the lists of the re-rank, or the slots of the search's tile pass)
 __global__ __launch_bounds__(256) AH_NO_PACKED_F32 void k_screen_verify_diff(DataView dv, ScreenSearch ss, const uint32_t *__restrict__ ids,
-                                                                            const float *__restrict__ dist_all,
+                                                                            const float *__restrict__ dist_all, uint32_t stride,
+                                                                            const uint32_t *__restrict__ counts,
                                                                             const RerankSeg *__restrict__ segs,
                                                                             const uint8_t *__restrict__ qvecs, uint64_t qstride,
                                                                             const float *__restrict__ qhdrs,
                                                                             unsigned long long *__restrict__ out) {
-    screen_verify_body<METRIC>(dv, ss, ids, dist_all, 0u, nullptr, segs, qvecs, qstride, qhdrs, out);
+    screen_verify_body<METRIC>(dv, ss, ids, dist_all, stride, counts, segs, qvecs, qstride, qhdrs, out);
 }
 
 // Launches k_screen_verify over a screened submission when AH_SCREEN_VERIFY is 1 (otherwise nothing).  The counters live in
@@ -3373,7 +3559,7 @@ static int launch_screen_verify(ah_dataset *ds, const ScreenSearch &ss, const ui
         constexpr int M = decltype(m)::value;
         if constexpr (metric_screens_difference(M)) {
             AH_TRY(lds_opt_in(reinterpret_cast<const void *>(k_screen_verify_diff<M>), ds->device, lds));
-            hipLaunchKernelGGL(k_screen_verify_diff<M>, grid, dim3(256), lds, s, dv, ss, nns, dist, segs, qvecs, qstride, qhdrs, ctr);
+            hipLaunchKernelGGL(k_screen_verify_diff<M>, grid, dim3(256), lds, s, dv, ss, nns, dist, stride, counts, segs, qvecs, qstride, qhdrs, ctr);
         } else {
             AH_TRY(lds_opt_in(reinterpret_cast<const void *>(k_screen_verify<M>), ds->device, lds));
             hipLaunchKernelGGL(k_screen_verify<M>, grid, dim3(256), lds, s, dv, ss, nns, dist, stride, counts, segs, qvecs, qstride, qhdrs, ctr);
@@ -3719,9 +3905,12 @@ int launch_rerank_screened(ah_dataset *ds, const RerankBufs &b, uint32_t tile_fi
 // the binary16 shadow of the rows for the certified top-k screen of the re-rank (made once per dataset; the forest build
 // of an f32 dataset has usually made it already).  No memory for it = no screen, not an error.
 void index_prepare_screens(ah_dataset *ds) {
-    if (tun(TUN_SEARCH_SCREEN) != 0 && (ds->metric == AH_COSINE || ds->metric == AH_DOT_PRODUCT) && ds->dims >= 32 && ds->n) {
+    // (Euclidean / Manhattan: only for the difference screen of the tiles, AH_SEARCH_SCREEN_DIFF, and never the int8 copy)
+    const bool dot = ds->metric == AH_COSINE || ds->metric == AH_DOT_PRODUCT;
+    const bool diff = metric_screens_difference(ds->metric) && tun(TUN_SEARCH_SCREEN_DIFF) != 0;
+    if (tun(TUN_SEARCH_SCREEN) != 0 && (dot || diff) && ds->dims >= 32 && ds->n) {
         ContextLease lease(ds);
-        if (lease.c && ensure_screen(ds, lease.c->stream, false) && tun(TUN_SEARCH_SCREEN8) != 0)
+        if (lease.c && ensure_screen(ds, lease.c->stream, false) && dot && tun(TUN_SEARCH_SCREEN8) != 0)
             (void)ensure_screen8_search(ds, lease.c->stream);  // ... and the int8 copy in front of it (round 6), likewise
     }
 }
@@ -4024,7 +4213,7 @@ static SearchKnobs search_knobs() {
     kn.multi_own_units = tun(TUN_SEARCH_MULTI_OWN_UNITS) != 0, kn.flat_tiles = tun(TUN_SEARCH_FLAT_TILES) != 0;
     kn.single_fused = tun(TUN_SEARCH_SINGLE_FUSED) != 0, kn.multi_ids_by_tiles = tun(TUN_SEARCH_MULTI_IDS_BY_TILES) != 0;
     kn.multi_trace = tun(TUN_SEARCH_MULTI_TRACE) != 0, kn.fused_flag = tun(TUN_SEARCH_FUSED_FLAG) != 0, kn.spin_wait = tun(TUN_SEARCH_SPIN_WAIT) != 0;
-    kn.wave = tun(TUN_SEARCH_WAVE) != 0, kn.debug = tun(TUN_DEBUG) != 0;
+    kn.wave = tun(TUN_SEARCH_WAVE) != 0, kn.debug = tun(TUN_DEBUG) != 0, kn.screen_diff = tun(TUN_SEARCH_SCREEN_DIFF) != 0;
     kn.small_tiles_max_queries = tun(TUN_SEARCH_SMALL_TILES_MAX_QUERIES), kn.screen8_min_queries = tun(TUN_SEARCH_SCREEN8_MIN_QUERIES);
     kn.small_units_max_queries = tun(TUN_SEARCH_SMALL_UNITS_MAX_QUERIES), kn.block_max_queries = tun(TUN_SEARCH_BLOCK_MAX_QUERIES);
     kn.multi_trees_per_block = tun(TUN_SEARCH_MULTI_TREES_PER_BLOCK), kn.multi_max_queries = tun(TUN_SEARCH_MULTI_MAX_QUERIES);
@@ -4130,6 +4319,7 @@ static ChunkShape chunk_shape(const ah_index *ix, const ChunkArgs &a) {
     z.screen_ready = ds->screen_ready.load(std::memory_order_acquire);  // (published: common.h)
     z.screen8_ready = ds->screen8_ready.load(std::memory_order_acquire);
     z.search8_off = ix->search8_off.load(std::memory_order_relaxed);
+    z.search_diff_off = ix->search_diff_off.load(std::memory_order_relaxed);
     z.tile_candidates = batch_tile_candidates();
     // counters of the row-major re-rank, reserved when the candidate lists could be long enough for it
     z.inv_bytes = batch_invert_wanted(ds->view(), (uint64_t)a.nq * a.nns_stride) ? batch_invert_counter_bytes(ds->n, (uint64_t)a.nq * a.nns_stride) : 0;
@@ -4310,20 +4500,22 @@ static int launch_tiles(ChunkCtx &c) {
                            b.d_err, plan.max_vis8 + 1);
         break;
     case TileLaunch::Flat:
-        hipLaunchKernelGGL((k_leaf_tiles16<true>), grid, dim3(256), 0, s, dv, ss, b.d_nns, b.d_sorted, b.d_units, nq == 1 ? d_n_units : b.d_unit_counts,
-                           b.d_dist, nns_stride, b.d_err, 0u, c.ix->d_desc, 0u, tile_trace, 1u, (const uint32_t *)nullptr, plan.units_per_query);
+        hipLaunchKernelGGL(tiles16_kernel<true>(ds->metric), grid, dim3(256), 0, s, dv, ss, b.d_nns, b.d_sorted, b.d_units,
+                           nq == 1 ? d_n_units : b.d_unit_counts, b.d_dist, nns_stride, b.d_err, 0u, c.ix->d_desc, 0u, tile_trace, 1u,
+                           (const uint32_t *)nullptr, plan.units_per_query);
         break;
     case TileLaunch::ItemList:
-        hipLaunchKernelGGL((k_leaf_tiles16<true>), grid, dim3(256), 0, s, dv, ss, b.d_nns, b.d_sorted, b.d_units, d_n_units, b.d_dist, nns_stride,
-                           b.d_err, 0u, c.ix->d_desc, 0u, tile_trace, 0u, b.d_items);
+        hipLaunchKernelGGL(tiles16_kernel<true>(ds->metric), grid, dim3(256), 0, s, dv, ss, b.d_nns, b.d_sorted, b.d_units, d_n_units, b.d_dist,
+                           nns_stride, b.d_err, 0u, c.ix->d_desc, 0u, tile_trace, 0u, b.d_items, 0u);
         break;
     case TileLaunch::Small2D:
-        hipLaunchKernelGGL((k_leaf_tiles16<true>), grid, dim3(256), 0, s, dv, ss, b.d_nns, b.d_sorted, b.d_units, d_n_units, b.d_dist, nns_stride,
-                           b.d_err, 0u, c.ix->d_desc, plan.visit_cap >= plan.tile_grid_x ? 1u : 0u, tile_trace);
+        hipLaunchKernelGGL(tiles16_kernel<true>(ds->metric), grid, dim3(256), 0, s, dv, ss, b.d_nns, b.d_sorted, b.d_units, d_n_units, b.d_dist,
+                           nns_stride, b.d_err, 0u, c.ix->d_desc, plan.visit_cap >= plan.tile_grid_x ? 1u : 0u, tile_trace, 0u,
+                           (const uint32_t *)nullptr, 0u);
         break;
     case TileLaunch::Big2D:
-        hipLaunchKernelGGL((k_leaf_tiles16<false>), grid, dim3(256), 0, s, dv, ss, b.d_nns, b.d_sorted, b.d_units, d_n_units, b.d_dist, nns_stride,
-                           b.d_err);
+        hipLaunchKernelGGL(tiles16_kernel<false>(ds->metric), grid, dim3(256), 0, s, dv, ss, b.d_nns, b.d_sorted, b.d_units, d_n_units, b.d_dist,
+                           nns_stride, b.d_err, 0u, (const uint32_t *)nullptr, 0u, (uint32_t *)nullptr, 0u, (const uint32_t *)nullptr, 0u);
         break;
     default:
         AH_TRY(with_tile_metric(ds->metric, [&](auto m) -> int {
@@ -4409,7 +4601,23 @@ static int launch_select_and_wait(ChunkCtx &c, hipError_t &launch_err) {
     }
     uint32_t *sel_trace = c.multi_trace() ? &c.multi_trace()->sel_trace[0] : nullptr;
     if (plan.screened) AH_TRY(launch_screen_verify(ds, ss, b.d_nns, b.d_dist, nns_stride, b.d_counts, nullptr, (uint32_t)nq, b.d_qvecs, qstride, b.d_qhdrs, s));
-    if (fused_flag)
+    if (plan.screened && metric_screens_difference(ds->metric))  // (a kernel of its own: k_search_select_diff)
+        AH_TRY(with_diff_metric(ds->metric, [&](auto m) -> int {
+            constexpr int M = decltype(m)::value;
+            if (fused_flag) {
+                AH_TRY(lds_opt_in(reinterpret_cast<const void *>(k_search_select_diff<M, true>), ds->device, plan.fused_lds, 0));
+                hipLaunchKernelGGL((k_search_select_diff<M, true>), dim3((unsigned)nq), dim3(1024), plan.fused_lds, s, dv, ss, b.d_nns, b.d_dist,
+                                   nns_stride, b.d_counts, b.d_unique, (uint32_t)k, b.d_qvecs, qstride, b.d_qhdrs, b.h_oi, b.h_od, b.d_err,
+                                   bitmap_words, max_id + 1, b.h_counts, h_err, sel_trace, sp.count_of);
+            } else {
+                AH_TRY(lds_opt_in(reinterpret_cast<const void *>(k_search_select_diff<M>), ds->device, plan.sel_lds, kSelectLdsFloor));
+                hipLaunchKernelGGL((k_search_select_diff<M>), dim3((unsigned)nq), dim3(1024), plan.sel_lds, s, dv, ss, b.d_nns, b.d_dist,
+                                   nns_stride, b.d_counts, b.d_unique, (uint32_t)k, b.d_qvecs, qstride, b.d_qhdrs, b.d_oi, b.d_od, b.d_err, 0u, 0u,
+                                   (uint32_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr, sp.count_of);
+            }
+            return AH_OK;
+        }));
+    else if (fused_flag)
         AH_TRY(with_screen_metric(ds->metric, [&](auto m) -> int {
             constexpr int M = decltype(m)::value;
             AH_TRY(lds_opt_in(reinterpret_cast<const void *>(k_search_select_screened<M, true>), ds->device, plan.fused_lds, 0));
@@ -4469,6 +4677,7 @@ static int finish_tiles(ChunkCtx &c, hipError_t launch_err, TileOutcome &outcome
     hipStream_t s = c.stream();
     const size_t nq = a.nq, k = a.count;
     const uint32_t *const h_err = b.h_err;
+    const bool diff = plan.screened && metric_screens_difference(c.shape.metric);  // the difference screen (AH_SEARCH_SCREEN_DIFF)
     AH_REQUIRE((*h_err & 1u) == 0 || *h_err == 0xFFFFFFFFu, AH_ERR_MISSING_ITEM, "a descendant id does not exist in the dataset");
     if ((*h_err & ~1u) == 0 && launch_err == hipSuccess) {
         if (plan.fused_flag) c.ctx->clean_status = b.d_err;  // (its selection kernel ran to its end and wiped the block behind itself)
@@ -4481,6 +4690,13 @@ static int finish_tiles(ChunkCtx &c, hipError_t launch_err, TileOutcome &outcome
         if (plan.screened8) (void)screen8_window_note(ix->search8_seen, ix->search8_fails, false);
         (plan.bitmap_fits ? cs.s.dedup_flag_bitmap : cs.s.dedup_flag_hash) = nq;
         cs.commit(ix);
+        if (diff) {
+            (void)screen8_window_note(ix->search_diff_seen, ix->search_diff_fails, false);
+            std::lock_guard<std::mutex> lk(ix->stats_mu);
+            ix->diff_stats.chunks_screened += 1;
+            ix->diff_stats.queries += h_err[SS_SCREENED];
+            ix->diff_stats.survivors += h_err[SS_SURVIVORS];
+        }
         outcome = TileOutcome::Done;
         return AH_OK;
     }
@@ -4494,6 +4710,16 @@ static int finish_tiles(ChunkCtx &c, hipError_t launch_err, TileOutcome &outcome
         }
         outcome = TileOutcome::RetryWithout8;
         return AH_OK;
+    }
+    if (diff && launch_err == hipSuccess && *h_err != 0xFFFFFFFFu) {
+        // the difference screen entered and left to the sorted path.  More survivors than the selection holds (bit 3: candidates
+        // closer together than delta) is what the window counts: eight within 64 sub-batches the stage took switch it off for the
+        // index — Euclidean returns to the f32 tiles, Manhattan to the sorted path
+        const bool overflowed = (*h_err & 8u) != 0;
+        if (screen8_window_note(ix->search_diff_seen, ix->search_diff_fails, overflowed)) ix->search_diff_off.store(true, std::memory_order_relaxed);
+        std::lock_guard<std::mutex> lk(ix->stats_mu);
+        ix->diff_stats.chunks_screened += 1;
+        ix->diff_stats.chunks_overflowed += overflowed ? 1 : 0;
     }
     // a case the tiles do not reproduce (bits 2..5 of *err, see k_search_select / VisitSink): redo it the long way
     cs.s.fallback_chunks = 1;
@@ -4863,6 +5089,20 @@ int ah_index_search_stats(ah_index *ix, ah_search_stats *out, int reset) {
     std::lock_guard<std::mutex> lk(ix->stats_mu);
     *out = ix->stats;
     if (reset) ix->stats = ah_search_stats{};
+    return AH_OK;
+    AH_GUARDED_END
+}
+
+// What the difference screen of the tile pass served on this index (AH_SEARCH_SCREEN_DIFF); reset as above.
+int ah_index_search_diff_stats(ah_index *ix, ah_search_diff_stats *out, int reset) {
+    AH_GUARDED("ah_index_search_diff_stats")
+    AH_REQUIRE(ix, AH_ERR_INVALID_ARGUMENT, "index is NULL");
+    std::lock_guard<std::mutex> lk(ix->stats_mu);
+    if (out) {
+        *out = ix->diff_stats;
+        out->switched_off = ix->search_diff_off.load(std::memory_order_relaxed) ? 1 : 0;
+    }
+    if (reset) ix->diff_stats = ah_search_diff_stats{};
     return AH_OK;
     AH_GUARDED_END
 }

@@ -30,6 +30,7 @@ constexpr uint32_t kStatusWords = 16;            // the per-chunk status block (
 struct SearchKnobs {
     bool bitmap, tiles, screen, screen8, item_list, small_gate, status_wipe, fused_prepare, multi, multi_own_units, flat_tiles,
         single_fused, multi_ids_by_tiles, multi_trace, fused_flag, spin_wait, wave, debug;
+    bool screen_diff;  // AH_SEARCH_SCREEN_DIFF: Euclidean / Manhattan sub-batches through the tiles on the difference screen
     long long small_tiles_max_queries, screen8_min_queries, small_units_max_queries, block_max_queries, multi_trees_per_block,
         multi_max_queries, screen8_max_visits;
 };
@@ -56,6 +57,7 @@ struct ChunkShape {
     uint32_t max_id;
     // atomics as sampled
     bool screen_ready, screen8_ready, search8_off;
+    bool search_diff_off;  // the difference screen of the tiles switched itself off on this index (ah_index::search_diff_off)
     // the batched re-rank (batch.hip) as asked: candidates per tile, the counters of the row-major re-rank (0: not wanted),
     // whether `count` is within the tournament top-k, and the keys per query of the tournament / of the single-query top-k
     // (the latter filled only when it is not: 0 otherwise)
@@ -130,18 +132,23 @@ inline ChunkPlan plan_chunk(const ChunkShape &z, const SearchKnobs &kn) {
     // candidates) of them, so a larger count could only do the whole tile pass, overflow and be redone — after an int8 pass and
     // its binary16 retry where that stage is on, each noted as a failure of the int8 stage in its window of 64 sub-batches.
     // Unless a query cannot have more than kSelectCap candidates at all: a count meant as "everything" under a small search_k)
-    p.tiles = !z.mixed && kn.tiles && (p.bitmap_fits || p.hash_fits) && !p.big_k && (k <= kSelectCap || z.nns_stride <= kSelectCap) &&
-              z.dims >= 32 && z.max_desc <= 65535u * kTileSlab &&
-              (z.metric == AH_EUCLIDEAN || z.metric == AH_COSINE || z.metric == AH_DOT_PRODUCT);
+    const bool tiles_fit = !z.mixed && kn.tiles && (p.bitmap_fits || p.hash_fits) && !p.big_k && (k <= kSelectCap || z.nns_stride <= kSelectCap) &&
+                           z.dims >= 32 && z.max_desc <= 65535u * kTileSlab;
+    // certified top-k screen of the tile re-rank: the binary16 shadow of the rows must exist (ah_index_create makes it).
+    // Cosine / DotProduct by the dot product of the copies; Euclidean / Manhattan by their difference (k_leaf_tiles_diff16),
+    // when AH_SEARCH_SCREEN_DIFF asks for it and the index has not switched it off — never with an int8 stage
+    const bool screen_fit = tiles_fit && kn.screen && z.screen_ready;
+    const bool diff_screened = screen_fit && (z.metric == AH_EUCLIDEAN || z.metric == AH_MANHATTAN) && kn.screen_diff && !z.search_diff_off;
+    // (Manhattan's reference distance is a sequential sum: no f32 tile — it takes the tiles only behind the screen)
+    p.tiles = tiles_fit && (z.metric == AH_EUCLIDEAN || z.metric == AH_COSINE || z.metric == AH_DOT_PRODUCT || diff_screened);
     p.visit_cap = (uint32_t)std::min<uint64_t>((uint64_t)nq * z.nns_stride, 2u << 20);
     p.n_leaf_sums = (z.n_nodes + kLeafScanItems - 1) / kLeafScanItems;
-    // certified top-k screen of the tile re-rank: the binary16 shadow of the rows must exist (ah_index_create makes it)
-    p.screened = p.tiles && kn.screen && (z.metric == AH_COSINE || z.metric == AH_DOT_PRODUCT) && z.screen_ready;
+    p.screened = screen_fit && (z.metric == AH_COSINE || z.metric == AH_DOT_PRODUCT || diff_screened);
     // ... and on the int8 copy before that (round 6): the submissions of at least AH_SEARCH_SCREEN8_MIN_QUERIES queries (65: past
     // the small ones' unit builder).  From 9 queries a call the leaf tiles are bound by the bytes of their rows (64 queries: 294 of
     // the call's 508 us) and the int8 rows do cut them to 249 — but the wider band of survivors costs the selection 65 -> 95 us
     // and the queries' digits a launch: 511 us against 502, measured, so the default leaves those calls on binary16; see ScreenSearch
-    p.screened8 = p.screened && z.allow8 && kn.screen8 && !z.search8_off &&
+    p.screened8 = p.screened && !diff_screened && z.allow8 && kn.screen8 && !z.search8_off &&
                   (long long)nq > std::max(kn.small_tiles_max_queries, kn.screen8_min_queries - 1) && z.screen8_ready;
     // (a few queries a call: the list of (unit, slab) pairs k_units_small leaves for the tile launch)
     p.items_cap = p.tiles && (long long)nq <= kn.small_units_max_queries && kn.item_list

@@ -910,6 +910,13 @@ class Index:
         _lib.check(_lib.lib().ah_index_search_stats(self._h, C.byref(st), 1 if reset else 0))
         return {f: int(getattr(st, f)) for f, _ in _lib.AhSearchStats._fields_ if f != "reserved"}
 
+    def search_diff_stats(self, reset: bool = False) -> dict:
+        """ah_index_search_diff_stats: what the difference screen of the tile pass served (tunable AH_SEARCH_SCREEN_DIFF=1,
+        Euclidean / Manhattan): sub-batches screened and overflowed, queries, survivors, and whether it switched itself off."""
+        st = _lib.AhSearchDiffStats()
+        _lib.check(_lib.lib().ah_index_search_diff_stats(self._h, C.byref(st), 1 if reset else 0))
+        return {f: getattr(st, f) for f, _ in _lib.AhSearchDiffStats._fields_}
+
     def route_items(self, item_ids: Sequence[int], tree_seeds: Sequence[int]) -> np.ndarray:
         """Incremental routing (src/writer.rs:1398-1459): [n_trees, n] forest-local Descendants node per item."""
         ids = _u32(item_ids)

@@ -56,7 +56,8 @@ extern "C" {
                                   ah_index_footprint_get / ah_index_compact; ah_index_audit / ah_forest_view_audit;
                                   ah_index_drop_trees; ah_index_create_from_encoded; ah_index_encode_nodes;
                                   ah_index_create_from_legacy;
-                                  ah_dataset_rerank_diff_stats (the difference screen of Euclidean / Manhattan lists) */
+                                  ah_dataset_rerank_diff_stats (the difference screen of Euclidean / Manhattan lists);
+                                  ah_index_search_diff_stats (the same screen in the tile pass of ah_search_batch) */
 
 /* every entry point is exported from the shared object (it is built with -fvisibility=hidden) */
 #if defined(__GNUC__)
@@ -684,6 +685,20 @@ typedef struct ah_search_stats {
                                        eight octets each: one query on more than one compute unit (submissions of <= 32 queries) */
 } ah_search_stats;
 AH_API int ah_index_search_stats(ah_index *index, ah_search_stats *out, int reset);
+/* The difference screen in the tile pass of ah_search_batch / _filters / _params (tunable AH_SEARCH_SCREEN_DIFF=1, default 0:
+ * Euclidean sub-batches read their candidates' f32 rows in the leaf tiles, Manhattan ones take the sorted path).  With it both
+ * take the leaf tiles on the binary16 copy of the rows, s = |q~ - x~|_p^p, and only the candidates whose proven interval of the
+ * reference distance reaches the top `count` are read in f32: the same ids and distance bits.  The tunable must be on at
+ * ah_index_create* for the copy to exist.  Its queries and survivors also count in ah_search_stats.rerank_screened /
+ * screen_survivors.  reset != 0 zeroes the counters after the copy (not switched_off).  An addition to v7: a caller that needs
+ * it looks the symbol up. */
+typedef struct ah_search_diff_stats {
+    uint64_t chunks_screened;    /* sub-batches that entered the stage                                                      */
+    uint64_t chunks_overflowed;  /* ... that left some query more than 1024 survivors: answered by the sorted path instead  */
+    uint64_t queries, survivors; /* queries answered through the stage, and their candidates evaluated in f32               */
+    uint64_t switched_off;       /* 1: eight overflows within one window of 64 sub-batches switched the stage off           */
+} ah_search_diff_stats;
+AH_API int ah_index_search_diff_stats(ah_index *index, ah_search_diff_stats *out, int reset);
 
 /* ------------------------------------------------------------------------------------------
  * Resident candidate filters (ABI v7 addition: look the symbols up).  `QueryBuilder::candidates` (src/reader.rs:110-123)

@@ -115,9 +115,16 @@ def one(rng, it):
             raise AssertionError(desc + f" stream in_flight={in_flight} sa={split_after}: {e!r}")
         assert [streamed.canonical(t) for t in range(len(seeds))] == [forest.canonical(t) for t in range(len(seeds))], desc + " stream"
         assert len(streamed.splits) + len(streamed.leaves) == len(forest.nodes), desc + " stream node count"
-    index = ds.create_index(forest)
-    count, search_k = int(rng.choice([1, 10, 200, 2500])), int(rng.choice([0, 1, 100, 2**62]))
-    got = index.search(count, queries=qs[: min(nq, 4)], search_k=search_k)
+    # (the difference screen of the search's tile pass, off by default: Euclidean / Manhattan configurations run with it, under
+    # verify — the switch must be on when the index is made, for the binary16 copy)
+    from arroy_amd._lib import tuning as _tuning_s
+    diff_tun = dict(AH_SEARCH_SCREEN_DIFF=1, AH_SCREEN_VERIFY=1) if metric in (O.EUCLIDEAN, O.MANHATTAN) else {}
+    with _tuning_s(**diff_tun):
+        index = ds.create_index(forest)
+        count, search_k = int(rng.choice([1, 10, 200, 2500])), int(rng.choice([0, 1, 100, 2**62]))
+        ds.query_screen_verify(reset=True)
+        got = index.search(count, queries=qs[: min(nq, 4)], search_k=search_k)
+        assert ds.query_screen_verify()["violations"] == 0, desc + " search difference screen: a candidate outside its interval"
     for i in range(min(nq, 4)):
         v, h = oracle.query_leaf(qs[i])
         want, _ = O.search(oracle, forest, v, h, count, search_k, 0, None)
