@@ -181,7 +181,8 @@ inline int guarded(const char *what, F &&f) noexcept {
     X(RERANK_SCREEN, "AH_RERANK_SCREEN", 1)     /* 0: ah_rerank_batch never screens its candidates (f32 rows for all) */ \
     X(RERANK_SCREEN_DIFF, "AH_RERANK_SCREEN_DIFF", 0) /* 1: ah_rerank_batch screens Euclidean / Manhattan lists on the binary16 rows too, by the difference of the copies (DESIGN.md 2.5 "The difference screen"); 0 (default): those lists take the f32 gather, no call and no statistic changes; AH_RERANK_SCREEN=0 wins */ \
     X(SEARCH_SCREEN_DIFF, "AH_SEARCH_SCREEN_DIFF", 0) /* 1: Euclidean / Manhattan sub-batches of ah_search_batch / _filters / _params take the leaf tiles on the binary16 rows, by the difference of the copies (k_leaf_tiles_diff16), and ah_index_create makes that copy for them; 0 (default): Euclidean keeps the f32 tiles, Manhattan the sorted path, no plan, launch, allocation or statistic changes; AH_SEARCH_SCREEN=0 wins */ \
-    X(REPLICATE_HOST_BOUNCE, "AH_REPLICATE_HOST_BOUNCE", 0) /* 1: ah_dataset_replicate copies through pinned host memory even where peer access works (test aid) */ \
+    X(SEARCH_TILES_BQ, "AH_SEARCH_TILES_BQ", 0) /* 1: the sub-batches of the three 1-bit metrics of ah_search_batch / _filters / _params take the leaf tiles (k_leaf_tiles_bq, DESIGN.md 4 "1-bit leaf tiles": exact distances, nothing screened) up to 8192 dimensions; 0 (default): they take the sorted path, no plan, launch, allocation or statistic changes */ \
+    X(REPLICATE_HOST_BOUNCE,"AH_REPLICATE_HOST_BOUNCE", 0) /* 1: ah_dataset_replicate copies through pinned host memory even where peer access works (test aid) */ \
     X(RERANK_TIMING, "AH_RERANK_TIMING", 0)     /* 1: ah_rerank_batch accounts its wall time by phase (ah_dataset_rerank_stats) */ \
     X(SEARCH_SCREEN, "AH_SEARCH_SCREEN", 1)     /* 0: the re-rank of ah_search_batch never screens its candidates (f32 rows for all) */ \
     X(SEARCH_FILTER_GROUP_MIN, "AH_SEARCH_FILTER_GROUP_MIN", 16) /* ah_search_batch_filters: the queries of one filter form a sub-batch of their own from this many on; fewer share a mixed sub-batch */ \

@@ -2476,8 +2476,9 @@ struct DotTile16 {
 };
 // The unit and slab walk of the binary16 leaf tiles, whatever TILE computes per (row, query) pair: which block takes which
 // (unit, slab) in each launch form, min_vis, the ids a single query's descent left in the blob, the trace stamps.
-template <bool SMALL, class TILE>
-__device__ __forceinline__ void leaf_tiles16_walk(const DataView &dv, const ScreenSearch &ss, const uint32_t *__restrict__ nns,
+// (QUERIES: what TILE reads its queries from — the screen's copies, or the 1-bit leaves of BqTile)
+template <bool SMALL, class TILE, class QUERIES = ScreenSearch>
+__device__ __forceinline__ void leaf_tiles16_walk(const DataView &dv, const QUERIES &ss, const uint32_t *__restrict__ nns,
                                                   const Visit *__restrict__ sorted, const TileUnit *__restrict__ units,
                                                   const uint32_t *__restrict__ n_units_p, float *__restrict__ dist, uint32_t stride,
                                                   uint32_t *err, uint32_t min_vis, const uint32_t *__restrict__ blob, uint32_t speculate,
@@ -3024,6 +3025,132 @@ template <bool SMALL>
 static auto tiles16_kernel(int metric) -> decltype(&k_leaf_tiles16<SMALL>) {
     return metric == AH_EUCLIDEAN ? k_leaf_tiles_diff16<AH_EUCLIDEAN, SMALL>
            : metric == AH_MANHATTAN ? k_leaf_tiles_diff16<AH_MANHATTAN, SMALL> : k_leaf_tiles16<SMALL>;
+}
+
+// ---- the leaf tiles of the three 1-bit metrics (AH_SEARCH_TILES_BQ) -----------------------------------------------------
+// A 1-bit distance is an exact integer function of a popcount, so these tiles write the DISTANCE itself where k_leaf_tiles
+// writes it — nothing is screened, k_search_select picks the top `count` as for the f32 tiles — and the bits are those of the
+// sorted path (k_batch_* in batch.hip) because the epilogue below is theirs, word for word.
+// A third tile type of leaf_tiles16_walk, not a walker of its own: which block takes which (unit, slab) in the launch forms
+// (item list, small 2-D, big 2-D; the plan never names the flat one: search_plan.h) and the kept ids of the unit's first visit
+// under a filter know nothing of the row format.  Only the R x Q x QO x KF shapes of the walk mean nothing here (the tile
+// takes all of a unit's visits at once, whatever their number), so BqTile::run ignores them.
+//
+// The work split.  A row is `pitch / 2` pieces of 16 bytes (pitch = round_up(words, 2): the last word of an odd `words` is
+// the row's own padding, inside the row, zero in rows and query leaves alike and counted by every other 1-bit kernel here —
+// so it is counted, not masked: masking could only differ from the sorted path).  G = 1, 2, 4 or 8 adjacent lanes own one row,
+// the smallest power of two that holds the row's pieces, so one request of a wave reads 64 / G rows' pieces side by side; a
+// row of more than 8 pieces (512 dimensions) takes ceil(pieces / 8) passes.  One-piece rows (up to 128 dimensions) therefore
+// have one lane per row and no reduction.  The unit's <= 16 query rows are gathered once per (unit, slab) into LDS; a lane
+// keeps its piece in registers and XORs / popcounts it against the same piece of every query (lanes with the same piece
+// index read the same LDS address: a broadcast; the G pieces of a group are adjacent 16-byte reads), one uint32 count per
+// visit in registers, summed over the group by DPP (no LDS or global atomics).  256 / G rows per round of a block.
+struct BqQueries {
+    const uint8_t *qvecs;  // the query leaves as the descent read them: `pitch` words each at q * qstride
+    uint64_t qstride;
+    const float *qhdrs;    // 2 floats per query; BQ-cosine: [0] = the stored norm
+};
+// dynamic LDS of a block: the 16 candidate-buffer offsets (8 B) and query norms (4 B) of the unit's visits, then their rows
+__host__ __device__ constexpr size_t bq_tile_lds_bytes(uint32_t pitch) { return 192u + (size_t)kUnitVisits * pitch * 8; }
+static_assert(bq_tile_lds_bytes(kBqTileMaxWords) <= (16u << 10) + 192u, "kBqTileMaxWords: 16 KiB of query rows per block (search_plan.h)");
+
+template <int CTRL>
+__device__ __forceinline__ uint32_t dpp_u32(uint32_t v) {
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xF, 0xF, false);
+}
+// the distance `Distance::built_distance` gives for a Hamming count (k_distances_bq, k_batch_distances: the same lines)
+template <int METRIC>
+__device__ __forceinline__ float bq_distance_of_hamming(uint32_t ham, uint32_t words, float qn, float xn) {
+    if (METRIC == AH_BQ_EUCLIDEAN) return (float)(ham * 4u);
+    if (METRIC == AH_BQ_MANHATTAN) return (float)(ham * 2u);
+    return bq_cosine_from_dot((float)bq_dot_from_hamming(ham, words), qn, xn);
+}
+
+template <int METRIC>
+__device__ __forceinline__ void leaf_tile_bq(const BqQueries &bq, const DataView &dv, const uint32_t *__restrict__ leaf_ids, uint32_t row_begin,
+                                             uint32_t n_rows, const Visit *__restrict__ vis, uint32_t n_vis, float *__restrict__ dist, uint32_t stride,
+                                             uint32_t *err, const Visit *only_visit) {
+    extern __shared__ uint4 s_bq_tile[];
+    uint64_t *s_out = reinterpret_cast<uint64_t *>(s_bq_tile);          // [16] query t's first slot of this leaf in `dist`
+    float *s_qn = reinterpret_cast<float *>(s_bq_tile) + 2 * kUnitVisits;  // [16] its stored norm (BQ-cosine)
+    uint4 *s_q = s_bq_tile + 12;                                        // [n_vis][pieces]
+    const uint32_t tid = threadIdx.x, pieces = dv.pitch >> 1;
+    n_vis = min(n_vis, kUnitVisits);
+    __syncthreads();  // (the block's previous (unit, slab) has been read to its end)
+    if (tid < n_vis) {
+        const Visit v = only_visit ? *only_visit : vis[tid];
+        s_out[tid] = (uint64_t)v.q * stride + v.pos;
+        s_qn[tid] = METRIC == AH_BQ_COSINE ? bq.qhdrs[2 * (uint64_t)v.q] : 0.0f;
+    }
+    for (uint32_t i = tid; i < n_vis * pieces; i += blockDim.x) {
+        const uint32_t t = i / pieces, p = i - t * pieces;
+        const uint32_t q = only_visit ? only_visit->q : vis[t].q;
+        s_q[i] = reinterpret_cast<const uint4 *>(bq.qvecs + (uint64_t)q * bq.qstride)[p];
+    }
+    __syncthreads();
+    // (block-uniform: the group size and the passes of a row)
+    const uint32_t g_log = pieces > 4 ? 3u : pieces > 2 ? 2u : pieces == 2 ? 1u : 0u, G = 1u << g_log;
+    const uint32_t j = tid & (G - 1u), passes = (pieces + G - 1u) >> g_log;
+    for (uint32_t r = row_begin + (tid >> g_log); r < n_rows; r += blockDim.x >> g_log) {  // (uniform within a group)
+        const uint64_t row = row_of_id(dv, leaf_ids[r]);
+        const bool missing = row == ~0ull;
+        const uint4 *rp = reinterpret_cast<const uint4 *>(dv.rows_bq + (missing ? 0ull : row) * dv.pitch);
+        const float xn = METRIC == AH_BQ_COSINE && !missing ? dv.headers[row] : 0.0f;
+        uint32_t ham[kUnitVisits];
+#pragma unroll
+        for (uint32_t t = 0; t < kUnitVisits; t++) ham[t] = 0u;
+        for (uint32_t pass = 0; pass < passes; pass++) {
+            // (the lanes of a group past the row's last piece re-read piece 0 and add nothing)
+            const bool active = (pass << g_log) + j < pieces;
+            const uint32_t p = active ? (pass << g_log) + j : 0u;
+            const uint4 x = rp[p];
+#pragma unroll
+            for (uint32_t t = 0; t < kUnitVisits; t++) {
+                if (t < n_vis) {  // (block-uniform)
+                    const uint4 y = s_q[t * pieces + p];
+                    const uint32_t c = (uint32_t)(__popc(x.x ^ y.x) + __popc(x.y ^ y.y) + __popc(x.z ^ y.z) + __popc(x.w ^ y.w));
+                    ham[t] += active ? c : 0u;
+                }
+            }
+        }
+        if (missing && j == 0) atomicOr(err, 1u);
+#pragma unroll
+        for (uint32_t t = 0; t < kUnitVisits; t++) {
+            if (t >= n_vis) continue;
+            uint32_t h = ham[t];
+            if (g_log >= 1u) h += dpp_u32<0xB1>(h);   // lane ^ 1
+            if (g_log >= 2u) h += dpp_u32<0x4E>(h);   // lane ^ 2
+            if (g_log >= 3u) h += dpp_u32<0x141>(h);  // + the other quad of the octet (half-row mirror)
+            if (j == 0) dist[s_out[t] + r] = missing ? __uint_as_float(0x7FC00000u) : bq_distance_of_hamming<METRIC>(h, dv.words, s_qn[t], xn);
+        }
+    }
+}
+template <int METRIC>
+struct BqTile {
+    template <int R, int Q, int QO, int KF = 1>
+    static __device__ __forceinline__ void run(const BqQueries &bq, const DataView &dv, const uint32_t *__restrict__ leaf_ids, uint32_t row_begin,
+                                               uint32_t n_rows, const Visit *__restrict__ vis, uint32_t n_vis, float *__restrict__ dist, uint32_t stride,
+                                               uint32_t *err, uint32_t *__restrict__ copy_ids_to = nullptr, const Visit *only_visit = nullptr) {
+        // (copy_ids_to is never set here: no descent the plan names for a 1-bit sub-batch leaves its ids in the blob)
+        leaf_tile_bq<METRIC>(bq, dv, leaf_ids, row_begin, n_rows, vis, n_vis, dist, stride, err, only_visit);
+    }
+};
+// k_leaf_tiles16's walk, launch forms and arguments with that tile; BqQueries in the place of the screen.
+template <int METRIC, bool SMALL>
+__global__ __launch_bounds__(256) AH_NO_PACKED_F32 void k_leaf_tiles_bq(DataView dv, BqQueries bq, const uint32_t *__restrict__ nns,
+                                                                        const Visit *__restrict__ sorted, const TileUnit *__restrict__ units,
+                                                                        const uint32_t *__restrict__ n_units_p, float *__restrict__ dist,
+                                                                        uint32_t stride, uint32_t *err, uint32_t min_vis = 0,
+                                                                        const uint32_t *__restrict__ blob = nullptr, uint32_t speculate = 0,
+                                                                        uint32_t *__restrict__ trace = nullptr, uint32_t flat = 0,
+                                                                        const uint32_t *__restrict__ items = nullptr, uint32_t per_query = 0) {
+    leaf_tiles16_walk<SMALL, BqTile<METRIC>, BqQueries>(dv, bq, nns, sorted, units, n_units_p, dist, stride, err, min_vis, blob, speculate, trace,
+                                                        flat, items, per_query);
+}
+template <bool SMALL>
+static auto tiles_bq_kernel(int metric) -> decltype(&k_leaf_tiles_bq<AH_BQ_EUCLIDEAN, SMALL>) {
+    return metric == AH_BQ_EUCLIDEAN ? k_leaf_tiles_bq<AH_BQ_EUCLIDEAN, SMALL>
+           : metric == AH_BQ_MANHATTAN ? k_leaf_tiles_bq<AH_BQ_MANHATTAN, SMALL> : k_leaf_tiles_bq<AH_BQ_COSINE, SMALL>;
 }
 
 // bounds of the reference distance of one candidate from its screen value (see above)
@@ -4214,6 +4341,7 @@ static SearchKnobs search_knobs() {
     kn.single_fused = tun(TUN_SEARCH_SINGLE_FUSED) != 0, kn.multi_ids_by_tiles = tun(TUN_SEARCH_MULTI_IDS_BY_TILES) != 0;
     kn.multi_trace = tun(TUN_SEARCH_MULTI_TRACE) != 0, kn.fused_flag = tun(TUN_SEARCH_FUSED_FLAG) != 0, kn.spin_wait = tun(TUN_SEARCH_SPIN_WAIT) != 0;
     kn.wave = tun(TUN_SEARCH_WAVE) != 0, kn.debug = tun(TUN_DEBUG) != 0, kn.screen_diff = tun(TUN_SEARCH_SCREEN_DIFF) != 0;
+    kn.tiles_bq = tun(TUN_SEARCH_TILES_BQ) != 0;
     kn.small_tiles_max_queries = tun(TUN_SEARCH_SMALL_TILES_MAX_QUERIES), kn.screen8_min_queries = tun(TUN_SEARCH_SCREEN8_MIN_QUERIES);
     kn.small_units_max_queries = tun(TUN_SEARCH_SMALL_UNITS_MAX_QUERIES), kn.block_max_queries = tun(TUN_SEARCH_BLOCK_MAX_QUERIES);
     kn.multi_trees_per_block = tun(TUN_SEARCH_MULTI_TREES_PER_BLOCK), kn.multi_max_queries = tun(TUN_SEARCH_MULTI_MAX_QUERIES);
@@ -4490,6 +4618,27 @@ static int launch_tiles(ChunkCtx &c) {
     const dim3 grid(plan.tile_grid_x, plan.tile_grid_y);
     uint32_t *const d_n_units = c.d_n_units();
     uint32_t *tile_trace = c.multi_trace() ? &c.multi_trace()->tile_trace[0] : nullptr;
+    // the four launch forms of leaf_tiles16_walk, whatever its tile: `small` / `big` are its two kernels, `queries` what the
+    // tile reads its queries from (the screen's copies; the leaves themselves for the 1-bit tiles), `lds` its dynamic LDS
+    auto walk_launch = [&](auto small, auto big, const auto &queries, size_t lds) {
+        switch (plan.tile_launch) {
+        case TileLaunch::Flat:
+            hipLaunchKernelGGL(small, grid, dim3(256), lds, s, dv, queries, b.d_nns, b.d_sorted, b.d_units, nq == 1 ? d_n_units : b.d_unit_counts,
+                               b.d_dist, nns_stride, b.d_err, 0u, c.ix->d_desc, 0u, tile_trace, 1u, (const uint32_t *)nullptr, plan.units_per_query);
+            break;
+        case TileLaunch::ItemList:
+            hipLaunchKernelGGL(small, grid, dim3(256), lds, s, dv, queries, b.d_nns, b.d_sorted, b.d_units, d_n_units, b.d_dist, nns_stride, b.d_err,
+                               0u, c.ix->d_desc, 0u, tile_trace, 0u, b.d_items, 0u);
+            break;
+        case TileLaunch::Small2D:
+            hipLaunchKernelGGL(small, grid, dim3(256), lds, s, dv, queries, b.d_nns, b.d_sorted, b.d_units, d_n_units, b.d_dist, nns_stride, b.d_err,
+                               0u, c.ix->d_desc, plan.visit_cap >= plan.tile_grid_x ? 1u : 0u, tile_trace, 0u, (const uint32_t *)nullptr, 0u);
+            break;
+        default:  // Big2D
+            hipLaunchKernelGGL(big, grid, dim3(256), lds, s, dv, queries, b.d_nns, b.d_sorted, b.d_units, d_n_units, b.d_dist, nns_stride, b.d_err, 0u,
+                               (const uint32_t *)nullptr, 0u, (uint32_t *)nullptr, 0u, (const uint32_t *)nullptr, 0u);
+        }
+    };
     switch (plan.tile_launch) {
     case TileLaunch::Tiles8And16:
         // (the queries' int8 digits here, behind the descent: a small submission's query leaves are prepared BY its descent)
@@ -4500,22 +4649,14 @@ static int launch_tiles(ChunkCtx &c) {
                            b.d_err, plan.max_vis8 + 1);
         break;
     case TileLaunch::Flat:
-        hipLaunchKernelGGL(tiles16_kernel<true>(ds->metric), grid, dim3(256), 0, s, dv, ss, b.d_nns, b.d_sorted, b.d_units,
-                           nq == 1 ? d_n_units : b.d_unit_counts, b.d_dist, nns_stride, b.d_err, 0u, c.ix->d_desc, 0u, tile_trace, 1u,
-                           (const uint32_t *)nullptr, plan.units_per_query);
-        break;
     case TileLaunch::ItemList:
-        hipLaunchKernelGGL(tiles16_kernel<true>(ds->metric), grid, dim3(256), 0, s, dv, ss, b.d_nns, b.d_sorted, b.d_units, d_n_units, b.d_dist,
-                           nns_stride, b.d_err, 0u, c.ix->d_desc, 0u, tile_trace, 0u, b.d_items, 0u);
-        break;
     case TileLaunch::Small2D:
-        hipLaunchKernelGGL(tiles16_kernel<true>(ds->metric), grid, dim3(256), 0, s, dv, ss, b.d_nns, b.d_sorted, b.d_units, d_n_units, b.d_dist,
-                           nns_stride, b.d_err, 0u, c.ix->d_desc, plan.visit_cap >= plan.tile_grid_x ? 1u : 0u, tile_trace, 0u,
-                           (const uint32_t *)nullptr, 0u);
-        break;
     case TileLaunch::Big2D:
-        hipLaunchKernelGGL(tiles16_kernel<false>(ds->metric), grid, dim3(256), 0, s, dv, ss, b.d_nns, b.d_sorted, b.d_units, d_n_units, b.d_dist,
-                           nns_stride, b.d_err, 0u, (const uint32_t *)nullptr, 0u, (uint32_t *)nullptr, 0u, (const uint32_t *)nullptr, 0u);
+        if (plan.tiles_bq)  // (AH_SEARCH_TILES_BQ: the distances themselves, from the 1-bit rows and the query leaves)
+            walk_launch(tiles_bq_kernel<true>(ds->metric), tiles_bq_kernel<false>(ds->metric), BqQueries{b.d_qvecs, qstride, b.d_qhdrs},
+                        bq_tile_lds_bytes(ds->pitch));
+        else
+            walk_launch(tiles16_kernel<true>(ds->metric), tiles16_kernel<false>(ds->metric), ss, 0);
         break;
     default:
         AH_TRY(with_tile_metric(ds->metric, [&](auto m) -> int {

@@ -25,6 +25,10 @@ constexpr uint32_t kSmallVisits = 2048;          // visits one call of k_units_s
 constexpr uint32_t kHashMaxCandidates = 24576;   // candidates of a query k_flag_duplicates_hash holds
 constexpr uint32_t kSelectCap = 1024;            // keys the selections behind the tiles hold
 constexpr uint32_t kStatusWords = 16;            // the per-chunk status block (SS_WORDS)
+// 64-bit words of a 1-bit row k_leaf_tiles_bq takes (8192 dimensions).  A block keeps the rows of its unit's 16 queries in
+// LDS: 16 x 128 x 8 B = 16 KiB (beside 192 B of per-visit slots and norms; the walker itself holds nothing there), so the
+// eight blocks of 256 threads that fill a compute unit's 32 waves hold 128 KiB of its 160 KiB
+constexpr uint32_t kBqTileMaxWords = 128;
 
 // The tunables (common.h) the sub-batch path reads, filled once per API call (search.hip: search_knobs).
 struct SearchKnobs {
@@ -33,6 +37,7 @@ struct SearchKnobs {
     bool screen_diff;  // AH_SEARCH_SCREEN_DIFF: Euclidean / Manhattan sub-batches through the tiles on the difference screen
     long long small_tiles_max_queries, screen8_min_queries, small_units_max_queries, block_max_queries, multi_trees_per_block,
         multi_max_queries, screen8_max_visits;
+    bool tiles_bq;  // AH_SEARCH_TILES_BQ: the sub-batches of the three 1-bit metrics through the tiles (k_leaf_tiles_bq)
 };
 
 // One sub-batch as the plan sees it.
@@ -99,6 +104,7 @@ struct ChunkPlan {
     uint64_t sel_lds = 0, fused_lds = 0;
     Flagger flagger = Flagger::None;
     uint32_t max_vis8 = 0;
+    bool tiles_bq = false;  // the tile launch is k_leaf_tiles_bq: the exact distances of 1-bit rows, nothing screened
 };
 
 // The descent runs one wave (or block) per query: AH_SEARCH_WAVE, a query leaf of at most 32 KiB (it is kept in LDS), and
@@ -132,15 +138,22 @@ inline ChunkPlan plan_chunk(const ChunkShape &z, const SearchKnobs &kn) {
     // candidates) of them, so a larger count could only do the whole tile pass, overflow and be redone — after an int8 pass and
     // its binary16 retry where that stage is on, each noted as a failure of the int8 stage in its window of 64 sub-batches.
     // Unless a query cannot have more than kSelectCap candidates at all: a count meant as "everything" under a small search_k)
+    // (AH_SEARCH_TILES_BQ, the 1-bit metrics: a row is whole 64-bit words from one dimension on, so instead of the f32 tiles'
+    // dims >= 32 the width must fit the LDS of k_leaf_tiles_bq)
+    const bool bq_wanted = kn.tiles_bq && z.metric >= AH_BQ_EUCLIDEAN;
+    const bool width_fits = bq_wanted ? (z.dims + 63u) / 64u <= kBqTileMaxWords : z.dims >= 32;
     const bool tiles_fit = !z.mixed && kn.tiles && (p.bitmap_fits || p.hash_fits) && !p.big_k && (k <= kSelectCap || z.nns_stride <= kSelectCap) &&
-                           z.dims >= 32 && z.max_desc <= 65535u * kTileSlab;
+                           width_fits && z.max_desc <= 65535u * kTileSlab;
     // certified top-k screen of the tile re-rank: the binary16 shadow of the rows must exist (ah_index_create makes it).
     // Cosine / DotProduct by the dot product of the copies; Euclidean / Manhattan by their difference (k_leaf_tiles_diff16),
     // when AH_SEARCH_SCREEN_DIFF asks for it and the index has not switched it off — never with an int8 stage
     const bool screen_fit = tiles_fit && kn.screen && z.screen_ready;
     const bool diff_screened = screen_fit && (z.metric == AH_EUCLIDEAN || z.metric == AH_MANHATTAN) && kn.screen_diff && !z.search_diff_off;
     // (Manhattan's reference distance is a sequential sum: no f32 tile — it takes the tiles only behind the screen)
-    p.tiles = tiles_fit && (z.metric == AH_EUCLIDEAN || z.metric == AH_COSINE || z.metric == AH_DOT_PRODUCT || diff_screened);
+    // (the 1-bit distances are exact integers of a popcount: their tiles need no screen, so screened, screened8, fuse_prepare
+    // and fused_flag stay off and no binary16 or int8 copy is made or read)
+    p.tiles_bq = tiles_fit && bq_wanted;
+    p.tiles = tiles_fit && (z.metric == AH_EUCLIDEAN || z.metric == AH_COSINE || z.metric == AH_DOT_PRODUCT || diff_screened || p.tiles_bq);
     p.visit_cap = (uint32_t)std::min<uint64_t>((uint64_t)nq * z.nns_stride, 2u << 20);
     p.n_leaf_sums = (z.n_nodes + kLeafScanItems - 1) / kLeafScanItems;
     p.screened = screen_fit && (z.metric == AH_COSINE || z.metric == AH_DOT_PRODUCT || diff_screened);
@@ -173,7 +186,11 @@ inline ChunkPlan plan_chunk(const ChunkShape &z, const SearchKnobs &kn) {
         block_fits = est_leaves / std::max(1u, std::min(z.n_trees, 32u)) <= 8.0;
         small_units_fit = (double)nq * est_leaves <= 0.8 * kSmallVisits;
     }
-    p.block_ok = block_fits && (long long)nq <= kn.block_max_queries;
+    // (tiles_bq: never the block / multi descent.  On the tile path it is the last pass, and equal keys of two octets across the
+    // cut — rare for f32 margins, the rule for 1-bit ones, which are small integers — make it give the whole sub-batch up to
+    // the sorted path (measured: 10 of 24 queries at 200 dimensions).  The wave descents hand such queries to k_descend, which
+    // appends their visits.  With it go own_units, single_fused, multi, ids_by_tiles and the Flat launch, which need that pass)
+    p.block_ok = block_fits && (long long)nq <= kn.block_max_queries && !p.tiles_bq;
     // (a small submission on the leaf-tile path makes the binary16 copies of its queries in the launch that places its visits)
     p.small_units = p.tiles && small_units_fit && (long long)nq <= kn.small_units_max_queries;
     // a query pops about 1 / (kept share) as many nodes under a filter: start with the big queues (one query per CU
@@ -192,7 +209,9 @@ inline ChunkPlan plan_chunk(const ChunkShape &z, const SearchKnobs &kn) {
     const unsigned tile_slabs = std::max(1u, (z.max_desc + kTileSlab - 1) / kTileSlab);
     const unsigned small_slabs = std::max(1u, (z.max_desc + kTileSmallSlab - 1) / kTileSmallSlab);
     // (never with the int8 stage: that one starts past AH_SEARCH_SMALL_TILES_MAX_QUERIES queries)
-    p.small_tiles = p.screened && !p.screened8 && (long long)nq <= kn.small_tiles_max_queries && small_slabs <= 65535u;
+    // (tiles_bq: small_units, items_cap and the small tiles hold for it — k_units_small knows no metric and makes the binary16
+    // copies only when screened; what needs the block descent is off with block_ok above)
+    p.small_tiles = (p.screened || p.tiles_bq) && !p.screened8 && (long long)nq <= kn.small_tiles_max_queries && small_slabs <= 65535u;
     if (!z.wave_descent)
         p.descent = Descent::Octet;
     else if (p.small_first && p.block_ok) {
@@ -226,7 +245,7 @@ inline ChunkPlan plan_chunk(const ChunkShape &z, const SearchKnobs &kn) {
         // many queries share on the binary16 copy as before; the selection takes every candidate's bound from its own stage
         p.tile_launch = TileLaunch::Tiles8And16, p.tile_grid_x = 2048, p.tile_grid_y = tile_slabs;
         p.max_vis8 = (uint32_t)std::max<long long>(1, kn.screen8_max_visits);
-    } else if (!p.screened) {
+    } else if (!p.screened && !p.tiles_bq) {
         p.tile_launch = TileLaunch::F32, p.tile_grid_x = 2048, p.tile_grid_y = tile_slabs;
     } else if (p.small_tiles && p.single_fused && (nq == 1 || p.units_per_query) && p.visit_cap >= 128u && kn.flat_tiles) {
         // (queries whose units came out of their descent: a flat list of (leaf, slab) items, see the kernel)
