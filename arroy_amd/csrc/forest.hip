@@ -774,8 +774,17 @@ __global__ __launch_bounds__(256) void k_stats_max(const float4 *__restrict__ st
 // The sign of a cosine margin does not depend on s_r > 0, so for Cosine the test runs in units of s_r with the
 // DATASET-WIDE maxima of |q|, |y/s_r - q|, |x|/s_r (all dimensionless, the same for every row up to a few percent): a decided
 // pair costs its 768-byte int8 row and nothing else — no per-row load at all.  Euclidean / Manhattan add the bias in real
-// units and fetch s_r (4 bytes per pair from a 40 MB array).  DotProduct has no int8 stage (its margin needs the row's header
-// anyway).  Rows that are all zero, not finite, or so small that f32 squares underflow (max|x| < 2^-40) get q = 0 and
+// units and fetch s_r (4 bytes per pair from a 40 MB array).  DotProduct (AH_SCREEN8_DOT=1; off by default: the binary16
+// stage alone, as before) fetches s_r and the row's extra dimension e_x (4 of its header's 8 bytes) beside the int8 row: the
+// reference margin is r = fl(fl_ref(<n, x>) + fl(h0 e_x)) with h0 the normal's extra dimension, the test runs on
+//   m = fl(sd + fl(h0 e_x)),  sd = fl(S s_r),
+//   E = E_dot s_r (1 + 1e-6) + 1.2e-7 |sd|, then E += 2.4e-7 (2 |h0 e_x| + |sd| + E)
+// — E_dot s_r bounds |S s_r - fl_ref(<n, x>)| as above, 1.2e-7 |sd| the rounding of sd; fl(h0 e_x) is the SAME f32 product on
+// both sides, so what remains is one rounding of each sum, of values bounded by |sd| + |p| and |sd| + E + |p|: 2^-24 of
+// their total is below the last term (the DotProduct branch of screen_decides, screen_device.h).  An all-zero row is stored
+// with s_r = 0 and q = 0 (k_shadow_rows8): m = fl(h0 e_x) is then the reference margin itself (fl_ref(<n, 0>) = 0) and
+// E = 4.8e-7 |h0 e_x|; against a normal that is not finite (bn = inf) E = inf 0 = NaN and the pair stays undecided.
+// Rows that are all zero, not finite, or so small that f32 squares underflow (max|x| < 2^-40) get q = 0 and
 // s_r = inf: they are never decided here.  Sides stay identical by construction; AH_SCREEN_VERIFY checks every pair at
 // every stage.  (NormalStats8, the tail of a normal's int8 record, is in forest_records.h: its size is part of a batch's sizes.)
 // ------------------------------------------------------------------------------------------------
@@ -1004,10 +1013,11 @@ __device__ __forceinline__ float screen8_octet_dot_regs(const uint4 *hi4, const 
     return octet_sum((float)(h0 + h1) + (float)(l0 + l1) * 0.00390625f);
 }
 // the decision of the int8 stage.  S = s_n x (the digits' dot products), i.e. the screen value in units of the row's scale;
-// max8 = dataset-wide {|q|, |y / s_r - q|, |x| / s_r}; s_row = the row's scale (Euclidean / Manhattan; unused for Cosine).
+// max8 = dataset-wide {|q|, |y / s_r - q|, |x| / s_r}; s_row = the row's scale (Euclidean / Manhattan / DotProduct; unused for
+// Cosine); row_extra = the row's extra dimension (DotProduct).
 template <int METRIC>
 __device__ __forceinline__ bool screen8_decides(float S, float s_row, const float4 max8, const NormalStats8 ns, float gamma_r,
-                                                uint32_t &side) {
+                                                uint32_t &side, float row_extra = 0.0f) {
     // g8 = 2e-6: the conversions and sums of the lane totals (each exact below 2^24) and the scale product
     float e = ns.bn * max8.x + ns.cn * max8.y + 2.0e-6f * (ns.an * max8.x) + gamma_r * (ns.cn0 * max8.z);
     float m = S;
@@ -1018,6 +1028,14 @@ __device__ __forceinline__ bool screen8_decides(float S, float s_row, const floa
         e = e * s_row * 1.000001f + 1.2e-7f * fabsf(sd);
         m = ns.extra + sd;
         e += 2.4e-7f * (fabsf(ns.extra) + fabsf(sd) + e);
+    } else if (METRIC == AH_DOT_PRODUCT) {
+        // real units likewise, then r = fl(fl_ref(dot) + fl(h0 e_x)) as in screen_decides (ns.extra = h0, the f32 the reference
+        // multiplies: the product is the reference's own).  An all-zero row has s_row = 0: m = p, e = the roundings of p
+        const float sd = S * s_row;
+        const float p = ns.extra * row_extra;
+        e = e * s_row * 1.000001f + 1.2e-7f * fabsf(sd);
+        m = sd + p;
+        e += 2.4e-7f * (2.0f * fabsf(p) + fabsf(sd) + e);
     }
     e = e * 1.002f + 1e-30f;
     side = (__float_as_uint(m) >> 31) ^ 1u;
@@ -1098,24 +1116,25 @@ __device__ __forceinline__ float screen_octet_dot(const uint4 *a4, const uint4 *
 // PRE > 0 (int8 rows of at most PRE 128-byte steps): the int8 chunks of the NEXT item of an octet are requested before the
 // current item is evaluated, and its row index one item earlier still — an item otherwise costs two dependent memory round
 // trips (perm -> row) with nothing else in flight on the octet.
-template <int METRIC, int PRE>
-__global__ __launch_bounds__(kBlock) void k_forest_screen_node(DataView dv, ScreenView sv, FNode *nodes,
-                                                               const FTile *__restrict__ tiles, uint32_t n_tiles,
-                                                               const uint32_t *__restrict__ perm,
-                                                               const uint8_t *__restrict__ normals, uint64_t nstride,
-                                                               uint64_t hdr_off, const uint8_t *__restrict__ shadow,
-                                                               uint64_t hstride, const uint8_t *__restrict__ shadow8,
-                                                               uint64_t stride8, uint64_t *__restrict__ masks,
-                                                               uint32_t *__restrict__ tile_left,
-                                                               const AbortFlags abort_flag,
-                                                               ScreenCounters *__restrict__ counters, uint32_t verify) {
+// DOT8 (DotProduct only, k_forest_screen_node_dot8): the int8 stages for DotProduct.  Its decision needs two words of the row
+// beside the int8 bytes — the scale s_r and the extra dimension e_x of the header — which travel WITH the row: requested where
+// the row's int8 chunks are requested (PRE > 0: one item ahead, so they are no third dependent trip to memory), held in two
+// registers, and e_x serves the binary16 stage of the pairs that get that far.
+template <int METRIC, int PRE, bool DOT8>
+__device__ __forceinline__ void forest_screen_node(const DataView &dv, const ScreenView &sv, FNode *nodes, const FTile *tiles,
+                                                   uint32_t n_tiles, const uint32_t *perm, const uint8_t *normals, uint64_t nstride,
+                                                   uint64_t hdr_off, const uint8_t *shadow, uint64_t hstride, const uint8_t *shadow8,
+                                                   uint64_t stride8, uint64_t *masks, uint32_t *tile_left, const AbortFlags abort_flag,
+                                                   ScreenCounters *counters, uint32_t verify) {  // (__restrict__: on the kernels)
+    static_assert(!DOT8 || METRIC == AH_DOT_PRODUCT, "DOT8 is the DotProduct variant");
     extern __shared__ float4 s_n4[];  // [pitch floats f32 normal][hpitch halves shadow normal][2 x pitch8 bytes: the int8 digits]
     __shared__ uint32_t s_left, s_fb, s_bad, s_n8, s_d8, s_d8b;
     const float *s_n = reinterpret_cast<const float *>(s_n4);
     const uint4 *s_h4 = reinterpret_cast<const uint4 *>(s_n4 + (dv.pitch >> 2));
     const uint4 *s_q4 = s_h4 + (sv.hpitch >> 3);        // q_hi
     const uint4 *s_ql4 = s_q4 + (sv.pitch8 >> 4);        // q_lo
-    const bool stage8 = METRIC != AH_DOT_PRODUCT && sv.rows8 != nullptr && shadow8 != nullptr;  // (DotProduct needs the row's header anyway)
+    // (DotProduct without DOT8: the binary16 stage alone, whether or not the dataset has an int8 copy)
+    const bool stage8 = (METRIC != AH_DOT_PRODUCT || DOT8) && sv.rows8 != nullptr && shadow8 != nullptr;
     const uint32_t steps8 = sv.pitch8 >> 7;
     const uint32_t o = threadIdx.x >> 3, j = threadIdx.x & 7u;
     const uint32_t steps = sv.hpitch >> 6;
@@ -1154,6 +1173,7 @@ __global__ __launch_bounds__(kBlock) void k_forest_screen_node(DataView dv, Scre
         constexpr int NPRE = PRE > 0 ? PRE : 1;
         uint4 xn[NPRE];
         uint32_t row_n = 0, row_nn = 0;
+        float srow_n = 0.0f, extra_n = 0.0f;  // DOT8: s_r and e_x of the item whose chunks are in xn
         if (PRE > 0 && stage8) {
             if (o < in_tile) row_n = pp[o];
             if (o + 32 < in_tile) row_nn = pp[o + 32];
@@ -1162,6 +1182,10 @@ __global__ __launch_bounds__(kBlock) void k_forest_screen_node(DataView dv, Scre
 #pragma unroll
                 for (int u = 0; u < NPRE; u++)
                     if ((uint32_t)u < steps8) xn[u] = ld_stream_u4(r8 + u * 8);
+                if (DOT8) {
+                    srow_n = sv.scale8_rows[row_n];
+                    extra_n = dv.headers[2 * (uint64_t)row_n];
+                }
             }
         }
         for (uint32_t i = 0; i < 64; i++) {
@@ -1169,10 +1193,13 @@ __global__ __launch_bounds__(kBlock) void k_forest_screen_node(DataView dv, Scre
             if (p >= in_tile) break;
             uint64_t row;
             uint4 x[NPRE];
+            float srow_d = 0.0f, extra_d = 0.0f;  // DOT8: the current item's
             if (PRE > 0 && stage8) {
                 row = row_n;
 #pragma unroll
                 for (int u = 0; u < NPRE; u++) x[u] = xn[u];
+                srow_d = srow_n;
+                extra_d = extra_n;
                 row_n = row_nn;
                 if (p + 64 < in_tile) row_nn = pp[p + 64];
                 if (p + 32 < in_tile) {
@@ -1180,31 +1207,41 @@ __global__ __launch_bounds__(kBlock) void k_forest_screen_node(DataView dv, Scre
 #pragma unroll
                     for (int u = 0; u < NPRE; u++)
                         if ((uint32_t)u < steps8) xn[u] = ld_stream_u4(r8n + u * 8);
+                    if (DOT8) {
+                        srow_n = sv.scale8_rows[row_n];
+                        extra_n = dv.headers[2 * (uint64_t)row_n];
+                    }
                 }
             } else {
                 row = pp[p];
+                if (DOT8 && stage8) {  // requested before the row's chunks: in flight together with them
+                    srow_d = sv.scale8_rows[row];
+                    extra_d = dv.headers[2 * row];
+                }
             }
             uint32_t side = 0;
             bool decided = false;
             if (stage8) {  // first stage: the int8 copy, 768 bytes of a 768-d row; bound from the dataset-wide maxima
                 const uint4 *r8 = reinterpret_cast<const uint4 *>(sv.rows8 + row * sv.pitch8) + j;
-                const float s_row = METRIC == AH_COSINE ? 1.0f : sv.scale8_rows[row];  // a cosine margin's sign needs no scale
+                // (a cosine margin's sign needs no scale)
+                const float s_row = DOT8 ? srow_d : METRIC == AH_COSINE ? 1.0f : sv.scale8_rows[row];
                 const float u8 = PRE > 0 ? screen8_octet_dot_regs<NPRE>(s_q4 + j, s_ql4 + j, x, steps8)
                                          : screen8_octet_dot(s_q4 + j, s_ql4 + j, r8, steps8);
-                decided = screen8_decides<METRIC>(u8 * ns8.scale, s_row, sv.max8, ns8, sv.gamma_r, side);
+                decided = screen8_decides<METRIC>(u8 * ns8.scale, s_row, sv.max8, ns8, sv.gamma_r, side, extra_d);
                 met8++;
                 decided8 += decided ? 1u : 0u;
                 if (!decided && sv.rows8_lo != nullptr) {  // octet-uniform: the row's second int8 digit (768 more bytes)
                     const uint4 *r8l = reinterpret_cast<const uint4 *>(sv.rows8_lo + row * sv.pitch8) + j;
                     const float u8b = u8 + screen8_octet_dot(s_q4 + j, s_ql4 + j, r8l, steps8) * 0.00390625f;
-                    decided = screen8_decides<METRIC>(u8b * ns8.scale, s_row, sv.max8b, ns8, sv.gamma_r, side);
+                    decided = screen8_decides<METRIC>(u8b * ns8.scale, s_row, sv.max8b, ns8, sv.gamma_r, side, extra_d);
                     decided8b += decided ? 1u : 0u;
                 }
             }
             if (!decided) {  // octet-uniform: second stage, the binary16 copy
                 const uint4 *r4 = reinterpret_cast<const uint4 *>(sv.rows + row * sv.hpitch) + j;
                 const float s = screen_octet_dot(s_h4 + j, r4, steps);
-                const float row_extra = METRIC == AH_DOT_PRODUCT ? dv.headers[2 * row] : 0.0f;
+                // (DOT8: the extra dimension came with the int8 row)
+                const float row_extra = METRIC != AH_DOT_PRODUCT ? 0.0f : DOT8 && stage8 ? extra_d : dv.headers[2 * row];
                 // the bound from the dataset-wide maxima first (monotone in every stat, so it is >= the row's own bound);
                 // the row's stats only when that one cannot decide
                 decided = screen_decides<METRIC>(s, sv.max_stats, ns, row_extra, sv.gamma_s, sv.gamma_r, side);
@@ -1246,6 +1283,36 @@ __global__ __launch_bounds__(kBlock) void k_forest_screen_node(DataView dv, Scre
         if (s_d8) atomicAdd(&counters->stage8_decided, (unsigned long long)s_d8);
         if (s_d8b) atomicAdd(&counters->stage8b_decided, (unsigned long long)s_d8b);
     }
+}
+template <int METRIC, int PRE>
+__global__ __launch_bounds__(kBlock) void k_forest_screen_node(DataView dv, ScreenView sv, FNode *nodes,
+                                                               const FTile *__restrict__ tiles, uint32_t n_tiles,
+                                                               const uint32_t *__restrict__ perm,
+                                                               const uint8_t *__restrict__ normals, uint64_t nstride,
+                                                               uint64_t hdr_off, const uint8_t *__restrict__ shadow,
+                                                               uint64_t hstride, const uint8_t *__restrict__ shadow8,
+                                                               uint64_t stride8, uint64_t *__restrict__ masks,
+                                                               uint32_t *__restrict__ tile_left,
+                                                               const AbortFlags abort_flag,
+                                                               ScreenCounters *__restrict__ counters, uint32_t verify) {
+    forest_screen_node<METRIC, PRE, false>(dv, sv, nodes, tiles, n_tiles, perm, normals, nstride, hdr_off, shadow, hstride, shadow8,
+                                           stride8, masks, tile_left, abort_flag, counters, verify);
+}
+// ... and with the int8 stages for DotProduct (AH_SCREEN8_DOT): a kernel of its own, so that the DotProduct builds of the
+// default setting run the kernel they ran before.
+template <int PRE>
+__global__ __launch_bounds__(kBlock) AH_NO_PACKED_F32 void k_forest_screen_node_dot8(DataView dv, ScreenView sv, FNode *nodes,
+                                                                                    const FTile *__restrict__ tiles, uint32_t n_tiles,
+                                                                                    const uint32_t *__restrict__ perm,
+                                                                                    const uint8_t *__restrict__ normals, uint64_t nstride,
+                                                                                    uint64_t hdr_off, const uint8_t *__restrict__ shadow,
+                                                                                    uint64_t hstride, const uint8_t *__restrict__ shadow8,
+                                                                                    uint64_t stride8, uint64_t *__restrict__ masks,
+                                                                                    uint32_t *__restrict__ tile_left,
+                                                                                    const AbortFlags abort_flag,
+                                                                                    ScreenCounters *__restrict__ counters, uint32_t verify) {
+    forest_screen_node<AH_DOT_PRODUCT, PRE, true>(dv, sv, nodes, tiles, n_tiles, perm, normals, nstride, hdr_off, shadow, hstride,
+                                                  shadow8, stride8, masks, tile_left, abort_flag, counters, verify);
 }
 
 // exact margin of (row, normal record in global memory) by one octet: the arithmetic of k_forest_margin_rows
@@ -2079,13 +2146,17 @@ bool ensure_screen(ah_dataset *ds, hipStream_t s, bool want8, bool retry_failed)
         ds->screen_ready.store(true, std::memory_order_release);  // readers without `mu` look at this flag only
     }
     const long long tun8 = tun(TUN_SCREEN8);
-    if (want8 && tun8 != 0 && ds->metric != AH_DOT_PRODUCT && !ds->d_rows_i8 && (!ds->screen8_decided || tun8 == 1))
+    // (a DotProduct build reads the int8 copy only with AH_SCREEN8_DOT; a copy the search made without the rows' second digit is
+    // used as it is: stage 1 is then the binary16 row)
+    const bool build8 = ds->metric != AH_DOT_PRODUCT || tun(TUN_SCREEN8_DOT) != 0;
+    if (want8 && tun8 != 0 && build8 && !ds->d_rows_i8 && (!ds->screen8_decided || tun8 == 1))
         (void)ensure_screen8(ds, s, tun8 == 1);
     return true;
 }
 // The int8 copy for the SEARCH side (round 6: the first stage of the certified top-k screen of ah_search_batch /
 // ah_rerank_batch): the copy the node-major levels of the build use — made here for DotProduct as well, whose build has no use
-// for it (and therefore without the second digit of the rows, which only the build's stage 1 reads).
+// for it unless AH_SCREEN8_DOT is set (and therefore, without it, without the second digit of the rows, which only the build's
+// stage 1 reads).
 bool ensure_screen8_search(ah_dataset *ds, hipStream_t s) {
     if (ds->screen8_ready.load(std::memory_order_acquire)) return true;
     std::lock_guard<std::mutex> lk(ds->mu);
@@ -2093,7 +2164,7 @@ bool ensure_screen8_search(ah_dataset *ds, hipStream_t s) {
     if (ds->d_rows_i8) return ds->screen8_ready.load(std::memory_order_acquire);
     const long long tun8 = tun(TUN_SCREEN8);
     if (tun8 == 0 || (ds->screen8_decided && tun8 != 1)) return false;  // found useless (or unavailable) before
-    return ensure_screen8(ds, s, tun8 == 1, ds->metric != AH_DOT_PRODUCT);
+    return ensure_screen8(ds, s, tun8 == 1, ds->metric != AH_DOT_PRODUCT || tun(TUN_SCREEN8_DOT) != 0);
 }
 }  // namespace ah
 // The int8 copy (rows, one scale per row, one power of two per dimension).  Kept only when it will decide most pairs: the
@@ -2872,8 +2943,10 @@ int launch_rows_f32(const LevelBufs &b, const LevelPlan &plan, uint64_t rec_byte
 }
 
 // The node-major pass of an attempt on a persistent grid: binary-quantised, screened (`node_pre`: the pipelined variant of
-// the int8 stage) or f32.  Very long vectors need more dynamic LDS than the default limit.
-int launch_node_major(const LevelBufs &b, bool bq, bool screen, bool screen8, bool node_pre, unsigned node_grid, ah_build_stats &st) {
+// the int8 stage; `dot8`: DotProduct with the int8 stages, k_forest_screen_node_dot8) or f32.  Very long vectors need more
+// dynamic LDS than the default limit.
+int launch_node_major(const LevelBufs &b, bool bq, bool screen, bool screen8, bool node_pre, bool dot8, unsigned node_grid,
+                      ah_build_stats &st) {
     if (bq) {
         hipLaunchKernelGGL(k_forest_margin_bq, dim3(node_grid), dim3(kBlock), b.dv.pitch * 8, b.s, b.dv, b.nodes, b.tiles, b.n_tiles,
                            b.perm, b.N, b.normals, b.nstride, b.hdr_off, b.masks, b.tile_left, b.abort_gated);
@@ -2890,9 +2963,21 @@ int launch_node_major(const LevelBufs &b, bool bq, bool screen, bool screen8, bo
                                b.tile_left, b.abort_gated, b.counters, b.verify);
             return AH_OK;
         };
-        AH_TRY(with_metric(b.metric, [&](auto m) -> int {
-            return node_pre ? launch(m, std::integral_constant<int, 6>{}) : launch(m, std::integral_constant<int, 0>{});
-        }));
+        auto launch_dot8 = [&](auto pre) -> int {
+            constexpr int PRE = decltype(pre)::value;
+            AH_TRY(lds_opt_in(reinterpret_cast<const void *>(k_forest_screen_node_dot8<PRE>), b.device, sh));
+            hipLaunchKernelGGL((k_forest_screen_node_dot8<PRE>), dim3(node_grid), dim3(kBlock), sh, b.s, b.dv, b.sv, b.nodes, b.tiles,
+                               b.n_tiles, b.perm, b.normals, b.nstride, b.hdr_off, b.shadow, b.hstride, b.shadow8, b.stride8, b.masks,
+                               b.tile_left, b.abort_gated, b.counters, b.verify);
+            return AH_OK;
+        };
+        if (dot8) {
+            AH_TRY(node_pre ? launch_dot8(std::integral_constant<int, 6>{}) : launch_dot8(std::integral_constant<int, 0>{}));
+        } else {
+            AH_TRY(with_metric(b.metric, [&](auto m) -> int {
+                return node_pre ? launch(m, std::integral_constant<int, 6>{}) : launch(m, std::integral_constant<int, 0>{});
+            }));
+        }
         st.margin_mode_launches[MM_NODE]++;
         st.screened_launches++;
         return AH_OK;
@@ -2930,6 +3015,7 @@ LevelKnobs read_level_knobs() {
     k.mask_bits = tun(TUN_MASK_BITS);
     k.exact_wide = tun(TUN_EXACT_WIDE) != 0;
     k.node_prefetch = tun(TUN_NODE_PREFETCH) != 0;
+    k.screen8_dot = tun(TUN_SCREEN8_DOT) != 0;
     k.tail_groups = (uint32_t)std::min<long long>(32, std::max<long long>(0, tun(TUN_TAIL_GROUPS)));
     k.tail_node_items = (double)std::max<long long>(1, tun(TUN_TAIL_NODE_ITEMS));
     k.tail_min_items = (uint64_t)std::max<long long>(0, tun(TUN_TAIL_MIN_MB)) * (1u << 20) / 4;
@@ -3597,8 +3683,9 @@ struct BatchBuild {
                 if (screen) forest->stats.screened_launches += passes;
             } else {
                 // rows of at most six 128-byte int8 steps (768 dimensions): the pipelined variant of the int8 stage
-                const bool node_pre = screen8 && ds->metric != AH_DOT_PRODUCT && sv.pitch8 <= 6 * 128 && knobs.node_prefetch;
-                AH_TRY(launch_node_major(lb, bq, screen, screen8, node_pre, node_grid, forest->stats));
+                const bool dot8 = screen8 && ds->metric == AH_DOT_PRODUCT && knobs.screen8_dot;
+                const bool node_pre = screen8 && (ds->metric != AH_DOT_PRODUCT || dot8) && sv.pitch8 <= 6 * 128 && knobs.node_prefetch;
+                AH_TRY(launch_node_major(lb, bq, screen, screen8, node_pre, dot8, node_grid, forest->stats));
             }
             AH_HIP(hipEventRecord(bc.ev_attempt[2 * attempt + 1], s));
             AH_DBG(s, "margin");
@@ -4187,10 +4274,11 @@ int ah_dataset_reserve_build(ah_dataset *ds, uint32_t n_trees, uint32_t split_af
     const bool f32 = !metric_is_bq(ds->metric) && ds->dims >= 32;
     const bool want_screen = f32 && tun(TUN_SCREEN) != 0 && !ds->d_rows_h16;
     const uint32_t hpitch = (ds->dims + 63u) & ~63u, pitch8 = (ds->dims + 127u) & ~127u;
+    const bool build8 = (ds->metric != AH_DOT_PRODUCT || tun(TUN_SCREEN8_DOT) != 0) && tun(TUN_SCREEN8) != 0;
     if (want_screen) {  // ensure_screen / ensure_screen8
         sizes.push_back(N * (size_t)hpitch * 2);
         sizes.push_back(N * sizeof(float4));
-        if (ds->metric != AH_DOT_PRODUCT && tun(TUN_SCREEN8) != 0) {
+        if (build8) {
             if (tun(TUN_SCREEN8_LO) != 0) sizes.push_back(N * (size_t)pitch8);
             sizes.push_back(N * (size_t)pitch8);
             sizes.push_back(N * sizeof(float));
@@ -4220,7 +4308,7 @@ int ah_dataset_reserve_build(ah_dataset *ds, uint32_t n_trees, uint32_t split_af
         if (f32 && tun(TUN_SCREEN) != 0) {
             sizes.push_back((size_t)z.shadow_block);
             sizes.push_back((size_t)z.shadow_block);  // (a 100-tree 10M build takes a second block for its deepest levels)
-            if (ds->metric != AH_DOT_PRODUCT && tun(TUN_SCREEN8) != 0) sizes.push_back((size_t)z.shadow8_block);
+            if (build8) sizes.push_back((size_t)z.shadow8_block);
         }
     }
     const size_t pinned_bytes = z.pinned_bytes();

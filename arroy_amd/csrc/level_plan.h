@@ -17,6 +17,7 @@ namespace ah {
 // The tunables (common.h) a level's plan and its launches read, filled once per batch.
 struct LevelKnobs {
     bool screen, screen_verify, rows_advance, rows_lds, retry_gate, exact_wide, node_prefetch;
+    bool screen8_dot;  // AH_SCREEN8_DOT: DotProduct's node-major pairs take the int8 stages too
     int rows_force, dense;
     uint32_t tile_blocks, node_blocks, split_blocks, row_blocks, rows_max_tc, dense_max_cols;
     double rows_cache_mb, dense_gmacs;
@@ -156,7 +157,10 @@ inline LevelPlan plan_level(const LevelShape &sh, const LevelKnobs &k) {
         // measured both ways, takes 130.7 ms row-major and 136.9 ms node-major, and this keeps it row-major)
         const double node8_ns = sh.rows8_lo ? std::min(0.24, 0.135 + 0.15 * sh.screen8_quality)
                                             : std::min(0.24, 0.155 + 0.125 * sh.screen8_quality);
-        const double node_ns = screen ? (sh.screen8 && sh.metric != AH_DOT_PRODUCT ? node8_ns : 0.24) : 0.47;
+        // (DotProduct: the binary16 rate unless AH_SCREEN8_DOT gives it the int8 stages; its 8 bytes per pair of scale and
+        // header beside the int8 row are within the spread of the measured figures)
+        const bool node8 = sh.screen8 && (sh.metric != AH_DOT_PRODUCT || k.screen8_dot);
+        const double node_ns = screen ? (node8 ? node8_ns : 0.24) : 0.47;
         const double active = (double)sh.pairs / ((double)n_trees * (double)N);
         const double cost_node = (double)sh.pairs * node_ns * scale;
         const double convert = (double)n_trees * (double)N *

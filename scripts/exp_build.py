@@ -1,4 +1,4 @@
-"""Experiment driver (no torch): fill N x 768 cosine rows in HBM, build T trees, print the build statistics.
+"""Experiment driver (no torch): fill N x 768 cosine (or DotProduct) rows in HBM, build T trees, print the build statistics.
 Used under rocprofv3 (--kernel-trace / --pmc) to study the forest kernels; env switches of forest.hip apply."""
 import json
 import sys
@@ -13,8 +13,11 @@ trees = int(sys.argv[2]) if len(sys.argv) > 2 else 100
 reps = int(sys.argv[3]) if len(sys.argv) > 3 else 1
 dims = int(sys.argv[4]) if len(sys.argv) > 4 else 768
 dist = int(sys.argv[5]) if len(sys.argv) > 5 else 1  # ah_synth_distribution: 1 uniform[-1,1), 2 ~N(0,1), 3 with outlier dimensions
-ds = Dataset(distances.Cosine, dims, n)
+metric = sys.argv[6] if len(sys.argv) > 6 else "cosine"  # or "dot": DotProduct rows, preprocessed on the device
+ds = Dataset(distances.DotProduct if metric == "dot" else distances.Cosine, dims, n)
 ds.fill_synthetic(42, dist, n)
+if metric == "dot":
+    ds.preprocess_dot()
 ds.finalize()
 # 13 trees = the share GPU 0 of an 8-GPU node builds of a 100-tree forest (t = 0 mod 8); otherwise trees 0..T-1
 seeds = shard.tree_seeds(42, shard.trees_for_rank(100, 0, 8)) if trees == 13 else shard.tree_seeds(42, range(trees))
