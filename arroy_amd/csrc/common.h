@@ -128,7 +128,8 @@ inline int guarded(const char *what, F &&f) noexcept {
     X(SCREEN8_LO, "AH_SCREEN8_LO", 1)           /* 0: no second int8 digit of the rows (stage 1 = the binary16 row) */      \
     X(SCREEN8, "AH_SCREEN8", -1)                /* 0: no int8 first stage; 1: keep it whatever the data; -1: by quality */ \
     X(SCREEN8_DOT, "AH_SCREEN8_DOT", 0)         /* 1: DotProduct builds take the int8 first stage too (read when a build starts) */ \
-    X(MASK_BITS, "AH_MASK_BITS", -1)            /* 0 / 1: never / always pack a row-major level's sides into bits before the tiles gather them; -1: by size */ \
+    X(BUILD_ROWS_BQ, "AH_BUILD_ROWS_BQ", 0)     /* 1: full-dataset builds of the three 1-bit metrics may take row-major levels (k_forest_margin_rows_bq, DESIGN.md 4 "1-bit row-major levels": rows of at most 2048 dimensions, n_trees >= 2; forced AH_MARGIN_ROWS_* modes are honoured, AH_MARGIN_AUTO prices both); 0 (default): every 1-bit level is node-major, no plan, launch, allocation or statistic changes (read when a build starts) */ \
+    X(MASK_BITS, "AH_MASK_BITS", -1)           /* 0 / 1: never / always pack a row-major level's sides into bits before the tiles gather them; -1: by size */ \
     X(DENSE, "AH_DENSE", -1)                    /* 0: never the dense MFMA screen; 1: whenever legal; -1: cost model */    \
     X(DENSE_MAX_COLS, "AH_DENSE_MAX_COLS", 16384)                                                                        \
     X(DENSE_NARROW, "AH_DENSE_NARROW", -1)      /* 0: never the narrow dense kernel (rows straight to registers) */         \

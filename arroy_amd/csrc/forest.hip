@@ -436,6 +436,103 @@ __global__ __launch_bounds__(TC >= 16 ? 512 : 1024) void k_forest_margin_rows_ld
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Row-major margin pass of the three 1-bit metrics (AH_BUILD_ROWS_BQ; first attempt of a level, full-dataset trees, rows
+// of at most 32 words = 2048 dimensions).
+//
+// A 1-bit row is 16-256 bytes, so the octet mapping of the f32 passes does not fit (8 lanes x 16 bytes is more than a
+// whole 768-d row).  Here a LANE owns a row.  A block takes a slab of blockDim.x consecutive rows — one contiguous,
+// 16-byte aligned range of rows_bq, since the pitch is even — and moves it into LDS with coalesced 16-byte loads; then
+// every lane pulls its own row into registers (W words, the smallest rung of the ladder 2 / 8 / 16 / 32 that holds the
+// pitch: the loops unroll and the row stays in VGPRs) and serves the TC trees of the group from there: per tree one
+// node_of entry (all TC loads issued first: 4 bytes per lane, coalesced, in flight together), XOR + popcount against
+// the node's normal, the margin by the functions of margin_bq (split_device.h) and one coalesced side byte.  Integer
+// popcounts and at most one f32 add of the bias: the sides are those of k_forest_margin_bq by construction.
+//
+// LDS row stride: pitch + 1 words.  The pitch is even, so the stride is an ODD number of 8-byte words: lane l reads
+// word w of its row at word l * (pitch + 1) + w, and l -> l * odd is a permutation modulo 32, so the 32 lanes of a
+// half-wave hit 32 different bank pairs (64 banks x 4 bytes) for every w — no conflict.  With stride = pitch the
+// lanes of a 768-d slab (12 words) would meet on 8 of the 32 pairs, four deep.  The price: rows in LDS are 8-byte
+// aligned only, so the staging writes are two 8-byte stores per 16-byte piece.
+//
+// Normals: LDSN — the records [first_node, first_node + n_group_nodes) of the group (stride nstride, a multiple of
+// 16) are copied to LDS once per block, in front of the slab; at the top levels most lanes of a wave name the same few
+// nodes and the reads are broadcasts.  Otherwise they are read from global memory (L2) 16 bytes at a time.
+// Dynamic LDS: [normals, n_group_nodes * nstride bytes (LDSN)][slab, rows_bq_slab_bytes (level_plan.h)].
+// ------------------------------------------------------------------------------------------------
+template <int W, int TC, bool LDSN>
+__global__ __launch_bounds__(256) void k_forest_margin_rows_bq(DataView dv, const uint32_t *__restrict__ node_of,
+                                                               uint32_t tree0, uint32_t n_pass,
+                                                               const uint8_t *__restrict__ normals, uint64_t nstride,
+                                                               uint64_t hdr_off, uint8_t *__restrict__ side_bytes,
+                                                               uint32_t first_node, uint32_t n_group_nodes,
+                                                               const AbortFlags abort_flag) {
+    extern __shared__ uint4 s_rows_bq[];
+    __shared__ uint32_t s_abort;
+    const uint32_t pitch = dv.pitch, pieces = pitch >> 1, stride_w = pitch + 1u, slab_rows = blockDim.x;
+    const uint32_t norm16 = LDSN ? n_group_nodes * (uint32_t)(nstride >> 4) : 0u;  // 16-byte units of normals in LDS
+    const uint4 *s_norm = s_rows_bq;
+    uint64_t *s_slab = reinterpret_cast<uint64_t *>(s_rows_bq + norm16);
+    if (LDSN) {
+        const uint4 *g = reinterpret_cast<const uint4 *>(normals + (uint64_t)first_node * nstride);
+        for (uint32_t i = threadIdx.x; i < norm16; i += blockDim.x) s_rows_bq[i] = g[i];
+    }
+    const uint64_t n_slabs = (dv.n + slab_rows - 1) / slab_rows;
+    for (uint64_t slab = blockIdx.x; slab < n_slabs; slab += gridDim.x) {
+        const uint64_t row0 = slab * slab_rows;
+        const uint32_t in_slab = (uint32_t)min((uint64_t)slab_rows, dv.n - row0);
+        __syncthreads();  // every lane has pulled its row of the slab before
+        if (threadIdx.x == 0) s_abort = abort_requested(abort_flag) ? 1u : 0u;
+        {
+            const uint4 *g = reinterpret_cast<const uint4 *>(dv.rows_bq + row0 * pitch);
+            const uint32_t total = in_slab * pieces;  // 16-byte pieces of the slab: at most 256 x 16
+            for (uint32_t i = threadIdx.x; i < total; i += blockDim.x) {
+                const uint4 v = ld_stream_u4(g + i);
+                const uint32_t r = i / pieces, p = i - r * pieces;
+                uint64_t *d = s_slab + r * stride_w + 2u * p;
+                d[0] = (uint64_t)v.x | ((uint64_t)v.y << 32);
+                d[1] = (uint64_t)v.z | ((uint64_t)v.w << 32);
+            }
+        }
+        __syncthreads();
+        if (s_abort) return;  // build cancelled: drain (block-uniform: the word thread 0 wrote before the barrier)
+        if (threadIdx.x >= in_slab) continue;  // (the barriers are at the top of the loop: every lane comes back to them)
+        const uint64_t row = row0 + threadIdx.x;
+        uint32_t node[TC];
+#pragma unroll
+        for (int t = 0; t < TC; t++) {
+            node[t] = 0xFFFFFFFFu;  // spare slots of the group: nothing to do
+            if ((uint32_t)t < n_pass) node[t] = node_of[(uint64_t)(tree0 + t) * dv.n + row];
+        }
+        uint64_t x[W];
+        {
+            const uint64_t *mine = s_slab + threadIdx.x * stride_w;
+#pragma unroll
+            for (int w = 0; w < W; w++) x[w] = (uint32_t)w < pitch ? mine[w] : 0ull;
+        }
+#pragma unroll
+        for (int t = 0; t < TC; t++) {
+            if (node[t] == 0xFFFFFFFFu) continue;
+            // the node's record [words][header]: in LDS, or 16 bytes at a time from global memory (L2)
+            const uint4 *n4 = LDSN ? s_norm + (node[t] - first_node) * (uint32_t)(nstride >> 4)
+                                   : reinterpret_cast<const uint4 *>(normals + (uint64_t)node[t] * nstride);
+            uint32_t ham = 0;
+#pragma unroll
+            for (int p = 0; p < W / 2; p++) {
+                if ((uint32_t)p < pieces) {
+                    const uint4 v = n4[p];
+                    ham += (uint32_t)__popcll(x[2 * p] ^ ((uint64_t)v.x | ((uint64_t)v.y << 32)));
+                    ham += (uint32_t)__popcll(x[2 * p + 1] ^ ((uint64_t)v.z | ((uint64_t)v.w << 32)));
+                }
+            }
+            const LeafHdr nh = {reinterpret_cast<const float *>(n4 + (hdr_off >> 4))[0], 0.0f};
+            const float d = (float)bq_dot_from_hamming(ham, dv.words);  // margin_bq, from the Hamming distance on
+            const float m = dv.metric == AH_BQ_COSINE ? d : f_add(nh.h0, d);
+            side_bytes[(uint64_t)(tree0 + t) * dv.n + row] = (uint8_t)side_of_margin(m);
+        }
+    }
+}
+
 // The side bytes of a level (0 / 1 per (tree, row)) as one bit each, bit g of the flat array = pair g = tree * N + row.
 // k_forest_masks_from_bytes reads the sides in the order of the trees' permutations, i.e. at random: a tree's bits are
 // N / 8 bytes (1.25 MB at 10M rows: they stay in an L2) where its bytes are N (10 MB: most gathers go out to the fabric).
@@ -2942,6 +3039,54 @@ int launch_rows_f32(const LevelBufs &b, const LevelPlan &plan, uint64_t rec_byte
     return AH_OK;
 }
 
+// The 1-bit row-major pass (k_forest_margin_rows_bq): one launch per group of the plan's list, as launch_rows_f32.  A slab
+// is 256 rows, or 128 where the group's normals leave LDS short (the plan has made sure that 128 fit: rows_bq_lds_fits);
+// the grid is persistent over the slabs, as many blocks per CU as their LDS allows.
+template <int W, int TC, bool LDSN>
+int launch_rows_bq_inst(const LevelBufs &b, uint32_t t0, uint32_t np, uint32_t first, uint32_t cnt, size_t norm_bytes, size_t lds_grant,
+                        unsigned row_blocks) {
+    const unsigned slab = norm_bytes + rows_bq_slab_bytes(b.dv.pitch, 256) <= lds_grant ? 256u : 128u;
+    const size_t sh = norm_bytes + rows_bq_slab_bytes(b.dv.pitch, slab);
+    const unsigned per_cu = (unsigned)std::max<size_t>(1, std::min<size_t>(2048 / slab, (160u << 10) / sh));
+    const unsigned grid = (unsigned)std::min<uint64_t>(std::min<uint64_t>((b.N + slab - 1) / slab, 256u * per_cu), row_blocks);
+    AH_TRY(lds_opt_in(reinterpret_cast<const void *>(k_forest_margin_rows_bq<W, TC, LDSN>), b.device, LDSN ? std::max(sh, lds_grant) : sh));
+    hipLaunchKernelGGL((k_forest_margin_rows_bq<W, TC, LDSN>), dim3(grid), dim3(slab), sh, b.s, b.dv, b.node_of, t0, np, b.normals,
+                       b.nstride, b.hdr_off, b.side_bytes, first, cnt, b.abort_all);
+    return AH_OK;
+}
+template <int W>
+int launch_rows_bq_width(const LevelBufs &b, const LevelPlan &plan, size_t lds_grant, unsigned row_blocks, ah_build_stats &st) {
+    for (const RowsLaunch &l : plan.launches)
+        for (uint32_t g = 0; g < l.groups; g++) {
+            const uint32_t t0 = l.t0 + g * l.tcv;
+            if (plan.lds_tc) {
+                const uint32_t first = plan.tree_first[t0], cnt = plan.tree_first[t0 + l.np] - first;
+                if (cnt == 0) continue;
+                const size_t nb = (size_t)cnt * b.nstride;
+                AH_TRY(l.tcv >= 16 ? (launch_rows_bq_inst<W, 16, true>(b, t0, l.np, first, cnt, nb, lds_grant, row_blocks))
+                                   : (launch_rows_bq_inst<W, 8, true>(b, t0, l.np, first, cnt, nb, lds_grant, row_blocks)));
+                st.margin_mode_launches[l.tcv >= 16 ? MM_LDS16 : MM_LDS8]++;
+            } else {
+                switch (l.tcv) {
+                case 16: AH_TRY((launch_rows_bq_inst<W, 16, false>(b, t0, l.np, 0, 0, 0, lds_grant, row_blocks))); break;
+                case 8: AH_TRY((launch_rows_bq_inst<W, 8, false>(b, t0, l.np, 0, 0, 0, lds_grant, row_blocks))); break;
+                case 4: AH_TRY((launch_rows_bq_inst<W, 4, false>(b, t0, l.np, 0, 0, 0, lds_grant, row_blocks))); break;
+                default: AH_TRY((launch_rows_bq_inst<W, 2, false>(b, t0, l.np, 0, 0, 0, lds_grant, row_blocks))); break;
+                }
+                st.margin_mode_launches[mm_rows(l.tcv)]++;
+            }
+        }
+    return AH_OK;
+}
+int launch_rows_bq(const LevelBufs &b, const LevelPlan &plan, size_t lds_grant, unsigned row_blocks, ah_build_stats &st) {
+    const uint32_t pitch = b.dv.pitch;  // the rung of the word ladder that holds the row (rows_allowed: pitch <= 32)
+    AH_REQUIRE(pitch <= kRowsBqMaxPitch, AH_ERR_DEVICE, "forest build: a 1-bit row of %u words in the row-major pass (internal error)", pitch);
+    return pitch <= 2    ? launch_rows_bq_width<2>(b, plan, lds_grant, row_blocks, st)
+           : pitch <= 8  ? launch_rows_bq_width<8>(b, plan, lds_grant, row_blocks, st)
+           : pitch <= 16 ? launch_rows_bq_width<16>(b, plan, lds_grant, row_blocks, st)
+                         : launch_rows_bq_width<32>(b, plan, lds_grant, row_blocks, st);
+}
+
 // The node-major pass of an attempt on a persistent grid: binary-quantised, screened (`node_pre`: the pipelined variant of
 // the int8 stage; `dot8`: DotProduct with the int8 stages, k_forest_screen_node_dot8) or f32.  Very long vectors need more
 // dynamic LDS than the default limit.
@@ -3016,6 +3161,7 @@ LevelKnobs read_level_knobs() {
     k.exact_wide = tun(TUN_EXACT_WIDE) != 0;
     k.node_prefetch = tun(TUN_NODE_PREFETCH) != 0;
     k.screen8_dot = tun(TUN_SCREEN8_DOT) != 0;
+    k.rows_bq = tun(TUN_BUILD_ROWS_BQ) != 0;
     k.tail_groups = (uint32_t)std::min<long long>(32, std::max<long long>(0, tun(TUN_TAIL_GROUPS)));
     k.tail_node_items = (double)std::max<long long>(1, tun(TUN_TAIL_NODE_ITEMS));
     k.tail_min_items = (uint64_t)std::max<long long>(0, tun(TUN_TAIL_MIN_MB)) * (1u << 20) / 4;
@@ -3223,8 +3369,8 @@ struct BatchBuild {
         const uint32_t env_mode = (uint32_t)tun(TUN_MARGIN_MODE) & 0xFFFu;
         mode_req = (opt->margin_mode & 0xFFFu) ? (opt->margin_mode & 0xFFFu) : env_mode;
         exact_only = (opt->margin_mode & AH_MARGIN_EXACT_ONLY) != 0 || !knobs.screen;
-        // row-major margin mode (full-dataset trees, f32 metrics)
-        rows_allowed = !subset_ids && !bq && ds->dims >= 32 && n_trees >= 2 &&
+        // row-major margin mode (full-dataset trees; f32 metrics, or 1-bit rows of at most 32 words under AH_BUILD_ROWS_BQ)
+        rows_allowed = !subset_ids && (bq ? knobs.rows_bq && dv.pitch <= kRowsBqMaxPitch : ds->dims >= 32) && n_trees >= 2 &&
                        (mode_req != AH_MARGIN_AUTO ? mode_req != AH_MARGIN_NODE_MAJOR : knobs.rows_force != 0);
         host_threads = host_thread_budget(opt);
         // (the shadow arenas' blocks are sized for the strides their records have WHEN a screen is up — ensure_screen decides
@@ -3668,6 +3814,8 @@ struct BatchBuild {
                         AH_HIP(hipMemcpyAsync(d_tree_first_fixed, h_tree_first, ((size_t)n_trees + 1) * 4, hipMemcpyHostToDevice, s));
                     }
                     AH_TRY(launch_rows_screened(lb, plan, nodes_per_tree, rec_bytes, d_tree_first_fixed, knobs.lds_normals_bytes, forest->stats));
+                } else if (bq) {
+                    AH_TRY(launch_rows_bq(lb, plan, knobs.lds_normals_bytes, knobs.row_blocks, forest->stats));
                 } else {
                     AH_TRY(launch_rows_f32(lb, plan, rec_bytes, (unsigned)std::min<uint64_t>((N + 31) / 32, knobs.row_blocks),
                                            knobs.lds_normals_bytes, forest->stats));
@@ -4286,9 +4434,11 @@ int ah_dataset_reserve_build(ah_dataset *ds, uint32_t n_trees, uint32_t split_af
     }
     // one batch of n_trees full-dataset trees, in the order BatchBuild::setup_device and the level loop ask (the pinned host
     // memory of that batch — node tables, level info, the read-back worker's double buffer — is z.pinned_bytes())
-    const bool f32_rows = f32 && n_trees >= 2;
+    // (the row-major buffers: f32 metrics, and 1-bit rows of at most 32 words under AH_BUILD_ROWS_BQ)
+    const bool bq_rows = metric_is_bq(ds->metric) && tun(TUN_BUILD_ROWS_BQ) != 0 && ds->pitch <= kRowsBqMaxPitch;
+    const bool want_rows = (f32 || bq_rows) && n_trees >= 2;
     const BatchSizes z = batch_sizes(N, n_trees, (uint64_t)n_trees * N, split_after, normal_record_stride(ds), shadow_stride16(hpitch),
-                                     shadow_stride8(pitch8), f32_rows, tun(TUN_MASK_BITS) > 0 || (tun(TUN_MASK_BITS) < 0 && N >= (1u << 20)),
+                                     shadow_stride8(pitch8), want_rows, tun(TUN_MASK_BITS) > 0 || (tun(TUN_MASK_BITS) < 0 && N >= (1u << 20)),
                                      tun(TUN_READBACK_MB));
     {
         auto buf = [&](uint64_t n, size_t elem) { sizes.push_back((size_t)std::max<uint64_t>(n, 1024) * elem); };  // (DevBuf's floor)
@@ -4299,7 +4449,7 @@ int ah_dataset_reserve_build(ah_dataset *ds, uint32_t n_trees, uint32_t split_af
         buf(z.tile_left, 4); buf(z.tile_left, 4);
         buf(z.child, 4);
         buf(z.block_sums, sizeof(NextCounts));
-        if (f32_rows) {
+        if (want_rows) {
             buf(z.node_of, 4);
             buf(z.side_bytes, 1);
             if (z.side_bits) buf(z.side_bits, 4);

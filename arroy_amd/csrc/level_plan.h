@@ -18,6 +18,7 @@ namespace ah {
 struct LevelKnobs {
     bool screen, screen_verify, rows_advance, rows_lds, retry_gate, exact_wide, node_prefetch;
     bool screen8_dot;  // AH_SCREEN8_DOT: DotProduct's node-major pairs take the int8 stages too
+    bool rows_bq;      // AH_BUILD_ROWS_BQ: 1-bit datasets may take row-major levels (k_forest_margin_rows_bq)
     int rows_force, dense;
     uint32_t tile_blocks, node_blocks, split_blocks, row_blocks, rows_max_tc, dense_max_cols;
     double rows_cache_mb, dense_gmacs;
@@ -39,7 +40,8 @@ struct LevelShape {
     int metric;
     bool screen, screen8, rows8_lo;
     double screen8_quality;
-    bool rows_allowed;      // full-dataset trees of an f32 metric, and the caller does not ask for node-major
+    bool rows_allowed;      // full-dataset trees of an f32 metric (of a 1-bit one of at most kRowsBqMaxPitch words under
+                            // AH_BUILD_ROWS_BQ), and the caller does not ask for node-major
     bool prev_rows;         // the previous level ran row-major
     bool grouped, fork_now;  // a tree group of the tail (node-major); the tail has been cut already
     bool subset;            // the trees cover id lists, not the dataset
@@ -90,6 +92,12 @@ inline std::vector<RowsLaunch> rows_launch_list(uint32_t n_trees, uint32_t tc, b
     return out;
 }
 
+// The 1-bit row-major pass (k_forest_margin_rows_bq, forest.hip): rows of at most 32 words (2048 dimensions) — the widest
+// rung of its register ladder — and the bytes of dynamic LDS a slab of `slab_rows` rows takes at its padded stride of
+// pitch + 1 words.
+constexpr uint32_t kRowsBqMaxPitch = 32;
+inline size_t rows_bq_slab_bytes(uint32_t pitch, uint32_t slab_rows) { return (size_t)slab_rows * (pitch + 1u) * 8u; }
+
 // Measured cost of one row-major pass in ns per row, as a function of the tree-group size and of the bytes of normals
 // the group streams in the level (profiles/r02_*: 10M x 768 x 100 trees, every level forced to one group size), for
 // the f32 kernels (rows of 3072 bytes) and for the screened kernels (binary16 rows of 1536 bytes).  While the normals fit
@@ -138,8 +146,51 @@ inline LevelPlan plan_level(const LevelShape &sh, const LevelKnobs &k) {
     const uint64_t nodes_per_tree = (n_nodes + n_trees - 1) / n_trees;
     uint32_t &row_tc = plan.row_tc, &lds_tc = plan.lds_tc, &lds_worst = plan.lds_worst;
     double &best_cost = plan.best_cost;
+    const bool bq = sh.metric >= AH_BQ_EUCLIDEAN;  // (rows_allowed for a 1-bit dataset: only under AH_BUILD_ROWS_BQ)
+    const uint32_t bq_pitch = (uint32_t)(sh.row_bytes / 8);
     if (grouped) {
         // a tree group of the tail: node-major (what the level it was cut from had chosen)
+    } else if (rows_allowed && bq && mode_req == AH_MARGIN_AUTO) {
+        // 1-bit rows (AH_BUILD_ROWS_BQ).  The f32 tables below are in ns per 3072-byte row and do not scale down to a row
+        // of 96 bytes: three constants of their own, in ns at 768 dimensions (12 words), scaled by the row's words.
+        //   node-major:  pairs x node_bq_ns                       (k_forest_margin_bq: a gathered row per pair)
+        //   row-major:   N x (row_ns + tc x slot_ns x active)     per pass of tc slots (k_forest_margin_rows_bq: the slab
+        //                through LDS once, then per slot and row still splitting the node_of entry, the normal from L2
+        //                or LDS, the popcounts and the side byte), plus the node_of / mask conversion of the level
+        // Measured (profiles/rows_bq_levels.txt: 10M x 768 BinaryQuantizedCosine, 100 trees, uniform rows, one MI355X; the
+        // switch off and every level forced to each shape, alternated in one process, and a kernel trace of its own):
+        //   node_bq_ns 0.17: 171-180 ms per level of 10^9 pairs on levels 3-11, 0.159-0.176 ns per pair in the tail
+        //                    (1M x 1536: 0.28-0.31 ns, the scale below says 0.34);
+        //   row_ns 0.017:    a pass over rows with nothing left to split (level 20) — 0.24 ms per 16-slot pass, 0.17 ms per
+        //                    4-slot pass of 10^7 rows, the node_of entries included;
+        //   slot_ns 0.03:    levels 11-14, where a level's normals (23-90 MB) have outgrown the L2s: 27.5 / 32.9 / 43.6 / 8.2 ms
+        //                    of kernel time for the seven launches of a 16-slot schedule (level 14: 23 % of the pairs).  The
+        //                    top levels cost 0.005 (5.8 ms), so the model over-prices them (50 ms where 11 were measured,
+        //                    conversion included) — against 176 ms node-major that decides nothing.  The close calls are
+        //                    levels 14 and 15 of that build: 15.7 ms row-major against 36.4 node-major (23 % of the pairs),
+        //                    then 9.0 against 6.0 (3.6 %: a slot then costs per WAVE that still has an active lane, 0.125 ns
+        //                    per active pair).  The model puts the hand-over between those two, as measured.
+        // Every term is linear in the slot count, so the widest schedule always prices cheapest; measured, the shapes are
+        // within 10 % of one another from level 8 on and 16 slots win above (the LDS variant, chosen below, by more).
+        const double node_bq_ns = 0.17, row_ns = 0.017, slot_ns = 0.03;
+        const double scale = (double)sh.row_bytes / 96.0;
+        const double active = (double)sh.pairs / ((double)n_trees * (double)N);
+        const double convert = (double)n_trees * (double)N *
+                               ((sh.prev_rows && k.rows_advance ? 0.007 : 0.01 + 0.03 * std::min(1.0, (double)nodes_per_tree / 256.0)) +
+                                0.012 * std::min(1.0, (double)nodes_per_tree / 512.0));
+        double best = (double)sh.pairs * node_bq_ns * scale;
+        for (uint32_t tc = std::min(16u, k.rows_max_tc); tc >= 2; tc >>= 1) {
+            if (tc > 2 && tc / 2 >= n_trees) continue;  // do not instantiate more slots than trees
+            double ns_per_row = 0.0;
+            for (const RowsLaunch &l : rows_launch_list(n_trees, tc, false))
+                ns_per_row += l.groups * (row_ns + l.tcv * slot_ns * std::min(1.0, active)) * scale;
+            const double cost_rows = (double)N * ns_per_row + convert;
+            if (cost_rows < best || (k.rows_force == 1 && row_tc == 0)) {
+                best = std::min(best, cost_rows);
+                row_tc = tc;
+            }
+        }
+        best_cost = best;
     } else if (rows_allowed && mode_req == AH_MARGIN_AUTO) {
         // Cost model in ns per row of 3072 bytes, fitted to per-level rocprofv3 traces of the 10M x 768 x 100-tree
         // build (profiles/): node-major = one HBM read of the row per (item, tree) pair; row-major = per pass and
@@ -233,7 +284,8 @@ inline LevelPlan plan_level(const LevelShape &sh, const LevelKnobs &k) {
             uint32_t worst = 0;
             for (uint32_t t0 = 0; t0 < n_trees; t0 += tc)
                 worst = std::max(worst, tree_first[std::min(n_trees, t0 + tc)] - tree_first[t0]);
-            if ((uint64_t)worst * rec_bytes <= k.lds_normals_bytes) {
+            // (1-bit rows: the slab of rows shares the grant with the normals; 128 rows is the smallest slab)
+            if ((uint64_t)worst * rec_bytes + (bq ? rows_bq_slab_bytes(bq_pitch, 128) : 0) <= k.lds_normals_bytes) {
                 lds_tc = tc;
                 lds_worst = worst;
                 break;

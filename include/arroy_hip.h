@@ -412,7 +412,8 @@ typedef struct ah_build_stats {
     uint64_t split_nodes, descendant_nodes, dummy_normals, retries;
     uint32_t levels;
     /* margin launches per kernel family: [0] node-major f32, [1] rows x2, [2] rows x4, [3] rows x8, [4] rows x16,
-     * [5] LDS x8, [6] LDS x16, [7] node-major 1-bit */
+     * [5] LDS x8, [6] LDS x16, [7] node-major 1-bit; the row-major launches of a 1-bit build (AH_BUILD_ROWS_BQ) count in
+     * [1..6] by group width, as the f32 ones do */
     uint64_t margin_mode_launches[8];
     uint64_t screened_launches;   /* margin launches that ran the certified binary16 screen                  */
     uint64_t screen_fallbacks;    /* (item, node) pairs the screen could not decide (recomputed in f32)       */
