@@ -159,6 +159,10 @@ class AhSearchDiffStats(C.Structure):  # ah_search_diff_stats: the same fields, 
     _fields_ = AhRerankDiffStats._fields_
 
 
+class AhMidStats(C.Structure):  # ah_mid_stats: the tile path of mid-size submissions (AH_SEARCH_MID_TILES)
+    _fields_ = [(f, C.c_uint64) for f in ("chunks", "queries", "items", "chunks_overflowed")]
+
+
 class AhSearchStats(C.Structure):
     _fields_ = [(f, C.c_uint64) for f in (
         "calls", "chunks", "queries", "descent_wave_small", "descent_wave_big", "descent_octet_lds", "descent_octet_global",
@@ -328,6 +332,7 @@ SIGNATURES = {
                                   C.c_int, _U32P, _F32P, _U32P]),
     "ah_index_search_stats": (C.c_int, [_VP, C.POINTER(AhSearchStats), C.c_int]),
     "ah_index_search_diff_stats": (C.c_int, [_VP, C.POINTER(AhSearchDiffStats), C.c_int]),
+    "ah_index_mid_stats": (C.c_int, [_VP, C.POINTER(AhMidStats), C.c_int]),
     "ah_route_items": (C.c_int, [_VP, _U32P, C.c_size_t, _U64P, _U32P]),
     # resident candidate filters, one per query in a batched call
     "ah_filter_create": (C.c_int, [_VP, _U32P, C.c_size_t, C.POINTER(C.c_void_p)]),

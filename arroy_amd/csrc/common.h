@@ -184,6 +184,9 @@ inline int guarded(const char *what, F &&f) noexcept {
     X(RERANK_SCREEN_DIFF, "AH_RERANK_SCREEN_DIFF", 0) /* 1: ah_rerank_batch screens Euclidean / Manhattan lists on the binary16 rows too, by the difference of the copies (DESIGN.md 2.5 "The difference screen"); 0 (default): those lists take the f32 gather, no call and no statistic changes; AH_RERANK_SCREEN=0 wins */ \
     X(SEARCH_SCREEN_DIFF, "AH_SEARCH_SCREEN_DIFF", 0) /* 1: Euclidean / Manhattan sub-batches of ah_search_batch / _filters / _params take the leaf tiles on the binary16 rows, by the difference of the copies (k_leaf_tiles_diff16), and ah_index_create makes that copy for them; 0 (default): Euclidean keeps the f32 tiles, Manhattan the sorted path, no plan, launch, allocation or statistic changes; AH_SEARCH_SCREEN=0 wins */ \
     X(SEARCH_TILES_BQ, "AH_SEARCH_TILES_BQ", 0) /* 1: the sub-batches of the three 1-bit metrics of ah_search_batch / _filters / _params take the leaf tiles (k_leaf_tiles_bq, DESIGN.md 4 "1-bit leaf tiles": exact distances, nothing screened) up to 8192 dimensions; 0 (default): they take the sorted path, no plan, launch, allocation or statistic changes */ \
+    X(SEARCH_MID_TILES, "AH_SEARCH_MID_TILES", 0) /* 1: a sub-batch of 9 .. AH_SEARCH_MID_TILES_MAX_QUERIES queries of ah_search_batch / _filters / _params whose plan is a screened or f32 leaf-tile plan launches one block of k_leaf_tiles_mid per (unit, slab of 64 rows) item of the list k_units_small leaves (DESIGN.md 4 "Mid-size submissions"); 0 (default): the 2-D grid of the big submissions' kernels, no plan, launch, allocation or statistic changes */ \
+    X(SEARCH_MID_TILES_MAX_QUERIES, "AH_SEARCH_MID_TILES_MAX_QUERIES", 64) /* ... up to this many queries a call (k_units_small places the visits of at most AH_SEARCH_SMALL_UNITS_MAX_QUERIES) */ \
+    X(SEARCH_MID_ITEMS_CAP, "AH_SEARCH_MID_ITEMS_CAP", 0) /* != 0: the item list of the mid tiles holds at most this many items (test aid: a list that does not fit sends the sub-batch the long way) */ \
     X(REPLICATE_HOST_BOUNCE,"AH_REPLICATE_HOST_BOUNCE", 0) /* 1: ah_dataset_replicate copies through pinned host memory even where peer access works (test aid) */ \
     X(RERANK_TIMING, "AH_RERANK_TIMING", 0)     /* 1: ah_rerank_batch accounts its wall time by phase (ah_dataset_rerank_stats) */ \
     X(SEARCH_SCREEN, "AH_SEARCH_SCREEN", 1)     /* 0: the re-rank of ah_search_batch never screens its candidates (f32 rows for all) */ \

@@ -84,6 +84,7 @@ struct ah_index {
     std::atomic<uint32_t> search_diff_fails{0}, search_diff_seen{0};
     std::atomic<bool> search_diff_off{false};
     ah_search_diff_stats diff_stats{};       // what that screen served (under stats_mu; switched_off: search_diff_off)
+    ah_mid_stats mid_stats{};                // what the mid-size submissions' tiles served (AH_SEARCH_MID_TILES; under stats_mu)
     bool counted = false;                    // counted in ds->live_indexes (an update of the dataset refuses meanwhile)
     bool suspended = false;                  // ah_index_suspend: not counted, and every call that reads the dataset refuses
     ah_params_stats pstats{};                // under stats_mu: how ah_search_batch_params cut its calls

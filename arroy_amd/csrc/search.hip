@@ -49,7 +49,9 @@ struct VisitSink {          // all null / 0: the descent records nothing
 // how the leaf tiles were cut.  Proof of the path taken (ah_index_search_stats), never an input of a result.
 enum SearchStatSlot {
     SS_ERR = 0, SS_WAVE_SMALL, SS_WAVE_BIG, SS_OCTET_LDS, SS_OCTET_GLOBAL, SS_UNITS_16, SS_UNITS_8, SS_UNITS_4, SS_VISITS,
-    SS_SCREENED, SS_SURVIVORS, SS_BLOCK, SS_VISIT_TOTAL, SS_N_UNITS, SS_DONE, SS_MULTI, SS_WORDS = 16
+    SS_SCREENED, SS_SURVIVORS, SS_BLOCK, SS_VISIT_TOTAL, SS_N_UNITS, SS_DONE, SS_MULTI,
+    SS_MID_ITEMS,  // the (unit, slab) items a mid-size submission listed (ah_index_mid_stats)
+    SS_WORDS = 17
 };
 static_assert(SS_WORDS == kStatusWords, "the status block as search_plan.h lays it out");
 
@@ -1856,7 +1858,9 @@ __global__ __launch_bounds__(256) void k_visit_scatter(const Visit *__restrict__
 __global__ __launch_bounds__(256) void k_units_small(const Visit *__restrict__ visits, const uint32_t *__restrict__ total,
                                                      uint32_t cap, Visit *__restrict__ sorted, TileUnit *__restrict__ units,
                                                      uint32_t *__restrict__ n_units, uint32_t *__restrict__ stats, QueriesH16 h16,
-                                                     uint32_t *__restrict__ items = nullptr, uint32_t items_cap = 0) {
+                                                     uint32_t *__restrict__ items = nullptr, uint32_t items_cap = 0, uint32_t mid = 0) {
+    // mid (AH_SEARCH_MID_TILES, 9 .. 64 queries a call): the list is k_leaf_tiles_mid's — every unit in slabs of kTileSmallSlab
+    // rows whatever its visits; a list that does not fit is bit 6 of *err and an empty list (the submission takes the long way)
     // items (round 6, a few queries a call): [count][unit << 16 | slab] — the (unit, slab of its leaf) pairs k_leaf_tiles16<true>
     // has work for, so that its launch is one block per pair instead of a 2-D grid of 32 nq x (largest leaf's slabs) blocks of
     // which a fifth find work (items[0] = 0xFFFFFFFF: more pairs than the list holds, the launch walks its grid as before)
@@ -1929,7 +1933,7 @@ __global__ __launch_bounds__(256) void k_units_small(const Visit *__restrict__ v
         const uint64_t key = s_key[p], node_key = key & 0xFFFFFFFF00000000ull;
         if (((p - lower_bound(node_key)) % kUnitVisits) != 0) continue;
         const uint32_t nv = min(kUnitVisits, lower_bound(node_key + (1ull << 32)) - p);
-        const uint32_t slab = tile_slab_rows(nv, true), n_leaf = visits[(uint32_t)key].n;
+        const uint32_t slab = mid ? kTileSmallSlab : tile_slab_rows(nv, true), n_leaf = visits[(uint32_t)key].n;
         my_unit[n_mine] = u;
         my_slabs[n_mine] = (n_leaf + slab - 1u) / slab;
         my_items += my_slabs[n_mine];
@@ -1956,7 +1960,11 @@ __global__ __launch_bounds__(256) void k_units_small(const Visit *__restrict__ v
         if (fits)
             for (uint32_t i = 0; i < n_mine; i++)
                 for (uint32_t sl = 0; sl < my_slabs[i]; sl++) items[1u + at++] = (my_unit[i] << 16) | min(sl, 0xFFFFu);
-        if (tid == 0) items[0] = fits ? all_items : 0xFFFFFFFFu;
+        if (tid == 0) {
+            items[0] = fits ? all_items : mid ? 0u : 0xFFFFFFFFu;
+            if (mid && !fits) atomicOr(&stats[SS_ERR], 64u);
+            if (mid && fits) atomicAdd(&stats[SS_MID_ITEMS], all_items);
+        }
     }
     if (u16) atomicAdd(&stats[SS_UNITS_16], u16);
     if (u8) atomicAdd(&stats[SS_UNITS_8], u8);
@@ -3021,6 +3029,229 @@ template <bool SMALL>
 static auto tiles16_kernel(int metric) -> decltype(&k_leaf_tiles16<SMALL>) {
     return metric == AH_EUCLIDEAN ? k_leaf_tiles_diff16<AH_EUCLIDEAN, SMALL>
            : metric == AH_MANHATTAN ? k_leaf_tiles_diff16<AH_MANHATTAN, SMALL> : k_leaf_tiles16<SMALL>;
+}
+
+// ---- the leaf tiles of a mid-size submission (AH_SEARCH_MID_TILES, 9 .. 64 queries a call) --------------------------------
+// Such a call places its visits with k_units_small like a small one, and then fell onto the big submissions' 2-D grid of 2048
+// units x the largest leaf's slabs, most of whose blocks find no unit or no slab.  k_leaf_tiles_mid is launched over the list
+// of (unit, slab of kTileSmallSlab rows) items k_units_small leaves instead: block b takes item b, the blocks past the list's
+// length leave at once.
+//   * The block's 32 octets take two rows of the slab each and ALL the unit's visits, so a row leaves memory once per unit and
+//     is passed over once (the big kernels' <4, 4, QO> shapes read a row once per query group of a wave).
+//   * kMidSteps k-steps of both rows are requested together, behind a scheduling fence, before the first is used: 4 x 2 x 16 B
+//     per lane, 8 KiB per block in flight, 32 registers.  That number is the occupancy decision: with the 2 x 16 sums it keeps
+//     the kernel near 100 registers, so four or five blocks share a compute unit and 32 - 40 KiB of row loads are outstanding
+//     on it.  The one-query kernel's 24 steps in flight (324 registers, one block per compute unit) fit a launch of a dozen
+//     leaves; 64 queries list thousands of items, and what hides the latency here is the next block, not a longer request.
+//   * Units of one to four visits read their queries' operands into registers with the rows (<2, Q, 1> of the small tiles, the
+//     existing rule).  Units of five to sixteen visits take them from LDS: the block stages the kMidSteps k-steps of all its
+//     queries once (16 x 4 x 128 B = 8 KiB) — requested BEFORE the rows of the chunk, so that the wait for them leaves the rows
+//     in flight — and every octet reads its operand there (eight lanes 128 contiguous bytes, the octets of a wave the same
+//     ones).  The barriers around the staging wait for LDS traffic only.
+//   * Per (row, query) pair nothing changes: lane j of the pair's octet owns the same 8 halves (4 floats) of every k-step, adds
+//     them in the same order with the same operations, and the octet's sum is octet_sum / octet_finish + scalar_tail as in
+//     leaf_tile16, leaf_tile_diff16 and leaf_tile — the same screen values and f32 distances bit for bit, so the selection,
+//     the intervals and the verification behind it are untouched.
+// The candidate ids stay where the descent put them: units cut by k_units_small carry no offset into the blob (TileUnit::pad),
+// so there is nothing for the tiles to copy (the one-query path's AH_SEARCH_MULTI_IDS_BY_TILES needs the descent's own units).
+enum MidKind { MID_DOT16, MID_DIFF16_EUCLIDEAN, MID_DIFF16_MANHATTAN, MID_F32_EUCLIDEAN };
+static constexpr uint32_t kMidSteps = 4;                      // k-steps of a row requested together
+static constexpr uint32_t kMidStageVecs = kMidSteps * 8;      // uint4 of one query in a staged chunk
+static constexpr uint32_t kMidStagePasses = kUnitVisits * kMidStageVecs / 256;
+static_assert(kMidStagePasses * 256 == kUnitVisits * kMidStageVecs, "a block stages a chunk of 16 queries in whole passes");
+
+// (LDS traffic only: the row loads of the chunk stay in flight across it)
+__device__ __forceinline__ void mid_lds_barrier() {
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+}
+
+// What lane j of an octet does with the 16 bytes it holds of a row (x) and of a query (y) in one k-step.
+template <int KIND>
+struct MidOps {
+    static constexpr bool kF32 = KIND == MID_F32_EUCLIDEAN, kDiff = KIND == MID_DIFF16_EUCLIDEAN || KIND == MID_DIFF16_MANHATTAN;
+    struct Wide { float w[8]; };
+    typedef std::conditional_t<kF32, float4, float> Acc;
+    typedef std::conditional_t<kDiff, Wide, uint4> Operand;  // (the difference screen widens every loaded uint4 once)
+    static __device__ __forceinline__ Acc zero() {
+        if constexpr (kF32) return make_float4(0.f, 0.f, 0.f, 0.f);
+        else return 0.f;
+    }
+    static __device__ __forceinline__ Operand prepare(const uint4 v) {
+        if constexpr (kDiff) {
+            Wide r;
+            widen_halves8(v, r.w);
+            return r;
+        } else return v;
+    }
+    static __device__ __forceinline__ void step(const Operand &x, const Operand &y, Acc &acc) {
+        if constexpr (kF32) {
+            fma_step<OP_EUCLID>(acc, __builtin_bit_cast(float4, y), __builtin_bit_cast(float4, x));
+        } else if constexpr (kDiff) {
+#pragma unroll
+            for (int i = 0; i < 8; i++) {
+                const float d = y.w[i] - x.w[i];
+                acc = KIND == MID_DIFF16_EUCLIDEAN ? fmaf(d, d, acc) : acc + fabsf(d);
+            }
+        } else acc = screen_dot8(x, y, acc);
+    }
+};
+
+// One slab of one unit: rows [row_begin + 2 o, + 2) of octet o = threadIdx.x / 8 against the unit's first Q visits (those past
+// n_vis compute on whatever the slots hold and store nothing).  s_vis: the unit's visits; s_q: the staged chunk (FROM_LDS).
+template <int KIND, int Q, bool FROM_LDS>
+__device__ __forceinline__ void mid_tile(const DataView &dv, const ScreenSearch &ss, const uint8_t *__restrict__ qvecs, uint64_t qstride,
+                                         const uint32_t *__restrict__ leaf_ids, uint32_t row_begin, uint32_t n_rows, const Visit *s_vis,
+                                         uint32_t n_vis, uint4 *s_q, float *__restrict__ dist, uint32_t stride, uint32_t *err) {
+    typedef MidOps<KIND> OPS;
+    constexpr uint32_t KC = kMidSteps;
+    const uint32_t tid = threadIdx.x, j = tid & 7u, r0 = row_begin + 2u * (tid >> 3);
+    const uint32_t steps = OPS::kF32 ? dv.dims >> 5 : ss.hpitch >> 6;
+    auto query = [&](uint32_t q) {  // the operand of query q: its f32 leaf, or its binary16 copy
+        return OPS::kF32 ? reinterpret_cast<const uint4 *>(qvecs + (uint64_t)q * qstride)
+                         : reinterpret_cast<const uint4 *>(ss.q16 + (uint64_t)q * ss.hpitch);
+    };
+    const uint4 *r4[2];
+    uint64_t row[2];
+#pragma unroll
+    for (int u = 0; u < 2; u++) {
+        row[u] = row_of_id(dv, leaf_ids[min(r0 + u, n_rows - 1)]);
+        const uint64_t at = row[u] == ~0ull ? 0ull : row[u];
+        r4[u] = (OPS::kF32 ? reinterpret_cast<const uint4 *>(dv.rows_f32 + at * dv.pitch) : reinterpret_cast<const uint4 *>(ss.rows16 + at * ss.hpitch)) + j;
+    }
+    const uint4 *q4[Q];
+    if constexpr (!FROM_LDS) {
+#pragma unroll
+        for (int t = 0; t < Q; t++) q4[t] = query(s_vis[min((uint32_t)t, n_vis - 1)].q) + j;
+    }
+    typename OPS::Acc acc[2][Q];
+#pragma unroll
+    for (int u = 0; u < 2; u++)
+#pragma unroll
+        for (int t = 0; t < Q; t++) acc[u][t] = OPS::zero();
+    // FROM_LDS: thread w of pass p stages vector e = w mod 32 of query w / 32 of the chunk — slot (t KC + f) 8 + j is lane j's
+    // operand of query t in step f
+    const uint4 *st_src[kMidStagePasses];
+    if constexpr (FROM_LDS) {
+#pragma unroll
+        for (uint32_t p = 0; p < kMidStagePasses; p++) {
+            const uint32_t w = tid + p * 256u;
+            st_src[p] = query(s_vis[min(w / kMidStageVecs, n_vis - 1)].q) + (w % kMidStageVecs);
+        }
+    }
+    auto stage_load = [&](uint4 (&st)[kMidStagePasses], uint32_t k0, uint32_t kc) {
+#pragma unroll
+        for (uint32_t p = 0; p < kMidStagePasses; p++) {
+            const uint32_t w = tid + p * 256u;
+            st[p] = w < n_vis * kMidStageVecs && (w % kMidStageVecs) < kc * 8u ? st_src[p][k0 * 8u] : make_uint4(0u, 0u, 0u, 0u);
+        }
+    };
+    auto stage_store = [&](const uint4 (&st)[kMidStagePasses]) {
+        mid_lds_barrier();  // everybody has read the chunk before
+#pragma unroll
+        for (uint32_t p = 0; p < kMidStagePasses; p++) s_q[tid + p * 256u] = st[p];
+        mid_lds_barrier();
+    };
+    // one k-step: both rows against query t's operand y(t), one query at a time (FROM_LDS: sixteen operands are not held at once)
+    auto step_all = [&](const uint4 (&x)[2], auto &&y) {
+        const typename OPS::Operand x0 = OPS::prepare(x[0]), x1 = OPS::prepare(x[1]);
+#pragma unroll
+        for (int t = 0; t < Q; t++) {
+            const typename OPS::Operand yt = OPS::prepare(y(t));
+            OPS::step(x0, yt, acc[0][t]);
+            OPS::step(x1, yt, acc[1][t]);
+        }
+    };
+    uint32_t k = 0;
+    for (; k + KC <= steps; k += KC) {
+        uint4 st[kMidStagePasses], x[KC][2], y[FROM_LDS ? 1 : KC][Q];  // (y: the register path's operands)
+        if constexpr (FROM_LDS) {
+            stage_load(st, k, KC);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+#pragma unroll
+        for (uint32_t f = 0; f < KC; f++) {
+            x[f][0] = r4[0][(k + f) * 8], x[f][1] = r4[1][(k + f) * 8];
+            if constexpr (!FROM_LDS) {
+#pragma unroll
+                for (int t = 0; t < Q; t++) y[f][t] = q4[t][(k + f) * 8];
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        if constexpr (FROM_LDS) stage_store(st);
+#pragma unroll
+        for (uint32_t f = 0; f < KC; f++) {
+            if constexpr (FROM_LDS) step_all(x[f], [&](int t) { return s_q[((uint32_t)t * KC + f) * 8u + j]; });
+            else step_all(x[f], [&](int t) { return y[f][t]; });
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    if (k < steps) {  // block-uniform: the last steps of a row that is no multiple of KC steps long, one trip each
+        if constexpr (FROM_LDS) {
+            uint4 st[kMidStagePasses];
+            stage_load(st, k, steps - k);
+            stage_store(st);
+        }
+        for (uint32_t f = 0; k + f < steps; f++) {
+            uint4 x[2];
+            x[0] = r4[0][(k + f) * 8], x[1] = r4[1][(k + f) * 8];
+            if constexpr (FROM_LDS) step_all(x, [&](int t) { return s_q[((uint32_t)t * KC + f) * 8u + j]; });
+            else step_all(x, [&](int t) { return q4[t][(k + f) * 8]; });
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < 2; u++) {
+        const uint32_t r = r0 + u;
+        const bool missing = row[u] == ~0ull;
+        // Cosine: the row's stored norm next to its screen value (cosine.rs:21-24)
+        const float xn = KIND == MID_DOT16 && ss.aux && !missing ? dv.headers[row[u]] : 0.0f;
+#pragma unroll
+        for (int t = 0; t < Q; t++) {
+            const Visit v = s_vis[min((uint32_t)t, n_vis - 1)];
+            float s;
+            if constexpr (OPS::kF32) {
+                s = octet_finish(acc[u][t]);
+                s = scalar_tail<OP_EUCLID>(s, reinterpret_cast<const float *>(query(v.q)), reinterpret_cast<const float *>(r4[u] - j), steps << 5, dv.dims);
+            } else s = octet_sum(acc[u][t]);
+            if (r >= n_rows || (uint32_t)t >= n_vis || j != 0) continue;
+            const uint64_t out = (uint64_t)v.q * stride + v.pos + r;
+            if (missing) atomicOr(err, 1u);
+            dist[out] = missing ? __uint_as_float(0x7FC00000u) : s;  // (screens — inf / NaN: an entry beyond 65504, not screened)
+            if (KIND == MID_DOT16 && ss.aux) ss.aux[out] = xn;
+            if (KIND == MID_DOT16 && ss.aux8) ss.aux8[out] = -1.0f;
+        }
+    }
+}
+
+// items: [count][unit << 16 | slab] as k_units_small lists them for this kernel (count 0: the list did not fit, or the visits
+// did not — the status word says which, and nothing here runs).
+template <int KIND>
+__global__ __launch_bounds__(256) AH_NO_PACKED_F32 void k_leaf_tiles_mid(DataView dv, ScreenSearch ss, const uint32_t *__restrict__ nns,
+                                                                        const Visit *__restrict__ sorted, const TileUnit *__restrict__ units,
+                                                                        const uint32_t *__restrict__ items, const uint8_t *__restrict__ qvecs,
+                                                                        uint64_t qstride, float *__restrict__ dist, uint32_t stride, uint32_t *err) {
+    __shared__ uint4 s_q[kUnitVisits * kMidStageVecs];
+    __shared__ Visit s_vis[kUnitVisits];
+    if (blockIdx.x >= items[0]) return;  // block-uniform
+    const uint32_t item = items[1u + blockIdx.x];
+    const TileUnit unit = units[item >> 16];
+    const uint32_t n_vis = min(unit.n_vis, kUnitVisits);
+    if (threadIdx.x < n_vis) s_vis[threadIdx.x] = sorted[unit.first + threadIdx.x];
+    mid_lds_barrier();
+    // the leaf's ids (those the candidate filter kept) as the descent wrote them for the unit's first visit
+    const Visit v0 = s_vis[0];
+    const uint32_t row_begin = (item & 0xFFFFu) * kTileSmallSlab, row_end = min(v0.n, row_begin + kTileSmallSlab);
+    if (n_vis == 0 || row_begin >= row_end) return;  // block-uniform; no listed item is like that
+    const uint32_t *leaf_ids = nns + (uint64_t)v0.q * stride + v0.pos;
+#define AH_MID(Q, FROM_LDS) \
+    mid_tile<KIND, Q, FROM_LDS>(dv, ss, qvecs, qstride, leaf_ids, row_begin, row_end, s_vis, n_vis, s_q, dist, stride, err)
+    if (n_vis > 8) AH_MID(16, true);
+    else if (n_vis > 4) AH_MID(8, true);
+    else if (n_vis > 2) AH_MID(4, false);
+    else if (n_vis == 2) AH_MID(2, false);
+    else AH_MID(1, false);
+#undef AH_MID
 }
 
 // ---- the leaf tiles of the three 1-bit metrics (AH_SEARCH_TILES_BQ) -----------------------------------------------------
@@ -4342,6 +4573,8 @@ static SearchKnobs search_knobs() {
     kn.small_units_max_queries = tun(TUN_SEARCH_SMALL_UNITS_MAX_QUERIES), kn.block_max_queries = tun(TUN_SEARCH_BLOCK_MAX_QUERIES);
     kn.multi_trees_per_block = tun(TUN_SEARCH_MULTI_TREES_PER_BLOCK), kn.multi_max_queries = tun(TUN_SEARCH_MULTI_MAX_QUERIES);
     kn.screen8_max_visits = tun(TUN_SEARCH_SCREEN8_MAX_VISITS);
+    kn.mid_tiles = tun(TUN_SEARCH_MID_TILES) != 0, kn.mid_tiles_max_queries = tun(TUN_SEARCH_MID_TILES_MAX_QUERIES);
+    kn.mid_items_cap = tun(TUN_SEARCH_MID_ITEMS_CAP);
     return kn;
 }
 
@@ -4589,7 +4822,7 @@ static int launch_units(ChunkCtx &c) {
     if (plan.units == UnitBuilder::UnitsSmall) {
         const QueriesH16 h16{b.d_qvecs, c.qstride(), ds->dims, ds->hpitch, b.d_q16, b.d_qstats};
         hipLaunchKernelGGL(k_units_small, dim3(1u + (plan.screened ? (unsigned)nq : 0u)), dim3(256), 0, s, b.d_visits, c.d_total(), plan.visit_cap,
-                           b.d_sorted, b.d_units, c.d_n_units(), b.d_err, h16, b.d_items, (uint32_t)plan.items_cap);
+                           b.d_sorted, b.d_units, c.d_n_units(), b.d_err, h16, b.d_items, (uint32_t)plan.items_cap, plan.mid_tiles ? 1u : 0u);
     } else if (plan.units == UnitBuilder::LeafScan) {
         hipLaunchKernelGGL(k_leaf_scan_block, dim3(plan.n_leaf_sums), dim3(256), 0, s, b.d_leaf_count, ix->n_nodes, b.d_cursor, b.d_ustart,
                            b.d_leaf_sums);
@@ -4636,6 +4869,17 @@ static int launch_tiles(ChunkCtx &c) {
         }
     };
     switch (plan.tile_launch) {
+    case TileLaunch::Mid: {  // (AH_SEARCH_MID_TILES: one block per (unit, slab) item of k_units_small's list)
+        auto mid_launch = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, dv, ss, b.d_nns, b.d_sorted, b.d_units, b.d_items, b.d_qvecs, qstride, b.d_dist,
+                               nns_stride, b.d_err);
+        };
+        if (!plan.screened) mid_launch(k_leaf_tiles_mid<MID_F32_EUCLIDEAN>);
+        else if (ds->metric == AH_EUCLIDEAN) mid_launch(k_leaf_tiles_mid<MID_DIFF16_EUCLIDEAN>);
+        else if (ds->metric == AH_MANHATTAN) mid_launch(k_leaf_tiles_mid<MID_DIFF16_MANHATTAN>);
+        else mid_launch(k_leaf_tiles_mid<MID_DOT16>);
+        break;
+    }
     case TileLaunch::Tiles8And16:
         // (the queries' int8 digits here, behind the descent: a small submission's query leaves are prepared BY its descent)
         hipLaunchKernelGGL(k_queries_i8, dim3((unsigned)nq), dim3(64), 0, s, b.d_qvecs, qstride, ds->dims, ss);
@@ -4827,6 +5071,12 @@ static int finish_tiles(ChunkCtx &c, hipError_t launch_err, TileOutcome &outcome
         if (plan.screened8) (void)screen8_window_note(ix->search8_seen, ix->search8_fails, false);
         (plan.bitmap_fits ? cs.s.dedup_flag_bitmap : cs.s.dedup_flag_hash) = nq;
         cs.commit(ix);
+        if (plan.mid_tiles) {
+            std::lock_guard<std::mutex> lk(ix->stats_mu);
+            ix->mid_stats.chunks += 1;
+            ix->mid_stats.queries += nq;
+            ix->mid_stats.items += h_err[SS_MID_ITEMS];
+        }
         if (diff) {
             (void)screen8_window_note(ix->search_diff_seen, ix->search_diff_fails, false);
             std::lock_guard<std::mutex> lk(ix->stats_mu);
@@ -4858,7 +5108,11 @@ static int finish_tiles(ChunkCtx &c, hipError_t launch_err, TileOutcome &outcome
         ix->diff_stats.chunks_screened += 1;
         ix->diff_stats.chunks_overflowed += overflowed ? 1 : 0;
     }
-    // a case the tiles do not reproduce (bits 2..5 of *err, see k_search_select / VisitSink): redo it the long way
+    if (plan.mid_tiles && launch_err == hipSuccess && *h_err != 0xFFFFFFFFu && (*h_err & 64u)) {
+        std::lock_guard<std::mutex> lk(ix->stats_mu);  // (bit 6: the item list of the mid tiles did not fit, k_units_small)
+        ix->mid_stats.chunks_overflowed += 1;
+    }
+    // a case the tiles do not reproduce (bits 2..6 of *err, see k_search_select / VisitSink / k_units_small): redo it the long way
     cs.s.fallback_chunks = 1;
     cs.s.fallback_non_finite = (*h_err & 4u) ? 1 : 0;
     cs.s.fallback_select = (*h_err & 8u) ? 1 : 0;
@@ -5240,6 +5494,17 @@ int ah_index_search_diff_stats(ah_index *ix, ah_search_diff_stats *out, int rese
         out->switched_off = ix->search_diff_off.load(std::memory_order_relaxed) ? 1 : 0;
     }
     if (reset) ix->diff_stats = ah_search_diff_stats{};
+    return AH_OK;
+    AH_GUARDED_END
+}
+
+// What the mid-size submissions' tile path served on this index (AH_SEARCH_MID_TILES); reset as above.
+int ah_index_mid_stats(ah_index *ix, ah_mid_stats *out, int reset) {
+    AH_GUARDED("ah_index_mid_stats")
+    AH_REQUIRE(ix, AH_ERR_INVALID_ARGUMENT, "index is NULL");
+    std::lock_guard<std::mutex> lk(ix->stats_mu);
+    if (out) *out = ix->mid_stats;
+    if (reset) ix->mid_stats = ah_mid_stats{};
     return AH_OK;
     AH_GUARDED_END
 }

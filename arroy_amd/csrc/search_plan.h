@@ -24,7 +24,8 @@ constexpr uint32_t kLeafScanItems = 2048;        // 256 threads x 8
 constexpr uint32_t kSmallVisits = 2048;          // visits one call of k_units_small holds
 constexpr uint32_t kHashMaxCandidates = 24576;   // candidates of a query k_flag_duplicates_hash holds
 constexpr uint32_t kSelectCap = 1024;            // keys the selections behind the tiles hold
-constexpr uint32_t kStatusWords = 16;            // the per-chunk status block (SS_WORDS)
+constexpr uint32_t kStatusWords = 17;            // the per-chunk status block (SS_WORDS; padded to 256 bytes in both layouts)
+constexpr uint32_t kMidMinQueries = 9;           // the first call past the small tiles' default (AH_SEARCH_MID_TILES)
 // 64-bit words of a 1-bit row k_leaf_tiles_bq takes (8192 dimensions).  A block keeps the rows of its unit's 16 queries in
 // LDS: 16 x 128 x 8 B = 16 KiB (beside 192 B of per-visit slots and norms; the walker itself holds nothing there), so the
 // eight blocks of 256 threads that fill a compute unit's 32 waves hold 128 KiB of its 160 KiB
@@ -38,6 +39,10 @@ struct SearchKnobs {
     long long small_tiles_max_queries, screen8_min_queries, small_units_max_queries, block_max_queries, multi_trees_per_block,
         multi_max_queries, screen8_max_visits;
     bool tiles_bq;  // AH_SEARCH_TILES_BQ: the sub-batches of the three 1-bit metrics through the tiles (k_leaf_tiles_bq)
+    // AH_SEARCH_MID_TILES: calls of kMidMinQueries .. mid_tiles_max_queries queries through k_leaf_tiles_mid, one block per
+    // (unit, slab) item; mid_items_cap != 0: the most items their list holds (test aid)
+    bool mid_tiles;
+    long long mid_tiles_max_queries, mid_items_cap;
 };
 
 // One sub-batch as the plan sees it.
@@ -74,7 +79,7 @@ struct ChunkShape {
 
 enum class Descent : uint8_t { Octet, WaveBig, WaveSmallBig, Block, Multi };  // of the tile pass; k_descend<false> follows the waves
 enum class UnitBuilder : uint8_t { None, Descent, UnitsSmall, LeafScan };     // None: no tile pass
-enum class TileLaunch : uint8_t { None, Tiles8And16, Flat, ItemList, Small2D, Big2D, F32 };
+enum class TileLaunch : uint8_t { None, Tiles8And16, Flat, ItemList, Small2D, Big2D, F32, Mid };
 enum class Flagger : uint8_t { None, Fused, Bitmap, Hash };                   // nns.dedup() of the tile pass
 enum class SortedDedup : uint8_t { Bitmap, SortLds, SortGlobal };             // ... of the sorted path
 
@@ -105,6 +110,7 @@ struct ChunkPlan {
     Flagger flagger = Flagger::None;
     uint32_t max_vis8 = 0;
     bool tiles_bq = false;  // the tile launch is k_leaf_tiles_bq: the exact distances of 1-bit rows, nothing screened
+    bool mid_tiles = false;  // the tile launch is k_leaf_tiles_mid over the items k_units_small lists in slabs of kTileSmallSlab rows
 };
 
 // The descent runs one wave (or block) per query: AH_SEARCH_WAVE, a query leaf of at most 32 KiB (it is kept in LDS), and
@@ -240,7 +246,16 @@ inline ChunkPlan plan_chunk(const ChunkShape &z, const SearchKnobs &kn) {
         p.descent = p.small_first ? Descent::WaveSmallBig : Descent::WaveBig;
     p.units = p.single_fused ? UnitBuilder::Descent : p.small_units ? UnitBuilder::UnitsSmall : UnitBuilder::LeafScan;
     const bool items_made = p.units == UnitBuilder::UnitsSmall && p.items_cap != 0;
-    if (p.screened8) {
+    // A mid-size submission (AH_SEARCH_MID_TILES): past the small tiles, up to what k_units_small places; a binary16 screen
+    // (Cosine, DotProduct, the difference screen) or Euclidean's f32 rows, never the int8 stage or the 1-bit tiles.  Every unit
+    // is listed in slabs of kTileSmallSlab rows: a unit lists at most one slab more than its first visit has whole ones, so
+    // items_cap as sized above always holds them — only the test aid makes the list shorter.
+    p.mid_tiles = kn.mid_tiles && nq >= kMidMinQueries && (long long)nq <= kn.mid_tiles_max_queries && !p.small_tiles && !p.screened8 &&
+                  !p.tiles_bq && (p.screened || z.metric == AH_EUCLIDEAN) && items_made && z.dims >= 32 && small_slabs <= 65535u;
+    if (p.mid_tiles && kn.mid_items_cap > 0) p.items_cap = std::min<uint64_t>(p.items_cap, (uint64_t)kn.mid_items_cap + 1);
+    if (p.mid_tiles) {  // one block per listed item; the blocks past the list's length leave at once
+        p.tile_launch = TileLaunch::Mid, p.tile_grid_x = (unsigned)(p.items_cap - 1), p.tile_grid_y = 1;
+    } else if (p.screened8) {
         // the leaves few queries reached on the int8 copy (a quarter of the f32 bytes, a wider band of survivors), the leaves
         // many queries share on the binary16 copy as before; the selection takes every candidate's bound from its own stage
         p.tile_launch = TileLaunch::Tiles8And16, p.tile_grid_x = 2048, p.tile_grid_y = tile_slabs;

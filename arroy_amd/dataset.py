@@ -917,6 +917,13 @@ class Index:
         _lib.check(_lib.lib().ah_index_search_diff_stats(self._h, C.byref(st), 1 if reset else 0))
         return {f: getattr(st, f) for f, _ in _lib.AhSearchDiffStats._fields_}
 
+    def mid_stats(self, reset: bool = False) -> dict:
+        """ah_index_mid_stats: what the tile path of mid-size submissions served (tunable AH_SEARCH_MID_TILES=1, 9 to 64
+        queries a call): sub-batches and queries through it, (unit, slab) items launched, sub-batches whose list overflowed."""
+        st = _lib.AhMidStats()
+        _lib.check(_lib.lib().ah_index_mid_stats(self._h, C.byref(st), 1 if reset else 0))
+        return {f: int(getattr(st, f)) for f, _ in _lib.AhMidStats._fields_}
+
     def route_items(self, item_ids: Sequence[int], tree_seeds: Sequence[int]) -> np.ndarray:
         """Incremental routing (src/writer.rs:1398-1459): [n_trees, n] forest-local Descendants node per item."""
         ids = _u32(item_ids)

@@ -57,7 +57,8 @@ extern "C" {
                                   ah_index_drop_trees; ah_index_create_from_encoded; ah_index_encode_nodes;
                                   ah_index_create_from_legacy;
                                   ah_dataset_rerank_diff_stats (the difference screen of Euclidean / Manhattan lists);
-                                  ah_index_search_diff_stats (the same screen in the tile pass of ah_search_batch) */
+                                  ah_index_search_diff_stats (the same screen in the tile pass of ah_search_batch);
+                                  ah_index_mid_stats (the tile path of submissions of 9 to 64 queries, AH_SEARCH_MID_TILES) */
 
 /* every entry point is exported from the shared object (it is built with -fvisibility=hidden) */
 #if defined(__GNUC__)
@@ -700,6 +701,17 @@ typedef struct ah_search_diff_stats {
     uint64_t switched_off;       /* 1: eight overflows within one window of 64 sub-batches switched the stage off           */
 } ah_search_diff_stats;
 AH_API int ah_index_search_diff_stats(ah_index *index, ah_search_diff_stats *out, int reset);
+/* The tile path of mid-size submissions (tunable AH_SEARCH_MID_TILES=1, default 0): a sub-batch of 9 to
+ * AH_SEARCH_MID_TILES_MAX_QUERIES (64) queries of ah_search_batch / _filters / _params whose plan is a screened or f32 leaf-tile
+ * plan launches one block per (work unit, slab of 64 rows) item instead of the big submissions' grid: the same ids and distance
+ * bits.  reset != 0 zeroes the counters after the copy.  An addition to v7: a caller that needs it looks the symbol up. */
+typedef struct ah_mid_stats {
+    uint64_t chunks;             /* sub-batches that took the mid tiles                                                     */
+    uint64_t queries;            /* queries in those sub-batches                                                            */
+    uint64_t items;              /* (unit, slab) items launched                                                             */
+    uint64_t chunks_overflowed;  /* sub-batches whose item list did not fit and were redone the long way                    */
+} ah_mid_stats;
+AH_API int ah_index_mid_stats(ah_index *index, ah_mid_stats *out, int reset);
 
 /* ------------------------------------------------------------------------------------------
  * Resident candidate filters (ABI v7 addition: look the symbols up).  `QueryBuilder::candidates` (src/reader.rs:110-123)
