@@ -3098,12 +3098,24 @@ struct MidOps {
     }
 };
 
+// One slab of kTileSmallSlab positions of a leaf as the visits of a MIXED sub-batch see it (k_leaf_tiles_mixed, in LDS): bit p
+// of keep[t] says whether visit t's filter keeps the id at position p of the slab, base[t] counts the ids it keeps before the
+// slab, and ids / pos list the positions some visit keeps, compacted in leaf order.
+struct MixedSlab {
+    uint64_t keep[kUnitVisits];
+    uint32_t base[kUnitVisits];
+    uint32_t ids[kTileSmallSlab], pos[kTileSmallSlab];
+};
+
 // One slab of one unit: rows [row_begin + 2 o, + 2) of octet o = threadIdx.x / 8 against the unit's first Q visits (those past
 // n_vis compute on whatever the slots hold and store nothing).  s_vis: the unit's visits; s_q: the staged chunk (FROM_LDS).
-template <int KIND, int Q, bool FROM_LDS>
+// MIXED: leaf_ids are mx->ids (row r of them is position mx->pos[r] of the slab) and a pair's distance goes to the rank of the
+// row among the ids the VISIT's filter keeps of the leaf — where its own descent put that id; a pair it does not keep is dropped.
+template <int KIND, int Q, bool FROM_LDS, bool MIXED = false>
 __device__ __forceinline__ void mid_tile(const DataView &dv, const ScreenSearch &ss, const uint8_t *__restrict__ qvecs, uint64_t qstride,
                                          const uint32_t *__restrict__ leaf_ids, uint32_t row_begin, uint32_t n_rows, const Visit *s_vis,
-                                         uint32_t n_vis, uint4 *s_q, float *__restrict__ dist, uint32_t stride, uint32_t *err) {
+                                         uint32_t n_vis, uint4 *s_q, float *__restrict__ dist, uint32_t stride, uint32_t *err,
+                                         const MixedSlab *mx = nullptr) {
     typedef MidOps<KIND> OPS;
     constexpr uint32_t KC = kMidSteps;
     const uint32_t tid = threadIdx.x, j = tid & 7u, r0 = row_begin + 2u * (tid >> 3);
@@ -3215,7 +3227,18 @@ __device__ __forceinline__ void mid_tile(const DataView &dv, const ScreenSearch 
                 s = scalar_tail<OP_EUCLID>(s, reinterpret_cast<const float *>(query(v.q)), reinterpret_cast<const float *>(r4[u] - j), steps << 5, dv.dims);
             } else s = octet_sum(acc[u][t]);
             if (r >= n_rows || (uint32_t)t >= n_vis || j != 0) continue;
-            const uint64_t out = (uint64_t)v.q * stride + v.pos + r;
+            uint32_t at = r;
+            if constexpr (MIXED) {
+                const uint32_t p = mx->pos[r];
+                const uint64_t kept = mx->keep[t];
+                if (!((kept >> p) & 1ull)) continue;
+                at = mx->base[t] + (uint32_t)__popcll(kept & ((1ull << p) - 1ull));
+                if (at >= v.n) {  // (a bitmap that changed under the call: never outside the visit's run; the sub-batch is redone)
+                    atomicOr(err, 32u);
+                    continue;
+                }
+            }
+            const uint64_t out = (uint64_t)v.q * stride + v.pos + at;
             if (missing) atomicOr(err, 1u);
             dist[out] = missing ? __uint_as_float(0x7FC00000u) : s;  // (screens — inf / NaN: an entry beyond 65504, not screened)
             if (KIND == MID_DOT16 && ss.aux) ss.aux[out] = xn;
@@ -3252,6 +3275,97 @@ __global__ __launch_bounds__(256) AH_NO_PACKED_F32 void k_leaf_tiles_mid(DataVie
     else if (n_vis == 2) AH_MID(2, false);
     else AH_MID(1, false);
 #undef AH_MID
+}
+
+// ---- the leaf tiles of a MIXED sub-batch (AH_SEARCH_MIXED_TILES) ----------------------------------------------------------
+// The queries of a mixed sub-batch are under different candidate filters, so the visits of one leaf kept different ids of it
+// and no visit's kept list serves the others.  The unit stays the leaf all the same — queries of one submission meet in the
+// same leaves, and keying units by (leaf, filter) would read a row once per query that wants it.  This kernel reads the FULL
+// leaf, desc[nd.a .. nd.a + nd.b), in slabs of kTileSmallSlab positions, and decides per (row, visit) pair whether the pair
+// exists and where its distance goes:
+//   * membership, once per block: wave w asks the filters of visits w, w + 4, ..., lane p the id at position p of the slab; one
+//     ballot per visit is keep[t].  The same ballots over the positions before the slab count base[t], the ids the visit's
+//     filter keeps of [0, 64 s) — at most nd.b x n_vis probes of bitmaps that lie in L2, none for an unfiltered visit.
+//     (The alternative, one block walking all slabs of its leaf and carrying the bases, probes every position once, but makes
+//     a leaf of four slabs one block's work where the grid has four: the launch of a small call is bound by its longest block.
+//     At 1536 dimensions, 24 slabs a leaf, the recounting is what the measured call costs, and that walk is the next step —
+//     DESIGN.md 4 "Mixed sub-batches through the leaf tiles".)
+//   * the rows: the union of the keep words, compacted in leaf order.  A row no visit keeps never leaves memory; a slab whose
+//     union is empty is left at once.
+//   * the accumulation is mid_tile's, untouched: octet o takes compacted rows 2 o, 2 o + 1 against ALL visits of the unit in
+//     lock step, so a pair whose keep bit is clear is computed and dropped — the price of shared accumulators, largest for
+//     disjoint filters.
+//   * the store: slot pos + base[t] + popcount(keep[t] below p) of the visit's query — copy_filtered keeps leaf order, so
+//     that is where the descent put the id.  From there on dist / aux / the candidate buffer of every query are what a
+//     uniform sub-batch of that query alone would have left.
+// grid: blockIdx.x walks the units persistently, blockIdx.y is the slab of the full leaf.
+template <int KIND>
+__global__ __launch_bounds__(256) AH_NO_PACKED_F32 void k_leaf_tiles_mixed(DataView dv, ScreenSearch ss, const DNode *__restrict__ nodes,
+                                                                          const uint32_t *__restrict__ desc,
+                                                                          const FilterSlot *__restrict__ filter_table,
+                                                                          const uint32_t *__restrict__ filter_of_query,
+                                                                          const Visit *__restrict__ sorted, const TileUnit *__restrict__ units,
+                                                                          const uint32_t *__restrict__ n_units_p, const uint8_t *__restrict__ qvecs,
+                                                                          uint64_t qstride, float *__restrict__ dist, uint32_t stride, uint32_t *err) {
+    __shared__ uint4 s_q[kUnitVisits * kMidStageVecs];
+    __shared__ Visit s_vis[kUnitVisits];
+    __shared__ MixedSlab s_mx;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t n_units = *n_units_p, slab_begin = blockIdx.y * kTileSmallSlab;
+    for (uint32_t u = blockIdx.x; u < n_units; u += gridDim.x) {
+        const TileUnit unit = units[u];
+        const uint32_t n_vis = min(unit.n_vis, kUnitVisits);
+        const DNode nd = nodes[unit.node];
+        if (n_vis == 0 || slab_begin >= nd.b) continue;  // block-uniform, as every `continue` below
+        __syncthreads();  // (the unit before is done with the LDS)
+        if (tid < n_vis) s_vis[tid] = sorted[unit.first + tid];
+        const uint32_t *leaf = desc + nd.a;
+        for (uint32_t t = wave; t < kUnitVisits; t += 4) {  // wave-uniform
+            uint64_t keep = 0;
+            uint32_t base = 0;
+            if (t < n_vis) {
+                const uint32_t slot = filter_of_query[sorted[unit.first + t].q];
+                if (slot == AH_NO_FILTER) {
+                    const uint32_t in_slab = min(kTileSmallSlab, nd.b - slab_begin);
+                    keep = in_slab == 64u ? ~0ull : (1ull << in_slab) - 1ull;
+                    base = slab_begin;
+                } else {
+                    const FilterSlot f = filter_table[slot];
+                    for (uint32_t p0 = 0; p0 <= slab_begin; p0 += kTileSmallSlab) {
+                        bool in = false;
+                        if (p0 + lane < nd.b) {
+                            const uint32_t id = leaf[p0 + lane];
+                            in = id < f.len_bits && ((f.bits[id >> 5] >> (id & 31u)) & 1u) != 0;
+                        }
+                        const uint64_t m = __ballot(in);
+                        if (p0 < slab_begin) base += (uint32_t)__popcll(m);
+                        else keep = m;
+                    }
+                }
+            }
+            if (lane == 0) s_mx.keep[t] = keep, s_mx.base[t] = base;
+        }
+        __syncthreads();
+        uint64_t wanted = 0;
+#pragma unroll
+        for (uint32_t t = 0; t < kUnitVisits; t++) wanted |= s_mx.keep[t];
+        if (wanted == 0) continue;  // no visit keeps a row of this slab
+        if (tid < kTileSmallSlab && ((wanted >> tid) & 1ull)) {
+            const uint32_t r = (uint32_t)__popcll(wanted & ((1ull << tid) - 1ull));
+            s_mx.ids[r] = leaf[slab_begin + tid];
+            s_mx.pos[r] = tid;
+        }
+        __syncthreads();
+        const uint32_t n_rows = (uint32_t)__popcll(wanted);
+#define AH_MIXED(Q, FROM_LDS) \
+    mid_tile<KIND, Q, FROM_LDS, true>(dv, ss, qvecs, qstride, s_mx.ids, 0u, n_rows, s_vis, n_vis, s_q, dist, stride, err, &s_mx)
+        if (n_vis > 8) AH_MIXED(16, true);
+        else if (n_vis > 4) AH_MIXED(8, true);
+        else if (n_vis > 2) AH_MIXED(4, false);
+        else if (n_vis == 2) AH_MIXED(2, false);
+        else AH_MIXED(1, false);
+#undef AH_MIXED
+    }
 }
 
 // ---- the leaf tiles of the three 1-bit metrics (AH_SEARCH_TILES_BQ) -----------------------------------------------------
@@ -4575,6 +4689,7 @@ static SearchKnobs search_knobs() {
     kn.screen8_max_visits = tun(TUN_SEARCH_SCREEN8_MAX_VISITS);
     kn.mid_tiles = tun(TUN_SEARCH_MID_TILES) != 0, kn.mid_tiles_max_queries = tun(TUN_SEARCH_MID_TILES_MAX_QUERIES);
     kn.mid_items_cap = tun(TUN_SEARCH_MID_ITEMS_CAP);
+    kn.mixed_tiles = tun(TUN_SEARCH_MIXED_TILES) != 0;
     return kn;
 }
 
@@ -4878,6 +4993,17 @@ static int launch_tiles(ChunkCtx &c) {
         else if (ds->metric == AH_EUCLIDEAN) mid_launch(k_leaf_tiles_mid<MID_DIFF16_EUCLIDEAN>);
         else if (ds->metric == AH_MANHATTAN) mid_launch(k_leaf_tiles_mid<MID_DIFF16_MANHATTAN>);
         else mid_launch(k_leaf_tiles_mid<MID_DOT16>);
+        break;
+    }
+    case TileLaunch::Mixed: {  // (AH_SEARCH_MIXED_TILES: the full leaf of every unit, each visit's own filter per (row, visit) pair)
+        auto mixed_launch = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, dv, ss, c.sp.nodes, c.sp.desc, c.sp.filter_table, c.sp.filter_of_query, b.d_sorted,
+                               b.d_units, d_n_units, b.d_qvecs, qstride, b.d_dist, nns_stride, b.d_err);
+        };
+        if (!plan.screened) mixed_launch(k_leaf_tiles_mixed<MID_F32_EUCLIDEAN>);
+        else if (ds->metric == AH_EUCLIDEAN) mixed_launch(k_leaf_tiles_mixed<MID_DIFF16_EUCLIDEAN>);
+        else if (ds->metric == AH_MANHATTAN) mixed_launch(k_leaf_tiles_mixed<MID_DIFF16_MANHATTAN>);
+        else mixed_launch(k_leaf_tiles_mixed<MID_DOT16>);
         break;
     }
     case TileLaunch::Tiles8And16:

@@ -43,6 +43,7 @@ struct SearchKnobs {
     // (unit, slab) item; mid_items_cap != 0: the most items their list holds (test aid)
     bool mid_tiles;
     long long mid_tiles_max_queries, mid_items_cap;
+    bool mixed_tiles;  // AH_SEARCH_MIXED_TILES: mixed sub-batches through the tiles, one unit per leaf whatever its visits' filters
 };
 
 // One sub-batch as the plan sees it.
@@ -79,7 +80,7 @@ struct ChunkShape {
 
 enum class Descent : uint8_t { Octet, WaveBig, WaveSmallBig, Block, Multi };  // of the tile pass; k_descend<false> follows the waves
 enum class UnitBuilder : uint8_t { None, Descent, UnitsSmall, LeafScan };     // None: no tile pass
-enum class TileLaunch : uint8_t { None, Tiles8And16, Flat, ItemList, Small2D, Big2D, F32, Mid };
+enum class TileLaunch : uint8_t { None, Tiles8And16, Flat, ItemList, Small2D, Big2D, F32, Mid, Mixed };  // (recorded plans hold the number)
 enum class Flagger : uint8_t { None, Fused, Bitmap, Hash };                   // nns.dedup() of the tile pass
 enum class SortedDedup : uint8_t { Bitmap, SortLds, SortGlobal };             // ... of the sorted path
 
@@ -111,6 +112,9 @@ struct ChunkPlan {
     uint32_t max_vis8 = 0;
     bool tiles_bq = false;  // the tile launch is k_leaf_tiles_bq: the exact distances of 1-bit rows, nothing screened
     bool mid_tiles = false;  // the tile launch is k_leaf_tiles_mid over the items k_units_small lists in slabs of kTileSmallSlab rows
+    // a mixed sub-batch on the tile path (AH_SEARCH_MIXED_TILES): the tile launch is k_leaf_tiles_mixed over slabs of
+    // kTileSmallSlab positions of the FULL leaf, and nothing that reads "the kept ids of a unit's first visit" is on
+    bool mixed_tiles = false;
 };
 
 // The descent runs one wave (or block) per query: AH_SEARCH_WAVE, a query leaf of at most 32 KiB (it is kept in LDS), and
@@ -138,8 +142,9 @@ inline ChunkPlan plan_chunk(const ChunkShape &z, const SearchKnobs &kn) {
     p.bitmap_fits = kn.bitmap && p.bitmap_words <= kBitmapMaxWords;
     // nns.dedup() of the tiles: the LDS bitmap, or a hash set of the candidates when the id space is too big for it
     p.hash_fits = z.nns_stride <= kHashMaxCandidates && z.max_id != 0xFFFFFFFFu;
-    // (never in a mixed sub-batch: the tiles read the kept ids of a leaf from ONE of its visits for all of them, k_leaf_tiles;
-    // without them no descent is a last pass, so k_descend_multi and the units of a single query are out as well)
+    // (a mixed sub-batch only under AH_SEARCH_MIXED_TILES: every other tile kernel reads the kept ids of a leaf from ONE of its
+    // visits for all of them, k_leaf_tiles; k_leaf_tiles_mixed reads the full leaf and asks every visit's own filter.  Without
+    // the tiles no descent is a last pass, so k_descend_multi and the units of a single query are out as well)
     // (count <= kSelectCap: the selections behind the tiles hold kSelectCap keys and select at least min(count, distinct
     // candidates) of them, so a larger count could only do the whole tile pass, overflow and be redone — after an int8 pass and
     // its binary16 retry where that stage is on, each noted as a failure of the int8 stage in its window of 64 sub-batches.
@@ -148,8 +153,10 @@ inline ChunkPlan plan_chunk(const ChunkShape &z, const SearchKnobs &kn) {
     // dims >= 32 the width must fit the LDS of k_leaf_tiles_bq)
     const bool bq_wanted = kn.tiles_bq && z.metric >= AH_BQ_EUCLIDEAN;
     const bool width_fits = bq_wanted ? (z.dims + 63u) / 64u <= kBqTileMaxWords : z.dims >= 32;
-    const bool tiles_fit = !z.mixed && kn.tiles && (p.bitmap_fits || p.hash_fits) && !p.big_k && (k <= kSelectCap || z.nns_stride <= kSelectCap) &&
-                           width_fits && z.max_desc <= 65535u * kTileSlab;
+    // (the slabs of kTileSmallSlab rows the largest leaf has: grid.y of the small and the mixed tiles)
+    const unsigned small_slabs = std::max(1u, (z.max_desc + kTileSmallSlab - 1) / kTileSmallSlab);
+    const bool tiles_fit = (!z.mixed || (kn.mixed_tiles && small_slabs <= 65535u)) && kn.tiles && (p.bitmap_fits || p.hash_fits) && !p.big_k &&
+                           (k <= kSelectCap || z.nns_stride <= kSelectCap) && width_fits && z.max_desc <= 65535u * kTileSlab;
     // certified top-k screen of the tile re-rank: the binary16 shadow of the rows must exist (ah_index_create makes it).
     // Cosine / DotProduct by the dot product of the copies; Euclidean / Manhattan by their difference (k_leaf_tiles_diff16),
     // when AH_SEARCH_SCREEN_DIFF asks for it and the index has not switched it off — never with an int8 stage
@@ -158,19 +165,24 @@ inline ChunkPlan plan_chunk(const ChunkShape &z, const SearchKnobs &kn) {
     // (Manhattan's reference distance is a sequential sum: no f32 tile — it takes the tiles only behind the screen)
     // (the 1-bit distances are exact integers of a popcount: their tiles need no screen, so screened, screened8, fuse_prepare
     // and fused_flag stay off and no binary16 or int8 copy is made or read)
-    p.tiles_bq = tiles_fit && bq_wanted;
-    p.tiles = tiles_fit && (z.metric == AH_EUCLIDEAN || z.metric == AH_COSINE || z.metric == AH_DOT_PRODUCT || diff_screened || p.tiles_bq);
+    p.tiles_bq = tiles_fit && bq_wanted && !z.mixed;
+    p.screened = screen_fit && (z.metric == AH_COSINE || z.metric == AH_DOT_PRODUCT || diff_screened);
+    // (a mixed sub-batch: the row formats k_leaf_tiles_mixed serves — a binary16 screen, or Euclidean's f32 rows.  Unscreened
+    // Cosine / DotProduct, Manhattan without the difference screen and the 1-bit metrics keep the sorted path)
+    p.tiles = tiles_fit && (z.mixed ? p.screened || z.metric == AH_EUCLIDEAN
+                                    : z.metric == AH_EUCLIDEAN || z.metric == AH_COSINE || z.metric == AH_DOT_PRODUCT || diff_screened || p.tiles_bq);
+    p.mixed_tiles = p.tiles && z.mixed;
     p.visit_cap = (uint32_t)std::min<uint64_t>((uint64_t)nq * z.nns_stride, 2u << 20);
     p.n_leaf_sums = (z.n_nodes + kLeafScanItems - 1) / kLeafScanItems;
-    p.screened = screen_fit && (z.metric == AH_COSINE || z.metric == AH_DOT_PRODUCT || diff_screened);
-    // ... and on the int8 copy before that (round 6): the submissions of at least AH_SEARCH_SCREEN8_MIN_QUERIES queries (65: past
+    // the screen (p.screened) ... and on the int8 copy before that (round 6): the submissions of at least AH_SEARCH_SCREEN8_MIN_QUERIES queries (65: past
     // the small ones' unit builder).  From 9 queries a call the leaf tiles are bound by the bytes of their rows (64 queries: 294 of
     // the call's 508 us) and the int8 rows do cut them to 249 — but the wider band of survivors costs the selection 65 -> 95 us
     // and the queries' digits a launch: 511 us against 502, measured, so the default leaves those calls on binary16; see ScreenSearch
-    p.screened8 = p.screened && !diff_screened && z.allow8 && kn.screen8 && !z.search8_off &&
+    // (mixed_tiles: never — k_leaf_tiles8 reads the first visit's kept ids; nor the item list, which counts its slabs from them)
+    p.screened8 = p.screened && !p.mixed_tiles && !diff_screened && z.allow8 && kn.screen8 && !z.search8_off &&
                   (long long)nq > std::max(kn.small_tiles_max_queries, kn.screen8_min_queries - 1) && z.screen8_ready;
     // (a few queries a call: the list of (unit, slab) pairs k_units_small leaves for the tile launch)
-    p.items_cap = p.tiles && (long long)nq <= kn.small_units_max_queries && kn.item_list
+    p.items_cap = p.tiles && !p.mixed_tiles && (long long)nq <= kn.small_units_max_queries && kn.item_list
                       ? nq * ((size_t)z.nns_stride / kTileSmallSlab + 1) + kSmallVisits + 1
                       : 0;
     // (a small submission: the kernel that prepares the query leaves reads the pinned staging buffer itself — 6 KB over the link
@@ -213,11 +225,10 @@ inline ChunkPlan plan_chunk(const ChunkShape &z, const SearchKnobs &kn) {
     // a small submission: slabs of 64 rows (a dozen leaves then fill 150 CUs instead of 50) and a grid that does not
     // dispatch 24 000 blocks to find 12 units
     const unsigned tile_slabs = std::max(1u, (z.max_desc + kTileSlab - 1) / kTileSlab);
-    const unsigned small_slabs = std::max(1u, (z.max_desc + kTileSmallSlab - 1) / kTileSmallSlab);
     // (never with the int8 stage: that one starts past AH_SEARCH_SMALL_TILES_MAX_QUERIES queries)
     // (tiles_bq: small_units, items_cap and the small tiles hold for it — k_units_small knows no metric and makes the binary16
     // copies only when screened; what needs the block descent is off with block_ok above)
-    p.small_tiles = (p.screened || p.tiles_bq) && !p.screened8 && (long long)nq <= kn.small_tiles_max_queries && small_slabs <= 65535u;
+    p.small_tiles = (p.screened || p.tiles_bq) && !p.screened8 && !p.mixed_tiles && (long long)nq <= kn.small_tiles_max_queries && small_slabs <= 65535u;
     if (!z.wave_descent)
         p.descent = Descent::Octet;
     else if (p.small_first && p.block_ok) {
@@ -228,7 +239,8 @@ inline ChunkPlan plan_chunk(const ChunkShape &z, const SearchKnobs &kn) {
         // each (k_descend_multi) — one query on G compute units.  Only as the last pass (what it cannot hold takes the long way).
         const uint32_t per_block = (uint32_t)std::min<long long>(8, std::max<long long>(1, kn.multi_trees_per_block));
         const uint32_t multi_blocks = std::min<uint32_t>(kMultiMaxBlocks, (z.n_trees + per_block - 1) / per_block);
-        const bool multi = kn.multi && multi_blocks >= 2 && (long long)nq <= std::min<long long>(kn.multi_max_queries, kMultiMaxQueries);
+        // (mixed_tiles: the block descent, never k_descend_multi — with it go own_units, single_fused and ids_by_tiles)
+        const bool multi = kn.multi && !p.mixed_tiles && multi_blocks >= 2 && (long long)nq <= std::min<long long>(kn.multi_max_queries, kMultiMaxQueries);
         p.descent = multi ? Descent::Multi : Descent::Block;
         p.multi_blocks = multi ? multi_blocks : 0;
         // ... and a few queries whose descents write their own units, query by query (the flat tile launch reads them with
@@ -237,7 +249,7 @@ inline ChunkPlan plan_chunk(const ChunkShape &z, const SearchKnobs &kn) {
         const uint32_t units_per_query = (uint32_t)(p.visit_cap / std::max<size_t>(nq, 1));
         p.own_units = multi && nq > 1 && p.small_tiles && units_per_query >= kMultiCap && kn.multi_own_units && kn.flat_tiles;
         // (one query: its units and its binary16 copy come out of the descent itself, see SingleQueryOut)
-        p.single_fused = (nq == 1 || p.own_units) && p.small_units && kn.single_fused;
+        p.single_fused = (nq == 1 || p.own_units) && p.small_units && !p.mixed_tiles && kn.single_fused;
         if (p.single_fused) {
             p.units_per_query = nq == 1 ? 0u : units_per_query;
             p.ids_by_tiles = p.small_tiles && !z.uniform_filter && kn.multi_ids_by_tiles;
@@ -250,10 +262,12 @@ inline ChunkPlan plan_chunk(const ChunkShape &z, const SearchKnobs &kn) {
     // (Cosine, DotProduct, the difference screen) or Euclidean's f32 rows, never the int8 stage or the 1-bit tiles.  Every unit
     // is listed in slabs of kTileSmallSlab rows: a unit lists at most one slab more than its first visit has whole ones, so
     // items_cap as sized above always holds them — only the test aid makes the list shorter.
-    p.mid_tiles = kn.mid_tiles && nq >= kMidMinQueries && (long long)nq <= kn.mid_tiles_max_queries && !p.small_tiles && !p.screened8 &&
+    p.mid_tiles = kn.mid_tiles && !p.mixed_tiles && nq >= kMidMinQueries && (long long)nq <= kn.mid_tiles_max_queries && !p.small_tiles && !p.screened8 &&
                   !p.tiles_bq && (p.screened || z.metric == AH_EUCLIDEAN) && items_made && z.dims >= 32 && small_slabs <= 65535u;
     if (p.mid_tiles && kn.mid_items_cap > 0) p.items_cap = std::min<uint64_t>(p.items_cap, (uint64_t)kn.mid_items_cap + 1);
-    if (p.mid_tiles) {  // one block per listed item; the blocks past the list's length leave at once
+    if (p.mixed_tiles) {  // blockIdx.x walks the units, blockIdx.y is the slab of the unit's FULL leaf
+        p.tile_launch = TileLaunch::Mixed, p.tile_grid_x = std::min<unsigned>(2048u, 32u * (unsigned)nq), p.tile_grid_y = small_slabs;
+    } else if (p.mid_tiles) {  // one block per listed item; the blocks past the list's length leave at once
         p.tile_launch = TileLaunch::Mid, p.tile_grid_x = (unsigned)(p.items_cap - 1), p.tile_grid_y = 1;
     } else if (p.screened8) {
         // the leaves few queries reached on the int8 copy (a quarter of the f32 bytes, a wider band of survivors), the leaves

@@ -768,7 +768,11 @@ AH_API int ah_filter_export(const ah_filter *f, uint64_t *out_len_bits, uint32_t
  * NULL = every query under filters[0] (n_filters == 1) or unfiltered (n_filters == 0).  Query q returns exactly what
  * ah_search_batch returns for it alone under the id list of its filter — the same ids and distance bits, whatever else is
  * in the call.  Runs of at least AH_SEARCH_FILTER_GROUP_MIN queries with one filter are served like a single-filter call
- * (uniform sub-batches); the rest share mixed sub-batches whose descents look up every query's own filter. */
+ * (uniform sub-batches); the rest share mixed sub-batches whose descents look up every query's own filter.  A mixed sub-batch
+ * takes the sorted re-rank; under the tunable AH_SEARCH_MIXED_TILES=1 (default 0) one whose rows are screened on binary16 or
+ * are Euclidean f32 takes the leaf tiles like a uniform one (k_leaf_tiles_mixed: the unit is the leaf, its rows are read once
+ * for all visits, every visit's own filter decides per (row, visit) pair): the same bits, counted in ah_search_stats as a
+ * tile sub-batch and in ah_filter_stats as a mixed one. */
 AH_API int ah_search_batch_filters(ah_index *index, const float *queries, const uint32_t *query_items, size_t nq, size_t count,
                                    size_t search_k, size_t oversampling, ah_filter *const *filters, size_t n_filters,
                                    const uint32_t *filter_of_query, uint32_t *out_ids, float *out_distances,

@@ -9,6 +9,9 @@ One process, one index.  Legs (queries/s or ms per call, median of `--reps` time
   (e) one composite filter a AND b (shares 0.5 x 0.5 and 0.5 x 0.01) made three ways, each alone and with the one-query search
       that follows: the host's list of the result through ah_filter_create, the host's bitmap through ah_filter_create_bitmap,
       ah_filter_combine of the two resident operands.  A library without the last two runs the list way only.
+  (m) (`--legs m` only) mixed sub-batches with AH_SEARCH_MIXED_TILES alternating 0 / 1 call by call: p50 / p99 per setting over
+      four filter sets, each under the default group min and as one mixed sub-batch (DESIGN.md §4 "Mixed sub-batches through
+      the leaf tiles"; profiles/mixed_tiles.txt).
 A library without ah_filter_create (the parent commit) runs the per-list legs only, so the same script measures both trees:
 run them alternating, three runs each, and compare every run of one with every run of the other.
 
@@ -104,6 +107,45 @@ def main():
                          timed(lambda: index.search(a.count, queries=queries, filters=filters, filter_of_query=slots, **kw), a.reps), a.nq)
             note(f"{name} {n_filters} filters: one call, default group min",
                  timed(lambda: index.search(a.count, queries=queries, filters=filters, filter_of_query=slots, **kw), a.reps), a.nq)
+            for f in filters:
+                f.close()
+    # (m) mixed sub-batches on the sorted path against the leaf tiles: AH_SEARCH_MIXED_TILES alternates 0 / 1 call by call inside
+    # this process (0 launches what a library without the switch launches), p50 / p99 per setting and the spread of each.
+    # Filter sets: (b)'s 8 and (c)'s 64 filters of mixed shares, 64 disjoint tenant filters of 1/64 of the ids each, and 64
+    # overlapping facet filters of half the ids each; every set with the default group min and as ONE mixed sub-batch.
+    def has_tunable(name):
+        try:
+            return _lib.tuning_get(name) is not None
+        except _lib.ArroyHipError:
+            return False
+
+    if "m" in a.legs and resident and has_tunable("AH_SEARCH_MIXED_TILES"):
+        steps = [2, 3, 5, 10, 20, 40, 100, 7]
+        sets = {"b 8 mixed shares": [ids[(i % 3)::steps[i % 8] + i // 8].copy() for i in range(8)],
+                "c 64 mixed shares": [ids[(i % 3)::steps[i % 8] + i // 8].copy() for i in range(64)],
+                "64 disjoint tenants": [ids[i::64].copy() for i in range(64)],
+                "64 overlapping facets": [np.sort(rng.choice(n, n // 2, replace=False)).astype(np.uint32) for _ in range(64)]}
+        for name, lists in sets.items():
+            filters = [index.make_filter(x, sorted=True) for x in lists]
+            slots = rng.integers(0, len(lists), a.nq).astype(np.uint32)
+            for gmin in (None, a.nq + 1):
+                t = {0: [], 1: []}
+                for rep in range(2 * (2 + 3 * a.reps)):
+                    on = rep & 1
+                    tun = dict(AH_SEARCH_MIXED_TILES=on, **({} if gmin is None else {"AH_SEARCH_FILTER_GROUP_MIN": gmin}))
+                    with _lib.tuning(**tun):
+                        t0 = time.perf_counter()
+                        index.search(a.count, queries=queries, filters=filters, filter_of_query=slots, **kw)
+                        if rep >= 4:  # (two warm-up calls per setting)
+                            t[on].append(time.perf_counter() - t0)
+                for on in (0, 1):
+                    p50, p99 = np.percentile(t[on], [50, 99])
+                    tag = f"m {name}, {'default group min' if gmin is None else 'one mixed sub-batch'}, switch {on}"
+                    out["legs"][tag] = {"p50_s": p50, "p99_s": p99, "min_s": min(t[on]), "max_s": max(t[on]), "calls": len(t[on]), "qps": a.nq / p50}
+                    print(f"{tag:72s} p50 {1e3 * p50:8.3f} ms  p99 {1e3 * p99:8.3f}  min {1e3 * min(t[on]):8.3f}  max {1e3 * max(t[on]):8.3f}  "
+                          f"({a.nq / p50:9.0f} queries/s)", flush=True)
+            st = index.stats()
+            print(f"  (ah_search_stats so far: rerank_tiles {st['rerank_tiles']}, rerank_sorted {st['rerank_sorted']}, fallback_chunks {st['fallback_chunks']})", flush=True)
             for f in filters:
                 f.close()
     # (e) the same composite filter a AND b made three ways, alone and with the one-query search that follows: the expression
