@@ -2299,6 +2299,160 @@ __global__ __launch_bounds__(256) void k_leaf_tiles(DataView dv, const uint32_t 
     }
 }
 
+// ---- the leaf tiles of Manhattan's exact rows (AH_SEARCH_TILES_MANHATTAN) -------------------------------------------------
+// `Manhattan::built_distance` (src/distance/manhattan.rs:44-46) is one sequential sum over the elements, so an octet cannot
+// share a (row, query) pair the way the tiles above do: octet_manhattan hands one running sum from lane to lane and throws seven
+// of every eight adds away.  Different pairs are independent, though.  Here a LANE owns one row of the slab against up to 8
+// visits: 8 chains r = f_add(r, |f_sub(x_i, q_i)|), i = 0 .. dims - 1 in order, in 8 accumulators that live over the whole
+// width — every add is used, and a lane has as many independent chains in flight as the unit's half has visits.
+//   Split.  <= 8 visits: the 256 lanes take the 256 rows of the slab.  9 .. 16: waves 0-1 take the slab's 128 rows against
+// visits 0 .. 7, waves 2-3 the same rows against visits 8 .. 15 (the rows are fetched twice, the second time from L2).
+//   Rows.  A wave streams its 64 rows through a wave-private ring in LDS, 32 dimensions (8 KiB) a chunk, by the DMA path of
+// leaf_tile_ring: 8 instructions a chunk, instruction i the rows 8 i .. 8 i + 7, octet u of the wave one whole 128-byte line of
+// row 8 i + u.  The DMA lands lane-linearly (lane s of an instruction at 16 s), so there is no row pitch to pad: the
+// transposition that keeps the reads free of bank conflicts is in WHICH 16 bytes of its line a lane fetches.  Lane p of octet u
+// fetches piece (p - (u >> 1) - 4 (i & 1)) mod 8, i.e. piece c of that row lies at
+//     1024 i + 128 u + 16 ((c + (u >> 1) + 4 (i & 1)) mod 8).
+// The reader of row 8 i + u is lane 8 i + u, and ds_read_b128 serves 16 consecutive lanes (i = 2 m, 2 m + 1; u = 0 .. 7) a
+// pass, 16 x 16 B = the 64 banks once when their addresses differ mod 256: 1024 i drops out, 128 u leaves 8 (u & 1), and among
+// the 8 lanes of either parity of u the rotation (u >> 1) + 4 (i & 1) takes 8 different values — 16 different 16-byte columns
+// for every piece c.  (A pitch of 144 bytes does the same for rows written from registers; that costs the 32 registers a chunk
+// in flight would hold, which the ring exists to avoid.)  kL1Depth = 2 chunks a wave: one summed, one in flight; 64 KiB a
+// block, so two blocks (8 waves) a compute unit keep 64 KiB of row loads outstanding — a third chunk would leave one block.
+//   Queries.  The 8 visits are the same for every lane of the wave, so their elements are read at wave-uniform addresses in the
+// constant address space — scalar loads, 8 dimensions of all visits (64 SGPRs) at a time — and enter v_sub_f32 as its scalar
+// operand.  As 16-byte LDS broadcasts they would be 64 reads a chunk beside the 8 of the rows, more LDS cycles than the
+// chunk's 512 VALU operations leave room for (counted from the shapes).  (The leaves were written by an earlier launch and no
+// launch writes them while the tiles run.)
+//   The tail (dims % 32) is summed from the same staged chunk — pitch is a multiple of 32, so the last chunk is there to
+// fetch — element by element up to dims, never the padding.
+static constexpr uint32_t kL1ChunkBytes = 64 * 128, kL1Depth = 2, kL1RingBytesPerWave = kL1Depth * kL1ChunkBytes;
+typedef const __attribute__((address_space(4))) ring_f4 *l1_query_f4;
+
+// One wave: rows row0 .. row0 + 63 of the leaf (those below row_end) against visits vis[0 .. n_vis), 1 <= n_vis <= NV.
+template <int NV>
+__device__ __forceinline__ void leaf_tile_l1(const DataView &dv, const uint32_t *__restrict__ leaf_ids, uint32_t row0, uint32_t row_end,
+                                             const Visit *__restrict__ vis, uint32_t n_vis, const uint8_t *__restrict__ qvecs, uint64_t qstride,
+                                             float *__restrict__ dist, uint32_t stride, uint32_t *err, uint8_t *ring) {
+    const uint32_t lane = threadIdx.x & 63u, oct = lane >> 3, j = lane & 7u;
+    const uint32_t n_chunks = (dv.dims + 31u) >> 5;  // (= pitch / 32: the last chunk of a row is whole in memory)
+    const uint32_t ring_addr = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint8_t *)ring;
+    // the row this lane sums (past the leaf's end: the last row again, summed and not stored)
+    const uint32_t r = row0 + lane;
+    const uint64_t row = row_of_id(dv, leaf_ids[min(r, row_end - 1)]);
+    const uint32_t my_row = row == ~0ull ? 0xFFFFFFFFu : (uint32_t)row;
+    // what this lane fetches for the ring: in instruction i, its octet's row 8 i + oct, the piece the rotation gives lane j
+    const uint8_t *src[8];
+#pragma unroll
+    for (uint32_t i = 0; i < 8; i++) {
+        const uint32_t fetched = (uint32_t)__shfl((int)my_row, (int)(i * 8 + oct));
+        const uint32_t piece = (j - (oct >> 1) - 4u * (i & 1u)) & 7u;
+        src[i] = reinterpret_cast<const uint8_t *>(dv.rows_f32 + (uint64_t)(fetched == 0xFFFFFFFFu ? 0u : fetched) * dv.pitch) + piece * 16;
+    }
+    auto issue = [&](uint32_t k) {
+        uint8_t *slot = ring + (k % kL1Depth) * kL1ChunkBytes;
+#pragma unroll
+        for (uint32_t i = 0; i < 8; i++)
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(src[i] + (uint64_t)k * 128),
+                                             (__attribute__((address_space(3))) void *)(slot + i * 1024), 16, 0, 0);
+    };
+    // ... and where it reads piece c of its own row (instruction oct, row j of it): x_addr + 16 ((c + rot) mod 8)
+    const uint32_t x_addr = ring_addr + oct * 1024 + j * 128, rot16 = 16u * ((j >> 1) + 4u * (oct & 1u));
+    l1_query_f4 qp[NV];
+#pragma unroll
+    for (int t = 0; t < NV; t++) qp[t] = (l1_query_f4)(qvecs + (uint64_t)vis[min((uint32_t)t, n_vis - 1)].q * qstride);
+    float acc[NV];
+#pragma unroll
+    for (int t = 0; t < NV; t++) acc[t] = 0.0f;
+    issue(0);
+    for (uint32_t k = 0; k < n_chunks; k++) {
+        if (k + 1 < n_chunks) {
+            issue(k + 1);  // (its slot: chunk k - 1, whose reads were waited for before they were summed)
+            asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+        } else {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+        const uint32_t chunk_addr = x_addr + (k % kL1Depth) * kL1ChunkBytes;
+        const uint32_t n_el = min(32u, dv.dims - (k << 5));
+        if (n_el == 32u) {
+            // two pieces a step, and the loop kept a loop: 8 dimensions of 8 visits are 64 SGPRs — unrolled, the compiler
+            // merges a visit's loads into 16 dwords, wants 128 SGPRs and spills them lane by lane into VGPRs (seen in its output)
+#pragma clang loop unroll(disable)
+            for (uint32_t c = 0; c < 8; c += 2) {
+                ring_f4 x0 = lds_read_f4(chunk_addr + ((c * 16 + rot16) & 112u)), x1 = lds_read_f4(chunk_addr + ((c * 16 + 16 + rot16) & 112u));
+                asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(x0), "+v"(x1)::"memory");
+#pragma unroll
+                for (int t = 0; t < NV; t++) {
+                    const ring_f4 q0 = qp[t][k * 8 + c], q1 = qp[t][k * 8 + c + 1];
+                    acc[t] = f_add(acc[t], fabsf(f_sub(x0.x, q0.x)));
+                    acc[t] = f_add(acc[t], fabsf(f_sub(x0.y, q0.y)));
+                    acc[t] = f_add(acc[t], fabsf(f_sub(x0.z, q0.z)));
+                    acc[t] = f_add(acc[t], fabsf(f_sub(x0.w, q0.w)));
+                    acc[t] = f_add(acc[t], fabsf(f_sub(x1.x, q1.x)));
+                    acc[t] = f_add(acc[t], fabsf(f_sub(x1.y, q1.y)));
+                    acc[t] = f_add(acc[t], fabsf(f_sub(x1.z, q1.z)));
+                    acc[t] = f_add(acc[t], fabsf(f_sub(x1.w, q1.w)));
+                }
+            }
+        } else {
+            for (uint32_t c = 0; c * 4 < n_el; c++) {
+                ring_f4 x = lds_read_f4(chunk_addr + ((c * 16 + rot16) & 112u));
+                asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(x)::"memory");
+                const uint32_t left = n_el - c * 4;  // 1 .. 4 elements of this piece are the row's
+#pragma unroll
+                for (int t = 0; t < NV; t++) {
+                    const ring_f4 q = qp[t][k * 8 + c];  // (within the query leaf's pitch floats)
+                    acc[t] = f_add(acc[t], fabsf(f_sub(x.x, q.x)));
+                    if (left > 1) acc[t] = f_add(acc[t], fabsf(f_sub(x.y, q.y)));
+                    if (left > 2) acc[t] = f_add(acc[t], fabsf(f_sub(x.z, q.z)));
+                    if (left > 3) acc[t] = f_add(acc[t], fabsf(f_sub(x.w, q.w)));
+                }
+            }
+        }
+    }
+    if (r >= row_end) return;
+    if (my_row == 0xFFFFFFFFu) atomicOr(err, 1u);
+#pragma unroll
+    for (int t = 0; t < NV; t++) {
+        if ((uint32_t)t >= n_vis) break;
+        const Visit v = vis[t];
+        dist[(uint64_t)v.q * stride + v.pos + r] = my_row == 0xFFFFFFFFu ? __uint_as_float(0x7FC00000u) : acc[t];
+    }
+}
+
+// The arguments, the walk and the slab rule of k_leaf_tiles; the value stored is the sum itself (normalized_distance clamps it).
+__global__ __launch_bounds__(256) AH_NO_PACKED_F32 void k_leaf_tiles_l1(DataView dv, const uint32_t *__restrict__ nns,
+                                                                        const Visit *__restrict__ sorted,
+                                                                        const TileUnit *__restrict__ units, const uint32_t *__restrict__ n_units_p,
+                                                                        const uint8_t *__restrict__ qvecs, uint64_t qstride,
+                                                                        const float *__restrict__ qhdrs, float *__restrict__ dist, uint32_t stride,
+                                                                        uint32_t *err) {
+    extern __shared__ uint4 s_l1_ring4[];
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // (uniform to the compiler as well)
+    uint8_t *ring = reinterpret_cast<uint8_t *>(s_l1_ring4) + wave * kL1RingBytesPerWave;
+    const uint32_t n_units = *n_units_p;
+    for (uint32_t u = blockIdx.x; u < n_units; u += gridDim.x) {
+        const TileUnit unit = units[u];
+        const Visit *vis = sorted + unit.first;
+        const uint32_t n_leaf = vis[0].n;
+        const uint32_t n_vis = unit.n_vis, slab = n_vis > 8 ? kTileSlab : 2 * kTileSlab;
+        const uint32_t row_begin = blockIdx.y * slab;
+        if (row_begin >= n_leaf) continue;
+        const uint32_t row_end = min(n_leaf, row_begin + slab);
+        const uint32_t *leaf_ids = nns + (uint64_t)vis[0].q * stride + vis[0].pos;
+        // the wave's 64 rows and its half of the visits
+        const uint32_t first = n_vis > 8 ? (wave >> 1) * 8u : 0u, row0 = row_begin + (n_vis > 8 ? wave & 1u : wave) * 64u;
+        if (row0 >= row_end || first >= n_vis) continue;
+        const uint32_t nv = min(n_vis - first, 8u);
+#define AH_L1(NV) leaf_tile_l1<NV>(dv, leaf_ids, row0, row_end, vis + first, nv, qvecs, qstride, dist, stride, err, ring)
+        if (nv > 4) AH_L1(8);
+        else if (nv > 2) AH_L1(4);
+        else if (nv == 2) AH_L1(2);
+        else AH_L1(1);
+#undef AH_L1
+    }
+}
+
 // ---- certified top-k screen of the re-rank (Cosine, DotProduct) ---------------------------------------------------
 // `Reader::nns_by_leaf` needs the `count` smallest (distance, id) of ~10 000 candidates (src/reader.rs:381-399): the VALUE of
 // a distance matters only for the ~1 % that can reach the top.  So the candidates are first evaluated on the binary16 shadow
@@ -4690,6 +4844,7 @@ static SearchKnobs search_knobs() {
     kn.mid_tiles = tun(TUN_SEARCH_MID_TILES) != 0, kn.mid_tiles_max_queries = tun(TUN_SEARCH_MID_TILES_MAX_QUERIES);
     kn.mid_items_cap = tun(TUN_SEARCH_MID_ITEMS_CAP);
     kn.mixed_tiles = tun(TUN_SEARCH_MIXED_TILES) != 0;
+    kn.tiles_manhattan = tun(TUN_SEARCH_TILES_MANHATTAN) != 0;
     return kn;
 }
 
@@ -5025,6 +5180,12 @@ static int launch_tiles(ChunkCtx &c) {
             walk_launch(tiles16_kernel<true>(ds->metric), tiles16_kernel<false>(ds->metric), ss, 0);
         break;
     default:
+        if (ds->metric == AH_MANHATTAN) {  // (AH_SEARCH_TILES_MANHATTAN: the f32 plan, one lane per (row, query) chain)
+            AH_TRY(lds_opt_in(reinterpret_cast<const void *>(k_leaf_tiles_l1), ds->device, 4 * kL1RingBytesPerWave));
+            hipLaunchKernelGGL(k_leaf_tiles_l1, grid, dim3(256), 4 * kL1RingBytesPerWave, s, dv, b.d_nns, b.d_sorted, b.d_units, d_n_units, b.d_qvecs,
+                               qstride, b.d_qhdrs, b.d_dist, nns_stride, b.d_err);
+            break;
+        }
         AH_TRY(with_tile_metric(ds->metric, [&](auto m) -> int {
             constexpr int M = decltype(m)::value;
             AH_TRY(lds_opt_in(reinterpret_cast<const void *>(k_leaf_tiles<M>), ds->device, 4 * kRingBytesPerWave));

@@ -44,6 +44,7 @@ struct SearchKnobs {
     bool mid_tiles;
     long long mid_tiles_max_queries, mid_items_cap;
     bool mixed_tiles;  // AH_SEARCH_MIXED_TILES: mixed sub-batches through the tiles, one unit per leaf whatever its visits' filters
+    bool tiles_manhattan;  // AH_SEARCH_TILES_MANHATTAN: uniform Manhattan sub-batches through the f32 tile plan (k_leaf_tiles_l1)
 };
 
 // One sub-batch as the plan sees it.
@@ -162,7 +163,11 @@ inline ChunkPlan plan_chunk(const ChunkShape &z, const SearchKnobs &kn) {
     // when AH_SEARCH_SCREEN_DIFF asks for it and the index has not switched it off — never with an int8 stage
     const bool screen_fit = tiles_fit && kn.screen && z.screen_ready;
     const bool diff_screened = screen_fit && (z.metric == AH_EUCLIDEAN || z.metric == AH_MANHATTAN) && kn.screen_diff && !z.search_diff_off;
-    // (Manhattan's reference distance is a sequential sum: no f32 tile — it takes the tiles only behind the screen)
+    // (Manhattan's reference distance is a sequential sum, which the octet tiles of k_leaf_tiles cannot give: it takes the tiles
+    // behind the difference screen, or — AH_SEARCH_TILES_MANHATTAN, uniform sub-batches the screen does not serve — the plan of
+    // a Euclidean f32 sub-batch field for field, with k_leaf_tiles_l1 as the kernel launch_tiles starts for TileLaunch::F32.
+    // Mixed sub-batches and the mid tiles have no Manhattan kind: those gates name Euclidean and stay as they are)
+    const bool l1_tiles = kn.tiles_manhattan && z.metric == AH_MANHATTAN && !diff_screened && !z.mixed;
     // (the 1-bit distances are exact integers of a popcount: their tiles need no screen, so screened, screened8, fuse_prepare
     // and fused_flag stay off and no binary16 or int8 copy is made or read)
     p.tiles_bq = tiles_fit && bq_wanted && !z.mixed;
@@ -170,7 +175,8 @@ inline ChunkPlan plan_chunk(const ChunkShape &z, const SearchKnobs &kn) {
     // (a mixed sub-batch: the row formats k_leaf_tiles_mixed serves — a binary16 screen, or Euclidean's f32 rows.  Unscreened
     // Cosine / DotProduct, Manhattan without the difference screen and the 1-bit metrics keep the sorted path)
     p.tiles = tiles_fit && (z.mixed ? p.screened || z.metric == AH_EUCLIDEAN
-                                    : z.metric == AH_EUCLIDEAN || z.metric == AH_COSINE || z.metric == AH_DOT_PRODUCT || diff_screened || p.tiles_bq);
+                                    : z.metric == AH_EUCLIDEAN || z.metric == AH_COSINE || z.metric == AH_DOT_PRODUCT || diff_screened || p.tiles_bq ||
+                                      l1_tiles);
     p.mixed_tiles = p.tiles && z.mixed;
     p.visit_cap = (uint32_t)std::min<uint64_t>((uint64_t)nq * z.nns_stride, 2u << 20);
     p.n_leaf_sums = (z.n_nodes + kLeafScanItems - 1) / kLeafScanItems;

@@ -121,6 +121,8 @@ def one(rng, it):
     diff_tun = dict(AH_SEARCH_SCREEN_DIFF=1, AH_SCREEN_VERIFY=1) if metric in (O.EUCLIDEAN, O.MANHATTAN) else {}
     if metric >= O.BQ_EUCLIDEAN:  # (the 1-bit leaf tiles, off by default as well: every other 1-bit configuration runs with them)
         diff_tun = dict(AH_SEARCH_TILES_BQ=int(rng.integers(2)))
+    if metric == O.MANHATTAN and rng.integers(2):  # (Manhattan's exact leaf tiles, off by default: the screen has precedence, so instead of it)
+        diff_tun = dict(AH_SEARCH_TILES_MANHATTAN=1)
     with _tuning_s(**diff_tun):
         index = ds.create_index(forest)
         count, search_k = int(rng.choice([1, 10, 200, 2500])), int(rng.choice([0, 1, 100, 2**62]))
