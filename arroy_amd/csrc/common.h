@@ -189,6 +189,8 @@ inline int guarded(const char *what, F &&f) noexcept {
     X(SEARCH_MID_ITEMS_CAP, "AH_SEARCH_MID_ITEMS_CAP", 0) /* != 0: the item list of the mid tiles holds at most this many items (test aid: a list that does not fit sends the sub-batch the long way) */ \
     X(SEARCH_MIXED_TILES, "AH_SEARCH_MIXED_TILES", 0) /* 1: a mixed sub-batch of ah_search_batch_filters / _params (queries under different filters) whose rows are screened on binary16 or are Euclidean f32 takes the leaf tiles: one unit per leaf, its rows read once for all visits, every visit's own filter asked per (row, visit) pair (k_leaf_tiles_mixed, DESIGN.md 4 "Mixed sub-batches through the leaf tiles"); 0 (default): it takes the sorted path, no plan, launch, allocation or statistic changes */ \
     X(SEARCH_TILES_MANHATTAN, "AH_SEARCH_TILES_MANHATTAN", 0) /* 1: a uniform Manhattan sub-batch of ah_search_batch / _filters / _params that the difference screen does not serve takes the leaf tiles on its exact rows, planned as a Euclidean f32 sub-batch is (k_leaf_tiles_l1, DESIGN.md 4 "Manhattan leaf tiles": one lane per (row, query) chain, the reference's sequential sum); 0 (default): it takes the sorted path, no plan, launch, allocation or statistic changes */ \
+    X(SEARCH_FLAG_SLICED, "AH_SEARCH_FLAG_SLICED", 0) /* 1: a sub-batch of ah_search_batch / _filters / _params whose candidate lists are longer than one LDS hash set holds (24 576) on an id space past the LDS bitmap (1 277 952 ids) keeps the leaf tiles: its duplicates are flagged by k_flag_duplicates_sliced, several blocks per query, each with the set of one slice of the ids (DESIGN.md 4 "Sliced duplicate flags"); 0 (default): it takes the sorted path, no plan, launch, allocation or statistic changes */ \
+    X(SEARCH_FLAG_SLICE_CANDIDATES, "AH_SEARCH_FLAG_SLICE_CANDIDATES", 16384) /* ... candidates budgeted per slice: blocks per query = candidate stride / this, rounded up, at most 64 (a slice holds 24 576; one that gets more sends the sub-batch the long way, which a large value here forces: test aid) */ \
     X(REPLICATE_HOST_BOUNCE,"AH_REPLICATE_HOST_BOUNCE", 0) /* 1: ah_dataset_replicate copies through pinned host memory even where peer access works (test aid) */ \
     X(RERANK_TIMING, "AH_RERANK_TIMING", 0)     /* 1: ah_rerank_batch accounts its wall time by phase (ah_dataset_rerank_stats) */ \
     X(SEARCH_SCREEN, "AH_SEARCH_SCREEN", 1)     /* 0: the re-rank of ah_search_batch never screens its candidates (f32 rows for all) */ \

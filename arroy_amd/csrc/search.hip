@@ -2063,6 +2063,80 @@ __global__ __launch_bounds__(1024) void k_flag_duplicates_hash(uint32_t *__restr
     if (tid == 0) unique[q] = s_unique;
 }
 
+// The same for lists longer than one set holds (AH_SEARCH_FLAG_SLICED): grid (queries, n_slices), block (q, s) owns the
+// candidates of query q whose id falls into slice s and keeps the set above for them alone.  The slice is a function of the id,
+// so every occurrence of an id meets in one block and no duplicate crosses two.  It is the high word of fmix32(id) x n_slices,
+// a mixer that shares nothing with the slot hash (the top 15 bits of id x 2654435761): a range of THOSE bits as the slice would
+// put all members of a slice into 1 / n_slices of its table.  Every block streams the whole list of its query (the n_slices
+// blocks read the same 4 n bytes, from L2), twice: pass 1 counts its members — more than kHashMaxCandidates raise bit 3 of
+// *err, block-uniformly, and the block leaves BEFORE it probes, since a CAS loop over a full table never ends (the budget per
+// slice is a mean; the sub-batch is then redone on the sorted path) — and pass 2 inserts them.  unique[q], zeroed by the
+// caller, is the sum over the query's slices.  One query's long list is flagged on n_slices compute units instead of one.
+// While a block reads the list the other blocks of its query flag THEIR members in it: an entry reads as its id or as
+// 0xFFFFFFFF, which belongs to no slice (it is no item's id on this path), so a block only ever sees its members become fewer.
+__device__ __forceinline__ uint32_t flag_slice_of(uint32_t id, uint32_t n_slices) {
+    uint32_t h = id;  // (MurmurHash3's 32-bit finalizer)
+    h ^= h >> 16, h *= 0x85EBCA6Bu, h ^= h >> 13, h *= 0xC2B2AE35u, h ^= h >> 16;
+    return __umulhi(h, n_slices);  // [0, n_slices)
+}
+__global__ __launch_bounds__(1024) void k_flag_duplicates_sliced(uint32_t *__restrict__ nns, uint32_t stride,
+                                                                 const uint32_t *__restrict__ counts, uint32_t n_slices,
+                                                                 uint32_t *__restrict__ unique, uint32_t *__restrict__ err) {
+    extern __shared__ uint32_t s_set[];  // kHashSlots
+    __shared__ uint32_t s_members, s_unique;
+    const uint32_t q = blockIdx.x, slice = blockIdx.y, tid = threadIdx.x;
+    const uint32_t n = min(counts[q], stride);
+    uint32_t *ids = nns + (uint64_t)q * stride;
+    for (uint32_t t = tid; t < kHashSlots / 4; t += 1024) reinterpret_cast<uint4 *>(s_set)[t] = make_uint4(~0u, ~0u, ~0u, ~0u);
+    if (tid == 0) s_members = 0, s_unique = 0;
+    __syncthreads();
+    // pass 1: the members of this slice, duplicates counted (four loads a lane in flight, as k_flag_duplicates)
+    uint32_t members = 0;
+    for (uint32_t t0 = tid; t0 < n; t0 += 4 * 1024) {
+        uint32_t id[4];
+#pragma unroll
+        for (int u = 0; u < 4; u++) id[u] = t0 + u * 1024 < n ? ids[t0 + u * 1024] : 0xFFFFFFFFu;
+#pragma unroll
+        for (int u = 0; u < 4; u++) members += id[u] != 0xFFFFFFFFu && flag_slice_of(id[u], n_slices) == slice ? 1u : 0u;
+    }
+    for (uint32_t d = 32; d > 0; d >>= 1) members += __shfl_xor(members, d, 64);
+    if ((tid & 63u) == 0 && members) atomicAdd(&s_members, members);
+    __syncthreads();
+    if (s_members > kHashMaxCandidates) {  // block-uniform: s_members is final behind the barrier, nobody has probed yet
+        if (tid == 0) atomicOr(err, 8u);
+        return;
+    }
+    if (s_members == 0) return;
+    // pass 2: at most kHashMaxCandidates insertions into kHashSlots slots, so every probe sequence meets its id or an empty slot
+    uint32_t mine = 0;
+    for (uint32_t t0 = tid; t0 < n; t0 += 4 * 1024) {
+        uint32_t id[4];
+#pragma unroll
+        for (int u = 0; u < 4; u++) id[u] = t0 + u * 1024 < n ? ids[t0 + u * 1024] : 0xFFFFFFFFu;
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            if (id[u] == 0xFFFFFFFFu || flag_slice_of(id[u], n_slices) != slice) continue;
+            uint32_t h = (id[u] * 2654435761u) >> 17;
+            for (;;) {
+                const uint32_t old = atomicCAS(&s_set[h], 0xFFFFFFFFu, id[u]);
+                if (old == 0xFFFFFFFFu) {
+                    mine++;
+                    break;
+                }
+                if (old == id[u]) {
+                    ids[t0 + u * 1024] = 0xFFFFFFFFu;
+                    break;
+                }
+                h = (h + 1) & (kHashSlots - 1);
+            }
+        }
+    }
+    for (uint32_t d = 32; d > 0; d >>= 1) mine += __shfl_xor(mine, d, 64);
+    if ((tid & 63u) == 0 && mine) atomicAdd(&s_unique, mine);
+    __syncthreads();
+    if (tid == 0 && s_unique) atomicAdd(&unique[q], s_unique);
+}
+
 template <int METRIC, int R, int Q, int QO>
 __device__ __forceinline__ void leaf_tile(const DataView &dv, const uint32_t *__restrict__ leaf_ids, uint32_t row_begin,
                                           uint32_t n_rows, const Visit *__restrict__ vis, uint32_t n_vis,
@@ -4845,6 +4919,7 @@ static SearchKnobs search_knobs() {
     kn.mid_items_cap = tun(TUN_SEARCH_MID_ITEMS_CAP);
     kn.mixed_tiles = tun(TUN_SEARCH_MIXED_TILES) != 0;
     kn.tiles_manhattan = tun(TUN_SEARCH_TILES_MANHATTAN) != 0;
+    kn.flag_sliced = tun(TUN_SEARCH_FLAG_SLICED) != 0, kn.flag_slice_candidates = tun(TUN_SEARCH_FLAG_SLICE_CANDIDATES);
     return kn;
 }
 
@@ -5262,10 +5337,16 @@ static int launch_select_and_wait(ChunkCtx &c, hipError_t &launch_err) {
         AH_TRY(lds_opt_in(reinterpret_cast<const void *>(k_flag_duplicates), ds->device, sh));
         hipLaunchKernelGGL(k_flag_duplicates, dim3((unsigned)nq), dim3(1024), sh, s, b.d_nns, nns_stride, b.d_counts, bitmap_words,
                            max_id + 1, b.d_unique, b.d_err);
-    } else {
+    } else if (plan.flagger == Flagger::Hash) {
         AH_TRY(lds_opt_in(reinterpret_cast<const void *>(k_flag_duplicates_hash), ds->device, kHashSlots * 4));
         hipLaunchKernelGGL(k_flag_duplicates_hash, dim3((unsigned)nq), dim3(1024), kHashSlots * 4, s, b.d_nns, nns_stride, b.d_counts,
                            b.d_unique, b.d_err);
+    } else {  // (AH_SEARCH_FLAG_SLICED: flag_slices blocks per query, each adds its slice's share to unique[q])
+        AH_REQUIRE(plan.flag_slices >= 1 && plan.flag_slices <= kFlagMaxSlices, AH_ERR_DEVICE, "internal: %u slices of duplicate flags", plan.flag_slices);
+        AH_TRY(lds_opt_in(reinterpret_cast<const void *>(k_flag_duplicates_sliced), ds->device, kHashSlots * 4));
+        AH_HIP(hipMemsetAsync(b.d_unique, 0, nq * 4, s));
+        hipLaunchKernelGGL(k_flag_duplicates_sliced, dim3((unsigned)nq, plan.flag_slices), dim3(1024), kHashSlots * 4, s, b.d_nns, nns_stride,
+                           b.d_counts, plan.flag_slices, b.d_unique, b.d_err);
     }
     uint32_t *sel_trace = c.multi_trace() ? &c.multi_trace()->sel_trace[0] : nullptr;
     if (plan.screened) AH_TRY(launch_screen_verify(ds, ss, b.d_nns, b.d_dist, nns_stride, b.d_counts, nullptr, (uint32_t)nq, b.d_qvecs, qstride, b.d_qhdrs, s));

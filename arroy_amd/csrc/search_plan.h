@@ -22,7 +22,8 @@ constexpr uint32_t kMultiMaxBlocks = 16, kMultiMaxQueries = 32, kMultiCap = 1024
 constexpr uint32_t kBitmapMaxWords = 39 * 1024;  // 156 KiB of the 160 KiB of LDS: 1 277 952 ids
 constexpr uint32_t kLeafScanItems = 2048;        // 256 threads x 8
 constexpr uint32_t kSmallVisits = 2048;          // visits one call of k_units_small holds
-constexpr uint32_t kHashMaxCandidates = 24576;   // candidates of a query k_flag_duplicates_hash holds
+constexpr uint32_t kHashMaxCandidates = 24576;   // candidates of a query k_flag_duplicates_hash holds (of a slice: _sliced)
+constexpr uint32_t kFlagMaxSlices = 64;          // blocks per query of k_flag_duplicates_sliced: strides up to 1 M at 16 384 a slice
 constexpr uint32_t kSelectCap = 1024;            // keys the selections behind the tiles hold
 constexpr uint32_t kStatusWords = 17;            // the per-chunk status block (SS_WORDS; padded to 256 bytes in both layouts)
 constexpr uint32_t kMidMinQueries = 9;           // the first call past the small tiles' default (AH_SEARCH_MID_TILES)
@@ -45,6 +46,10 @@ struct SearchKnobs {
     long long mid_tiles_max_queries, mid_items_cap;
     bool mixed_tiles;  // AH_SEARCH_MIXED_TILES: mixed sub-batches through the tiles, one unit per leaf whatever its visits' filters
     bool tiles_manhattan;  // AH_SEARCH_TILES_MANHATTAN: uniform Manhattan sub-batches through the f32 tile plan (k_leaf_tiles_l1)
+    // AH_SEARCH_FLAG_SLICED: candidate lists past kHashMaxCandidates on an id space past the bitmap keep the tiles, their
+    // duplicates flagged by k_flag_duplicates_sliced; flag_slice_candidates: the candidates budgeted per slice
+    bool flag_sliced;
+    long long flag_slice_candidates;
 };
 
 // One sub-batch as the plan sees it.
@@ -82,7 +87,7 @@ struct ChunkShape {
 enum class Descent : uint8_t { Octet, WaveBig, WaveSmallBig, Block, Multi };  // of the tile pass; k_descend<false> follows the waves
 enum class UnitBuilder : uint8_t { None, Descent, UnitsSmall, LeafScan };     // None: no tile pass
 enum class TileLaunch : uint8_t { None, Tiles8And16, Flat, ItemList, Small2D, Big2D, F32, Mid, Mixed };  // (recorded plans hold the number)
-enum class Flagger : uint8_t { None, Fused, Bitmap, Hash };                   // nns.dedup() of the tile pass
+enum class Flagger : uint8_t { None, Fused, Bitmap, Hash, HashSliced };       // nns.dedup() of the tile pass
 enum class SortedDedup : uint8_t { Bitmap, SortLds, SortGlobal };             // ... of the sorted path
 
 struct ChunkPlan {
@@ -116,6 +121,9 @@ struct ChunkPlan {
     // a mixed sub-batch on the tile path (AH_SEARCH_MIXED_TILES): the tile launch is k_leaf_tiles_mixed over slabs of
     // kTileSmallSlab positions of the FULL leaf, and nothing that reads "the kept ids of a unit's first visit" is on
     bool mixed_tiles = false;
+    // != 0: neither the bitmap nor one hash set holds the candidates of a query, k_flag_duplicates_sliced flags them with this
+    // many blocks per query (AH_SEARCH_FLAG_SLICED)
+    uint32_t flag_slices = 0;
 };
 
 // The descent runs one wave (or block) per query: AH_SEARCH_WAVE, a query leaf of at most 32 KiB (it is kept in LDS), and
@@ -143,6 +151,14 @@ inline ChunkPlan plan_chunk(const ChunkShape &z, const SearchKnobs &kn) {
     p.bitmap_fits = kn.bitmap && p.bitmap_words <= kBitmapMaxWords;
     // nns.dedup() of the tiles: the LDS bitmap, or a hash set of the candidates when the id space is too big for it
     p.hash_fits = z.nns_stride <= kHashMaxCandidates && z.max_id != 0xFFFFFFFFu;
+    // (AH_SEARCH_FLAG_SLICED) ... or, for longer lists, one such set per slice of the id space: the stride over the budget of a
+    // slice, rounded up.  Past kFlagMaxSlices the sub-batch keeps the sorted path.  A slice that ends up with more than
+    // kHashMaxCandidates members (the budget is a mean) gives the sub-batch up on the device, bit 3 of the status word
+    if (kn.flag_sliced && !p.bitmap_fits && !p.hash_fits && z.max_id != 0xFFFFFFFFu) {
+        const uint64_t per_slice = (uint64_t)std::max<long long>(1, kn.flag_slice_candidates);
+        const uint64_t slices = ((uint64_t)z.nns_stride + per_slice - 1) / per_slice;
+        p.flag_slices = slices <= kFlagMaxSlices ? (uint32_t)slices : 0u;
+    }
     // (a mixed sub-batch only under AH_SEARCH_MIXED_TILES: every other tile kernel reads the kept ids of a leaf from ONE of its
     // visits for all of them, k_leaf_tiles; k_leaf_tiles_mixed reads the full leaf and asks every visit's own filter.  Without
     // the tiles no descent is a last pass, so k_descend_multi and the units of a single query are out as well)
@@ -156,7 +172,8 @@ inline ChunkPlan plan_chunk(const ChunkShape &z, const SearchKnobs &kn) {
     const bool width_fits = bq_wanted ? (z.dims + 63u) / 64u <= kBqTileMaxWords : z.dims >= 32;
     // (the slabs of kTileSmallSlab rows the largest leaf has: grid.y of the small and the mixed tiles)
     const unsigned small_slabs = std::max(1u, (z.max_desc + kTileSmallSlab - 1) / kTileSmallSlab);
-    const bool tiles_fit = (!z.mixed || (kn.mixed_tiles && small_slabs <= 65535u)) && kn.tiles && (p.bitmap_fits || p.hash_fits) && !p.big_k &&
+    const bool tiles_fit = (!z.mixed || (kn.mixed_tiles && small_slabs <= 65535u)) && kn.tiles &&
+                           (p.bitmap_fits || p.hash_fits || p.flag_slices != 0) && !p.big_k &&
                            (k <= kSelectCap || z.nns_stride <= kSelectCap) && width_fits && z.max_desc <= 65535u * kTileSlab;
     // certified top-k screen of the tile re-rank: the binary16 shadow of the rows must exist (ah_index_create makes it).
     // Cosine / DotProduct by the dot product of the copies; Euclidean / Manhattan by their difference (k_leaf_tiles_diff16),
@@ -297,7 +314,7 @@ inline ChunkPlan plan_chunk(const ChunkShape &z, const SearchKnobs &kn) {
     p.fused_lds = p.sel_lds + (size_t)p.bitmap_words * 4;
     p.fused_flag = p.small_units && p.screened && p.bitmap_fits && z.nns_stride <= 16384 && p.fused_lds + (26u << 10) <= (160u << 10) &&
                    kn.fused_flag;
-    p.flagger = p.fused_flag ? Flagger::Fused : p.bitmap_fits ? Flagger::Bitmap : Flagger::Hash;
+    p.flagger = p.fused_flag ? Flagger::Fused : p.bitmap_fits ? Flagger::Bitmap : p.hash_fits ? Flagger::Hash : Flagger::HashSliced;
     return p;
 }
 
